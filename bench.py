@@ -25,7 +25,13 @@ The line carries (keys fixed, tests/test_bench_line.py):
                   coherent-schedule tuner settled first, as many steps as the headline
 Everything else (per-GPU rows, tuner state, counters in full, the legs of `--detail`) goes to the sidecar file named by `detail_file`.
 
-`--detail` adds the side legs of bench_detail.py (configs 1 / 2 / 5, reference OpenCL kernels on the same GPU, HBM-regime scenes, rotated
+A plain run does only what the headline needs: scene and build, ray batches, warm-up, the K timed steps, the line (`value`, `ms_per_step`,
+`kernel_mrays` without `shadow`, `schedule`; `roofline`, `cpu_baseline`, `parity`, `reference_blob`, `config4_strong` empty, no sidecar file).
+`--full` adds everything after `value` in the list above: the shadow batch, config 4, the reference-blob step, the parity check (a mismatch
+exits non-zero), the roofline with its counter children, the CPU baseline, configs 2 / 5 and the sidecar file.  `--dump-outputs DIR` writes
+the hit records the last timed step left (a fixed seeded sample, bench.dump_outputs) so that two builds can be compared output for output.
+
+`--detail` (implies `--full`) adds the side legs of bench_detail.py (configs 1 / 2 / 5, reference OpenCL kernels on the same GPU, HBM-regime scenes, rotated
 scene, other layouts, host rays, wavefront frames, device refit / build); `--ceilings` re-measures the box's ceilings (streaming read / copy
 bandwidth, VALU issue rate of the node-test mix) instead of reading profiles/ceilings.json.
 
@@ -70,6 +76,22 @@ class Legs:
         self.t = now
 
 
+DUMP_SAMPLE = 1 << 20                  # rays per batch written by --dump-outputs: 2 batches x (3 x 4 + 8) bytes x 2^20 = 40 MiB
+DUMP_SEED = 2024
+
+
+def dump_outputs(out_dir, kind, records):
+    """--dump-outputs: the hit records (t, u, v, prim) of one batch as the last timed step left them, for a fixed seeded sample of the rays
+    (the same rays for the same --side), as <out_dir>/<kind>_<field>.npy; t / u / v float32, prim float64 (exact for every uint32)."""
+    os.makedirs(out_dir, exist_ok=True)
+    n = records.shape[0]
+    idx = np.sort(np.random.default_rng(DUMP_SEED).choice(n, DUMP_SAMPLE, replace=False)) if n > DUMP_SAMPLE else np.arange(n)
+    sample = records[idx]
+    for field in ("t", "u", "v"):
+        np.save(os.path.join(out_dir, f"{kind}_{field}.npy"), np.ascontiguousarray(sample[field], dtype=np.float32))
+    np.save(os.path.join(out_dir, f"{kind}_prim.npy"), sample["prim"].astype(np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -78,9 +100,13 @@ def main():
     ap.add_argument("--scene", default="bistro")
     ap.add_argument("--side", type=int, default=4096, help="primary rays per GPU = side^2")
     ap.add_argument("--layout", type=int, default=10, help="5 BVH_GPU, 8 BVH4_GPU, 10 BVH8_CWBVH (BVHBase::BVHType)")
-    ap.add_argument("--detail", action="store_true", help="also run the side legs of bench_detail.py (sidecar file only; the line stays compact)")
-    ap.add_argument("--detail-out", default="", help="sidecar path (default: gpurun_out/bench_detail.json if gpurun_out/ exists, else ./bench_detail.json)")
-    ap.add_argument("--ceilings", action="store_true", help="re-measure the box's ceilings (read / copy bandwidth, VALU issue rate) instead of reading profiles/ceilings.json")
+    ap.add_argument("--full", action="store_true", help="also everything beyond the headline: shadow batch, config 4 strong batch, reference-blob step, parity, "
+                    "roofline with counter children, CPU baseline, configs 2 / 5, sidecar file (without it: set-up, warm-up, timed steps, line)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="after the timed steps write the hit records (t, u, v, prim) the last step left, of a fixed "
+                    "seeded sample of 2^20 rays per batch, as DIR/<batch>_<field>.npy (float32; prim as float64)")
+    ap.add_argument("--detail", action="store_true", help="also run the side legs of bench_detail.py (sidecar file only; the line stays compact; implies --full)")
+    ap.add_argument("--detail-out", default="", help="sidecar path of --full (default: ./bench_detail.json)")
+    ap.add_argument("--ceilings", action="store_true", help="re-measure the GPU's ceilings (read / copy bandwidth, VALU issue rate) instead of reading profiles/ceilings.json (implies --full)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--variant", type=int, default=0)
     ap.add_argument("--no-pmc", action="store_true", help="skip the rocprofv3 --pmc child runs (roofline.traffic is then null)")
@@ -98,6 +124,10 @@ def main():
     for old in ("--no-configs", "--no-hbm-regime", "--no-rotated", "--no-other-layouts", "--no-host-rays"):
         ap.add_argument(old, action="store_true", help=argparse.SUPPRESS)
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    if a.detail or a.ceilings or a.one_process_devices:     # legs and figures of the full run
+        a.full = True
     legs = Legs()
 
     rank = int(os.environ.get("RANK", "0"))
@@ -163,7 +193,7 @@ def main():
     build_threads = max(1, usable_cores() // world) if world > 1 else 0
     replication = None
     own_cache = None
-    if not child and not use_dist and not a.blob_cache and a.layout == tb.LAYOUT_CWBVH and not a.device_build and not a.no_pmc:
+    if a.full and not child and not use_dist and not a.blob_cache and a.layout == tb.LAYOUT_CWBVH and not a.device_build and not a.no_pmc:
         # the rocprofv3 --pmc children of this run load the blobs this process builds (the blob cache of SURVEY par. 8(f4)) instead of building again
         import tempfile
         own_cache = tempfile.mkdtemp(prefix="tbvh_bench_", dir="/tmp")
@@ -282,24 +312,25 @@ def main():
             ctx_.synchronize()
         return int(scene_.coherent_schedule(anyhit)[0])
 
-    # the any-hit pass (config "16 M IsOccluded shadow rays") is not part of the metric's step (primary + diffuse): HIP events only
-    for i in range(2):
-        sc.occluded_device(d_shad, n, d_occ)
-    ctx.synchronize()
-    settle(sc, ctx, d_shad, anyhit=True)
-    for i in range(a.steps):
-        sc.occluded_device(d_shad, n, d_occ)
-    ctx.synchronize()
-    kern_ms["shadow"] = ctx.time_history(min(a.steps, 128))
-    # strided sample of the shadow batch and its occlusion flags, for the parity check below (the buffers are freed before it)
     ns_par = 65536
     par_stride = max(n // ns_par, 1)
     shadow_sample = shadow_occ = None
-    if rank == 0:
-        full = np.zeros(n, dtype=tb.RAY_DTYPE); ctx.from_device(full, d_shad)
-        shadow_sample = full[::par_stride][:ns_par].copy(); del full
-        occ_all = np.zeros(n, np.uint8); ctx.from_device(occ_all, d_occ)
-        shadow_occ = occ_all[::par_stride][:ns_par].copy(); del occ_all
+    if a.full:
+        # the any-hit pass (config "16 M IsOccluded shadow rays") is not part of the metric's step (primary + diffuse): HIP events only
+        for i in range(2):
+            sc.occluded_device(d_shad, n, d_occ)
+        ctx.synchronize()
+        settle(sc, ctx, d_shad, anyhit=True)
+        for i in range(a.steps):
+            sc.occluded_device(d_shad, n, d_occ)
+        ctx.synchronize()
+        kern_ms["shadow"] = ctx.time_history(min(a.steps, 128))
+        # strided sample of the shadow batch and its occlusion flags, for the parity check below (the buffers are freed before it)
+        if rank == 0:
+            full = np.zeros(n, dtype=tb.RAY_DTYPE); ctx.from_device(full, d_shad)
+            shadow_sample = full[::par_stride][:ns_par].copy(); del full
+            occ_all = np.zeros(n, np.uint8); ctx.from_device(occ_all, d_occ)
+            shadow_occ = occ_all[::par_stride][:ns_par].copy(); del occ_all
     for i in range(max(a.warmup, 1)):
         step()
         if i % 2:
@@ -317,19 +348,23 @@ def main():
     hist = ctx.time_history(2 * min(a.steps, 128))      # (primary, diffuse) x steps, oldest first
     kern_ms["primary"], kern_ms["diffuse"] = hist[0::2], hist[1::2]
     # the records the TIMED launches left in HBM, sampled now — before anything else traces into these buffers — for the parity checks below
+    # and for --dump-outputs
     timed_got = {}
-    if rank == 0:
+    if rank == 0 and (a.full or a.dump_outputs):
         for kind, dptr in (("diffuse", d_diff), ("primary", d_prim)):
             full = np.zeros(n, dtype=tb.RAY_DTYPE)
             ctx.from_device(full, dptr)
-            timed_got[kind] = full[::par_stride][:ns_par].copy()
+            if a.full:
+                timed_got[kind] = full[::par_stride][:ns_par].copy()
+            if a.dump_outputs:
+                dump_outputs(a.dump_outputs, kind, full)
             del full
     if use_dist:
         import torch
         t = torch.tensor([elapsed], dtype=torch.float64, device="cuda")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
-    legs.mark("shadow_warmup_timed_steps")
+    legs.mark("shadow_warmup_timed_steps" if a.full else "warmup_timed_steps")
 
     # ---- config 4 as BASELINE.json words it: ONE 64 M-ray diffuse batch, sharded over the ranks (strong scaling) ------
     strong = None
@@ -337,7 +372,7 @@ def main():
     n_gpus = len(inproc_devices) if inproc_devices else world
     for p_ in (d_tmp, d_shad, d_occ):
         ctx.free(p_)
-    if not a.no_strong and not inproc_devices:   # (a one-process N-GPU run shards the batch over its contexts instead: strong_one_process below)
+    if a.full and not a.no_strong and not inproc_devices:   # (a one-process N-GPU run shards the batch over its contexts instead: strong_one_process below)
         try:
             from tinybvh_amd.sharding import shard_range
             side4 = 8192 if a.side >= 4096 else 2 * a.side
@@ -401,17 +436,18 @@ def main():
     # visible device when this is a single-process run that sees more than one
     one_proc = None
     kdev = a.one_process_devices if a.one_process_devices else (len(inproc_devices) if inproc_devices else 0)
-    if rank == 0 and world == 1 and kdev >= 2 and not a.no_strong:
+    if a.full and rank == 0 and world == 1 and kdev >= 2 and not a.no_strong:
         try:
             import bench_detail
             one_proc = bench_detail.strong_one_process(tb, R, sc, verts, eye, view, 8192 if a.side >= 4096 else 2 * a.side, kdev, log, devices=inproc_devices)
         except Exception as e:
             log(f"[bench] one-process multi-device batch failed: {e!r}")
-    legs.mark("config4_strong")
+    if a.full:
+        legs.mark("config4_strong")
 
     # ---- the drop-in case (rank 0, outside the timed region): the same step on blobs of the real tinybvh BuildHQ ------------------------
     ref_blob = None
-    if rank == 0 and not a.no_reference_blob and a.layout == tb.LAYOUT_CWBVH:
+    if a.full and rank == 0 and not a.no_reference_blob and a.layout == tb.LAYOUT_CWBVH:
         try:
             ref_blob = reference_blob_step(tb, ctx, verts, d_prim, d_diff, n, timed_got, par_stride, ns_par, a.steps)
         except Exception as e:
@@ -425,7 +461,7 @@ def main():
         ms_per_step = elapsed / a.steps * 1e3
         rays_per_step = 2 * n * n_gpus  # primary + diffuse (the metric); shadow reported beside it
         value = rays_per_step / (elapsed / a.steps) / 1e6
-        mean = {k: float(np.mean(v)) for k, v in kern_ms.items()}
+        mean = {k: float(np.mean(v)) for k, v in kern_ms.items() if len(v)}
         detail = {k + "_mrays": n / (mean[k] * 1e-3) / 1e6 for k in mean}
         detail["kernel_ms"] = mean
         detail["primary_plus_diffuse_kernel_mrays"] = 2 * n / ((mean["primary"] + mean["diffuse"]) * 1e-3) / 1e6
@@ -455,84 +491,84 @@ def main():
         # layout (which also counts node visits S and triangle tests T per ray for the roofline lines); the shadow batch's occlusion flags
         # against BVH::IsOccluded restated.  A real mismatch makes this process exit non-zero after the JSON line.
         S_T = {}
-        try:
-            if a.no_parity:
-                raise RuntimeError("--no-parity")
-            sys.path.insert(0, os.path.join(ROOT, "tests"))
-            from oracle_lib import Oracle, compare_hits
-            orc = Oracle()
-            h = sc.host
-            parity = {"n": ns_par, "rule": "exact prim (library tie rule: smaller prim at equal t), t / u / v bit-identical", "hitmiss": 0, "prim_real": 0, "t_bad": 0, "uv_bad": 0,
-                      "tie": 0, "onsurf": 0, "not_bit_identical": 0, "shadow_flags_differ": 0}
-            for kind in ("diffuse", "primary"):
-                got = timed_got[kind]
-                sample = got.copy()
-                sample["t"] = 1e30; sample["u"] = 0; sample["v"] = 0; sample["prim"] = 0
-                if a.layout == tb.LAYOUT_CWBVH:
-                    mirror, cnt = orc.cwbvh_intersect(h.blob(0, np.uint32, 4), h.blob(1, np.uint32, 4), sample, counts=True)
-                elif a.layout == tb.LAYOUT_BVH4_GPU:
-                    mirror, cnt = orc.bvh4_intersect(h.blob(0, np.uint32, 4), sample, counts=True)
-                else:
-                    mirror, cnt = orc.bvhgpu_intersect(h.blob(0, np.uint32, 16), h.blob(1, np.uint32, 1), verts, sample, counts=True)
-                S_T[kind] = (float(cnt[0]) / sample.shape[0], float(cnt[1]) / sample.shape[0])
-                want = orc.bvh2_intersect(h.bvh2_nodes(), h.bvh2_prim_idx(), verts, sample)
-                for ref_records in (want, mirror):
-                    cmp_ = compare_hits(got, ref_records)
-                    for k in ("hitmiss", "prim_real", "t_bad", "uv_bad", "tie", "onsurf"):
-                        parity[k] += cmp_[k]
-                    parity["not_bit_identical"] += cmp_["same_prim"] - cmp_["bit_identical"]
-                parity[kind + "_hits"] = int((got["t"] < 1e30).sum())
-            if shadow_sample is not None:
-                want_occ = orc.bvh2_occluded(h.bvh2_nodes(), h.bvh2_prim_idx(), verts, shadow_sample)
-                parity["shadow_flags_differ"] = int((want_occ != shadow_occ).sum())
-                parity["shadow_occluded"] = int(want_occ.sum())
-            # ... and against the REAL reference under ITS OWN tie rule (oracle/_ref: BVH::Intersect of tiny_bvh.h on its own BuildHQ tree), the
-            # library's two deliberate deviations counted, not tolerated away (tests/oracle_lib.py: compare_with_real_reference)
-            if ref_blob and ref_blob.get("timed_launches_vs_real_reference"):
-                parity["vs_real_reference"] = ref_blob.pop("timed_launches_vs_real_reference")
-            parity["ok"] = (parity["hitmiss"] == 0 and parity["prim_real"] == 0 and parity["t_bad"] == 0 and parity["uv_bad"] == 0 and parity["tie"] == 0 and
-                            parity["not_bit_identical"] == 0 and parity["onsurf"] <= 16 and parity["shadow_flags_differ"] <= 2)
-            vr = parity.get("vs_real_reference")
-            if vr and "error" not in vr:
-                parity["ok"] = parity["ok"] and all(vr[k]["hitmiss"] == 0 and vr[k]["prim_real"] == 0 and vr[k]["t_bad"] == 0 and vr[k]["uv_differs"] == 0 and
-                                                    vr[k]["farther_by_ulps"] == 0 for k in ("primary", "diffuse"))
-        except Exception as e:
-            log(f"[bench] parity sample failed: {e!r}")
-            parity["error"] = repr(e)
-        detail["parity_sample"] = parity
-        legs.mark("parity")
-
-        # ---- roofline (contract: `achieved` = ALGORITHMIC bytes per launch / mean launch time; `traffic` = PMC bytes per launch) ------------------
-        roof = None
-        try:
-            ceil = ceilings(ctx, a.ceilings, log)
-            # (the children run the schedule this process's tuner settled on for coherent batches, pinned: a child is too short to decide for itself)
-            a.coh_pin = {1: "0", 2: "2", 3: "3"}.get(sc.coherent_schedule(False)[0] if a.layout == tb.LAYOUT_CWBVH else 0)
-            passes = ("FETCH_SIZE", "WRITE_SIZE", "SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_THREAD_CYCLES_VALU SQ_BUSY_CYCLES") + \
-                     (("TCC_EA0_RDREQ_LEVEL_sum TCC_EA0_RDREQ_sum",) if a.detail else ())
-            pm = live_counters(a, log, passes=passes) if (world == 1 and not a.no_pmc) else None
-            roof = roofline_lines(a.layout, n, mean, S_T, pm, ceil)
-        except Exception as e:  # the checker is optional for the number itself
-            log(f"[bench] roofline failed: {e!r}")
-        legs.mark("roofline_pmc_children")
-
-        cpu = None
-        if not a.no_cpu_baseline:
+        roof = cpu = None
+        if a.full:
             try:
-                cpu = cpu_baseline(tb, ctx, verts, d_prim, d_diff, n, more=a.detail)
+                if a.no_parity:
+                    raise RuntimeError("--no-parity")
+                sys.path.insert(0, os.path.join(ROOT, "tests"))
+                from oracle_lib import Oracle, compare_hits
+                orc = Oracle()
+                h = sc.host
+                parity = {"n": ns_par, "rule": "exact prim (library tie rule: smaller prim at equal t), t / u / v bit-identical", "hitmiss": 0, "prim_real": 0, "t_bad": 0, "uv_bad": 0,
+                          "tie": 0, "onsurf": 0, "not_bit_identical": 0, "shadow_flags_differ": 0}
+                for kind in ("diffuse", "primary"):
+                    got = timed_got[kind]
+                    sample = got.copy()
+                    sample["t"] = 1e30; sample["u"] = 0; sample["v"] = 0; sample["prim"] = 0
+                    if a.layout == tb.LAYOUT_CWBVH:
+                        mirror, cnt = orc.cwbvh_intersect(h.blob(0, np.uint32, 4), h.blob(1, np.uint32, 4), sample, counts=True)
+                    elif a.layout == tb.LAYOUT_BVH4_GPU:
+                        mirror, cnt = orc.bvh4_intersect(h.blob(0, np.uint32, 4), sample, counts=True)
+                    else:
+                        mirror, cnt = orc.bvhgpu_intersect(h.blob(0, np.uint32, 16), h.blob(1, np.uint32, 1), verts, sample, counts=True)
+                    S_T[kind] = (float(cnt[0]) / sample.shape[0], float(cnt[1]) / sample.shape[0])
+                    want = orc.bvh2_intersect(h.bvh2_nodes(), h.bvh2_prim_idx(), verts, sample)
+                    for ref_records in (want, mirror):
+                        cmp_ = compare_hits(got, ref_records)
+                        for k in ("hitmiss", "prim_real", "t_bad", "uv_bad", "tie", "onsurf"):
+                            parity[k] += cmp_[k]
+                        parity["not_bit_identical"] += cmp_["same_prim"] - cmp_["bit_identical"]
+                    parity[kind + "_hits"] = int((got["t"] < 1e30).sum())
+                if shadow_sample is not None:
+                    want_occ = orc.bvh2_occluded(h.bvh2_nodes(), h.bvh2_prim_idx(), verts, shadow_sample)
+                    parity["shadow_flags_differ"] = int((want_occ != shadow_occ).sum())
+                    parity["shadow_occluded"] = int(want_occ.sum())
+                # ... and against the REAL reference under ITS OWN tie rule (oracle/_ref: BVH::Intersect of tiny_bvh.h on its own BuildHQ tree), the
+                # library's two deliberate deviations counted, not tolerated away (tests/oracle_lib.py: compare_with_real_reference)
+                if ref_blob and ref_blob.get("timed_launches_vs_real_reference"):
+                    parity["vs_real_reference"] = ref_blob.pop("timed_launches_vs_real_reference")
+                parity["ok"] = (parity["hitmiss"] == 0 and parity["prim_real"] == 0 and parity["t_bad"] == 0 and parity["uv_bad"] == 0 and parity["tie"] == 0 and
+                                parity["not_bit_identical"] == 0 and parity["onsurf"] <= 16 and parity["shadow_flags_differ"] <= 2)
+                vr = parity.get("vs_real_reference")
+                if vr and "error" not in vr:
+                    parity["ok"] = parity["ok"] and all(vr[k]["hitmiss"] == 0 and vr[k]["prim_real"] == 0 and vr[k]["t_bad"] == 0 and vr[k]["uv_differs"] == 0 and
+                                                        vr[k]["farther_by_ulps"] == 0 for k in ("primary", "diffuse"))
             except Exception as e:
-                log(f"[bench] cpu baseline failed: {e!r}")
-            legs.mark("cpu_baseline")
+                log(f"[bench] parity sample failed: {e!r}")
+                parity["error"] = repr(e)
+            detail["parity_sample"] = parity
+            legs.mark("parity")
 
-        # BASELINE configs 2 and 5 beside the headline (cheap: ~1 s each; their comparisons with the reference's OpenCL kernels live behind --detail)
-        if world == 1 and not inproc_devices:
-            import bench_detail as bd
-            for name, fn in (("config2", lambda: bd.config2_quick(tb, ctx, R, scenes)), ("tlas_1000_instances", lambda: bd.tlas_frames_leg(tb, ctx, R, scenes))):
+            # ---- roofline (contract: `achieved` = ALGORITHMIC bytes per launch / mean launch time; `traffic` = PMC bytes per launch) ------------------
+            try:
+                ceil = ceilings(ctx, a.ceilings, log)
+                # (the children run the schedule this process's tuner settled on for coherent batches, pinned: a child is too short to decide for itself)
+                a.coh_pin = {1: "0", 2: "2", 3: "3"}.get(sc.coherent_schedule(False)[0] if a.layout == tb.LAYOUT_CWBVH else 0)
+                passes = ("FETCH_SIZE", "WRITE_SIZE", "SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_THREAD_CYCLES_VALU SQ_BUSY_CYCLES") + \
+                         (("TCC_EA0_RDREQ_LEVEL_sum TCC_EA0_RDREQ_sum",) if a.detail else ())
+                pm = live_counters(a, log, passes=passes) if (world == 1 and not a.no_pmc) else None
+                roof = roofline_lines(a.layout, n, mean, S_T, pm, ceil)
+            except Exception as e:  # the checker is optional for the number itself
+                log(f"[bench] roofline failed: {e!r}")
+            legs.mark("roofline_pmc_children")
+
+            if not a.no_cpu_baseline:
                 try:
-                    detail[name] = fn()
+                    cpu = cpu_baseline(tb, ctx, verts, d_prim, d_diff, n, more=a.detail)
                 except Exception as e:
-                    log(f"[bench] {name} failed: {e!r}")
-            legs.mark("config2_config5")
+                    log(f"[bench] cpu baseline failed: {e!r}")
+                legs.mark("cpu_baseline")
+
+            # BASELINE configs 2 and 5 beside the headline (cheap: ~1 s each; their comparisons with the reference's OpenCL kernels live behind --detail)
+            if world == 1 and not inproc_devices:
+                import bench_detail as bd
+                for name, fn in (("config2", lambda: bd.config2_quick(tb, ctx, R, scenes)), ("tlas_1000_instances", lambda: bd.tlas_frames_leg(tb, ctx, R, scenes))):
+                    try:
+                        detail[name] = fn()
+                    except Exception as e:
+                        log(f"[bench] {name} failed: {e!r}")
+                legs.mark("config2_config5")
 
         if a.detail and world == 1:
             side_legs(a, tb, ctx, R, scenes, sc, verts, d_verts, d_prim, d_diff, n, cam, light, seed, kern_ms, timed_got, par_stride, ns_par, detail, legs,
@@ -551,13 +587,15 @@ def main():
             "parity_checked": bool(parity.get("n")) and "error" not in parity, "parity_ok": bool(parity.get("ok", False)),
             "detail": detail, "roofline": roof, "cpu_baseline": cpu, "legs_s": legs.rows,
         }
-        path = a.detail_out or (os.path.join("gpurun_out", "bench_detail.json") if os.path.isdir("gpurun_out") else "bench_detail.json")
-        try:
-            with open(path, "w") as f:
-                json.dump(full, f, indent=1)
-        except OSError as e:
-            log(f"[bench] could not write {path}: {e!r}")
-            path = None
+        path = None
+        if a.full:    # the run's full record: the sidecar file the line names
+            path = a.detail_out or "bench_detail.json"
+            try:
+                with open(path, "w") as f:
+                    json.dump(full, f, indent=1)
+            except OSError as e:
+                log(f"[bench] could not write {path}: {e!r}")
+                path = None
         line = compact_line(full, path)
         flush_c_stdio()
         print(json.dumps(line, separators=(",", ":")), flush=True)
@@ -570,7 +608,7 @@ def main():
     if own_cache:
         import shutil
         shutil.rmtree(own_cache, ignore_errors=True)
-    if rank == 0 and not a.no_parity:
+    if a.full and rank == 0 and not a.no_parity:
         if "error" in parity:      # the timed kernels were never checked: not a result either
             log(f"[bench] the parity check of the timed kernels could not run: {parity['error']}")
             sys.exit(4)

@@ -93,3 +93,23 @@ def test_plain_gpus_n_without_devices_says_so_and_exits_nonzero():
     assert r.returncode == 2, (r.returncode, r.stderr[-500:])
     line = json.loads([l for l in r.stdout.split("\n") if l.startswith("{")][-1])
     assert line["n_gpus"] == 2 and line["value"] is None and "HIP device" in line["error"]
+
+
+def test_dump_outputs_writes_a_fixed_sample_of_the_hit_records(tmp_path):
+    """`--dump-outputs`: t / u / v / prim of a seeded sample, the same rays for the same batch size, float32 / float64, well under 64 MB."""
+    import numpy as np
+    import tinybvh_amd as tb
+    n = bench.DUMP_SAMPLE + 4099
+    rec = np.zeros(n, dtype=tb.RAY_DTYPE)
+    rec["t"] = np.arange(n, dtype=np.float32); rec["u"] = 0.25; rec["v"] = 0.5; rec["prim"] = np.uint32(0xFFFFFFF0) - np.arange(n, dtype=np.uint32)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), "primary", rec)
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == ["primary_prim.npy", "primary_t.npy", "primary_u.npy", "primary_v.npy"]
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in files) < 32 << 20
+    t, prim = np.load(tmp_path / "a" / "primary_t.npy"), np.load(tmp_path / "a" / "primary_prim.npy")
+    assert t.dtype == np.float32 and prim.dtype == np.float64 and t.shape == (bench.DUMP_SAMPLE,)
+    idx = t.astype(np.int64)
+    assert np.all(np.diff(idx) > 0) and np.array_equal(prim, (0xFFFFFFF0 - idx).astype(np.float64))
+    for f in files:
+        assert np.array_equal(np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)), f

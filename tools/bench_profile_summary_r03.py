@@ -1,4 +1,4 @@
-"""Summary of `rocprofv3 --kernel-trace --stats -- python bench.py --steps 5 --warmup 2 --no-pmc --no-configs --no-cpu-baseline --no-strong`
+"""Summary of `rocprofv3 --kernel-trace --stats -- python bench.py --full --steps 5 --warmup 2 --no-pmc --no-configs --no-cpu-baseline --no-strong`
 (tools/runs/r03_run6.sh) next to the JSON line the same process printed: per traversal kernel the launches that did work (a probed query is TWO
 launches, one per verdict of the coherence probe; the flavor the verdict is not for leaves after ~4 us and is listed apart), whose average must
 agree with the HIP-event averages inside bench.py (detail.kernel_ms).
