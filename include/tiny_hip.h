@@ -57,6 +57,22 @@ public:
     explicit Scene(const tinybvh::BVH8_CWBVH& b, int device = 0, tbvh_context* own = nullptr) : dev(device), ctx(own ? own : Context(device)) {
         Check(tbvh_upload_cwbvh(ctx, b.bvh8Data, b.usedBlocks, b.bvh8Tris, (uint64_t)b.bvh8.idxCount * 3, &s), "tbvh_upload_cwbvh");
     }
+#ifdef DOUBLE_PRECISION_SUPPORT
+    // BVH_Double (tiny_bvh.h:1035-1090): traced in fp64 over RayEx records (tbvh_upload_bvh_double; custom geometry is not supported)
+    explicit Scene(const tinybvh::BVH_Double& b, int device = 0, tbvh_context* own = nullptr) : dev(device), ctx(own ? own : Context(device)) {
+        Check(tbvh_upload_bvh_double(ctx, b.bvhNode, b.usedNodes, b.primIdx, b.idxCount, b.verts, b.triCount, &s), "tbvh_upload_bvh_double");
+    }
+    // a BVH_Double built over BLASInstanceEx records (BVH_Double::Build( BLASInstanceEx*, ... )): blas[i] is the Scene of blasIdx == i
+    Scene(const tinybvh::BVH_Double& tlas, const std::vector<Scene*>& blas, int device = 0, tbvh_context* own = nullptr) : dev(device), ctx(own ? own : Context(device)) {
+        std::vector<tbvh_scene*> h;
+        for (Scene* b : blas) h.push_back(b->Handle());
+        Check(tbvh_upload_tlas_double(ctx, tlas.bvhNode, tlas.usedNodes, tlas.primIdx, tlas.idxCount, tlas.instList, tlas.triCount, h.data(), h.size(), &s),
+              "tbvh_upload_tlas_double");
+    }
+    // BVH_Double::Intersect( RayEx& ) / IsOccluded( const RayEx& ) (TLAS: IntersectTLAS / IsOccludedTLAS) over a host RayEx[], in place
+    void Intersect(tinybvh::RayEx* rays, size_t n) { Check(tbvh_intersect_ex(s, rays, n), "tbvh_intersect_ex"); }
+    void IsOccluded(const tinybvh::RayEx* rays, size_t n, uint8_t* out) { Check(tbvh_occluded_ex(s, rays, n, out), "tbvh_occluded_ex"); }
+#endif
     // the reference's flow for animated geometry — bvh.Refit() on the host, X.ConvertFrom( bvh ) again (tiny_bvh.h:3055-3093) — without a new
     // Scene: the refitted blob goes into the same device memory, TLASes over this BLAS keep working (tbvh_update_*)
     void Update(const tinybvh::BVH_GPU& b, const tinybvh::bvhvec4* verts) { Check(tbvh_update_bvh_gpu(s, b.bvhNode, b.usedNodes, b.bvh.primIdx, b.bvh.idxCount, verts, b.triCount), "tbvh_update_bvh_gpu"); }

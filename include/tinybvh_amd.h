@@ -46,7 +46,7 @@
 extern "C" {
 #endif
 
-#define TBVH_ABI_VERSION 5   /* 5: tbvh_pinned_malloc / _free, tbvh_scene_get / _set_schedule_hint, tbvh_measure_link_bandwidth, TBVH_BUILD_SPLIT_TRIANGLES / _WHOLE_TRIANGLES, development aids moved to tinybvh_amd_debug.h (nothing removed from the library); 4: tbvh_update_bvh_gpu / _bvh4_gpu / _cwbvh, tbvh_time_history, contexts are thread-safe; 3: deterministic ties, tbvh_bin_rays_device, tbvh_cwbvh_set_hybrid, device-resident multi-device calls */
+#define TBVH_ABI_VERSION 5   /* 5 (additions, nothing changed: BVH_Double scenes — TBVH_LAYOUT_BVH_DOUBLE, tbvh_upload_bvh_double / _tlas_double, tbvh_intersect_ex / _occluded_ex (+ _device), tbvh_host_build_double / _tlas_double); 5: tbvh_pinned_malloc / _free, tbvh_scene_get / _set_schedule_hint, tbvh_measure_link_bandwidth, TBVH_BUILD_SPLIT_TRIANGLES / _WHOLE_TRIANGLES, development aids moved to tinybvh_amd_debug.h (nothing removed from the library); 4: tbvh_update_bvh_gpu / _bvh4_gpu / _cwbvh, tbvh_time_history, contexts are thread-safe; 3: deterministic ties, tbvh_bin_rays_device, tbvh_cwbvh_set_hybrid, device-resident multi-device calls */
 
 /* error codes */
 #define TBVH_OK            0
@@ -59,6 +59,7 @@ extern "C" {
 /* layouts; the values ARE BVHBase::BVHType (tiny_bvh.h:773-791), so a caller can pass bvh.layout
  * (ABI version 1 used 4 / 6 / 9 here, which are LAYOUT_BVH_SOA / LAYOUT_MBVH / LAYOUT_MBVH8 in the reference) */
 #define TBVH_LAYOUT_BVH2_WALD  1  /* LAYOUT_BVH       32-byte nodes (host/oracle only)   */
+#define TBVH_LAYOUT_BVH_DOUBLE 3  /* LAYOUT_BVH_DOUBLE fp64 64-byte nodes, RayEx queries  */
 #define TBVH_LAYOUT_BVH_GPU    5  /* LAYOUT_BVH_GPU   Aila-Laine 64-byte nodes           */
 #define TBVH_LAYOUT_BVH4_GPU   8  /* LAYOUT_BVH4_GPU  quantized 4-wide + inline tris     */
 #define TBVH_LAYOUT_CWBVH     10  /* LAYOUT_CWBVH     compressed wide BVH8               */
@@ -545,6 +546,42 @@ uint64_t    tbvh_host_blob_count(const tbvh_hostbvh* h, int which); /* elements,
 /* Convenience: upload a host-built BVH (verts16 needed for BVH_GPU only). */
 int tbvh_upload_host(tbvh_context* ctx, const tbvh_hostbvh* h, const void* verts16,
                      uint64_t n_tris, tbvh_scene** out);
+
+/* ----------------------------------------------------------------------------------
+ * double precision — BVH_Double (tiny_bvh.h:1035-1090) and its queries BVH_Double::Intersect / IsOccluded / IntersectTLAS /
+ * IsOccludedTLAS (tiny_bvh.h:8158-8375) over RayEx records, in fp64 on the device (DESIGN.md par. 9).  Records are tinybvh's own:
+ *   node (64 bytes)       aabbMin dbl3 @0, aabbMax dbl3 @24, leftFirst u64 @48, triCount u64 @56; leaf iff triCount > 0, children
+ *                         leftFirst and leftFirst + 1 (BVH_Double::bvhNode, n_nodes = usedNodes)
+ *   RayEx (128 bytes)     O @0, D @24, rD @48 (dbl3 each), hit.t @72, hit.u @80, hit.v @88, hit.inst u64 @96, hit.prim u64 @104,
+ *                         instIdx u64 @112, mask u64 @120 (tiny_bvh.h:733-761)
+ *   BLASInstanceEx (320)  transform[16] @0, invTransform[16] @128, aabbMin @256, blasIdx u64 @280, aabbMax @288, mask u64 @312
+ *   vertices              bvhdbl3 verts[3 * n_tris] (BVH_Double::verts), prim indices uint64_t primIdx[n_idx]
+ * A hit writes t, u, v, prim and inst (= ray.instIdx for a BLAS, the instance index under a TLAS); a miss leaves the record untouched;
+ * occlusion is a hit with 0 < t < hit.t.  Equal distances resolve as everywhere in this library (smaller prim, then smaller instance).
+ * Blobs are validated before anything is allocated (TBVH_E_FORMAT names the first bad entry: child or leaf range, primIdx, blasIdx, fewer than
+ * 2^32 nodes, not a tree).  A BVH_DOUBLE scene takes the four _ex queries, tbvh_free_scene, tbvh_scene_layout (3) and tbvh_scene_device_bytes;
+ * every other entry point refuses it (TBVH_E_INVALID), and the _ex queries refuse the fp32 layouts.  Custom geometry (customIntersect) is
+ * not supported: upload needs triangles.
+ * ---------------------------------------------------------------------------------- */
+int tbvh_upload_bvh_double(tbvh_context* ctx, const void* nodes64, uint64_t n_nodes, const uint64_t* prim_idx, uint64_t n_idx,
+                           const void* verts_dbl3, uint64_t n_tris, tbvh_scene** out);
+/* tlas_nodes64 / tlas_idx = the TLAS BVH_Double's bvhNode / primIdx (instance indices), instances320 = its instList; blas[i] is the BVH_DOUBLE
+ * scene of blasIdx == i.  The TLAS keeps references to its BLASes as tbvh_upload_tlas does. */
+int tbvh_upload_tlas_double(tbvh_context* ctx, const void* tlas_nodes64, uint64_t n_nodes, const uint64_t* tlas_idx, uint64_t n_idx,
+                            const void* instances320, uint64_t n_inst, tbvh_scene* const* blas, uint64_t n_blas, tbvh_scene** out);
+/* device RayEx arrays (16-byte aligned), asynchronous on the context's stream */
+int tbvh_intersect_ex_device(tbvh_scene* scene, void* d_rays128, uint64_t n_rays);
+int tbvh_occluded_ex_device(tbvh_scene* scene, const void* d_rays128, uint64_t n_rays, uint8_t* d_occluded);
+/* host RayEx arrays: copied up, traced, copied back; synchronous */
+int tbvh_intersect_ex(tbvh_scene* scene, void* rays128, uint64_t n_rays);
+int tbvh_occluded_ex(tbvh_scene* scene, const void* rays128, uint64_t n_rays, uint8_t* occluded);
+/* The library's builders for callers without tinybvh: the topology of the fp32 builder (tbvh_host_build / _tlas) run on the input translated
+ * by its centre and rounded to float, every node box recomputed bottom-up in double, so the boxes are exact.  tbvh_host_blob(h, 0) = nodes
+ * (64 bytes each), (h, 1) = prim / instance indices (uint64_t); tbvh_host_layout = TBVH_LAYOUT_BVH_DOUBLE.  The TLAS builder first fills every
+ * instance's invTransform, aabbMin and aabbMax as BLASInstanceEx::Update does (tiny_bvh.h:8432-8472) from blas_bounds_dbl6 (6 doubles per BLAS:
+ * aabbMin, aabbMax). */
+int tbvh_host_build_double(const void* verts_dbl3, uint64_t n_tris, tbvh_hostbvh** out);
+int tbvh_host_build_tlas_double(void* instances320, uint64_t n_instances, const double* blas_bounds_dbl6, uint64_t n_blas, tbvh_hostbvh** out);
 
 #ifdef __cplusplus
 }

@@ -1,0 +1,143 @@
+"""Shared pieces of the BVH_Double tests: the restated oracle (tests/oracle_double.c, compiled per session into a pytest temp dir
+with -ffp-contract=off), scenes promoted to double and rays built in double."""
+import ctypes as C
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+import tinybvh_amd as tb
+from tinybvh_amd import rays as R
+from tinybvh_amd import scenes
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+_vp, _u64, _i = C.c_void_p, C.c_uint64, C.c_int
+
+
+def _p(a):
+    return C.c_void_p(a.ctypes.data)
+
+
+class OracleDouble:
+    """BVH_Double::Intersect / IsOccluded / IntersectTLAS / IsOccludedTLAS restated (oracle_double.c); rule 0 = the reference's
+    tie behaviour, rule 1 = the library's rule plus the eight-ulp box slack."""
+
+    def __init__(self, so_path: str):
+        self.lib = C.CDLL(so_path)
+        self.lib.od_intersect.argtypes = [_vp, _vp, _vp, _vp, _u64, _i]
+        self.lib.od_occluded.argtypes = [_vp, _vp, _vp, _vp, _u64, _i, _vp]
+        self.lib.od_intersect_tlas.argtypes = [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _u64, _i]
+        self.lib.od_occluded_tlas.argtypes = [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _u64, _i, _vp]
+
+    @staticmethod
+    def _blob(nodes, idx, verts):
+        return (np.ascontiguousarray(nodes), np.ascontiguousarray(idx, np.uint64), np.ascontiguousarray(verts, np.float64))
+
+    def intersect(self, nodes, idx, verts, rays, rule=1):
+        nodes, idx, verts = self._blob(nodes, idx, verts)
+        out = np.ascontiguousarray(rays).copy()
+        self.lib.od_intersect(_p(nodes), _p(idx), _p(verts), _p(out), out.shape[0], rule)
+        return out
+
+    def occluded(self, nodes, idx, verts, rays, rule=1):
+        nodes, idx, verts = self._blob(nodes, idx, verts)
+        rays = np.ascontiguousarray(rays)
+        out = np.zeros(rays.shape[0], np.uint8)
+        self.lib.od_occluded(_p(nodes), _p(idx), _p(verts), _p(rays), rays.shape[0], rule, _p(out))
+        return out
+
+    def _tlas_args(self, tnodes, tidx, inst, blas):
+        keep = [self._blob(*b) for b in blas]
+        bn = (C.c_void_p * len(keep))(*[k[0].ctypes.data for k in keep])
+        bi = (C.c_void_p * len(keep))(*[k[1].ctypes.data for k in keep])
+        bv = (C.c_void_p * len(keep))(*[k[2].ctypes.data for k in keep])
+        tnodes, tidx, _ = self._blob(tnodes, tidx, np.zeros(1))
+        inst = np.ascontiguousarray(inst)
+        return keep, (tnodes, tidx, inst), (_p(tnodes), _p(tidx), _p(inst), C.cast(bn, _vp), C.cast(bi, _vp), C.cast(bv, _vp))
+
+    def intersect_tlas(self, tnodes, tidx, inst, blas, rays, rule=1):
+        """blas: list of (nodes, prim_idx, verts) per blasIdx."""
+        keep, keep2, a = self._tlas_args(tnodes, tidx, inst, blas)
+        out = np.ascontiguousarray(rays).copy()
+        self.lib.od_intersect_tlas(*a, _p(out), out.shape[0], rule)
+        return out
+
+    def occluded_tlas(self, tnodes, tidx, inst, blas, rays, rule=1):
+        keep, keep2, a = self._tlas_args(tnodes, tidx, inst, blas)
+        rays = np.ascontiguousarray(rays)
+        out = np.zeros(rays.shape[0], np.uint8)
+        self.lib.od_occluded_tlas(*a, _p(rays), rays.shape[0], rule, _p(out))
+        return out
+
+
+@pytest.fixture(scope="session")
+def odbl(tmp_path_factory):
+    d = tmp_path_factory.mktemp("oracle_double")
+    so = str(d / "liboracle_double.so")
+    subprocess.check_call(["cc", "-O2", "-ffp-contract=off", "-fPIC", "-shared", os.path.join(HERE, "oracle_double.c"), "-o", so, "-lm"])
+    return OracleDouble(so)
+
+
+# ---- scenes and rays in double -----------------------------------------------------------------------------------------------------
+
+def to_dbl(verts4: np.ndarray) -> np.ndarray:
+    """(3 n, 4) float32 -> (3 n, 3) float64 (exact)."""
+    return np.ascontiguousarray(np.asarray(verts4)[:, :3], np.float64)
+
+
+def rot_matrix(ax: float, ay: float, az: float) -> np.ndarray:
+    cx, sx, cy, sy, cz, sz = np.cos(ax), np.sin(ax), np.cos(ay), np.sin(ay), np.cos(az), np.sin(az)
+    Rx = np.array([[1, 0, 0], [0, cx, -sx], [0, sx, cx]])
+    Ry = np.array([[cy, 0, sy], [0, 1, 0], [-sy, 0, cy]])
+    Rz = np.array([[cz, -sz, 0], [sz, cz, 0], [0, 0, 1]])
+    return Rz @ Ry @ Rx
+
+
+def rotated_soup(n_tris: int, seed: int = 7) -> np.ndarray:
+    v = to_dbl(scenes.soup(n_tris, seed=seed, extent=20.0, size=0.5))
+    return np.ascontiguousarray((v - 10.0) @ rot_matrix(0.61, 0.75, 0.33).T)
+
+
+def camera_rays_dbl(eye, view, w: int, h: int, scale: float = 1.0, offset=(0.0, 0.0, 0.0)) -> np.ndarray:
+    """The atrium camera's primary rays, origin and direction promoted to double, then scaled / translated in double."""
+    r = R.primary(R.camera(eye, view, w, h, 1, 1))
+    O = r["O"].astype(np.float64) * scale + np.asarray(offset, np.float64)
+    return tb.make_rays_ex(O, r["D"].astype(np.float64))
+
+
+def bounce_rays_dbl(traced: np.ndarray, seed: int = 5, scale: float = 1.0) -> np.ndarray:
+    """Diffuse-ish secondary rays from the hit points of traced RayEx records (misses start 20 * scale along the ray), origins moved
+    1e-4 * scale off the surface."""
+    rng = np.random.default_rng(seed)
+    n = traced.shape[0]
+    hit = traced["t"] < 1e299
+    t = np.where(hit, traced["t"], 20.0 * scale)
+    I = traced["O"] + t[:, None] * traced["D"]
+    Dn = rng.normal(size=(n, 3))
+    Dn = np.where(((Dn * traced["D"]).sum(1) > 0)[:, None], -Dn, Dn)   # back towards where the ray came from
+    return tb.make_rays_ex(I + 1e-4 * scale * Dn / np.linalg.norm(Dn, axis=1, keepdims=True), Dn)
+
+
+def random_rays_dbl(n: int, lo, hi, seed: int = 11) -> np.ndarray:
+    rng = np.random.default_rng(seed)
+    lo = np.asarray(lo, np.float64); hi = np.asarray(hi, np.float64)
+    return tb.make_rays_ex(lo + rng.random((n, 3)) * (hi - lo), rng.normal(size=(n, 3)))
+
+
+def instance_scene(n_inst: int = 500, seed: int = 3):
+    """Three BLASes (float-exact soups / atrium piece) and n_inst instances with random rotation, scale and offsets near 1e6."""
+    rng = np.random.default_rng(seed)
+    blas_verts = [to_dbl(scenes.soup(3000, seed=11, extent=6.0, size=0.8)) - 3.0, to_dbl(scenes.atrium(6000, seed=2)) * 0.1,
+                  rotated_soup(2000, seed=13) * 0.4]
+    T = np.zeros((n_inst, 4, 4))
+    for i in range(n_inst):
+        s = rng.uniform(0.5, 2.0)
+        T[i, :3, :3] = rot_matrix(*rng.uniform(0, 2 * np.pi, 3)) * s
+        T[i, :3, 3] = np.array([1.0e6, -2.0e6, 3.0e6]) + rng.uniform(-60, 60, 3)
+        T[i, 3, 3] = 1.0
+    blas_idx = rng.integers(0, 3, n_inst)
+    masks = np.where(rng.random(n_inst) < 0.2, 0x2, 0xFFFF).astype(np.uint64)   # a fifth of the instances only answer rays whose mask has bit 1
+    inst = tb.make_instances_ex(T, blas_idx)
+    inst["mask"] = masks
+    return blas_verts, inst

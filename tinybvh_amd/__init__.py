@@ -18,6 +18,7 @@ from . import _capi
 from ._capi import BuildParams, Camera, TbvhError, check, lib
 
 LAYOUT_BVH2_WALD = 1
+LAYOUT_BVH_DOUBLE = 3
 LAYOUT_BVH_GPU = 5
 LAYOUT_BVH4_GPU = 8
 LAYOUT_CWBVH = 10
@@ -732,3 +733,172 @@ class Wavefront:
             self.close()
         except Exception:
             pass
+
+
+# ---- double precision: BVH_Double, RayEx, BLASInstanceEx (tiny_bvh.h:733-761, 1035-1090, 1462-1474) --------------------------------------
+BVH_DBL_FAR = 1e300   # tiny_bvh.h:145
+
+RAYEX_DTYPE = np.dtype([
+    ("O", "<f8", 3), ("D", "<f8", 3), ("rD", "<f8", 3),
+    ("t", "<f8"), ("u", "<f8"), ("v", "<f8"), ("inst", "<u8"), ("prim", "<u8"),
+    ("instIdx", "<u8"), ("mask", "<u8"),
+])
+assert RAYEX_DTYPE.itemsize == 128
+
+INSTANCE_EX_DTYPE = np.dtype([
+    ("transform", "<f8", 16), ("invTransform", "<f8", 16),
+    ("aabbMin", "<f8", 3), ("blasIdx", "<u8"), ("aabbMax", "<f8", 3), ("mask", "<u8"),
+])
+assert INSTANCE_EX_DTYPE.itemsize == 320
+
+NODE_DBL_DTYPE = np.dtype([("aabbMin", "<f8", 3), ("aabbMax", "<f8", 3), ("leftFirst", "<u8"), ("triCount", "<u8")])   # BVH_Double::BVHNode
+assert NODE_DBL_DTYPE.itemsize == 64
+
+
+def make_rays_ex(O: np.ndarray, D: np.ndarray, tmax=BVH_DBL_FAR, mask: int = 0xFFFF) -> np.ndarray:
+    """RayEx records as the RayEx constructor makes them (tiny_bvh.h:744-755): D normalised with 1 / sqrt, rD = 1 / D unguarded
+    (an axis-parallel ray gets rD = +-inf), hit = {tmax, 0, 0}, instIdx 0, mask & 0xFFFF."""
+    O = np.ascontiguousarray(O, dtype=np.float64).reshape(-1, 3)
+    D = np.ascontiguousarray(D, dtype=np.float64).reshape(-1, 3)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        rl = 1.0 / np.sqrt(D[:, 0] * D[:, 0] + D[:, 1] * D[:, 1] + D[:, 2] * D[:, 2])
+        D = D * rl[:, None]
+        rD = 1.0 / D
+    rays = np.zeros(O.shape[0], dtype=RAYEX_DTYPE)
+    rays["O"] = O
+    rays["D"] = D
+    rays["rD"] = rD
+    rays["t"] = tmax
+    rays["mask"] = mask & 0xFFFF
+    return rays
+
+
+def make_instances_ex(transforms: np.ndarray, blas_idx, mask: int = 0xFFFF) -> np.ndarray:
+    """BLASInstanceEx records from (n, 4, 4) row-major double transforms; invTransform and the bounds are filled by
+    TLAS_Double.Build (BLASInstanceEx::Update, tiny_bvh.h:8432-8472)."""
+    t = np.ascontiguousarray(transforms, np.float64).reshape(-1, 16)
+    inst = np.zeros(t.shape[0], INSTANCE_EX_DTYPE)
+    inst["transform"] = t
+    inst["invTransform"] = np.eye(4).reshape(16)
+    inst["blasIdx"] = blas_idx
+    inst["mask"] = mask
+    return inst
+
+
+class HostBVHDouble:
+    """Blobs of the library's double-precision builders (tbvh_host_build_double / tbvh_host_build_tlas_double): nodes (NODE_DBL_DTYPE)
+    and the uint64 prim (TLAS: instance) indices."""
+
+    def __init__(self, h: C.c_void_p):
+        self._h = h
+
+    def nodes(self) -> np.ndarray:
+        return self._view(0, NODE_DBL_DTYPE)
+
+    def prim_idx(self) -> np.ndarray:
+        return self._view(1, np.dtype("<u8"))
+
+    def _view(self, which: int, dtype) -> np.ndarray:
+        p = lib.tbvh_host_blob(self._h, which)
+        n = lib.tbvh_host_blob_count(self._h, which)
+        if not p or n == 0:
+            return np.zeros(0, dtype)
+        buf = (C.c_char * (n * dtype.itemsize)).from_address(p)
+        buf._owner = self
+        a = np.frombuffer(buf, dtype=dtype)
+        a.flags.writeable = False
+        return a
+
+    def __del__(self):
+        try:
+            if self._h:
+                lib.tbvh_host_free(self._h)
+                self._h = None
+        except Exception:
+            pass
+
+
+def host_build_double(verts: np.ndarray) -> HostBVHDouble:
+    """tbvh_host_build_double over a (3 n, 3) float64 triangle soup."""
+    verts = np.ascontiguousarray(verts, np.float64).reshape(-1, 3)
+    assert verts.shape[0] % 3 == 0
+    h = C.c_void_p()
+    check(lib.tbvh_host_build_double(_ptr(verts), verts.shape[0] // 3, C.byref(h)), "tbvh_host_build_double")
+    return HostBVHDouble(h)
+
+
+def host_build_tlas_double(instances: np.ndarray, blas_bounds: np.ndarray) -> HostBVHDouble:
+    """tbvh_host_build_tlas_double: instances (INSTANCE_EX_DTYPE, updated in place) over BLASes with bounds (n_blas, 6) float64."""
+    assert instances.dtype == INSTANCE_EX_DTYPE and instances.flags["C_CONTIGUOUS"]
+    bounds = np.ascontiguousarray(blas_bounds, np.float64).reshape(-1, 6)
+    h = C.c_void_p()
+    check(lib.tbvh_host_build_tlas_double(_ptr(instances), instances.shape[0], _ptr(bounds), bounds.shape[0], C.byref(h)), "tbvh_host_build_tlas_double")
+    return HostBVHDouble(h)
+
+
+class _SceneDouble(_Scene):
+    """A BVH_DOUBLE scene: RayEx queries only (tbvh_intersect_ex / tbvh_occluded_ex); every fp32 entry point refuses it."""
+    layout = LAYOUT_BVH_DOUBLE
+
+    def Intersect(self, rays: np.ndarray) -> np.ndarray:
+        """rays: RAYEX_DTYPE array, updated in place (records that hit) and returned."""
+        assert rays.dtype == RAYEX_DTYPE and rays.flags["C_CONTIGUOUS"] and rays.flags["WRITEABLE"]
+        check(lib.tbvh_intersect_ex(self._h, _ptr(rays), rays.shape[0]), "tbvh_intersect_ex")
+        return rays
+
+    def IsOccluded(self, rays: np.ndarray) -> np.ndarray:
+        assert rays.dtype == RAYEX_DTYPE and rays.flags["C_CONTIGUOUS"]
+        out = np.zeros(rays.shape[0], dtype=np.uint8)
+        check(lib.tbvh_occluded_ex(self._h, _ptr(rays), rays.shape[0], _ptr(out)), "tbvh_occluded_ex")
+        return out
+
+    def intersect_device(self, d_rays: int, n: int):
+        check(lib.tbvh_intersect_ex_device(self._h, C.c_void_p(d_rays), n), "tbvh_intersect_ex_device")
+
+    def occluded_device(self, d_rays: int, n: int, d_out: int):
+        check(lib.tbvh_occluded_ex_device(self._h, C.c_void_p(d_rays), n, C.c_void_p(d_out)), "tbvh_occluded_ex_device")
+
+
+class BVH_Double(_SceneDouble):
+    """BVH_Double (tiny_bvh.h:1035-1090) on the device: Intersect / IsOccluded in fp64 over RayEx records."""
+
+    def Build(self, verts: np.ndarray) -> "BVH_Double":
+        """verts: (3 n, 3) float64 triangle soup (BVH_Double::verts)."""
+        self.verts = np.ascontiguousarray(verts, np.float64).reshape(-1, 3)
+        self.host = host_build_double(self.verts)
+        return self.Upload(self.host.nodes(), self.host.prim_idx(), self.verts)
+
+    def Upload(self, nodes: np.ndarray, prim_idx: np.ndarray, verts: np.ndarray) -> "BVH_Double":
+        """nodes: BVH_Double::bvhNode (NODE_DBL_DTYPE or raw 64-byte records), prim_idx: uint64 primIdx, verts: float64 (3 n, 3)."""
+        nodes = np.ascontiguousarray(nodes); prim_idx = np.ascontiguousarray(prim_idx, np.uint64)
+        verts = np.ascontiguousarray(verts, np.float64)
+        self.verts = verts
+        check(lib.tbvh_upload_bvh_double(self.ctx._h, _ptr(nodes), nodes.nbytes // 64, _ptr(prim_idx), prim_idx.size, _ptr(verts), verts.size // 9,
+                                         C.byref(self._h)), "tbvh_upload_bvh_double")
+        return self
+
+    @property
+    def bounds(self) -> np.ndarray:
+        """aabbMin, aabbMax of the vertices (what BLASInstanceEx::Update reads from a BLAS)."""
+        v = self.verts.reshape(-1, 3)
+        return np.concatenate([v.min(0), v.max(0)])
+
+
+class TLAS_Double(_SceneDouble):
+    """A BVH_Double over BLASInstanceEx records (BVH_Double::Build(BLASInstanceEx*, ...); IntersectTLAS / IsOccludedTLAS)."""
+
+    def Build(self, instances: np.ndarray, blas: list) -> "TLAS_Double":
+        """instances: INSTANCE_EX_DTYPE with transform / blasIdx / mask set (updated in place); blas: uploaded BVH_Double scenes."""
+        bounds = np.stack([b.bounds for b in blas])
+        self.host = host_build_tlas_double(instances, bounds)
+        return self.Upload(self.host.nodes(), self.host.prim_idx(), instances, blas)
+
+    def Upload(self, nodes: np.ndarray, tlas_idx: np.ndarray, instances: np.ndarray, blas: list) -> "TLAS_Double":
+        nodes = np.ascontiguousarray(nodes); tlas_idx = np.ascontiguousarray(tlas_idx, np.uint64)
+        instances = np.ascontiguousarray(instances)
+        arr = (C.c_void_p * len(blas))(*[b._h for b in blas])
+        check(lib.tbvh_upload_tlas_double(self.ctx._h, _ptr(nodes), nodes.nbytes // 64, _ptr(tlas_idx), tlas_idx.size, _ptr(instances), instances.shape[0],
+                                          arr, len(blas), C.byref(self._h)), "tbvh_upload_tlas_double")
+        self.instances = instances
+        self.blas = list(blas)   # the BLAS scenes must outlive the TLAS
+        return self

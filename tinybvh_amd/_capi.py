@@ -118,6 +118,15 @@ SYMBOLS = {
     "tbvh_host_blob": (_vp, [_vp, _i]),
     "tbvh_host_blob_count": (_u64, [_vp, _i]),
     "tbvh_upload_host": (_i, [_vp, _vp, _vp, _u64, _pp]),
+    # BVH_Double scenes (capi_double.hip)
+    "tbvh_upload_bvh_double": (_i, [_vp, _vp, _u64, _vp, _u64, _vp, _u64, _pp]),
+    "tbvh_upload_tlas_double": (_i, [_vp, _vp, _u64, _vp, _u64, _vp, _u64, _pp, _u64, _pp]),
+    "tbvh_intersect_ex_device": (_i, [_vp, _vp, _u64]),
+    "tbvh_occluded_ex_device": (_i, [_vp, _vp, _u64, _vp]),
+    "tbvh_intersect_ex": (_i, [_vp, _vp, _u64]),
+    "tbvh_occluded_ex": (_i, [_vp, _vp, _u64, _vp]),
+    "tbvh_host_build_double": (_i, [_vp, _u64, _pp]),
+    "tbvh_host_build_tlas_double": (_i, [_vp, _u64, _vp, _u64, _pp]),
 }
 
 

@@ -1,0 +1,344 @@
+// capi_double.hip — BVH_Double scenes (tiny_bvh.h:1035-1090): upload with validation, the _ex queries over RayEx records, and the host
+// builders behind tbvh_host_build_double / tbvh_host_build_tlas_double.  The kernels are kernels_double.hip.
+// A BVH_DOUBLE scene keeps its device memory in the fields every scene has (capi_scene.hip: tbvh_free_scene frees them): a BLAS its nodes in
+// `nodes` and its gathered triangle records in `tris`; a TLAS ONE allocation in `nodes` = [TLAS nodes | instance indices | instances | BLAS
+// descriptors], each part 16-byte aligned.  Nothing else of the fp32 machinery (copies, tuners, refit, updates) applies to it: the entry
+// points of those refuse a BVH_DOUBLE scene.
+#include "capi_internal.h"
+
+using namespace tbvh;
+using namespace tbvh_capi;
+
+namespace {
+
+constexpr double kDblFarHost = 1e300;   // BVH_DBL_FAR, tiny_bvh.h:145
+
+uint64_t align16(uint64_t b) { return (b + 15) & ~15ull; }
+
+// The checks of a caller's blob, before anything is allocated.  msg receives the first bad entry; returns TBVH_E_FORMAT or 0.
+int validateDouble(const NodeDbl* n, uint64_t nNodes, const uint64_t* idx, uint64_t nIdx, uint64_t nPrims, const char* who, const char* primWhat) {
+    if (nNodes == 0) return fail(TBVH_E_FORMAT, "%s: empty node array", who);
+    if (nNodes >= (1ull << 32)) return fail(TBVH_E_FORMAT, "%s: %llu nodes: at most 2^32 - 1 (traversal stack entries are 32-bit)", who, (unsigned long long)nNodes);
+    for (uint64_t i = 0; i < nNodes; i++) {
+        const uint64_t lf = n[i].leftFirst, cnt = n[i].triCount;
+        if (cnt) {
+            if (lf > nIdx || cnt > nIdx - lf)
+                return fail(TBVH_E_FORMAT, "%s: node %llu: leaf range [%llu, %llu + %llu) beyond n_idx = %llu", who, (unsigned long long)i, (unsigned long long)lf,
+                            (unsigned long long)lf, (unsigned long long)cnt, (unsigned long long)nIdx);
+        } else if (lf >= nNodes - 1)
+            return fail(TBVH_E_FORMAT, "%s: node %llu: child index %llu out of range (leftFirst + 1 >= n_nodes = %llu)", who, (unsigned long long)i, (unsigned long long)lf,
+                        (unsigned long long)nNodes);
+    }
+    for (uint64_t i = 0; i < nIdx; i++)
+        if (idx[i] >= nPrims)
+            return fail(TBVH_E_FORMAT, "%s: primIdx[%llu] = %llu >= %s = %llu", who, (unsigned long long)i, (unsigned long long)idx[i], primWhat, (unsigned long long)nPrims);
+    // in-range indices keep every read in bounds; only a TREE keeps the traversal finite: from the root, no node may be reached twice
+    std::vector<uint8_t> seen;
+    std::vector<uint32_t> stack{0};
+    try { seen.assign(nNodes, 0); } catch (const std::bad_alloc&) { return fail(TBVH_E_NOMEM, "%s: out of host memory", who); }
+    seen[0] = 1;
+    while (!stack.empty()) {
+        const uint32_t i = stack.back(); stack.pop_back();
+        if (n[i].triCount) continue;
+        for (const uint32_t c : {(uint32_t)n[i].leftFirst, (uint32_t)n[i].leftFirst + 1u}) {
+            if (seen[c]) return fail(TBVH_E_FORMAT, "%s: node %u is reachable along two paths (the node array is not a tree)", who, c);
+            seen[c] = 1; stack.push_back(c);
+        }
+    }
+    return 0;
+}
+
+bool isDouble(const tbvh_scene* s) { return s->layout == TBVH_LAYOUT_BVH_DOUBLE; }
+
+// TLAS parts inside its one allocation
+struct TlasParts { const uint64_t* idx; const InstanceDbl* inst; const BlasDbl* blas; };
+TlasParts tlasParts(const tbvh_scene* s) {
+    const char* base = (const char*)s->nodes;
+    const uint64_t oIdx = align16(s->nTlasNodes * sizeof(NodeDbl)), oInst = oIdx + align16(s->nTlasIdx * 8), oBlas = oInst + s->nInst * sizeof(InstanceDbl);
+    return TlasParts{(const uint64_t*)(base + oIdx), (const InstanceDbl*)(base + oInst), (const BlasDbl*)(base + oBlas)};
+}
+
+// one query launch on the context's stream (asynchronous), the ray pool and stack spill shared with launchQuery (capi_query.hip)
+int launchDouble(tbvh_scene* s, RayExRec* dRays, uint64_t n, uint8_t* dOcc) {
+    tbvh_context* c = s->ctx;
+    TBVH_ENTER(c);
+    if (n == 0) return 0;
+    const size_t poolWords = (size_t)(kPoolParts + 1) * kPoolCounterStride;
+    if (!c->poolClean) HIP_TRY(hipMemsetAsync(c->pool, 0, poolWords * 4 * 2, c->stream));
+    c->poolClean = false;
+    DoubleArgs q;
+    q.rays = dRays; q.nRays = n; q.occluded = dOcc;
+    q.spill = c->spill; q.spillStride = c->spillEntries;
+    q.counter = (uint32_t*)c->pool + (size_t)c->poolCur * poolWords; q.counterNext = (uint32_t*)c->pool + (size_t)(c->poolCur ^ 1) * poolWords;
+    q.poolParts = c->poolParts;
+    q.nodes = (const NodeDbl*)s->nodes; q.tris = (const TriDbl*)s->tris;
+    q.tlasIdx = nullptr; q.inst = nullptr; q.blas = nullptr;
+    if (s->isTlas) { const TlasParts p = tlasParts(s); q.tlasIdx = p.idx; q.inst = p.inst; q.blas = p.blas; }
+    // one workgroup per 128 rays, at least four per CU, at most the persistent grid the spill area is sized for
+    const uint64_t want = (n + 127) / 128, lo = (uint64_t)c->numCUs * 4u;
+    const uint32_t blocks = (uint32_t)(want < lo ? lo : (want > c->blocks ? c->blocks : want));
+    HIP_TRY(timedBegin(c));
+    launch_double(dOcc != nullptr, s->isTlas, q, c->status, blocks, c->stream);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(timedEnd(c));
+    c->poolCur ^= 1; c->poolClean = true;
+    return 0;
+}
+
+// host RayEx[] queries: one staged copy up, one launch, one copy back
+int hostQueryEx(tbvh_scene* s, void* rays, uint64_t n, uint8_t* occ, const char* who) {
+    tbvh_context* c = s->ctx;
+    TBVH_ENTER(c);
+    void* d = nullptr;
+    uint8_t* dOcc = nullptr;
+    if (hipMalloc(&d, n * sizeof(RayExRec)) != hipSuccess) return fail(TBVH_E_NOMEM, "%s: no device memory for %llu rays", who, (unsigned long long)n);
+    if (occ && hipMalloc((void**)&dOcc, n) != hipSuccess) { hipFree(d); return fail(TBVH_E_NOMEM, "%s: no device memory for %llu results", who, (unsigned long long)n); }
+    int r = 0;
+    if (hipMemcpyAsync(d, rays, n * sizeof(RayExRec), hipMemcpyHostToDevice, c->stream) != hipSuccess) r = fail(TBVH_E_HIP, "%s: copy to the device failed", who);
+    if (!r) r = launchDouble(s, (RayExRec*)d, n, dOcc);
+    if (!r) {
+        const hipError_t e = occ ? hipMemcpyAsync(occ, dOcc, n, hipMemcpyDeviceToHost, c->stream) : hipMemcpyAsync(rays, d, n * sizeof(RayExRec), hipMemcpyDeviceToHost, c->stream);
+        if (e != hipSuccess) r = fail(TBVH_E_HIP, "%s: copy from the device failed", who);
+    }
+    if (!r) r = checkStatus(c);   // (synchronizes)
+    else hipStreamSynchronize(c->stream);
+    hipFree(d);
+    if (dOcc) hipFree(dOcc);
+    return r;
+}
+
+// ---- host builders --------------------------------------------------------------------------------------------------------------------
+// The topology comes from the fp32 builders (build_bvh2 / build_bvh2_boxes) run on the input translated by its centre and rounded to float;
+// every node box is then recomputed bottom-up in double from the double triangles / instance boxes, so the tree is exact and only its SAH
+// quality depends on float.
+void doubleFromTopology(const BVH2& b, const std::function<void(uint64_t prim, double* mn, double* mx)>& primBox, std::vector<NodeDbl>& out) {
+    out.assign(b.nodes.size(), NodeDbl{});
+    for (size_t i = 0; i < b.nodes.size(); i++) { out[i].leftFirst = b.nodes[i].leftFirst; out[i].triCount = b.nodes[i].triCount; }
+    std::vector<uint32_t> order, stack{0};
+    while (!stack.empty()) {   // pre-order from the root; reversed, children come before their parent
+        const uint32_t i = stack.back(); stack.pop_back();
+        order.push_back(i);
+        if (!b.nodes[i].leaf()) { stack.push_back(b.nodes[i].leftFirst); stack.push_back(b.nodes[i].leftFirst + 1); }
+    }
+    for (size_t k = order.size(); k-- > 0;) {
+        NodeDbl& n = out[order[k]];
+        for (int a = 0; a < 3; a++) { n.mn[a] = kDblFarHost; n.mx[a] = -kDblFarHost; }
+        if (n.triCount) {
+            for (uint64_t j = 0; j < n.triCount; j++) {
+                double mn[3], mx[3];
+                primBox(b.primIdx[n.leftFirst + j], mn, mx);
+                for (int a = 0; a < 3; a++) { n.mn[a] = std::min(n.mn[a], mn[a]); n.mx[a] = std::max(n.mx[a], mx[a]); }
+            }
+        } else {
+            const NodeDbl &l = out[n.leftFirst], &r = out[n.leftFirst + 1];
+            for (int a = 0; a < 3; a++) { n.mn[a] = std::min(l.mn[a], r.mn[a]); n.mx[a] = std::max(l.mx[a], r.mx[a]); }
+        }
+    }
+}
+
+// BLASInstanceEx::Update + InvertTransform (tiny_bvh.h:8432-8472), restated
+void updateInstanceDbl(InstanceDbl& in, const double* bb) {
+    const double* T = in.transform;
+    double* iT = in.invTransform;
+    iT[0] = T[5] * T[10] * T[15] - T[5] * T[11] * T[14] - T[9] * T[6] * T[15] + T[9] * T[7] * T[14] + T[13] * T[6] * T[11] - T[13] * T[7] * T[10];
+    iT[1] = -T[1] * T[10] * T[15] + T[1] * T[11] * T[14] + T[9] * T[2] * T[15] - T[9] * T[3] * T[14] - T[13] * T[2] * T[11] + T[13] * T[3] * T[10];
+    iT[2] = T[1] * T[6] * T[15] - T[1] * T[7] * T[14] - T[5] * T[2] * T[15] + T[5] * T[3] * T[14] + T[13] * T[2] * T[7] - T[13] * T[3] * T[6];
+    iT[3] = -T[1] * T[6] * T[11] + T[1] * T[7] * T[10] + T[5] * T[2] * T[11] - T[5] * T[3] * T[10] - T[9] * T[2] * T[7] + T[9] * T[3] * T[6];
+    iT[4] = -T[4] * T[10] * T[15] + T[4] * T[11] * T[14] + T[8] * T[6] * T[15] - T[8] * T[7] * T[14] - T[12] * T[6] * T[11] + T[12] * T[7] * T[10];
+    iT[5] = T[0] * T[10] * T[15] - T[0] * T[11] * T[14] - T[8] * T[2] * T[15] + T[8] * T[3] * T[14] + T[12] * T[2] * T[11] - T[12] * T[3] * T[10];
+    iT[6] = -T[0] * T[6] * T[15] + T[0] * T[7] * T[14] + T[4] * T[2] * T[15] - T[4] * T[3] * T[14] - T[12] * T[2] * T[7] + T[12] * T[3] * T[6];
+    iT[7] = T[0] * T[6] * T[11] - T[0] * T[7] * T[10] - T[4] * T[2] * T[11] + T[4] * T[3] * T[10] + T[8] * T[2] * T[7] - T[8] * T[3] * T[6];
+    iT[8] = T[4] * T[9] * T[15] - T[4] * T[11] * T[13] - T[8] * T[5] * T[15] + T[8] * T[7] * T[13] + T[12] * T[5] * T[11] - T[12] * T[7] * T[9];
+    iT[9] = -T[0] * T[9] * T[15] + T[0] * T[11] * T[13] + T[8] * T[1] * T[15] - T[8] * T[3] * T[13] - T[12] * T[1] * T[11] + T[12] * T[3] * T[9];
+    iT[10] = T[0] * T[5] * T[15] - T[0] * T[7] * T[13] - T[4] * T[1] * T[15] + T[4] * T[3] * T[13] + T[12] * T[1] * T[7] - T[12] * T[3] * T[5];
+    iT[11] = -T[0] * T[5] * T[11] + T[0] * T[7] * T[9] + T[4] * T[1] * T[11] - T[4] * T[3] * T[9] - T[8] * T[1] * T[7] + T[8] * T[3] * T[5];
+    iT[12] = -T[4] * T[9] * T[14] + T[4] * T[10] * T[13] + T[8] * T[5] * T[14] - T[8] * T[6] * T[13] - T[12] * T[5] * T[10] + T[12] * T[6] * T[9];
+    iT[13] = T[0] * T[9] * T[14] - T[0] * T[10] * T[13] - T[8] * T[1] * T[14] + T[8] * T[2] * T[13] + T[12] * T[1] * T[10] - T[12] * T[2] * T[9];
+    iT[14] = -T[0] * T[5] * T[14] + T[0] * T[6] * T[13] + T[4] * T[1] * T[14] - T[4] * T[2] * T[13] - T[12] * T[1] * T[6] + T[12] * T[2] * T[5];
+    iT[15] = T[0] * T[5] * T[10] - T[0] * T[6] * T[9] - T[4] * T[1] * T[10] + T[4] * T[2] * T[9] + T[8] * T[1] * T[6] - T[8] * T[2] * T[5];
+    const double det = T[0] * iT[0] + T[1] * iT[4] + T[2] * iT[8] + T[3] * iT[12];
+    if (det != 0) {   // (the reference returns here and keeps the unscaled cofactors)
+        const double invdet = 1. / det;
+        for (int i = 0; i < 16; i++) iT[i] *= invdet;
+    }
+    const double far32 = (double)1e30f;   // aabbMin = bvhdbl3( BVH_FAR ): the float constant
+    for (int a = 0; a < 3; a++) { in.aabbMin[a] = far32; in.aabbMax[a] = -far32; }
+    for (int j = 0; j < 8; j++) {
+        const double p[3] = {j & 1 ? bb[3] : bb[0], j & 2 ? bb[4] : bb[1], j & 4 ? bb[5] : bb[2]};
+        double t[3] = {T[0] * p[0] + T[1] * p[1] + T[2] * p[2] + T[3], T[4] * p[0] + T[5] * p[1] + T[6] * p[2] + T[7], T[8] * p[0] + T[9] * p[1] + T[10] * p[2] + T[11]};
+        const double w = T[12] * p[0] + T[13] * p[1] + T[14] * p[2] + T[15];
+        if (w != 1) { const double rw = 1. / w; for (int a = 0; a < 3; a++) t[a] = t[a] * rw; }
+        for (int a = 0; a < 3; a++) {
+            in.aabbMin[a] = in.aabbMin[a] < t[a] ? in.aabbMin[a] : t[a];
+            in.aabbMax[a] = in.aabbMax[a] > t[a] ? in.aabbMax[a] : t[a];
+        }
+    }
+}
+
+}  // namespace
+
+extern "C" {
+
+// ---- uploads ------------------------------------------------------------------------------------------------------------------------
+
+int tbvh_upload_bvh_double(tbvh_context* c, const void* nodes64, uint64_t nNodes, const uint64_t* primIdx, uint64_t nIdx, const void* vertsDbl3, uint64_t nTris,
+                           tbvh_scene** out) {
+    if (!c || !nodes64 || !primIdx || !vertsDbl3 || !out || !nIdx || !nTris) return fail(TBVH_E_INVALID, "tbvh_upload_bvh_double: null/empty argument");
+    if (int r = validateDouble((const NodeDbl*)nodes64, nNodes, primIdx, nIdx, nTris, "tbvh_upload_bvh_double", "n_tris")) return r;
+    TBVH_ENTER(c);
+    tbvh_scene* s = newScene(c, TBVH_LAYOUT_BVH_DOUBLE);
+    if (!s) return fail(TBVH_E_NOMEM, "out of host memory");
+    void *dIdx = nullptr, *dVerts = nullptr;
+    auto bail = [&](int code, const char* what) { if (dIdx) hipFree(dIdx); if (dVerts) hipFree(dVerts); tbvh_free_scene(s); return fail(code, "tbvh_upload_bvh_double: %s", what); };
+    if (hipMalloc((void**)&s->nodes, nNodes * sizeof(NodeDbl)) != hipSuccess || hipMalloc((void**)&s->tris, nIdx * sizeof(TriDbl)) != hipSuccess ||
+        hipMalloc(&dIdx, nIdx * 8) != hipSuccess || hipMalloc(&dVerts, nTris * 72) != hipSuccess)
+        return bail(TBVH_E_NOMEM, "out of device memory");
+    if (hipMemcpyAsync(s->nodes, nodes64, nNodes * sizeof(NodeDbl), hipMemcpyHostToDevice, c->stream) != hipSuccess ||
+        hipMemcpyAsync(dIdx, primIdx, nIdx * 8, hipMemcpyHostToDevice, c->stream) != hipSuccess ||
+        hipMemcpyAsync(dVerts, vertsDbl3, nTris * 72, hipMemcpyHostToDevice, c->stream) != hipSuccess)
+        return bail(TBVH_E_HIP, "copy to the device failed");
+    launch_gather_tris_dbl((const uint64_t*)dIdx, (const double*)dVerts, (TriDbl*)s->tris, nIdx, c->stream);
+    if (hipGetLastError() != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) return bail(TBVH_E_HIP, "triangle gather failed");
+    hipFree(dIdx); hipFree(dVerts);
+    s->nNodes = (uint32_t)nNodes;
+    s->bytes = nNodes * sizeof(NodeDbl) + nIdx * sizeof(TriDbl);
+    *out = s;
+    return 0;
+}
+
+int tbvh_upload_tlas_double(tbvh_context* c, const void* nodes64, uint64_t nNodes, const uint64_t* idx, uint64_t nIdx, const void* instances320, uint64_t nInst,
+                            tbvh_scene* const* blas, uint64_t nBlas, tbvh_scene** out) {
+    if (!c || !nodes64 || !idx || !instances320 || !blas || !out || !nIdx || !nInst || !nBlas) return fail(TBVH_E_INVALID, "tbvh_upload_tlas_double: null/empty argument");
+    for (uint64_t i = 0; i < nBlas; i++) {
+        const tbvh_scene* b = blas[i];
+        if (!b || b->ctx != c || b->isTlas || b->zombie) return fail(TBVH_E_INVALID, "tbvh_upload_tlas_double: BLAS %llu is null, freed, a TLAS, or from another context", (unsigned long long)i);
+        if (!isDouble(b)) return fail(TBVH_E_INVALID, "tbvh_upload_tlas_double: BLAS %llu has layout %d; every BLAS must be a BVH_DOUBLE scene", (unsigned long long)i, b->layout);
+    }
+    if (int r = validateDouble((const NodeDbl*)nodes64, nNodes, idx, nIdx, nInst, "tbvh_upload_tlas_double", "n_inst")) return r;
+    const InstanceDbl* inst = (const InstanceDbl*)instances320;
+    for (uint64_t i = 0; i < nInst; i++)
+        if (inst[i].blasIdx >= nBlas)
+            return fail(TBVH_E_FORMAT, "tbvh_upload_tlas_double: instance %llu: blasIdx %llu >= n_blas = %llu", (unsigned long long)i, (unsigned long long)inst[i].blasIdx, (unsigned long long)nBlas);
+    TBVH_ENTER(c);
+    std::vector<BlasDbl> descs(nBlas);
+    for (uint64_t i = 0; i < nBlas; i++) descs[i] = BlasDbl{(const NodeDbl*)blas[i]->nodes, (const TriDbl*)blas[i]->tris};
+    tbvh_scene* s = newScene(c, TBVH_LAYOUT_BVH_DOUBLE);
+    if (!s) return fail(TBVH_E_NOMEM, "out of host memory");
+    s->isTlas = true; s->nTlasNodes = nNodes; s->nTlasIdx = nIdx; s->nInst = nInst; s->nBlas = nBlas; s->nNodes = (uint32_t)nNodes;
+    const uint64_t oIdx = align16(nNodes * sizeof(NodeDbl)), oInst = oIdx + align16(nIdx * 8), oBlas = oInst + nInst * sizeof(InstanceDbl), total = oBlas + nBlas * sizeof(BlasDbl);
+    if (hipMalloc((void**)&s->nodes, total) != hipSuccess) { tbvh_free_scene(s); return fail(TBVH_E_NOMEM, "tbvh_upload_tlas_double: out of device memory"); }
+    char* base = (char*)s->nodes;
+    if (hipMemcpyAsync(base, nodes64, nNodes * sizeof(NodeDbl), hipMemcpyHostToDevice, c->stream) != hipSuccess ||
+        hipMemcpyAsync(base + oIdx, idx, nIdx * 8, hipMemcpyHostToDevice, c->stream) != hipSuccess ||
+        hipMemcpyAsync(base + oInst, inst, nInst * sizeof(InstanceDbl), hipMemcpyHostToDevice, c->stream) != hipSuccess ||
+        hipMemcpyAsync(base + oBlas, descs.data(), nBlas * sizeof(BlasDbl), hipMemcpyHostToDevice, c->stream) != hipSuccess ||
+        hipStreamSynchronize(c->stream) != hipSuccess) {
+        tbvh_free_scene(s);
+        return fail(TBVH_E_HIP, "tbvh_upload_tlas_double: copy to the device failed");
+    }
+    for (uint64_t i = 0; i < nBlas; i++) { s->blasList.push_back(blas[i]); blas[i]->usedBy.push_back(s); }   // (the BLASes outlive the TLAS: tbvh_free_scene)
+    s->bytes = total;
+    *out = s;
+    return 0;
+}
+
+// ---- queries ----------------------------------------------------------------------------------------------------------------------
+
+int tbvh_intersect_ex_device(tbvh_scene* s, void* dRays, uint64_t n) {
+    if (!s || (!dRays && n)) return fail(TBVH_E_INVALID, "tbvh_intersect_ex_device: null argument");
+    if (!isDouble(s)) return fail(TBVH_E_INVALID, "tbvh_intersect_ex_device: scene layout %d is not BVH_DOUBLE (RayEx queries need a BVH_Double scene)", s->layout);
+    if (((uintptr_t)dRays) & 15) return fail(TBVH_E_INVALID, "tbvh_intersect_ex_device: ray array must be 16-byte aligned");
+    return launchDouble(s, (RayExRec*)dRays, n, nullptr);
+}
+
+int tbvh_occluded_ex_device(tbvh_scene* s, const void* dRays, uint64_t n, uint8_t* dOcc) {
+    if (!s || ((!dRays || !dOcc) && n)) return fail(TBVH_E_INVALID, "tbvh_occluded_ex_device: null argument");
+    if (!isDouble(s)) return fail(TBVH_E_INVALID, "tbvh_occluded_ex_device: scene layout %d is not BVH_DOUBLE (RayEx queries need a BVH_Double scene)", s->layout);
+    if (((uintptr_t)dRays) & 15) return fail(TBVH_E_INVALID, "tbvh_occluded_ex_device: ray array must be 16-byte aligned");
+    return launchDouble(s, (RayExRec*)dRays, n, dOcc);
+}
+
+int tbvh_intersect_ex(tbvh_scene* s, void* rays, uint64_t n) {
+    if (!s || (!rays && n)) return fail(TBVH_E_INVALID, "tbvh_intersect_ex: null argument");
+    if (!isDouble(s)) return fail(TBVH_E_INVALID, "tbvh_intersect_ex: scene layout %d is not BVH_DOUBLE (RayEx queries need a BVH_Double scene)", s->layout);
+    if (n == 0) return 0;
+    return hostQueryEx(s, rays, n, nullptr, "tbvh_intersect_ex");
+}
+
+int tbvh_occluded_ex(tbvh_scene* s, const void* rays, uint64_t n, uint8_t* occ) {
+    if (!s || ((!rays || !occ) && n)) return fail(TBVH_E_INVALID, "tbvh_occluded_ex: null argument");
+    if (!isDouble(s)) return fail(TBVH_E_INVALID, "tbvh_occluded_ex: scene layout %d is not BVH_DOUBLE (RayEx queries need a BVH_Double scene)", s->layout);
+    if (n == 0) return 0;
+    return hostQueryEx(s, (void*)rays, n, occ, "tbvh_occluded_ex");
+}
+
+// ---- host builders ------------------------------------------------------------------------------------------------------------------
+
+int tbvh_host_build_double(const void* vertsDbl3, uint64_t nTris, tbvh_hostbvh** out) {
+    if (!vertsDbl3 || !out || nTris == 0) return fail(TBVH_E_INVALID, "tbvh_host_build_double: null/empty argument");
+    if (nTris > 0x3fffffffull) return fail(TBVH_E_INVALID, "tbvh_host_build_double: too many triangles");
+    const double* v = (const double*)vertsDbl3;
+    tbvh_hostbvh* h = new (std::nothrow) tbvh_hostbvh;
+    if (!h) return fail(TBVH_E_NOMEM, "out of host memory");
+    h->layout = TBVH_LAYOUT_BVH_DOUBLE;
+    try {
+        double lo[3] = {kDblFarHost, kDblFarHost, kDblFarHost}, hi[3] = {-kDblFarHost, -kDblFarHost, -kDblFarHost};
+        for (uint64_t i = 0; i < nTris * 3; i++)
+            for (int a = 0; a < 3; a++) { lo[a] = std::min(lo[a], v[i * 3 + a]); hi[a] = std::max(hi[a], v[i * 3 + a]); }
+        double ctr[3];
+        for (int a = 0; a < 3; a++) ctr[a] = lo[a] * 0.5 + hi[a] * 0.5;
+        std::vector<Vec4> f(nTris * 3);
+        for (uint64_t i = 0; i < nTris * 3; i++) f[i] = Vec4{(float)(v[i * 3] - ctr[0]), (float)(v[i * 3 + 1] - ctr[1]), (float)(v[i * 3 + 2] - ctr[2]), 0.f};
+        BuildParams bp;
+        bp.splitBudget = 0.f;   // every triangle in exactly one leaf
+        build_bvh2(f.data(), (uint32_t)nTris, bp, h->bvh2);
+        doubleFromTopology(h->bvh2, [&](uint64_t p, double* mn, double* mx) {
+            for (int a = 0; a < 3; a++) {
+                const double x = v[p * 9 + a], y = v[p * 9 + 3 + a], z = v[p * 9 + 6 + a];
+                mn[a] = std::min(x, std::min(y, z)); mx[a] = std::max(x, std::max(y, z));
+            }
+        }, h->dnodes);
+        h->didx.assign(h->bvh2.primIdx.begin(), h->bvh2.primIdx.end());
+    } catch (const std::bad_alloc&) {
+        delete h;
+        return fail(TBVH_E_NOMEM, "out of host memory while building");
+    }
+    *out = h;
+    return 0;
+}
+
+int tbvh_host_build_tlas_double(void* instances320, uint64_t nInst, const double* blasBounds6, uint64_t nBlas, tbvh_hostbvh** out) {
+    if (!instances320 || !blasBounds6 || !out || nInst == 0 || nBlas == 0) return fail(TBVH_E_INVALID, "tbvh_host_build_tlas_double: null/empty argument");
+    if (nInst > 0x3fffffffull) return fail(TBVH_E_INVALID, "tbvh_host_build_tlas_double: too many instances");
+    InstanceDbl* inst = (InstanceDbl*)instances320;
+    for (uint64_t i = 0; i < nInst; i++)
+        if (inst[i].blasIdx >= nBlas) return fail(TBVH_E_INVALID, "tbvh_host_build_tlas_double: instance %llu: blasIdx %llu out of range", (unsigned long long)i, (unsigned long long)inst[i].blasIdx);
+    tbvh_hostbvh* h = new (std::nothrow) tbvh_hostbvh;
+    if (!h) return fail(TBVH_E_NOMEM, "out of host memory");
+    h->layout = TBVH_LAYOUT_BVH_DOUBLE;
+    try {
+        double lo[3] = {kDblFarHost, kDblFarHost, kDblFarHost}, hi[3] = {-kDblFarHost, -kDblFarHost, -kDblFarHost};
+        for (uint64_t i = 0; i < nInst; i++) {
+            updateInstanceDbl(inst[i], blasBounds6 + 6 * inst[i].blasIdx);
+            for (int a = 0; a < 3; a++) { lo[a] = std::min(lo[a], inst[i].aabbMin[a]); hi[a] = std::max(hi[a], inst[i].aabbMax[a]); }
+        }
+        double ctr[3];
+        for (int a = 0; a < 3; a++) ctr[a] = lo[a] * 0.5 + hi[a] * 0.5;
+        std::vector<float> boxes(nInst * 6);
+        for (uint64_t i = 0; i < nInst; i++)
+            for (int a = 0; a < 3; a++) { boxes[i * 6 + a] = (float)(inst[i].aabbMin[a] - ctr[a]); boxes[i * 6 + 3 + a] = (float)(inst[i].aabbMax[a] - ctr[a]); }
+        BuildParams bp; bp.maxLeafTris = 1; bp.threads = 1;   // (as tbvh_host_build_tlas)
+        build_bvh2_boxes(boxes.data(), (uint32_t)nInst, bp, h->bvh2);
+        doubleFromTopology(h->bvh2, [&](uint64_t p, double* mn, double* mx) {
+            for (int a = 0; a < 3; a++) { mn[a] = inst[p].aabbMin[a]; mx[a] = inst[p].aabbMax[a]; }
+        }, h->dnodes);
+        h->didx.assign(h->bvh2.primIdx.begin(), h->bvh2.primIdx.end());
+    } catch (const std::bad_alloc&) {
+        delete h;
+        return fail(TBVH_E_NOMEM, "out of host memory while building");
+    }
+    *out = h;
+    return 0;
+}
+
+}  // extern "C"

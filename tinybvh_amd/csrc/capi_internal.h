@@ -36,6 +36,14 @@ namespace tbvh_capi {
 int fail(int code, const char* fmt, ...);   // sets tbvh_last_error() of the calling thread, returns code
 }  // namespace tbvh_capi
 
+// A BVH_DOUBLE scene (capi_double.hip) answers tbvh_intersect_ex / tbvh_occluded_ex (and free / layout / bytes) only: every other entry point
+// that takes a scene refuses it with this, before it touches the scene's memory or launches anything.
+#define TBVH_REFUSE_DOUBLE(scene, who)                                                                                              \
+    do {                                                                                                                            \
+        if ((scene) && (scene)->layout == TBVH_LAYOUT_BVH_DOUBLE)                                                                   \
+            return tbvh_capi::fail(TBVH_E_INVALID, "%s: a BVH_DOUBLE scene takes tbvh_intersect_ex / tbvh_occluded_ex only", who);   \
+    } while (0)
+
 #define HIP_TRY(expr)                                                                        \
     do {                                                                                     \
         hipError_t e_ = (expr);                                                              \
@@ -229,6 +237,8 @@ struct tbvh_hostbvh {
     BVH2 bvh2;
     std::vector<NodeAL> al;
     std::vector<Vec4> blocksA, blocksB;
+    std::vector<NodeDbl> dnodes;     // TBVH_LAYOUT_BVH_DOUBLE (capi_double.hip): BVH_Double::bvhNode ...
+    std::vector<uint64_t> didx;      // ... and primIdx (TLAS: instance indices)
 };
 
 struct HostPipe {

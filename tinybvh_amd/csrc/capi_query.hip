@@ -462,24 +462,28 @@ extern "C" {
 // ---- queries ---------------------------------------------------------------------------
 
 int tbvh_intersect_device(tbvh_scene* s, void* dRays, uint64_t n) {
+    TBVH_REFUSE_DOUBLE(s, "tbvh_intersect_device");
     if (!s || (!dRays && n)) return fail(TBVH_E_INVALID, "tbvh_intersect_device: null argument");
     if (((uintptr_t)dRays) & 15) return fail(TBVH_E_INVALID, "ray array must be 16-byte aligned");
     return launchQuery(s, (RayRec*)dRays, n, nullptr);
 }
 
 int tbvh_intersect_device_fresh(tbvh_scene* s, void* dRays, uint64_t n, float tmax) {
+    TBVH_REFUSE_DOUBLE(s, "tbvh_intersect_device_fresh");
     if (!s || (!dRays && n)) return fail(TBVH_E_INVALID, "tbvh_intersect_device_fresh: null argument");
     if (((uintptr_t)dRays) & 15) return fail(TBVH_E_INVALID, "ray array must be 16-byte aligned");
     return launchQuery(s, (RayRec*)dRays, n, nullptr, true, tmax);
 }
 
 int tbvh_occluded_device(tbvh_scene* s, const void* dRays, uint64_t n, uint8_t* dOcc) {
+    TBVH_REFUSE_DOUBLE(s, "tbvh_occluded_device");
     if (!s || ((!dRays || !dOcc) && n)) return fail(TBVH_E_INVALID, "tbvh_occluded_device: null argument");
     if (((uintptr_t)dRays) & 15) return fail(TBVH_E_INVALID, "ray array must be 16-byte aligned");
     return launchQuery(s, (RayRec*)dRays, n, dOcc);
 }
 
 int tbvh_intersect(tbvh_scene* s, void* rays, uint64_t n, uint32_t stride) {
+    TBVH_REFUSE_DOUBLE(s, "tbvh_intersect");
     if (!s || (!rays && n)) return fail(TBVH_E_INVALID, "tbvh_intersect: null argument");
     if (stride < 64 || (stride & 3)) return fail(TBVH_E_INVALID, "stride must be >= 64 and a multiple of 4 (got %u)", stride);
     if (n == 0) return 0;
@@ -489,6 +493,7 @@ int tbvh_intersect(tbvh_scene* s, void* rays, uint64_t n, uint32_t stride) {
 }
 
 int tbvh_occluded(tbvh_scene* s, const void* rays, uint64_t n, uint32_t stride, uint8_t* occ) {
+    TBVH_REFUSE_DOUBLE(s, "tbvh_occluded");
     if (!s || ((!rays || !occ) && n)) return fail(TBVH_E_INVALID, "tbvh_occluded: null argument");
     if (stride < 64 || (stride & 3)) return fail(TBVH_E_INVALID, "stride must be >= 64 and a multiple of 4 (got %u)", stride);
     if (n == 0) return 0;
@@ -544,6 +549,7 @@ int shardedQuery(tbvh_scene* const* scenes, uint32_t nDev, void* rays, uint64_t 
     if (stride < 64 || (stride & 3)) return fail(TBVH_E_INVALID, "stride must be >= 64 and a multiple of 4 (got %u)", stride);
     for (uint32_t i = 0; i < nDev; i++) {
         if (!scenes[i]) return fail(TBVH_E_INVALID, "%s: scene %u is null", who, i);
+        TBVH_REFUSE_DOUBLE(scenes[i], who);
         if (scenes[i]->layout != scenes[0]->layout || scenes[i]->isTlas != scenes[0]->isTlas) return fail(TBVH_E_INVALID, "%s: scene %u is not a replica of scene 0 (layout differs)", who, i);
         for (uint32_t j = 0; j < i; j++) if (scenes[j]->ctx == scenes[i]->ctx) return fail(TBVH_E_INVALID, "%s: scenes %u and %u share a context (one context, i.e. one stream and staging area, per shard)", who, j, i);
     }
@@ -586,6 +592,7 @@ int shardedDeviceQuery(tbvh_scene* const* scenes, uint32_t nDev, void* const* dR
     if (!scenes || !nDev || !dRays || !nRays) return fail(TBVH_E_INVALID, "%s: null argument", who);
     for (uint32_t i = 0; i < nDev; i++) {
         if (!scenes[i]) return fail(TBVH_E_INVALID, "%s: scenes[%u] is null", who, i);
+        TBVH_REFUSE_DOUBLE(scenes[i], who);
         if (nRays[i] && (!dRays[i] || (dOcc && !dOcc[i]))) return fail(TBVH_E_INVALID, "%s: null ray / output pointer for device %u", who, i);
         for (uint32_t k = 0; k < i; k++) if (scenes[k]->ctx == scenes[i]->ctx) return fail(TBVH_E_INVALID, "%s: scenes %u and %u share a context (one scene per context)", who, k, i);
     }

@@ -486,6 +486,7 @@ int tbvh_upload_tlas(tbvh_context* c, const void* nodes64, uint64_t nNodes, cons
 }
 
 int tbvh_update_tlas(tbvh_scene* s, const void* nodes64, uint64_t nNodes, const uint32_t* idx, uint64_t nIdx, const void* inst, uint64_t nInst) {
+    TBVH_REFUSE_DOUBLE(s, "tbvh_update_tlas");
     if (!s || !s->isTlas || !nodes64 || !idx || !inst || !nNodes || !nIdx || !nInst) return fail(TBVH_E_INVALID, "tbvh_update_tlas: not a TLAS or null/empty argument");
     TBVH_ENTER(s->ctx);
     return tlasCopy(s, nodes64, nNodes, idx, nIdx, inst, nInst);
@@ -495,6 +496,7 @@ int tbvh_update_tlas(tbvh_scene* s, const void* nodes64, uint64_t nNodes, const 
 // (BVH::Refit tiny_bvh.h:3055-3093 + X::ConvertFrom again: the reference's flow for animated geometry.)  The device allocations, the scene
 // handle and the pointers the TLASes over this BLAS hold stay as they are; the library's derived copies follow.
 int tbvh_update_bvh_gpu(tbvh_scene* s, const void* nodes64, uint64_t nNodes, const uint32_t* primIdx, uint64_t nIdx, const void* verts16, uint64_t nTris) {
+    TBVH_REFUSE_DOUBLE(s, "tbvh_update_bvh_gpu");
     if (!s || s->isTlas || s->layout != TBVH_LAYOUT_BVH_GPU || !nodes64 || !primIdx || !verts16 || !nNodes) return fail(TBVH_E_INVALID, "tbvh_update_bvh_gpu: not a BVH_GPU scene or null/empty argument");
     if (nNodes * 4 > s->capNodeBlocks || nIdx * 3 > s->capTriBlocks) return fail(TBVH_E_INVALID, "tbvh_update_bvh_gpu: the blob (%llu nodes, %llu indices) is larger than the one uploaded: free the scene and upload", (unsigned long long)nNodes, (unsigned long long)nIdx);
     if (const char* why = validate_bvh_gpu((const NodeAL*)nodes64, nNodes, nIdx)) return fail(why == kValidateNoMemory ? TBVH_E_NOMEM : TBVH_E_FORMAT, "%s", why);
@@ -517,6 +519,7 @@ int tbvh_update_bvh_gpu(tbvh_scene* s, const void* nodes64, uint64_t nNodes, con
 }
 
 int tbvh_update_bvh4_gpu(tbvh_scene* s, const void* blocks16, uint64_t nBlocks) {
+    TBVH_REFUSE_DOUBLE(s, "tbvh_update_bvh4_gpu");
     if (!s || s->isTlas || s->layout != TBVH_LAYOUT_BVH4_GPU || !blocks16 || nBlocks < 4) return fail(TBVH_E_INVALID, "tbvh_update_bvh4_gpu: not a BVH4_GPU scene or null/empty argument");
     if (nBlocks > s->capNodeBlocks) return fail(TBVH_E_INVALID, "tbvh_update_bvh4_gpu: the blob (%llu blocks) is larger than the one uploaded (%llu): free the scene and upload", (unsigned long long)nBlocks, (unsigned long long)s->capNodeBlocks);
     if (const char* why = validate_bvh4_gpu((const Vec4*)blocks16, nBlocks)) return fail(why == kValidateNoMemory ? TBVH_E_NOMEM : TBVH_E_FORMAT, "%s", why);
@@ -567,6 +570,7 @@ static int updateCwbvhImpl(tbvh_scene* s, const void* nodes16, uint64_t nNodeBlo
 }
 
 int tbvh_update_cwbvh(tbvh_scene* s, const void* nodes16, uint64_t nNodeBlocks, const void* tris16, uint64_t nTriBlocks) {
+    TBVH_REFUSE_DOUBLE(s, "tbvh_update_cwbvh");
     if (s && !s->isTlas && (s->wide4 || s->pendingCopies)) {   // the 4-wide copy TLASes enter this BLAS through is of the old tree (also if the update is refused: harmless)
         TBVH_ENTER(s->ctx);
         dropCopiesAfterUpdate(s);
@@ -734,6 +738,7 @@ int refreshBlasDescs(tbvh_scene* b) {
 }  // namespace
 
 int tbvh_set_opacity_micromaps(tbvh_scene* s, const uint32_t* mapData, uint32_t N, uint64_t nTris, int onDevice) {
+    TBVH_REFUSE_DOUBLE(s, "tbvh_set_opacity_micromaps");
     if (!s || s->isTlas) return fail(TBVH_E_INVALID, "tbvh_set_opacity_micromaps: not a BLAS scene (set the maps on the BLASes before uploading their TLAS)");
     tbvh_context* c = s->ctx;
     TBVH_ENTER(c);
@@ -767,6 +772,7 @@ int tbvh_set_opacity_micromaps(tbvh_scene* s, const uint32_t* mapData, uint32_t 
 }
 
 int tbvh_scene_download(tbvh_scene* s, int which, void* dst, uint64_t capBytes, uint64_t* bytesOut) {
+    TBVH_REFUSE_DOUBLE(s, "tbvh_scene_download");
     if (!s || s->isTlas || (which != 0 && which != 1)) return fail(TBVH_E_INVALID, "tbvh_scene_download: not a BLAS scene or bad blob selector");
     tbvh_context* c = s->ctx;
     TBVH_ENTER(c);
@@ -799,6 +805,7 @@ bool refitDropsCopies(tbvh_scene* s) {
 }  // namespace
 
 int tbvh_refit(tbvh_scene* s, const void* verts16, uint64_t nTris, int onDevice) {
+    TBVH_REFUSE_DOUBLE(s, "tbvh_refit");
     if (!s || !verts16 || !nTris) return fail(TBVH_E_INVALID, "tbvh_refit: null/empty argument");
     if (s->isTlas) return fail(TBVH_E_INVALID, "tbvh_refit: a TLAS is rebuilt with tbvh_rebuild_tlas_device / tbvh_update_tlas");
     tbvh_context* c = s->ctx;
@@ -859,6 +866,7 @@ int tbvh_refit(tbvh_scene* s, const void* verts16, uint64_t nTris, int onDevice)
 }
 
 int tbvh_rebuild_tlas_device(tbvh_scene* s, const void* transforms, int onDevice, const float* blasBounds6, uint64_t nBlas) {
+    TBVH_REFUSE_DOUBLE(s, "tbvh_rebuild_tlas_device");
     if (!s || !s->isTlas) return fail(TBVH_E_INVALID, "tbvh_rebuild_tlas_device: not a TLAS");
     tbvh_context* c = s->ctx;
     TBVH_ENTER(c);
@@ -907,6 +915,7 @@ int tbvh_rebuild_tlas_device(tbvh_scene* s, const void* transforms, int onDevice
 
 int tbvh_tlas_download(tbvh_scene* s, void* nodes64, uint64_t capNodes, uint32_t* idx, uint64_t capIdx, void* instances192, uint64_t capInst,
                        uint64_t* nNodesOut) {
+    TBVH_REFUSE_DOUBLE(s, "tbvh_tlas_download");
     if (!s || !s->isTlas) return fail(TBVH_E_INVALID, "tbvh_tlas_download: not a TLAS");
     tbvh_context* c = s->ctx;
     TBVH_ENTER(c);
@@ -977,6 +986,7 @@ int tbvh_debug_coherent_schedule(tbvh_scene* s, int anyhit, uint32_t out[4]) {
 
 // ---- the coherent-batch schedule as something a caller can read, keep and give back -------------------------------------------------------
 int tbvh_scene_get_schedule_hint(tbvh_scene* s, tbvh_schedule_hint* out) {
+    TBVH_REFUSE_DOUBLE(s, "tbvh_scene_get_schedule_hint");
     if (!s || !out) return fail(TBVH_E_INVALID, "tbvh_scene_get_schedule_hint: null argument");
     TBVH_LOCK(s->ctx);
     std::memset(out, 0, sizeof *out);
@@ -992,6 +1002,7 @@ int tbvh_scene_get_schedule_hint(tbvh_scene* s, tbvh_schedule_hint* out) {
 }
 
 int tbvh_scene_set_schedule_hint(tbvh_scene* s, const tbvh_schedule_hint* hint) {
+    TBVH_REFUSE_DOUBLE(s, "tbvh_scene_set_schedule_hint");
     if (!s || !hint) return fail(TBVH_E_INVALID, "tbvh_scene_set_schedule_hint: null argument");
     for (int k = 0; k < 3; k++) if (hint->closest_hit[k] > 3 || hint->any_hit[k] > 3) return fail(TBVH_E_INVALID, "tbvh_scene_set_schedule_hint: entries are 0 (measure), 1 (deferred + gated), 2 (strict) or 3 (one traversal per wave)");
     if (hint->reserved[0] > 3 || hint->reserved[1] > 3) return fail(TBVH_E_INVALID, "tbvh_scene_set_schedule_hint: entries are 0 (measure), 1 (deferred + gated), 2 (strict) or 3 (one traversal per wave)");
@@ -1021,6 +1032,7 @@ int tbvh_set_variant(tbvh_scene* s, int v) {
 }
 
 int tbvh_cwbvh_set_hybrid(tbvh_scene* s, int64_t packedNodes) {
+    TBVH_REFUSE_DOUBLE(s, "tbvh_cwbvh_set_hybrid");
     if (!s || s->isTlas || s->layout != TBVH_LAYOUT_CWBVH) return fail(TBVH_E_INVALID, "tbvh_cwbvh_set_hybrid: not a BVH8_CWBVH scene");
     tbvh_context* c = s->ctx;
     TBVH_ENTER(c);

@@ -121,6 +121,15 @@ __device__ __forceinline__ bool hit_wins(float t, uint32_t prim, uint32_t inst, 
     return !found || t < best.x || prim < as_u32(best.w) || (prim == as_u32(best.w) && inst < bestInst);
 }
 
+// The same rule for BVH_Double scenes (kernels_double.hip): the slack of the box culls is again eight ulps, 2^-49 in double, and a
+// candidate that tri_test_dbl has accepted against the closest hit so far replaces it iff it is strictly closer or, at EQUAL distance, a hit
+// has been found already and the candidate has the smaller primitive index, then the smaller instance.  The reference's own test is strict
+// (t < ray.hit.t, tiny_bvh.h:8194): the ray's tmax itself is never a hit, and among equal distances the FIRST found stays.
+__device__ __host__ __forceinline__ double cull_bound_dbl(double t) { return t * 1.0000000000000017763568394002504646778106689453125; }
+__device__ __host__ __forceinline__ bool hit_wins_dbl(double t, uint64_t prim, uint64_t inst, bool found, double bestT, uint64_t bestPrim, uint64_t bestInst) {
+    return t < bestT || (found && t == bestT && (prim < bestPrim || (prim == bestPrim && inst < bestInst)));
+}
+
 // Kernel launch parameters common to the query kernels.
 struct QueryArgs {
     RayRec* rays;          // device, 64-byte stride

@@ -39,6 +39,42 @@ void launch_tlas8(bool anyhit, int variant, const float4* tlasNodes, const uint3
                   uint32_t* status, uint32_t blocks, hipStream_t s, uint32_t blocks7, bool mixed = false);
 void launch_tlas2(bool anyhit, int variant, const float4* tlasNodes, const uint32_t* tlasIdx, const float4* instances, const BlasDesc* blas, const QueryArgs& q,
                   uint32_t* status, uint32_t blocks, hipStream_t s, uint32_t blocks7);   // BVH_GPU BLASes (kernels_tlas2.hip)
+// BVH_Double scenes (kernels_double.hip; records as tinybvh defines them, tiny_bvh.h:733-761, 1035-1090, 1462-1474)
+struct __attribute__((aligned(16))) RayExRec {   // tinybvh::RayEx, 128 bytes
+    double O[3], D[3], rD[3];
+    double t, u, v;
+    uint64_t inst, prim, instIdx, mask;
+};
+static_assert(sizeof(RayExRec) == 128, "RayEx is 128 bytes");
+struct NodeDbl { double mn[3], mx[3]; uint64_t leftFirst, triCount; };   // BVH_Double::BVHNode, 64 bytes
+static_assert(sizeof(NodeDbl) == 64, "BVH_Double::BVHNode is 64 bytes");
+struct TriDbl { double v0[3], e1[3], e2[3]; uint64_t prim; };             // gathered at upload: one per primIdx entry, 80 bytes
+static_assert(sizeof(TriDbl) == 80, "double triangle record is 80 bytes");
+struct InstanceDbl {                                                         // BLASInstanceEx, 320 bytes
+    double transform[16], invTransform[16];
+    double aabbMin[3]; uint64_t blasIdx;
+    double aabbMax[3]; uint64_t mask;
+};
+static_assert(sizeof(InstanceDbl) == 320, "BLASInstanceEx is 320 bytes");
+struct BlasDbl { const NodeDbl* nodes; const TriDbl* tris; };   // one per BLAS of a double TLAS
+struct DoubleArgs {
+    RayExRec* rays;
+    uint64_t nRays;
+    uint8_t* occluded;     // any-hit output, 1 byte per ray
+    uint32_t* spill;       // stack spill area and its entries per lane
+    uint32_t spillStride;
+    uint32_t* counter;     // ray-pool counters of this launch / of the next one (ray_pool.h)
+    uint32_t* counterNext;
+    uint32_t poolParts;
+    const NodeDbl* nodes;  // BLAS: its nodes and records; TLAS: the TLAS nodes, its instance indices, the instances and the BLASes
+    const TriDbl* tris;
+    const uint64_t* tlasIdx;
+    const InstanceDbl* inst;
+    const BlasDbl* blas;
+};
+void launch_double(bool anyhit, bool tlas, const DoubleArgs& q, uint32_t* status, uint32_t blocks, hipStream_t s);
+void launch_gather_tris_dbl(const uint64_t* primIdx, const double* verts, TriDbl* out, uint64_t nIdx, hipStream_t s);
+
 // device TLAS rebuild (kernels_tlasbuild.hip)
 size_t tlas_build_scratch_bytes(uint32_t n, size_t* sortTempBytes);
 hipError_t launch_tlas_rebuild(float4* tlasNodes, uint32_t* tlasIdx, float4* instances, const float* transformsDev, const float* blasBoundsDev,
