@@ -98,6 +98,48 @@ private:
     tbvh_context* ctx = nullptr;
 };
 
+// VoxelSet (tiny_bvh.h:988-1030) on the device, with the reference's method names: Set fills a brick map on the host exactly as VoxelSet::Set
+// does (tiny_bvh.h:3786-3807: the same brick numbering, so the same arrays), UpdateTopGrid (3809-3827) completes it and uploads it
+// (tbvh_upload_voxelset); Intersect / IsOccluded trace a host tinybvh::Ray[] in place.  The reference's own VoxelSet keeps its arrays private,
+// so this class holds its own.  Handle() is the scene a TLAS takes as a BLAS (tbvh_upload_tlas: every BLAS a voxel set; bounds the unit cube).
+// One deviation, DESIGN.md par. 10: a voxel hit is recorded only if it beats the ray's hit.t (the reference's Intersect records the first
+// filled voxel whatever hit.t holds).
+class VoxelSet {
+public:
+    static constexpr uint32_t objectDim = 256;
+    explicit VoxelSet(int device = 0, tbvh_context* own = nullptr) : ctx(own ? own : Context(device)), grid(32768u, 0u), brick(512u, 0u), top(16u, 0u) {}
+    VoxelSet(const VoxelSet&) = delete;
+    VoxelSet& operator=(const VoxelSet&) = delete;
+    ~VoxelSet() { if (s) tbvh_free_scene(s); }
+    void Set(const uint32_t x, const uint32_t y, const uint32_t z, const uint32_t v) {
+        const uint32_t g = x / 8 + (y / 8) * 32 + (z / 8) * 1024;
+        uint32_t b = grid[g];
+        if (!b) { b = grid[g] = (uint32_t)(brick.size() / 512); brick.resize(brick.size() + 512, 0u); }
+        brick[(size_t)b * 512 + (x & 7) + (y & 7) * 8 + (z & 7) * 64] = v;
+    }
+    // the top grid, then the upload (again after further Set calls: the set is re-uploaded; TLASes over the old upload keep the old one)
+    void UpdateTopGrid() {
+        for (uint32_t& w : top) w = 0;
+        for (uint32_t x = 0; x < 8; x++) for (uint32_t y = 0; y < 8; y++) for (uint32_t z = 0; z < 8; z++) {
+            bool has = false;
+            for (uint32_t u = 0; u < 4 && !has; u++) for (uint32_t v = 0; v < 4 && !has; v++) for (uint32_t w = 0; w < 4 && !has; w++)
+                has = grid[(x * 4 + u) + (y * 4 + v) * 32 + (z * 4 + w) * 1024] != 0;
+            if (has) { const uint32_t ti = x + y * 8 + z * 64; top[ti >> 5] |= 1u << (ti & 31); }
+        }
+        if (s) { tbvh_free_scene(s); s = nullptr; }
+        Check(tbvh_upload_voxelset(ctx, grid.data(), brick.data(), brick.size() / 512, top.data(), &s), "tbvh_upload_voxelset");
+    }
+    // VoxelSet::Intersect( Ray& ) / IsOccluded( const Ray& ) over a host tinybvh::Ray[] (after UpdateTopGrid)
+    void Intersect(tinybvh::Ray* rays, size_t n) { Check(tbvh_intersect(s, rays, n, sizeof(tinybvh::Ray)), "tbvh_intersect"); }
+    void IsOccluded(const tinybvh::Ray* rays, size_t n, uint8_t* out) { Check(tbvh_occluded(s, rays, n, sizeof(tinybvh::Ray), out), "tbvh_occluded"); }
+    tbvh_scene* Handle() const { return s; }
+    tbvh_context* Ctx() const { return ctx; }
+private:
+    tbvh_context* ctx;
+    tbvh_scene* s = nullptr;
+    std::vector<uint32_t> grid, brick, top;   // 32^3 brick indices, the bricks in use (brick 0 the empty one), 512 occupancy bits
+};
+
 // tinyocl::Buffer( bytes ) for a ray array that is traced many times (tiny_bvh_speedtest.cpp:1101-1108 wraps its ray array in one per GPU block): page-locked
 // host memory of the library's for the object's lifetime (tbvh_pinned_malloc); a PACKED 64-byte ray array in it goes up by DMA straight from there.
 class PinnedBuffer {

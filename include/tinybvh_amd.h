@@ -46,7 +46,7 @@
 extern "C" {
 #endif
 
-#define TBVH_ABI_VERSION 5   /* 5 (additions, nothing changed: BVH_Double scenes — TBVH_LAYOUT_BVH_DOUBLE, tbvh_upload_bvh_double / _tlas_double, tbvh_intersect_ex / _occluded_ex (+ _device), tbvh_host_build_double / _tlas_double); 5: tbvh_pinned_malloc / _free, tbvh_scene_get / _set_schedule_hint, tbvh_measure_link_bandwidth, TBVH_BUILD_SPLIT_TRIANGLES / _WHOLE_TRIANGLES, development aids moved to tinybvh_amd_debug.h (nothing removed from the library); 4: tbvh_update_bvh_gpu / _bvh4_gpu / _cwbvh, tbvh_time_history, contexts are thread-safe; 3: deterministic ties, tbvh_bin_rays_device, tbvh_cwbvh_set_hybrid, device-resident multi-device calls */
+#define TBVH_ABI_VERSION 5   /* 5 (additions, nothing changed: VoxelSet scenes — TBVH_LAYOUT_VOXELSET, tbvh_upload_voxelset / _voxelset_dense, tbvh_host_build_voxelset, TLASes over voxel sets); 5 (additions, nothing changed: BVH_Double scenes — TBVH_LAYOUT_BVH_DOUBLE, tbvh_upload_bvh_double / _tlas_double, tbvh_intersect_ex / _occluded_ex (+ _device), tbvh_host_build_double / _tlas_double); 5: tbvh_pinned_malloc / _free, tbvh_scene_get / _set_schedule_hint, tbvh_measure_link_bandwidth, TBVH_BUILD_SPLIT_TRIANGLES / _WHOLE_TRIANGLES, development aids moved to tinybvh_amd_debug.h (nothing removed from the library); 4: tbvh_update_bvh_gpu / _bvh4_gpu / _cwbvh, tbvh_time_history, contexts are thread-safe; 3: deterministic ties, tbvh_bin_rays_device, tbvh_cwbvh_set_hybrid, device-resident multi-device calls */
 
 /* error codes */
 #define TBVH_OK            0
@@ -63,6 +63,7 @@ extern "C" {
 #define TBVH_LAYOUT_BVH_GPU    5  /* LAYOUT_BVH_GPU   Aila-Laine 64-byte nodes           */
 #define TBVH_LAYOUT_BVH4_GPU   8  /* LAYOUT_BVH4_GPU  quantized 4-wide + inline tris     */
 #define TBVH_LAYOUT_CWBVH     10  /* LAYOUT_CWBVH     compressed wide BVH8               */
+#define TBVH_LAYOUT_VOXELSET  12  /* LAYOUT_VOXELSET  brick-map voxel set, DDA traversal */
 
 typedef struct tbvh_context tbvh_context;  /* one HIP device + stream + scratch          */
 typedef struct tbvh_scene   tbvh_scene;    /* one uploaded layout (BLAS or TLAS)         */
@@ -582,6 +583,40 @@ int tbvh_occluded_ex(tbvh_scene* scene, const void* rays128, uint64_t n_rays, ui
  * aabbMin, aabbMax). */
 int tbvh_host_build_double(const void* verts_dbl3, uint64_t n_tris, tbvh_hostbvh** out);
 int tbvh_host_build_tlas_double(void* instances320, uint64_t n_instances, const double* blas_bounds_dbl6, uint64_t n_blas, tbvh_hostbvh** out);
+
+/* ----------------------------------------------------------------------------------
+ * voxel sets — VoxelSet (tiny_bvh.h:988-1030, 3772-4158): a brick map over the unit cube (object space (0,0,0)-(1,1,1)) of a fixed
+ * objectDim = 256 (the reference's compiled value; others are refused), traced by a three-level Amanatides & Woo DDA on the device
+ * (kernels_voxel.hip, DESIGN.md par. 10).  The three arrays are the reference's own:
+ *   grid       32^3 uint32 brick indices, x + 32 y + 1024 z, 0 = empty
+ *   bricks     n_bricks x 512 uint32 voxel values, 8^3 per brick (x + 8 y + 64 z), 0 = empty; brick 0 is never read (n_bricks counts it)
+ *   top_grid   16 uint32 = 512 occupancy bits, one per 4^3 group of grid cells (UpdateTopGrid)
+ * A voxel scene has layout TBVH_LAYOUT_VOXELSET from its upload, so TLASes enter it (the reference's constructor leaves `layout` UNDEFINED,
+ * and its TLAS traversals then skip the set: defect 1 of DESIGN.md par. 10).  Queries are the ordinary ones over the 64-byte Ray record —
+ * tbvh_intersect / _occluded (+ _device, tbvh_intersect_device_fresh, the _sharded variants) —, D and rD as the record holds them.  A hit
+ * writes hit.t = the entry distance of the voxel's cell, hit.prim = the voxel's value and hit.inst = ray.instIdx (under a TLAS the instance
+ * index); u and v are not written (the reference's INST_IDX_BITS == 32 build); a miss leaves the record as it was.
+ * One deliberate deviation (defect 3): the reference's Intersect records the first filled voxel whatever hit.t holds (3920-3935), so a ray
+ * with a finite tmax, or a TLAS ray with a nearer hit already, can get a FARTHER hit.  Here a voxel is recorded only if it wins by the
+ * library's rule (t < hit.t; under a TLAS at equal t the smaller prim, then the smaller instance), which is what the reference's own
+ * IsOccluded compares (4038, 4071); for hit.t = 1e30 and no TLAS the records are the reference's, bit for bit.
+ * TLAS: tbvh_upload_tlas / tbvh_update_tlas / tbvh_rebuild_tlas_device take a BLAS list in which EVERY BLAS is a voxel scene (their bounds
+ * are the unit cube); a TLAS mixing voxel and triangle BLASes is refused (TBVH_E_INVALID).  The reference's TLAS asserts do not list
+ * LAYOUT_VOXELSET (defect 2: a build without NDEBUG aborts there); nothing on the device corresponds.
+ * A voxel scene is refused (TBVH_E_INVALID) by refit and the tbvh_update_bvh_gpu / _bvh4_gpu / _cwbvh calls, opacity micromaps,
+ * tbvh_wavefront_render, tbvh_scene_download, the schedule hints and the _ex queries; tbvh_upload_tlas_double refuses it as a BLAS.
+ * ---------------------------------------------------------------------------------- */
+/* Validated before anything is allocated: n_bricks >= 1 and at most 2^22, every grid entry < n_bricks (TBVH_E_FORMAT names the first bad
+ * entry).  Only the bricks passed are uploaded; the reference's unused pool tail is not needed (n_bricks = its freeBrickPtr suffices). */
+int tbvh_upload_voxelset(tbvh_context* ctx, const uint32_t* grid32768, const uint32_t* bricks, uint64_t n_bricks, const uint32_t* top_grid16,
+                         tbvh_scene** out);
+/* The arrays of a VoxelSet filled from a dense values[x + y * nx + z * nx * ny] (0 = empty) in the order of tiny_bvh_voxel.cpp's loop, x
+ * outermost and z innermost, then UpdateTopGrid (Set 3786-3807, UpdateTopGrid 3809-3827, restated): byte for byte the reference's.
+ * Extents 1..256 per axis (larger: TBVH_E_INVALID).  tbvh_host_blob(h, 0) = grid (32768 uint32), (h, 1) = bricks (n_bricks x 512 uint32,
+ * brick 0 included; tbvh_host_blob_count gives words), (h, 2) = top grid (16 uint32); tbvh_host_layout = TBVH_LAYOUT_VOXELSET. */
+int tbvh_host_build_voxelset(const uint32_t* values, uint32_t nx, uint32_t ny, uint32_t nz, tbvh_hostbvh** out);
+/* tbvh_host_build_voxelset followed by tbvh_upload_voxelset */
+int tbvh_upload_voxelset_dense(tbvh_context* ctx, const uint32_t* values, uint32_t nx, uint32_t ny, uint32_t nz, tbvh_scene** out);
 
 #ifdef __cplusplus
 }

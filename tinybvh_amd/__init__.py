@@ -22,6 +22,7 @@ LAYOUT_BVH_DOUBLE = 3
 LAYOUT_BVH_GPU = 5
 LAYOUT_BVH4_GPU = 8
 LAYOUT_CWBVH = 10
+LAYOUT_VOXELSET = 12
 # wavefront materials: v0.w of a triangle's first vertex = type << 24 | 0xRRGGBB (wavefront.cl:12-13, 160)
 MATERIAL_DIFFUSE, MATERIAL_LIGHT, MATERIAL_SPECULAR = 0, 1, 2
 
@@ -901,4 +902,111 @@ class TLAS_Double(_SceneDouble):
                                           arr, len(blas), C.byref(self._h)), "tbvh_upload_tlas_double")
         self.instances = instances
         self.blas = list(blas)   # the BLAS scenes must outlive the TLAS
+        return self
+
+
+# ---- voxel sets: VoxelSet (tiny_bvh.h:988-1030, 3772-4158) -----------------------------------------------------------------------------
+VOXEL_OBJECT_DIM = 256   # VoxelSet::objectDim, the reference's compiled value (the only one supported)
+
+
+def load_voxel_file(path: str) -> np.ndarray:
+    """A voxel file of the reference's demos (tiny_bvh_voxel.cpp:44-48): gzip, a bvhint3 size, then size.x * size.y * size.z uint32 values
+    values[x + y * size.x + z * size.x * size.y].  Returns them as a dense (z, y, x) uint32 array."""
+    import gzip
+    with gzip.open(path, "rb") as f:
+        raw = f.read()
+    size = np.frombuffer(raw[:12], "<i4")
+    nx, ny, nz = (int(v) for v in size)
+    n = nx * ny * nz
+    assert nx > 0 and ny > 0 and nz > 0 and len(raw) >= 12 + 4 * n, "truncated voxel file"
+    return np.frombuffer(raw[12:12 + 4 * n], "<u4").reshape(nz, ny, nx).copy()
+
+
+class HostVoxelSet:
+    """The three arrays of tbvh_host_build_voxelset: grid (32768 uint32), bricks (n_bricks x 512 uint32, brick 0 included), top grid (16 uint32)."""
+
+    def __init__(self, h: C.c_void_p):
+        self._h = h
+
+    def _view(self, which: int) -> np.ndarray:
+        p = lib.tbvh_host_blob(self._h, which)
+        n = lib.tbvh_host_blob_count(self._h, which)
+        if not p or n == 0:
+            return np.zeros(0, np.uint32)
+        return np.ctypeslib.as_array((C.c_uint32 * n).from_address(p)).copy()
+
+    def arrays(self):
+        return self._view(0), self._view(1), self._view(2)
+
+    def __del__(self):
+        try:
+            if self._h:
+                lib.tbvh_host_free(self._h)
+                self._h = None
+        except Exception:
+            pass
+
+
+def host_build_voxelset(dense: np.ndarray):
+    """(grid, bricks, top) of a VoxelSet filled from a dense (z, y, x) uint32 array (0 = empty) in tiny_bvh_voxel.cpp's loop order, then
+    UpdateTopGrid: the reference's arrays byte for byte (tbvh_host_build_voxelset)."""
+    d = np.ascontiguousarray(dense, np.uint32)
+    assert d.ndim == 3
+    nz, ny, nx = d.shape
+    h = C.c_void_p()
+    check(lib.tbvh_host_build_voxelset(_ptr(d), nx, ny, nz, C.byref(h)), "tbvh_host_build_voxelset")
+    return HostVoxelSet(h).arrays()
+
+
+class VoxelSet(_Scene):
+    """VoxelSet (tiny_bvh.h:988-1030) on the device: a 256^3 brick map over the unit cube, traced by a three-level DDA (kernels_voxel.hip).
+    Set / UpdateTopGrid fill it on the host as the reference does; the first query (or Upload) puts it on the device.  Intersect / IsOccluded
+    take the ordinary Ray records (RAY_DTYPE); a hit writes t, prim = the voxel's value and inst = instIdx, and is recorded only if it wins
+    against the record's hit (DESIGN.md par. 10).  _bounds is the unit cube, so TLAS.Build takes voxel sets as BLASes (all of them voxel sets)."""
+    layout = LAYOUT_VOXELSET
+
+    def __init__(self, ctx: Context):
+        super().__init__(ctx)
+        self._bounds = np.array([0, 0, 0, 1, 1, 1], np.float32)
+        self._dense = None     # Set() collects here (x, y, z, v), applied in call order
+        self._pending = []
+
+    def Set(self, x, y, z, v) -> "VoxelSet":
+        """VoxelSet::Set (tiny_bvh.h:3786-3807) for scalars or equal-length arrays, applied in order (later calls win).  Takes effect on
+        the device at UpdateTopGrid."""
+        x, y, z, v = (np.atleast_1d(np.asarray(a)).astype(np.int64) for a in (x, y, z, v))
+        x, y, z, v = np.broadcast_arrays(x, y, z, v)
+        if x.size and (x.min() < 0 or y.min() < 0 or z.min() < 0 or max(x.max(), y.max(), z.max()) >= VOXEL_OBJECT_DIM):
+            raise ValueError("voxel coordinates are 0..255")
+        self._pending.append((x.ravel(), y.ravel(), z.ravel(), (v.ravel() & 0xFFFFFFFF).astype(np.uint32)))
+        return self
+
+    def UpdateTopGrid(self) -> "VoxelSet":
+        """VoxelSet::UpdateTopGrid (tiny_bvh.h:3809-3827), and the (re-)upload of the set.  The brick numbering is that of a reference set
+        filled in tiny_bvh_voxel.cpp's loop order (x outermost, z innermost), whatever order Set was called in."""
+        if self._dense is None:
+            self._dense = np.zeros((VOXEL_OBJECT_DIM,) * 3, np.uint32)
+        for x, y, z, v in self._pending:
+            self._dense[z, y, x] = v
+        self._pending = []
+        zz, yy, xx = np.nonzero(self._dense)
+        ext = (int(xx.max()) + 1, int(yy.max()) + 1, int(zz.max()) + 1) if xx.size else (1, 1, 1)
+        return self.Build(self._dense[:ext[2], :ext[1], :ext[0]])
+
+    def Build(self, dense: np.ndarray) -> "VoxelSet":
+        """Set every non-zero voxel of a dense (z, y, x) uint32 array (extents up to 256) and UpdateTopGrid, then upload."""
+        grid, bricks, top = host_build_voxelset(dense)
+        return self.Upload(grid, bricks, top)
+
+    def Upload(self, grid: np.ndarray, bricks: np.ndarray, top: np.ndarray) -> "VoxelSet":
+        """The reference's three arrays verbatim (tbvh_upload_voxelset): grid 32768 uint32, bricks n_bricks x 512 uint32 (brick 0 included;
+        an unused pool tail may be left off), top grid 16 uint32."""
+        grid = np.ascontiguousarray(grid, np.uint32).reshape(-1); bricks = np.ascontiguousarray(bricks, np.uint32).reshape(-1)
+        top = np.ascontiguousarray(top, np.uint32).reshape(-1)
+        assert grid.size == 32768 and top.size == 16 and bricks.size % 512 == 0
+        if self._h:
+            self.free()
+            self._h = C.c_void_p()
+        check(lib.tbvh_upload_voxelset(self.ctx._h, _ptr(grid), _ptr(bricks), bricks.size // 512, _ptr(top), C.byref(self._h)), "tbvh_upload_voxelset")
+        self.arrays = (grid, bricks, top)
         return self

@@ -127,6 +127,10 @@ SYMBOLS = {
     "tbvh_occluded_ex": (_i, [_vp, _vp, _u64, _vp]),
     "tbvh_host_build_double": (_i, [_vp, _u64, _pp]),
     "tbvh_host_build_tlas_double": (_i, [_vp, _u64, _vp, _u64, _pp]),
+    # VoxelSet scenes (capi_voxel.hip)
+    "tbvh_upload_voxelset": (_i, [_vp, _vp, _vp, _u64, _vp, _pp]),
+    "tbvh_host_build_voxelset": (_i, [_vp, _u32, _u32, _u32, _pp]),
+    "tbvh_upload_voxelset_dense": (_i, [_vp, _vp, _u32, _u32, _u32, _pp]),
 }
 
 

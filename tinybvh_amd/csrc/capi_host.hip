@@ -171,6 +171,7 @@ const void* tbvh_host_blob(const tbvh_hostbvh* h, int which) {
     case TBVH_LAYOUT_BVH4_GPU: return which == 0 ? (const void*)h->blocksA.data() : which == 2 ? (const void*)h->bvh2.nodes.data() : which == 3 ? (const void*)h->bvh2.primIdx.data() : nullptr;
     case TBVH_LAYOUT_CWBVH: return which == 0 ? (const void*)h->blocksA.data() : which == 1 ? (const void*)h->blocksB.data() : which == 2 ? (const void*)h->bvh2.nodes.data() : which == 3 ? (const void*)h->bvh2.primIdx.data() : nullptr;
     case TBVH_LAYOUT_BVH_DOUBLE: return which == 0 ? (const void*)h->dnodes.data() : which == 1 ? (const void*)h->didx.data() : nullptr;
+    case TBVH_LAYOUT_VOXELSET: return which == 0 ? (const void*)h->vgrid.data() : which == 1 ? (const void*)h->vbricks.data() : which == 2 ? (const void*)h->vtop.data() : nullptr;
     }
     return nullptr;
 }
@@ -182,6 +183,7 @@ uint64_t tbvh_host_blob_count(const tbvh_hostbvh* h, int which) {
     case TBVH_LAYOUT_BVH4_GPU: return which == 0 ? h->blocksA.size() : which == 2 ? h->bvh2.nodes.size() : which == 3 ? h->bvh2.primIdx.size() : 0;
     case TBVH_LAYOUT_CWBVH: return which == 0 ? h->blocksA.size() : which == 1 ? h->blocksB.size() : which == 2 ? h->bvh2.nodes.size() : which == 3 ? h->bvh2.primIdx.size() : 0;
     case TBVH_LAYOUT_BVH_DOUBLE: return which == 0 ? h->dnodes.size() : which == 1 ? h->didx.size() : 0;
+    case TBVH_LAYOUT_VOXELSET: return which == 0 ? h->vgrid.size() : which == 1 ? h->vbricks.size() : which == 2 ? h->vtop.size() : 0;
     }
     return 0;
 }

@@ -44,6 +44,14 @@ int fail(int code, const char* fmt, ...);   // sets tbvh_last_error() of the cal
             return tbvh_capi::fail(TBVH_E_INVALID, "%s: a BVH_DOUBLE scene takes tbvh_intersect_ex / tbvh_occluded_ex only", who);   \
     } while (0)
 
+// A VOXELSET scene (capi_voxel.hip) answers the ordinary queries (launchQuery) and can be a TLAS's BLAS; the entry points that have no
+// voxel form refuse it with this, before they touch the scene's memory or launch anything.
+#define TBVH_REFUSE_VOXEL(scene, who)                                                                                                   \
+    do {                                                                                                                                \
+        if ((scene) && (scene)->layout == TBVH_LAYOUT_VOXELSET)                                                                         \
+            return tbvh_capi::fail(TBVH_E_INVALID, "%s: a VOXELSET scene takes the queries and can be a TLAS's BLAS; nothing else", who); \
+    } while (0)
+
 #define HIP_TRY(expr)                                                                        \
     do {                                                                                     \
         hipError_t e_ = (expr);                                                              \
@@ -239,6 +247,7 @@ struct tbvh_hostbvh {
     std::vector<Vec4> blocksA, blocksB;
     std::vector<NodeDbl> dnodes;     // TBVH_LAYOUT_BVH_DOUBLE (capi_double.hip): BVH_Double::bvhNode ...
     std::vector<uint64_t> didx;      // ... and primIdx (TLAS: instance indices)
+    std::vector<uint32_t> vgrid, vbricks, vtop;   // TBVH_LAYOUT_VOXELSET (capi_voxel.hip): VoxelSet's grid, brick pool (used bricks) and top grid
 };
 
 struct HostPipe {

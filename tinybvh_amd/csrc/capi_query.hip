@@ -223,6 +223,9 @@ static void launchTlasKernels(tbvh_scene* s, QueryArgs& q, bool any, uint32_t bl
     } else if (s->tlas8 && (layout == TBVH_LAYOUT_CWBVH || mix)) {   // BVH8_CWBVH BLASes (or those and BVH_GPU ones): the unified 8-wide kernel
         q.spillStride = c->spillEntries / 2;   // 8-byte stack entries
         launch_tlas8(any, 0, s->tlas8, s->tlas8Refs, s->instances, desc, q, c->status, blocks, c->stream, blocks7, mix);
+    } else if (layout == TBVH_LAYOUT_VOXELSET) {   // voxel sets (kernels_voxel.hip); tbvh_upload_tlas admits them only all together
+        q.spillStride = c->spillEntries;   // 32-bit stack entries
+        launch_voxel(any, nullptr, s->nodes, s->tlasIdx, s->instances, desc, q, c->status, blocks, c->stream);
     } else if (layout == TBVH_LAYOUT_BVH_GPU) {   // BVH_GPU BLASes: the TLAS already has their node format (kernels_tlas2.hip)
         q.spillStride = c->spillEntries;
         launch_tlas2(any, 0, s->nodes, s->tlasIdx, s->instances, desc, q, c->status, blocks, c->stream, blocks7);
@@ -427,6 +430,10 @@ int launchQuery(tbvh_scene* s, RayRec* d_rays, uint64_t n, uint8_t* d_occ, bool 
     case TBVH_LAYOUT_CWBVH:
         q.spillStride = c->spillEntries / 2;  // 8-byte entries
         if (int r = launchCwbvhKernels(s, q, CwbvhLaunch{any, small, probedSmall, sizeClass, blocks, blocksBase, poolArea + (size_t)kPoolParts * kPoolCounterStride})) return r;
+        break;
+    case TBVH_LAYOUT_VOXELSET:
+        q.spillStride = c->spillEntries;
+        launch_voxel(any, (const uint32_t*)s->nodes, nullptr, nullptr, nullptr, nullptr, q, c->status, blocks, c->stream);
         break;
     default:
         return fail(TBVH_E_INVALID, "scene layout %d has no query kernel", s->layout);

@@ -1,0 +1,105 @@
+// capi_voxel.hip — VoxelSet scenes (tiny_bvh.h:988-1030, 3772-4158): upload with validation and the host builder behind
+// tbvh_host_build_voxelset.  The kernels are kernels_voxel.hip; queries reach them through launchQuery (capi_query.hip), TLASes over voxel sets
+// through tbvh_upload_tlas (capi_scene.hip).
+// A VOXELSET scene keeps ONE device allocation in `nodes`: [top grid 16 | grid 32768 | bricks n_bricks x 512] uint32 words, which is also
+// what a TLAS's BlasDesc::nodes points at.  tbvh_free_scene frees it like any scene's nodes.
+#include "capi_internal.h"
+
+using namespace tbvh;
+using namespace tbvh_capi;
+
+namespace {
+
+constexpr uint32_t kObjDim = 256, kBrickDim = 8, kGridDim = 32, kGroupDim = 4, kTopDim = 8;   // VoxelSet::objectDim = 256 (tiny_bvh.h:1008-1022)
+constexpr uint64_t kGridWords = (uint64_t)kGridDim * kGridDim * kGridDim, kBrickWords = (uint64_t)kBrickDim * kBrickDim * kBrickDim, kTopWords = 16;
+constexpr uint64_t kMaxBricks = 1ull << 22;   // (device offsets are 32-bit: 16 + 32768 + 2^22 x 512 < 2^31)
+
+// VoxelSet::Set (tiny_bvh.h:3786-3807): a brick is numbered when its first voxel is set (freeBrickPtr, brick 0 skipped); the pool's
+// reallocation does not change the numbering, so a growing vector stands for it
+void setVoxel(tbvh_hostbvh* h, uint32_t x, uint32_t y, uint32_t z, uint32_t v) {
+    const uint32_t g = x / kBrickDim + (y / kBrickDim) * kGridDim + (z / kBrickDim) * kGridDim * kGridDim;
+    uint32_t b = h->vgrid[g];
+    if (!b) {
+        b = h->vgrid[g] = (uint32_t)(h->vbricks.size() / kBrickWords);
+        h->vbricks.resize(h->vbricks.size() + kBrickWords, 0u);
+    }
+    h->vbricks[(size_t)b * kBrickWords + (x & (kBrickDim - 1)) + (y & (kBrickDim - 1)) * kBrickDim + (z & (kBrickDim - 1)) * kBrickDim * kBrickDim] = v;
+}
+
+// VoxelSet::UpdateTopGrid (tiny_bvh.h:3809-3827)
+void updateTopGrid(tbvh_hostbvh* h) {
+    h->vtop.assign(kTopWords, 0u);
+    for (uint32_t x = 0; x < kTopDim; x++) for (uint32_t y = 0; y < kTopDim; y++) for (uint32_t z = 0; z < kTopDim; z++) {
+        const uint32_t* base = h->vgrid.data() + x * kGroupDim + y * kGroupDim * kGridDim + z * kGroupDim * kGridDim * kGridDim;
+        bool has = false;
+        for (uint32_t u = 0; u < kGroupDim && !has; u++) for (uint32_t v = 0; v < kGroupDim && !has; v++) for (uint32_t w = 0; w < kGroupDim && !has; w++)
+            has = base[u + v * kGridDim + w * kGridDim * kGridDim] != 0;
+        if (!has) continue;
+        const uint32_t ti = x + y * kTopDim + z * kTopDim * kTopDim;
+        h->vtop[ti >> 5] |= 1u << (ti & 31);
+    }
+}
+
+}  // namespace
+
+extern "C" {
+
+int tbvh_upload_voxelset(tbvh_context* c, const uint32_t* grid, const uint32_t* bricks, uint64_t nBricks, const uint32_t* top, tbvh_scene** out) {
+    if (!c || !grid || !bricks || !top || !out) return fail(TBVH_E_INVALID, "tbvh_upload_voxelset: null argument");
+    if (nBricks == 0) return fail(TBVH_E_FORMAT, "tbvh_upload_voxelset: n_bricks = 0 (brick 0, the empty one, is part of the pool)");
+    if (nBricks > kMaxBricks) return fail(TBVH_E_FORMAT, "tbvh_upload_voxelset: %llu bricks: at most %llu", (unsigned long long)nBricks, (unsigned long long)kMaxBricks);
+    for (uint64_t i = 0; i < kGridWords; i++)
+        if (grid[i] >= nBricks)
+            return fail(TBVH_E_FORMAT, "tbvh_upload_voxelset: grid[%llu] = %u >= n_bricks = %llu", (unsigned long long)i, grid[i], (unsigned long long)nBricks);
+    TBVH_ENTER(c);
+    tbvh_scene* s = newScene(c, TBVH_LAYOUT_VOXELSET);
+    if (!s) return fail(TBVH_E_NOMEM, "out of host memory");
+    const uint64_t words = kTopWords + kGridWords + nBricks * kBrickWords;
+    if (hipMalloc((void**)&s->nodes, words * 4) != hipSuccess) { tbvh_free_scene(s); return fail(TBVH_E_NOMEM, "tbvh_upload_voxelset: out of device memory"); }
+    uint32_t* base = (uint32_t*)s->nodes;
+    if (hipMemcpyAsync(base, top, kTopWords * 4, hipMemcpyHostToDevice, c->stream) != hipSuccess ||
+        hipMemcpyAsync(base + kTopWords, grid, kGridWords * 4, hipMemcpyHostToDevice, c->stream) != hipSuccess ||
+        hipMemcpyAsync(base + kTopWords + kGridWords, bricks, nBricks * kBrickWords * 4, hipMemcpyHostToDevice, c->stream) != hipSuccess ||
+        hipStreamSynchronize(c->stream) != hipSuccess) {
+        tbvh_free_scene(s);
+        return fail(TBVH_E_HIP, "tbvh_upload_voxelset: copy to the device failed");
+    }
+    s->nNodes = (uint32_t)nBricks;
+    s->bytes = words * 4;
+    *out = s;
+    return 0;
+}
+
+int tbvh_host_build_voxelset(const uint32_t* values, uint32_t nx, uint32_t ny, uint32_t nz, tbvh_hostbvh** out) {
+    if (!values || !out || !nx || !ny || !nz) return fail(TBVH_E_INVALID, "tbvh_host_build_voxelset: null/empty argument");
+    if (nx > kObjDim || ny > kObjDim || nz > kObjDim)
+        return fail(TBVH_E_INVALID, "tbvh_host_build_voxelset: extent %u x %u x %u beyond the object's %u^3 voxels", nx, ny, nz, kObjDim);
+    tbvh_hostbvh* h = new (std::nothrow) tbvh_hostbvh;
+    if (!h) return fail(TBVH_E_NOMEM, "out of host memory");
+    h->layout = TBVH_LAYOUT_VOXELSET;
+    try {
+        h->vgrid.assign(kGridWords, 0u);
+        h->vbricks.assign(kBrickWords, 0u);   // brick 0: never written
+        for (uint32_t x = 0; x < nx; x++) for (uint32_t y = 0; y < ny; y++) for (uint32_t z = 0; z < nz; z++) {   // tiny_bvh_voxel.cpp's loop order
+            const uint32_t v = values[x + (size_t)y * nx + (size_t)z * nx * ny];
+            if (v) setVoxel(h, x, y, z, v);
+        }
+        updateTopGrid(h);
+    } catch (const std::bad_alloc&) {
+        delete h;
+        return fail(TBVH_E_NOMEM, "out of host memory while building");
+    }
+    *out = h;
+    return 0;
+}
+
+int tbvh_upload_voxelset_dense(tbvh_context* c, const uint32_t* values, uint32_t nx, uint32_t ny, uint32_t nz, tbvh_scene** out) {
+    if (!c || !out) return fail(TBVH_E_INVALID, "tbvh_upload_voxelset_dense: null argument");
+    tbvh_hostbvh* h = nullptr;
+    if (int r = tbvh_host_build_voxelset(values, nx, ny, nz, &h)) return r;
+    const int r = tbvh_upload_voxelset(c, h->vgrid.data(), h->vbricks.data(), h->vbricks.size() / kBrickWords, h->vtop.data(), out);
+    delete h;
+    return r;
+}
+
+}  // extern "C"

@@ -85,6 +85,9 @@ int tbvh_wavefront_set_blas_vertices(tbvh_wavefront* w, const void* const* dVert
 int tbvh_wavefront_render(tbvh_wavefront* w, tbvh_scene* scene, const void* dVerts, const tbvh_camera* cam, const tbvh_wf_params* p,
                           tbvh_wf_stats* stats) {
     TBVH_REFUSE_DOUBLE(scene, "tbvh_wavefront_render");
+    TBVH_REFUSE_VOXEL(scene, "tbvh_wavefront_render");
+    if (scene && scene->isTlas && !scene->blasList.empty() && scene->blasList[0]->layout == TBVH_LAYOUT_VOXELSET)
+        return fail(TBVH_E_INVALID, "tbvh_wavefront_render: a TLAS over VOXELSET scenes takes the queries only (the path tracer shades triangles)");
     if (!w || !scene || !cam || !p) return fail(TBVH_E_INVALID, "tbvh_wavefront_render: null argument");
     if (scene->isTlas) {
         if (w->nBlasVerts < scene->nBlas) return fail(TBVH_E_INVALID, "tbvh_wavefront_render: a TLAS scene needs tbvh_wavefront_set_blas_vertices (%llu BLASes)", (unsigned long long)scene->nBlas);

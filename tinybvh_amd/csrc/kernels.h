@@ -75,6 +75,11 @@ struct DoubleArgs {
 void launch_double(bool anyhit, bool tlas, const DoubleArgs& q, uint32_t* status, uint32_t blocks, hipStream_t s);
 void launch_gather_tris_dbl(const uint64_t* primIdx, const double* verts, TriDbl* out, uint64_t nIdx, hipStream_t s);
 
+// VoxelSet scenes (kernels_voxel.hip): vox = one set's [top grid 16 | grid 32768 | bricks] words; tlasNodes != nullptr: a BVH_GPU-format TLAS over
+// BLASInstance records whose BLASes are all voxel sets (BlasDesc::nodes = each set's array)
+void launch_voxel(bool anyhit, const uint32_t* vox, const float4* tlasNodes, const uint32_t* tlasIdx, const float4* instances, const BlasDesc* blas,
+                  const QueryArgs& q, uint32_t* status, uint32_t blocks, hipStream_t s);
+
 // device TLAS rebuild (kernels_tlasbuild.hip)
 size_t tlas_build_scratch_bytes(uint32_t n, size_t* sortTempBytes);
 hipError_t launch_tlas_rebuild(float4* tlasNodes, uint32_t* tlasIdx, float4* instances, const float* transformsDev, const float* blasBoundsDev,
