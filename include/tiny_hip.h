@@ -89,6 +89,15 @@ public:
     float LastKernelMs() const { return tbvh_time_last_ms(ctx); }
     // animated geometry: BVH::Refit + ConvertFrom + upload of the reference flow, on the device
     void Refit(const tinybvh::bvhvec4* verts, size_t triCount) { Check(tbvh_refit(s, verts, triCount, 0), "tbvh_refit"); }
+    // BVH::IntersectSphere( pos, r ) batched (tiny_bvh.h:3140-3200; tiny_bvh_collide.cpp:169): hit[i] = 1 if sphere i = {x, y, z, r} touches a
+    // triangle; verts = the scene's bvhvec4 vertex array, 3 per triangle, as Refit takes it.  BLAS scenes of the three GPU layouts only.
+    void IntersectSpheres(const tinybvh::bvhvec4* spheres, size_t n, const tinybvh::bvhvec4* verts, size_t triCount, uint8_t* hit) {
+        Check(tbvh_intersect_spheres(s, spheres, n, verts, triCount, hit), "tbvh_intersect_spheres");
+    }
+    // the same over device arrays, asynchronous on the context's stream
+    void IntersectSpheresDevice(const void* dSpheres, size_t n, const void* dVerts, size_t triCount, uint8_t* dHit) {
+        Check(tbvh_intersect_spheres_device(s, dSpheres, n, dVerts, triCount, dHit), "tbvh_intersect_spheres_device");
+    }
     tbvh_scene* Handle() const { return s; }
     int Device() const { return dev; }
     tbvh_context* Ctx() const { return ctx; }

@@ -46,7 +46,7 @@
 extern "C" {
 #endif
 
-#define TBVH_ABI_VERSION 5   /* 5 (additions, nothing changed: VoxelSet scenes — TBVH_LAYOUT_VOXELSET, tbvh_upload_voxelset / _voxelset_dense, tbvh_host_build_voxelset, TLASes over voxel sets); 5 (additions, nothing changed: BVH_Double scenes — TBVH_LAYOUT_BVH_DOUBLE, tbvh_upload_bvh_double / _tlas_double, tbvh_intersect_ex / _occluded_ex (+ _device), tbvh_host_build_double / _tlas_double); 5: tbvh_pinned_malloc / _free, tbvh_scene_get / _set_schedule_hint, tbvh_measure_link_bandwidth, TBVH_BUILD_SPLIT_TRIANGLES / _WHOLE_TRIANGLES, development aids moved to tinybvh_amd_debug.h (nothing removed from the library); 4: tbvh_update_bvh_gpu / _bvh4_gpu / _cwbvh, tbvh_time_history, contexts are thread-safe; 3: deterministic ties, tbvh_bin_rays_device, tbvh_cwbvh_set_hybrid, device-resident multi-device calls */
+#define TBVH_ABI_VERSION 5   /* 5 (additions, nothing changed: tbvh_intersect_spheres / _device); 5 (additions, nothing changed: VoxelSet scenes — TBVH_LAYOUT_VOXELSET, tbvh_upload_voxelset / _voxelset_dense, tbvh_host_build_voxelset, TLASes over voxel sets); 5 (additions, nothing changed: BVH_Double scenes — TBVH_LAYOUT_BVH_DOUBLE, tbvh_upload_bvh_double / _tlas_double, tbvh_intersect_ex / _occluded_ex (+ _device), tbvh_host_build_double / _tlas_double); 5: tbvh_pinned_malloc / _free, tbvh_scene_get / _set_schedule_hint, tbvh_measure_link_bandwidth, TBVH_BUILD_SPLIT_TRIANGLES / _WHOLE_TRIANGLES, development aids moved to tinybvh_amd_debug.h (nothing removed from the library); 4: tbvh_update_bvh_gpu / _bvh4_gpu / _cwbvh, tbvh_time_history, contexts are thread-safe; 3: deterministic ties, tbvh_bin_rays_device, tbvh_cwbvh_set_hybrid, device-resident multi-device calls */
 
 /* error codes */
 #define TBVH_OK            0
@@ -617,6 +617,26 @@ int tbvh_upload_voxelset(tbvh_context* ctx, const uint32_t* grid32768, const uin
 int tbvh_host_build_voxelset(const uint32_t* values, uint32_t nx, uint32_t ny, uint32_t nz, tbvh_hostbvh** out);
 /* tbvh_host_build_voxelset followed by tbvh_upload_voxelset */
 int tbvh_upload_voxelset_dense(tbvh_context* ctx, const uint32_t* values, uint32_t nx, uint32_t ny, uint32_t nz, tbvh_scene** out);
+
+/* ----------------------------------------------------------------------------------
+ * sphere-overlap queries — BVH::IntersectSphere (tiny_bvh.h:3140-3200), batched (kernels_sphere.hip, DESIGN.md par. 11):
+ * hit[i] = 1 if sphere i = {x, y, z, r} (16 bytes) touches a triangle, else 0.
+ * verts16: the caller's bvhvec4 vertex array, 3 per triangle, as tbvh_refit takes it; each triangle record's primitive index selects its
+ * three vertices (the uploaded records keep only v0 and edges).  Scenes: BVH_GPU, BVH4_GPU and BVH8_CWBVH BLASes; the uploaded node arrays
+ * are walked (not a library copy).  The reference's float operations are repeated exactly, including the products its x86 build fuses;
+ * r <= 0, NaN / infinite components and degenerate triangles answer as the reference does.  One deliberate deviation: a node taken off the
+ * stack goes through the leaf check (the reference walks it as an interior node, which skips that leaf's triangles and can loop forever).
+ * BVH_GPU answers are the reference's for the same tree; BVH4_GPU / BVH8_CWBVH use their quantised (conservative) child boxes and can differ
+ * only where a deciding quantity sits at its threshold within rounding.
+ * Refused with TBVH_E_INVALID before any launch: a null scene, a TLAS, BVH_DOUBLE and VOXELSET scenes, null arrays (n_spheres > 0), an empty
+ * vertex array, unaligned device arrays (16 bytes).  n_spheres == 0 is a no-op.  A triangle record whose primitive lies beyond n_tris is
+ * skipped (never read) and reported as TBVH_E_FORMAT by the host variant, or by the next synchronizing call after the device variant.
+ * tbvh_time_last_ms() reports the kernel.
+ * ---------------------------------------------------------------------------------- */
+int tbvh_intersect_spheres(tbvh_scene* scene, const void* spheres16, uint64_t n_spheres,
+                           const void* verts16, uint64_t n_tris, uint8_t* hit);          /* host arrays; returns when done */
+int tbvh_intersect_spheres_device(tbvh_scene* scene, const void* d_spheres16, uint64_t n_spheres,
+                                  const void* d_verts16, uint64_t n_tris, uint8_t* d_hit); /* device arrays; asynchronous on the context's stream */
 
 #ifdef __cplusplus
 }

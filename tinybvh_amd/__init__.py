@@ -377,7 +377,32 @@ class _Scene:
         check(lib.tbvh_occluded_device(self._h, C.c_void_p(d_rays), n, C.c_void_p(d_out)), "tbvh_occluded_device")
 
 
-class BVH_GPU(_Scene):
+class _SphereQueries:
+    """BVH::IntersectSphere (tiny_bvh.h:3140-3200) over a BLAS, batched (tbvh_intersect_spheres): does a sphere touch any triangle?
+    verts is the vertex array the scene was built from (3 bvhvec4 per triangle), as Refit takes it."""
+
+    def intersect_spheres(self, spheres: np.ndarray, verts: np.ndarray) -> np.ndarray:
+        """spheres: (n, 4) float32 {x, y, z, r}; returns uint8[n], 1 = the sphere touches a triangle"""
+        spheres = np.ascontiguousarray(spheres, np.float32).reshape(-1, 4)
+        verts = np.ascontiguousarray(verts, np.float32).reshape(-1, 4)
+        assert verts.shape[0] % 3 == 0
+        out = np.zeros(spheres.shape[0], np.uint8)
+        check(lib.tbvh_intersect_spheres(self._h, _ptr(spheres), spheres.shape[0], _ptr(verts), verts.shape[0] // 3, _ptr(out)),
+              "tbvh_intersect_spheres")
+        return out
+
+    def intersect_spheres_device(self, d_spheres: int, n: int, d_verts: int, n_tris: int, d_hit: int):
+        """device arrays (16-byte spheres, 3 x 16-byte vertices per triangle, 1 byte per answer); asynchronous on the context's stream"""
+        check(lib.tbvh_intersect_spheres_device(self._h, C.c_void_p(d_spheres), n, C.c_void_p(d_verts), n_tris, C.c_void_p(d_hit)),
+              "tbvh_intersect_spheres_device")
+
+    def intersect_sphere(self, pos, r: float, verts: np.ndarray) -> bool:
+        """one sphere, as BVH::IntersectSphere( pos, r ) asks it"""
+        s = np.array([[pos[0], pos[1], pos[2], r]], np.float32)
+        return bool(self.intersect_spheres(s, verts)[0])
+
+
+class BVH_GPU(_SphereQueries, _Scene):
     """Aila-Laine 2-wide layout (tiny_bvh.h:1092-1127)."""
     layout = LAYOUT_BVH_GPU
 
@@ -400,7 +425,7 @@ class BVH_GPU(_Scene):
         return self
 
 
-class BVH4_GPU(_Scene):
+class BVH4_GPU(_SphereQueries, _Scene):
     """Quantized 4-wide layout with inline triangles (tiny_bvh.h:1245-1289)."""
     layout = LAYOUT_BVH4_GPU
 
@@ -436,7 +461,7 @@ class BVH4_GPU(_Scene):
         return self
 
 
-class BVH8_CWBVH(_Scene):
+class BVH8_CWBVH(_SphereQueries, _Scene):
     """Compressed wide BVH (tiny_bvh.h:1334-1362)."""
     layout = LAYOUT_CWBVH
 

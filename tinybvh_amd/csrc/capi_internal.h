@@ -326,6 +326,8 @@ hipError_t timedEnd(tbvh_context* c);     // end event recorded; the operation c
 int launchQuery(tbvh_scene* s, tbvh::RayRec* d_rays, uint64_t n, uint8_t* d_occ, bool fresh = false, float freshTmax = 1e30f,
                 const unsigned long long* nDev = nullptr);
 int checkStatus(tbvh_context* c);   // synchronizes the stream, turns the device status word into an error code
+int ensureStage(tbvh_context* c, uint64_t n);      // (capi_query.hip) the host-array staging buffers hold at least n ray records ...
+int ensureStageOcc(tbvh_context* c, uint64_t n);   // ... and n any-hit result bytes
 tbvh_scene* newScene(tbvh_context* c, int layout);
 uint64_t cwbvhTopologyHash(const tbvh::Vec4* nodes, uint32_t nNodes);
 int padCwbvhIfLarge(tbvh_scene* s);

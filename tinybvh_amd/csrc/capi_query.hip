@@ -460,6 +460,10 @@ int checkStatus(tbvh_context* c) {
         hipMemsetAsync(c->status, 0, 4, c->stream);
         return fail(TBVH_E_FORMAT, "wide TLAS build: the node capacity did not hold the collapsed tree");
     }
+    if (st & 16u) {
+        hipMemsetAsync(c->status, 0, 4, c->stream);
+        return fail(TBVH_E_FORMAT, "sphere query: a triangle record refers to a primitive beyond the vertex array");
+    }
     return 0;
 }
 }  // namespace tbvh_capi

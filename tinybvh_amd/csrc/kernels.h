@@ -80,6 +80,24 @@ void launch_gather_tris_dbl(const uint64_t* primIdx, const double* verts, TriDbl
 void launch_voxel(bool anyhit, const uint32_t* vox, const float4* tlasNodes, const uint32_t* tlasIdx, const float4* instances, const BlasDesc* blas,
                   const QueryArgs& q, uint32_t* status, uint32_t blocks, hipStream_t s);
 
+// BVH::IntersectSphere batched (kernels_sphere.hip): hit[i] = 1 if sphere i = {x, y, z, r} touches a triangle of a BVH_GPU / BVH4_GPU / BVH8_CWBVH
+// BLAS; verts = the caller's vertex array (3 float4 per triangle, nTris triangles), indexed by the primitive index of each triangle record
+struct SphereArgs {
+    const float4* spheres;   // device, 16 bytes per sphere
+    uint64_t nSpheres;
+    uint8_t* hit;            // device, 1 byte per sphere
+    const float4* nodes;     // the scene's node array (BVH4_GPU: the stream, triangles inline)
+    const float4* tris;      // BVH_GPU / BVH8_CWBVH triangle records
+    const float4* verts;
+    uint64_t nTris;
+    uint32_t* spill;         // stack spill area (8-byte entries)
+    uint32_t spillStride;    // 8-byte entries per lane in `spill`
+    uint32_t* counter;       // ray-pool counters of this launch and of the next one (ray_pool.h)
+    uint32_t* counterNext;
+    uint32_t poolParts;
+};
+void launch_spheres(int layout, const SphereArgs& q, uint32_t* status, uint32_t blocks, hipStream_t s);   // status |= 16: a record's primitive is beyond nTris
+
 // device TLAS rebuild (kernels_tlasbuild.hip)
 size_t tlas_build_scratch_bytes(uint32_t n, size_t* sortTempBytes);
 hipError_t launch_tlas_rebuild(float4* tlasNodes, uint32_t* tlasIdx, float4* instances, const float* transformsDev, const float* blasBoundsDev,
