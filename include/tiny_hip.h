@@ -149,6 +149,37 @@ private:
     std::vector<uint32_t> grid, brick, top;   // 32^3 brick indices, the bricks in use (brick 0 the empty one), 512 occupancy bits
 };
 
+// A BVH over custom geometry whose primitives are spheres (tinybvh's BVH::Build( customGetAABB, n ) with the anim demo's sphere callbacks) on the
+// device: Build() takes the spheres {x, y, z, r} and builds with the library's builder, Upload() takes a reference BVH's own arrays (bvhNode,
+// usedNodes, primIdx, idxCount).  Handle() is usable as a BLAS of tbvh_upload_tlas, also next to triangle BLASes (DESIGN.md par. 12).
+class SphereBVH {
+public:
+    explicit SphereBVH(int device = 0, tbvh_context* own = nullptr) : ctx(own ? own : Context(device)) {}
+    SphereBVH(const SphereBVH&) = delete;
+    SphereBVH& operator=(const SphereBVH&) = delete;
+    ~SphereBVH() { if (s) tbvh_free_scene(s); }
+    void Build(const float* spheres16, uint32_t n) {
+        tbvh_hostbvh* h = nullptr;
+        Check(tbvh_host_build_custom_spheres(spheres16, n, &h), "tbvh_host_build_custom_spheres");
+        const int r = tbvh_upload_custom_spheres(ctx, tbvh_host_blob(h, 0), tbvh_host_blob_count(h, 0), (const uint32_t*)tbvh_host_blob(h, 1),
+                                                 tbvh_host_blob_count(h, 1), spheres16, n, Fresh());
+        tbvh_host_free(h);
+        Check(r, "tbvh_upload_custom_spheres");
+    }
+    void Upload(const void* nodes32, uint32_t usedNodes, const uint32_t* primIdx, uint32_t idxCount, const float* spheres16, uint32_t n) {
+        Check(tbvh_upload_custom_spheres(ctx, nodes32, usedNodes, primIdx, idxCount, spheres16, n, Fresh()), "tbvh_upload_custom_spheres");
+    }
+    // BVH::Intersect( Ray& ) / IsOccluded( const Ray& ) with the sphere callbacks, over a host tinybvh::Ray[]
+    void Intersect(tinybvh::Ray* rays, size_t n) { Check(tbvh_intersect(s, rays, n, sizeof(tinybvh::Ray)), "tbvh_intersect"); }
+    void IsOccluded(const tinybvh::Ray* rays, size_t n, uint8_t* out) { Check(tbvh_occluded(s, rays, n, sizeof(tinybvh::Ray), out), "tbvh_occluded"); }
+    tbvh_scene* Handle() const { return s; }
+    tbvh_context* Ctx() const { return ctx; }
+private:
+    tbvh_scene** Fresh() { if (s) { tbvh_free_scene(s); s = nullptr; } return &s; }
+    tbvh_context* ctx;
+    tbvh_scene* s = nullptr;
+};
+
 // tinyocl::Buffer( bytes ) for a ray array that is traced many times (tiny_bvh_speedtest.cpp:1101-1108 wraps its ray array in one per GPU block): page-locked
 // host memory of the library's for the object's lifetime (tbvh_pinned_malloc); a PACKED 64-byte ray array in it goes up by DMA straight from there.
 class PinnedBuffer {

@@ -46,7 +46,7 @@
 extern "C" {
 #endif
 
-#define TBVH_ABI_VERSION 5   /* 5 (additions, nothing changed: tbvh_intersect_spheres / _device); 5 (additions, nothing changed: VoxelSet scenes — TBVH_LAYOUT_VOXELSET, tbvh_upload_voxelset / _voxelset_dense, tbvh_host_build_voxelset, TLASes over voxel sets); 5 (additions, nothing changed: BVH_Double scenes — TBVH_LAYOUT_BVH_DOUBLE, tbvh_upload_bvh_double / _tlas_double, tbvh_intersect_ex / _occluded_ex (+ _device), tbvh_host_build_double / _tlas_double); 5: tbvh_pinned_malloc / _free, tbvh_scene_get / _set_schedule_hint, tbvh_measure_link_bandwidth, TBVH_BUILD_SPLIT_TRIANGLES / _WHOLE_TRIANGLES, development aids moved to tinybvh_amd_debug.h (nothing removed from the library); 4: tbvh_update_bvh_gpu / _bvh4_gpu / _cwbvh, tbvh_time_history, contexts are thread-safe; 3: deterministic ties, tbvh_bin_rays_device, tbvh_cwbvh_set_hybrid, device-resident multi-device calls */
+#define TBVH_ABI_VERSION 5   /* 5 (additions, nothing changed: custom-geometry sphere BLASes — tbvh_upload_custom_spheres, tbvh_host_build_custom_spheres, TLASes over them); 5 (additions, nothing changed: tbvh_intersect_spheres / _device); 5 (additions, nothing changed: VoxelSet scenes — TBVH_LAYOUT_VOXELSET, tbvh_upload_voxelset / _voxelset_dense, tbvh_host_build_voxelset, TLASes over voxel sets); 5 (additions, nothing changed: BVH_Double scenes — TBVH_LAYOUT_BVH_DOUBLE, tbvh_upload_bvh_double / _tlas_double, tbvh_intersect_ex / _occluded_ex (+ _device), tbvh_host_build_double / _tlas_double); 5: tbvh_pinned_malloc / _free, tbvh_scene_get / _set_schedule_hint, tbvh_measure_link_bandwidth, TBVH_BUILD_SPLIT_TRIANGLES / _WHOLE_TRIANGLES, development aids moved to tinybvh_amd_debug.h (nothing removed from the library); 4: tbvh_update_bvh_gpu / _bvh4_gpu / _cwbvh, tbvh_time_history, contexts are thread-safe; 3: deterministic ties, tbvh_bin_rays_device, tbvh_cwbvh_set_hybrid, device-resident multi-device calls */
 
 /* error codes */
 #define TBVH_OK            0
@@ -58,7 +58,7 @@ extern "C" {
 
 /* layouts; the values ARE BVHBase::BVHType (tiny_bvh.h:773-791), so a caller can pass bvh.layout
  * (ABI version 1 used 4 / 6 / 9 here, which are LAYOUT_BVH_SOA / LAYOUT_MBVH / LAYOUT_MBVH8 in the reference) */
-#define TBVH_LAYOUT_BVH2_WALD  1  /* LAYOUT_BVH       32-byte nodes (host/oracle only)   */
+#define TBVH_LAYOUT_BVH2_WALD  1  /* LAYOUT_BVH       32-byte nodes (host builds; on the device: sphere BLASes) */
 #define TBVH_LAYOUT_BVH_DOUBLE 3  /* LAYOUT_BVH_DOUBLE fp64 64-byte nodes, RayEx queries  */
 #define TBVH_LAYOUT_BVH_GPU    5  /* LAYOUT_BVH_GPU   Aila-Laine 64-byte nodes           */
 #define TBVH_LAYOUT_BVH4_GPU   8  /* LAYOUT_BVH4_GPU  quantized 4-wide + inline tris     */
@@ -561,8 +561,8 @@ int tbvh_upload_host(tbvh_context* ctx, const tbvh_hostbvh* h, const void* verts
  * occlusion is a hit with 0 < t < hit.t.  Equal distances resolve as everywhere in this library (smaller prim, then smaller instance).
  * Blobs are validated before anything is allocated (TBVH_E_FORMAT names the first bad entry: child or leaf range, primIdx, blasIdx, fewer than
  * 2^32 nodes, not a tree).  A BVH_DOUBLE scene takes the four _ex queries, tbvh_free_scene, tbvh_scene_layout (3) and tbvh_scene_device_bytes;
- * every other entry point refuses it (TBVH_E_INVALID), and the _ex queries refuse the fp32 layouts.  Custom geometry (customIntersect) is
- * not supported: upload needs triangles.
+ * every other entry point refuses it (TBVH_E_INVALID), and the _ex queries refuse the fp32 layouts.  Custom geometry (customIntersect) in
+ * double precision is not supported: upload needs triangles (fp32 sphere BLASes: the custom-geometry section below).
  * ---------------------------------------------------------------------------------- */
 int tbvh_upload_bvh_double(tbvh_context* ctx, const void* nodes64, uint64_t n_nodes, const uint64_t* prim_idx, uint64_t n_idx,
                            const void* verts_dbl3, uint64_t n_tris, tbvh_scene** out);
@@ -637,6 +637,49 @@ int tbvh_intersect_spheres(tbvh_scene* scene, const void* spheres16, uint64_t n_
                            const void* verts16, uint64_t n_tris, uint8_t* hit);          /* host arrays; returns when done */
 int tbvh_intersect_spheres_device(tbvh_scene* scene, const void* d_spheres16, uint64_t n_spheres,
                                   const void* d_verts16, uint64_t n_tris, uint8_t* d_hit); /* device arrays; asynchronous on the context's stream */
+
+/* ----------------------------------------------------------------------------------
+ * custom geometry: sphere BLASes — BVH::Build( customGetAABB, n ) (tiny_bvh.h:2190-2219) traced through the custom branch of BVH::Intersect /
+ * IsOccluded (3270-3279, 3424-3428) and IntersectTLAS / IsOccludedTLAS.  A device cannot call a host function pointer, so the primitive is
+ * one the library knows: the sphere of the reference's custom and anim demos, {x, y, z, r} (16 bytes), with the anim demo's callback
+ * (kernels_custom.hip, DESIGN.md par. 12).  The arrays are the reference's own:
+ *   nodes32    BVH::bvhNode, 32-byte Wald nodes {aabbMin, leftFirst, aabbMax, triCount}: a leaf iff triCount > 0, children leftFirst and
+ *              leftFirst + 1, node 1 may be unused; n_nodes = usedNodes
+ *   prim_idx   BVH::primIdx, n_idx = idxCount
+ *   spheres16  {x, y, z, r} per primitive, indexed by primitive index
+ * The callback (the form that stays right when D is not of unit length, as under a scaled instance): mag = |D|, reciMag = 1 / mag,
+ * oc = O - pos, b = dot(oc, D) * reciMag, c = dot(oc, oc) - r r, d = b b - c; no hit if d <= 0, else t = -b - sqrt(d); a candidate iff
+ * 0 < t < tmax_in * mag, and it records hit.t = t * reciMag.  The float operations are the reference's in its order, with the products its
+ * x86 build fuses (read from the disassembly) as explicit fmas; the divisions and square roots are correctly rounded.  tiny_bvh_custom.cpp's
+ * unit-direction form is not offered.
+ * Winner rule (independent of the visit order, like every query here): of the candidates (tmax_in = the record's incoming hit.t), spheres and
+ * triangles alike, the ray keeps the one with the smallest recorded distance, then the smaller prim, then the smaller instance; box culls stay
+ * conservative (DESIGN.md par. 4).  Limits (DESIGN.md par. 12): the minimum is over the spheres the walk tests, so a sphere the sphere test
+ * reports hit while the slab test misses its box (rounding far from the origin) is lost, as in the reference; and under a TLAS mixing spheres
+ * and triangles, a sphere whose recorded t * reciMag rounds above tmax_in lets a triangle up to that distance in, which tested first would
+ * have been rejected.  The reference keeps the FIRST accepted sphere instead and compares t < hit.t * mag against the hit it has,
+ * so at near-ties (recorded distances equal, or within the rounding of t * reciMag * mag) the two can name different spheres: DESIGN.md par. 12
+ * counts that class.
+ * A hit writes hit.t, hit.prim and hit.inst (byte 44: ray.instIdx for a BLAS, as the reference's custom branch; the instance index under a
+ * TLAS); u and v stay as the record had them on input (the callback never touches them — for a BLAS query exactly the reference; under a TLAS
+ * the reference can carry the u, v of a farther triangle it met first, DESIGN.md par. 12).  A miss leaves the record untouched; IsOccluded
+ * writes one byte per ray.  r <= 0, a zero-length D and NaN / infinite components answer as the restated operations make them answer.
+ * Queries are the ordinary ones: tbvh_intersect / _occluded (+ _device, tbvh_intersect_device_fresh, the _sharded variants).
+ * TLAS: tbvh_upload_tlas / tbvh_update_tlas / tbvh_rebuild_tlas_device take sphere BLASes alone or mixed with BVH_GPU, BVH4_GPU and
+ * BVH8_CWBVH triangle BLASes (tiny_bvh_anim.cpp's scene); a sphere BLAS's bounds are its root box.  Such a TLAS walks every BLAS in its own
+ * layout (no 4- or 8-wide copies); a TLAS mixing sphere BLASes with voxel sets is refused.
+ * A sphere BLAS is refused (TBVH_E_INVALID) by refit and the tbvh_update_bvh_gpu / _bvh4_gpu / _cwbvh calls, opacity micromaps,
+ * tbvh_scene_download, the schedule hints, tbvh_cwbvh_set_hybrid, tbvh_wavefront_render (a TLAS with sphere BLASes too),
+ * tbvh_intersect_spheres (+ _device) and the _ex queries; tbvh_upload_tlas_double refuses it as a BLAS.
+ * ---------------------------------------------------------------------------------- */
+/* Validated before anything is allocated (TBVH_E_FORMAT names the first bad entry): a child pair beyond n_nodes, a leaf range beyond n_idx,
+ * prim_idx[k] >= n_spheres, a node reached twice (shared child or cycle), sizes beyond the 32-bit device offsets.  The spheres are gathered
+ * into leaf order at upload; tbvh_scene_layout = TBVH_LAYOUT_BVH2_WALD. */
+int tbvh_upload_custom_spheres(tbvh_context* ctx, const void* nodes32, uint64_t n_nodes, const uint32_t* prim_idx, uint64_t n_idx,
+                               const void* spheres16, uint64_t n_spheres, tbvh_scene** out);
+/* The library's builder for callers without tinybvh: a binned SAH BVH over the boxes pos -/+ r (the demos' sphereAABB).
+ * tbvh_host_blob(h, 0) = Wald nodes (32 bytes each), (h, 1) = primIdx; tbvh_host_layout = TBVH_LAYOUT_BVH2_WALD. */
+int tbvh_host_build_custom_spheres(const void* spheres16, uint64_t n, tbvh_hostbvh** out);
 
 #ifdef __cplusplus
 }

@@ -1035,3 +1035,49 @@ class VoxelSet(_Scene):
         check(lib.tbvh_upload_voxelset(self.ctx._h, _ptr(grid), _ptr(bricks), bricks.size // 512, _ptr(top), C.byref(self._h)), "tbvh_upload_voxelset")
         self.arrays = (grid, bricks, top)
         return self
+
+
+# ---- custom geometry: sphere BLASes (BVH::Build( customGetAABB, n ) + the anim demo's sphere callback) ----------------------------------------
+def host_build_custom_spheres(spheres: np.ndarray):
+    """(nodes32 as (n, 8) uint32, prim_idx) of the library's BVH over the boxes pos -/+ r of spheres {x, y, z, r} (tbvh_host_build_custom_spheres)."""
+    sph = np.ascontiguousarray(spheres, np.float32).reshape(-1, 4)
+    h = C.c_void_p()
+    check(lib.tbvh_host_build_custom_spheres(_ptr(sph), sph.shape[0], C.byref(h)), "tbvh_host_build_custom_spheres")
+    try:
+        out = []
+        for which, width in ((0, 8), (1, 1)):
+            n = int(lib.tbvh_host_blob_count(h, which))
+            p = lib.tbvh_host_blob(h, which)
+            a = np.ctypeslib.as_array((C.c_uint32 * (n * width)).from_address(p)).copy()
+            out.append(a.reshape(n, width) if width > 1 else a)
+    finally:
+        lib.tbvh_host_free(h)
+    return out[0], out[1]
+
+
+class SphereBVH(_Scene):
+    """A BVH over custom geometry (BVH::Build( customGetAABB, n ), tiny_bvh.h:2190-2219) whose primitives are spheres {x, y, z, r}, traced on
+    the device with the sphere callback of the reference's anim demo (kernels_custom.hip, DESIGN.md par. 12).  Intersect / IsOccluded take the
+    ordinary Ray records (RAY_DTYPE); a hit writes t, prim and inst = instIdx and leaves u, v as they were.  _bounds is the root box, so
+    TLAS.Build / Upload / RebuildOnDevice take it as a BLAS, alone or next to triangle BLASes."""
+    layout = LAYOUT_BVH2_WALD
+
+    def Build(self, spheres: np.ndarray) -> "SphereBVH":
+        """The library's host builder over the boxes pos -/+ r, then Upload."""
+        nodes, prim_idx = host_build_custom_spheres(spheres)
+        return self.Upload(nodes, prim_idx, spheres)
+
+    def Upload(self, nodes32: np.ndarray, prim_idx: np.ndarray, spheres: np.ndarray) -> "SphereBVH":
+        """The reference's own arrays: BVH::bvhNode (32-byte Wald nodes, usedNodes of them), BVH::primIdx (idxCount) and the spheres
+        {x, y, z, r} by primitive index (tbvh_upload_custom_spheres: validated before anything is allocated)."""
+        nodes32 = np.ascontiguousarray(nodes32).view(np.uint32).reshape(-1, 8)
+        prim_idx = np.ascontiguousarray(prim_idx, np.uint32).reshape(-1)
+        spheres = np.ascontiguousarray(spheres, np.float32).reshape(-1, 4)
+        if self._h:
+            self.free()
+            self._h = C.c_void_p()
+        check(lib.tbvh_upload_custom_spheres(self.ctx._h, _ptr(nodes32), nodes32.shape[0], _ptr(prim_idx), prim_idx.size, _ptr(spheres),
+                                             spheres.shape[0], C.byref(self._h)), "tbvh_upload_custom_spheres")
+        self.nodes, self.prim_idx, self.spheres = nodes32, prim_idx, spheres
+        self._bounds = np.concatenate([nodes32[0, 0:3].view(np.float32), nodes32[0, 4:7].view(np.float32)]).astype(np.float32)
+        return self

@@ -131,6 +131,9 @@ SYMBOLS = {
     "tbvh_upload_voxelset": (_i, [_vp, _vp, _vp, _u64, _vp, _pp]),
     "tbvh_host_build_voxelset": (_i, [_vp, _u32, _u32, _u32, _pp]),
     "tbvh_upload_voxelset_dense": (_i, [_vp, _vp, _u32, _u32, _u32, _pp]),
+    # custom-geometry sphere BLASes (capi_custom.hip)
+    "tbvh_upload_custom_spheres": (_i, [_vp, _vp, _u64, _vp, _u64, _vp, _u64, _pp]),
+    "tbvh_host_build_custom_spheres": (_i, [_vp, _u64, _pp]),
     # sphere-overlap queries (capi_sphere.hip)
     "tbvh_intersect_spheres": (_i, [_vp, _vp, _u64, _vp, _u64, _vp]),
     "tbvh_intersect_spheres_device": (_i, [_vp, _vp, _u64, _vp, _u64, _vp]),

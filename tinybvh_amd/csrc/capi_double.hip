@@ -212,6 +212,7 @@ int tbvh_upload_tlas_double(tbvh_context* c, const void* nodes64, uint64_t nNode
     for (uint64_t i = 0; i < nBlas; i++) {
         const tbvh_scene* b = blas[i];
         if (!b || b->ctx != c || b->isTlas || b->zombie) return fail(TBVH_E_INVALID, "tbvh_upload_tlas_double: BLAS %llu is null, freed, a TLAS, or from another context", (unsigned long long)i);
+        TBVH_REFUSE_CUSTOM(b, "tbvh_upload_tlas_double");
         if (!isDouble(b)) return fail(TBVH_E_INVALID, "tbvh_upload_tlas_double: BLAS %llu has layout %d; every BLAS must be a BVH_DOUBLE scene", (unsigned long long)i, b->layout);
     }
     if (int r = validateDouble((const NodeDbl*)nodes64, nNodes, idx, nIdx, nInst, "tbvh_upload_tlas_double", "n_inst")) return r;
@@ -246,6 +247,7 @@ int tbvh_upload_tlas_double(tbvh_context* c, const void* nodes64, uint64_t nNode
 
 int tbvh_intersect_ex_device(tbvh_scene* s, void* dRays, uint64_t n) {
     if (!s || (!dRays && n)) return fail(TBVH_E_INVALID, "tbvh_intersect_ex_device: null argument");
+    TBVH_REFUSE_CUSTOM(s, "tbvh_intersect_ex_device");
     if (!isDouble(s)) return fail(TBVH_E_INVALID, "tbvh_intersect_ex_device: scene layout %d is not BVH_DOUBLE (RayEx queries need a BVH_Double scene)", s->layout);
     if (((uintptr_t)dRays) & 15) return fail(TBVH_E_INVALID, "tbvh_intersect_ex_device: ray array must be 16-byte aligned");
     return launchDouble(s, (RayExRec*)dRays, n, nullptr);
@@ -253,6 +255,7 @@ int tbvh_intersect_ex_device(tbvh_scene* s, void* dRays, uint64_t n) {
 
 int tbvh_occluded_ex_device(tbvh_scene* s, const void* dRays, uint64_t n, uint8_t* dOcc) {
     if (!s || ((!dRays || !dOcc) && n)) return fail(TBVH_E_INVALID, "tbvh_occluded_ex_device: null argument");
+    TBVH_REFUSE_CUSTOM(s, "tbvh_occluded_ex_device");
     if (!isDouble(s)) return fail(TBVH_E_INVALID, "tbvh_occluded_ex_device: scene layout %d is not BVH_DOUBLE (RayEx queries need a BVH_Double scene)", s->layout);
     if (((uintptr_t)dRays) & 15) return fail(TBVH_E_INVALID, "tbvh_occluded_ex_device: ray array must be 16-byte aligned");
     return launchDouble(s, (RayExRec*)dRays, n, dOcc);
@@ -260,6 +263,7 @@ int tbvh_occluded_ex_device(tbvh_scene* s, const void* dRays, uint64_t n, uint8_
 
 int tbvh_intersect_ex(tbvh_scene* s, void* rays, uint64_t n) {
     if (!s || (!rays && n)) return fail(TBVH_E_INVALID, "tbvh_intersect_ex: null argument");
+    TBVH_REFUSE_CUSTOM(s, "tbvh_intersect_ex");
     if (!isDouble(s)) return fail(TBVH_E_INVALID, "tbvh_intersect_ex: scene layout %d is not BVH_DOUBLE (RayEx queries need a BVH_Double scene)", s->layout);
     if (n == 0) return 0;
     return hostQueryEx(s, rays, n, nullptr, "tbvh_intersect_ex");
@@ -267,6 +271,7 @@ int tbvh_intersect_ex(tbvh_scene* s, void* rays, uint64_t n) {
 
 int tbvh_occluded_ex(tbvh_scene* s, const void* rays, uint64_t n, uint8_t* occ) {
     if (!s || ((!rays || !occ) && n)) return fail(TBVH_E_INVALID, "tbvh_occluded_ex: null argument");
+    TBVH_REFUSE_CUSTOM(s, "tbvh_occluded_ex");
     if (!isDouble(s)) return fail(TBVH_E_INVALID, "tbvh_occluded_ex: scene layout %d is not BVH_DOUBLE (RayEx queries need a BVH_Double scene)", s->layout);
     if (n == 0) return 0;
     return hostQueryEx(s, (void*)rays, n, occ, "tbvh_occluded_ex");

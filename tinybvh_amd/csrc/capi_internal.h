@@ -52,6 +52,14 @@ int fail(int code, const char* fmt, ...);   // sets tbvh_last_error() of the cal
             return tbvh_capi::fail(TBVH_E_INVALID, "%s: a VOXELSET scene takes the queries and can be a TLAS's BLAS; nothing else", who); \
     } while (0)
 
+// A custom-geometry sphere BLAS (TBVH_LAYOUT_BVH2_WALD, capi_custom.hip) answers the ordinary queries (launchQuery) and can be a TLAS's BLAS; the
+// entry points that have no sphere form refuse it with this, before they touch the scene's memory or launch anything.
+#define TBVH_REFUSE_CUSTOM(scene, who)                                                                                                    \
+    do {                                                                                                                                  \
+        if ((scene) && (scene)->layout == TBVH_LAYOUT_BVH2_WALD)                                                                          \
+            return tbvh_capi::fail(TBVH_E_INVALID, "%s: a sphere BLAS (custom geometry) takes the queries and can be a TLAS's BLAS; nothing else", who); \
+    } while (0)
+
 #define HIP_TRY(expr)                                                                        \
     do {                                                                                     \
         hipError_t e_ = (expr);                                                              \
@@ -170,6 +178,7 @@ struct tbvh_scene {
     BlasDesc* blasDesc = nullptr;
     int blasLayout = 0;
     bool blasMixCw2 = false;          // blasLayout == 0 and every BLAS is BVH8_CWBVH or BVH_GPU: the reference's two BLAS types (traverse_tlas.cl:50-72)
+    bool blasSpheres = false;         // some BLAS is a sphere BLAS (capi_custom.hip): every query takes the flat loop with the sphere step, BLASes in their own layouts
     // any-hit queries may enter the BLASes through other arrays than closest-hit ones (BVH4_GPU BLASes: their own stream for closest hits — k_tlas4 —, their
     // 8-wide copies for IsOccluded — k_tlas8, + 28 % on 1000 instances —: capi_scene.hip: reclassifyTlas); blasDescAny == nullptr: the same as above
     BlasDesc* blasDescAny = nullptr;

@@ -217,7 +217,10 @@ static void launchTlasKernels(tbvh_scene* s, QueryArgs& q, bool any, uint32_t bl
     const int layout = own ? s->blasLayoutAny : s->blasLayout;
     const bool mix = own ? s->blasMixCw2Any : s->blasMixCw2;
     const BlasDesc* desc = own ? s->blasDescAny : s->blasDesc;
-    if (s->tlas4 && layout == TBVH_LAYOUT_BVH4_GPU) {   // BVH4_GPU BLASes: the unified 4-wide kernel
+    if (s->blasSpheres) {   // sphere BLASes, alone or with triangle BLASes walked in their own layouts: the flat loop with the sphere step (kernels_tlas.hip)
+        q.spillStride = c->spillEntries / 2;   // 8-byte stack entries
+        launch_tlas_custom(any, layout, s->nodes, s->tlasIdx, s->instances, desc, q, c->status, blocks, c->stream);
+    } else if (s->tlas4 && layout == TBVH_LAYOUT_BVH4_GPU) {   // BVH4_GPU BLASes: the unified 4-wide kernel
         q.spillStride = c->spillEntries;   // 32-bit stack entries
         launch_tlas4(any, 0, s->tlas4, s->instances, desc, q, c->status, blocks, c->stream, blocks7);
     } else if (s->tlas8 && (layout == TBVH_LAYOUT_CWBVH || mix)) {   // BVH8_CWBVH BLASes (or those and BVH_GPU ones): the unified 8-wide kernel
@@ -337,7 +340,7 @@ int launchQuery(tbvh_scene* s, RayRec* d_rays, uint64_t n, uint8_t* d_occ, bool 
     if (!s->wideTried && !s->isTlas && s->variant == 0 && (nDev || n >= 1024u) && (s->layout == TBVH_LAYOUT_BVH_GPU || s->layout == TBVH_LAYOUT_BVH4_GPU)) makeWideCopy(s);   // first query of this scene (not part of its time)
     if (s->wide && s->variant == 0 && !s->wideTlasOnly) return launchQuery(s->wide, d_rays, n, d_occ, fresh, freshTmax, nDev);   // BVH_GPU with an 8-wide copy (capi_scene.hip: makeWideCopy)
     const bool any = d_occ != nullptr;
-    if (any && s->isTlas && !s->anyHitSeen) {   // the first IsOccluded through this TLAS (not part of its time): its BVH4_GPU and BVH_GPU BLASes are entered through 8-wide copies by any-hit queries
+    if (any && s->isTlas && !s->anyHitSeen && !s->blasSpheres) {   // the first IsOccluded through this TLAS (not part of its time): its BVH4_GPU and BVH_GPU BLASes are entered through 8-wide copies by any-hit queries
         s->anyHitSeen = true;
         for (tbvh_scene* b : s->blasList)
             if ((b->layout == TBVH_LAYOUT_BVH4_GPU || b->layout == TBVH_LAYOUT_BVH_GPU) && !b->wideTried && b->variant == 0) makeWideCopy(b);   // (re-classifies the TLASes over b, this one included)
@@ -430,6 +433,10 @@ int launchQuery(tbvh_scene* s, RayRec* d_rays, uint64_t n, uint8_t* d_occ, bool 
     case TBVH_LAYOUT_CWBVH:
         q.spillStride = c->spillEntries / 2;  // 8-byte entries
         if (int r = launchCwbvhKernels(s, q, CwbvhLaunch{any, small, probedSmall, sizeClass, blocks, blocksBase, poolArea + (size_t)kPoolParts * kPoolCounterStride})) return r;
+        break;
+    case TBVH_LAYOUT_BVH2_WALD:   // a sphere BLAS (kernels_custom.hip)
+        q.spillStride = c->spillEntries / 2;  // 8-byte entries
+        launch_custom(any, s->nodes, s->tris, q, c->status, blocks, c->stream);
         break;
     case TBVH_LAYOUT_VOXELSET:
         q.spillStride = c->spillEntries;

@@ -370,6 +370,21 @@ static const tbvh_scene* blasView(const tbvh_scene* b, bool any, bool allow4 = t
 // With every BLAS copied, BLASes of different layouts under one TLAS share one kernel class per kind of query instead of the flat three-state loop.
 int reclassifyTlas(tbvh_scene* t) {
     const size_t nBlas = t->blasList.size();
+    if (t->blasSpheres) {   // sphere BLASes (capi_custom.hip): one class for both kinds of query, every BLAS through its own arrays (no copies, no wide TLAS)
+        std::vector<BlasDesc> desc(nBlas);
+        int layout = 0;
+        for (size_t i = 0; i < nBlas; i++) {
+            const tbvh_scene* b = t->blasList[i];
+            layout = i == 0 ? b->layout : (layout == b->layout ? layout : 0);
+            desc[i] = BlasDesc{b->nodes, b->tris, b->opmap, b->opmapN, (uint32_t)b->layout};
+        }
+        t->blasLayout = layout; t->blasMixCw2 = false; t->blasLayoutAny = -1; t->blasMixCw2Any = false;
+        if (!t->blasDesc) HIP_TRY(hipMalloc((void**)&t->blasDesc, nBlas * sizeof(BlasDesc)));
+        HIP_TRY(hipStreamSynchronize(t->ctx->stream));   // (launches in flight read the old descriptors)
+        HIP_TRY(hipMemcpy(t->blasDesc, desc.data(), nBlas * sizeof(BlasDesc), hipMemcpyHostToDevice));
+        if (t->blasDescAny) { hipFree(t->blasDescAny); t->blasDescAny = nullptr; }
+        return 0;
+    }
     std::vector<BlasDesc> desc[2] = {std::vector<BlasDesc>(nBlas), std::vector<BlasDesc>(nBlas)};
     int layout[2] = {0, 0};
     bool mix[2] = {false, false}, same = true;
@@ -467,19 +482,23 @@ int tbvh_upload_tlas(tbvh_context* c, const void* nodes64, uint64_t nNodes, cons
     for (uint64_t i = 0; i < nBlas; i++) {
         const tbvh_scene* b = blas[i];
         if (!b || b->ctx != c || b->isTlas || b->zombie) return fail(TBVH_E_INVALID, "BLAS %llu is null, freed, a TLAS, or from another context", (unsigned long long)i);
-        if (b->layout != TBVH_LAYOUT_CWBVH && b->layout != TBVH_LAYOUT_BVH4_GPU && b->layout != TBVH_LAYOUT_BVH_GPU && b->layout != TBVH_LAYOUT_VOXELSET)
+        if (b->layout != TBVH_LAYOUT_CWBVH && b->layout != TBVH_LAYOUT_BVH4_GPU && b->layout != TBVH_LAYOUT_BVH_GPU && b->layout != TBVH_LAYOUT_VOXELSET &&
+            b->layout != TBVH_LAYOUT_BVH2_WALD)
             return fail(TBVH_E_INVALID, "BLAS %llu: layout %d cannot be a BLAS", (unsigned long long)i, b->layout);
         // voxel sets only all together (kernels_voxel.hip); a TLAS mixing them with triangle BLASes would need the kernels_tlas* loops to enter them
         if ((b->layout == TBVH_LAYOUT_VOXELSET) != (blas[0]->layout == TBVH_LAYOUT_VOXELSET))
             return fail(TBVH_E_INVALID, "BLAS %llu: a TLAS over voxel sets takes voxel sets only (BLAS 0 has layout %d, this one %d)", (unsigned long long)i, blas[0]->layout, b->layout);
     }
+    // sphere BLASes (capi_custom.hip) alone or with triangle BLASes: the flat loop with the sphere step enters every BLAS in its own layout, no copies
+    bool spheres = false;
+    for (uint64_t i = 0; i < nBlas; i++) spheres |= blas[i]->layout == TBVH_LAYOUT_BVH2_WALD;
     TBVH_ENTER(c);
-    for (uint64_t i = 0; i < nBlas; i++)   // closest-hit queries enter BVH_GPU and BVH8_CWBVH BLASes through 4-wide copies (blasView), made now; the 8-wide copies any-hit queries
-                                           // enter BVH_GPU and BVH4_GPU BLASes through are made by the TLAS's first any-hit query (launchQuery)
+    for (uint64_t i = 0; i < nBlas && !spheres; i++)   // closest-hit queries enter BVH_GPU and BVH8_CWBVH BLASes through 4-wide copies (blasView), made now; the 8-wide copies any-hit queries
+                                                       // enter BVH_GPU and BVH4_GPU BLASes through are made by the TLAS's first any-hit query (launchQuery)
         if ((blas[i]->layout == TBVH_LAYOUT_BVH_GPU || blas[i]->layout == TBVH_LAYOUT_CWBVH) && !blas[i]->wide4Tried && blas[i]->variant == 0) makeWide4Copy(blas[i]);
     tbvh_scene* s = newScene(c, TBVH_LAYOUT_BVH_GPU);
     if (!s) return fail(TBVH_E_NOMEM, "out of host memory");
-    s->isTlas = true; s->nBlas = nBlas;
+    s->isTlas = true; s->nBlas = nBlas; s->blasSpheres = spheres;
     s->blasLayout = -1;   // (not classified yet)
     for (uint64_t i = 0; i < nBlas; i++) { s->blasList.push_back(blas[i]); blas[i]->usedBy.push_back(s); }
     if (int r = reclassifyTlas(s)) { tbvh_free_scene(s); return r; }
@@ -501,6 +520,7 @@ int tbvh_update_tlas(tbvh_scene* s, const void* nodes64, uint64_t nNodes, const 
 int tbvh_update_bvh_gpu(tbvh_scene* s, const void* nodes64, uint64_t nNodes, const uint32_t* primIdx, uint64_t nIdx, const void* verts16, uint64_t nTris) {
     TBVH_REFUSE_DOUBLE(s, "tbvh_update_bvh_gpu");
     TBVH_REFUSE_VOXEL(s, "tbvh_update_bvh_gpu");
+    TBVH_REFUSE_CUSTOM(s, "tbvh_update_bvh_gpu");
     if (!s || s->isTlas || s->layout != TBVH_LAYOUT_BVH_GPU || !nodes64 || !primIdx || !verts16 || !nNodes) return fail(TBVH_E_INVALID, "tbvh_update_bvh_gpu: not a BVH_GPU scene or null/empty argument");
     if (nNodes * 4 > s->capNodeBlocks || nIdx * 3 > s->capTriBlocks) return fail(TBVH_E_INVALID, "tbvh_update_bvh_gpu: the blob (%llu nodes, %llu indices) is larger than the one uploaded: free the scene and upload", (unsigned long long)nNodes, (unsigned long long)nIdx);
     if (const char* why = validate_bvh_gpu((const NodeAL*)nodes64, nNodes, nIdx)) return fail(why == kValidateNoMemory ? TBVH_E_NOMEM : TBVH_E_FORMAT, "%s", why);
@@ -525,6 +545,7 @@ int tbvh_update_bvh_gpu(tbvh_scene* s, const void* nodes64, uint64_t nNodes, con
 int tbvh_update_bvh4_gpu(tbvh_scene* s, const void* blocks16, uint64_t nBlocks) {
     TBVH_REFUSE_DOUBLE(s, "tbvh_update_bvh4_gpu");
     TBVH_REFUSE_VOXEL(s, "tbvh_update_bvh4_gpu");
+    TBVH_REFUSE_CUSTOM(s, "tbvh_update_bvh4_gpu");
     if (!s || s->isTlas || s->layout != TBVH_LAYOUT_BVH4_GPU || !blocks16 || nBlocks < 4) return fail(TBVH_E_INVALID, "tbvh_update_bvh4_gpu: not a BVH4_GPU scene or null/empty argument");
     if (nBlocks > s->capNodeBlocks) return fail(TBVH_E_INVALID, "tbvh_update_bvh4_gpu: the blob (%llu blocks) is larger than the one uploaded (%llu): free the scene and upload", (unsigned long long)nBlocks, (unsigned long long)s->capNodeBlocks);
     if (const char* why = validate_bvh4_gpu((const Vec4*)blocks16, nBlocks)) return fail(why == kValidateNoMemory ? TBVH_E_NOMEM : TBVH_E_FORMAT, "%s", why);
@@ -577,6 +598,7 @@ static int updateCwbvhImpl(tbvh_scene* s, const void* nodes16, uint64_t nNodeBlo
 int tbvh_update_cwbvh(tbvh_scene* s, const void* nodes16, uint64_t nNodeBlocks, const void* tris16, uint64_t nTriBlocks) {
     TBVH_REFUSE_DOUBLE(s, "tbvh_update_cwbvh");
     TBVH_REFUSE_VOXEL(s, "tbvh_update_cwbvh");
+    TBVH_REFUSE_CUSTOM(s, "tbvh_update_cwbvh");
     if (s && !s->isTlas && (s->wide4 || s->pendingCopies)) {   // the 4-wide copy TLASes enter this BLAS through is of the old tree (also if the update is refused: harmless)
         TBVH_ENTER(s->ctx);
         dropCopiesAfterUpdate(s);
@@ -746,6 +768,7 @@ int refreshBlasDescs(tbvh_scene* b) {
 int tbvh_set_opacity_micromaps(tbvh_scene* s, const uint32_t* mapData, uint32_t N, uint64_t nTris, int onDevice) {
     TBVH_REFUSE_DOUBLE(s, "tbvh_set_opacity_micromaps");
     TBVH_REFUSE_VOXEL(s, "tbvh_set_opacity_micromaps");
+    TBVH_REFUSE_CUSTOM(s, "tbvh_set_opacity_micromaps");
     if (!s || s->isTlas) return fail(TBVH_E_INVALID, "tbvh_set_opacity_micromaps: not a BLAS scene (set the maps on the BLASes before uploading their TLAS)");
     tbvh_context* c = s->ctx;
     TBVH_ENTER(c);
@@ -781,6 +804,7 @@ int tbvh_set_opacity_micromaps(tbvh_scene* s, const uint32_t* mapData, uint32_t 
 int tbvh_scene_download(tbvh_scene* s, int which, void* dst, uint64_t capBytes, uint64_t* bytesOut) {
     TBVH_REFUSE_DOUBLE(s, "tbvh_scene_download");
     TBVH_REFUSE_VOXEL(s, "tbvh_scene_download");
+    TBVH_REFUSE_CUSTOM(s, "tbvh_scene_download");
     if (!s || s->isTlas || (which != 0 && which != 1)) return fail(TBVH_E_INVALID, "tbvh_scene_download: not a BLAS scene or bad blob selector");
     tbvh_context* c = s->ctx;
     TBVH_ENTER(c);
@@ -815,6 +839,7 @@ bool refitDropsCopies(tbvh_scene* s) {
 int tbvh_refit(tbvh_scene* s, const void* verts16, uint64_t nTris, int onDevice) {
     TBVH_REFUSE_DOUBLE(s, "tbvh_refit");
     TBVH_REFUSE_VOXEL(s, "tbvh_refit");
+    TBVH_REFUSE_CUSTOM(s, "tbvh_refit");
     if (!s || !verts16 || !nTris) return fail(TBVH_E_INVALID, "tbvh_refit: null/empty argument");
     if (s->isTlas) return fail(TBVH_E_INVALID, "tbvh_refit: a TLAS is rebuilt with tbvh_rebuild_tlas_device / tbvh_update_tlas");
     tbvh_context* c = s->ctx;
@@ -997,6 +1022,7 @@ int tbvh_debug_coherent_schedule(tbvh_scene* s, int anyhit, uint32_t out[4]) {
 int tbvh_scene_get_schedule_hint(tbvh_scene* s, tbvh_schedule_hint* out) {
     TBVH_REFUSE_DOUBLE(s, "tbvh_scene_get_schedule_hint");
     TBVH_REFUSE_VOXEL(s, "tbvh_scene_get_schedule_hint");
+    TBVH_REFUSE_CUSTOM(s, "tbvh_scene_get_schedule_hint");
     if (!s || !out) return fail(TBVH_E_INVALID, "tbvh_scene_get_schedule_hint: null argument");
     TBVH_LOCK(s->ctx);
     std::memset(out, 0, sizeof *out);
@@ -1014,6 +1040,7 @@ int tbvh_scene_get_schedule_hint(tbvh_scene* s, tbvh_schedule_hint* out) {
 int tbvh_scene_set_schedule_hint(tbvh_scene* s, const tbvh_schedule_hint* hint) {
     TBVH_REFUSE_DOUBLE(s, "tbvh_scene_set_schedule_hint");
     TBVH_REFUSE_VOXEL(s, "tbvh_scene_set_schedule_hint");
+    TBVH_REFUSE_CUSTOM(s, "tbvh_scene_set_schedule_hint");
     if (!s || !hint) return fail(TBVH_E_INVALID, "tbvh_scene_set_schedule_hint: null argument");
     for (int k = 0; k < 3; k++) if (hint->closest_hit[k] > 3 || hint->any_hit[k] > 3) return fail(TBVH_E_INVALID, "tbvh_scene_set_schedule_hint: entries are 0 (measure), 1 (deferred + gated), 2 (strict) or 3 (one traversal per wave)");
     if (hint->reserved[0] > 3 || hint->reserved[1] > 3) return fail(TBVH_E_INVALID, "tbvh_scene_set_schedule_hint: entries are 0 (measure), 1 (deferred + gated), 2 (strict) or 3 (one traversal per wave)");
@@ -1045,6 +1072,7 @@ int tbvh_set_variant(tbvh_scene* s, int v) {
 int tbvh_cwbvh_set_hybrid(tbvh_scene* s, int64_t packedNodes) {
     TBVH_REFUSE_DOUBLE(s, "tbvh_cwbvh_set_hybrid");
     TBVH_REFUSE_VOXEL(s, "tbvh_cwbvh_set_hybrid");
+    TBVH_REFUSE_CUSTOM(s, "tbvh_cwbvh_set_hybrid");
     if (!s || s->isTlas || s->layout != TBVH_LAYOUT_CWBVH) return fail(TBVH_E_INVALID, "tbvh_cwbvh_set_hybrid: not a BVH8_CWBVH scene");
     tbvh_context* c = s->ctx;
     TBVH_ENTER(c);

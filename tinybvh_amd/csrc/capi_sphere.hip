@@ -13,6 +13,7 @@ int checkSphereArgs(tbvh_scene* s, const void* spheres, uint64_t n, const void* 
     if (!s) return fail(TBVH_E_INVALID, "%s: null scene", who);
     TBVH_REFUSE_DOUBLE(s, who);
     TBVH_REFUSE_VOXEL(s, who);
+    TBVH_REFUSE_CUSTOM(s, who);
     if (s->isTlas) return fail(TBVH_E_INVALID, "%s: a TLAS has no sphere query (the reference's would read instance indices as triangles); query its BLASes", who);
     if (s->layout != TBVH_LAYOUT_BVH_GPU && s->layout != TBVH_LAYOUT_BVH4_GPU && s->layout != TBVH_LAYOUT_CWBVH)
         return fail(TBVH_E_INVALID, "%s: scene layout %d has no sphere query", who, s->layout);

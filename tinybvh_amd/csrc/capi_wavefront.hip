@@ -86,6 +86,9 @@ int tbvh_wavefront_render(tbvh_wavefront* w, tbvh_scene* scene, const void* dVer
                           tbvh_wf_stats* stats) {
     TBVH_REFUSE_DOUBLE(scene, "tbvh_wavefront_render");
     TBVH_REFUSE_VOXEL(scene, "tbvh_wavefront_render");
+    TBVH_REFUSE_CUSTOM(scene, "tbvh_wavefront_render");
+    if (scene && scene->isTlas && scene->blasSpheres)
+        return fail(TBVH_E_INVALID, "tbvh_wavefront_render: a TLAS with sphere BLASes (custom geometry) takes the queries only (the path tracer shades triangles)");
     if (scene && scene->isTlas && !scene->blasList.empty() && scene->blasList[0]->layout == TBVH_LAYOUT_VOXELSET)
         return fail(TBVH_E_INVALID, "tbvh_wavefront_render: a TLAS over VOXELSET scenes takes the queries only (the path tracer shades triangles)");
     if (!w || !scene || !cam || !p) return fail(TBVH_E_INVALID, "tbvh_wavefront_render: null argument");

@@ -1485,6 +1485,46 @@ static const char* validate_cwbvh_impl(const Vec4* nodes, uint64_t nNodes, uint6
 // The walks above allocate (a visited flag per node, a stack): running out of host memory on a very large blob must come back through the C ABI
 // as TBVH_E_NOMEM, not unwind through extern "C" (kValidateNoMemory is compared by address in capi_internal.h: validate_failed).
 const char* const kValidateNoMemory = "out of host memory while validating the blob";
+// Wald nodes (BVH::bvhNode) over primIdx over nPrims primitives: every reachable child pair and leaf range in range, every primIdx entry a
+// primitive, and a tree (no node reached twice: a cycle would never end a traversal).  Names the first bad entry.
+static const char* validate_bvh2_impl(const Node2* n, uint64_t nNodes, const uint32_t* primIdx, uint64_t nIdx, uint64_t nPrims) {
+    static thread_local char msg[192];
+    if (nNodes == 0) return "BVH (Wald nodes): empty node array";
+    for (uint64_t k = 0; k < nIdx; k++)
+        if (primIdx[k] >= nPrims) {
+            std::snprintf(msg, sizeof msg, "BVH (Wald nodes): primIdx[%llu] = %u >= %llu primitives", (unsigned long long)k, primIdx[k], (unsigned long long)nPrims);
+            return msg;
+        }
+    std::vector<uint8_t> seen(nNodes, 0);
+    std::vector<uint32_t> stack{0};
+    seen[0] = 1;
+    while (!stack.empty()) {
+        const uint32_t i = stack.back(); stack.pop_back();
+        if (n[i].triCount) {
+            if ((uint64_t)n[i].leftFirst + n[i].triCount > nIdx) {
+                std::snprintf(msg, sizeof msg, "BVH (Wald nodes): leaf %u: leftFirst %u + triCount %u exceeds the %llu primIdx entries", i, n[i].leftFirst, n[i].triCount, (unsigned long long)nIdx);
+                return msg;
+            }
+            continue;
+        }
+        if ((uint64_t)n[i].leftFirst + 1 >= nNodes) {
+            std::snprintf(msg, sizeof msg, "BVH (Wald nodes): node %u: children %u, %u beyond the %llu nodes", i, n[i].leftFirst, n[i].leftFirst + 1u, (unsigned long long)nNodes);
+            return msg;
+        }
+        for (const uint32_t c : {n[i].leftFirst, n[i].leftFirst + 1}) {
+            if (seen[c]) {
+                std::snprintf(msg, sizeof msg, "BVH (Wald nodes): node %u is reached twice (child of node %u): the node array is not a tree", c, i);
+                return msg;
+            }
+            seen[c] = 1; stack.push_back(c);
+        }
+    }
+    return nullptr;
+}
+
+const char* validate_bvh2(const Node2* n, uint64_t nNodes, const uint32_t* primIdx, uint64_t nIdx, uint64_t nPrims) {
+    try { return validate_bvh2_impl(n, nNodes, primIdx, nIdx, nPrims); } catch (const std::bad_alloc&) { return kValidateNoMemory; }
+}
 const char* validate_bvh_gpu(const NodeAL* n, uint64_t nNodes, uint64_t nIdx) {
     try { return validate_bvh_gpu_impl(n, nNodes, nIdx); } catch (const std::bad_alloc&) { return kValidateNoMemory; }
 }

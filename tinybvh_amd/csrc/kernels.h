@@ -98,6 +98,14 @@ struct SphereArgs {
 };
 void launch_spheres(int layout, const SphereArgs& q, uint32_t* status, uint32_t blocks, hipStream_t s);   // status |= 16: a record's primitive is beyond nTris
 
+// custom-geometry sphere BLASes (kernels_custom.hip, custom_sphere.h): nodes = the Wald nodes (32 bytes: 2 float4 each), recs = the spheres gathered
+// in primIdx order, 2 float4 each ({x, y, z, r}, {prim, 0, 0, 0})
+void launch_custom(bool anyhit, const float4* nodes, const float4* recs, const QueryArgs& q, uint32_t* status, uint32_t blocks, hipStream_t s);
+// TLASes with sphere BLASes (kernels_tlas.hip: the flat loop with the sphere step): blasLayout = TBVH_LAYOUT_BVH2_WALD when every BLAS is a sphere
+// BLAS, 0 when they mix with BVH_GPU / BVH4_GPU / BVH8_CWBVH BLASes (BlasDesc::layout per BLAS: nodes = Wald nodes, tris = sphere records)
+void launch_tlas_custom(bool anyhit, int blasLayout, const float4* tlasNodes, const uint32_t* tlasIdx, const float4* instances,
+                        const BlasDesc* blas, const QueryArgs& q, uint32_t* status, uint32_t blocks, hipStream_t s);
+
 // device TLAS rebuild (kernels_tlasbuild.hip)
 size_t tlas_build_scratch_bytes(uint32_t n, size_t* sortTempBytes);
 hipError_t launch_tlas_rebuild(float4* tlasNodes, uint32_t* tlasIdx, float4* instances, const float* transformsDev, const float* blasBoundsDev,

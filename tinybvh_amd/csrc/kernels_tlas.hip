@@ -25,6 +25,7 @@
 #include "ray_pool.h"
 #include "kernels.h"
 #include "cwbvh_node.h"
+#include "custom_sphere.h"
 
 namespace tbvh {
 
@@ -59,7 +60,9 @@ struct RayL {  // a ray in some space + its current best hit
 // is what nested loops cost (three levels of "everybody waits for the slowest": round 1's first kernel).  Idle lanes take new
 // rays as in the other kernels.  Per ray the order of instances, nodes and triangles is the nested version's.
 // ---------------------------------------------------------------------------------------------------------------
-template <bool ANYHIT, int BLAS_LAYOUT, int LDS_N, int REFILL_MIN, int PHASE_MIN, bool ADAPT, bool STATS = false>
+// SPHERES: the BLAS step also walks custom-geometry sphere BLASes (layout TBVH_LAYOUT_BVH2_WALD, custom_sphere.h) — only the k_tlas_flat_sph_*
+// kernels; the others compile as if the step did not exist.
+template <bool ANYHIT, int BLAS_LAYOUT, int LDS_N, int REFILL_MIN, int PHASE_MIN, bool ADAPT, bool STATS = false, bool SPHERES = false>
 __device__ __forceinline__ void tlas_flat_body(const float4* __restrict__ tlasNodes, const uint32_t* __restrict__ tlasIdx,
                                                const float4* __restrict__ instances, const BlasDesc* __restrict__ blas, const QueryArgs& q,
                                                StackT<LDS_N>& st, RayPool<64>& pool, const uint64_t nRaysTotal) {
@@ -79,6 +82,9 @@ __device__ __forceinline__ void tlas_flat_body(const float4* __restrict__ tlasNo
     // CWBVH BLAS state (kernels_cwbvh.hip: k_cwbvh)
     uint32_t oct = 0;
     uint2 ng = make_uint2(0u, 0u), tg = make_uint2(0u, 0u);
+    // sphere BLAS state (SPHERES only; kernels_custom.hip: k_custom): the callback's factors for the instance's D; offset (children of the node to
+    // visit), leafQ0 (next sphere record) and leafCnt (spheres left) as above
+    SphereRay sr{0.f, 0.f};
 
     LockstepGovernor gov;   // ADAPT only: lockstep (whole-wave generations) while the rays are coherent, per-lane replacement otherwise
     gov.init();
@@ -116,7 +122,44 @@ __device__ __forceinline__ void tlas_flat_body(const float4* __restrict__ tlasNo
         if (mode == M_BLAS) { if (runC) {
             bool pop = false;   // this lane's BLAS step ended with nothing pending: take the next stack entry (or leave the BLAS)
             const uint32_t lay = BLAS_LAYOUT ? (uint32_t)BLAS_LAYOUT : blay;
-            if (lay == (uint32_t)kLayoutCwbvh) {
+            if (SPHERES && lay == (uint32_t)kLayoutBvh2Wald) {   // a sphere BLAS (kernels_custom.hip: k_custom)
+                if (leafCnt != 0) {   // one sphere
+                    const float4 s = btris[(size_t)leafQ0 * 2], pr = btris[(size_t)leafQ0 * 2 + 1];
+                    leafQ0++; leafCnt--;
+                    float t;
+                    if (sphere_test(O, D, s, sr, t)) {
+                        const uint32_t prim = as_u32(pr.x);
+                        if (ANYHIT) { found = true; hitInst = curInst; done = true; }
+                        else if (sphere_wins(t, prim, curInst, found, hit, hitInst)) {
+                            // u, v as the record had them on input (the callback leaves them alone; a triangle found before may have set them)
+                            const float4 h0 = q.fresh ? make_float4(0.f, 0.f, 0.f, 0.f) : q.rays[ri].hit;
+                            hit = make_float4(t, h0.y, h0.z, as_f32(prim));
+                            found = true; hitInst = curInst;
+                        }
+                    }
+                    if (!done && leafCnt == 0) pop = true;
+                } else {   // one node: its two children
+                    const float4 a0 = bnodes[(size_t)offset * 2], a1 = bnodes[(size_t)offset * 2 + 1], b0 = bnodes[(size_t)offset * 2 + 2], b1 = bnodes[(size_t)offset * 2 + 3];
+                    const float bound = cull_bound(hit.x);
+                    const float3 sro = make_float3(O.x * rD.x, O.y * rD.y, O.z * rD.z);
+                    const bool spx = D.x >= 0.f, spy = D.y >= 0.f, spz = D.z >= 0.f;
+                    float d1 = wald_slab(a0, a1, rD, sro, spx, spy, spz, bound), d2 = wald_slab(b0, b1, rD, sro, spx, spy, spz, bound);
+                    uint2 c1 = make_uint2(as_u32(a0.w), as_u32(a1.w)), c2 = make_uint2(as_u32(b0.w), as_u32(b1.w));
+                    if (d1 > d2) { const float tf = d1; d1 = d2; d2 = tf; const uint2 tc = c1; c1 = c2; c2 = tc; }
+                    if (d1 == kFar) pop = true;
+                    else {
+                        if (d2 != kFar) st.push(c2);
+                        if (c1.y) { leafQ0 = c1.x; leafCnt = c1.y; } else offset = c1.x;
+                    }
+                }
+                if (pop) {
+                    if (st.sp == base) mode = M_INST;
+                    else {
+                        const uint2 e = st.pop();
+                        if (e.y) { leafQ0 = e.x; leafCnt = e.y; } else offset = e.x;
+                    }
+                }
+            } else if (lay == (uint32_t)kLayoutCwbvh) {
                 if (tg.y != 0) {   // one triangle
                     const uint32_t ti = 31u - (uint32_t)__clz(tg.y);
                     tg.y &= ~(1u << ti);
@@ -293,7 +336,13 @@ __device__ __forceinline__ void tlas_flat_body(const float4* __restrict__ tlasNo
                     bnodes = GlobalF4(bd.nodes); btris = GlobalF4(bd.tris);
                     curInst = ii; base = st.sp; mode = M_BLAS;
                     if (BLAS_LAYOUT == 0) blay = bd.layout;
-                    if ((BLAS_LAYOUT ? (uint32_t)BLAS_LAYOUT : blay) == (uint32_t)kLayoutCwbvh) {
+                    if (SPHERES && (BLAS_LAYOUT ? (uint32_t)BLAS_LAYOUT : blay) == (uint32_t)kLayoutBvh2Wald) {
+                        // the callback's factors for this instance's D and the ray's incoming tmax (read again from the record); the root is entered
+                        // without a box test, as a one-leaf tree if it is a leaf
+                        sr = sphere_ray(D, q.fresh ? q.freshTmax : q.rays[ri].hit.x);
+                        const uint32_t rootFirst = as_u32(bnodes[0].w), rootCount = as_u32(bnodes[1].w);
+                        if (rootCount) { leafQ0 = rootFirst; leafCnt = rootCount; } else { offset = rootFirst; leafCnt = 0; }
+                    } else if ((BLAS_LAYOUT ? (uint32_t)BLAS_LAYOUT : blay) == (uint32_t)kLayoutCwbvh) {
                         oct = 7u - ((D.x < 0 ? 4u : 0u) | (D.y < 0 ? 2u : 0u) | (D.z < 0 ? 1u : 0u));
                         ng = make_uint2(0u, 0x80000000u); tg = make_uint2(0u, 0u);
                     } else { offset = 0; leafCnt = 0; leafCntB = 0; }
@@ -371,6 +420,25 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(6, 6))) void
     if (st.overflow) atomicOr(status, 1u);
 }
 
+// the same with the sphere-BLAS step (TLASes with custom-geometry sphere BLASes: kernels_custom.hip's walk per sphere instance); sphere BLASes mixed
+// with triangle layouts get 4 waves per SIMD: at 5 the closest-hit kernel spills (four BLAS steps inlined)
+template <bool ANYHIT, int BLAS_LAYOUT, int LDS_N = 12, int REFILL_MIN = 16, int PHASE_MIN = 16>
+__global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(4, 4))) void k_tlas_flat_sph_w4(const float4* __restrict__ tlasNodes, const uint32_t* __restrict__ tlasIdx,
+                                                  const float4* __restrict__ instances, const BlasDesc* __restrict__ blas, QueryArgs q,
+                                                  uint32_t* __restrict__ status) {
+    TBVH_TLAS_PROLOGUE
+    tlas_flat_body<ANYHIT, BLAS_LAYOUT, LDS_N, REFILL_MIN, PHASE_MIN, false, false, true>(tlasNodes, tlasIdx, instances, blas, q, st, pool, nRaysTotal);
+    if (st.overflow) atomicOr(status, 1u);
+}
+template <bool ANYHIT, int BLAS_LAYOUT, int LDS_N = 12, int REFILL_MIN = 16, int PHASE_MIN = 16>
+__global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(6, 6))) void k_tlas_flat_sph_w6(const float4* __restrict__ tlasNodes, const uint32_t* __restrict__ tlasIdx,
+                                                  const float4* __restrict__ instances, const BlasDesc* __restrict__ blas, QueryArgs q,
+                                                  uint32_t* __restrict__ status) {
+    TBVH_TLAS_PROLOGUE
+    tlas_flat_body<ANYHIT, BLAS_LAYOUT, LDS_N, REFILL_MIN, PHASE_MIN, false, false, true>(tlasNodes, tlasIdx, instances, blas, q, st, pool, nRaysTotal);
+    if (st.overflow) atomicOr(status, 1u);
+}
+
 }  // namespace
 
 // The flat loop serves what the unified two-level kernels (kernels_tlas4 / 8 / 2.hip) do not: TLASes that mix BVH4_GPU BLASes with other
@@ -388,6 +456,20 @@ void launch_tlas(bool anyhit, int blasLayout, const float4* tlasNodes, const uin
     else if (blasLayout == kLayoutCwbvh) TBVH_LT(k_tlas_flat_w6, kLayoutCwbvh);
     else if (blasLayout == kLayoutBvh4Gpu) TBVH_LT(k_tlas_flat_w6, kLayoutBvh4Gpu);
     else TBVH_LT(k_tlas_flat_w5, 0);
+#undef TBVH_LT
+}
+
+// TLASes with sphere BLASes (kernels_custom.hip): every such TLAS takes the flat loop with the sphere step — sphere BLASes only
+// (blasLayout == TBVH_LAYOUT_BVH2_WALD), or mixed with BVH_GPU / BVH4_GPU / BVH8_CWBVH BLASes walked in their own layouts (blasLayout == 0)
+void launch_tlas_custom(bool anyhit, int blasLayout, const float4* tlasNodes, const uint32_t* tlasIdx, const float4* instances,
+                        const BlasDesc* blas, const QueryArgs& q, uint32_t* status, uint32_t blocks, hipStream_t s) {
+#define TBVH_LT(K, LAYOUT)                                                                                                               \
+    do {                                                                                                                                 \
+        if (anyhit) hipLaunchKernelGGL((K<true, LAYOUT, 12, 16, 32>), dim3(blocks), dim3(WG), 0, s, tlasNodes, tlasIdx, instances, blas, q, status); \
+        else hipLaunchKernelGGL((K<false, LAYOUT, 12, 16, 32>), dim3(blocks), dim3(WG), 0, s, tlasNodes, tlasIdx, instances, blas, q, status);       \
+    } while (0)
+    if (blasLayout == kLayoutBvh2Wald) TBVH_LT(k_tlas_flat_sph_w6, kLayoutBvh2Wald);
+    else TBVH_LT(k_tlas_flat_sph_w4, 0);
 #undef TBVH_LT
 }
 
