@@ -51,6 +51,17 @@ public:
     Scene(const tinybvh::BVH_GPU& b, const tinybvh::bvhvec4* verts, int device = 0, tbvh_context* own = nullptr) : dev(device), ctx(own ? own : Context(device)) {
         Check(tbvh_upload_bvh_gpu(ctx, b.bvhNode, b.usedNodes, b.bvh.primIdx, b.bvh.idxCount, verts, b.triCount, &s), "tbvh_upload_bvh_gpu");
     }
+    // a BVH_GPU uploads however it was built: the vertices, their stride and the index buffer are taken from the object itself (b.bvh.verts.data /
+    // .stride, b.bvh.vertIdx — Build( verts, indices, n ), Build( bvhvec4slice, indices, n ) or the flat Build( verts, n ); tbvh_upload_bvh_gpu_mesh).
+    // vertCount: the number of vertices behind the slice; 0 = found here — BVH_GPU::Build( verts, indices, n ) sets slice.count = 3 n, not the vertex
+    // count (tiny_bvh.h:4564), so for an indexed BVH it is max( index ) + 1, for a flat one slice.count.  The arrays stay the caller's.
+    explicit Scene(const tinybvh::BVH_GPU& b, int device = 0, tbvh_context* own = nullptr, uint32_t vertCount = 0) : dev(device), ctx(own ? own : Context(device)) {
+        vertIdx = b.bvh.vertIdx; meshTris = b.triCount;
+        nVerts = vertCount ? vertCount : b.bvh.verts.count;
+        if (!vertCount && vertIdx) { nVerts = 0; for (size_t i = 0; i < (size_t)meshTris * 3; i++) if (vertIdx[i] >= nVerts) nVerts = vertIdx[i] + 1; }
+        const tbvh_mesh m = MeshOf(b.bvh.verts, vertIdx);
+        Check(tbvh_upload_bvh_gpu_mesh(ctx, b.bvhNode, b.usedNodes, b.bvh.primIdx, b.bvh.idxCount, &m, &s), "tbvh_upload_bvh_gpu_mesh");
+    }
     explicit Scene(const tinybvh::BVH4_GPU& b, int device = 0, tbvh_context* own = nullptr) : dev(device), ctx(own ? own : Context(device)) {
         Check(tbvh_upload_bvh4_gpu(ctx, b.bvh4Data, b.usedBlocks, &s), "tbvh_upload_bvh4_gpu");
     }
@@ -89,10 +100,23 @@ public:
     float LastKernelMs() const { return tbvh_time_last_ms(ctx); }
     // animated geometry: BVH::Refit + ConvertFrom + upload of the reference flow, on the device
     void Refit(const tinybvh::bvhvec4* verts, size_t triCount) { Check(tbvh_refit(s, verts, triCount, 0), "tbvh_refit"); }
+    // (Refit( slice ) and IntersectSpheres( .., slice, .. ) belong to a Scene made by Scene( const BVH_GPU& ), which knows the vertex and triangle
+    // counts; on a Scene made by one of the other constructors they send an empty mesh and the library refuses it: TBVH_E_INVALID, "null/empty mesh")
+    // the same for a Scene made from the BVH_GPU itself: the moved vertices as the slice the BVH reads (data and stride; the vertex count is the
+    // constructor's).  An indexed scene holds its index buffer on the device, so only the shared vertices go up (tbvh_refit_mesh, indices = NULL).
+    void Refit(const tinybvh::bvhvec4slice& verts) {
+        const tbvh_mesh m = MeshOf(verts, nullptr);
+        Check(tbvh_refit_mesh(s, &m), "tbvh_refit_mesh");
+    }
     // BVH::IntersectSphere( pos, r ) batched (tiny_bvh.h:3140-3200; tiny_bvh_collide.cpp:169): hit[i] = 1 if sphere i = {x, y, z, r} touches a
     // triangle; verts = the scene's bvhvec4 vertex array, 3 per triangle, as Refit takes it.  BLAS scenes of the three GPU layouts only.
     void IntersectSpheres(const tinybvh::bvhvec4* spheres, size_t n, const tinybvh::bvhvec4* verts, size_t triCount, uint8_t* hit) {
         Check(tbvh_intersect_spheres(s, spheres, n, verts, triCount, hit), "tbvh_intersect_spheres");
+    }
+    // ... with the vertices as the slice the BVH reads, through the index buffer the Scene was made with (tbvh_intersect_spheres_mesh)
+    void IntersectSpheres(const tinybvh::bvhvec4* spheres, size_t n, const tinybvh::bvhvec4slice& verts, uint8_t* hit) {
+        const tbvh_mesh m = MeshOf(verts, vertIdx);
+        Check(tbvh_intersect_spheres_mesh(s, spheres, n, &m, hit), "tbvh_intersect_spheres_mesh");
     }
     // the same over device arrays, asynchronous on the context's stream
     void IntersectSpheresDevice(const void* dSpheres, size_t n, const void* dVerts, size_t triCount, uint8_t* dHit) {
@@ -102,9 +126,16 @@ public:
     int Device() const { return dev; }
     tbvh_context* Ctx() const { return ctx; }
 private:
+    tbvh_mesh MeshOf(const tinybvh::bvhvec4slice& v, const uint32_t* indices) const {
+        tbvh_mesh m;
+        m.verts = v.data; m.n_verts = nVerts; m.stride_bytes = v.stride; m.on_device = 0; m.indices = indices; m.n_tris = meshTris;
+        return m;
+    }
     tbvh_scene* s = nullptr;
     int dev = 0;
     tbvh_context* ctx = nullptr;
+    const uint32_t* vertIdx = nullptr;   // Scene( const BVH_GPU& ): the BVH's index buffer (the caller's), vertex and triangle counts
+    uint32_t nVerts = 0, meshTris = 0;
 };
 
 // VoxelSet (tiny_bvh.h:988-1030) on the device, with the reference's method names: Set fills a brick map on the host exactly as VoxelSet::Set

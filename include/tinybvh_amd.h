@@ -46,7 +46,7 @@
 extern "C" {
 #endif
 
-#define TBVH_ABI_VERSION 5   /* 5 (additions, nothing changed: custom-geometry sphere BLASes — tbvh_upload_custom_spheres, tbvh_host_build_custom_spheres, TLASes over them); 5 (additions, nothing changed: tbvh_intersect_spheres / _device); 5 (additions, nothing changed: VoxelSet scenes — TBVH_LAYOUT_VOXELSET, tbvh_upload_voxelset / _voxelset_dense, tbvh_host_build_voxelset, TLASes over voxel sets); 5 (additions, nothing changed: BVH_Double scenes — TBVH_LAYOUT_BVH_DOUBLE, tbvh_upload_bvh_double / _tlas_double, tbvh_intersect_ex / _occluded_ex (+ _device), tbvh_host_build_double / _tlas_double); 5: tbvh_pinned_malloc / _free, tbvh_scene_get / _set_schedule_hint, tbvh_measure_link_bandwidth, TBVH_BUILD_SPLIT_TRIANGLES / _WHOLE_TRIANGLES, development aids moved to tinybvh_amd_debug.h (nothing removed from the library); 4: tbvh_update_bvh_gpu / _bvh4_gpu / _cwbvh, tbvh_time_history, contexts are thread-safe; 3: deterministic ties, tbvh_bin_rays_device, tbvh_cwbvh_set_hybrid, device-resident multi-device calls */
+#define TBVH_ABI_VERSION 5   /* 5 (additions, nothing changed: indexed and strided triangle meshes — tbvh_mesh and the tbvh_*_mesh entry points, tbvh_flatten_mesh_device); 5 (additions, nothing changed: custom-geometry sphere BLASes — tbvh_upload_custom_spheres, tbvh_host_build_custom_spheres, TLASes over them); 5 (additions, nothing changed: tbvh_intersect_spheres / _device); 5 (additions, nothing changed: VoxelSet scenes — TBVH_LAYOUT_VOXELSET, tbvh_upload_voxelset / _voxelset_dense, tbvh_host_build_voxelset, TLASes over voxel sets); 5 (additions, nothing changed: BVH_Double scenes — TBVH_LAYOUT_BVH_DOUBLE, tbvh_upload_bvh_double / _tlas_double, tbvh_intersect_ex / _occluded_ex (+ _device), tbvh_host_build_double / _tlas_double); 5: tbvh_pinned_malloc / _free, tbvh_scene_get / _set_schedule_hint, tbvh_measure_link_bandwidth, TBVH_BUILD_SPLIT_TRIANGLES / _WHOLE_TRIANGLES, development aids moved to tinybvh_amd_debug.h (nothing removed from the library); 4: tbvh_update_bvh_gpu / _bvh4_gpu / _cwbvh, tbvh_time_history, contexts are thread-safe; 3: deterministic ties, tbvh_bin_rays_device, tbvh_cwbvh_set_hybrid, device-resident multi-device calls */
 
 /* error codes */
 #define TBVH_OK            0
@@ -680,6 +680,73 @@ int tbvh_upload_custom_spheres(tbvh_context* ctx, const void* nodes32, uint64_t 
 /* The library's builder for callers without tinybvh: a binned SAH BVH over the boxes pos -/+ r (the demos' sphereAABB).
  * tbvh_host_blob(h, 0) = Wald nodes (32 bytes each), (h, 1) = primIdx; tbvh_host_layout = TBVH_LAYOUT_BVH2_WALD. */
 int tbvh_host_build_custom_spheres(const void* spheres16, uint64_t n, tbvh_hostbvh** out);
+
+/* ----------------------------------------------------------------------------------
+ * indexed and strided triangle meshes — the second form the reference takes triangles in: Build( bvhvec4slice { data, count, stride }, indices,
+ * n ) of every layout (tiny_bvh.h:428-436, 889-900, 1111-1116, 1272-1276, 1344-1348, 4561-4604), BVH::vertIdx honoured by Intersect, IsOccluded,
+ * Refit, IntersectSphere and the wide converters (1659-1661, 3067-3075, 3165-3168, 4931-4934, 5165-5168, 5993-5996).  One description of where
+ * the vertices are, understood by every entry point that reads vertices; each tbvh_*_mesh call below is its flat counterpart with (verts16,
+ * n_tris) replaced by a tbvh_mesh.  Query kernels never see vertices (all three layouts keep triangle records inline), so queries do not change.
+ *   - results do not depend on the form: for one set of triangles the indexed, the strided and the flat form give the same bytes — host-built
+ *     blobs, gathered records, refitted nodes, sphere flags, hit records.  The floats read are the same; only the addresses differ.
+ *   - no flattened copy of the vertices is made on the device (tbvh_flatten_mesh_device is the one call that writes one, for the entry points
+ *     that stay flat-only: tbvh_generate_bounce_device, tbvh_wavefront_render): the kernels fetch indices[3 p + k], then the vertex
+ *     (tinybvh_amd/csrc/mesh_source.h; DESIGN.md par. 13).
+ *   - a scene made from a mesh WITH indices keeps its own device copy of the index buffer (12 bytes per triangle, counted by
+ *     tbvh_scene_device_bytes).  tbvh_refit_mesh with indices == NULL on such a scene means "the indices the scene holds": the per-frame call of
+ *     an animated mesh passes the shared vertex array and nothing else, and a host-staged refit copies n_verts * stride_bytes bytes, not
+ *     n_tris * 48.  Passing indices replaces the held copy (same n_tris, else TBVH_E_INVALID) — once they are known to be good: host indices at
+ *     validation, device-resident ones after the refit's kernels have read them all (a buffer with a bad index is reported, TBVH_E_FORMAT, and never
+ *     becomes the held copy; the records it reached are then those of the failed refit until the next good one).  A scene made WITHOUT indices
+ *     uses passed indices for that call only and never starts holding any.  tbvh_update_bvh_gpu(_mesh) with a mesh that has no indices drops a
+ *     held copy (the blob is then described by the vertices alone).  tbvh_refit keeps working on any scene.
+ *   - validation: a null mesh / vertex array, n_tris == 0, stride_bytes not 0 and (not a multiple of 4 or < 12), n_verts or 3 * n_tris beyond 32
+ *     bits, device vertices misaligned (16 bytes at a 16-byte stride, else 4), fewer than 3 * n_tris vertices without indices: TBVH_E_INVALID.
+ *     Host indices are checked before anything is allocated: TBVH_E_FORMAT names the first triangle with an index >= n_verts.  Device-resident
+ *     indices are checked by the kernels that read them: an out-of-range index is never dereferenced, the status word records it, and the call
+ *     itself (where it synchronises: uploads, builds, conversions, refits, the host sphere query) or the next synchronising call returns
+ *     TBVH_E_FORMAT.
+ * Not offered: BVH_Double, voxel sets and sphere BLASes (the reference has no indexed form of them), 16-bit indices.
+ * ---------------------------------------------------------------------------------- */
+typedef struct tbvh_mesh {
+    const void*     verts;         /* vertex i = three floats at (char*)verts + i * stride_bytes (bvhvec4slice::operator[])   */
+    uint64_t        n_verts;       /* bvhvec4slice::count; indices are validated against it                                  */
+    uint32_t        stride_bytes;  /* 0 = 16 (bvhvec4); otherwise a multiple of 4, >= 12.  w is read at 16 only; any other stride reads
+                                      x, y, z (12 bytes) and takes w = 0: the last vertex need not be followed by 4 more bytes */
+    uint32_t        on_device;     /* 0: verts and indices are host memory, 1: device memory                                 */
+    const uint32_t* indices;       /* BVH::vertIdx, 3 per triangle; NULL: triangle i = vertices 3i, 3i + 1, 3i + 2           */
+    uint64_t        n_tris;
+} tbvh_mesh;
+/* With stride_bytes 0 / 16 and indices == NULL a tbvh_mesh means exactly what (verts16, n_tris) mean, and runs the same kernels. */
+
+/* BVH_GPU::Build( slice, indices, n ) (tiny_bvh.h:4561-4573) built by the caller: tbvh_upload_bvh_gpu / tbvh_update_bvh_gpu with the blob's
+ * primIdx referring to triangles whose vertices are found through the mesh.  The blob is host memory; the mesh may be on the device. */
+int tbvh_upload_bvh_gpu_mesh(tbvh_context* ctx, const void* nodes64, uint64_t n_nodes, const uint32_t* prim_idx, uint64_t n_idx,
+                             const tbvh_mesh* mesh, tbvh_scene** out);
+int tbvh_update_bvh_gpu_mesh(tbvh_scene* scene, const void* nodes64, uint64_t n_nodes, const uint32_t* prim_idx, uint64_t n_idx, const tbvh_mesh* mesh);
+/* The library's builder reading the triangles as BVH::PrepareBuild does (tiny_bvh.h:2310-2324): tbvh_host_build / tbvh_upload_host over a mesh
+ * (host memory for the build).  The blobs are byte-identical to tbvh_host_build of the flattened triangles. */
+int tbvh_host_build_mesh(const tbvh_mesh* mesh, int layout, const tbvh_build_params* params, tbvh_hostbvh** out);
+/* (BVH4_GPU / BVH8_CWBVH blobs carry their triangles: the upload reads nothing of the mesh and only keeps its index buffer.  A DEVICE-resident index
+ * buffer is therefore kept unread here; the first tbvh_refit_mesh through it checks every index against that call's n_verts, dereferences none that
+ * is out of range and reports TBVH_E_FORMAT then — one frame late, and the buffer is the held copy until good indices are passed.) */
+int tbvh_upload_host_mesh(tbvh_context* ctx, const tbvh_hostbvh* h, const tbvh_mesh* mesh, tbvh_scene** out);   /* mesh is read for BVH_GPU; kept indices for every layout */
+/* tbvh_build_device (builder 0: LBVH, max_leaf_tris applies) / tbvh_build_device_ploc (builder 1: radius applies) over a mesh. */
+int tbvh_build_device_mesh(tbvh_context* ctx, const tbvh_mesh* mesh, int layout, uint32_t max_leaf_tris, int builder, uint32_t radius, tbvh_scene** out);
+/* BVH4_GPU / BVH8_CWBVH::ConvertFrom of a BVH built over indices (tiny_bvh.h:5165-5168, 5993-5996): tbvh_convert_bvh2_device with the leaf writers
+ * fetching through the mesh.  on_device says where nodes32 / prim_idx are; the mesh carries its own flag. */
+int tbvh_convert_bvh2_device_mesh(tbvh_context* ctx, const void* nodes32, uint64_t n_nodes, const uint32_t* prim_idx, uint64_t n_idx,
+                                  const tbvh_mesh* mesh, int on_device, int layout, tbvh_scene** out);
+/* BVH::Refit / MBVH::Refit with vertIdx (tiny_bvh.h:3067-3075, 4931-4934): tbvh_refit over a mesh; indices == NULL on a scene that holds an index
+ * buffer means that buffer (see above).  The scene's derived copies follow, as after tbvh_refit. */
+int tbvh_refit_mesh(tbvh_scene* scene, const tbvh_mesh* mesh);
+/* BVH::IntersectSphere with vertIdx (tiny_bvh.h:3165-3168): tbvh_intersect_spheres (host spheres and flags; the mesh where its flag says) and
+ * tbvh_intersect_spheres_device (everything on the device, the mesh included; asynchronous). */
+int tbvh_intersect_spheres_mesh(tbvh_scene* scene, const void* spheres16, uint64_t n_spheres, const tbvh_mesh* mesh, uint8_t* hit);
+int tbvh_intersect_spheres_mesh_device(tbvh_scene* scene, const void* d_spheres16, uint64_t n_spheres, const tbvh_mesh* mesh, uint8_t* d_hit);
+/* 3 float4 per triangle into d_verts16_out (device, 16-byte aligned, n_tris * 48 bytes), w copied at a 16-byte stride, else 0: the vertex array
+ * of the entry points that stay flat-only.  Asynchronous for a device-resident mesh; a host mesh is staged and the call returns when done. */
+int tbvh_flatten_mesh_device(tbvh_context* ctx, const tbvh_mesh* mesh, void* d_verts16_out);
 
 #ifdef __cplusplus
 }

@@ -15,7 +15,7 @@ import os
 import numpy as np
 
 from . import _capi
-from ._capi import BuildParams, Camera, TbvhError, check, lib
+from ._capi import BuildParams, Camera, Mesh, TbvhError, check, lib
 
 LAYOUT_BVH2_WALD = 1
 LAYOUT_BVH_DOUBLE = 3
@@ -177,6 +177,14 @@ class Context:
         assert a.flags["C_CONTIGUOUS"]
         check(lib.tbvh_copy_from_device(self._h, _ptr(a), C.c_void_p(dptr), a.nbytes), "tbvh_copy_from_device")
 
+    def flatten_mesh(self, verts, indices=None, d_out: int = 0) -> int:
+        """tbvh_flatten_mesh_device: 3 float4 per triangle on the device (for generate_bounce / Wavefront.render, which stay flat-only).
+        Returns the device pointer (allocated here with malloc() unless d_out is given)."""
+        m, keep = _mesh(verts, indices)
+        d = d_out or self.malloc(int(m.n_tris) * 48)
+        check(lib.tbvh_flatten_mesh_device(self._h, C.byref(m), C.c_void_p(d)), "tbvh_flatten_mesh_device")
+        return d
+
     def reset_hits(self, d_rays: int, n: int, tmax: float = 1e30):
         check(lib.tbvh_reset_hits_device(self._h, C.c_void_p(d_rays), n, float(tmax)), "tbvh_reset_hits_device")
 
@@ -197,15 +205,64 @@ class Context:
         check(lib.tbvh_generate_shadow_device(self._h, C.c_void_p(d_in), C.c_void_p(d_out), n, l, float(eps)), "tbvh_generate_shadow_device")
 
 
+def device_mesh(d_verts: int, n_verts: int, n_tris: int, d_indices: int = 0, stride_bytes: int = 16) -> Mesh:
+    """A tbvh_mesh whose vertices (and indices, if any) are device memory: pass it wherever `verts` is taken together with indices=."""
+    return Mesh(C.c_void_p(int(d_verts)), int(n_verts), int(stride_bytes), 1, C.c_void_p(int(d_indices)) if d_indices else None, int(n_tris))
+
+
+def _is_mesh(verts, indices=None) -> bool:
+    """Does (verts, indices) name the mesh form?  Yes with indices=, for a device_mesh(), for an (n, 3) array, and for a 2-D float32 view whose rows
+    are not packed (interleaved[:, :3]: the row stride says where the vertices are).  Everything else — any packed array that reshapes to (3 n, 4),
+    as before — is the flat form."""
+    if indices is not None or isinstance(verts, Mesh):
+        return True
+    if not isinstance(verts, np.ndarray) or verts.ndim != 2:
+        return False
+    return verts.shape[1] == 3 or (verts.dtype == np.float32 and verts.shape[1] >= 3 and verts.strides[1] == 4 and verts.strides[0] != verts.shape[1] * 4)
+
+
+def _mesh(verts, indices=None):
+    """(tbvh_mesh, the arrays it points into) for a host mesh: verts any float32 array of shape (n_verts, k >= 3) whose row stride is a
+    multiple of 4 — the stride is ndarray.strides[0], so interleaved[:, :3] is used in place —, indices (n_tris, 3) or flat uint32, or None
+    (triangle i = vertices 3i, 3i + 1, 3i + 2).  A 16-byte row stride is a bvhvec4 array (w is read); any other stride reads x, y, z only.
+    A Mesh made by device_mesh() passes through."""
+    if isinstance(verts, Mesh):
+        assert indices is None, "a device_mesh() carries its own indices"
+        return verts, ()
+    v = np.asarray(verts)
+    if v.dtype != np.float32 or v.ndim != 2 or v.shape[1] < 3 or v.strides[1] != 4 or v.strides[0] % 4 or v.strides[0] < 12:
+        v = np.ascontiguousarray(v, np.float32)
+        assert v.ndim == 2 and v.shape[1] >= 3, "verts: (n_verts, k >= 3) float32"
+    idx = None
+    if indices is not None:
+        idx = np.ascontiguousarray(indices, np.uint32).reshape(-1)
+        assert idx.size % 3 == 0
+        n_tris = idx.size // 3
+    else:
+        assert v.shape[0] % 3 == 0
+        n_tris = v.shape[0] // 3
+    m = Mesh(C.c_void_p(v.ctypes.data), v.shape[0], v.strides[0], 0, None if idx is None else C.c_void_p(idx.ctypes.data), n_tris)
+    return m, (v, idx)
+
+
 class HostBVH:
-    """Blobs built on the host by the library's own builder (tbvh_host_build)."""
+    """Blobs built on the host by the library's own builder (tbvh_host_build; with indices=, or a vertex array that is not (3 n, 4):
+    tbvh_host_build_mesh — the same blobs, byte for byte, as for the flattened triangles)."""
 
     def __init__(self, verts: np.ndarray, layout: int, bins: int = 0, max_leaf_tris: int = 0, threads: int = 0,
-                 optimal_collapse: bool = False, c_prim: float = 0.0, greedy_collapse: bool = False, split_budget: Optional[float] = None):
-        verts = np.ascontiguousarray(verts, dtype=np.float32).reshape(-1, 4)
-        assert verts.shape[0] % 3 == 0
+                 optimal_collapse: bool = False, c_prim: float = 0.0, greedy_collapse: bool = False, split_budget: Optional[float] = None,
+                 indices=None):
+        self.indices = None
+        self.mesh = None
+        if not _is_mesh(verts, indices):
+            verts = np.ascontiguousarray(verts, dtype=np.float32).reshape(-1, 4)
+            assert verts.shape[0] % 3 == 0
+            self.n_tris = verts.shape[0] // 3
+        else:   # an indexed and / or strided mesh
+            self.mesh, keep = _mesh(verts, indices)
+            verts, self.indices = keep if keep else (None, None)   # (a device_mesh(): the library answers that the host builder reads host memory)
+            self.n_tris = int(self.mesh.n_tris)
         self.verts = verts
-        self.n_tris = verts.shape[0] // 3
         self.layout = layout
         flags = (2 if optimal_collapse else 0) | (4 if greedy_collapse else 0) | (int(round(c_prim * 100)) << 8)
         if split_budget is not None:   # None: the layout's default (BVH8_CWBVH: 30 % extra references; the others: whole triangles)
@@ -215,7 +272,10 @@ class HostBVH:
                 flags |= 16            # TBVH_BUILD_WHOLE_TRIANGLES
         bp = BuildParams(bins, max_leaf_tris, threads, flags)
         h = C.c_void_p()
-        check(lib.tbvh_host_build(_ptr(verts), self.n_tris, layout, C.byref(bp), C.byref(h)), "tbvh_host_build")
+        if self.mesh is not None:
+            check(lib.tbvh_host_build_mesh(C.byref(self.mesh), layout, C.byref(bp), C.byref(h)), "tbvh_host_build_mesh")
+        else:
+            check(lib.tbvh_host_build(_ptr(verts), self.n_tris, layout, C.byref(bp), C.byref(h)), "tbvh_host_build")
         self._h = h
 
     @classmethod
@@ -291,9 +351,45 @@ class _Scene:
     def device_bytes(self) -> int:
         return int(lib.tbvh_scene_device_bytes(self._h))
 
-    def Refit(self, verts, on_device: bool = False):
+    def _build_mesh(self, layout: int, verts, indices, kw) -> "_Scene":
+        """Build over an indexed / strided mesh on the host and upload (tbvh_host_build_mesh + tbvh_upload_host_mesh)."""
+        self.host = HostBVH(verts, layout, indices=indices, **kw)
+        check(lib.tbvh_upload_host_mesh(self.ctx._h, self.host._h, C.byref(self.host.mesh), C.byref(self._h)), "tbvh_upload_host_mesh")
+        self._mesh_tris = int(self.host.mesh.n_tris)
+        return self
+
+    def _build_device_mesh(self, layout: int, verts, indices, max_leaf_tris: int, builder: str, radius: int) -> "_Scene":
+        m, keep = _mesh(verts, indices)
+        check(lib.tbvh_build_device_mesh(self.ctx._h, C.byref(m), layout, max_leaf_tris if builder != "ploc" else 0, 1 if builder == "ploc" else 0, radius,
+                                         C.byref(self._h)), "tbvh_build_device_mesh")
+        self._mesh_tris = int(m.n_tris)
+        return self
+
+    def _convert_mesh(self, layout: int, nodes32, prim_idx, verts, indices) -> "_Scene":
+        nodes32 = np.ascontiguousarray(nodes32); prim_idx = np.ascontiguousarray(prim_idx, np.uint32)
+        m, keep = _mesh(verts, indices)
+        check(lib.tbvh_convert_bvh2_device_mesh(self.ctx._h, _ptr(nodes32), nodes32.nbytes // 32, _ptr(prim_idx), prim_idx.size, C.byref(m), 0, layout,
+                                                C.byref(self._h)), "tbvh_convert_bvh2_device_mesh")
+        self._mesh_tris = int(m.n_tris)
+        return self
+
+    def Refit(self, verts, on_device: bool = False, indices=None, mesh: bool = False):
         """Refit this BLAS on the device to moved vertices (tbvh_refit; BVH::Refit, tiny_bvh.h:3055-3093):
-        verts is the (3 n_tris, 4) float32 vertex array (host) or a device pointer with n_tris = on_device."""
+        verts is the (3 n_tris, 4) float32 vertex array (host) or a device pointer with n_tris = on_device.
+        With indices=, a device_mesh(), a vertex array that is not (3 n, 4), or mesh=True: tbvh_refit_mesh — on a scene made from an indexed
+        mesh, mesh=True with indices=None passes the shared vertices only and the scene's own index buffer is used."""
+        if indices is not None or mesh or isinstance(verts, Mesh):
+            if isinstance(verts, Mesh):
+                m = verts
+            else:
+                v = np.asarray(verts)
+                if v.dtype != np.float32 or v.ndim != 2 or v.strides[1] != 4 or v.strides[0] % 4 or v.strides[0] < 12:
+                    v = np.ascontiguousarray(v, np.float32)
+                idx = None if indices is None else np.ascontiguousarray(indices, np.uint32).reshape(-1)
+                n_tris = idx.size // 3 if idx is not None else (getattr(self, "_mesh_tris", 0) or v.shape[0] // 3)
+                m = Mesh(C.c_void_p(v.ctypes.data), v.shape[0], v.strides[0], 0, None if idx is None else C.c_void_p(idx.ctypes.data), n_tris)
+            check(lib.tbvh_refit_mesh(self._h, C.byref(m)), "tbvh_refit_mesh")
+            return self
         if on_device:
             ptr, n_tris = C.c_void_p(int(verts[0])), int(verts[1])
         else:
@@ -381,9 +477,15 @@ class _SphereQueries:
     """BVH::IntersectSphere (tiny_bvh.h:3140-3200) over a BLAS, batched (tbvh_intersect_spheres): does a sphere touch any triangle?
     verts is the vertex array the scene was built from (3 bvhvec4 per triangle), as Refit takes it."""
 
-    def intersect_spheres(self, spheres: np.ndarray, verts: np.ndarray) -> np.ndarray:
-        """spheres: (n, 4) float32 {x, y, z, r}; returns uint8[n], 1 = the sphere touches a triangle"""
+    def intersect_spheres(self, spheres: np.ndarray, verts: np.ndarray, indices=None) -> np.ndarray:
+        """spheres: (n, 4) float32 {x, y, z, r}; returns uint8[n], 1 = the sphere touches a triangle.
+        indices= (or a device_mesh() / a vertex array that is not (3 n, 4)): the mesh form, tbvh_intersect_spheres_mesh."""
         spheres = np.ascontiguousarray(spheres, np.float32).reshape(-1, 4)
+        if _is_mesh(verts, indices):
+            m, keep = _mesh(verts, indices)
+            out = np.zeros(spheres.shape[0], np.uint8)
+            check(lib.tbvh_intersect_spheres_mesh(self._h, _ptr(spheres), spheres.shape[0], C.byref(m), _ptr(out)), "tbvh_intersect_spheres_mesh")
+            return out
         verts = np.ascontiguousarray(verts, np.float32).reshape(-1, 4)
         assert verts.shape[0] % 3 == 0
         out = np.zeros(spheres.shape[0], np.uint8)
@@ -396,30 +498,48 @@ class _SphereQueries:
         check(lib.tbvh_intersect_spheres_device(self._h, C.c_void_p(d_spheres), n, C.c_void_p(d_verts), n_tris, C.c_void_p(d_hit)),
               "tbvh_intersect_spheres_device")
 
-    def intersect_sphere(self, pos, r: float, verts: np.ndarray) -> bool:
+    def intersect_spheres_mesh_device(self, d_spheres: int, n: int, mesh: Mesh, d_hit: int):
+        """the same with a device_mesh(); asynchronous on the context's stream"""
+        check(lib.tbvh_intersect_spheres_mesh_device(self._h, C.c_void_p(d_spheres), n, C.byref(mesh), C.c_void_p(d_hit)), "tbvh_intersect_spheres_mesh_device")
+
+    def intersect_sphere(self, pos, r: float, verts: np.ndarray, indices=None) -> bool:
         """one sphere, as BVH::IntersectSphere( pos, r ) asks it"""
         s = np.array([[pos[0], pos[1], pos[2], r]], np.float32)
-        return bool(self.intersect_spheres(s, verts)[0])
+        return bool(self.intersect_spheres(s, verts, indices)[0])
 
 
 class BVH_GPU(_SphereQueries, _Scene):
     """Aila-Laine 2-wide layout (tiny_bvh.h:1092-1127)."""
     layout = LAYOUT_BVH_GPU
 
-    def Build(self, verts: np.ndarray, **kw) -> "BVH_GPU":
+    def Build(self, verts: np.ndarray, indices=None, **kw) -> "BVH_GPU":
+        if _is_mesh(verts, indices):
+            return self._build_mesh(LAYOUT_BVH_GPU, verts, indices, kw)
         self.host = HostBVH(verts, LAYOUT_BVH_GPU, **kw)
         return self.Upload(self.host.blob(0, np.uint32, 16), self.host.blob(1, np.uint32, 1), self.host.verts)
 
-    def Upload(self, nodes64: np.ndarray, prim_idx: np.ndarray, verts: np.ndarray) -> "BVH_GPU":
+    def Upload(self, nodes64: np.ndarray, prim_idx: np.ndarray, verts: np.ndarray, indices=None) -> "BVH_GPU":
+        """verts: the caller's bvhvec4 array, 3 per triangle; with indices= (BVH_GPU::Build( verts, indices, n )), a device_mesh() or a strided
+        vertex array: tbvh_upload_bvh_gpu_mesh."""
         nodes64 = np.ascontiguousarray(nodes64); prim_idx = np.ascontiguousarray(prim_idx, dtype=np.uint32)
+        if _is_mesh(verts, indices):
+            m, keep = _mesh(verts, indices)
+            check(lib.tbvh_upload_bvh_gpu_mesh(self.ctx._h, _ptr(nodes64), nodes64.nbytes // 64, _ptr(prim_idx), prim_idx.size, C.byref(m), C.byref(self._h)),
+                  "tbvh_upload_bvh_gpu_mesh")
+            self._mesh_tris = int(m.n_tris)
+            return self
         verts = np.ascontiguousarray(verts, dtype=np.float32)
         check(lib.tbvh_upload_bvh_gpu(self.ctx._h, _ptr(nodes64), nodes64.nbytes // 64, _ptr(prim_idx), prim_idx.size,
                                       _ptr(verts), verts.size // 12, C.byref(self._h)), "tbvh_upload_bvh_gpu")
         return self
 
-    def Update(self, nodes64: np.ndarray, prim_idx: np.ndarray, verts: np.ndarray) -> "BVH_GPU":
-        """In-place re-upload of a blob refitted / re-converted on the host (tbvh_update_bvh_gpu): same handle, same device memory."""
+    def Update(self, nodes64: np.ndarray, prim_idx: np.ndarray, verts: np.ndarray, indices=None) -> "BVH_GPU":
+        """In-place re-upload of a blob refitted / re-converted on the host (tbvh_update_bvh_gpu; mesh forms: tbvh_update_bvh_gpu_mesh): same handle, same device memory."""
         nodes64 = np.ascontiguousarray(nodes64); prim_idx = np.ascontiguousarray(prim_idx, dtype=np.uint32)
+        if _is_mesh(verts, indices):
+            m, keep = _mesh(verts, indices)
+            check(lib.tbvh_update_bvh_gpu_mesh(self._h, _ptr(nodes64), nodes64.nbytes // 64, _ptr(prim_idx), prim_idx.size, C.byref(m)), "tbvh_update_bvh_gpu_mesh")
+            return self
         verts = np.ascontiguousarray(verts, dtype=np.float32)
         check(lib.tbvh_update_bvh_gpu(self._h, _ptr(nodes64), nodes64.nbytes // 64, _ptr(prim_idx), prim_idx.size, _ptr(verts), verts.size // 12), "tbvh_update_bvh_gpu")
         return self
@@ -429,12 +549,16 @@ class BVH4_GPU(_SphereQueries, _Scene):
     """Quantized 4-wide layout with inline triangles (tiny_bvh.h:1245-1289)."""
     layout = LAYOUT_BVH4_GPU
 
-    def Build(self, verts: np.ndarray, **kw) -> "BVH4_GPU":
+    def Build(self, verts: np.ndarray, indices=None, **kw) -> "BVH4_GPU":
+        if _is_mesh(verts, indices):
+            return self._build_mesh(LAYOUT_BVH4_GPU, verts, indices, kw)
         self.host = HostBVH(verts, LAYOUT_BVH4_GPU, **kw)
         return self.Upload(self.host.blob(0, np.uint32, 4))
 
-    def BuildOnDevice(self, verts: np.ndarray, max_leaf_tris: int = 4, builder: str = "lbvh", radius: int = 0) -> "BVH4_GPU":
-        """LBVH (tbvh_build_device) or PLOC (tbvh_build_device_ploc) build + 4-wide collapse + encode on the GPU."""
+    def BuildOnDevice(self, verts: np.ndarray, max_leaf_tris: int = 4, builder: str = "lbvh", radius: int = 0, indices=None) -> "BVH4_GPU":
+        """LBVH (tbvh_build_device) or PLOC (tbvh_build_device_ploc) build + 4-wide collapse + encode on the GPU (mesh forms: tbvh_build_device_mesh)."""
+        if _is_mesh(verts, indices):
+            return self._build_device_mesh(LAYOUT_BVH4_GPU, verts, indices, max_leaf_tris, builder, radius)
         verts = np.ascontiguousarray(verts, np.float32)
         if builder == "ploc":
             check(lib.tbvh_build_device_ploc(self.ctx._h, _ptr(verts), verts.shape[0] // 3, 0, LAYOUT_BVH4_GPU, radius, C.byref(self._h)), "tbvh_build_device_ploc")
@@ -442,8 +566,10 @@ class BVH4_GPU(_SphereQueries, _Scene):
             check(lib.tbvh_build_device(self.ctx._h, _ptr(verts), verts.shape[0] // 3, 0, LAYOUT_BVH4_GPU, max_leaf_tris, C.byref(self._h)), "tbvh_build_device")
         return self
 
-    def ConvertFromBVH2(self, nodes32: np.ndarray, prim_idx: np.ndarray, verts: np.ndarray) -> "BVH4_GPU":
-        """BVH4_GPU::ConvertFrom on the device (tbvh_convert_bvh2_device)."""
+    def ConvertFromBVH2(self, nodes32: np.ndarray, prim_idx: np.ndarray, verts: np.ndarray, indices=None) -> "BVH4_GPU":
+        """BVH4_GPU::ConvertFrom on the device (tbvh_convert_bvh2_device; mesh forms: tbvh_convert_bvh2_device_mesh)."""
+        if _is_mesh(verts, indices):
+            return self._convert_mesh(LAYOUT_BVH4_GPU, nodes32, prim_idx, verts, indices)
         nodes32 = np.ascontiguousarray(nodes32); prim_idx = np.ascontiguousarray(prim_idx, np.uint32); verts = np.ascontiguousarray(verts, np.float32)
         check(lib.tbvh_convert_bvh2_device(self.ctx._h, _ptr(nodes32), nodes32.nbytes // 32, _ptr(prim_idx), prim_idx.size, _ptr(verts), verts.shape[0] // 3,
                                            0, LAYOUT_BVH4_GPU, C.byref(self._h)), "tbvh_convert_bvh2_device")
@@ -465,12 +591,17 @@ class BVH8_CWBVH(_SphereQueries, _Scene):
     """Compressed wide BVH (tiny_bvh.h:1334-1362)."""
     layout = LAYOUT_CWBVH
 
-    def Build(self, verts: np.ndarray, **kw) -> "BVH8_CWBVH":
+    def Build(self, verts: np.ndarray, indices=None, **kw) -> "BVH8_CWBVH":
+        if _is_mesh(verts, indices):
+            return self._build_mesh(LAYOUT_CWBVH, verts, indices, kw)
         self.host = HostBVH(verts, LAYOUT_CWBVH, **kw)
         return self.Upload(self.host.blob(0, np.uint32, 4), self.host.blob(1, np.uint32, 4))
 
-    def BuildOnDevice(self, verts: np.ndarray, max_leaf_tris: int = 0, builder: str = "lbvh", radius: int = 0) -> "BVH8_CWBVH":
-        """LBVH (tbvh_build_device) or PLOC (tbvh_build_device_ploc) build + wide collapse + encode on the GPU; nothing is built on the host."""
+    def BuildOnDevice(self, verts: np.ndarray, max_leaf_tris: int = 0, builder: str = "lbvh", radius: int = 0, indices=None) -> "BVH8_CWBVH":
+        """LBVH (tbvh_build_device) or PLOC (tbvh_build_device_ploc) build + wide collapse + encode on the GPU; nothing is built on the host
+        (mesh forms: tbvh_build_device_mesh)."""
+        if _is_mesh(verts, indices):
+            return self._build_device_mesh(LAYOUT_CWBVH, verts, indices, max_leaf_tris, builder, radius)
         verts = np.ascontiguousarray(verts, np.float32)
         if builder == "ploc":
             check(lib.tbvh_build_device_ploc(self.ctx._h, _ptr(verts), verts.shape[0] // 3, 0, LAYOUT_CWBVH, radius, C.byref(self._h)), "tbvh_build_device_ploc")
@@ -478,9 +609,11 @@ class BVH8_CWBVH(_SphereQueries, _Scene):
             check(lib.tbvh_build_device(self.ctx._h, _ptr(verts), verts.shape[0] // 3, 0, LAYOUT_CWBVH, max_leaf_tris, C.byref(self._h)), "tbvh_build_device")
         return self
 
-    def ConvertFromBVH2(self, nodes32: np.ndarray, prim_idx: np.ndarray, verts: np.ndarray) -> "BVH8_CWBVH":
+    def ConvertFromBVH2(self, nodes32: np.ndarray, prim_idx: np.ndarray, verts: np.ndarray, indices=None) -> "BVH8_CWBVH":
         """BVH8_CWBVH::ConvertFrom on the device (tbvh_convert_bvh2_device): a plain BVH2 (32-byte BVHNode
-        array with leaves of at most 3 triangles, primIdx, vertices) goes up, the GPU collapses and encodes."""
+        array with leaves of at most 3 triangles, primIdx, vertices) goes up, the GPU collapses and encodes (mesh forms: tbvh_convert_bvh2_device_mesh)."""
+        if _is_mesh(verts, indices):
+            return self._convert_mesh(LAYOUT_CWBVH, nodes32, prim_idx, verts, indices)
         nodes32 = np.ascontiguousarray(nodes32); prim_idx = np.ascontiguousarray(prim_idx, np.uint32); verts = np.ascontiguousarray(verts, np.float32)
         check(lib.tbvh_convert_bvh2_device(self.ctx._h, _ptr(nodes32), nodes32.nbytes // 32, _ptr(prim_idx), prim_idx.size, _ptr(verts), verts.shape[0] // 3,
                                            0, LAYOUT_CWBVH, C.byref(self._h)), "tbvh_convert_bvh2_device")

@@ -21,6 +21,11 @@ class BuildParams(C.Structure):
     _fields_ = [("bins", _u32), ("max_leaf_tris", _u32), ("threads", _u32), ("flags", _u32)]
 
 
+class Mesh(C.Structure):   # tbvh_mesh
+    _fields_ = [("verts", C.c_void_p), ("n_verts", C.c_uint64), ("stride_bytes", C.c_uint32), ("on_device", C.c_uint32),
+                ("indices", C.c_void_p), ("n_tris", C.c_uint64)]
+
+
 class Camera(C.Structure):
     _fields_ = [("eye", C.c_float * 3), ("p1", C.c_float * 3), ("p2", C.c_float * 3), ("p3", C.c_float * 3),
                 ("width", _u32), ("height", _u32), ("spp_x", _u32), ("spp_y", _u32)]
@@ -137,6 +142,17 @@ SYMBOLS = {
     # sphere-overlap queries (capi_sphere.hip)
     "tbvh_intersect_spheres": (_i, [_vp, _vp, _u64, _vp, _u64, _vp]),
     "tbvh_intersect_spheres_device": (_i, [_vp, _vp, _u64, _vp, _u64, _vp]),
+    # indexed / strided triangle meshes (tbvh_mesh)
+    "tbvh_upload_bvh_gpu_mesh": (_i, [_vp, _vp, _u64, _vp, _u64, C.POINTER(Mesh), _pp]),
+    "tbvh_update_bvh_gpu_mesh": (_i, [_vp, _vp, _u64, _vp, _u64, C.POINTER(Mesh)]),
+    "tbvh_host_build_mesh": (_i, [C.POINTER(Mesh), _i, C.POINTER(BuildParams), _pp]),
+    "tbvh_upload_host_mesh": (_i, [_vp, _vp, C.POINTER(Mesh), _pp]),
+    "tbvh_build_device_mesh": (_i, [_vp, C.POINTER(Mesh), _i, _u32, _i, _u32, _pp]),
+    "tbvh_convert_bvh2_device_mesh": (_i, [_vp, _vp, _u64, _vp, _u64, C.POINTER(Mesh), _i, _i, _pp]),
+    "tbvh_refit_mesh": (_i, [_vp, C.POINTER(Mesh)]),
+    "tbvh_intersect_spheres_mesh": (_i, [_vp, _vp, _u64, C.POINTER(Mesh), _vp]),
+    "tbvh_intersect_spheres_mesh_device": (_i, [_vp, _vp, _u64, C.POINTER(Mesh), _vp]),
+    "tbvh_flatten_mesh_device": (_i, [_vp, C.POINTER(Mesh), _vp]),
 }
 
 

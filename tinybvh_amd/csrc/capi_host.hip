@@ -4,13 +4,11 @@
 using namespace tbvh;
 using namespace tbvh_capi;
 
-extern "C" {
-
-
 // ---- host builder ------------------------------------------------------------------------
 
-int tbvh_host_build(const void* verts16, uint64_t nTris, int layout, const tbvh_build_params* p, tbvh_hostbvh** out) {
-    if (!verts16 || !out || nTris == 0) return fail(TBVH_E_INVALID, "tbvh_host_build: null/empty argument");
+namespace tbvh_capi {
+// the triangles come through a HostMesh (host_builder.h): 3 x Vec4 per triangle for tbvh_host_build, indexed / strided for tbvh_host_build_mesh
+int hostBuildImpl(const HostMesh& v, uint64_t nTris, int layout, const tbvh_build_params* p, tbvh_hostbvh** out) {
     if (nTris > 0x3fffffffull) return fail(TBVH_E_INVALID, "too many triangles");
     if (layout != TBVH_LAYOUT_BVH2_WALD && layout != TBVH_LAYOUT_BVH_GPU && layout != TBVH_LAYOUT_BVH4_GPU && layout != TBVH_LAYOUT_CWBVH)
         return fail(TBVH_E_INVALID, "unknown layout %d", layout);
@@ -39,7 +37,6 @@ int tbvh_host_build(const void* verts16, uint64_t nTris, int layout, const tbvh_
     if (!bp.maxLeafTris) bp.maxLeafTris = layout == TBVH_LAYOUT_CWBVH ? (bp.greedyCollapse ? 3 : 1) : 4;
     if (layout == TBVH_LAYOUT_CWBVH && bp.maxLeafTris > 3) bp.maxLeafTris = 3;
     try {
-        const Vec4* v = (const Vec4*)verts16;
         build_bvh2(v, (uint32_t)nTris, bp, h->bvh2);
         if (layout == TBVH_LAYOUT_BVH_GPU) encode_bvh_gpu(h->bvh2, h->al);
         else if (layout == TBVH_LAYOUT_BVH4_GPU) encode_bvh4_gpu(h->bvh2, v, bp, h->blocksA);
@@ -50,6 +47,14 @@ int tbvh_host_build(const void* verts16, uint64_t nTris, int layout, const tbvh_
     }
     *out = h;
     return 0;
+}
+}  // namespace tbvh_capi
+
+extern "C" {
+
+int tbvh_host_build(const void* verts16, uint64_t nTris, int layout, const tbvh_build_params* p, tbvh_hostbvh** out) {
+    if (!verts16 || !out || nTris == 0) return fail(TBVH_E_INVALID, "tbvh_host_build: null/empty argument");
+    return hostBuildImpl(HostMesh((const Vec4*)verts16), nTris, layout, p, out);
 }
 
 int tbvh_host_build_tlas(void* instances192, uint64_t nInst, const float* blasBounds6, uint64_t nBlas, tbvh_hostbvh** out) {

@@ -219,7 +219,14 @@ struct tbvh_scene {
     uint32_t* opmap = nullptr;
     uint32_t opmapN = 0;
     uint64_t opmapBytes = 0;
-    uint64_t vertStageTris = 0;
+    uint64_t vertStageBytes = 0;
+    // a scene made from an INDEXED mesh (tbvh_*_mesh with indices) keeps its own device copy of the index buffer, 12 bytes per triangle, counted in
+    // `bytes`: tbvh_refit_mesh with indices == NULL then means "the indices the scene holds" — the per-frame call of an animated mesh passes the
+    // shared vertices only.  The derived copies (wide / wide4) hold none: their refit is handed the owner's source.
+    uint32_t* meshIdx = nullptr;
+    uint64_t meshIdxTris = 0;
+    uint32_t* idxStage = nullptr;        // staged host indices of tbvh_intersect_spheres_mesh (a per-frame query: no allocation per call)
+    uint64_t idxStageBytes = 0;
     // BVH_GPU / BVH4_GPU: the same tree collapsed 8-wide into the BVH8_CWBVH format (capi_scene.hip: makeWideCopy; made by the first query), kept current by update / refit / micromap
     // calls and traced INSTEAD of `nodes` by the queries on this scene: hit records do not depend on the layout (device_common.h: hit_wins), and the
     // compressed wide kernels trace the same rays 1.6-2.9 x faster than the 2-wide one (profiles/r06_bvh2.txt).  Owned by this scene, not listed in
@@ -349,5 +356,25 @@ int makeWide4Copy(tbvh_scene* s);   // the 4-wide copy of a BVH_GPU / BVH8_CWBVH
 int reclassifyTlas(tbvh_scene* t);
 void dropCopiesAfterUpdate(tbvh_scene* s);   // (capi_scene.hip) tbvh_update_*: see tbvh_scene::pendingCopies
 void countQueryForRecopy(tbvh_scene* s);     // ... and the query side of it (launchQuery)   // (capi_scene.hip) descriptors, kernel class and wide trees of a TLAS from its BLASes as they are now
+// ---- vertex sources (capi_mesh.hip): tbvh_mesh of the public header -> MeshSrc of the kernels (mesh_source.h) ------------------------------
+int checkMesh(const tbvh_mesh* m, const char* who, bool indicesMayBeHeld = false);   // the header's validation rules; host indices are range-checked here, before anything is allocated
+tbvh_mesh flatMesh(const void* verts16, uint64_t nTris, int onDevice);   // what (verts16, n_tris) of the flat entry points mean
+uint64_t meshVertexBytes(const tbvh_mesh& m);                          // bytes of the vertex array that may be read (the last vertex: 12 unless the stride is 16)
+// a mesh as the kernels see it: device-resident arrays are used in place, host arrays are copied into allocations this object owns (asynchronous on the
+// context's stream: synchronise before the caller's arrays may change and before this object goes)
+struct DeviceMesh {
+    tbvh::MeshSrc src;
+    void *ownVerts = nullptr, *ownIdx = nullptr;
+    DeviceMesh() = default;
+    DeviceMesh(const DeviceMesh&) = delete;
+    DeviceMesh& operator=(const DeviceMesh&) = delete;
+    ~DeviceMesh() { if (ownVerts) hipFree(ownVerts); if (ownIdx) hipFree(ownIdx); }
+};
+int stageMesh(tbvh_context* c, const tbvh_mesh& m, DeviceMesh& out);
+int keepMeshIndices(tbvh_scene* s, const tbvh::MeshSrc& src);          // the scene's own copy of src.indices (no-op without indices); device to device, asynchronous
+int refitDeviceSource(tbvh_scene* s, const tbvh::MeshSrc& src);        // (capi_scene.hip) tbvh_refit / tbvh_refit_mesh once the source is on the device
+int hostBuildImpl(const tbvh::HostMesh& mesh, uint64_t nTris, int layout, const tbvh_build_params* p, tbvh_hostbvh** out);   // (capi_host.hip) tbvh_host_build / _mesh
+int checkSphereScene(tbvh_scene* s, const char* who);   // (capi_sphere.hip) the refusals a sphere query makes before it looks at anything else
+int launchSpheres(tbvh_scene* s, const float4* dSpheres, uint64_t n, const tbvh::MeshSrc& verts, uint8_t* dHit);   // (capi_sphere.hip)
 int makeWideCopy(tbvh_scene* s);   // (lazily, from launchQuery) the 8-wide copy of a BVH_GPU / BVH4_GPU scene   // (lazily, from launchQuery) hybrid node copy + 64-byte triangle records for incoherent batches
 }  // namespace tbvh_capi

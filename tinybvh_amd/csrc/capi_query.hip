@@ -471,6 +471,10 @@ int checkStatus(tbvh_context* c) {
         hipMemsetAsync(c->status, 0, 4, c->stream);
         return fail(TBVH_E_FORMAT, "sphere query: a triangle record refers to a primitive beyond the vertex array");
     }
+    if (st & kStatusMeshIndex) {
+        hipMemsetAsync(c->status, 0, 4, c->stream);
+        return fail(TBVH_E_FORMAT, "mesh: a vertex index of a device-resident index buffer is not a vertex (index >= n_verts)");
+    }
     return 0;
 }
 }  // namespace tbvh_capi

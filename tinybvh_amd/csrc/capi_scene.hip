@@ -110,7 +110,7 @@ void freeWide4Copy(tbvh_scene* s) {
 // BVH8_CWBVH conversion uses collapses and encodes it in ITS record mode (kernels_convert.hip; the greedy collapse of MBVH<8>::ConvertFrom,
 // tiny_bvh.h:4975-5048): triangle records are carried over bit for bit.  Blobs below TBVH_WIDE_COPY_MIN entries / triangles (default 32768; 0 = never)
 // keep their own kernel.  A failure here is never an error of the query: the scene then simply traces its own nodes.
-static int convertDeviceImpl(tbvh_context* c, int layout, const float4* dN2, uint64_t nNodes2, const uint32_t* dIdx, uint64_t nIdx, const float4* dV, uint64_t nTris, tbvh_scene** out);
+static int convertDeviceImpl(tbvh_context* c, int layout, const float4* dN2, uint64_t nNodes2, const uint32_t* dIdx, uint64_t nIdx, const MeshSrc& dV, tbvh_scene** out);
 // One copy of scene s in the `target` layout (BVH8_CWBVH from a BVH_GPU / BVH4_GPU scene, BVH4_GPU from a BVH_GPU / BVH8_CWBVH one), or nullptr (too small,
 // too large, out of memory: never an error of the caller's operation).  Not listed in the context's scene table; shares the owner's opacity maps.
 // forTlas: the copy is wanted by a TLAS over s — there ONE kernel class for all BLASes is worth more than any single BLAS's speed (a BLAS without the copy
@@ -161,7 +161,7 @@ static tbvh_scene* buildCopy(tbvh_scene* s, int target, bool forTlas) {
     if (hipMalloc(&t.n2, n2.size() * 32) != hipSuccess ||
         hipMemcpyAsync(t.n2, n2.data(), n2.size() * 32, hipMemcpyHostToDevice, c->stream) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
     tbvh_scene* w = nullptr;
-    if (convertDeviceImpl(c, target, (const float4*)t.n2, n2.size(), nullptr, nRecs, dRecs, nRecs, &w) != 0 || !w) { (void)hipGetLastError(); return nullptr; }
+    if (convertDeviceImpl(c, target, (const float4*)t.n2, n2.size(), nullptr, nRecs, flat_mesh(dRecs, nRecs), &w) != 0 || !w) { (void)hipGetLastError(); return nullptr; }
     for (size_t i = 0; i < c->scenes.size(); i++)
         if (c->scenes[i] == w) { c->scenes.erase(c->scenes.begin() + i); break; }   // owned by `s`, freed with it
     w->opmap = s->opmap; w->opmapN = s->opmapN;
@@ -188,37 +188,103 @@ static int makeWide4CopyImpl(tbvh_scene* s) {
     if (tbvh_scene* w = buildCopy(s, TBVH_LAYOUT_BVH4_GPU, true)) { s->wide4 = w; s->bytes += w->bytes; }
     return 0;
 }
+
+// ---- device refit (tbvh_refit / tbvh_refit_mesh below) ----------------------------------------------------------------------------------
+constexpr uint64_t kRefitKeepRays = 8ull << 20;   // a copy's refit (0.3-0.5 ms per 100 k triangles) pays from about this many rays per refit on (0.04-0.08 ns gained per ray)
+// a mesh refitted every frame with few rays traced in between: the copies are dropped (they come back like after an update: tbvh_scene::pendingCopies)
+static bool refitDropsCopies(tbvh_scene* s) {
+    uint64_t total = s->raysTraced;
+    for (size_t i = 0; i < s->usedBy.size(); i++) {
+        bool seen = false;
+        for (size_t k = 0; k < i; k++) seen |= s->usedBy[k] == s->usedBy[i];
+        if (!seen) total += s->usedBy[i]->raysTraced;
+    }
+    const bool drop = (s->wide || s->wide4) && s->refitSeen && total - s->raysAtRefit < kRefitKeepRays;
+    s->refitSeen = true; s->raysAtRefit = total;
+    if (drop) dropCopiesAfterUpdate(s);
+    return drop;
+}
+
+// the refit itself: src is device-resident (the caller's arrays, the scene's vertex staging buffer, the scene's held index buffer)
+int refitDeviceSource(tbvh_scene* s, const MeshSrc& src) {
+    tbvh_context* c = s->ctx;
+    if (s->layout == TBVH_LAYOUT_BVH4_GPU) {
+        // node list per level, child-box hand-over area: sized for the most nodes the stream can hold (4 blocks each)
+        const uint32_t capNodes = (uint32_t)(s->nNodeBlocks / 4 + 1);
+        if (!s->refitScratch) HIP_TRY(hipMalloc(&s->refitScratch, (size_t)capNodes * (16 + 128) + 256));
+        char* base = (char*)s->refitScratch;
+        uint32_t* counter = (uint32_t*)base;
+        void* items = base + 256;
+        float4* childBox = (float4*)(base + 256 + (size_t)capNodes * 16);
+        HIP_TRY(timedBegin(c));
+        HIP_TRY(run_refit_bvh4(s->nodes, s->nNodeBlocks, src, items, capNodes, counter, childBox, s->b4Levels, c->status, c->stream));
+        HIP_TRY(timedEnd(c));
+        if (refitDropsCopies(s)) return 0;
+        if (s->wide) return refitDeviceSource(s->wide, src);   // the 8-wide copy follows
+        return 0;
+    }
+    if (s->layout != TBVH_LAYOUT_CWBVH && s->layout != TBVH_LAYOUT_BVH_GPU)
+        return fail(TBVH_E_INVALID, "tbvh_refit: layout %d is not refittable", s->layout);
+    const uint32_t nNodes = (uint32_t)(s->layout == TBVH_LAYOUT_CWBVH ? s->nNodeBlocks / 5 : s->nNodeBlocks / 4);
+    const uint64_t nRecords = s->nTriBlocks / 3;
+    if (!s->refitScratch) HIP_TRY(hipMalloc(&s->refitScratch, refit_scratch_bytes(s->layout, nNodes)));
+    HIP_TRY(timedBegin(c));
+    HIP_TRY(launch_refit(s->layout, s->nodes, nNodes, s->tris, nRecords, src, s->refitScratch, c->status, c->stream));
+    HIP_TRY(timedEnd(c));
+    // derived node layouts of the experiment kernels would be stale now
+    if (s->nodes128) launch_cwbvh_pad(s->nodes, s->nodes128, nNodes, c->stream);   // keep the padded copy current
+    if (s->nodesHy) launch_cwbvh_derive_hybrid(s->nodes, s->hyPerm, s->nodesHy, nNodes, s->hybridK, (c->embedTris && !(c->expFlags & 8u)) ? s->tris : nullptr, c->stream);
+    if (s->tris64) launch_cwbvh_pad_tris(s->tris, s->tris64, s->nTriBlocks / 3, c->stream);
+    if (refitDropsCopies(s)) return 0;
+    if (s->wide) if (int r = refitDeviceSource(s->wide, src)) return r;     // the 8-wide copy follows (same vertices, already on the device)
+    if (s->wide4) return refitDeviceSource(s->wide4, src);                 // ... and the 4-wide one
+    return 0;
+}
 }  // namespace tbvh_capi
 
 extern "C" {
 
 // ---- uploads ---------------------------------------------------------------------------
 
-int tbvh_upload_bvh_gpu(tbvh_context* c, const void* nodes64, uint64_t nNodes, const uint32_t* primIdx, uint64_t nIdx,
-                        const void* verts16, uint64_t nTris, tbvh_scene** out) {
-    if (!c || !nodes64 || !primIdx || !verts16 || !out || nNodes == 0) return fail(TBVH_E_INVALID, "tbvh_upload_bvh_gpu: null/empty argument");
+// BVH_GPU upload: the blob's primIdx names triangles, whose vertices the gather finds through the mesh (flat: 3 float4 per triangle)
+static int uploadBvhGpuImpl(tbvh_context* c, const void* nodes64, uint64_t nNodes, const uint32_t* primIdx, uint64_t nIdx, const tbvh_mesh& mesh, tbvh_scene** out) {
     if (const char* why = validate_bvh_gpu((const NodeAL*)nodes64, nNodes, nIdx)) return fail(why == kValidateNoMemory ? TBVH_E_NOMEM : TBVH_E_FORMAT, "%s", why);
     TBVH_ENTER(c);
     tbvh_scene* s = newScene(c, TBVH_LAYOUT_BVH_GPU);
     if (!s) return fail(TBVH_E_NOMEM, "out of host memory");
-    uint32_t* dIdx = nullptr; float4* dVerts = nullptr;
+    uint32_t* dIdx = nullptr;
+    DeviceMesh dm;
     hipError_t e = hipMalloc((void**)&s->nodes, nNodes * 64);
     if (e == hipSuccess) e = hipMalloc((void**)&s->tris, (nIdx ? nIdx : 1) * 48);
     if (e == hipSuccess) e = hipMalloc((void**)&dIdx, (nIdx ? nIdx : 1) * 4);
-    if (e == hipSuccess) e = hipMalloc((void**)&dVerts, (nTris ? nTris : 1) * 48);
+    if (e == hipSuccess && stageMesh(c, mesh, dm)) e = hipErrorOutOfMemory;
     if (e == hipSuccess) e = hipMemcpyAsync(s->nodes, nodes64, nNodes * 64, hipMemcpyHostToDevice, c->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(dIdx, primIdx, nIdx * 4, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(dVerts, verts16, nTris * 48, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess && nIdx) { launch_gather_tris(dIdx, dVerts, s->tris, nIdx, nTris, c->stream); e = hipGetLastError(); }
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if (dIdx) hipFree(dIdx);
-    if (dVerts) hipFree(dVerts);
-    if (e != hipSuccess) { tbvh_free_scene(s); return fail(TBVH_E_HIP, "BVH_GPU upload failed: %s", hipGetErrorString(e)); }
+    if (e == hipSuccess && nIdx) { launch_gather_tris(dIdx, dm.src, s->tris, nIdx, c->status, c->stream); e = hipGetLastError(); }
     s->nNodeBlocks = nNodes * 4; s->nTriBlocks = nIdx * 3;
     s->capNodeBlocks = s->nNodeBlocks; s->capTriBlocks = s->nTriBlocks;
     s->bytes = nNodes * 64 + nIdx * 48;
+    int r = 0;
+    if (e == hipSuccess && dm.src.indices) r = keepMeshIndices(s, dm.src);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (dIdx) hipFree(dIdx);
+    if (e != hipSuccess) { tbvh_free_scene(s); return fail(TBVH_E_HIP, "BVH_GPU upload failed: %s", hipGetErrorString(e)); }
+    if (!r && dm.src.general()) r = checkStatus(c);   // (device-resident indices: the gather reports an index that is not a vertex)
+    if (r) { tbvh_free_scene(s); return r; }
     *out = s;
     return 0;
+}
+
+int tbvh_upload_bvh_gpu(tbvh_context* c, const void* nodes64, uint64_t nNodes, const uint32_t* primIdx, uint64_t nIdx,
+                        const void* verts16, uint64_t nTris, tbvh_scene** out) {
+    if (!c || !nodes64 || !primIdx || !verts16 || !out || nNodes == 0) return fail(TBVH_E_INVALID, "tbvh_upload_bvh_gpu: null/empty argument");
+    return uploadBvhGpuImpl(c, nodes64, nNodes, primIdx, nIdx, flatMesh(verts16, nTris, 0), out);
+}
+
+int tbvh_upload_bvh_gpu_mesh(tbvh_context* c, const void* nodes64, uint64_t nNodes, const uint32_t* primIdx, uint64_t nIdx, const tbvh_mesh* mesh, tbvh_scene** out) {
+    if (!c || !nodes64 || !primIdx || !out || nNodes == 0) return fail(TBVH_E_INVALID, "tbvh_upload_bvh_gpu_mesh: null/empty argument");
+    if (int r = checkMesh(mesh, "tbvh_upload_bvh_gpu_mesh")) return r;
+    return uploadBvhGpuImpl(c, nodes64, nNodes, primIdx, nIdx, *mesh, out);
 }
 
 int tbvh_upload_bvh4_gpu(tbvh_context* c, const void* blocks16, uint64_t nBlocks, tbvh_scene** out) {
@@ -517,29 +583,45 @@ int tbvh_update_tlas(tbvh_scene* s, const void* nodes64, uint64_t nNodes, const 
 // ---- in-place re-upload of a BLAS whose blob the caller refitted / re-converted on the host ---------------------------------------------
 // (BVH::Refit tiny_bvh.h:3055-3093 + X::ConvertFrom again: the reference's flow for animated geometry.)  The device allocations, the scene
 // handle and the pointers the TLASes over this BLAS hold stay as they are; the library's derived copies follow.
-int tbvh_update_bvh_gpu(tbvh_scene* s, const void* nodes64, uint64_t nNodes, const uint32_t* primIdx, uint64_t nIdx, const void* verts16, uint64_t nTris) {
-    TBVH_REFUSE_DOUBLE(s, "tbvh_update_bvh_gpu");
-    TBVH_REFUSE_VOXEL(s, "tbvh_update_bvh_gpu");
-    TBVH_REFUSE_CUSTOM(s, "tbvh_update_bvh_gpu");
-    if (!s || s->isTlas || s->layout != TBVH_LAYOUT_BVH_GPU || !nodes64 || !primIdx || !verts16 || !nNodes) return fail(TBVH_E_INVALID, "tbvh_update_bvh_gpu: not a BVH_GPU scene or null/empty argument");
-    if (nNodes * 4 > s->capNodeBlocks || nIdx * 3 > s->capTriBlocks) return fail(TBVH_E_INVALID, "tbvh_update_bvh_gpu: the blob (%llu nodes, %llu indices) is larger than the one uploaded: free the scene and upload", (unsigned long long)nNodes, (unsigned long long)nIdx);
+static int updateBvhGpuImpl(const char* who, tbvh_scene* s, const void* nodes64, uint64_t nNodes, const uint32_t* primIdx, uint64_t nIdx, const tbvh_mesh* mesh) {
+    TBVH_REFUSE_DOUBLE(s, who);
+    TBVH_REFUSE_VOXEL(s, who);
+    TBVH_REFUSE_CUSTOM(s, who);
+    if (!s || s->isTlas || s->layout != TBVH_LAYOUT_BVH_GPU || !nodes64 || !primIdx || !mesh || !mesh->verts || !nNodes) return fail(TBVH_E_INVALID, "%s: not a BVH_GPU scene or null/empty argument", who);
+    if (nNodes * 4 > s->capNodeBlocks || nIdx * 3 > s->capTriBlocks) return fail(TBVH_E_INVALID, "%s: the blob (%llu nodes, %llu indices) is larger than the one uploaded: free the scene and upload", who, (unsigned long long)nNodes, (unsigned long long)nIdx);
     if (const char* why = validate_bvh_gpu((const NodeAL*)nodes64, nNodes, nIdx)) return fail(why == kValidateNoMemory ? TBVH_E_NOMEM : TBVH_E_FORMAT, "%s", why);
     tbvh_context* c = s->ctx;
     TBVH_ENTER(c);
-    uint32_t* dIdx = nullptr; float4* dVerts = nullptr;
+    uint32_t* dIdx = nullptr;
+    DeviceMesh dm;
     hipError_t e = hipMalloc((void**)&dIdx, (nIdx ? nIdx : 1) * 4);
-    if (e == hipSuccess) e = hipMalloc((void**)&dVerts, (nTris ? nTris : 1) * 48);
+    if (e == hipSuccess && stageMesh(c, *mesh, dm)) e = hipErrorOutOfMemory;
     if (e == hipSuccess) e = hipMemcpyAsync(s->nodes, nodes64, nNodes * 64, hipMemcpyHostToDevice, c->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(dIdx, primIdx, nIdx * 4, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(dVerts, verts16, nTris * 48, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess && nIdx) { launch_gather_tris(dIdx, dVerts, s->tris, nIdx, nTris, c->stream); e = hipGetLastError(); }
+    if (e == hipSuccess && nIdx) { launch_gather_tris(dIdx, dm.src, s->tris, nIdx, c->status, c->stream); e = hipGetLastError(); }
+    int r = 0;
+    if (e == hipSuccess && dm.src.indices) r = keepMeshIndices(s, dm.src);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
     if (dIdx) hipFree(dIdx);
-    if (dVerts) hipFree(dVerts);
-    if (e != hipSuccess) return fail(TBVH_E_HIP, "tbvh_update_bvh_gpu: %s", hipGetErrorString(e));
+    if (e != hipSuccess) return fail(TBVH_E_HIP, "%s: %s", who, hipGetErrorString(e));
+    if (!dm.src.indices && s->meshIdx) {   // re-uploaded from vertices without indices: a held index buffer would describe another mesh
+        hipFree(s->meshIdx); s->meshIdx = nullptr;
+        s->bytes -= s->meshIdxTris * 12; s->meshIdxTris = 0;
+    }
     s->nNodeBlocks = nNodes * 4; s->nTriBlocks = nIdx * 3;
     dropCopiesAfterUpdate(s);   // (the copies are of the old tree: they come back once the blob has settled — tbvh_scene::pendingCopies)
-    return 0;
+    if (!r && dm.src.general()) r = checkStatus(c);
+    return r;
+}
+
+int tbvh_update_bvh_gpu(tbvh_scene* s, const void* nodes64, uint64_t nNodes, const uint32_t* primIdx, uint64_t nIdx, const void* verts16, uint64_t nTris) {
+    const tbvh_mesh m = flatMesh(verts16, nTris, 0);
+    return updateBvhGpuImpl("tbvh_update_bvh_gpu", s, nodes64, nNodes, primIdx, nIdx, &m);
+}
+
+int tbvh_update_bvh_gpu_mesh(tbvh_scene* s, const void* nodes64, uint64_t nNodes, const uint32_t* primIdx, uint64_t nIdx, const tbvh_mesh* mesh) {
+    if (s && s->layout == TBVH_LAYOUT_BVH_GPU && !s->isTlas) if (int r = checkMesh(mesh, "tbvh_update_bvh_gpu_mesh")) return r;
+    return updateBvhGpuImpl("tbvh_update_bvh_gpu_mesh", s, nodes64, nNodes, primIdx, nIdx, mesh);
 }
 
 int tbvh_update_bvh4_gpu(tbvh_scene* s, const void* blocks16, uint64_t nBlocks) {
@@ -608,8 +690,7 @@ int tbvh_update_cwbvh(tbvh_scene* s, const void* nodes16, uint64_t nNodeBlocks, 
 
 namespace {
 // BVH2 (device arrays) -> CWBVH scene.  msBefore: device time already spent on this request (builder), added to the report.
-int convertDeviceImpl4(tbvh_context* c, const float4* dN2, uint64_t nNodes2, const uint32_t* dIdx, uint64_t nIdx, const float4* dV, uint64_t nTris,
-                       tbvh_scene** out) {
+int convertDeviceImpl4(tbvh_context* c, const float4* dN2, uint64_t nNodes2, const uint32_t* dIdx, uint64_t nIdx, const MeshSrc& dV, tbvh_scene** out) {
     struct Tmp {
         void *blocks = nullptr, *itA = nullptr, *itB = nullptr, *cnt = nullptr;
         ~Tmp() { for (void* p : {blocks, itA, itB, cnt}) if (p) hipFree(p); }
@@ -619,10 +700,11 @@ int convertDeviceImpl4(tbvh_context* c, const float4* dN2, uint64_t nNodes2, con
     HIP_TRY(hipMalloc(&t.blocks, capBlocks * 16));
     HIP_TRY(hipMalloc(&t.itA, capItems * 8)); HIP_TRY(hipMalloc(&t.itB, capItems * 8)); HIP_TRY(hipMalloc(&t.cnt, 16));
     uint64_t nBlocks = 0; uint32_t levels = 0;
-    HIP_TRY(run_convert_bvh4(dN2, (uint32_t)nNodes2, dIdx, nIdx, dV, nTris, (float4*)t.blocks, capBlocks, (uint2*)t.itA, (uint2*)t.itB, (uint32_t*)t.cnt, c->status,
+    HIP_TRY(run_convert_bvh4(dN2, (uint32_t)nNodes2, dIdx, nIdx, dV, (float4*)t.blocks, capBlocks, (uint2*)t.itA, (uint2*)t.itB, (uint32_t*)t.cnt, c->status,
                              c->stream, &nBlocks, &levels));
     uint32_t st = 0;
     HIP_TRY(hipMemcpy(&st, c->status, 4, hipMemcpyDeviceToHost));
+    if (st & kStatusMeshIndex) { hipMemset(c->status, 0, 4); return fail(TBVH_E_FORMAT, "BVH2 -> BVH4_GPU: mesh: a vertex index is not a vertex (index >= n_verts)"); }
     if (st & 12u) {
         hipMemset(c->status, 0, 4);
         return fail(TBVH_E_FORMAT, (st & 8u) ? "BVH2 -> BVH4_GPU: a node's inline triangles exceed the 16-bit relative offset (leaves too large)"
@@ -641,9 +723,8 @@ int convertDeviceImpl4(tbvh_context* c, const float4* dN2, uint64_t nNodes2, con
 
 }  // namespace
 namespace tbvh_capi {
-static int convertDeviceImpl(tbvh_context* c, int layout, const float4* dN2, uint64_t nNodes2, const uint32_t* dIdx, uint64_t nIdx, const float4* dV, uint64_t nTris,
-                      tbvh_scene** out) {
-    if (layout == TBVH_LAYOUT_BVH4_GPU) return convertDeviceImpl4(c, dN2, nNodes2, dIdx, nIdx, dV, nTris, out);
+static int convertDeviceImpl(tbvh_context* c, int layout, const float4* dN2, uint64_t nNodes2, const uint32_t* dIdx, uint64_t nIdx, const MeshSrc& dV, tbvh_scene** out) {
+    if (layout == TBVH_LAYOUT_BVH4_GPU) return convertDeviceImpl4(c, dN2, nNodes2, dIdx, nIdx, dV, out);
     struct Tmp {
         void *nodes = nullptr, *tris = nullptr, *itA = nullptr, *itB = nullptr, *cnt = nullptr;
         ~Tmp() { for (void* p : {nodes, tris, itA, itB, cnt}) if (p) hipFree(p); }
@@ -653,10 +734,11 @@ static int convertDeviceImpl(tbvh_context* c, int layout, const float4* dN2, uin
     HIP_TRY(hipMalloc(&t.nodes, (size_t)capNodes * 80)); HIP_TRY(hipMalloc(&t.tris, nIdx * 48));
     HIP_TRY(hipMalloc(&t.itA, (size_t)capNodes * 8)); HIP_TRY(hipMalloc(&t.itB, (size_t)capNodes * 8)); HIP_TRY(hipMalloc(&t.cnt, 16));
     uint32_t nWide = 0, levels = 0; uint64_t nWideTris = 0;
-    HIP_TRY(run_convert_cwbvh(dN2, (uint32_t)nNodes2, dIdx, nIdx, dV, nTris, (float4*)t.nodes, capNodes, (float4*)t.tris, nIdx, (uint2*)t.itA, (uint2*)t.itB,
+    HIP_TRY(run_convert_cwbvh(dN2, (uint32_t)nNodes2, dIdx, nIdx, dV, (float4*)t.nodes, capNodes, (float4*)t.tris, nIdx, (uint2*)t.itA, (uint2*)t.itB,
                               (uint32_t*)t.cnt, c->status, c->stream, &nWide, &nWideTris, &levels));
     uint32_t st = 0;
     HIP_TRY(hipMemcpy(&st, c->status, 4, hipMemcpyDeviceToHost));
+    if (st & kStatusMeshIndex) { hipMemset(c->status, 0, 4); return fail(TBVH_E_FORMAT, "BVH2 -> CWBVH: mesh: a vertex index is not a vertex (index >= n_verts)"); }
     if (st & 12u) {
         hipMemset(c->status, 0, 4);
         return fail(TBVH_E_FORMAT, (st & 8u) ? "BVH2 -> CWBVH: a BVH2 leaf holds more than 3 triangles (SplitLeafs(3) first, like BVH8_CWBVH::ConvertFrom)"
@@ -682,75 +764,112 @@ static int convertDeviceImpl(tbvh_context* c, int layout, const float4* dN2, uin
 }
 }  // namespace
 
+static int convertBvh2Impl(const char* who, tbvh_context* c, const void* nodes32, uint64_t nNodes2, const uint32_t* primIdx, uint64_t nIdx, const tbvh_mesh& mesh,
+                           int onDevice, int layout, tbvh_scene** out) {
+    if (layout != TBVH_LAYOUT_CWBVH && layout != TBVH_LAYOUT_BVH4_GPU) return fail(TBVH_E_INVALID, "%s: target layout %d not supported (BVH8_CWBVH and BVH4_GPU are)", who, layout);
+    if (nNodes2 > 0x7fffffffull || nIdx > 0x7fffffffull) return fail(TBVH_E_INVALID, "%s: BVH2 too large for 32-bit node / triangle indices", who);
+    TBVH_ENTER(c);
+    struct Tmp {
+        void *n2 = nullptr, *idx = nullptr;
+        ~Tmp() { for (void* p : {n2, idx}) if (p) hipFree(p); }
+    } t;
+    DeviceMesh dm;
+    const float4* dN2 = (const float4*)nodes32;
+    const uint32_t* dIdx = primIdx;
+    if (!onDevice) {
+        HIP_TRY(hipMalloc(&t.n2, nNodes2 * 32)); HIP_TRY(hipMalloc(&t.idx, nIdx * 4));
+        HIP_TRY(hipMemcpyAsync(t.n2, nodes32, nNodes2 * 32, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipMemcpyAsync(t.idx, primIdx, nIdx * 4, hipMemcpyHostToDevice, c->stream));
+        dN2 = (const float4*)t.n2; dIdx = (const uint32_t*)t.idx;
+    }
+    if (int r = stageMesh(c, mesh, dm)) return r;
+    HIP_TRY(timedBegin(c));
+    int r = convertDeviceImpl(c, layout, dN2, nNodes2, dIdx, nIdx, dm.src, out);
+    HIP_TRY(timedEnd(c));
+    if (!r && dm.src.indices) {
+        r = keepMeshIndices(*out, dm.src);
+        if (!r && hipStreamSynchronize(c->stream) != hipSuccess) r = fail(TBVH_E_HIP, "%s: copying the index buffer failed", who);
+        if (r) { tbvh_free_scene(*out); *out = nullptr; }
+    }
+    return r;
+}
+
 int tbvh_convert_bvh2_device(tbvh_context* c, const void* nodes32, uint64_t nNodes2, const uint32_t* primIdx, uint64_t nIdx, const void* verts16,
                              uint64_t nTris, int onDevice, int layout, tbvh_scene** out) {
     if (!c || !nodes32 || !primIdx || !verts16 || !out || nNodes2 == 0 || nIdx == 0 || nTris == 0) return fail(TBVH_E_INVALID, "tbvh_convert_bvh2_device: null/empty argument");
-    if (layout != TBVH_LAYOUT_CWBVH && layout != TBVH_LAYOUT_BVH4_GPU) return fail(TBVH_E_INVALID, "tbvh_convert_bvh2_device: target layout %d not supported (BVH8_CWBVH and BVH4_GPU are)", layout);
-    if (nNodes2 > 0x7fffffffull || nIdx > 0x7fffffffull) return fail(TBVH_E_INVALID, "tbvh_convert_bvh2_device: BVH2 too large for 32-bit node / triangle indices");
-    TBVH_ENTER(c);
-    struct Tmp {
-        void *n2 = nullptr, *idx = nullptr, *v = nullptr;
-        ~Tmp() { for (void* p : {n2, idx, v}) if (p) hipFree(p); }
-    } t;
-    const float4 *dN2 = (const float4*)nodes32, *dV = (const float4*)verts16;
-    const uint32_t* dIdx = primIdx;
-    if (!onDevice) {
-        HIP_TRY(hipMalloc(&t.n2, nNodes2 * 32)); HIP_TRY(hipMalloc(&t.idx, nIdx * 4)); HIP_TRY(hipMalloc(&t.v, nTris * 48));
-        HIP_TRY(hipMemcpyAsync(t.n2, nodes32, nNodes2 * 32, hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(hipMemcpyAsync(t.idx, primIdx, nIdx * 4, hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(hipMemcpyAsync(t.v, verts16, nTris * 48, hipMemcpyHostToDevice, c->stream));
-        dN2 = (const float4*)t.n2; dIdx = (const uint32_t*)t.idx; dV = (const float4*)t.v;
-    }
-    HIP_TRY(timedBegin(c));
-    const int r = convertDeviceImpl(c, layout, dN2, nNodes2, dIdx, nIdx, dV, nTris, out);
-    HIP_TRY(timedEnd(c));
-    return r;
+    return convertBvh2Impl("tbvh_convert_bvh2_device", c, nodes32, nNodes2, primIdx, nIdx, flatMesh(verts16, nTris, onDevice), onDevice, layout, out);
+}
+
+int tbvh_convert_bvh2_device_mesh(tbvh_context* c, const void* nodes32, uint64_t nNodes2, const uint32_t* primIdx, uint64_t nIdx, const tbvh_mesh* mesh,
+                                  int onDevice, int layout, tbvh_scene** out) {
+    if (!c || !nodes32 || !primIdx || !out || nNodes2 == 0 || nIdx == 0) return fail(TBVH_E_INVALID, "tbvh_convert_bvh2_device_mesh: null/empty argument");
+    if (int r = checkMesh(mesh, "tbvh_convert_bvh2_device_mesh")) return r;
+    return convertBvh2Impl("tbvh_convert_bvh2_device_mesh", c, nodes32, nNodes2, primIdx, nIdx, *mesh, onDevice, layout, out);
 }
 
 namespace {
 // builder: 0 = LBVH (maxLeafTris applies), 1 = PLOC (one triangle per leaf; radius = search window to each side)
-int buildDeviceImpl(const char* who, tbvh_context* c, const void* verts16, uint64_t nTris, int onDevice, int layout, uint32_t maxLeafTris, int builder, uint32_t radius,
-                    tbvh_scene** out) {
-    if (!c || !verts16 || !out || nTris == 0) return fail(TBVH_E_INVALID, "%s: null/empty argument", who);
+int buildDeviceImpl(const char* who, tbvh_context* c, const tbvh_mesh& mesh, int layout, uint32_t maxLeafTris, int builder, uint32_t radius, tbvh_scene** out) {
+    const uint64_t nTris = mesh.n_tris;
+    if (!c || !mesh.verts || !out || nTris == 0) return fail(TBVH_E_INVALID, "%s: null/empty argument", who);
     if (layout != TBVH_LAYOUT_CWBVH && layout != TBVH_LAYOUT_BVH4_GPU) return fail(TBVH_E_INVALID, "%s: target layout %d not supported (BVH8_CWBVH and BVH4_GPU are)", who, layout);
     if (nTris > 0x3fffffffull) return fail(TBVH_E_INVALID, "%s: too many triangles for 32-bit node indices", who);
     TBVH_ENTER(c);
     struct Tmp {
-        void *v = nullptr, *n2 = nullptr, *idx = nullptr, *scratch = nullptr;
-        ~Tmp() { for (void* p : {v, n2, idx, scratch}) if (p) hipFree(p); }
+        void *n2 = nullptr, *idx = nullptr, *scratch = nullptr;
+        ~Tmp() { for (void* p : {n2, idx, scratch}) if (p) hipFree(p); }
     } t;
-    const float4* dV = (const float4*)verts16;
-    if (!onDevice) {
-        HIP_TRY(hipMalloc(&t.v, nTris * 48));
-        HIP_TRY(hipMemcpyAsync(t.v, verts16, nTris * 48, hipMemcpyHostToDevice, c->stream));
-        dV = (const float4*)t.v;
-    }
+    DeviceMesh dm;
+    if (int r = stageMesh(c, mesh, dm)) return r;
     size_t sortTemp = 0, scanTemp = 0;
     const size_t scratchBytes = builder == 1 ? ploc_scratch_bytes((uint32_t)nTris, &sortTemp, &scanTemp) : lbvh_scratch_bytes((uint32_t)nTris, &sortTemp);
     HIP_TRY(hipMalloc(&t.n2, nTris * 2 * 32)); HIP_TRY(hipMalloc(&t.idx, nTris * 4)); HIP_TRY(hipMalloc(&t.scratch, scratchBytes));
     HIP_TRY(timedBegin(c));
-    if (builder == 1) HIP_TRY(launch_ploc_build(dV, (uint32_t)nTris, radius, (float4*)t.n2, (uint32_t*)t.idx, t.scratch, sortTemp, scanTemp, c->stream, nullptr));
-    else HIP_TRY(launch_lbvh_build(dV, (uint32_t)nTris, maxLeafTris, (float4*)t.n2, (uint32_t*)t.idx, t.scratch, sortTemp, c->stream));
-    const int r = convertDeviceImpl(c, layout, (const float4*)t.n2, nTris * 2, (const uint32_t*)t.idx, nTris, dV, nTris, out);
+    if (builder == 1) HIP_TRY(launch_ploc_build(dm.src, (uint32_t)nTris, radius, (float4*)t.n2, (uint32_t*)t.idx, t.scratch, sortTemp, scanTemp, c->stream, nullptr));
+    else HIP_TRY(launch_lbvh_build(dm.src, (uint32_t)nTris, maxLeafTris, (float4*)t.n2, (uint32_t*)t.idx, t.scratch, sortTemp, c->stream));
+    int r = convertDeviceImpl(c, layout, (const float4*)t.n2, nTris * 2, (const uint32_t*)t.idx, nTris, dm.src, out);
     HIP_TRY(timedEnd(c));
+    if (!r && dm.src.indices) {
+        r = keepMeshIndices(*out, dm.src);
+        if (!r && hipStreamSynchronize(c->stream) != hipSuccess) r = fail(TBVH_E_HIP, "%s: copying the index buffer failed", who);
+        if (r) { tbvh_free_scene(*out); *out = nullptr; }
+    }
     return r;
 }
 }  // namespace
 
-int tbvh_build_device(tbvh_context* c, const void* verts16, uint64_t nTris, int onDevice, int layout, uint32_t maxLeafTris, tbvh_scene** out) {
+// LBVH leaf size: 0 = the layout's default; false: more than the layout holds
+static bool lbvhLeafTris(const char* who, int layout, uint32_t& maxLeafTris) {
     const uint32_t leafCap = layout == TBVH_LAYOUT_CWBVH ? 3u : 4u;
     // default: one triangle per leaf for CWBVH.  Contiguous Morton ranges make poor multi-triangle leaves: measured on the
     // Bistro stand-in, 1 / 2 / 3 triangles per leaf trace camera rays at 3629 / 3354 / 3125 and bounce rays at 2323 / 2150 /
     // 1884 MRays/s (the host SAH tree: 3300 / 2480), for 13 instead of 8 ms of build time and 22 % more memory
     if (maxLeafTris == 0) maxLeafTris = layout == TBVH_LAYOUT_CWBVH ? 1u : leafCap;
-    if (maxLeafTris > leafCap) return fail(TBVH_E_INVALID, "tbvh_build_device: at most %u triangles per leaf for this layout", leafCap);
-    return buildDeviceImpl("tbvh_build_device", c, verts16, nTris, onDevice, layout, maxLeafTris, 0, 0, out);
+    if (maxLeafTris > leafCap) { fail(TBVH_E_INVALID, "%s: at most %u triangles per leaf for this layout", who, leafCap); return false; }
+    return true;
+}
+
+int tbvh_build_device(tbvh_context* c, const void* verts16, uint64_t nTris, int onDevice, int layout, uint32_t maxLeafTris, tbvh_scene** out) {
+    if (!lbvhLeafTris("tbvh_build_device", layout, maxLeafTris)) return TBVH_E_INVALID;
+    return buildDeviceImpl("tbvh_build_device", c, flatMesh(verts16, nTris, onDevice), layout, maxLeafTris, 0, 0, out);
 }
 
 int tbvh_build_device_ploc(tbvh_context* c, const void* verts16, uint64_t nTris, int onDevice, int layout, uint32_t radius, tbvh_scene** out) {
     if (radius == 0) radius = 16;
     if (radius > 32u) return fail(TBVH_E_INVALID, "tbvh_build_device_ploc: search radius %u (1..32; 0 = the default 16)", radius);
-    return buildDeviceImpl("tbvh_build_device_ploc", c, verts16, nTris, onDevice, layout, 1, 1, radius, out);
+    return buildDeviceImpl("tbvh_build_device_ploc", c, flatMesh(verts16, nTris, onDevice), layout, 1, 1, radius, out);
+}
+
+int tbvh_build_device_mesh(tbvh_context* c, const tbvh_mesh* mesh, int layout, uint32_t maxLeafTris, int builder, uint32_t radius, tbvh_scene** out) {
+    if (!c || !out) return fail(TBVH_E_INVALID, "tbvh_build_device_mesh: null argument");
+    if (int r = checkMesh(mesh, "tbvh_build_device_mesh")) return r;
+    if (builder == 0) { if (!lbvhLeafTris("tbvh_build_device_mesh", layout, maxLeafTris)) return TBVH_E_INVALID; }
+    else if (builder == 1) {
+        if (radius == 0) radius = 16;
+        if (radius > 32u) return fail(TBVH_E_INVALID, "tbvh_build_device_mesh: search radius %u (1..32; 0 = the default 16)", radius);
+        maxLeafTris = 1;
+    } else return fail(TBVH_E_INVALID, "tbvh_build_device_mesh: builder %d (0 = LBVH, 1 = PLOC)", builder);
+    return buildDeviceImpl("tbvh_build_device_mesh", c, *mesh, layout, maxLeafTris, builder, radius, out);
 }
 
 namespace {
@@ -819,22 +938,17 @@ int tbvh_scene_download(tbvh_scene* s, int which, void* dst, uint64_t capBytes, 
     return 0;
 }
 
-namespace {
-constexpr uint64_t kRefitKeepRays = 8ull << 20;   // a copy's refit (0.3-0.5 ms per 100 k triangles) pays from about this many rays per refit on (0.04-0.08 ns gained per ray)
-// a mesh refitted every frame with few rays traced in between: the copies are dropped (they come back like after an update: tbvh_scene::pendingCopies)
-bool refitDropsCopies(tbvh_scene* s) {
-    uint64_t total = s->raysTraced;
-    for (size_t i = 0; i < s->usedBy.size(); i++) {
-        bool seen = false;
-        for (size_t k = 0; k < i; k++) seen |= s->usedBy[k] == s->usedBy[i];
-        if (!seen) total += s->usedBy[i]->raysTraced;
+// the scene's vertex staging buffer holds `bytes` bytes of the caller's host array (asynchronous copy)
+static int stageRefitVertices(tbvh_scene* s, const void* hostVerts, uint64_t bytes) {
+    if (s->vertStageBytes < bytes) {
+        if (s->vertStage) hipFree(s->vertStage);
+        s->vertStage = nullptr; s->vertStageBytes = 0;
+        HIP_TRY(hipMalloc((void**)&s->vertStage, bytes));
+        s->vertStageBytes = bytes;
     }
-    const bool drop = (s->wide || s->wide4) && s->refitSeen && total - s->raysAtRefit < kRefitKeepRays;
-    s->refitSeen = true; s->raysAtRefit = total;
-    if (drop) dropCopiesAfterUpdate(s);
-    return drop;
+    HIP_TRY(hipMemcpyAsync(s->vertStage, hostVerts, bytes, hipMemcpyHostToDevice, s->ctx->stream));
+    return 0;
 }
-}  // namespace
 
 int tbvh_refit(tbvh_scene* s, const void* verts16, uint64_t nTris, int onDevice) {
     TBVH_REFUSE_DOUBLE(s, "tbvh_refit");
@@ -844,59 +958,58 @@ int tbvh_refit(tbvh_scene* s, const void* verts16, uint64_t nTris, int onDevice)
     if (s->isTlas) return fail(TBVH_E_INVALID, "tbvh_refit: a TLAS is rebuilt with tbvh_rebuild_tlas_device / tbvh_update_tlas");
     tbvh_context* c = s->ctx;
     TBVH_ENTER(c);
-    if (s->layout == TBVH_LAYOUT_BVH4_GPU) {
-        // node list per level, child-box hand-over area: sized for the most nodes the stream can hold (4 blocks each)
-        const uint32_t capNodes = (uint32_t)(s->nNodeBlocks / 4 + 1);
-        if (!s->refitScratch) HIP_TRY(hipMalloc(&s->refitScratch, (size_t)capNodes * (16 + 128) + 256));
-        const float4* dv4 = (const float4*)verts16;
-        if (!onDevice) {
-            if (s->vertStageTris < nTris) {
-                if (s->vertStage) hipFree(s->vertStage);
-                s->vertStage = nullptr; s->vertStageTris = 0;
-                HIP_TRY(hipMalloc((void**)&s->vertStage, nTris * 48));
-                s->vertStageTris = nTris;
-            }
-            HIP_TRY(hipMemcpyAsync(s->vertStage, verts16, nTris * 48, hipMemcpyHostToDevice, c->stream));
-            dv4 = s->vertStage;
-        }
-        char* base = (char*)s->refitScratch;
-        uint32_t* counter = (uint32_t*)base;
-        void* items = base + 256;
-        float4* childBox = (float4*)(base + 256 + (size_t)capNodes * 16);
-        HIP_TRY(timedBegin(c));
-        HIP_TRY(run_refit_bvh4(s->nodes, s->nNodeBlocks, dv4, nTris, items, capNodes, counter, childBox, s->b4Levels, c->status, c->stream));
-        HIP_TRY(timedEnd(c));
-        if (refitDropsCopies(s)) return 0;
-        if (s->wide) return tbvh_refit(s->wide, dv4, nTris, 1);   // the 8-wide copy follows
-        return 0;
-    }
-    if (s->layout != TBVH_LAYOUT_CWBVH && s->layout != TBVH_LAYOUT_BVH_GPU)
+    if (s->layout != TBVH_LAYOUT_CWBVH && s->layout != TBVH_LAYOUT_BVH_GPU && s->layout != TBVH_LAYOUT_BVH4_GPU)
         return fail(TBVH_E_INVALID, "tbvh_refit: layout %d is not refittable", s->layout);
-    const uint32_t nNodes = (uint32_t)(s->layout == TBVH_LAYOUT_CWBVH ? s->nNodeBlocks / 5 : s->nNodeBlocks / 4);
-    const uint64_t nRecords = s->nTriBlocks / 3;
-    if (!s->refitScratch) HIP_TRY(hipMalloc(&s->refitScratch, refit_scratch_bytes(s->layout, nNodes)));
     const float4* dv = (const float4*)verts16;
     if (!onDevice) {
-        if (s->vertStageTris < nTris) {
-            if (s->vertStage) hipFree(s->vertStage);
-            s->vertStage = nullptr; s->vertStageTris = 0;
-            HIP_TRY(hipMalloc((void**)&s->vertStage, nTris * 48));
-            s->vertStageTris = nTris;
-        }
-        HIP_TRY(hipMemcpyAsync(s->vertStage, verts16, nTris * 48, hipMemcpyHostToDevice, c->stream));
+        if (int r = stageRefitVertices(s, verts16, nTris * 48)) return r;
         dv = s->vertStage;
     }
-    HIP_TRY(timedBegin(c));
-    HIP_TRY(launch_refit(s->layout, s->nodes, nNodes, s->tris, nRecords, dv, nTris, s->refitScratch, c->status, c->stream));
-    HIP_TRY(timedEnd(c));
-    // derived node layouts of the experiment kernels would be stale now
-    if (s->nodes128) launch_cwbvh_pad(s->nodes, s->nodes128, nNodes, c->stream);   // keep the padded copy current
-    if (s->nodesHy) launch_cwbvh_derive_hybrid(s->nodes, s->hyPerm, s->nodesHy, nNodes, s->hybridK, (c->embedTris && !(c->expFlags & 8u)) ? s->tris : nullptr, c->stream);
-    if (s->tris64) launch_cwbvh_pad_tris(s->tris, s->tris64, s->nTriBlocks / 3, c->stream);
-    if (refitDropsCopies(s)) return 0;
-    if (s->wide) if (int r = tbvh_refit(s->wide, dv, nTris, 1)) return r;     // the 8-wide copy follows (same vertices, already on the device)
-    if (s->wide4) return tbvh_refit(s->wide4, dv, nTris, 1);                 // ... and the 4-wide one
-    return 0;
+    return refitDeviceSource(s, flat_mesh(dv, nTris));
+}
+
+int tbvh_refit_mesh(tbvh_scene* s, const tbvh_mesh* mesh) {
+    TBVH_REFUSE_DOUBLE(s, "tbvh_refit_mesh");
+    TBVH_REFUSE_VOXEL(s, "tbvh_refit_mesh");
+    TBVH_REFUSE_CUSTOM(s, "tbvh_refit_mesh");
+    if (!s) return fail(TBVH_E_INVALID, "tbvh_refit_mesh: null scene");
+    if (s->isTlas) return fail(TBVH_E_INVALID, "tbvh_refit_mesh: a TLAS is rebuilt with tbvh_rebuild_tlas_device / tbvh_update_tlas");
+    if (s->layout != TBVH_LAYOUT_CWBVH && s->layout != TBVH_LAYOUT_BVH_GPU && s->layout != TBVH_LAYOUT_BVH4_GPU)
+        return fail(TBVH_E_INVALID, "tbvh_refit_mesh: layout %d is not refittable", s->layout);
+    const bool held = mesh && !mesh->indices && s->meshIdx;   // indices == NULL on a scene made from an indexed mesh: the indices the scene holds
+    if (int r = checkMesh(mesh, "tbvh_refit_mesh", held)) return r;
+    if (held && mesh->n_tris != s->meshIdxTris)
+        return fail(TBVH_E_INVALID, "tbvh_refit_mesh: %llu triangles, the index buffer the scene holds has %llu", (unsigned long long)mesh->n_tris, (unsigned long long)s->meshIdxTris);
+    if (mesh->indices && s->meshIdx && mesh->n_tris != s->meshIdxTris)
+        return fail(TBVH_E_INVALID, "tbvh_refit_mesh: new indices for %llu triangles, the scene was made from %llu", (unsigned long long)mesh->n_tris, (unsigned long long)s->meshIdxTris);
+    tbvh_context* c = s->ctx;
+    TBVH_ENTER(c);
+    MeshSrc src;
+    src.nTris = mesh->n_tris; src.nVerts = (uint32_t)mesh->n_verts; src.stride = mesh->stride_bytes ? mesh->stride_bytes : 16u;
+    src.verts = (const float4*)mesh->verts;
+    if (!mesh->on_device) {   // n_verts * stride_bytes go over the link, not n_tris * 48
+        if (int r = stageRefitVertices(s, mesh->verts, meshVertexBytes(*mesh))) return r;
+        src.verts = s->vertStage;
+    }
+    if (!mesh->indices) {
+        src.indices = held ? s->meshIdx : nullptr;
+        return refitDeviceSource(s, src);
+    }
+    // indices passed: this refit reads them where they are (host indices from a temporary device copy).  A scene that holds an index buffer takes
+    // them as its new copy afterwards — device-resident ones only once the kernels have read them all without finding one out of range, so a bad
+    // buffer never replaces a good one.  A scene made without indices does not start holding any: what indices == NULL means for it stays as it was.
+    void* tmp = nullptr;
+    src.indices = mesh->indices;
+    if (!mesh->on_device) {
+        HIP_TRY(hipMalloc(&tmp, mesh->n_tris * 12));
+        if (hipMemcpyAsync(tmp, mesh->indices, mesh->n_tris * 12, hipMemcpyHostToDevice, c->stream) != hipSuccess) { hipFree(tmp); return fail(TBVH_E_HIP, "tbvh_refit_mesh: copying the indices failed"); }
+        src.indices = (const uint32_t*)tmp;
+    }
+    int r = refitDeviceSource(s, src);
+    if (!r && mesh->on_device) r = checkStatus(c);   // (synchronizes; only the kernels have seen these indices)
+    if (!r && s->meshIdx) r = keepMeshIndices(s, src);
+    if (tmp) { hipStreamSynchronize(c->stream); hipFree(tmp); }
+    return r;
 }
 
 int tbvh_rebuild_tlas_device(tbvh_scene* s, const void* transforms, int onDevice, const float* blasBounds6, uint64_t nBlas) {
@@ -999,6 +1112,8 @@ void tbvh_free_scene(tbvh_scene* s) {
     if (s->refitScratch) hipFree(s->refitScratch);
     if (s->opmap) hipFree(s->opmap);
     if (s->vertStage) hipFree(s->vertStage);
+    if (s->meshIdx) hipFree(s->meshIdx);
+    if (s->idxStage) hipFree(s->idxStage);
     for (auto& kind : s->cohTuner) for (CohTuner& tu : kind) tu.drop_pending();
     for (size_t i = 0; i < c->scenes.size(); i++)
         if (c->scenes[i] == s) { c->scenes.erase(c->scenes.begin() + i); break; }

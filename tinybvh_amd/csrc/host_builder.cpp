@@ -527,9 +527,9 @@ void split_piece(const SplitGrid& g, const Poly& poly, const Box& box, uint32_t 
 }
 
 // prims / refTri: one entry per reference (>= one per triangle), in triangle order
-void presplit(const Vec4* verts, uint32_t triCount, float budgetFrac, std::vector<Prim>& prims, std::vector<uint32_t>& refTri) {
+void presplit(const HostMesh& verts, uint32_t triCount, float budgetFrac, std::vector<Prim>& prims, std::vector<uint32_t>& refTri) {
     Box scene; scene.reset();
-    for (size_t i = 0; i < (size_t)triCount * 3; i++) scene.grow(&verts[i].x);
+    for (size_t i = 0; i < (size_t)triCount; i++) for (int k = 0; k < 3; k++) scene.grow(verts.xyz(i, k));
     SplitGrid g;
     float pad[3];
     for (int a = 0; a < 3; a++) {
@@ -539,7 +539,7 @@ void presplit(const Vec4* verts, uint32_t triCount, float budgetFrac, std::vecto
     std::vector<float> prio(triCount);
     std::vector<Box> boxes(triCount);
     for (uint32_t i = 0; i < triCount; i++) {
-        const Vec4* v = verts + 3 * (size_t)i;
+        const Vec4 v[3] = {verts.at(i, 0), verts.at(i, 1), verts.at(i, 2)};
         Box b; b.reset();
         for (int k = 0; k < 3; k++) b.grow(&v[k].x);
         boxes[i] = b;
@@ -575,7 +575,7 @@ void presplit(const Vec4* verts, uint32_t triCount, float budgetFrac, std::vecto
             continue;
         }
         Poly poly; poly.n = 3;
-        for (int k = 0; k < 3; k++) { poly.v[k][0] = verts[3 * (size_t)i + k].x; poly.v[k][1] = verts[3 * (size_t)i + k].y; poly.v[k][2] = verts[3 * (size_t)i + k].z; }
+        for (int k = 0; k < 3; k++) { const float* q = verts.xyz(i, k); poly.v[k][0] = q[0]; poly.v[k][1] = q[1]; poly.v[k][2] = q[2]; }
         split_piece(g, poly, boxes[i], s, i, pad, prims, refTri);
     }
 }
@@ -602,7 +602,7 @@ void refs_to_triangles(BVH2& bvh, const std::vector<uint32_t>& refTri) {
 
 }  // namespace
 
-void build_bvh2(const Vec4* verts, uint32_t triCount, const BuildParams& p, BVH2& out) {
+void build_bvh2(const HostMesh& verts, uint32_t triCount, const BuildParams& p, BVH2& out) {
     if (p.splitBudget > 0 && triCount > 0) {
         std::vector<Prim> prims; std::vector<uint32_t> refTri;
         presplit(verts, triCount, p.splitBudget, prims, refTri);
@@ -615,7 +615,7 @@ void build_bvh2(const Vec4* verts, uint32_t triCount, const BuildParams& p, BVH2
     for (uint32_t i = 0; i < triCount; i++) {
         Prim& pr = prims[i];
         pr.box.reset();
-        for (int k = 0; k < 3; k++) pr.box.grow(&verts[3 * (size_t)i + k].x);
+        for (int k = 0; k < 3; k++) pr.box.grow(verts.xyz(i, k));
         for (int a = 0; a < 3; a++) pr.c[a] = 0.5f * (pr.box.mn[a] + pr.box.mx[a]);
     }
     buildFromPrims(prims, p, out);
@@ -675,7 +675,7 @@ template <class F> static void parallel_ranges(size_t n, uint32_t threads, F bod
 }
 
 // BVH4_GPU stream (format: tiny_bvh.h:1248-1266, 5120-5127).
-void encode_bvh4_gpu(const BVH2& bvh, const Vec4* verts, const BuildParams& p, std::vector<Vec4>& blocks) {
+void encode_bvh4_gpu(const BVH2& bvh, const HostMesh& verts, const BuildParams& p, std::vector<Vec4>& blocks) {
     std::vector<WideNode<4>> W;
     if (p.greedyCollapse) collapse<4>(bvh, W);
     else collapse_optimal<4>(bvh, std::max<uint32_t>(p.maxLeafTris, 1), 1.0f, p.cPrim, W);
@@ -745,7 +745,7 @@ void encode_bvh4_gpu(const BVH2& bvh, const Vec4* verts, const BuildParams& p, s
                     info[i] = 0x80000000u | (c.triCount << 16) | rel;
                     for (uint32_t j = 0; j < c.triCount; j++) {
                         const uint32_t prim = bvh.primIdx[c.firstTri + j];
-                        const Vec4 v0 = verts[3 * (size_t)prim], v1 = verts[3 * (size_t)prim + 1], v2 = verts[3 * (size_t)prim + 2];
+                        const Vec4 v0 = verts.at(prim, 0), v1 = verts.at(prim, 1), v2 = verts.at(prim, 2);
                         blocks[out++] = Vec4{v0.x, v0.y, v0.z, asF32(prim)};
                         blocks[out++] = Vec4{v1.x - v0.x, v1.y - v0.y, v1.z - v0.z, v1.w - v0.w};
                         blocks[out++] = Vec4{v2.x - v0.x, v2.y - v0.y, v2.z - v0.z, v2.w - v0.w};
@@ -766,7 +766,7 @@ void encode_bvh4_gpu(const BVH2& bvh, const Vec4* verts, const BuildParams& p, s
 }
 
 // CWBVH (format: Ylitie et al. 2017 as laid out by tiny_bvh.h:5884-6018).
-void encode_cwbvh(const BVH2& bvh, const Vec4* verts, const BuildParams& p, std::vector<Vec4>& nodeBlocks,
+void encode_cwbvh(const BVH2& bvh, const HostMesh& verts, const BuildParams& p, std::vector<Vec4>& nodeBlocks,
                   std::vector<Vec4>& triBlocks) {
     std::vector<WideNode<8>> W;
     if (p.greedyCollapse) collapse<8>(bvh, W);
@@ -895,7 +895,7 @@ void encode_cwbvh(const BVH2& bvh, const Vec4* verts, const BuildParams& p, std:
                     nTris += c.triCount;
                     for (uint32_t j = 0; j < c.triCount; j++) {
                         const uint32_t prim = bvh.primIdx[c.firstTri + j];
-                        const Vec4 v0 = verts[3 * (size_t)prim], v1 = verts[3 * (size_t)prim + 1], v2 = verts[3 * (size_t)prim + 2];
+                        const Vec4 v0 = verts.at(prim, 0), v1 = verts.at(prim, 1), v2 = verts.at(prim, 2);
                         triBlocks[triOut++] = Vec4{v2.x - v0.x, v2.y - v0.y, v2.z - v0.z, v2.w - v0.w};
                         triBlocks[triOut++] = Vec4{v1.x - v0.x, v1.y - v0.y, v1.z - v0.z, v1.w - v0.w};
                         triBlocks[triOut++] = Vec4{v0.x, v0.y, v0.z, asF32(prim)};

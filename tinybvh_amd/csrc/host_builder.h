@@ -4,6 +4,7 @@
 // deterministic task-parallel subtree construction, surface-area-greedy wide collapse, and
 // encoders for BVH_GPU (Aila-Laine), BVH4_GPU and BVH8_CWBVH.
 #pragma once
+#include <cstddef>
 #include <cstdint>
 #include <vector>
 
@@ -50,16 +51,36 @@ struct BVH2 {
     uint32_t triCount = 0;
 };
 
-// Build a BVH2 over triangles given as 3 x Vec4 per triangle.
-void build_bvh2(const Vec4* verts, uint32_t triCount, const BuildParams& p, BVH2& out);
+// Where a builder or encoder finds triangle i's three vertices (tbvh_mesh of the public header; bvhvec4slice + BVH::vertIdx, tiny_bvh.h:428-436,
+// 1659-1661): vertex j = three floats at verts + j * stride bytes, j = indices[3 i + k], or 3 i + k without an index buffer.  w is read only
+// at a 16-byte stride (a bvhvec4); every other stride gives w = 0, and the 4 bytes behind z are never touched.
+struct HostMesh {
+    const void* verts = nullptr;
+    const uint32_t* indices = nullptr;
+    uint32_t stride = 16;
+    HostMesh() = default;
+    HostMesh(const Vec4* flat) : verts(flat) {}   // today's form: 3 x Vec4 per triangle
+    HostMesh(const void* v, uint32_t strideBytes, const uint32_t* idx) : verts(v), indices(idx), stride(strideBytes ? strideBytes : 16u) {}
+    const float* xyz(size_t tri, int k) const {
+        const size_t j = indices ? (size_t)indices[3 * tri + k] : 3 * tri + k;
+        return (const float*)((const char*)verts + j * stride);
+    }
+    Vec4 at(size_t tri, int k) const {
+        const float* p = xyz(tri, k);
+        return Vec4{p[0], p[1], p[2], stride == 16 ? p[3] : 0.f};
+    }
+};
+
+// Build a BVH2 over the triangles of a mesh (a plain const Vec4* converts: 3 x Vec4 per triangle).
+void build_bvh2(const HostMesh& verts, uint32_t triCount, const BuildParams& p, BVH2& out);
 
 // Build a BVH2 over arbitrary boxes (used for the TLAS): box i = {mn[3], mx[3]}.
 void build_bvh2_boxes(const float* boxes6, uint32_t count, const BuildParams& p, BVH2& out);
 
 // Encoders.
 void encode_bvh_gpu(const BVH2& bvh, std::vector<NodeAL>& out);
-void encode_bvh4_gpu(const BVH2& bvh, const Vec4* verts, const BuildParams& p, std::vector<Vec4>& blocks);
-void encode_cwbvh(const BVH2& bvh, const Vec4* verts, const BuildParams& p, std::vector<Vec4>& nodeBlocks,
+void encode_bvh4_gpu(const BVH2& bvh, const HostMesh& verts, const BuildParams& p, std::vector<Vec4>& blocks);
+void encode_cwbvh(const BVH2& bvh, const HostMesh& verts, const BuildParams& p, std::vector<Vec4>& nodeBlocks,
                   std::vector<Vec4>& triBlocks);
 
 // An uploaded BVH_GPU blob (Aila-Laine nodes: every node carries its CHILDREN's boxes, tiny_bvh.h:1095-1105) as a BVH2 in the Wald layout the wide

@@ -2,6 +2,7 @@
 #pragma once
 #include <vector>
 #include "device_common.h"
+#include "mesh_source.h"
 
 namespace tbvh {
 
@@ -88,8 +89,7 @@ struct SphereArgs {
     uint8_t* hit;            // device, 1 byte per sphere
     const float4* nodes;     // the scene's node array (BVH4_GPU: the stream, triangles inline)
     const float4* tris;      // BVH_GPU / BVH8_CWBVH triangle records
-    const float4* verts;
-    uint64_t nTris;
+    MeshSrc verts;           // the caller's vertices (mesh_source.h); verts.nTris triangles
     uint32_t* spill;         // stack spill area (8-byte entries)
     uint32_t spillStride;    // 8-byte entries per lane in `spill`
     uint32_t* counter;       // ray-pool counters of this launch and of the next one (ray_pool.h)
@@ -113,29 +113,30 @@ hipError_t launch_tlas_rebuild(float4* tlasNodes, uint32_t* tlasIdx, float4* ins
 // LBVH build on the device (kernels_build.hip)
 size_t lbvh_scratch_bytes(uint32_t n, size_t* sortTempBytes);
 size_t ploc_scratch_bytes(uint32_t n, size_t* sortTempBytes, size_t* scanTempBytes);
-hipError_t launch_ploc_build(const float4* verts, uint32_t n, uint32_t radius, float4* nodes32, uint32_t* primIdx, void* scratch, size_t sortTempBytes,
+hipError_t launch_ploc_build(const MeshSrc& verts, uint32_t n, uint32_t radius, float4* nodes32, uint32_t* primIdx, void* scratch, size_t sortTempBytes,
                              size_t scanTempBytes, hipStream_t s, uint32_t* steps);
-hipError_t launch_lbvh_build(const float4* verts, uint32_t n, uint32_t maxLeaf, float4* nodes32, uint32_t* primIdx, void* scratch, size_t sortTempBytes,
+hipError_t launch_lbvh_build(const MeshSrc& verts, uint32_t n, uint32_t maxLeaf, float4* nodes32, uint32_t* primIdx, void* scratch, size_t sortTempBytes,
                              hipStream_t s);
 // BVH2 -> CWBVH conversion on the device (kernels_convert.hip)
-hipError_t run_convert_cwbvh(const float4* nodes2, uint32_t nNodes2, const uint32_t* primIdx, uint64_t nIdx, const float4* verts, uint64_t nTris,
+hipError_t run_convert_cwbvh(const float4* nodes2, uint32_t nNodes2, const uint32_t* primIdx, uint64_t nIdx, const MeshSrc& verts,
                              float4* cwNodes, uint32_t capNodes, float4* cwTris, uint64_t capTris, uint2* itemsA, uint2* itemsB, uint32_t* counters,
                              uint32_t* status, hipStream_t s, uint32_t* nNodesOut, uint64_t* nTrisOut, uint32_t* levelsOut);
-hipError_t run_convert_bvh4(const float4* nodes2, uint32_t nNodes2, const uint32_t* primIdx, uint64_t nIdx, const float4* verts, uint64_t nTris,
+hipError_t run_convert_bvh4(const float4* nodes2, uint32_t nNodes2, const uint32_t* primIdx, uint64_t nIdx, const MeshSrc& verts,
                             float4* blocks, uint64_t capBlocks, uint2* itemsA, uint2* itemsB, uint32_t* counters, uint32_t* status, hipStream_t s,
                             uint64_t* nBlocksOut, uint32_t* levelsOut);
 // device BLAS refit (kernels_refit.hip)
-hipError_t run_refit_bvh4(float4* blocks, uint64_t nBlocks, const float4* verts, uint64_t nTris, void* itemsDev, uint32_t capNodes, uint32_t* counterDev,
+hipError_t run_refit_bvh4(float4* blocks, uint64_t nBlocks, const MeshSrc& verts, void* itemsDev, uint32_t capNodes, uint32_t* counterDev,
                           float4* childBox, std::vector<uint32_t>& levelFirst, uint32_t* status, hipStream_t s);
 size_t refit_scratch_bytes(int layout, uint32_t nNodes);
-hipError_t launch_refit(int layout, float4* nodes, uint32_t nNodes, float4* tris, uint64_t nTriRecords, const float4* verts, uint64_t nTris,
+hipError_t launch_refit(int layout, float4* nodes, uint32_t nNodes, float4* tris, uint64_t nTriRecords, const MeshSrc& verts,
                         void* scratch, uint32_t* status, hipStream_t s);
 void launch_stream_copy(const float4* src, float4* dst, uint64_t n16, hipStream_t s);
 void launch_stream_read(const float4* src, float* sink, uint64_t n16, uint32_t blocks, hipStream_t s);
 void launch_valu_mix(float* out, int iters, uint32_t blocks, hipStream_t s);   // 32 VALU instructions per iteration and wave
 void launch_pack_hits(const RayRec* rays, uint32_t* out, uint64_t n, hipStream_t s);
-void launch_gather_tris(const uint32_t* primIdx, const float4* verts, float4* out, uint64_t nIdx, uint64_t nTris,
-                        hipStream_t s);
+// (kernels_mesh.hip) every kernel that reads vertices takes a MeshSrc (mesh_source.h): flat 3 x float4 per triangle, or indexed / strided
+void launch_gather_tris(const uint32_t* primIdx, const MeshSrc& verts, float4* out, uint64_t nIdx, uint32_t* status, hipStream_t s);
+void launch_flatten_mesh(const MeshSrc& verts, float4* out, uint32_t* status, hipStream_t s);   // 3 float4 per triangle, in triangle order
 
 // ray generators (kernels_raygen.hip)
 struct CameraArgs {

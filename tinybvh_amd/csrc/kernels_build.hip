@@ -43,12 +43,17 @@ __device__ __forceinline__ unsigned long long spread21(uint32_t v) {   // 21 bit
 // per-triangle box + centroid bounds of the scene.  Grid-stride over the triangles, wave reduction, then ONE set of six
 // atomics per wave at the very end: the six words share a cache line, and same-line atomics are serialised memory-side
 // (~12 ns each): one set per 64 triangles cost 3 ms for Bistro, one per wave of a 2048-block grid costs nothing.
-__global__ void k_tri_boxes(const float4* __restrict__ verts, uint32_t n, float4* __restrict__ triMin, float4* __restrict__ triMax,
+// (GENERAL: mesh_source.h; a triangle whose vertex index is out of range gets a box at the origin here — the conversion's leaf writer, which fetches
+// the same triangle, reports it and the build fails)
+template <bool GENERAL>
+__global__ void k_tri_boxes(const MeshSrc verts, uint32_t n, float4* __restrict__ triMin, float4* __restrict__ triMax,
                             uint32_t* __restrict__ centreBounds) {
     float3 cmn = make_float3(1e30f, 1e30f, 1e30f), cmx = make_float3(-1e30f, -1e30f, -1e30f);
     for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
         float3 mn = make_float3(1e30f, 1e30f, 1e30f), mx = make_float3(-1e30f, -1e30f, -1e30f);
-        for (int k = 0; k < 3; k++) { const float4 v = verts[3 * (uint64_t)i + k]; const float3 p = make_float3(v.x, v.y, v.z); mn = min3(mn, p); mx = max3(mx, p); }
+        float4 v[3];
+        if (!mesh_tri<GENERAL>(verts, i, v[0], v[1], v[2])) v[0] = v[1] = v[2] = make_float4(0.f, 0.f, 0.f, 0.f);
+        for (int k = 0; k < 3; k++) { const float3 p = make_float3(v[k].x, v[k].y, v[k].z); mn = min3(mn, p); mx = max3(mx, p); }
         triMin[i] = make_float4(mn.x, mn.y, mn.z, 0.f); triMax[i] = make_float4(mx.x, mx.y, mx.z, 0.f);
         const float3 c = make_float3(0.5f * (mn.x + mx.x), 0.5f * (mn.y + mx.y), 0.5f * (mn.z + mx.z));
         cmn = min3(cmn, c); cmx = max3(cmx, c);
@@ -336,7 +341,7 @@ size_t lbvh_scratch_bytes(uint32_t n, size_t* sortTempBytes) {
 
 // verts: 3 float4 per triangle (device).  Out: nodes32 (2n BVHNode records; [1] unused), primIdx (n entries = the
 // triangles in Morton order).  maxLeaf: 1..3 triangles per leaf.
-hipError_t launch_lbvh_build(const float4* verts, uint32_t n, uint32_t maxLeaf, float4* nodes32, uint32_t* primIdx, void* scratch, size_t sortTempBytes,
+hipError_t launch_lbvh_build(const MeshSrc& verts, uint32_t n, uint32_t maxLeaf, float4* nodes32, uint32_t* primIdx, void* scratch, size_t sortTempBytes,
                              hipStream_t s) {
     const Scratch sc = carve(scratch, n, sortTempBytes);
     hipError_t e;
@@ -345,7 +350,8 @@ hipError_t launch_lbvh_build(const float4* verts, uint32_t n, uint32_t maxLeaf, 
     if ((e = hipMemsetAsync(sc.flags, 0, (size_t)n * 4, s)) != hipSuccess) return e;
     if ((e = hipMemsetAsync(nodes32, 0, 64, s)) != hipSuccess) return e;   // root + the unused node 1
     const uint32_t bs = 256, nb = (n + bs - 1) / bs;
-    hipLaunchKernelGGL(k_tri_boxes, dim3(nb < 2048u ? nb : 2048u), dim3(bs), 0, s, verts, n, sc.triMin, sc.triMax, sc.bounds);
+    if (verts.general()) hipLaunchKernelGGL(k_tri_boxes<true>, dim3(nb < 2048u ? nb : 2048u), dim3(bs), 0, s, verts, n, sc.triMin, sc.triMax, sc.bounds);
+    else hipLaunchKernelGGL(k_tri_boxes<false>, dim3(nb < 2048u ? nb : 2048u), dim3(bs), 0, s, verts, n, sc.triMin, sc.triMax, sc.bounds);
     hipLaunchKernelGGL(k_tri_morton, dim3(nb), dim3(bs), 0, s, sc.triMin, sc.triMax, sc.bounds, n, sc.keysA, sc.valsA);
     size_t tmp = sortTempBytes;
     if ((e = hipcub::DeviceRadixSort::SortPairs(sc.sortTemp, tmp, sc.keysA, sc.keysB, sc.valsA, primIdx, (int)n, 0, 63, s)) != hipSuccess) return e;
@@ -373,14 +379,15 @@ size_t ploc_scratch_bytes(uint32_t n, size_t* sortTempBytes, size_t* scanTempByt
 
 // PLOC build (see above).  Out as launch_lbvh_build: nodes32 (2n BVHNode records, [1] unused), primIdx (the triangles in Morton order); one
 // triangle per leaf.  radius: search window to each side (8, 16 or 32).  steps (optional): number of clustering steps taken.
-hipError_t launch_ploc_build(const float4* verts, uint32_t n, uint32_t radius, float4* nodes32, uint32_t* primIdx, void* scratch, size_t sortTempBytes,
+hipError_t launch_ploc_build(const MeshSrc& verts, uint32_t n, uint32_t radius, float4* nodes32, uint32_t* primIdx, void* scratch, size_t sortTempBytes,
                              size_t scanTempBytes, hipStream_t s, uint32_t* steps) {
     const PlocScratch sc = carve_ploc(scratch, n, sortTempBytes, scanTempBytes);
     hipError_t e;
     if ((e = hipMemsetAsync(sc.bounds, 0xff, 12, s)) != hipSuccess) return e;
     if ((e = hipMemsetAsync(sc.bounds + 3, 0x00, 12, s)) != hipSuccess) return e;
     const uint32_t bs = 256, nb = (n + bs - 1) / bs;
-    hipLaunchKernelGGL(k_tri_boxes, dim3(nb < 2048u ? nb : 2048u), dim3(bs), 0, s, verts, n, sc.triMin, sc.triMax, sc.bounds);
+    if (verts.general()) hipLaunchKernelGGL(k_tri_boxes<true>, dim3(nb < 2048u ? nb : 2048u), dim3(bs), 0, s, verts, n, sc.triMin, sc.triMax, sc.bounds);
+    else hipLaunchKernelGGL(k_tri_boxes<false>, dim3(nb < 2048u ? nb : 2048u), dim3(bs), 0, s, verts, n, sc.triMin, sc.triMax, sc.bounds);
     hipLaunchKernelGGL(k_tri_morton, dim3(nb), dim3(bs), 0, s, sc.triMin, sc.triMax, sc.bounds, n, sc.keysA, sc.valsA);
     size_t tmp = sortTempBytes;
     if ((e = hipcub::DeviceRadixSort::SortPairs(sc.sortTemp, tmp, sc.keysA, sc.keysB, sc.valsA, primIdx, (int)n, 0, 63, s)) != hipSuccess) return e;

@@ -20,6 +20,7 @@
 #include "cwbvh_encode.h"
 #include "bvh4_encode.h"
 #include "device_common.h"
+#include "mesh_source.h"
 #include "kernels.h"
 
 namespace tbvh {
@@ -39,12 +40,15 @@ __device__ __forceinline__ float half_area(const N2& n) {
 }
 
 // counters: [0] wide nodes allocated, [1] triangles allocated, [2] work items written for the next level
+template <bool GENERAL>
 __global__ void k_convert_level(const float4* __restrict__ nodes2, uint32_t nNodes2, const uint32_t* __restrict__ primIdx, uint64_t nIdx,
-                                const float4* __restrict__ verts, uint64_t nTris, const uint2* __restrict__ itemsIn, uint32_t nIn,
+                                const MeshSrc mesh, const uint2* __restrict__ itemsIn, uint32_t nIn,
                                 uint2* __restrict__ itemsOut, uint32_t* __restrict__ counters, float4* __restrict__ cwNodes, uint32_t capNodes,
                                 float4* __restrict__ cwTris, uint64_t capTris, uint32_t* __restrict__ status) {
     const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= nIn) return;
+    const float4* __restrict__ verts = mesh.verts;   // (record mode reads finished records through it; triangles go through mesh_tri)
+    const uint64_t nTris = mesh.nTris;
     const uint2 item = itemsIn[t];   // x = BVH2 node, y = wide node index
     const N2 self = load_n2(nodes2, item.x);
     uint32_t kids[8];
@@ -116,7 +120,8 @@ __global__ void k_convert_level(const float4* __restrict__ nodes2, uint32_t nNod
                 }
                 const uint32_t prim = pi < nIdx ? primIdx[pi] : 0xffffffffu;
                 if (prim >= nTris) { atomicOr(status, 4u); continue; }
-                const float4 v0 = verts[3 * (uint64_t)prim], v1 = verts[3 * (uint64_t)prim + 1], v2 = verts[3 * (uint64_t)prim + 2];
+                float4 v0, v1, v2;
+                if (!mesh_tri<GENERAL>(mesh, prim, v0, v1, v2)) { atomicOr(status, kStatusMeshIndex); continue; }
                 float4* o = cwTris + 3 * (uint64_t)(triFirst + tris + j);
                 o[0] = make_float4(v2.x - v0.x, v2.y - v0.y, v2.z - v0.z, v2.w - v0.w);
                 o[1] = make_float4(v1.x - v0.x, v1.y - v0.y, v1.z - v0.z, v1.w - v0.w);
@@ -145,12 +150,15 @@ __global__ void k_convert_level(const float4* __restrict__ nodes2, uint32_t nNod
 // one level later (the host encoder does the same with its patchWord).
 // counters: [0] blocks allocated, [2] work items for the next level.  items: x = BVH2 node, y = u32 index (into the
 // stream viewed as words) of the childInfo word to patch, 0xffffffff for the root.
+template <bool GENERAL>
 __global__ void k_convert4_level(const float4* __restrict__ nodes2, uint32_t nNodes2, const uint32_t* __restrict__ primIdx, uint64_t nIdx,
-                                 const float4* __restrict__ verts, uint64_t nTris, const uint2* __restrict__ itemsIn, uint32_t nIn,
+                                 const MeshSrc mesh, const uint2* __restrict__ itemsIn, uint32_t nIn,
                                  uint2* __restrict__ itemsOut, uint32_t* __restrict__ counters, float4* __restrict__ blocks, uint64_t capBlocks,
                                  uint32_t* __restrict__ status) {
     const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= nIn) return;
+    const float4* __restrict__ verts = mesh.verts;   // (record mode reads finished records through it; triangles go through mesh_tri)
+    const uint64_t nTris = mesh.nTris;
     const uint2 item = itemsIn[t];
     const N2 self = load_n2(nodes2, item.x);
     uint32_t kids[4];
@@ -203,7 +211,8 @@ __global__ void k_convert4_level(const float4* __restrict__ nodes2, uint32_t nNo
                 }
                 const uint32_t prim = pi < nIdx ? primIdx[pi] : 0xffffffffu;
                 if (prim >= nTris) { atomicOr(status, 4u); o[0] = o[1] = o[2] = make_float4(0, 0, 0, 0); continue; }
-                const float4 v0 = verts[3 * (uint64_t)prim], v1 = verts[3 * (uint64_t)prim + 1], v2 = verts[3 * (uint64_t)prim + 2];
+                float4 v0, v1, v2;
+                if (!mesh_tri<GENERAL>(mesh, prim, v0, v1, v2)) { atomicOr(status, kStatusMeshIndex); o[0] = o[1] = o[2] = make_float4(0, 0, 0, 0); continue; }
                 o[0] = make_float4(v0.x, v0.y, v0.z, as_f32(prim));
                 o[1] = make_float4(v1.x - v0.x, v1.y - v0.y, v1.z - v0.z, v1.w - v0.w);
                 o[2] = make_float4(v2.x - v0.x, v2.y - v0.y, v2.z - v0.z, v2.w - v0.w);
@@ -221,7 +230,7 @@ __global__ void k_convert4_level(const float4* __restrict__ nodes2, uint32_t nNo
 
 // itemsA/itemsB: two work-item arrays of capNodes entries; counters: 4 x u32 in device memory.
 // Runs level by level until no interior child is left; returns the node and triangle counts.
-hipError_t run_convert_cwbvh(const float4* nodes2, uint32_t nNodes2, const uint32_t* primIdx, uint64_t nIdx, const float4* verts, uint64_t nTris,
+hipError_t run_convert_cwbvh(const float4* nodes2, uint32_t nNodes2, const uint32_t* primIdx, uint64_t nIdx, const MeshSrc& verts,
                              float4* cwNodes, uint32_t capNodes, float4* cwTris, uint64_t capTris, uint2* itemsA, uint2* itemsB, uint32_t* counters,
                              uint32_t* status, hipStream_t s, uint32_t* nNodesOut, uint64_t* nTrisOut, uint32_t* levelsOut) {
     const uint32_t init[4] = {1u, 0u, 0u, 0u};   // wide node 0 = root
@@ -233,8 +242,10 @@ hipError_t run_convert_cwbvh(const float4* nodes2, uint32_t nNodes2, const uint3
     uint2 *in = itemsA, *out = itemsB;
     while (nIn) {
         if ((e = hipMemsetAsync(counters + 2, 0, 4, s)) != hipSuccess) return e;
-        hipLaunchKernelGGL(k_convert_level, dim3((nIn + 63) / 64), dim3(64), 0, s, nodes2, nNodes2, primIdx, nIdx, verts, nTris, in, nIn, out, counters,
-                           cwNodes, capNodes, cwTris, capTris, status);
+        if (verts.general()) hipLaunchKernelGGL(k_convert_level<true>, dim3((nIn + 63) / 64), dim3(64), 0, s, nodes2, nNodes2, primIdx, nIdx, verts, in, nIn, out, counters,
+                                                cwNodes, capNodes, cwTris, capTris, status);
+        else hipLaunchKernelGGL(k_convert_level<false>, dim3((nIn + 63) / 64), dim3(64), 0, s, nodes2, nNodes2, primIdx, nIdx, verts, in, nIn, out, counters,
+                                cwNodes, capNodes, cwTris, capTris, status);
         if ((e = hipGetLastError()) != hipSuccess) return e;
         uint32_t c[3];
         if ((e = hipMemcpyAsync(c, counters, 12, hipMemcpyDeviceToHost, s)) != hipSuccess) return e;
@@ -252,7 +263,7 @@ hipError_t run_convert_cwbvh(const float4* nodes2, uint32_t nNodes2, const uint3
 
 namespace tbvh {
 // BVH4_GPU: same driver loop, one stream.  Returns the number of 16-byte blocks.
-hipError_t run_convert_bvh4(const float4* nodes2, uint32_t nNodes2, const uint32_t* primIdx, uint64_t nIdx, const float4* verts, uint64_t nTris,
+hipError_t run_convert_bvh4(const float4* nodes2, uint32_t nNodes2, const uint32_t* primIdx, uint64_t nIdx, const MeshSrc& verts,
                             float4* blocks, uint64_t capBlocks, uint2* itemsA, uint2* itemsB, uint32_t* counters, uint32_t* status, hipStream_t s,
                             uint64_t* nBlocksOut, uint32_t* levelsOut) {
     const uint32_t init[4] = {0u, 0u, 0u, 0u};
@@ -264,8 +275,10 @@ hipError_t run_convert_bvh4(const float4* nodes2, uint32_t nNodes2, const uint32
     uint2 *in = itemsA, *out = itemsB;
     while (nIn) {
         if ((e = hipMemsetAsync(counters + 2, 0, 4, s)) != hipSuccess) return e;
-        hipLaunchKernelGGL(k_convert4_level, dim3((nIn + 63) / 64), dim3(64), 0, s, nodes2, nNodes2, primIdx, nIdx, verts, nTris, in, nIn, out, counters,
-                           blocks, capBlocks, status);
+        if (verts.general()) hipLaunchKernelGGL(k_convert4_level<true>, dim3((nIn + 63) / 64), dim3(64), 0, s, nodes2, nNodes2, primIdx, nIdx, verts, in, nIn, out, counters,
+                                                blocks, capBlocks, status);
+        else hipLaunchKernelGGL(k_convert4_level<false>, dim3((nIn + 63) / 64), dim3(64), 0, s, nodes2, nNodes2, primIdx, nIdx, verts, in, nIn, out, counters,
+                                blocks, capBlocks, status);
         if ((e = hipGetLastError()) != hipSuccess) return e;
         uint32_t c[3];
         if ((e = hipMemcpyAsync(c, counters, 12, hipMemcpyDeviceToHost, s)) != hipSuccess) return e;

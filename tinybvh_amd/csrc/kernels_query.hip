@@ -342,26 +342,6 @@ __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(8, 8))) void
     bvh4_body<ANYHIT, LDS_N, REFILL_MIN, TRI_MIN, ADAPT, NODE_REPS, SIGNSEL, GOV_KEEP, HAS_OMM, TIMELINE, STEAL>(data, q, status);
 }
 
-// ---------------------------------------------------------------------------------------
-// upload helper: gather {v0|prim, e1, e2} per primIdx entry for the BVH_GPU layout.
-// e1 = v1 - v0, e2 = v2 - v0 are the same single IEEE subtractions IntersectTri performs
-// per test (tiny_bvh.h:8510-8511), so pre-computing them changes no result bit.
-// ---------------------------------------------------------------------------------------
-__global__ void k_gather_tris(const uint32_t* __restrict__ primIdx, const float4* __restrict__ verts,
-                              float4* __restrict__ out, uint64_t nIdx, uint64_t nTris) {
-    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= nIdx) return;
-    const uint32_t p = primIdx[i];
-    if (p >= nTris) {  // slack entries of SBVH primIdx arrays (idxCount = 1.5 * triCount)
-        out[i * 3] = make_float4(0, 0, 0, 0); out[i * 3 + 1] = make_float4(0, 0, 0, 0); out[i * 3 + 2] = make_float4(0, 0, 0, 0);
-        return;
-    }
-    const float4 a = verts[(uint64_t)p * 3], b = verts[(uint64_t)p * 3 + 1], c = verts[(uint64_t)p * 3 + 2];
-    out[i * 3] = make_float4(a.x, a.y, a.z, as_f32(p));
-    out[i * 3 + 1] = make_float4(b.x - a.x, b.y - a.y, b.z - a.z, 0.f);
-    out[i * 3 + 2] = make_float4(c.x - a.x, c.y - a.y, c.z - a.z, 0.f);
-}
-
 }  // namespace
 
 // ---- launchers (called from capi.hip) ----------------------------------------------------
@@ -408,11 +388,6 @@ void launch_bvh4(bool anyhit, int variant, const float4* data, const QueryArgs& 
     }
 #undef TBVH_L4
 #undef TBVH_L4W
-}
-
-void launch_gather_tris(const uint32_t* primIdx, const float4* verts, float4* out, uint64_t nIdx, uint64_t nTris, hipStream_t s) {
-    const uint32_t bs = 256;
-    hipLaunchKernelGGL(k_gather_tris, dim3((uint32_t)((nIdx + bs - 1) / bs)), dim3(bs), 0, s, primIdx, verts, out, nIdx, nTris);
 }
 
 }  // namespace tbvh

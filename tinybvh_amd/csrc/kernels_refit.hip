@@ -22,6 +22,7 @@
 //      Slot assignment, child order and triangle order are topology and stay.
 #include "device_common.h"
 #include "cwbvh_encode.h"
+#include "mesh_source.h"
 #include "kernels.h"
 
 #include <vector>
@@ -33,13 +34,14 @@ namespace {
 // ---- triangle records -----------------------------------------------------------------------
 
 // CWBVH: {e2, e1, v0|prim} per triangle (tiny_bvh.h:6004-6008); BVH_GPU gathered form: {v0|prim, e1, e2}.
-template <bool CWBVH_ORDER>
-__global__ void k_regather(float4* __restrict__ tris, const float4* __restrict__ verts, uint64_t nRecords, uint64_t nTris, uint32_t* __restrict__ status) {
+template <bool CWBVH_ORDER, bool GENERAL>
+__global__ void k_regather(float4* __restrict__ tris, const MeshSrc verts, uint64_t nRecords, uint32_t* __restrict__ status) {
     const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= nRecords) return;
     const uint32_t prim = as_u32(tris[3 * t + (CWBVH_ORDER ? 2 : 0)].w);
-    if (prim >= nTris) { atomicOr(status, 2u); return; }
-    const float4 v0 = verts[3 * (uint64_t)prim], v1 = verts[3 * (uint64_t)prim + 1], v2 = verts[3 * (uint64_t)prim + 2];
+    if (prim >= verts.nTris) { atomicOr(status, 2u); return; }
+    float4 v0, v1, v2;
+    if (!mesh_tri<GENERAL>(verts, prim, v0, v1, v2)) { atomicOr(status, kStatusMeshIndex); return; }
     const float4 e1 = make_float4(v1.x - v0.x, v1.y - v0.y, v1.z - v0.z, v1.w - v0.w);
     const float4 e2 = make_float4(v2.x - v0.x, v2.y - v0.y, v2.z - v0.z, v2.w - v0.w);
     const float4 a = make_float4(v0.x, v0.y, v0.z, as_f32(prim));
@@ -47,10 +49,15 @@ __global__ void k_regather(float4* __restrict__ tris, const float4* __restrict__
     else { tris[3 * t] = a; tris[3 * t + 1] = e1; tris[3 * t + 2] = e2; }
 }
 
-__device__ __forceinline__ void grow_prim(const float4* __restrict__ verts, uint32_t prim, float3& mn, float3& mx) {
+// (GENERAL: a prim beyond the mesh or a vertex index beyond the vertices is never dereferenced — the triangle counts as a point at the origin, so every
+// box stays finite; k_regather, which reads the same records, reports both)
+template <bool GENERAL>
+__device__ __forceinline__ void grow_prim(const MeshSrc& verts, uint32_t prim, float3& mn, float3& mx) {
+    float4 v[3];
+    if (!GENERAL) mesh_tri<false>(verts, prim, v[0], v[1], v[2]);
+    else if (prim >= verts.nTris || !mesh_tri<true>(verts, prim, v[0], v[1], v[2])) v[0] = v[1] = v[2] = make_float4(0.f, 0.f, 0.f, 0.f);
     for (int k = 0; k < 3; k++) {
-        const float4 v = verts[3 * (uint64_t)prim + k];
-        const float3 p = make_float3(v.x, v.y, v.z);
+        const float3 p = make_float3(v[k].x, v[k].y, v[k].z);
         mn = min3(mn, p); mx = max3(mx, p);
     }
 }
@@ -62,7 +69,8 @@ __device__ __forceinline__ void grow_prim(const float4* __restrict__ verts, uint
 // Box of child c of an interior node; false when c is an interior node that was not finished before this pass.
 // Leaves are marked done = 1 by the first pass (pass 2), so later passes can tell "unfinished interior node"
 // from the done word alone, without touching the child's record.
-__device__ __forceinline__ bool al_child_box(const float4* __restrict__ nodes, uint32_t nNodes, const float4* __restrict__ tris, const float4* __restrict__ verts,
+template <bool GENERAL>
+__device__ __forceinline__ bool al_child_box(const float4* __restrict__ nodes, uint32_t nNodes, const float4* __restrict__ tris, const MeshSrc& verts,
                                              const uint32_t* __restrict__ done, uint32_t pass, uint32_t c, float3& mn, float3& mx) {
     mn = make_float3(1e30f, 1e30f, 1e30f); mx = make_float3(-1e30f, -1e30f, -1e30f);
     if (c >= nNodes) return true;   // malformed: leave an empty box
@@ -72,7 +80,7 @@ __device__ __forceinline__ bool al_child_box(const float4* __restrict__ nodes, u
     const uint32_t cnt = as_u32(c2.w);
     if (cnt) {
         const uint32_t first = as_u32(c3.w);
-        for (uint32_t k = 0; k < cnt; k++) grow_prim(verts, as_u32(tris[3 * (uint64_t)(first + k)].w), mn, mx);
+        for (uint32_t k = 0; k < cnt; k++) grow_prim<GENERAL>(verts, as_u32(tris[3 * (uint64_t)(first + k)].w), mn, mx);
         return true;
     }
     if (d == 0u) return false;      // first pass: an interior child cannot be finished yet
@@ -82,7 +90,8 @@ __device__ __forceinline__ bool al_child_box(const float4* __restrict__ nodes, u
     return true;
 }
 
-__global__ void k_al_pass(float4* __restrict__ nodes, uint32_t nNodes, const float4* __restrict__ tris, const float4* __restrict__ verts,
+template <bool GENERAL>
+__global__ void k_al_pass(float4* __restrict__ nodes, uint32_t nNodes, const float4* __restrict__ tris, const MeshSrc verts,
                           uint32_t* __restrict__ done, uint32_t pass) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= nNodes || done[i]) return;
@@ -91,8 +100,8 @@ __global__ void k_al_pass(float4* __restrict__ nodes, uint32_t nNodes, const flo
     const uint32_t left = as_u32(w[3]), right = as_u32(w[7]), cnt = as_u32(w[11]);   // the .w of the first three float4
     if (cnt) { done[i] = 1u; return; }   // leaf: nothing stored in it depends on the vertices
     float3 lmn, lmx, rmn, rmx;
-    if (!al_child_box(nodes, nNodes, tris, verts, done, pass, left, lmn, lmx)) return;
-    if (!al_child_box(nodes, nNodes, tris, verts, done, pass, right, rmn, rmx)) return;
+    if (!al_child_box<GENERAL>(nodes, nNodes, tris, verts, done, pass, left, lmn, lmx)) return;
+    if (!al_child_box<GENERAL>(nodes, nNodes, tris, verts, done, pass, right, rmn, rmx)) return;
     np[0] = make_float4(lmn.x, lmn.y, lmn.z, as_f32(left)); np[1] = make_float4(lmx.x, lmx.y, lmx.z, as_f32(right));
     np[2] = make_float4(rmn.x, rmn.y, rmn.z, as_f32(0u)); np[3] = make_float4(rmx.x, rmx.y, rmx.z, np[3].w);
     done[i] = pass;
@@ -102,7 +111,8 @@ __global__ void k_al_pass(float4* __restrict__ nodes, uint32_t nNodes, const flo
 
 // Re-encode node j from the boxes of its children (leaf children: from the vertices; interior children:
 // nodeBox[child], complete by the time this runs).  Returns the node's own box.
-__device__ void cw_encode(float4* __restrict__ np, uint32_t nNodes, const float4* __restrict__ tris, const float4* __restrict__ verts,
+template <bool GENERAL>
+__device__ void cw_encode(float4* __restrict__ np, uint32_t nNodes, const float4* __restrict__ tris, const MeshSrc& verts,
                           const float4* __restrict__ boxMin, const float4* __restrict__ boxMax, float3& outMn, float3& outMx) {
     const uint32_t ew = as_u32(np[0].w), imask = ew >> 24;
     const uint32_t childBase = as_u32(np[1].x), triBase = as_u32(np[1].y);
@@ -121,7 +131,7 @@ __device__ void cw_encode(float4* __restrict__ np, uint32_t nNodes, const float4
         } else {
             // triBase counts float4 blocks (3 per triangle: the kernel addresses triBase + 3 * triangle), meta bits 0-4 the triangle offset
             const uint32_t first = triBase / 3u + (meta & 31u), cnt = __popc(meta >> 5);
-            for (uint32_t k = 0; k < cnt; k++) grow_prim(verts, as_u32(tris[3 * (uint64_t)(first + k) + 2].w), a, b);
+            for (uint32_t k = 0; k < cnt; k++) grow_prim<GENERAL>(verts, as_u32(tris[3 * (uint64_t)(first + k) + 2].w), a, b);
         }
         cmn[s] = a; cmx[s] = b;
         mn = min3(mn, a); mx = max3(mx, b);
@@ -130,7 +140,8 @@ __device__ void cw_encode(float4* __restrict__ np, uint32_t nNodes, const float4
     cw_quantize_write(np, mn, mx, cmn, cmx, used, imask, childBase, triBase, m0, m1);
 }
 
-__global__ void k_cw_pass(float4* __restrict__ nodes, uint32_t nNodes, const float4* __restrict__ tris, const float4* __restrict__ verts,
+template <bool GENERAL>
+__global__ void k_cw_pass(float4* __restrict__ nodes, uint32_t nNodes, const float4* __restrict__ tris, const MeshSrc verts,
                           uint32_t* __restrict__ done, uint32_t pass, float4* __restrict__ boxMin, float4* __restrict__ boxMax) {
     const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
     if (j >= nNodes || done[j]) return;
@@ -143,7 +154,7 @@ __global__ void k_cw_pass(float4* __restrict__ nodes, uint32_t nNodes, const flo
         if (d == 0u || d >= pass) return;      // an interior child is not finished yet (or only in this pass)
     }
     float3 mn, mx;
-    cw_encode(nodes + (size_t)j * 5, nNodes, tris, verts, boxMin, boxMax, mn, mx);
+    cw_encode<GENERAL>(nodes + (size_t)j * 5, nNodes, tris, verts, boxMin, boxMax, mn, mx);
     boxMin[j] = make_float4(mn.x, mn.y, mn.z, 0.f); boxMax[j] = make_float4(mx.x, mx.y, mx.z, 0.f);
     done[j] = pass;
 }
@@ -172,7 +183,8 @@ __global__ void k_b4_collect(const float4* __restrict__ blocks, uint64_t nBlocks
     }
 }
 
-__global__ void k_b4_refit_level(float4* __restrict__ blocks, uint64_t nBlocks, const float4* __restrict__ verts, uint64_t nTris,
+template <bool GENERAL>
+__global__ void k_b4_refit_level(float4* __restrict__ blocks, uint64_t nBlocks, const MeshSrc verts,
                                  const B4Item* __restrict__ items, uint32_t first, uint32_t count, float4* __restrict__ childBox, uint32_t* __restrict__ status) {
     const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= count) return;
@@ -194,8 +206,9 @@ __global__ void k_b4_refit_level(float4* __restrict__ blocks, uint64_t nBlocks, 
                 float4* tr = nb + rel + 3 * j;
                 if ((uint64_t)it.offset + rel + 3 * j + 3 > nBlocks) break;
                 const uint32_t prim = as_u32(tr[0].w);
-                if (prim >= nTris) { atomicOr(status, 2u); continue; }
-                const float4 v0 = verts[3 * (uint64_t)prim], v1 = verts[3 * (uint64_t)prim + 1], v2 = verts[3 * (uint64_t)prim + 2];
+                if (prim >= verts.nTris) { atomicOr(status, 2u); continue; }
+                float4 v0, v1, v2;
+                if (!mesh_tri<GENERAL>(verts, prim, v0, v1, v2)) { atomicOr(status, kStatusMeshIndex); continue; }
                 tr[0] = make_float4(v0.x, v0.y, v0.z, as_f32(prim));
                 tr[1] = make_float4(v1.x - v0.x, v1.y - v0.y, v1.z - v0.z, v1.w - v0.w);
                 tr[2] = make_float4(v2.x - v0.x, v2.y - v0.y, v2.z - v0.z, v2.w - v0.w);
@@ -252,26 +265,33 @@ size_t refit_scratch_bytes(int layout, uint32_t nNodes) {
 }
 
 // scratch layout: done[nNodes] | boxMin[nNodes] | boxMax[nNodes]
-hipError_t launch_refit(int layout, float4* nodes, uint32_t nNodes, float4* tris, uint64_t nTriRecords, const float4* verts, uint64_t nTris,
+hipError_t launch_refit(int layout, float4* nodes, uint32_t nNodes, float4* tris, uint64_t nTriRecords, const MeshSrc& verts,
                         void* scratch, uint32_t* status, hipStream_t s) {
     uint32_t* done = (uint32_t*)scratch;
     float4* boxMin = (float4*)(((uintptr_t)(done + nNodes) + 255) & ~(uintptr_t)255);
     float4* boxMax = boxMin + nNodes;
     const uint32_t bs = 128, nb = (nNodes + bs - 1) / bs;
     const uint32_t tb = (uint32_t)((nTriRecords + 255) / 256);
+    const bool gen = verts.general();   // (decided per launch: the flat instances are the kernels as they were)
     hipError_t e = hipMemsetAsync(done, 0, (size_t)nNodes * 4, s);
     if (e != hipSuccess) return e;
     if (nTriRecords) {
-        if (layout == kLayoutCwbvh) hipLaunchKernelGGL(k_regather<true>, dim3(tb), dim3(256), 0, s, tris, verts, nTriRecords, nTris, status);
-        else hipLaunchKernelGGL(k_regather<false>, dim3(tb), dim3(256), 0, s, tris, verts, nTriRecords, nTris, status);
+        if (layout == kLayoutCwbvh) {
+            if (gen) hipLaunchKernelGGL((k_regather<true, true>), dim3(tb), dim3(256), 0, s, tris, verts, nTriRecords, status);
+            else hipLaunchKernelGGL((k_regather<true, false>), dim3(tb), dim3(256), 0, s, tris, verts, nTriRecords, status);
+        } else if (gen) hipLaunchKernelGGL((k_regather<false, true>), dim3(tb), dim3(256), 0, s, tris, verts, nTriRecords, status);
+        else hipLaunchKernelGGL((k_regather<false, false>), dim3(tb), dim3(256), 0, s, tris, verts, nTriRecords, status);
     }
     // passes in batches; after each batch look at the root's done word (pass numbers start at 2)
     const int batch = layout == kLayoutCwbvh ? 6 : 24;
     uint32_t pass = 2, rootDone = 0;
     while (!rootDone) {
         for (int k = 0; k < batch; k++, pass++) {
-            if (layout == kLayoutCwbvh) hipLaunchKernelGGL(k_cw_pass, dim3(nb), dim3(bs), 0, s, nodes, nNodes, tris, verts, done, pass, boxMin, boxMax);
-            else hipLaunchKernelGGL(k_al_pass, dim3(nb), dim3(bs), 0, s, nodes, nNodes, tris, verts, done, pass);
+            if (layout == kLayoutCwbvh) {
+                if (gen) hipLaunchKernelGGL(k_cw_pass<true>, dim3(nb), dim3(bs), 0, s, nodes, nNodes, tris, verts, done, pass, boxMin, boxMax);
+                else hipLaunchKernelGGL(k_cw_pass<false>, dim3(nb), dim3(bs), 0, s, nodes, nNodes, tris, verts, done, pass, boxMin, boxMax);
+            } else if (gen) hipLaunchKernelGGL(k_al_pass<true>, dim3(nb), dim3(bs), 0, s, nodes, nNodes, tris, verts, done, pass);
+            else hipLaunchKernelGGL(k_al_pass<false>, dim3(nb), dim3(bs), 0, s, nodes, nNodes, tris, verts, done, pass);
         }
         if ((e = hipMemcpyAsync(&rootDone, done, 4, hipMemcpyDeviceToHost, s)) != hipSuccess) return e;
         if ((e = hipStreamSynchronize(s)) != hipSuccess) return e;
@@ -286,7 +306,7 @@ namespace tbvh {
 
 // BVH4_GPU refit.  items: capacity capNodes; levelFirst: host array filled by the first call (node list per level, root
 // level first); childBox: capNodes * 8 float4.  Returns the number of nodes found (0 on the calls that reuse the lists).
-hipError_t run_refit_bvh4(float4* blocks, uint64_t nBlocks, const float4* verts, uint64_t nTris, void* itemsDev, uint32_t capNodes, uint32_t* counterDev,
+hipError_t run_refit_bvh4(float4* blocks, uint64_t nBlocks, const MeshSrc& verts, void* itemsDev, uint32_t capNodes, uint32_t* counterDev,
                           float4* childBox, std::vector<uint32_t>& levelFirst, uint32_t* status, hipStream_t s) {
     B4Item* items = (B4Item*)itemsDev;
     hipError_t e;
@@ -309,7 +329,8 @@ hipError_t run_refit_bvh4(float4* blocks, uint64_t nBlocks, const float4* verts,
     }
     for (size_t l = levelFirst.size() - 1; l-- > 0;) {
         const uint32_t first = levelFirst[l], count = levelFirst[l + 1] - first;
-        hipLaunchKernelGGL(k_b4_refit_level, dim3((count + 127) / 128), dim3(128), 0, s, blocks, nBlocks, verts, nTris, items, first, count, childBox, status);
+        if (verts.general()) hipLaunchKernelGGL(k_b4_refit_level<true>, dim3((count + 127) / 128), dim3(128), 0, s, blocks, nBlocks, verts, items, first, count, childBox, status);
+        else hipLaunchKernelGGL(k_b4_refit_level<false>, dim3((count + 127) / 128), dim3(128), 0, s, blocks, nBlocks, verts, items, first, count, childBox, status);
     }
     return hipGetLastError();
 }

@@ -21,6 +21,7 @@
 // count}; BVH_GPU entries are nodes whose leafness is known only once fetched, so they carry the leaf test's verdict instead: {node, 1}
 // when the box failed the distance test.  One iteration = at most one pop (node visit or leaf start) and one triangle test per lane.
 #include "device_common.h"
+#include "mesh_source.h"
 #include "cwbvh_node.h"
 #include "lane_stack.h"
 #include "ray_pool.h"
@@ -96,7 +97,7 @@ template <int LAYOUT> __device__ __forceinline__ uint32_t record_prim(const floa
     return as_u32(tris[(size_t)k * 3].w);
 }
 
-template <int LAYOUT>
+template <int LAYOUT, bool GENERAL>
 __global__ __launch_bounds__(WG) void k_spheres(const SphereArgs q, uint32_t* __restrict__ status) {
     __shared__ uint2 stk[kSphereLds][WG];
     Stack64 st;
@@ -105,7 +106,8 @@ __global__ __launch_bounds__(WG) void k_spheres(const SphereArgs q, uint32_t* __
     pool.init(q.poolParts, q.counterNext);
     const float4* __restrict__ nodes = q.nodes;
     const float4* __restrict__ tris = LAYOUT == kLayoutBvh4Gpu ? q.nodes : q.tris;
-    const float4* __restrict__ verts = q.verts;
+    const MeshSrc& verts = q.verts;   // the triangle test's vertices: mesh_source.h
+    const uint64_t nTris = q.verts.nTris;
 
     bool active = false;
     uint64_t si = 0;
@@ -113,7 +115,7 @@ __global__ __launch_bounds__(WG) void k_spheres(const SphereArgs q, uint32_t* __
     s.pos = s.bmin = s.bmax = make_float3(0.f, 0.f, 0.f);
     s.r = s.r2 = 0.f;
     uint32_t triPtr = 0, triLeft = 0;   // the current leaf's records still to test (BVH4_GPU / CWBVH: float4 address, step 3)
-    bool badPrim = false;
+    bool badPrim = false, badIndex = false;
 
     for (;;) {
         const uint32_t nIdle = (uint32_t)__popcll(__ballot(!active));
@@ -153,9 +155,11 @@ __global__ __launch_bounds__(WG) void k_spheres(const SphereArgs q, uint32_t* __
                             float3 mn = make_float3(kFar, kFar, kFar), mx = make_float3(-kFar, -kFar, -kFar);
                             for (uint32_t k = 0; k < cnt; k++) {
                                 const uint32_t prim = record_prim<LAYOUT>(tris, as_u32(n3.w) + k);
-                                if (prim >= q.nTris) { badPrim = true; continue; }
+                                if (prim >= nTris) { badPrim = true; continue; }
+                                float4 tv[3];
+                                if (!mesh_tri<GENERAL>(verts, prim, tv[0], tv[1], tv[2])) { badIndex = true; continue; }
                                 for (int j = 0; j < 3; j++) {
-                                    const float4 v = verts[(size_t)prim * 3 + j];
+                                    const float4 v = tv[j];
                                     mn = make_float3(fminf(mn.x, v.x), fminf(mn.y, v.y), fminf(mn.z, v.z));
                                     mx = make_float3(fmaxf(mx.x, v.x), fmaxf(mx.y, v.y), fmaxf(mx.z, v.z));
                                 }
@@ -220,9 +224,10 @@ __global__ __launch_bounds__(WG) void k_spheres(const SphereArgs q, uint32_t* __
         if (triLeft != 0 && !done) {
             const uint32_t prim = record_prim<LAYOUT>(tris, triPtr);
             triPtr += LAYOUT == kLayoutBvhGpu ? 1u : 3u; triLeft--;
-            if (prim >= q.nTris) badPrim = true;   // (a vertex array shorter than the blob: tbvh_intersect_spheres reports it)
+            float4 a, b, c;
+            if (prim >= nTris) badPrim = true;   // (a vertex array shorter than the blob: tbvh_intersect_spheres reports it)
+            else if (!mesh_tri<GENERAL>(verts, prim, a, b, c)) badIndex = true;   // (an index beyond the vertices: never dereferenced)
             else {
-                const float4 a = verts[(size_t)prim * 3], b = verts[(size_t)prim * 3 + 1], c = verts[(size_t)prim * 3 + 2];
                 if (tri_sphere(s, make_float3(a.x, a.y, a.z), make_float3(b.x, b.y, b.z), make_float3(c.x, c.y, c.z))) { found = true; done = true; }
             }
             if (!done && triLeft == 0 && st.empty()) done = true;
@@ -234,14 +239,21 @@ __global__ __launch_bounds__(WG) void k_spheres(const SphereArgs q, uint32_t* __
     }
     if (st.overflow) atomicOr(status, 1u);
     if (badPrim) atomicOr(status, 16u);
+    if (GENERAL && badIndex) atomicOr(status, kStatusMeshIndex);
 }
 
 }  // namespace
 
 void launch_spheres(int layout, const SphereArgs& q, uint32_t* status, uint32_t blocks, hipStream_t s) {
-    if (layout == kLayoutBvh4Gpu) hipLaunchKernelGGL(k_spheres<kLayoutBvh4Gpu>, dim3(blocks), dim3(WG), 0, s, q, status);
-    else if (layout == kLayoutCwbvh) hipLaunchKernelGGL(k_spheres<kLayoutCwbvh>, dim3(blocks), dim3(WG), 0, s, q, status);
-    else hipLaunchKernelGGL(k_spheres<kLayoutBvhGpu>, dim3(blocks), dim3(WG), 0, s, q, status);
+#define TBVH_LS(L)                                                                                                    \
+    do {                                                                                                              \
+        if (q.verts.general()) hipLaunchKernelGGL((k_spheres<L, true>), dim3(blocks), dim3(WG), 0, s, q, status);     \
+        else hipLaunchKernelGGL((k_spheres<L, false>), dim3(blocks), dim3(WG), 0, s, q, status);                      \
+    } while (0)
+    if (layout == kLayoutBvh4Gpu) TBVH_LS(kLayoutBvh4Gpu);
+    else if (layout == kLayoutCwbvh) TBVH_LS(kLayoutCwbvh);
+    else TBVH_LS(kLayoutBvhGpu);
+#undef TBVH_LS
 }
 
 }  // namespace tbvh

@@ -263,6 +263,16 @@ def soup(n_tris: int, seed: int = 7, extent: float = 10.0, size: float = 0.6) ->
     return _pack([np.stack([p, p + d1, p + d2], 1)])
 
 
+def weld(verts: np.ndarray):
+    """The inverse of flattening: (positions, indices) of a flat (3 n, 4) vertex array, one position per distinct bit pattern of the 16
+    bytes (exact: nothing is merged by distance), indices (n, 3) uint32 with positions[indices].reshape(-1, 4) == verts bit for bit."""
+    v = np.ascontiguousarray(verts, np.float32).reshape(-1, 4)
+    assert v.shape[0] % 3 == 0
+    keys = v.view(np.uint32)
+    uniq, inv = np.unique(keys, axis=0, return_inverse=True)
+    return np.ascontiguousarray(uniq).view(np.float32), np.ascontiguousarray(inv.reshape(-1, 3).astype(np.uint32))
+
+
 def get(name: str):
     """Returns (verts, label).  Real files win when present."""
     real = {"sponza": "cryteksponza.bin", "dragon": "dragon.bin"}
