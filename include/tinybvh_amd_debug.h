@@ -45,7 +45,7 @@ int tbvh_set_variant(tbvh_scene* scene, int variant);
 
 /* The BVH2 (tinybvh::BVH::BVHNode layout, 32 bytes per node, leaves of at most max_leaf_tris entries) the library derives on the HOST from an uploaded
  * BVH_GPU blob (layout 5: nodes64 + prim_idx + verts16) or BVH4_GPU stream (layout 8: blocks16 in `blob`, n_blob 16-byte blocks; prim_idx / verts16 unused)
- * before it collapses it into the scene's 8-wide copy (tinybvh_amd/csrc/capi_scene.hip: makeWideCopy).  No device involved: the tests walk the result
+ * before it collapses it into the scene's 8-wide copy (tinybvh_amd/csrc/capi_scene.hip: makeCopy).  No device involved: the tests walk the result
  * with the oracle.  Layout 5 with prim_idx == NULL = RECORD MODE, the form the library runs (the blob is read back from the device, where the triangles
  * live as gathered records): verts16 then holds n_idx records {v0|prim, e1 = v1 - v0, e2 = v2 - v0} of 48 bytes.  nodes32_out: cap_nodes x 32 bytes; recs_out (layout 8 only): the stream's triangle records {v0|prim, e1, e2} in the order the leaves
  * index them, cap_recs x 48 bytes.  Counts are returned also when a capacity is too small (TBVH_E_INVALID then): call twice.  TBVH_E_FORMAT: the root is
@@ -53,6 +53,12 @@ int tbvh_set_variant(tbvh_scene* scene, int variant);
 int tbvh_debug_wide_copy_bvh2(int layout, const void* blob, uint64_t n_blob, const uint32_t* prim_idx, uint64_t n_idx, const void* verts16, uint64_t n_tris,
                               uint32_t max_leaf_tris, void* nodes32_out, uint64_t cap_nodes, uint64_t* n_nodes_out, void* recs_out, uint64_t cap_recs,
                               uint64_t* n_recs_out);
+
+/* Device memory the library itself owns right now, over every context of this process: out[0] = live allocations, out[1] = their bytes.  Scenes (their
+ * derived copies, staging and scratch areas included), contexts and wavefront objects are counted; memory handed to the caller (tbvh_device_malloc,
+ * tbvh_pinned_malloc) and the library's pinned host buffers are not.  Both return to their earlier values once everything created since was freed:
+ * what tests/test_device_memory.py asserts.  Needs no device and no context. */
+int tbvh_debug_device_allocations(uint64_t out[2]);
 
 #ifdef __cplusplus
 }

@@ -92,11 +92,11 @@ int tbvh_init(int device, tbvh_context** out) {
         if (v >= 2 && v <= 232) c->spillEntries = (uint32_t)v & ~1u;
     }
     const size_t spillBytes = (size_t)(c->blocks + c->blocks / 3u) * 64 * c->spillEntries * 4;   // the largest grid any launch uses
-    e = hipMalloc((void**)&c->spill, spillBytes);
-    if (e == hipSuccess) e = hipMalloc((void**)&c->counter, 256);
-    if (e == hipSuccess) e = hipMalloc((void**)&c->pool, (size_t)(kPoolParts + 1) * kPoolCounterStride * 4 * 2);
+    e = c->spill.alloc(spillBytes / 4);
+    if (e == hipSuccess) e = c->counter.alloc(32);
+    if (e == hipSuccess) e = c->pool.alloc((size_t)(kPoolParts + 1) * kPoolCounterStride * 2);
     if (e != hipSuccess) { tbvh_shutdown(c); return fail(TBVH_E_NOMEM, "device allocation failed: %s", hipGetErrorString(e)); }
-    c->status = (uint32_t*)(c->counter + 4);
+    c->status = (uint32_t*)(c->counter.get() + 4);
     hipMemset(c->counter, 0, 256);
     *out = c;
     return 0;
@@ -113,18 +113,18 @@ void tbvh_shutdown(tbvh_context* c) {
         tbvh_free_scene(t);
     }
     while (!c->scenes.empty()) tbvh_free_scene(c->scenes.back());
-    if (c->spill) hipFree(c->spill);
-    if (c->counter) hipFree(c->counter);
-    if (c->pool) hipFree(c->pool);
     for (const tbvh_context::PinnedRange& r : c->pinned) hipHostFree(r.host);   // (memory of tbvh_pinned_malloc the caller never gave back goes with the context)
     c->pinned.clear();
-    if (c->stageRays) hipFree(c->stageRays);
-    if (c->stageOcc) hipFree(c->stageOcc);
-    if (c->binScratch) hipFree(c->binScratch);
     delete c->pipe;
     for (auto& pair : c->evRing) for (hipEvent_t ev : pair) if (ev) hipEventDestroy(ev);
     if (c->ownStream) hipStreamDestroy(c->ownStream);
-    delete c;
+    delete c;   // (its device buffers go here: the device is current, its stream was idle)
+}
+
+int tbvh_debug_device_allocations(uint64_t out[2]) {
+    if (!out) return fail(TBVH_E_INVALID, "tbvh_debug_device_allocations: null argument");
+    out[0] = g_devBufLive.load(); out[1] = g_devBufBytes.load();
+    return 0;
 }
 
 int tbvh_synchronize(tbvh_context* c) {
@@ -266,13 +266,12 @@ static int timeBest(tbvh_context* c, uint32_t reps, const std::function<void()>&
 int tbvh_measure_copy_bandwidth(tbvh_context* c, uint64_t bytes, uint32_t reps, double* gbps) {
     if (!c || !gbps || bytes < (1u << 20)) return fail(TBVH_E_INVALID, "tbvh_measure_copy_bandwidth: null argument or under 1 MB");
     TBVH_ENTER(c);
-    void *a = nullptr, *b = nullptr;
-    if (hipMalloc(&a, bytes) != hipSuccess || hipMalloc(&b, bytes) != hipSuccess) { if (a) hipFree(a); return fail(TBVH_E_NOMEM, "tbvh_measure_copy_bandwidth: cannot allocate 2 x %llu bytes", (unsigned long long)bytes); }
+    DevBuf<void> a, b;
+    if (a.alloc(bytes) != hipSuccess || b.alloc(bytes) != hipSuccess) return fail(TBVH_E_NOMEM, "tbvh_measure_copy_bandwidth: cannot allocate 2 x %llu bytes", (unsigned long long)bytes);
     int r = 0;
     if (hipMemsetAsync(a, 1, bytes, c->stream) != hipSuccess) r = fail(TBVH_E_HIP, "hipMemsetAsync failed");
     double ms = 0;
-    if (!r) r = timeBest(c, reps ? reps : 3, [&] { launch_stream_copy((const float4*)a, (float4*)b, bytes / 16, c->stream); }, &ms);
-    hipFree(a); hipFree(b);
+    if (!r) r = timeBest(c, reps ? reps : 3, [&] { launch_stream_copy((const float4*)a.get(), (float4*)b.get(), bytes / 16, c->stream); }, &ms);
     if (r) return r;
     *gbps = 2.0 * (double)bytes / (ms * 1e-3) / 1e9;
     return 0;
@@ -281,13 +280,13 @@ int tbvh_measure_copy_bandwidth(tbvh_context* c, uint64_t bytes, uint32_t reps, 
 int tbvh_measure_read_bandwidth(tbvh_context* c, uint64_t bytes, uint32_t reps, double* gbps) {
     if (!c || !gbps || bytes < (1u << 20)) return fail(TBVH_E_INVALID, "tbvh_measure_read_bandwidth: null argument or under 1 MB");
     TBVH_ENTER(c);
-    void *a = nullptr, *sink = nullptr;
-    if (hipMalloc(&a, bytes) != hipSuccess || hipMalloc(&sink, 256) != hipSuccess) { if (a) hipFree(a); return fail(TBVH_E_NOMEM, "tbvh_measure_read_bandwidth: cannot allocate %llu bytes", (unsigned long long)bytes); }
+    DevBuf<void> a;
+    DevBuf<float> sink;
+    if (a.alloc(bytes) != hipSuccess || sink.alloc(64) != hipSuccess) return fail(TBVH_E_NOMEM, "tbvh_measure_read_bandwidth: cannot allocate %llu bytes", (unsigned long long)bytes);
     int r = 0;
     if (hipMemsetAsync(a, 1, bytes, c->stream) != hipSuccess) r = fail(TBVH_E_HIP, "hipMemsetAsync failed");
     double ms = 0;
-    if (!r) r = timeBest(c, reps ? reps : 3, [&] { launch_stream_read((const float4*)a, (float*)sink, bytes / 16, (uint32_t)c->numCUs * 32u, c->stream); }, &ms);
-    hipFree(a); hipFree(sink);
+    if (!r) r = timeBest(c, reps ? reps : 3, [&] { launch_stream_read((const float4*)a.get(), sink, bytes / 16, (uint32_t)c->numCUs * 32u, c->stream); }, &ms);
     if (r) return r;
     *gbps = (double)bytes / (ms * 1e-3) / 1e9;
     return 0;
@@ -298,14 +297,15 @@ int tbvh_measure_read_bandwidth(tbvh_context* c, uint64_t bytes, uint32_t reps, 
 int tbvh_measure_link_bandwidth(tbvh_context* c, uint64_t bytes, uint32_t reps, double* h2d_gbps, double* d2h_gbps) {
     if (!c || !h2d_gbps || !d2h_gbps || bytes < (1u << 20)) return fail(TBVH_E_INVALID, "tbvh_measure_link_bandwidth: null argument or under 1 MB");
     TBVH_ENTER(c);
-    void *h = nullptr, *d = nullptr;
+    void* h = nullptr;
+    DevBuf<void> d;
     if (hipHostMalloc(&h, bytes, hipHostMallocDefault) != hipSuccess) return fail(TBVH_E_NOMEM, "tbvh_measure_link_bandwidth: cannot pin %llu bytes", (unsigned long long)bytes);
-    if (hipMalloc(&d, bytes) != hipSuccess) { hipHostFree(h); return fail(TBVH_E_NOMEM, "tbvh_measure_link_bandwidth: cannot allocate %llu device bytes", (unsigned long long)bytes); }
+    if (d.alloc(bytes) != hipSuccess) { hipHostFree(h); return fail(TBVH_E_NOMEM, "tbvh_measure_link_bandwidth: cannot allocate %llu device bytes", (unsigned long long)bytes); }
     memset(h, 1, bytes);
     double up = 0, down = 0;
     int r = timeBest(c, reps ? reps : 3, [&] { (void)hipMemcpyAsync(d, h, bytes, hipMemcpyHostToDevice, c->stream); }, &up);
     if (!r) r = timeBest(c, reps ? reps : 3, [&] { (void)hipMemcpyAsync(h, d, bytes, hipMemcpyDeviceToHost, c->stream); }, &down);
-    hipFree(d); hipHostFree(h);
+    hipHostFree(h);
     if (r) return r;
     *h2d_gbps = (double)bytes / (up * 1e-3) / 1e9; *d2h_gbps = (double)bytes / (down * 1e-3) / 1e9;
     return 0;
@@ -318,11 +318,10 @@ int tbvh_measure_valu_issue(tbvh_context* c, uint32_t reps, double* ginstr_per_s
     TBVH_ENTER(c);
     const uint32_t blocks = (uint32_t)c->numCUs * 32u;
     const int iters = 20000;
-    void* out = nullptr;
-    if (hipMalloc(&out, (size_t)blocks * 64 * 4) != hipSuccess) return fail(TBVH_E_NOMEM, "tbvh_measure_valu_issue: out of device memory");
+    DevBuf<float> out;
+    if (out.alloc((size_t)blocks * 64) != hipSuccess) return fail(TBVH_E_NOMEM, "tbvh_measure_valu_issue: out of device memory");
     double ms = 0;
-    const int r = timeBest(c, reps ? reps : 3, [&] { launch_valu_mix((float*)out, iters, blocks, c->stream); }, &ms);
-    hipFree(out);
+    const int r = timeBest(c, reps ? reps : 3, [&] { launch_valu_mix(out, iters, blocks, c->stream); }, &ms);
     if (r) return r;
     *ginstr_per_s = (double)blocks * iters * 32.0 / (ms * 1e-3) / 1e9;
     return 0;

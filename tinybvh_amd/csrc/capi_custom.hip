@@ -32,7 +32,7 @@ int tbvh_upload_custom_spheres(tbvh_context* c, const void* nodes32, uint64_t nN
     TBVH_ENTER(c);
     tbvh_scene* s = newScene(c, TBVH_LAYOUT_BVH2_WALD);
     if (!s) return fail(TBVH_E_NOMEM, "out of host memory");
-    if (hipMalloc((void**)&s->nodes, nNodes * 32) != hipSuccess || hipMalloc((void**)&s->tris, nIdx * 32) != hipSuccess) {
+    if (s->nodes.alloc(nNodes * 2) != hipSuccess || s->tris.alloc(nIdx * 2) != hipSuccess) {
         tbvh_free_scene(s);
         return fail(TBVH_E_NOMEM, "tbvh_upload_custom_spheres: out of device memory");
     }

@@ -1,8 +1,8 @@
 // capi_double.hip — BVH_Double scenes (tiny_bvh.h:1035-1090): upload with validation, the _ex queries over RayEx records, and the host
 // builders behind tbvh_host_build_double / tbvh_host_build_tlas_double.  The kernels are kernels_double.hip.
-// A BVH_DOUBLE scene keeps its device memory in the fields every scene has (capi_scene.hip: tbvh_free_scene frees them): a BLAS its nodes in
+// A BVH_DOUBLE scene keeps its device memory in the fields every scene has (they go with the scene: tbvh_free_scene): a BLAS its nodes in
 // `nodes` and its gathered triangle records in `tris`; a TLAS ONE allocation in `nodes` = [TLAS nodes | instance indices | instances | BLAS
-// descriptors], each part 16-byte aligned.  Nothing else of the fp32 machinery (copies, tuners, refit, updates) applies to it: the entry
+// descriptors], each part 16-byte aligned.  Those buffers count 16-byte blocks: a NodeDbl is 4 of them, a TriDbl 5.  Nothing else of the fp32 machinery (copies, tuners, refit, updates) applies to it: the entry
 // points of those refuse a BVH_DOUBLE scene.
 #include "capi_internal.h"
 
@@ -14,6 +14,9 @@ namespace {
 constexpr double kDblFarHost = 1e300;   // BVH_DBL_FAR, tiny_bvh.h:145
 
 uint64_t align16(uint64_t b) { return (b + 15) & ~15ull; }
+
+// a scene's `nodes` / `tris` buffers count 16-byte blocks: every fp64 record is a whole number of them
+static_assert(sizeof(NodeDbl) % 16 == 0 && sizeof(TriDbl) % 16 == 0 && sizeof(InstanceDbl) % 16 == 0 && sizeof(BlasDbl) % 16 == 0, "fp64 records are multiples of 16 bytes");
 
 // The checks of a caller's blob, before anything is allocated.  msg receives the first bad entry; returns TBVH_E_FORMAT or 0.
 int validateDouble(const NodeDbl* n, uint64_t nNodes, const uint64_t* idx, uint64_t nIdx, uint64_t nPrims, const char* who, const char* primWhat) {
@@ -53,7 +56,7 @@ bool isDouble(const tbvh_scene* s) { return s->layout == TBVH_LAYOUT_BVH_DOUBLE;
 // TLAS parts inside its one allocation
 struct TlasParts { const uint64_t* idx; const InstanceDbl* inst; const BlasDbl* blas; };
 TlasParts tlasParts(const tbvh_scene* s) {
-    const char* base = (const char*)s->nodes;
+    const char* base = (const char*)s->nodes.get();
     const uint64_t oIdx = align16(s->nTlasNodes * sizeof(NodeDbl)), oInst = oIdx + align16(s->nTlasIdx * 8), oBlas = oInst + s->nInst * sizeof(InstanceDbl);
     return TlasParts{(const uint64_t*)(base + oIdx), (const InstanceDbl*)(base + oInst), (const BlasDbl*)(base + oBlas)};
 }
@@ -71,7 +74,7 @@ int launchDouble(tbvh_scene* s, RayExRec* dRays, uint64_t n, uint8_t* dOcc) {
     q.spill = c->spill; q.spillStride = c->spillEntries;
     q.counter = (uint32_t*)c->pool + (size_t)c->poolCur * poolWords; q.counterNext = (uint32_t*)c->pool + (size_t)(c->poolCur ^ 1) * poolWords;
     q.poolParts = c->poolParts;
-    q.nodes = (const NodeDbl*)s->nodes; q.tris = (const TriDbl*)s->tris;
+    q.nodes = (const NodeDbl*)s->nodes.get(); q.tris = (const TriDbl*)s->tris.get();
     q.tlasIdx = nullptr; q.inst = nullptr; q.blas = nullptr;
     if (s->isTlas) { const TlasParts p = tlasParts(s); q.tlasIdx = p.idx; q.inst = p.inst; q.blas = p.blas; }
     // one workgroup per 128 rays, at least four per CU, at most the persistent grid the spill area is sized for
@@ -89,21 +92,19 @@ int launchDouble(tbvh_scene* s, RayExRec* dRays, uint64_t n, uint8_t* dOcc) {
 int hostQueryEx(tbvh_scene* s, void* rays, uint64_t n, uint8_t* occ, const char* who) {
     tbvh_context* c = s->ctx;
     TBVH_ENTER(c);
-    void* d = nullptr;
-    uint8_t* dOcc = nullptr;
-    if (hipMalloc(&d, n * sizeof(RayExRec)) != hipSuccess) return fail(TBVH_E_NOMEM, "%s: no device memory for %llu rays", who, (unsigned long long)n);
-    if (occ && hipMalloc((void**)&dOcc, n) != hipSuccess) { hipFree(d); return fail(TBVH_E_NOMEM, "%s: no device memory for %llu results", who, (unsigned long long)n); }
+    DevBuf<RayExRec> d;
+    DevBuf<uint8_t> dOcc;
+    if (d.alloc(n) != hipSuccess) return fail(TBVH_E_NOMEM, "%s: no device memory for %llu rays", who, (unsigned long long)n);
+    if (occ && dOcc.alloc(n) != hipSuccess) return fail(TBVH_E_NOMEM, "%s: no device memory for %llu results", who, (unsigned long long)n);
     int r = 0;
     if (hipMemcpyAsync(d, rays, n * sizeof(RayExRec), hipMemcpyHostToDevice, c->stream) != hipSuccess) r = fail(TBVH_E_HIP, "%s: copy to the device failed", who);
-    if (!r) r = launchDouble(s, (RayExRec*)d, n, dOcc);
+    if (!r) r = launchDouble(s, d, n, dOcc);
     if (!r) {
         const hipError_t e = occ ? hipMemcpyAsync(occ, dOcc, n, hipMemcpyDeviceToHost, c->stream) : hipMemcpyAsync(rays, d, n * sizeof(RayExRec), hipMemcpyDeviceToHost, c->stream);
         if (e != hipSuccess) r = fail(TBVH_E_HIP, "%s: copy from the device failed", who);
     }
     if (!r) r = checkStatus(c);   // (synchronizes)
-    else hipStreamSynchronize(c->stream);
-    hipFree(d);
-    if (dOcc) hipFree(dOcc);
+    else hipStreamSynchronize(c->stream);   // (either way nothing in flight reads the two buffers when they go)
     return r;
 }
 
@@ -188,18 +189,18 @@ int tbvh_upload_bvh_double(tbvh_context* c, const void* nodes64, uint64_t nNodes
     TBVH_ENTER(c);
     tbvh_scene* s = newScene(c, TBVH_LAYOUT_BVH_DOUBLE);
     if (!s) return fail(TBVH_E_NOMEM, "out of host memory");
-    void *dIdx = nullptr, *dVerts = nullptr;
-    auto bail = [&](int code, const char* what) { if (dIdx) hipFree(dIdx); if (dVerts) hipFree(dVerts); tbvh_free_scene(s); return fail(code, "tbvh_upload_bvh_double: %s", what); };
-    if (hipMalloc((void**)&s->nodes, nNodes * sizeof(NodeDbl)) != hipSuccess || hipMalloc((void**)&s->tris, nIdx * sizeof(TriDbl)) != hipSuccess ||
-        hipMalloc(&dIdx, nIdx * 8) != hipSuccess || hipMalloc(&dVerts, nTris * 72) != hipSuccess)
+    DevBuf<uint64_t> dIdx;
+    DevBuf<double> dVerts;
+    auto bail = [&](int code, const char* what) { tbvh_free_scene(s); return fail(code, "tbvh_upload_bvh_double: %s", what); };
+    if (s->nodes.alloc(nNodes * (sizeof(NodeDbl) / 16)) != hipSuccess || s->tris.alloc(nIdx * (sizeof(TriDbl) / 16)) != hipSuccess ||
+        dIdx.alloc(nIdx) != hipSuccess || dVerts.alloc(nTris * 9) != hipSuccess)
         return bail(TBVH_E_NOMEM, "out of device memory");
     if (hipMemcpyAsync(s->nodes, nodes64, nNodes * sizeof(NodeDbl), hipMemcpyHostToDevice, c->stream) != hipSuccess ||
         hipMemcpyAsync(dIdx, primIdx, nIdx * 8, hipMemcpyHostToDevice, c->stream) != hipSuccess ||
         hipMemcpyAsync(dVerts, vertsDbl3, nTris * 72, hipMemcpyHostToDevice, c->stream) != hipSuccess)
         return bail(TBVH_E_HIP, "copy to the device failed");
-    launch_gather_tris_dbl((const uint64_t*)dIdx, (const double*)dVerts, (TriDbl*)s->tris, nIdx, c->stream);
+    launch_gather_tris_dbl(dIdx, dVerts, (TriDbl*)s->tris.get(), nIdx, c->stream);
     if (hipGetLastError() != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) return bail(TBVH_E_HIP, "triangle gather failed");
-    hipFree(dIdx); hipFree(dVerts);
     s->nNodes = (uint32_t)nNodes;
     s->bytes = nNodes * sizeof(NodeDbl) + nIdx * sizeof(TriDbl);
     *out = s;
@@ -222,13 +223,13 @@ int tbvh_upload_tlas_double(tbvh_context* c, const void* nodes64, uint64_t nNode
             return fail(TBVH_E_FORMAT, "tbvh_upload_tlas_double: instance %llu: blasIdx %llu >= n_blas = %llu", (unsigned long long)i, (unsigned long long)inst[i].blasIdx, (unsigned long long)nBlas);
     TBVH_ENTER(c);
     std::vector<BlasDbl> descs(nBlas);
-    for (uint64_t i = 0; i < nBlas; i++) descs[i] = BlasDbl{(const NodeDbl*)blas[i]->nodes, (const TriDbl*)blas[i]->tris};
+    for (uint64_t i = 0; i < nBlas; i++) descs[i] = BlasDbl{(const NodeDbl*)blas[i]->nodes.get(), (const TriDbl*)blas[i]->tris.get()};
     tbvh_scene* s = newScene(c, TBVH_LAYOUT_BVH_DOUBLE);
     if (!s) return fail(TBVH_E_NOMEM, "out of host memory");
     s->isTlas = true; s->nTlasNodes = nNodes; s->nTlasIdx = nIdx; s->nInst = nInst; s->nBlas = nBlas; s->nNodes = (uint32_t)nNodes;
     const uint64_t oIdx = align16(nNodes * sizeof(NodeDbl)), oInst = oIdx + align16(nIdx * 8), oBlas = oInst + nInst * sizeof(InstanceDbl), total = oBlas + nBlas * sizeof(BlasDbl);
-    if (hipMalloc((void**)&s->nodes, total) != hipSuccess) { tbvh_free_scene(s); return fail(TBVH_E_NOMEM, "tbvh_upload_tlas_double: out of device memory"); }
-    char* base = (char*)s->nodes;
+    if (s->nodes.alloc(total / 16) != hipSuccess) { tbvh_free_scene(s); return fail(TBVH_E_NOMEM, "tbvh_upload_tlas_double: out of device memory"); }
+    char* base = (char*)s->nodes.get();
     if (hipMemcpyAsync(base, nodes64, nNodes * sizeof(NodeDbl), hipMemcpyHostToDevice, c->stream) != hipSuccess ||
         hipMemcpyAsync(base + oIdx, idx, nIdx * 8, hipMemcpyHostToDevice, c->stream) != hipSuccess ||
         hipMemcpyAsync(base + oInst, inst, nInst * sizeof(InstanceDbl), hipMemcpyHostToDevice, c->stream) != hipSuccess ||

@@ -23,11 +23,13 @@
 #include <thread>
 #include <vector>
 
+#include "dev_buf.h"
 #include "host_builder.h"
 #include "kernels.h"
 #include "ray_pool.h"
 
 using namespace tbvh;
+using tbvh_capi::DevBuf;
 
 static_assert(kLayoutBvhGpu == TBVH_LAYOUT_BVH_GPU && kLayoutBvh4Gpu == TBVH_LAYOUT_BVH4_GPU && kLayoutCwbvh == TBVH_LAYOUT_CWBVH,
               "kernels.h and the public header agree on the layout codes");
@@ -88,9 +90,9 @@ struct tbvh_context {
     bool timed = false;
     int numCUs = 0;
     uint32_t blocks = 0;          // persistent grid size (64-thread workgroups)
-    uint32_t* spill = nullptr;    // stack spill area
+    DevBuf<uint32_t> spill;       // stack spill area
     uint32_t spillEntries = 0;    // 32-bit entries per lane
-    unsigned long long* counter = nullptr;  // status word, instrumentation counters
+    DevBuf<unsigned long long> counter;     // status word, instrumentation counters
     uint32_t poolParts = 5;   // log2: 32 partitions
     bool embedTris = true;          // TBVH_EMBED_TRIS=0: the hybrid node copy without a triangle in each node's line (A/B: tools/ab_configs.py)
     bool incoherentCopies = true;   // TBVH_INCOHERENT_COPIES=0: no hybrid node copy / 64-byte triangle records (prepareIncoherentCopies)
@@ -100,14 +102,12 @@ struct tbvh_context {
     bool gridOverride = false;     // TBVH_BLOCKS_PER_CU / TBVH_RAYS_PER_BLOCK given: no per-scene adjustment
     uint64_t splitBelow = 12ull << 20;   // batches of fewer rays split their last rays over idle lanes; TBVH_SPLIT_RAYS=0 turns that off (tie order then reproducible run to run)
     uint32_t raysPerBlock = 128;   // small batches: one workgroup per this many rays (with split rays, profiles/r02_grid_sweep.txt: 96-128 best on 1 M-ray batches, +5 % over 192; flat at 4 M)
-    unsigned long long* pool = nullptr;     // ray-fetch counters: kPoolParts of them, 256 bytes apart (ray_pool.h), + the coherence probe's line; TWO such areas
+    DevBuf<uint32_t> pool;                  // ray-fetch counters: kPoolParts of them, 256 bytes apart (ray_pool.h), + the coherence probe's line; TWO such areas
     int poolCur = 0;              // the area the next launch draws from; its kernels zero the other one for the launch after (no memset in the stream)
     bool poolClean = false;       // both areas are known to be as that scheme leaves them (false: the next launch clears them itself)
-    uint32_t* status = nullptr;
-    RayRec* stageRays = nullptr;  // staging for host-array queries
-    uint64_t stageCap = 0;
-    uint8_t* stageOcc = nullptr;
-    uint64_t stageOccCap = 0;
+    uint32_t* status = nullptr;   // (inside `counter`)
+    DevBuf<RayRec> stageRays;     // staging for host-array queries
+    DevBuf<uint8_t> stageOcc;
     // host-array queries of more than a few 10 k rays go through pinned staging in chunks: worker threads gather the
     // 64-byte prefixes of the caller's records into a pinned buffer while the previous chunk is in flight (a pageable
     // hipMemcpy2D moves ~9 GB/s because one CPU thread does the staging copy), and the 20 result bytes per ray come back
@@ -119,8 +119,7 @@ struct tbvh_context {
     float hostQueryMs = -1.f;     // device time of the most recent host-array query (the sum over its groups' launches) ...
     uint64_t hostQuerySeq = ~0ull; // ... valid while no later operation was timed (evSeq still equals this)
     std::vector<PinnedRange> pinned;
-    void* binScratch = nullptr;   // tbvh_bin_rays_device
-    size_t binScratchBytes = 0;
+    DevBuf<void> binScratch;      // tbvh_bin_rays_device
     std::vector<tbvh_scene*> scenes;
 };
 
@@ -155,12 +154,12 @@ struct tbvh_scene {
     tbvh_context* ctx = nullptr;
     int layout = 0;
     int variant = 0;
-    float4* nodes = nullptr;   // BVH_GPU nodes / BVH4 stream / CWBVH nodes
-    float4* tris = nullptr;    // BVH_GPU gathered tris / CWBVH tris
-    float4* nodes128 = nullptr; // CWBVH: the same nodes padded to one 128-byte line each (padCwbvhIfLarge: node arrays beyond the Infinity Cache)
-    float4* nodesHy = nullptr;  // CWBVH: the same nodes in surface-area priority order, the first hybridK packed, the others one per line (cwbvh_node.h: kNodeHybrid)
-    uint32_t* hyPerm = nullptr; // device: position of node i in nodesHy
-    float4* tris64 = nullptr;   // CWBVH (experiment flag 2): triangle records padded to 64 bytes
+    DevBuf<float4> nodes;      // BVH_GPU nodes / BVH4 stream / CWBVH nodes
+    DevBuf<float4> tris;       // BVH_GPU gathered tris / CWBVH tris
+    DevBuf<float4> nodes128;    // CWBVH: the same nodes padded to one 128-byte line each (padCwbvhIfLarge: node arrays beyond the Infinity Cache)
+    DevBuf<float4> nodesHy;     // CWBVH: the same nodes in surface-area priority order, the first hybridK packed, the others one per line (cwbvh_node.h: kNodeHybrid)
+    DevBuf<uint32_t> hyPerm;    // device: position of node i in nodesHy
+    DevBuf<float4> tris64;      // CWBVH (experiment flag 2): triangle records padded to 64 bytes
     uint32_t hybridK = 0;
     CohTuner cohTuner[2][4];    // [any-hit][batch-size class: < 6 M, < 12 M, more rays; 3 = 768 k .. 1.5 M rays on a scene under 48 MB]: which schedule wins can depend on the batch size (the tail of a launch weighs differently)
     uint8_t cohLastClass[2] = {2, 2};   // the class of the most recent two-flavor launch (tbvh_debug_coherent_schedule reports that one)
@@ -173,61 +172,56 @@ struct tbvh_scene {
     uint64_t bytes = 0;
     // TLAS (layout = BVH_GPU nodes in `nodes`)
     bool isTlas = false;
-    uint32_t* tlasIdx = nullptr;
-    float4* instances = nullptr;
-    BlasDesc* blasDesc = nullptr;
+    DevBuf<uint32_t> tlasIdx;
+    DevBuf<float4> instances;   // 12 per instance
+    DevBuf<BlasDesc> blasDesc;
     int blasLayout = 0;
     bool blasMixCw2 = false;          // blasLayout == 0 and every BLAS is BVH8_CWBVH or BVH_GPU: the reference's two BLAS types (traverse_tlas.cl:50-72)
     bool blasSpheres = false;         // some BLAS is a sphere BLAS (capi_custom.hip): every query takes the flat loop with the sphere step, BLASes in their own layouts
     // any-hit queries may enter the BLASes through other arrays than closest-hit ones (BVH4_GPU BLASes: their own stream for closest hits — k_tlas4 —, their
-    // 8-wide copies for IsOccluded — k_tlas8, + 28 % on 1000 instances —: capi_scene.hip: reclassifyTlas); blasDescAny == nullptr: the same as above
-    BlasDesc* blasDescAny = nullptr;
+    // 8-wide copies for IsOccluded — k_tlas8, + 28 % on 1000 instances —: capi_scene.hip: reclassifyTlas); blasDescAny empty: the same as above
+    DevBuf<BlasDesc> blasDescAny;
     bool anyHitSeen = false;          // the TLAS has had an any-hit query: only then do its BVH4_GPU BLASes get their copies and the second wide tree is kept (a frame loop that only
                                       // ever calls Intersect pays for neither: per frame the second tree's rebuild and the copies' refit cost 0.27 ms at 1000 instances)
     int blasLayoutAny = -1;
     bool blasMixCw2Any = false;
-    uint64_t capNodes = 0, capIdx = 0, capInst = 0;
     uint64_t nInst = 0, nBlas = 0, nTlasNodes = 0, nTlasIdx = 0;
     // the same TLAS collapsed 4-wide in the BVH4_GPU node format (kernels_tlas4.hip), kept current by every upload / update / device rebuild;
     // only for TLASes whose BLASes are all BVH4_GPU
-    float4* tlas4 = nullptr;
-    uint64_t tlas4Cap = 0;            // blocks
-    void* tlas4Scratch = nullptr;
-    size_t tlas4ScratchBytes = 0;
+    DevBuf<float4> tlas4;             // count(): blocks
+    DevBuf<void> tlas4Scratch;
     // ... or 8-wide in the BVH8_CWBVH node format (kernels_tlas8.hip) for TLASes whose BLASes are all BVH8_CWBVH; same scratch
-    float4* tlas8 = nullptr;
-    uint32_t* tlas8Refs = nullptr;
-    uint64_t tlas8Cap = 0;            // nodes; instance references: the same number
+    DevBuf<float4> tlas8;             // 5 per node: count() / 5 = nodes the wide tree may have (allocated after tlas8Refs: never there without them)
+    DevBuf<uint32_t> tlas8Refs;       // instance references: the same number
     // device-side TLAS rebuild (kernels_tlasbuild.hip)
-    float* blasBounds = nullptr;      // 6 floats per BLAS
-    float* xformStage = nullptr;      // staged transforms (16 floats per instance) when the caller passes host memory
-    uint64_t xformStageCap = 0;       // instances the staging buffer holds
+    DevBuf<float> blasBounds;         // 6 floats per BLAS
+    DevBuf<float> xformStage;         // staged transforms (16 floats per instance) when the caller passes host memory
     // BLAS <-> TLAS references: a TLAS snapshots its BLASes' device pointers (BlasDesc), so a BLAS knows the TLASes that
     // use it (their descriptors are refreshed when its opacity maps change) and outlives them (tbvh_free_scene on a BLAS
     // that is still referenced only marks it; the memory goes when the last TLAS over it is freed)
     std::vector<tbvh_scene*> blasList;   // TLAS: its BLASes, in blasIdx order
     std::vector<tbvh_scene*> usedBy;     // BLAS: the TLASes built over it (one entry per reference)
     bool zombie = false;                 // BLAS: freed by the caller while still referenced
-    void* buildScratch = nullptr;
-    size_t buildScratchBytes = 0, sortTempBytes = 0;
+    DevBuf<void> buildScratch;
+    size_t sortTempBytes = 0;
     uint64_t buildScratchFor = 0;     // instance count the scratch was sized for
     // device-side BLAS refit (kernels_refit.hip)
-    void* refitScratch = nullptr;
+    DevBuf<void> refitScratch;
     std::vector<uint32_t> b4Levels;   // BVH4_GPU: first node of every tree level in the item list (filled by the first refit)
-    float4* vertStage = nullptr;      // staged vertices when the caller passes host memory
-    // opacity micromaps (BVHBase::SetOpacityMicroMaps)
+    DevBuf<void> vertStage;           // staged vertices when the caller passes host memory (strided meshes: sized in bytes)
+    // opacity micromaps (BVHBase::SetOpacityMicroMaps): what the kernels read is a plain pointer on every scene — a derived copy (wide / wide4)
+    // shares its owner's maps —, the allocation belongs to the scene they were set on
     uint32_t* opmap = nullptr;
+    DevBuf<uint32_t> opmapOwn;
     uint32_t opmapN = 0;
     uint64_t opmapBytes = 0;
-    uint64_t vertStageBytes = 0;
     // a scene made from an INDEXED mesh (tbvh_*_mesh with indices) keeps its own device copy of the index buffer, 12 bytes per triangle, counted in
     // `bytes`: tbvh_refit_mesh with indices == NULL then means "the indices the scene holds" — the per-frame call of an animated mesh passes the
     // shared vertices only.  The derived copies (wide / wide4) hold none: their refit is handed the owner's source.
-    uint32_t* meshIdx = nullptr;
+    DevBuf<uint32_t> meshIdx;
     uint64_t meshIdxTris = 0;
-    uint32_t* idxStage = nullptr;        // staged host indices of tbvh_intersect_spheres_mesh (a per-frame query: no allocation per call)
-    uint64_t idxStageBytes = 0;
-    // BVH_GPU / BVH4_GPU: the same tree collapsed 8-wide into the BVH8_CWBVH format (capi_scene.hip: makeWideCopy; made by the first query), kept current by update / refit / micromap
+    DevBuf<uint32_t> idxStage;           // staged host indices of tbvh_intersect_spheres_mesh (a per-frame query: no allocation per call)
+    // BVH_GPU / BVH4_GPU: the same tree collapsed 8-wide into the BVH8_CWBVH format (capi_scene.hip: makeCopy; made by the first query), kept current by update / refit / micromap
     // calls and traced INSTEAD of `nodes` by the queries on this scene: hit records do not depend on the layout (device_common.h: hit_wins), and the
     // compressed wide kernels trace the same rays 1.6-2.9 x faster than the 2-wide one (profiles/r06_bvh2.txt).  Owned by this scene, not listed in
     // the context's scene table; TLASes over this BLAS enter it through the copies as well (capi_scene.hip: blasView).
@@ -273,9 +267,8 @@ struct HostPipe {
     hipStream_t down = nullptr;   // the results' way back: pack kernel + device-to-host copies, beside the uploads and kernels on the context's stream
     hipEvent_t evKernel = nullptr;
     std::vector<hipEvent_t> evGroup;   // group g's results have landed in pinDown
-    uint32_t* packed = nullptr;   // device: 5 dwords per ray (bytes 44..63 of the record)
+    DevBuf<uint32_t> packed;      // device: 5 dwords per ray (bytes 44..63 of the record)
     void* pinDown = nullptr;      // pinned host: the same, for the whole batch
-    uint64_t packedCap = 0;
     // a small persistent worker pool: parallel_for(n, fn) runs fn(part, parts) on every worker and the caller
     std::vector<std::thread> workers;
     std::mutex m;
@@ -327,7 +320,6 @@ struct HostPipe {
         if (evKernel) hipEventDestroy(evKernel);
         if (down) hipStreamDestroy(down);
         if (pinDown) hipHostFree(pinDown);
-        if (packed) hipFree(packed);
     }
 };
 
@@ -350,9 +342,11 @@ int padCwbvhIfLarge(tbvh_scene* s);
 size_t hybridBytes(uint32_t nNodes, uint32_t K);
 bool wantsIncoherentCopies(const tbvh_scene* s);
 int prepareIncoherentCopies(tbvh_scene* s);
-void freeWideCopy(tbvh_scene* s);
-void freeWide4Copy(tbvh_scene* s);
-int makeWide4Copy(tbvh_scene* s);   // the 4-wide copy of a BVH_GPU / BVH8_CWBVH BLAS (closest-hit queries of the TLASes over it)
+// (capi_scene.hip) the derived copies of a BLAS: the 8-wide one of a BVH_GPU / BVH4_GPU scene (tbvh_scene::wide; made lazily, from launchQuery) and the
+// 4-wide one of a BVH_GPU / BVH8_CWBVH BLAS (tbvh_scene::wide4; closest-hit queries of the TLASes over it).  The values are the bits of pendingCopies.
+enum CopyKind { kCopyWide8 = 1, kCopyWide4 = 2 };
+void freeCopy(tbvh_scene* s, CopyKind kind);
+int makeCopy(tbvh_scene* s, CopyKind kind);
 int reclassifyTlas(tbvh_scene* t);
 void dropCopiesAfterUpdate(tbvh_scene* s);   // (capi_scene.hip) tbvh_update_*: see tbvh_scene::pendingCopies
 void countQueryForRecopy(tbvh_scene* s);     // ... and the query side of it (launchQuery)   // (capi_scene.hip) descriptors, kernel class and wide trees of a TLAS from its BLASes as they are now
@@ -364,11 +358,8 @@ uint64_t meshVertexBytes(const tbvh_mesh& m);                          // bytes 
 // context's stream: synchronise before the caller's arrays may change and before this object goes)
 struct DeviceMesh {
     tbvh::MeshSrc src;
-    void *ownVerts = nullptr, *ownIdx = nullptr;
-    DeviceMesh() = default;
-    DeviceMesh(const DeviceMesh&) = delete;
-    DeviceMesh& operator=(const DeviceMesh&) = delete;
-    ~DeviceMesh() { if (ownVerts) hipFree(ownVerts); if (ownIdx) hipFree(ownIdx); }
+    DevBuf<void> ownVerts;
+    DevBuf<uint32_t> ownIdx;
 };
 int stageMesh(tbvh_context* c, const tbvh_mesh& m, DeviceMesh& out);
 int keepMeshIndices(tbvh_scene* s, const tbvh::MeshSrc& src);          // the scene's own copy of src.indices (no-op without indices); device to device, asynchronous
@@ -376,5 +367,4 @@ int refitDeviceSource(tbvh_scene* s, const tbvh::MeshSrc& src);        // (capi_
 int hostBuildImpl(const tbvh::HostMesh& mesh, uint64_t nTris, int layout, const tbvh_build_params* p, tbvh_hostbvh** out);   // (capi_host.hip) tbvh_host_build / _mesh
 int checkSphereScene(tbvh_scene* s, const char* who);   // (capi_sphere.hip) the refusals a sphere query makes before it looks at anything else
 int launchSpheres(tbvh_scene* s, const float4* dSpheres, uint64_t n, const tbvh::MeshSrc& verts, uint8_t* dHit);   // (capi_sphere.hip)
-int makeWideCopy(tbvh_scene* s);   // (lazily, from launchQuery) the 8-wide copy of a BVH_GPU / BVH4_GPU scene   // (lazily, from launchQuery) hybrid node copy + 64-byte triangle records for incoherent batches
 }  // namespace tbvh_capi

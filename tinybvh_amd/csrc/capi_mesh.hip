@@ -44,13 +44,13 @@ int stageMesh(tbvh_context* c, const tbvh_mesh& m, DeviceMesh& out) {
     out.src.nTris = m.n_tris; out.src.nVerts = (uint32_t)m.n_verts; out.src.stride = m.stride_bytes ? m.stride_bytes : 16u;
     if (m.on_device) { out.src.verts = (const float4*)m.verts; out.src.indices = m.indices; return 0; }
     const uint64_t vb = meshVertexBytes(m);
-    HIP_TRY(hipMalloc(&out.ownVerts, vb ? vb : 16));
+    HIP_TRY(out.ownVerts.alloc(vb ? vb : 16));
     if (vb) HIP_TRY(hipMemcpyAsync(out.ownVerts, m.verts, vb, hipMemcpyHostToDevice, c->stream));
-    out.src.verts = (const float4*)out.ownVerts;
+    out.src.verts = (const float4*)out.ownVerts.get();
     if (m.indices) {
-        HIP_TRY(hipMalloc(&out.ownIdx, m.n_tris * 12));
+        HIP_TRY(out.ownIdx.alloc(m.n_tris * 3));
         HIP_TRY(hipMemcpyAsync(out.ownIdx, m.indices, m.n_tris * 12, hipMemcpyHostToDevice, c->stream));
-        out.src.indices = (const uint32_t*)out.ownIdx;
+        out.src.indices = out.ownIdx;
     }
     return 0;
 }
@@ -59,11 +59,11 @@ int keepMeshIndices(tbvh_scene* s, const MeshSrc& src) {
     if (!src.indices) return 0;
     if (s->meshIdx && s->meshIdxTris != src.nTris) {
         HIP_TRY(hipStreamSynchronize(s->ctx->stream));
-        hipFree(s->meshIdx); s->meshIdx = nullptr;
+        s->meshIdx.reset();
         s->bytes -= s->meshIdxTris * 12; s->meshIdxTris = 0;
     }
     if (!s->meshIdx) {
-        HIP_TRY(hipMalloc((void**)&s->meshIdx, src.nTris * 12));
+        HIP_TRY(s->meshIdx.alloc(src.nTris * 3));
         s->meshIdxTris = src.nTris; s->bytes += src.nTris * 12;
     }
     HIP_TRY(hipMemcpyAsync(s->meshIdx, src.indices, src.nTris * 12, hipMemcpyDeviceToDevice, s->ctx->stream));
@@ -97,18 +97,17 @@ int tbvh_upload_host_mesh(tbvh_context* c, const tbvh_hostbvh* h, const tbvh_mes
     if (mesh->indices) {
         TBVH_ENTER(c);
         MeshSrc only;
-        void* tmp = nullptr;
+        DevBuf<uint32_t> tmp;
         only.nTris = mesh->n_tris; only.indices = mesh->indices;
         int r = 0;
         if (!mesh->on_device) {
-            if (hipMalloc(&tmp, mesh->n_tris * 12) != hipSuccess || hipMemcpyAsync(tmp, mesh->indices, mesh->n_tris * 12, hipMemcpyHostToDevice, c->stream) != hipSuccess) {
+            if (tmp.alloc(mesh->n_tris * 3) != hipSuccess || hipMemcpyAsync(tmp, mesh->indices, mesh->n_tris * 12, hipMemcpyHostToDevice, c->stream) != hipSuccess) {
                 (void)hipGetLastError(); r = fail(TBVH_E_NOMEM, "tbvh_upload_host_mesh: %llu bytes of device memory for the index buffer", (unsigned long long)(mesh->n_tris * 12));
             }
-            only.indices = (const uint32_t*)tmp;
+            only.indices = tmp;
         }
         if (!r) r = keepMeshIndices(s, only);
-        hipStreamSynchronize(c->stream);
-        if (tmp) hipFree(tmp);
+        hipStreamSynchronize(c->stream);   // (the copy out of the temporary is done before it goes)
         if (r) { tbvh_free_scene(s); return r; }
     }
     *out = s;
@@ -145,24 +144,14 @@ int tbvh_intersect_spheres_mesh(tbvh_scene* s, const void* spheres, uint64_t n, 
     src.verts = (const float4*)mesh->verts; src.indices = mesh->indices;
     if (!mesh->on_device) {
         const uint64_t vb = meshVertexBytes(*mesh), ib = mesh->indices ? mesh->n_tris * 12 : 0;
-        if (s->vertStageBytes < vb) {
-            if (s->vertStage) hipFree(s->vertStage);
-            s->vertStage = nullptr; s->vertStageBytes = 0;
-            HIP_TRY(hipMalloc((void**)&s->vertStage, vb));
-            s->vertStageBytes = vb;
-        }
-        if (s->idxStageBytes < ib) {
-            if (s->idxStage) hipFree(s->idxStage);
-            s->idxStage = nullptr; s->idxStageBytes = 0;
-            HIP_TRY(hipMalloc((void**)&s->idxStage, ib));
-            s->idxStageBytes = ib;
-        }
+        HIP_TRY(s->vertStage.reserve(vb));
+        HIP_TRY(s->idxStage.reserve(ib / 4));
         HIP_TRY(hipMemcpyAsync(s->vertStage, mesh->verts, vb, hipMemcpyHostToDevice, c->stream));
         if (ib) HIP_TRY(hipMemcpyAsync(s->idxStage, mesh->indices, ib, hipMemcpyHostToDevice, c->stream));
-        src.verts = s->vertStage; src.indices = ib ? s->idxStage : nullptr;
+        src.verts = (const float4*)s->vertStage.get(); src.indices = ib ? s->idxStage.get() : nullptr;
     }
     HIP_TRY(hipMemcpyAsync(c->stageRays, spheres, n * 16, hipMemcpyHostToDevice, c->stream));
-    int r = launchSpheres(s, (const float4*)c->stageRays, n, src, c->stageOcc);
+    int r = launchSpheres(s, (const float4*)c->stageRays.get(), n, src, c->stageOcc);
     if (!r && hipMemcpyAsync(hit, c->stageOcc, n, hipMemcpyDeviceToHost, c->stream) != hipSuccess) r = fail(TBVH_E_HIP, "tbvh_intersect_spheres_mesh: copy from the device failed");
     if (!r) return checkStatus(c);   // (synchronizes)
     hipStreamSynchronize(c->stream);

@@ -6,19 +6,11 @@ using namespace tbvh_capi;
 
 namespace tbvh_capi {
 int ensureStage(tbvh_context* c, uint64_t n) {
-    if (c->stageCap >= n) return 0;
-    if (c->stageRays) hipFree(c->stageRays);
-    c->stageRays = nullptr; c->stageCap = 0;
-    HIP_TRY(hipMalloc((void**)&c->stageRays, n * sizeof(RayRec)));
-    c->stageCap = n;
+    HIP_TRY(c->stageRays.reserve(n));
     return 0;
 }
 int ensureStageOcc(tbvh_context* c, uint64_t n) {
-    if (c->stageOccCap >= n) return 0;
-    if (c->stageOcc) hipFree(c->stageOcc);
-    c->stageOcc = nullptr; c->stageOccCap = 0;
-    HIP_TRY(hipMalloc((void**)&c->stageOcc, n));
-    c->stageOccCap = n;
+    HIP_TRY(c->stageOcc.reserve(n));
     return 0;
 }
 }  // namespace tbvh_capi
@@ -89,14 +81,13 @@ int ensurePipe(tbvh_context* c, uint64_t nHits) {
         c->pipe = p.release();
     }
     HostPipe* p = c->pipe;
-    if (p->packedCap < nHits) {   // nHits: 20-byte result records the two buffers must hold (two groups of a closest-hit batch, or an any-hit batch's flags)
+    if (p->packed.count() < nHits * 5) {   // nHits: 20-byte result records the two buffers must hold (two groups of a closest-hit batch, or an any-hit batch's flags)
         HIP_TRY(hipStreamSynchronize(p->down));
-        if (p->packed) hipFree(p->packed);
+        p->packed.reset();   // (a failure below leaves no device buffer: the next query makes both again)
         if (p->pinDown) hipHostFree(p->pinDown);
-        p->packed = nullptr; p->pinDown = nullptr; p->packedCap = 0;
-        HIP_TRY(hipMalloc((void**)&p->packed, nHits * 20));
+        p->pinDown = nullptr;
         HIP_TRY(hipHostMalloc(&p->pinDown, nHits * 20, hipHostMallocDefault));
-        p->packedCap = nHits;
+        HIP_TRY(p->packed.alloc(nHits * 5));
     }
     return 0;
 }
@@ -132,7 +123,7 @@ static int hostQuerySmall(tbvh_scene* s, const char* raysIn, char* raysOut, uint
     HIP_TRY(hipMemcpy2DAsync(c->stageRays, 64, raysIn, stride, 64, n, hipMemcpyHostToDevice, c->stream));
     if (int r = launchQuery(s, c->stageRays, n, occ ? c->stageOcc : nullptr)) return r;
     if (occ) HIP_TRY(hipMemcpyAsync(occ, c->stageOcc, n, hipMemcpyDeviceToHost, c->stream));
-    else HIP_TRY(hipMemcpy2DAsync(raysOut + 44, stride, (const char*)c->stageRays + 44, 64, 20, n, hipMemcpyDeviceToHost, c->stream));
+    else HIP_TRY(hipMemcpy2DAsync(raysOut + 44, stride, (const char*)c->stageRays.get() + 44, 64, 20, n, hipMemcpyDeviceToHost, c->stream));
     return checkStatus(c);   // (synchronizes the stream)
 }
 
@@ -337,13 +328,13 @@ int launchQuery(tbvh_scene* s, RayRec* d_rays, uint64_t n, uint8_t* d_occ, bool 
     if (n == 0) return 0;
     s->raysTraced += n;   // (what tbvh_refit weighs the refit of a scene's copies against)
     if (s->pendingCopies || s->blasRecopyPending) countQueryForRecopy(s);   // copies dropped by a tbvh_update_* come back once the blob has settled
-    if (!s->wideTried && !s->isTlas && s->variant == 0 && (nDev || n >= 1024u) && (s->layout == TBVH_LAYOUT_BVH_GPU || s->layout == TBVH_LAYOUT_BVH4_GPU)) makeWideCopy(s);   // first query of this scene (not part of its time)
-    if (s->wide && s->variant == 0 && !s->wideTlasOnly) return launchQuery(s->wide, d_rays, n, d_occ, fresh, freshTmax, nDev);   // BVH_GPU with an 8-wide copy (capi_scene.hip: makeWideCopy)
+    if (!s->wideTried && !s->isTlas && s->variant == 0 && (nDev || n >= 1024u) && (s->layout == TBVH_LAYOUT_BVH_GPU || s->layout == TBVH_LAYOUT_BVH4_GPU)) makeCopy(s, kCopyWide8);   // first query of this scene (not part of its time)
+    if (s->wide && s->variant == 0 && !s->wideTlasOnly) return launchQuery(s->wide, d_rays, n, d_occ, fresh, freshTmax, nDev);   // BVH_GPU with an 8-wide copy (capi_scene.hip: makeCopy)
     const bool any = d_occ != nullptr;
     if (any && s->isTlas && !s->anyHitSeen && !s->blasSpheres) {   // the first IsOccluded through this TLAS (not part of its time): its BVH4_GPU and BVH_GPU BLASes are entered through 8-wide copies by any-hit queries
         s->anyHitSeen = true;
         for (tbvh_scene* b : s->blasList)
-            if ((b->layout == TBVH_LAYOUT_BVH4_GPU || b->layout == TBVH_LAYOUT_BVH_GPU) && !b->wideTried && b->variant == 0) makeWideCopy(b);   // (re-classifies the TLASes over b, this one included)
+            if ((b->layout == TBVH_LAYOUT_BVH4_GPU || b->layout == TBVH_LAYOUT_BVH_GPU) && !b->wideTried && b->variant == 0) makeCopy(b, kCopyWide8);   // (re-classifies the TLASes over b, this one included)
         if (int r = reclassifyTlas(s)) return r;
     }
     // ray-fetch counters: two areas alternate; the kernels of this launch zero the other area for the next one.  After anything that went wrong
@@ -440,7 +431,7 @@ int launchQuery(tbvh_scene* s, RayRec* d_rays, uint64_t n, uint8_t* d_occ, bool 
         break;
     case TBVH_LAYOUT_VOXELSET:
         q.spillStride = c->spillEntries;
-        launch_voxel(any, (const uint32_t*)s->nodes, nullptr, nullptr, nullptr, nullptr, q, c->status, blocks, c->stream);
+        launch_voxel(any, (const uint32_t*)s->nodes.get(), nullptr, nullptr, nullptr, nullptr, q, c->status, blocks, c->stream);
         break;
     default:
         return fail(TBVH_E_INVALID, "scene layout %d has no query kernel", s->layout);
@@ -658,12 +649,9 @@ int tbvh_bin_rays_device(tbvh_context* c, const void* dIn, void* dOut, uint64_t 
     if (!n) return 0;
     size_t scanTemp = 0;
     const size_t need = ray_bin_scratch_bytes(n, cellBits, flags, &scanTemp);
-    if (need > c->binScratchBytes) {
+    if (need > c->binScratch.count()) {
         HIP_TRY(hipStreamSynchronize(c->stream));
-        if (c->binScratch) hipFree(c->binScratch);
-        c->binScratch = nullptr; c->binScratchBytes = 0;
-        HIP_TRY(hipMalloc(&c->binScratch, need));
-        c->binScratchBytes = need;
+        HIP_TRY(c->binScratch.alloc(need));
     }
     RayBinArgs a;
     for (int k = 0; k < 3; k++) {

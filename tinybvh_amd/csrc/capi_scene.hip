@@ -12,7 +12,7 @@ int padCwbvhIfLarge(tbvh_scene* s) {
     if (s->layout != TBVH_LAYOUT_CWBVH || s->isTlas || s->nodes128 || (uint64_t)s->nNodes * 80 < (512ull << 20)) return 0;
     if ((uint64_t)s->nNodes * 8 >> 32) return 0;   // (cw_load_node addresses float4s with 32 bits: beyond 2^29 nodes — 64 GB padded — the packed array serves)
     tbvh_context* c = s->ctx;
-    if (hipMalloc((void**)&s->nodes128, (size_t)s->nNodes * 128) != hipSuccess) { s->nodes128 = nullptr; (void)hipGetLastError(); return 0; }   // no memory to spare: the packed array serves
+    if (s->nodes128.alloc((size_t)s->nNodes * 8) != hipSuccess) { (void)hipGetLastError(); return 0; }   // no memory to spare: the packed array serves
     launch_cwbvh_pad(s->nodes, s->nodes128, s->nNodes, c->stream);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(c->stream));
@@ -20,7 +20,8 @@ int padCwbvhIfLarge(tbvh_scene* s) {
     return 0;
 }
 
-size_t hybridBytes(uint32_t nNodes, uint32_t K) { return ((size_t)K * 5 + (size_t)(nNodes - K) * 8) * 16; }
+static size_t hybridBlocks(uint32_t nNodes, uint32_t K) { return (size_t)K * 5 + (size_t)(nNodes - K) * 8; }   // 16-byte blocks of the hybrid node copy
+size_t hybridBytes(uint32_t nNodes, uint32_t K) { return hybridBlocks(nNodes, K) * 16; }
 
 // BVH8_CWBVH scenes of the class that gets the per-launch coherence probe (48 - 384 MB of blobs: beyond the L2s, within reach of the Infinity
 // Cache) keep two derived copies for INCOHERENT batches (kernels_cwbvh.hip: PROBED == 2): the nodes in surface-area priority order with the
@@ -49,11 +50,11 @@ int prepareIncoherentCopies(tbvh_scene* s) {
         HIP_TRY(hipMemcpy(host.data(), s->nodes, host.size() * 16, hipMemcpyDeviceToHost));
         std::vector<uint32_t> perm;
         if (!cwbvh_priority_order(host.data(), s->nNodes, perm)) return 0;   // not a strict tree: traversed as uploaded
-        if (hipMalloc((void**)&s->hyPerm, (size_t)s->nNodes * 4) != hipSuccess) { s->hyPerm = nullptr; (void)hipGetLastError(); return 0; }
+        if (s->hyPerm.alloc(s->nNodes) != hipSuccess) { (void)hipGetLastError(); return 0; }
         HIP_TRY(hipMemcpy(s->hyPerm, perm.data(), (size_t)s->nNodes * 4, hipMemcpyHostToDevice));
     }
-    if (!s->nodesHy && hipMalloc((void**)&s->nodesHy, hybridBytes(s->nNodes, K)) != hipSuccess) { s->nodesHy = nullptr; (void)hipGetLastError(); return 0; }
-    if (!s->tris64 && hipMalloc((void**)&s->tris64, nT * 64) != hipSuccess) { s->tris64 = nullptr; (void)hipGetLastError(); hipFree(s->nodesHy); s->nodesHy = nullptr; return 0; }
+    if (!s->nodesHy && s->nodesHy.alloc(hybridBlocks(s->nNodes, K)) != hipSuccess) { (void)hipGetLastError(); return 0; }
+    if (!s->tris64 && s->tris64.alloc(nT * 4) != hipSuccess) { (void)hipGetLastError(); s->nodesHy.reset(); return 0; }
     s->hybridK = K;
     HIP_TRY(hipMemsetAsync(s->nodesHy, 0, hybridBytes(s->nNodes, K), c->stream));
     launch_cwbvh_derive_hybrid(s->nodes, s->hyPerm, s->nodesHy, s->nNodes, K, (c->embedTris && !(c->expFlags & 8u)) ? s->tris : nullptr, c->stream);
@@ -86,22 +87,25 @@ tbvh_scene* newScene(tbvh_context* c, int layout) {
 
 constexpr uint64_t kWideCopyMin = 32768;   // blob entries from which a scene's own queries go through its 8-wide copy (TBVH_WIDE_COPY_MIN)
 
-void freeWideCopy(tbvh_scene* s) {
-    if (!s || !s->wide) return;
-    tbvh_scene* w = s->wide;
-    s->wide = nullptr;
+void freeCopy(tbvh_scene* s, CopyKind kind) {
+    if (!s) return;
+    tbvh_scene*& slot = kind == kCopyWide4 ? s->wide4 : s->wide;
+    tbvh_scene* w = slot;
+    if (!w) return;
+    slot = nullptr;
     s->bytes -= w->bytes < s->bytes ? w->bytes : 0;
-    w->opmap = nullptr; w->opmapBytes = 0;   // (shared with the owner, never owned)
-    tbvh_free_scene(w);
+    tbvh_free_scene(w);   // (the opacity maps it read are the owner's: tbvh_scene::opmapOwn)
 }
 
-void freeWide4Copy(tbvh_scene* s) {
-    if (!s || !s->wide4) return;
-    tbvh_scene* w = s->wide4;
-    s->wide4 = nullptr;
-    s->bytes -= w->bytes < s->bytes ? w->bytes : 0;
-    w->opmap = nullptr; w->opmapBytes = 0;   // (shared with the owner, never owned)
-    tbvh_free_scene(w);
+// f(t) for each distinct TLAS t over BLAS b (usedBy holds one entry per reference), until one returns non-zero: that value, or 0
+template <class F>
+static int forEachTlasOver(tbvh_scene* b, F f) {
+    for (size_t i = 0; i < b->usedBy.size(); i++) {
+        bool seen = false;
+        for (size_t k = 0; k < i; k++) seen |= b->usedBy[k] == b->usedBy[i];
+        if (!seen) if (int r = f(b->usedBy[i])) return r;
+    }
+    return 0;
 }
 
 // The 8-wide copy of a BVH_GPU / BVH4_GPU scene (tbvh_scene::wide), made LAZILY by the scene's first query of 1024 rays or more (launchQuery) — a BLAS
@@ -123,7 +127,7 @@ static tbvh_scene* buildCopy(tbvh_scene* s, int target, bool forTlas) {
     std::vector<Vec4> blob, recs;
     const float4* dRecs = nullptr;
     uint64_t nRecs = 0;
-    struct Tmp { void *n2 = nullptr, *r = nullptr; ~Tmp() { if (n2) hipFree(n2); if (r) hipFree(r); } } t;
+    DevBuf<float4> dN2, dOwnRecs;
     try {
         if (s->layout == TBVH_LAYOUT_BVH_GPU) {
             const uint64_t nNodes = s->nNodeBlocks / 4, nIdx = s->nTriBlocks / 3;
@@ -152,53 +156,29 @@ static tbvh_scene* buildCopy(tbvh_scene* s, int target, bool forTlas) {
             }
             nRecs = recs.size() / 3;
             if (nRecs < minIdx || nRecs > 0x7fffffffull) return nullptr;
-            if (hipMalloc(&t.r, recs.size() * 16) != hipSuccess ||
-                hipMemcpyAsync(t.r, recs.data(), recs.size() * 16, hipMemcpyHostToDevice, c->stream) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
-            dRecs = (const float4*)t.r;
+            if (dOwnRecs.alloc(recs.size()) != hipSuccess ||
+                hipMemcpyAsync(dOwnRecs, recs.data(), recs.size() * 16, hipMemcpyHostToDevice, c->stream) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
+            dRecs = dOwnRecs;
         }
     } catch (const std::bad_alloc&) { return nullptr; }
     if (n2.size() > 0x7fffffffull) return nullptr;
-    if (hipMalloc(&t.n2, n2.size() * 32) != hipSuccess ||
-        hipMemcpyAsync(t.n2, n2.data(), n2.size() * 32, hipMemcpyHostToDevice, c->stream) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
+    if (dN2.alloc(n2.size() * 2) != hipSuccess ||
+        hipMemcpyAsync(dN2, n2.data(), n2.size() * 32, hipMemcpyHostToDevice, c->stream) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
     tbvh_scene* w = nullptr;
-    if (convertDeviceImpl(c, target, (const float4*)t.n2, n2.size(), nullptr, nRecs, flat_mesh(dRecs, nRecs), &w) != 0 || !w) { (void)hipGetLastError(); return nullptr; }
+    if (convertDeviceImpl(c, target, dN2, n2.size(), nullptr, nRecs, flat_mesh(dRecs, nRecs), &w) != 0 || !w) { (void)hipGetLastError(); return nullptr; }
     for (size_t i = 0; i < c->scenes.size(); i++)
         if (c->scenes[i] == w) { c->scenes.erase(c->scenes.begin() + i); break; }   // owned by `s`, freed with it
     w->opmap = s->opmap; w->opmapN = s->opmapN;
     return w;
 }
 
-static int makeWideCopyImpl(tbvh_scene* s) {
-    freeWideCopy(s);
-    s->wideTried = true;
-    if (s->isTlas || (s->layout != TBVH_LAYOUT_BVH_GPU && s->layout != TBVH_LAYOUT_BVH4_GPU)) return 0;
-    if (tbvh_scene* w = buildCopy(s, TBVH_LAYOUT_CWBVH, !s->usedBy.empty())) {
-        s->wide = w; s->bytes += w->bytes;
-        // a copy below the size at which the scene's OWN queries gain from it (made for the TLASes over the scene): those queries keep the uploaded nodes
-        const uint64_t entries = s->layout == TBVH_LAYOUT_BVH_GPU ? s->nTriBlocks / 3 : w->nTriBlocks / 3;
-        s->wideTlasOnly = entries < kWideCopyMin && !getenv("TBVH_WIDE_COPY_MIN");
-    }
-    return 0;
-}
-
-static int makeWide4CopyImpl(tbvh_scene* s) {
-    freeWide4Copy(s);
-    s->wide4Tried = true;
-    if (s->isTlas || (s->layout != TBVH_LAYOUT_BVH_GPU && s->layout != TBVH_LAYOUT_CWBVH)) return 0;
-    if (tbvh_scene* w = buildCopy(s, TBVH_LAYOUT_BVH4_GPU, true)) { s->wide4 = w; s->bytes += w->bytes; }
-    return 0;
-}
 
 // ---- device refit (tbvh_refit / tbvh_refit_mesh below) ----------------------------------------------------------------------------------
 constexpr uint64_t kRefitKeepRays = 8ull << 20;   // a copy's refit (0.3-0.5 ms per 100 k triangles) pays from about this many rays per refit on (0.04-0.08 ns gained per ray)
 // a mesh refitted every frame with few rays traced in between: the copies are dropped (they come back like after an update: tbvh_scene::pendingCopies)
 static bool refitDropsCopies(tbvh_scene* s) {
     uint64_t total = s->raysTraced;
-    for (size_t i = 0; i < s->usedBy.size(); i++) {
-        bool seen = false;
-        for (size_t k = 0; k < i; k++) seen |= s->usedBy[k] == s->usedBy[i];
-        if (!seen) total += s->usedBy[i]->raysTraced;
-    }
+    forEachTlasOver(s, [&](tbvh_scene* t) { total += t->raysTraced; return 0; });
     const bool drop = (s->wide || s->wide4) && s->refitSeen && total - s->raysAtRefit < kRefitKeepRays;
     s->refitSeen = true; s->raysAtRefit = total;
     if (drop) dropCopiesAfterUpdate(s);
@@ -211,8 +191,8 @@ int refitDeviceSource(tbvh_scene* s, const MeshSrc& src) {
     if (s->layout == TBVH_LAYOUT_BVH4_GPU) {
         // node list per level, child-box hand-over area: sized for the most nodes the stream can hold (4 blocks each)
         const uint32_t capNodes = (uint32_t)(s->nNodeBlocks / 4 + 1);
-        if (!s->refitScratch) HIP_TRY(hipMalloc(&s->refitScratch, (size_t)capNodes * (16 + 128) + 256));
-        char* base = (char*)s->refitScratch;
+        if (!s->refitScratch) HIP_TRY(s->refitScratch.alloc((size_t)capNodes * (16 + 128) + 256));
+        char* base = (char*)s->refitScratch.get();
         uint32_t* counter = (uint32_t*)base;
         void* items = base + 256;
         float4* childBox = (float4*)(base + 256 + (size_t)capNodes * 16);
@@ -227,7 +207,7 @@ int refitDeviceSource(tbvh_scene* s, const MeshSrc& src) {
         return fail(TBVH_E_INVALID, "tbvh_refit: layout %d is not refittable", s->layout);
     const uint32_t nNodes = (uint32_t)(s->layout == TBVH_LAYOUT_CWBVH ? s->nNodeBlocks / 5 : s->nNodeBlocks / 4);
     const uint64_t nRecords = s->nTriBlocks / 3;
-    if (!s->refitScratch) HIP_TRY(hipMalloc(&s->refitScratch, refit_scratch_bytes(s->layout, nNodes)));
+    if (!s->refitScratch) HIP_TRY(s->refitScratch.alloc(refit_scratch_bytes(s->layout, nNodes)));
     HIP_TRY(timedBegin(c));
     HIP_TRY(launch_refit(s->layout, s->nodes, nNodes, s->tris, nRecords, src, s->refitScratch, c->status, c->stream));
     HIP_TRY(timedEnd(c));
@@ -252,11 +232,11 @@ static int uploadBvhGpuImpl(tbvh_context* c, const void* nodes64, uint64_t nNode
     TBVH_ENTER(c);
     tbvh_scene* s = newScene(c, TBVH_LAYOUT_BVH_GPU);
     if (!s) return fail(TBVH_E_NOMEM, "out of host memory");
-    uint32_t* dIdx = nullptr;
+    DevBuf<uint32_t> dIdx;
     DeviceMesh dm;
-    hipError_t e = hipMalloc((void**)&s->nodes, nNodes * 64);
-    if (e == hipSuccess) e = hipMalloc((void**)&s->tris, (nIdx ? nIdx : 1) * 48);
-    if (e == hipSuccess) e = hipMalloc((void**)&dIdx, (nIdx ? nIdx : 1) * 4);
+    hipError_t e = s->nodes.alloc(nNodes * 4);
+    if (e == hipSuccess) e = s->tris.alloc((nIdx ? nIdx : 1) * 3);
+    if (e == hipSuccess) e = dIdx.alloc(nIdx ? nIdx : 1);
     if (e == hipSuccess && stageMesh(c, mesh, dm)) e = hipErrorOutOfMemory;
     if (e == hipSuccess) e = hipMemcpyAsync(s->nodes, nodes64, nNodes * 64, hipMemcpyHostToDevice, c->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(dIdx, primIdx, nIdx * 4, hipMemcpyHostToDevice, c->stream);
@@ -267,7 +247,6 @@ static int uploadBvhGpuImpl(tbvh_context* c, const void* nodes64, uint64_t nNode
     int r = 0;
     if (e == hipSuccess && dm.src.indices) r = keepMeshIndices(s, dm.src);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if (dIdx) hipFree(dIdx);
     if (e != hipSuccess) { tbvh_free_scene(s); return fail(TBVH_E_HIP, "BVH_GPU upload failed: %s", hipGetErrorString(e)); }
     if (!r && dm.src.general()) r = checkStatus(c);   // (device-resident indices: the gather reports an index that is not a vertex)
     if (r) { tbvh_free_scene(s); return r; }
@@ -293,7 +272,7 @@ int tbvh_upload_bvh4_gpu(tbvh_context* c, const void* blocks16, uint64_t nBlocks
     TBVH_ENTER(c);
     tbvh_scene* s = newScene(c, TBVH_LAYOUT_BVH4_GPU);
     if (!s) return fail(TBVH_E_NOMEM, "out of host memory");
-    hipError_t e = hipMalloc((void**)&s->nodes, nBlocks * 16);
+    hipError_t e = s->nodes.alloc(nBlocks);
     if (e == hipSuccess) e = hipMemcpyAsync(s->nodes, blocks16, nBlocks * 16, hipMemcpyHostToDevice, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
     if (e != hipSuccess) { tbvh_free_scene(s); return fail(TBVH_E_HIP, "BVH4_GPU upload failed: %s", hipGetErrorString(e)); }
@@ -311,8 +290,8 @@ int tbvh_upload_cwbvh(tbvh_context* c, const void* nodes16, uint64_t nNodeBlocks
     TBVH_ENTER(c);
     tbvh_scene* s = newScene(c, TBVH_LAYOUT_CWBVH);
     if (!s) return fail(TBVH_E_NOMEM, "out of host memory");
-    hipError_t e = hipMalloc((void**)&s->nodes, nNodeBlocks * 16);
-    if (e == hipSuccess) e = hipMalloc((void**)&s->tris, (nTriBlocks ? nTriBlocks : 1) * 16);
+    hipError_t e = s->nodes.alloc(nNodeBlocks);
+    if (e == hipSuccess) e = s->tris.alloc(nTriBlocks ? nTriBlocks : 1);
     if (e == hipSuccess) e = hipMemcpyAsync(s->nodes, nodes16, nNodeBlocks * 16, hipMemcpyHostToDevice, c->stream);
     if (e == hipSuccess && nTriBlocks) e = hipMemcpyAsync(s->tris, tris16, nTriBlocks * 16, hipMemcpyHostToDevice, c->stream);
     s->nNodes = (uint32_t)(nNodeBlocks / 5);
@@ -330,34 +309,32 @@ int tbvh_upload_cwbvh(tbvh_context* c, const void* nodes16, uint64_t nNodeBlocks
 namespace {
 // (re)build the wide TLAS(es) from the BVH_GPU nodes on the device — 8-wide in the BVH8_CWBVH node format, 4-wide in the BVH4_GPU one, whichever the
 // two-level kernels of this TLAS's closest-hit and any-hit queries walk; asynchronous on the context's stream
+// the scratch area the two wide builds share holds what this TLAS needs
+int reserveTlasWideScratch(tbvh_scene* s) {
+    HIP_TRY(s->tlas4Scratch.reserve(tlas_wide_scratch_bytes(s->nTlasNodes, s->nInst)));
+    return 0;
+}
+
 int buildTlasWide8(tbvh_scene* s) {
     tbvh_context* c = s->ctx;
     const uint64_t cap = tlas8_cap_nodes(s->nTlasNodes, s->nInst);
     if (cap > 0x00ffffffull) {   // wide-node indices share a word with 8 flag bits in places: the flat loop serves larger TLASes — and a wide
         // TLAS left from an earlier, smaller upload must not be traversed in its place (launchQuery keys on the pointer)
-        if (s->tlas8) hipFree(s->tlas8);
-        if (s->tlas8Refs) hipFree(s->tlas8Refs);
-        s->tlas8 = nullptr; s->tlas8Refs = nullptr; s->tlas8Cap = 0;
+        s->tlas8.reset(); s->tlas8Refs.reset();
         return 0;
     }
-    if (cap > s->tlas8Cap) {
-        if (s->tlas8) hipFree(s->tlas8);
-        if (s->tlas8Refs) hipFree(s->tlas8Refs);
-        s->tlas8 = nullptr; s->tlas8Refs = nullptr; s->tlas8Cap = 0;
-        HIP_TRY(hipMalloc((void**)&s->tlas8, cap * 80));
-        HIP_TRY(hipMalloc((void**)&s->tlas8Refs, cap * 4));
-        s->tlas8Cap = cap;
+    if (cap * 5 > s->tlas8.count()) {
+        // both go before either is made again, and the nodes — whose size is the capacity, and which launchQuery keys on — are made last: a failure
+        // of either allocation leaves no wide tree and capacity 0, so the next build allocates again
+        s->tlas8.reset(); s->tlas8Refs.reset();
+        HIP_TRY(s->tlas8Refs.alloc(cap));
+        HIP_TRY(s->tlas8.alloc(cap * 5));
         s->bytes += cap * 84;
     }
-    const size_t sb = tlas_wide_scratch_bytes(s->nTlasNodes, s->nInst);
-    if (sb > s->tlas4ScratchBytes) {
-        if (s->tlas4Scratch) hipFree(s->tlas4Scratch);
-        s->tlas4Scratch = nullptr; s->tlas4ScratchBytes = 0;
-        HIP_TRY(hipMalloc(&s->tlas4Scratch, sb));
-        s->tlas4ScratchBytes = sb;
-    }
-    launch_tlas8_build(s->nodes, (uint32_t)s->nTlasNodes, s->tlasIdx, (uint32_t)s->nTlasIdx, s->instances, (uint32_t)s->nInst, s->tlas8, (uint32_t)s->tlas8Cap, s->tlas8Refs,
-                       (uint32_t)s->tlas8Cap, s->tlas4Scratch, c->status, c->stream);
+    if (int r = reserveTlasWideScratch(s)) return r;
+    const uint32_t cap8 = (uint32_t)(s->tlas8.count() / 5);
+    launch_tlas8_build(s->nodes, (uint32_t)s->nTlasNodes, s->tlasIdx, (uint32_t)s->nTlasIdx, s->instances, (uint32_t)s->nInst, s->tlas8, cap8, s->tlas8Refs,
+                       cap8, s->tlas4Scratch, c->status, c->stream);
     HIP_TRY(hipGetLastError());
     return 0;
 }
@@ -366,31 +343,21 @@ int buildTlasWide4(tbvh_scene* s) {
     tbvh_context* c = s->ctx;
     const uint64_t cap = tlas4_cap_blocks(s->nTlasNodes, s->nInst);
     if (cap > 0x7fffffffull) {   // beyond 31-bit block offsets: the flat loop serves this TLAS; drop a 4-wide TLAS of an earlier, smaller upload
-        if (s->tlas4) hipFree(s->tlas4);
-        s->tlas4 = nullptr; s->tlas4Cap = 0;
+        s->tlas4.reset();
         return 0;
     }
-    if (cap > s->tlas4Cap) {
-        if (s->tlas4) hipFree(s->tlas4);
-        s->tlas4 = nullptr; s->tlas4Cap = 0;
-        HIP_TRY(hipMalloc((void**)&s->tlas4, cap * 16));
-        s->tlas4Cap = cap;
+    if (cap > s->tlas4.count()) {
+        HIP_TRY(s->tlas4.alloc(cap));
         s->bytes += cap * 16;
     }
-    const size_t sb = tlas_wide_scratch_bytes(s->nTlasNodes, s->nInst);
-    if (sb > s->tlas4ScratchBytes) {
-        if (s->tlas4Scratch) hipFree(s->tlas4Scratch);
-        s->tlas4Scratch = nullptr; s->tlas4ScratchBytes = 0;
-        HIP_TRY(hipMalloc(&s->tlas4Scratch, sb));
-        s->tlas4ScratchBytes = sb;
-    }
-    launch_tlas4_build(s->nodes, (uint32_t)s->nTlasNodes, s->tlasIdx, (uint32_t)s->nTlasIdx, s->instances, (uint32_t)s->nInst, s->tlas4, (uint32_t)s->tlas4Cap, s->tlas4Scratch, c->status, c->stream);
+    if (int r = reserveTlasWideScratch(s)) return r;
+    launch_tlas4_build(s->nodes, (uint32_t)s->nTlasNodes, s->tlasIdx, (uint32_t)s->nTlasIdx, s->instances, (uint32_t)s->nInst, s->tlas4, (uint32_t)s->tlas4.count(), s->tlas4Scratch, c->status, c->stream);
     HIP_TRY(hipGetLastError());
     return 0;
 }
 
 int buildTlas4(tbvh_scene* s) {
-    const bool any2 = s->blasDescAny != nullptr;
+    const bool any2 = (bool)s->blasDescAny;
     const bool want8 = s->blasLayout == TBVH_LAYOUT_CWBVH || s->blasMixCw2 || (any2 && (s->blasLayoutAny == TBVH_LAYOUT_CWBVH || s->blasMixCw2Any));
     const bool want4 = s->blasLayout == TBVH_LAYOUT_BVH4_GPU || (any2 && s->blasLayoutAny == TBVH_LAYOUT_BVH4_GPU);
     if (want8) if (int r = buildTlasWide8(s)) return r;   // (the two builds share the scratch area: in order on one stream)
@@ -405,9 +372,9 @@ int tlasCopy(tbvh_scene* s, const void* nodes64, uint64_t nNodes, const uint32_t
     for (uint64_t i = 0; i < nIdx; i++) if (idx[i] >= nInst) return fail(TBVH_E_FORMAT, "TLAS: primIdx[%llu] = %u is not an instance (%llu instances)", (unsigned long long)i, idx[i], (unsigned long long)nInst);
     const BLASInstanceCheck* ic = (const BLASInstanceCheck*)inst;
     for (uint64_t i = 0; i < nInst; i++) if (ic[i].blasIdx >= s->nBlas) return fail(TBVH_E_FORMAT, "instance %llu: blasIdx %u out of range (%llu BLASes)", (unsigned long long)i, ic[i].blasIdx, (unsigned long long)s->nBlas);
-    if (nNodes > s->capNodes) { if (s->nodes) hipFree(s->nodes); s->nodes = nullptr; HIP_TRY(hipMalloc((void**)&s->nodes, nNodes * 64)); s->capNodes = nNodes; }
-    if (nIdx > s->capIdx) { if (s->tlasIdx) hipFree(s->tlasIdx); s->tlasIdx = nullptr; HIP_TRY(hipMalloc((void**)&s->tlasIdx, nIdx * 4)); s->capIdx = nIdx; }
-    if (nInst > s->capInst) { if (s->instances) hipFree(s->instances); s->instances = nullptr; HIP_TRY(hipMalloc((void**)&s->instances, nInst * 192)); s->capInst = nInst; }
+    HIP_TRY(s->nodes.reserve(nNodes * 4));
+    HIP_TRY(s->tlasIdx.reserve(nIdx));
+    HIP_TRY(s->instances.reserve(nInst * 12));
     HIP_TRY(hipMemcpyAsync(s->nodes, nodes64, nNodes * 64, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipMemcpyAsync(s->tlasIdx, idx, nIdx * 4, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipMemcpyAsync(s->instances, inst, nInst * 192, hipMemcpyHostToDevice, c->stream));
@@ -445,10 +412,10 @@ int reclassifyTlas(tbvh_scene* t) {
             desc[i] = BlasDesc{b->nodes, b->tris, b->opmap, b->opmapN, (uint32_t)b->layout};
         }
         t->blasLayout = layout; t->blasMixCw2 = false; t->blasLayoutAny = -1; t->blasMixCw2Any = false;
-        if (!t->blasDesc) HIP_TRY(hipMalloc((void**)&t->blasDesc, nBlas * sizeof(BlasDesc)));
+        if (!t->blasDesc) HIP_TRY(t->blasDesc.alloc(nBlas));
         HIP_TRY(hipStreamSynchronize(t->ctx->stream));   // (launches in flight read the old descriptors)
         HIP_TRY(hipMemcpy(t->blasDesc, desc.data(), nBlas * sizeof(BlasDesc), hipMemcpyHostToDevice));
-        if (t->blasDescAny) { hipFree(t->blasDescAny); t->blasDescAny = nullptr; }
+        t->blasDescAny.reset();
         return 0;
     }
     std::vector<BlasDesc> desc[2] = {std::vector<BlasDesc>(nBlas), std::vector<BlasDesc>(nBlas)};
@@ -475,57 +442,52 @@ int reclassifyTlas(tbvh_scene* t) {
     const bool any2 = t->anyHitSeen && !same && (layout[1] == TBVH_LAYOUT_CWBVH || mix[1]);
     t->blasLayout = layout[0]; t->blasMixCw2 = mix[0];
     t->blasLayoutAny = any2 ? layout[1] : -1; t->blasMixCw2Any = any2 && mix[1];
-    if (!t->blasDesc) HIP_TRY(hipMalloc((void**)&t->blasDesc, nBlas * sizeof(BlasDesc)));
+    if (!t->blasDesc) HIP_TRY(t->blasDesc.alloc(nBlas));
     HIP_TRY(hipStreamSynchronize(t->ctx->stream));   // (launches in flight read the old descriptors)
     HIP_TRY(hipMemcpy(t->blasDesc, desc[0].data(), nBlas * sizeof(BlasDesc), hipMemcpyHostToDevice));
     if (any2) {
-        if (!t->blasDescAny) HIP_TRY(hipMalloc((void**)&t->blasDescAny, nBlas * sizeof(BlasDesc)));
+        if (!t->blasDescAny) HIP_TRY(t->blasDescAny.alloc(nBlas));
         HIP_TRY(hipMemcpy(t->blasDescAny, desc[1].data(), nBlas * sizeof(BlasDesc), hipMemcpyHostToDevice));
-    } else if (t->blasDescAny) { hipFree(t->blasDescAny); t->blasDescAny = nullptr; }
+    } else t->blasDescAny.reset();
     if (t->nodes) return buildTlas4(t);
     return 0;
 }
 
-int makeWideCopy(tbvh_scene* s) {
-    const int r = makeWideCopyImpl(s);
-    for (size_t i = 0; i < s->usedBy.size(); i++) {
-        bool seen = false;
-        for (size_t k = 0; k < i; k++) seen |= s->usedBy[k] == s->usedBy[i];
-        if (!seen) (void)reclassifyTlas(s->usedBy[i]);   // (the copy's arrays are new ones — or gone)
+// (one body for what were makeWideCopy and makeWide4Copy)
+int makeCopy(tbvh_scene* s, CopyKind kind) {
+    const bool four = kind == kCopyWide4;
+    freeCopy(s, kind);
+    (four ? s->wide4Tried : s->wideTried) = true;
+    // the 8-wide copy is of a BVH_GPU / BVH4_GPU scene, the 4-wide one of a BVH_GPU / BVH8_CWBVH one and always for the TLASes over it
+    const bool has = !s->isTlas && (s->layout == TBVH_LAYOUT_BVH_GPU || s->layout == (four ? TBVH_LAYOUT_CWBVH : TBVH_LAYOUT_BVH4_GPU));
+    if (tbvh_scene* w = has ? buildCopy(s, four ? TBVH_LAYOUT_BVH4_GPU : TBVH_LAYOUT_CWBVH, four || !s->usedBy.empty()) : nullptr) {
+        (four ? s->wide4 : s->wide) = w; s->bytes += w->bytes;
+        if (!four) {
+            // a copy below the size at which the scene's OWN queries gain from it (made for the TLASes over the scene): those queries keep the uploaded nodes
+            const uint64_t entries = s->layout == TBVH_LAYOUT_BVH_GPU ? s->nTriBlocks / 3 : w->nTriBlocks / 3;
+            s->wideTlasOnly = entries < kWideCopyMin && !getenv("TBVH_WIDE_COPY_MIN");
+        }
     }
-    return r;
-}
-
-int makeWide4Copy(tbvh_scene* s) {
-    const int r = makeWide4CopyImpl(s);
-    for (size_t i = 0; i < s->usedBy.size(); i++) {
-        bool seen = false;
-        for (size_t k = 0; k < i; k++) seen |= s->usedBy[k] == s->usedBy[i];
-        if (!seen) (void)reclassifyTlas(s->usedBy[i]);   // (the copy's arrays are new ones — or gone)
-    }
-    return r;
+    forEachTlasOver(s, [](tbvh_scene* t) { (void)reclassifyTlas(t); return 0; });   // (the copy's arrays are new ones — or gone)
+    return 0;
 }
 
 void dropCopiesAfterUpdate(tbvh_scene* s) {
-    const uint8_t had = (uint8_t)((s->wide ? 1 : 0) | (s->wide4 ? 2 : 0) | s->pendingCopies);
+    const uint8_t had = (uint8_t)((s->wide ? kCopyWide8 : 0) | (s->wide4 ? kCopyWide4 : 0) | s->pendingCopies);
     if (!had) return;
     if (s->remadeSinceUpdate && s->recopyAfter < (1u << 20)) s->recopyAfter *= 4u;   // updated again soon after the copies came back: a blob that keeps changing
     s->remadeSinceUpdate = false;
     hipStreamSynchronize(s->ctx->stream);
-    freeWideCopy(s); freeWide4Copy(s);
+    freeCopy(s, kCopyWide8); freeCopy(s, kCopyWide4);
     s->pendingCopies = had; s->queriesSinceUpdate = 0;
-    for (size_t i = 0; i < s->usedBy.size(); i++) {
-        bool seen = false;
-        for (size_t k = 0; k < i; k++) seen |= s->usedBy[k] == s->usedBy[i];
-        if (!seen) { (void)reclassifyTlas(s->usedBy[i]); s->usedBy[i]->blasRecopyPending = true; }   // (the TLASes enter this BLAS through its own nodes meanwhile)
-    }
+    forEachTlasOver(s, [](tbvh_scene* t) { (void)reclassifyTlas(t); t->blasRecopyPending = true; return 0; });   // (the TLASes enter this BLAS through its own nodes meanwhile)
 }
 
 static void remakePendingCopies(tbvh_scene* b) {
     const uint8_t kinds = b->pendingCopies;
     b->pendingCopies = 0; b->remadeSinceUpdate = true;
-    if (kinds & 1u) makeWideCopy(b);
-    if (kinds & 2u) makeWide4Copy(b);
+    if (kinds & kCopyWide8) makeCopy(b, kCopyWide8);
+    if (kinds & kCopyWide4) makeCopy(b, kCopyWide4);
 }
 
 void countQueryForRecopy(tbvh_scene* s) {
@@ -561,7 +523,7 @@ int tbvh_upload_tlas(tbvh_context* c, const void* nodes64, uint64_t nNodes, cons
     TBVH_ENTER(c);
     for (uint64_t i = 0; i < nBlas && !spheres; i++)   // closest-hit queries enter BVH_GPU and BVH8_CWBVH BLASes through 4-wide copies (blasView), made now; the 8-wide copies any-hit queries
                                                        // enter BVH_GPU and BVH4_GPU BLASes through are made by the TLAS's first any-hit query (launchQuery)
-        if ((blas[i]->layout == TBVH_LAYOUT_BVH_GPU || blas[i]->layout == TBVH_LAYOUT_CWBVH) && !blas[i]->wide4Tried && blas[i]->variant == 0) makeWide4Copy(blas[i]);
+        if ((blas[i]->layout == TBVH_LAYOUT_BVH_GPU || blas[i]->layout == TBVH_LAYOUT_CWBVH) && !blas[i]->wide4Tried && blas[i]->variant == 0) makeCopy(blas[i], kCopyWide4);
     tbvh_scene* s = newScene(c, TBVH_LAYOUT_BVH_GPU);
     if (!s) return fail(TBVH_E_NOMEM, "out of host memory");
     s->isTlas = true; s->nBlas = nBlas; s->blasSpheres = spheres;
@@ -592,9 +554,9 @@ static int updateBvhGpuImpl(const char* who, tbvh_scene* s, const void* nodes64,
     if (const char* why = validate_bvh_gpu((const NodeAL*)nodes64, nNodes, nIdx)) return fail(why == kValidateNoMemory ? TBVH_E_NOMEM : TBVH_E_FORMAT, "%s", why);
     tbvh_context* c = s->ctx;
     TBVH_ENTER(c);
-    uint32_t* dIdx = nullptr;
+    DevBuf<uint32_t> dIdx;
     DeviceMesh dm;
-    hipError_t e = hipMalloc((void**)&dIdx, (nIdx ? nIdx : 1) * 4);
+    hipError_t e = dIdx.alloc(nIdx ? nIdx : 1);
     if (e == hipSuccess && stageMesh(c, *mesh, dm)) e = hipErrorOutOfMemory;
     if (e == hipSuccess) e = hipMemcpyAsync(s->nodes, nodes64, nNodes * 64, hipMemcpyHostToDevice, c->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(dIdx, primIdx, nIdx * 4, hipMemcpyHostToDevice, c->stream);
@@ -602,10 +564,9 @@ static int updateBvhGpuImpl(const char* who, tbvh_scene* s, const void* nodes64,
     int r = 0;
     if (e == hipSuccess && dm.src.indices) r = keepMeshIndices(s, dm.src);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if (dIdx) hipFree(dIdx);
     if (e != hipSuccess) return fail(TBVH_E_HIP, "%s: %s", who, hipGetErrorString(e));
     if (!dm.src.indices && s->meshIdx) {   // re-uploaded from vertices without indices: a held index buffer would describe another mesh
-        hipFree(s->meshIdx); s->meshIdx = nullptr;
+        s->meshIdx.reset();
         s->bytes -= s->meshIdxTris * 12; s->meshIdxTris = 0;
     }
     s->nNodeBlocks = nNodes * 4; s->nTriBlocks = nIdx * 3;
@@ -637,7 +598,7 @@ int tbvh_update_bvh4_gpu(tbvh_scene* s, const void* blocks16, uint64_t nBlocks) 
     HIP_TRY(hipStreamSynchronize(c->stream));
     s->nNodeBlocks = nBlocks;
     s->b4Levels.clear();   // (the node list of a device refit is rebuilt by the next tbvh_refit)
-    if (s->refitScratch) { hipFree(s->refitScratch); s->refitScratch = nullptr; }
+    s->refitScratch.reset();
     dropCopiesAfterUpdate(s);   // (the copy is of the old tree: it comes back once the blob has settled — tbvh_scene::pendingCopies)
     return 0;
 }
@@ -658,7 +619,7 @@ static int updateCwbvhImpl(tbvh_scene* s, const void* nodes16, uint64_t nNodeBlo
     const bool sameShape = nNodes == s->nNodes && nTriBlocks == s->nTriBlocks && hash == s->topoHash;
     s->bytes -= (s->nNodeBlocks + s->nTriBlocks) * 16; s->bytes += (nNodeBlocks + nTriBlocks) * 16;
     s->nNodes = nNodes; s->nNodeBlocks = nNodeBlocks; s->nTriBlocks = nTriBlocks; s->topoHash = hash;
-    if (s->refitScratch) { hipFree(s->refitScratch); s->refitScratch = nullptr; }   // (sized and filled for the old tree)
+    s->refitScratch.reset();   // (sized and filled for the old tree)
     if (!sameShape) for (auto& kind : s->cohTuner) for (CohTuner& tu : kind) if (!tu.pinned) { tu.drop_pending(); tu = CohTuner(); }   // (its timings were taken on the old tree)
     if (sameShape) {   // boxes and vertices moved, the tree did not: the derived copies keep their numbering and are re-derived on the device
         if (s->nodes128) launch_cwbvh_pad(s->nodes, s->nodes128, nNodes, c->stream);
@@ -668,10 +629,7 @@ static int updateCwbvhImpl(tbvh_scene* s, const void* nodes16, uint64_t nNodeBlo
         return 0;
     }
     // another tree in the same allocation: the derived copies go; they come back as at upload (padded nodes now, the incoherent-batch copies lazily)
-    if (s->nodes128) { hipFree(s->nodes128); s->nodes128 = nullptr; }
-    if (s->nodesHy) { hipFree(s->nodesHy); s->nodesHy = nullptr; }
-    if (s->tris64) { hipFree(s->tris64); s->tris64 = nullptr; }
-    if (s->hyPerm) { hipFree(s->hyPerm); s->hyPerm = nullptr; }
+    s->nodes128.reset(); s->nodesHy.reset(); s->tris64.reset(); s->hyPerm.reset();
     s->hybridK = 0; s->hyTried = false; s->hyLevelOrder = false;
     s->bytes = (nNodeBlocks + nTriBlocks) * 16 + s->opmapBytes;
     return padCwbvhIfLarge(s);
@@ -691,17 +649,15 @@ int tbvh_update_cwbvh(tbvh_scene* s, const void* nodes16, uint64_t nNodeBlocks, 
 namespace {
 // BVH2 (device arrays) -> CWBVH scene.  msBefore: device time already spent on this request (builder), added to the report.
 int convertDeviceImpl4(tbvh_context* c, const float4* dN2, uint64_t nNodes2, const uint32_t* dIdx, uint64_t nIdx, const MeshSrc& dV, tbvh_scene** out) {
-    struct Tmp {
-        void *blocks = nullptr, *itA = nullptr, *itB = nullptr, *cnt = nullptr;
-        ~Tmp() { for (void* p : {blocks, itA, itB, cnt}) if (p) hipFree(p); }
-    } t;
+    DevBuf<float4> blocks;
+    DevBuf<uint2> itA, itB;
+    DevBuf<uint32_t> cnt;
     const uint64_t capItems = nNodes2 / 2 + 2, capBlocks = capItems * 4 + nIdx * 3;
     if (capBlocks > 0xffffffffull) return fail(TBVH_E_INVALID, "BVH2 -> BVH4_GPU: stream would exceed 32-bit block indices");
-    HIP_TRY(hipMalloc(&t.blocks, capBlocks * 16));
-    HIP_TRY(hipMalloc(&t.itA, capItems * 8)); HIP_TRY(hipMalloc(&t.itB, capItems * 8)); HIP_TRY(hipMalloc(&t.cnt, 16));
+    HIP_TRY(blocks.alloc(capBlocks));
+    HIP_TRY(itA.alloc(capItems)); HIP_TRY(itB.alloc(capItems)); HIP_TRY(cnt.alloc(4));
     uint64_t nBlocks = 0; uint32_t levels = 0;
-    HIP_TRY(run_convert_bvh4(dN2, (uint32_t)nNodes2, dIdx, nIdx, dV, (float4*)t.blocks, capBlocks, (uint2*)t.itA, (uint2*)t.itB, (uint32_t*)t.cnt, c->status,
-                             c->stream, &nBlocks, &levels));
+    HIP_TRY(run_convert_bvh4(dN2, (uint32_t)nNodes2, dIdx, nIdx, dV, blocks, capBlocks, itA, itB, cnt, c->status, c->stream, &nBlocks, &levels));
     uint32_t st = 0;
     HIP_TRY(hipMemcpy(&st, c->status, 4, hipMemcpyDeviceToHost));
     if (st & kStatusMeshIndex) { hipMemset(c->status, 0, 4); return fail(TBVH_E_FORMAT, "BVH2 -> BVH4_GPU: mesh: a vertex index is not a vertex (index >= n_verts)"); }
@@ -712,8 +668,8 @@ int convertDeviceImpl4(tbvh_context* c, const float4* dN2, uint64_t nNodes2, con
     }
     tbvh_scene* s = newScene(c, TBVH_LAYOUT_BVH4_GPU);
     if (!s) return fail(TBVH_E_NOMEM, "out of host memory");
-    hipError_t e = hipMalloc((void**)&s->nodes, nBlocks * 16);
-    if (e == hipSuccess) e = hipMemcpyAsync(s->nodes, t.blocks, nBlocks * 16, hipMemcpyDeviceToDevice, c->stream);
+    hipError_t e = s->nodes.alloc(nBlocks);
+    if (e == hipSuccess) e = hipMemcpyAsync(s->nodes, blocks, nBlocks * 16, hipMemcpyDeviceToDevice, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
     if (e != hipSuccess) { tbvh_free_scene(s); return fail(TBVH_E_HIP, "BVH2 -> BVH4_GPU: %s", hipGetErrorString(e)); }
     s->nNodeBlocks = nBlocks; s->capNodeBlocks = nBlocks; s->bytes = nBlocks * 16;
@@ -725,17 +681,15 @@ int convertDeviceImpl4(tbvh_context* c, const float4* dN2, uint64_t nNodes2, con
 namespace tbvh_capi {
 static int convertDeviceImpl(tbvh_context* c, int layout, const float4* dN2, uint64_t nNodes2, const uint32_t* dIdx, uint64_t nIdx, const MeshSrc& dV, tbvh_scene** out) {
     if (layout == TBVH_LAYOUT_BVH4_GPU) return convertDeviceImpl4(c, dN2, nNodes2, dIdx, nIdx, dV, out);
-    struct Tmp {
-        void *nodes = nullptr, *tris = nullptr, *itA = nullptr, *itB = nullptr, *cnt = nullptr;
-        ~Tmp() { for (void* p : {nodes, tris, itA, itB, cnt}) if (p) hipFree(p); }
-    } t;
+    DevBuf<float4> nodes, tris;
+    DevBuf<uint2> itA, itB;
+    DevBuf<uint32_t> cnt;
     // worst case: every BVH2 interior node becomes a wide node ((n + 1) / 2 of them in a full binary tree, + the root)
     const uint32_t capNodes = (uint32_t)(nNodes2 / 2 + 2);
-    HIP_TRY(hipMalloc(&t.nodes, (size_t)capNodes * 80)); HIP_TRY(hipMalloc(&t.tris, nIdx * 48));
-    HIP_TRY(hipMalloc(&t.itA, (size_t)capNodes * 8)); HIP_TRY(hipMalloc(&t.itB, (size_t)capNodes * 8)); HIP_TRY(hipMalloc(&t.cnt, 16));
+    HIP_TRY(nodes.alloc((size_t)capNodes * 5)); HIP_TRY(tris.alloc(nIdx * 3));
+    HIP_TRY(itA.alloc(capNodes)); HIP_TRY(itB.alloc(capNodes)); HIP_TRY(cnt.alloc(4));
     uint32_t nWide = 0, levels = 0; uint64_t nWideTris = 0;
-    HIP_TRY(run_convert_cwbvh(dN2, (uint32_t)nNodes2, dIdx, nIdx, dV, (float4*)t.nodes, capNodes, (float4*)t.tris, nIdx, (uint2*)t.itA, (uint2*)t.itB,
-                              (uint32_t*)t.cnt, c->status, c->stream, &nWide, &nWideTris, &levels));
+    HIP_TRY(run_convert_cwbvh(dN2, (uint32_t)nNodes2, dIdx, nIdx, dV, nodes, capNodes, tris, nIdx, itA, itB, cnt, c->status, c->stream, &nWide, &nWideTris, &levels));
     uint32_t st = 0;
     HIP_TRY(hipMemcpy(&st, c->status, 4, hipMemcpyDeviceToHost));
     if (st & kStatusMeshIndex) { hipMemset(c->status, 0, 4); return fail(TBVH_E_FORMAT, "BVH2 -> CWBVH: mesh: a vertex index is not a vertex (index >= n_verts)"); }
@@ -748,10 +702,10 @@ static int convertDeviceImpl(tbvh_context* c, int layout, const float4* dN2, uin
     tbvh_scene* s = newScene(c, TBVH_LAYOUT_CWBVH);
     if (!s) return fail(TBVH_E_NOMEM, "out of host memory");
     // keep exactly what was produced
-    hipError_t e = hipMalloc((void**)&s->nodes, (size_t)nWide * 80);
-    if (e == hipSuccess) e = hipMalloc((void**)&s->tris, (nWideTris ? nWideTris : 1) * 48);
-    if (e == hipSuccess) e = hipMemcpyAsync(s->nodes, t.nodes, (size_t)nWide * 80, hipMemcpyDeviceToDevice, c->stream);
-    if (e == hipSuccess && nWideTris) e = hipMemcpyAsync(s->tris, t.tris, nWideTris * 48, hipMemcpyDeviceToDevice, c->stream);
+    hipError_t e = s->nodes.alloc((size_t)nWide * 5);
+    if (e == hipSuccess) e = s->tris.alloc((nWideTris ? nWideTris : 1) * 3);
+    if (e == hipSuccess) e = hipMemcpyAsync(s->nodes, nodes, (size_t)nWide * 80, hipMemcpyDeviceToDevice, c->stream);
+    if (e == hipSuccess && nWideTris) e = hipMemcpyAsync(s->tris, tris, nWideTris * 48, hipMemcpyDeviceToDevice, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
     if (e != hipSuccess) { tbvh_free_scene(s); return fail(TBVH_E_HIP, "BVH2 -> CWBVH: %s", hipGetErrorString(e)); }
     s->nNodes = nWide; s->nNodeBlocks = (uint64_t)nWide * 5; s->nTriBlocks = nWideTris * 3;
@@ -769,18 +723,16 @@ static int convertBvh2Impl(const char* who, tbvh_context* c, const void* nodes32
     if (layout != TBVH_LAYOUT_CWBVH && layout != TBVH_LAYOUT_BVH4_GPU) return fail(TBVH_E_INVALID, "%s: target layout %d not supported (BVH8_CWBVH and BVH4_GPU are)", who, layout);
     if (nNodes2 > 0x7fffffffull || nIdx > 0x7fffffffull) return fail(TBVH_E_INVALID, "%s: BVH2 too large for 32-bit node / triangle indices", who);
     TBVH_ENTER(c);
-    struct Tmp {
-        void *n2 = nullptr, *idx = nullptr;
-        ~Tmp() { for (void* p : {n2, idx}) if (p) hipFree(p); }
-    } t;
+    DevBuf<float4> ownN2;
+    DevBuf<uint32_t> ownIdx;
     DeviceMesh dm;
     const float4* dN2 = (const float4*)nodes32;
     const uint32_t* dIdx = primIdx;
     if (!onDevice) {
-        HIP_TRY(hipMalloc(&t.n2, nNodes2 * 32)); HIP_TRY(hipMalloc(&t.idx, nIdx * 4));
-        HIP_TRY(hipMemcpyAsync(t.n2, nodes32, nNodes2 * 32, hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(hipMemcpyAsync(t.idx, primIdx, nIdx * 4, hipMemcpyHostToDevice, c->stream));
-        dN2 = (const float4*)t.n2; dIdx = (const uint32_t*)t.idx;
+        HIP_TRY(ownN2.alloc(nNodes2 * 2)); HIP_TRY(ownIdx.alloc(nIdx));
+        HIP_TRY(hipMemcpyAsync(ownN2, nodes32, nNodes2 * 32, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipMemcpyAsync(ownIdx, primIdx, nIdx * 4, hipMemcpyHostToDevice, c->stream));
+        dN2 = ownN2; dIdx = ownIdx;
     }
     if (int r = stageMesh(c, mesh, dm)) return r;
     HIP_TRY(timedBegin(c));
@@ -815,19 +767,18 @@ int buildDeviceImpl(const char* who, tbvh_context* c, const tbvh_mesh& mesh, int
     if (layout != TBVH_LAYOUT_CWBVH && layout != TBVH_LAYOUT_BVH4_GPU) return fail(TBVH_E_INVALID, "%s: target layout %d not supported (BVH8_CWBVH and BVH4_GPU are)", who, layout);
     if (nTris > 0x3fffffffull) return fail(TBVH_E_INVALID, "%s: too many triangles for 32-bit node indices", who);
     TBVH_ENTER(c);
-    struct Tmp {
-        void *n2 = nullptr, *idx = nullptr, *scratch = nullptr;
-        ~Tmp() { for (void* p : {n2, idx, scratch}) if (p) hipFree(p); }
-    } t;
+    DevBuf<float4> n2;
+    DevBuf<uint32_t> idx;
+    DevBuf<void> scratch;
     DeviceMesh dm;
     if (int r = stageMesh(c, mesh, dm)) return r;
     size_t sortTemp = 0, scanTemp = 0;
     const size_t scratchBytes = builder == 1 ? ploc_scratch_bytes((uint32_t)nTris, &sortTemp, &scanTemp) : lbvh_scratch_bytes((uint32_t)nTris, &sortTemp);
-    HIP_TRY(hipMalloc(&t.n2, nTris * 2 * 32)); HIP_TRY(hipMalloc(&t.idx, nTris * 4)); HIP_TRY(hipMalloc(&t.scratch, scratchBytes));
+    HIP_TRY(n2.alloc(nTris * 4)); HIP_TRY(idx.alloc(nTris)); HIP_TRY(scratch.alloc(scratchBytes));
     HIP_TRY(timedBegin(c));
-    if (builder == 1) HIP_TRY(launch_ploc_build(dm.src, (uint32_t)nTris, radius, (float4*)t.n2, (uint32_t*)t.idx, t.scratch, sortTemp, scanTemp, c->stream, nullptr));
-    else HIP_TRY(launch_lbvh_build(dm.src, (uint32_t)nTris, maxLeafTris, (float4*)t.n2, (uint32_t*)t.idx, t.scratch, sortTemp, c->stream));
-    int r = convertDeviceImpl(c, layout, (const float4*)t.n2, nTris * 2, (const uint32_t*)t.idx, nTris, dm.src, out);
+    if (builder == 1) HIP_TRY(launch_ploc_build(dm.src, (uint32_t)nTris, radius, n2, idx, scratch, sortTemp, scanTemp, c->stream, nullptr));
+    else HIP_TRY(launch_lbvh_build(dm.src, (uint32_t)nTris, maxLeafTris, n2, idx, scratch, sortTemp, c->stream));
+    int r = convertDeviceImpl(c, layout, n2, nTris * 2, idx, nTris, dm.src, out);
     HIP_TRY(timedEnd(c));
     if (!r && dm.src.indices) {
         r = keepMeshIndices(*out, dm.src);
@@ -875,12 +826,7 @@ int tbvh_build_device_mesh(tbvh_context* c, const tbvh_mesh* mesh, int layout, u
 namespace {
 // the TLASes over BLAS b hold a snapshot of its device pointers: rewrite their entries for b
 int refreshBlasDescs(tbvh_scene* b) {
-    for (size_t i = 0; i < b->usedBy.size(); i++) {
-        bool seen = false;
-        for (size_t k = 0; k < i; k++) seen |= b->usedBy[k] == b->usedBy[i];
-        if (!seen) if (int r = reclassifyTlas(b->usedBy[i])) return r;
-    }
-    return 0;
+    return forEachTlasOver(b, reclassifyTlas);
 }
 }  // namespace
 
@@ -895,28 +841,29 @@ int tbvh_set_opacity_micromaps(tbvh_scene* s, const uint32_t* mapData, uint32_t 
     // snapshots) pointing at live memory — the old maps on a failure, the new ones on success
     const bool clear = !mapData || N == 0;
     if (!clear && (N > 1024 || nTris == 0)) return fail(TBVH_E_INVALID, "tbvh_set_opacity_micromaps: N = %u, %llu triangles", N, (unsigned long long)nTris);
-    uint32_t* fresh = nullptr;
+    DevBuf<uint32_t> fresh;
     uint64_t freshBytes = 0;
     if (!clear) {
         const uint64_t wordsPerTri = ((uint64_t)N * N + 31) >> 5, words = wordsPerTri * nTris;
         // the reference's index can run one row past the map when u + v == 1 exactly (tiny_bvh.h:8518-8519): keep that read inside the allocation
         const uint64_t pad = (((uint64_t)N + 1) * (N + 1) + 63) >> 5;
         freshBytes = (words + pad) * 4;
-        if (hipMalloc((void**)&fresh, freshBytes) != hipSuccess) { (void)hipGetLastError(); return fail(TBVH_E_NOMEM, "tbvh_set_opacity_micromaps: %llu bytes of device memory", (unsigned long long)freshBytes); }
+        if (fresh.alloc(words + pad) != hipSuccess) { (void)hipGetLastError(); return fail(TBVH_E_NOMEM, "tbvh_set_opacity_micromaps: %llu bytes of device memory", (unsigned long long)freshBytes); }
         hipError_t e = hipMemsetAsync(fresh + words, 0, pad * 4, c->stream);
         if (e == hipSuccess) e = hipMemcpyAsync(fresh, mapData, words * 4, onDevice ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, c->stream);
         if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-        if (e != hipSuccess) { hipFree(fresh); return fail(TBVH_E_HIP, "tbvh_set_opacity_micromaps: copying the maps failed: %s", hipGetErrorString(e)); }
+        if (e != hipSuccess) return fail(TBVH_E_HIP, "tbvh_set_opacity_micromaps: copying the maps failed: %s", hipGetErrorString(e));
     }
     HIP_TRY(hipStreamSynchronize(c->stream));   // no query may still read the old maps
-    uint32_t* old = s->opmap;
+    DevBuf<uint32_t> old = std::move(s->opmapOwn);
     const uint64_t oldBytes = s->opmapBytes;
-    s->opmap = fresh; s->opmapN = clear ? 0u : N; s->opmapBytes = freshBytes;
+    s->opmapOwn = std::move(fresh);
+    s->opmap = s->opmapOwn; s->opmapN = clear ? 0u : N; s->opmapBytes = freshBytes;
     s->bytes += freshBytes; s->bytes -= oldBytes;
     if (s->wide) { s->wide->opmap = s->opmap; s->wide->opmapN = s->opmapN; }   // (shared, owned here)
     if (s->wide4) { s->wide4->opmap = s->opmap; s->wide4->opmapN = s->opmapN; }
     const int r = refreshBlasDescs(s);   // the descriptors are rewritten before the old maps go
-    if (old && r == 0) hipFree(old);   // (a failed refresh may have left a descriptor on the old maps: leak them rather than dangle)
+    if (r != 0) (void)old.release();   // (a failed refresh may have left a descriptor on the old maps: leak them rather than dangle)
     return r;
 }
 
@@ -940,12 +887,7 @@ int tbvh_scene_download(tbvh_scene* s, int which, void* dst, uint64_t capBytes, 
 
 // the scene's vertex staging buffer holds `bytes` bytes of the caller's host array (asynchronous copy)
 static int stageRefitVertices(tbvh_scene* s, const void* hostVerts, uint64_t bytes) {
-    if (s->vertStageBytes < bytes) {
-        if (s->vertStage) hipFree(s->vertStage);
-        s->vertStage = nullptr; s->vertStageBytes = 0;
-        HIP_TRY(hipMalloc((void**)&s->vertStage, bytes));
-        s->vertStageBytes = bytes;
-    }
+    HIP_TRY(s->vertStage.reserve(bytes));
     HIP_TRY(hipMemcpyAsync(s->vertStage, hostVerts, bytes, hipMemcpyHostToDevice, s->ctx->stream));
     return 0;
 }
@@ -963,7 +905,7 @@ int tbvh_refit(tbvh_scene* s, const void* verts16, uint64_t nTris, int onDevice)
     const float4* dv = (const float4*)verts16;
     if (!onDevice) {
         if (int r = stageRefitVertices(s, verts16, nTris * 48)) return r;
-        dv = s->vertStage;
+        dv = (const float4*)s->vertStage.get();
     }
     return refitDeviceSource(s, flat_mesh(dv, nTris));
 }
@@ -989,7 +931,7 @@ int tbvh_refit_mesh(tbvh_scene* s, const tbvh_mesh* mesh) {
     src.verts = (const float4*)mesh->verts;
     if (!mesh->on_device) {   // n_verts * stride_bytes go over the link, not n_tris * 48
         if (int r = stageRefitVertices(s, mesh->verts, meshVertexBytes(*mesh))) return r;
-        src.verts = s->vertStage;
+        src.verts = (const float4*)s->vertStage.get();
     }
     if (!mesh->indices) {
         src.indices = held ? s->meshIdx : nullptr;
@@ -998,17 +940,17 @@ int tbvh_refit_mesh(tbvh_scene* s, const tbvh_mesh* mesh) {
     // indices passed: this refit reads them where they are (host indices from a temporary device copy).  A scene that holds an index buffer takes
     // them as its new copy afterwards — device-resident ones only once the kernels have read them all without finding one out of range, so a bad
     // buffer never replaces a good one.  A scene made without indices does not start holding any: what indices == NULL means for it stays as it was.
-    void* tmp = nullptr;
+    DevBuf<uint32_t> tmp;
     src.indices = mesh->indices;
     if (!mesh->on_device) {
-        HIP_TRY(hipMalloc(&tmp, mesh->n_tris * 12));
-        if (hipMemcpyAsync(tmp, mesh->indices, mesh->n_tris * 12, hipMemcpyHostToDevice, c->stream) != hipSuccess) { hipFree(tmp); return fail(TBVH_E_HIP, "tbvh_refit_mesh: copying the indices failed"); }
-        src.indices = (const uint32_t*)tmp;
+        HIP_TRY(tmp.alloc(mesh->n_tris * 3));
+        if (hipMemcpyAsync(tmp, mesh->indices, mesh->n_tris * 12, hipMemcpyHostToDevice, c->stream) != hipSuccess) return fail(TBVH_E_HIP, "tbvh_refit_mesh: copying the indices failed");
+        src.indices = tmp;
     }
     int r = refitDeviceSource(s, src);
     if (!r && mesh->on_device) r = checkStatus(c);   // (synchronizes; only the kernels have seen these indices)
     if (!r && s->meshIdx) r = keepMeshIndices(s, src);
-    if (tmp) { hipStreamSynchronize(c->stream); hipFree(tmp); }
+    if (tmp) hipStreamSynchronize(c->stream);   // (the kernels and the copy above read the temporary)
     return r;
 }
 
@@ -1021,32 +963,25 @@ int tbvh_rebuild_tlas_device(tbvh_scene* s, const void* transforms, int onDevice
     if (n == 0 || n > 0x7fffffffull) return fail(TBVH_E_INVALID, "tbvh_rebuild_tlas_device: %llu instances", (unsigned long long)n);
     if (blasBounds6) {
         if (nBlas != s->nBlas) return fail(TBVH_E_INVALID, "tbvh_rebuild_tlas_device: %llu BLAS bounds for a TLAS over %llu BLASes", (unsigned long long)nBlas, (unsigned long long)s->nBlas);
-        if (!s->blasBounds) HIP_TRY(hipMalloc((void**)&s->blasBounds, s->nBlas * 24));
+        if (!s->blasBounds) HIP_TRY(s->blasBounds.alloc(s->nBlas * 6));
         HIP_TRY(hipMemcpyAsync(s->blasBounds, blasBounds6, s->nBlas * 24, hipMemcpyHostToDevice, c->stream));
         HIP_TRY(hipStreamSynchronize(c->stream));   // the caller's array may go away
     }
     if (!s->blasBounds) return fail(TBVH_E_INVALID, "tbvh_rebuild_tlas_device: the first call needs blas_bounds6");
     // an LBVH over n leaves has 2n - 1 nodes and n index entries
     const uint64_t nNodes = 2 * n - 1;
-    if (nNodes > s->capNodes) { if (s->nodes) hipFree(s->nodes); s->nodes = nullptr; s->capNodes = 0; HIP_TRY(hipMalloc((void**)&s->nodes, nNodes * 64)); s->capNodes = nNodes; }
-    if (n > s->capIdx) { if (s->tlasIdx) hipFree(s->tlasIdx); s->tlasIdx = nullptr; s->capIdx = 0; HIP_TRY(hipMalloc((void**)&s->tlasIdx, n * 4)); s->capIdx = n; }
+    HIP_TRY(s->nodes.reserve(nNodes * 4));
+    HIP_TRY(s->tlasIdx.reserve(n));
     if (s->buildScratchFor != n) {
-        if (s->buildScratch) hipFree(s->buildScratch);
-        s->buildScratch = nullptr; s->buildScratchFor = 0;
-        s->buildScratchBytes = tlas_build_scratch_bytes((uint32_t)n, &s->sortTempBytes);
-        HIP_TRY(hipMalloc(&s->buildScratch, s->buildScratchBytes));
+        s->buildScratchFor = 0;
+        HIP_TRY(s->buildScratch.alloc(tlas_build_scratch_bytes((uint32_t)n, &s->sortTempBytes)));
         s->buildScratchFor = n;
     }
     const float* xf = nullptr;
     if (transforms) {
         if (onDevice) xf = (const float*)transforms;
         else {
-            if (s->xformStageCap < n) {   // tbvh_update_tlas may have grown the instance array since the last rebuild
-                if (s->xformStage) hipFree(s->xformStage);
-                s->xformStage = nullptr; s->xformStageCap = 0;
-                HIP_TRY(hipMalloc((void**)&s->xformStage, n * 64));
-                s->xformStageCap = n;
-            }
+            HIP_TRY(s->xformStage.reserve(n * 16));   // (tbvh_update_tlas may have grown the instance array since the last rebuild)
             HIP_TRY(hipMemcpyAsync(s->xformStage, transforms, n * 64, hipMemcpyHostToDevice, c->stream));
             xf = s->xformStage;
         }
@@ -1082,8 +1017,8 @@ void tbvh_free_scene(tbvh_scene* s) {
     hipSetDevice(c->device);
     hipStreamSynchronize(c->stream);
     if (!s->isTlas && !s->usedBy.empty()) { s->zombie = true; return; }   // a TLAS still points at this BLAS's memory: freed with the last such TLAS
-    freeWideCopy(s);
-    freeWide4Copy(s);
+    freeCopy(s, kCopyWide8);
+    freeCopy(s, kCopyWide4);
     if (s->isTlas) {
         std::vector<tbvh_scene*> mine;
         mine.swap(s->blasList);
@@ -1092,32 +1027,10 @@ void tbvh_free_scene(tbvh_scene* s) {
             if (b->zombie && b->usedBy.empty()) { b->zombie = false; tbvh_free_scene(b); }
         }
     }
-    if (s->nodes) hipFree(s->nodes);
-    if (s->tris) hipFree(s->tris);
-    if (s->nodes128) hipFree(s->nodes128);
-    if (s->nodesHy) hipFree(s->nodesHy);
-    if (s->tris64) hipFree(s->tris64);
-    if (s->hyPerm) hipFree(s->hyPerm);
-    if (s->tlasIdx) hipFree(s->tlasIdx);
-    if (s->instances) hipFree(s->instances);
-    if (s->blasDesc) hipFree(s->blasDesc);
-    if (s->blasDescAny) hipFree(s->blasDescAny);
-    if (s->blasBounds) hipFree(s->blasBounds);
-    if (s->xformStage) hipFree(s->xformStage);
-    if (s->buildScratch) hipFree(s->buildScratch);
-    if (s->tlas4) hipFree(s->tlas4);
-    if (s->tlas4Scratch) hipFree(s->tlas4Scratch);
-    if (s->tlas8) hipFree(s->tlas8);
-    if (s->tlas8Refs) hipFree(s->tlas8Refs);
-    if (s->refitScratch) hipFree(s->refitScratch);
-    if (s->opmap) hipFree(s->opmap);
-    if (s->vertStage) hipFree(s->vertStage);
-    if (s->meshIdx) hipFree(s->meshIdx);
-    if (s->idxStage) hipFree(s->idxStage);
     for (auto& kind : s->cohTuner) for (CohTuner& tu : kind) tu.drop_pending();
     for (size_t i = 0; i < c->scenes.size(); i++)
         if (c->scenes[i] == s) { c->scenes.erase(c->scenes.begin() + i); break; }
-    delete s;
+    delete s;   // (its device buffers go here: the device is current, the stream idle)
 }
 int tbvh_scene_layout(const tbvh_scene* s) { return s ? s->layout : TBVH_E_INVALID; }
 uint64_t tbvh_scene_device_bytes(const tbvh_scene* s) { return s ? s->bytes : 0; }
@@ -1192,7 +1105,7 @@ int tbvh_cwbvh_set_hybrid(tbvh_scene* s, int64_t packedNodes) {
     tbvh_context* c = s->ctx;
     TBVH_ENTER(c);
     HIP_TRY(hipStreamSynchronize(c->stream));
-    if (s->nodesHy) { s->bytes -= hybridBytes(s->nNodes, s->hybridK); hipFree(s->nodesHy); s->nodesHy = nullptr; }
+    if (s->nodesHy) { s->bytes -= hybridBytes(s->nNodes, s->hybridK); s->nodesHy.reset(); }
     s->hyTried = true;   // the caller decides now: no lazy build behind its back
     if (packedNodes < 0) return 0;
     if (s->nTriBlocks / 3 >= (1ull << 27)) return fail(TBVH_E_INVALID, "tbvh_cwbvh_set_hybrid: 2^27 triangle records or more");
@@ -1203,10 +1116,10 @@ int tbvh_cwbvh_set_hybrid(tbvh_scene* s, int64_t packedNodes) {
         HIP_TRY(hipMemcpy(host.data(), s->nodes, host.size() * 16, hipMemcpyDeviceToHost));
         std::vector<uint32_t> perm;
         if (!cwbvh_priority_order(host.data(), s->nNodes, perm)) return fail(TBVH_E_FORMAT, "tbvh_cwbvh_set_hybrid: the node array is not a strict tree (a child range shared by two parents or out of range)");
-        HIP_TRY(hipMalloc((void**)&s->hyPerm, (size_t)s->nNodes * 4));
+        HIP_TRY(s->hyPerm.alloc(s->nNodes));
         HIP_TRY(hipMemcpy(s->hyPerm, perm.data(), (size_t)s->nNodes * 4, hipMemcpyHostToDevice));
     }
-    HIP_TRY(hipMalloc((void**)&s->nodesHy, hybridBytes(s->nNodes, K)));
+    HIP_TRY(s->nodesHy.alloc(hybridBlocks(s->nNodes, K)));
     HIP_TRY(hipMemsetAsync(s->nodesHy, 0, hybridBytes(s->nNodes, K), c->stream));
     s->hybridK = K;
     launch_cwbvh_derive_hybrid(s->nodes, s->hyPerm, s->nodesHy, s->nNodes, K, (c->embedTris && !(c->expFlags & 8u)) ? s->tris : nullptr, c->stream);
@@ -1214,7 +1127,7 @@ int tbvh_cwbvh_set_hybrid(tbvh_scene* s, int64_t packedNodes) {
     s->bytes += hybridBytes(s->nNodes, K);
     if (!s->tris64 && s->nTriBlocks) {
         const uint64_t nT = s->nTriBlocks / 3;
-        HIP_TRY(hipMalloc((void**)&s->tris64, nT * 64));
+        HIP_TRY(s->tris64.alloc(nT * 4));
         launch_cwbvh_pad_tris(s->tris, s->tris64, nT, c->stream);
         HIP_TRY(hipGetLastError());
         s->bytes += nT * 64;

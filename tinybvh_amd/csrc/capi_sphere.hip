@@ -78,15 +78,10 @@ int tbvh_intersect_spheres(tbvh_scene* s, const void* spheres, uint64_t n, const
     TBVH_ENTER(c);
     if (int r = ensureStage(c, (n + 3) / 4)) return r;
     if (int r = ensureStageOcc(c, n)) return r;
-    if (s->vertStageBytes < nTris * 48) {
-        if (s->vertStage) hipFree(s->vertStage);
-        s->vertStage = nullptr; s->vertStageBytes = 0;
-        HIP_TRY(hipMalloc((void**)&s->vertStage, nTris * 48));
-        s->vertStageBytes = nTris * 48;
-    }
+    HIP_TRY(s->vertStage.reserve(nTris * 48));
     HIP_TRY(hipMemcpyAsync(c->stageRays, spheres, n * 16, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipMemcpyAsync(s->vertStage, verts, nTris * 48, hipMemcpyHostToDevice, c->stream));
-    int r = launchSpheres(s, (const float4*)c->stageRays, n, flat_mesh(s->vertStage, nTris), c->stageOcc);
+    int r = launchSpheres(s, (const float4*)c->stageRays.get(), n, flat_mesh((const float4*)s->vertStage.get(), nTris), c->stageOcc);
     if (!r && hipMemcpyAsync(hit, c->stageOcc, n, hipMemcpyDeviceToHost, c->stream) != hipSuccess) r = fail(TBVH_E_HIP, "tbvh_intersect_spheres: copy from the device failed");
     if (!r) return checkStatus(c);   // (synchronizes)
     hipStreamSynchronize(c->stream);

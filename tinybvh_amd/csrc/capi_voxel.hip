@@ -54,9 +54,10 @@ int tbvh_upload_voxelset(tbvh_context* c, const uint32_t* grid, const uint32_t* 
     TBVH_ENTER(c);
     tbvh_scene* s = newScene(c, TBVH_LAYOUT_VOXELSET);
     if (!s) return fail(TBVH_E_NOMEM, "out of host memory");
+    static_assert(kTopWords % 4 == 0 && kGridWords % 4 == 0 && kBrickWords % 4 == 0, "each part is a whole number of the 16-byte blocks `nodes` counts");
     const uint64_t words = kTopWords + kGridWords + nBricks * kBrickWords;
-    if (hipMalloc((void**)&s->nodes, words * 4) != hipSuccess) { tbvh_free_scene(s); return fail(TBVH_E_NOMEM, "tbvh_upload_voxelset: out of device memory"); }
-    uint32_t* base = (uint32_t*)s->nodes;
+    if (s->nodes.alloc(words / 4) != hipSuccess) { tbvh_free_scene(s); return fail(TBVH_E_NOMEM, "tbvh_upload_voxelset: out of device memory"); }
+    uint32_t* base = (uint32_t*)s->nodes.get();
     if (hipMemcpyAsync(base, top, kTopWords * 4, hipMemcpyHostToDevice, c->stream) != hipSuccess ||
         hipMemcpyAsync(base + kTopWords, grid, kGridWords * 4, hipMemcpyHostToDevice, c->stream) != hipSuccess ||
         hipMemcpyAsync(base + kTopWords + kGridWords, bricks, nBricks * kBrickWords * 4, hipMemcpyHostToDevice, c->stream) != hipSuccess ||

@@ -15,16 +15,16 @@ struct tbvh_wavefront {
     uint32_t width = 0, height = 0;   // of this object's accumulator: the image, or a band of it
     uint32_t firstRow = 0, fullHeight = 0;   // tbvh_wavefront_set_band: rows [firstRow, firstRow + height) of an image of fullHeight rows (0: the whole image)
     uint64_t n = 0;
-    RayRec* rays[2] = {nullptr, nullptr};
-    PathAux* aux[2] = {nullptr, nullptr};
-    RayRec* shadow = nullptr;
-    PathAux* shadowAux = nullptr;
-    uint8_t* occ = nullptr;
-    float* accum = nullptr;
-    const float4** blasVerts = nullptr;        // device array: vertex array of every BLAS (TLAS scenes)
-    uint32_t* blueNoise = nullptr;             // device copy of the 128 x 128 x 8 table (optional)
-    uint64_t nBlasVerts = 0;
-    unsigned long long* counters = nullptr;   // [0],[1] path queues, [2] shadow queue, [8..] per-depth history
+    DevBuf<RayRec> rays[2];
+    DevBuf<PathAux> aux[2];
+    DevBuf<RayRec> shadow;
+    DevBuf<PathAux> shadowAux;
+    DevBuf<uint8_t> occ;
+    DevBuf<float> accum;                       // 4 per pixel
+    DevBuf<const float4*> blasVerts;           // device array: vertex array of every BLAS (TLAS scenes)
+    uint64_t nBlasVerts = 0;                   // BLASes that array was FILLED for (0 while it is not)
+    DevBuf<uint32_t> blueNoise;                // device copy of the 128 x 128 x 8 table (optional)
+    DevBuf<unsigned long long> counters;      // [0],[1] path queues, [2] shadow queue, [8..] per-depth history
     hipEvent_t e0 = nullptr, e1 = nullptr;
 };
 
@@ -36,14 +36,14 @@ int tbvh_wavefront_create(tbvh_context* c, uint32_t width, uint32_t height, tbvh
     w->ctx = c; w->width = width; w->height = height; w->n = (uint64_t)width * height;
     hipError_t e = hipSuccess;
     for (int i = 0; i < 2 && e == hipSuccess; i++) {
-        e = hipMalloc((void**)&w->rays[i], w->n * 64);
-        if (e == hipSuccess) e = hipMalloc((void**)&w->aux[i], w->n * sizeof(PathAux));
+        e = w->rays[i].alloc(w->n);
+        if (e == hipSuccess) e = w->aux[i].alloc(w->n);
     }
-    if (e == hipSuccess) e = hipMalloc((void**)&w->shadow, w->n * 64);
-    if (e == hipSuccess) e = hipMalloc((void**)&w->shadowAux, w->n * sizeof(PathAux));
-    if (e == hipSuccess) e = hipMalloc((void**)&w->occ, w->n);
-    if (e == hipSuccess) e = hipMalloc((void**)&w->accum, w->n * 16);
-    if (e == hipSuccess) e = hipMalloc((void**)&w->counters, (size_t)kWfCounterWords * 8);
+    if (e == hipSuccess) e = w->shadow.alloc(w->n);
+    if (e == hipSuccess) e = w->shadowAux.alloc(w->n);
+    if (e == hipSuccess) e = w->occ.alloc(w->n);
+    if (e == hipSuccess) e = w->accum.alloc(w->n * 4);
+    if (e == hipSuccess) e = w->counters.alloc(kWfCounterWords);
     if (e == hipSuccess) e = hipMemset(w->accum, 0, w->n * 16);
     if (e == hipSuccess) e = hipEventCreate(&w->e0);
     if (e == hipSuccess) e = hipEventCreate(&w->e1);
@@ -57,27 +57,19 @@ void tbvh_wavefront_destroy(tbvh_wavefront* w) {
     TBVH_LOCK(w->ctx);
     hipSetDevice(w->ctx->device);
     hipStreamSynchronize(w->ctx->stream);
-    for (int i = 0; i < 2; i++) { if (w->rays[i]) hipFree(w->rays[i]); if (w->aux[i]) hipFree(w->aux[i]); }
-    if (w->shadow) hipFree(w->shadow);
-    if (w->shadowAux) hipFree(w->shadowAux);
-    if (w->occ) hipFree(w->occ);
-    if (w->accum) hipFree(w->accum);
-    if (w->counters) hipFree(w->counters);
-    if (w->blasVerts) hipFree((void*)w->blasVerts);
-    if (w->blueNoise) hipFree(w->blueNoise);
     if (w->ctx->ev0 == w->e0 || w->ctx->ev1 == w->e1) { w->ctx->timed = false; w->ctx->ev0 = w->ctx->ev1 = nullptr; }   // (tbvh_time_last_ms pointed at this frame)
     if (w->e0) hipEventDestroy(w->e0);
     if (w->e1) hipEventDestroy(w->e1);
-    delete w;
+    delete w;   // (its device buffers go here: the device is current, the stream idle)
 }
 
 int tbvh_wavefront_set_blas_vertices(tbvh_wavefront* w, const void* const* dVertsPerBlas, uint64_t nBlas) {
     if (!w || !dVertsPerBlas || !nBlas) return fail(TBVH_E_INVALID, "tbvh_wavefront_set_blas_vertices: null/empty argument");
     TBVH_ENTER(w->ctx);
     HIP_TRY(hipStreamSynchronize(w->ctx->stream));
-    if (w->blasVerts) { hipFree((void*)w->blasVerts); w->blasVerts = nullptr; w->nBlasVerts = 0; }
-    HIP_TRY(hipMalloc((void**)&w->blasVerts, nBlas * sizeof(void*)));
-    HIP_TRY(hipMemcpy((void*)w->blasVerts, dVertsPerBlas, nBlas * sizeof(void*), hipMemcpyHostToDevice));
+    w->nBlasVerts = 0;
+    HIP_TRY(w->blasVerts.alloc(nBlas));
+    HIP_TRY(hipMemcpy(w->blasVerts, dVertsPerBlas, nBlas * sizeof(void*), hipMemcpyHostToDevice));
     w->nBlasVerts = nBlas;
     return 0;
 }
@@ -231,9 +223,9 @@ int tbvh_wavefront_set_blue_noise(tbvh_wavefront* w, const uint32_t* table, uint
     if (table && nWords != 128ull * 128 * 8) return fail(TBVH_E_INVALID, "tbvh_wavefront_set_blue_noise: the table is 128 x 128 x 8 = 131072 words (got %llu)", (unsigned long long)nWords);
     TBVH_ENTER(w->ctx);
     HIP_TRY(hipStreamSynchronize(w->ctx->stream));
-    if (w->blueNoise) { hipFree(w->blueNoise); w->blueNoise = nullptr; }
+    w->blueNoise.reset();
     if (!table) return 0;
-    HIP_TRY(hipMalloc((void**)&w->blueNoise, nWords * 4));
+    HIP_TRY(w->blueNoise.alloc(nWords));
     HIP_TRY(hipMemcpy(w->blueNoise, table, nWords * 4, hipMemcpyHostToDevice));
     return 0;
 }
@@ -249,7 +241,7 @@ int tbvh_wavefront_read(tbvh_wavefront* w, float* rgba) {
 int tbvh_wavefront_finalize(tbvh_wavefront* w, float scale, uint32_t* pixels) {
     if (!w || !pixels) return fail(TBVH_E_INVALID, "tbvh_wavefront_finalize: null argument");
     TBVH_ENTER(w->ctx);
-    uint32_t* d = (uint32_t*)w->shadow;   // 4 bytes per pixel in the shadow-ray buffer (64 bytes per pixel, idle between frames)
+    uint32_t* d = (uint32_t*)w->shadow.get();   // 4 bytes per pixel in the shadow-ray buffer (64 bytes per pixel, idle between frames)
     launch_wf_finalize(w->accum, scale, d, w->n, w->ctx->stream);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(pixels, d, w->n * 4, hipMemcpyDeviceToHost, w->ctx->stream));
