@@ -200,6 +200,20 @@ public:
     void Upload(const void* nodes32, uint32_t usedNodes, const uint32_t* primIdx, uint32_t idxCount, const float* spheres16, uint32_t n) {
         Check(tbvh_upload_custom_spheres(ctx, nodes32, usedNodes, primIdx, idxCount, spheres16, n, Fresh()), "tbvh_upload_custom_spheres");
     }
+    // sphere sets that move (tiny_bvh_anim.cpp's obj.Build( &sphereAABB, n ) per frame), on the device: LBVH (maxLeaf 1..4, 0 = 1) or PLOC
+    // (ploc = true; radius 1..32, 0 = 16); Rebuild = a new tree in the same scene with the same builder, Refit = the same tree, new boxes.
+    // spheres16 in host memory, or in device memory with onDevice = true.  A TLAS over Handle() needs no new upload after Rebuild / Refit.
+    void BuildOnDevice(const float* spheres16, uint32_t n, bool ploc = false, uint32_t maxLeaf = 0, uint32_t radius = 0, bool onDevice = false) {
+        Check(tbvh_build_device_custom_spheres(ctx, spheres16, n, onDevice ? 1 : 0, ploc ? 1 : 0, maxLeaf, radius, Fresh()), "tbvh_build_device_custom_spheres");
+    }
+    void Rebuild(const float* spheres16, uint32_t n, bool onDevice = false) {
+        Check(tbvh_rebuild_custom_spheres_device(s, spheres16, n, onDevice ? 1 : 0), "tbvh_rebuild_custom_spheres_device");
+    }
+    void Refit(const float* spheres16, uint32_t n, bool onDevice = false) {
+        Check(tbvh_refit_custom_spheres(s, spheres16, n, onDevice ? 1 : 0), "tbvh_refit_custom_spheres");
+    }
+    // the root box as it is on the device now: {min, max}, what tbvh_rebuild_tlas_device takes as this BLAS's bounds
+    void Bounds(float bounds6[6]) const { Check(tbvh_custom_spheres_bounds(s, bounds6), "tbvh_custom_spheres_bounds"); }
     // BVH::Intersect( Ray& ) / IsOccluded( const Ray& ) with the sphere callbacks, over a host tinybvh::Ray[]
     void Intersect(tinybvh::Ray* rays, size_t n) { Check(tbvh_intersect(s, rays, n, sizeof(tinybvh::Ray)), "tbvh_intersect"); }
     void IsOccluded(const tinybvh::Ray* rays, size_t n, uint8_t* out) { Check(tbvh_occluded(s, rays, n, sizeof(tinybvh::Ray), out), "tbvh_occluded"); }

@@ -664,13 +664,18 @@ int tbvh_intersect_spheres_device(tbvh_scene* scene, const void* d_spheres16, ui
  * TLAS); u and v stay as the record had them on input (the callback never touches them — for a BLAS query exactly the reference; under a TLAS
  * the reference can carry the u, v of a farther triangle it met first, DESIGN.md par. 12).  A miss leaves the record untouched; IsOccluded
  * writes one byte per ray.  r <= 0, a zero-length D and NaN / infinite components answer as the restated operations make them answer.
+ * The device builder and the refit below do not refuse non-finite spheres, r <= 0 or coincident spheres either (a device array cannot be checked
+ * cheaply): the build terminates with a structurally valid tree, whose boxes are what pos - r / pos + r and min / max give (an inverted box for
+ * r < 0), and the answers are whatever the restated operations give on that tree.
  * Queries are the ordinary ones: tbvh_intersect / _occluded (+ _device, tbvh_intersect_device_fresh, the _sharded variants).
  * TLAS: tbvh_upload_tlas / tbvh_update_tlas / tbvh_rebuild_tlas_device take sphere BLASes alone or mixed with BVH_GPU, BVH4_GPU and
  * BVH8_CWBVH triangle BLASes (tiny_bvh_anim.cpp's scene); a sphere BLAS's bounds are its root box.  Such a TLAS walks every BLAS in its own
  * layout (no 4- or 8-wide copies); a TLAS mixing sphere BLASes with voxel sets is refused.
  * A sphere BLAS is refused (TBVH_E_INVALID) by refit and the tbvh_update_bvh_gpu / _bvh4_gpu / _cwbvh calls, opacity micromaps,
  * tbvh_scene_download, the schedule hints, tbvh_cwbvh_set_hybrid, tbvh_wavefront_render (a TLAS with sphere BLASes too),
- * tbvh_intersect_spheres (+ _device) and the _ex queries; tbvh_upload_tlas_double refuses it as a BLAS.
+ * tbvh_intersect_spheres (+ _device) and the _ex queries; tbvh_upload_tlas_double refuses it as a BLAS.  Sphere sets that move have calls of
+ * their own: tbvh_build_device_custom_spheres, tbvh_rebuild_custom_spheres_device, tbvh_refit_custom_spheres and tbvh_custom_spheres_download,
+ * below.
  * ---------------------------------------------------------------------------------- */
 /* Validated before anything is allocated (TBVH_E_FORMAT names the first bad entry): a child pair beyond n_nodes, a leaf range beyond n_idx,
  * prim_idx[k] >= n_spheres, a node reached twice (shared child or cycle), sizes beyond the 32-bit device offsets.  The spheres are gathered
@@ -680,6 +685,38 @@ int tbvh_upload_custom_spheres(tbvh_context* ctx, const void* nodes32, uint64_t 
 /* The library's builder for callers without tinybvh: a binned SAH BVH over the boxes pos -/+ r (the demos' sphereAABB).
  * tbvh_host_blob(h, 0) = Wald nodes (32 bytes each), (h, 1) = primIdx; tbvh_host_layout = TBVH_LAYOUT_BVH2_WALD. */
 int tbvh_host_build_custom_spheres(const void* spheres16, uint64_t n, tbvh_hostbvh** out);
+
+/* Sphere sets that move (particles, point clouds, tiny_bvh_anim.cpp's obj.Build( &sphereAABB, n ) per frame): build, rebuild and refit on the device.
+ * spheres16 = {x, y, z, r} x n in host (on_device = 0) or device memory; a primitive's box is the demos' sphereAABB, pos - r and pos + r.  Each
+ * call is ONE timed operation (tbvh_time_last_ms: the device time of the whole build or refit), reads nothing back but the builders' small
+ * counters, and returns once the device has finished with spheres16.
+ *
+ * tbvh_build_device_custom_spheres: builder 0 = LBVH (max_leaf 1..4 spheres per leaf, 0 = 1), 1 = PLOC (radius as tbvh_build_device_ploc: 1..32,
+ * 0 = 16; one sphere per leaf, max_leaf ignored); 1 <= n <= 2^31 - 1.  The result is an ordinary TBVH_LAYOUT_BVH2_WALD sphere scene — 2 n Wald
+ * nodes (root at 0, node 1 unused, children adjacent) and the records gathered in primIdx order, as tbvh_upload_custom_spheres leaves them —, which
+ * every query and TLAS call takes unchanged.  The scene remembers n, the builder and its parameters, and keeps the build scratch
+ * (tbvh_scene_device_bytes counts it).
+ *
+ * tbvh_rebuild_custom_spheres_device: a new tree over moved spheres in the SAME scene, with the parameters it remembers (a scene that came from
+ * tbvh_upload_custom_spheres: LBVH, one sphere per leaf); n must be the scene's sphere count.  No allocation from the second call on.  A TLAS
+ * over the scene traces the new tree without being uploaded again (an uploaded scene's arrays are replaced by larger ones once, and the TLASes
+ * over it re-pointed); its instance boxes follow the new root box through tbvh_rebuild_tlas_device with blas_bounds6.
+ *
+ * tbvh_refit_custom_spheres: the topology and primIdx stay; every record is fetched again through the primitive index it carries, a leaf's box is
+ * the min of pos - r / the max of pos + r over its records, an interior box the min / max of its two children (BVH::Refit, tiny_bvh.h:3087-3090),
+ * the root's included.  Any sphere scene, uploaded ones too: children need not be numbered after their parents; nodes the root does not reach are
+ * neither followed out of range nor waited for (their boxes are unspecified afterwards).  n must be the scene's sphere count.
+ *
+ * tbvh_custom_spheres_download: the Wald nodes, primIdx (taken out of the records) and the gathered spheres in primIdx order; any buffer may be
+ * NULL, with all three NULL only the sizes are reported.  cap_* in elements (nodes of 32 bytes, indices, spheres of 16 bytes).
+ * tbvh_custom_spheres_bounds: the root box {min, max} as it is on the device now (24 bytes read back): the BLAS bounds a TLAS build wants. */
+int tbvh_build_device_custom_spheres(tbvh_context* ctx, const void* spheres16, uint64_t n, int on_device, int builder, uint32_t max_leaf,
+                                     uint32_t radius, tbvh_scene** out);
+int tbvh_rebuild_custom_spheres_device(tbvh_scene* scene, const void* spheres16, uint64_t n, int on_device);
+int tbvh_refit_custom_spheres(tbvh_scene* scene, const void* spheres16, uint64_t n, int on_device);
+int tbvh_custom_spheres_download(tbvh_scene* scene, void* nodes32, uint64_t cap_nodes, uint32_t* prim_idx, uint64_t cap_idx, void* spheres16,
+                                 uint64_t cap_spheres, uint64_t* n_nodes, uint64_t* n_idx);
+int tbvh_custom_spheres_bounds(tbvh_scene* scene, float bounds6[6]);
 
 /* ----------------------------------------------------------------------------------
  * indexed and strided triangle meshes — the second form the reference takes triangles in: Build( bvhvec4slice { data, count, stride }, indices,

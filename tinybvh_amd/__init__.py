@@ -802,9 +802,10 @@ class TLAS(_Scene):
         """Per-frame rebuild on the GPU (tbvh_rebuild_tlas_device): instance update + LBVH TLAS, no host
         build and no node upload.  transforms: (n, 16) float32 array (host), a device pointer (int,
         on_device=True), or None to keep the transforms already in the device records."""
-        bounds = None
-        if not getattr(self, "_bounds_sent", False):
-            bounds = self._blas_bounds(self.blas)
+        bounds = self._blas_bounds(self.blas)   # sent with the first call, and again when a BLAS's box has changed (SphereBVH.RebuildOnDevice / Refit)
+        last = getattr(self, "_bounds_last", None)
+        if getattr(self, "_bounds_sent", False) and (last is None or np.array_equal(bounds, last)):
+            bounds = None
         if transforms is None:
             t = None
         elif on_device:
@@ -816,6 +817,8 @@ class TLAS(_Scene):
         check(lib.tbvh_rebuild_tlas_device(self._h, t, 1 if on_device else 0, _ptr(bounds) if bounds is not None else None,
                                            len(self.blas) if bounds is not None else 0), "tbvh_rebuild_tlas_device")
         self._bounds_sent = True
+        if bounds is not None:
+            self._bounds_last = bounds
         return self
 
     def Download(self):
@@ -1214,3 +1217,61 @@ class SphereBVH(_Scene):
         self.nodes, self.prim_idx, self.spheres = nodes32, prim_idx, spheres
         self._bounds = np.concatenate([nodes32[0, 0:3].view(np.float32), nodes32[0, 4:7].view(np.float32)]).astype(np.float32)
         return self
+
+    # ---- sphere sets that move: build, rebuild and refit on the device (tbvh_build_device_custom_spheres and its neighbours) ----
+    @staticmethod
+    def _sphere_arg(spheres):
+        """(pointer, n, on_device, keep-alive) of a numpy array of {x, y, z, r} or a (device_pointer, n) pair"""
+        if isinstance(spheres, tuple):
+            return C.c_void_p(int(spheres[0])), int(spheres[1]), 1, None
+        a = np.ascontiguousarray(spheres, np.float32).reshape(-1, 4)
+        return _ptr(a), a.shape[0], 0, a
+
+    def _after_device_call(self, host_spheres) -> "SphereBVH":
+        """_bounds = the new root box (24 bytes read back), so that TLAS.Build / RebuildOnDevice take the scene as a BLAS; the host mirrors
+        (nodes, prim_idx) are stale until Download()."""
+        b = np.zeros(6, np.float32)
+        check(lib.tbvh_custom_spheres_bounds(self._h, _ptr(b)), "tbvh_custom_spheres_bounds")
+        self._bounds = b
+        self.nodes = self.prim_idx = None
+        if host_spheres is not None:
+            self.spheres = host_spheres
+        return self
+
+    def BuildOnDevice(self, spheres, builder: str = "lbvh", max_leaf: int = 0, radius: int = 0) -> "SphereBVH":
+        """LBVH (max_leaf 1..4 spheres per leaf, 0 = 1) or PLOC (radius 1..32, 0 = 16) over the boxes pos -/+ r, on the device
+        (tbvh_build_device_custom_spheres).  spheres: a numpy array or a (device_pointer, n) pair."""
+        ptr, n, on_device, keep = self._sphere_arg(spheres)
+        if self._h:
+            self.free()
+            self._h = C.c_void_p()
+        check(lib.tbvh_build_device_custom_spheres(self.ctx._h, ptr, n, on_device, {"lbvh": 0, "ploc": 1}[builder], int(max_leaf), int(radius),
+                                                   C.byref(self._h)), "tbvh_build_device_custom_spheres")
+        return self._after_device_call(keep)
+
+    def RebuildOnDevice(self, spheres) -> "SphereBVH":
+        """A new tree over moved spheres in the same scene, with the builder it remembers (tbvh_rebuild_custom_spheres_device); a TLAS over
+        it needs no new upload, only its RebuildOnDevice() for the instance boxes."""
+        ptr, n, on_device, keep = self._sphere_arg(spheres)
+        check(lib.tbvh_rebuild_custom_spheres_device(self._h, ptr, n, on_device), "tbvh_rebuild_custom_spheres_device")
+        return self._after_device_call(keep)
+
+    def Refit(self, spheres, on_device: bool = False) -> "SphereBVH":
+        """Same topology, new boxes and records (tbvh_refit_custom_spheres).  spheres: a numpy array, a (device_pointer, n) pair, or with
+        on_device=True a device pointer to as many spheres as the scene holds."""
+        if on_device and not isinstance(spheres, tuple):
+            spheres = (int(spheres), self.spheres.shape[0])
+        ptr, n, dev, keep = self._sphere_arg(spheres)
+        check(lib.tbvh_refit_custom_spheres(self._h, ptr, n, dev), "tbvh_refit_custom_spheres")
+        return self._after_device_call(keep)
+
+    def Download(self):
+        """(nodes32 as (n, 8) uint32, prim_idx, the gathered spheres in prim_idx order) as they are on the device now
+        (tbvh_custom_spheres_download); fills self.nodes / self.prim_idx."""
+        nn, ni = C.c_uint64(0), C.c_uint64(0)
+        check(lib.tbvh_custom_spheres_download(self._h, None, 0, None, 0, None, 0, C.byref(nn), C.byref(ni)), "tbvh_custom_spheres_download")
+        nodes = np.zeros((nn.value, 8), np.uint32); idx = np.zeros(ni.value, np.uint32); gathered = np.zeros((ni.value, 4), np.float32)
+        check(lib.tbvh_custom_spheres_download(self._h, _ptr(nodes), nn.value, _ptr(idx), ni.value, _ptr(gathered), ni.value, C.byref(nn), C.byref(ni)),
+              "tbvh_custom_spheres_download")
+        self.nodes, self.prim_idx = nodes, idx
+        return nodes, idx, gathered

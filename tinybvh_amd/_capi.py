@@ -140,6 +140,11 @@ SYMBOLS = {
     # custom-geometry sphere BLASes (capi_custom.hip)
     "tbvh_upload_custom_spheres": (_i, [_vp, _vp, _u64, _vp, _u64, _vp, _u64, _pp]),
     "tbvh_host_build_custom_spheres": (_i, [_vp, _u64, _pp]),
+    "tbvh_build_device_custom_spheres": (_i, [_vp, _vp, _u64, _i, _i, _u32, _u32, _pp]),
+    "tbvh_rebuild_custom_spheres_device": (_i, [_vp, _vp, _u64, _i]),
+    "tbvh_refit_custom_spheres": (_i, [_vp, _vp, _u64, _i]),
+    "tbvh_custom_spheres_download": (_i, [_vp, _vp, _u64, _vp, _u64, _vp, _u64, _vp, _vp]),
+    "tbvh_custom_spheres_bounds": (_i, [_vp, _vp]),
     # sphere-overlap queries (capi_sphere.hip)
     "tbvh_intersect_spheres": (_i, [_vp, _vp, _u64, _vp, _u64, _vp]),
     "tbvh_intersect_spheres_device": (_i, [_vp, _vp, _u64, _vp, _u64, _vp]),

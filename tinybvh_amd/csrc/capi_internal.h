@@ -245,6 +245,15 @@ struct tbvh_scene {
     // closest hits (1000 instances, camera rays: 4650 MRays/s against 4190 through BVH8_CWBVH BLASes and 3840 through BVH_GPU ones), k_tlas8 for any-hit queries
     tbvh_scene* wide4 = nullptr;
     bool wide4Tried = false;
+    // a sphere BLAS that moves (capi_custom.hip: tbvh_build_device_custom_spheres / tbvh_rebuild_custom_spheres_device / tbvh_refit_custom_spheres): the
+    // sphere count and the builder a rebuild repeats (an uploaded scene: LBVH, one sphere per leaf).  The build keeps its scratch in buildScratch
+    // (sized for buildScratchFor spheres) and its primIdx here, the refit its pass words in refitScratch, host spheres are staged in vertStage: no
+    // allocation per frame; `bytes` counts them all.
+    uint64_t sphN = 0;
+    int sphBuilder = 0;                  // 0 LBVH, 1 PLOC
+    uint32_t sphMaxLeaf = 1, sphRadius = 16;
+    size_t scanTempBytes = 0;
+    DevBuf<uint32_t> sphIdx;
 };
 
 struct BLASInstanceCheck { float m[32]; float mn[3]; uint32_t blasIdx; float mx[3]; uint32_t mask; uint32_t pad[8]; };

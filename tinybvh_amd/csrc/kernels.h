@@ -114,9 +114,13 @@ hipError_t launch_tlas_rebuild(float4* tlasNodes, uint32_t* tlasIdx, float4* ins
 size_t lbvh_scratch_bytes(uint32_t n, size_t* sortTempBytes);
 size_t ploc_scratch_bytes(uint32_t n, size_t* sortTempBytes, size_t* scanTempBytes);
 hipError_t launch_ploc_build(const MeshSrc& verts, uint32_t n, uint32_t radius, float4* nodes32, uint32_t* primIdx, void* scratch, size_t sortTempBytes,
-                             size_t scanTempBytes, hipStream_t s, uint32_t* steps);
+                             size_t scanTempBytes, hipStream_t s, uint32_t* steps, const float4* spheres = nullptr);
 hipError_t launch_lbvh_build(const MeshSrc& verts, uint32_t n, uint32_t maxLeaf, float4* nodes32, uint32_t* primIdx, void* scratch, size_t sortTempBytes,
-                             hipStream_t s);
+                             hipStream_t s, const float4* spheres = nullptr);   // spheres: the box source is {x, y, z, r} x n (capi_custom.hip), verts is not read
+// custom-geometry sphere BLASes that move (kernels_custom_build.hip): the record gather after a build, and the refit of a Wald tree over sphere records
+void launch_gather_sphere_records(const uint32_t* primIdx, const float4* spheres, float4* recs, uint32_t n, hipStream_t s);
+hipError_t launch_refit_spheres(float4* nodes32, uint32_t nNodes, float4* recs, uint64_t nRecs, const float4* spheres, uint64_t nSpheres, uint32_t* done,
+                                hipStream_t s);
 // BVH2 -> CWBVH conversion on the device (kernels_convert.hip)
 hipError_t run_convert_cwbvh(const float4* nodes2, uint32_t nNodes2, const uint32_t* primIdx, uint64_t nIdx, const MeshSrc& verts,
                              float4* cwNodes, uint32_t capNodes, float4* cwTris, uint64_t capTris, uint2* itemsA, uint2* itemsB, uint32_t* counters,

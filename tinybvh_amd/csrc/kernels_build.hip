@@ -68,6 +68,29 @@ __global__ void k_tri_boxes(const MeshSrc verts, uint32_t n, float4* __restrict_
     }
 }
 
+// the second box source: custom-geometry spheres {x, y, z, r} (capi_custom.hip).  A sphere's box is the demos' sphereAABB, pos - r and pos + r (one
+// float operation per component); loop, wave reduction and the one set of atomics per wave are k_tri_boxes'.  Nothing after this kernel knows
+// where the boxes came from.  (r <= 0 and non-finite values are not refused: an inverted or NaN box only moves its Morton key.)
+__global__ void k_sphere_boxes(const float4* __restrict__ spheres, uint32_t n, float4* __restrict__ triMin, float4* __restrict__ triMax,
+                               uint32_t* __restrict__ centreBounds) {
+    float3 cmn = make_float3(1e30f, 1e30f, 1e30f), cmx = make_float3(-1e30f, -1e30f, -1e30f);
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+        const float4 p = spheres[i];
+        const float3 mn = make_float3(p.x - p.w, p.y - p.w, p.z - p.w), mx = make_float3(p.x + p.w, p.y + p.w, p.z + p.w);
+        triMin[i] = make_float4(mn.x, mn.y, mn.z, 0.f); triMax[i] = make_float4(mx.x, mx.y, mx.z, 0.f);
+        const float3 c = make_float3(0.5f * (mn.x + mx.x), 0.5f * (mn.y + mx.y), 0.5f * (mn.z + mx.z));
+        cmn = min3(cmn, c); cmx = max3(cmx, c);
+    }
+    for (int o = 32; o > 0; o >>= 1) {
+        cmn = min3(cmn, make_float3(__shfl_xor(cmn.x, o), __shfl_xor(cmn.y, o), __shfl_xor(cmn.z, o)));
+        cmx = max3(cmx, make_float3(__shfl_xor(cmx.x, o), __shfl_xor(cmx.y, o), __shfl_xor(cmx.z, o)));
+    }
+    if ((threadIdx.x & 63u) == 0 && cmn.x <= cmx.x) {
+        atomicMin(centreBounds + 0, enc_f32(cmn.x)); atomicMin(centreBounds + 1, enc_f32(cmn.y)); atomicMin(centreBounds + 2, enc_f32(cmn.z));
+        atomicMax(centreBounds + 3, enc_f32(cmx.x)); atomicMax(centreBounds + 4, enc_f32(cmx.y)); atomicMax(centreBounds + 5, enc_f32(cmx.z));
+    }
+}
+
 __global__ void k_tri_morton(const float4* __restrict__ triMin, const float4* __restrict__ triMax, const uint32_t* __restrict__ centreBounds,
                              uint32_t n, unsigned long long* __restrict__ keys, uint32_t* __restrict__ vals) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -232,7 +255,8 @@ __global__ __launch_bounds__(kPlocBlock) void k_ploc_nearest(const float4* __res
         if (d == 0 || g < 0 || (uint32_t)g >= c) continue;
         const int t = me + d;
         const float ex = fmaxf(a3, tile[3][t]) - fminf(a0, tile[0][t]), ey = fmaxf(a4, tile[4][t]) - fminf(a1, tile[1][t]), ez = fmaxf(a5, tile[5][t]) - fminf(a2, tile[2][t]);
-        const float area = ex * ey + ey * ez + ez * ex;
+        float area = ex * ey + ey * ez + ez * ex;
+        area = area < 2.9e38f ? area : 2.9e38f;   // (an infinite or NaN area — non-finite sphere boxes — still names a neighbour: every step merges a pair)
         const uint32_t h = pair_hash(i, (uint32_t)g);
         if (area < best || (area == best && h < bestH)) { best = area; bestJ = (uint32_t)g; bestH = h; }
     }
@@ -330,6 +354,14 @@ Scratch carve(void* base, uint32_t n, size_t sortTempBytes) {
     return s;
 }
 
+// the builders' first kernel: boxes and centroid bounds from the triangles, or from `spheres` when given
+void launch_prim_boxes(const MeshSrc& verts, const float4* spheres, uint32_t n, float4* triMin, float4* triMax, uint32_t* bounds, hipStream_t s) {
+    const uint32_t bs = 256, nb = (n + bs - 1) / bs, grid = nb < 2048u ? nb : 2048u;
+    if (spheres) hipLaunchKernelGGL(k_sphere_boxes, dim3(grid), dim3(bs), 0, s, spheres, n, triMin, triMax, bounds);
+    else if (verts.general()) hipLaunchKernelGGL(k_tri_boxes<true>, dim3(grid), dim3(bs), 0, s, verts, n, triMin, triMax, bounds);
+    else hipLaunchKernelGGL(k_tri_boxes<false>, dim3(grid), dim3(bs), 0, s, verts, n, triMin, triMax, bounds);
+}
+
 }  // namespace
 
 size_t lbvh_scratch_bytes(uint32_t n, size_t* sortTempBytes) {
@@ -340,9 +372,10 @@ size_t lbvh_scratch_bytes(uint32_t n, size_t* sortTempBytes) {
 }
 
 // verts: 3 float4 per triangle (device).  Out: nodes32 (2n BVHNode records; [1] unused), primIdx (n entries = the
-// triangles in Morton order).  maxLeaf: 1..3 triangles per leaf.
+// triangles in Morton order).  maxLeaf: 1..3 triangles per leaf.  spheres (device, {x, y, z, r} x n): the primitives are these spheres, `verts` is
+// not read and maxLeaf may be up to 4.
 hipError_t launch_lbvh_build(const MeshSrc& verts, uint32_t n, uint32_t maxLeaf, float4* nodes32, uint32_t* primIdx, void* scratch, size_t sortTempBytes,
-                             hipStream_t s) {
+                             hipStream_t s, const float4* spheres) {
     const Scratch sc = carve(scratch, n, sortTempBytes);
     hipError_t e;
     if ((e = hipMemsetAsync(sc.bounds, 0xff, 12, s)) != hipSuccess) return e;
@@ -350,8 +383,7 @@ hipError_t launch_lbvh_build(const MeshSrc& verts, uint32_t n, uint32_t maxLeaf,
     if ((e = hipMemsetAsync(sc.flags, 0, (size_t)n * 4, s)) != hipSuccess) return e;
     if ((e = hipMemsetAsync(nodes32, 0, 64, s)) != hipSuccess) return e;   // root + the unused node 1
     const uint32_t bs = 256, nb = (n + bs - 1) / bs;
-    if (verts.general()) hipLaunchKernelGGL(k_tri_boxes<true>, dim3(nb < 2048u ? nb : 2048u), dim3(bs), 0, s, verts, n, sc.triMin, sc.triMax, sc.bounds);
-    else hipLaunchKernelGGL(k_tri_boxes<false>, dim3(nb < 2048u ? nb : 2048u), dim3(bs), 0, s, verts, n, sc.triMin, sc.triMax, sc.bounds);
+    launch_prim_boxes(verts, spheres, n, sc.triMin, sc.triMax, sc.bounds, s);
     hipLaunchKernelGGL(k_tri_morton, dim3(nb), dim3(bs), 0, s, sc.triMin, sc.triMax, sc.bounds, n, sc.keysA, sc.valsA);
     size_t tmp = sortTempBytes;
     if ((e = hipcub::DeviceRadixSort::SortPairs(sc.sortTemp, tmp, sc.keysA, sc.keysB, sc.valsA, primIdx, (int)n, 0, 63, s)) != hipSuccess) return e;
@@ -378,16 +410,16 @@ size_t ploc_scratch_bytes(uint32_t n, size_t* sortTempBytes, size_t* scanTempByt
 }
 
 // PLOC build (see above).  Out as launch_lbvh_build: nodes32 (2n BVHNode records, [1] unused), primIdx (the triangles in Morton order); one
-// triangle per leaf.  radius: search window to each side (8, 16 or 32).  steps (optional): number of clustering steps taken.
+// triangle per leaf.  radius: search window to each side (8, 16 or 32).  steps (optional): number of clustering steps taken.  spheres: as for
+// launch_lbvh_build.
 hipError_t launch_ploc_build(const MeshSrc& verts, uint32_t n, uint32_t radius, float4* nodes32, uint32_t* primIdx, void* scratch, size_t sortTempBytes,
-                             size_t scanTempBytes, hipStream_t s, uint32_t* steps) {
+                             size_t scanTempBytes, hipStream_t s, uint32_t* steps, const float4* spheres) {
     const PlocScratch sc = carve_ploc(scratch, n, sortTempBytes, scanTempBytes);
     hipError_t e;
     if ((e = hipMemsetAsync(sc.bounds, 0xff, 12, s)) != hipSuccess) return e;
     if ((e = hipMemsetAsync(sc.bounds + 3, 0x00, 12, s)) != hipSuccess) return e;
     const uint32_t bs = 256, nb = (n + bs - 1) / bs;
-    if (verts.general()) hipLaunchKernelGGL(k_tri_boxes<true>, dim3(nb < 2048u ? nb : 2048u), dim3(bs), 0, s, verts, n, sc.triMin, sc.triMax, sc.bounds);
-    else hipLaunchKernelGGL(k_tri_boxes<false>, dim3(nb < 2048u ? nb : 2048u), dim3(bs), 0, s, verts, n, sc.triMin, sc.triMax, sc.bounds);
+    launch_prim_boxes(verts, spheres, n, sc.triMin, sc.triMax, sc.bounds, s);
     hipLaunchKernelGGL(k_tri_morton, dim3(nb), dim3(bs), 0, s, sc.triMin, sc.triMax, sc.bounds, n, sc.keysA, sc.valsA);
     size_t tmp = sortTempBytes;
     if ((e = hipcub::DeviceRadixSort::SortPairs(sc.sortTemp, tmp, sc.keysA, sc.keysB, sc.valsA, primIdx, (int)n, 0, 63, s)) != hipSuccess) return e;
