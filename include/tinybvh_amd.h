@@ -377,6 +377,8 @@ typedef struct tbvh_camera {
     float eye[3];  float p1[3]; float p2[3]; float p3[3];  /* view pyramid corners      */
     uint32_t width, height, spp_x, spp_y;                 /* pixels and samples/pixel   */
 } tbvh_camera;
+/* width and height are positive multiples of 4, spp_x and spp_y positive: anything else is TBVH_E_INVALID and launches nothing.
+ * Ray i of the image (i = first .. first + n_rays - 1) is sample i % spp of pixel i / spp in 4x4-tile order. */
 int tbvh_generate_primary_device(tbvh_context* ctx, const tbvh_camera* cam,
                                  void* d_rays64, uint64_t first, uint64_t n_rays);
 /* For every ray i: if it hit (hit.t < 1e30), spawn a uniform random bounce in the hemisphere

@@ -670,7 +670,8 @@ int tbvh_bin_rays_device(tbvh_context* c, const void* dIn, void* dOut, uint64_t 
 
 int tbvh_generate_primary_device(tbvh_context* c, const tbvh_camera* cam, void* dRays, uint64_t first, uint64_t n) {
     if (!c || !cam || (!dRays && n)) return fail(TBVH_E_INVALID, "tbvh_generate_primary_device: null argument");
-    if (cam->width % 4 || cam->height % 4 || !cam->spp_x || !cam->spp_y) return fail(TBVH_E_INVALID, "camera: width/height must be multiples of 4, spp > 0");
+    if (!cam->width || !cam->height || cam->width % 4 || cam->height % 4 || !cam->spp_x || !cam->spp_y)   // (width 0: k_gen_primary divides by width / 4)
+        return fail(TBVH_E_INVALID, "camera: width/height must be positive multiples of 4, spp > 0");
     TBVH_ENTER(c);
     if (!n) return 0;
     CameraArgs a;

@@ -1,5 +1,8 @@
 """Host-side (numpy) ray generators: the ray batches of tiny_bvh_speedtest.cpp, for tests and
-small runs.  The benchmark generates the same batches on the device (kernels_raygen.hip).
+small runs.  The benchmark generates its batches on the device (kernels_raygen.hip): primary and shadow
+rays follow the same formulas as here, in the same order (tests/test_raygen_host.py and test_raygen_gpu.py
+hold the two to one fp64 reference); bounce rays follow the same construction but draw from another random generator (WangHash +
+xorshift32 per ray index there, numpy's default_rng here), so those batches are alike in kind, not in value.
 """
 from __future__ import annotations
 
