@@ -225,6 +225,48 @@ private:
     tbvh_scene* s = nullptr;
 };
 
+// Mesh::SetPose of tiny_scene.h on the device (tbvh_pose_*): what Node::Update (tiny_scene.h:1973-2027) does per skinned / morphed mesh and frame —
+// mesh->SetPose( skin ) or SetPose( weights ) on the CPU, then blas.dynamicGPU->Build( ... ) — becomes pose.SetPose( skin->jointMat.data(), n ) +
+// pose.Refit( scene ): 64 bytes per joint go up, the vertices are made where the refit reads them.  Skin() / Morph() once per mesh; nVerts counts
+// vertices (an indexed mesh: every shared vertex once).  Matrices are row-major 4 x 4 (ts_mat4 / bvhmat4::cell).  A Pose on a NewContext() context
+// must be destroyed before that context's tbvh_shutdown (which frees the poses still alive on it).
+class Pose {
+public:
+    explicit Pose(tbvh_context* own = nullptr, int device = 0) : ctx(own ? own : Context(device)) {}
+    Pose(const Pose&) = delete;
+    Pose& operator=(const Pose&) = delete;
+    ~Pose() { tbvh_pose_free(p); }
+    // Mesh::original / joints / weights: rest16 = bvhvec4 per vertex, joints4 = bvhuint4 per vertex, weights16 = bvhvec4 per vertex
+    void Skin(const void* rest16, size_t nVerts, const uint32_t* joints4, const void* weights16, uint32_t nJoints) {
+        tbvh_pose_free(p); p = nullptr;
+        Check(tbvh_pose_create_skin(ctx, rest16, nVerts, joints4, weights16, nJoints, 0, &p), "tbvh_pose_create_skin");
+    }
+    // Mesh::poses[ 0 .. nTargets ].positions back to back: (nTargets + 1) arrays of nVerts * 3 floats, the base pose first
+    void Morph(const float* positions12, size_t nVerts, uint32_t nTargets) {
+        tbvh_pose_free(p); p = nullptr;
+        Check(tbvh_pose_create_morph(ctx, positions12, nVerts, nTargets, 0, &p), "tbvh_pose_create_morph");
+    }
+    // Mesh::SetPose( const Skin* ): skin->jointMat.data(), skin->jointMat.size()
+    void SetPose(const float* jointMats16, uint32_t nJoints, bool onDevice = false) { Check(tbvh_pose_set_skin(p, jointMats16, nJoints, onDevice ? 1 : 0), "tbvh_pose_set_skin"); }
+    // Mesh::SetPose( const vector<float>& )
+    void SetPose(const std::vector<float>& weights) { Check(tbvh_pose_set_morph(p, weights.data(), (uint32_t)weights.size(), 0), "tbvh_pose_set_morph"); }
+    // the BLAS follows the posed vertices (a Scene made from an indexed mesh: through the index buffer it holds)
+    void Refit(Scene& scene) { Check(tbvh_pose_refit(p, scene.Handle()), "tbvh_pose_refit"); }
+    void Refit(tbvh_scene* scene) { Check(tbvh_pose_refit(p, scene), "tbvh_pose_refit"); }
+    // the posed vertices on the device (bvhvec4 each): vertex input of tbvh_refit / tbvh_build_device* / a tbvh_mesh with on_device = 1
+    const void* Vertices(size_t* nVerts = nullptr) const {
+        const void* d = nullptr; uint64_t n = 0;
+        Check(tbvh_pose_vertices(p, &d, &n), "tbvh_pose_vertices");
+        if (nVerts) *nVerts = (size_t)n;
+        return d;
+    }
+    void Download(void* dst16, size_t capVerts) { Check(tbvh_pose_download(p, dst16, capVerts), "tbvh_pose_download"); }
+    tbvh_pose* Handle() const { return p; }
+private:
+    tbvh_context* ctx;
+    tbvh_pose* p = nullptr;
+};
+
 // tinyocl::Buffer( bytes ) for a ray array that is traced many times (tiny_bvh_speedtest.cpp:1101-1108 wraps its ray array in one per GPU block): page-locked
 // host memory of the library's for the object's lifetime (tbvh_pinned_malloc); a PACKED 64-byte ray array in it goes up by DMA straight from there.
 class PinnedBuffer {

@@ -787,6 +787,52 @@ int tbvh_intersect_spheres_mesh_device(tbvh_scene* scene, const void* d_spheres1
  * of the entry points that stay flat-only.  Asynchronous for a device-resident mesh; a host mesh is staged and the call returns when done. */
 int tbvh_flatten_mesh_device(tbvh_context* ctx, const tbvh_mesh* mesh, void* d_verts16_out);
 
+/* ----------------------------------------------------------------------------------
+ * skinned and morph-target meshes posed on the device — Mesh::SetPose( const Skin* ) and Mesh::SetPose( const vector<float>& ) of tiny_scene.h
+ * (1785-1825, 1751-1778), the vertex part: what Node::Update (1973-2027) runs on the CPU per animated mesh and frame before it rebuilds or refits
+ * the BLAS.  A tbvh_pose keeps the rest data on the device and ONE output buffer of n_verts float4; per frame the caller sends the joint matrices
+ * (64 bytes per joint) or the morph weights, the vertices are produced where the refit reads them, and tbvh_pose_refit refits a scene from them.
+ * n_verts is the number of VERTICES: an indexed mesh poses every shared vertex once.  The scene graph (the joint matrix products), animation
+ * sampling, normals and the FatTri data stay with the caller.  The two kinds are separate calls, as in the reference (whose skin pass starts from
+ * its own backup and overwrites a morph pass).
+ *   - the arithmetic is the reference's, float operation for float operation, as its build (g++ -O3 -mavx2 -mfma, tinyscene's vector types set to
+ *     tinybvh's as tiny_bvh_gltf.cpp does) performs it: tinybvh_amd/csrc/pose.h, DESIGN.md par. 14.  Skin: w of the output is 0; the homogeneous
+ *     divide (multiply by the rounded reciprocal) is taken whenever the blended row 3 gives anything but exactly 1; no weight is skipped for being
+ *     zero.  Morph: v = base, then v = fma( weight[j-1], target j, v ) in order; w of the output is 1.
+ *   - matrices are 16 floats, row-major (ts_mat4 / bvhmat4::cell).  joints4 is 4 uint32 per vertex, weights16 4 floats per vertex, rest16 a bvhvec4
+ *     array (w is not read).  positions12 holds (n_targets + 1) arrays of n_verts * 3 floats back to back, array 0 the base pose.
+ *   - validation: null pointers, n_verts == 0 or beyond 32 bits, n_joints == 0, misaligned device arrays (16 bytes; morph positions and weights 4), a
+ *     count that differs from the pose's, the wrong kind of pose: TBVH_E_INVALID.  Host joint indices are checked before anything is allocated:
+ *     TBVH_E_FORMAT names the first vertex with an index >= n_joints.  Device-resident joint indices are checked by the kernel: an out-of-range index
+ *     is never used as an address, that vertex is left unwritten, the status word records it and the next synchronising call returns TBVH_E_FORMAT.
+ *   - tbvh_pose_set_* are asynchronous on the context's stream; host matrices / weights are staged before the call returns (the caller may reuse
+ *     its array).  They are timed operations (tbvh_time_last_ms: the pose kernel).
+ * ---------------------------------------------------------------------------------- */
+typedef struct tbvh_pose tbvh_pose;
+int tbvh_pose_create_skin(tbvh_context* ctx, const void* rest16, uint64_t n_verts, const uint32_t* joints4, const void* weights16, uint32_t n_joints,
+                          int on_device, tbvh_pose** out);
+int tbvh_pose_create_morph(tbvh_context* ctx, const float* positions12, uint64_t n_verts, uint32_t n_targets, int on_device, tbvh_pose** out);   /* n_targets == 0: the base pose, w = 1 */
+int tbvh_pose_set_skin(tbvh_pose* pose, const float* joint_mats16, uint32_t n_joints, int on_device);
+int tbvh_pose_set_morph(tbvh_pose* pose, const float* weights, uint32_t n_targets, int on_device);
+/* The posed vertices: device memory owned by the pose, n_verts float4, valid until tbvh_pose_free, written by every tbvh_pose_set_* in stream order.
+ * Usable as verts16 of tbvh_refit (on_device = 1), as a tbvh_mesh with on_device = 1, in tbvh_build_device*, and — for a flat mesh — as the vertex
+ * array of tbvh_wavefront_render / tbvh_generate_bounce_device. */
+int tbvh_pose_vertices(tbvh_pose* pose, const void** d_verts16, uint64_t* n_verts);
+/* The per-frame call after tbvh_pose_set_*: tbvh_refit of `scene` (same context) from the posed vertices.  A scene that holds an index buffer is
+ * refitted through it (tbvh_refit_mesh with indices == NULL); any other scene is flat and needs n_verts == 3 * its triangle count (n_verts not a
+ * multiple of 3: TBVH_E_INVALID; too few: reported as by tbvh_refit, TBVH_E_FORMAT at the next synchronising call; too many: accepted, as tbvh_refit
+ * accepts a longer array — the records name the triangles they read, the vertices behind them are never looked at).  Returns as tbvh_refit does. */
+int tbvh_pose_refit(tbvh_pose* pose, tbvh_scene* scene);
+int tbvh_pose_download(tbvh_pose* pose, void* dst16, uint64_t cap_verts);   /* synchronous; reports the status word */
+/* Waits for the context's stream, then frees.  A pose belongs to its context as a scene does: tbvh_shutdown frees the poses that are still alive, and
+ * their handles are dead from then on (free a pose before its context, or not at all). */
+void tbvh_pose_free(tbvh_pose* pose);
+/* The same arithmetic on the CPU (pose.h compiled for the host), host arrays in and out, no context: for callers without a device-resident flow.
+ * out16: n_verts float4.  tbvh_host_pose_skin validates the joint indices first (TBVH_E_FORMAT, nothing written). */
+int tbvh_host_pose_skin(const void* rest16, uint64_t n_verts, const uint32_t* joints4, const void* weights16, const float* joint_mats16, uint32_t n_joints,
+                        void* out16);
+int tbvh_host_pose_morph(const float* positions12, uint64_t n_verts, uint32_t n_targets, const float* weights, void* out16);
+
 #ifdef __cplusplus
 }
 #endif

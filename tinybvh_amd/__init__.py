@@ -1275,3 +1275,115 @@ class SphereBVH(_Scene):
               "tbvh_custom_spheres_download")
         self.nodes, self.prim_idx = nodes, idx
         return nodes, idx, gathered
+
+
+# ---- skinned / morph-target meshes posed on the device (capi_pose.hip) -------------------------------------------------------------------
+def _skin_arrays(rest, joints, weights):
+    rest = np.asarray(rest, np.float32)
+    if rest.ndim == 2 and rest.shape[1] == 3:   # (n, 3) positions: the bvhvec4 array the library takes, w = 0 (not read)
+        rest = np.concatenate([rest, np.zeros((rest.shape[0], 1), np.float32)], 1)
+    rest = np.ascontiguousarray(rest, np.float32).reshape(-1, 4)
+    joints = np.ascontiguousarray(joints, np.uint32).reshape(-1, 4)
+    weights = np.ascontiguousarray(weights, np.float32).reshape(-1, 4)
+    assert rest.shape[0] == joints.shape[0] == weights.shape[0], "rest, joints and weights: one row of 4 per vertex"
+    return rest, joints, weights
+
+
+def host_pose_skin(rest, joints, weights, joint_mats) -> np.ndarray:
+    """Mesh::SetPose( skin ) on the CPU (tbvh_host_pose_skin): the (n_verts, 4) posed vertices, w = 0.  joint_mats: (n_joints, 16) or (n_joints, 4, 4),
+    row-major."""
+    rest, joints, weights = _skin_arrays(rest, joints, weights)
+    mats = np.ascontiguousarray(joint_mats, np.float32).reshape(-1, 16)
+    out = np.zeros((rest.shape[0], 4), np.float32)
+    check(lib.tbvh_host_pose_skin(_ptr(rest), rest.shape[0], _ptr(joints), _ptr(weights), _ptr(mats), mats.shape[0], _ptr(out)), "tbvh_host_pose_skin")
+    return out
+
+
+def host_pose_morph(positions, weights) -> np.ndarray:
+    """Mesh::SetPose( weights ) on the CPU (tbvh_host_pose_morph): positions (n_targets + 1, n_verts, 3), pose 0 the base; the (n_verts, 4) posed
+    vertices, w = 1."""
+    pos = np.ascontiguousarray(positions, np.float32)
+    assert pos.ndim == 3 and pos.shape[2] == 3, "positions: (n_targets + 1, n_verts, 3)"
+    w = np.ascontiguousarray(weights, np.float32).reshape(-1)
+    out = np.zeros((pos.shape[1], 4), np.float32)
+    check(lib.tbvh_host_pose_morph(_ptr(pos), pos.shape[1], w.size, _ptr(w) if w.size else None, _ptr(out)), "tbvh_host_pose_morph")
+    return out
+
+
+class Pose:
+    """A skinned or morph-target mesh posed on the device (tbvh_pose_*; Mesh::SetPose of tiny_scene.h): Skin() or Morph() once, then per frame
+    SetPose( joint matrices | morph weights ) and Refit( scene )."""
+
+    def __init__(self, ctx: Context):
+        self.ctx = ctx
+        self._h = C.c_void_p()
+        self.kind = None
+        self.n_verts = 0
+
+    def Skin(self, rest, joints, weights, n_joints: int) -> "Pose":
+        """rest (n_verts, 4) or (n_verts, 3), joints (n_verts, 4) uint32, weights (n_verts, 4); n_verts counts VERTICES (shared ones once)."""
+        assert not self._h, "this Pose is already made"
+        rest, joints, weights = _skin_arrays(rest, joints, weights)
+        check(lib.tbvh_pose_create_skin(self.ctx._h, _ptr(rest), rest.shape[0], _ptr(joints), _ptr(weights), int(n_joints), 0, C.byref(self._h)), "tbvh_pose_create_skin")
+        self.kind, self.n_verts, self.n_params = "skin", rest.shape[0], int(n_joints)
+        return self
+
+    def SkinOnDevice(self, d_rest: int, d_joints: int, d_weights: int, n_verts: int, n_joints: int) -> "Pose":
+        """The same from device-resident arrays (copied; the joint indices are then checked by the kernel)."""
+        assert not self._h, "this Pose is already made"
+        check(lib.tbvh_pose_create_skin(self.ctx._h, C.c_void_p(d_rest), n_verts, C.c_void_p(d_joints), C.c_void_p(d_weights), int(n_joints), 1, C.byref(self._h)),
+              "tbvh_pose_create_skin")
+        self.kind, self.n_verts, self.n_params = "skin", int(n_verts), int(n_joints)
+        return self
+
+    def Morph(self, positions) -> "Pose":
+        """positions (n_targets + 1, n_verts, 3): pose 0 is the base."""
+        assert not self._h, "this Pose is already made"
+        pos = np.ascontiguousarray(positions, np.float32)
+        assert pos.ndim == 3 and pos.shape[2] == 3 and pos.shape[0] >= 1, "positions: (n_targets + 1, n_verts, 3)"
+        check(lib.tbvh_pose_create_morph(self.ctx._h, _ptr(pos), pos.shape[1], pos.shape[0] - 1, 0, C.byref(self._h)), "tbvh_pose_create_morph")
+        self.kind, self.n_verts, self.n_params = "morph", pos.shape[1], pos.shape[0] - 1
+        return self
+
+    def SetPose(self, params, on_device: bool = False) -> "Pose":
+        """Skin: the joint matrices, (n_joints, 16) or (n_joints, 4, 4) row-major; morph: the n_targets weights.  on_device: params is a device
+        pointer to that many.  Asynchronous; a host array may be reused on return."""
+        skin = self.kind == "skin"
+        if on_device:
+            ptr, n = C.c_void_p(int(params)), self.n_params
+        else:
+            a = np.ascontiguousarray(params, np.float32)
+            a = a.reshape(-1, 16) if skin else a.reshape(-1)
+            ptr, n = (_ptr(a) if a.size else None), a.shape[0]
+        if skin:
+            check(lib.tbvh_pose_set_skin(self._h, ptr, n, 1 if on_device else 0), "tbvh_pose_set_skin")
+        else:
+            check(lib.tbvh_pose_set_morph(self._h, ptr, n, 1 if on_device else 0), "tbvh_pose_set_morph")
+        return self
+
+    def Refit(self, scene: "_Scene") -> "Pose":
+        """tbvh_pose_refit: refit `scene` from the posed vertices (through the scene's own index buffer when it holds one)."""
+        check(lib.tbvh_pose_refit(self._h, scene._h), "tbvh_pose_refit")
+        return self
+
+    def Vertices(self):
+        """(device pointer of the posed vertices, n_verts)"""
+        p = C.c_void_p(); n = C.c_uint64(0)
+        check(lib.tbvh_pose_vertices(self._h, C.byref(p), C.byref(n)), "tbvh_pose_vertices")
+        return p.value, int(n.value)
+
+    def Download(self) -> np.ndarray:
+        out = np.zeros((self.n_verts, 4), np.float32)
+        check(lib.tbvh_pose_download(self._h, _ptr(out), self.n_verts), "tbvh_pose_download")
+        return out
+
+    def free(self):
+        if self._h and self.ctx._h:   # (a closed context has freed its poses itself: tbvh_shutdown)
+            lib.tbvh_pose_free(self._h)
+        self._h = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass

@@ -159,6 +159,17 @@ SYMBOLS = {
     "tbvh_intersect_spheres_mesh": (_i, [_vp, _vp, _u64, C.POINTER(Mesh), _vp]),
     "tbvh_intersect_spheres_mesh_device": (_i, [_vp, _vp, _u64, C.POINTER(Mesh), _vp]),
     "tbvh_flatten_mesh_device": (_i, [_vp, C.POINTER(Mesh), _vp]),
+    # skinned / morph-target meshes posed on the device (capi_pose.hip)
+    "tbvh_pose_create_skin": (_i, [_vp, _vp, _u64, _vp, _vp, _u32, _i, _pp]),
+    "tbvh_pose_create_morph": (_i, [_vp, _vp, _u64, _u32, _i, _pp]),
+    "tbvh_pose_set_skin": (_i, [_vp, _vp, _u32, _i]),
+    "tbvh_pose_set_morph": (_i, [_vp, _vp, _u32, _i]),
+    "tbvh_pose_vertices": (_i, [_vp, _pp, C.POINTER(_u64)]),
+    "tbvh_pose_refit": (_i, [_vp, _vp]),
+    "tbvh_pose_download": (_i, [_vp, _vp, _u64]),
+    "tbvh_pose_free": (None, [_vp]),
+    "tbvh_host_pose_skin": (_i, [_vp, _u64, _vp, _vp, _vp, _u32, _vp]),
+    "tbvh_host_pose_morph": (_i, [_vp, _u64, _u32, _vp, _vp]),
 }
 
 

@@ -121,6 +121,7 @@ struct tbvh_context {
     std::vector<PinnedRange> pinned;
     DevBuf<void> binScratch;      // tbvh_bin_rays_device
     std::vector<tbvh_scene*> scenes;
+    std::vector<struct tbvh_pose*> poses;   // (capi_pose.hip) the poses made on this context: tbvh_shutdown frees those the caller has not
 };
 
 // Which schedule runs COHERENT batches of a two-flavor launch on this scene: the deferred-triangles + gated schedule on a third more waves
@@ -376,4 +377,5 @@ int refitDeviceSource(tbvh_scene* s, const tbvh::MeshSrc& src);        // (capi_
 int hostBuildImpl(const tbvh::HostMesh& mesh, uint64_t nTris, int layout, const tbvh_build_params* p, tbvh_hostbvh** out);   // (capi_host.hip) tbvh_host_build / _mesh
 int checkSphereScene(tbvh_scene* s, const char* who);   // (capi_sphere.hip) the refusals a sphere query makes before it looks at anything else
 int launchSpheres(tbvh_scene* s, const float4* dSpheres, uint64_t n, const tbvh::MeshSrc& verts, uint8_t* dHit);   // (capi_sphere.hip)
+void freePosesOf(tbvh_context* c);   // (capi_pose.hip) tbvh_shutdown: the context's stream is idle, its device current
 }  // namespace tbvh_capi

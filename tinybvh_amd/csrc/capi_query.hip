@@ -466,6 +466,10 @@ int checkStatus(tbvh_context* c) {
         hipMemsetAsync(c->status, 0, 4, c->stream);
         return fail(TBVH_E_FORMAT, "mesh: a vertex index of a device-resident index buffer is not a vertex (index >= n_verts)");
     }
+    if (st & kStatusPoseJoint) {
+        hipMemsetAsync(c->status, 0, 4, c->stream);
+        return fail(TBVH_E_FORMAT, "pose: a joint index of a device-resident joint array is not a joint (index >= n_joints); that vertex was not written");
+    }
     return 0;
 }
 }  // namespace tbvh_capi

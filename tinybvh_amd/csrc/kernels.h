@@ -141,6 +141,13 @@ void launch_pack_hits(const RayRec* rays, uint32_t* out, uint64_t n, hipStream_t
 // (kernels_mesh.hip) every kernel that reads vertices takes a MeshSrc (mesh_source.h): flat 3 x float4 per triangle, or indexed / strided
 void launch_gather_tris(const uint32_t* primIdx, const MeshSrc& verts, float4* out, uint64_t nIdx, uint32_t* status, hipStream_t s);
 void launch_flatten_mesh(const MeshSrc& verts, float4* out, uint32_t* status, hipStream_t s);   // 3 float4 per triangle, in triangle order
+// (kernels_pose.hip) Mesh::SetPose on the device, one vertex per lane through pose.h: skin (rest16, joints4, weights16: one float4 / uint4 per vertex;
+// mats: 4 float4 per joint; a vertex with a joint index >= nJoints is left unwritten and status |= kStatusPoseJoint) and morph (positions12: nTargets + 1
+// arrays of nVerts * 3 floats)
+constexpr uint32_t kStatusPoseJoint = 64u;
+void launch_pose_skin(const float4* rest16, const uint4* joints4, const float4* weights16, const float4* mats, uint32_t nJoints, float4* out, uint64_t nVerts,
+                      uint32_t* status, hipStream_t s);
+void launch_pose_morph(const float* positions12, const float* weights, uint32_t nTargets, float4* out, uint64_t nVerts, hipStream_t s);
 
 // ray generators (kernels_raygen.hip)
 struct CameraArgs {
