@@ -108,6 +108,12 @@ public:
         const tbvh_mesh m = MeshOf(verts, nullptr);
         Check(tbvh_refit_mesh(s, &m), "tbvh_refit_mesh");
     }
+    // BVHBase::SetOpacityMicroMaps( maps, N ) (tiny_bvh.h:823-826): N x N bits per triangle, (N * N + 31) / 32 words each, copied to the device; honoured by
+    // Intersect and IsOccluded, also of the TLASes over this scene.  maps == nullptr or N == 0 removes them.
+    void SetOpacityMicroMaps(const uint32_t* maps, uint32_t N, size_t triCount) { Check(tbvh_set_opacity_micromaps(s, maps, N, triCount, 0), "tbvh_set_opacity_micromaps"); }
+    // Mesh::CreateOpacityMicroMaps( N ) of tiny_scene.h followed by SetOpacityMicroMaps, on the device: the maps are baked from UVs and alpha textures into the
+    // buffer the scene then owns (tinybvh_amd.h: tbvh_omm_source; N a power of two from 1 to 64)
+    void BakeOpacityMicroMaps(const tbvh_omm_source& source, uint32_t N = 32) { Check(tbvh_bake_set_opacity_micromaps(s, &source, N), "tbvh_bake_set_opacity_micromaps"); }
     // BVH::IntersectSphere( pos, r ) batched (tiny_bvh.h:3140-3200; tiny_bvh_collide.cpp:169): hit[i] = 1 if sphere i = {x, y, z, r} touches a
     // triangle; verts = the scene's bvhvec4 vertex array, 3 per triangle, as Refit takes it.  BLAS scenes of the three GPU layouts only.
     void IntersectSpheres(const tinybvh::bvhvec4* spheres, size_t n, const tinybvh::bvhvec4* verts, size_t triCount, uint8_t* hit) {

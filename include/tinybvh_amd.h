@@ -833,6 +833,56 @@ int tbvh_host_pose_skin(const void* rest16, uint64_t n_verts, const uint32_t* jo
                         void* out16);
 int tbvh_host_pose_morph(const float* positions12, uint64_t n_verts, uint32_t n_targets, const float* weights, void* out16);
 
+/* ----------------------------------------------------------------------------------
+ * opacity micromaps baked from alpha textures on the device — Mesh::CreateOpacityMicroMaps( N ) of tiny_scene.h (1679-1744), the producer of what
+ * tbvh_set_opacity_micromaps consumes: for every triangle a 4N x 4N grid of barycentric samples (those inside the triangle: (4N - 1) * 2N), the corner
+ * UVs interpolated, one texel fetched per sample, and the micro-triangle's bit set when the texel's alpha (bits 24-31) is above 2.  Output:
+ * (N * N + 31) / 32 words per triangle, triangle i's first word at i * that — the layout tbvh_set_opacity_micromaps takes.  Texture decoding, mips,
+ * filtering, the second UV layer, HDR textures (the reference treats them as opaque: pass TBVH_OMM_NO_TEXTURE), materials and the scene graph stay with
+ * the caller.
+ *   - the arithmetic is the reference's, float operation for float operation, as its build (g++ -O3 -mavx2 -mfma) performs it: tinybvh_amd/csrc/omm.h,
+ *     DESIGN.md par. 15.  UVs wrap (t - floorf( t )), texel coordinates are clamped to the texture on both sides.  A triangle without a texture gets all
+ *     its words 0xFFFFFFFF (the padding bits of the last word included, as the reference's memset( 255 )); a textured triangle's unused high bits are 0.
+ *   - N is a power of two from 1 to 64; anything else is TBVH_E_INVALID.  For these N the sample grid and the bit index are exact in fp32 and a sample
+ *     never lands outside its triangle's words; for other N the reference's own index can reach N * N by rounding and write past them.
+ *   - a non-finite UV: the reference converts a NaN to int (undefined) and indexes with it; here the triangle's bits are unspecified and nothing outside
+ *     the texture is read.
+ *   - validation: a null source, uv, textures (with n_textures > 0) or output, n_tris == 0 or beyond 32 bits, n_uv == 0 or beyond 32 bits, fewer than
+ *     3 * n_tris UVs without indices, a stride below 8 or not a multiple of 4, a misaligned uv / indices / tri_texture / texels pointer (4 bytes), a
+ *     texture with null texels or a zero (or beyond 2^31 - 1) width or height, tri_texture == NULL with n_textures == 0: TBVH_E_INVALID.  Host-resident
+ *     arrays are checked before anything is allocated or launched: TBVH_E_INVALID names the first triangle with an index >= n_uv, or with a texture
+ *     index >= n_textures that is not TBVH_OMM_NO_TEXTURE.  Device-resident arrays are checked by the kernel, which never reads outside the arrays it was
+ *     given: a bad vertex index is clamped to the last UV, a bad texture index means no texture, the status word records either and the next
+ *     synchronising call returns TBVH_E_FORMAT (tbvh_bake_set_opacity_micromaps is one: it then installs nothing).
+ * ---------------------------------------------------------------------------------- */
+#define TBVH_OMM_NO_TEXTURE 0xFFFFFFFFu
+typedef struct tbvh_alpha_texture {   /* as Texture::idata: one uint32 per texel, alpha in bits 24-31, row-major, row 0 first */
+    const uint32_t* texels;
+    uint32_t width, height;
+} tbvh_alpha_texture;
+typedef struct tbvh_omm_source {
+    const void* uv;                       /* two floats (u, v) per vertex, uv_stride_bytes apart */
+    uint64_t n_uv;
+    uint32_t uv_stride_bytes;             /* >= 8, a multiple of 4 */
+    uint32_t on_device;                   /* where uv, indices, tri_texture and every texels pointer point: 0 host, 1 device memory */
+    const uint32_t* indices;              /* three per triangle; NULL: triangle i has corners 3i, 3i + 1, 3i + 2 */
+    uint64_t n_tris;
+    const uint32_t* tri_texture;          /* one per triangle, an index into textures or TBVH_OMM_NO_TEXTURE; NULL: every triangle uses texture 0 */
+    const tbvh_alpha_texture* textures;   /* the descriptor array itself is always host memory */
+    uint32_t n_textures;
+} tbvh_omm_source;
+/* n_tris * ((N * N + 31) / 32) words into d_maps_out (device memory, 4-byte aligned).  A timed operation (tbvh_time_last_ms: the bake kernel).
+ * Asynchronous on the context's stream when the source is device-resident; a host-resident source is staged and the call returns when the maps are
+ * written (the caller's arrays are free on return either way). */
+int tbvh_bake_opacity_micromaps(tbvh_context* ctx, const tbvh_omm_source* src, uint32_t N, uint32_t* d_maps_out);
+/* The same, baked straight into the buffer the scene then owns — no host round trip, no copy — and installed as tbvh_set_opacity_micromaps installs
+ * maps: the scene's derived copies and every TLAS over the BLAS see them, the previous maps go.  src->n_tris is the scene's triangle count as in
+ * tbvh_set_opacity_micromaps.  Refuses what that call refuses (BVH_DOUBLE, VOXELSET and sphere scenes, a TLAS).  Synchronous. */
+int tbvh_bake_set_opacity_micromaps(tbvh_scene* blas, const tbvh_omm_source* src, uint32_t N);
+/* The same arithmetic on the CPU (omm.h compiled for the host), host arrays in and out (src->on_device must be 0), no context, one thread: for callers
+ * without a device flow.  maps_out: n_tris * ((N * N + 31) / 32) words; nothing is written when the source is refused. */
+int tbvh_host_bake_opacity_micromaps(const tbvh_omm_source* src, uint32_t N, uint32_t* maps_out);
+
 #ifdef __cplusplus
 }
 #endif

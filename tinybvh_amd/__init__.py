@@ -15,7 +15,7 @@ import os
 import numpy as np
 
 from . import _capi
-from ._capi import BuildParams, Camera, Mesh, TbvhError, check, lib
+from ._capi import AlphaTexture, BuildParams, Camera, Mesh, OmmSource, TbvhError, check, lib
 
 LAYOUT_BVH2_WALD = 1
 LAYOUT_BVH_DOUBLE = 3
@@ -409,6 +409,13 @@ class _Scene:
         assert m.size % wpt == 0
         check(lib.tbvh_set_opacity_micromaps(self._h, _ptr(m), N, m.size // wpt, 0), "tbvh_set_opacity_micromaps")
         return self
+
+    def BakeOpacityMicroMaps(self, uv, textures, N: int = 32, indices=None, tri_texture=None):
+        """Mesh::CreateOpacityMicroMaps( N ) of tiny_scene.h on the device, installed on this scene without a host round trip (tbvh_bake_set_opacity_micromaps):
+        uv, textures, indices, tri_texture as bake_opacity_micromaps takes them, or an OmmSource made by device_omm_source()."""
+        src, keep = _omm_source(uv, textures, indices, tri_texture)
+        check(lib.tbvh_bake_set_opacity_micromaps(self._h, C.byref(src), N), "tbvh_bake_set_opacity_micromaps")
+        del keep
 
     def download_blobs(self):
         """(nodes, triangle records) as (n, 4) uint32 arrays of 16-byte blocks, read back from the device."""
@@ -1275,6 +1282,91 @@ class SphereBVH(_Scene):
               "tbvh_custom_spheres_download")
         self.nodes, self.prim_idx = nodes, idx
         return nodes, idx, gathered
+
+
+# ---- opacity micromaps baked from alpha textures (capi_omm.hip) ---------------------------------------------------------------------------
+OMM_NO_TEXTURE = 0xFFFFFFFF
+
+
+def _alpha_texels(tex) -> np.ndarray:
+    """(h, w) uint32 texels, alpha in bits 24-31, from an (h, w) uint32 array (used in place when packed) or an (h, w, 4) uint8 RGBA array"""
+    t = np.asarray(tex)
+    if t.ndim == 3 and t.shape[2] == 4 and t.dtype == np.uint8:
+        return np.ascontiguousarray(t).view("<u4").reshape(t.shape[0], t.shape[1])   # (bytes R, G, B, A: A is the top byte of the little-endian word)
+    assert t.ndim == 2 and t.dtype == np.uint32, "a texture: (h, w) uint32 or (h, w, 4) uint8"
+    return np.ascontiguousarray(t)
+
+
+def device_omm_source(d_uv: int, n_uv: int, n_tris: int, textures, d_indices: int = 0, d_tri_texture: int = 0, uv_stride_bytes: int = 8) -> OmmSource:
+    """A tbvh_omm_source whose arrays are device memory; textures: a list of (device pointer, width, height).  Pass it as `uv` of the bake calls."""
+    arr = (AlphaTexture * max(len(textures), 1))(*[AlphaTexture(C.c_void_p(int(p)), int(w), int(h)) for p, w, h in textures])
+    src = OmmSource(C.c_void_p(int(d_uv)), int(n_uv), int(uv_stride_bytes), 1, C.c_void_p(int(d_indices)) if d_indices else None, int(n_tris),
+                    C.c_void_p(int(d_tri_texture)) if d_tri_texture else None, arr, len(textures))
+    src._keep = arr
+    return src
+
+
+def _omm_source(uv, textures=None, indices=None, tri_texture=None):
+    """(tbvh_omm_source, the arrays it points into) for host arrays: uv any float32 array of shape (n_uv, k >= 2) whose row stride is a multiple of 4 — the
+    stride is ndarray.strides[0], so interleaved[:, 3:5] is used in place —, textures one texture or a list of them ((h, w) uint32 or (h, w, 4) uint8 RGBA),
+    indices (n_tris, 3) or flat uint32 or None (triangle i = UVs 3i, 3i + 1, 3i + 2), tri_texture (n_tris,) uint32 (OMM_NO_TEXTURE: opaque) or None (texture 0).
+    An OmmSource made by device_omm_source() passes through."""
+    if isinstance(uv, OmmSource):
+        assert textures is None and indices is None and tri_texture is None, "a device_omm_source() carries its own arrays"
+        return uv, ()
+    v = np.asarray(uv)
+    if v.dtype != np.float32 or v.ndim != 2 or v.shape[1] < 2 or v.strides[1] != 4 or v.strides[0] % 4 or v.strides[0] < 8:
+        v = np.ascontiguousarray(v, np.float32)
+        assert v.ndim == 2 and v.shape[1] >= 2, "uv: (n_uv, k >= 2) float32"
+    if isinstance(textures, np.ndarray) and (textures.ndim == 2 or (textures.ndim == 3 and textures.dtype == np.uint8)):
+        textures = [textures]
+    tex = [_alpha_texels(t) for t in (textures or [])]
+    arr = (AlphaTexture * max(len(tex), 1))(*[AlphaTexture(C.c_void_p(t.ctypes.data), t.shape[1], t.shape[0]) for t in tex])
+    idx = tt = None
+    if indices is not None:
+        idx = np.ascontiguousarray(indices, np.uint32).reshape(-1)
+        assert idx.size % 3 == 0
+        n_tris = idx.size // 3
+    else:
+        n_tris = v.shape[0] // 3
+    if tri_texture is not None:
+        tt = np.ascontiguousarray(tri_texture, np.uint32).reshape(-1)
+        assert tt.size == n_tris, "tri_texture: one per triangle"
+    src = OmmSource(C.c_void_p(v.ctypes.data), v.shape[0], v.strides[0], 0, None if idx is None else C.c_void_p(idx.ctypes.data), n_tris,
+                    None if tt is None else C.c_void_p(tt.ctypes.data), arr, len(tex))
+    return src, (v, idx, tt, tex, arr)
+
+
+def omm_words(N: int) -> int:
+    return (N * N + 31) // 32
+
+
+def host_bake_opacity_micromaps(uv, textures, N: int = 32, indices=None, tri_texture=None) -> np.ndarray:
+    """Mesh::CreateOpacityMicroMaps( N ) on the CPU (tbvh_host_bake_opacity_micromaps): the (n_tris, (N * N + 31) // 32) uint32 words."""
+    src, keep = _omm_source(uv, textures, indices, tri_texture)
+    out = np.zeros((int(src.n_tris), omm_words(N) if N > 0 else 1), np.uint32)
+    check(lib.tbvh_host_bake_opacity_micromaps(C.byref(src), N, _ptr(out)), "tbvh_host_bake_opacity_micromaps")
+    del keep
+    return out
+
+
+def bake_opacity_micromaps(ctx: "Context", uv, textures=None, N: int = 32, indices=None, tri_texture=None, d_out: int = 0):
+    """The same on the device (tbvh_bake_opacity_micromaps).  d_out == 0: the words come back as an (n_tris, words) array; otherwise they stay in device memory at
+    d_out (asynchronous for a device_omm_source()) and nothing is returned."""
+    src, keep = _omm_source(uv, textures, indices, tri_texture)
+    if d_out:
+        check(lib.tbvh_bake_opacity_micromaps(ctx._h, C.byref(src), N, C.c_void_p(int(d_out))), "tbvh_bake_opacity_micromaps")
+        del keep
+        return None
+    out = np.zeros((int(src.n_tris), omm_words(N) if N > 0 else 1), np.uint32)
+    d = ctx.malloc(max(out.nbytes, 4))
+    try:
+        check(lib.tbvh_bake_opacity_micromaps(ctx._h, C.byref(src), N, C.c_void_p(d)), "tbvh_bake_opacity_micromaps")
+        ctx.from_device(out, d)
+    finally:
+        ctx.free(d)
+    del keep
+    return out
 
 
 # ---- skinned / morph-target meshes posed on the device (capi_pose.hip) -------------------------------------------------------------------

@@ -26,6 +26,15 @@ class Mesh(C.Structure):   # tbvh_mesh
                 ("indices", C.c_void_p), ("n_tris", C.c_uint64)]
 
 
+class AlphaTexture(C.Structure):   # tbvh_alpha_texture
+    _fields_ = [("texels", C.c_void_p), ("width", C.c_uint32), ("height", C.c_uint32)]
+
+
+class OmmSource(C.Structure):   # tbvh_omm_source
+    _fields_ = [("uv", C.c_void_p), ("n_uv", C.c_uint64), ("uv_stride_bytes", C.c_uint32), ("on_device", C.c_uint32), ("indices", C.c_void_p),
+                ("n_tris", C.c_uint64), ("tri_texture", C.c_void_p), ("textures", C.POINTER(AlphaTexture)), ("n_textures", C.c_uint32)]
+
+
 class Camera(C.Structure):
     _fields_ = [("eye", C.c_float * 3), ("p1", C.c_float * 3), ("p2", C.c_float * 3), ("p3", C.c_float * 3),
                 ("width", _u32), ("height", _u32), ("spp_x", _u32), ("spp_y", _u32)]
@@ -170,6 +179,10 @@ SYMBOLS = {
     "tbvh_pose_free": (None, [_vp]),
     "tbvh_host_pose_skin": (_i, [_vp, _u64, _vp, _vp, _vp, _u32, _vp]),
     "tbvh_host_pose_morph": (_i, [_vp, _u64, _u32, _vp, _vp]),
+    # opacity micromaps baked from alpha textures (capi_omm.hip)
+    "tbvh_bake_opacity_micromaps": (_i, [_vp, C.POINTER(OmmSource), _u32, _vp]),
+    "tbvh_bake_set_opacity_micromaps": (_i, [_vp, C.POINTER(OmmSource), _u32]),
+    "tbvh_host_bake_opacity_micromaps": (_i, [C.POINTER(OmmSource), _u32, _vp]),
 }
 
 

@@ -122,6 +122,13 @@ struct tbvh_context {
     DevBuf<void> binScratch;      // tbvh_bin_rays_device
     std::vector<tbvh_scene*> scenes;
     std::vector<struct tbvh_pose*> poses;   // (capi_pose.hip) the poses made on this context: tbvh_shutdown frees those the caller has not
+    // (capi_omm.hip) the texture descriptors of a bake go up through a pinned area, in stream order, into ommDesc: a device-resident bake stays asynchronous;
+    // the area is reused once the previous bake's copy has left it (ommEv)
+    DevBuf<void> ommDesc;
+    void* ommPin = nullptr;
+    size_t ommPinBytes = 0;
+    hipEvent_t ommEv = nullptr;
+    bool ommPinUsed = false;
 };
 
 // Which schedule runs COHERENT batches of a two-flavor launch on this scene: the deferred-triangles + gated schedule on a third more waves
@@ -377,5 +384,11 @@ int refitDeviceSource(tbvh_scene* s, const tbvh::MeshSrc& src);        // (capi_
 int hostBuildImpl(const tbvh::HostMesh& mesh, uint64_t nTris, int layout, const tbvh_build_params* p, tbvh_hostbvh** out);   // (capi_host.hip) tbvh_host_build / _mesh
 int checkSphereScene(tbvh_scene* s, const char* who);   // (capi_sphere.hip) the refusals a sphere query makes before it looks at anything else
 int launchSpheres(tbvh_scene* s, const float4* dSpheres, uint64_t n, const tbvh::MeshSrc& verts, uint8_t* dHit);   // (capi_sphere.hip)
+// (capi_scene.hip) the two halves of tbvh_set_opacity_micromaps, for tbvh_bake_set_opacity_micromaps (capi_omm.hip), which fills the buffer in place:
+// room for nTris maps of N x N bits plus the padding the traversal's index may read (cleared, on the context's stream), and the swap that makes a filled
+// buffer the scene's maps (N == 0 with an empty buffer: none) — derived copies and the TLASes over the scene follow, the old maps go
+int allocOpacityMaps(tbvh_context* c, uint32_t N, uint64_t nTris, const char* who, DevBuf<uint32_t>& fresh, uint64_t* wordsOut);
+int installOpacityMaps(tbvh_scene* s, DevBuf<uint32_t>&& fresh, uint32_t N);
+void freeOmmStagingOf(tbvh_context* c);   // (capi_omm.hip) tbvh_shutdown: the pinned area and the event of the texture-descriptor upload
 void freePosesOf(tbvh_context* c);   // (capi_pose.hip) tbvh_shutdown: the context's stream is idle, its device current
 }  // namespace tbvh_capi

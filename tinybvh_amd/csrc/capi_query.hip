@@ -470,6 +470,10 @@ int checkStatus(tbvh_context* c) {
         hipMemsetAsync(c->status, 0, 4, c->stream);
         return fail(TBVH_E_FORMAT, "pose: a joint index of a device-resident joint array is not a joint (index >= n_joints); that vertex was not written");
     }
+    if (st & kStatusOmmIndex) {
+        hipMemsetAsync(c->status, 0, 4, c->stream);
+        return fail(TBVH_E_FORMAT, "opacity micromap bake: a device-resident index is not a UV (>= n_uv; clamped) or a texture index is not a texture (>= n_textures; taken as none)");
+    }
     return 0;
 }
 }  // namespace tbvh_capi

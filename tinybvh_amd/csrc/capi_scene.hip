@@ -842,23 +842,37 @@ int tbvh_set_opacity_micromaps(tbvh_scene* s, const uint32_t* mapData, uint32_t 
     const bool clear = !mapData || N == 0;
     if (!clear && (N > 1024 || nTris == 0)) return fail(TBVH_E_INVALID, "tbvh_set_opacity_micromaps: N = %u, %llu triangles", N, (unsigned long long)nTris);
     DevBuf<uint32_t> fresh;
-    uint64_t freshBytes = 0;
     if (!clear) {
-        const uint64_t wordsPerTri = ((uint64_t)N * N + 31) >> 5, words = wordsPerTri * nTris;
-        // the reference's index can run one row past the map when u + v == 1 exactly (tiny_bvh.h:8518-8519): keep that read inside the allocation
-        const uint64_t pad = (((uint64_t)N + 1) * (N + 1) + 63) >> 5;
-        freshBytes = (words + pad) * 4;
-        if (fresh.alloc(words + pad) != hipSuccess) { (void)hipGetLastError(); return fail(TBVH_E_NOMEM, "tbvh_set_opacity_micromaps: %llu bytes of device memory", (unsigned long long)freshBytes); }
-        hipError_t e = hipMemsetAsync(fresh + words, 0, pad * 4, c->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(fresh, mapData, words * 4, onDevice ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, c->stream);
+        uint64_t words = 0;
+        if (int r = allocOpacityMaps(c, N, nTris, "tbvh_set_opacity_micromaps", fresh, &words)) return r;
+        hipError_t e = hipMemcpyAsync(fresh, mapData, words * 4, onDevice ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, c->stream);
         if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
         if (e != hipSuccess) return fail(TBVH_E_HIP, "tbvh_set_opacity_micromaps: copying the maps failed: %s", hipGetErrorString(e));
     }
+    return installOpacityMaps(s, std::move(fresh), clear ? 0u : N);
+}
+
+extern "C++" {
+namespace tbvh_capi {
+int allocOpacityMaps(tbvh_context* c, uint32_t N, uint64_t nTris, const char* who, DevBuf<uint32_t>& fresh, uint64_t* wordsOut) {
+    const uint64_t wordsPerTri = ((uint64_t)N * N + 31) >> 5, words = wordsPerTri * nTris;
+    // the reference's index can run one row past the map when u + v == 1 exactly (tiny_bvh.h:8518-8519): keep that read inside the allocation
+    const uint64_t pad = (((uint64_t)N + 1) * (N + 1) + 63) >> 5;
+    if (fresh.alloc(words + pad) != hipSuccess) { (void)hipGetLastError(); return fail(TBVH_E_NOMEM, "%s: %llu bytes of device memory", who, (unsigned long long)((words + pad) * 4)); }
+    const hipError_t e = hipMemsetAsync(fresh + words, 0, pad * 4, c->stream);
+    if (e != hipSuccess) return fail(TBVH_E_HIP, "%s: clearing the maps' padding failed: %s", who, hipGetErrorString(e));
+    *wordsOut = words;
+    return 0;
+}
+
+int installOpacityMaps(tbvh_scene* s, DevBuf<uint32_t>&& fresh, uint32_t N) {
+    tbvh_context* c = s->ctx;
     HIP_TRY(hipStreamSynchronize(c->stream));   // no query may still read the old maps
+    const uint64_t freshBytes = fresh.count() * 4;
     DevBuf<uint32_t> old = std::move(s->opmapOwn);
     const uint64_t oldBytes = s->opmapBytes;
     s->opmapOwn = std::move(fresh);
-    s->opmap = s->opmapOwn; s->opmapN = clear ? 0u : N; s->opmapBytes = freshBytes;
+    s->opmap = s->opmapOwn; s->opmapN = N; s->opmapBytes = freshBytes;
     s->bytes += freshBytes; s->bytes -= oldBytes;
     if (s->wide) { s->wide->opmap = s->opmap; s->wide->opmapN = s->opmapN; }   // (shared, owned here)
     if (s->wide4) { s->wide4->opmap = s->opmap; s->wide4->opmapN = s->opmapN; }
@@ -866,6 +880,8 @@ int tbvh_set_opacity_micromaps(tbvh_scene* s, const uint32_t* mapData, uint32_t 
     if (r != 0) (void)old.release();   // (a failed refresh may have left a descriptor on the old maps: leak them rather than dangle)
     return r;
 }
+}  // namespace tbvh_capi
+}  // extern "C++"
 
 int tbvh_scene_download(tbvh_scene* s, int which, void* dst, uint64_t capBytes, uint64_t* bytesOut) {
     TBVH_REFUSE_DOUBLE(s, "tbvh_scene_download");

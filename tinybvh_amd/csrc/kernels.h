@@ -148,6 +148,12 @@ constexpr uint32_t kStatusPoseJoint = 64u;
 void launch_pose_skin(const float4* rest16, const uint4* joints4, const float4* weights16, const float4* mats, uint32_t nJoints, float4* out, uint64_t nVerts,
                       uint32_t* status, hipStream_t s);
 void launch_pose_morph(const float* positions12, const float* weights, uint32_t nTargets, float4* out, uint64_t nVerts, hipStream_t s);
+// (kernels_omm.hip) Mesh::CreateOpacityMicroMaps on the device, one wave per triangle through omm.h: src with every pointer (the texture descriptors and
+// the texels they name included) in device memory; out: nTris * ((N * N + 31) / 32) words; N a power of two from 1 to 64.  A corner index >= nUV is clamped,
+// a texture index >= nTextures that is not the no-texture mark means no texture, and status |= kStatusOmmIndex for either.  maxBlocks: the grid's cap.
+constexpr uint32_t kStatusOmmIndex = 128u;
+struct OmmSrc;
+void launch_omm_bake(const OmmSrc& src, uint32_t N, uint32_t* out, uint32_t* status, uint32_t maxBlocks, hipStream_t s);
 
 // ray generators (kernels_raygen.hip)
 struct CameraArgs {
