@@ -325,7 +325,7 @@ def tlas_child(a, tb, R, scenes):
         mh, rh = mine["t"][: ref.shape[0]] < 1e30, ref[:, 0] < 1e30
         out.update({"cwbvh_blas_ms": float(np.mean(ms8)), "cwbvh_blas_mrays": nt / float(np.mean(ms8)) / 1e3, "ref_opencl_traverse_tlas_ms": ref_ms,
                     "ref_opencl_traverse_tlas_mrays": ref.shape[0] / ref_ms / 1e3, "ratio_cwbvh_blas": ref_ms / float(np.mean(ms8)),
-                    "cwbvh_blas_note": "closest-hit queries enter BVH8_CWBVH BLASes through their 4-wide copies (k_tlas4; capi_scene.hip: blasView) since round 6",
+                    "cwbvh_blas_note": "closest-hit queries enter BVH8_CWBVH BLASes through their 4-wide copies (k_tlas4; capi_copies.hip: blasView) since round 6",
                     "ratio_k_tlas4_bvh4_blas": ref_ms / float(np.mean(ms)), "hitmiss_diff": int((mh != rh).sum()), "opencl_device": ocl.device,
                     "ref_kernel": "traverse_tlas (traverse_tlas.cl:13-107) via wavefront2.cl Extend, BVH8_CWBVH BLAS (the configuration of tiny_bvh_gpu2.cpp), same TLAS / instances / rays"})
     except Exception as e:

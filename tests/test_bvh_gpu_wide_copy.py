@@ -1,4 +1,4 @@
-"""A BVH_GPU / BVH4_GPU scene makes an 8-wide copy of its tree at its first query (tinybvh_amd/csrc/capi_scene.hip: makeWideCopy) and its queries trace that copy: the hit records
+"""A BVH_GPU / BVH4_GPU scene makes an 8-wide copy of its tree at its first query (tinybvh_amd/csrc/capi_copies.hip: makeCopy) and its queries trace that copy: the hit records
 must be the ones the uploaded 2-wide nodes give — byte for byte under the library's tie rule (device_common.h: hit_wins), variant 1 = k_bvh2 on the
 nodes as uploaded — and the reference's own (golden vectors from the real tiny_bvh.h: BVH::Intersect, tiny_bvh.h:3222-3304).  Blobs: the reference's
 BVH_GPU::Build and BuildHQ (SBVH: clipped leaf boxes, primIdx with repeats and slack) from tests/golden, and the library's own builder; the copy
@@ -213,7 +213,7 @@ def test_tlas_any_hit_queries_enter_bvh4_blases_through_their_copies(ctx, oracle
 
 def test_tlas_enters_bvh_gpu_blases_through_their_wide_copies(ctx, oracle):
     """A TLAS over BVH_GPU BLASes (the reference's BLAS type for geometry that is refitted or rebuilt, traverse_tlas.cl:66-72) enters them through their
-    8-wide copies, made at the TLAS upload (capi_scene.hip: reclassifyTlas, blasView): the records are BVH::IntersectTLAS's either way; tbvh_set_variant(blas, 1)
+    8-wide copies, made at the TLAS upload (capi_scene.hip: reclassifyTlas, capi_copies.hip: blasView): the records are BVH::IntersectTLAS's either way; tbvh_set_variant(blas, 1)
     puts the TLAS back on the uploaded nodes, a BLAS update is followed, a BLAS freed before its TLAS lives on with its copy."""
     from test_tlas import grid_instances, oracle_tlas, check
     meshes = [scenes.blob(40_000, seed=5), scenes.soup(3_000, seed=6, extent=1.6, size=0.2)]       # a small BLAS gets its copies too when a TLAS wants them: one kernel class for the TLAS
@@ -291,7 +291,7 @@ def test_tlas_closest_hit_queries_enter_cwbvh_blases_through_4_wide_copies(ctx, 
 def test_an_update_drops_the_copies_until_the_blob_has_settled(ctx, oracle):
     """tbvh_update_* is the reference's animation flow (BVH::Refit + ConvertFrom on the host, the blob re-uploaded every frame): making the copies again costs more
     than a frame's queries gain, so an update drops them and they come back after four queries without another update — and an update that arrives soon
-    after they came back makes the scene wait four times as long (capi_internal.h: tbvh_scene::pendingCopies).  Results are right throughout."""
+    after they came back makes the scene wait four times as long (tinybvh_amd/csrc/copy_policy.h: CopyPolicy; its arithmetic alone: test_copy_policy.py).  Results are right throughout."""
     verts = scenes.blob(40_000, seed=21)
     sc = tb.BVH_GPU(ctx).Build(verts)
     h = sc.host

@@ -1,5 +1,5 @@
 """Randomised parity on the paths only LARGER inputs reach (tests/test_random_configs.py stays under 20 k triangles and 34 k rays): scenes of
-30 k .. 400 k triangles in all three layouts — BVH_GPU and BVH4_GPU scenes then trace their 8-wide copy (capi_scene.hip: makeWideCopy) — and batches of
+30 k .. 400 k triangles in all three layouts — BVH_GPU and BVH4_GPU scenes then trace their 8-wide copy (capi_copies.hip: makeCopy) — and batches of
 0.8 .. 2.2 M camera, bounce, shadow and random rays, which a scene under 48 MB probes for the wave-packet kernel while its tuner measures (capi_query.hip:
 launchCoherentFlavor).  Eight launches in a row — the tuner moves through its schedules meanwhile.
 

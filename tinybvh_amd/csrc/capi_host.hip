@@ -215,7 +215,7 @@ int tbvh_debug_wide_copy_bvh2(int layout, const void* blob, uint64_t nBlob, cons
         if (layout == TBVH_LAYOUT_BVH_GPU) {
             if (!verts16) return fail(TBVH_E_INVALID, "tbvh_debug_wide_copy_bvh2: BVH_GPU needs prim_idx and verts16, or (prim_idx NULL) the gathered records in verts16");
             if (const char* why = validate_bvh_gpu((const NodeAL*)blob, nBlob, nIdx)) return fail(TBVH_E_FORMAT, "%s", why);
-            // prim_idx == NULL: RECORD MODE, what the library itself runs (capi_scene.hip: makeCopy) — verts16 = n_idx records {v0|prim, e1, e2}
+            // prim_idx == NULL: RECORD MODE, what the library itself runs (capi_copies.hip: makeCopy) — verts16 = n_idx records {v0|prim, e1, e2}
             if (!bvh_gpu_to_bvh2((const NodeAL*)blob, nBlob, primIdx, nIdx, primIdx ? (const Vec4*)verts16 : nullptr, nTris, maxLeaf, n2, primIdx ? nullptr : (const Vec4*)verts16))
                 return fail(TBVH_E_FORMAT, "the root is a leaf");
         } else if (layout == TBVH_LAYOUT_BVH4_GPU) {

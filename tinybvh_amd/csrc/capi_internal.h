@@ -1,5 +1,5 @@
 // capi_internal.h — what the translation units behind include/tinybvh_amd.h share: the context and scene objects, the error
-// helper, and the few internal entry points that cross files (capi_context / capi_scene / capi_query / capi_wavefront / capi_host).
+// helper, and the few internal entry points that cross files (capi_context / capi_scene / capi_copies / capi_query / capi_wavefront / capi_host).
 // Not installed; nothing outside tinybvh_amd/csrc includes it.
 #pragma once
 #include "../../include/tinybvh_amd.h"
@@ -23,6 +23,7 @@
 #include <thread>
 #include <vector>
 
+#include "copy_policy.h"
 #include "dev_buf.h"
 #include "host_builder.h"
 #include "kernels.h"
@@ -30,6 +31,10 @@
 
 using namespace tbvh;
 using tbvh_capi::DevBuf;
+using tbvh_capi::CopyKind;
+using tbvh_capi::CopyPolicy;
+using tbvh_capi::kCopyWide4;
+using tbvh_capi::kCopyWide8;
 
 static_assert(kLayoutBvhGpu == TBVH_LAYOUT_BVH_GPU && kLayoutBvh4Gpu == TBVH_LAYOUT_BVH4_GPU && kLayoutCwbvh == TBVH_LAYOUT_CWBVH,
               "kernels.h and the public header agree on the layout codes");
@@ -158,21 +163,42 @@ struct CohTuner {
     int least_sampled() const;   // the schedule with the fewest samples taken or in flight
 };
 
+// The derived copies of a BLAS in ANOTHER layout, each a scene of its own that this one owns (capi_copies.hip makes, drops, refits and selects them; not
+// listed in the context's scene table).  copy8: a BVH_GPU / BVH4_GPU tree collapsed 8-wide into the BVH8_CWBVH format, made by the first query, kept current
+// by update / refit / micromap calls and traced INSTEAD of `nodes` by the queries on the scene: hit records do not depend on the layout (device_common.h:
+// hit_wins), and the compressed wide kernels trace the same rays 1.6-2.9 x faster than the 2-wide one (profiles/r06_bvh2.txt).  copy4: a BVH_GPU /
+// BVH8_CWBVH BLAS in the BVH4_GPU format, made when a TLAS is uploaded over it: under a TLAS k_tlas4 is the fastest kernel for closest hits (1000 instances,
+// camera rays: 4650 MRays/s against 4190 through BVH8_CWBVH BLASes and 3840 through BVH_GPU ones), k_tlas8 for any-hit queries (blasView).
+struct WideCopies {
+    tbvh_scene* copy8 = nullptr;
+    tbvh_scene* copy4 = nullptr;
+    bool tried8 = false, tried4 = false;   // the copy was made, or found unwanted / impossible: not tried again
+    bool tlasOnly = false;                 // copy8 is a small one made for the TLASes over this scene: the scene's own queries keep the uploaded nodes
+    CopyPolicy policy;                     // when they are dropped and come back (copy_policy.h)
+    uint8_t live() const { return (uint8_t)((copy8 ? kCopyWide8 : 0) | (copy4 ? kCopyWide4 : 0)); }
+    uint8_t pending() const { return policy.pendingCopies; }
+};
+
+// The re-layouts of a BVH8_CWBVH scene's own arrays (capi_copies.hip; launchCwbvhKernels picks among them)
+struct CwbvhLayouts {
+    DevBuf<float4> padded;       // the same nodes padded to one 128-byte line each (padCwbvhIfLarge: node arrays beyond the Infinity Cache)
+    DevBuf<float4> hybrid;       // the same nodes in surface-area priority order, the first `packed` packed, the others one per line (cwbvh_node.h: kNodeHybrid)
+    DevBuf<uint32_t> perm;       // device: position of node i in `hybrid`
+    DevBuf<float4> trisPadded;   // triangle records padded to 64 bytes
+    uint32_t packed = 0;         // (QueryArgs::hybridK)
+    bool tried = false;          // the incoherent-batch copies were built, or found impossible / unwanted: launchQuery does not try again
+    bool levelOrder = false;     // the node array is in level order (made on the device): the hybrid copy needs no renumbering
+};
+
 struct tbvh_scene {
     tbvh_context* ctx = nullptr;
     int layout = 0;
     int variant = 0;
     DevBuf<float4> nodes;      // BVH_GPU nodes / BVH4 stream / CWBVH nodes
     DevBuf<float4> tris;       // BVH_GPU gathered tris / CWBVH tris
-    DevBuf<float4> nodes128;    // CWBVH: the same nodes padded to one 128-byte line each (padCwbvhIfLarge: node arrays beyond the Infinity Cache)
-    DevBuf<float4> nodesHy;     // CWBVH: the same nodes in surface-area priority order, the first hybridK packed, the others one per line (cwbvh_node.h: kNodeHybrid)
-    DevBuf<uint32_t> hyPerm;    // device: position of node i in nodesHy
-    DevBuf<float4> tris64;      // CWBVH (experiment flag 2): triangle records padded to 64 bytes
-    uint32_t hybridK = 0;
+    CwbvhLayouts cw;
     CohTuner cohTuner[2][4];    // [any-hit][batch-size class: < 6 M, < 12 M, more rays; 3 = 768 k .. 1.5 M rays on a scene under 48 MB]: which schedule wins can depend on the batch size (the tail of a launch weighs differently)
     uint8_t cohLastClass[2] = {2, 2};   // the class of the most recent two-flavor launch (tbvh_debug_coherent_schedule reports that one)
-    bool hyTried = false;       // the incoherent-batch copies were built, or found impossible / unwanted: launchQuery does not try again
-    bool hyLevelOrder = false;  // the node array is in level order (made on the device): the hybrid copy needs no renumbering
     uint32_t nNodes = 0;
     uint64_t nNodeBlocks = 0, nTriBlocks = 0;
     uint64_t capNodeBlocks = 0, capTriBlocks = 0;   // what the allocations hold (tbvh_update_*: a re-converted blob of at most this size goes in place)
@@ -217,7 +243,7 @@ struct tbvh_scene {
     DevBuf<void> refitScratch;
     std::vector<uint32_t> b4Levels;   // BVH4_GPU: first node of every tree level in the item list (filled by the first refit)
     DevBuf<void> vertStage;           // staged vertices when the caller passes host memory (strided meshes: sized in bytes)
-    // opacity micromaps (BVHBase::SetOpacityMicroMaps): what the kernels read is a plain pointer on every scene — a derived copy (wide / wide4)
+    // opacity micromaps (BVHBase::SetOpacityMicroMaps): what the kernels read is a plain pointer on every scene — a derived copy (WideCopies)
     // shares its owner's maps —, the allocation belongs to the scene they were set on
     uint32_t* opmap = nullptr;
     DevBuf<uint32_t> opmapOwn;
@@ -225,34 +251,13 @@ struct tbvh_scene {
     uint64_t opmapBytes = 0;
     // a scene made from an INDEXED mesh (tbvh_*_mesh with indices) keeps its own device copy of the index buffer, 12 bytes per triangle, counted in
     // `bytes`: tbvh_refit_mesh with indices == NULL then means "the indices the scene holds" — the per-frame call of an animated mesh passes the
-    // shared vertices only.  The derived copies (wide / wide4) hold none: their refit is handed the owner's source.
+    // shared vertices only.  The derived copies (WideCopies) hold none: their refit is handed the owner's source.
     DevBuf<uint32_t> meshIdx;
     uint64_t meshIdxTris = 0;
     DevBuf<uint32_t> idxStage;           // staged host indices of tbvh_intersect_spheres_mesh (a per-frame query: no allocation per call)
-    // BVH_GPU / BVH4_GPU: the same tree collapsed 8-wide into the BVH8_CWBVH format (capi_scene.hip: makeCopy; made by the first query), kept current by update / refit / micromap
-    // calls and traced INSTEAD of `nodes` by the queries on this scene: hit records do not depend on the layout (device_common.h: hit_wins), and the
-    // compressed wide kernels trace the same rays 1.6-2.9 x faster than the 2-wide one (profiles/r06_bvh2.txt).  Owned by this scene, not listed in
-    // the context's scene table; TLASes over this BLAS enter it through the copies as well (capi_scene.hip: blasView).
-    tbvh_scene* wide = nullptr;
-    bool wideTried = false;      // the copy was made, or found unwanted / impossible: launchQuery does not try again
-    bool wideTlasOnly = false;   // the copy is a small one made for the TLASes over this scene: the scene's own queries keep the uploaded nodes
-    // tbvh_update_* (the reference's animation flow: BVH::Refit + ConvertFrom on the host, the blob re-uploaded) DROPS the copies — making them again costs
-    // milliseconds, more than a frame's queries gain — and they come back once the scene has answered `recopyAfter` queries without another update; an
-    // update that arrives soon after they came back quadruples that number (a blob that keeps changing ends up without copies, a blob updated once has
-    // them again after four queries).  tbvh_refit keeps the copies: it refits them in place.
-    uint8_t pendingCopies = 0;           // bit 0: the 8-wide copy, bit 1: the 4-wide one — dropped by an update, to be made again
-    uint32_t recopyAfter = 4, queriesSinceUpdate = 0;
-    bool remadeSinceUpdate = false;
-    bool blasRecopyPending = false;      // TLAS: some BLAS has pendingCopies
-    // tbvh_refit refits the copies in place (0.3-0.5 ms each for 100 k triangles) — unless fewer than kRefitKeepRays rays were traced through the scene (or the
-    // TLASes over it) since the previous refit: then the copies cost a frame more than they save and are dropped like after an update
-    uint64_t raysTraced = 0;             // rays of every query launched on this scene (a TLAS counts its own)
-    uint64_t raysAtRefit = 0;            // raysTraced of this scene + of the TLASes over it, at the previous tbvh_refit
-    bool refitSeen = false;
-    // ... and a 4-wide one (BVH4_GPU format) of a BVH_GPU / BVH8_CWBVH BLAS, made when a TLAS is uploaded over it: under a TLAS k_tlas4 is the fastest kernel for
-    // closest hits (1000 instances, camera rays: 4650 MRays/s against 4190 through BVH8_CWBVH BLASes and 3840 through BVH_GPU ones), k_tlas8 for any-hit queries
-    tbvh_scene* wide4 = nullptr;
-    bool wide4Tried = false;
+    WideCopies copies;
+    bool blasRecopyPending = false;      // TLAS: the copies of some BLAS are waiting to be made again
+    uint64_t raysTraced = 0;             // rays of every query launched on this scene (a TLAS counts its own): what a refit weighs the copies' refit against
     // a sphere BLAS that moves (capi_custom.hip: tbvh_build_device_custom_spheres / tbvh_rebuild_custom_spheres_device / tbvh_refit_custom_spheres): the
     // sphere count and the builder a rebuild repeats (an uploaded scene: LBVH, one sphere per leaf).  The build keeps its scratch in buildScratch
     // (sized for buildScratchFor spheres) and its primIdx here, the refit its pass words in refitScratch, host spheres are staged in vertStage: no
@@ -354,19 +359,31 @@ int checkStatus(tbvh_context* c);   // synchronizes the stream, turns the device
 int ensureStage(tbvh_context* c, uint64_t n);      // (capi_query.hip) the host-array staging buffers hold at least n ray records ...
 int ensureStageOcc(tbvh_context* c, uint64_t n);   // ... and n any-hit result bytes
 tbvh_scene* newScene(tbvh_context* c, int layout);
+int reclassifyTlas(tbvh_scene* t);   // (capi_scene.hip) descriptors, kernel class and wide trees of a TLAS from its BLASes as they are now
+// ---- derived copies (capi_copies.hip): WideCopies and CwbvhLayouts are made, dropped, refitted and selected there and nowhere else -----------
 uint64_t cwbvhTopologyHash(const tbvh::Vec4* nodes, uint32_t nNodes);
-int padCwbvhIfLarge(tbvh_scene* s);
-size_t hybridBytes(uint32_t nNodes, uint32_t K);
-bool wantsIncoherentCopies(const tbvh_scene* s);
-int prepareIncoherentCopies(tbvh_scene* s);
-// (capi_scene.hip) the derived copies of a BLAS: the 8-wide one of a BVH_GPU / BVH4_GPU scene (tbvh_scene::wide; made lazily, from launchQuery) and the
-// 4-wide one of a BVH_GPU / BVH8_CWBVH BLAS (tbvh_scene::wide4; closest-hit queries of the TLASes over it).  The values are the bits of pendingCopies.
-enum CopyKind { kCopyWide8 = 1, kCopyWide4 = 2 };
+int prepareIncoherentCopies(tbvh_scene* s);   // launchQuery: a probed launch on the scene (the first one builds, or finds them unwanted)
+int rederiveCwbvhLayouts(tbvh_scene* s);      // the node boxes or triangle records changed in place, the tree (s->nNodes, s->nTriBlocks) did not; asynchronous
+int resetCwbvhLayouts(tbvh_scene* s, bool levelOrder = false);   // a new tree in the scene's arrays (upload, device conversion, update): none but the padded nodes of a large one
 void freeCopy(tbvh_scene* s, CopyKind kind);
-int makeCopy(tbvh_scene* s, CopyKind kind);
-int reclassifyTlas(tbvh_scene* t);
-void dropCopiesAfterUpdate(tbvh_scene* s);   // (capi_scene.hip) tbvh_update_*: see tbvh_scene::pendingCopies
-void countQueryForRecopy(tbvh_scene* s);     // ... and the query side of it (launchQuery)   // (capi_scene.hip) descriptors, kernel class and wide trees of a TLAS from its BLASes as they are now
+void makeCopyOnce(tbvh_scene* b, CopyKind kind);   // the copy of this kind, unless it was tried before, b's layout has none or b pins its uploaded nodes (tbvh_set_variant)
+void dropCopiesAfterUpdate(tbvh_scene* s);   // tbvh_update_*: see copy_policy.h
+void countQueryForRecopy(tbvh_scene* s);     // ... and the query side of it (launchQuery)
+tbvh_scene* wideCopyForQuery(tbvh_scene* s);   // the 8-wide copy the scene's own queries run on, or nullptr: they run on s
+tbvh_scene* tunedScene(tbvh_scene* s);         // the scene whose CohTuner decides for queries on s: its 8-wide copy if it has one
+void shareOpacityMaps(tbvh_scene* s);          // the copies read the owner's maps
+int refitCopies(tbvh_scene* s, const tbvh::MeshSrc& src);   // tail of a refit of s: its copies follow in place, or go (CopyPolicy::refit)
+const tbvh_scene* blasView(const tbvh_scene* b, bool any, bool allow4 = true);   // what a TLAS traverses for BLAS b, by the kind of query
+// f(t) for each distinct TLAS t over BLAS b (usedBy holds one entry per reference), until one returns non-zero: that value, or 0
+template <class F>
+int forEachTlasOver(tbvh_scene* b, F f) {
+    for (size_t i = 0; i < b->usedBy.size(); i++) {
+        bool seen = false;
+        for (size_t k = 0; k < i; k++) seen |= b->usedBy[k] == b->usedBy[i];
+        if (!seen) if (int r = f(b->usedBy[i])) return r;
+    }
+    return 0;
+}
 // ---- vertex sources (capi_mesh.hip): tbvh_mesh of the public header -> MeshSrc of the kernels (mesh_source.h) ------------------------------
 int checkMesh(const tbvh_mesh* m, const char* who, bool indicesMayBeHeld = false);   // the header's validation rules; host indices are range-checked here, before anything is allocated
 tbvh_mesh flatMesh(const void* verts16, uint64_t nTris, int onDevice);   // what (verts16, n_tris) of the flat entry points mean
@@ -380,6 +397,8 @@ struct DeviceMesh {
 };
 int stageMesh(tbvh_context* c, const tbvh_mesh& m, DeviceMesh& out);
 int keepMeshIndices(tbvh_scene* s, const tbvh::MeshSrc& src);          // the scene's own copy of src.indices (no-op without indices); device to device, asynchronous
+// (capi_scene.hip) BVH2 on the device -> a new BVH8_CWBVH / BVH4_GPU scene; the wide copies are made by it too
+int convertDeviceImpl(tbvh_context* c, int layout, const float4* dN2, uint64_t nNodes2, const uint32_t* dIdx, uint64_t nIdx, const tbvh::MeshSrc& dV, tbvh_scene** out);
 int refitDeviceSource(tbvh_scene* s, const tbvh::MeshSrc& src);        // (capi_scene.hip) tbvh_refit / tbvh_refit_mesh once the source is on the device
 int hostBuildImpl(const tbvh::HostMesh& mesh, uint64_t nTris, int layout, const tbvh_build_params* p, tbvh_hostbvh** out);   // (capi_host.hip) tbvh_host_build / _mesh
 int checkSphereScene(tbvh_scene* s, const char* who);   // (capi_sphere.hip) the refusals a sphere query makes before it looks at anything else

@@ -287,15 +287,15 @@ static int launchCoherentFlavor(tbvh_scene* s, const QueryArgs& q, const CwbvhLa
 // Bistro stand-in, 16.7 M rays, interleaved medians (profiles/r03_ab_16m.txt): bounce rays +10 %, camera and shadow rays unchanged.
 static int launchCwbvhKernels(tbvh_scene* s, QueryArgs& q, const CwbvhLaunch& L) {
     tbvh_context* c = s->ctx;
-    const bool autoPad = s->variant == 0 && s->nodes128 != nullptr;   // nodes beyond the Infinity Cache: the padded copy (padCwbvhIfLarge)
+    const bool autoPad = s->variant == 0 && s->cw.padded != nullptr;   // nodes beyond the Infinity Cache: the padded copy (padCwbvhIfLarge)
     const uint32_t blocks7 = c->gridOverride ? 0xFFFFFFFFu : (uint32_t)c->numCUs * 28u;
     const float4* tris = s->tris;
 #ifdef TBVH_EXPERIMENTS
-    if ((c->expFlags & 2u) && s->tris64) { tris = s->tris64; q.flags |= 2u; }   // experiment: 64-byte triangle records in the ordinary kernels too
+    if ((c->expFlags & 2u) && s->cw.trisPadded) { tris = s->cw.trisPadded; q.flags |= 2u; }   // experiment: 64-byte triangle records in the ordinary kernels too
 #endif
-    const bool twoFlavors = q.probe && s->variant == 0 && ((!autoPad && s->nodesHy && s->tris64) || L.probedSmall) && !(c->expFlags & 4u);
-    if (s->variant == 90 && s->nodesHy && s->tris64) {   // diagnostic: the incoherent flavor whatever the batch (tests, tools/ab_configs.py)
-        launch_cwbvh(L.any, 0, s->nodesHy, s->tris64, q, c->status, L.blocksBase, c->stream, 13, L.small, blocks7);
+    const bool twoFlavors = q.probe && s->variant == 0 && ((!autoPad && s->cw.hybrid && s->cw.trisPadded) || L.probedSmall) && !(c->expFlags & 4u);
+    if (s->variant == 90 && s->cw.hybrid && s->cw.trisPadded) {   // diagnostic: the incoherent flavor whatever the batch (tests, tools/ab_configs.py)
+        launch_cwbvh(L.any, 0, s->cw.hybrid, s->cw.trisPadded, q, c->status, L.blocksBase, c->stream, 13, L.small, blocks7);
     } else if (s->variant == 91) {   // diagnostic: the coherent flavor (deferred triangles, gated triangle phase) whatever the batch and whatever its probe says
         QueryArgs qa = q;
         qa.probe = L.probeWords; qa.baseBlocks = 0; qa.flags |= 16u;
@@ -307,17 +307,17 @@ static int launchCwbvhKernels(tbvh_scene* s, QueryArgs& q, const CwbvhLaunch& L)
         if (L.probedSmall) {   // behind it: the scene's unprobed kernel, as launched without a probe
             QueryArgs qp = q;
             qp.probe = nullptr; qp.baseBlocks = 0;
-            launch_cwbvh(L.any, s->variant, autoPad ? s->nodes128 : s->nodes, tris, qp, c->status, L.blocks, c->stream, autoPad ? 8 : 5, L.small, blocks7);
+            launch_cwbvh(L.any, s->variant, autoPad ? s->cw.padded : s->nodes, tris, qp, c->status, L.blocks, c->stream, autoPad ? 8 : 5, L.small, blocks7);
         } else {
             // the incoherent flavor on 28 one-wave workgroups per CU when the batch fills the grid (24 is the persistent grid's size: 20 / 26 / 28 / 30 /
             // 32 per CU trace bounce rays at -4.4 / +0.6 / +0.9 / +0.5 / +0.5 %, interleaved medians of 13 rounds)
             uint32_t wX = (c->expFlags >> 8) & 0xffu;   // experiment: another number of waves per CU
             if (wX > 32u) wX = 32u;                     // (the spill area holds blocks + blocks / 3 = 32 workgroups per CU: LaneStack strides by gridDim)
             const uint32_t wB = wX ? wX : (c->gridOverride ? 0u : 28u);
-            launch_cwbvh(L.any, 0, s->nodesHy, s->tris64, q, c->status, (wB && L.blocksBase == c->blocks) ? (uint32_t)c->numCUs * wB : L.blocksBase, c->stream, 13, L.small, blocks7);
+            launch_cwbvh(L.any, 0, s->cw.hybrid, s->cw.trisPadded, q, c->status, (wB && L.blocksBase == c->blocks) ? (uint32_t)c->numCUs * wB : L.blocksBase, c->stream, 13, L.small, blocks7);
         }
     } else {
-        launch_cwbvh(L.any, s->variant, autoPad ? s->nodes128 : s->nodes, tris, q, c->status, L.blocks, c->stream, autoPad ? 8 : 5, L.small, blocks7);
+        launch_cwbvh(L.any, s->variant, autoPad ? s->cw.padded : s->nodes, tris, q, c->status, L.blocks, c->stream, autoPad ? 8 : 5, L.small, blocks7);
     }
     return 0;
 }
@@ -327,14 +327,13 @@ int launchQuery(tbvh_scene* s, RayRec* d_rays, uint64_t n, uint8_t* d_occ, bool 
     TBVH_ENTER(c);
     if (n == 0) return 0;
     s->raysTraced += n;   // (what tbvh_refit weighs the refit of a scene's copies against)
-    if (s->pendingCopies || s->blasRecopyPending) countQueryForRecopy(s);   // copies dropped by a tbvh_update_* come back once the blob has settled
-    if (!s->wideTried && !s->isTlas && s->variant == 0 && (nDev || n >= 1024u) && (s->layout == TBVH_LAYOUT_BVH_GPU || s->layout == TBVH_LAYOUT_BVH4_GPU)) makeCopy(s, kCopyWide8);   // first query of this scene (not part of its time)
-    if (s->wide && s->variant == 0 && !s->wideTlasOnly) return launchQuery(s->wide, d_rays, n, d_occ, fresh, freshTmax, nDev);   // BVH_GPU with an 8-wide copy (capi_scene.hip: makeCopy)
+    countQueryForRecopy(s);   // copies dropped by a tbvh_update_* come back once the blob has settled
+    if (!s->isTlas && (nDev || n >= 1024u)) makeCopyOnce(s, kCopyWide8);   // first query of a BVH_GPU / BVH4_GPU scene (not part of its time)
+    if (tbvh_scene* w = wideCopyForQuery(s)) return launchQuery(w, d_rays, n, d_occ, fresh, freshTmax, nDev);   // BVH_GPU / BVH4_GPU with an 8-wide copy (capi_copies.hip)
     const bool any = d_occ != nullptr;
     if (any && s->isTlas && !s->anyHitSeen && !s->blasSpheres) {   // the first IsOccluded through this TLAS (not part of its time): its BVH4_GPU and BVH_GPU BLASes are entered through 8-wide copies by any-hit queries
         s->anyHitSeen = true;
-        for (tbvh_scene* b : s->blasList)
-            if ((b->layout == TBVH_LAYOUT_BVH4_GPU || b->layout == TBVH_LAYOUT_BVH_GPU) && !b->wideTried && b->variant == 0) makeCopy(b, kCopyWide8);   // (re-classifies the TLASes over b, this one included)
+        for (tbvh_scene* b : s->blasList) makeCopyOnce(b, kCopyWide8);   // (re-classifies the TLASes over b, this one included)
         if (int r = reclassifyTlas(s)) return r;
     }
     // ray-fetch counters: two areas alternate; the kernels of this launch zero the other area for the next one.  After anything that went wrong
@@ -348,7 +347,7 @@ int launchQuery(tbvh_scene* s, RayRec* d_rays, uint64_t n, uint8_t* d_occ, bool 
     q.spill = c->spill; q.counter = poolArea; q.counterNext = (uint32_t*)c->pool + (size_t)(c->poolCur ^ 1) * poolWords; q.poolParts = c->poolParts;
     q.stats = c->counter + 8;
     q.fresh = fresh ? 1u : 0u; q.freshTmax = freshTmax; q.nRaysDev = nDev; q.omm = Omm{s->opmap, s->opmapN};
-    q.probe = nullptr; q.baseBlocks = 0; q.hybridK = s->hybridK; q.flags = 0u;
+    q.probe = nullptr; q.baseBlocks = 0; q.hybridK = s->cw.packed; q.flags = 0u;
 #ifdef TBVH_EXPERIMENTS
     q.flags = c->expFlags & 0x3FF0001u;
 #endif
@@ -369,8 +368,8 @@ int launchQuery(tbvh_scene* s, RayRec* d_rays, uint64_t n, uint8_t* d_occ, bool 
     const uint32_t lo = (uint32_t)c->numCUs * 4u;
     uint32_t blocks = (uint32_t)(want < lo ? lo : (want > cap ? cap : want));
     const bool probed = !s->isTlas && !small && blobBytes <= (384ull << 20) && s->layout == TBVH_LAYOUT_CWBVH && n >= (1ull << 21) && (s->variant == 0 || s->variant == 88) && !(c->expFlags & 64u);
-    if (probed && !s->hyTried) { if (int r = prepareIncoherentCopies(s)) return r; }   // first launch of this class on the scene: the derived copies for incoherent batches (not part of the query's time)
-    q.hybridK = s->hybridK;
+    if (probed) { if (int r = prepareIncoherentCopies(s)) return r; }   // first launch of this class on the scene: the derived copies for incoherent batches (not part of the query's time)
+    q.hybridK = s->cw.packed;
     HIP_TRY(timedBegin(c));
     // BVH8_CWBVH scenes beyond the L2s (the `small` class runs dense triangle phases, where the gated schedule loses 15 %) but within reach
     // of the Infinity Cache (beyond it camera rays are bound by memory too: 30 M / 60 M triangles lose 11 / 19 % under the gate), batches of 2 M

@@ -1,82 +1,11 @@
-// capi_scene.hip — scenes: uploads and their validation, derived copies, device conversion / build / refit, TLAS upload and rebuild, opacity maps.
+// capi_scene.hip — scenes: uploads and their validation, in-place updates, device conversion / build / refit, TLAS upload, classification and rebuild,
+// opacity maps, schedule hints.  The copies the library derives from a scene are capi_copies.hip's: this file reaches them through capi_internal.h's functions.
 #include "capi_internal.h"
 
 using namespace tbvh;
 using namespace tbvh_capi;
 
 namespace tbvh_capi {
-// A BVH8_CWBVH scene whose node array is larger than twice the 256 MB Infinity Cache is traversed through a copy with one node per
-// 128-byte line: an 80-byte node straddles 1.6 lines on average, and once the lines come from HBM that is 17 % more traffic than the
-// 60 % larger array costs (tools/size_sweep.py, 60 M triangles: bounce rays +6 %; below that size the smaller footprint wins).
-int padCwbvhIfLarge(tbvh_scene* s) {
-    if (s->layout != TBVH_LAYOUT_CWBVH || s->isTlas || s->nodes128 || (uint64_t)s->nNodes * 80 < (512ull << 20)) return 0;
-    if ((uint64_t)s->nNodes * 8 >> 32) return 0;   // (cw_load_node addresses float4s with 32 bits: beyond 2^29 nodes — 64 GB padded — the packed array serves)
-    tbvh_context* c = s->ctx;
-    if (s->nodes128.alloc((size_t)s->nNodes * 8) != hipSuccess) { (void)hipGetLastError(); return 0; }   // no memory to spare: the packed array serves
-    launch_cwbvh_pad(s->nodes, s->nodes128, s->nNodes, c->stream);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    s->bytes += (uint64_t)s->nNodes * 128;
-    return 0;
-}
-
-static size_t hybridBlocks(uint32_t nNodes, uint32_t K) { return (size_t)K * 5 + (size_t)(nNodes - K) * 8; }   // 16-byte blocks of the hybrid node copy
-size_t hybridBytes(uint32_t nNodes, uint32_t K) { return hybridBlocks(nNodes, K) * 16; }
-
-// BVH8_CWBVH scenes of the class that gets the per-launch coherence probe (48 - 384 MB of blobs: beyond the L2s, within reach of the Infinity
-// Cache) keep two derived copies for INCOHERENT batches (kernels_cwbvh.hip: PROBED == 2): the nodes in surface-area priority order with the
-// first kHybridPacked packed and the others one per 128-byte line (each with one of its triangles in the line's spare 48 bytes), and the
-// triangle records padded to 64 bytes.  Built LAZILY by the first launch that would use them (launchQuery: a batch of 2 M rays or more) — a
-// scene that is only ever a BLAS under a TLAS, or only traced with small batches, never pays the 2.3 x memory and the host pass; that first
-// launch waits for the build (~0.1 s for 600 k nodes: the node array is read back, ordered on the host, scattered on the device).  Trees made
-// on the device (tbvh_convert_bvh2_device, tbvh_build_device) are in level order, which already is close to priority order: no renumbering.
-// A blob that is not a strict tree (cwbvh_priority_order), one with 2^27 triangle records or more, or a failed allocation is not an error:
-// the scene then runs the one-kernel path.  TBVH_INCOHERENT_COPIES=0 turns the copies off.
-constexpr uint32_t kHybridPacked = 8192;
-bool wantsIncoherentCopies(const tbvh_scene* s) {
-    const uint64_t blobBytes = (s->nNodeBlocks + s->nTriBlocks) * 16;
-    return s->layout == TBVH_LAYOUT_CWBVH && !s->isTlas && s->ctx->incoherentCopies && blobBytes >= (48ull << 20) && blobBytes <= (384ull << 20) && s->nNodes > kHybridPacked &&
-           s->nTriBlocks != 0 && s->nTriBlocks / 3 < (1ull << 27);
-}
-int prepareIncoherentCopies(tbvh_scene* s) {
-    tbvh_context* c = s->ctx;
-    s->hyTried = true;
-    if (!wantsIncoherentCopies(s)) return 0;
-    const uint32_t K = kHybridPacked;
-    const uint64_t nT = s->nTriBlocks / 3;
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    if (!s->hyLevelOrder && !s->hyPerm) {
-        std::vector<Vec4> host((size_t)s->nNodes * 5);
-        HIP_TRY(hipMemcpy(host.data(), s->nodes, host.size() * 16, hipMemcpyDeviceToHost));
-        std::vector<uint32_t> perm;
-        if (!cwbvh_priority_order(host.data(), s->nNodes, perm)) return 0;   // not a strict tree: traversed as uploaded
-        if (s->hyPerm.alloc(s->nNodes) != hipSuccess) { (void)hipGetLastError(); return 0; }
-        HIP_TRY(hipMemcpy(s->hyPerm, perm.data(), (size_t)s->nNodes * 4, hipMemcpyHostToDevice));
-    }
-    if (!s->nodesHy && s->nodesHy.alloc(hybridBlocks(s->nNodes, K)) != hipSuccess) { (void)hipGetLastError(); return 0; }
-    if (!s->tris64 && s->tris64.alloc(nT * 4) != hipSuccess) { (void)hipGetLastError(); s->nodesHy.reset(); return 0; }
-    s->hybridK = K;
-    HIP_TRY(hipMemsetAsync(s->nodesHy, 0, hybridBytes(s->nNodes, K), c->stream));
-    launch_cwbvh_derive_hybrid(s->nodes, s->hyPerm, s->nodesHy, s->nNodes, K, (c->embedTris && !(c->expFlags & 8u)) ? s->tris : nullptr, c->stream);
-    launch_cwbvh_pad_tris(s->tris, s->tris64, nT, c->stream);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    s->bytes += hybridBytes(s->nNodes, K) + nT * 64;
-    return 0;
-}
-
-// order-dependent hash of what the hybrid copy's numbering depends on: which slots of every node are interior children and where they start
-uint64_t cwbvhTopologyHash(const Vec4* nodes, uint32_t nNodes) {
-    uint64_t h = 0x9E3779B97F4A7C15ull ^ nNodes;
-    for (uint32_t i = 0; i < nNodes; i++) {
-        uint32_t w[2];
-        std::memcpy(&w[0], &nodes[(size_t)i * 5].w, 4); std::memcpy(&w[1], &nodes[(size_t)i * 5 + 1].x, 4);
-        const uint64_t k = ((uint64_t)(w[0] >> 24) << 32) | ((w[0] >> 24) ? w[1] : 0u);
-        h = (h ^ k) * 0x100000001B3ull; h ^= h >> 29;
-    }
-    return h;
-}
-
 tbvh_scene* newScene(tbvh_context* c, int layout) {
     tbvh_scene* s = new (std::nothrow) tbvh_scene;
     if (!s) return nullptr;
@@ -85,106 +14,7 @@ tbvh_scene* newScene(tbvh_context* c, int layout) {
     return s;
 }
 
-constexpr uint64_t kWideCopyMin = 32768;   // blob entries from which a scene's own queries go through its 8-wide copy (TBVH_WIDE_COPY_MIN)
-
-void freeCopy(tbvh_scene* s, CopyKind kind) {
-    if (!s) return;
-    tbvh_scene*& slot = kind == kCopyWide4 ? s->wide4 : s->wide;
-    tbvh_scene* w = slot;
-    if (!w) return;
-    slot = nullptr;
-    s->bytes -= w->bytes < s->bytes ? w->bytes : 0;
-    tbvh_free_scene(w);   // (the opacity maps it read are the owner's: tbvh_scene::opmapOwn)
-}
-
-// f(t) for each distinct TLAS t over BLAS b (usedBy holds one entry per reference), until one returns non-zero: that value, or 0
-template <class F>
-static int forEachTlasOver(tbvh_scene* b, F f) {
-    for (size_t i = 0; i < b->usedBy.size(); i++) {
-        bool seen = false;
-        for (size_t k = 0; k < i; k++) seen |= b->usedBy[k] == b->usedBy[i];
-        if (!seen) if (int r = f(b->usedBy[i])) return r;
-    }
-    return 0;
-}
-
-// The 8-wide copy of a BVH_GPU / BVH4_GPU scene (tbvh_scene::wide), made LAZILY by the scene's first query of 1024 rays or more (launchQuery) — a BLAS
-// that is only ever traced through a TLAS never pays for it — from what the scene keeps on the device: the blob is read back, the host turns it into a
-// Wald-layout BVH2 with leaves of at most 3 entries (host_builder.cpp: bvh_gpu_to_bvh2 in record mode / bvh4_gpu_to_bvh2), the device converter every
-// BVH8_CWBVH conversion uses collapses and encodes it in ITS record mode (kernels_convert.hip; the greedy collapse of MBVH<8>::ConvertFrom,
-// tiny_bvh.h:4975-5048): triangle records are carried over bit for bit.  Blobs below TBVH_WIDE_COPY_MIN entries / triangles (default 32768; 0 = never)
-// keep their own kernel.  A failure here is never an error of the query: the scene then simply traces its own nodes.
-static int convertDeviceImpl(tbvh_context* c, int layout, const float4* dN2, uint64_t nNodes2, const uint32_t* dIdx, uint64_t nIdx, const MeshSrc& dV, tbvh_scene** out);
-// One copy of scene s in the `target` layout (BVH8_CWBVH from a BVH_GPU / BVH4_GPU scene, BVH4_GPU from a BVH_GPU / BVH8_CWBVH one), or nullptr (too small,
-// too large, out of memory: never an error of the caller's operation).  Not listed in the context's scene table; shares the owner's opacity maps.
-// forTlas: the copy is wanted by a TLAS over s — there ONE kernel class for all BLASes is worth more than any single BLAS's speed (a BLAS without the copy
-// puts the whole TLAS on the flat loop), so small blobs get one too (from 64 entries; TBVH_WIDE_COPY_MIN still rules when set).
-static tbvh_scene* buildCopy(tbvh_scene* s, int target, bool forTlas) {
-    tbvh_context* c = s->ctx;
-    uint64_t minIdx = forTlas ? 64 : kWideCopyMin;
-    if (const char* e = getenv("TBVH_WIDE_COPY_MIN")) { const long long v = atoll(e); minIdx = v <= 0 ? ~0ull : (uint64_t)v; }
-    std::vector<Node2> n2;
-    std::vector<Vec4> blob, recs;
-    const float4* dRecs = nullptr;
-    uint64_t nRecs = 0;
-    DevBuf<float4> dN2, dOwnRecs;
-    try {
-        if (s->layout == TBVH_LAYOUT_BVH_GPU) {
-            const uint64_t nNodes = s->nNodeBlocks / 4, nIdx = s->nTriBlocks / 3;
-            if (nIdx < minIdx || nIdx > 0x7fffffffull || nNodes > 0x3fffffffull) return nullptr;
-            blob.resize(s->nNodeBlocks); recs.resize(s->nTriBlocks);
-            if (hipMemcpyAsync(blob.data(), s->nodes, s->nNodeBlocks * 16, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
-                hipMemcpyAsync(recs.data(), s->tris, s->nTriBlocks * 16, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
-                hipStreamSynchronize(c->stream) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
-            if (!bvh_gpu_to_bvh2((const NodeAL*)blob.data(), nNodes, nullptr, nIdx, nullptr, 0, 3u, n2, recs.data())) return nullptr;
-            dRecs = s->tris; nRecs = nIdx;       // (the gathered records are on the device already, in leaf order)
-        } else {
-            if (s->layout == TBVH_LAYOUT_BVH4_GPU) {
-                if (s->nNodeBlocks / 4 < minIdx || s->nNodeBlocks > 0x7fffffffull) return nullptr;   // (a stream of n triangles has at least 3 n blocks: a cheap first cut)
-                blob.resize(s->nNodeBlocks);
-                if (hipMemcpyAsync(blob.data(), s->nodes, s->nNodeBlocks * 16, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
-                    hipStreamSynchronize(c->stream) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
-                if (!bvh4_gpu_to_bvh2(blob.data(), s->nNodeBlocks, 3u, n2, recs)) return nullptr;
-            } else {   // BVH8_CWBVH
-                if (s->nTriBlocks / 3 < minIdx || s->nTriBlocks > 0x7fffffffull) return nullptr;
-                std::vector<Vec4> tris(s->nTriBlocks);
-                blob.resize(s->nNodeBlocks);
-                if (hipMemcpyAsync(blob.data(), s->nodes, s->nNodeBlocks * 16, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
-                    hipMemcpyAsync(tris.data(), s->tris, s->nTriBlocks * 16, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
-                    hipStreamSynchronize(c->stream) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
-                if (!cwbvh_to_bvh2(blob.data(), s->nNodeBlocks / 5, tris.data(), s->nTriBlocks, n2, recs)) return nullptr;
-            }
-            nRecs = recs.size() / 3;
-            if (nRecs < minIdx || nRecs > 0x7fffffffull) return nullptr;
-            if (dOwnRecs.alloc(recs.size()) != hipSuccess ||
-                hipMemcpyAsync(dOwnRecs, recs.data(), recs.size() * 16, hipMemcpyHostToDevice, c->stream) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
-            dRecs = dOwnRecs;
-        }
-    } catch (const std::bad_alloc&) { return nullptr; }
-    if (n2.size() > 0x7fffffffull) return nullptr;
-    if (dN2.alloc(n2.size() * 2) != hipSuccess ||
-        hipMemcpyAsync(dN2, n2.data(), n2.size() * 32, hipMemcpyHostToDevice, c->stream) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
-    tbvh_scene* w = nullptr;
-    if (convertDeviceImpl(c, target, dN2, n2.size(), nullptr, nRecs, flat_mesh(dRecs, nRecs), &w) != 0 || !w) { (void)hipGetLastError(); return nullptr; }
-    for (size_t i = 0; i < c->scenes.size(); i++)
-        if (c->scenes[i] == w) { c->scenes.erase(c->scenes.begin() + i); break; }   // owned by `s`, freed with it
-    w->opmap = s->opmap; w->opmapN = s->opmapN;
-    return w;
-}
-
-
 // ---- device refit (tbvh_refit / tbvh_refit_mesh below) ----------------------------------------------------------------------------------
-constexpr uint64_t kRefitKeepRays = 8ull << 20;   // a copy's refit (0.3-0.5 ms per 100 k triangles) pays from about this many rays per refit on (0.04-0.08 ns gained per ray)
-// a mesh refitted every frame with few rays traced in between: the copies are dropped (they come back like after an update: tbvh_scene::pendingCopies)
-static bool refitDropsCopies(tbvh_scene* s) {
-    uint64_t total = s->raysTraced;
-    forEachTlasOver(s, [&](tbvh_scene* t) { total += t->raysTraced; return 0; });
-    const bool drop = (s->wide || s->wide4) && s->refitSeen && total - s->raysAtRefit < kRefitKeepRays;
-    s->refitSeen = true; s->raysAtRefit = total;
-    if (drop) dropCopiesAfterUpdate(s);
-    return drop;
-}
-
 // the refit itself: src is device-resident (the caller's arrays, the scene's vertex staging buffer, the scene's held index buffer)
 int refitDeviceSource(tbvh_scene* s, const MeshSrc& src) {
     tbvh_context* c = s->ctx;
@@ -199,9 +29,7 @@ int refitDeviceSource(tbvh_scene* s, const MeshSrc& src) {
         HIP_TRY(timedBegin(c));
         HIP_TRY(run_refit_bvh4(s->nodes, s->nNodeBlocks, src, items, capNodes, counter, childBox, s->b4Levels, c->status, c->stream));
         HIP_TRY(timedEnd(c));
-        if (refitDropsCopies(s)) return 0;
-        if (s->wide) return refitDeviceSource(s->wide, src);   // the 8-wide copy follows
-        return 0;
+        return refitCopies(s, src);   // the 8-wide copy follows
     }
     if (s->layout != TBVH_LAYOUT_CWBVH && s->layout != TBVH_LAYOUT_BVH_GPU)
         return fail(TBVH_E_INVALID, "tbvh_refit: layout %d is not refittable", s->layout);
@@ -211,14 +39,8 @@ int refitDeviceSource(tbvh_scene* s, const MeshSrc& src) {
     HIP_TRY(timedBegin(c));
     HIP_TRY(launch_refit(s->layout, s->nodes, nNodes, s->tris, nRecords, src, s->refitScratch, c->status, c->stream));
     HIP_TRY(timedEnd(c));
-    // derived node layouts of the experiment kernels would be stale now
-    if (s->nodes128) launch_cwbvh_pad(s->nodes, s->nodes128, nNodes, c->stream);   // keep the padded copy current
-    if (s->nodesHy) launch_cwbvh_derive_hybrid(s->nodes, s->hyPerm, s->nodesHy, nNodes, s->hybridK, (c->embedTris && !(c->expFlags & 8u)) ? s->tris : nullptr, c->stream);
-    if (s->tris64) launch_cwbvh_pad_tris(s->tris, s->tris64, s->nTriBlocks / 3, c->stream);
-    if (refitDropsCopies(s)) return 0;
-    if (s->wide) if (int r = refitDeviceSource(s->wide, src)) return r;     // the 8-wide copy follows (same vertices, already on the device)
-    if (s->wide4) return refitDeviceSource(s->wide4, src);                 // ... and the 4-wide one
-    return 0;
+    if (int r = rederiveCwbvhLayouts(s)) return r;   // the padded / hybrid nodes and the 64-byte triangle records would be stale now
+    return refitCopies(s, src);                      // the 8-wide and the 4-wide copy follow
 }
 }  // namespace tbvh_capi
 
@@ -226,29 +48,40 @@ extern "C" {
 
 // ---- uploads ---------------------------------------------------------------------------
 
-// BVH_GPU upload: the blob's primIdx names triangles, whose vertices the gather finds through the mesh (flat: 3 float4 per triangle)
-static int uploadBvhGpuImpl(tbvh_context* c, const void* nodes64, uint64_t nNodes, const uint32_t* primIdx, uint64_t nIdx, const tbvh_mesh& mesh, tbvh_scene** out) {
-    if (const char* why = validate_bvh_gpu((const NodeAL*)nodes64, nNodes, nIdx)) return fail(why == kValidateNoMemory ? TBVH_E_NOMEM : TBVH_E_FORMAT, "%s", why);
-    TBVH_ENTER(c);
-    tbvh_scene* s = newScene(c, TBVH_LAYOUT_BVH_GPU);
-    if (!s) return fail(TBVH_E_NOMEM, "out of host memory");
+// What a BVH_GPU upload and an in-place update share (skipped when e comes in as an error): the blob's nodes go into s->nodes, its primIdx names triangles,
+// whose vertices the gather finds through the mesh (flat: 3 float4 per triangle) and writes to s->tris, an indexed mesh leaves its indices with the scene
+// (counted in s->bytes: set before); synchronous.  e: the first HIP error — the caller words it and cleans up —, r: keepMeshIndices' code; general: the gather
+// read through indices or a stride, so checkStatus is due (device-resident indices: the gather reports an index that is not a vertex)
+struct BvhGpuFill { hipError_t e; int r; bool indexed, general; };
+static BvhGpuFill fillBvhGpu(tbvh_scene* s, hipError_t e, const void* nodes64, uint64_t nNodes, const uint32_t* primIdx, uint64_t nIdx, const tbvh_mesh& mesh) {
+    tbvh_context* c = s->ctx;
     DevBuf<uint32_t> dIdx;
     DeviceMesh dm;
-    hipError_t e = s->nodes.alloc(nNodes * 4);
-    if (e == hipSuccess) e = s->tris.alloc((nIdx ? nIdx : 1) * 3);
     if (e == hipSuccess) e = dIdx.alloc(nIdx ? nIdx : 1);
     if (e == hipSuccess && stageMesh(c, mesh, dm)) e = hipErrorOutOfMemory;
     if (e == hipSuccess) e = hipMemcpyAsync(s->nodes, nodes64, nNodes * 64, hipMemcpyHostToDevice, c->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(dIdx, primIdx, nIdx * 4, hipMemcpyHostToDevice, c->stream);
     if (e == hipSuccess && nIdx) { launch_gather_tris(dIdx, dm.src, s->tris, nIdx, c->status, c->stream); e = hipGetLastError(); }
-    s->nNodeBlocks = nNodes * 4; s->nTriBlocks = nIdx * 3;
-    s->capNodeBlocks = s->nNodeBlocks; s->capTriBlocks = s->nTriBlocks;
-    s->bytes = nNodes * 64 + nIdx * 48;
     int r = 0;
     if (e == hipSuccess && dm.src.indices) r = keepMeshIndices(s, dm.src);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if (e != hipSuccess) { tbvh_free_scene(s); return fail(TBVH_E_HIP, "BVH_GPU upload failed: %s", hipGetErrorString(e)); }
-    if (!r && dm.src.general()) r = checkStatus(c);   // (device-resident indices: the gather reports an index that is not a vertex)
+    return {e, r, dm.src.indices != nullptr, dm.src.general()};
+}
+
+static int uploadBvhGpuImpl(tbvh_context* c, const void* nodes64, uint64_t nNodes, const uint32_t* primIdx, uint64_t nIdx, const tbvh_mesh& mesh, tbvh_scene** out) {
+    if (const char* why = validate_bvh_gpu((const NodeAL*)nodes64, nNodes, nIdx)) return fail(why == kValidateNoMemory ? TBVH_E_NOMEM : TBVH_E_FORMAT, "%s", why);
+    TBVH_ENTER(c);
+    tbvh_scene* s = newScene(c, TBVH_LAYOUT_BVH_GPU);
+    if (!s) return fail(TBVH_E_NOMEM, "out of host memory");
+    hipError_t e = s->nodes.alloc(nNodes * 4);
+    if (e == hipSuccess) e = s->tris.alloc((nIdx ? nIdx : 1) * 3);
+    s->nNodeBlocks = nNodes * 4; s->nTriBlocks = nIdx * 3;
+    s->capNodeBlocks = s->nNodeBlocks; s->capTriBlocks = s->nTriBlocks;
+    s->bytes = nNodes * 64 + nIdx * 48;
+    const BvhGpuFill f = fillBvhGpu(s, e, nodes64, nNodes, primIdx, nIdx, mesh);
+    if (f.e != hipSuccess) { tbvh_free_scene(s); return fail(TBVH_E_HIP, "BVH_GPU upload failed: %s", hipGetErrorString(f.e)); }
+    int r = f.r;
+    if (!r && f.general) r = checkStatus(c);
     if (r) { tbvh_free_scene(s); return r; }
     *out = s;
     return 0;
@@ -301,7 +134,7 @@ int tbvh_upload_cwbvh(tbvh_context* c, const void* nodes16, uint64_t nNodeBlocks
     s->capNodeBlocks = nNodeBlocks; s->capTriBlocks = nTriBlocks ? nTriBlocks : 1;
     s->topoHash = cwbvhTopologyHash((const Vec4*)nodes16, s->nNodes);
     s->bytes = (nNodeBlocks + nTriBlocks) * 16;
-    if (int r = padCwbvhIfLarge(s)) { tbvh_free_scene(s); return r; }
+    if (int r = resetCwbvhLayouts(s)) { tbvh_free_scene(s); return r; }
     *out = s;
     return 0;
 }
@@ -387,17 +220,6 @@ int tlasCopy(tbvh_scene* s, const void* nodes64, uint64_t nNodes, const uint32_t
 
 extern "C++" {
 namespace tbvh_capi {
-// What a TLAS traverses for BLAS b, by the kind of query (round 6; 1000 instances of a 100 k-triangle BLAS, camera / shadow / random MRays/s in DESIGN.md par. 3.5):
-// closest hits through a 4-wide stream — a BVH4_GPU BLAS's own, the 4-wide copy of a BVH_GPU / BVH8_CWBVH one (k_tlas4 is the fastest two-level kernel for
-// closest hits) —, any-hit queries through 8-wide nodes — a BVH8_CWBVH BLAS's own, the 8-wide copy of the others (k_tlas8 is the fastest there).  A forced
-// variant on the BLAS (tbvh_set_variant) pins the uploaded nodes; allow4 = false: the closest-hit view without the 4-wide copies (reclassifyTlas's fallback).
-static const tbvh_scene* blasView(const tbvh_scene* b, bool any, bool allow4 = true) {
-    if (b->variant != 0) return b;
-    if (!any && allow4 && b->wide4 && (b->layout == TBVH_LAYOUT_BVH_GPU || b->layout == TBVH_LAYOUT_CWBVH)) return b->wide4;   // closest hits: the 4-wide kernel
-    const bool viaCopy = b->wide && (b->layout == TBVH_LAYOUT_BVH_GPU || (any && b->layout == TBVH_LAYOUT_BVH4_GPU));
-    return viaCopy ? b->wide : b;
-}
-
 // The BLAS descriptors of TLAS t and the class of two-level kernel that serves each kind of query, from its BLASes as they are NOW (their copies come and
 // go: a tbvh_update_* drops them, queries bring them back, tbvh_set_variant switches between copy and nodes); builds the wide TLAS(es) those kernels walk.
 // With every BLAS copied, BLASes of different layouts under one TLAS share one kernel class per kind of query instead of the flat three-state loop.
@@ -452,55 +274,6 @@ int reclassifyTlas(tbvh_scene* t) {
     if (t->nodes) return buildTlas4(t);
     return 0;
 }
-
-// (one body for what were makeWideCopy and makeWide4Copy)
-int makeCopy(tbvh_scene* s, CopyKind kind) {
-    const bool four = kind == kCopyWide4;
-    freeCopy(s, kind);
-    (four ? s->wide4Tried : s->wideTried) = true;
-    // the 8-wide copy is of a BVH_GPU / BVH4_GPU scene, the 4-wide one of a BVH_GPU / BVH8_CWBVH one and always for the TLASes over it
-    const bool has = !s->isTlas && (s->layout == TBVH_LAYOUT_BVH_GPU || s->layout == (four ? TBVH_LAYOUT_CWBVH : TBVH_LAYOUT_BVH4_GPU));
-    if (tbvh_scene* w = has ? buildCopy(s, four ? TBVH_LAYOUT_BVH4_GPU : TBVH_LAYOUT_CWBVH, four || !s->usedBy.empty()) : nullptr) {
-        (four ? s->wide4 : s->wide) = w; s->bytes += w->bytes;
-        if (!four) {
-            // a copy below the size at which the scene's OWN queries gain from it (made for the TLASes over the scene): those queries keep the uploaded nodes
-            const uint64_t entries = s->layout == TBVH_LAYOUT_BVH_GPU ? s->nTriBlocks / 3 : w->nTriBlocks / 3;
-            s->wideTlasOnly = entries < kWideCopyMin && !getenv("TBVH_WIDE_COPY_MIN");
-        }
-    }
-    forEachTlasOver(s, [](tbvh_scene* t) { (void)reclassifyTlas(t); return 0; });   // (the copy's arrays are new ones — or gone)
-    return 0;
-}
-
-void dropCopiesAfterUpdate(tbvh_scene* s) {
-    const uint8_t had = (uint8_t)((s->wide ? kCopyWide8 : 0) | (s->wide4 ? kCopyWide4 : 0) | s->pendingCopies);
-    if (!had) return;
-    if (s->remadeSinceUpdate && s->recopyAfter < (1u << 20)) s->recopyAfter *= 4u;   // updated again soon after the copies came back: a blob that keeps changing
-    s->remadeSinceUpdate = false;
-    hipStreamSynchronize(s->ctx->stream);
-    freeCopy(s, kCopyWide8); freeCopy(s, kCopyWide4);
-    s->pendingCopies = had; s->queriesSinceUpdate = 0;
-    forEachTlasOver(s, [](tbvh_scene* t) { (void)reclassifyTlas(t); t->blasRecopyPending = true; return 0; });   // (the TLASes enter this BLAS through its own nodes meanwhile)
-}
-
-static void remakePendingCopies(tbvh_scene* b) {
-    const uint8_t kinds = b->pendingCopies;
-    b->pendingCopies = 0; b->remadeSinceUpdate = true;
-    if (kinds & kCopyWide8) makeCopy(b, kCopyWide8);
-    if (kinds & kCopyWide4) makeCopy(b, kCopyWide4);
-}
-
-void countQueryForRecopy(tbvh_scene* s) {
-    if (!s->isTlas) {
-        if (s->pendingCopies && ++s->queriesSinceUpdate >= s->recopyAfter) remakePendingCopies(s);
-        return;
-    }
-    if (!s->blasRecopyPending) return;
-    bool still = false;
-    for (tbvh_scene* b : s->blasList)
-        if (b->pendingCopies) { if (++b->queriesSinceUpdate >= b->recopyAfter) remakePendingCopies(b); else still = true; }
-    s->blasRecopyPending = still;
-}
 }  // namespace tbvh_capi
 }  // extern "C++"
 
@@ -523,7 +296,7 @@ int tbvh_upload_tlas(tbvh_context* c, const void* nodes64, uint64_t nNodes, cons
     TBVH_ENTER(c);
     for (uint64_t i = 0; i < nBlas && !spheres; i++)   // closest-hit queries enter BVH_GPU and BVH8_CWBVH BLASes through 4-wide copies (blasView), made now; the 8-wide copies any-hit queries
                                                        // enter BVH_GPU and BVH4_GPU BLASes through are made by the TLAS's first any-hit query (launchQuery)
-        if ((blas[i]->layout == TBVH_LAYOUT_BVH_GPU || blas[i]->layout == TBVH_LAYOUT_CWBVH) && !blas[i]->wide4Tried && blas[i]->variant == 0) makeCopy(blas[i], kCopyWide4);
+        makeCopyOnce(blas[i], kCopyWide4);
     tbvh_scene* s = newScene(c, TBVH_LAYOUT_BVH_GPU);
     if (!s) return fail(TBVH_E_NOMEM, "out of host memory");
     s->isTlas = true; s->nBlas = nBlas; s->blasSpheres = spheres;
@@ -554,25 +327,15 @@ static int updateBvhGpuImpl(const char* who, tbvh_scene* s, const void* nodes64,
     if (const char* why = validate_bvh_gpu((const NodeAL*)nodes64, nNodes, nIdx)) return fail(why == kValidateNoMemory ? TBVH_E_NOMEM : TBVH_E_FORMAT, "%s", why);
     tbvh_context* c = s->ctx;
     TBVH_ENTER(c);
-    DevBuf<uint32_t> dIdx;
-    DeviceMesh dm;
-    hipError_t e = dIdx.alloc(nIdx ? nIdx : 1);
-    if (e == hipSuccess && stageMesh(c, *mesh, dm)) e = hipErrorOutOfMemory;
-    if (e == hipSuccess) e = hipMemcpyAsync(s->nodes, nodes64, nNodes * 64, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(dIdx, primIdx, nIdx * 4, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess && nIdx) { launch_gather_tris(dIdx, dm.src, s->tris, nIdx, c->status, c->stream); e = hipGetLastError(); }
-    int r = 0;
-    if (e == hipSuccess && dm.src.indices) r = keepMeshIndices(s, dm.src);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if (e != hipSuccess) return fail(TBVH_E_HIP, "%s: %s", who, hipGetErrorString(e));
-    if (!dm.src.indices && s->meshIdx) {   // re-uploaded from vertices without indices: a held index buffer would describe another mesh
+    const BvhGpuFill f = fillBvhGpu(s, hipSuccess, nodes64, nNodes, primIdx, nIdx, *mesh);
+    if (f.e != hipSuccess) return fail(TBVH_E_HIP, "%s: %s", who, hipGetErrorString(f.e));
+    if (!f.indexed && s->meshIdx) {   // re-uploaded from vertices without indices: a held index buffer would describe another mesh
         s->meshIdx.reset();
         s->bytes -= s->meshIdxTris * 12; s->meshIdxTris = 0;
     }
     s->nNodeBlocks = nNodes * 4; s->nTriBlocks = nIdx * 3;
-    dropCopiesAfterUpdate(s);   // (the copies are of the old tree: they come back once the blob has settled — tbvh_scene::pendingCopies)
-    if (!r && dm.src.general()) r = checkStatus(c);
-    return r;
+    dropCopiesAfterUpdate(s);   // (the copies are of the old tree: they come back once the blob has settled — copy_policy.h)
+    return !f.r && f.general ? checkStatus(c) : f.r;
 }
 
 int tbvh_update_bvh_gpu(tbvh_scene* s, const void* nodes64, uint64_t nNodes, const uint32_t* primIdx, uint64_t nIdx, const void* verts16, uint64_t nTris) {
@@ -599,7 +362,7 @@ int tbvh_update_bvh4_gpu(tbvh_scene* s, const void* blocks16, uint64_t nBlocks) 
     s->nNodeBlocks = nBlocks;
     s->b4Levels.clear();   // (the node list of a device refit is rebuilt by the next tbvh_refit)
     s->refitScratch.reset();
-    dropCopiesAfterUpdate(s);   // (the copy is of the old tree: it comes back once the blob has settled — tbvh_scene::pendingCopies)
+    dropCopiesAfterUpdate(s);   // (the copy is of the old tree: it comes back once the blob has settled — copy_policy.h)
     return 0;
 }
 
@@ -621,25 +384,17 @@ static int updateCwbvhImpl(tbvh_scene* s, const void* nodes16, uint64_t nNodeBlo
     s->nNodes = nNodes; s->nNodeBlocks = nNodeBlocks; s->nTriBlocks = nTriBlocks; s->topoHash = hash;
     s->refitScratch.reset();   // (sized and filled for the old tree)
     if (!sameShape) for (auto& kind : s->cohTuner) for (CohTuner& tu : kind) if (!tu.pinned) { tu.drop_pending(); tu = CohTuner(); }   // (its timings were taken on the old tree)
-    if (sameShape) {   // boxes and vertices moved, the tree did not: the derived copies keep their numbering and are re-derived on the device
-        if (s->nodes128) launch_cwbvh_pad(s->nodes, s->nodes128, nNodes, c->stream);
-        if (s->nodesHy) launch_cwbvh_derive_hybrid(s->nodes, s->hyPerm, s->nodesHy, nNodes, s->hybridK, (c->embedTris && !(c->expFlags & 8u)) ? s->tris : nullptr, c->stream);
-        if (s->tris64) launch_cwbvh_pad_tris(s->tris, s->tris64, nTriBlocks / 3, c->stream);
-        HIP_TRY(hipGetLastError());
-        return 0;
-    }
-    // another tree in the same allocation: the derived copies go; they come back as at upload (padded nodes now, the incoherent-batch copies lazily)
-    s->nodes128.reset(); s->nodesHy.reset(); s->tris64.reset(); s->hyPerm.reset();
-    s->hybridK = 0; s->hyTried = false; s->hyLevelOrder = false;
+    if (sameShape) return rederiveCwbvhLayouts(s);   // boxes and vertices moved, the tree did not: the derived copies keep their numbering and are re-derived on the device
+    // another tree in the same allocation: the derived copies go; they come back as at upload
     s->bytes = (nNodeBlocks + nTriBlocks) * 16 + s->opmapBytes;
-    return padCwbvhIfLarge(s);
+    return resetCwbvhLayouts(s);
 }
 
 int tbvh_update_cwbvh(tbvh_scene* s, const void* nodes16, uint64_t nNodeBlocks, const void* tris16, uint64_t nTriBlocks) {
     TBVH_REFUSE_DOUBLE(s, "tbvh_update_cwbvh");
     TBVH_REFUSE_VOXEL(s, "tbvh_update_cwbvh");
     TBVH_REFUSE_CUSTOM(s, "tbvh_update_cwbvh");
-    if (s && !s->isTlas && (s->wide4 || s->pendingCopies)) {   // the 4-wide copy TLASes enter this BLAS through is of the old tree (also if the update is refused: harmless)
+    if (s && !s->isTlas && ((s->copies.live() & kCopyWide4) || s->copies.pending())) {   // the 4-wide copy TLASes enter this BLAS through is of the old tree (also if the update is refused: harmless)
         TBVH_ENTER(s->ctx);
         dropCopiesAfterUpdate(s);
     }
@@ -678,8 +433,9 @@ int convertDeviceImpl4(tbvh_context* c, const float4* dN2, uint64_t nNodes2, con
 }
 
 }  // namespace
+extern "C++" {
 namespace tbvh_capi {
-static int convertDeviceImpl(tbvh_context* c, int layout, const float4* dN2, uint64_t nNodes2, const uint32_t* dIdx, uint64_t nIdx, const MeshSrc& dV, tbvh_scene** out) {
+int convertDeviceImpl(tbvh_context* c, int layout, const float4* dN2, uint64_t nNodes2, const uint32_t* dIdx, uint64_t nIdx, const MeshSrc& dV, tbvh_scene** out) {
     if (layout == TBVH_LAYOUT_BVH4_GPU) return convertDeviceImpl4(c, dN2, nNodes2, dIdx, nIdx, dV, out);
     DevBuf<float4> nodes, tris;
     DevBuf<uint2> itA, itB;
@@ -711,12 +467,21 @@ static int convertDeviceImpl(tbvh_context* c, int layout, const float4* dN2, uin
     s->nNodes = nWide; s->nNodeBlocks = (uint64_t)nWide * 5; s->nTriBlocks = nWideTris * 3;
     s->capNodeBlocks = s->nNodeBlocks; s->capTriBlocks = nWideTris ? s->nTriBlocks : 3;
     s->bytes = (s->nNodeBlocks + s->nTriBlocks) * 16;
-    if (int r = padCwbvhIfLarge(s)) { tbvh_free_scene(s); return r; }
-    s->hyLevelOrder = true;   // (level order is close to priority order: the incoherent-batch copies need no renumbering)
+    if (int r = resetCwbvhLayouts(s, true)) { tbvh_free_scene(s); return r; }   // (level order is close to priority order: the incoherent-batch copies need no renumbering)
     *out = s;
     return 0;
 }
-}  // namespace
+}  // namespace tbvh_capi
+}  // extern "C++"
+
+// tail of a device conversion / build (r: its code): a scene made from an indexed mesh keeps the indices; a failure there frees it
+static int keepIndicesOrFree(const char* who, int r, const MeshSrc& src, tbvh_scene** out) {
+    if (r || !src.indices) return r;
+    r = keepMeshIndices(*out, src);
+    if (!r && hipStreamSynchronize((*out)->ctx->stream) != hipSuccess) r = fail(TBVH_E_HIP, "%s: copying the index buffer failed", who);
+    if (r) { tbvh_free_scene(*out); *out = nullptr; }
+    return r;
+}
 
 static int convertBvh2Impl(const char* who, tbvh_context* c, const void* nodes32, uint64_t nNodes2, const uint32_t* primIdx, uint64_t nIdx, const tbvh_mesh& mesh,
                            int onDevice, int layout, tbvh_scene** out) {
@@ -738,12 +503,7 @@ static int convertBvh2Impl(const char* who, tbvh_context* c, const void* nodes32
     HIP_TRY(timedBegin(c));
     int r = convertDeviceImpl(c, layout, dN2, nNodes2, dIdx, nIdx, dm.src, out);
     HIP_TRY(timedEnd(c));
-    if (!r && dm.src.indices) {
-        r = keepMeshIndices(*out, dm.src);
-        if (!r && hipStreamSynchronize(c->stream) != hipSuccess) r = fail(TBVH_E_HIP, "%s: copying the index buffer failed", who);
-        if (r) { tbvh_free_scene(*out); *out = nullptr; }
-    }
-    return r;
+    return keepIndicesOrFree(who, r, dm.src, out);
 }
 
 int tbvh_convert_bvh2_device(tbvh_context* c, const void* nodes32, uint64_t nNodes2, const uint32_t* primIdx, uint64_t nIdx, const void* verts16,
@@ -780,12 +540,7 @@ int buildDeviceImpl(const char* who, tbvh_context* c, const tbvh_mesh& mesh, int
     else HIP_TRY(launch_lbvh_build(dm.src, (uint32_t)nTris, maxLeafTris, n2, idx, scratch, sortTemp, c->stream));
     int r = convertDeviceImpl(c, layout, n2, nTris * 2, idx, nTris, dm.src, out);
     HIP_TRY(timedEnd(c));
-    if (!r && dm.src.indices) {
-        r = keepMeshIndices(*out, dm.src);
-        if (!r && hipStreamSynchronize(c->stream) != hipSuccess) r = fail(TBVH_E_HIP, "%s: copying the index buffer failed", who);
-        if (r) { tbvh_free_scene(*out); *out = nullptr; }
-    }
-    return r;
+    return keepIndicesOrFree(who, r, dm.src, out);
 }
 }  // namespace
 
@@ -874,8 +629,7 @@ int installOpacityMaps(tbvh_scene* s, DevBuf<uint32_t>&& fresh, uint32_t N) {
     s->opmapOwn = std::move(fresh);
     s->opmap = s->opmapOwn; s->opmapN = N; s->opmapBytes = freshBytes;
     s->bytes += freshBytes; s->bytes -= oldBytes;
-    if (s->wide) { s->wide->opmap = s->opmap; s->wide->opmapN = s->opmapN; }   // (shared, owned here)
-    if (s->wide4) { s->wide4->opmap = s->opmap; s->wide4->opmapN = s->opmapN; }
+    shareOpacityMaps(s);
     const int r = refreshBlasDescs(s);   // the descriptors are rewritten before the old maps go
     if (r != 0) (void)old.release();   // (a failed refresh may have left a descriptor on the old maps: leak them rather than dangle)
     return r;
@@ -1054,7 +808,7 @@ uint64_t tbvh_scene_device_bytes(const tbvh_scene* s) { return s ? s->bytes : 0;
 int tbvh_debug_coherent_schedule(tbvh_scene* s, int anyhit, uint32_t out[4]) {
     if (!s || !out) return fail(TBVH_E_INVALID, "tbvh_debug_coherent_schedule: null argument");
     TBVH_LOCK(s->ctx);
-    if (s->wide) s = s->wide;
+    s = tunedScene(s);
     const CohTuner& t = s->cohTuner[anyhit ? 1 : 0][s->cohLastClass[anyhit ? 1 : 0]];   // (kept per batch-size class; this is the class of the most recent such launch)
     out[0] = s->ctx->cohTunerMode ? (uint32_t)s->ctx->cohTunerMode : (uint32_t)t.decided;
     out[1] = t.n[0]; out[2] = t.n[1];
@@ -1070,7 +824,7 @@ int tbvh_scene_get_schedule_hint(tbvh_scene* s, tbvh_schedule_hint* out) {
     if (!s || !out) return fail(TBVH_E_INVALID, "tbvh_scene_get_schedule_hint: null argument");
     TBVH_LOCK(s->ctx);
     std::memset(out, 0, sizeof *out);
-    if (s->wide) s = s->wide;   // (a BVH_GPU / BVH4_GPU scene: its queries run on the 8-wide copy, whose tuner decides)
+    s = tunedScene(s);   // (a BVH_GPU / BVH4_GPU scene: its queries run on the 8-wide copy, whose tuner decides)
     for (int k = 0; k < 3; k++) {
         out->closest_hit[k] = (uint8_t)(s->ctx->cohTunerMode ? s->ctx->cohTunerMode : s->cohTuner[0][k].decided);
         out->any_hit[k] = (uint8_t)(s->ctx->cohTunerMode ? s->ctx->cohTunerMode : s->cohTuner[1][k].decided);
@@ -1089,7 +843,7 @@ int tbvh_scene_set_schedule_hint(tbvh_scene* s, const tbvh_schedule_hint* hint) 
     for (int k = 0; k < 3; k++) if (hint->closest_hit[k] > 3 || hint->any_hit[k] > 3) return fail(TBVH_E_INVALID, "tbvh_scene_set_schedule_hint: entries are 0 (measure), 1 (deferred + gated), 2 (strict) or 3 (one traversal per wave)");
     if (hint->reserved[0] > 3 || hint->reserved[1] > 3) return fail(TBVH_E_INVALID, "tbvh_scene_set_schedule_hint: entries are 0 (measure), 1 (deferred + gated), 2 (strict) or 3 (one traversal per wave)");
     TBVH_LOCK(s->ctx);
-    if (s->wide) s = s->wide;
+    s = tunedScene(s);
     for (int a = 0; a < 2; a++) for (int k = 0; k < 4; k++) {
         const uint8_t v = k == 3 ? hint->reserved[a] : a ? hint->any_hit[k] : hint->closest_hit[k];
         CohTuner& tu = s->cohTuner[a][k];
@@ -1107,49 +861,9 @@ int tbvh_set_variant(tbvh_scene* s, int v) {
     // ... and BVH_GPU / BVH4_GPU scenes one: 1 = trace the nodes as uploaded (k_bvh2 / k_bvh4) even when the scene has an 8-wide copy (tests, A/B)
     const bool ok = v == 0 || (!s->isTlas && s->layout == TBVH_LAYOUT_CWBVH && cwbvh_variant_valid(v)) || (!s->isTlas && (s->layout == TBVH_LAYOUT_BVH_GPU || s->layout == TBVH_LAYOUT_BVH4_GPU) && v == 1);
     if (!ok) return fail(TBVH_E_INVALID, "unknown variant %d for layout %d", v, s->layout);
-    const bool viewChanges = !s->isTlas && (s->wide || s->wide4) && (s->variant == 0) != (v == 0);
+    const bool viewChanges = !s->isTlas && s->copies.live() && (s->variant == 0) != (v == 0);
     s->variant = v;
     if (viewChanges) return refreshBlasDescs(s);   // (the TLASes over this BLAS enter it through the copy, or through its own nodes)
     return 0;
 }
-
-int tbvh_cwbvh_set_hybrid(tbvh_scene* s, int64_t packedNodes) {
-    TBVH_REFUSE_DOUBLE(s, "tbvh_cwbvh_set_hybrid");
-    TBVH_REFUSE_VOXEL(s, "tbvh_cwbvh_set_hybrid");
-    TBVH_REFUSE_CUSTOM(s, "tbvh_cwbvh_set_hybrid");
-    if (!s || s->isTlas || s->layout != TBVH_LAYOUT_CWBVH) return fail(TBVH_E_INVALID, "tbvh_cwbvh_set_hybrid: not a BVH8_CWBVH scene");
-    tbvh_context* c = s->ctx;
-    TBVH_ENTER(c);
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    if (s->nodesHy) { s->bytes -= hybridBytes(s->nNodes, s->hybridK); s->nodesHy.reset(); }
-    s->hyTried = true;   // the caller decides now: no lazy build behind its back
-    if (packedNodes < 0) return 0;
-    if (s->nTriBlocks / 3 >= (1ull << 27)) return fail(TBVH_E_INVALID, "tbvh_cwbvh_set_hybrid: 2^27 triangle records or more");
-    if ((uint64_t)s->nNodes * 8 >> 32) return fail(TBVH_E_INVALID, "tbvh_cwbvh_set_hybrid: 2^29 nodes or more (the copy is addressed in 32-bit float4 offsets: cwbvh_node.h)");
-    const uint32_t K = (uint32_t)std::min<uint64_t>((uint64_t)packedNodes, s->nNodes) & ~7u;   // the padded part starts on a 128-byte line
-    if (!s->hyPerm && !s->hyLevelOrder) {
-        std::vector<Vec4> host((size_t)s->nNodes * 5);
-        HIP_TRY(hipMemcpy(host.data(), s->nodes, host.size() * 16, hipMemcpyDeviceToHost));
-        std::vector<uint32_t> perm;
-        if (!cwbvh_priority_order(host.data(), s->nNodes, perm)) return fail(TBVH_E_FORMAT, "tbvh_cwbvh_set_hybrid: the node array is not a strict tree (a child range shared by two parents or out of range)");
-        HIP_TRY(s->hyPerm.alloc(s->nNodes));
-        HIP_TRY(hipMemcpy(s->hyPerm, perm.data(), (size_t)s->nNodes * 4, hipMemcpyHostToDevice));
-    }
-    HIP_TRY(s->nodesHy.alloc(hybridBlocks(s->nNodes, K)));
-    HIP_TRY(hipMemsetAsync(s->nodesHy, 0, hybridBytes(s->nNodes, K), c->stream));
-    s->hybridK = K;
-    launch_cwbvh_derive_hybrid(s->nodes, s->hyPerm, s->nodesHy, s->nNodes, K, (c->embedTris && !(c->expFlags & 8u)) ? s->tris : nullptr, c->stream);
-    HIP_TRY(hipGetLastError());
-    s->bytes += hybridBytes(s->nNodes, K);
-    if (!s->tris64 && s->nTriBlocks) {
-        const uint64_t nT = s->nTriBlocks / 3;
-        HIP_TRY(s->tris64.alloc(nT * 4));
-        launch_cwbvh_pad_tris(s->tris, s->tris64, nT, c->stream);
-        HIP_TRY(hipGetLastError());
-        s->bytes += nT * 64;
-    }
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return 0;
-}
-
 }  // extern "C"

@@ -1266,7 +1266,7 @@ bool bvh4_gpu_to_bvh2(const Vec4* b, uint64_t nBlocks, uint32_t maxLeafTris, std
 }
 
 // BVH8_CWBVH blob -> Wald-layout BVH2 + triangle records {v0|prim, e1, e2} in leaf order (the 4-wide copy a TLAS enters a BVH8_CWBVH BLAS through for
-// closest-hit queries: capi_scene.hip: makeCopy).  Child boxes as the kernels evaluate them (origin + q * 2^e, padded by ulps of the larger operand);
+// closest-hit queries: capi_copies.hip: makeCopy).  Child boxes as the kernels evaluate them (origin + q * 2^e, padded by ulps of the larger operand);
 // the up to eight children of a node become a small binary tree: sorted along the node's widest axis, halved recursively.  Leaves keep their 1-3 triangles.
 bool cwbvh_to_bvh2(const Vec4* nodes, uint64_t nNodes, const Vec4* tris, uint64_t nTriBlocks, std::vector<Node2>& out, std::vector<Vec4>& recs) {
     out.clear(); recs.clear();
