@@ -83,6 +83,32 @@ public:
     // BVH_Double::Intersect( RayEx& ) / IsOccluded( const RayEx& ) (TLAS: IntersectTLAS / IsOccludedTLAS) over a host RayEx[], in place
     void Intersect(tinybvh::RayEx* rays, size_t n) { Check(tbvh_intersect_ex(s, rays, n), "tbvh_intersect_ex"); }
     void IsOccluded(const tinybvh::RayEx* rays, size_t n, uint8_t* out) { Check(tbvh_occluded_ex(s, rays, n, out), "tbvh_occluded_ex"); }
+    // double scenes that move.  A TLAS: "just move build to Tick if instance transforms are not static" (tiny_bvh_anim_double.cpp:110) —
+    // BLASInstanceEx::Update + BVH_Double::Build( BLASInstanceEx*, ... ) on the device from n_inst x 16 row-major doubles (nullptr: the transforms
+    // the records hold; onDevice: a device array), asynchronous ...
+    void RebuildOnDevice(const double* transforms16 = nullptr, bool onDevice = false) {
+        Check(tbvh_rebuild_tlas_double_device(s, transforms16, onDevice ? 1 : 0), "tbvh_rebuild_tlas_double_device");
+    }
+    // ... or the TLAS rebuilt by tinybvh on the host, into the same Scene (the BLAS list stays)
+    void Update(const tinybvh::BVH_Double& tlas) {
+        Check(tbvh_update_tlas_double(s, tlas.bvhNode, tlas.usedNodes, tlas.primIdx, tlas.idxCount, tlas.instList, tlas.triCount), "tbvh_update_tlas_double");
+    }
+    // A BLAS: same topology, new vertices (the reference has no BVH_Double::Refit); RebuildOnDevice() of the TLASes over it then reads the new bounds
+    void Refit(const tinybvh::bvhdbl3* verts, size_t triCount, bool onDevice = false) { Check(tbvh_refit_double(s, verts, triCount, onDevice ? 1 : 0), "tbvh_refit_double"); }
+    // read-back for inspection: the node array of a BLAS; of a TLAS also its instance indices and BLASInstanceEx records
+    std::vector<tinybvh::BVH_Double::BVHNode> Download() {
+        uint64_t n = 0;
+        Check(tbvh_double_download(s, nullptr, 0, &n), "tbvh_double_download");
+        std::vector<tinybvh::BVH_Double::BVHNode> nodes(n);
+        Check(tbvh_double_download(s, nodes.data(), n, nullptr), "tbvh_double_download");
+        return nodes;
+    }
+    // (any buffer may be nullptr; a buffer smaller than its array is refused; returns the node count)
+    uint64_t Download(tinybvh::BVH_Double::BVHNode* nodes, size_t capNodes, uint64_t* idx, size_t capIdx, tinybvh::BLASInstanceEx* instances, size_t capInst) {
+        uint64_t n = 0;
+        Check(tbvh_tlas_double_download(s, nodes, capNodes, idx, capIdx, instances, capInst, &n), "tbvh_tlas_double_download");
+        return n;
+    }
 #endif
     // the reference's flow for animated geometry — bvh.Refit() on the host, X.ConvertFrom( bvh ) again (tiny_bvh.h:3055-3093) — without a new
     // Scene: the refitted blob goes into the same device memory, TLASes over this BLAS keep working (tbvh_update_*)

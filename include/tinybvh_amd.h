@@ -562,8 +562,8 @@ int tbvh_upload_host(tbvh_context* ctx, const tbvh_hostbvh* h, const void* verts
  * A hit writes t, u, v, prim and inst (= ray.instIdx for a BLAS, the instance index under a TLAS); a miss leaves the record untouched;
  * occlusion is a hit with 0 < t < hit.t.  Equal distances resolve as everywhere in this library (smaller prim, then smaller instance).
  * Blobs are validated before anything is allocated (TBVH_E_FORMAT names the first bad entry: child or leaf range, primIdx, blasIdx, fewer than
- * 2^32 nodes, not a tree).  A BVH_DOUBLE scene takes the four _ex queries, tbvh_free_scene, tbvh_scene_layout (3) and tbvh_scene_device_bytes;
- * every other entry point refuses it (TBVH_E_INVALID), and the _ex queries refuse the fp32 layouts.  Custom geometry (customIntersect) in
+ * 2^32 nodes, not a tree).  A BVH_DOUBLE scene takes the four _ex queries, the calls of the next section (scenes that move), tbvh_free_scene, tbvh_scene_layout (3) and
+ * tbvh_scene_device_bytes; every other entry point refuses it (TBVH_E_INVALID), and the _ex queries refuse the fp32 layouts.  Custom geometry (customIntersect) in
  * double precision is not supported: upload needs triangles (fp32 sphere BLASes: the custom-geometry section below).
  * ---------------------------------------------------------------------------------- */
 int tbvh_upload_bvh_double(tbvh_context* ctx, const void* nodes64, uint64_t n_nodes, const uint64_t* prim_idx, uint64_t n_idx,
@@ -585,6 +585,44 @@ int tbvh_occluded_ex(tbvh_scene* scene, const void* rays128, uint64_t n_rays, ui
  * aabbMin, aabbMax). */
 int tbvh_host_build_double(const void* verts_dbl3, uint64_t n_tris, tbvh_hostbvh** out);
 int tbvh_host_build_tlas_double(void* instances320, uint64_t n_instances, const double* blas_bounds_dbl6, uint64_t n_blas, tbvh_hostbvh** out);
+
+/* ----------------------------------------------------------------------------------
+ * double precision, scenes that move — the frame loop of the reference's double demo (tiny_bvh_anim_double.cpp:110: "just move build to Tick
+ * if instance transforms are not static") without a new scene per frame.  Records as in the section above.  Every call here refuses, with
+ * TBVH_E_INVALID and before anything is launched: a null handle, an fp32 scene, a BLAS the caller has freed, and the wrong kind of double
+ * scene (the three TLAS calls a BLAS, tbvh_refit_double / tbvh_double_download a TLAS).  The fp32 entry points keep refusing double scenes.
+ *
+ * tbvh_rebuild_tlas_double_device: BLASInstanceEx::Update for every instance (tiny_bvh.h:8432-8472: InvertTransform operation for operation,
+ *   det == 0 keeps the unscaled cofactors; the world box of the 8 BLAS-box corners through tinybvh_transform_point, the w != 1 divide included,
+ *   minima / maxima from (double)1e30f) and BVH_Double::Build( BLASInstanceEx*, ... ) (tiny_bvh.h:7955-...), on the device.  transforms_dbl16:
+ *   n_inst x 16 doubles, row-major; on_device = 0: host memory, staged asynchronously; 1: device memory (8-byte aligned); NULL: the
+ *   transforms already in the records.  transform, invTransform, aabbMin, aabbMax are rewritten — bit for bit what
+ *   tbvh_host_build_tlas_double writes —, blasIdx and mask stay.  There is no BLAS-bounds argument: the reference's blas->aabbMin / aabbMax is
+ *   bvhNode[0]'s box (tiny_bvh.h:8133), which the kernel reads from each BLAS.  The tree is an LBVH over 63-bit Morton keys: 2 n - 1 nodes, the
+ *   root at 0, one instance per leaf; hit records do not depend on the TLAS's shape.  Asynchronous on the context's stream;
+ *   tbvh_time_last_ms reports the rebuild.  The first call moves the scene into an allocation laid out for 2 n - 1 nodes and allocates its
+ *   scratch with it (tbvh_scene_device_bytes follows); later calls allocate nothing.  The handle and the BLASes' device pointers stay valid.
+ * tbvh_update_tlas_double: a TLAS built by tinybvh on the host (the reference's frame loop) into the same scene: nodes, instance indices and
+ *   instances are replaced, the BLAS list stays.  The upload's checks, all before the scene is touched: a refused update returns
+ *   TBVH_E_INVALID, names the first bad entry, and the old TLAS goes on answering.  Reallocates only when the TLAS grew.  Synchronous.
+ * tbvh_tlas_double_download / tbvh_double_download: for tests and inspection, like tbvh_tlas_download: the TLAS's nodes (64 bytes each),
+ *   instance indices and BLASInstanceEx records / a BLAS's nodes.  Any buffer may be NULL; a buffer smaller than its array: TBVH_E_INVALID.
+ *   *n_nodes_out (may be NULL) = the node count.  Synchronous.
+ * tbvh_refit_double: same topology, new vertices (bvhdbl3 verts[3 * n_tris]; on_device = 1: device memory, 8-byte aligned).  The reference has
+ *   no BVH_Double::Refit; this is the fp64 twin of tbvh_refit.  Every triangle record is rewritten (v0, v1 - v0, v2 - v0: the upload's
+ *   subtractions), every leaf box taken from the vertices, every interior box the exact union of its children's.  n_tris must equal the
+ *   scene's (TBVH_E_INVALID).  Asynchronous on the context's stream (host vertices are staged); the first refit of a scene also derives the
+ *   parent index of every node and the list of its leaves, kept with the scene and counted in tbvh_scene_device_bytes.  A TLAS over a
+ *   refitted BLAS keeps valid pointers but stale instance boxes: tbvh_rebuild_tlas_double_device( tlas, NULL, 0 ) brings them up to date,
+ *   because it reads the new root boxes.
+ * ---------------------------------------------------------------------------------- */
+int tbvh_rebuild_tlas_double_device(tbvh_scene* tlas, const void* transforms_dbl16, int on_device);
+int tbvh_update_tlas_double(tbvh_scene* tlas, const void* tlas_nodes64, uint64_t n_nodes, const uint64_t* tlas_idx, uint64_t n_idx,
+                            const void* instances320, uint64_t n_inst);
+int tbvh_tlas_double_download(tbvh_scene* tlas, void* nodes64, uint64_t cap_nodes, uint64_t* idx, uint64_t cap_idx,
+                              void* instances320, uint64_t cap_inst, uint64_t* n_nodes_out);
+int tbvh_double_download(tbvh_scene* blas, void* nodes64, uint64_t cap_nodes, uint64_t* n_nodes_out);
+int tbvh_refit_double(tbvh_scene* blas, const void* verts_dbl3, uint64_t n_tris, int on_device);
 
 /* ----------------------------------------------------------------------------------
  * voxel sets — VoxelSet (tiny_bvh.h:988-1030, 3772-4158): a brick map over the unit cube (object space (0,0,0)-(1,1,1)) of a fixed

@@ -1042,13 +1042,39 @@ class BVH_Double(_SceneDouble):
         nodes = np.ascontiguousarray(nodes); prim_idx = np.ascontiguousarray(prim_idx, np.uint64)
         verts = np.ascontiguousarray(verts, np.float64)
         self.verts = verts
+        self.n_tris = verts.size // 9
         check(lib.tbvh_upload_bvh_double(self.ctx._h, _ptr(nodes), nodes.nbytes // 64, _ptr(prim_idx), prim_idx.size, _ptr(verts), verts.size // 9,
                                          C.byref(self._h)), "tbvh_upload_bvh_double")
         return self
 
+    def Refit(self, verts, on_device: bool = False) -> "BVH_Double":
+        """Same topology, new vertices (tbvh_refit_double; asynchronous).  verts: (3 n, 3) float64 of the scene's triangle count, or with
+        on_device=True a device pointer to as many doubles.  self.verts follows (device-resident vertices: dropped; `bounds` then reads the
+        refitted root box).  TLASes over this BLAS keep stale instance boxes until their RebuildOnDevice()."""
+        n_tris = self.n_tris
+        if on_device:
+            check(lib.tbvh_refit_double(self._h, C.c_void_p(verts), n_tris, 1), "tbvh_refit_double")
+            self.verts = None
+        else:
+            verts = np.ascontiguousarray(verts, np.float64)
+            check(lib.tbvh_refit_double(self._h, _ptr(verts), verts.size // 9, 0), "tbvh_refit_double")
+            self.verts = verts
+        return self
+
+    def Download(self) -> np.ndarray:
+        """The node array as it is on the device (NODE_DBL_DTYPE); synchronizes."""
+        n = C.c_uint64(0)
+        check(lib.tbvh_double_download(self._h, None, 0, C.byref(n)), "tbvh_double_download")
+        nodes = np.zeros(n.value, NODE_DBL_DTYPE)
+        check(lib.tbvh_double_download(self._h, _ptr(nodes), n.value, None), "tbvh_double_download")
+        return nodes
+
     @property
     def bounds(self) -> np.ndarray:
-        """aabbMin, aabbMax of the vertices (what BLASInstanceEx::Update reads from a BLAS)."""
+        """aabbMin, aabbMax of the vertices (what BLASInstanceEx::Update reads from a BLAS: the root's box)."""
+        if self.verts is None:
+            root = self.Download()[0]
+            return np.concatenate([root["aabbMin"], root["aabbMax"]])
         v = self.verts.reshape(-1, 3)
         return np.concatenate([v.min(0), v.max(0)])
 
@@ -1070,7 +1096,42 @@ class TLAS_Double(_SceneDouble):
                                           arr, len(blas), C.byref(self._h)), "tbvh_upload_tlas_double")
         self.instances = instances
         self.blas = list(blas)   # the BLAS scenes must outlive the TLAS
+        self._n_idx = tlas_idx.size
         return self
+
+    def RebuildOnDevice(self, transforms=None, on_device: bool = False) -> "TLAS_Double":
+        """BLASInstanceEx::Update of every instance + a new TLAS, on the device (tbvh_rebuild_tlas_double_device; asynchronous).  transforms:
+        (n_inst, 4, 4) float64 row-major, with on_device=True a device pointer to as many doubles, or None: the transforms the records hold.
+        The BLAS bounds are read from the BLASes as they are now (after BVH_Double.Refit: the refitted ones)."""
+        if transforms is None:
+            check(lib.tbvh_rebuild_tlas_double_device(self._h, None, 0), "tbvh_rebuild_tlas_double_device")
+        elif on_device:
+            check(lib.tbvh_rebuild_tlas_double_device(self._h, C.c_void_p(transforms), 1), "tbvh_rebuild_tlas_double_device")
+        else:
+            t = np.ascontiguousarray(transforms, np.float64)
+            assert t.size == 16 * self.instances.shape[0], "one 4 x 4 transform per instance"
+            check(lib.tbvh_rebuild_tlas_double_device(self._h, _ptr(t), 0), "tbvh_rebuild_tlas_double_device")
+        self._n_idx = self.instances.shape[0]   # one leaf per instance
+        return self
+
+    def Update(self, nodes: np.ndarray, idx: np.ndarray, instances: np.ndarray) -> "TLAS_Double":
+        """A TLAS built on the host into the same scene (tbvh_update_tlas_double): the BLAS list stays; validated like Upload, and a refused
+        update leaves the old TLAS answering."""
+        nodes = np.ascontiguousarray(nodes); idx = np.ascontiguousarray(idx, np.uint64)
+        instances = np.ascontiguousarray(instances)
+        check(lib.tbvh_update_tlas_double(self._h, _ptr(nodes), nodes.nbytes // 64, _ptr(idx), idx.size, _ptr(instances), instances.shape[0]), "tbvh_update_tlas_double")
+        self.instances = instances
+        self._n_idx = idx.size
+        return self
+
+    def Download(self):
+        """(nodes, instance indices, instances) as they are on the device: NODE_DBL_DTYPE, uint64, INSTANCE_EX_DTYPE; synchronizes."""
+        n_inst = self.instances.shape[0]
+        n = C.c_uint64(0)
+        check(lib.tbvh_tlas_double_download(self._h, None, 0, None, 0, None, 0, C.byref(n)), "tbvh_tlas_double_download")
+        nodes = np.zeros(n.value, NODE_DBL_DTYPE); idx = np.zeros(self._n_idx, np.uint64); inst = np.zeros(n_inst, INSTANCE_EX_DTYPE)
+        check(lib.tbvh_tlas_double_download(self._h, _ptr(nodes), n.value, _ptr(idx), idx.size, _ptr(inst), n_inst, None), "tbvh_tlas_double_download")
+        return nodes, idx, inst
 
 
 # ---- voxel sets: VoxelSet (tiny_bvh.h:988-1030, 3772-4158) -----------------------------------------------------------------------------

@@ -142,6 +142,12 @@ SYMBOLS = {
     "tbvh_occluded_ex": (_i, [_vp, _vp, _u64, _vp]),
     "tbvh_host_build_double": (_i, [_vp, _u64, _pp]),
     "tbvh_host_build_tlas_double": (_i, [_vp, _u64, _vp, _u64, _pp]),
+    # ... that move (capi_double.hip, kernels_double_anim.hip)
+    "tbvh_rebuild_tlas_double_device": (_i, [_vp, _vp, _i]),
+    "tbvh_update_tlas_double": (_i, [_vp, _vp, _u64, _vp, _u64, _vp, _u64]),
+    "tbvh_tlas_double_download": (_i, [_vp, _vp, _u64, _vp, _u64, _vp, _u64, _vp]),
+    "tbvh_double_download": (_i, [_vp, _vp, _u64, _vp]),
+    "tbvh_refit_double": (_i, [_vp, _vp, _u64, _i]),
     # VoxelSet scenes (capi_voxel.hip)
     "tbvh_upload_voxelset": (_i, [_vp, _vp, _vp, _u64, _vp, _pp]),
     "tbvh_host_build_voxelset": (_i, [_vp, _u32, _u32, _u32, _pp]),

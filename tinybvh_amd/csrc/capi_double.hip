@@ -3,7 +3,8 @@
 // A BVH_DOUBLE scene keeps its device memory in the fields every scene has (they go with the scene: tbvh_free_scene): a BLAS its nodes in
 // `nodes` and its gathered triangle records in `tris`; a TLAS ONE allocation in `nodes` = [TLAS nodes | instance indices | instances | BLAS
 // descriptors], each part 16-byte aligned.  Those buffers count 16-byte blocks: a NodeDbl is 4 of them, a TriDbl 5.  Nothing else of the fp32 machinery (copies, tuners, refit, updates) applies to it: the entry
-// points of those refuse a BVH_DOUBLE scene.
+// points of those refuse a BVH_DOUBLE scene.  Double scenes that move have calls of their own at the end of this file (the kernels are
+// kernels_double_anim.hip): tbvh_rebuild_tlas_double_device / tbvh_update_tlas_double for a TLAS, tbvh_refit_double for a BLAS, and the downloads.
 #include "capi_internal.h"
 
 using namespace tbvh;
@@ -53,12 +54,19 @@ int validateDouble(const NodeDbl* n, uint64_t nNodes, const uint64_t* idx, uint6
 
 bool isDouble(const tbvh_scene* s) { return s->layout == TBVH_LAYOUT_BVH_DOUBLE; }
 
-// TLAS parts inside its one allocation
-struct TlasParts { const uint64_t* idx; const InstanceDbl* inst; const BlasDbl* blas; };
+// TLAS parts inside its one allocation, laid out for what each part may hold (dblCap*: at upload what it holds; a device rebuild needs 2 n - 1 nodes)
+struct TlasLayout { uint64_t oIdx, oInst, oBlas, total; };
+TlasLayout tlasLayout(uint64_t capNodes, uint64_t capIdx, uint64_t capInst, uint64_t nBlas) {
+    TlasLayout l;
+    l.oIdx = align16(capNodes * sizeof(NodeDbl)); l.oInst = l.oIdx + align16(capIdx * 8); l.oBlas = l.oInst + capInst * sizeof(InstanceDbl);
+    l.total = l.oBlas + nBlas * sizeof(BlasDbl);
+    return l;
+}
+struct TlasParts { NodeDbl* nodes; uint64_t* idx; InstanceDbl* inst; BlasDbl* blas; };
 TlasParts tlasParts(const tbvh_scene* s) {
-    const char* base = (const char*)s->nodes.get();
-    const uint64_t oIdx = align16(s->nTlasNodes * sizeof(NodeDbl)), oInst = oIdx + align16(s->nTlasIdx * 8), oBlas = oInst + s->nInst * sizeof(InstanceDbl);
-    return TlasParts{(const uint64_t*)(base + oIdx), (const InstanceDbl*)(base + oInst), (const BlasDbl*)(base + oBlas)};
+    char* base = (char*)s->nodes.get();
+    const TlasLayout l = tlasLayout(s->dblCapNodes, s->dblCapIdx, s->dblCapInst, s->nBlas);
+    return TlasParts{(NodeDbl*)base, (uint64_t*)(base + l.oIdx), (InstanceDbl*)(base + l.oInst), (BlasDbl*)(base + l.oBlas)};
 }
 
 // one query launch on the context's stream (asynchronous), the ray pool and stack spill shared with launchQuery (capi_query.hip)
@@ -202,6 +210,7 @@ int tbvh_upload_bvh_double(tbvh_context* c, const void* nodes64, uint64_t nNodes
     launch_gather_tris_dbl(dIdx, dVerts, (TriDbl*)s->tris.get(), nIdx, c->stream);
     if (hipGetLastError() != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) return bail(TBVH_E_HIP, "triangle gather failed");
     s->nNodes = (uint32_t)nNodes;
+    s->dblTris = nTris; s->dblRecs = nIdx;
     s->bytes = nNodes * sizeof(NodeDbl) + nIdx * sizeof(TriDbl);
     *out = s;
     return 0;
@@ -227,7 +236,9 @@ int tbvh_upload_tlas_double(tbvh_context* c, const void* nodes64, uint64_t nNode
     tbvh_scene* s = newScene(c, TBVH_LAYOUT_BVH_DOUBLE);
     if (!s) return fail(TBVH_E_NOMEM, "out of host memory");
     s->isTlas = true; s->nTlasNodes = nNodes; s->nTlasIdx = nIdx; s->nInst = nInst; s->nBlas = nBlas; s->nNodes = (uint32_t)nNodes;
-    const uint64_t oIdx = align16(nNodes * sizeof(NodeDbl)), oInst = oIdx + align16(nIdx * 8), oBlas = oInst + nInst * sizeof(InstanceDbl), total = oBlas + nBlas * sizeof(BlasDbl);
+    s->dblCapNodes = nNodes; s->dblCapIdx = nIdx; s->dblCapInst = nInst;
+    const TlasLayout lay = tlasLayout(nNodes, nIdx, nInst, nBlas);
+    const uint64_t oIdx = lay.oIdx, oInst = lay.oInst, oBlas = lay.oBlas, total = lay.total;
     if (s->nodes.alloc(total / 16) != hipSuccess) { tbvh_free_scene(s); return fail(TBVH_E_NOMEM, "tbvh_upload_tlas_double: out of device memory"); }
     char* base = (char*)s->nodes.get();
     if (hipMemcpyAsync(base, nodes64, nNodes * sizeof(NodeDbl), hipMemcpyHostToDevice, c->stream) != hipSuccess ||
@@ -344,6 +355,179 @@ int tbvh_host_build_tlas_double(void* instances320, uint64_t nInst, const double
         return fail(TBVH_E_NOMEM, "out of host memory while building");
     }
     *out = h;
+    return 0;
+}
+
+}  // extern "C"
+
+// ---- double scenes that move ----------------------------------------------------------------------------------------------------------
+
+namespace {
+
+// what every call below refuses before it looks at anything else: a null handle, an fp32 scene, a scene the caller has freed, the wrong kind
+int checkDoubleScene(const tbvh_scene* s, bool wantTlas, const char* who) {
+    if (!s) return fail(TBVH_E_INVALID, "%s: null scene", who);
+    if (!isDouble(s)) return fail(TBVH_E_INVALID, "%s: scene layout %d is not BVH_DOUBLE", who, s->layout);
+    if (s->zombie) return fail(TBVH_E_INVALID, "%s: the scene has been freed (a TLAS still holds its memory)", who);
+    if (wantTlas && !s->isTlas) return fail(TBVH_E_INVALID, "%s: not a TLAS (a BVH_DOUBLE BLAS takes tbvh_refit_double / tbvh_double_download)", who);
+    if (!wantTlas && s->isTlas)
+        return fail(TBVH_E_INVALID, "%s: a TLAS (it takes tbvh_rebuild_tlas_double_device / tbvh_update_tlas_double / tbvh_tlas_double_download)", who);
+    return 0;
+}
+
+void accountTlas(tbvh_scene* s) { s->bytes = tlasLayout(s->dblCapNodes, s->dblCapIdx, s->dblCapInst, s->nBlas).total + s->buildScratch.count(); }
+
+// The TLAS in a new allocation whose parts hold capNodes / capIdx / capInst (each at least what the scene holds now): everything is carried over, the
+// BLAS descriptors with it, so the scene answers as before; synchronizes, then the old allocation goes.  A failure leaves the scene as it was.
+int moveTlas(tbvh_scene* s, uint64_t capNodes, uint64_t capIdx, uint64_t capInst, const char* who) {
+    tbvh_context* c = s->ctx;
+    const TlasLayout l = tlasLayout(capNodes, capIdx, capInst, s->nBlas);
+    DevBuf<float4> fresh;
+    if (fresh.alloc(l.total / 16) != hipSuccess) return fail(TBVH_E_NOMEM, "%s: out of device memory", who);
+    const TlasParts o = tlasParts(s);
+    char* base = (char*)fresh.get();
+    if (hipMemcpyAsync(base, o.nodes, s->nTlasNodes * sizeof(NodeDbl), hipMemcpyDeviceToDevice, c->stream) != hipSuccess ||
+        hipMemcpyAsync(base + l.oIdx, o.idx, s->nTlasIdx * 8, hipMemcpyDeviceToDevice, c->stream) != hipSuccess ||
+        hipMemcpyAsync(base + l.oInst, o.inst, s->nInst * sizeof(InstanceDbl), hipMemcpyDeviceToDevice, c->stream) != hipSuccess ||
+        hipMemcpyAsync(base + l.oBlas, o.blas, s->nBlas * sizeof(BlasDbl), hipMemcpyDeviceToDevice, c->stream) != hipSuccess ||
+        hipStreamSynchronize(c->stream) != hipSuccess)
+        return fail(TBVH_E_HIP, "%s: moving the TLAS failed", who);
+    s->nodes = std::move(fresh);
+    s->dblCapNodes = capNodes; s->dblCapIdx = capIdx; s->dblCapInst = capInst;
+    accountTlas(s);
+    return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int tbvh_rebuild_tlas_double_device(tbvh_scene* s, const void* transformsDbl16, int onDevice) {
+    const char* who = "tbvh_rebuild_tlas_double_device";
+    if (int r = checkDoubleScene(s, true, who)) return r;
+    if (transformsDbl16 && onDevice && (((uintptr_t)transformsDbl16) & 7)) return fail(TBVH_E_INVALID, "%s: device transforms must be 8-byte aligned", who);
+    tbvh_context* c = s->ctx;
+    TBVH_ENTER(c);
+    const uint64_t n = s->nInst;
+    if (n == 0 || n > 0x7fffffffull) return fail(TBVH_E_INVALID, "%s: %llu instances", who, (unsigned long long)n);
+    // an LBVH over n leaves has 2n - 1 nodes and n index entries: the first rebuild moves an uploaded TLAS that holds fewer
+    const uint64_t nNodes = 2 * n - 1;
+    if (s->dblCapNodes < nNodes || s->dblCapIdx < n)
+        if (int r = moveTlas(s, std::max(s->dblCapNodes, nNodes), std::max(s->dblCapIdx, n), s->dblCapInst, who)) return r;
+    if (s->buildScratchFor != n) {
+        s->buildScratchFor = 0;
+        const size_t bytes = tlas_dbl_build_scratch_bytes((uint32_t)n, &s->sortTempBytes);
+        if (s->buildScratch.alloc(bytes) != hipSuccess) { accountTlas(s); return fail(TBVH_E_NOMEM, "%s: out of device memory for %zu bytes of scratch", who, bytes); }
+        s->buildScratchFor = n;
+        accountTlas(s);
+    }
+    const double* xf = nullptr;
+    if (transformsDbl16) {
+        if (onDevice) xf = (const double*)transformsDbl16;
+        else {
+            double* stage = tlas_dbl_xform_stage(s->buildScratch, (uint32_t)n, s->sortTempBytes);
+            HIP_TRY(hipMemcpyAsync(stage, transformsDbl16, n * 128, hipMemcpyHostToDevice, c->stream));
+            xf = stage;
+        }
+    }
+    const TlasParts p = tlasParts(s);
+    HIP_TRY(timedBegin(c));
+    HIP_TRY(launch_tlas_dbl_rebuild(p.nodes, p.idx, p.inst, p.blas, s->nBlas, xf, (uint32_t)n, s->buildScratch, s->sortTempBytes, c->stream));
+    s->nTlasNodes = nNodes; s->nTlasIdx = n; s->nNodes = (uint32_t)nNodes;
+    HIP_TRY(timedEnd(c));
+    return 0;
+}
+
+int tbvh_update_tlas_double(tbvh_scene* s, const void* nodes64, uint64_t nNodes, const uint64_t* idx, uint64_t nIdx, const void* instances320, uint64_t nInst) {
+    const char* who = "tbvh_update_tlas_double";
+    if (int r = checkDoubleScene(s, true, who)) return r;
+    if (!nodes64 || !idx || !instances320 || !nIdx || !nInst) return fail(TBVH_E_INVALID, "%s: null/empty argument", who);
+    // the upload's checks, all of them before the scene is touched: a refused update (TBVH_E_INVALID: the scene keeps what it has) leaves the old TLAS answering
+    if (validateDouble((const NodeDbl*)nodes64, nNodes, idx, nIdx, nInst, who, "n_inst")) return TBVH_E_INVALID;
+    const InstanceDbl* inst = (const InstanceDbl*)instances320;
+    for (uint64_t i = 0; i < nInst; i++)
+        if (inst[i].blasIdx >= s->nBlas)
+            return fail(TBVH_E_INVALID, "%s: instance %llu: blasIdx %llu >= n_blas = %llu", who, (unsigned long long)i, (unsigned long long)inst[i].blasIdx, (unsigned long long)s->nBlas);
+    tbvh_context* c = s->ctx;
+    TBVH_ENTER(c);
+    if (nNodes > s->dblCapNodes || nIdx > s->dblCapIdx || nInst > s->dblCapInst)   // the TLAS grew
+        if (int r = moveTlas(s, std::max(s->dblCapNodes, nNodes), std::max(s->dblCapIdx, nIdx), std::max(s->dblCapInst, nInst), who)) return r;
+    const TlasParts p = tlasParts(s);
+    if (hipMemcpyAsync(p.nodes, nodes64, nNodes * sizeof(NodeDbl), hipMemcpyHostToDevice, c->stream) != hipSuccess ||
+        hipMemcpyAsync(p.idx, idx, nIdx * 8, hipMemcpyHostToDevice, c->stream) != hipSuccess ||
+        hipMemcpyAsync(p.inst, inst, nInst * sizeof(InstanceDbl), hipMemcpyHostToDevice, c->stream) != hipSuccess ||
+        hipStreamSynchronize(c->stream) != hipSuccess)   // (the caller's arrays may go away)
+        return fail(TBVH_E_HIP, "%s: copy to the device failed", who);
+    s->nTlasNodes = nNodes; s->nTlasIdx = nIdx; s->nInst = nInst; s->nNodes = (uint32_t)nNodes;
+    return 0;
+}
+
+int tbvh_tlas_double_download(tbvh_scene* s, void* nodes64, uint64_t capNodes, uint64_t* idx, uint64_t capIdx, void* instances320, uint64_t capInst,
+                              uint64_t* nNodesOut) {
+    const char* who = "tbvh_tlas_double_download";
+    if (int r = checkDoubleScene(s, true, who)) return r;
+    tbvh_context* c = s->ctx;
+    TBVH_ENTER(c);
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (nNodesOut) *nNodesOut = s->nTlasNodes;
+    if (nodes64 && capNodes < s->nTlasNodes) return fail(TBVH_E_INVALID, "%s: node buffer too small", who);
+    if (idx && capIdx < s->nTlasIdx) return fail(TBVH_E_INVALID, "%s: index buffer too small", who);
+    if (instances320 && capInst < s->nInst) return fail(TBVH_E_INVALID, "%s: instance buffer too small", who);
+    const TlasParts p = tlasParts(s);
+    if (nodes64) HIP_TRY(hipMemcpy(nodes64, p.nodes, s->nTlasNodes * sizeof(NodeDbl), hipMemcpyDeviceToHost));
+    if (idx) HIP_TRY(hipMemcpy(idx, p.idx, s->nTlasIdx * 8, hipMemcpyDeviceToHost));
+    if (instances320) HIP_TRY(hipMemcpy(instances320, p.inst, s->nInst * sizeof(InstanceDbl), hipMemcpyDeviceToHost));
+    return 0;
+}
+
+int tbvh_double_download(tbvh_scene* s, void* nodes64, uint64_t capNodes, uint64_t* nNodesOut) {
+    const char* who = "tbvh_double_download";
+    if (int r = checkDoubleScene(s, false, who)) return r;
+    tbvh_context* c = s->ctx;
+    TBVH_ENTER(c);
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (nNodesOut) *nNodesOut = s->nNodes;
+    if (nodes64 && capNodes < s->nNodes) return fail(TBVH_E_INVALID, "%s: node buffer too small", who);
+    if (nodes64) HIP_TRY(hipMemcpy(nodes64, s->nodes.get(), (uint64_t)s->nNodes * sizeof(NodeDbl), hipMemcpyDeviceToHost));
+    return 0;
+}
+
+int tbvh_refit_double(tbvh_scene* s, const void* vertsDbl3, uint64_t nTris, int onDevice) {
+    const char* who = "tbvh_refit_double";
+    if (int r = checkDoubleScene(s, false, who)) return r;
+    if (!vertsDbl3) return fail(TBVH_E_INVALID, "%s: null vertex array", who);
+    if (nTris != s->dblTris) return fail(TBVH_E_INVALID, "%s: %llu triangles, the scene was uploaded with %llu", who, (unsigned long long)nTris, (unsigned long long)s->dblTris);
+    if (onDevice && (((uintptr_t)vertsDbl3) & 7)) return fail(TBVH_E_INVALID, "%s: device vertices must be 8-byte aligned", who);
+    tbvh_context* c = s->ctx;
+    TBVH_ENTER(c);
+    const uint32_t nNodes = s->nNodes;
+    if (!s->refitScratch) {
+        // first refit of the scene: parent[] | leaf list | flags, nNodes words each; the walk that fills the first two needs two frontier lists once
+        DevBuf<uint32_t> fronts;
+        DevBuf<void> keep;
+        if (keep.alloc((size_t)nNodes * 12) != hipSuccess || fronts.alloc((size_t)nNodes * 2 + 1) != hipSuccess) return fail(TBVH_E_NOMEM, "%s: out of device memory", who);
+        uint32_t* parent = (uint32_t*)keep.get();
+        uint32_t nLeaves = 0;
+        launch_parents_dbl((const NodeDbl*)s->nodes.get(), nNodes, parent, parent + nNodes, fronts, fronts + nNodes, fronts + 2 * (size_t)nNodes, c->stream);
+        if (hipGetLastError() != hipSuccess || hipMemcpyAsync(&nLeaves, fronts + 2 * (size_t)nNodes, 4, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
+            hipStreamSynchronize(c->stream) != hipSuccess)
+            return fail(TBVH_E_HIP, "%s: the parent pass failed", who);
+        s->refitScratch = std::move(keep);
+        s->dblLeaves = nLeaves;
+        s->bytes += (uint64_t)nNodes * 12;
+    }
+    const double* dv = (const double*)vertsDbl3;
+    if (!onDevice) {
+        const size_t had = s->vertStage.count();
+        if (s->vertStage.reserve(nTris * 72) != hipSuccess) { s->bytes -= had; return fail(TBVH_E_NOMEM, "%s: out of device memory for the vertices", who); }
+        s->bytes += s->vertStage.count() - had;
+        HIP_TRY(hipMemcpyAsync(s->vertStage, vertsDbl3, nTris * 72, hipMemcpyHostToDevice, c->stream));
+        dv = (const double*)s->vertStage.get();
+    }
+    uint32_t* parent = (uint32_t*)s->refitScratch.get();
+    HIP_TRY(timedBegin(c));
+    HIP_TRY(launch_refit_dbl((NodeDbl*)s->nodes.get(), nNodes, (TriDbl*)s->tris.get(), s->dblRecs, dv, nTris, parent + nNodes, s->dblLeaves, parent, parent + 2 * (size_t)nNodes, c->stream));
+    HIP_TRY(timedEnd(c));
     return 0;
 }
 

@@ -267,6 +267,12 @@ struct tbvh_scene {
     uint32_t sphMaxLeaf = 1, sphRadius = 16;
     size_t scanTempBytes = 0;
     DevBuf<uint32_t> sphIdx;
+    // BVH_DOUBLE scenes that move (capi_double.hip).  A TLAS: what the parts of its one allocation hold (tlasParts lays them out by these, so a smaller
+    // tree goes in place); the rebuild keeps its scratch in buildScratch (sized for buildScratchFor instances).  A BLAS: its triangle count, and from the
+    // first refit on parent[] | leaf list | flags in refitScratch (dblLeaves leaves); host vertices are staged in vertStage.  `bytes` counts them all.
+    uint64_t dblCapNodes = 0, dblCapIdx = 0, dblCapInst = 0;
+    uint64_t dblTris = 0, dblRecs = 0;
+    uint32_t dblLeaves = 0;
 };
 
 struct BLASInstanceCheck { float m[32]; float mn[3]; uint32_t blasIdx; float mx[3]; uint32_t mask; uint32_t pad[8]; };

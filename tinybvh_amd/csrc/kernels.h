@@ -75,6 +75,18 @@ struct DoubleArgs {
 };
 void launch_double(bool anyhit, bool tlas, const DoubleArgs& q, uint32_t* status, uint32_t blocks, hipStream_t s);
 void launch_gather_tris_dbl(const uint64_t* primIdx, const double* verts, TriDbl* out, uint64_t nIdx, hipStream_t s);
+// BVH_Double scenes that move (kernels_double_anim.hip).  TLAS rebuild: BLASInstanceEx::Update of every instance (transformsDev: 16 doubles per instance, or
+// nullptr: the transforms in the records; the BLAS boxes are node 0 of each BLAS), then an LBVH of 2 n - 1 nodes over the instance boxes into tlasNodes /
+// tlasIdx.  The scratch is one allocation of tlas_dbl_build_scratch_bytes(n); host transforms are staged in its part tlas_dbl_xform_stage names.
+size_t tlas_dbl_build_scratch_bytes(uint32_t n, size_t* sortTempBytes);
+double* tlas_dbl_xform_stage(void* scratch, uint32_t n, size_t sortTempBytes);
+hipError_t launch_tlas_dbl_rebuild(NodeDbl* tlasNodes, uint64_t* tlasIdx, InstanceDbl* instances, const BlasDbl* blas, uint64_t nBlas, const double* transformsDev,
+                                   uint32_t n, void* scratch, size_t sortTempBytes, hipStream_t s);
+// BLAS refit: parent[] and the leaf list of a tree (once per scene; nNodes entries each, frontA / frontB: nNodes entries of scratch), then per call the
+// records and boxes from verts (9 doubles per triangle); flags: nNodes words, zeroed by the launcher
+void launch_parents_dbl(const NodeDbl* nodes, uint32_t nNodes, uint32_t* parent, uint32_t* leaves, uint32_t* frontA, uint32_t* frontB, uint32_t* nLeavesOut, hipStream_t s);
+hipError_t launch_refit_dbl(NodeDbl* nodes, uint32_t nNodes, TriDbl* tris, uint64_t nRecs, const double* verts, uint64_t nTris, const uint32_t* leaves,
+                            uint32_t nLeaves, const uint32_t* parent, uint32_t* flags, hipStream_t s);
 
 // VoxelSet scenes (kernels_voxel.hip): vox = one set's [top grid 16 | grid 32768 | bricks] words; tlasNodes != nullptr: a BVH_GPU-format TLAS over
 // BLASInstance records whose BLASes are all voxel sets (BlasDesc::nodes = each set's array)

@@ -1,0 +1,369 @@
+// kernels_double_anim.hip — BVH_Double scenes that move, for gfx950 (MI355X), in fp64: the per-frame TLAS rebuild and the BLAS refit.
+//
+// TLAS rebuild.  Replaces, for a TLAS_Double that already lives on the GPU, the host work of the reference's double frame loop
+// (tiny_bvh_anim_double.cpp:110: "just move build to Tick if instance transforms are not static"): BLASInstanceEx::Update for every
+// instance (tiny_bvh.h:8432-8472: invert the transform, world box of the 8 transformed BLAS-box corners) and
+// BVH_Double::Build( BLASInstanceEx*, ... ) (tiny_bvh.h:7955-...).  The instance records keep the reference's 320-byte format and the
+// result is a BVH_Double node array + instance index list, exactly what k_double traverses.  Five steps, as kernels_tlasbuild.hip:
+//   1. instance update, one thread per instance: the expressions of capi_double.hip: updateInstanceDbl, operation for operation (the
+//      Makefile's -ffp-contract=off keeps them uncontracted), so device-updated and host-updated records are bit-identical.  The BLAS box
+//      is node 0 of the BLAS (tiny_bvh.h:8133: aabbMin / aabbMax = bvhNode[0]'s), read through the BlasDbl descriptors: no bounds argument.
+//   2. 63-bit Morton keys, 21 bits per axis, of the box centres relative to the centre bounds, computed in double.  (30 bits over an
+//      extent of 1e7 units are cells of 1e4 units: a cluster of nearby instances far from the rest would share ONE key.)  The centre
+//      bounds are reduced per wave, then one set of 64-bit atomicMin / atomicMax per wave on an order-preserving encoding.
+//   3. hipcub::DeviceRadixSort::SortPairs on the uint64_t keys.
+//   4. Karras 2012 topology in one pass; equal keys are told apart by their position.
+//   5. nodes, bottom-up: leaf threads climb, the second thread to reach an interior node owns it (one atomic flag per node), the first
+//      returns: nothing waits or spins.  Numbering: root = 0, the children of Karras interior node i at 1 + 2 i and 2 + 2 i — 2 n - 1
+//      nodes without an unused slot, as the library's host builder numbers them.  One leaf per instance.
+// The tree is an LBVH instead of the host builder's binned-SAH tree: a different but valid TLAS — hit records do not depend on the TLAS
+// shape (device_common.h: hit_wins_dbl), up to rays that a box of one tree culls within the eight-ulp slack and the other's does not.
+//
+// BLAS refit.  The reference has no BVH_Double::Refit; this is the fp64 twin of kernels_refit.hip: same topology, new vertices.  One
+// thread per leaf rewrites its TriDbl records ({v0, e1 = v1 - v0, e2 = v2 - v0, prim}: the subtractions of k_gather_tris_dbl; prim comes
+// from the record), takes the leaf box from the three VERTICES (v0 + e1 would round) and climbs by parent index under the same
+// second-arrival rule; no stack, so chains of any depth work.  BVH_Double nodes carry no parent index: k_parents_dbl fills a parent array
+// and the list of leaf nodes once per scene, walking the tree from the root (slots the root does not reach — the reference's builder
+// leaves node 1 unused — are never read).
+#include <hip/hip_runtime.h>
+#include <hipcub/hipcub.hpp>
+
+#include <cstdio>
+
+#include "device_common.h"
+#include "kernels.h"
+
+namespace tbvh {
+
+namespace {
+
+constexpr double kDblFar = 1e300;   // BVH_DBL_FAR, tiny_bvh.h:145
+constexpr uint32_t kNoParent = 0xffffffffu;
+
+__device__ __forceinline__ uint64_t enc_f64(double d) {   // order-preserving double -> uint64
+    const uint64_t b = (uint64_t)__double_as_longlong(d);
+    return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
+}
+__device__ __forceinline__ double dec_f64(uint64_t e) {
+    const uint64_t b = (e >> 63) ? (e & 0x7fffffffffffffffull) : ~e;
+    return __longlong_as_double((long long)b);
+}
+
+__device__ __forceinline__ double ld_agent(const double* p) {   // bypass this CU's (non-coherent) L1: a sibling on another CU wrote it
+    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// node `out` = the union of its two children c and c + 1 (tinybvh_min / _max: the ternaries); the children were written by other threads
+__device__ __forceinline__ void write_union(NodeDbl* __restrict__ nodes, uint64_t at, uint64_t c) {
+    const double* l = nodes[c].mn;       // (mn[3], mx[3] are contiguous)
+    const double* r = nodes[c + 1].mn;
+    for (int a = 0; a < 3; a++) {
+        const double lmn = ld_agent(l + a), rmn = ld_agent(r + a), lmx = ld_agent(l + 3 + a), rmx = ld_agent(r + 3 + a);
+        nodes[at].mn[a] = lmn < rmn ? lmn : rmn;
+        nodes[at].mx[a] = lmx > rmx ? lmx : rmx;
+    }
+}
+
+// ---- 1. BLASInstanceEx::Update + InvertTransform (tiny_bvh.h:8432-8472), one thread per instance ----------------------------------
+__global__ void k_instance_update_dbl(InstanceDbl* __restrict__ instances, const double* __restrict__ transforms, const BlasDbl* __restrict__ blas,
+                                      uint32_t n, uint64_t nBlas, unsigned long long* __restrict__ centreBounds) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    double cLo[3] = {kDblFar, kDblFar, kDblFar}, cHi[3] = {-kDblFar, -kDblFar, -kDblFar};   // this lane's centre, reduced over the wave below
+    if (i < n) {
+        InstanceDbl& in = instances[i];
+        double T[16], iT[16];
+        if (transforms) {
+            for (int k = 0; k < 16; k++) { T[k] = transforms[(size_t)i * 16 + k]; in.transform[k] = T[k]; }
+        } else {
+            for (int k = 0; k < 16; k++) T[k] = in.transform[k];
+        }
+        iT[0] = T[5] * T[10] * T[15] - T[5] * T[11] * T[14] - T[9] * T[6] * T[15] + T[9] * T[7] * T[14] + T[13] * T[6] * T[11] - T[13] * T[7] * T[10];
+        iT[1] = -T[1] * T[10] * T[15] + T[1] * T[11] * T[14] + T[9] * T[2] * T[15] - T[9] * T[3] * T[14] - T[13] * T[2] * T[11] + T[13] * T[3] * T[10];
+        iT[2] = T[1] * T[6] * T[15] - T[1] * T[7] * T[14] - T[5] * T[2] * T[15] + T[5] * T[3] * T[14] + T[13] * T[2] * T[7] - T[13] * T[3] * T[6];
+        iT[3] = -T[1] * T[6] * T[11] + T[1] * T[7] * T[10] + T[5] * T[2] * T[11] - T[5] * T[3] * T[10] - T[9] * T[2] * T[7] + T[9] * T[3] * T[6];
+        iT[4] = -T[4] * T[10] * T[15] + T[4] * T[11] * T[14] + T[8] * T[6] * T[15] - T[8] * T[7] * T[14] - T[12] * T[6] * T[11] + T[12] * T[7] * T[10];
+        iT[5] = T[0] * T[10] * T[15] - T[0] * T[11] * T[14] - T[8] * T[2] * T[15] + T[8] * T[3] * T[14] + T[12] * T[2] * T[11] - T[12] * T[3] * T[10];
+        iT[6] = -T[0] * T[6] * T[15] + T[0] * T[7] * T[14] + T[4] * T[2] * T[15] - T[4] * T[3] * T[14] - T[12] * T[2] * T[7] + T[12] * T[3] * T[6];
+        iT[7] = T[0] * T[6] * T[11] - T[0] * T[7] * T[10] - T[4] * T[2] * T[11] + T[4] * T[3] * T[10] + T[8] * T[2] * T[7] - T[8] * T[3] * T[6];
+        iT[8] = T[4] * T[9] * T[15] - T[4] * T[11] * T[13] - T[8] * T[5] * T[15] + T[8] * T[7] * T[13] + T[12] * T[5] * T[11] - T[12] * T[7] * T[9];
+        iT[9] = -T[0] * T[9] * T[15] + T[0] * T[11] * T[13] + T[8] * T[1] * T[15] - T[8] * T[3] * T[13] - T[12] * T[1] * T[11] + T[12] * T[3] * T[9];
+        iT[10] = T[0] * T[5] * T[15] - T[0] * T[7] * T[13] - T[4] * T[1] * T[15] + T[4] * T[3] * T[13] + T[12] * T[1] * T[7] - T[12] * T[3] * T[5];
+        iT[11] = -T[0] * T[5] * T[11] + T[0] * T[7] * T[9] + T[4] * T[1] * T[11] - T[4] * T[3] * T[9] - T[8] * T[1] * T[7] + T[8] * T[3] * T[5];
+        iT[12] = -T[4] * T[9] * T[14] + T[4] * T[10] * T[13] + T[8] * T[5] * T[14] - T[8] * T[6] * T[13] - T[12] * T[5] * T[10] + T[12] * T[6] * T[9];
+        iT[13] = T[0] * T[9] * T[14] - T[0] * T[10] * T[13] - T[8] * T[1] * T[14] + T[8] * T[2] * T[13] + T[12] * T[1] * T[10] - T[12] * T[2] * T[9];
+        iT[14] = -T[0] * T[5] * T[14] + T[0] * T[6] * T[13] + T[4] * T[1] * T[14] - T[4] * T[2] * T[13] - T[12] * T[1] * T[6] + T[12] * T[2] * T[5];
+        iT[15] = T[0] * T[5] * T[10] - T[0] * T[6] * T[9] - T[4] * T[1] * T[10] + T[4] * T[2] * T[9] + T[8] * T[1] * T[6] - T[8] * T[2] * T[5];
+        const double det = T[0] * iT[0] + T[1] * iT[4] + T[2] * iT[8] + T[3] * iT[12];
+        if (det != 0) {   // (the reference returns here and keeps the unscaled cofactors)
+            const double invdet = 1. / det;
+            for (int k = 0; k < 16; k++) iT[k] *= invdet;
+        }
+        for (int k = 0; k < 16; k++) in.invTransform[k] = iT[k];
+        const uint64_t bi = in.blasIdx;
+        const NodeDbl* root = blas[bi < nBlas ? bi : 0].nodes;   // (blasIdx < n_blas: validated by the upload / update)
+        const double bb[6] = {root->mn[0], root->mn[1], root->mn[2], root->mx[0], root->mx[1], root->mx[2]};
+        const double far32 = (double)1e30f;   // aabbMin = bvhdbl3( BVH_FAR ): the float constant
+        double mn[3] = {far32, far32, far32}, mx[3] = {-far32, -far32, -far32};
+        for (int j = 0; j < 8; j++) {
+            const double p[3] = {j & 1 ? bb[3] : bb[0], j & 2 ? bb[4] : bb[1], j & 4 ? bb[5] : bb[2]};
+            // tinybvh_transform_point (tiny_bvh.h:576-584), the w != 1 divide included
+            double t[3] = {T[0] * p[0] + T[1] * p[1] + T[2] * p[2] + T[3], T[4] * p[0] + T[5] * p[1] + T[6] * p[2] + T[7], T[8] * p[0] + T[9] * p[1] + T[10] * p[2] + T[11]};
+            const double w = T[12] * p[0] + T[13] * p[1] + T[14] * p[2] + T[15];
+            if (w != 1) { const double rw = 1. / w; for (int a = 0; a < 3; a++) t[a] = t[a] * rw; }
+            for (int a = 0; a < 3; a++) {
+                mn[a] = mn[a] < t[a] ? mn[a] : t[a];
+                mx[a] = mx[a] > t[a] ? mx[a] : t[a];
+            }
+        }
+        for (int a = 0; a < 3; a++) { in.aabbMin[a] = mn[a]; in.aabbMax[a] = mx[a]; }   // (blasIdx and mask, in the same records, stay)
+        for (int a = 0; a < 3; a++) {
+            const double c = 0.5 * mn[a] + 0.5 * mx[a];
+            if (c > -kDblFar && c < kDblFar) cLo[a] = cHi[a] = c;   // (a NaN or infinite box — w == 0 — takes no part in the bounds; its key is 0)
+        }
+    }
+    // one set of six atomics per wave: the six words share a cache line and same-line atomics are serialised memory-side
+    for (int a = 0; a < 3; a++)
+        for (int o = 32; o > 0; o >>= 1) { cLo[a] = fmin(cLo[a], __shfl_xor(cLo[a], o)); cHi[a] = fmax(cHi[a], __shfl_xor(cHi[a], o)); }
+    if ((threadIdx.x & 63u) == 0)
+        for (int a = 0; a < 3; a++)
+            if (cLo[a] <= cHi[a]) { atomicMin(centreBounds + a, (unsigned long long)enc_f64(cLo[a])); atomicMax(centreBounds + 3 + a, (unsigned long long)enc_f64(cHi[a])); }
+}
+
+// ---- 2. Morton keys ---------------------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ uint64_t spread21(uint64_t v) {   // 21 bits -> every third bit
+    v &= 0x1fffffull;
+    v = (v | (v << 32)) & 0x001f00000000ffffull;
+    v = (v | (v << 16)) & 0x001f0000ff0000ffull;
+    v = (v | (v << 8)) & 0x100f00f00f00f00full;
+    v = (v | (v << 4)) & 0x10c30c30c30c30c3ull;
+    v = (v | (v << 2)) & 0x1249249249249249ull;
+    return v;
+}
+
+__global__ void k_morton_dbl(const InstanceDbl* __restrict__ instances, const unsigned long long* __restrict__ centreBounds, uint32_t n,
+                             uint64_t* __restrict__ keys, uint32_t* __restrict__ vals) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const InstanceDbl& in = instances[i];
+    uint64_t q[3];
+    for (int a = 0; a < 3; a++) {
+        const double c = 0.5 * in.aabbMin[a] + 0.5 * in.aabbMax[a];
+        const double lo = dec_f64(centreBounds[a]), hi = dec_f64(centreBounds[3 + a]);
+        const double ext = hi - lo;
+        double u = ext > 0 ? (c - lo) / ext : 0.;
+        u = u > 0 ? (u < 1 ? u : 1.) : 0.;   // (NaN -> 0)
+        const uint64_t v = (uint64_t)(u * 2097151.0);
+        q[a] = v > 2097151ull ? 2097151ull : v;
+    }
+    keys[i] = (spread21(q[0]) << 2) | (spread21(q[1]) << 1) | spread21(q[2]);
+    vals[i] = i;
+}
+
+// ---- 4. Karras 2012 topology ---------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ int delta64(const uint64_t* __restrict__ keys, int n, int i, int j) {
+    if (j < 0 || j >= n) return -1;
+    const uint64_t a = keys[i], b = keys[j];
+    return a == b ? 64 + __clz((uint32_t)(i ^ j)) : __clzll((long long)(a ^ b));
+}
+
+// Karras ids: interior node i -> i, leaf k -> (n - 1) + k.  parent[id] = the Karras interior node above id, slot[id] = where id goes in the
+// BVH_Double node array: the root at 0, the children of interior node i at 1 + 2 i and 2 + 2 i.
+__global__ void k_lbvh_topology_dbl(const uint64_t* __restrict__ keys, uint32_t n, uint32_t* __restrict__ parent, uint32_t* __restrict__ slot) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    const int N = (int)n;
+    if (i >= N - 1) return;
+    const int d = delta64(keys, N, i, i + 1) - delta64(keys, N, i, i - 1) >= 0 ? 1 : -1;
+    const int dmin = delta64(keys, N, i, i - d);
+    int lmax = 2;
+    while (delta64(keys, N, i, i + lmax * d) > dmin) lmax <<= 1;
+    int l = 0;
+    for (int t = lmax >> 1; t >= 1; t >>= 1)
+        if (delta64(keys, N, i, i + (l + t) * d) > dmin) l += t;
+    const int j = i + l * d;
+    const int dnode = delta64(keys, N, i, j);
+    int s = 0;
+    for (int t = (l + 1) >> 1;; t = (t + 1) >> 1) {
+        if (delta64(keys, N, i, i + (s + t) * d) > dnode) s += t;
+        if (t <= 1) break;
+    }
+    const int gamma = i + s * d + (d < 0 ? d : 0);
+    const int lo = i < j ? i : j, hi = i < j ? j : i;
+    const uint32_t left = lo == gamma ? (uint32_t)(N - 1 + gamma) : (uint32_t)gamma;
+    const uint32_t right = hi == gamma + 1 ? (uint32_t)(N - 1 + gamma + 1) : (uint32_t)(gamma + 1);
+    parent[left] = (uint32_t)i; slot[left] = 1u + 2u * (uint32_t)i;
+    parent[right] = (uint32_t)i; slot[right] = 2u + 2u * (uint32_t)i;
+    if (i == 0) slot[0] = 0u;
+}
+
+// ---- 5. nodes: one thread per leaf writes the leaf node, then climbs ---------------------------------------------------------------------
+__global__ void k_lbvh_nodes_dbl(const uint32_t* __restrict__ sortedIdx, const InstanceDbl* __restrict__ instances, const uint32_t* __restrict__ parent,
+                                 const uint32_t* __restrict__ slot, uint32_t* __restrict__ flags, uint32_t n, NodeDbl* __restrict__ nodes,
+                                 uint64_t* __restrict__ tlasIdx) {
+    const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= n) return;
+    const uint32_t inst = sortedIdx[k];   // (< n: a permutation of the values k_morton_dbl wrote)
+    tlasIdx[k] = inst;
+    const uint32_t id = n - 1 + k;
+    const InstanceDbl& in = instances[inst];
+    NodeDbl* ln = nodes + (n == 1 ? 0u : slot[id]);   // with a single instance the leaf IS the root
+    for (int a = 0; a < 3; a++) { ln->mn[a] = in.aabbMin[a]; ln->mx[a] = in.aabbMax[a]; }
+    ln->leftFirst = k; ln->triCount = 1;
+    if (n == 1) return;
+    __threadfence();
+    uint32_t node = parent[id];
+    for (;;) {
+        if (atomicAdd(flags + node, 1u) == 0u) return;   // first to arrive: the sibling subtree is not finished yet
+        __threadfence();
+        const uint32_t at = slot[node], c = 1u + 2u * node;
+        write_union(nodes, at, c);
+        nodes[at].leftFirst = c; nodes[at].triCount = 0;
+        if (node == 0) return;
+        __threadfence();
+        node = parent[node];
+    }
+}
+
+// ---- refit ----------------------------------------------------------------------------------------------------------------------------
+// Once per scene, ONE workgroup: walk the tree from the root level by level (two frontier lists in global memory), parent[] of every node
+// reached and the list of the leaves reached.  A tree (validated at upload) reaches every node at most once, so at most nNodes entries are
+// ever appended; the bounds checks keep a wrong blob from writing beyond them all the same.
+constexpr uint32_t kParentsBlock = 1024;
+__global__ __launch_bounds__(kParentsBlock) void k_parents_dbl(const NodeDbl* __restrict__ nodes, uint32_t nNodes, uint32_t* __restrict__ parent,
+                                                               uint32_t* __restrict__ leaves, uint32_t* frontA, uint32_t* frontB, uint32_t* __restrict__ nLeavesOut) {
+    __shared__ uint32_t nCur, nNext, nLeaf;
+    if (threadIdx.x == 0) { frontA[0] = 0; parent[0] = kNoParent; nCur = 1; nNext = 0; nLeaf = 0; }
+    __syncthreads();
+    for (;;) {
+        const uint32_t cur = nCur;
+        if (cur == 0) break;
+        for (uint32_t i = threadIdx.x; i < cur; i += kParentsBlock) {
+            const uint32_t node = frontA[i];
+            if (nodes[node].triCount != 0) {
+                const uint32_t at = atomicAdd(&nLeaf, 1u);
+                if (at < nNodes) leaves[at] = node;
+            } else {
+                const uint64_t c = nodes[node].leftFirst;
+                if (c + 1 < nNodes) {
+                    const uint32_t at = atomicAdd(&nNext, 2u);
+                    if (at + 1 < nNodes) { parent[c] = node; parent[c + 1] = node; frontB[at] = (uint32_t)c; frontB[at + 1] = (uint32_t)c + 1u; }
+                }
+            }
+        }
+        __syncthreads();
+        if (threadIdx.x == 0) { nCur = nNext < nNodes ? nNext : 0u; nNext = 0; }
+        uint32_t* t = frontA; frontA = frontB; frontB = t;
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) *nLeavesOut = nLeaf < nNodes ? nLeaf : nNodes;
+}
+
+// One thread per leaf node: its records from the new vertices, its box from the vertices, then the climb.
+__global__ void k_refit_dbl(NodeDbl* __restrict__ nodes, uint32_t nNodes, TriDbl* __restrict__ tris, uint64_t nRecs, const double* __restrict__ verts,
+                            uint64_t nTris, const uint32_t* __restrict__ leaves, uint32_t nLeaves, const uint32_t* __restrict__ parent,
+                            uint32_t* __restrict__ flags) {
+    const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= nLeaves) return;
+    const uint32_t leaf = leaves[j];
+    const uint64_t first = nodes[leaf].leftFirst, cnt = nodes[leaf].triCount;
+    double mn[3] = {kDblFar, kDblFar, kDblFar}, mx[3] = {-kDblFar, -kDblFar, -kDblFar};
+    for (uint64_t r = first; r < first + cnt && r < nRecs; r++) {
+        const uint64_t p = tris[r].prim;
+        if (p >= nTris) continue;   // (< n_tris: validated at upload)
+        const double* v = verts + p * 9;
+        for (int a = 0; a < 3; a++) {
+            const double x = v[a], y = v[3 + a], z = v[6 + a];
+            tris[r].v0[a] = x; tris[r].e1[a] = y - x; tris[r].e2[a] = z - x;
+            const double lo = x < y ? (x < z ? x : z) : (y < z ? y : z), hi = x > y ? (x > z ? x : z) : (y > z ? y : z);
+            mn[a] = mn[a] < lo ? mn[a] : lo;
+            mx[a] = mx[a] > hi ? mx[a] : hi;
+        }
+    }
+    for (int a = 0; a < 3; a++) { nodes[leaf].mn[a] = mn[a]; nodes[leaf].mx[a] = mx[a]; }
+    uint32_t node = parent[leaf];
+    if (node == kNoParent) return;   // the root is a leaf
+    __threadfence();
+    for (;;) {
+        if (node >= nNodes || atomicAdd(flags + node, 1u) == 0u) return;   // first to arrive: the sibling subtree is not finished yet
+        __threadfence();
+        write_union(nodes, node, nodes[node].leftFirst);
+        node = parent[node];
+        if (node == kNoParent) return;
+        __threadfence();
+    }
+}
+
+struct Scratch {
+    uint64_t *keysA, *keysB;
+    uint32_t *valsA, *valsB, *parent, *slot, *flags;
+    unsigned long long* bounds;
+    double* xforms;
+    void* sortTemp;
+    size_t total;
+};
+// one allocation, carved up here (every part 256-byte aligned); base may be null to just measure
+Scratch carve(void* base, uint32_t n, size_t sortTempBytes) {
+    char* p = (char*)base;
+    auto take = [&](size_t bytes) { char* r = p; p += (bytes + 255) & ~(size_t)255; return r; };
+    Scratch s;
+    s.keysA = (uint64_t*)take((size_t)n * 8); s.keysB = (uint64_t*)take((size_t)n * 8);
+    s.valsA = (uint32_t*)take((size_t)n * 4); s.valsB = (uint32_t*)take((size_t)n * 4);
+    s.parent = (uint32_t*)take((size_t)n * 8); s.slot = (uint32_t*)take((size_t)n * 8);   // 2n - 1 Karras ids
+    s.flags = (uint32_t*)take((size_t)n * 4);
+    s.bounds = (unsigned long long*)take(64);
+    s.xforms = (double*)take((size_t)n * 128);   // staged host transforms
+    s.sortTemp = take(sortTempBytes);
+    s.total = (size_t)(p - (char*)base);
+    return s;
+}
+
+}  // namespace
+
+size_t tlas_dbl_build_scratch_bytes(uint32_t n, size_t* sortTempBytes) {
+    size_t tmp = 0;
+    hipcub::DeviceRadixSort::SortPairs(nullptr, tmp, (const uint64_t*)nullptr, (uint64_t*)nullptr, (const uint32_t*)nullptr, (uint32_t*)nullptr, (int)n, 0, 64);
+    *sortTempBytes = tmp;
+    return carve(nullptr, n, tmp).total;
+}
+
+double* tlas_dbl_xform_stage(void* scratch, uint32_t n, size_t sortTempBytes) { return carve(scratch, n, sortTempBytes).xforms; }
+
+hipError_t launch_tlas_dbl_rebuild(NodeDbl* tlasNodes, uint64_t* tlasIdx, InstanceDbl* instances, const BlasDbl* blas, uint64_t nBlas, const double* transformsDev,
+                                   uint32_t n, void* scratch, size_t sortTempBytes, hipStream_t s) {
+    const Scratch sc = carve(scratch, n, sortTempBytes);
+    hipError_t e;
+    if ((e = hipMemsetAsync(sc.bounds, 0xff, 24, s)) != hipSuccess) return e;       // centre minima: +max in the ordered encoding
+    if ((e = hipMemsetAsync(sc.bounds + 3, 0x00, 24, s)) != hipSuccess) return e;    // centre maxima
+    if ((e = hipMemsetAsync(sc.flags, 0, (size_t)n * 4, s)) != hipSuccess) return e;
+    const uint32_t bs = 128, nb = (n + bs - 1) / bs;
+#define TBVH_STEP(what) do { if ((e = hipGetLastError()) != hipSuccess) { fprintf(stderr, "[tinybvh_amd] TLAS_Double rebuild: %s: %s\n", what, hipGetErrorString(e)); return e; } } while (0)
+    hipLaunchKernelGGL(k_instance_update_dbl, dim3(nb), dim3(bs), 0, s, instances, transformsDev, blas, n, nBlas, sc.bounds);
+    TBVH_STEP("instance update");
+    hipLaunchKernelGGL(k_morton_dbl, dim3(nb), dim3(bs), 0, s, instances, sc.bounds, n, sc.keysA, sc.valsA);
+    TBVH_STEP("morton keys");
+    size_t tmp = sortTempBytes;
+    if ((e = hipcub::DeviceRadixSort::SortPairs(sc.sortTemp, tmp, sc.keysA, sc.keysB, sc.valsA, sc.valsB, (int)n, 0, 64, s)) != hipSuccess) {
+        fprintf(stderr, "[tinybvh_amd] TLAS_Double rebuild: radix sort (%zu temp bytes): %s\n", sortTempBytes, hipGetErrorString(e));
+        return e;
+    }
+    if (n > 1) hipLaunchKernelGGL(k_lbvh_topology_dbl, dim3(nb), dim3(bs), 0, s, sc.keysB, n, sc.parent, sc.slot);
+    TBVH_STEP("topology");
+    hipLaunchKernelGGL(k_lbvh_nodes_dbl, dim3(nb), dim3(bs), 0, s, sc.valsB, instances, sc.parent, sc.slot, sc.flags, n, tlasNodes, tlasIdx);
+    TBVH_STEP("nodes");
+#undef TBVH_STEP
+    return hipGetLastError();
+}
+
+void launch_parents_dbl(const NodeDbl* nodes, uint32_t nNodes, uint32_t* parent, uint32_t* leaves, uint32_t* frontA, uint32_t* frontB, uint32_t* nLeavesOut, hipStream_t s) {
+    hipLaunchKernelGGL(k_parents_dbl, dim3(1), dim3(kParentsBlock), 0, s, nodes, nNodes, parent, leaves, frontA, frontB, nLeavesOut);
+}
+
+hipError_t launch_refit_dbl(NodeDbl* nodes, uint32_t nNodes, TriDbl* tris, uint64_t nRecs, const double* verts, uint64_t nTris, const uint32_t* leaves,
+                            uint32_t nLeaves, const uint32_t* parent, uint32_t* flags, hipStream_t s) {
+    hipError_t e;
+    if ((e = hipMemsetAsync(flags, 0, (size_t)nNodes * 4, s)) != hipSuccess) return e;
+    const uint32_t bs = 128;
+    hipLaunchKernelGGL(k_refit_dbl, dim3((nLeaves + bs - 1) / bs), dim3(bs), 0, s, nodes, nNodes, tris, nRecs, verts, nTris, leaves, nLeaves, parent, flags);
+    return hipGetLastError();
+}
+
+}  // namespace tbvh
