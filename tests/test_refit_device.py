@@ -9,6 +9,7 @@ import tinybvh_amd as tb
 from tinybvh_amd import rays as R
 from tinybvh_amd import scenes
 from oracle_lib import compare_hits
+from tree_check import assert_tree, check_tree, describe
 
 
 def deform(verts, amount, seed):
@@ -35,6 +36,19 @@ def check(got, want):
     return c
 
 
+def blobs(sc):
+    nodes, tris = sc.download_blobs()
+    return nodes, (None if sc.layout == tb.LAYOUT_BVH4_GPU else tris)
+
+
+def check_boxes(sc, verts, held, label):
+    """the refitted boxes are conservative (and exact where the format is, tight where it quantises: tests/tree_check.py), the records are the moved
+    triangles', and the tree still reaches the prim words `held` it reached before"""
+    F = assert_tree(sc.layout, *blobs(sc), verts, prims=held, label=label)
+    print(label, describe(F))
+    return F
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("layout", [tb.LAYOUT_CWBVH, tb.LAYOUT_BVH_GPU, tb.LAYOUT_BVH4_GPU])
 def test_refit_parity(ctx, oracle, layout):
@@ -43,9 +57,11 @@ def test_refit_parity(ctx, oracle, layout):
     lo, hi = verts[:, :3].min(0) - 0.5, verts[:, :3].max(0) + 0.5
     rays = R.random_rays(40_000, lo, hi, seed=11)
     check(sc.Intersect(rays.copy()), oracle_hits(oracle, verts, rays))
+    held = check_tree(layout, *blobs(sc), verts)["prims"]   # (the default BVH8_CWBVH build may hold a triangle in several leaves)
     for frame, amount in enumerate((0.05, 0.2, 0.0)):       # the last frame returns to the rest pose
         v2 = deform(verts, amount, seed=frame) if amount else verts
         sc.Refit(v2)
+        check_boxes(sc, v2, held, f"frame {frame}")
         want = oracle_hits(oracle, v2, rays)
         c = check(sc.Intersect(rays.copy()), want)
         assert c["hits"] > 4000
@@ -55,6 +71,7 @@ def test_refit_parity(ctx, oracle, layout):
     v3 = deform(verts, 0.1, seed=9)
     d_v = ctx.malloc(v3.nbytes); ctx.to_device(d_v, v3)
     sc.Refit((d_v, v3.shape[0] // 3), on_device=True)
+    check_boxes(sc, v3, held, "device-resident vertices")
     check(sc.Intersect(rays.copy()), oracle_hits(oracle, v3, rays))
     ctx.free(d_v)
 
@@ -87,9 +104,12 @@ def test_refit_of_a_split_tree_keeps_every_record(ctx, oracle):
     sc.Refit(verts)
     n, t = sc.download_blobs()
     assert np.array_equal(t, before_t)
+    held = before_t.reshape(-1, 3, 4)[:, 2, 3]
+    check_boxes(sc, verts, held, "refitted to the same vertices")
     check(sc.Intersect(rays.copy()), want)
     v2 = deform(verts, 0.1, seed=4)
     sc.Refit(v2)
+    check_boxes(sc, v2, held, "refitted to moved vertices")
     check(sc.Intersect(rays.copy()), oracle_hits(oracle, v2, rays))
 
 
