@@ -293,10 +293,46 @@ public:
         return d;
     }
     void Download(void* dst16, size_t capVerts) { Check(tbvh_pose_download(p, dst16, capVerts), "tbvh_pose_download"); }
+    // the FatTri half of Mesh::SetPose: every SetPose from now on also rewrites the records of blasSlot of `shading` (a tbvh_shading*, e.g. Shading::Handle()).
+    // normals12: Mesh::origNormal (skin) or poses[ 0 .. nTargets ].normals back to back (morph); indices: nullptr for a flat mesh
+    void AttachFatTris(tbvh_shading* shading, uint32_t blasSlot, const float* normals12, size_t nTris, const uint32_t* indices = nullptr) {
+        Check(tbvh_pose_attach_fat_tris(p, shading, blasSlot, normals12, indices, nTris, 0), "tbvh_pose_attach_fat_tris");
+    }
     tbvh_pose* Handle() const { return p; }
 private:
     tbvh_context* ctx;
     tbvh_pose* p = nullptr;
+};
+
+// GetShadingData of the reference's renderers on the device (tbvh_shading_*, tbvh_shade_hits): materials and textures once, the FatTri records of every BLAS
+// slot (Mesh::triangles.data(), taken verbatim), then per frame ShadeHits after the trace: 48 bytes per ray — albedo + alpha, N + material, iN + texel.
+//   tinyhip::Shading shading( materials, nMaterials, textures, nTextures );
+//   shading.SetFatTris( blasIdx, mesh->triangles.data(), mesh->triangles.size() );
+//   tlas.Intersect( rays, n ); shading.ShadeHits( tlas, rays, n, sizeof( tinybvh::Ray ), out48 );
+class Shading {
+public:
+    Shading(const tbvh_material* materials, uint32_t nMaterials, const tbvh_alpha_texture* textures, uint32_t nTextures, tbvh_context* own = nullptr, int device = 0)
+        : ctx(own ? own : Context(device)) {
+        Check(tbvh_shading_create(ctx, materials, nMaterials, textures, nTextures, 0, &p), "tbvh_shading_create");
+    }
+    Shading(const Shading&) = delete;
+    Shading& operator=(const Shading&) = delete;
+    ~Shading() { tbvh_shading_free(p); }
+    void SetFatTris(uint32_t blasSlot, const void* fatTris192, size_t nTris, bool onDevice = false) {
+        Check(tbvh_shading_set_fat_tris(p, blasSlot, fatTris192, nTris, onDevice ? 1 : 0), "tbvh_shading_set_fat_tris");
+    }
+    // host ray records as Intersect left them, rayStride bytes apart (sizeof( tinybvh::Ray ) or 64); out48: 12 floats per ray
+    void ShadeHits(Scene& scene, const void* rays, size_t n, uint32_t rayStride, void* out48) { Check(tbvh_shade_hits(p, scene.Handle(), rays, n, rayStride, out48), "tbvh_shade_hits"); }
+    void ShadeHits(tbvh_scene* scene, const void* rays, size_t n, uint32_t rayStride, void* out48) { Check(tbvh_shade_hits(p, scene, rays, n, rayStride, out48), "tbvh_shade_hits"); }
+    // device-resident records and output; asynchronous on the context's stream
+    void ShadeHitsDevice(tbvh_scene* scene, const void* dRays, size_t n, uint32_t rayStride, void* dOut48) {
+        Check(tbvh_shade_hits_device(p, scene, dRays, n, rayStride, dOut48), "tbvh_shade_hits_device");
+    }
+    void Download(uint32_t blasSlot, void* dst192, size_t capTris) { Check(tbvh_shading_download_fat_tris(p, blasSlot, dst192, capTris), "tbvh_shading_download_fat_tris"); }
+    tbvh_shading* Handle() const { return p; }
+private:
+    tbvh_context* ctx;
+    tbvh_shading* p = nullptr;
 };
 
 // tinyocl::Buffer( bytes ) for a ray array that is traced many times (tiny_bvh_speedtest.cpp:1101-1108 wraps its ray array in one per GPU block): page-locked

@@ -46,7 +46,7 @@
 extern "C" {
 #endif
 
-#define TBVH_ABI_VERSION 5   /* 5 (additions, nothing changed: indexed and strided triangle meshes — tbvh_mesh and the tbvh_*_mesh entry points, tbvh_flatten_mesh_device); 5 (additions, nothing changed: custom-geometry sphere BLASes — tbvh_upload_custom_spheres, tbvh_host_build_custom_spheres, TLASes over them); 5 (additions, nothing changed: tbvh_intersect_spheres / _device); 5 (additions, nothing changed: VoxelSet scenes — TBVH_LAYOUT_VOXELSET, tbvh_upload_voxelset / _voxelset_dense, tbvh_host_build_voxelset, TLASes over voxel sets); 5 (additions, nothing changed: BVH_Double scenes — TBVH_LAYOUT_BVH_DOUBLE, tbvh_upload_bvh_double / _tlas_double, tbvh_intersect_ex / _occluded_ex (+ _device), tbvh_host_build_double / _tlas_double); 5: tbvh_pinned_malloc / _free, tbvh_scene_get / _set_schedule_hint, tbvh_measure_link_bandwidth, TBVH_BUILD_SPLIT_TRIANGLES / _WHOLE_TRIANGLES, development aids moved to tinybvh_amd_debug.h (nothing removed from the library); 4: tbvh_update_bvh_gpu / _bvh4_gpu / _cwbvh, tbvh_time_history, contexts are thread-safe; 3: deterministic ties, tbvh_bin_rays_device, tbvh_cwbvh_set_hybrid, device-resident multi-device calls */
+#define TBVH_ABI_VERSION 5   /* 5 (additions, nothing changed: hits resolved to shading data — tbvh_shading_*, tbvh_shade_hits / _device, tbvh_shade_continue_device, tbvh_host_shade_hits, tbvh_pose_attach_fat_tris, tbvh_host_pose_skin_normals / _morph_normals / _update_fat_tris); 5 (additions, nothing changed: indexed and strided triangle meshes — tbvh_mesh and the tbvh_*_mesh entry points, tbvh_flatten_mesh_device); 5 (additions, nothing changed: custom-geometry sphere BLASes — tbvh_upload_custom_spheres, tbvh_host_build_custom_spheres, TLASes over them); 5 (additions, nothing changed: tbvh_intersect_spheres / _device); 5 (additions, nothing changed: VoxelSet scenes — TBVH_LAYOUT_VOXELSET, tbvh_upload_voxelset / _voxelset_dense, tbvh_host_build_voxelset, TLASes over voxel sets); 5 (additions, nothing changed: BVH_Double scenes — TBVH_LAYOUT_BVH_DOUBLE, tbvh_upload_bvh_double / _tlas_double, tbvh_intersect_ex / _occluded_ex (+ _device), tbvh_host_build_double / _tlas_double); 5: tbvh_pinned_malloc / _free, tbvh_scene_get / _set_schedule_hint, tbvh_measure_link_bandwidth, TBVH_BUILD_SPLIT_TRIANGLES / _WHOLE_TRIANGLES, development aids moved to tinybvh_amd_debug.h (nothing removed from the library); 4: tbvh_update_bvh_gpu / _bvh4_gpu / _cwbvh, tbvh_time_history, contexts are thread-safe; 3: deterministic ties, tbvh_bin_rays_device, tbvh_cwbvh_set_hybrid, device-resident multi-device calls */
 
 /* error codes */
 #define TBVH_OK            0
@@ -831,7 +831,7 @@ int tbvh_flatten_mesh_device(tbvh_context* ctx, const tbvh_mesh* mesh, void* d_v
  * the BLAS.  A tbvh_pose keeps the rest data on the device and ONE output buffer of n_verts float4; per frame the caller sends the joint matrices
  * (64 bytes per joint) or the morph weights, the vertices are produced where the refit reads them, and tbvh_pose_refit refits a scene from them.
  * n_verts is the number of VERTICES: an indexed mesh poses every shared vertex once.  The scene graph (the joint matrix products), animation
- * sampling, normals and the FatTri data stay with the caller.  The two kinds are separate calls, as in the reference (whose skin pass starts from
+ * sampling and the shading data stay with the caller (the FatTri records of a shading table can follow the pose: tbvh_pose_attach_fat_tris, below).  The two kinds are separate calls, as in the reference (whose skin pass starts from
  * its own backup and overwrites a morph pass).
  *   - the arithmetic is the reference's, float operation for float operation, as its build (g++ -O3 -mavx2 -mfma, tinyscene's vector types set to
  *     tinybvh's as tiny_bvh_gltf.cpp does) performs it: tinybvh_amd/csrc/pose.h, DESIGN.md par. 14.  Skin: w of the output is 0; the homogeneous
@@ -920,6 +920,88 @@ int tbvh_bake_set_opacity_micromaps(tbvh_scene* blas, const tbvh_omm_source* src
 /* The same arithmetic on the CPU (omm.h compiled for the host), host arrays in and out (src->on_device must be 0), no context, one thread: for callers
  * without a device flow.  maps_out: n_tris * ((N * N + 31) / 32) words; nothing is written when the source is refused. */
 int tbvh_host_bake_opacity_micromaps(const tbvh_omm_source* src, uint32_t N, uint32_t* maps_out);
+
+/* ----------------------------------------------------------------------------------
+ * hits resolved to shading data on the device — GetShadingData of the reference's renderers (tiny_bvh_foliage.cpp:80-125, tiny_bvh_gltf.cpp:89,
+ * raytracer.cl's Trace): hit.inst -> BLASInstance::blasIdx -> FatTri[ hit.prim ] -> Material -> texel, giving an albedo, an alpha decision, the geometric
+ * normal and the interpolated (optionally normal-mapped) normal, both in world space.  A tbvh_shading (one or more per context) owns device copies of
+ * the materials, the texture descriptors and, per BLAS slot, the tinyscene::FatTri records (192 bytes each, taken verbatim as the BVH blobs are); the
+ * scene graph, glTF loading, texture decoding, mips, HDR (fdata) textures, the second UV layer and sky / fog / tone mapping stay with the caller.
+ *   - the arithmetic is the reference's, float operation for float operation, as its build (g++ -O3 -mavx2 -mfma) performs it: tinybvh_amd/csrc/shade.h,
+ *     DESIGN.md par. 16.  One deliberate difference: a tiny negative texture coordinate wraps to exactly 1.0f, and the reference then reads the next
+ *     row's first texel or, in the last row, past its array; here the reference's linear index is clamped to width * height - 1 — identical wherever the
+ *     reference's read is inside the texture, and nothing outside it is ever read.  A non-finite u, v or UV gives unspecified values in that record.
+ *   - input: the ray records as the queries leave them (D at byte 16, hit.inst at 44, t u v prim at 48..63), ray_stride_bytes apart (64 or 128; the
+ *     _device form takes any multiple of 16 from 64 on, 16-byte aligned).  scene: a TLAS over fp32 BLASes — its instance records give the transform and
+ *     the blasIdx, which is the BLAS slot —, or a single triangle BLAS, taken as instance 0 of slot 0 with the identity matrix through the same arithmetic
+ *     (hit.inst is then not looked at).  BVH_DOUBLE, VOXELSET and sphere scenes are refused (TBVH_E_INVALID); a TLAS holding voxel or sphere BLASes is
+ *     accepted, a hit on such an instance gets the "no surface" record.
+ *   - output, 48 bytes per ray:   float4 0: albedo.xyz, alpha (1 / 0 as tiny_bvh_foliage.cpp:104: texel alpha > 2; untextured: the material's colour, 1)
+ *                                 float4 1: N.xyz, the bits of FatTri.material
+ *                                 float4 2: iN.xyz, the bits of the colour texel (0 when untextured), for callers with another alpha rule
+ *     "no surface": all twelve words 0 except alpha = -1 — for a miss (hit.t >= 1e30f), and for a hit whose inst, slot or prim is out of range or whose
+ *     slot has no records, which also sets the status word: the next synchronising call returns TBVH_E_FORMAT.  A device-resident FatTri.material or
+ *     material texture index that is out of range is never used as an address: that hit is shaded untextured with albedo 0, same status.
+ *   - validation: null pointers, zero counts, misaligned pointers (host arrays 4 bytes, device-resident FatTri records 16), a texture with null texels or a
+ *     zero (or, width * height, beyond 2^31 - 1) size: TBVH_E_INVALID.  Host-resident input is range-checked before anything is allocated: a material
+ *     naming a texture >= n_textures that is not TBVH_OMM_NO_TEXTURE, or a FatTri.material >= n_materials: TBVH_E_FORMAT naming the first.
+ *   - on_device: where materials, every texels pointer (tbvh_shading_create) or the records (tbvh_shading_set_fat_tris) point.  The descriptor array is
+ *     always host memory.  The table keeps its own copy of everything except device-resident texels, which stay the caller's and must outlive it.
+ *   - tbvh_shading_set_fat_tris: blas_slot is the blasIdx the instances carry; a second call for a slot replaces its records.  Synchronous.
+ *   - a table belongs to its context as a pose does: tbvh_shutdown frees the ones still alive (free a table before its context, or not at all).
+ *   - tbvh_shade_hits_device is asynchronous on the context's stream and a timed operation (tbvh_time_last_ms: the shading kernel); tbvh_shade_hits
+ *     takes host arrays, stages them, and returns the status.
+ * ---------------------------------------------------------------------------------- */
+typedef struct tbvh_material {   /* Material::color (value, textureID) and Material::normals.textureID; TBVH_OMM_NO_TEXTURE stands for textureID == -1 */
+    float color[3];
+    uint32_t color_texture;      /* texels as Texture::idata: x in the low byte, alpha in bits 24-31 */
+    uint32_t normal_texture;
+} tbvh_material;
+typedef struct tbvh_shading tbvh_shading;
+int tbvh_shading_create(tbvh_context* ctx, const tbvh_material* materials, uint32_t n_materials, const tbvh_alpha_texture* textures, uint32_t n_textures,
+                        int on_device, tbvh_shading** out);
+int tbvh_shading_set_fat_tris(tbvh_shading* shading, uint32_t blas_slot, const void* fat_tris192, uint64_t n_tris, int on_device);
+/* The slot's records: device memory owned by the table, n_tris x 192 bytes, valid until the slot is set again or the table is freed. */
+int tbvh_shading_fat_tris(tbvh_shading* shading, uint32_t blas_slot, void** d_fat_tris192, uint64_t* n_tris);
+int tbvh_shading_download_fat_tris(tbvh_shading* shading, uint32_t blas_slot, void* dst192, uint64_t cap_tris);   /* synchronous; reports the status word */
+void tbvh_shading_free(tbvh_shading* shading);   /* waits for the context's stream, then frees */
+int tbvh_shade_hits(tbvh_shading* shading, tbvh_scene* scene, const void* rays, uint64_t n_rays, uint32_t ray_stride_bytes, void* out48);
+int tbvh_shade_hits_device(tbvh_shading* shading, tbvh_scene* scene, const void* d_rays, uint64_t n_rays, uint32_t ray_stride_bytes, void* d_out48);
+/* The alpha-continue step of the reference's renderers (tiny_bvh_gltf.cpp:140-150) between two tbvh_intersect_device calls: every record whose d_out48
+ * alpha is 0 gets O = ( O + D * t ) + D * 1e-4 (each product and sum rounded), hit.t = 1e30 and u, v, prim cleared; every other record is left as it is
+ * (traced again it keeps its hit).  d_continued: NULL, or a device counter (8-byte aligned) to which the number of records that stepped on is ADDED.
+ * Asynchronous on the context's stream. */
+int tbvh_shade_continue_device(tbvh_context* ctx, void* d_rays, uint32_t ray_stride_bytes, const void* d_out48, uint64_t n_rays, unsigned long long* d_continued);
+/* The same arithmetic on the CPU (shade.h compiled for the host), host arrays in and out, no context, one thread.  fat_tris192[ k ] / n_tris[ k ]: the
+ * records of BLAS slot k (NULL / 0: none); instances192: the TLAS's BLASInstance records, or NULL for a single BLAS (slot 0, identity).  Everything is
+ * range-checked first (as above; nothing written when refused); records, instances, FatTri arrays and out48 are 16-byte aligned.  A record whose inst,
+ * slot or prim is out of range gets "no surface" and the call returns TBVH_E_FORMAT after writing every record. */
+int tbvh_host_shade_hits(const tbvh_material* materials, uint32_t n_materials, const tbvh_alpha_texture* textures, uint32_t n_textures,
+                         const void* const* fat_tris192, const uint64_t* n_tris, uint32_t n_slots, const void* instances192, uint64_t n_instances,
+                         const void* rays, uint64_t n_rays, uint32_t ray_stride_bytes, void* out48);
+
+/* The FatTri half of Mesh::SetPose (tiny_scene.h:1761-1777, 1809-1824): a pose with a slot's records attached rewrites them in every tbvh_pose_set_*, in
+ * the same timed operation, so that the shading follows the animation.  Per triangle vertex0..2 (the posed corners) and vN0..2 are written, 12 bytes each;
+ * a skin pose also writes Nx Ny Nz = normalize( cross( v1 - v0, v2 - v0 ) ), a morph pose leaves them, as the reference does.  Every other byte of the
+ * record (UVs, material, T, B, the w of the vertices, ...) is kept.
+ *   - skin: normals12 holds n_verts rest normals (3 floats each; the reference's origNormal); the posed normal is normalize( transform_vector( normal,
+ *     skinMatrix ) ) with the blended matrix the vertex itself uses.  morph: normals12 holds (n_targets + 1) arrays of n_verts * 3 floats, array 0 the
+ *     base; vN = normalize( base + the sum of the target normals ) — the sum takes NO weights, which is the reference's arithmetic (1767-1776).
+ *   - indices: NULL — triangle i has corners 3i .. 3i + 2, and n_verts must be 3 * n_tris — or 3 per triangle (an indexed pose: every shared vertex and
+ *     normal is posed once, the records gather).  Host indices are range-checked before anything is allocated (TBVH_E_FORMAT names the first triangle);
+ *     device-resident ones by the kernel: a triangle with an index >= n_verts is left as it is and the next synchronising call returns TBVH_E_FORMAT.
+ *   - n_tris must equal the record count of blas_slot of `shading` (same context), at the call and at every later tbvh_pose_set_* (TBVH_E_INVALID).
+ *     The pose keeps its own copies of normals12 and indices.  A second call replaces the attachment; freeing the shading table detaches it.  A pose
+ *     with nothing attached behaves exactly as before.  Synchronous. */
+int tbvh_pose_attach_fat_tris(tbvh_pose* pose, tbvh_shading* shading, uint32_t blas_slot, const float* normals12, const uint32_t* indices, uint64_t n_tris,
+                              int on_device);
+/* The same on the CPU (pose.h compiled for the host), no context: the posed normals per vertex (out16: n_verts float4, w = 0), and the rewrite of
+ * fat_tris192 in place from posed vertices (tbvh_host_pose_skin / _morph) and posed normals; skin != 0 also writes Nx Ny Nz. */
+int tbvh_host_pose_skin_normals(uint64_t n_verts, const uint32_t* joints4, const void* weights16, const float* joint_mats16, uint32_t n_joints,
+                                const float* normals12, void* out16);
+int tbvh_host_pose_morph_normals(const float* normals12, uint64_t n_verts, uint32_t n_targets, void* out16);
+int tbvh_host_pose_update_fat_tris(void* fat_tris192, uint64_t n_tris, const void* verts16, const void* normals16, uint64_t n_verts, const uint32_t* indices,
+                                   int skin);
 
 #ifdef __cplusplus
 }

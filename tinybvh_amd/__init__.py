@@ -1463,6 +1463,36 @@ def host_pose_morph(positions, weights) -> np.ndarray:
     return out
 
 
+def host_pose_fat_tris(fat_tris, verts16, normals16, indices=None, skin: bool = True) -> np.ndarray:
+    """The FatTri half of Mesh::SetPose on the CPU (tbvh_host_pose_update_fat_tris): a copy of fat_tris (FATTRI_DTYPE) rewritten from posed vertices
+    (host_pose_skin / host_pose_morph) and posed normals (host_pose_skin_normals / host_pose_morph_normals), both (n_verts, 4)."""
+    f = np.array(fat_tris, FATTRI_DTYPE).reshape(-1)
+    v = np.ascontiguousarray(verts16, np.float32).reshape(-1, 4); n = np.ascontiguousarray(normals16, np.float32).reshape(-1, 4)
+    assert v.shape == n.shape
+    idx = None if indices is None else np.ascontiguousarray(indices, np.uint32).reshape(-1, 3)
+    check(lib.tbvh_host_pose_update_fat_tris(_ptr(f), f.size, _ptr(v), _ptr(n), v.shape[0], None if idx is None else _ptr(idx), 1 if skin else 0), "tbvh_host_pose_update_fat_tris")
+    return f
+
+
+def host_pose_skin_normals(normals, joints, weights, joint_mats) -> np.ndarray:
+    """(n_verts, 4) posed normals of a skin pose (tbvh_host_pose_skin_normals): normalize( transform_vector( normal, the vertex's blended matrix ) ), w = 0"""
+    nrm = np.ascontiguousarray(normals, np.float32).reshape(-1, 3)
+    _, joints, weights = _skin_arrays(np.zeros((nrm.shape[0], 4), np.float32), joints, weights)
+    mats = np.ascontiguousarray(joint_mats, np.float32).reshape(-1, 16)
+    out = np.zeros((nrm.shape[0], 4), np.float32)
+    check(lib.tbvh_host_pose_skin_normals(nrm.shape[0], _ptr(joints), _ptr(weights), _ptr(mats), mats.shape[0], _ptr(nrm), _ptr(out)), "tbvh_host_pose_skin_normals")
+    return out
+
+
+def host_pose_morph_normals(normals) -> np.ndarray:
+    """(n_verts, 4) normals of a morph pose (tbvh_host_pose_morph_normals): normalize( base + the target normals ), no weights, as the reference has it"""
+    nrm = np.ascontiguousarray(normals, np.float32)
+    assert nrm.ndim == 3 and nrm.shape[2] == 3, "normals: (n_targets + 1, n_verts, 3)"
+    out = np.zeros((nrm.shape[1], 4), np.float32)
+    check(lib.tbvh_host_pose_morph_normals(_ptr(nrm), nrm.shape[1], nrm.shape[0] - 1, _ptr(out)), "tbvh_host_pose_morph_normals")
+    return out
+
+
 class Pose:
     """A skinned or morph-target mesh posed on the device (tbvh_pose_*; Mesh::SetPose of tiny_scene.h): Skin() or Morph() once, then per frame
     SetPose( joint matrices | morph weights ) and Refit( scene )."""
@@ -1519,6 +1549,17 @@ class Pose:
         check(lib.tbvh_pose_refit(self._h, scene._h), "tbvh_pose_refit")
         return self
 
+    def AttachFatTris(self, shading: "Shading", slot: int, normals, indices=None) -> "Pose":
+        """tbvh_pose_attach_fat_tris: from now on every SetPose also rewrites the FatTri records of `slot` of `shading` (vertex0..2, vN0..2 and, for a skin,
+        Nx Ny Nz).  normals: skin (n_verts, 3) rest normals, morph (n_targets + 1, n_verts, 3); indices: (n_tris, 3) for an indexed pose."""
+        nrm = np.ascontiguousarray(normals, np.float32)
+        want = self.n_verts * 3 * (self.n_params + 1 if self.kind == "morph" else 1)
+        assert nrm.size == want, "normals: (n_verts, 3) for a skin, (n_targets + 1, n_verts, 3) for a morph pose"
+        idx = None if indices is None else np.ascontiguousarray(indices, np.uint32).reshape(-1, 3)
+        n_tris = self.n_verts // 3 if idx is None else idx.shape[0]
+        check(lib.tbvh_pose_attach_fat_tris(self._h, shading._h, int(slot), _ptr(nrm), None if idx is None else _ptr(idx), n_tris, 0), "tbvh_pose_attach_fat_tris")
+        return self
+
     def Vertices(self):
         """(device pointer of the posed vertices, n_verts)"""
         p = C.c_void_p(); n = C.c_uint64(0)
@@ -1533,6 +1574,138 @@ class Pose:
     def free(self):
         if self._h and self.ctx._h:   # (a closed context has freed its poses itself: tbvh_shutdown)
             lib.tbvh_pose_free(self._h)
+        self._h = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+# ---- hits resolved to shading data (capi_shade.hip) --------------------------------------------------------------------------------------
+# tinyscene::FatTri, 192 bytes, taken verbatim
+FATTRI_DTYPE = np.dtype([
+    ("u0", "<f4"), ("u1", "<f4"), ("u2", "<f4"), ("ltriIdx", "<i4"),
+    ("v0", "<f4"), ("v1", "<f4"), ("v2", "<f4"), ("material", "<u4"),
+    ("vN0", "<f4", 3), ("Nx", "<f4"), ("vN1", "<f4", 3), ("Ny", "<f4"), ("vN2", "<f4", 3), ("Nz", "<f4"),
+    ("vertex0", "<f4", 3), ("u0_2", "<f4"), ("vertex1", "<f4", 3), ("u1_2", "<f4"), ("vertex2", "<f4", 3), ("u2_2", "<f4"),
+    ("T", "<f4", 3), ("area", "<f4"), ("B", "<f4", 3), ("invArea", "<f4"),
+    ("alpha", "<f4", 3), ("LOD", "<f4"), ("v0_2", "<f4"), ("v1_2", "<f4"), ("v2_2", "<f4"), ("dummy4", "<f4"),
+])
+assert FATTRI_DTYPE.itemsize == 192
+# tbvh_material: Material::color (value, textureID) and Material::normals.textureID; NO_TEXTURE stands for textureID == -1
+MATERIAL_DTYPE = np.dtype([("color", "<f4", 3), ("color_texture", "<u4"), ("normal_texture", "<u4")])
+assert MATERIAL_DTYPE.itemsize == 20
+NO_TEXTURE = 0xFFFFFFFF
+# what tbvh_shade_hits writes per ray, 48 bytes; "no surface" (a miss): all zero except alpha = -1
+SHADED_DTYPE = np.dtype([("albedo", "<f4", 3), ("alpha", "<f4"), ("N", "<f4", 3), ("material", "<u4"), ("iN", "<f4", 3), ("texel", "<u4")])
+assert SHADED_DTYPE.itemsize == 48
+
+
+class ShadedHits(np.ndarray):
+    """The (n, 12) float32 records of ShadeHits, with the fields by name: .albedo (n, 3), .alpha (n,), .N (n, 3), .material (n,) uint32, .iN (n, 3),
+    .texel (n,) uint32, .surface (n,) bool."""
+
+    @property
+    def records(self):
+        return np.asarray(self).view(SHADED_DTYPE).reshape(-1)
+
+    albedo = property(lambda self: self.records["albedo"])
+    alpha = property(lambda self: self.records["alpha"])
+    N = property(lambda self: self.records["N"])
+    material = property(lambda self: self.records["material"])
+    iN = property(lambda self: self.records["iN"])
+    texel = property(lambda self: self.records["texel"])
+    surface = property(lambda self: self.records["alpha"] >= 0)
+
+
+def _shade_tables(materials, textures):
+    mats = np.ascontiguousarray(materials, MATERIAL_DTYPE).reshape(-1)
+    tex = [_alpha_texels(t) for t in (textures or [])]
+    arr = (AlphaTexture * max(len(tex), 1))(*[AlphaTexture(C.c_void_p(t.ctypes.data), t.shape[1], t.shape[0]) for t in tex])
+    return mats, tex, arr
+
+
+def _aligned(a: np.ndarray, dtype=None) -> np.ndarray:
+    """`a`, C-contiguous, at a 16-byte aligned address (copied when it is not)"""
+    a = np.ascontiguousarray(a, dtype)
+    if a.ctypes.data & 15:
+        raw = np.empty(a.nbytes + 16, np.uint8)
+        off = -raw.ctypes.data & 15
+        b = raw[off:off + a.nbytes].view(a.dtype).reshape(a.shape)
+        b[...] = a
+        return b
+    return a
+
+
+def host_shade_hits(materials, textures, fat_tris, rays, instances=None) -> ShadedHits:
+    """GetShadingData on the CPU (tbvh_host_shade_hits).  fat_tris: one FATTRI_DTYPE array per BLAS slot (None: a slot without records); instances:
+    the TLAS's (n, 48) float32 / 192-byte BLASInstance records, or None for a single BLAS (slot 0, identity); rays: RAY_DTYPE records (or 128-byte
+    ones: any array whose rows are the records)."""
+    mats, tex, arr = _shade_tables(materials, textures)
+    slots = [None if f is None else _aligned(f, FATTRI_DTYPE).reshape(-1) for f in fat_tris]
+    ptrs = (C.c_void_p * len(slots))(*[None if f is None else f.ctypes.data for f in slots])
+    counts = np.array([0 if f is None else f.size for f in slots], np.uint64)
+    rays = _aligned(rays)
+    n, stride = rays.shape[0], rays.strides[0]
+    inst = None if instances is None else _aligned(instances)
+    n_inst = 0 if inst is None else inst.nbytes // 192
+    out = _aligned(np.zeros((n, 12), np.float32))
+    check(lib.tbvh_host_shade_hits(_ptr(mats), mats.size, arr, len(tex), ptrs, _ptr(counts), len(slots), None if inst is None else _ptr(inst), n_inst,
+                                   _ptr(rays) if n else None, n, stride, _ptr(out) if n else None), "tbvh_host_shade_hits")
+    return out.view(ShadedHits)
+
+
+class Shading:
+    """A shading table (tbvh_shading_*; GetShadingData of the reference's renderers): materials (MATERIAL_DTYPE) and textures ((h, w) uint32 arrays as
+    Texture::idata) once, SetFatTris( slot, FATTRI_DTYPE array ) per BLAS, then ShadeHits( scene, rays ) after every Intersect."""
+
+    def __init__(self, ctx: Context, materials, textures=None):
+        self.ctx = ctx
+        self._h = C.c_void_p()
+        mats, tex, arr = _shade_tables(materials, textures)
+        check(lib.tbvh_shading_create(ctx._h, _ptr(mats), mats.size, arr, len(tex), 0, C.byref(self._h)), "tbvh_shading_create")
+        self.n_tris = {}
+
+    def SetFatTris(self, slot: int, fat_tris=None, d_fat_tris: int = 0, n_tris: int = 0) -> "Shading":
+        """The slot's FatTri records (slot = the blasIdx the instances carry), copied; a second call replaces them.  d_fat_tris / n_tris: from device memory."""
+        if d_fat_tris:
+            check(lib.tbvh_shading_set_fat_tris(self._h, int(slot), C.c_void_p(int(d_fat_tris)), int(n_tris), 1), "tbvh_shading_set_fat_tris")
+        else:
+            f = np.ascontiguousarray(fat_tris, FATTRI_DTYPE).reshape(-1)
+            n_tris = f.size
+            check(lib.tbvh_shading_set_fat_tris(self._h, int(slot), _ptr(f) if n_tris else None, n_tris, 0), "tbvh_shading_set_fat_tris")
+        self.n_tris[int(slot)] = int(n_tris)
+        return self
+
+    def FatTris(self, slot: int):
+        """(device pointer of the slot's records, n_tris)"""
+        p = C.c_void_p(); n = C.c_uint64(0)
+        check(lib.tbvh_shading_fat_tris(self._h, int(slot), C.byref(p), C.byref(n)), "tbvh_shading_fat_tris")
+        return p.value, int(n.value)
+
+    def Download(self, slot: int) -> np.ndarray:
+        out = np.zeros(self.FatTris(slot)[1], FATTRI_DTYPE)
+        check(lib.tbvh_shading_download_fat_tris(self._h, int(slot), _ptr(out), out.size), "tbvh_shading_download_fat_tris")
+        return out
+
+    def ShadeHits(self, scene: "_Scene", rays: np.ndarray) -> ShadedHits:
+        """tbvh_shade_hits: the (n, 12) float32 records for host ray records as Intersect left them (rows 64 or 128 bytes apart)."""
+        rays = np.ascontiguousarray(rays)
+        n = rays.shape[0]
+        out = np.zeros((n, 12), np.float32)
+        check(lib.tbvh_shade_hits(self._h, scene._h, _ptr(rays) if n else None, n, rays.strides[0] if n else 64, _ptr(out) if n else None), "tbvh_shade_hits")
+        return out.view(ShadedHits)
+
+    def ShadeHitsDevice(self, scene: "_Scene", d_rays: int, n: int, d_out48: int, stride: int = 64) -> "Shading":
+        """tbvh_shade_hits_device: asynchronous on the context's stream, 48 bytes per ray into d_out48."""
+        check(lib.tbvh_shade_hits_device(self._h, scene._h, C.c_void_p(int(d_rays)), int(n), int(stride), C.c_void_p(int(d_out48))), "tbvh_shade_hits_device")
+        return self
+
+    def free(self):
+        if self._h and self.ctx._h:   # (a closed context has freed its tables itself: tbvh_shutdown)
+            lib.tbvh_shading_free(self._h)
         self._h = None
 
     def __del__(self):

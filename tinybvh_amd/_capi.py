@@ -189,6 +189,20 @@ SYMBOLS = {
     "tbvh_bake_opacity_micromaps": (_i, [_vp, C.POINTER(OmmSource), _u32, _vp]),
     "tbvh_bake_set_opacity_micromaps": (_i, [_vp, C.POINTER(OmmSource), _u32]),
     "tbvh_host_bake_opacity_micromaps": (_i, [C.POINTER(OmmSource), _u32, _vp]),
+    # hits resolved to shading data (capi_shade.hip)
+    "tbvh_shading_create": (_i, [_vp, _vp, _u32, _vp, _u32, _i, _pp]),
+    "tbvh_shading_set_fat_tris": (_i, [_vp, _u32, _vp, _u64, _i]),
+    "tbvh_shading_fat_tris": (_i, [_vp, _u32, _pp, C.POINTER(_u64)]),
+    "tbvh_shading_download_fat_tris": (_i, [_vp, _u32, _vp, _u64]),
+    "tbvh_shading_free": (None, [_vp]),
+    "tbvh_shade_hits": (_i, [_vp, _vp, _vp, _u64, _u32, _vp]),
+    "tbvh_shade_hits_device": (_i, [_vp, _vp, _vp, _u64, _u32, _vp]),
+    "tbvh_shade_continue_device": (_i, [_vp, _vp, _u32, _vp, _u64, _vp]),
+    "tbvh_pose_attach_fat_tris": (_i, [_vp, _vp, _u32, _vp, _vp, _u64, _i]),
+    "tbvh_host_pose_skin_normals": (_i, [_u64, _vp, _vp, _vp, _u32, _vp, _vp]),
+    "tbvh_host_pose_morph_normals": (_i, [_vp, _u64, _u32, _vp]),
+    "tbvh_host_pose_update_fat_tris": (_i, [_vp, _u64, _vp, _vp, _u64, _vp, _i]),
+    "tbvh_host_shade_hits": (_i, [_vp, _u32, _vp, _u32, _vp, _vp, _u32, _vp, _u64, _vp, _u64, _u32, _vp]),
 }
 
 

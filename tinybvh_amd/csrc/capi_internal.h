@@ -127,6 +127,7 @@ struct tbvh_context {
     DevBuf<void> binScratch;      // tbvh_bin_rays_device
     std::vector<tbvh_scene*> scenes;
     std::vector<struct tbvh_pose*> poses;   // (capi_pose.hip) the poses made on this context: tbvh_shutdown frees those the caller has not
+    std::vector<struct tbvh_shading*> shadings;   // (capi_shade.hip) likewise the shading tables
     // (capi_omm.hip) the texture descriptors of a bake go up through a pinned area, in stream order, into ommDesc: a device-resident bake stays asynchronous;
     // the area is reused once the previous bake's copy has left it (ommEv)
     DevBuf<void> ommDesc;
@@ -416,4 +417,9 @@ int allocOpacityMaps(tbvh_context* c, uint32_t N, uint64_t nTris, const char* wh
 int installOpacityMaps(tbvh_scene* s, DevBuf<uint32_t>&& fresh, uint32_t N);
 void freeOmmStagingOf(tbvh_context* c);   // (capi_omm.hip) tbvh_shutdown: the pinned area and the event of the texture-descriptor upload
 void freePosesOf(tbvh_context* c);   // (capi_pose.hip) tbvh_shutdown: the context's stream is idle, its device current
+void freeShadingsOf(tbvh_context* c);   // (capi_shade.hip) likewise
+// (capi_shade.hip) what a pose with FatTri records attached needs of a shading table: its context, and a slot's records as they are now (nullptr / 0: none)
+tbvh_context* shadingContext(const struct tbvh_shading* sh);
+void shadingSlotRecords(const struct tbvh_shading* sh, uint32_t slot, float4** tris, uint64_t* nTris);
+void detachPosesFrom(tbvh_context* c, const struct tbvh_shading* sh);   // (capi_pose.hip) the table goes: the poses attached to it pose vertices only from here on
 }  // namespace tbvh_capi

@@ -19,6 +19,14 @@ struct tbvh_pose {
     DevBuf<float> positions;         // morph: (nTargets + 1) * nVerts * 3
     DevBuf<float> params;            // skin: nJoints * 16 floats (the joint table); morph: nTargets weights
     DevBuf<float4> out;              // nVerts posed vertices
+    // FatTri records attached (tbvh_pose_attach_fat_tris): every tbvh_pose_set_* also rewrites the records of `slot` of `shading` (looked up per call: the
+    // slot may have been set again since).  normals: skin nVerts * 3 rest normals, morph (nTargets + 1) * nVerts * 3; nOut: one posed normal per vertex
+    tbvh_shading* shading = nullptr;
+    uint32_t slot = 0;
+    uint64_t fatTris = 0;
+    DevBuf<float> normals;
+    DevBuf<float4> nOut;
+    DevBuf<uint32_t> fatIdx;         // 3 per triangle, or empty: triangle i has corners 3i .. 3i + 2
     // host matrices / weights are copied here before tbvh_pose_set_* returns and go up by DMA from here; a slot is reused once its copy has left
     char* pin = nullptr;
     uint64_t pinSlotBytes = 0;
@@ -67,7 +75,27 @@ void destroyPose(tbvh_pose* p) {
 
 }  // namespace
 
+namespace {
+// tbvh_pose_set_* with records attached: the slot's records as they are now, refused before anything is staged or launched when their number changed
+int attachedRecords(tbvh_pose* p, const char* who, float4** tris) {
+    *tris = nullptr;
+    if (!p->shading) return 0;
+    uint64_t n = 0;
+    shadingSlotRecords(p->shading, p->slot, tris, &n);
+    if (n != p->fatTris) return fail(TBVH_E_INVALID, "%s: slot %u of the attached shading table now holds %llu records, the pose was attached to %llu", who, p->slot, (unsigned long long)n, (unsigned long long)p->fatTris);
+    return 0;
+}
+// ... and its tail: the records follow the vertices and normals just posed (inside the same timed operation)
+void updateFatTris(tbvh_pose* p, float4* tris) {
+    launch_pose_fat_tris(tris, p->fatTris, p->out, p->nOut, p->nVerts, p->fatIdx ? p->fatIdx.get() : nullptr, p->kind == kPoseSkin, p->ctx->status, p->ctx->stream);
+}
+}  // namespace
+
 namespace tbvh_capi {
+void detachPosesFrom(tbvh_context* c, const tbvh_shading* sh) {
+    for (tbvh_pose* p : c->poses)
+        if (p->shading == sh) { p->shading = nullptr; p->normals.reset(); p->nOut.reset(); p->fatIdx.reset(); p->fatTris = 0; }
+}
 void freePosesOf(tbvh_context* c) {
     for (tbvh_pose* p : c->poses) destroyPose(p);
     c->poses.clear();
@@ -139,10 +167,16 @@ int tbvh_pose_set_skin(tbvh_pose* p, const float* mats16, uint32_t nJoints, int 
     if (onDevice && ((uintptr_t)mats16 & 15)) return fail(TBVH_E_INVALID, "tbvh_pose_set_skin: device matrices must be 16-byte aligned");
     tbvh_context* c = p->ctx;
     TBVH_ENTER(c);
+    float4* fat = nullptr;
+    if (int r = attachedRecords(p, "tbvh_pose_set_skin", &fat)) return r;
     const float* dMats = nullptr;
     if (int r = stageParams(p, mats16, (uint64_t)nJoints * 64, onDevice, &dMats)) return r;
     HIP_TRY(timedBegin(c));
-    launch_pose_skin(p->rest, p->joints, p->weights, (const float4*)dMats, nJoints, p->out, p->nVerts, c->status, c->stream);
+    if (p->shading) {
+        launch_pose_skin_normals(p->rest, p->joints, p->weights, (const float4*)dMats, nJoints, p->normals, p->out, p->nOut, p->nVerts, c->status, c->stream);
+        updateFatTris(p, fat);
+    } else
+        launch_pose_skin(p->rest, p->joints, p->weights, (const float4*)dMats, nJoints, p->out, p->nVerts, c->status, c->stream);
     HIP_TRY(hipGetLastError());
     HIP_TRY(timedEnd(c));
     return 0;
@@ -156,12 +190,47 @@ int tbvh_pose_set_morph(tbvh_pose* p, const float* weights, uint32_t nTargets, i
     if (onDevice && ((uintptr_t)weights & 3)) return fail(TBVH_E_INVALID, "tbvh_pose_set_morph: device weights must be 4-byte aligned");
     tbvh_context* c = p->ctx;
     TBVH_ENTER(c);
+    float4* fat = nullptr;
+    if (int r = attachedRecords(p, "tbvh_pose_set_morph", &fat)) return r;
     const float* dW = nullptr;
     if (int r = stageParams(p, weights, (uint64_t)nTargets * 4, onDevice, &dW)) return r;
     HIP_TRY(timedBegin(c));
-    launch_pose_morph(p->positions, nTargets ? dW : p->params.get(), nTargets, p->out, p->nVerts, c->stream);
+    if (p->shading) {
+        launch_pose_morph_normals(p->positions, nTargets ? dW : p->params.get(), nTargets, p->normals, p->out, p->nOut, p->nVerts, c->stream);
+        updateFatTris(p, fat);
+    } else
+        launch_pose_morph(p->positions, nTargets ? dW : p->params.get(), nTargets, p->out, p->nVerts, c->stream);
     HIP_TRY(hipGetLastError());
     HIP_TRY(timedEnd(c));
+    return 0;
+}
+
+int tbvh_pose_attach_fat_tris(tbvh_pose* p, tbvh_shading* sh, uint32_t slot, const float* normals12, const uint32_t* indices, uint64_t nTris, int onDevice) {
+    if (!p || !sh || !normals12) return fail(TBVH_E_INVALID, "tbvh_pose_attach_fat_tris: null argument");
+    if (shadingContext(sh) != p->ctx) return fail(TBVH_E_INVALID, "tbvh_pose_attach_fat_tris: the pose and the shading table belong to different contexts");
+    if (((uintptr_t)normals12 | (uintptr_t)indices) & 3) return fail(TBVH_E_INVALID, "tbvh_pose_attach_fat_tris: misaligned normals or indices (4 bytes)");
+    if (nTris == 0 || nTris >> 32) return fail(TBVH_E_INVALID, "tbvh_pose_attach_fat_tris: %llu triangles", (unsigned long long)nTris);
+    if (!indices && p->nVerts != 3 * nTris)
+        return fail(TBVH_E_INVALID, "tbvh_pose_attach_fat_tris: %llu vertices for %llu triangles: without indices triangle i has corners 3i .. 3i + 2", (unsigned long long)p->nVerts, (unsigned long long)nTris);
+    tbvh_context* c = p->ctx;
+    TBVH_ENTER(c);
+    float4* tris = nullptr; uint64_t have = 0;
+    shadingSlotRecords(sh, slot, &tris, &have);
+    if (have != nTris) return fail(TBVH_E_INVALID, "tbvh_pose_attach_fat_tris: slot %u of the shading table holds %llu records, not %llu", slot, (unsigned long long)have, (unsigned long long)nTris);
+    if (indices && !onDevice) {   // before anything is allocated
+        const uint64_t bad = pose_first_bad_corner(indices, nTris, p->nVerts);
+        if (bad != nTris) return fail(TBVH_E_FORMAT, "tbvh_pose_attach_fat_tris: triangle %llu: an index is not a vertex (%llu vertices)", (unsigned long long)bad, (unsigned long long)p->nVerts);
+    }
+    const uint64_t nFloats = (p->kind == kPoseMorph ? (uint64_t)p->nTargets + 1 : 1) * p->nVerts * 3;
+    DevBuf<float> normals; DevBuf<float4> nOut; DevBuf<uint32_t> idx;
+    if (normals.alloc(nFloats) != hipSuccess || nOut.alloc(p->nVerts) != hipSuccess || (indices && idx.alloc(3 * nTris) != hipSuccess))
+        return allocFail("tbvh_pose_attach_fat_tris", nFloats * 4 + p->nVerts * 16 + (indices ? nTris * 12 : 0));
+    const hipMemcpyKind kind = onDevice ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
+    HIP_TRY(hipMemcpyAsync(normals, normals12, nFloats * 4, kind, c->stream));
+    if (indices) HIP_TRY(hipMemcpyAsync(idx, indices, nTris * 12, kind, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));   // (the caller's arrays are free on return; a pose in flight no longer reads the buffers replaced below)
+    p->normals = std::move(normals); p->nOut = std::move(nOut); p->fatIdx = std::move(idx);
+    p->shading = sh; p->slot = slot; p->fatTris = nTris;
     return 0;
 }
 

@@ -160,12 +160,27 @@ constexpr uint32_t kStatusPoseJoint = 64u;
 void launch_pose_skin(const float4* rest16, const uint4* joints4, const float4* weights16, const float4* mats, uint32_t nJoints, float4* out, uint64_t nVerts,
                       uint32_t* status, hipStream_t s);
 void launch_pose_morph(const float* positions12, const float* weights, uint32_t nTargets, float4* out, uint64_t nVerts, hipStream_t s);
+// ... and for a pose with FatTri records attached: the same vertices plus one posed normal per vertex, then the records' vertex0..2, vN0..2 and (skin) Nx Ny Nz
+void launch_pose_skin_normals(const float4* rest16, const uint4* joints4, const float4* weights16, const float4* mats, uint32_t nJoints, const float* normals12, float4* out,
+                              float4* nOut, uint64_t nVerts, uint32_t* status, hipStream_t s);
+void launch_pose_morph_normals(const float* positions12, const float* weights, uint32_t nTargets, const float* normals12, float4* out, float4* nOut, uint64_t nVerts,
+                               hipStream_t s);
+void launch_pose_fat_tris(float4* tris, uint64_t nTris, const float4* verts, const float4* normals, uint64_t nVerts, const uint32_t* indices, bool skin, uint32_t* status,
+                          hipStream_t s);   // a corner index >= nVerts: the triangle is left, kStatusMeshIndex (mesh_source.h) is raised
 // (kernels_omm.hip) Mesh::CreateOpacityMicroMaps on the device, one wave per triangle through omm.h: src with every pointer (the texture descriptors and
 // the texels they name included) in device memory; out: nTris * ((N * N + 31) / 32) words; N a power of two from 1 to 64.  A corner index >= nUV is clamped,
 // a texture index >= nTextures that is not the no-texture mark means no texture, and status |= kStatusOmmIndex for either.  maxBlocks: the grid's cap.
 constexpr uint32_t kStatusOmmIndex = 128u;
 struct OmmSrc;
 void launch_omm_bake(const OmmSrc& src, uint32_t N, uint32_t* out, uint32_t* status, uint32_t maxBlocks, hipStream_t s);
+// (kernels_shade.hip) GetShadingData on the device, one hit record per lane through shade.h: 48 bytes out per record; an inst / slot / prim / material /
+// texture index that is out of range is never used as an address and sets kStatusShade.  launch_shade_continue: the alpha-continue step (records whose
+// out48 alpha is 0 step on; how many did is ADDED to *nContinued when that is not null)
+constexpr uint32_t kStatusShade = 256u;
+struct ShadeTables;
+void launch_shade_hits(const ShadeTables& tb, const float4* instances, uint64_t nInst, const uint32_t* blasLayout, uint32_t blasStride, uint32_t nBlas, const void* rays,
+                       uint64_t n, uint32_t strideBytes, void* out48, uint32_t* status, hipStream_t s);
+void launch_shade_continue(void* rays, uint32_t strideBytes, const void* out48, uint64_t n, unsigned long long* nContinued, hipStream_t s);
 
 // ray generators (kernels_raygen.hip)
 struct CameraArgs {
