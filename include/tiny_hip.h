@@ -304,6 +304,47 @@ private:
     tbvh_pose* p = nullptr;
 };
 
+// Scene::UpdateSceneGraph( dt ) without the BLAS / TLAS builds, kept on the device (tbvh_scenegraph_*): made once from a tbvh_scenegraph_desc (plain arrays: the
+// node tree, the samplers' keys, the channels, the instances' nodes, the skins' joints and inverse bind matrices), then per frame Advance( dt ).  The three
+// outputs are device pointers owned by the graph: InstanceTransforms() feeds tbvh_rebuild_tlas_device( tlas, ptr, 1, .. ), JointMatrices( use ) feeds
+// Pose::SetPose( ptr, n, true ), MorphWeights( node ) feeds tbvh_pose_set_morph( pose, ptr, n, 1 ).
+class SceneGraph {
+public:
+    explicit SceneGraph(const tbvh_scenegraph_desc& desc, tbvh_context* own = nullptr, int device = 0) : ctx(own ? own : Context(device)) {
+        Check(tbvh_scenegraph_create(ctx, &desc, &g), "tbvh_scenegraph_create");
+    }
+    SceneGraph(const SceneGraph&) = delete;
+    SceneGraph& operator=(const SceneGraph&) = delete;
+    ~SceneGraph() { tbvh_scenegraph_free(g); }
+    void Advance(float dt) { Check(tbvh_scenegraph_advance(g, dt), "tbvh_scenegraph_advance"); }                                   // Scene::UpdateSceneGraph
+    void AdvanceAnimation(uint32_t anim, float dt) { Check(tbvh_scenegraph_advance_animation(g, anim, dt), "tbvh_scenegraph_advance_animation"); }   // Scene::UpdateAnimation
+    void UpdateNodes() { Check(tbvh_scenegraph_update_nodes(g), "tbvh_scenegraph_update_nodes"); }                                 // the walk of Node::Update alone
+    void SetTime(uint32_t anim, float t) { Check(tbvh_scenegraph_set_time(g, anim, t), "tbvh_scenegraph_set_time"); }              // Animation::SetTime
+    void Reset(uint32_t anim) { Check(tbvh_scenegraph_reset(g, anim), "tbvh_scenegraph_reset"); }                                  // Animation::Reset
+    void SetNodeTransform(uint32_t node, const float* mat16) { Check(tbvh_scenegraph_set_local(g, node, mat16), "tbvh_scenegraph_set_local"); }   // Scene::SetNodeTransform
+    const float* InstanceTransforms(size_t* n = nullptr) const {
+        const float* d = nullptr; uint64_t k = 0;
+        Check(tbvh_scenegraph_instance_transforms(g, &d, &k), "tbvh_scenegraph_instance_transforms");
+        if (n) *n = (size_t)k;
+        return d;
+    }
+    const float* JointMatrices(uint32_t skinUse, uint32_t* nJoints = nullptr) const {
+        const float* d = nullptr;
+        Check(tbvh_scenegraph_joint_matrices(g, skinUse, &d, nJoints), "tbvh_scenegraph_joint_matrices");
+        return d;
+    }
+    const float* MorphWeights(uint32_t node, uint32_t* nWeights = nullptr) const {
+        const float* d = nullptr;
+        Check(tbvh_scenegraph_morph_weights(g, node, &d, nWeights), "tbvh_scenegraph_morph_weights");
+        return d;
+    }
+    void Download(int what, void* dst, size_t capBytes) { Check(tbvh_scenegraph_download(g, what, dst, capBytes), "tbvh_scenegraph_download"); }
+    tbvh_scenegraph* Handle() const { return g; }
+private:
+    tbvh_context* ctx;
+    tbvh_scenegraph* g = nullptr;
+};
+
 // GetShadingData of the reference's renderers on the device (tbvh_shading_*, tbvh_shade_hits): materials and textures once, the FatTri records of every BLAS
 // slot (Mesh::triangles.data(), taken verbatim), then per frame ShadeHits after the trace: 48 bytes per ray — albedo + alpha, N + material, iN + texel.
 //   tinyhip::Shading shading( materials, nMaterials, textures, nTextures );

@@ -830,8 +830,8 @@ int tbvh_flatten_mesh_device(tbvh_context* ctx, const tbvh_mesh* mesh, void* d_v
  * (1785-1825, 1751-1778), the vertex part: what Node::Update (1973-2027) runs on the CPU per animated mesh and frame before it rebuilds or refits
  * the BLAS.  A tbvh_pose keeps the rest data on the device and ONE output buffer of n_verts float4; per frame the caller sends the joint matrices
  * (64 bytes per joint) or the morph weights, the vertices are produced where the refit reads them, and tbvh_pose_refit refits a scene from them.
- * n_verts is the number of VERTICES: an indexed mesh poses every shared vertex once.  The scene graph (the joint matrix products), animation
- * sampling and the shading data stay with the caller (the FatTri records of a shading table can follow the pose: tbvh_pose_attach_fat_tris, below).  The two kinds are separate calls, as in the reference (whose skin pass starts from
+ * n_verts is the number of VERTICES: an indexed mesh poses every shared vertex once.  The shading data stays with the caller; the scene graph (the joint matrix
+ * products) and animation sampling were on this list until tbvh_scenegraph_* (below) — what a tbvh_pose takes can still come from anywhere (the FatTri records of a shading table can follow the pose: tbvh_pose_attach_fat_tris, below).  The two kinds are separate calls, as in the reference (whose skin pass starts from
  * its own backup and overwrites a morph pass).
  *   - the arithmetic is the reference's, float operation for float operation, as its build (g++ -O3 -mavx2 -mfma, tinyscene's vector types set to
  *     tinybvh's as tiny_bvh_gltf.cpp does) performs it: tinybvh_amd/csrc/pose.h, DESIGN.md par. 14.  Skin: w of the output is 0; the homogeneous
@@ -1002,6 +1002,125 @@ int tbvh_host_pose_skin_normals(uint64_t n_verts, const uint32_t* joints4, const
 int tbvh_host_pose_morph_normals(const float* normals12, uint64_t n_verts, uint32_t n_targets, void* out16);
 int tbvh_host_pose_update_fat_tris(void* fat_tris192, uint64_t n_tris, const void* verts16, const void* normals16, uint64_t n_verts, const uint32_t* indices,
                                    int skin);
+
+/* ----------------------------------------------------------------------------------
+ * the animated scene graph on the device — Scene::UpdateSceneGraph of tiny_scene.h (3664-3697) without the BLAS and TLAS builds: Animation::Update ->
+ * Channel::Update -> Sampler::SampleVec3 / SampleQuat / SampleFloat (2457-2626), Node::UpdateTransformFromTRS (1939-1951), the matrix products of the
+ * recursive Node::Update (1959-1971), the per-skin jointMat[j] = inverse( mesh node ) * joint node * inverseBind[j] (1983-1990) and the instance
+ * transforms (2129-2136).  A tbvh_scenegraph is made once from host arrays (no glTF in the library); per frame ONE float goes up (dt), and the instance
+ * transforms, joint matrices and morph weights are produced in device memory, where tbvh_rebuild_tlas_device( .., on_device = 1 ), tbvh_pose_set_skin
+ * ( .., on_device = 1 ) and tbvh_pose_set_morph( .., on_device = 1 ) read them.  tbvh_rebuild_tlas_double_device takes double transforms: the fp64 TLAS
+ * is not fed from here.  Out of scope: Node::UpdateLights, the BLAS rebuild of BVH_DYNAMIC meshes (chain tbvh_refit / tbvh_pose_refit), morph normals.
+ *   - arithmetic: the reference's, float operation for float operation, as its build (g++ -O3 -mavx2 -mfma, tinyscene's vector types = tinybvh's)
+ *     performs it: tinybvh_amd/csrc/scenegraph.h, DESIGN.md par. 17.  The one exception is slerp's branch for cosTheta <= 0.99, which calls acosf and
+ *     sinf: the device's math library is not the host's there.
+ *   - state: per channel Channel::t and Channel::k live in the graph; the loops are the reference's ( t += dt; while (t >= duration) t -= duration, k = 0;
+ *     while (t >= time[(k + 1) % keys]) k++ ), the duration-0 / one-key branch included, so a negative or NaN dt behaves as it does there.  Where that
+ *     wrap loop would not end or would take more than 65536 turns ( |time| > 65536 * the shortest non-zero sampler duration, or an infinity ) the call
+ *     is refused (TBVH_E_INVALID) instead — a negative time of that size too, although the reference's loops would digest it without a turn: the one
+ *     departure from "a negative dt behaves as the reference".  The samplers' quirks are kept: f <= 0 returns key 0, a time before the first key returns key 0 (key 1 of a
+ *     SPLINE sampler), SampleFloat's STEP returns floatKey[k] whatever the weight, ts_normalize multiplies by the rounded 1 / m.
+ *   - two channels may write the same field of a node (across animations): the later in (animation, channel) order wins, as sequential execution has
+ *     it; this is decided at creation, and a shadowed channel still advances its t and k.  tbvh_scenegraph_advance_animation decides among the channels
+ *     of that animation alone.
+ *   - a node rebuilds localTransform = T * R * S * matrix in a walk only if a translation, rotation or scale channel ran on it since the last walk (the
+ *     reference's `transformed`); others keep the local_transform they were created with or last given (tbvh_scenegraph_set_local).  A root's combined
+ *     transform is identity * localTransform, multiplied.
+ *   - joints: Node::Update computes a skin's joint matrices when it returns from the mesh node's children, so a joint node the walk visits later
+ *     contributes the combined transform of the PREVIOUS walk (identity before the first).  Which (skin use, joint) pairs are stale follows from the
+ *     visit order and is decided at creation; those pairs read last walk's matrices, and a run of frames equals the reference's.
+ *     TBVH_SCENEGRAPH_FRESH_JOINTS makes every pair read this walk's matrix (what the reference's author presumably meant).
+ *   - visit order: roots, and the children of a node, in increasing node index — or, with visit_order, the given pre-order listing of all nodes (a
+ *     parent before its children, every subtree contiguous).  Instances are the caller's numbering (node_of_instance); the reference numbers a mesh
+ *     node's instance by its first visit.
+ *   - creation validates on the host before anything is allocated and names the first offender: null arrays, counts beyond 32 bits, a parent out of
+ *     range or a cycle, key times that are not finite and non-decreasing, a sampler without keys or with a key array too short for its interpolation
+ *     (and, for weights, the node's weight count), channel / instance / joint node indices out of range, a channel whose target does not fit its
+ *     sampler's type, a weights channel on a node without weights, channels not sorted by animation, a skin use with 0 joints: TBVH_E_INVALID for
+ *     the shape of the call, TBVH_E_FORMAT for the contents of an array.  On the device every index is checked again before it is used as an address
+ *     (the tables can be overwritten through the debug header): a violation leaves that item unwritten and the next synchronising call returns
+ *     TBVH_E_FORMAT.
+ *   - the per-frame calls are asynchronous on the context's stream; tbvh_time_last_ms reports the device time of the last advance / walk.  The
+ *     output pointers are owned by the graph, stay valid until tbvh_scenegraph_free and are written in stream order.  A graph still alive at
+ *     tbvh_shutdown is freed by it. */
+#define TBVH_SCENEGRAPH_FRESH_JOINTS 1u
+#define TBVH_GRAPH_LINEAR 0u   /* tbvh_scenegraph_desc.sampler_interpolation: Animation::Sampler's enum */
+#define TBVH_GRAPH_SPLINE 1u
+#define TBVH_GRAPH_STEP   2u
+#define TBVH_GRAPH_VEC3   0u   /* .sampler_type: 3 floats per element (translation, scale) */
+#define TBVH_GRAPH_QUAT   1u   /* 4 floats per element in ts_quat's member order w x y z (rotation) */
+#define TBVH_GRAPH_FLOAT  2u   /* the reference's floatKey (weights): element (k * count + i), times 3 (+ 0 in-tangent, + 1 value, + 2 out-tangent) for SPLINE */
+typedef struct tbvh_scenegraph_desc {
+    uint32_t flags;                        /* 0 or TBVH_SCENEGRAPH_FRESH_JOINTS */
+    uint64_t n_nodes;
+    const int32_t* parent;                 /* n_nodes; -1 for a root */
+    const uint32_t* visit_order;           /* n_nodes, or NULL: increasing node index among siblings */
+    const float* translation;              /* n_nodes x 3 */
+    const float* rotation;                 /* n_nodes x 4, w x y z */
+    const float* scale;                    /* n_nodes x 3 */
+    const float* matrix;                   /* n_nodes x 16, row-major: Node::matrix */
+    const float* local_transform;          /* n_nodes x 16: Node::localTransform as it is before the first frame */
+    const uint32_t* n_weights;             /* n_nodes morph weight counts, or NULL: none */
+    const float* weights;                  /* the initial weights, node after node, or NULL: zeros */
+    uint64_t n_samplers;
+    const uint32_t* sampler_interpolation; /* n_samplers */
+    const uint32_t* sampler_type;          /* n_samplers */
+    const uint32_t* sampler_key_offset;    /* n_samplers + 1: sampler s has key times [ offset[s], offset[s + 1] ) of key_times */
+    const uint32_t* sampler_value_offset;  /* n_samplers + 1: ... and the floats [ offset[s], offset[s + 1] ) of key_values */
+    const float* key_times;
+    const float* key_values;
+    uint64_t n_animations;
+    uint64_t n_channels;
+    const uint32_t* channel_animation;     /* n_channels, non-decreasing */
+    const uint32_t* channel_sampler;       /* an index into the samplers above (all animations' samplers in one list) */
+    const uint32_t* channel_node;
+    const uint32_t* channel_target;        /* 0 translation, 1 rotation, 2 scale, 3 weights */
+    uint64_t n_instances;
+    const uint32_t* node_of_instance;      /* n_instances */
+    uint64_t n_skin_uses;                  /* one per skinned mesh node */
+    const uint32_t* skin_mesh_node;        /* n_skin_uses */
+    const uint32_t* skin_joint_offset;     /* n_skin_uses + 1: skin use u has the joints [ offset[u], offset[u + 1] ) of the two arrays below */
+    const uint32_t* skin_joint_node;
+    const float* skin_inverse_bind;        /* 16 floats per joint */
+} tbvh_scenegraph_desc;
+/* tbvh_scenegraph_download( what ): dst receives ... (cap_bytes smaller than that: TBVH_E_INVALID) */
+#define TBVH_GRAPH_TRS        0   /* n_nodes x 10 floats: translation, rotation (w x y z), scale */
+#define TBVH_GRAPH_LOCAL      1   /* n_nodes x 16 floats */
+#define TBVH_GRAPH_COMBINED   2   /* n_nodes x 16 floats */
+#define TBVH_GRAPH_CHANNEL_T  3   /* n_channels floats */
+#define TBVH_GRAPH_CHANNEL_K  4   /* n_channels int32 */
+#define TBVH_GRAPH_INSTANCES  5   /* n_instances x 16 floats */
+#define TBVH_GRAPH_JOINTS     6   /* 16 floats per joint, skin use after skin use */
+#define TBVH_GRAPH_WEIGHTS    7   /* the morph weights, node after node */
+#define TBVH_GRAPH_STALE      8   /* one uint32 per joint, skin use after skin use: 1 = reads last walk's matrix (a property of the tree) */
+#define TBVH_GRAPH_TRIG       9   /* one uint32 per channel: 1 = its last sample took slerp's trigonometric branch (acosf, sinf: the one path that is not bit-exact) */
+typedef struct tbvh_scenegraph tbvh_scenegraph;
+int tbvh_scenegraph_create(tbvh_context* ctx, const tbvh_scenegraph_desc* desc, tbvh_scenegraph** out);
+int tbvh_scenegraph_advance(tbvh_scenegraph* g, float dt);                               /* UpdateSceneGraph( dt ) minus the builds */
+int tbvh_scenegraph_advance_animation(tbvh_scenegraph* g, uint32_t animation, float dt); /* Scene::UpdateAnimation: no walk */
+int tbvh_scenegraph_update_nodes(tbvh_scenegraph* g);                                    /* the walk alone */
+int tbvh_scenegraph_set_time(tbvh_scenegraph* g, uint32_t animation, float t);           /* Animation::SetTime */
+int tbvh_scenegraph_reset(tbvh_scenegraph* g, uint32_t animation);                       /* Animation::Reset */
+int tbvh_scenegraph_set_local(tbvh_scenegraph* g, uint32_t node, const float* mat16);    /* Scene::SetNodeTransform (host matrix, staged before return) */
+int tbvh_scenegraph_instance_transforms(tbvh_scenegraph* g, const float** d_mats16, uint64_t* n_instances);
+int tbvh_scenegraph_joint_matrices(tbvh_scenegraph* g, uint32_t skin_use, const float** d_mats16, uint32_t* n_joints);
+int tbvh_scenegraph_morph_weights(tbvh_scenegraph* g, uint32_t node, const float** d_weights, uint32_t* n_weights);
+int tbvh_scenegraph_download(tbvh_scenegraph* g, int what, void* dst, uint64_t cap_bytes);   /* synchronous; reports the status word */
+void tbvh_scenegraph_free(tbvh_scenegraph* g);
+/* The same object and calls on the CPU (scenegraph.h compiled for the host), no context; the pointers of the three output calls are host memory. */
+typedef struct tbvh_host_scenegraph tbvh_host_scenegraph;
+int tbvh_host_scenegraph_create(const tbvh_scenegraph_desc* desc, tbvh_host_scenegraph** out);
+int tbvh_host_scenegraph_advance(tbvh_host_scenegraph* g, float dt);
+int tbvh_host_scenegraph_advance_animation(tbvh_host_scenegraph* g, uint32_t animation, float dt);
+int tbvh_host_scenegraph_update_nodes(tbvh_host_scenegraph* g);
+int tbvh_host_scenegraph_set_time(tbvh_host_scenegraph* g, uint32_t animation, float t);
+int tbvh_host_scenegraph_reset(tbvh_host_scenegraph* g, uint32_t animation);
+int tbvh_host_scenegraph_set_local(tbvh_host_scenegraph* g, uint32_t node, const float* mat16);
+int tbvh_host_scenegraph_instance_transforms(tbvh_host_scenegraph* g, const float** mats16, uint64_t* n_instances);
+int tbvh_host_scenegraph_joint_matrices(tbvh_host_scenegraph* g, uint32_t skin_use, const float** mats16, uint32_t* n_joints);
+int tbvh_host_scenegraph_morph_weights(tbvh_host_scenegraph* g, uint32_t node, const float** weights, uint32_t* n_weights);
+int tbvh_host_scenegraph_download(tbvh_host_scenegraph* g, int what, void* dst, uint64_t cap_bytes);
+void tbvh_host_scenegraph_free(tbvh_host_scenegraph* g);
 
 #ifdef __cplusplus
 }

@@ -60,6 +60,23 @@ int tbvh_debug_wide_copy_bvh2(int layout, const void* blob, uint64_t n_blob, con
  * what tests/test_device_memory.py asserts.  Needs no device and no context. */
 int tbvh_debug_device_allocations(uint64_t out[2]);
 
+/* The device address of one of a scene graph's arrays (what: the TBVH_GRAPH_* codes of tbvh_scenegraph_download; TBVH_GRAPH_COMBINED: the last walk's), so that a
+ * test can overwrite a table or a key state on the device and see the kernels' own range checks answer (tests/test_scenegraph_gpu.py).  Not for products: the
+ * arrays are the graph's private state. */
+struct tbvh_scenegraph;
+int tbvh_debug_scenegraph_array(struct tbvh_scenegraph* g, int what, void** d_ptr);
+/* ONE kernel of an advance as a timed operation of its own (tbvh_time_last_ms), for tools/scenegraph_anim_bench.py: step 0 = k_graph_sample over every channel
+ * with dt, 1 = k_graph_local, 2 = k_graph_combine, 3 = k_graph_outputs.  Steps 0, 1, 2, 3 in this order are one tbvh_scenegraph_advance. */
+int tbvh_debug_scenegraph_step(struct tbvh_scenegraph* g, int step, float dt);
+/* Every node's T, R, S of a host graph replaced at once (n_nodes x 10 floats: translation, rotation w x y z, scale; n_nodes must be the graph's).  Which nodes
+ * rebuild their local transform in the next walk stays as the channels left it.  For tests that pin the walk to given inputs. */
+struct tbvh_host_scenegraph;
+int tbvh_debug_host_scenegraph_set_trs(struct tbvh_host_scenegraph* g, const float* trs10, uint64_t n_nodes);
+/* The host twin walks parent-first; the kernels multiply every node down its own ancestor list (k_graph_combine).  This runs THAT form on the CPU over the host
+ * graph's lists, as the kernel does, and reports how many nodes' combined transforms differ in any bit from the last walk's (0 is the only right answer), so that
+ * the lists sg_compile builds and their range checks are exercised without a GPU (tools/scenegraph_sanitize.cpp, tests/test_scenegraph_host.py). */
+int tbvh_debug_host_scenegraph_check_chains(struct tbvh_host_scenegraph* g, uint64_t* n_differ);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1583,6 +1583,160 @@ class Pose:
             pass
 
 
+# ---- the animated scene graph (capi_scenegraph.hip, scenegraph_host.cpp) ------------------------------------------------------------------
+SCENEGRAPH_FRESH_JOINTS = 1
+GRAPH_LINEAR, GRAPH_SPLINE, GRAPH_STEP = 0, 1, 2
+GRAPH_VEC3, GRAPH_QUAT, GRAPH_FLOAT = 0, 1, 2
+GRAPH_TRS, GRAPH_LOCAL, GRAPH_COMBINED, GRAPH_CHANNEL_T, GRAPH_CHANNEL_K, GRAPH_INSTANCES, GRAPH_JOINTS, GRAPH_WEIGHTS, GRAPH_STALE, GRAPH_TRIG = range(10)
+_GRAPH_ARRAYS = (("parent", np.int32), ("visit_order", np.uint32), ("translation", np.float32), ("rotation", np.float32), ("scale", np.float32), ("matrix", np.float32),
+                 ("local_transform", np.float32), ("n_weights", np.uint32), ("weights", np.float32), ("sampler_interpolation", np.uint32), ("sampler_type", np.uint32),
+                 ("sampler_key_offset", np.uint32), ("sampler_value_offset", np.uint32), ("key_times", np.float32), ("key_values", np.float32),
+                 ("channel_animation", np.uint32), ("channel_sampler", np.uint32), ("channel_node", np.uint32), ("channel_target", np.uint32),
+                 ("node_of_instance", np.uint32), ("skin_mesh_node", np.uint32), ("skin_joint_offset", np.uint32), ("skin_joint_node", np.uint32),
+                 ("skin_inverse_bind", np.float32))
+
+
+def scenegraph_desc(d: dict):
+    """tbvh_scenegraph_desc from a dict of arrays named as the struct's members (missing or None: NULL), plus "flags" and "n_animations".  The counts come
+    from the arrays: parent (nodes), sampler_interpolation, channel_node, node_of_instance, skin_mesh_node.  Returns (struct, the arrays it points into)."""
+    keep = {}
+    desc = _capi.SceneGraphDesc()
+    for name, dt in _GRAPH_ARRAYS:
+        a = d.get(name)
+        if a is None:
+            continue
+        keep[name] = a = np.ascontiguousarray(a, dt).reshape(-1)
+        setattr(desc, name, a.ctypes.data if a.size else None)
+    n = lambda k: keep[k].size if k in keep else 0
+    desc.flags = int(d.get("flags", 0))
+    desc.n_nodes, desc.n_samplers, desc.n_channels, desc.n_instances, desc.n_skin_uses = n("parent"), n("sampler_interpolation"), n("channel_node"), n("node_of_instance"), n("skin_mesh_node")
+    desc.n_animations = int(d.get("n_animations", (int(keep["channel_animation"].max()) + 1) if n("channel_animation") else 0))
+    return desc, keep
+
+
+class _GraphBase:
+    """What SceneGraph (device) and HostSceneGraph (CPU) share: the calls differ in their prefix and in where the output pointers live."""
+    _prefix = ""
+
+    def _fn(self, name):
+        return getattr(lib, self._prefix + name)
+
+    def _made(self, keep):
+        n = lambda k: keep[k].size if k in keep else 0
+        self.n_nodes, self.n_channels, self.n_instances, self.n_skin_uses = n("parent"), n("channel_node"), n("node_of_instance"), n("skin_mesh_node")
+        self.n_joints = int(keep["skin_joint_offset"][-1]) if self.n_skin_uses else 0
+        self.n_weights = int(keep["n_weights"].sum()) if "n_weights" in keep else 0
+
+    def Advance(self, dt: float):
+        """Scene::UpdateSceneGraph( dt ) without the BLAS / TLAS builds"""
+        check(self._fn("advance")(self._h, float(dt)), self._prefix + "advance")
+        return self
+
+    def AdvanceAnimation(self, animation: int, dt: float):
+        check(self._fn("advance_animation")(self._h, int(animation), float(dt)), self._prefix + "advance_animation")
+        return self
+
+    def UpdateNodes(self):
+        check(self._fn("update_nodes")(self._h), self._prefix + "update_nodes")
+        return self
+
+    def SetTime(self, animation: int, t: float):
+        check(self._fn("set_time")(self._h, int(animation), float(t)), self._prefix + "set_time")
+        return self
+
+    def Reset(self, animation: int):
+        check(self._fn("reset")(self._h, int(animation)), self._prefix + "reset")
+        return self
+
+    def SetLocal(self, node: int, mat16):
+        m = np.ascontiguousarray(mat16, np.float32).reshape(16)
+        check(self._fn("set_local")(self._h, int(node), _ptr(m)), self._prefix + "set_local")
+        return self
+
+    def InstanceTransforms(self):
+        """(pointer to n_instances x 16 floats, n_instances): feeds TLAS.RebuildOnDevice( ptr, on_device=True )"""
+        p = C.c_void_p(); n = C.c_uint64(0)
+        check(self._fn("instance_transforms")(self._h, C.byref(p), C.byref(n)), self._prefix + "instance_transforms")
+        return p.value, int(n.value)
+
+    def JointMatrices(self, skin_use: int):
+        """(pointer to n_joints x 16 floats, n_joints) of one skin use: feeds Pose.SetPose( ptr, on_device=True )"""
+        p = C.c_void_p(); n = C.c_uint32(0)
+        check(self._fn("joint_matrices")(self._h, int(skin_use), C.byref(p), C.byref(n)), self._prefix + "joint_matrices")
+        return p.value, int(n.value)
+
+    def MorphWeights(self, node: int):
+        """(pointer to the node's morph weights, their number): feeds a morph Pose.SetPose( ptr, on_device=True )"""
+        p = C.c_void_p(); n = C.c_uint32(0)
+        check(self._fn("morph_weights")(self._h, int(node), C.byref(p), C.byref(n)), self._prefix + "morph_weights")
+        return p.value, int(n.value)
+
+    def Download(self, what: int) -> np.ndarray:
+        """GRAPH_TRS (n, 10), GRAPH_LOCAL / GRAPH_COMBINED (n, 16), GRAPH_CHANNEL_T / _K (channels,), GRAPH_INSTANCES (instances, 16), GRAPH_JOINTS (joints, 16),
+        GRAPH_WEIGHTS, GRAPH_STALE (joints,), GRAPH_TRIG (channels,).  Synchronous; raises for a device-detected bad index."""
+        shape, dt = {GRAPH_TRS: ((self.n_nodes, 10), np.float32), GRAPH_LOCAL: ((self.n_nodes, 16), np.float32), GRAPH_COMBINED: ((self.n_nodes, 16), np.float32),
+                     GRAPH_CHANNEL_T: ((self.n_channels,), np.float32), GRAPH_CHANNEL_K: ((self.n_channels,), np.int32), GRAPH_INSTANCES: ((self.n_instances, 16), np.float32),
+                     GRAPH_JOINTS: ((self.n_joints, 16), np.float32), GRAPH_WEIGHTS: ((self.n_weights,), np.float32), GRAPH_STALE: ((self.n_joints,), np.uint32),
+                     GRAPH_TRIG: ((self.n_channels,), np.uint32)}[what]
+        out = np.zeros(shape, dt)
+        buf = out if out.size else np.zeros(1, dt)
+        check(self._fn("download")(self._h, int(what), _ptr(buf), out.nbytes), self._prefix + "download")
+        return out
+
+
+class SceneGraph(_GraphBase):
+    """An animated scene graph kept on the device (tbvh_scenegraph_*; Scene::UpdateSceneGraph of tiny_scene.h): made once from a dict of arrays
+    (scenegraph_desc), then per frame Advance( dt ); the instance transforms, joint matrices and morph weights stay in device memory."""
+    _prefix = "tbvh_scenegraph_"
+
+    def __init__(self, ctx: Context, desc: dict):
+        self.ctx = ctx
+        self._h = C.c_void_p()
+        st, keep = scenegraph_desc(desc)
+        check(lib.tbvh_scenegraph_create(ctx._h, C.byref(st), C.byref(self._h)), "tbvh_scenegraph_create")
+        self._made(keep)
+
+    def free(self):
+        if self._h and self.ctx._h:   # (a closed context has freed its graphs itself: tbvh_shutdown)
+            lib.tbvh_scenegraph_free(self._h)
+        self._h = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+class HostSceneGraph(_GraphBase):
+    """The same object on the CPU (tbvh_host_scenegraph_*): the same arithmetic header compiled for the host, no context."""
+    _prefix = "tbvh_host_scenegraph_"
+
+    def __init__(self, desc: dict):
+        self._h = C.c_void_p()
+        st, keep = scenegraph_desc(desc)
+        check(lib.tbvh_host_scenegraph_create(C.byref(st), C.byref(self._h)), "tbvh_host_scenegraph_create")
+        self._made(keep)
+
+    def SetTRS(self, trs10):
+        """every node's translation, rotation (w x y z), scale at once; the nodes' "written" marks stay as the channels left them"""
+        a = np.ascontiguousarray(trs10, np.float32)
+        assert a.size == self.n_nodes * 10
+        check(lib.tbvh_debug_host_scenegraph_set_trs(self._h, _ptr(a), self.n_nodes), "tbvh_debug_host_scenegraph_set_trs")
+        return self
+
+    def free(self):
+        if self._h:
+            lib.tbvh_host_scenegraph_free(self._h)
+        self._h = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
 # ---- hits resolved to shading data (capi_shade.hip) --------------------------------------------------------------------------------------
 # tinyscene::FatTri, 192 bytes, taken verbatim
 FATTRI_DTYPE = np.dtype([

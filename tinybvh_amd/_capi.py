@@ -35,6 +35,16 @@ class OmmSource(C.Structure):   # tbvh_omm_source
                 ("n_tris", C.c_uint64), ("tri_texture", C.c_void_p), ("textures", C.POINTER(AlphaTexture)), ("n_textures", C.c_uint32)]
 
 
+class SceneGraphDesc(C.Structure):   # tbvh_scenegraph_desc
+    _fields_ = [("flags", C.c_uint32), ("n_nodes", C.c_uint64), ("parent", C.c_void_p), ("visit_order", C.c_void_p), ("translation", C.c_void_p), ("rotation", C.c_void_p),
+                ("scale", C.c_void_p), ("matrix", C.c_void_p), ("local_transform", C.c_void_p), ("n_weights", C.c_void_p), ("weights", C.c_void_p),
+                ("n_samplers", C.c_uint64), ("sampler_interpolation", C.c_void_p), ("sampler_type", C.c_void_p), ("sampler_key_offset", C.c_void_p),
+                ("sampler_value_offset", C.c_void_p), ("key_times", C.c_void_p), ("key_values", C.c_void_p), ("n_animations", C.c_uint64), ("n_channels", C.c_uint64),
+                ("channel_animation", C.c_void_p), ("channel_sampler", C.c_void_p), ("channel_node", C.c_void_p), ("channel_target", C.c_void_p),
+                ("n_instances", C.c_uint64), ("node_of_instance", C.c_void_p), ("n_skin_uses", C.c_uint64), ("skin_mesh_node", C.c_void_p),
+                ("skin_joint_offset", C.c_void_p), ("skin_joint_node", C.c_void_p), ("skin_inverse_bind", C.c_void_p)]
+
+
 class Camera(C.Structure):
     _fields_ = [("eye", C.c_float * 3), ("p1", C.c_float * 3), ("p2", C.c_float * 3), ("p3", C.c_float * 3),
                 ("width", _u32), ("height", _u32), ("spp_x", _u32), ("spp_y", _u32)]
@@ -183,6 +193,35 @@ SYMBOLS = {
     "tbvh_pose_refit": (_i, [_vp, _vp]),
     "tbvh_pose_download": (_i, [_vp, _vp, _u64]),
     "tbvh_pose_free": (None, [_vp]),
+    # the animated scene graph (capi_scenegraph.hip, scenegraph_host.cpp)
+    "tbvh_scenegraph_create": (_i, [_vp, C.POINTER(SceneGraphDesc), _pp]),
+    "tbvh_scenegraph_advance": (_i, [_vp, C.c_float]),
+    "tbvh_scenegraph_advance_animation": (_i, [_vp, _u32, C.c_float]),
+    "tbvh_scenegraph_update_nodes": (_i, [_vp]),
+    "tbvh_scenegraph_set_time": (_i, [_vp, _u32, C.c_float]),
+    "tbvh_scenegraph_reset": (_i, [_vp, _u32]),
+    "tbvh_scenegraph_set_local": (_i, [_vp, _u32, _vp]),
+    "tbvh_scenegraph_instance_transforms": (_i, [_vp, _pp, C.POINTER(_u64)]),
+    "tbvh_scenegraph_joint_matrices": (_i, [_vp, _u32, _pp, C.POINTER(_u32)]),
+    "tbvh_scenegraph_morph_weights": (_i, [_vp, _u32, _pp, C.POINTER(_u32)]),
+    "tbvh_scenegraph_download": (_i, [_vp, _i, _vp, _u64]),
+    "tbvh_scenegraph_free": (None, [_vp]),
+    "tbvh_debug_scenegraph_array": (_i, [_vp, _i, _pp]),
+    "tbvh_debug_scenegraph_step": (_i, [_vp, _i, C.c_float]),
+    "tbvh_host_scenegraph_create": (_i, [C.POINTER(SceneGraphDesc), _pp]),
+    "tbvh_host_scenegraph_advance": (_i, [_vp, C.c_float]),
+    "tbvh_host_scenegraph_advance_animation": (_i, [_vp, _u32, C.c_float]),
+    "tbvh_host_scenegraph_update_nodes": (_i, [_vp]),
+    "tbvh_host_scenegraph_set_time": (_i, [_vp, _u32, C.c_float]),
+    "tbvh_host_scenegraph_reset": (_i, [_vp, _u32]),
+    "tbvh_host_scenegraph_set_local": (_i, [_vp, _u32, _vp]),
+    "tbvh_debug_host_scenegraph_set_trs": (_i, [_vp, _vp, _u64]),
+    "tbvh_debug_host_scenegraph_check_chains": (_i, [_vp, C.POINTER(_u64)]),
+    "tbvh_host_scenegraph_instance_transforms": (_i, [_vp, _pp, C.POINTER(_u64)]),
+    "tbvh_host_scenegraph_joint_matrices": (_i, [_vp, _u32, _pp, C.POINTER(_u32)]),
+    "tbvh_host_scenegraph_morph_weights": (_i, [_vp, _u32, _pp, C.POINTER(_u32)]),
+    "tbvh_host_scenegraph_download": (_i, [_vp, _i, _vp, _u64]),
+    "tbvh_host_scenegraph_free": (None, [_vp]),
     "tbvh_host_pose_skin": (_i, [_vp, _u64, _vp, _vp, _vp, _u32, _vp]),
     "tbvh_host_pose_morph": (_i, [_vp, _u64, _u32, _vp, _vp]),
     # opacity micromaps baked from alpha textures (capi_omm.hip)

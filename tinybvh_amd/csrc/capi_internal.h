@@ -127,6 +127,7 @@ struct tbvh_context {
     DevBuf<void> binScratch;      // tbvh_bin_rays_device
     std::vector<tbvh_scene*> scenes;
     std::vector<struct tbvh_pose*> poses;   // (capi_pose.hip) the poses made on this context: tbvh_shutdown frees those the caller has not
+    std::vector<struct tbvh_scenegraph*> graphs;   // (capi_scenegraph.hip) likewise the scene graphs
     std::vector<struct tbvh_shading*> shadings;   // (capi_shade.hip) likewise the shading tables
     // (capi_omm.hip) the texture descriptors of a bake go up through a pinned area, in stream order, into ommDesc: a device-resident bake stays asynchronous;
     // the area is reused once the previous bake's copy has left it (ommEv)
@@ -416,6 +417,7 @@ int launchSpheres(tbvh_scene* s, const float4* dSpheres, uint64_t n, const tbvh:
 int allocOpacityMaps(tbvh_context* c, uint32_t N, uint64_t nTris, const char* who, DevBuf<uint32_t>& fresh, uint64_t* wordsOut);
 int installOpacityMaps(tbvh_scene* s, DevBuf<uint32_t>&& fresh, uint32_t N);
 void freeOmmStagingOf(tbvh_context* c);   // (capi_omm.hip) tbvh_shutdown: the pinned area and the event of the texture-descriptor upload
+void freeGraphsOf(tbvh_context* c);   // (capi_scenegraph.hip) likewise
 void freePosesOf(tbvh_context* c);   // (capi_pose.hip) tbvh_shutdown: the context's stream is idle, its device current
 void freeShadingsOf(tbvh_context* c);   // (capi_shade.hip) likewise
 // (capi_shade.hip) what a pose with FatTri records attached needs of a shading table: its context, and a slot's records as they are now (nullptr / 0: none)

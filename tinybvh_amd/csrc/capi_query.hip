@@ -473,6 +473,10 @@ int checkStatus(tbvh_context* c) {
         hipMemsetAsync(c->status, 0, 4, c->stream);
         return fail(TBVH_E_FORMAT, "opacity micromap bake: a device-resident index is not a UV (>= n_uv; clamped) or a texture index is not a texture (>= n_textures; taken as none)");
     }
+    if (st & kStatusGraph) {
+        hipMemsetAsync(c->status, 0, 4, c->stream);
+        return fail(TBVH_E_FORMAT, "scene graph: a sampler, node, key state or key position of a graph was out of range on the device; that channel, node, instance or joint was not written");
+    }
     if (st & kStatusShade) {
         hipMemsetAsync(c->status, 0, 4, c->stream);
         return fail(TBVH_E_FORMAT, "shade: a hit record's instance, BLAS slot or primitive, or a device-resident material or texture index, is out of range (the record got no surface, or an untextured albedo of 0)");

@@ -3,6 +3,7 @@
 #include <vector>
 #include "device_common.h"
 #include "mesh_source.h"
+#include "scenegraph.h"
 
 namespace tbvh {
 
@@ -227,5 +228,14 @@ void launch_wf_generate(const CameraArgs& cam, RayRec* rays, PathAux* aux, uint6
 void launch_wf_shade(const ShadeArgs& a, uint64_t capacity, hipStream_t s);
 void launch_wf_finalize(const float* accum, float scale, uint32_t* pixels, uint64_t n, hipStream_t s);
 void launch_wf_connect(const uint8_t* occ, const PathAux* aux, const unsigned long long* nShadow, float* accum, uint64_t capacity, hipStream_t s);
+
+// kernels_scenegraph.hip: the animated scene graph (tbvh_scenegraph_*; scenegraph.h holds the arithmetic and kStatusGraph).  One work item per lane, exact grids.
+// launch_graph_sample: channels [c0, c1) advance by dt and write their node's T, R, S or weights unless (flags & shadowMask).  launch_graph_walk: the three kernels
+// of one walk (local transforms of written nodes; combined transforms down each node's own ancestor chain; instance transforms and joint matrices).
+void launch_graph_sample(const SgView& g, uint32_t c0, uint32_t c1, float dt, uint32_t shadowMask, hipStream_t s);
+void launch_graph_walk(const SgView& g, int only, hipStream_t s);   // only: -1 all, 1 local, 2 combine, 3 outputs
+void launch_graph_set_time(float* cT, int32_t* cK, uint32_t c0, uint32_t c1, float t, hipStream_t s);
+struct SgMat { float m[16]; };
+void launch_graph_set_local(float* local, uint32_t node, const SgMat& m, hipStream_t s);   // (the matrix travels as a kernel argument: nothing of the caller's is read after the call)
 
 }  // namespace tbvh
