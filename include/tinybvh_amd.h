@@ -81,6 +81,14 @@ int         tbvh_synchronize(tbvh_context* ctx);
 /* Make subsequent launches of this context go to an external hipStream_t (e.g. the
  * current torch stream); NULL restores the context's own stream. */
 int         tbvh_set_stream(tbvh_context* ctx, void* hip_stream);
+/* Independent device-resident queries overlap within one context (default on; TBVH_OVERLAP=0 in the environment, or enabled = 0 here: every launch waits
+ * for the one before it, as on a context with one stream).  tbvh_intersect_device, tbvh_intersect_device_fresh and tbvh_occluded_device return once the
+ * launch is enqueued; a launch whose ray records (64 n bytes from d_rays) and any-hit flags (n bytes from d_occ) share no byte with a launch still in flight
+ * starts while that one's last waves are still running, on a second stream of the context's own.  Launches that share a byte keep their order, and so does
+ * everything else: a query comes after every generator, copy, refit or update called before it, and every other call on the context comes after every
+ * query called before it.  The caller sees no difference but in time.  Never used on a caller's stream (tbvh_set_stream), with timing off
+ * (tbvh_set_timing) or while the scene's schedule tuner is measuring. */
+int         tbvh_context_set_overlap(tbvh_context* ctx, int enabled);
 /* Per-operation device timing on (default) or off.  On: every query / refit / rebuild is bracketed by a HIP event pair — what
  * tbvh_time_last_ms and tbvh_time_history read, the CL_PROFILING_COMMAND_START / END of tiny_bvh_speedtest.cpp:1126-1131.  Off: nothing but the
  * kernels is enqueued (two event records fewer per query: a few microseconds each, which a renderer issuing many small queries per frame
@@ -318,7 +326,11 @@ float tbvh_time_last_ms(tbvh_context* ctx);
  * the 256 the context remembers; *count = how many were written.  A renderer (or bench.py's timed loop) enqueues its
  * launches back to back and reads the durations once at the end — per-launch tbvh_time_last_ms() calls expose every
  * launch's latency (0.4 ms per two-query step on the round-3 driver box).  Waits for the operations it reports.
- * An entry is -1 when that operation failed before its end was recorded. */
+ * An entry is -1 when that operation failed before its end was recorded.
+ * Queries that overlapped (tbvh_context_set_overlap): a launch that started before an earlier launch had ended reports the time it ADDED — from the latest
+ * end of another launch inside its own interval to its own end, i.e. end(k) - end(k - 1) for launches that finish in the order they were enqueued — and
+ * not its raw interval, which would count the other launch's work again.  The entries of a loop thus still sum to (at most) its wall time; a launch that
+ * overlapped nothing reports its own interval exactly as before.  tbvh_time_last_ms() follows the same rule. */
 int tbvh_time_history(tbvh_context* ctx, float* ms, uint32_t cap, uint32_t* count);
 
 /* The machine's own ceilings, measured where the kernels run (bench.py's roofline denominators; best of `reps` launches, 0 = 3):

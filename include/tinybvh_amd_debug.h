@@ -38,6 +38,16 @@ int tbvh_debug_coherent_schedule(tbvh_scene* scene, int anyhit, uint32_t out[4])
  * triangle phase, a third more waves).  Synchronizes the stream. */
 int tbvh_debug_last_probe(tbvh_context* ctx, uint32_t out[3]);
 
+/* The two launch lanes of a context (tbvh_context_set_overlap): out[0] = query launches that went to the second lane since the context was made,
+ * out[1] = joins taken (the first lane made to wait for the second one's last launch: by a launch that conflicted with launches on both lanes or found
+ * its lane's list full, by a launch a schedule tuner measured, or by any other call on the context while the second lane held work). */
+int tbvh_debug_overlap_stats(tbvh_context* ctx, uint64_t out[2]);
+/* The rule that picks a launch's lane (tinybvh_amd/csrc/overlap_lanes.h), run over a script on the host; no device, no context.  ops5: n_ops rows of 5 x u64
+ * {operation, a, b, c, d}.  0 = a launch touching ray bytes [a, b) and flag bytes [c, d) (c == d: none): finished launches are pruned, the lane is chosen, the
+ * launch is recorded under its row number; out[row] = lane + 2 if the lanes were joined first.  1 = the launch of row a has finished.  2 = the second lane
+ * is available (a != 0) or not.  3 = out[row] = launches in flight on lane 0 + 256 x those on lane 1, after pruning.  Other rows leave out[row] = 0. */
+int tbvh_debug_lane_script(const uint64_t* ops5, uint64_t n_ops, int32_t* out);
+
 /* Diagnostic kernel variants of BVH8_CWBVH scenes (0 = default): 72 / 52 force the strict / the coherent schedule whatever
  * the probe says, 90 the incoherent flavor on the copies of tbvh_cwbvh_set_hybrid, 75 / 88 split the last rays whatever the batch size, 59 / 61 / 73 / 78 / 82 / 83 are the instrumented
  * kernels behind tbvh_debug_stats.  Returns TBVH_E_INVALID for anything else. */

@@ -94,6 +94,16 @@ class Context:
     def set_stream(self, hip_stream: Optional[int]):
         check(lib.tbvh_set_stream(self._h, C.c_void_p(hip_stream or 0)), "tbvh_set_stream")
 
+    def set_overlap(self, enabled: bool):
+        """Independent device-resident queries overlap within this context (tbvh_context_set_overlap; default on, TBVH_OVERLAP=0 turns it off)."""
+        check(lib.tbvh_context_set_overlap(self._h, 1 if enabled else 0), "tbvh_context_set_overlap")
+
+    def overlap_stats(self):
+        """(query launches that took the second lane, joins taken) since the context was made (tbvh_debug_overlap_stats)."""
+        out = (C.c_uint64 * 2)()
+        check(lib.tbvh_debug_overlap_stats(self._h, out), "tbvh_debug_overlap_stats")
+        return int(out[0]), int(out[1])
+
     def set_timing(self, enabled: bool):
         """Per-operation HIP-event timing on / off (tbvh_set_timing): off saves two event records per query."""
         check(lib.tbvh_set_timing(self._h, 1 if enabled else 0), "tbvh_set_timing")

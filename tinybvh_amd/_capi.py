@@ -75,6 +75,9 @@ SYMBOLS = {
     "tbvh_shutdown": (None, [_vp]),
     "tbvh_synchronize": (_i, [_vp]),
     "tbvh_set_stream": (_i, [_vp, _vp]),
+    "tbvh_context_set_overlap": (_i, [_vp, _i]),
+    "tbvh_debug_overlap_stats": (_i, [_vp, _vp]),
+    "tbvh_debug_lane_script": (_i, [_vp, _u64, _vp]),
     "tbvh_set_timing": (_i, [_vp, _i]),
     "tbvh_upload_bvh_gpu": (_i, [_vp, _vp, _u64, _vp, _u64, _vp, _u64, _pp]),
     "tbvh_upload_bvh4_gpu": (_i, [_vp, _vp, _u64, _pp]),

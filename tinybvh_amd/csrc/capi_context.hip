@@ -17,25 +17,65 @@ int fail(int code, const char* fmt, ...) {
     return code;
 }
 
-int setDevice(tbvh_context* c) {
-    HIP_TRY(hipSetDevice(c->device));
+// Lane 0 waits for lane 1's last launch; from here on nothing that is enqueued on either lane can pass a launch enqueued before.  (Lane 1's next
+// launch waits for lane 0's position in turn: lane0Touched.)  Called by every entry point through setDevice; a launch that may overlap skips it.
+int joinLanes(tbvh_context* c) {
+    if (c->lane1Dirty) {
+        HIP_TRY(hipStreamWaitEvent(c->stream, c->lane1Last, 0));
+        c->lane1Dirty = false;
+        c->laneJoins++;
+    }
+    c->book.joined();
+    c->lane0Touched = true;
+    c->chain++;
+    if (!c->chain) c->chain = 1;
     return 0;
 }
-hipError_t timedBegin(tbvh_context* c) {
+int setDevice(tbvh_context* c) {
+    HIP_TRY(hipSetDevice(c->device));
+    return joinLanes(c);
+}
+hipError_t timedBegin(tbvh_context* c, hipStream_t lane) {
     if (c->skipTiming) return hipSuccess;
     const uint32_t slot = (uint32_t)(c->evSeq % tbvh_context::kTimeRing);
     for (int k = 0; k < 2; k++)
         if (!c->evRing[slot][k]) { const hipError_t e = hipEventCreate(&c->evRing[slot][k]); if (e != hipSuccess) return e; }
     c->evDone[slot] = false;
+    c->evChain[slot] = 0;
     c->ev0 = c->evRing[slot][0]; c->ev1 = c->evRing[slot][1];
     c->evSeq++;
-    return hipEventRecord(c->ev0, c->stream);
+    return hipEventRecord(c->ev0, lane ? lane : c->stream);
 }
-hipError_t timedEnd(tbvh_context* c) {
+hipError_t timedEnd(tbvh_context* c, hipStream_t lane) {
     if (c->skipTiming) return hipSuccess;
-    const hipError_t e = hipEventRecord(c->ev1, c->stream);
+    const hipError_t e = hipEventRecord(c->ev1, lane ? lane : c->stream);
     if (e == hipSuccess && c->evSeq) { c->evDone[(c->evSeq - 1) % tbvh_context::kTimeRing] = true; c->timed = true; }
     return e;
+}
+// A serial operation reports its own interval, start event to end event.  A launch that may have overlapped its neighbours (evChain: the same chain, a few
+// operations either side) reports the time it ADDED: from its start, or from the latest end of another launch of the chain that lies inside its interval,
+// to its own end.  Launches that finish one after the other in the order they were enqueued thus report end(k) - end(k - 1), a launch nothing overlapped
+// reports exactly its interval, and the figures of a loop are disjoint pieces of its wall time whatever the order the launches finished in.
+float timedMs(tbvh_context* c, uint64_t seq) {
+    constexpr uint64_t R = tbvh_context::kTimeRing;
+    const uint32_t slot = (uint32_t)(seq % R);
+    float own = -1.0f;
+    if (hipEventElapsedTime(&own, c->evRing[slot][0], c->evRing[slot][1]) != hipSuccess) { (void)hipGetLastError(); return -1.0f; }
+    const uint32_t chain = c->evChain[slot];
+    if (!chain) return own;
+    constexpr uint64_t kReach = 2 * LaneBook::kMaxInFlight;   // (launches that ran at the same time were enqueued next to each other: a launch starts after the launches before it on its lane have ended and those on the other lane have started)
+    const uint64_t oldest = c->evSeq > R ? c->evSeq - R : 0;
+    const uint64_t lo = seq > oldest + kReach ? seq - kReach : oldest, hi = seq + kReach < c->evSeq ? seq + kReach + 1 : c->evSeq;
+    float from = 0.f;   // ms after this launch's start
+    for (uint64_t j = lo; j < hi; j++) {
+        const uint32_t sj = (uint32_t)(j % R);
+        if (j == seq || c->evChain[sj] != chain || !c->evDone[sj]) continue;
+        float endJ = 0.f;
+        if (hipEventSynchronize(c->evRing[sj][1]) != hipSuccess || hipEventElapsedTime(&endJ, c->evRing[slot][0], c->evRing[sj][1]) != hipSuccess) { (void)hipGetLastError(); continue; }
+        const bool before = endJ < own || (endJ == own && j < seq);   // (equal time stamps: in the order enqueued)
+        if (before && endJ > from) from = endJ;
+    }
+    return own - from;
 }
 }  // namespace tbvh_capi
 
@@ -82,6 +122,7 @@ int tbvh_init(int device, tbvh_context** out) {
     if (const char* e = getenv("TBVH_EMBED_TRIS")) { if (atoi(e) == 0) c->embedTris = false; }
     if (const char* e = getenv("TBVH_DEBUG_FLAGS")) c->expFlags = (uint32_t)strtoul(e, nullptr, 0);   // tbvh_debug_set_flags from the environment (counter runs of tools/)
     if (const char* e = getenv("TBVH_COHERENT_TUNER")) { const int v = atoi(e); c->cohTunerMode = v == 0 ? 1 : (v == 2 ? 2 : (v == 3 ? 3 : 0)); }   // 0: off (always deferred + gated), 2: always strict, 3: always one traversal per wave
+    if (const char* e = getenv("TBVH_OVERLAP")) { if (atoi(e) == 0) c->overlap = false; }   // every launch on lane 0 (tbvh_context_set_overlap)
     if (const char* e = getenv("TBVH_POOL_PARTS")) {  // experiment knob
         const int b = atoi(e);
         if (b >= 0 && (1 << b) <= kPoolParts) c->poolParts = (uint32_t)b;   // log2 of the partition count
@@ -105,7 +146,9 @@ int tbvh_init(int device, tbvh_context** out) {
 void tbvh_shutdown(tbvh_context* c) {
     if (!c) return;
     hipSetDevice(c->device);
+    if (c->lane1.stream) hipStreamSynchronize(c->lane1.stream);
     if (c->ownStream) hipStreamSynchronize(c->ownStream);
+    c->lane1Dirty = false;
     for (;;) {   // TLASes first: they hold references to their BLASes
         tbvh_scene* t = nullptr;
         for (tbvh_scene* s : c->scenes) if (s->isTlas) { t = s; break; }
@@ -121,6 +164,8 @@ void tbvh_shutdown(tbvh_context* c) {
     c->pinned.clear();
     delete c->pipe;
     for (auto& pair : c->evRing) for (hipEvent_t ev : pair) if (ev) hipEventDestroy(ev);
+    if (c->evBase) hipEventDestroy(c->evBase);
+    if (c->lane1.stream) hipStreamDestroy(c->lane1.stream);
     if (c->ownStream) hipStreamDestroy(c->ownStream);
     delete c;   // (its device buffers go here: the device is current, its stream was idle)
 }
@@ -140,8 +185,56 @@ int tbvh_synchronize(tbvh_context* c) {
 
 int tbvh_set_stream(tbvh_context* c, void* s) {
     if (!c) return fail(TBVH_E_INVALID, "null context");
-    TBVH_LOCK(c);
+    TBVH_ENTER(c);   // (lane 1 is used on the context's own stream only: what it holds is joined into that stream before the context leaves it)
     c->stream = s ? (hipStream_t)s : c->ownStream;
+    return 0;
+}
+
+int tbvh_context_set_overlap(tbvh_context* c, int enabled) {
+    if (!c) return fail(TBVH_E_INVALID, "tbvh_context_set_overlap: null context");
+    TBVH_ENTER(c);
+    c->overlap = enabled != 0;
+    return 0;
+}
+
+// The lane rule of overlap_lanes.h driven by a script, without a device (tests/test_overlap_lanes_host.py).  The book the script works on is the type the
+// contexts keep; a launch's slot is its row number.
+int tbvh_debug_lane_script(const uint64_t* ops5, uint64_t nOps, int32_t* out) {
+    if ((!ops5 || !out) && nOps) return fail(TBVH_E_INVALID, "tbvh_debug_lane_script: null argument");
+    LaneBook book;
+    std::vector<uint8_t> done(nOps, 0);
+    bool allowLane1 = true;
+    auto prune = [&] { book.prune([&](int, uint32_t slot) { return done[slot] != 0; }); };
+    for (uint64_t i = 0; i < nOps; i++) {
+        const uint64_t* op = ops5 + i * 5;
+        out[i] = 0;
+        switch (op[0]) {
+        case 0: {
+            LaneFootprint fp;
+            fp.rays.lo = (uintptr_t)op[1]; fp.rays.hi = (uintptr_t)op[2]; fp.occ.lo = (uintptr_t)op[3]; fp.occ.hi = (uintptr_t)op[4];
+            prune();
+            const LaneChoice ch = book.decide(fp, allowLane1);
+            if (ch.join) book.joined();
+            book.add(ch.lane, fp, (uint32_t)i);
+            out[i] = ch.lane + (ch.join ? 2 : 0);
+            break;
+        }
+        case 1:
+            if (op[1] >= nOps) return fail(TBVH_E_INVALID, "tbvh_debug_lane_script: row %llu finishes a row beyond the script", (unsigned long long)i);
+            done[op[1]] = 1;
+            break;
+        case 2: allowLane1 = op[1] != 0; break;
+        case 3: prune(); out[i] = book.count[0] + 256 * book.count[1]; break;
+        default: return fail(TBVH_E_INVALID, "tbvh_debug_lane_script: row %llu has no such operation", (unsigned long long)i);
+        }
+    }
+    return 0;
+}
+
+int tbvh_debug_overlap_stats(tbvh_context* c, uint64_t out[2]) {
+    if (!c || !out) return fail(TBVH_E_INVALID, "tbvh_debug_overlap_stats: null argument");
+    TBVH_LOCK(c);
+    out[0] = c->lane1Launches; out[1] = c->laneJoins;
     return 0;
 }
 
@@ -152,6 +245,7 @@ float tbvh_time_last_ms(tbvh_context* c) {
     if (c->hostQuerySeq == c->evSeq && c->hostQueryMs >= 0.f) return c->hostQueryMs;   // a host-array query runs as several launches: their sum
     hipSetDevice(c->device);
     if (hipEventSynchronize(c->ev1) != hipSuccess) return -1.0f;
+    if (c->evSeq && c->ev1 == c->evRing[(c->evSeq - 1) % tbvh_context::kTimeRing][1]) return timedMs(c, c->evSeq - 1);   // (not so: a wavefront frame's own pair)
     float ms = -1.0f;
     if (hipEventElapsedTime(&ms, c->ev0, c->ev1) != hipSuccess) return -1.0f;
     return ms;
@@ -168,7 +262,8 @@ int tbvh_time_history(tbvh_context* c, float* ms, uint32_t cap, uint32_t* count)
         float t = -1.0f;
         if (c->evDone[slot]) {
             HIP_TRY(hipEventSynchronize(c->evRing[slot][1]));
-            HIP_TRY(hipEventElapsedTime(&t, c->evRing[slot][0], c->evRing[slot][1]));
+            t = timedMs(c, c->evSeq - n + i);
+            if (t < 0.f && !c->evChain[slot]) HIP_TRY(hipEventElapsedTime(&t, c->evRing[slot][0], c->evRing[slot][1]));   // (reports the failure)
         }
         ms[i] = t;
     }
@@ -205,8 +300,10 @@ int tbvh_debug_last_probe(tbvh_context* c, uint32_t out[3]) {
     out[0] = out[1] = out[2] = 0;
     if (!c->lastProbed) return 0;
     HIP_TRY(hipStreamSynchronize(c->stream));
-    // (the area the last launch drew from: the next launch's kernels will zero it)
-    HIP_TRY(hipMemcpy(out, (uint32_t*)c->pool + (size_t)(c->poolCur ^ 1) * ((size_t)(kPoolParts + 1) * kPoolCounterStride) + (size_t)kPoolParts * kPoolCounterStride, 8, hipMemcpyDeviceToHost));
+    // (the area the last launch drew from, on the lane it took: the next launch's kernels will zero it)
+    const uint32_t* pool = c->lastProbedLane ? c->lane1.pool.get() : c->pool.get();
+    const int last = (c->lastProbedLane ? c->lane1.poolCur : c->poolCur) ^ 1;
+    HIP_TRY(hipMemcpy(out, pool + (size_t)last * ((size_t)(kPoolParts + 1) * kPoolCounterStride) + (size_t)kPoolParts * kPoolCounterStride, 8, hipMemcpyDeviceToHost));
     out[2] = (out[1] != 0 && out[0] * 10u >= out[1] * 6u) ? 2u : 1u;   // the rule of k_cwbvh (kernels_cwbvh.hip)
     return 0;
 }

@@ -27,6 +27,7 @@
 #include "dev_buf.h"
 #include "host_builder.h"
 #include "kernels.h"
+#include "overlap_lanes.h"
 #include "ray_pool.h"
 
 using namespace tbvh;
@@ -111,6 +112,32 @@ struct tbvh_context {
     int poolCur = 0;              // the area the next launch draws from; its kernels zero the other one for the launch after (no memset in the stream)
     bool poolClean = false;       // both areas are known to be as that scheme leaves them (false: the next launch clears them itself)
     uint32_t* status = nullptr;   // (inside `counter`)
+    // ---- two launch lanes (overlap_lanes.h; capi_query.hip: launchQuery) ----------------------------------------------------------------------
+    // Lane 0 is `stream`, lane 1 a second stream of the context's own, made by the first launch that takes it.  Only the device-resident queries
+    // (tbvh_intersect_device, tbvh_intersect_device_fresh, tbvh_occluded_device) ever take lane 1, and only while the context runs on its own
+    // stream; every other entry point joins the lanes first (setDevice).  What above is per launch in flight belongs to lane 0 — `pool`, `poolCur`,
+    // `poolClean`, `spill` — and lane 1 has its own here: the counter areas' zero-the-other-one scheme and the stack spill area assume that the
+    // launches using them are serial, which holds within a lane only.
+    struct Lane1 {
+        hipStream_t stream = nullptr;
+        DevBuf<uint32_t> pool, spill;
+        int poolCur = 0;
+        bool poolClean = false;
+        bool unusable = false;      // the stream or an allocation failed: launches do not overlap on this context
+    } lane1;
+    bool overlap = true;            // TBVH_OVERLAP=0 / tbvh_context_set_overlap(ctx, 0): every launch on lane 0, as before the lanes
+    tbvh_capi::LaneBook book;       // launches in flight on each lane (a record's slot = its event pair in evRing)
+    hipEvent_t evBase = nullptr;    // lane 0's position ahead of its in-flight query launches: what a launch on lane 1 waits for (generators, uploads, refits enqueued earlier)
+    hipEvent_t lane1Last = nullptr; // end event of lane 1's most recent launch (one of evRing)
+    hipEvent_t laneStart[2] = {nullptr, nullptr};   // start event of each lane's most recent overlappable launch (of evRing): the other lane's next launch starts after it
+    bool lane1Dirty = false;        // lane 1 holds launches lane 0 has not waited for
+    bool lane0Touched = true;       // something other than an overlappable launch went onto lane 0 since evBase was recorded
+    bool lane1SawBase = false;      // lane 1 waits for evBase as recorded now
+    bool serialiseNext = false;     // the previous launch was one a CohTuner measured: this one does not overlap with it either
+    int lastProbedLane = 0;
+    uint32_t chain = 1;             // counts the joins: launches of one chain may have overlapped each other
+    uint32_t evChain[kTimeRing] = {};   // per timed operation: the chain of an overlappable launch, 0 for everything else (tbvh_time_history)
+    uint64_t lane1Launches = 0, laneJoins = 0;   // tbvh_debug_overlap_stats
     DevBuf<RayRec> stageRays;     // staging for host-array queries
     DevBuf<uint8_t> stageOcc;
     // host-array queries of more than a few 10 k rays go through pinned staging in chunks: worker threads gather the
@@ -358,11 +385,15 @@ int setDevice(tbvh_context* c);
 // first statement of an entry point once its arguments are known to be non-null: take the context's lock for the rest of the call, make its device current
 #define TBVH_LOCK(ctxptr) std::lock_guard<std::recursive_mutex> ctx_lock_((ctxptr)->mu)
 #define TBVH_ENTER(ctxptr) std::lock_guard<std::recursive_mutex> ctx_lock_((ctxptr)->mu); if (int r_ = tbvh_capi::setDevice(ctxptr)) return r_
-hipError_t timedBegin(tbvh_context* c);   // next event pair of the ring, start event recorded on the context's stream
-hipError_t timedEnd(tbvh_context* c);     // end event recorded; the operation counts as timed
-// one query launch (probe-in-kernel + traversal kernel(s)) on the context's stream; asynchronous.  nDev: batch size in device memory (wavefront queues)
+// the common entry path: the device is current and lane 0 comes after everything enqueued on lane 1 (joinLanes)
+int joinLanes(tbvh_context* c);
+hipError_t timedBegin(tbvh_context* c, hipStream_t lane = nullptr);   // next event pair of the ring, start event recorded on the context's stream (or on `lane`)
+hipError_t timedEnd(tbvh_context* c, hipStream_t lane = nullptr);     // end event recorded; the operation counts as timed
+float timedMs(tbvh_context* c, uint64_t seq);   // what timed operation `seq` (counted from 0; still in the ring, its events reached) reports: see tbvh_time_history
+// one query launch (probe-in-kernel + traversal kernel(s)) on the context's stream; asynchronous.  nDev: batch size in device memory (wavefront queues).
+// mayOverlap: the launch may take lane 1 (the three device-resident query entry points pass it; everything else stays on lane 0 behind a join)
 int launchQuery(tbvh_scene* s, tbvh::RayRec* d_rays, uint64_t n, uint8_t* d_occ, bool fresh = false, float freshTmax = 1e30f,
-                const unsigned long long* nDev = nullptr);
+                const unsigned long long* nDev = nullptr, bool mayOverlap = false);
 int checkStatus(tbvh_context* c);   // synchronizes the stream, turns the device status word into an error code
 int ensureStage(tbvh_context* c, uint64_t n);      // (capi_query.hip) the host-array staging buffers hold at least n ray records ...
 int ensureStageOcc(tbvh_context* c, uint64_t n);   // ... and n any-hit result bytes

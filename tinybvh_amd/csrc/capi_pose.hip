@@ -268,7 +268,7 @@ void tbvh_pose_free(tbvh_pose* p) {
     if (!p) return;
     tbvh_context* c = p->ctx;
     TBVH_LOCK(c);
-    hipSetDevice(c->device);
+    (void)tbvh_capi::setDevice(c);   // (joins the launch lanes)
     hipStreamSynchronize(c->stream);   // (kernels and refits in flight read the pose's buffers)
     for (size_t i = 0; i < c->poses.size(); i++)
         if (c->poses[i] == p) { c->poses.erase(c->poses.begin() + i); break; }

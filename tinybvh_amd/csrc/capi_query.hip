@@ -200,7 +200,7 @@ int hostQuery(tbvh_scene* s, const char* raysIn, char* raysOut, uint64_t n, uint
 
 
 // The two-level kernels: one per BLAS layout (and one for BVH8_CWBVH and BVH_GPU BLASes mixed), each walking the TLAS form made for it at upload.
-static void launchTlasKernels(tbvh_scene* s, QueryArgs& q, bool any, uint32_t blocks) {
+static void launchTlasKernels(tbvh_scene* s, QueryArgs& q, bool any, uint32_t blocks, hipStream_t st) {
     tbvh_context* c = s->ctx;
     const uint32_t blocks7 = (!c->gridOverride && blocks == c->blocks) ? (uint32_t)c->numCUs * 28u : blocks;   // the full grid of the kernels built for 7 waves per SIMD
     // any-hit queries may have a class of their own (capi_scene.hip: reclassifyTlas)
@@ -210,22 +210,22 @@ static void launchTlasKernels(tbvh_scene* s, QueryArgs& q, bool any, uint32_t bl
     const BlasDesc* desc = own ? s->blasDescAny : s->blasDesc;
     if (s->blasSpheres) {   // sphere BLASes, alone or with triangle BLASes walked in their own layouts: the flat loop with the sphere step (kernels_tlas.hip)
         q.spillStride = c->spillEntries / 2;   // 8-byte stack entries
-        launch_tlas_custom(any, layout, s->nodes, s->tlasIdx, s->instances, desc, q, c->status, blocks, c->stream);
+        launch_tlas_custom(any, layout, s->nodes, s->tlasIdx, s->instances, desc, q, c->status, blocks, st);
     } else if (s->tlas4 && layout == TBVH_LAYOUT_BVH4_GPU) {   // BVH4_GPU BLASes: the unified 4-wide kernel
         q.spillStride = c->spillEntries;   // 32-bit stack entries
-        launch_tlas4(any, 0, s->tlas4, s->instances, desc, q, c->status, blocks, c->stream, blocks7);
+        launch_tlas4(any, 0, s->tlas4, s->instances, desc, q, c->status, blocks, st, blocks7);
     } else if (s->tlas8 && (layout == TBVH_LAYOUT_CWBVH || mix)) {   // BVH8_CWBVH BLASes (or those and BVH_GPU ones): the unified 8-wide kernel
         q.spillStride = c->spillEntries / 2;   // 8-byte stack entries
-        launch_tlas8(any, 0, s->tlas8, s->tlas8Refs, s->instances, desc, q, c->status, blocks, c->stream, blocks7, mix);
+        launch_tlas8(any, 0, s->tlas8, s->tlas8Refs, s->instances, desc, q, c->status, blocks, st, blocks7, mix);
     } else if (layout == TBVH_LAYOUT_VOXELSET) {   // voxel sets (kernels_voxel.hip); tbvh_upload_tlas admits them only all together
         q.spillStride = c->spillEntries;   // 32-bit stack entries
-        launch_voxel(any, nullptr, s->nodes, s->tlasIdx, s->instances, desc, q, c->status, blocks, c->stream);
+        launch_voxel(any, nullptr, s->nodes, s->tlasIdx, s->instances, desc, q, c->status, blocks, st);
     } else if (layout == TBVH_LAYOUT_BVH_GPU) {   // BVH_GPU BLASes: the TLAS already has their node format (kernels_tlas2.hip)
         q.spillStride = c->spillEntries;
-        launch_tlas2(any, 0, s->nodes, s->tlasIdx, s->instances, desc, q, c->status, blocks, c->stream, blocks7);
+        launch_tlas2(any, 0, s->nodes, s->tlasIdx, s->instances, desc, q, c->status, blocks, st, blocks7);
     } else {
         q.spillStride = c->spillEntries / 2;
-        launch_tlas(any, layout, s->nodes, s->tlasIdx, s->instances, desc, q, c->status, blocks, c->stream);
+        launch_tlas(any, layout, s->nodes, s->tlasIdx, s->instances, desc, q, c->status, blocks, st);
     }
 }
 
@@ -238,6 +238,7 @@ struct CwbvhLaunch {
     uint32_t blocks;       // grid of a coherent batch (a third more waves when probed)
     uint32_t blocksBase;   // grid of an incoherent one
     uint32_t* probeWords;  // the coherence probe's counters in this launch's pool area
+    hipStream_t stream;    // the lane the launch takes
 };
 
 // One coherent-flavor kernel of a two-flavor launch, in the schedule the scene's tuner asks for; timed by the tuner's own events while it still measures.
@@ -264,17 +265,17 @@ static int launchCoherentFlavor(tbvh_scene* s, const QueryArgs& q, const CwbvhLa
     if (mode == 2) qa.flags |= 32u;
     CohTuner::Pending pe{nullptr, nullptr, mode, q.nRays};
     if (measuring && tu.pending.size() < 16) {
-        if (hipEventCreate(&pe.e0) != hipSuccess || hipEventCreate(&pe.e1) != hipSuccess || hipEventRecord(pe.e0, c->stream) != hipSuccess) {   // no sample then
+        if (hipEventCreate(&pe.e0) != hipSuccess || hipEventCreate(&pe.e1) != hipSuccess || hipEventRecord(pe.e0, L.stream) != hipSuccess) {   // no sample then
             if (pe.e0) hipEventDestroy(pe.e0);
             if (pe.e1) hipEventDestroy(pe.e1);
             pe.e0 = pe.e1 = nullptr; (void)hipGetLastError();
         }
     }
-    if (mode == 3) launch_cwbvh_packet(L.any, s->nodes, s->tris, qa, c->status, L.blocks, c->stream);   // one traversal per wave of 64 consecutive rays
-    else launch_cwbvh(L.any, 0, s->nodes, tris, qa, c->status, mode == 2 ? L.blocksBase : L.blocks, c->stream, 5, L.small, blocks7);
+    if (mode == 3) launch_cwbvh_packet(L.any, s->nodes, s->tris, qa, c->status, L.blocks, L.stream);   // one traversal per wave of 64 consecutive rays
+    else launch_cwbvh(L.any, 0, s->nodes, tris, qa, c->status, mode == 2 ? L.blocksBase : L.blocks, L.stream, 5, L.small, blocks7);
     const hipError_t le = hipGetLastError();
     if (pe.e0) {
-        if (le == hipSuccess && hipEventRecord(pe.e1, c->stream) == hipSuccess) tu.pending.push_back(pe);
+        if (le == hipSuccess && hipEventRecord(pe.e1, L.stream) == hipSuccess) tu.pending.push_back(pe);
         else { hipEventDestroy(pe.e0); hipEventDestroy(pe.e1); }
     }
     HIP_TRY(le);
@@ -295,56 +296,86 @@ static int launchCwbvhKernels(tbvh_scene* s, QueryArgs& q, const CwbvhLaunch& L)
 #endif
     const bool twoFlavors = q.probe && s->variant == 0 && ((!autoPad && s->cw.hybrid && s->cw.trisPadded) || L.probedSmall) && !(c->expFlags & 4u);
     if (s->variant == 90 && s->cw.hybrid && s->cw.trisPadded) {   // diagnostic: the incoherent flavor whatever the batch (tests, tools/ab_configs.py)
-        launch_cwbvh(L.any, 0, s->cw.hybrid, s->cw.trisPadded, q, c->status, L.blocksBase, c->stream, 13, L.small, blocks7);
+        launch_cwbvh(L.any, 0, s->cw.hybrid, s->cw.trisPadded, q, c->status, L.blocksBase, L.stream, 13, L.small, blocks7);
     } else if (s->variant == 91) {   // diagnostic: the coherent flavor (deferred triangles, gated triangle phase) whatever the batch and whatever its probe says
         QueryArgs qa = q;
         qa.probe = L.probeWords; qa.baseBlocks = 0; qa.flags |= 16u;
-        launch_cwbvh(L.any, 0, s->nodes, tris, qa, c->status, L.blocks, c->stream, 5, L.small, blocks7);
+        launch_cwbvh(L.any, 0, s->nodes, tris, qa, c->status, L.blocks, L.stream, 5, L.small, blocks7);
     } else if (s->variant == 92) {   // diagnostic: one traversal per wave of 64 consecutive rays (kernels_cwbvh_packet.hip) whatever the batch, the scene's size and the tuner
-        launch_cwbvh_packet(L.any, s->nodes, s->tris, q, c->status, L.blocks, c->stream);
+        launch_cwbvh_packet(L.any, s->nodes, s->tris, q, c->status, L.blocks, L.stream);
     } else if (twoFlavors) {
         if (int r = launchCoherentFlavor(s, q, L, tris, blocks7)) return r;
         if (L.probedSmall) {   // behind it: the scene's unprobed kernel, as launched without a probe
             QueryArgs qp = q;
             qp.probe = nullptr; qp.baseBlocks = 0;
-            launch_cwbvh(L.any, s->variant, autoPad ? s->cw.padded : s->nodes, tris, qp, c->status, L.blocks, c->stream, autoPad ? 8 : 5, L.small, blocks7);
+            launch_cwbvh(L.any, s->variant, autoPad ? s->cw.padded : s->nodes, tris, qp, c->status, L.blocks, L.stream, autoPad ? 8 : 5, L.small, blocks7);
         } else {
             // the incoherent flavor on 28 one-wave workgroups per CU when the batch fills the grid (24 is the persistent grid's size: 20 / 26 / 28 / 30 /
             // 32 per CU trace bounce rays at -4.4 / +0.6 / +0.9 / +0.5 / +0.5 %, interleaved medians of 13 rounds)
             uint32_t wX = (c->expFlags >> 8) & 0xffu;   // experiment: another number of waves per CU
             if (wX > 32u) wX = 32u;                     // (the spill area holds blocks + blocks / 3 = 32 workgroups per CU: LaneStack strides by gridDim)
             const uint32_t wB = wX ? wX : (c->gridOverride ? 0u : 28u);
-            launch_cwbvh(L.any, 0, s->cw.hybrid, s->cw.trisPadded, q, c->status, (wB && L.blocksBase == c->blocks) ? (uint32_t)c->numCUs * wB : L.blocksBase, c->stream, 13, L.small, blocks7);
+            launch_cwbvh(L.any, 0, s->cw.hybrid, s->cw.trisPadded, q, c->status, (wB && L.blocksBase == c->blocks) ? (uint32_t)c->numCUs * wB : L.blocksBase, L.stream, 13, L.small, blocks7);
         }
     } else {
-        launch_cwbvh(L.any, s->variant, autoPad ? s->cw.padded : s->nodes, tris, q, c->status, L.blocks, c->stream, autoPad ? 8 : 5, L.small, blocks7);
+        launch_cwbvh(L.any, s->variant, autoPad ? s->cw.padded : s->nodes, tris, q, c->status, L.blocks, L.stream, autoPad ? 8 : 5, L.small, blocks7);
     }
     return 0;
 }
 
-int launchQuery(tbvh_scene* s, RayRec* d_rays, uint64_t n, uint8_t* d_occ, bool fresh, float freshTmax, const unsigned long long* nDev) {
+// Lane 1 of the context with what a launch on it needs (its stream, counter areas and stack spill area), made by the first launch that would take
+// it.  false: it cannot be had (no memory): launches do not overlap on this context, which is never an error of the query.
+static bool ensureLane1(tbvh_context* c) {
+    tbvh_context::Lane1& l = c->lane1;
+    if (l.unusable) return false;
+    if (l.stream && l.pool && l.spill && c->evBase) return true;
+    const size_t poolWords = (size_t)(kPoolParts + 1) * kPoolCounterStride;
+    const size_t spillWords = (size_t)(c->blocks + c->blocks / 3u) * 64 * c->spillEntries;   // (as lane 0's: the largest grid any launch uses)
+    if ((!c->evBase && hipEventCreateWithFlags(&c->evBase, hipEventDisableTiming) != hipSuccess) ||
+        (!l.stream && hipStreamCreateWithFlags(&l.stream, hipStreamNonBlocking) != hipSuccess) ||
+        (!l.pool && l.pool.alloc(poolWords * 2) != hipSuccess) || (!l.spill && l.spill.alloc(spillWords) != hipSuccess)) {
+        (void)hipGetLastError();
+        l.pool.reset(); l.spill.reset();
+        l.unusable = true;
+        return false;
+    }
+    l.poolClean = false;
+    return true;
+}
+
+// Something the launch does before its kernels would enqueue work on lane 0 or replace arrays that launches in flight read (a derived copy made or made
+// again, a TLAS re-classified): such a launch joins the lanes first.
+static bool launchPrepares(const tbvh_scene* s, uint64_t n, bool any) {
+    if (s->isTlas) return s->blasRecopyPending || (any && !s->anyHitSeen && !s->blasSpheres);
+    if (s->copies.pending()) return true;
+    return n >= 1024u && s->variant == 0 && !s->copies.tried8 && (s->layout == TBVH_LAYOUT_BVH_GPU || s->layout == TBVH_LAYOUT_BVH4_GPU);
+}
+
+int launchQuery(tbvh_scene* s, RayRec* d_rays, uint64_t n, uint8_t* d_occ, bool fresh, float freshTmax, const unsigned long long* nDev, bool mayOverlap) {
     tbvh_context* c = s->ctx;
-    TBVH_ENTER(c);
+    TBVH_LOCK(c);
+    const bool any = d_occ != nullptr;
+    // Two lanes (overlap_lanes.h): a device-resident query whose buffers no launch in flight touches need not wait for the launches before it — the
+    // persistent grids fill every wave slot, so its workgroups start where the earlier launch's waves retire and its body hides that launch's tail.
+    // Everything else (and every launch while overlap is off, on a caller's stream, untimed or sized on the device) joins the lanes like any entry point.
+    bool lanes = mayOverlap && c->overlap && c->stream == c->ownStream && !c->skipTiming && !nDev && n != 0;
+    if (lanes && launchPrepares(s, n, any)) lanes = false;
+    if (lanes) HIP_TRY(hipSetDevice(c->device));
+    else if (int r = setDevice(c)) return r;
     if (n == 0) return 0;
     s->raysTraced += n;   // (what tbvh_refit weighs the refit of a scene's copies against)
     countQueryForRecopy(s);   // copies dropped by a tbvh_update_* come back once the blob has settled
     if (!s->isTlas && (nDev || n >= 1024u)) makeCopyOnce(s, kCopyWide8);   // first query of a BVH_GPU / BVH4_GPU scene (not part of its time)
-    if (tbvh_scene* w = wideCopyForQuery(s)) return launchQuery(w, d_rays, n, d_occ, fresh, freshTmax, nDev);   // BVH_GPU / BVH4_GPU with an 8-wide copy (capi_copies.hip)
-    const bool any = d_occ != nullptr;
+    if (tbvh_scene* w = wideCopyForQuery(s)) return launchQuery(w, d_rays, n, d_occ, fresh, freshTmax, nDev, mayOverlap);   // BVH_GPU / BVH4_GPU with an 8-wide copy (capi_copies.hip)
     if (any && s->isTlas && !s->anyHitSeen && !s->blasSpheres) {   // the first IsOccluded through this TLAS (not part of its time): its BVH4_GPU and BVH_GPU BLASes are entered through 8-wide copies by any-hit queries
         s->anyHitSeen = true;
         for (tbvh_scene* b : s->blasList) makeCopyOnce(b, kCopyWide8);   // (re-classifies the TLASes over b, this one included)
         if (int r = reclassifyTlas(s)) return r;
     }
-    // ray-fetch counters: two areas alternate; the kernels of this launch zero the other area for the next one.  After anything that went wrong
-    // between two launches (poolClean still false) both are cleared here.
     const size_t poolWords = (size_t)(kPoolParts + 1) * kPoolCounterStride;   // + the coherence-probe counters on their own line
-    if (!c->poolClean) HIP_TRY(hipMemsetAsync(c->pool, 0, poolWords * 4 * 2, c->stream));
-    c->poolClean = false;
-    uint32_t* const poolArea = (uint32_t*)c->pool + (size_t)c->poolCur * poolWords;
     QueryArgs q;
     q.rays = d_rays; q.nRays = n; q.occluded = d_occ;
-    q.spill = c->spill; q.counter = poolArea; q.counterNext = (uint32_t*)c->pool + (size_t)(c->poolCur ^ 1) * poolWords; q.poolParts = c->poolParts;
+    q.poolParts = c->poolParts;
     q.stats = c->counter + 8;
     q.fresh = fresh ? 1u : 0u; q.freshTmax = freshTmax; q.nRaysDev = nDev; q.omm = Omm{s->opmap, s->opmapN};
     q.probe = nullptr; q.baseBlocks = 0; q.hybridK = s->cw.packed; q.flags = 0u;
@@ -368,9 +399,87 @@ int launchQuery(tbvh_scene* s, RayRec* d_rays, uint64_t n, uint8_t* d_occ, bool 
     const uint32_t lo = (uint32_t)c->numCUs * 4u;
     uint32_t blocks = (uint32_t)(want < lo ? lo : (want > cap ? cap : want));
     const bool probed = !s->isTlas && !small && blobBytes <= (384ull << 20) && s->layout == TBVH_LAYOUT_CWBVH && n >= (1ull << 21) && (s->variant == 0 || s->variant == 88) && !(c->expFlags & 64u);
-    if (probed) { if (int r = prepareIncoherentCopies(s)) return r; }   // first launch of this class on the scene: the derived copies for incoherent batches (not part of the query's time)
+    if (probed && !s->cw.tried) {   // first launch of this class on the scene: the derived copies for incoherent batches (not part of the query's time)
+        if (lanes) if (int r = joinLanes(c)) return r;   // (built on lane 0)
+        if (int r = prepareIncoherentCopies(s)) return r;
+    }
     q.hybridK = s->cw.packed;
-    HIP_TRY(timedBegin(c));
+    const bool huge = !small && blobBytes > (384ull << 20);
+    const int sizeClass = (small && n < (3ull << 19)) ? 3 : n < (6ull << 20) ? 0 : n < (12ull << 20) ? 1 : 2;
+    bool probedSmall = !s->isTlas && (small || huge) && s->layout == TBVH_LAYOUT_CWBVH && s->variant == 0 && !nDev && n >= (small ? (3ull << 18) : (6ull << 20)) && !(c->expFlags & 64u) && !c->gridOverride;
+    if (probedSmall) {
+        const int m = c->cohTunerMode ? c->cohTunerMode : s->cohTuner[any ? 1 : 0][sizeClass].decided;
+        if (m == 1 || m == 2) { probedSmall = false; s->cohLastClass[any ? 1 : 0] = (uint8_t)sizeClass; }
+    }
+    // ---- the lane this launch takes -------------------------------------------------------------------------------------------------------------
+    // A launch the scene's CohTuner may time (a two-flavor launch of a class still undecided) and the launch after it run serialised: a sample taken
+    // beside another launch's tail must not decide a schedule.
+    int lane = 0;
+    if (lanes) {
+        const bool tunerMeasures = (probed || probedSmall) && !c->cohTunerMode && !s->cohTuner[any ? 1 : 0][sizeClass].decided;
+        // (lane 1 is made by the first launch that MAY overlap, also one that does not: its stack spill area is a large allocation — 10 ms on the bench's
+        // context —, which belongs to a caller's warm-up launches, serialised by the tuner or not, and not to the first launch that finds a neighbour in flight)
+        const bool haveLane1 = ensureLane1(c);
+        if (tunerMeasures || c->serialiseNext) {
+            if (int r = joinLanes(c)) return r;
+            c->serialiseNext = tunerMeasures;
+        } else {
+            c->book.prune([c](int, uint32_t slot) {
+                const hipError_t qe = hipEventQuery(c->evRing[slot][1]);
+                if (qe != hipSuccess) (void)hipGetLastError();
+                return qe != hipErrorNotReady;
+            });
+            LaneFootprint fp;
+            fp.rays.lo = (uintptr_t)d_rays; fp.rays.hi = fp.rays.lo + (uintptr_t)n * sizeof(RayRec);
+            if (any) { fp.occ.lo = (uintptr_t)d_occ; fp.occ.hi = fp.occ.lo + (uintptr_t)n; }
+            const LaneChoice ch = c->book.decide(fp, haveLane1);
+            if (ch.join) { if (int r = joinLanes(c)) return r; }
+            lane = ch.lane;
+            // What was enqueued on lane 0 before its in-flight query launches (ray generators, uploads, refits) comes before a launch on lane 1 too: evBase marks
+            // that position — NOT lane 0's end, which would put the launch behind the very launches it may overlap.
+            if (c->lane0Touched && c->evBase) {
+                HIP_TRY(hipEventRecord(c->evBase, c->stream));
+                c->lane0Touched = false; c->lane1SawBase = false;
+            }
+            if (lane == 1 && !c->lane1SawBase) {
+                HIP_TRY(hipStreamWaitEvent(c->lane1.stream, c->evBase, 0));
+                c->lane1SawBase = true;
+            }
+            // Launches START in the order they were enqueued, across the lanes too: this one waits for the start (not the end) of the other lane's latest launch.
+            // Neither lane then runs more than one launch ahead of the other: a caller's frame k is complete before frame k + 1's launches take the GPU, and the
+            // launches that ran beside a launch are its neighbours in the order enqueued (what timedMs looks at).
+            if (!c->book.idle(lane ^ 1) && c->laneStart[lane ^ 1]) HIP_TRY(hipStreamWaitEvent(lane ? c->lane1.stream : c->stream, c->laneStart[lane ^ 1], 0));
+        }
+    }
+    const hipStream_t st = lane ? c->lane1.stream : c->stream;
+    // ray-fetch counters: two areas alternate; the kernels of this launch zero the other area for the next one ON THE SAME LANE (each lane has its own
+    // pair: a launch overlapping this one would otherwise draw from the area this one is zeroing).  After anything that went wrong between two launches
+    // (poolClean still false) both are cleared here.
+    uint32_t* const pool = lane ? c->lane1.pool.get() : c->pool.get();
+    int& poolCur = lane ? c->lane1.poolCur : c->poolCur;
+    bool& poolClean = lane ? c->lane1.poolClean : c->poolClean;
+    if (!poolClean) HIP_TRY(hipMemsetAsync(pool, 0, poolWords * 4 * 2, st));
+    poolClean = false;
+    uint32_t* const poolArea = pool + (size_t)poolCur * poolWords;
+    q.spill = lane ? c->lane1.spill : c->spill; q.counter = poolArea; q.counterNext = pool + (size_t)(poolCur ^ 1) * poolWords;
+    HIP_TRY(timedBegin(c, st));
+    const uint32_t ringSlot = (uint32_t)((c->evSeq - 1) % tbvh_context::kTimeRing);   // (lanes: timing is on, the launch has its event pair)
+    // the launch's end, once its kernels are enqueued: the end event, the lane's record of it, the other counter area now zeroed by what was enqueued
+    auto finish = [&]() -> int {
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(timedEnd(c, st));
+        poolCur ^= 1; poolClean = true;
+        if (lanes) {
+            LaneFootprint fp;
+            fp.rays.lo = (uintptr_t)d_rays; fp.rays.hi = fp.rays.lo + (uintptr_t)n * sizeof(RayRec);
+            if (any) { fp.occ.lo = (uintptr_t)d_occ; fp.occ.hi = fp.occ.lo + (uintptr_t)n; }
+            c->book.add(lane, fp, ringSlot);
+            c->evChain[ringSlot] = c->chain;
+            c->laneStart[lane] = c->evRing[ringSlot][0];
+            if (lane) { c->lane1Last = c->evRing[ringSlot][1]; c->lane1Dirty = true; c->lane1Launches++; }
+        }
+        return 0;
+    };
     // BVH8_CWBVH scenes beyond the L2s (the `small` class runs dense triangle phases, where the gated schedule loses 15 %) but within reach
     // of the Infinity Cache (beyond it camera rays are bound by memory too: 30 M / 60 M triangles lose 11 / 19 % under the gate), batches of 2 M
     // rays and more: a probe of the batch's coherence (256 neighbouring ray pairs, sampled by every wave of the traversal kernel itself: kernels_cwbvh.hip)
@@ -387,62 +496,51 @@ int launchQuery(tbvh_scene* s, RayRec* d_rays, uint64_t n, uint8_t* d_occ, bool 
     // a few us slower, the batch runs as before round 6: ONE unprobed kernel.  Only the measuring launches (6-9 per class of batch size) pay.
     // ... and scenes beyond 384 MB (never probed either: the deferred schedule loses there), from 6 M rays on: the street at 12 M triangles traces 16.7 M camera
     // rays at 7094 instead of 4718 MRays/s with the packet kernel — and 4.2 M at 3383 instead of 3733, shadow rays slower throughout: measured per class likewise.
-    const bool huge = !small && blobBytes > (384ull << 20);
-    const int sizeClass = (small && n < (3ull << 19)) ? 3 : n < (6ull << 20) ? 0 : n < (12ull << 20) ? 1 : 2;
-    bool probedSmall = !s->isTlas && (small || huge) && s->layout == TBVH_LAYOUT_CWBVH && s->variant == 0 && !nDev && n >= (small ? (3ull << 18) : (6ull << 20)) && !(c->expFlags & 64u) && !c->gridOverride;
-    if (probedSmall) {
-        const int m = c->cohTunerMode ? c->cohTunerMode : s->cohTuner[any ? 1 : 0][sizeClass].decided;
-        if (m == 1 || m == 2) { probedSmall = false; s->cohLastClass[any ? 1 : 0] = (uint8_t)sizeClass; }
-    }
+    // (`huge`, `sizeClass` and `probedSmall` are worked out above, ahead of the lane choice, which needs to know whether a tuner may time this launch)
     if (probedSmall) {
         q.probe = poolArea + (size_t)kPoolParts * kPoolCounterStride; q.baseBlocks = blocks;
-        c->lastProbed = true;
+        c->lastProbed = true; c->lastProbedLane = lane;
     }
     if (probed) {
         uint32_t* probe = poolArea + (size_t)kPoolParts * kPoolCounterStride;
         q.probe = probe; q.baseBlocks = blocks;
-        c->lastProbed = true;
+        c->lastProbed = true; c->lastProbedLane = lane;
         if (!c->gridOverride && blocks == c->blocks) blocks = c->blocks + c->blocks / 3u;   // 24 -> 32 one-wave workgroups per CU
     }
     if (s->isTlas) {
-        launchTlasKernels(s, q, any, blocks);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(timedEnd(c));
-        c->poolCur ^= 1; c->poolClean = true;   // (the other counter area has been zeroed by what was just enqueued)
-        return 0;
+        launchTlasKernels(s, q, any, blocks, st);
+        return finish();
     }
     switch (s->layout) {
     case TBVH_LAYOUT_BVH_GPU:
         q.spillStride = c->spillEntries;
-        launch_bvh2(any, s->variant, s->nodes, s->tris, q, c->status, blocks, c->stream);
+        launch_bvh2(any, s->variant, s->nodes, s->tris, q, c->status, blocks, st);
         break;
     case TBVH_LAYOUT_BVH4_GPU:
         q.spillStride = c->spillEntries;
-        launch_bvh4(any, s->variant, s->nodes, q, c->status, blocks, c->stream);
+        launch_bvh4(any, s->variant, s->nodes, q, c->status, blocks, st);
         break;
     case TBVH_LAYOUT_CWBVH:
         q.spillStride = c->spillEntries / 2;  // 8-byte entries
-        if (int r = launchCwbvhKernels(s, q, CwbvhLaunch{any, small, probedSmall, sizeClass, blocks, blocksBase, poolArea + (size_t)kPoolParts * kPoolCounterStride})) return r;
+        if (int r = launchCwbvhKernels(s, q, CwbvhLaunch{any, small, probedSmall, sizeClass, blocks, blocksBase, poolArea + (size_t)kPoolParts * kPoolCounterStride, st})) return r;
         break;
     case TBVH_LAYOUT_BVH2_WALD:   // a sphere BLAS (kernels_custom.hip)
         q.spillStride = c->spillEntries / 2;  // 8-byte entries
-        launch_custom(any, s->nodes, s->tris, q, c->status, blocks, c->stream);
+        launch_custom(any, s->nodes, s->tris, q, c->status, blocks, st);
         break;
     case TBVH_LAYOUT_VOXELSET:
         q.spillStride = c->spillEntries;
-        launch_voxel(any, (const uint32_t*)s->nodes.get(), nullptr, nullptr, nullptr, nullptr, q, c->status, blocks, c->stream);
+        launch_voxel(any, (const uint32_t*)s->nodes.get(), nullptr, nullptr, nullptr, nullptr, q, c->status, blocks, st);
         break;
     default:
         return fail(TBVH_E_INVALID, "scene layout %d has no query kernel", s->layout);
     }
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(timedEnd(c));
-    c->poolCur ^= 1; c->poolClean = true;   // (the other counter area has been zeroed by what was just enqueued)
-    return 0;
+    return finish();
 }
 
 int checkStatus(tbvh_context* c) {
     uint32_t st = 0;
+    if (int r = joinLanes(c)) return r;   // (launches on lane 1 set the status word too)
     HIP_TRY(hipMemcpyAsync(&st, c->status, 4, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     if (st & 1u) {
@@ -493,21 +591,21 @@ int tbvh_intersect_device(tbvh_scene* s, void* dRays, uint64_t n) {
     TBVH_REFUSE_DOUBLE(s, "tbvh_intersect_device");
     if (!s || (!dRays && n)) return fail(TBVH_E_INVALID, "tbvh_intersect_device: null argument");
     if (((uintptr_t)dRays) & 15) return fail(TBVH_E_INVALID, "ray array must be 16-byte aligned");
-    return launchQuery(s, (RayRec*)dRays, n, nullptr);
+    return launchQuery(s, (RayRec*)dRays, n, nullptr, false, 1e30f, nullptr, true);
 }
 
 int tbvh_intersect_device_fresh(tbvh_scene* s, void* dRays, uint64_t n, float tmax) {
     TBVH_REFUSE_DOUBLE(s, "tbvh_intersect_device_fresh");
     if (!s || (!dRays && n)) return fail(TBVH_E_INVALID, "tbvh_intersect_device_fresh: null argument");
     if (((uintptr_t)dRays) & 15) return fail(TBVH_E_INVALID, "ray array must be 16-byte aligned");
-    return launchQuery(s, (RayRec*)dRays, n, nullptr, true, tmax);
+    return launchQuery(s, (RayRec*)dRays, n, nullptr, true, tmax, nullptr, true);
 }
 
 int tbvh_occluded_device(tbvh_scene* s, const void* dRays, uint64_t n, uint8_t* dOcc) {
     TBVH_REFUSE_DOUBLE(s, "tbvh_occluded_device");
     if (!s || ((!dRays || !dOcc) && n)) return fail(TBVH_E_INVALID, "tbvh_occluded_device: null argument");
     if (((uintptr_t)dRays) & 15) return fail(TBVH_E_INVALID, "ray array must be 16-byte aligned");
-    return launchQuery(s, (RayRec*)dRays, n, dOcc);
+    return launchQuery(s, (RayRec*)dRays, n, dOcc, false, 1e30f, nullptr, true);
 }
 
 int tbvh_intersect(tbvh_scene* s, void* rays, uint64_t n, uint32_t stride) {

@@ -784,7 +784,7 @@ void tbvh_free_scene(tbvh_scene* s) {
     if (!s) return;
     tbvh_context* c = s->ctx;
     TBVH_LOCK(c);
-    hipSetDevice(c->device);
+    (void)tbvh_capi::setDevice(c);   // (joins the launch lanes)
     hipStreamSynchronize(c->stream);
     if (!s->isTlas && !s->usedBy.empty()) { s->zombie = true; return; }   // a TLAS still points at this BLAS's memory: freed with the last such TLAS
     freeCopy(s, kCopyWide8);

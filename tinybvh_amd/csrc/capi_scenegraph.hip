@@ -246,7 +246,7 @@ void tbvh_scenegraph_free(tbvh_scenegraph* g) {
     if (!g) return;
     tbvh_context* c = g->ctx;
     TBVH_LOCK(c);
-    hipSetDevice(c->device);
+    (void)tbvh_capi::setDevice(c);   // (joins the launch lanes)
     hipStreamSynchronize(c->stream);   // (kernels in flight, and the TLAS rebuilds and poses fed from the outputs, read the graph's memory)
     for (size_t i = 0; i < c->graphs.size(); i++)
         if (c->graphs[i] == g) { c->graphs.erase(c->graphs.begin() + i); break; }

@@ -187,7 +187,7 @@ void tbvh_shading_free(tbvh_shading* sh) {
     if (!sh) return;
     tbvh_context* c = sh->ctx;
     TBVH_LOCK(c);
-    hipSetDevice(c->device);
+    (void)tbvh_capi::setDevice(c);   // (joins the launch lanes)
     hipStreamSynchronize(c->stream);   // (kernels in flight read the tables)
     for (size_t i = 0; i < c->shadings.size(); i++)
         if (c->shadings[i] == sh) { c->shadings.erase(c->shadings.begin() + i); break; }

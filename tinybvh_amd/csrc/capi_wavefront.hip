@@ -55,7 +55,7 @@ int tbvh_wavefront_create(tbvh_context* c, uint32_t width, uint32_t height, tbvh
 void tbvh_wavefront_destroy(tbvh_wavefront* w) {
     if (!w) return;
     TBVH_LOCK(w->ctx);
-    hipSetDevice(w->ctx->device);
+    (void)tbvh_capi::setDevice(w->ctx);   // (joins the launch lanes)
     hipStreamSynchronize(w->ctx->stream);
     if (w->ctx->ev0 == w->e0 || w->ctx->ev1 == w->e1) { w->ctx->timed = false; w->ctx->ev0 = w->ctx->ev1 = nullptr; }   // (tbvh_time_last_ms pointed at this frame)
     if (w->e0) hipEventDestroy(w->e0);
