@@ -184,6 +184,7 @@ int tbvh_build_device(tbvh_context* ctx, const void* verts16, uint64_t n_tris, i
  * hence an entry point of its own rather than the default.
  * radius: 1..32 positions to each side, 0 = the default 16.  Everything else as tbvh_build_device. */
 int tbvh_build_device_ploc(tbvh_context* ctx, const void* verts16, uint64_t n_tris, int on_device, int layout, uint32_t radius, tbvh_scene** out);
+/* (the reference's own binned-SAH tree built on the device: tbvh_build_device_sah, declared with tbvh_build_bvh2_sah_device below, after tbvh_mesh) */
 
 /* Read a BLAS scene's device blobs back (tests, caching a refitted blob): which = 0 nodes, 1 triangle
  * records (BVH_GPU: the gathered {v0|prim, e1, e2} form; BVH4_GPU has none).  dst = NULL only reports the size. */
@@ -820,8 +821,36 @@ int tbvh_host_build_mesh(const tbvh_mesh* mesh, int layout, const tbvh_build_par
  * buffer is therefore kept unread here; the first tbvh_refit_mesh through it checks every index against that call's n_verts, dereferences none that
  * is out of range and reports TBVH_E_FORMAT then — one frame late, and the buffer is the held copy until good indices are passed.) */
 int tbvh_upload_host_mesh(tbvh_context* ctx, const tbvh_hostbvh* h, const tbvh_mesh* mesh, tbvh_scene** out);   /* mesh is read for BVH_GPU; kept indices for every layout */
-/* tbvh_build_device (builder 0: LBVH, max_leaf_tris applies) / tbvh_build_device_ploc (builder 1: radius applies) over a mesh. */
+/* tbvh_build_device (builder 0: LBVH, max_leaf_tris applies) / tbvh_build_device_ploc (builder 1: radius applies) / tbvh_build_device_sah (builder 2:
+ * max_leaf_tris applies, radius is ignored) over a mesh. */
 int tbvh_build_device_mesh(tbvh_context* ctx, const tbvh_mesh* mesh, int layout, uint32_t max_leaf_tris, int builder, uint32_t radius, tbvh_scene** out);
+
+/* The reference's OWN tree on the device: BVH::Build( nodeIdx, depth ) (tiny_bvh.h:2332-2461 with PrepareBuild, 2261-2329; the binned-SAH default
+ * builder, non-threaded node numbering) reproduced node for node and byte for byte by a level-synchronous parallel builder (DESIGN.md par. 18):
+ * every quantity the builder reduces over primitives is a min, a max or an integer count, the split decision is scalar arithmetic per node
+ * (tinybvh_amd/csrc/sah_split.h, shared with the host twin below), and the in-place partition only decides the order inside a leaf.  For content
+ * whose topology changes (BVH_DYNAMIC meshes, streamed geometry): the tree the host builder gives, without the host.
+ *   output: Wald nodes (32 bytes: aabbMin, leftFirst, aabbMax, triCount) — node 0 the root, node 1 unused and zero, child pairs in the order
+ *   the reference's loop allocates them — and primIdx, in which EVERY LEAF'S PRIMITIVES ARE IN ASCENDING ORDER (the reference's order inside a
+ *   leaf is an accident of its partition; the sets are the reference's).  max_leaf_tris = 0 leaves the tree as BVH::Build does; k > 0 applies
+ *   BVH::SplitLeafs( k ) (1988-2017: the first k primitives go left, the rest right, repeated), the new nodes behind the built ones, each with
+ *   the bounds of its own primitives (the reference copies the leaf's box to both halves).
+ *   Not reproduced: the reference's printf for a large node it cannot split, and its 256-entry task stack (beyond 256 pending right children the
+ *   reference stops splitting; the builders here have no such limit).  A box face that meets both -0 and +0 may differ in that sign bit.
+ * tbvh_build_bvh2_sah_device: mesh where its on_device flag says (a flat array is a tbvh_mesh without indices); nodes32_out (cap_nodes nodes) and
+ *   prim_idx_out (cap_idx entries) in host memory (out_on_device = 0) or device memory (1) — what tbvh_convert_bvh2_device( on_device = 1 ) takes.
+ *   *n_nodes_out is always the node count; nodes32_out == NULL reports it only (2 * n_tris nodes always suffice); a capacity that is too small
+ *   returns TBVH_E_INVALID with the need in *n_nodes_out.  Null arguments / n_tris == 0: TBVH_E_INVALID; host indices are checked before anything
+ *   is allocated, device-resident ones by the kernels (TBVH_E_FORMAT, never dereferenced).  Synchronous: one small read-back per level of the upper tree (subtrees of at most 64 triangles are finished by one wave each without any);
+ *   tbvh_time_last_ms() = the device time of the build.
+ * tbvh_build_device_sah: that builder, then the device conversion (tbvh_convert_bvh2_device), nothing on the host.  layout: TBVH_LAYOUT_CWBVH
+ *   (max_leaf_tris 1..3) or TBVH_LAYOUT_BVH4_GPU (1..4); 0 = the most the layout's leaves hold (3 / 4).  Any other layout: TBVH_E_INVALID.
+ * tbvh_host_build_bvh2_sah: the CPU twin over the same header, sequential; same output contract, host memory only. */
+int tbvh_build_bvh2_sah_device(tbvh_context* ctx, const tbvh_mesh* mesh, uint32_t max_leaf_tris, void* nodes32_out, uint64_t cap_nodes,
+                               uint32_t* prim_idx_out, uint64_t cap_idx, int out_on_device, uint64_t* n_nodes_out);
+int tbvh_build_device_sah(tbvh_context* ctx, const void* verts16, uint64_t n_tris, int on_device, int layout, uint32_t max_leaf_tris, tbvh_scene** out);
+int tbvh_host_build_bvh2_sah(const tbvh_mesh* mesh, uint32_t max_leaf_tris, void* nodes32_out, uint64_t cap_nodes, uint32_t* prim_idx_out,
+                             uint64_t cap_idx, uint64_t* n_nodes_out);
 /* BVH4_GPU / BVH8_CWBVH::ConvertFrom of a BVH built over indices (tiny_bvh.h:5165-5168, 5993-5996): tbvh_convert_bvh2_device with the leaf writers
  * fetching through the mesh.  on_device says where nodes32 / prim_idx are; the mesh carries its own flag. */
 int tbvh_convert_bvh2_device_mesh(tbvh_context* ctx, const void* nodes32, uint64_t n_nodes, const uint32_t* prim_idx, uint64_t n_idx,

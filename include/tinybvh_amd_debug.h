@@ -64,6 +64,11 @@ int tbvh_debug_wide_copy_bvh2(int layout, const void* blob, uint64_t n_blob, con
                               uint32_t max_leaf_tris, void* nodes32_out, uint64_t cap_nodes, uint64_t* n_nodes_out, void* recs_out, uint64_t cap_recs,
                               uint64_t* n_recs_out);
 
+/* The device SAH builder (tbvh_build_bvh2_sah_device, tbvh_build_device_sah) finishes subtrees of at most n primitives by one wave each, out of LDS,
+ * instead of by its per-level kernels.  n = 0: the per-level path alone; n >= the triangle count: one wave builds the whole tree.  The tree does not
+ * depend on n (tests force both paths); the build time does.  A new context starts at 64 (profiles/sah_device_build.txt). */
+int tbvh_debug_set_sah_small_subtree(tbvh_context* ctx, uint32_t n);
+
 /* Device memory the library itself owns right now, over every context of this process: out[0] = live allocations, out[1] = their bytes.  Scenes (their
  * derived copies, staging and scratch areas included), contexts and wavefront objects are counted; memory handed to the caller (tbvh_device_malloc,
  * tbvh_pinned_malloc) and the library's pinned host buffers are not.  Both return to their earlier values once everything created since was freed:

@@ -215,6 +215,15 @@ class Context:
         check(lib.tbvh_generate_shadow_device(self._h, C.c_void_p(d_in), C.c_void_p(d_out), n, l, float(eps)), "tbvh_generate_shadow_device")
 
 
+_DEVICE_BUILDERS = {"lbvh": 0, "ploc": 1, "sah": 2}   # tbvh_build_device_mesh's builder argument
+
+
+def _device_builder(builder: str) -> int:
+    if builder not in _DEVICE_BUILDERS:
+        raise ValueError(f"BuildOnDevice: builder {builder!r} (one of {', '.join(sorted(_DEVICE_BUILDERS))})")
+    return _DEVICE_BUILDERS[builder]
+
+
 def device_mesh(d_verts: int, n_verts: int, n_tris: int, d_indices: int = 0, stride_bytes: int = 16) -> Mesh:
     """A tbvh_mesh whose vertices (and indices, if any) are device memory: pass it wherever `verts` is taken together with indices=."""
     return Mesh(C.c_void_p(int(d_verts)), int(n_verts), int(stride_bytes), 1, C.c_void_p(int(d_indices)) if d_indices else None, int(n_tris))
@@ -253,6 +262,28 @@ def _mesh(verts, indices=None):
         n_tris = v.shape[0] // 3
     m = Mesh(C.c_void_p(v.ctypes.data), v.shape[0], v.strides[0], 0, None if idx is None else C.c_void_p(idx.ctypes.data), n_tris)
     return m, (v, idx)
+
+
+def host_build_bvh2_sah(verts, indices=None, max_leaf_tris: int = 0):
+    """The reference's binned-SAH tree (BVH::Build, non-threaded numbering) by the library's sequential CPU twin (tbvh_host_build_bvh2_sah):
+    (nodes32 (n, 8) uint32, prim_idx (n_tris,) uint32), every leaf's primitives ascending; max_leaf_tris > 0 = BVH::SplitLeafs afterwards."""
+    m, keep = _mesh(verts, indices)
+    nodes = np.zeros((max(2 * int(m.n_tris), 2), 8), np.uint32)
+    idx = np.zeros(int(m.n_tris), np.uint32)
+    n = C.c_uint64(0)
+    check(lib.tbvh_host_build_bvh2_sah(C.byref(m), int(max_leaf_tris), _ptr(nodes), nodes.shape[0], _ptr(idx), idx.size, C.byref(n)), "tbvh_host_build_bvh2_sah")
+    return nodes[:n.value].copy(), idx
+
+
+def build_bvh2_sah(ctx, verts, indices=None, max_leaf_tris: int = 0):
+    """The same tree built on the device (tbvh_build_bvh2_sah_device) and read back: byte for byte what host_build_bvh2_sah gives."""
+    m, keep = _mesh(verts, indices)
+    nodes = np.zeros((max(2 * int(m.n_tris), 2), 8), np.uint32)
+    idx = np.zeros(int(m.n_tris), np.uint32)
+    n = C.c_uint64(0)
+    check(lib.tbvh_build_bvh2_sah_device(ctx._h, C.byref(m), int(max_leaf_tris), _ptr(nodes), nodes.shape[0], _ptr(idx), idx.size, 0, C.byref(n)),
+          "tbvh_build_bvh2_sah_device")
+    return nodes[:n.value].copy(), idx
 
 
 class HostBVH:
@@ -370,7 +401,7 @@ class _Scene:
 
     def _build_device_mesh(self, layout: int, verts, indices, max_leaf_tris: int, builder: str, radius: int) -> "_Scene":
         m, keep = _mesh(verts, indices)
-        check(lib.tbvh_build_device_mesh(self.ctx._h, C.byref(m), layout, max_leaf_tris if builder != "ploc" else 0, 1 if builder == "ploc" else 0, radius,
+        check(lib.tbvh_build_device_mesh(self.ctx._h, C.byref(m), layout, max_leaf_tris if builder != "ploc" else 0, _device_builder(builder), radius,
                                          C.byref(self._h)), "tbvh_build_device_mesh")
         self._mesh_tris = int(m.n_tris)
         return self
@@ -573,12 +604,16 @@ class BVH4_GPU(_SphereQueries, _Scene):
         return self.Upload(self.host.blob(0, np.uint32, 4))
 
     def BuildOnDevice(self, verts: np.ndarray, max_leaf_tris: int = 4, builder: str = "lbvh", radius: int = 0, indices=None) -> "BVH4_GPU":
-        """LBVH (tbvh_build_device) or PLOC (tbvh_build_device_ploc) build + 4-wide collapse + encode on the GPU (mesh forms: tbvh_build_device_mesh)."""
+        """LBVH (tbvh_build_device), PLOC (tbvh_build_device_ploc) or, with builder="sah", the reference's binned-SAH tree (tbvh_build_device_sah)
+        + 4-wide collapse + encode on the GPU (mesh forms: tbvh_build_device_mesh)."""
+        _device_builder(builder)
         if _is_mesh(verts, indices):
             return self._build_device_mesh(LAYOUT_BVH4_GPU, verts, indices, max_leaf_tris, builder, radius)
         verts = np.ascontiguousarray(verts, np.float32)
         if builder == "ploc":
             check(lib.tbvh_build_device_ploc(self.ctx._h, _ptr(verts), verts.shape[0] // 3, 0, LAYOUT_BVH4_GPU, radius, C.byref(self._h)), "tbvh_build_device_ploc")
+        elif builder == "sah":
+            check(lib.tbvh_build_device_sah(self.ctx._h, _ptr(verts), verts.shape[0] // 3, 0, LAYOUT_BVH4_GPU, max_leaf_tris, C.byref(self._h)), "tbvh_build_device_sah")
         else:
             check(lib.tbvh_build_device(self.ctx._h, _ptr(verts), verts.shape[0] // 3, 0, LAYOUT_BVH4_GPU, max_leaf_tris, C.byref(self._h)), "tbvh_build_device")
         return self
@@ -615,13 +650,16 @@ class BVH8_CWBVH(_SphereQueries, _Scene):
         return self.Upload(self.host.blob(0, np.uint32, 4), self.host.blob(1, np.uint32, 4))
 
     def BuildOnDevice(self, verts: np.ndarray, max_leaf_tris: int = 0, builder: str = "lbvh", radius: int = 0, indices=None) -> "BVH8_CWBVH":
-        """LBVH (tbvh_build_device) or PLOC (tbvh_build_device_ploc) build + wide collapse + encode on the GPU; nothing is built on the host
-        (mesh forms: tbvh_build_device_mesh)."""
+        """LBVH (tbvh_build_device), PLOC (tbvh_build_device_ploc) or, with builder="sah", the reference's binned-SAH tree (tbvh_build_device_sah)
+        + wide collapse + encode on the GPU; nothing is built on the host (mesh forms: tbvh_build_device_mesh)."""
+        _device_builder(builder)
         if _is_mesh(verts, indices):
             return self._build_device_mesh(LAYOUT_CWBVH, verts, indices, max_leaf_tris, builder, radius)
         verts = np.ascontiguousarray(verts, np.float32)
         if builder == "ploc":
             check(lib.tbvh_build_device_ploc(self.ctx._h, _ptr(verts), verts.shape[0] // 3, 0, LAYOUT_CWBVH, radius, C.byref(self._h)), "tbvh_build_device_ploc")
+        elif builder == "sah":
+            check(lib.tbvh_build_device_sah(self.ctx._h, _ptr(verts), verts.shape[0] // 3, 0, LAYOUT_CWBVH, max_leaf_tris, C.byref(self._h)), "tbvh_build_device_sah")
         else:
             check(lib.tbvh_build_device(self.ctx._h, _ptr(verts), verts.shape[0] // 3, 0, LAYOUT_CWBVH, max_leaf_tris, C.byref(self._h)), "tbvh_build_device")
         return self

@@ -93,6 +93,9 @@ SYMBOLS = {
     "tbvh_scene_download": (_i, [_vp, _i, _vp, _u64, _vp]),
     "tbvh_build_device": (_i, [_vp, _vp, _u64, _i, _i, _u32, _vp]),
     "tbvh_build_device_ploc": (_i, [_vp, _vp, _u64, _i, _i, _u32, _vp]),
+    "tbvh_build_device_sah": (_i, [_vp, _vp, _u64, _i, _i, _u32, _vp]),
+    "tbvh_build_bvh2_sah_device": (_i, [_vp, C.POINTER(Mesh), _u32, _vp, _u64, _vp, _u64, _i, C.POINTER(_u64)]),
+    "tbvh_host_build_bvh2_sah": (_i, [C.POINTER(Mesh), _u32, _vp, _u64, _vp, _u64, C.POINTER(_u64)]),
     "tbvh_convert_bvh2_device": (_i, [_vp, _vp, _u64, _vp, _u64, _vp, _u64, _i, _i, _vp]),
     "tbvh_tlas_download": (_i, [_vp, _vp, _u64, _vp, _u64, _vp, _u64, _vp]),
     "tbvh_free_scene": (None, [_vp]),
@@ -127,6 +130,7 @@ SYMBOLS = {
     "tbvh_debug_stats": (_i, [_vp, _vp, _i]),
     "tbvh_debug_last_probe": (_i, [_vp, _vp]),
     "tbvh_debug_set_flags": (_i, [_vp, _u32]),
+    "tbvh_debug_set_sah_small_subtree": (_i, [_vp, _u32]),
     "tbvh_debug_device_allocations": (_i, [C.POINTER(_u64)]),
     "tbvh_cwbvh_set_hybrid": (_i, [_vp, C.c_int64]),
     "tbvh_bin_rays_device": (_i, [_vp, _vp, _vp, _u64, C.POINTER(C.c_float), _u32, _u32, _vp]),

@@ -152,6 +152,7 @@ struct tbvh_context {
     uint64_t hostQuerySeq = ~0ull; // ... valid while no later operation was timed (evSeq still equals this)
     std::vector<PinnedRange> pinned;
     DevBuf<void> binScratch;      // tbvh_bin_rays_device
+    uint32_t sahSmallSubtree = 64;   // (sahbuild.h: kSahSmallSubtreeDefault) tbvh_debug_set_sah_small_subtree
     std::vector<tbvh_scene*> scenes;
     std::vector<struct tbvh_pose*> poses;   // (capi_pose.hip) the poses made on this context: tbvh_shutdown frees those the caller has not
     std::vector<struct tbvh_scenegraph*> graphs;   // (capi_scenegraph.hip) likewise the scene graphs

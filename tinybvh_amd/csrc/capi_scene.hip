@@ -1,6 +1,7 @@
 // capi_scene.hip — scenes: uploads and their validation, in-place updates, device conversion / build / refit, TLAS upload, classification and rebuild,
 // opacity maps, schedule hints.  The copies the library derives from a scene are capi_copies.hip's: this file reaches them through capi_internal.h's functions.
 #include "capi_internal.h"
+#include "sahbuild.h"
 
 using namespace tbvh;
 using namespace tbvh_capi;
@@ -520,7 +521,8 @@ int tbvh_convert_bvh2_device_mesh(tbvh_context* c, const void* nodes32, uint64_t
 }
 
 namespace {
-// builder: 0 = LBVH (maxLeafTris applies), 1 = PLOC (one triangle per leaf; radius = search window to each side)
+// builder: 0 = LBVH (maxLeafTris applies), 1 = PLOC (one triangle per leaf; radius = search window to each side), 2 = the reference's binned-SAH
+// tree (kernels_sahbuild.hip; maxLeafTris = SplitLeafs)
 int buildDeviceImpl(const char* who, tbvh_context* c, const tbvh_mesh& mesh, int layout, uint32_t maxLeafTris, int builder, uint32_t radius, tbvh_scene** out) {
     const uint64_t nTris = mesh.n_tris;
     if (!c || !mesh.verts || !out || nTris == 0) return fail(TBVH_E_INVALID, "%s: null/empty argument", who);
@@ -533,9 +535,18 @@ int buildDeviceImpl(const char* who, tbvh_context* c, const tbvh_mesh& mesh, int
     DeviceMesh dm;
     if (int r = stageMesh(c, mesh, dm)) return r;
     size_t sortTemp = 0, scanTemp = 0;
-    const size_t scratchBytes = builder == 1 ? ploc_scratch_bytes((uint32_t)nTris, &sortTemp, &scanTemp) : lbvh_scratch_bytes((uint32_t)nTris, &sortTemp);
+    const size_t scratchBytes = builder == 2 ? sah_scratch_bytes((uint32_t)nTris, &sortTemp, &scanTemp)
+                              : builder == 1 ? ploc_scratch_bytes((uint32_t)nTris, &sortTemp, &scanTemp) : lbvh_scratch_bytes((uint32_t)nTris, &sortTemp);
     HIP_TRY(n2.alloc(nTris * 4)); HIP_TRY(idx.alloc(nTris)); HIP_TRY(scratch.alloc(scratchBytes));
     HIP_TRY(timedBegin(c));
+    if (builder == 2) {
+        uint32_t nNodes = 0;
+        HIP_TRY(run_sah_build(dm.src, (uint32_t)nTris, maxLeafTris, c->sahSmallSubtree, n2, idx, scratch, sortTemp, scanTemp, c->status, c->stream, &nNodes));
+        scratch.reset();
+        int r = convertDeviceImpl(c, layout, n2, nNodes, idx, nTris, dm.src, out);
+        HIP_TRY(timedEnd(c));
+        return keepIndicesOrFree(who, r, dm.src, out);
+    }
     if (builder == 1) HIP_TRY(launch_ploc_build(dm.src, (uint32_t)nTris, radius, n2, idx, scratch, sortTemp, scanTemp, c->stream, nullptr));
     else HIP_TRY(launch_lbvh_build(dm.src, (uint32_t)nTris, maxLeafTris, n2, idx, scratch, sortTemp, c->stream));
     int r = convertDeviceImpl(c, layout, n2, nTris * 2, idx, nTris, dm.src, out);
@@ -560,6 +571,20 @@ int tbvh_build_device(tbvh_context* c, const void* verts16, uint64_t nTris, int 
     return buildDeviceImpl("tbvh_build_device", c, flatMesh(verts16, nTris, onDevice), layout, maxLeafTris, 0, 0, out);
 }
 
+// SAH leaf size: 0 = what the layout's leaves hold; false: more than that
+static bool sahLeafTris(const char* who, int layout, uint32_t& maxLeafTris) {
+    const uint32_t leafCap = layout == TBVH_LAYOUT_CWBVH ? 3u : 4u;
+    if (maxLeafTris == 0) maxLeafTris = leafCap;
+    if (maxLeafTris > leafCap) { fail(TBVH_E_INVALID, "%s: at most %u triangles per leaf for this layout", who, leafCap); return false; }
+    return true;
+}
+
+int tbvh_build_device_sah(tbvh_context* c, const void* verts16, uint64_t nTris, int onDevice, int layout, uint32_t maxLeafTris, tbvh_scene** out) {
+    if (layout != TBVH_LAYOUT_CWBVH && layout != TBVH_LAYOUT_BVH4_GPU) return fail(TBVH_E_INVALID, "tbvh_build_device_sah: target layout %d not supported (BVH8_CWBVH and BVH4_GPU are)", layout);
+    if (!sahLeafTris("tbvh_build_device_sah", layout, maxLeafTris)) return TBVH_E_INVALID;
+    return buildDeviceImpl("tbvh_build_device_sah", c, flatMesh(verts16, nTris, onDevice), layout, maxLeafTris, 2, 0, out);
+}
+
 int tbvh_build_device_ploc(tbvh_context* c, const void* verts16, uint64_t nTris, int onDevice, int layout, uint32_t radius, tbvh_scene** out) {
     if (radius == 0) radius = 16;
     if (radius > 32u) return fail(TBVH_E_INVALID, "tbvh_build_device_ploc: search radius %u (1..32; 0 = the default 16)", radius);
@@ -574,7 +599,10 @@ int tbvh_build_device_mesh(tbvh_context* c, const tbvh_mesh* mesh, int layout, u
         if (radius == 0) radius = 16;
         if (radius > 32u) return fail(TBVH_E_INVALID, "tbvh_build_device_mesh: search radius %u (1..32; 0 = the default 16)", radius);
         maxLeafTris = 1;
-    } else return fail(TBVH_E_INVALID, "tbvh_build_device_mesh: builder %d (0 = LBVH, 1 = PLOC)", builder);
+    } else if (builder == 2) {
+        if (layout != TBVH_LAYOUT_CWBVH && layout != TBVH_LAYOUT_BVH4_GPU) return fail(TBVH_E_INVALID, "tbvh_build_device_mesh: target layout %d not supported (BVH8_CWBVH and BVH4_GPU are)", layout);
+        if (!sahLeafTris("tbvh_build_device_mesh", layout, maxLeafTris)) return TBVH_E_INVALID;
+    } else return fail(TBVH_E_INVALID, "tbvh_build_device_mesh: builder %d (0 = LBVH, 1 = PLOC, 2 = binned SAH)", builder);
     return buildDeviceImpl("tbvh_build_device_mesh", c, *mesh, layout, maxLeafTris, builder, radius, out);
 }
 
