@@ -48,6 +48,15 @@ int tbvh_debug_overlap_stats(tbvh_context* ctx, uint64_t out[2]);
  * is available (a != 0) or not.  3 = out[row] = launches in flight on lane 0 + 256 x those on lane 1, after pruning.  Other rows leave out[row] = 0. */
 int tbvh_debug_lane_script(const uint64_t* ops5, uint64_t n_ops, int32_t* out);
 
+/* The wave-packet kernel's child filter (tinybvh_amd/csrc/packet_cull.h) beside its exact per-lane test, for ONE 64-ray chunk against n_nodes BVH8_CWBVH nodes
+ * (80 bytes each), on the host as k_cwbvh_packet runs them; no device, no context.  rays64: 64 ray records of 64 bytes (O, D, rD, hit; O and rD are read);
+ * have_mask: bit l = lane l holds a ray (at least one); tcull64: each lane's cull distance as the kernel forms it (cull_bound(hit.t), -1 for a ray that is out
+ * of the game).  Per node: maybe_out = the children the wave's interval test lets through (every non-empty child where the filter is off), exact_out = the
+ * children some lane's ray enters by the exact test.  exact is a subset of maybe, always; neither has a bit in an empty slot.  chunk_flags (may be NULL):
+ * bit 0 = the lanes differ in octant, bit 1 = a ray with a non-finite origin or reciprocal direction — either turns the filter off for the chunk. */
+int tbvh_debug_packet_cull(const void* nodes80, uint64_t n_nodes, const void* rays64, uint64_t have_mask, const float* tcull64, uint8_t* maybe_out,
+                           uint8_t* exact_out, uint32_t* chunk_flags);
+
 /* Diagnostic kernel variants of BVH8_CWBVH scenes (0 = default): 72 / 52 force the strict / the coherent schedule whatever
  * the probe says, 90 the incoherent flavor on the copies of tbvh_cwbvh_set_hybrid, 75 / 88 split the last rays whatever the batch size, 59 / 61 / 73 / 78 / 82 / 83 are the instrumented
  * kernels behind tbvh_debug_stats.  Returns TBVH_E_INVALID for anything else. */

@@ -78,6 +78,7 @@ SYMBOLS = {
     "tbvh_context_set_overlap": (_i, [_vp, _i]),
     "tbvh_debug_overlap_stats": (_i, [_vp, _vp]),
     "tbvh_debug_lane_script": (_i, [_vp, _u64, _vp]),
+    "tbvh_debug_packet_cull": (_i, [_vp, _u64, _vp, _u64, _vp, _vp, _vp, _vp]),
     "tbvh_set_timing": (_i, [_vp, _i]),
     "tbvh_upload_bvh_gpu": (_i, [_vp, _vp, _u64, _vp, _u64, _vp, _u64, _pp]),
     "tbvh_upload_bvh4_gpu": (_i, [_vp, _vp, _u64, _pp]),

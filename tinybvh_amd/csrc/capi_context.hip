@@ -1,5 +1,6 @@
 // capi_context.hip — contexts, streams, timing, debug knobs, device buffers and the ceilings bench.py measures (include/tinybvh_amd.h).
 #include "capi_internal.h"
+#include "packet_cull.h"
 
 using namespace tbvh;
 using namespace tbvh_capi;
@@ -227,6 +228,77 @@ int tbvh_debug_lane_script(const uint64_t* ops5, uint64_t nOps, int32_t* out) {
         case 3: prune(); out[i] = book.count[0] + 256 * book.count[1]; break;
         default: return fail(TBVH_E_INVALID, "tbvh_debug_lane_script: row %llu has no such operation", (unsigned long long)i);
         }
+    }
+    return 0;
+}
+
+// The packet kernel's child filter (packet_cull.h) and its exact per-lane test, both as k_cwbvh_packet runs them for one 64-ray chunk, on the host
+// (tests/test_packet_cull_host.py): the same functions, the same order of planes, the same rules for when the filter is off.
+int tbvh_debug_packet_cull(const void* nodes80, uint64_t nNodes, const void* rays64, uint64_t haveMask, const float* tcull64, uint8_t* maybeOut, uint8_t* exactOut,
+                           uint32_t* chunkFlags) {
+    if (!rays64 || !tcull64 || haveMask == 0 || (nNodes && (!nodes80 || !maybeOut || !exactOut)))
+        return fail(TBVH_E_INVALID, "tbvh_debug_packet_cull: null argument or no lane holds a ray");
+    using namespace tbvh;
+    float O[64][3], rD[64][3];
+    uint32_t oct[64];
+    for (int l = 0; l < 64; l++) {
+        const float* r = (const float*)((const uint8_t*)rays64 + 64 * l);
+        for (int a = 0; a < 3; a++) { O[l][a] = r[a]; rD[l][a] = r[8 + a]; }
+        oct[l] = 7u - ((rD[l][0] < 0 ? 4u : 0u) | (rD[l][1] < 0 ? 2u : 0u) | (rD[l][2] < 0 ? 1u : 0u));
+    }
+    const int first = __builtin_ctzll(haveMask);
+    const uint32_t oct0 = oct[first];
+    const bool neg0[3] = {((7u - oct0) & 4u) != 0, ((7u - oct0) & 2u) != 0, ((7u - oct0) & 1u) != 0};
+    bool mixed = false, raysFinite = true;
+    float Olo[3], Ohi[3], rlo[3], rhi[3], TC = -1.0f;
+    for (int a = 0; a < 3; a++) { Olo[a] = Ohi[a] = O[first][a]; rlo[a] = rhi[a] = rD[first][a]; }
+    for (int l = 0; l < 64; l++) {
+        if (!((haveMask >> l) & 1u)) continue;
+        mixed |= oct[l] != oct0;
+        for (int a = 0; a < 3; a++) {
+            raysFinite &= pkc_finite(O[l][a]) && pkc_finite(rD[l][a]);
+            Olo[a] = __builtin_fminf(Olo[a], O[l][a]); Ohi[a] = __builtin_fmaxf(Ohi[a], O[l][a]);
+            rlo[a] = __builtin_fminf(rlo[a], rD[l][a]); rhi[a] = __builtin_fmaxf(rhi[a], rD[l][a]);
+        }
+        TC = __builtin_fmaxf(TC, pk_cull_tc(tcull64[l]));
+    }
+    const bool useCull = !mixed && raysFinite;
+    if (chunkFlags) *chunkFlags = (mixed ? 1u : 0u) | (raysFinite ? 0u : 2u);
+    for (uint64_t n = 0; n < nNodes; n++) {
+        const uint8_t* node = (const uint8_t*)nodes80 + 80 * n;
+        float n0[3];
+        uint32_t ew;
+        memcpy(n0, node, 12); memcpy(&ew, node + 12, 4);
+        const int e[3] = {(int)(int8_t)ew, (int)(int8_t)(ew >> 8), (int)(int8_t)(ew >> 16)};
+        const uint8_t* meta = node + 24;
+        const uint8_t* qbytes = node + 32;
+        float planes[8][6], bounds[8][6];
+        bool allFinite = true;
+        for (uint32_t L = 0; L < 48; L++) {     // what lane L of the wave does
+            const uint32_t p = L >> 3, axis = p % 3u, isHi = p / 3u, dstPlane = axis + 3u * (isHi ^ (neg0[axis] ? 1u : 0u));
+            const float qf = (float)qbytes[L];
+            planes[L & 7u][dstPlane] = qf;
+            bool fin;
+            bounds[L & 7u][dstPlane] = pk_cull_plane(dstPlane >= 3u, qf, n0[axis], e[axis], Olo[axis], Ohi[axis], rlo[axis], rhi[axis], fin);
+            allFinite &= fin;
+        }
+        float ax[64][3], ox[64][3];                  // each lane's ldexpf(rD, e) and (n0 - O) * rD, as the kernel forms them
+        for (int l = 0; l < 64; l++)
+            for (int a = 0; a < 3; a++) { ax[l][a] = ldexpf(rD[l][a], e[a]); ox[l][a] = (n0[a] - O[l][a]) * rD[l][a]; }
+        uint32_t maybe = 0, exact = 0;
+        for (uint32_t c = 0; c < 8; c++) {
+            if (meta[c] == 0) continue;
+            const float* b = bounds[c];
+            if (!useCull || pk_cull_pass(b[0], b[1], b[2], b[3], b[4], b[5], TC, allFinite)) maybe |= 1u << c;
+            const float* q = planes[c];
+            for (int l = 0; l < 64 && !((exact >> c) & 1u); l++) {
+                if (!((haveMask >> l) & 1u)) continue;
+                const bool in = mixed ? pk_child_exact<true>(q[0], q[1], q[2], q[3], q[4], q[5], ax[l][0], ax[l][1], ax[l][2], ox[l][0], ox[l][1], ox[l][2], tcull64[l])
+                                      : pk_child_exact<false>(q[0], q[1], q[2], q[3], q[4], q[5], ax[l][0], ax[l][1], ax[l][2], ox[l][0], ox[l][1], ox[l][2], tcull64[l]);
+                if (in) exact |= 1u << c;
+            }
+        }
+        maybeOut[n] = (uint8_t)maybe; exactOut[n] = (uint8_t)exact;
     }
     return 0;
 }

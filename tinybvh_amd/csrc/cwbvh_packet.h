@@ -3,6 +3,7 @@
 #pragma once
 #include "device_common.h"
 #include "cwbvh_node.h"
+#include "packet_cull.h"
 
 namespace tbvh {
 
@@ -21,14 +22,23 @@ __device__ __forceinline__ uint32_t sgpr(uint32_t v) { return (uint32_t)__builti
 // instructions per ray before this form), so what a slot's bits look like in the hit mask (`placed`: its unary triangle bits at its offset, or bit
 // 24 + (slot ^ octant) for an interior child) is worked out by LANES 0..7 in a handful of vector instructions and read back per slot, instead of eight
 // times a dozen scalar ones; a lane whose ray is out of the game carries tcull = -1 and needs no mask of its own.
-template <bool MIXED>
-__device__ __forceinline__ uint32_t pk_test_children(const float (*planes)[8], float ax, float ay, float az, float ox, float oy, float oz, float tcull,
-                                                     uint32_t m0, uint32_t m1, uint32_t oct0) {
+// (Compaction "has nothing to save" is about EMPTY slots.  Children no ray of the wave enters are another matter — four out of five of a camera wave's: the
+// interval filter of packet_cull.h rejects most of them for the wave at once, and pk_test_survivors below runs the per-lane test for the rest.)
+struct PkMeta { uint32_t placedL, nonEmpty; };
+__device__ __forceinline__ PkMeta pk_meta(uint32_t m0, uint32_t m1, uint32_t oct0) {
     const uint32_t lane = threadIdx.x;
     const uint32_t metaL = ((lane & 4u) ? m1 : m0) >> (8u * (lane & 3u)) & 255u;          // lane c (< 8): slot c's meta byte
     const bool innerL = (metaL & 0x18u) == 0x18u;
-    const uint32_t placedL = (metaL >> 5) << ((innerL ? (metaL ^ oct0) : metaL) & 31u);
-    const uint32_t nonEmpty = (uint32_t)wave_ballot(lane < 8u && metaL != 0u);
+    PkMeta m;
+    m.placedL = (metaL >> 5) << ((innerL ? (metaL ^ oct0) : metaL) & 31u);
+    m.nonEmpty = (uint32_t)wave_ballot(metaL != 0u) & 0xFFu;   // (lanes 8..63 repeat lanes 0..7: a mask of the ballot, not of the predicate)
+    return m;
+}
+
+// every child of `todo` (a wave-uniform mask of slots), all eight slots unrolled
+template <bool MIXED>
+__device__ __forceinline__ uint32_t pk_test_children_of(const float (*planes)[8], float ax, float ay, float az, float ox, float oy, float oz, float tcull,
+                                                        uint32_t placedL, uint32_t todo) {
     uint32_t hitmask = 0;
     float4 pa = *(const float4*)&planes[0][0];
     float2 pb = *(const float2*)&planes[0][4];
@@ -36,21 +46,47 @@ __device__ __forceinline__ uint32_t pk_test_children(const float (*planes)[8], f
     for (int c = 0; c < 8; c++) {
         const float4 qa = pa; const float2 qb = pb;
         if (c < 7) { pa = *(const float4*)&planes[c + 1][0]; pb = *(const float2*)&planes[c + 1][4]; }
-        if (!((nonEmpty >> c) & 1u)) continue;
-        // (the six FMAs as three v_pk_fma_f32 — the planes do arrive in register pairs — measured 6 % SLOWER on camera rays, same records: profiles/r06_packet_counters.txt)
-        float tnx = __builtin_fmaf(qa.x, ax, ox), tny = __builtin_fmaf(qa.y, ay, oy), tnz = __builtin_fmaf(qa.z, az, oz);
-        float tfx = __builtin_fmaf(qa.w, ax, ox), tfy = __builtin_fmaf(qb.x, ay, oy), tfz = __builtin_fmaf(qb.y, az, oz);
-        if (MIXED) {
-            const float a0 = __builtin_fminf(tnx, tfx), a1 = __builtin_fmaxf(tnx, tfx), b0 = __builtin_fminf(tny, tfy), b1 = __builtin_fmaxf(tny, tfy);
-            const float c0 = __builtin_fminf(tnz, tfz), c1 = __builtin_fmaxf(tnz, tfz);
-            tnx = a0; tfx = a1; tny = b0; tfy = b1; tnz = c0; tfz = c1;
-        }
-        const float cmin = __builtin_fmaxf(cw_fmax3(tnx, tny, tnz), 0.0f);
-        const float cmax = __builtin_fminf(cw_fmin3(tfx, tfy, tfz), tcull);
+        if (!((todo >> c) & 1u)) continue;
         const uint32_t placed = (uint32_t)__builtin_amdgcn_readlane((int)placedL, c);
-        hitmask |= wave_ballot(cmin <= cmax) != 0ull ? placed : 0u;
+        hitmask |= wave_ballot(pk_child_exact<MIXED>(qa.x, qa.y, qa.z, qa.w, qb.x, qb.y, ax, ay, az, ox, oy, oz, tcull)) != 0ull ? placed : 0u;
     }
     return hitmask;
+}
+
+template <bool MIXED>
+__device__ __forceinline__ uint32_t pk_test_children(const float (*planes)[8], float ax, float ay, float az, float ox, float oy, float oz, float tcull,
+                                                     uint32_t m0, uint32_t m1, uint32_t oct0) {
+    const PkMeta m = pk_meta(m0, m1, oct0);
+    return pk_test_children_of<MIXED>(planes, ax, ay, az, ox, oy, oz, tcull, m.placedL, m.nonEmpty);
+}
+
+// The few children the wave's filter left (`todo`: 1.4 of a camera wave's 7.6 on average, often none), one after the other: nothing is read from LDS and
+// no branch is taken for a slot that is not in the mask.  Wave-octant order only (a mixed chunk does not use the filter).
+__device__ __forceinline__ uint32_t pk_test_survivors(const float (*planes)[8], float ax, float ay, float az, float ox, float oy, float oz, float tcull,
+                                                      uint32_t placedL, uint32_t todo) {
+    uint32_t hitmask = 0;
+    while (todo != 0u) {
+        const uint32_t c = (uint32_t)__builtin_ctz(todo);
+        todo &= todo - 1u;
+        const float4 qa = *(const float4*)&planes[c][0];
+        const float2 qb = *(const float2*)&planes[c][4];
+        const uint32_t placed = (uint32_t)__builtin_amdgcn_readlane((int)placedL, (int)c);
+        hitmask |= wave_ballot(pk_child_exact<false>(qa.x, qa.y, qa.z, qa.w, qb.x, qb.y, ax, ay, az, ox, oy, oz, tcull)) != 0ull ? placed : 0u;
+    }
+    return hitmask;
+}
+
+// Wave-wide max / min of a float, the same value returned to every lane (wave-uniform).  All 64 lanes must be active.  Four rotations within each row of 16
+// lanes (DPP row_ror 1, 2, 4, 8: afterwards every lane holds its row's result), then the four rows through v_readlane.  fmaxf / fminf: a NaN is dropped.
+template <bool MAX>
+__device__ __forceinline__ float pk_wave_reduce(float v) {
+#define TBVH_PK_ROR(n) { const float o_ = __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x120 + (n), 0xF, 0xF, false)); \
+                         v = MAX ? __builtin_fmaxf(v, o_) : __builtin_fminf(v, o_); }
+    TBVH_PK_ROR(1) TBVH_PK_ROR(2) TBVH_PK_ROR(4) TBVH_PK_ROR(8)
+#undef TBVH_PK_ROR
+    const float r0 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 0)), r1 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 16));
+    const float r2 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 32)), r3 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 48));
+    return MAX ? __builtin_fmaxf(__builtin_fmaxf(r0, r1), __builtin_fmaxf(r2, r3)) : __builtin_fminf(__builtin_fminf(r0, r1), __builtin_fminf(r2, r3));
 }
 
 }  // namespace tbvh

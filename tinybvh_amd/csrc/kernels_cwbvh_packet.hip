@@ -10,6 +10,12 @@
 //     child on ITS ray, and the wave descends into a child when ANY lane's ray enters its box (culled per lane against that lane's own closest hit,
 //     with the cull slack of device_common.h);
 //   * the triangles of a leaf any lane entered are tested by all lanes, the record fetched once through the scalar cache.
+//   * (closest-hit kernel) before the per-lane child tests, the wave's FILTER (packet_cull.h): the 48 lanes that decode the planes also bound them over the box of
+//     the wave's origins and the box of its reciprocal directions (taken once per chunk), lanes 0..7 combine a child's six bounds, and one ballot names the
+//     children some ray MAY enter.  Four children out of five of a camera wave are entered by no ray, and the filter rejects 95 % of those; only the others
+//     (1.4 per node on average, often none: then not even ax..oz are formed) get the exact per-lane test, one after the other (pk_test_survivors).  The filter is
+//     conservative as computed, so the wave visits exactly the nodes and triangles it did without it.  Camera launch of the bench: 5 406 -> 4 407 vector and 662 -> 273
+//     LDS instructions per 64-ray chunk, 6 % faster inside the bench step and 11 % on its own (profiles/r08_packet_cull.txt).  The any-hit kernel runs no filter.
 // A ray therefore meets a SUPERSET of the nodes and triangles it would meet alone; with the library's tie rule (hit_wins: the result does not depend
 // on the order or the number of candidates tested) its record is the same bytes.  Work per wave: the UNION of its rays' visits — 38 node visits and
 // 12 triangle tests per 64 camera rays of the bench scene where one ray alone makes 26 and 4 (CPU count, tools/packet_union.py) — at about half the
@@ -31,7 +37,8 @@ constexpr int WG = 64;
 
 template <bool ANYHIT, bool HAS_OMM>
 __global__ __launch_bounds__(WG, 8) void k_cwbvh_packet(const float4* __restrict__ nodes, const float4* __restrict__ tris, QueryArgs q, uint32_t* __restrict__ status) {
-    __shared__ float planes[8][8];      // the current node's child boxes as floats: [child][near x, near y, near z, far x, far y, far z, -, -] in units of 2^e from the node's origin
+    __shared__ float planes[16][8];     // rows 0..7: the current node's child boxes as floats: [child][near x, near y, near z, far x, far y, far z, -, -] in units of 2^e from the node's
+                                        // origin; rows 8..15: the wave's bounds on the same planes (packet_cull.h: TN_lb of the near planes, TF_ub of the far ones)
     const uint64_t nRaysTotal = q.nRaysDev ? *q.nRaysDev : q.nRays;
     RayPool<64> pool;
     pool.init(q.poolParts, q.counterNext);
@@ -75,6 +82,31 @@ __global__ __launch_bounds__(WG, 8) void k_cwbvh_packet(const float4* __restrict
         const bool negA = axis == 0 ? negX0 : axis == 1 ? negY0 : negZ0;
         const uint32_t dstPlane = axis + 3u * (isHi ^ (negA ? 1u : 0u));
         float* const myPlane = &planes[lane & 7u][lane < 48u ? dstPlane : 6u + ((lane >> 3) & 1u)];   // (columns 6, 7 of a row are spare)
+
+        // ---- the wave's filter (packet_cull.h): the boxes of its rays' origins and reciprocal directions, on the axis of this lane's plane ---------------
+        // Not for a mixed chunk (the exact test sorts near / far per lane there), nor for one with a non-finite origin or reciprocal direction (a NaN falls out
+        // of a min / max here AND out of the exact test's, where it stands for "no bound on this axis").  Lanes without a ray take the first ray's values.
+        // Not in the any-hit kernel either: shadow rays leave from scattered hit points, the wave's origin box is wide, most children pass, and the filter
+        // then costs more than it saves (16.7 M shadow rays of the bench scene 6 ... 10 % slower with it: profiles/r08_packet_cull.txt).
+        const bool farL = dstPlane >= 3u;
+        const bool rayFinite = pkc_finite(O.x) && pkc_finite(O.y) && pkc_finite(O.z) && pkc_finite(rD.x) && pkc_finite(rD.y) && pkc_finite(rD.z);
+        const bool useCull = !ANYHIT && !mixed && wave_ballot(have && !rayFinite) == 0ull;
+        float cOlo = 0, cOhi = 0, crlo = 0, crhi = 0, TC = 0;
+        auto refreshTC = [&]() {   // the wave maximum of the cull distances of the rays in the game
+            TC = as_f32(sgpr(as_u32(pk_wave_reduce<true>(pk_cull_tc(on ? cull_bound(hit.x) : -1.0f)))));
+        };
+        if (useCull) {
+            auto first_or = [&](float v) { return have ? v : __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), (int)first)); };
+            const float3 Of = make_float3(first_or(O.x), first_or(O.y), first_or(O.z)), rf = make_float3(first_or(rD.x), first_or(rD.y), first_or(rD.z));
+            // (each box over ALL lanes, then this lane keeps its axis': the reductions are wave-wide, the axis differs between lanes)
+            const float oxl = pk_wave_reduce<false>(Of.x), oyl = pk_wave_reduce<false>(Of.y), ozl = pk_wave_reduce<false>(Of.z);
+            const float oxh = pk_wave_reduce<true>(Of.x), oyh = pk_wave_reduce<true>(Of.y), ozh = pk_wave_reduce<true>(Of.z);
+            const float rxl = pk_wave_reduce<false>(rf.x), ryl = pk_wave_reduce<false>(rf.y), rzl = pk_wave_reduce<false>(rf.z);
+            const float rxh = pk_wave_reduce<true>(rf.x), ryh = pk_wave_reduce<true>(rf.y), rzh = pk_wave_reduce<true>(rf.z);
+            cOlo = axis == 0 ? oxl : axis == 1 ? oyl : ozl; cOhi = axis == 0 ? oxh : axis == 1 ? oyh : ozh;
+            crlo = axis == 0 ? rxl : axis == 1 ? ryl : rzl; crhi = axis == 0 ? rxh : axis == 1 ? ryh : rzh;
+            refreshTC();
+        }
 
         uint32_t sp = 0;
         uint32_t ngx = 0, ngy = 0x80000000u;
@@ -120,17 +152,37 @@ __global__ __launch_bounds__(WG, 8) void k_cwbvh_packet(const float4* __restrict
         if (more) fetch(ci);
         while (more) {
             // ---- the node: decoded once for the wave ---------------------------------------------------------------------
-            __builtin_amdgcn_wave_barrier();               // (every lane has read the previous node's planes before they are overwritten)
-            *myPlane = (float)qb;
-            __builtin_amdgcn_wave_barrier();
+            __builtin_amdgcn_wave_barrier();               // (every lane has read the previous node's planes and bounds before they are overwritten)
+            const float qf = (float)qb;
+            *myPlane = qf;
             const uint32_t ew = sgpr(as_u32(n0.w));
-            const float ax = ldexpf(rD.x, (int)(int8_t)(ew)), ay = ldexpf(rD.y, (int)(int8_t)(ew >> 8)), az = ldexpf(rD.z, (int)(int8_t)(ew >> 16));
-            const float ox = (n0.x - O.x) * rD.x, oy = (n0.y - O.y) * rD.y, oz = (n0.z - O.z) * rD.z;
-            const bool lives = ANYHIT ? (on && !found) : on;
-            const float tcull = lives ? cull_bound(hit.x) : -1.0f;   // (a lane without a live ray enters no box: entry distances are clamped to >= 0)
             const uint32_t m0 = sgpr(as_u32(n1.z)), m1 = sgpr(as_u32(n1.w));
-            const uint32_t hitmask = mixed ? pk_test_children<true>(planes, ax, ay, az, ox, oy, oz, tcull, m0, m1, oct0)
-                                           : pk_test_children<false>(planes, ax, ay, az, ox, oy, oz, tcull, m0, m1, oct0);
+            const PkMeta meta = pk_meta(m0, m1, oct0);
+            uint32_t todo = meta.nonEmpty;
+            if (useCull) {
+                // the wave's filter (packet_cull.h): lane L bounds ITS plane over the wave's origin and reciprocal-direction boxes, lanes 0..7 combine the six
+                // bounds of a child, one ballot says which children some ray of the wave MAY enter; only those get the per-lane test below
+                bool fin;
+                const float n0a = axis == 0 ? n0.x : axis == 1 ? n0.y : n0.z;
+                const float bound = pk_cull_plane(farL, qf, n0a, (int)(int8_t)(ew >> (8u * axis)), cOlo, cOhi, crlo, crhi, fin);
+                myPlane[64] = bound;                       // (the second tile: rows 8..15)
+                const bool allFinite = (wave_ballot(!fin) & 0x0000FFFFFFFFFFFFull) == 0ull;   // (lanes 48..63 hold no plane)
+                __builtin_amdgcn_wave_barrier();
+                const float4 ba = *(const float4*)&planes[8u + (lane & 7u)][0];
+                const float2 bb = *(const float2*)&planes[8u + (lane & 7u)][4];
+                const uint32_t passMask = (uint32_t)wave_ballot(pk_cull_pass(ba.x, ba.y, ba.z, ba.w, bb.x, bb.y, TC, true));
+                if (allFinite) todo &= passMask;             // (pk_cull_pass's "every child passes", taken for the wave)
+            } else __builtin_amdgcn_wave_barrier();
+            uint32_t hitmask = 0;
+            if (todo != 0u) {
+                const float ax = ldexpf(rD.x, (int)(int8_t)(ew)), ay = ldexpf(rD.y, (int)(int8_t)(ew >> 8)), az = ldexpf(rD.z, (int)(int8_t)(ew >> 16));
+                const float ox = (n0.x - O.x) * rD.x, oy = (n0.y - O.y) * rD.y, oz = (n0.z - O.z) * rD.z;
+                const bool lives = ANYHIT ? (on && !found) : on;
+                const float tcull = lives ? cull_bound(hit.x) : -1.0f;   // (a lane without a live ray enters no box: entry distances are clamped to >= 0)
+                if (mixed) hitmask = pk_test_children_of<true>(planes, ax, ay, az, ox, oy, oz, tcull, meta.placedL, todo);
+                else if (!useCull) hitmask = pk_test_children_of<false>(planes, ax, ay, az, ox, oy, oz, tcull, meta.placedL, todo);
+                else hitmask = pk_test_survivors(planes, ax, ay, az, ox, oy, oz, tcull, meta.placedL, todo);
+            }
             ngx = sgpr(as_u32(n1.x));
             ngy = (hitmask & 0xFF000000u) | (ew >> 24);
             uint32_t tgy = hitmask & 0x00FFFFFFu;
@@ -140,6 +192,8 @@ __global__ __launch_bounds__(WG, 8) void k_cwbvh_packet(const float4* __restrict
             more = pick(ci);
             if (more) fetch(ci);
             // ---- the triangles of the leaves any ray entered: every lane tests them -----------------------------------------
+            bool changed = false;
+            const bool hadTris = tgy != 0u;
             while (tgy != 0u) {
                 const uint32_t ti = 31u - (uint32_t)__builtin_clz(tgy);
                 tgy &= ~(1u << ti);
@@ -150,9 +204,11 @@ __global__ __launch_bounds__(WG, 8) void k_cwbvh_packet(const float4* __restrict
                     tri_test(O, D, xyz(v0), xyz(e1), xyz(e2), hit.x, h, HAS_OMM ? q.omm : Omm{nullptr, 0}, as_u32(v0.w)) &&
                     (ANYHIT || hit_wins(h.t, as_u32(v0.w), found, hit))) {
                     found = true;
+                    changed = true;
                     if (!ANYHIT) hit = make_float4(h.t, h.u, h.v, v0.w);
                 }
             }
+            if (useCull && hadTris && wave_ballot(changed) != 0ull) refreshTC();   // (a stale TC is only conservative: hits come closer, occluded rays leave)
             if (ANYHIT && wave_ballot(on && !found) == 0ull) break;   // every ray of the wave is occluded
         }
         // ---- results ----------------------------------------------------------------------------------------------------------
