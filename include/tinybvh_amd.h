@@ -851,6 +851,40 @@ int tbvh_build_bvh2_sah_device(tbvh_context* ctx, const tbvh_mesh* mesh, uint32_
 int tbvh_build_device_sah(tbvh_context* ctx, const void* verts16, uint64_t n_tris, int on_device, int layout, uint32_t max_leaf_tris, tbvh_scene** out);
 int tbvh_host_build_bvh2_sah(const tbvh_mesh* mesh, uint32_t max_leaf_tris, void* nodes32_out, uint64_t cap_nodes, uint32_t* prim_idx_out,
                              uint64_t cap_idx, uint64_t* n_nodes_out);
+
+/* The reference's SBVH on the device: BVH::BuildHQ (tiny_bvh.h:2623-3040: the spatial-split builder every GPU layout of the reference's demos is
+ * built with), reproduced node for node and byte for byte (DESIGN.md par. 19) by the method of the builder above: one header for the arithmetic
+ * (tinybvh_amd/csrc/sbvh_split.h, shared with the host twin), order-free reductions, the reference build's FMA contractions written out.
+ *   output: what BuildHQ leaves after its final Compact(): Wald nodes — node 0 the root, node 1 unused and zero, child pairs in the pre-order of the
+ *   interior nodes — and prim_idx = the references the leaves hold, consecutive from 0 in that walk's leaf order and, unlike above, IN THE REFERENCE'S
+ *   OWN ORDER inside a leaf; a triangle a spatial split has cut is named by several leaves.  *n_idx_out = the references (the sum of the leaves'
+ *   counts), at most n_tris + n_tris / 2; 3 * n_tris nodes always suffice.  With max_leaf_tris = 0 nodes and prim_idx are the reference's bytes
+ *   (threaded or not: Compact makes its numbering canonical; of the reference's primIdx only that used prefix is defined).  k > 0: every leaf of
+ *   more than k references becomes a chain of pairs behind the built nodes, in the leaf's order, every new node with the bounds of its triangles
+ *   INTERSECTED with the leaf's box (a leaf a spatial split has clipped must not grow back).
+ *   Not reproduced: the reference's "spatial split failed" path (2967-2975), which reads index entries that may be stale: a node whose partition left one side empty becomes a leaf
+ *   over its fragments in partition order with refreshed bounds and is counted in n_failed_partitions — byte equality is not promised for a tree
+ *   where that is not 0 (it is 0 on every scene tried); the 512-entry localTask stack and Compact's 128-entry stack (no depth limit here);
+ *   hqbvhoddeven and bin counts other than 8.  A box face that meets both -0 and +0 may differ in that sign bit.
+ * tbvh_sbvh_stats: what the builder did (the host twin and the device builder count the same): references, nodes split spatially, straddlers that
+ *   went left / right whole (unsplitting), straddlers cut in two, cuts that left one half empty, cuts of a fragment that had been clipped before,
+ *   spatial candidates refused only because the node's slice had no room for them, and the path above.
+ * tbvh_build_bvh2_sbvh_device: arguments, count-only calls (nodes32_out == NULL), capacity errors (TBVH_E_INVALID with the needs in *n_nodes_out
+ *   and *n_idx_out), index validation, tbvh_time_last_ms() and error codes as tbvh_build_bvh2_sah_device.  One small read-back per level of the tree.
+ * tbvh_build_device_sbvh / _mesh: that builder, then the device conversion with n_idx = *n_idx_out; layouts and max_leaf_tris as
+ *   tbvh_build_device_sah.  The scene refits and updates exactly as an uploaded BuildHQ blob does.
+ * tbvh_host_build_bvh2_sbvh: the CPU twin over the same header, sequential; same output contract, host memory only. */
+typedef struct tbvh_sbvh_stats {
+    uint64_t n_refs, n_spatial_splits, n_unsplit_left, n_unsplit_right, n_fragment_splits, n_one_sided_splits, n_clipped_reclips, n_budget_refusals,
+             n_failed_partitions;
+} tbvh_sbvh_stats;
+int tbvh_build_bvh2_sbvh_device(tbvh_context* ctx, const tbvh_mesh* mesh, uint32_t max_leaf_tris, void* nodes32_out, uint64_t cap_nodes,
+                                uint32_t* prim_idx_out, uint64_t cap_idx, int out_on_device, uint64_t* n_nodes_out, uint64_t* n_idx_out,
+                                tbvh_sbvh_stats* stats /* may be NULL */);
+int tbvh_host_build_bvh2_sbvh(const tbvh_mesh* mesh, uint32_t max_leaf_tris, void* nodes32_out, uint64_t cap_nodes, uint32_t* prim_idx_out,
+                              uint64_t cap_idx, uint64_t* n_nodes_out, uint64_t* n_idx_out, tbvh_sbvh_stats* stats /* may be NULL */);
+int tbvh_build_device_sbvh(tbvh_context* ctx, const void* verts16, uint64_t n_tris, int on_device, int layout, uint32_t max_leaf_tris, tbvh_scene** out);
+int tbvh_build_device_sbvh_mesh(tbvh_context* ctx, const tbvh_mesh* mesh, int layout, uint32_t max_leaf_tris, tbvh_scene** out);
 /* BVH4_GPU / BVH8_CWBVH::ConvertFrom of a BVH built over indices (tiny_bvh.h:5165-5168, 5993-5996): tbvh_convert_bvh2_device with the leaf writers
  * fetching through the mesh.  on_device says where nodes32 / prim_idx are; the mesh carries its own flag. */
 int tbvh_convert_bvh2_device_mesh(tbvh_context* ctx, const void* nodes32, uint64_t n_nodes, const uint32_t* prim_idx, uint64_t n_idx,

@@ -216,11 +216,15 @@ class Context:
 
 
 _DEVICE_BUILDERS = {"lbvh": 0, "ploc": 1, "sah": 2}   # tbvh_build_device_mesh's builder argument
+_SBVH = "sbvh"                                        # the reference's BuildHQ tree: entry points of its own (tbvh_build_device_sbvh, _mesh)
 
 
-def _device_builder(builder: str) -> int:
+def _device_builder(builder: str):
+    """validates the name; the code tbvh_build_device_mesh takes for it (None for the SBVH, which that entry point does not build)"""
+    if builder == _SBVH:
+        return None
     if builder not in _DEVICE_BUILDERS:
-        raise ValueError(f"BuildOnDevice: builder {builder!r} (one of {', '.join(sorted(_DEVICE_BUILDERS))})")
+        raise ValueError(f"BuildOnDevice: builder {builder!r} (one of {', '.join(sorted(list(_DEVICE_BUILDERS) + [_SBVH]))})")
     return _DEVICE_BUILDERS[builder]
 
 
@@ -284,6 +288,38 @@ def build_bvh2_sah(ctx, verts, indices=None, max_leaf_tris: int = 0):
     check(lib.tbvh_build_bvh2_sah_device(ctx._h, C.byref(m), int(max_leaf_tris), _ptr(nodes), nodes.shape[0], _ptr(idx), idx.size, 0, C.byref(n)),
           "tbvh_build_bvh2_sah_device")
     return nodes[:n.value].copy(), idx
+
+
+SBVH_STATS = ("n_refs", "n_spatial_splits", "n_unsplit_left", "n_unsplit_right", "n_fragment_splits", "n_one_sided_splits", "n_clipped_reclips",
+              "n_budget_refusals", "n_failed_partitions")   # tbvh_sbvh_stats, field for field
+
+
+def _sbvh_result(nodes, idx, n, m, st, stats):
+    out = (nodes[:n.value].copy(), idx[:m.value].copy())
+    return out + (dict(zip(SBVH_STATS, (int(x) for x in st))),) if stats else out
+
+
+def host_build_bvh2_sbvh(verts, indices=None, max_leaf_tris: int = 0, stats: bool = False):
+    """The reference's SBVH (BVH::BuildHQ after its Compact) by the library's sequential CPU twin (tbvh_host_build_bvh2_sbvh): (nodes32 (n, 8) uint32,
+    prim_idx uint32: the references the leaves hold, in the reference's order), and with stats=True a dict of tbvh_sbvh_stats as a third item."""
+    m, keep = _mesh(verts, indices)
+    nodes = np.zeros((3 * int(m.n_tris) + 2, 8), np.uint32)
+    idx = np.zeros(int(m.n_tris) + int(m.n_tris) // 2 + 1, np.uint32)
+    n, k, st = C.c_uint64(0), C.c_uint64(0), (C.c_uint64 * len(SBVH_STATS))()
+    check(lib.tbvh_host_build_bvh2_sbvh(C.byref(m), int(max_leaf_tris), _ptr(nodes), nodes.shape[0], _ptr(idx), idx.size, C.byref(n), C.byref(k), st),
+          "tbvh_host_build_bvh2_sbvh")
+    return _sbvh_result(nodes, idx, n, k, st, stats)
+
+
+def build_bvh2_sbvh(ctx, verts, indices=None, max_leaf_tris: int = 0, stats: bool = False):
+    """The same tree built on the device (tbvh_build_bvh2_sbvh_device) and read back: byte for byte what host_build_bvh2_sbvh gives."""
+    m, keep = _mesh(verts, indices)
+    nodes = np.zeros((3 * int(m.n_tris) + 2, 8), np.uint32)
+    idx = np.zeros(int(m.n_tris) + int(m.n_tris) // 2 + 1, np.uint32)
+    n, k, st = C.c_uint64(0), C.c_uint64(0), (C.c_uint64 * len(SBVH_STATS))()
+    check(lib.tbvh_build_bvh2_sbvh_device(ctx._h, C.byref(m), int(max_leaf_tris), _ptr(nodes), nodes.shape[0], _ptr(idx), idx.size, 0, C.byref(n), C.byref(k), st),
+          "tbvh_build_bvh2_sbvh_device")
+    return _sbvh_result(nodes, idx, n, k, st, stats)
 
 
 class HostBVH:
@@ -401,6 +437,10 @@ class _Scene:
 
     def _build_device_mesh(self, layout: int, verts, indices, max_leaf_tris: int, builder: str, radius: int) -> "_Scene":
         m, keep = _mesh(verts, indices)
+        if builder == _SBVH:
+            check(lib.tbvh_build_device_sbvh_mesh(self.ctx._h, C.byref(m), layout, max_leaf_tris, C.byref(self._h)), "tbvh_build_device_sbvh_mesh")
+            self._mesh_tris = int(m.n_tris)
+            return self
         check(lib.tbvh_build_device_mesh(self.ctx._h, C.byref(m), layout, max_leaf_tris if builder != "ploc" else 0, _device_builder(builder), radius,
                                          C.byref(self._h)), "tbvh_build_device_mesh")
         self._mesh_tris = int(m.n_tris)
@@ -604,8 +644,8 @@ class BVH4_GPU(_SphereQueries, _Scene):
         return self.Upload(self.host.blob(0, np.uint32, 4))
 
     def BuildOnDevice(self, verts: np.ndarray, max_leaf_tris: int = 4, builder: str = "lbvh", radius: int = 0, indices=None) -> "BVH4_GPU":
-        """LBVH (tbvh_build_device), PLOC (tbvh_build_device_ploc) or, with builder="sah", the reference's binned-SAH tree (tbvh_build_device_sah)
-        + 4-wide collapse + encode on the GPU (mesh forms: tbvh_build_device_mesh)."""
+        """LBVH (tbvh_build_device), PLOC (tbvh_build_device_ploc) or, with builder="sah", the reference's binned-SAH tree (tbvh_build_device_sah), or with
+        builder="sbvh" its spatial-split tree (BVH::BuildHQ: tbvh_build_device_sbvh) + 4-wide collapse + encode on the GPU (mesh forms: tbvh_build_device_mesh)."""
         _device_builder(builder)
         if _is_mesh(verts, indices):
             return self._build_device_mesh(LAYOUT_BVH4_GPU, verts, indices, max_leaf_tris, builder, radius)
@@ -614,6 +654,8 @@ class BVH4_GPU(_SphereQueries, _Scene):
             check(lib.tbvh_build_device_ploc(self.ctx._h, _ptr(verts), verts.shape[0] // 3, 0, LAYOUT_BVH4_GPU, radius, C.byref(self._h)), "tbvh_build_device_ploc")
         elif builder == "sah":
             check(lib.tbvh_build_device_sah(self.ctx._h, _ptr(verts), verts.shape[0] // 3, 0, LAYOUT_BVH4_GPU, max_leaf_tris, C.byref(self._h)), "tbvh_build_device_sah")
+        elif builder == _SBVH:
+            check(lib.tbvh_build_device_sbvh(self.ctx._h, _ptr(verts), verts.shape[0] // 3, 0, LAYOUT_BVH4_GPU, max_leaf_tris, C.byref(self._h)), "tbvh_build_device_sbvh")
         else:
             check(lib.tbvh_build_device(self.ctx._h, _ptr(verts), verts.shape[0] // 3, 0, LAYOUT_BVH4_GPU, max_leaf_tris, C.byref(self._h)), "tbvh_build_device")
         return self
@@ -650,8 +692,8 @@ class BVH8_CWBVH(_SphereQueries, _Scene):
         return self.Upload(self.host.blob(0, np.uint32, 4), self.host.blob(1, np.uint32, 4))
 
     def BuildOnDevice(self, verts: np.ndarray, max_leaf_tris: int = 0, builder: str = "lbvh", radius: int = 0, indices=None) -> "BVH8_CWBVH":
-        """LBVH (tbvh_build_device), PLOC (tbvh_build_device_ploc) or, with builder="sah", the reference's binned-SAH tree (tbvh_build_device_sah)
-        + wide collapse + encode on the GPU; nothing is built on the host (mesh forms: tbvh_build_device_mesh)."""
+        """LBVH (tbvh_build_device), PLOC (tbvh_build_device_ploc) or, with builder="sah", the reference's binned-SAH tree (tbvh_build_device_sah), or with
+        builder="sbvh" its spatial-split tree (BVH::BuildHQ: tbvh_build_device_sbvh) + wide collapse + encode on the GPU; nothing is built on the host (mesh forms: tbvh_build_device_mesh)."""
         _device_builder(builder)
         if _is_mesh(verts, indices):
             return self._build_device_mesh(LAYOUT_CWBVH, verts, indices, max_leaf_tris, builder, radius)
@@ -660,6 +702,8 @@ class BVH8_CWBVH(_SphereQueries, _Scene):
             check(lib.tbvh_build_device_ploc(self.ctx._h, _ptr(verts), verts.shape[0] // 3, 0, LAYOUT_CWBVH, radius, C.byref(self._h)), "tbvh_build_device_ploc")
         elif builder == "sah":
             check(lib.tbvh_build_device_sah(self.ctx._h, _ptr(verts), verts.shape[0] // 3, 0, LAYOUT_CWBVH, max_leaf_tris, C.byref(self._h)), "tbvh_build_device_sah")
+        elif builder == _SBVH:
+            check(lib.tbvh_build_device_sbvh(self.ctx._h, _ptr(verts), verts.shape[0] // 3, 0, LAYOUT_CWBVH, max_leaf_tris, C.byref(self._h)), "tbvh_build_device_sbvh")
         else:
             check(lib.tbvh_build_device(self.ctx._h, _ptr(verts), verts.shape[0] // 3, 0, LAYOUT_CWBVH, max_leaf_tris, C.byref(self._h)), "tbvh_build_device")
         return self

@@ -97,6 +97,10 @@ SYMBOLS = {
     "tbvh_build_device_sah": (_i, [_vp, _vp, _u64, _i, _i, _u32, _vp]),
     "tbvh_build_bvh2_sah_device": (_i, [_vp, C.POINTER(Mesh), _u32, _vp, _u64, _vp, _u64, _i, C.POINTER(_u64)]),
     "tbvh_host_build_bvh2_sah": (_i, [C.POINTER(Mesh), _u32, _vp, _u64, _vp, _u64, C.POINTER(_u64)]),
+    "tbvh_build_bvh2_sbvh_device": (_i, [_vp, C.POINTER(Mesh), _u32, _vp, _u64, _vp, _u64, _i, C.POINTER(_u64), C.POINTER(_u64), _vp]),
+    "tbvh_host_build_bvh2_sbvh": (_i, [C.POINTER(Mesh), _u32, _vp, _u64, _vp, _u64, C.POINTER(_u64), C.POINTER(_u64), _vp]),
+    "tbvh_build_device_sbvh": (_i, [_vp, _vp, _u64, _i, _i, _u32, _vp]),
+    "tbvh_build_device_sbvh_mesh": (_i, [_vp, C.POINTER(Mesh), _i, _u32, _vp]),
     "tbvh_convert_bvh2_device": (_i, [_vp, _vp, _u64, _vp, _u64, _vp, _u64, _i, _i, _vp]),
     "tbvh_tlas_download": (_i, [_vp, _vp, _u64, _vp, _u64, _vp, _u64, _vp]),
     "tbvh_free_scene": (None, [_vp]),
