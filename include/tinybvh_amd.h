@@ -331,7 +331,11 @@ float tbvh_time_last_ms(tbvh_context* ctx);
  * Queries that overlapped (tbvh_context_set_overlap): a launch that started before an earlier launch had ended reports the time it ADDED — from the latest
  * end of another launch inside its own interval to its own end, i.e. end(k) - end(k - 1) for launches that finish in the order they were enqueued — and
  * not its raw interval, which would count the other launch's work again.  The entries of a loop thus still sum to (at most) its wall time; a launch that
- * overlapped nothing reports its own interval exactly as before.  tbvh_time_last_ms() follows the same rule. */
+ * overlapped nothing reports its own interval exactly as before.  tbvh_time_last_ms() follows the same rule.
+ * The order in which overlapped launches may START: a launch starts after the launches before it on its own lane have ended and after the other lane's
+ * latest launch has started (with TBVH_OVERLAP_DEPTH=2: after the other lane's launch BEFORE its latest has started, so one lane runs up to two launches
+ * ahead); they may END in any order, and a launch of a loop over two buffers typically starts in the tail of the other buffer's launch before it.  The
+ * rule above does not depend on that order: an entry is measured from the latest other end inside the launch's own interval, whichever launch that is. */
 int tbvh_time_history(tbvh_context* ctx, float* ms, uint32_t cap, uint32_t* count);
 
 /* The machine's own ceilings, measured where the kernels run (bench.py's roofline denominators; best of `reps` launches, 0 = 3):

@@ -48,6 +48,26 @@ int tbvh_debug_overlap_stats(tbvh_context* ctx, uint64_t out[2]);
  * is available (a != 0) or not.  3 = out[row] = launches in flight on lane 0 + 256 x those on lane 1, after pruning.  Other rows leave out[row] = 0. */
 int tbvh_debug_lane_script(const uint64_t* ops5, uint64_t n_ops, int32_t* out);
 
+/* How many launches one lane may START ahead of the other (TBVH_OVERLAP_DEPTH in the environment; 1 or 2, default 1).  1: a launch waits for the start of
+ * the other lane's latest launch.  2: for the start of the other lane's launch before its latest one, while that one is in flight — a caller alternating
+ * two buffers (camera rays, bounce rays) gets the next camera launch into the tail of the bounce launch before the last.  Footprint conflicts keep their
+ * order at either depth. */
+int tbvh_debug_set_overlap_depth(tbvh_context* ctx, int depth);
+/* The context's memory of the coherence probe's verdicts (TBVH_PROBE_MEMORY=0 in the environment: off).  On (default): a probed two-flavor launch on a
+ * buffer (the same ray range, closest or any hit, scene) whose last two FINISHED launches were both classified incoherent leaves out the coherent flavor,
+ * which would only have sampled the probe and left; the incoherent flavor takes the sample, so the memory keeps learning and one coherent batch brings the
+ * two flavors back.  Which rays are traced, and what is written, never depends on it.  Setting it forgets what was learnt. */
+int tbvh_debug_set_probe_memory(tbvh_context* ctx, int enabled);
+/* out[0] = launches that left out the coherent flavor since the context was made, out[1] = verdicts read back from finished launches. */
+int tbvh_debug_probe_memory_stats(tbvh_context* ctx, uint64_t out[2]);
+/* tbvh_debug_lane_script with the start rule at `depth` and the verdict memory (tinybvh_amd/csrc/overlap_lanes.h: LaneBook::gate, probe_memory.h); no device,
+ * no context.  ops6: n_ops rows of 6 x u64 {operation, a, b, c, d, e}; out2: two numbers per row, {0, -1} where nothing is said.  Operations 0 to 3 as in
+ * tbvh_debug_lane_script (their answer in out2[2 row]); for a launch (0) out2[2 row + 1] = the row of the launch whose start it waits for, -1 for none.
+ * 4 = a call that joins the lanes.  5 = a probed launch of ray bytes [a, b) on scene c, any hit if d != 0, on lane e: verdicts of finished launches are
+ * harvested, out2[2 row] = 1 if it goes solo, and it is remembered under its row number.  6 = the probe of the launch of row a said b (1 incoherent,
+ * 2 coherent, 0 nothing), read once that row is finished (operation 1). */
+int tbvh_debug_runahead_script(const uint64_t* ops6, uint64_t n_ops, int depth, int64_t* out2);
+
 /* The wave-packet kernel's child filter (tinybvh_amd/csrc/packet_cull.h) beside its exact per-lane test, for ONE 64-ray chunk against n_nodes BVH8_CWBVH nodes
  * (80 bytes each), on the host as k_cwbvh_packet runs them; no device, no context.  rays64: 64 ray records of 64 bytes (O, D, rD, hit; O and rD are read);
  * have_mask: bit l = lane l holds a ray (at least one); tcull64: each lane's cull distance as the kernel forms it (cull_bound(hit.t), -1 for a ray that is out

@@ -104,6 +104,20 @@ class Context:
         check(lib.tbvh_debug_overlap_stats(self._h, out), "tbvh_debug_overlap_stats")
         return int(out[0]), int(out[1])
 
+    def set_overlap_depth(self, depth: int):
+        """How many launches one lane may start ahead of the other: 1 or 2 (tbvh_debug_set_overlap_depth; default 1, TBVH_OVERLAP_DEPTH)."""
+        check(lib.tbvh_debug_set_overlap_depth(self._h, int(depth)), "tbvh_debug_set_overlap_depth")
+
+    def set_probe_memory(self, enabled: bool):
+        """Remember the coherence probe's verdicts per buffer and launch incoherent batches as one kernel (tbvh_debug_set_probe_memory; default on, TBVH_PROBE_MEMORY=0)."""
+        check(lib.tbvh_debug_set_probe_memory(self._h, 1 if enabled else 0), "tbvh_debug_set_probe_memory")
+
+    def probe_memory_stats(self):
+        """(launches that left out the coherent flavor, verdicts read back) since the context was made (tbvh_debug_probe_memory_stats)."""
+        out = (C.c_uint64 * 2)()
+        check(lib.tbvh_debug_probe_memory_stats(self._h, out), "tbvh_debug_probe_memory_stats")
+        return int(out[0]), int(out[1])
+
     def set_timing(self, enabled: bool):
         """Per-operation HIP-event timing on / off (tbvh_set_timing): off saves two event records per query."""
         check(lib.tbvh_set_timing(self._h, 1 if enabled else 0), "tbvh_set_timing")

@@ -78,6 +78,10 @@ SYMBOLS = {
     "tbvh_context_set_overlap": (_i, [_vp, _i]),
     "tbvh_debug_overlap_stats": (_i, [_vp, _vp]),
     "tbvh_debug_lane_script": (_i, [_vp, _u64, _vp]),
+    "tbvh_debug_set_overlap_depth": (_i, [_vp, _i]),
+    "tbvh_debug_set_probe_memory": (_i, [_vp, _i]),
+    "tbvh_debug_probe_memory_stats": (_i, [_vp, _vp]),
+    "tbvh_debug_runahead_script": (_i, [_vp, _u64, _i, _vp]),
     "tbvh_debug_packet_cull": (_i, [_vp, _u64, _vp, _u64, _vp, _vp, _vp, _vp]),
     "tbvh_set_timing": (_i, [_vp, _i]),
     "tbvh_upload_bvh_gpu": (_i, [_vp, _vp, _u64, _vp, _u64, _vp, _u64, _pp]),

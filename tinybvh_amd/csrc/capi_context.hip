@@ -64,7 +64,11 @@ float timedMs(tbvh_context* c, uint64_t seq) {
     if (hipEventElapsedTime(&own, c->evRing[slot][0], c->evRing[slot][1]) != hipSuccess) { (void)hipGetLastError(); return -1.0f; }
     const uint32_t chain = c->evChain[slot];
     if (!chain) return own;
-    constexpr uint64_t kReach = 2 * LaneBook::kMaxInFlight;   // (launches that ran at the same time were enqueued next to each other: a launch starts after the launches before it on its lane have ended and those on the other lane have started)
+    // Launches that ran at the same time were enqueued near each other: a launch starts after the launches before it on its own lane have ended and, of those
+    // on the other lane, all but the last overlapDepth - 1 have started (LaneBook::gate) — beside a launch ran at most the other lane's last kMaxDepth launches
+    // before it and the launches that lane took until the next one of this lane.  Alternating lanes that is 2 x kMaxDepth numbers either side; a lane takes
+    // several launches in a row only for buffers that conflict there, which the book holds kMaxInFlight of before it joins.
+    constexpr uint64_t kReach = 2 * LaneBook::kMaxInFlight * LaneBook::kMaxDepth;
     const uint64_t oldest = c->evSeq > R ? c->evSeq - R : 0;
     const uint64_t lo = seq > oldest + kReach ? seq - kReach : oldest, hi = seq + kReach < c->evSeq ? seq + kReach + 1 : c->evSeq;
     float from = 0.f;   // ms after this launch's start
@@ -124,6 +128,8 @@ int tbvh_init(int device, tbvh_context** out) {
     if (const char* e = getenv("TBVH_DEBUG_FLAGS")) c->expFlags = (uint32_t)strtoul(e, nullptr, 0);   // tbvh_debug_set_flags from the environment (counter runs of tools/)
     if (const char* e = getenv("TBVH_COHERENT_TUNER")) { const int v = atoi(e); c->cohTunerMode = v == 0 ? 1 : (v == 2 ? 2 : (v == 3 ? 3 : 0)); }   // 0: off (always deferred + gated), 2: always strict, 3: always one traversal per wave
     if (const char* e = getenv("TBVH_OVERLAP")) { if (atoi(e) == 0) c->overlap = false; }   // every launch on lane 0 (tbvh_context_set_overlap)
+    if (const char* e = getenv("TBVH_OVERLAP_DEPTH")) { const int v = atoi(e); if (v >= 1 && v <= LaneBook::kMaxDepth) c->overlapDepth = v; }   // launches one lane may start ahead of the other (tbvh_debug_set_overlap_depth)
+    if (const char* e = getenv("TBVH_PROBE_MEMORY")) { if (atoi(e) == 0) c->probeMemoryOn = false; }   // every probed launch is two flavors (tbvh_debug_set_probe_memory)
     if (const char* e = getenv("TBVH_POOL_PARTS")) {  // experiment knob
         const int b = atoi(e);
         if (b >= 0 && (1 << b) <= kPoolParts) c->poolParts = (uint32_t)b;   // log2 of the partition count
@@ -166,6 +172,7 @@ void tbvh_shutdown(tbvh_context* c) {
     delete c->pipe;
     for (auto& pair : c->evRing) for (hipEvent_t ev : pair) if (ev) hipEventDestroy(ev);
     if (c->evBase) hipEventDestroy(c->evBase);
+    if (c->probeSlots) hipHostFree(c->probeSlots);   // (both lanes were idle above: no kernel still stores a verdict)
     if (c->lane1.stream) hipStreamDestroy(c->lane1.stream);
     if (c->ownStream) hipStreamDestroy(c->ownStream);
     delete c;   // (its device buffers go here: the device is current, its stream was idle)
@@ -229,6 +236,79 @@ int tbvh_debug_lane_script(const uint64_t* ops5, uint64_t nOps, int32_t* out) {
         default: return fail(TBVH_E_INVALID, "tbvh_debug_lane_script: row %llu has no such operation", (unsigned long long)i);
         }
     }
+    return 0;
+}
+
+// The same script with the rule for WHEN a launch may start (LaneBook::gate, at the given depth) and the memory of the probe's verdicts (probe_memory.h),
+// again without a device (tests/test_lane_runahead_host.py).  Rows of 6 x u64; out: two numbers per row.  Operations 0-3 as above, and for a launch (0)
+// out[2 i + 1] = the row of the launch whose start it waits for, or -1;
+//   4: an entry point that joins the lanes;
+//   5: a probed launch {rays lo, rays hi, scene, any hit, lane}: the finished launches' verdicts are harvested, out[2 i] = 1 if it goes solo; it is remembered;
+//   6: what the probe of row op[1] counted: op[2] = 1 incoherent, 2 coherent, 0 nothing (read when that row is seen finished, operation 1).
+int tbvh_debug_runahead_script(const uint64_t* ops6, uint64_t nOps, int depth, int64_t* out2) {
+    if ((!ops6 || !out2) && nOps) return fail(TBVH_E_INVALID, "tbvh_debug_runahead_script: null argument");
+    if (depth < 1 || depth > LaneBook::kMaxDepth) return fail(TBVH_E_INVALID, "tbvh_debug_runahead_script: depth %d (1..%d)", depth, LaneBook::kMaxDepth);
+    LaneBook book;
+    ProbeMemory memory;
+    std::vector<uint8_t> done(nOps, 0), said(nOps, 0);
+    bool allowLane1 = true;
+    auto prune = [&] { book.prune([&](int, uint32_t slot) { return done[slot] != 0; }); };
+    for (uint64_t i = 0; i < nOps; i++) {
+        const uint64_t* op = ops6 + i * 6;
+        out2[2 * i] = 0; out2[2 * i + 1] = -1;
+        if ((op[0] == 1 || op[0] == 6) && op[1] >= nOps) return fail(TBVH_E_INVALID, "tbvh_debug_runahead_script: row %llu names a row beyond the script", (unsigned long long)i);
+        switch (op[0]) {
+        case 0: {
+            LaneFootprint fp;
+            fp.rays.lo = (uintptr_t)op[1]; fp.rays.hi = (uintptr_t)op[2]; fp.occ.lo = (uintptr_t)op[3]; fp.occ.hi = (uintptr_t)op[4];
+            prune();
+            const LaneChoice ch = book.decide(fp, allowLane1);
+            if (ch.join) book.joined();
+            const uint64_t g = book.gate(ch.lane, depth, [&](uint64_t id) { return done[id] != 0; });
+            book.add(ch.lane, fp, (uint32_t)i, i);
+            out2[2 * i] = ch.lane + (ch.join ? 2 : 0);
+            out2[2 * i + 1] = g == LaneBook::kNoGate ? -1 : (int64_t)g;
+            break;
+        }
+        case 1: done[op[1]] = 1; break;
+        case 2: allowLane1 = op[1] != 0; break;
+        case 3: prune(); out2[2 * i] = book.count[0] + 256 * book.count[1]; break;
+        case 4: book.joined(); break;
+        case 5: {
+            ProbeKey key;
+            key.lo = (uintptr_t)op[1]; key.hi = (uintptr_t)op[2]; key.scene = (const void*)(uintptr_t)op[3]; key.any = op[4] != 0;
+            memory.harvest([&](uint64_t id) { return done[id] ? 1 : 0; }, [&](uint64_t id) { return (int)said[id]; });
+            out2[2 * i] = memory.solo(key) ? 1 : 0;
+            memory.note(key, i, (int)(op[5] & 1u));
+            break;
+        }
+        case 6: said[op[1]] = (uint8_t)(op[2] <= 2 ? op[2] : 0); break;
+        default: return fail(TBVH_E_INVALID, "tbvh_debug_runahead_script: row %llu has no such operation", (unsigned long long)i);
+        }
+    }
+    return 0;
+}
+
+int tbvh_debug_set_overlap_depth(tbvh_context* c, int depth) {
+    if (!c) return fail(TBVH_E_INVALID, "tbvh_debug_set_overlap_depth: null context");
+    if (depth < 1 || depth > LaneBook::kMaxDepth) return fail(TBVH_E_INVALID, "tbvh_debug_set_overlap_depth: depth %d (1..%d)", depth, LaneBook::kMaxDepth);
+    TBVH_ENTER(c);
+    c->overlapDepth = depth;
+    return 0;
+}
+
+int tbvh_debug_set_probe_memory(tbvh_context* c, int enabled) {
+    if (!c) return fail(TBVH_E_INVALID, "tbvh_debug_set_probe_memory: null context");
+    TBVH_ENTER(c);
+    c->probeMemoryOn = enabled != 0;
+    c->probeMemory.clear();   // (what was learnt under the other setting is not carried over)
+    return 0;
+}
+
+int tbvh_debug_probe_memory_stats(tbvh_context* c, uint64_t out[2]) {
+    if (!c || !out) return fail(TBVH_E_INVALID, "tbvh_debug_probe_memory_stats: null argument");
+    TBVH_LOCK(c);
+    out[0] = c->soloLaunches; out[1] = c->probeVerdicts;
     return 0;
 }
 

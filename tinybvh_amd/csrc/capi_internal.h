@@ -28,6 +28,7 @@
 #include "host_builder.h"
 #include "kernels.h"
 #include "overlap_lanes.h"
+#include "probe_memory.h"
 #include "ray_pool.h"
 
 using namespace tbvh;
@@ -129,7 +130,17 @@ struct tbvh_context {
     tbvh_capi::LaneBook book;       // launches in flight on each lane (a record's slot = its event pair in evRing)
     hipEvent_t evBase = nullptr;    // lane 0's position ahead of its in-flight query launches: what a launch on lane 1 waits for (generators, uploads, refits enqueued earlier)
     hipEvent_t lane1Last = nullptr; // end event of lane 1's most recent launch (one of evRing)
-    hipEvent_t laneStart[2] = {nullptr, nullptr};   // start event of each lane's most recent overlappable launch (of evRing): the other lane's next launch starts after it
+    // The other lane's next launch starts after the start of one of a lane's last launches (LaneBook::gate names it by its evSeq number; its start event
+    // is evRing[number % kTimeRing][0] for as long as fewer than kTimeRing timed operations have begun since: ringHolds).
+    int overlapDepth = 1;           // TBVH_OVERLAP_DEPTH / tbvh_debug_set_overlap_depth: how many launches one lane may start ahead of the other (1 or 2).  2 measured
+                                    // +1.3 % on the bench alone and nothing on top of the probe memory (profiles/r09_runahead.txt): it stays a setting, off
+    bool ringHolds(uint64_t seq) const { return seq < evSeq && evSeq - seq <= kTimeRing; }
+    // ---- what the coherence probe said about a buffer's last launches (probe_memory.h; capi_query.hip: launchQuery) -----------------------------
+    bool probeMemoryOn = true;      // TBVH_PROBE_MEMORY=0 / tbvh_debug_set_probe_memory(ctx, 0): every probed launch is two flavors
+    tbvh_capi::ProbeMemory probeMemory;
+    uint32_t* probeSlots = nullptr; // host-coherent pinned memory, two words per entry of evRing: the probe counts of the launch with that event pair, stored by its block 0
+    bool probeSlotsFailed = false;
+    uint64_t soloLaunches = 0, probeVerdicts = 0;   // tbvh_debug_probe_memory_stats
     bool lane1Dirty = false;        // lane 1 holds launches lane 0 has not waited for
     bool lane0Touched = true;       // something other than an overlappable launch went onto lane 0 since evBase was recorded
     bool lane1SawBase = false;      // lane 1 waits for evBase as recorded now

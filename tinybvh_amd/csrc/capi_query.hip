@@ -239,6 +239,7 @@ struct CwbvhLaunch {
     uint32_t blocksBase;   // grid of an incoherent one
     uint32_t* probeWords;  // the coherence probe's counters in this launch's pool area
     hipStream_t stream;    // the lane the launch takes
+    bool solo;             // the buffer's last two finished launches were incoherent (probe_memory.h): a two-flavor launch leaves out the coherent flavor
 };
 
 // One coherent-flavor kernel of a two-flavor launch, in the schedule the scene's tuner asks for; timed by the tuner's own events while it still measures.
@@ -304,7 +305,18 @@ static int launchCwbvhKernels(tbvh_scene* s, QueryArgs& q, const CwbvhLaunch& L)
     } else if (s->variant == 92) {   // diagnostic: one traversal per wave of 64 consecutive rays (kernels_cwbvh_packet.hip) whatever the batch, the scene's size and the tuner
         launch_cwbvh_packet(L.any, s->nodes, s->tris, q, c->status, L.blocks, L.stream);
     } else if (twoFlavors) {
-        if (int r = launchCoherentFlavor(s, q, L, tris, blocks7)) return r;
+        // Solo: the coherent flavor is left out.  The prediction decides nothing about which rays are traced: the incoherent flavor never looks at a verdict and
+        // draws every ray from the pool (as under variant 90), so a batch that has turned coherent is traced correctly, once, by the slower flavor; its block 0
+        // publishes the sample, the host sees the coherent vote when the launch has finished, and the buffer's next launch is two flavors again.  What is saved
+        // is a kernel of 8192 workgroups that sample and leave — 16 us into an idle GPU, but a stream barrier in front of the real kernel when the launch starts
+        // beside another lane's persistent waves (every slot taken: the dead flavor's last workgroup runs when that kernel retires).
+        const bool solo = L.solo && !L.probedSmall;
+        if (solo) {   // (what launchCoherentFlavor keeps for tbvh_debug_coherent_schedule is kept here too: the class of the latest launch, the launches counted)
+            q.flags |= 64u; c->soloLaunches++;
+            s->cohLastClass[L.any ? 1 : 0] = (uint8_t)L.sizeClass;
+            s->cohTuner[L.any ? 1 : 0][L.sizeClass].launches++;
+        }
+        else if (int r = launchCoherentFlavor(s, q, L, tris, blocks7)) return r;
         if (L.probedSmall) {   // behind it: the scene's unprobed kernel, as launched without a probe
             QueryArgs qp = q;
             qp.probe = nullptr; qp.baseBlocks = 0;
@@ -341,6 +353,43 @@ static bool ensureLane1(tbvh_context* c) {
     }
     l.poolClean = false;
     return true;
+}
+
+// The host's side of the probe's verdicts (probe_memory.h): two words per entry of the event ring in host-coherent pinned memory, made by the first probed
+// launch.  Block 0 of the kernel that publishes a launch's probe counts stores them there as well (cwbvh_probe.h: probe_publish) — no copy goes into the
+// stream — and the host reads a launch's words only after it has seen that launch's end event complete.  false: no such memory (every launch two flavors).
+static bool ensureProbeSlots(tbvh_context* c) {
+    if (c->probeSlots) return true;
+    if (c->probeSlotsFailed) return false;
+    void* p = nullptr;
+    if (hipHostMalloc(&p, (size_t)tbvh_context::kTimeRing * 2 * sizeof(uint32_t), hipHostMallocCoherent) != hipSuccess || !p) {
+        (void)hipGetLastError();
+        c->probeSlotsFailed = true;
+        return false;
+    }
+    memset(p, 0, (size_t)tbvh_context::kTimeRing * 2 * sizeof(uint32_t));
+    c->probeSlots = (uint32_t*)p;
+    return true;
+}
+
+// Verdicts of the remembered launches that have finished by now join the table.  Never waits: a launch still in flight stays remembered, one whose event
+// pair the ring has handed to a later operation leaves without a vote.
+static void harvestVerdicts(tbvh_context* c) {
+    c->probeMemory.harvest(
+        [c](uint64_t seq) {
+            if (!c->ringHolds(seq) || !c->probeSlots) return 2;
+            const hipError_t qe = hipEventQuery(c->evRing[seq % tbvh_context::kTimeRing][1]);
+            if (qe == hipSuccess) return 1;
+            (void)hipGetLastError();
+            return qe == hipErrorNotReady ? 0 : 2;
+        },
+        [c](uint64_t seq) {
+            const volatile uint32_t* w = c->probeSlots + 2 * (seq % tbvh_context::kTimeRing);
+            const uint32_t agree = w[0], pairs = w[1];
+            if (!pairs) return (int)ProbeMemory::kNone;
+            c->probeVerdicts++;
+            return (int)(agree * 10u >= pairs * 6u ? ProbeMemory::kCoherent : ProbeMemory::kIncoherent);   // the rule of k_cwbvh (kernels_cwbvh.hip)
+        });
 }
 
 // Something the launch does before its kernels would enqueue work on lane 0 or replace arrays that launches in flight read (a derived copy made or made
@@ -445,10 +494,23 @@ int launchQuery(tbvh_scene* s, RayRec* d_rays, uint64_t n, uint8_t* d_occ, bool 
                 HIP_TRY(hipStreamWaitEvent(c->lane1.stream, c->evBase, 0));
                 c->lane1SawBase = true;
             }
-            // Launches START in the order they were enqueued, across the lanes too: this one waits for the start (not the end) of the other lane's latest launch.
-            // Neither lane then runs more than one launch ahead of the other: a caller's frame k is complete before frame k + 1's launches take the GPU, and the
-            // launches that ran beside a launch are its neighbours in the order enqueued (what timedMs looks at).
-            if (!c->book.idle(lane ^ 1) && c->laneStart[lane ^ 1]) HIP_TRY(hipStreamWaitEvent(lane ? c->lane1.stream : c->stream, c->laneStart[lane ^ 1], 0));
+            // Launches START in the order they were enqueued, across the lanes too, give or take overlapDepth launches (LaneBook::gate): this one waits for the
+            // start (not the end) of one of the other lane's last launches.  Depth 1, the latest: neither lane runs more than one launch ahead of the other.
+            // Depth 2, the one before the latest, while it is in flight: a caller alternating camera and bounce batches (C1 D1 C2 D2 ...) gets C(k+2) into the
+            // tail of D(k) — at depth 1 it waits for the start of D(k+1), which stream order holds behind D(k)'s end, and lane 0 sits empty for exactly that
+            // tail.  The camera launch still takes the wave slots first: it starts in D(k)'s tail, D(k+1) behind D(k)'s end.  Either way the launches that ran
+            // beside a launch are its near neighbours in the order enqueued (what timedMs looks at).  Measured (profiles/r09_runahead.txt): depth 2 alone +1.3 %
+            // on the bench step.  That C(k+2) meets D(k) at all is the dead coherent flavor's doing: in front of D(1) it cannot finish before C(1) retires, so
+            // D(1) starts at C(1)'s end and every D(k) runs beside C(k+1).  Launched as one kernel (the probe memory below) D(k) starts beside C(k), C(k+1) waits
+            // for a start long past and takes D(k)'s tail at depth 1 already: depth 2 adds nothing then, so the default is 1.
+            // (A start event the ring has given to a later operation stands for a launch kTimeRing operations back: taken as finished, never waited for.)
+            const uint64_t g = c->book.gate(lane, c->overlapDepth, [c](uint64_t seq) {
+                if (!c->ringHolds(seq)) return true;
+                const hipError_t qe = hipEventQuery(c->evRing[seq % tbvh_context::kTimeRing][1]);
+                if (qe != hipSuccess) (void)hipGetLastError();
+                return qe != hipErrorNotReady;
+            });
+            if (g != LaneBook::kNoGate && c->ringHolds(g)) HIP_TRY(hipStreamWaitEvent(lane ? c->lane1.stream : c->stream, c->evRing[g % tbvh_context::kTimeRing][0], 0));
         }
     }
     const hipStream_t st = lane ? c->lane1.stream : c->stream;
@@ -463,7 +525,10 @@ int launchQuery(tbvh_scene* s, RayRec* d_rays, uint64_t n, uint8_t* d_occ, bool 
     uint32_t* const poolArea = pool + (size_t)poolCur * poolWords;
     q.spill = lane ? c->lane1.spill : c->spill; q.counter = poolArea; q.counterNext = pool + (size_t)(poolCur ^ 1) * poolWords;
     HIP_TRY(timedBegin(c, st));
-    const uint32_t ringSlot = (uint32_t)((c->evSeq - 1) % tbvh_context::kTimeRing);   // (lanes: timing is on, the launch has its event pair)
+    const uint64_t launchSeq = c->evSeq - 1;   // (lanes, probe memory: timing is on, the launch has its event pair)
+    const uint32_t ringSlot = (uint32_t)(launchSeq % tbvh_context::kTimeRing);
+    bool remember = false, solo = false;   // the probe's verdict on this launch will be remembered; the launch leaves out the coherent flavor (below)
+    ProbeKey pkey;
     // the launch's end, once its kernels are enqueued: the end event, the lane's record of it, the other counter area now zeroed by what was enqueued
     auto finish = [&]() -> int {
         HIP_TRY(hipGetLastError());
@@ -473,11 +538,11 @@ int launchQuery(tbvh_scene* s, RayRec* d_rays, uint64_t n, uint8_t* d_occ, bool 
             LaneFootprint fp;
             fp.rays.lo = (uintptr_t)d_rays; fp.rays.hi = fp.rays.lo + (uintptr_t)n * sizeof(RayRec);
             if (any) { fp.occ.lo = (uintptr_t)d_occ; fp.occ.hi = fp.occ.lo + (uintptr_t)n; }
-            c->book.add(lane, fp, ringSlot);
+            c->book.add(lane, fp, ringSlot, launchSeq);
             c->evChain[ringSlot] = c->chain;
-            c->laneStart[lane] = c->evRing[ringSlot][0];
             if (lane) { c->lane1Last = c->evRing[ringSlot][1]; c->lane1Dirty = true; c->lane1Launches++; }
         }
+        if (remember) c->probeMemory.note(pkey, launchSeq, lane);
         return 0;
     };
     // BVH8_CWBVH scenes beyond the L2s (the `small` class runs dense triangle phases, where the gated schedule loses 15 %) but within reach
@@ -507,6 +572,23 @@ int launchQuery(tbvh_scene* s, RayRec* d_rays, uint64_t n, uint8_t* d_occ, bool 
         c->lastProbed = true; c->lastProbedLane = lane;
         if (!c->gridOverride && blocks == c->blocks) blocks = c->blocks + c->blocks / 3u;   // 24 -> 32 one-wave workgroups per CU
     }
+    // What the probe said about this buffer's last launches (probe_memory.h).  A probed launch whose size the host knows gets a slot for its verdict (the
+    // slot of its event pair) and is remembered until it is seen finished.  It goes SOLO — the incoherent flavor alone, launchCwbvhKernels — when the last two
+    // finished launches with exactly this footprint both voted incoherent, the scene's tuner has settled this class of batch (it must see every coherent
+    // launch it would have seen) and nothing diagnostic is set.  Any doubt: two flavors, as without the memory.
+    if (c->probeMemory.nPending) harvestVerdicts(c);
+    // Only a launch that could ever go solo is given a slot and remembered: two flavors on the incoherent-batch copies (launchCwbvhKernels: twoFlavors without
+    // probedSmall), variant 0, nothing diagnostic set — variant 88, the one-kernel launch of a padded scene and runs under debug flags neither ask the
+    // events nor take an entry of the table.
+    const bool soloCandidate = probed && s->variant == 0 && !s->cw.padded && s->cw.hybrid && s->cw.trisPadded && !c->expFlags && !c->cohTunerMode && !c->gridOverride;
+    if (soloCandidate && c->probeMemoryOn && !c->skipTiming && !nDev && ensureProbeSlots(c)) {
+        pkey.lo = (uintptr_t)d_rays; pkey.hi = pkey.lo + (uintptr_t)n * sizeof(RayRec); pkey.scene = s; pkey.any = any;
+        remember = true;
+        uint32_t* const slot = c->probeSlots + 2 * (size_t)ringSlot;
+        slot[0] = slot[1] = 0u;   // (pairs == 0: no verdict)
+        q.probeHost = slot;
+        solo = s->cohTuner[any ? 1 : 0][sizeClass].decided != 0 && c->probeMemory.solo(pkey);
+    }
     if (s->isTlas) {
         launchTlasKernels(s, q, any, blocks, st);
         return finish();
@@ -522,7 +604,7 @@ int launchQuery(tbvh_scene* s, RayRec* d_rays, uint64_t n, uint8_t* d_occ, bool 
         break;
     case TBVH_LAYOUT_CWBVH:
         q.spillStride = c->spillEntries / 2;  // 8-byte entries
-        if (int r = launchCwbvhKernels(s, q, CwbvhLaunch{any, small, probedSmall, sizeClass, blocks, blocksBase, poolArea + (size_t)kPoolParts * kPoolCounterStride, st})) return r;
+        if (int r = launchCwbvhKernels(s, q, CwbvhLaunch{any, small, probedSmall, sizeClass, blocks, blocksBase, poolArea + (size_t)kPoolParts * kPoolCounterStride, st, solo})) return r;
         break;
     case TBVH_LAYOUT_BVH2_WALD:   // a sphere BLAS (kernels_custom.hip)
         q.spillStride = c->spillEntries / 2;  // 8-byte entries

@@ -33,4 +33,13 @@ __device__ __forceinline__ void coherence_sample(const RayRec* __restrict__ rays
     }
 }
 
+// Block 0's counts, for tbvh_debug_last_probe (the device words) and for the host's memory of this buffer's verdicts (capi_query.hip, probe_memory.h):
+// plain vector stores into host-coherent pinned memory, which the host reads once it has seen the launch's end event complete.
+__device__ __forceinline__ void probe_publish(const QueryArgs& q, uint32_t agree, uint32_t pairs) {
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        q.probe[0] = agree; q.probe[1] = pairs;
+        if (q.probeHost) { q.probeHost[0] = agree; q.probeHost[1] = pairs; }
+    }
+}
+
 }  // namespace tbvh

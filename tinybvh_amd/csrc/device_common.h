@@ -153,6 +153,10 @@ struct QueryArgs {
     uint32_t baseBlocks;
     uint32_t flags;        // 1 = non-temporal ray loads / hit stores, 2 = triangle records padded to 64 bytes (experiments); 16 = take the batch for coherent whatever the probe finds (variant 91); 32 = the first kernel of a two-flavor launch runs the strict schedule (PROBED == 4)
     uint32_t hybridK;      // BVH8_CWBVH, hybrid node array (cwbvh_node.h: kNodeHybrid): nodes below this index are packed, the others one per line
+    // the same two probe counts once more, for the host: two words of host-coherent pinned memory that the kernel publishing `probe` also stores
+    // (cwbvh_probe.h: probe_publish); nullptr: nobody remembers this launch's verdict.  flags & 64: the launch is the incoherent flavor ALONE (capi_query.hip:
+    // a buffer whose last launches were incoherent) — its block 0 takes the sample and publishes it, no wave acts on it.
+    uint32_t* probeHost = nullptr;
 };
 
 // Host side: does this launch use the kernels with split rays?  Batches below the threshold, and the wavefront stages (ray count

@@ -75,7 +75,13 @@ __global__ __launch_bounds__(WG, (STEAL || TRI2 || (SPEC && PROBED == 2)) ? MINW
         uint32_t agree = 0, pairs = 0;
         if (PROBED != 2) {
             coherence_sample(q.rays, nRaysTotal, q.fresh != 0u, q.freshTmax, agree, pairs);
-            if (blockIdx.x == 0 && threadIdx.x == 0) { q.probe[0] = agree; q.probe[1] = pairs; }
+            probe_publish(q, agree, pairs);
+        } else if ((q.flags & 64u) != 0 && blockIdx.x == 0) {
+            // the incoherent flavor launched ALONE (the host remembers this buffer's last two verdicts as incoherent: capi_query.hip): block 0 takes the
+            // sample the missing coherent flavor would have published, so that the host keeps learning; the verdict changes nothing in this launch
+            coherence_sample(q.rays, nRaysTotal, q.fresh != 0u, q.freshTmax, agree, pairs);
+            probe_publish(q, agree, pairs);
+            agree = 0;
         }
         coh = (pairs != 0 && agree * 10u >= pairs * 6u) || (q.flags & 16u) != 0;   // (flag 16: tbvh_set_variant 91 forces the coherent verdict — tests)
         if (PROBED == 3 || PROBED == 4) { if (!coh) return; }   // the coherent flavor of a two-kernel launch: 3 = deferred + gated schedule only (SPEC = true); 4 = the strict

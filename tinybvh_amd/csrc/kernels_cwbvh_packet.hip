@@ -45,7 +45,7 @@ __global__ __launch_bounds__(WG, 8) void k_cwbvh_packet(const float4* __restrict
     if (q.probe) {   // the coherent flavor of a two-kernel launch: same protocol as k_cwbvh<PROBED == 3> (the incoherent flavor behind it takes what this one leaves in the pool)
         uint32_t agree, pairs;
         coherence_sample(q.rays, nRaysTotal, q.fresh != 0u, q.freshTmax, agree, pairs);
-        if (blockIdx.x == 0 && threadIdx.x == 0) { q.probe[0] = agree; q.probe[1] = pairs; }
+        probe_publish(q, agree, pairs);
         if (!((pairs != 0 && agree * 10u >= pairs * 6u) || (q.flags & 16u) != 0)) return;
     }
     uint2* const spill = (uint2*)q.spill + (size_t)blockIdx.x * WG;

@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "overlap_lanes.h"
+#include "probe_memory.h"
 
 using namespace tbvh_capi;
 
@@ -72,10 +73,55 @@ int main() {
             if (ch.join) { b.joined(); live.clear(); }
             for (const Live& l : live)      // the property: a launch still running on the OTHER lane shares no byte with this one
                 if (!l.done && l.lane != ch.lane) CHECK(!footprintsIntersect(l.f, f));
+            // the start rule at either depth: the launch named is an unfinished one of the other lane since the last join — at depth 2 not that lane's latest
+            for (int depth = 1; depth <= LaneBook::kMaxDepth; depth++) {
+                const uint64_t g = b.gate(ch.lane, depth, [&](uint64_t id) { return id < live.size() ? live[id].done : true; });
+                if (g == LaneBook::kNoGate) continue;
+                CHECK(g < live.size() && live[g].lane != ch.lane);
+                size_t later = 0;
+                for (size_t j = (size_t)g + 1; j < live.size(); j++) later += live[j].lane == live[g].lane;
+                CHECK(later == (size_t)depth - 1);
+                if (depth == 2) CHECK(!live[g].done);
+            }
             live.push_back(Live{f, ch.lane, false});
             b.add(ch.lane, f, (uint32_t)live.size() - 1);
             CHECK(b.count[0] >= 0 && b.count[0] <= LaneBook::kMaxInFlight && b.count[1] >= 0 && b.count[1] <= LaneBook::kMaxInFlight);
             CHECK(b.lastLane == ch.lane);
+        }
+    }
+    // the verdict memory (probe_memory.h): random launches on a dozen footprints, random completions in lane order, against a model that keeps every
+    // footprint's finished verdicts — a launch goes solo only if the model's last two for exactly that footprint are incoherent (the table may have
+    // forgotten a footprint: never the other way round)
+    for (int script = 0; script < 200; script++) {
+        ProbeMemory m;
+        struct Flight { ProbeKey key; int lane; uint8_t said; bool done, lost; };
+        std::vector<Flight> flights;
+        std::vector<std::vector<uint8_t>> votes(12);
+        size_t harvested[2] = {0, 0};       // per lane: flights before this index have been offered to the table
+        for (uint32_t i = 0; i < 600; i++) {
+            if (next(3) == 0 && !flights.empty()) {
+                const size_t k = next(flights.size());
+                for (size_t j = 0; j <= k; j++) if (flights[j].lane == flights[k].lane) flights[j].done = true;
+                continue;
+            }
+            if (flights.size() - (harvested[0] < harvested[1] ? harvested[0] : harvested[1]) >= 40)   // (the model has no cap on launches in flight; the memory's is 64)
+                for (Flight& f : flights) f.done = true;
+            const uint32_t which = (uint32_t)next(12);
+            ProbeKey key;
+            key.lo = 1000 * (which % 6); key.hi = key.lo + 1000; key.scene = (const void*)(uintptr_t)(1 + which / 6); key.any = false;
+            m.harvest([&](uint64_t id) { return flights[id].lost ? 2 : flights[id].done ? 1 : 0; }, [&](uint64_t id) { return (int)flights[id].said; });
+            for (int lane = 0; lane < 2; lane++)    // the model: what the table has been offered by now, in the same order
+                for (size_t& j = harvested[lane]; j < flights.size(); j++) {
+                    if (flights[j].lane != lane) continue;
+                    if (!flights[j].done && !flights[j].lost) break;
+                    if (!flights[j].lost && flights[j].said) votes[(flights[j].key.lo / 1000) + 6 * ((uintptr_t)flights[j].key.scene - 1)].push_back(flights[j].said);
+                }
+            const std::vector<uint8_t>& v = votes[which];
+            const bool may = v.size() >= 2 && v[v.size() - 1] == ProbeMemory::kIncoherent && v[v.size() - 2] == ProbeMemory::kIncoherent;
+            if (m.solo(key)) CHECK(may);
+            CHECK(m.nPending >= 0 && m.nPending <= ProbeMemory::kPending);
+            flights.push_back(Flight{key, (int)(which & 1u), (uint8_t)next(3), false, next(16) == 0});   // (launches on one buffer conflict: always the same lane)
+            m.note(key, flights.size() - 1, flights.back().lane);
         }
     }
     std::puts("overlap_lanes: ok");
