@@ -155,6 +155,8 @@ public:
         Check(tbvh_intersect_spheres_device(s, dSpheres, n, dVerts, triCount, dHit), "tbvh_intersect_spheres_device");
     }
     tbvh_scene* Handle() const { return s; }
+    // a TLAS scene: which tree tbvh_rebuild_tlas_device builds from now on — the LBVH (default) or, sah = true, the reference's own BVH::Build( BLASInstance*, n ) tree
+    void SetTlasBuilder(bool sah) { Check(tbvh_tlas_set_builder(s, sah ? 2 : 0), "tbvh_tlas_set_builder"); }
     int Device() const { return dev; }
     tbvh_context* Ctx() const { return ctx; }
 private:
@@ -237,6 +239,11 @@ public:
     // spheres16 in host memory, or in device memory with onDevice = true.  A TLAS over Handle() needs no new upload after Rebuild / Refit.
     void BuildOnDevice(const float* spheres16, uint32_t n, bool ploc = false, uint32_t maxLeaf = 0, uint32_t radius = 0, bool onDevice = false) {
         Check(tbvh_build_device_custom_spheres(ctx, spheres16, n, onDevice ? 1 : 0, ploc ? 1 : 0, maxLeaf, radius, Fresh()), "tbvh_build_device_custom_spheres");
+    }
+    // the reference's own tree over the spheres, BVH::Build( &sphereAABB, n ), built on the device (maxLeaf 0 = its leaves, 1..4 = SplitLeafs); Rebuild
+    // then rebuilds with SAH as well
+    void BuildOnDeviceSAH(const float* spheres16, uint32_t n, uint32_t maxLeaf = 0, bool onDevice = false) {
+        Check(tbvh_build_device_custom_spheres_sah(ctx, spheres16, n, onDevice ? 1 : 0, maxLeaf, Fresh()), "tbvh_build_device_custom_spheres_sah");
     }
     void Rebuild(const float* spheres16, uint32_t n, bool onDevice = false) {
         Check(tbvh_rebuild_custom_spheres_device(s, spheres16, n, onDevice ? 1 : 0), "tbvh_rebuild_custom_spheres_device");

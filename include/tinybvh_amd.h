@@ -222,7 +222,13 @@ int tbvh_refit(tbvh_scene* scene, const void* verts16, uint64_t n_tris, int on_d
  * Asynchronous on the context's stream; tbvh_time_last_ms() reports the device time of the rebuild.
  * The instance update follows BLASInstance::Update / InvertTransform operation for operation (including the FMA
  * contraction of the reference build), so the records equal the ones tinybvh computes bit for bit.
- * The tree is an LBVH, not the reference's binned-SAH TLAS: same hit records, different node order. */
+ * The tree is an LBVH by default, not the reference's binned-SAH TLAS: same hit records, different node order.  tbvh_tlas_set_builder( tlas, 2 )
+ * switches the rebuilds of that TLAS to the reference's own tree — BVH::Build( BLASInstance*, n ) over the updated records, then
+ * BVH_GPU::ConvertFrom, both on the device (DESIGN.md par. 20), byte for byte what BVH_GPU::Build( BLASInstance*, .. ) gives, leaves of several
+ * instances included (the wide collapse splits them) — and 0 switches back.  The SAH rebuild runs on the context's stream too but synchronises it
+ * (one small read-back, or one per level above tbvh_debug_set_sah_one_group instances).  Any other builder, or a scene that is no TLAS: TBVH_E_INVALID.
+ * tbvh_host_build_tlas_sah is the host twin. */
+int tbvh_tlas_set_builder(tbvh_scene* tlas, int builder);
 int tbvh_rebuild_tlas_device(tbvh_scene* tlas, const void* transforms, int on_device,
                              const float* blas_bounds6, uint64_t n_blas);
 /* Read the TLAS back (tests, inspection): any of the three buffers may be NULL. */
@@ -774,6 +780,12 @@ int tbvh_refit_custom_spheres(tbvh_scene* scene, const void* spheres16, uint64_t
 int tbvh_custom_spheres_download(tbvh_scene* scene, void* nodes32, uint64_t cap_nodes, uint32_t* prim_idx, uint64_t cap_idx, void* spheres16,
                                  uint64_t cap_spheres, uint64_t* n_nodes, uint64_t* n_idx);
 int tbvh_custom_spheres_bounds(tbvh_scene* scene, float bounds6[6]);
+/* tbvh_build_device_custom_spheres_sah: the reference's OWN tree over the spheres, BVH::Build( customGetAABB, n ) with the sphereAABB callback
+ * (tiny_bvh.h:2190-2219), built on the device by the SAH builder declared with tbvh_build_bvh2_sah_device_aabbs below (DESIGN.md par. 20).  max_leaf = 0 leaves
+ * the tree as BVH::Build does (leaves of any size, the tree as many nodes as the loop made: at most 2 n); 1..4 applies BVH::SplitLeafs( max_leaf );
+ * more: TBVH_E_INVALID.  1 <= n <= 2^30 - 1.  The result is an ordinary TBVH_LAYOUT_BVH2_WALD sphere scene that remembers its builder:
+ * tbvh_rebuild_custom_spheres_device rebuilds it with SAH in place, tbvh_refit_custom_spheres, the download and every query take it as any other. */
+int tbvh_build_device_custom_spheres_sah(tbvh_context* ctx, const void* spheres16, uint64_t n, int on_device, uint32_t max_leaf, tbvh_scene** out);
 
 /* ----------------------------------------------------------------------------------
  * indexed and strided triangle meshes — the second form the reference takes triangles in: Build( bvhvec4slice { data, count, stride }, indices,
@@ -855,6 +867,29 @@ int tbvh_build_bvh2_sah_device(tbvh_context* ctx, const tbvh_mesh* mesh, uint32_
 int tbvh_build_device_sah(tbvh_context* ctx, const void* verts16, uint64_t n_tris, int on_device, int layout, uint32_t max_leaf_tris, tbvh_scene** out);
 int tbvh_host_build_bvh2_sah(const tbvh_mesh* mesh, uint32_t max_leaf_tris, void* nodes32_out, uint64_t cap_nodes, uint32_t* prim_idx_out,
                              uint64_t cap_idx, uint64_t* n_nodes_out);
+/* The same tree over BOXES (DESIGN.md par. 20).  The reference's three builds over boxes fill fragment[] and call the very Build() above, so only the
+ * fragment step differs; everything of the contract above holds (numbering, ascending leaves, max_leaf = SplitLeafs, what is not reproduced, the
+ * output and capacity rules of tbvh_build_bvh2_sah_device with n in place of n_tris).
+ *   tbvh_build_bvh2_sah_device_aabbs / tbvh_host_build_bvh2_sah_aabbs: BVH::BuildAABB( aabbs, n ) (tiny_bvh.h:2151-2186): aabbs32[2 i] is box i's min and
+ *     aabbs32[2 i + 1] its max, as float4 (w ignored, 32 bytes per box), in host (on_device = 0) or device memory.
+ *   tbvh_host_build_bvh2_sah_spheres: BVH::Build( customGetAABB, n ) (2190-2219) with the demos' sphereAABB over {x, y, z, r} records: the twin of
+ *     tbvh_build_device_custom_spheres_sah.
+ *   tbvh_host_build_tlas_sah: BVH::Build( BLASInstance*, n, 0, 0 ) (2221-2259, the null-blasList form) over the aabbMin / aabbMax of 192-byte instance records
+ *     ALREADY UPDATED, then BVH_GPU::ConvertFrom (4612-4655): nodes64_out = the Aila-Laine nodes BVH_GPU::Build( BLASInstance*, .. ) leaves
+ *     (usedNodes - 1 of them: the pad node is not emitted), idx_out = the instance indices, every leaf's ascending.  cap_nodes counts 64-byte nodes;
+ *     2 n always suffice.
+ * 1 <= n <= 2^30 - 1, null arguments: TBVH_E_INVALID.  Device-resident arrays are not validated: the build terminates with a structurally valid tree
+ * whatever they hold (r <= 0 gives inverted boxes; NaNs answer as the operations of sah_split.h answer).
+ * Small inputs (at most tbvh_debug_set_sah_one_group primitives, triangles too) are built by ONE workgroup in one launch, with one 4-byte read-back at the
+ * end instead of one per level; the tree does not depend on which path built it. */
+int tbvh_build_bvh2_sah_device_aabbs(tbvh_context* ctx, const void* aabbs32, uint64_t n, int on_device, uint32_t max_leaf, void* nodes32_out,
+                                     uint64_t cap_nodes, uint32_t* prim_idx_out, uint64_t cap_idx, int out_on_device, uint64_t* n_nodes_out);
+int tbvh_host_build_bvh2_sah_aabbs(const void* aabbs32, uint64_t n, uint32_t max_leaf, void* nodes32_out, uint64_t cap_nodes, uint32_t* prim_idx_out,
+                                   uint64_t cap_idx, uint64_t* n_nodes_out);
+int tbvh_host_build_bvh2_sah_spheres(const void* spheres16, uint64_t n, uint32_t max_leaf, void* nodes32_out, uint64_t cap_nodes, uint32_t* prim_idx_out,
+                                     uint64_t cap_idx, uint64_t* n_nodes_out);
+int tbvh_host_build_tlas_sah(const void* instances192, uint64_t n, void* nodes64_out, uint64_t cap_nodes, uint32_t* idx_out, uint64_t cap_idx,
+                             uint64_t* n_nodes_out);
 
 /* The reference's SBVH on the device: BVH::BuildHQ (tiny_bvh.h:2623-3040: the spatial-split builder every GPU layout of the reference's demos is
  * built with), reproduced node for node and byte for byte (DESIGN.md par. 19) by the method of the builder above: one header for the arithmetic

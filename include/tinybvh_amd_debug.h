@@ -97,6 +97,13 @@ int tbvh_debug_wide_copy_bvh2(int layout, const void* blob, uint64_t n_blob, con
  * instead of by its per-level kernels.  n = 0: the per-level path alone; n >= the triangle count: one wave builds the whole tree.  The tree does not
  * depend on n (tests force both paths); the build time does.  A new context starts at 64 (profiles/sah_device_build.txt). */
 int tbvh_debug_set_sah_small_subtree(tbvh_context* ctx, uint32_t n);
+/* Inputs of at most n primitives (triangles, boxes, spheres) are built by ONE workgroup in one launch (kernels_sahbuild.hip: k_sah_one_group: the level loop
+ * with workgroup barriers in place of kernel boundaries, no read-back per level) instead of by the per-level kernels.  0: never.  Inputs of more than 2^14
+ * primitives take the level path whatever n says.  The tree does not depend on n (tests force both paths); the build time does
+ * (a new context starts at 3000: profiles/box_sah_build.txt has the sweep it was chosen from). */
+int tbvh_debug_set_sah_one_group(tbvh_context* ctx, uint32_t n);
+/* out[0] = the context's small-subtree threshold, out[1] = its one-workgroup threshold, as they are now (a test saves them before it changes them). */
+int tbvh_debug_get_sah_thresholds(tbvh_context* ctx, uint32_t out[2]);
 
 /* Device memory the library itself owns right now, over every context of this process: out[0] = live allocations, out[1] = their bytes.  Scenes (their
  * derived copies, staging and scratch areas included), contexts and wavefront objects are counted; memory handed to the caller (tbvh_device_malloc,

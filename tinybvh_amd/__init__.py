@@ -304,6 +304,56 @@ def build_bvh2_sah(ctx, verts, indices=None, max_leaf_tris: int = 0):
     return nodes[:n.value].copy(), idx
 
 
+def _boxes_arg(aabbs):
+    """BVH::BuildAABB's layout from (n, 2, 4), (2 n, 4) or (n, 8) float32: box i = min at float4 2 i, max at 2 i + 1 (w ignored)"""
+    a = np.ascontiguousarray(aabbs, np.float32)
+    assert a.size % 8 == 0 and a.size > 0, "aabbs: n x {min float4, max float4}"
+    return a.reshape(-1, 8)
+
+
+def _sah_box_call(fn, name, head, n, max_leaf, width=8):
+    nodes = np.zeros((max(2 * n, 2), width), np.uint32)
+    idx = np.zeros(n, np.uint32)
+    nn = C.c_uint64(0)
+    check(fn(*head, n, *max_leaf, _ptr(nodes), nodes.shape[0], _ptr(idx), idx.size, C.byref(nn)), name)
+    return nodes[:nn.value].copy(), idx
+
+
+def host_build_bvh2_sah_boxes(aabbs, max_leaf: int = 0):
+    """The reference's BVH::BuildAABB tree over boxes by the sequential CPU twin (tbvh_host_build_bvh2_sah_aabbs): (nodes32 (n, 8) uint32, prim_idx)."""
+    a = _boxes_arg(aabbs)
+    return _sah_box_call(lib.tbvh_host_build_bvh2_sah_aabbs, "tbvh_host_build_bvh2_sah_aabbs", (_ptr(a),), a.shape[0], (int(max_leaf),))
+
+
+def host_build_bvh2_sah_spheres(spheres, max_leaf: int = 0):
+    """The reference's BVH::Build( customGetAABB, n ) tree over spheres {x, y, z, r} (boxes pos -/+ r) by the CPU twin (tbvh_host_build_bvh2_sah_spheres)."""
+    a = np.ascontiguousarray(spheres, np.float32).reshape(-1, 4)
+    return _sah_box_call(lib.tbvh_host_build_bvh2_sah_spheres, "tbvh_host_build_bvh2_sah_spheres", (_ptr(a),), a.shape[0], (int(max_leaf),))
+
+
+def host_build_tlas_sah(instances192):
+    """The reference's TLAS over 192-byte instance records already updated (tbvh_host_build_tlas_sah): BVH::Build( BLASInstance*, n, 0, 0 ), then
+    BVH_GPU::ConvertFrom: (nodes64 (n, 16) uint32 Aila-Laine nodes, instance indices with every leaf's ascending)."""
+    a = np.ascontiguousarray(instances192).view(np.uint8).reshape(-1, 192)
+    return _sah_box_call(lib.tbvh_host_build_tlas_sah, "tbvh_host_build_tlas_sah", (_ptr(a),), a.shape[0], (), width=16)
+
+
+def build_bvh2_sah_boxes(ctx, aabbs, max_leaf: int = 0):
+    """The BVH::BuildAABB tree built on the device (tbvh_build_bvh2_sah_device_aabbs) and read back: byte for byte what host_build_bvh2_sah_boxes gives.
+    aabbs: a numpy array, or a (device_pointer, n) pair."""
+    if isinstance(aabbs, tuple):
+        ptr, n, on_device, a = C.c_void_p(int(aabbs[0])), int(aabbs[1]), 1, None
+    else:
+        a = _boxes_arg(aabbs)
+        ptr, n, on_device = _ptr(a), a.shape[0], 0
+    nodes = np.zeros((max(2 * n, 2), 8), np.uint32)
+    idx = np.zeros(n, np.uint32)
+    nn = C.c_uint64(0)
+    check(lib.tbvh_build_bvh2_sah_device_aabbs(ctx._h, ptr, n, on_device, int(max_leaf), _ptr(nodes), nodes.shape[0], _ptr(idx), idx.size, 0, C.byref(nn)),
+          "tbvh_build_bvh2_sah_device_aabbs")
+    return nodes[:nn.value].copy(), idx
+
+
 SBVH_STATS = ("n_refs", "n_spatial_splits", "n_unsplit_left", "n_unsplit_right", "n_fragment_splits", "n_one_sided_splits", "n_clipped_reclips",
               "n_budget_refusals", "n_failed_partitions")   # tbvh_sbvh_stats, field for field
 
@@ -911,10 +961,20 @@ class TLAS(_Scene):
             bounds[i] = b._bounds
         return bounds
 
-    def RebuildOnDevice(self, transforms=None, on_device: bool = False) -> "TLAS":
-        """Per-frame rebuild on the GPU (tbvh_rebuild_tlas_device): instance update + LBVH TLAS, no host
-        build and no node upload.  transforms: (n, 16) float32 array (host), a device pointer (int,
+    def SetBuilder(self, builder: str) -> "TLAS":
+        """The tree RebuildOnDevice builds from now on: "lbvh" (the default) or "sah", the reference's own BVH::Build( BLASInstance*, n ) tree
+        (tbvh_tlas_set_builder)."""
+        if builder not in ("lbvh", "sah"):
+            raise ValueError(f"TLAS.SetBuilder: builder {builder!r} (lbvh or sah)")
+        check(lib.tbvh_tlas_set_builder(self._h, {"lbvh": 0, "sah": 2}[builder]), "tbvh_tlas_set_builder")
+        return self
+
+    def RebuildOnDevice(self, transforms=None, on_device: bool = False, builder=None) -> "TLAS":
+        """Per-frame rebuild on the GPU (tbvh_rebuild_tlas_device): instance update + LBVH TLAS (or the reference's SAH TLAS: builder="sah",
+        which stays set, as after SetBuilder), no host build and no node upload.  transforms: (n, 16) float32 array (host), a device pointer (int,
         on_device=True), or None to keep the transforms already in the device records."""
+        if builder is not None:
+            self.SetBuilder(builder)
         bounds = self._blas_bounds(self.blas)   # sent with the first call, and again when a BLAS's box has changed (SphereBVH.RebuildOnDevice / Refit)
         last = getattr(self, "_bounds_last", None)
         if getattr(self, "_bounds_sent", False) and (last is None or np.array_equal(bounds, last)):
@@ -1414,11 +1474,17 @@ class SphereBVH(_Scene):
 
     def BuildOnDevice(self, spheres, builder: str = "lbvh", max_leaf: int = 0, radius: int = 0) -> "SphereBVH":
         """LBVH (max_leaf 1..4 spheres per leaf, 0 = 1) or PLOC (radius 1..32, 0 = 16) over the boxes pos -/+ r, on the device
-        (tbvh_build_device_custom_spheres).  spheres: a numpy array or a (device_pointer, n) pair."""
+        (tbvh_build_device_custom_spheres), or builder="sah": the reference's own BVH::Build( customGetAABB, n ) tree (max_leaf 0 = its leaves,
+        1..4 = SplitLeafs; tbvh_build_device_custom_spheres_sah).  spheres: a numpy array or a (device_pointer, n) pair."""
         ptr, n, on_device, keep = self._sphere_arg(spheres)
+        if builder not in ("lbvh", "ploc", "sah"):
+            raise ValueError(f"SphereBVH.BuildOnDevice: builder {builder!r} (lbvh, ploc or sah)")
         if self._h:
             self.free()
             self._h = C.c_void_p()
+        if builder == "sah":
+            check(lib.tbvh_build_device_custom_spheres_sah(self.ctx._h, ptr, n, on_device, int(max_leaf), C.byref(self._h)), "tbvh_build_device_custom_spheres_sah")
+            return self._after_device_call(keep)
         check(lib.tbvh_build_device_custom_spheres(self.ctx._h, ptr, n, on_device, {"lbvh": 0, "ploc": 1}[builder], int(max_leaf), int(radius),
                                                    C.byref(self._h)), "tbvh_build_device_custom_spheres")
         return self._after_device_call(keep)

@@ -101,6 +101,11 @@ SYMBOLS = {
     "tbvh_build_device_sah": (_i, [_vp, _vp, _u64, _i, _i, _u32, _vp]),
     "tbvh_build_bvh2_sah_device": (_i, [_vp, C.POINTER(Mesh), _u32, _vp, _u64, _vp, _u64, _i, C.POINTER(_u64)]),
     "tbvh_host_build_bvh2_sah": (_i, [C.POINTER(Mesh), _u32, _vp, _u64, _vp, _u64, C.POINTER(_u64)]),
+    "tbvh_build_bvh2_sah_device_aabbs": (_i, [_vp, _vp, _u64, _i, _u32, _vp, _u64, _vp, _u64, _i, C.POINTER(_u64)]),
+    "tbvh_host_build_bvh2_sah_aabbs": (_i, [_vp, _u64, _u32, _vp, _u64, _vp, _u64, C.POINTER(_u64)]),
+    "tbvh_host_build_bvh2_sah_spheres": (_i, [_vp, _u64, _u32, _vp, _u64, _vp, _u64, C.POINTER(_u64)]),
+    "tbvh_host_build_tlas_sah": (_i, [_vp, _u64, _vp, _u64, _vp, _u64, C.POINTER(_u64)]),
+    "tbvh_build_device_custom_spheres_sah": (_i, [_vp, _vp, _u64, _i, _u32, C.POINTER(_vp)]),
     "tbvh_build_bvh2_sbvh_device": (_i, [_vp, C.POINTER(Mesh), _u32, _vp, _u64, _vp, _u64, _i, C.POINTER(_u64), C.POINTER(_u64), _vp]),
     "tbvh_host_build_bvh2_sbvh": (_i, [C.POINTER(Mesh), _u32, _vp, _u64, _vp, _u64, C.POINTER(_u64), C.POINTER(_u64), _vp]),
     "tbvh_build_device_sbvh": (_i, [_vp, _vp, _u64, _i, _i, _u32, _vp]),
@@ -140,6 +145,9 @@ SYMBOLS = {
     "tbvh_debug_last_probe": (_i, [_vp, _vp]),
     "tbvh_debug_set_flags": (_i, [_vp, _u32]),
     "tbvh_debug_set_sah_small_subtree": (_i, [_vp, _u32]),
+    "tbvh_debug_set_sah_one_group": (_i, [_vp, _u32]),
+    "tbvh_debug_get_sah_thresholds": (_i, [_vp, C.POINTER(_u32)]),
+    "tbvh_tlas_set_builder": (_i, [_vp, _i]),
     "tbvh_debug_device_allocations": (_i, [C.POINTER(_u64)]),
     "tbvh_cwbvh_set_hybrid": (_i, [_vp, C.c_int64]),
     "tbvh_bin_rays_device": (_i, [_vp, _vp, _vp, _u64, C.POINTER(C.c_float), _u32, _u32, _vp]),

@@ -1,12 +1,13 @@
 // capi_custom.hip — custom-geometry sphere BLASes (BVH::Build( customGetAABB, n ), tiny_bvh.h:2190-2219, traced through the sphere callback of the
 // reference's anim demo): upload with validation and the host builder behind tbvh_host_build_custom_spheres.  The kernels are kernels_custom.hip;
 // queries reach them through launchQuery (capi_query.hip), TLASes over sphere BLASes through tbvh_upload_tlas (capi_scene.hip).
-// Sphere sets that move: tbvh_build_device_custom_spheres / tbvh_rebuild_custom_spheres_device (the LBVH / PLOC builders of kernels_build.hip with the
+// Sphere sets that move: tbvh_build_device_custom_spheres / _sah / tbvh_rebuild_custom_spheres_device (the LBVH / PLOC builders of kernels_build.hip, or the SAH builder of kernels_sahbuild.hip, with the
 // spheres as their box source, then the record gather) and tbvh_refit_custom_spheres (kernels_custom_build.hip); tbvh_custom_spheres_download reads a
 // sphere scene back.
 // A sphere scene (layout TBVH_LAYOUT_BVH2_WALD) keeps the Wald nodes as uploaded in `nodes` and the spheres gathered in primIdx order in `tris`
 // (2 float4 per index entry: {x, y, z, r}, {prim, 0, 0, 0}); a TLAS's BlasDesc points at the two.  tbvh_free_scene frees them like any scene's.
 #include "capi_internal.h"
+#include "sahbuild.h"
 
 using namespace tbvh;
 using namespace tbvh_capi;
@@ -112,7 +113,9 @@ int buildSphereTree(tbvh_scene* s, const char* who, const float4* dSph, uint64_t
     const uint64_t nNodes = n > 1 ? 2 * n : 2;   // root, the unused node 1, the n - 1 child pairs
     if (s->buildScratchFor != n || !s->buildScratch) {
         s->buildScratchFor = 0;
-        const size_t bytes = s->sphBuilder == 1 ? ploc_scratch_bytes((uint32_t)n, &s->sortTempBytes, &s->scanTempBytes) : lbvh_scratch_bytes((uint32_t)n, &s->sortTempBytes);
+        const size_t bytes = s->sphBuilder == 2   ? sah_scratch_bytes((uint32_t)n, &s->sortTempBytes, &s->scanTempBytes)
+                             : s->sphBuilder == 1 ? ploc_scratch_bytes((uint32_t)n, &s->sortTempBytes, &s->scanTempBytes)
+                                                  : lbvh_scratch_bytes((uint32_t)n, &s->sortTempBytes);
         if (s->buildScratch.alloc(bytes) != hipSuccess || s->sphIdx.reserve(n) != hipSuccess) {
             (void)hipGetLastError();
             return fail(TBVH_E_NOMEM, "%s: out of device memory (%llu bytes of build scratch)", who, (unsigned long long)bytes);
@@ -133,14 +136,20 @@ int buildSphereTree(tbvh_scene* s, const char* who, const float4* dSph, uint64_t
         }
         if (r) { (void)oldNodes.release(); (void)oldRecs.release(); return r; }   // (a descriptor may still point at the old arrays: leak them rather than dangle)
     }
+    uint32_t built = (uint32_t)nNodes;
     HIP_TRY(timedBegin(c));
-    if (s->sphBuilder == 1) HIP_TRY(launch_ploc_build(MeshSrc{}, (uint32_t)n, s->sphRadius, s->nodes, s->sphIdx, s->buildScratch, s->sortTempBytes, s->scanTempBytes, c->stream, nullptr, dSph));
+    // builder 2: the reference's BVH::Build( customGetAABB, n ) with the sphereAABB callback (kernels_sahbuild.hip over sphere boxes); the tree has as many
+    // nodes as the SAH loop made (at most 2 n), leaves of any size unless sphMaxLeaf cuts them (SplitLeafs)
+    if (s->sphBuilder == 2)
+        HIP_TRY(run_sah_build(SahSrc(sah_boxes_spheres(dSph)), (uint32_t)n, s->sphMaxLeaf, c->sahSmallSubtree, c->sahOneGroup, s->nodes, s->sphIdx, s->buildScratch,
+                              s->sortTempBytes, s->scanTempBytes, c->status, c->stream, &built));
+    else if (s->sphBuilder == 1) HIP_TRY(launch_ploc_build(MeshSrc{}, (uint32_t)n, s->sphRadius, s->nodes, s->sphIdx, s->buildScratch, s->sortTempBytes, s->scanTempBytes, c->stream, nullptr, dSph));
     else HIP_TRY(launch_lbvh_build(MeshSrc{}, (uint32_t)n, s->sphMaxLeaf, s->nodes, s->sphIdx, s->buildScratch, s->sortTempBytes, c->stream, dSph));
     launch_gather_sphere_records(s->sphIdx, dSph, s->tris, (uint32_t)n, c->stream);
     HIP_TRY(timedEnd(c));
     HIP_TRY(hipStreamSynchronize(c->stream));   // (the caller's spheres may change; a launch error surfaces here)
-    s->nNodes = (uint32_t)nNodes;
-    s->nNodeBlocks = nNodes * 2; s->nTriBlocks = n * 2;
+    s->nNodes = built;
+    s->nNodeBlocks = (uint64_t)built * 2; s->nTriBlocks = n * 2;
     s->bytes = sphereSceneBytes(s);
     return 0;
 }
@@ -165,6 +174,23 @@ int tbvh_build_device_custom_spheres(tbvh_context* c, const void* spheres16, uin
     const float4* dSph = nullptr;
     int r = stageSpheres(s, "tbvh_build_device_custom_spheres", spheres16, n, onDevice, &dSph);
     if (!r) r = buildSphereTree(s, "tbvh_build_device_custom_spheres", dSph, n);
+    if (r) { tbvh_free_scene(s); return r; }
+    *out = s;
+    return 0;
+}
+
+int tbvh_build_device_custom_spheres_sah(tbvh_context* c, const void* spheres16, uint64_t n, int onDevice, uint32_t maxLeaf, tbvh_scene** out) {
+    const char* who = "tbvh_build_device_custom_spheres_sah";
+    if (!c || !spheres16 || !out || !n) return fail(TBVH_E_INVALID, "%s: null/empty argument", who);
+    if (n > 0x3fffffffull) return fail(TBVH_E_INVALID, "%s: %llu spheres: at most 2^30 - 1", who, (unsigned long long)n);
+    if (maxLeaf > 4u) return fail(TBVH_E_INVALID, "%s: %u spheres per leaf (1..4; 0 = the leaves BVH::Build makes)", who, maxLeaf);
+    TBVH_ENTER(c);
+    tbvh_scene* s = newScene(c, TBVH_LAYOUT_BVH2_WALD);
+    if (!s) return fail(TBVH_E_NOMEM, "out of host memory");
+    s->sphN = n; s->sphBuilder = 2; s->sphMaxLeaf = maxLeaf;
+    const float4* dSph = nullptr;
+    int r = stageSpheres(s, who, spheres16, n, onDevice, &dSph);
+    if (!r) r = buildSphereTree(s, who, dSph, n);
     if (r) { tbvh_free_scene(s); return r; }
     *out = s;
     return 0;

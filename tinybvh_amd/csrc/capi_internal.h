@@ -164,6 +164,7 @@ struct tbvh_context {
     std::vector<PinnedRange> pinned;
     DevBuf<void> binScratch;      // tbvh_bin_rays_device
     uint32_t sahSmallSubtree = 64;   // (sahbuild.h: kSahSmallSubtreeDefault) tbvh_debug_set_sah_small_subtree
+    uint32_t sahOneGroup = 3000;     // (sahbuild.h: kSahOneGroupDefault) tbvh_debug_set_sah_one_group
     std::vector<tbvh_scene*> scenes;
     std::vector<struct tbvh_pose*> poses;   // (capi_pose.hip) the poses made on this context: tbvh_shutdown frees those the caller has not
     std::vector<struct tbvh_scenegraph*> graphs;   // (capi_scenegraph.hip) likewise the scene graphs
@@ -270,6 +271,13 @@ struct tbvh_scene {
     DevBuf<uint32_t> tlas8Refs;       // instance references: the same number
     // device-side TLAS rebuild (kernels_tlasbuild.hip)
     DevBuf<float> blasBounds;         // 6 floats per BLAS
+    // tbvh_tlas_set_builder: 0 = LBVH, 2 = the reference's SAH tree (kernels_sahbuild.hip over the instance records, then the device Aila-Laine encode).
+    // The SAH build keeps its Wald nodes (2 n) and its scratch here, sized for tlasSahFor instances: no allocation per frame; `bytes` counts them.
+    int tlasBuilder = 0;
+    DevBuf<float4> tlasWald;
+    DevBuf<void> tlasSah;
+    uint64_t tlasSahFor = 0;
+    size_t tlasSahSort = 0, tlasSahScan = 0;
     DevBuf<float> xformStage;         // staged transforms (16 floats per instance) when the caller passes host memory
     // BLAS <-> TLAS references: a TLAS snapshots its BLASes' device pointers (BlasDesc), so a BLAS knows the TLASes that
     // use it (their descriptors are refreshed when its opacity maps change) and outlives them (tbvh_free_scene on a BLAS
@@ -304,7 +312,7 @@ struct tbvh_scene {
     // (sized for buildScratchFor spheres) and its primIdx here, the refit its pass words in refitScratch, host spheres are staged in vertStage: no
     // allocation per frame; `bytes` counts them all.
     uint64_t sphN = 0;
-    int sphBuilder = 0;                  // 0 LBVH, 1 PLOC
+    int sphBuilder = 0;                  // 0 LBVH, 1 PLOC, 2 SAH (tbvh_build_device_custom_spheres_sah; sphMaxLeaf 0 = the leaves BVH::Build makes)
     uint32_t sphMaxLeaf = 1, sphRadius = 16;
     size_t scanTempBytes = 0;
     DevBuf<uint32_t> sphIdx;

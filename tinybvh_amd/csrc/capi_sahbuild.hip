@@ -17,6 +17,25 @@ int checkOutputs(const char* who, uint64_t need, uint64_t nTris, const void* nod
                     (unsigned long long)capNodes, (unsigned long long)capIdx);
     return 0;
 }
+
+// the host twin over a box source into the caller's arrays
+int hostBoxBuild(const char* who, const SahBoxes& boxes, uint64_t n, uint32_t maxLeaf, void* nodesOut, uint64_t capNodes, uint32_t* idxOut, uint64_t capIdx,
+                 uint64_t* nNodesOut) {
+    if (!boxes.data || !nNodesOut) return fail(TBVH_E_INVALID, "%s: null argument", who);
+    if (n == 0 || n > 0x3fffffffull) return fail(TBVH_E_INVALID, "%s: %llu primitives (1 .. 2^30 - 1)", who, (unsigned long long)n);
+    std::vector<Node2> nodes;
+    std::vector<uint32_t> idx;
+    try {
+        sah_build_host(boxes, (uint32_t)n, maxLeaf, nodes, idx);
+    } catch (const std::bad_alloc&) { return fail(TBVH_E_NOMEM, "%s: out of host memory", who); }
+    *nNodesOut = nodes.size();
+    if (int r = checkOutputs(who, nodes.size(), n, nodesOut, capNodes, idxOut, capIdx)) return r;
+    if (nodesOut) {
+        memcpy(nodesOut, nodes.data(), nodes.size() * sizeof(Node2));
+        memcpy(idxOut, idx.data(), idx.size() * 4);
+    }
+    return 0;
+}
 }  // namespace
 
 extern "C" {
@@ -59,7 +78,7 @@ int tbvh_build_bvh2_sah_device(tbvh_context* c, const tbvh_mesh* mesh, uint32_t 
     HIP_TRY(n2.alloc(nTris * 4)); HIP_TRY(idx.alloc(nTris)); HIP_TRY(scratch.alloc(scratchBytes));
     uint32_t nNodes = 0;
     HIP_TRY(timedBegin(c));
-    HIP_TRY(run_sah_build(dm.src, (uint32_t)nTris, maxLeafTris, c->sahSmallSubtree, n2, idx, scratch, sortTemp, scanTemp, c->status, c->stream, &nNodes));
+    HIP_TRY(run_sah_build(dm.src, (uint32_t)nTris, maxLeafTris, c->sahSmallSubtree, c->sahOneGroup, n2, idx, scratch, sortTemp, scanTemp, c->status, c->stream, &nNodes));
     HIP_TRY(timedEnd(c));
     if (int r = checkStatus(c)) return r;   // (a device-resident index that is not a vertex: TBVH_E_FORMAT)
     *nNodesOut = nNodes;
@@ -70,6 +89,87 @@ int tbvh_build_bvh2_sah_device(tbvh_context* c, const tbvh_mesh* mesh, uint32_t 
         HIP_TRY(hipMemcpyAsync(idxOut, idx, nTris * 4, kind, c->stream));
         HIP_TRY(hipStreamSynchronize(c->stream));
     }
+    return 0;
+}
+
+int tbvh_host_build_bvh2_sah_aabbs(const void* aabbs32, uint64_t n, uint32_t maxLeaf, void* nodesOut, uint64_t capNodes, uint32_t* idxOut, uint64_t capIdx,
+                                   uint64_t* nNodesOut) {
+    return hostBoxBuild("tbvh_host_build_bvh2_sah_aabbs", sah_boxes_aabbs(aabbs32), n, maxLeaf, nodesOut, capNodes, idxOut, capIdx, nNodesOut);
+}
+
+int tbvh_host_build_bvh2_sah_spheres(const void* spheres16, uint64_t n, uint32_t maxLeaf, void* nodesOut, uint64_t capNodes, uint32_t* idxOut, uint64_t capIdx,
+                                     uint64_t* nNodesOut) {
+    return hostBoxBuild("tbvh_host_build_bvh2_sah_spheres", sah_boxes_spheres(spheres16), n, maxLeaf, nodesOut, capNodes, idxOut, capIdx, nNodesOut);
+}
+
+int tbvh_host_build_tlas_sah(const void* instances192, uint64_t n, void* nodes64Out, uint64_t capNodes, uint32_t* idxOut, uint64_t capIdx, uint64_t* nNodesOut) {
+    const char* who = "tbvh_host_build_tlas_sah";
+    if (!instances192 || !nNodesOut) return fail(TBVH_E_INVALID, "%s: null argument", who);
+    if (n == 0 || n > 0x3fffffffull) return fail(TBVH_E_INVALID, "%s: %llu instances (1 .. 2^30 - 1)", who, (unsigned long long)n);
+    BVH2 bvh;
+    std::vector<NodeAL> al;
+    try {
+        sah_build_host(sah_boxes_instances(instances192), (uint32_t)n, 0, bvh.nodes, bvh.primIdx);
+        bvh.triCount = (uint32_t)n;
+        encode_bvh_gpu(bvh, al);   // (BVH_GPU::ConvertFrom: depth-first pre-order, the pad node 1 not emitted)
+    } catch (const std::bad_alloc&) { return fail(TBVH_E_NOMEM, "%s: out of host memory", who); }
+    *nNodesOut = al.size();
+    if (int r = checkOutputs(who, al.size(), n, nodes64Out, capNodes, idxOut, capIdx)) return r;
+    if (nodes64Out) {
+        memcpy(nodes64Out, al.data(), al.size() * sizeof(NodeAL));
+        memcpy(idxOut, bvh.primIdx.data(), bvh.primIdx.size() * 4);
+    }
+    return 0;
+}
+
+int tbvh_build_bvh2_sah_device_aabbs(tbvh_context* c, const void* aabbs32, uint64_t n, int onDevice, uint32_t maxLeaf, void* nodesOut, uint64_t capNodes,
+                                     uint32_t* idxOut, uint64_t capIdx, int outOnDevice, uint64_t* nNodesOut) {
+    const char* who = "tbvh_build_bvh2_sah_device_aabbs";
+    if (!c || !aabbs32 || !nNodesOut) return fail(TBVH_E_INVALID, "%s: null argument", who);
+    if (n == 0 || n > 0x3fffffffull) return fail(TBVH_E_INVALID, "%s: %llu boxes (1 .. 2^30 - 1)", who, (unsigned long long)n);
+    if (onDevice && ((uintptr_t)aabbs32 & 3)) return fail(TBVH_E_INVALID, "%s: device boxes must be 4-byte aligned", who);
+    if (nodesOut && outOnDevice && (((uintptr_t)nodesOut & 15) || ((uintptr_t)idxOut & 3)))
+        return fail(TBVH_E_INVALID, "%s: device outputs must be 16-byte (nodes) and 4-byte (indices) aligned", who);
+    TBVH_ENTER(c);
+    DevBuf<float4> n2, staged;
+    DevBuf<uint32_t> idx;
+    DevBuf<void> scratch;
+    const void* dBoxes = aabbs32;
+    if (!onDevice) {
+        HIP_TRY(staged.alloc(n * 2));
+        HIP_TRY(hipMemcpyAsync(staged, aabbs32, n * 32, hipMemcpyHostToDevice, c->stream));
+        dBoxes = staged.get();
+    }
+    size_t sortTemp = 0, scanTemp = 0;
+    const size_t scratchBytes = sah_scratch_bytes((uint32_t)n, &sortTemp, &scanTemp);
+    HIP_TRY(n2.alloc(n * 4)); HIP_TRY(idx.alloc(n)); HIP_TRY(scratch.alloc(scratchBytes));
+    uint32_t nNodes = 0;
+    HIP_TRY(timedBegin(c));
+    HIP_TRY(run_sah_build(SahSrc(sah_boxes_aabbs(dBoxes)), (uint32_t)n, maxLeaf, c->sahSmallSubtree, c->sahOneGroup, n2, idx, scratch, sortTemp, scanTemp, c->status,
+                          c->stream, &nNodes));
+    HIP_TRY(timedEnd(c));
+    *nNodesOut = nNodes;
+    if (int r = checkOutputs(who, nNodes, n, nodesOut, capNodes, idxOut, capIdx)) return r;
+    if (nodesOut) {
+        const hipMemcpyKind kind = outOnDevice ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+        HIP_TRY(hipMemcpyAsync(nodesOut, n2, (size_t)nNodes * 32, kind, c->stream));
+        HIP_TRY(hipMemcpyAsync(idxOut, idx, n * 4, kind, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+    }
+    return 0;
+}
+
+int tbvh_debug_set_sah_one_group(tbvh_context* c, uint32_t n) {
+    if (!c) return fail(TBVH_E_INVALID, "tbvh_debug_set_sah_one_group: null argument");
+    TBVH_LOCK(c);
+    c->sahOneGroup = n;
+    return 0;
+}
+
+int tbvh_debug_get_sah_thresholds(tbvh_context* c, uint32_t out[2]) {
+    if (!c || !out) return fail(TBVH_E_INVALID, "tbvh_debug_get_sah_thresholds: null argument");
+    TBVH_LOCK(c);
+    out[0] = c->sahSmallSubtree; out[1] = c->sahOneGroup;
     return 0;
 }
 

@@ -541,7 +541,7 @@ int buildDeviceImpl(const char* who, tbvh_context* c, const tbvh_mesh& mesh, int
     HIP_TRY(timedBegin(c));
     if (builder == 2) {
         uint32_t nNodes = 0;
-        HIP_TRY(run_sah_build(dm.src, (uint32_t)nTris, maxLeafTris, c->sahSmallSubtree, n2, idx, scratch, sortTemp, scanTemp, c->status, c->stream, &nNodes));
+        HIP_TRY(run_sah_build(dm.src, (uint32_t)nTris, maxLeafTris, c->sahSmallSubtree, c->sahOneGroup, n2, idx, scratch, sortTemp, scanTemp, c->status, c->stream, &nNodes));
         scratch.reset();
         int r = convertDeviceImpl(c, layout, n2, nNodes, idx, nTris, dm.src, out);
         HIP_TRY(timedEnd(c));
@@ -784,12 +784,42 @@ int tbvh_rebuild_tlas_device(tbvh_scene* s, const void* transforms, int onDevice
             xf = s->xformStage;
         }
     }
+    if (s->tlasBuilder == 2) {
+        if (n > 0x3fffffffull) return fail(TBVH_E_INVALID, "tbvh_rebuild_tlas_device: %llu instances: the SAH builder takes at most 2^30 - 1", (unsigned long long)n);
+        if (s->tlasSahFor != n) {
+            s->tlasSahFor = 0;
+            HIP_TRY(s->tlasSah.alloc(sah_scratch_bytes((uint32_t)n, &s->tlasSahSort, &s->tlasSahScan)));
+            HIP_TRY(s->tlasWald.alloc(n * 4));
+            s->tlasSahFor = n;
+        }
+        // the existing instance update, the reference's BVH::Build( BLASInstance*, n ) over the updated records, BVH_GPU::ConvertFrom: all on the stream
+        HIP_TRY(timedBegin(c));
+        HIP_TRY(launch_tlas_instance_update(s->instances, xf, s->blasBounds, (uint32_t)n, (uint32_t)s->nBlas, s->buildScratch, s->sortTempBytes, c->stream));
+        uint32_t nWald = 0;
+        HIP_TRY(run_sah_build(SahSrc(sah_boxes_instances(s->instances.get())), (uint32_t)n, 0, c->sahSmallSubtree, c->sahOneGroup, s->tlasWald, s->tlasIdx, s->tlasSah,
+                              s->tlasSahSort, s->tlasSahScan, c->status, c->stream, &nWald));
+        HIP_TRY(run_al_encode(s->tlasWald, nWald, (uint32_t)n, s->tlasSah, s->tlasSahSort, s->tlasSahScan, s->nodes, c->stream));
+        s->nTlasNodes = nWald - 1; s->nTlasIdx = n;
+        s->bytes = s->nTlasNodes * 64 + n * 4 + n * 192 + s->tlasSah.count() + s->tlasWald.count() * 16;
+        if (int r = buildTlas4(s)) return r;
+        HIP_TRY(timedEnd(c));
+        return 0;
+    }
     HIP_TRY(timedBegin(c));
     HIP_TRY(launch_tlas_rebuild(s->nodes, s->tlasIdx, s->instances, xf, s->blasBounds, (uint32_t)n, (uint32_t)s->nBlas, s->buildScratch, s->sortTempBytes, c->stream));
     s->bytes = nNodes * 64 + n * 4 + n * 192;
     s->nTlasNodes = nNodes; s->nTlasIdx = n;
     if (int r = buildTlas4(s)) return r;
     HIP_TRY(timedEnd(c));
+    return 0;
+}
+
+int tbvh_tlas_set_builder(tbvh_scene* s, int builder) {
+    TBVH_REFUSE_DOUBLE(s, "tbvh_tlas_set_builder");
+    if (!s || !s->isTlas) return fail(TBVH_E_INVALID, "tbvh_tlas_set_builder: not a TLAS");
+    if (builder != 0 && builder != 2) return fail(TBVH_E_INVALID, "tbvh_tlas_set_builder: builder %d (0 = LBVH, 2 = the reference's SAH tree)", builder);
+    TBVH_LOCK(s->ctx);
+    s->tlasBuilder = builder;
     return 0;
 }
 

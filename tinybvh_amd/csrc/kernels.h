@@ -121,6 +121,8 @@ void launch_tlas_custom(bool anyhit, int blasLayout, const float4* tlasNodes, co
 
 // device TLAS rebuild (kernels_tlasbuild.hip)
 size_t tlas_build_scratch_bytes(uint32_t n, size_t* sortTempBytes);
+hipError_t launch_tlas_instance_update(float4* instances, const float* transformsDev, const float* blasBoundsDev, uint32_t n, uint32_t nBlas, void* scratch,
+                                       size_t sortTempBytes, hipStream_t s);   // the first step of launch_tlas_rebuild alone
 hipError_t launch_tlas_rebuild(float4* tlasNodes, uint32_t* tlasIdx, float4* instances, const float* transformsDev, const float* blasBoundsDev,
                                uint32_t n, uint32_t nBlas, void* scratch, size_t sortTempBytes, hipStream_t s);
 // LBVH build on the device (kernels_build.hip)

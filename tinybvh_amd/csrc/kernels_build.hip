@@ -19,6 +19,7 @@
 #include "cwbvh_encode.h"
 #include "device_common.h"
 #include "kernels.h"
+#include "sah_split.h"
 
 namespace tbvh {
 
@@ -76,7 +77,10 @@ __global__ void k_sphere_boxes(const float4* __restrict__ spheres, uint32_t n, f
     float3 cmn = make_float3(1e30f, 1e30f, 1e30f), cmx = make_float3(-1e30f, -1e30f, -1e30f);
     for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
         const float4 p = spheres[i];
-        const float3 mn = make_float3(p.x - p.w, p.y - p.w, p.z - p.w), mx = make_float3(p.x + p.w, p.y + p.w, p.z + p.w);
+        const float s4[4] = {p.x, p.y, p.z, p.w};
+        float lo[3], hi[3];
+        sah::sphere_box(s4, lo, hi);   // (the one definition of a sphere's box: the SAH builder's fragments and the refit use it too)
+        const float3 mn = make_float3(lo[0], lo[1], lo[2]), mx = make_float3(hi[0], hi[1], hi[2]);
         triMin[i] = make_float4(mn.x, mn.y, mn.z, 0.f); triMax[i] = make_float4(mx.x, mx.y, mx.z, 0.f);
         const float3 c = make_float3(0.5f * (mn.x + mx.x), 0.5f * (mn.y + mx.y), 0.5f * (mn.z + mx.z));
         cmn = min3(cmn, c); cmx = max3(cmx, c);

@@ -15,6 +15,7 @@
 
 #include "device_common.h"
 #include "kernels.h"
+#include "sah_split.h"
 
 namespace tbvh {
 
@@ -45,7 +46,10 @@ __global__ void k_sphere_refit_leaves(float4* __restrict__ nodes32, uint32_t nNo
         if (prim >= nSpheres) continue;
         const float4 p = spheres[prim];
         r[0] = p;
-        const float3 lo = make_float3(p.x - p.w, p.y - p.w, p.z - p.w), hi = make_float3(p.x + p.w, p.y + p.w, p.z + p.w);
+        const float s4[4] = {p.x, p.y, p.z, p.w};
+        float bl[3], bh[3];
+        sah::sphere_box(s4, bl, bh);   // (sah_split.h: the box the builders gave this sphere, bit for bit)
+        const float3 lo = make_float3(bl[0], bl[1], bl[2]), hi = make_float3(bh[0], bh[1], bh[2]);
         mn = any ? make_float3(fminf(mn.x, lo.x), fminf(mn.y, lo.y), fminf(mn.z, lo.z)) : lo;
         mx = any ? make_float3(fmaxf(mx.x, hi.x), fmaxf(mx.y, hi.y), fmaxf(mx.z, hi.z)) : hi;
         any = true;

@@ -292,4 +292,16 @@ hipError_t launch_tlas_rebuild(float4* tlasNodes, uint32_t* tlasIdx, float4* ins
     return hipGetLastError();
 }
 
+// the instance update alone (the first step above), for a rebuild whose tree another builder makes (capi_scene.hip: the SAH TLAS, DESIGN.md par. 20)
+hipError_t launch_tlas_instance_update(float4* instances, const float* transformsDev, const float* blasBoundsDev, uint32_t n, uint32_t nBlas, void* scratch,
+                                       size_t sortTempBytes, hipStream_t s) {
+    const Scratch sc = carve(scratch, n, sortTempBytes);
+    hipError_t e;
+    if ((e = hipMemsetAsync(sc.bounds, 0xff, 12, s)) != hipSuccess) return e;
+    if ((e = hipMemsetAsync(sc.bounds + 3, 0x00, 12, s)) != hipSuccess) return e;
+    const uint32_t bs = 128, nb = (n + bs - 1) / bs;
+    hipLaunchKernelGGL(k_instance_update, dim3(nb), dim3(bs), 0, s, instances, transformsDev, blasBoundsDev, n, nBlas, sc.instMin, sc.instMax, sc.bounds);
+    return hipGetLastError();
+}
+
 }  // namespace tbvh

@@ -63,6 +63,11 @@ SAH_HD void fragment_box(const float v0[3], const float v1[3], const float v2[3]
     for (int k = 0; k < 3; k++) { mn[k] = min_ref(v0[k], min_ref(v1[k], v2[k])); mx[k] = max_ref(v0[k], max_ref(v1[k], v2[k])); }
 }
 
+// the demos' sphereAABB for a record {x, y, z, r}: pos - bvhvec3( r ), pos + bvhvec3( r ), one rounding each (r <= 0 gives an inverted or empty box)
+SAH_HD void sphere_box(const float s[4], float mn[3], float mx[3]) {
+    for (int k = 0; k < 3; k++) { mn[k] = s[k] - s[3]; mx[k] = s[k] + s[3]; }
+}
+
 SAH_HD float half_area(float x, float y, float z) { return x < -kFar ? 0.f : fma1(z, x, fma1(x, y, y * z)); }
 
 // rpd3 = bvhvec3( BVHBINS ) / (node.aabbMax - node.aabbMin) (2362)
@@ -85,11 +90,17 @@ struct Split {
 // The per-axis sweep and the termination test (2378-2412).  B: bins.mn( a, i, k ), bins.mx( a, i, k ), bins.count( a, i ) — empty bins hold
 // +/- BVH_FAR and 0.  minDim = (rootMax - rootMin) * 1e-20f.  false: not splitting is better (splitCost >= noSplitCost); the caller still
 // makes a leaf when one side would be empty (2425).  The strict C < splitCost lets the first axis, then the first bin, win ties.
+// A sweep in which NO candidate beat BVH_FAR — every axis behind the minDim gate, or every cost infinite — can still pass the termination test when the
+// node's area is so large that rSAV * BVH_FAR is small (extents beyond 1e14): the reference then splits at axis 0, bin 0 and gives the children
+// bestLMin .. bestRMax as an EARLIER node's sweep left them (2350: they live outside the loop).  first = this is the first node the reference
+// evaluates (the root): they still hold their initial zeros, which is what the children get here.  For any later node they depend on the order of the
+// sequential walk and are not reproduced: the children get the boxes of bin 0 and of bins 1 .. 7 on axis 0.
 template <class B>
-SAH_HD bool find_split(const B& bins, const float nmin[3], const float nmax[3], const float minDim[3], uint32_t triCount, Split& s) {
+SAH_HD bool find_split(const B& bins, const float nmin[3], const float nmax[3], const float minDim[3], uint32_t triCount, bool first, Split& s) {
     float splitCost = kFar;
     const float rSAV = 1.0f / half_area(nmax[0] - nmin[0], nmax[1] - nmin[1], nmax[2] - nmin[2]);   // (BVHBase::SA: no BVH_FAR test, and an extent is never below it)
     uint32_t bestAxis = 0, bestPos = 0;
+    bool found = false;
     for (int a = 0; a < 3; a++) if ((nmax[a] - nmin[a]) > minDim[a]) {
         // right-to-left: ANR[i] = area x count of bins i + 1 .. 7
         float ANR[kBins - 1];
@@ -110,7 +121,7 @@ SAH_HD bool find_split(const B& bins, const float nmin[3], const float nmax[3], 
             lN += bins.count(a, i);
             const float ANL = lN == 0 ? kFar : (half_area(l2[0] - l1[0], l2[1] - l1[1], l2[2] - l1[2]) * (float)lN);
             const float C = ANL + ANR[i];
-            if (C < splitCost) splitCost = C, bestAxis = (uint32_t)a, bestPos = (uint32_t)i;
+            if (C < splitCost) splitCost = C, bestAxis = (uint32_t)a, bestPos = (uint32_t)i, found = true;
         }
     }
     splitCost = fma1(1.0f * rSAV, splitCost, 1.0f);
@@ -118,6 +129,10 @@ SAH_HD bool find_split(const B& bins, const float nmin[3], const float nmax[3], 
     if (splitCost >= noSplitCost) return false;
     // the child boxes are the sweep's own prefix / suffix boxes at the winning position (2402), taken again in the same order
     s.axis = bestAxis; s.pos = bestPos;
+    if (!found && first) {
+        for (int k = 0; k < 3; k++) s.lmin[k] = s.lmax[k] = s.rmin[k] = s.rmax[k] = 0.f;
+        return true;
+    }
     for (int k = 0; k < 3; k++) { s.lmin[k] = kFar; s.lmax[k] = -kFar; s.rmin[k] = kFar; s.rmax[k] = -kFar; }
     for (int i = 0; i <= (int)bestPos; i++)
         for (int k = 0; k < 3; k++) { s.lmin[k] = min_ref(s.lmin[k], bins.mn(bestAxis, i, k)); s.lmax[k] = max_ref(s.lmax[k], bins.mx(bestAxis, i, k)); }

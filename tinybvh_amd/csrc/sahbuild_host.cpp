@@ -25,17 +25,15 @@ struct HostBins {
 };
 }  // namespace
 
-uint32_t sah_build_host(const HostMesh& mesh, uint32_t nTris, uint32_t maxLeafTris, std::vector<Node2>& nodes, std::vector<uint32_t>& primIdx) {
-    nodes.clear(); primIdx.clear();
-    if (nTris == 0) return 0;
-    std::vector<float> fmn((size_t)nTris * 3), fmx((size_t)nTris * 3);
+// Build() over filled fragments: everything after the fragment step (the root box included, taken in the order of sah::key)
+static uint32_t build_fragments(const std::vector<float>& fmn, const std::vector<float>& fmx, uint32_t nTris, uint32_t maxLeafTris, std::vector<Node2>& nodes,
+                                std::vector<uint32_t>& primIdx) {
     nodes.assign((size_t)nTris * 2, Node2{});   // (node 1 stays zero)
     primIdx.resize(nTris);
     Node2& root = nodes[0];
     for (int k = 0; k < 3; k++) root.mn[k] = sah::kFar, root.mx[k] = -sah::kFar;
     root.leftFirst = 0; root.triCount = nTris;
     for (uint32_t i = 0; i < nTris; i++) {
-        sah::fragment_box(mesh.xyz(i, 0), mesh.xyz(i, 1), mesh.xyz(i, 2), &fmn[3 * (size_t)i], &fmx[3 * (size_t)i]);
         for (int k = 0; k < 3; k++) {
             root.mn[k] = sah::min_ord(root.mn[k], fmn[3 * (size_t)i + k]);
             root.mx[k] = sah::max_ord(root.mx[k], fmx[3 * (size_t)i + k]);
@@ -66,7 +64,7 @@ uint32_t sah_build_host(const HostMesh& mesh, uint32_t nTris, uint32_t maxLeafTr
                 }
             }
             sah::Split s;
-            if (!sah::find_split(bins, node.mn, node.mx, minDim, node.triCount, s)) break;
+            if (!sah::find_split(bins, node.mn, node.mx, minDim, node.triCount, nodeIdx == 0, s)) break;
             const uint32_t leftCount = sah::left_count(bins, s), rightCount = node.triCount - leftCount;
             if (leftCount == 0 || rightCount == 0) break;
             // partition: the order inside the two halves is free (the leaves are sorted at the end)
@@ -126,6 +124,26 @@ uint32_t sah_build_host(const HostMesh& mesh, uint32_t nTris, uint32_t maxLeafTr
     }
     nodes.resize(used);
     return used;
+}
+
+uint32_t sah_build_host(const HostMesh& mesh, uint32_t nTris, uint32_t maxLeafTris, std::vector<Node2>& nodes, std::vector<uint32_t>& primIdx) {
+    nodes.clear(); primIdx.clear();
+    if (nTris == 0) return 0;
+    std::vector<float> fmn((size_t)nTris * 3), fmx((size_t)nTris * 3);
+    for (uint32_t i = 0; i < nTris; i++) sah::fragment_box(mesh.xyz(i, 0), mesh.xyz(i, 1), mesh.xyz(i, 2), &fmn[3 * (size_t)i], &fmx[3 * (size_t)i]);
+    return build_fragments(fmn, fmx, nTris, maxLeafTris, nodes, primIdx);
+}
+
+uint32_t sah_build_host(const SahBoxes& boxes, uint32_t n, uint32_t maxLeaf, std::vector<Node2>& nodes, std::vector<uint32_t>& primIdx) {
+    nodes.clear(); primIdx.clear();
+    if (n == 0) return 0;
+    std::vector<float> fmn((size_t)n * 3), fmx((size_t)n * 3);
+    for (uint32_t i = 0; i < n; i++) {
+        const float* rec = boxes.data + (size_t)i * boxes.stride;
+        if (boxes.spheres) sah::sphere_box(rec, &fmn[3 * (size_t)i], &fmx[3 * (size_t)i]);
+        else for (int k = 0; k < 3; k++) { fmn[3 * (size_t)i + k] = rec[boxes.offMin + k]; fmx[3 * (size_t)i + k] = rec[boxes.offMax + k]; }
+    }
+    return build_fragments(fmn, fmx, n, maxLeaf, nodes, primIdx);
 }
 
 }  // namespace tbvh
