@@ -151,6 +151,59 @@ def test_restated_tlas_traversal_equals_the_reference(oracle_ref, reference):
     assert np.array_equal(got["inst"][same], want["inst"][same])
 
 
+def test_restated_tlas_traversal_equals_the_reference_on_hostile_instances(oracle_ref, reference):
+    """orc_tlas_intersect against the real BVH::IntersectTLAS on the instance families and ray groups of tests/tlas_edges_lib.py (mirrored, exactly
+    axis-aligned, strongly anisotropic, sheared and PROJECTIVE transforms: the oracle's w != 1 branch; duplicated and masked instances), with
+    tmax = 1e30, a finite tmax and carried-in records.  This is what entitles tests/test_tlas_edges_gpu.py to take the oracle for the reference there."""
+    import ctypes as C
+    from oracle_lib import tlas_intersect
+    import tlas_edges_lib as E
+    vs = E.meshes()
+    rs = [reference.build(v, hq=False, threaded=False) for v in vs]
+    inst, names = E.families(len(vs))
+    arr = (C.c_void_p * len(rs))(*[r.h for r in rs])
+    t = reference.lib.ref_tlas_build(C.c_void_p(inst.ctypes.data), inst.shape[0], arr, len(rs))     # (BLASInstance::Update fills inst)
+    mine = E.fill_instances(E.families(len(vs))[0], E.mesh_bounds(vs))
+    for f in ("invTransform", "aabbMin", "aabbMax"):
+        assert np.array_equal(mine[f].view(np.uint32), inst[f].view(np.uint32)), f
+    p = C.c_void_p()
+    nn = reference.lib.ref_tlas_blob(t, 2, C.byref(p)); nodes = np.frombuffer((C.c_char * (nn * 32)).from_address(p.value), np.uint32).reshape(-1, 8).copy()
+    ni = reference.lib.ref_tlas_blob(t, 1, C.byref(p)); idx = np.frombuffer((C.c_char * (ni * 4)).from_address(p.value), np.uint32).copy()
+    bl = [(r.blob(1, 0, np.uint32, 8), r.blob(1, 1, np.uint32, 1).reshape(-1), v) for r, v in zip(rs, vs)]
+    rays, groups = E.ray_groups(inst, dict(enumerate(vs)))
+    tmax = np.float32(0.3 * E.scene_diagonal(inst))
+    finite = rays.copy(); finite["t"] = tmax
+    try:
+        first = None
+        for label, batch in (("far", rays), ("finite", finite), ("carried", E.carried(rays, tmax)), ("retrace", None)):
+            if batch is None:       # the first result's hit distance as tmax, the rest of the record junk
+                batch = first.copy(); batch["u"] = 7.0; batch["v"] = -3.0; batch["prim"] = 12345; batch["inst"] = 0xDEAD
+            want = np.ascontiguousarray(batch).copy()
+            reference.lib.ref_tlas_intersect(t, C.c_void_p(want.ctypes.data), want.shape[0], want.strides[0])
+            got = tlas_intersect(oracle_ref, nodes, idx, inst, bl, batch)
+            if first is None:
+                first = want
+            # compare_hits takes t < 1e30 for a hit: the records that changed are the hits here
+            hit_w, hit_g = E.differing(want, batch), E.differing(got, batch)
+            assert np.array_equal(hit_w, hit_g), (label, hit_w.size, hit_g.size)
+            c = compare_hits(got[hit_w], want[hit_w])
+            print(label, "hits", hit_w.size, "bit-identical", c["bit_identical"], "same prim", c["same_prim"], "ties", c["tie"])
+            assert c["hitmiss"] == 0 and c["prim_real"] == 0 and c["t_bad"] == 0 and c["uv_bad"] == 0, (label, c)
+            same = (got["prim"] == want["prim"]) & (got["t"] == want["t"])
+            assert np.array_equal(got["inst"][same], want["inst"][same]), label
+            miss = np.setdiff1d(np.arange(batch.shape[0]), hit_w)
+            assert np.array_equal(E.bytes_of(got[miss]), E.bytes_of(batch[miss])) and np.array_equal(E.bytes_of(want[miss]), E.bytes_of(batch[miss])), label
+            if label != "retrace":
+                assert hit_w.size > 300 and miss.size > 300, (label, hit_w.size, miss.size)
+            if label == "far":      # every family but the masked-out one is hit, the projective one included
+                hit_inst = set(want["inst"][hit_w].tolist())
+                assert hit_inst >= set(range(inst.shape[0])) - {names.index("mask_none"), names.index("dup0"), names.index("dup1")}, sorted(hit_inst)
+                assert names.index("mask_none") not in hit_inst and hit_inst & {names.index("dup0"), names.index("dup1")}
+                assert hit_w[groups["mask0"].start <= hit_w].size == 0      # (the mask-0 group is last)
+    finally:
+        reference.lib.ref_tlas_free(t)
+
+
 def random_opmap(n_tris, N, seed, density=0.6):
     rng = np.random.default_rng(seed)
     wpt = (N * N + 31) // 32
