@@ -128,6 +128,17 @@ int tbvh_debug_host_scenegraph_set_trs(struct tbvh_host_scenegraph* g, const flo
  * the lists sg_compile builds and their range checks are exercised without a GPU (tools/scenegraph_sanitize.cpp, tests/test_scenegraph_host.py). */
 int tbvh_debug_host_scenegraph_check_chains(struct tbvh_host_scenegraph* g, uint64_t* n_differ);
 
+/* The queues of a wavefront object as they stand after its last tbvh_wavefront_render, copied to the host so that a test can hold every path vertex to a
+ * restatement (tests/test_wavefront_paths_gpu.py).  Not for products: the queues are the path tracer's private state.  Every buffer takes width x height
+ * records (the capacity; the counters say how many are live) and may be NULL: rays0 / rays1 the two path queues (64-byte ray records), aux0 / aux1 their
+ * PathAux (16 bytes: throughput, pixel << 8 | depth << 4 | flags), shadow / shadow_aux the shadow queue (16 bytes: contribution, pixel), occ its any-hit
+ * flags (one byte each).  counters[d] = entries of the path queue depth d read (d = 0 .. 8), counters[9 + d] = entries of the shadow queue depth d filled.
+ * After a render with max_depth K: rays[(K - 1) & 1] is the input of the last Shade with Extend's hit records; for K >= 2 rays[(K - 2) & 1] is the input of
+ * the Shade before it (the last stage writes no bounce rays); the shadow queue and occ are stage K - 1's.  Synchronizes the stream, changes nothing on the
+ * device.  Call it BEFORE tbvh_wavefront_finalize: that reuses the shadow-ray buffer for its pixels. */
+int tbvh_debug_wavefront_queues(tbvh_wavefront* w, void* rays0, void* aux0, void* rays1, void* aux1, void* shadow, void* shadow_aux, uint8_t* occ,
+                                uint64_t counters[18]);
+
 #ifdef __cplusplus
 }
 #endif

@@ -77,7 +77,7 @@ def test_frame_against_host_recomputation(ctx, oracle):
     bad = np.abs(got - ref).max(1) > 1e-3 * (1 + np.abs(ref).max(1))
     assert bad.sum() <= n // 2000, int(bad.sum())
     assert abs(got.mean() - ref.mean()) < 1e-3 * ref.mean()
-    assert st["shadow_rays"][0] == int(((ndl > 0) & (dist > 2 * eps)).sum()) or abs(st["shadow_rays"][0] - int((ndl > 0).sum())) < 20
+    assert st["shadow_rays"][0] == int(((ndl > 0) & (dist > 2 * eps)).sum())      # (every decision held to the device's own: tests/test_wavefront_paths_gpu.py)
     wf.close(); ctx.free(d_verts)
 
 

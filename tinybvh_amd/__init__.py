@@ -36,6 +36,8 @@ RAY_DTYPE = np.dtype([
     ("t", "<f4"), ("u", "<f4"), ("v", "<f4"), ("prim", "<u4"),
 ])
 assert RAY_DTYPE.itemsize == 64
+# what rides beside a ray in the path tracer's queues (kernels.h: PathAux): throughput + pixel << 8 | depth << 4 | flags, or contribution + pixel
+PATH_AUX_DTYPE = np.dtype([("T", "<f4", 3), ("pixel", "<u4")])
 
 
 def safercp(x: np.ndarray) -> np.ndarray:
@@ -1051,6 +1053,18 @@ class Wavefront:
         """TLAS scenes: the device vertex array of every BLAS, in blasIdx order (tbvh_wavefront_set_blas_vertices)."""
         arr = (C.c_void_p * len(d_verts_per_blas))(*[int(p) for p in d_verts_per_blas])
         check(lib.tbvh_wavefront_set_blas_vertices(self._h, arr, len(d_verts_per_blas)), "tbvh_wavefront_set_blas_vertices")
+
+    def debug_queues(self) -> dict:
+        """The queues as the last render left them (tbvh_debug_wavefront_queues; a development aid, call it before finalize): "rays" / "aux" the two
+        path queues (RAY_DTYPE, PATH_AUX_DTYPE), "shadow" / "shadow_aux" / "occ" the shadow queue, "path_counts"[d] (d = 0 .. 8) and "shadow_counts"[d]
+        (d = 0 .. 7) the per-depth counters.  Arrays have the capacity width x height; the counters say how many entries are live."""
+        n = self.width * self.height
+        rays = [np.zeros(n, RAY_DTYPE) for _ in range(2)]; aux = [np.zeros(n, PATH_AUX_DTYPE) for _ in range(2)]
+        shadow = np.zeros(n, RAY_DTYPE); shadow_aux = np.zeros(n, PATH_AUX_DTYPE); occ = np.zeros(n, np.uint8); cnt = np.zeros(18, np.uint64)
+        check(lib.tbvh_debug_wavefront_queues(self._h, _ptr(rays[0]), _ptr(aux[0]), _ptr(rays[1]), _ptr(aux[1]), _ptr(shadow), _ptr(shadow_aux), _ptr(occ), _ptr(cnt)),
+              "tbvh_debug_wavefront_queues")
+        return {"rays": rays, "aux": aux, "shadow": shadow, "shadow_aux": shadow_aux, "occ": occ,
+                "path_counts": [int(x) for x in cnt[:9]], "shadow_counts": [int(x) for x in cnt[9:17]]}
 
     def finalize(self, scale: float = 1.0) -> np.ndarray:
         """Finalize of wavefront.cl:275-286: (height, width) uint32 0x00RRGGBB."""

@@ -122,6 +122,7 @@ SYMBOLS = {
     "tbvh_intersect_sharded_device": (_i, [_vp, _u32, _vp, _vp, _i, C.c_float, _vp, _vp]),
     "tbvh_occluded_sharded_device": (_i, [_vp, _u32, _vp, _vp, _vp, _vp, _vp]),
     "tbvh_wavefront_set_band": (_i, [_vp, _u32, _u32]),
+    "tbvh_debug_wavefront_queues": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "tbvh_wavefront_render_sharded": (_i, [_vp, _vp, _vp, _u32, C.POINTER(Camera), _vp, _vp, _vp]),
     "tbvh_wavefront_read_sharded": (_i, [_vp, _u32, _vp]),
     "tbvh_shard_range": (None, [_u64, _u32, _u32, C.POINTER(_u64), C.POINTER(_u64)]),

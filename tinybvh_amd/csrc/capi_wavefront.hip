@@ -238,6 +238,27 @@ int tbvh_wavefront_read(tbvh_wavefront* w, float* rgba) {
     return 0;
 }
 
+int tbvh_debug_wavefront_queues(tbvh_wavefront* w, void* rays0, void* aux0, void* rays1, void* aux1, void* shadow, void* shadowAux, uint8_t* occ,
+                                uint64_t counters[18]) {
+    if (!w) return fail(TBVH_E_INVALID, "tbvh_debug_wavefront_queues: null wavefront");
+    TBVH_ENTER(w->ctx);
+    hipStream_t st = w->ctx->stream;
+    HIP_TRY(hipStreamSynchronize(st));
+    if (rays0) HIP_TRY(hipMemcpy(rays0, w->rays[0], w->n * sizeof(RayRec), hipMemcpyDeviceToHost));
+    if (aux0) HIP_TRY(hipMemcpy(aux0, w->aux[0], w->n * sizeof(PathAux), hipMemcpyDeviceToHost));
+    if (rays1) HIP_TRY(hipMemcpy(rays1, w->rays[1], w->n * sizeof(RayRec), hipMemcpyDeviceToHost));
+    if (aux1) HIP_TRY(hipMemcpy(aux1, w->aux[1], w->n * sizeof(PathAux), hipMemcpyDeviceToHost));
+    if (shadow) HIP_TRY(hipMemcpy(shadow, w->shadow, w->n * sizeof(RayRec), hipMemcpyDeviceToHost));
+    if (shadowAux) HIP_TRY(hipMemcpy(shadowAux, w->shadowAux, w->n * sizeof(PathAux), hipMemcpyDeviceToHost));
+    if (occ) HIP_TRY(hipMemcpy(occ, w->occ, w->n, hipMemcpyDeviceToHost));
+    if (counters) {
+        std::vector<unsigned long long> h(kWfCounterWords);
+        HIP_TRY(hipMemcpy(h.data(), w->counters, (size_t)kWfCounterWords * 8, hipMemcpyDeviceToHost));
+        for (uint32_t k = 0; k < 18; k++) counters[k] = h[32u * k];
+    }
+    return 0;
+}
+
 int tbvh_wavefront_finalize(tbvh_wavefront* w, float scale, uint32_t* pixels) {
     if (!w || !pixels) return fail(TBVH_E_INVALID, "tbvh_wavefront_finalize: null argument");
     TBVH_ENTER(w->ctx);
