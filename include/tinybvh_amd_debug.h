@@ -68,6 +68,15 @@ int tbvh_debug_probe_memory_stats(tbvh_context* ctx, uint64_t out[2]);
  * 2 coherent, 0 nothing), read once that row is finished (operation 1). */
 int tbvh_debug_runahead_script(const uint64_t* ops6, uint64_t n_ops, int depth, int64_t* out2);
 
+/* What a query launch will do (tinybvh_amd/csrc/launch_plan.h: the functions launchQuery itself calls), from the facts it reads; no device, no context.
+ * facts: n_facts = 22 words {is TLAS, layout, variant, blob bytes, rays, the host knows the size, any hit, grid override, CUs, persistent grid, rays per
+ * block, debug flags, TBVH_COHERENT_TUNER's mode, the schedules settled for the four size classes, the scene has the padded node copy / the hybrid node copy /
+ * the 64-byte triangle records, probe memory on, timing off}.  out: n_out = 15 words {small, huge, probed, probedSmall, probedSmall cancelled by a per-lane
+ * schedule, size class, grid by size, grid of a coherent batch, 7-waves grid of the two-level kernels, of the BVH8_CWBVH kernels, a tuner may time it,
+ * solo candidate, wants a verdict slot, shape of a BVH8_CWBVH launch (0 one kernel, 1 two flavors, 2 flavor + unprobed kernel behind, 3 / 4 / 5 variant
+ * 90 / 91 / 92), padded node copy walked}.  TBVH_E_INVALID for other word counts or 0 rays per block. */
+int tbvh_debug_launch_plan(const uint64_t* facts, uint32_t n_facts, uint32_t* out, uint32_t n_out);
+
 /* The wave-packet kernel's child filter (tinybvh_amd/csrc/packet_cull.h) beside its exact per-lane test, for ONE 64-ray chunk against n_nodes BVH8_CWBVH nodes
  * (80 bytes each), on the host as k_cwbvh_packet runs them; no device, no context.  rays64: 64 ray records of 64 bytes (O, D, rD, hit; O and rD are read);
  * have_mask: bit l = lane l holds a ray (at least one); tcull64: each lane's cull distance as the kernel forms it (cull_bound(hit.t), -1 for a ray that is out

@@ -289,6 +289,21 @@ int tbvh_debug_runahead_script(const uint64_t* ops6, uint64_t nOps, int depth, i
     return 0;
 }
 
+// What launchQuery plans for a launch (launch_plan.h: the two functions it calls, in its order), from facts stated as words; no device, no scene
+// (tests/test_launch_plan_host.py).
+int tbvh_debug_launch_plan(const uint64_t* facts, uint32_t nFacts, uint32_t* out, uint32_t nOut) {
+    if (!facts || !out) return fail(TBVH_E_INVALID, "tbvh_debug_launch_plan: null argument");
+    if (nFacts != kLaunchFactWords || nOut != kLaunchPlanWords)
+        return fail(TBVH_E_INVALID, "tbvh_debug_launch_plan: %u facts and %u plan words (this library: %u and %u)", nFacts, nOut, kLaunchFactWords,
+                    kLaunchPlanWords);
+    const LaunchFacts f = launchFactsFromWords(facts);
+    if (!f.raysPerBlock) return fail(TBVH_E_INVALID, "tbvh_debug_launch_plan: raysPerBlock is 0");
+    LaunchPlan p = planBatch(f);
+    planShape(p, f);
+    launchPlanToWords(p, out);
+    return 0;
+}
+
 int tbvh_debug_set_overlap_depth(tbvh_context* c, int depth) {
     if (!c) return fail(TBVH_E_INVALID, "tbvh_debug_set_overlap_depth: null context");
     if (depth < 1 || depth > LaneBook::kMaxDepth) return fail(TBVH_E_INVALID, "tbvh_debug_set_overlap_depth: depth %d (1..%d)", depth, LaneBook::kMaxDepth);

@@ -61,7 +61,7 @@ static int ensureHybridOrder(tbvh_scene* s) {
 // BVH8_CWBVH scenes of the class that gets the per-launch coherence probe (48 - 384 MB of blobs: beyond the L2s, within reach of the Infinity
 // Cache) keep two derived copies for INCOHERENT batches (kernels_cwbvh.hip: PROBED == 2): the nodes in surface-area priority order with the
 // first kHybridPacked packed and the others one per 128-byte line (each with one of its triangles in the line's spare 48 bytes), and the
-// triangle records padded to 64 bytes.  Built LAZILY by the first launch that would use them (launchQuery: a batch of 2 M rays or more) — a
+// triangle records padded to 64 bytes.  Built LAZILY by the first launch that would use them (capi_query.hip: planLaunch, a `probed` batch) — a
 // scene that is only ever a BLAS under a TLAS, or only traced with small batches, never pays the 2.3 x memory and the host pass; that first
 // launch waits for the build (~0.1 s for 600 k nodes: the node array is read back, ordered on the host, scattered on the device).  Trees made
 // on the device (tbvh_convert_bvh2_device, tbvh_build_device) are in level order, which already is close to priority order: no renumbering.
@@ -123,7 +123,7 @@ void freeCopy(tbvh_scene* s, CopyKind kind) {
     tbvh_free_scene(w);   // (the opacity maps it read are the owner's: tbvh_scene::opmapOwn)
 }
 
-// The 8-wide copy of a BVH_GPU / BVH4_GPU scene, made LAZILY by the scene's first query of 1024 rays or more (launchQuery) — a BLAS
+// The 8-wide copy of a BVH_GPU / BVH4_GPU scene, made LAZILY by the scene's first query of 1024 rays or more (capi_query.hip: prepareScene) — a BLAS
 // that is only ever traced through a TLAS never pays for it — from what the scene keeps on the device: the blob is read back, the host turns it into a
 // Wald-layout BVH2 with leaves of at most 3 entries (host_builder.cpp: bvh_gpu_to_bvh2 in record mode / bvh4_gpu_to_bvh2), the device converter every
 // BVH8_CWBVH conversion uses collapses and encodes it in ITS record mode (kernels_convert.hip; the greedy collapse of MBVH<8>::ConvertFrom,

@@ -27,6 +27,7 @@
 #include "dev_buf.h"
 #include "host_builder.h"
 #include "kernels.h"
+#include "launch_plan.h"
 #include "overlap_lanes.h"
 #include "probe_memory.h"
 #include "ray_pool.h"
@@ -40,6 +41,7 @@ using tbvh_capi::kCopyWide8;
 
 static_assert(kLayoutBvhGpu == TBVH_LAYOUT_BVH_GPU && kLayoutBvh4Gpu == TBVH_LAYOUT_BVH4_GPU && kLayoutCwbvh == TBVH_LAYOUT_CWBVH,
               "kernels.h and the public header agree on the layout codes");
+static_assert(tbvh_capi::kPlanLayoutCwbvh == TBVH_LAYOUT_CWBVH, "launch_plan.h and the public header agree on BVH8_CWBVH's code");
 
 namespace tbvh_capi {
 int fail(int code, const char* fmt, ...);   // sets tbvh_last_error() of the calling thread, returns code

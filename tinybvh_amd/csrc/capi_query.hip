@@ -1,4 +1,5 @@
-// capi_query.hip — the query path: launchQuery (grid shape, schedule choice, kernel flavors), host-array staging, multi-device sharding, ray generators.
+// capi_query.hip — the query path: launchQuery and its steps (the plan of launch_plan.h carried out: lane, counter pool, probe, kernels), host-array
+// staging, multi-device sharding, ray generators.
 #include "capi_internal.h"
 
 using namespace tbvh;
@@ -198,139 +199,162 @@ int hostQuery(tbvh_scene* s, const char* raysIn, char* raysOut, uint64_t n, uint
     return 0;
 }
 
+// one counter area: the pool's partitions + the coherence-probe counters on their own line
+constexpr size_t kPoolWords = (size_t)(kPoolParts + 1) * kPoolCounterStride;
 
-// The two-level kernels: one per BLAS layout (and one for BVH8_CWBVH and BVH_GPU BLASes mixed), each walking the TLAS form made for it at upload.
-static void launchTlasKernels(tbvh_scene* s, QueryArgs& q, bool any, uint32_t blocks, hipStream_t st) {
-    tbvh_context* c = s->ctx;
-    const uint32_t blocks7 = (!c->gridOverride && blocks == c->blocks) ? (uint32_t)c->numCUs * 28u : blocks;   // the full grid of the kernels built for 7 waves per SIMD
-    // any-hit queries may have a class of their own (capi_scene.hip: reclassifyTlas)
-    const bool own = any && s->blasDescAny != nullptr;
-    const int layout = own ? s->blasLayoutAny : s->blasLayout;
-    const bool mix = own ? s->blasMixCw2Any : s->blasMixCw2;
-    const BlasDesc* desc = own ? s->blasDescAny : s->blasDesc;
-    if (s->blasSpheres) {   // sphere BLASes, alone or with triangle BLASes walked in their own layouts: the flat loop with the sphere step (kernels_tlas.hip)
-        q.spillStride = c->spillEntries / 2;   // 8-byte stack entries
-        launch_tlas_custom(any, layout, s->nodes, s->tlasIdx, s->instances, desc, q, c->status, blocks, st);
-    } else if (s->tlas4 && layout == TBVH_LAYOUT_BVH4_GPU) {   // BVH4_GPU BLASes: the unified 4-wide kernel
-        q.spillStride = c->spillEntries;   // 32-bit stack entries
-        launch_tlas4(any, 0, s->tlas4, s->instances, desc, q, c->status, blocks, st, blocks7);
-    } else if (s->tlas8 && (layout == TBVH_LAYOUT_CWBVH || mix)) {   // BVH8_CWBVH BLASes (or those and BVH_GPU ones): the unified 8-wide kernel
-        q.spillStride = c->spillEntries / 2;   // 8-byte stack entries
-        launch_tlas8(any, 0, s->tlas8, s->tlas8Refs, s->instances, desc, q, c->status, blocks, st, blocks7, mix);
-    } else if (layout == TBVH_LAYOUT_VOXELSET) {   // voxel sets (kernels_voxel.hip); tbvh_upload_tlas admits them only all together
-        q.spillStride = c->spillEntries;   // 32-bit stack entries
-        launch_voxel(any, nullptr, s->nodes, s->tlasIdx, s->instances, desc, q, c->status, blocks, st);
-    } else if (layout == TBVH_LAYOUT_BVH_GPU) {   // BVH_GPU BLASes: the TLAS already has their node format (kernels_tlas2.hip)
-        q.spillStride = c->spillEntries;
-        launch_tlas2(any, 0, s->nodes, s->tlasIdx, s->instances, desc, q, c->status, blocks, st, blocks7);
-    } else {
-        q.spillStride = c->spillEntries / 2;
-        launch_tlas(any, layout, s->nodes, s->tlasIdx, s->instances, desc, q, c->status, blocks, st);
-    }
-}
-
-// What launchQuery has worked out about a launch on a BVH8_CWBVH scene before the kernels are chosen.
-struct CwbvhLaunch {
-    bool any;              // IsOccluded
-    bool small;            // the scene lives in the L2s (< 48 MB)
-    bool probedSmall;      // a scene under 48 MB or beyond 384 MB whose batch is probed for the packet kernel
-    int sizeClass;         // which of the scene's tuners the batch belongs to
-    uint32_t blocks;       // grid of a coherent batch (a third more waves when probed)
-    uint32_t blocksBase;   // grid of an incoherent one
-    uint32_t* probeWords;  // the coherence probe's counters in this launch's pool area
-    hipStream_t stream;    // the lane the launch takes
-    bool solo;             // the buffer's last two finished launches were incoherent (probe_memory.h): a two-flavor launch leaves out the coherent flavor
+// One launch as the steps of launchQuery hand it on: each member is set once, by the step named.
+struct Launch {
+    bool any = false, overlaps = false;   // IsOccluded; it may take lane 1 and the lanes' book records it (launchQuery)
+    LaneFootprint fp;                // the bytes it writes (footprintOf)
+    int lane = 0;                    // chooseLane
+    hipStream_t st = nullptr;        // ... and that lane's stream
+    uint32_t* probeLine = nullptr;   // the coherence probe's counters in this launch's pool area (bindLanePool)
+    uint64_t launchSeq = 0;          // its event pair (launchQuery, after timedBegin): the number LaneBook::gate and the verdict memory know it by,
+    uint32_t ringSlot = 0;           //   and the pair's place in the ring
+    ProbeKey key;                    // armProbe: the probe's verdict on this launch will be remembered under `key` (remember); the buffer's last two
+    bool remember = false, solo = false;   //   finished launches were incoherent (probe_memory.h) and the coherent flavor is left out (solo)
 };
 
+static LaneFootprint footprintOf(const RayRec* d_rays, uint64_t n, const uint8_t* d_occ) {
+    LaneFootprint fp;
+    fp.rays.lo = (uintptr_t)d_rays; fp.rays.hi = fp.rays.lo + (uintptr_t)n * sizeof(RayRec);
+    if (d_occ) { fp.occ.lo = (uintptr_t)d_occ; fp.occ.hi = fp.occ.lo + (uintptr_t)n; }
+    return fp;
+}
+
+// ---- which kernels a scene's queries run, and how wide their stack entries are ---------------------------------------------------------------------
+enum class KernelFamily { kBvh2, kBvh4, kCwbvh, kSphere, kVoxel, kTlasSphere, kTlas4, kTlas8, kTlasVoxel, kTlas2, kTlasFlat, kNone };
+// The class of BLAS layouts a TLAS query walks: any-hit queries may have a class of their own (capi_scene.hip: reclassifyTlas)
+struct TlasClass { int layout; bool mix; const BlasDesc* desc; };
+static TlasClass tlasClass(const tbvh_scene* s, bool any) {
+    const bool own = any && s->blasDescAny != nullptr;
+    return own ? TlasClass{s->blasLayoutAny, s->blasMixCw2Any, s->blasDescAny} : TlasClass{s->blasLayout, s->blasMixCw2, s->blasDesc};
+}
+
+// The two-level kernels: one per BLAS layout (and one for BVH8_CWBVH and BVH_GPU BLASes mixed), each walking the TLAS form made for it at upload.
+static KernelFamily kernelFamily(const tbvh_scene* s, const TlasClass& t) {
+    if (s->isTlas) {
+        // sphere BLASes, alone or with triangle BLASes walked in their own layouts: the flat loop with the sphere step
+        if (s->blasSpheres) return KernelFamily::kTlasSphere;
+        if (s->tlas4 && t.layout == TBVH_LAYOUT_BVH4_GPU) return KernelFamily::kTlas4;           // BVH4_GPU BLASes: the unified 4-wide kernel
+        if (s->tlas8 && (t.layout == TBVH_LAYOUT_CWBVH || t.mix)) return KernelFamily::kTlas8;   // BVH8_CWBVH BLASes (or those and BVH_GPU ones): 8-wide
+        if (t.layout == TBVH_LAYOUT_VOXELSET) return KernelFamily::kTlasVoxel;   // voxel sets; tbvh_upload_tlas admits them only all together
+        if (t.layout == TBVH_LAYOUT_BVH_GPU) return KernelFamily::kTlas2;     // BVH_GPU BLASes: the TLAS already has their node format
+        return KernelFamily::kTlasFlat;
+    }
+    return s->layout == TBVH_LAYOUT_BVH_GPU ? KernelFamily::kBvh2 : s->layout == TBVH_LAYOUT_BVH4_GPU ? KernelFamily::kBvh4
+           : s->layout == TBVH_LAYOUT_CWBVH ? KernelFamily::kCwbvh : s->layout == TBVH_LAYOUT_VOXELSET ? KernelFamily::kVoxel
+           : s->layout == TBVH_LAYOUT_BVH2_WALD ? KernelFamily::kSphere /* a sphere BLAS (kernels_custom.hip) */ : KernelFamily::kNone;
+}
+
+// Stack entries per lane in the spill area, which holds spillEntries 32-bit words per lane: half as many where a family pushes 8-byte entries.
+static uint32_t stackEntriesPerLane(const tbvh_context* c, KernelFamily f) {
+    using F = KernelFamily;
+    const bool eightBytes = f == F::kCwbvh || f == F::kSphere || f == F::kTlasSphere || f == F::kTlas8 || f == F::kTlasFlat;
+    return eightBytes ? c->spillEntries / 2 : c->spillEntries;
+}
+
 // One coherent-flavor kernel of a two-flavor launch, in the schedule the scene's tuner asks for; timed by the tuner's own events while it still measures.
-static int launchCoherentFlavor(tbvh_scene* s, const QueryArgs& q, const CwbvhLaunch& L, const float4* tris, uint32_t blocks7) {
+static int launchCoherentFlavor(tbvh_scene* s, const QueryArgs& q, const LaunchPlan& P, const Launch& L, const float4* tris) {
     tbvh_context* c = s->ctx;
     QueryArgs qa = q;
     qa.baseBlocks = 0;   // every wave of the coherent flavor leaves unless the batch is coherent
     if (c->expFlags & 16u) qa.flags |= 16u;   // (debug flag 16: the coherent flavor takes the batch whatever the probe finds: tests put incoherent rays through it)
     // which schedule serves a coherent batch on this scene is measured, not assumed (CohTuner, capi_internal.h)
-    s->cohLastClass[L.any ? 1 : 0] = (uint8_t)L.sizeClass;
-    CohTuner& tu = s->cohTuner[L.any ? 1 : 0][L.sizeClass];
+    s->cohLastClass[L.any ? 1 : 0] = (uint8_t)P.sizeClass;
+    CohTuner& tu = s->cohTuner[L.any ? 1 : 0][P.sizeClass];
     const bool sizeKnown = q.nRaysDev == nullptr;   // a batch whose size only the device knows (the wavefront stages) cannot be priced per ray: the default schedule, no sample
-    if (L.probedSmall && !tu.decided && tu.n[0] == 0) { tu.n[0] = CohTuner::kSamples; tu.best[0] = 1e30f; }   // (no deferred schedule on such a scene: strict or packet)
+    if (P.probedSmall && !tu.decided && tu.n[0] == 0) { tu.n[0] = CohTuner::kSamples; tu.best[0] = 1e30f; }   // (no deferred schedule there: strict or packet)
     if (!tu.decided && !c->cohTunerMode) {
-        tu.harvest(L.probedSmall ? 0.015f : 0.05f);
-        tu.settle(L.probedSmall, L.small ? 0.97f : 0.92f);   // (beyond 384 MB the per-lane flavor measured here walks the packed nodes; a scene with the padded node copy runs a few % faster unprobed)
+        tu.harvest(P.probedSmall ? 0.015f : 0.05f);
+        // (beyond 384 MB the per-lane flavor measured here walks the packed nodes; a scene with the padded node copy runs a few % faster unprobed)
+        tu.settle(P.probedSmall, P.small ? 0.97f : 0.92f);
     }
     const bool measuring = !tu.decided && !c->cohTunerMode && sizeKnown;
     // while undecided: the schedule with the fewest samples taken or in flight (round-robin by launch count aliased with callers whose coherent
     // launches come every third time: one schedule got every sample, the others none, and the tuner idled into its fallback)
     int mode = c->cohTunerMode ? c->cohTunerMode : tu.decided ? tu.decided : measuring ? 1 + tu.least_sampled() : 1;
-    if (L.probedSmall && mode == 1) mode = 2;
+    if (P.probedSmall && mode == 1) mode = 2;
     if (sizeKnown) tu.launches++;
     if (mode == 2) qa.flags |= 32u;
     CohTuner::Pending pe{nullptr, nullptr, mode, q.nRays};
     if (measuring && tu.pending.size() < 16) {
-        if (hipEventCreate(&pe.e0) != hipSuccess || hipEventCreate(&pe.e1) != hipSuccess || hipEventRecord(pe.e0, L.stream) != hipSuccess) {   // no sample then
+        if (hipEventCreate(&pe.e0) != hipSuccess || hipEventCreate(&pe.e1) != hipSuccess || hipEventRecord(pe.e0, L.st) != hipSuccess) {   // no sample then
             if (pe.e0) hipEventDestroy(pe.e0);
             if (pe.e1) hipEventDestroy(pe.e1);
             pe.e0 = pe.e1 = nullptr; (void)hipGetLastError();
         }
     }
-    if (mode == 3) launch_cwbvh_packet(L.any, s->nodes, s->tris, qa, c->status, L.blocks, L.stream);   // one traversal per wave of 64 consecutive rays
-    else launch_cwbvh(L.any, 0, s->nodes, tris, qa, c->status, mode == 2 ? L.blocksBase : L.blocks, L.stream, 5, L.small, blocks7);
+    if (mode == 3) launch_cwbvh_packet(L.any, s->nodes, s->tris, qa, c->status, P.blocks, L.st);   // one traversal per wave of 64 consecutive rays
+    else launch_cwbvh(L.any, 0, s->nodes, tris, qa, c->status, mode == 2 ? P.blocksBase : P.blocks, L.st, 5, P.small, P.blocks7Cwbvh);
     const hipError_t le = hipGetLastError();
     if (pe.e0) {
-        if (le == hipSuccess && hipEventRecord(pe.e1, L.stream) == hipSuccess) tu.pending.push_back(pe);
+        if (le == hipSuccess && hipEventRecord(pe.e1, L.st) == hipSuccess) tu.pending.push_back(pe);
         else { hipEventDestroy(pe.e0); hipEventDestroy(pe.e1); }
     }
     HIP_TRY(le);
     return 0;
 }
 
-// The kernels of one launch on a BVH8_CWBVH scene.  A probed launch on a scene with the incoherent-batch copies (prepareIncoherentCopies) is TWO kernels
-// back to back, each for one verdict of the probe; the one the verdict is not for leaves at once (~10 us).  The coherent flavor keeps the packed arrays as
-// uploaded (its working set lives in the L2s); the incoherent one walks the hybrid node copy and the 64-byte triangle records.
+// The scene's own kernel, as a launch without a second flavor runs it: on the padded node copy where the plan says so (launch_plan.h: autoPad)
+static void launchSceneKernel(tbvh_scene* s, const QueryArgs& q, const LaunchPlan& P, const Launch& L, const float4* tris) {
+    launch_cwbvh(L.any, s->variant, P.autoPad ? s->cw.padded : s->nodes, tris, q, s->ctx->status, P.blocks, L.st, P.autoPad ? 8 : 5, P.small, P.blocks7Cwbvh);
+}
+
+// The kernels of one launch on a BVH8_CWBVH scene, by the plan's shape (launch_plan.h: planShape).  A probed launch on a scene with the incoherent-batch
+// copies (prepareIncoherentCopies) is TWO kernels back to back, each for one verdict of the probe; the one the verdict is not for leaves at once (~10 us).
+// The coherent flavor keeps the packed arrays as uploaded (its working set lives in the L2s); the incoherent one walks the hybrid node copy and the
+// 64-byte triangle records.
 // Bistro stand-in, 16.7 M rays, interleaved medians (profiles/r03_ab_16m.txt): bounce rays +10 %, camera and shadow rays unchanged.
-static int launchCwbvhKernels(tbvh_scene* s, QueryArgs& q, const CwbvhLaunch& L) {
+static int launchCwbvhKernels(tbvh_scene* s, QueryArgs& q, const LaunchPlan& P, const Launch& L) {
     tbvh_context* c = s->ctx;
-    const bool autoPad = s->variant == 0 && s->cw.padded != nullptr;   // nodes beyond the Infinity Cache: the padded copy (padCwbvhIfLarge)
-    const uint32_t blocks7 = c->gridOverride ? 0xFFFFFFFFu : (uint32_t)c->numCUs * 28u;
     const float4* tris = s->tris;
 #ifdef TBVH_EXPERIMENTS
     if ((c->expFlags & 2u) && s->cw.trisPadded) { tris = s->cw.trisPadded; q.flags |= 2u; }   // experiment: 64-byte triangle records in the ordinary kernels too
 #endif
-    const bool twoFlavors = q.probe && s->variant == 0 && ((!autoPad && s->cw.hybrid && s->cw.trisPadded) || L.probedSmall) && !(c->expFlags & 4u);
-    if (s->variant == 90 && s->cw.hybrid && s->cw.trisPadded) {   // diagnostic: the incoherent flavor whatever the batch (tests, tools/ab_configs.py)
-        launch_cwbvh(L.any, 0, s->cw.hybrid, s->cw.trisPadded, q, c->status, L.blocksBase, L.stream, 13, L.small, blocks7);
-    } else if (s->variant == 91) {   // diagnostic: the coherent flavor (deferred triangles, gated triangle phase) whatever the batch and whatever its probe says
+    switch (P.shape) {
+    case CwbvhShape::kVariant90:   // diagnostic: the incoherent flavor whatever the batch (tests, tools/ab_configs.py)
+        launch_cwbvh(L.any, 0, s->cw.hybrid, s->cw.trisPadded, q, c->status, P.blocksBase, L.st, 13, P.small, P.blocks7Cwbvh);
+        break;
+    case CwbvhShape::kVariant91: {   // diagnostic: the coherent flavor (deferred triangles, gated triangle phase) whatever the batch and its probe say
         QueryArgs qa = q;
-        qa.probe = L.probeWords; qa.baseBlocks = 0; qa.flags |= 16u;
-        launch_cwbvh(L.any, 0, s->nodes, tris, qa, c->status, L.blocks, L.stream, 5, L.small, blocks7);
-    } else if (s->variant == 92) {   // diagnostic: one traversal per wave of 64 consecutive rays (kernels_cwbvh_packet.hip) whatever the batch, the scene's size and the tuner
-        launch_cwbvh_packet(L.any, s->nodes, s->tris, q, c->status, L.blocks, L.stream);
-    } else if (twoFlavors) {
-        // Solo: the coherent flavor is left out.  The prediction decides nothing about which rays are traced: the incoherent flavor never looks at a verdict and
-        // draws every ray from the pool (as under variant 90), so a batch that has turned coherent is traced correctly, once, by the slower flavor; its block 0
-        // publishes the sample, the host sees the coherent vote when the launch has finished, and the buffer's next launch is two flavors again.  What is saved
-        // is a kernel of 8192 workgroups that sample and leave — 16 us into an idle GPU, but a stream barrier in front of the real kernel when the launch starts
-        // beside another lane's persistent waves (every slot taken: the dead flavor's last workgroup runs when that kernel retires).
-        const bool solo = L.solo && !L.probedSmall;
-        if (solo) {   // (what launchCoherentFlavor keeps for tbvh_debug_coherent_schedule is kept here too: the class of the latest launch, the launches counted)
+        qa.probe = L.probeLine; qa.baseBlocks = 0; qa.flags |= 16u;
+        launch_cwbvh(L.any, 0, s->nodes, tris, qa, c->status, P.blocks, L.st, 5, P.small, P.blocks7Cwbvh);
+        break;
+    }
+    case CwbvhShape::kVariant92:   // diagnostic: one traversal per wave of 64 consecutive rays (kernels_cwbvh_packet.hip) whatever batch, scene and tuner
+        launch_cwbvh_packet(L.any, s->nodes, s->tris, q, c->status, P.blocks, L.st);
+        break;
+    case CwbvhShape::kTwoFlavors:
+    case CwbvhShape::kFlavorAndBehind:
+        // Solo (only ever a kTwoFlavors launch: launch_plan.h, soloCandidate): the coherent flavor is left out.  The prediction decides nothing about which
+        // rays are traced: the incoherent flavor never looks at a verdict and draws every ray from the pool (as under variant 90), so a batch that has turned
+        // coherent is traced correctly, once, by the slower flavor; its block 0 publishes the sample, the host sees the coherent vote when the launch has
+        // finished, and the buffer's next launch is two flavors again.  What is saved is a kernel of 8192 workgroups that sample and leave — 16 us into an
+        // idle GPU, but a stream barrier in front of the real kernel when the launch starts beside another lane's persistent waves (every slot taken: the
+        // dead flavor's last workgroup runs when that kernel retires).
+        if (L.solo) {   // (what launchCoherentFlavor keeps for tbvh_debug_coherent_schedule is kept too: the latest launch's class, the launches counted)
             q.flags |= 64u; c->soloLaunches++;
-            s->cohLastClass[L.any ? 1 : 0] = (uint8_t)L.sizeClass;
-            s->cohTuner[L.any ? 1 : 0][L.sizeClass].launches++;
-        }
-        else if (int r = launchCoherentFlavor(s, q, L, tris, blocks7)) return r;
-        if (L.probedSmall) {   // behind it: the scene's unprobed kernel, as launched without a probe
+            s->cohLastClass[L.any ? 1 : 0] = (uint8_t)P.sizeClass;
+            s->cohTuner[L.any ? 1 : 0][P.sizeClass].launches++;
+        } else if (int r = launchCoherentFlavor(s, q, P, L, tris)) return r;
+        if (P.shape == CwbvhShape::kFlavorAndBehind) {   // behind it: the scene's unprobed kernel, as launched without a probe
             QueryArgs qp = q;
             qp.probe = nullptr; qp.baseBlocks = 0;
-            launch_cwbvh(L.any, s->variant, autoPad ? s->cw.padded : s->nodes, tris, qp, c->status, L.blocks, L.stream, autoPad ? 8 : 5, L.small, blocks7);
+            launchSceneKernel(s, qp, P, L, tris);
         } else {
             // the incoherent flavor on 28 one-wave workgroups per CU when the batch fills the grid (24 is the persistent grid's size: 20 / 26 / 28 / 30 /
             // 32 per CU trace bounce rays at -4.4 / +0.6 / +0.9 / +0.5 / +0.5 %, interleaved medians of 13 rounds)
             uint32_t wX = (c->expFlags >> 8) & 0xffu;   // experiment: another number of waves per CU
             if (wX > 32u) wX = 32u;                     // (the spill area holds blocks + blocks / 3 = 32 workgroups per CU: LaneStack strides by gridDim)
             const uint32_t wB = wX ? wX : (c->gridOverride ? 0u : 28u);
-            launch_cwbvh(L.any, 0, s->cw.hybrid, s->cw.trisPadded, q, c->status, (wB && L.blocksBase == c->blocks) ? (uint32_t)c->numCUs * wB : L.blocksBase, L.stream, 13, L.small, blocks7);
+            const uint32_t blocksIncoherent = (wB && P.blocksBase == c->blocks) ? (uint32_t)c->numCUs * wB : P.blocksBase;
+            launch_cwbvh(L.any, 0, s->cw.hybrid, s->cw.trisPadded, q, c->status, blocksIncoherent, L.st, 13, P.small, P.blocks7Cwbvh);
         }
-    } else {
-        launch_cwbvh(L.any, s->variant, autoPad ? s->cw.padded : s->nodes, tris, q, c->status, L.blocks, L.stream, autoPad ? 8 : 5, L.small, blocks7);
+        break;
+    case CwbvhShape::kOneKernel:
+        launchSceneKernel(s, q, P, L, tris);
+        break;
     }
     return 0;
 }
@@ -341,11 +365,10 @@ static bool ensureLane1(tbvh_context* c) {
     tbvh_context::Lane1& l = c->lane1;
     if (l.unusable) return false;
     if (l.stream && l.pool && l.spill && c->evBase) return true;
-    const size_t poolWords = (size_t)(kPoolParts + 1) * kPoolCounterStride;
     const size_t spillWords = (size_t)(c->blocks + c->blocks / 3u) * 64 * c->spillEntries;   // (as lane 0's: the largest grid any launch uses)
     if ((!c->evBase && hipEventCreateWithFlags(&c->evBase, hipEventDisableTiming) != hipSuccess) ||
         (!l.stream && hipStreamCreateWithFlags(&l.stream, hipStreamNonBlocking) != hipSuccess) ||
-        (!l.pool && l.pool.alloc(poolWords * 2) != hipSuccess) || (!l.spill && l.spill.alloc(spillWords) != hipSuccess)) {
+        (!l.pool && l.pool.alloc(kPoolWords * 2) != hipSuccess) || (!l.spill && l.spill.alloc(spillWords) != hipSuccess)) {
         (void)hipGetLastError();
         l.pool.reset(); l.spill.reset();
         l.unusable = true;
@@ -372,17 +395,33 @@ static bool ensureProbeSlots(tbvh_context* c) {
     return true;
 }
 
+// ---- has a launch finished? ---------------------------------------------------------------------------------------------------------------------
+// One question to the runtime, never a wait: the end event of the launch whose event pair is entry `slot` of the ring.
+enum EndState { kInFlight = 0, kEnded = 1, kCannotTell = 2 };   // kCannotTell: the query itself failed
+static EndState endEventState(tbvh_context* c, uint32_t slot) {
+    const hipError_t qe = hipEventQuery(c->evRing[slot][1]);
+    if (qe == hipSuccess) return kEnded;
+    (void)hipGetLastError();
+    return qe == hipErrorNotReady ? kInFlight : kCannotTell;
+}
+// Its three readers differ in how they name a launch and in what they make of one the ring no longer holds (its event pair has gone to a later operation):
+// LaneBook::prune names a record by its slot: whatever is not in flight leaves the list;
+static bool recordHasLeft(tbvh_context* c, uint32_t slot) { return endEventState(c, slot) != kInFlight; }
+// LaneBook::gate names a launch by its number: one the ring no longer holds is kTimeRing operations back and counts as finished, never waited for;
+static bool finishedOrForgotten(tbvh_context* c, uint64_t seq) {
+    return !c->ringHolds(seq) || endEventState(c, (uint32_t)(seq % tbvh_context::kTimeRing)) != kInFlight;
+}
+// ProbeMemory::harvest likewise by number: such a launch (or any, without the verdict slots) leaves without a vote — kCannotTell; kEnded: its words are read.
+static EndState verdictState(tbvh_context* c, uint64_t seq) {
+    if (!c->ringHolds(seq) || !c->probeSlots) return kCannotTell;
+    return endEventState(c, (uint32_t)(seq % tbvh_context::kTimeRing));
+}
+
 // Verdicts of the remembered launches that have finished by now join the table.  Never waits: a launch still in flight stays remembered, one whose event
 // pair the ring has handed to a later operation leaves without a vote.
 static void harvestVerdicts(tbvh_context* c) {
     c->probeMemory.harvest(
-        [c](uint64_t seq) {
-            if (!c->ringHolds(seq) || !c->probeSlots) return 2;
-            const hipError_t qe = hipEventQuery(c->evRing[seq % tbvh_context::kTimeRing][1]);
-            if (qe == hipSuccess) return 1;
-            (void)hipGetLastError();
-            return qe == hipErrorNotReady ? 0 : 2;
-        },
+        [c](uint64_t seq) { return (int)verdictState(c, seq); },
         [c](uint64_t seq) {
             const volatile uint32_t* w = c->probeSlots + 2 * (seq % tbvh_context::kTimeRing);
             const uint32_t agree = w[0], pairs = w[1];
@@ -400,28 +439,25 @@ static bool launchPrepares(const tbvh_scene* s, uint64_t n, bool any) {
     return n >= 1024u && s->variant == 0 && !s->copies.tried8 && (s->layout == TBVH_LAYOUT_BVH_GPU || s->layout == TBVH_LAYOUT_BVH4_GPU);
 }
 
-int launchQuery(tbvh_scene* s, RayRec* d_rays, uint64_t n, uint8_t* d_occ, bool fresh, float freshTmax, const unsigned long long* nDev, bool mayOverlap) {
-    tbvh_context* c = s->ctx;
-    TBVH_LOCK(c);
-    const bool any = d_occ != nullptr;
-    // Two lanes (overlap_lanes.h): a device-resident query whose buffers no launch in flight touches need not wait for the launches before it — the
-    // persistent grids fill every wave slot, so its workgroups start where the earlier launch's waves retire and its body hides that launch's tail.
-    // Everything else (and every launch while overlap is off, on a caller's stream, untimed or sized on the device) joins the lanes like any entry point.
-    bool lanes = mayOverlap && c->overlap && c->stream == c->ownStream && !c->skipTiming && !nDev && n != 0;
-    if (lanes && launchPrepares(s, n, any)) lanes = false;
-    if (lanes) HIP_TRY(hipSetDevice(c->device));
-    else if (int r = setDevice(c)) return r;
-    if (n == 0) return 0;
+// ---- launchQuery's steps, in the order it takes them ---------------------------------------------------------------------------------------------------
+// Step 1, the scene: what a query does to it before anything is launched (none of it part of the query's time).  *wide: the scene the query runs on
+// instead — a BVH_GPU / BVH4_GPU scene with an 8-wide copy (capi_copies.hip) —, for which the caller starts over.
+static int prepareScene(tbvh_scene* s, uint64_t n, bool any, bool sizeKnown, tbvh_scene** wide) {
     s->raysTraced += n;   // (what tbvh_refit weighs the refit of a scene's copies against)
     countQueryForRecopy(s);   // copies dropped by a tbvh_update_* come back once the blob has settled
-    if (!s->isTlas && (nDev || n >= 1024u)) makeCopyOnce(s, kCopyWide8);   // first query of a BVH_GPU / BVH4_GPU scene (not part of its time)
-    if (tbvh_scene* w = wideCopyForQuery(s)) return launchQuery(w, d_rays, n, d_occ, fresh, freshTmax, nDev, mayOverlap);   // BVH_GPU / BVH4_GPU with an 8-wide copy (capi_copies.hip)
-    if (any && s->isTlas && !s->anyHitSeen && !s->blasSpheres) {   // the first IsOccluded through this TLAS (not part of its time): its BVH4_GPU and BVH_GPU BLASes are entered through 8-wide copies by any-hit queries
+    if (!s->isTlas && (!sizeKnown || n >= 1024u)) makeCopyOnce(s, kCopyWide8);   // first query of a BVH_GPU / BVH4_GPU scene
+    if ((*wide = wideCopyForQuery(s))) return 0;
+    // the first IsOccluded through this TLAS: its BVH4_GPU and BVH_GPU BLASes are entered through 8-wide copies by any-hit queries
+    if (any && s->isTlas && !s->anyHitSeen && !s->blasSpheres) {
         s->anyHitSeen = true;
         for (tbvh_scene* b : s->blasList) makeCopyOnce(b, kCopyWide8);   // (re-classifies the TLASes over b, this one included)
         if (int r = reclassifyTlas(s)) return r;
     }
-    const size_t poolWords = (size_t)(kPoolParts + 1) * kPoolCounterStride;   // + the coherence-probe counters on their own line
+    return 0;
+}
+
+static QueryArgs queryArgsOf(const tbvh_scene* s, RayRec* d_rays, uint64_t n, uint8_t* d_occ, bool fresh, float freshTmax, const unsigned long long* nDev) {
+    const tbvh_context* c = s->ctx;
     QueryArgs q;
     q.rays = d_rays; q.nRays = n; q.occluded = d_occ;
     q.poolParts = c->poolParts;
@@ -431,236 +467,201 @@ int launchQuery(tbvh_scene* s, RayRec* d_rays, uint64_t n, uint8_t* d_occ, bool 
 #ifdef TBVH_EXPERIMENTS
     q.flags = c->expFlags & 0x3FF0001u;
 #endif
-    c->lastProbed = false;
     q.splitBelow = c->splitBelow;
-    // persistent grid: 24 one-wave workgroups per CU for large batches; small batches get fewer
-    // (about one workgroup per 128 rays, measured best for 1 M-ray launches) so every wave still
-    // has a few ray replacements' worth of work
-    // A scene that (nearly) lives in the L2s — the Sponza class: < 48 MB of nodes and triangles against 8 x 4 MB of L2
-    // plus the Infinity Cache — is latency-bound, not cache-bound: it runs best with a third more waves (32 per CU) of
-    // fewer rays each (measured +1..20 % on the Sponza stand-in from 0.26 M to 16.7 M rays; the same shape costs the
-    // 196 MB Bistro stand-in 5-10 % on bounce and shadow rays, which thrash the caches more with more waves).
-    const uint64_t blobBytes = (!s->isTlas && s->layout == TBVH_LAYOUT_CWBVH) ? (s->nNodeBlocks + s->nTriBlocks) * 16 : s->bytes;   // (without the library's own re-laid-out copies)
-    const bool small = !s->isTlas && !c->gridOverride && blobBytes < (48ull << 20);
-    const uint32_t perBlock = c->raysPerBlock;
-    const uint32_t cap = small ? c->blocks + c->blocks / 3u : c->blocks;
-    uint64_t want = (n + perBlock - 1) / perBlock;
-    const uint32_t lo = (uint32_t)c->numCUs * 4u;
-    uint32_t blocks = (uint32_t)(want < lo ? lo : (want > cap ? cap : want));
-    const bool probed = !s->isTlas && !small && blobBytes <= (384ull << 20) && s->layout == TBVH_LAYOUT_CWBVH && n >= (1ull << 21) && (s->variant == 0 || s->variant == 88) && !(c->expFlags & 64u);
-    if (probed && !s->cw.tried) {   // first launch of this class on the scene: the derived copies for incoherent batches (not part of the query's time)
-        if (lanes) if (int r = joinLanes(c)) return r;   // (built on lane 0)
+    return q;
+}
+
+// Step 2, the plan (launch_plan.h): the facts of this launch, planBatch, what `probed` asks of the scene, planShape over the copies as they then are.
+static int planLaunch(tbvh_scene* s, uint64_t n, bool sizeKnown, const Launch& L, LaunchPlan* plan) {
+    tbvh_context* c = s->ctx;
+    LaunchFacts f;
+    f.isTlas = s->isTlas; f.layout = s->layout; f.variant = s->variant; f.n = n; f.sizeKnown = sizeKnown; f.any = L.any;
+    f.blobBytes = (!s->isTlas && s->layout == TBVH_LAYOUT_CWBVH) ? (s->nNodeBlocks + s->nTriBlocks) * 16 : s->bytes;   // (without the library's own copies)
+    f.gridOverride = c->gridOverride; f.numCUs = (uint32_t)c->numCUs; f.blocks = c->blocks; f.raysPerBlock = c->raysPerBlock;
+    f.expFlags = c->expFlags; f.cohTunerMode = c->cohTunerMode; f.probeMemoryOn = c->probeMemoryOn; f.skipTiming = c->skipTiming;
+    for (int k = 0; k < 4; k++) f.decided[k] = s->cohTuner[L.any ? 1 : 0][k].decided;
+    *plan = planBatch(f);
+    if (plan->probed && !s->cw.tried) {   // first launch of this class on the scene: the derived copies for incoherent batches (not part of the query's time)
+        if (L.overlaps) if (int r = joinLanes(c)) return r;   // (built on lane 0)
         if (int r = prepareIncoherentCopies(s)) return r;
     }
-    q.hybridK = s->cw.packed;
-    const bool huge = !small && blobBytes > (384ull << 20);
-    const int sizeClass = (small && n < (3ull << 19)) ? 3 : n < (6ull << 20) ? 0 : n < (12ull << 20) ? 1 : 2;
-    bool probedSmall = !s->isTlas && (small || huge) && s->layout == TBVH_LAYOUT_CWBVH && s->variant == 0 && !nDev && n >= (small ? (3ull << 18) : (6ull << 20)) && !(c->expFlags & 64u) && !c->gridOverride;
-    if (probedSmall) {
-        const int m = c->cohTunerMode ? c->cohTunerMode : s->cohTuner[any ? 1 : 0][sizeClass].decided;
-        if (m == 1 || m == 2) { probedSmall = false; s->cohLastClass[any ? 1 : 0] = (uint8_t)sizeClass; }
-    }
-    // ---- the lane this launch takes -------------------------------------------------------------------------------------------------------------
-    // A launch the scene's CohTuner may time (a two-flavor launch of a class still undecided) and the launch after it run serialised: a sample taken
-    // beside another launch's tail must not decide a schedule.
-    int lane = 0;
-    if (lanes) {
-        const bool tunerMeasures = (probed || probedSmall) && !c->cohTunerMode && !s->cohTuner[any ? 1 : 0][sizeClass].decided;
-        // (lane 1 is made by the first launch that MAY overlap, also one that does not: its stack spill area is a large allocation — 10 ms on the bench's
-        // context —, which belongs to a caller's warm-up launches, serialised by the tuner or not, and not to the first launch that finds a neighbour in flight)
-        const bool haveLane1 = ensureLane1(c);
-        if (tunerMeasures || c->serialiseNext) {
-            if (int r = joinLanes(c)) return r;
-            c->serialiseNext = tunerMeasures;
-        } else {
-            c->book.prune([c](int, uint32_t slot) {
-                const hipError_t qe = hipEventQuery(c->evRing[slot][1]);
-                if (qe != hipSuccess) (void)hipGetLastError();
-                return qe != hipErrorNotReady;
-            });
-            LaneFootprint fp;
-            fp.rays.lo = (uintptr_t)d_rays; fp.rays.hi = fp.rays.lo + (uintptr_t)n * sizeof(RayRec);
-            if (any) { fp.occ.lo = (uintptr_t)d_occ; fp.occ.hi = fp.occ.lo + (uintptr_t)n; }
-            const LaneChoice ch = c->book.decide(fp, haveLane1);
-            if (ch.join) { if (int r = joinLanes(c)) return r; }
-            lane = ch.lane;
-            // What was enqueued on lane 0 before its in-flight query launches (ray generators, uploads, refits) comes before a launch on lane 1 too: evBase marks
-            // that position — NOT lane 0's end, which would put the launch behind the very launches it may overlap.
-            if (c->lane0Touched && c->evBase) {
-                HIP_TRY(hipEventRecord(c->evBase, c->stream));
-                c->lane0Touched = false; c->lane1SawBase = false;
-            }
-            if (lane == 1 && !c->lane1SawBase) {
-                HIP_TRY(hipStreamWaitEvent(c->lane1.stream, c->evBase, 0));
-                c->lane1SawBase = true;
-            }
-            // Launches START in the order they were enqueued, across the lanes too, give or take overlapDepth launches (LaneBook::gate): this one waits for the
-            // start (not the end) of one of the other lane's last launches.  Depth 1, the latest: neither lane runs more than one launch ahead of the other.
-            // Depth 2, the one before the latest, while it is in flight: a caller alternating camera and bounce batches (C1 D1 C2 D2 ...) gets C(k+2) into the
-            // tail of D(k) — at depth 1 it waits for the start of D(k+1), which stream order holds behind D(k)'s end, and lane 0 sits empty for exactly that
-            // tail.  The camera launch still takes the wave slots first: it starts in D(k)'s tail, D(k+1) behind D(k)'s end.  Either way the launches that ran
-            // beside a launch are its near neighbours in the order enqueued (what timedMs looks at).  Measured (profiles/r09_runahead.txt): depth 2 alone +1.3 %
-            // on the bench step.  That C(k+2) meets D(k) at all is the dead coherent flavor's doing: in front of D(1) it cannot finish before C(1) retires, so
-            // D(1) starts at C(1)'s end and every D(k) runs beside C(k+1).  Launched as one kernel (the probe memory below) D(k) starts beside C(k), C(k+1) waits
-            // for a start long past and takes D(k)'s tail at depth 1 already: depth 2 adds nothing then, so the default is 1.
-            // (A start event the ring has given to a later operation stands for a launch kTimeRing operations back: taken as finished, never waited for.)
-            const uint64_t g = c->book.gate(lane, c->overlapDepth, [c](uint64_t seq) {
-                if (!c->ringHolds(seq)) return true;
-                const hipError_t qe = hipEventQuery(c->evRing[seq % tbvh_context::kTimeRing][1]);
-                if (qe != hipSuccess) (void)hipGetLastError();
-                return qe != hipErrorNotReady;
-            });
-            if (g != LaneBook::kNoGate && c->ringHolds(g)) HIP_TRY(hipStreamWaitEvent(lane ? c->lane1.stream : c->stream, c->evRing[g % tbvh_context::kTimeRing][0], 0));
-        }
-    }
-    const hipStream_t st = lane ? c->lane1.stream : c->stream;
-    // ray-fetch counters: two areas alternate; the kernels of this launch zero the other area for the next one ON THE SAME LANE (each lane has its own
-    // pair: a launch overlapping this one would otherwise draw from the area this one is zeroing).  After anything that went wrong between two launches
-    // (poolClean still false) both are cleared here.
-    uint32_t* const pool = lane ? c->lane1.pool.get() : c->pool.get();
-    int& poolCur = lane ? c->lane1.poolCur : c->poolCur;
-    bool& poolClean = lane ? c->lane1.poolClean : c->poolClean;
-    if (!poolClean) HIP_TRY(hipMemsetAsync(pool, 0, poolWords * 4 * 2, st));
-    poolClean = false;
-    uint32_t* const poolArea = pool + (size_t)poolCur * poolWords;
-    q.spill = lane ? c->lane1.spill : c->spill; q.counter = poolArea; q.counterNext = pool + (size_t)(poolCur ^ 1) * poolWords;
-    HIP_TRY(timedBegin(c, st));
-    const uint64_t launchSeq = c->evSeq - 1;   // (lanes, probe memory: timing is on, the launch has its event pair)
-    const uint32_t ringSlot = (uint32_t)(launchSeq % tbvh_context::kTimeRing);
-    bool remember = false, solo = false;   // the probe's verdict on this launch will be remembered; the launch leaves out the coherent flavor (below)
-    ProbeKey pkey;
-    // the launch's end, once its kernels are enqueued: the end event, the lane's record of it, the other counter area now zeroed by what was enqueued
-    auto finish = [&]() -> int {
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(timedEnd(c, st));
-        poolCur ^= 1; poolClean = true;
-        if (lanes) {
-            LaneFootprint fp;
-            fp.rays.lo = (uintptr_t)d_rays; fp.rays.hi = fp.rays.lo + (uintptr_t)n * sizeof(RayRec);
-            if (any) { fp.occ.lo = (uintptr_t)d_occ; fp.occ.hi = fp.occ.lo + (uintptr_t)n; }
-            c->book.add(lane, fp, ringSlot, launchSeq);
-            c->evChain[ringSlot] = c->chain;
-            if (lane) { c->lane1Last = c->evRing[ringSlot][1]; c->lane1Dirty = true; c->lane1Launches++; }
-        }
-        if (remember) c->probeMemory.note(pkey, launchSeq, lane);
+    f.hasPadded = s->cw.padded != nullptr; f.hasHybrid = s->cw.hybrid != nullptr; f.hasTrisPadded = s->cw.trisPadded != nullptr;
+    planShape(*plan, f);
+    if (plan->probedSmallCancelled) s->cohLastClass[L.any ? 1 : 0] = (uint8_t)plan->sizeClass;
+    return 0;
+}
+
+// Step 3, the lane of a launch that may overlap others (L.overlaps).
+// A launch the scene's CohTuner may time (a two-flavor launch of a class still undecided) and the launch after it run serialised: a sample taken
+// beside another launch's tail must not decide a schedule.
+static int chooseLane(tbvh_context* c, bool tunerMeasures, Launch& L) {
+    // (lane 1 is made by the first launch that MAY overlap, also one that does not: its stack spill area is a large allocation — 10 ms on the bench's
+    // context —, which belongs to a caller's warm-up launches, serialised by the tuner or not, and not to the first launch that finds a neighbour in flight)
+    const bool haveLane1 = ensureLane1(c);
+    if (tunerMeasures || c->serialiseNext) {
+        if (int r = joinLanes(c)) return r;
+        c->serialiseNext = tunerMeasures;
         return 0;
-    };
-    // BVH8_CWBVH scenes beyond the L2s (the `small` class runs dense triangle phases, where the gated schedule loses 15 %) but within reach
-    // of the Infinity Cache (beyond it camera rays are bound by memory too: 30 M / 60 M triangles lose 11 / 19 % under the gate), batches of 2 M
-    // rays and more: a probe of the batch's coherence (256 neighbouring ray pairs, sampled by every wave of the traversal kernel itself: kernels_cwbvh.hip)
-    // lets the traversal kernel pick its schedule for the launch; a coherent batch also gets a third more waves (the surplus leaves at once
-    // otherwise).  Bistro stand-in, 16.7 M rays: camera rays +4.5 %, shadow rays +6 %, bounce rays unchanged.
-    uint32_t blocksBase = blocks;
-    // Scenes under 48 MB (round 6; `probedSmall` also covers the scenes beyond 384 MB, below): batches of 768 k rays and more whose size the host knows are probed too — not for the deferred schedule (it loses
-    // there) but for the PACKET kernel: one traversal per wave traces the Sponza stand-in's camera rays 1.23 / 1.64 / 1.56 x as fast at 1 / 4.2 / 16.7 M
-    // rays, its shadow rays 0.97 / 1.51 / 1.74 x (profiles/r06_small_scene_packet.txt).  Two kernels back to back as on the larger scenes: the coherent
-    // flavor the scene's tuner has settled on (strict per-lane, or packet) leaves at once unless the batch is coherent, the unprobed kernel behind it
-    // takes what the pool still holds.
-    // The two-kernel launch costs a small launch 10-20 us (the probe, the second kernel's start and exit): where the scene's tuner has measured the per-lane
-    // kernel faster — the Dragon stand-in: a 16 x 4-pixel chunk of camera rays covers hundreds of its triangles, the packet walk is 5-8 x slower — or only
-    // a few us slower, the batch runs as before round 6: ONE unprobed kernel.  Only the measuring launches (6-9 per class of batch size) pay.
-    // ... and scenes beyond 384 MB (never probed either: the deferred schedule loses there), from 6 M rays on: the street at 12 M triangles traces 16.7 M camera
-    // rays at 7094 instead of 4718 MRays/s with the packet kernel — and 4.2 M at 3383 instead of 3733, shadow rays slower throughout: measured per class likewise.
-    // (`huge`, `sizeClass` and `probedSmall` are worked out above, ahead of the lane choice, which needs to know whether a tuner may time this launch)
-    if (probedSmall) {
-        q.probe = poolArea + (size_t)kPoolParts * kPoolCounterStride; q.baseBlocks = blocks;
-        c->lastProbed = true; c->lastProbedLane = lane;
     }
-    if (probed) {
-        uint32_t* probe = poolArea + (size_t)kPoolParts * kPoolCounterStride;
-        q.probe = probe; q.baseBlocks = blocks;
-        c->lastProbed = true; c->lastProbedLane = lane;
-        if (!c->gridOverride && blocks == c->blocks) blocks = c->blocks + c->blocks / 3u;   // 24 -> 32 one-wave workgroups per CU
+    c->book.prune([c](int, uint32_t slot) { return recordHasLeft(c, slot); });
+    const LaneChoice ch = c->book.decide(L.fp, haveLane1);
+    if (ch.join) { if (int r = joinLanes(c)) return r; }
+    L.lane = ch.lane;
+    // What was enqueued on lane 0 before its in-flight query launches (ray generators, uploads, refits) comes before a launch on lane 1 too: evBase marks
+    // that position — NOT lane 0's end, which would put the launch behind the very launches it may overlap.
+    if (c->lane0Touched && c->evBase) {
+        HIP_TRY(hipEventRecord(c->evBase, c->stream));
+        c->lane0Touched = false; c->lane1SawBase = false;
     }
-    // What the probe said about this buffer's last launches (probe_memory.h).  A probed launch whose size the host knows gets a slot for its verdict (the
-    // slot of its event pair) and is remembered until it is seen finished.  It goes SOLO — the incoherent flavor alone, launchCwbvhKernels — when the last two
-    // finished launches with exactly this footprint both voted incoherent, the scene's tuner has settled this class of batch (it must see every coherent
-    // launch it would have seen) and nothing diagnostic is set.  Any doubt: two flavors, as without the memory.
+    if (L.lane == 1 && !c->lane1SawBase) {
+        HIP_TRY(hipStreamWaitEvent(c->lane1.stream, c->evBase, 0));
+        c->lane1SawBase = true;
+    }
+    // Launches START in the order they were enqueued, across the lanes too, give or take overlapDepth launches (LaneBook::gate): this one waits for the
+    // start (not the end) of one of the other lane's last launches.  Depth 1, the latest: neither lane runs more than one launch ahead of the other.
+    // Depth 2, the one before the latest, while it is in flight: a caller alternating camera and bounce batches (C1 D1 C2 D2 ...) gets C(k+2) into the
+    // tail of D(k) — at depth 1 it waits for the start of D(k+1), which stream order holds behind D(k)'s end, and lane 0 sits empty for exactly that
+    // tail.  The camera launch still takes the wave slots first: it starts in D(k)'s tail, D(k+1) behind D(k)'s end.  Either way the launches that ran
+    // beside a launch are its near neighbours in the order enqueued (what timedMs looks at).  Measured (profiles/r09_runahead.txt): depth 2 alone +1.3 %
+    // on the bench step.  That C(k+2) meets D(k) at all is the dead coherent flavor's doing: in front of D(1) it cannot finish before C(1) retires, so
+    // D(1) starts at C(1)'s end and every D(k) runs beside C(k+1).  Launched as one kernel (the probe memory, armProbe) D(k) starts beside C(k), C(k+1) waits
+    // for a start long past and takes D(k)'s tail at depth 1 already: depth 2 adds nothing then, so the default is 1.
+    // (A start event the ring has given to a later operation stands for a launch kTimeRing operations back: finishedOrForgotten.)
+    const uint64_t g = c->book.gate(L.lane, c->overlapDepth, [c](uint64_t seq) { return finishedOrForgotten(c, seq); });
+    if (g != LaneBook::kNoGate && c->ringHolds(g))
+        HIP_TRY(hipStreamWaitEvent(L.lane ? c->lane1.stream : c->stream, c->evRing[g % tbvh_context::kTimeRing][0], 0));
+    return 0;
+}
+
+// Step 4, the lane's counter pool and spill area.
+// ray-fetch counters: two areas alternate; the kernels of this launch zero the other area for the next one ON THE SAME LANE (each lane has its own
+// pair: a launch overlapping this one would otherwise draw from the area this one is zeroing).  After anything that went wrong between two launches
+// (poolClean still false) both are cleared here.
+static int bindLanePool(tbvh_context* c, Launch& L, QueryArgs& q) {
+    uint32_t* const pool = L.lane ? c->lane1.pool.get() : c->pool.get();
+    const int poolCur = L.lane ? c->lane1.poolCur : c->poolCur;
+    bool& poolClean = L.lane ? c->lane1.poolClean : c->poolClean;
+    if (!poolClean) HIP_TRY(hipMemsetAsync(pool, 0, kPoolWords * 4 * 2, L.st));
+    poolClean = false;
+    q.spill = L.lane ? c->lane1.spill : c->spill; q.counter = pool + (size_t)poolCur * kPoolWords; q.counterNext = pool + (size_t)(poolCur ^ 1) * kPoolWords;
+    L.probeLine = q.counter + (size_t)kPoolParts * kPoolCounterStride;
+    return 0;
+}
+
+// Step 6, the probe: its counters for a probed launch, and what the probe said about this buffer's last launches (probe_memory.h).  A probed launch whose
+// size the host knows gets a slot for its verdict (the slot of its event pair) and is remembered until it is seen finished.  It goes SOLO — the incoherent
+// flavor alone, launchCwbvhKernels — when the last two finished launches with exactly this footprint both voted incoherent, the scene's tuner has settled
+// this class of batch (it must see every coherent launch it would have seen) and nothing diagnostic is set (launch_plan.h: soloCandidate, wantsVerdictSlot).
+// Any doubt: two flavors, as without the memory.
+static void armProbe(tbvh_scene* s, const LaunchPlan& plan, Launch& L, QueryArgs& q) {
+    tbvh_context* c = s->ctx;
+    if (plan.probed || plan.probedSmall) {
+        q.probe = L.probeLine; q.baseBlocks = plan.blocksBase;
+        c->lastProbed = true; c->lastProbedLane = L.lane;
+    }
     if (c->probeMemory.nPending) harvestVerdicts(c);
-    // Only a launch that could ever go solo is given a slot and remembered: two flavors on the incoherent-batch copies (launchCwbvhKernels: twoFlavors without
-    // probedSmall), variant 0, nothing diagnostic set — variant 88, the one-kernel launch of a padded scene and runs under debug flags neither ask the
-    // events nor take an entry of the table.
-    const bool soloCandidate = probed && s->variant == 0 && !s->cw.padded && s->cw.hybrid && s->cw.trisPadded && !c->expFlags && !c->cohTunerMode && !c->gridOverride;
-    if (soloCandidate && c->probeMemoryOn && !c->skipTiming && !nDev && ensureProbeSlots(c)) {
-        pkey.lo = (uintptr_t)d_rays; pkey.hi = pkey.lo + (uintptr_t)n * sizeof(RayRec); pkey.scene = s; pkey.any = any;
-        remember = true;
-        uint32_t* const slot = c->probeSlots + 2 * (size_t)ringSlot;
+    if (plan.wantsVerdictSlot && ensureProbeSlots(c)) {
+        L.key.lo = L.fp.rays.lo; L.key.hi = L.fp.rays.hi; L.key.scene = s; L.key.any = L.any; L.remember = true;
+        uint32_t* const slot = c->probeSlots + 2 * (size_t)L.ringSlot;
         slot[0] = slot[1] = 0u;   // (pairs == 0: no verdict)
         q.probeHost = slot;
-        solo = s->cohTuner[any ? 1 : 0][sizeClass].decided != 0 && c->probeMemory.solo(pkey);
+        L.solo = s->cohTuner[L.any ? 1 : 0][plan.sizeClass].decided != 0 && c->probeMemory.solo(L.key);
     }
-    if (s->isTlas) {
-        launchTlasKernels(s, q, any, blocks, st);
-        return finish();
+}
+
+// Step 7, the kernels, by the scene's kernel family.
+static int enqueueKernels(tbvh_scene* s, QueryArgs& q, const LaunchPlan& plan, const Launch& L) {
+    tbvh_context* c = s->ctx;
+    const TlasClass t = s->isTlas ? tlasClass(s, L.any) : TlasClass{s->layout, false, nullptr};
+    const KernelFamily family = kernelFamily(s, t);
+    const uint32_t blocks = plan.blocks, blocks7 = plan.blocks7Tlas;
+    q.spillStride = stackEntriesPerLane(c, family);
+    switch (family) {
+    case KernelFamily::kBvh2: launch_bvh2(L.any, s->variant, s->nodes, s->tris, q, c->status, blocks, L.st); break;
+    case KernelFamily::kBvh4: launch_bvh4(L.any, s->variant, s->nodes, q, c->status, blocks, L.st); break;
+    case KernelFamily::kCwbvh: return launchCwbvhKernels(s, q, plan, L);
+    case KernelFamily::kSphere: launch_custom(L.any, s->nodes, s->tris, q, c->status, blocks, L.st); break;
+    case KernelFamily::kVoxel: launch_voxel(L.any, (const uint32_t*)s->nodes.get(), nullptr, nullptr, nullptr, nullptr, q, c->status, blocks, L.st); break;
+    case KernelFamily::kTlasSphere: launch_tlas_custom(L.any, t.layout, s->nodes, s->tlasIdx, s->instances, t.desc, q, c->status, blocks, L.st); break;
+    case KernelFamily::kTlas4: launch_tlas4(L.any, 0, s->tlas4, s->instances, t.desc, q, c->status, blocks, L.st, blocks7); break;
+    case KernelFamily::kTlas8: launch_tlas8(L.any, 0, s->tlas8, s->tlas8Refs, s->instances, t.desc, q, c->status, blocks, L.st, blocks7, t.mix); break;
+    case KernelFamily::kTlasVoxel: launch_voxel(L.any, nullptr, s->nodes, s->tlasIdx, s->instances, t.desc, q, c->status, blocks, L.st); break;
+    case KernelFamily::kTlas2: launch_tlas2(L.any, 0, s->nodes, s->tlasIdx, s->instances, t.desc, q, c->status, blocks, L.st, blocks7); break;
+    case KernelFamily::kTlasFlat: launch_tlas(L.any, t.layout, s->nodes, s->tlasIdx, s->instances, t.desc, q, c->status, blocks, L.st); break;
+    case KernelFamily::kNone: return fail(TBVH_E_INVALID, "scene layout %d has no query kernel", s->layout);
     }
-    switch (s->layout) {
-    case TBVH_LAYOUT_BVH_GPU:
-        q.spillStride = c->spillEntries;
-        launch_bvh2(any, s->variant, s->nodes, s->tris, q, c->status, blocks, st);
-        break;
-    case TBVH_LAYOUT_BVH4_GPU:
-        q.spillStride = c->spillEntries;
-        launch_bvh4(any, s->variant, s->nodes, q, c->status, blocks, st);
-        break;
-    case TBVH_LAYOUT_CWBVH:
-        q.spillStride = c->spillEntries / 2;  // 8-byte entries
-        if (int r = launchCwbvhKernels(s, q, CwbvhLaunch{any, small, probedSmall, sizeClass, blocks, blocksBase, poolArea + (size_t)kPoolParts * kPoolCounterStride, st, solo})) return r;
-        break;
-    case TBVH_LAYOUT_BVH2_WALD:   // a sphere BLAS (kernels_custom.hip)
-        q.spillStride = c->spillEntries / 2;  // 8-byte entries
-        launch_custom(any, s->nodes, s->tris, q, c->status, blocks, st);
-        break;
-    case TBVH_LAYOUT_VOXELSET:
-        q.spillStride = c->spillEntries;
-        launch_voxel(any, (const uint32_t*)s->nodes.get(), nullptr, nullptr, nullptr, nullptr, q, c->status, blocks, st);
-        break;
-    default:
-        return fail(TBVH_E_INVALID, "scene layout %d has no query kernel", s->layout);
+    return 0;
+}
+
+// Step 8, the launch's end, once its kernels are enqueued: the end event, the lane's record of it, the other counter area now zeroed by what was enqueued.
+static int finishLaunch(tbvh_context* c, const Launch& L) {
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(timedEnd(c, L.st));
+    (L.lane ? c->lane1.poolCur : c->poolCur) ^= 1; (L.lane ? c->lane1.poolClean : c->poolClean) = true;
+    if (L.overlaps) {
+        c->book.add(L.lane, L.fp, L.ringSlot, L.launchSeq);
+        c->evChain[L.ringSlot] = c->chain;
+        if (L.lane) { c->lane1Last = c->evRing[L.ringSlot][1]; c->lane1Dirty = true; c->lane1Launches++; }
     }
-    return finish();
+    if (L.remember) c->probeMemory.note(L.key, L.launchSeq, L.lane);
+    return 0;
+}
+
+int launchQuery(tbvh_scene* s, RayRec* d_rays, uint64_t n, uint8_t* d_occ, bool fresh, float freshTmax, const unsigned long long* nDev, bool mayOverlap) {
+    tbvh_context* c = s->ctx;
+    TBVH_LOCK(c);
+    Launch L;
+    L.any = d_occ != nullptr;
+    // Two lanes (overlap_lanes.h): a device-resident query whose buffers no launch in flight touches need not wait for the launches before it — the
+    // persistent grids fill every wave slot, so its workgroups start where the earlier launch's waves retire and its body hides that launch's tail.
+    // Everything else (and every launch while overlap is off, on a caller's stream, untimed or sized on the device) joins the lanes like any entry point.
+    L.overlaps = mayOverlap && c->overlap && c->stream == c->ownStream && !c->skipTiming && !nDev && n != 0 && !launchPrepares(s, n, L.any);
+    if (L.overlaps) HIP_TRY(hipSetDevice(c->device));
+    else if (int r = setDevice(c)) return r;
+    if (n == 0) return 0;
+    tbvh_scene* wide = nullptr;
+    if (int r = prepareScene(s, n, L.any, nDev == nullptr, &wide)) return r;
+    if (wide) return launchQuery(wide, d_rays, n, d_occ, fresh, freshTmax, nDev, mayOverlap);
+    L.fp = footprintOf(d_rays, n, d_occ);
+    QueryArgs q = queryArgsOf(s, d_rays, n, d_occ, fresh, freshTmax, nDev);
+    c->lastProbed = false;
+    LaunchPlan plan;
+    if (int r = planLaunch(s, n, nDev == nullptr, L, &plan)) return r;
+    q.hybridK = s->cw.packed;   // (as the copies now are)
+    if (L.overlaps) if (int r = chooseLane(c, plan.tunerMeasures, L)) return r;
+    L.st = L.lane ? c->lane1.stream : c->stream;
+    if (int r = bindLanePool(c, L, q)) return r;
+    HIP_TRY(timedBegin(c, L.st));   // step 5
+    L.launchSeq = c->evSeq - 1; L.ringSlot = (uint32_t)(L.launchSeq % tbvh_context::kTimeRing);   // (lanes, probe memory: timing is on, it has its event pair)
+    armProbe(s, plan, L, q);
+    if (int r = enqueueKernels(s, q, plan, L)) return r;
+    return finishLaunch(c, L);
 }
 
 int checkStatus(tbvh_context* c) {
+    static const struct { uint32_t bit; const char* message; } kStatusErrors[] = {   // in the order they are looked for: the first bit found is reported
+        {1u, "traversal stack overflow (tree deeper than the spill area allows)"},
+        {2u, "refit: a triangle record refers to a primitive beyond the vertex array"},
+        {4u, "wide TLAS build: the node capacity did not hold the collapsed tree"},
+        {16u, "sphere query: a triangle record refers to a primitive beyond the vertex array"},
+        {kStatusMeshIndex, "mesh: a vertex index of a device-resident index buffer is not a vertex (index >= n_verts)"},
+        {kStatusPoseJoint, "pose: a joint index of a device-resident joint array is not a joint (index >= n_joints); that vertex was not written"},
+        {kStatusOmmIndex, "opacity micromap bake: a device-resident index is not a UV (>= n_uv; clamped) or a texture index is not a texture (>= n_textures; "
+                          "taken as none)"},
+        {kStatusGraph, "scene graph: a sampler, node, key state or key position of a graph was out of range on the device; that channel, node, instance or "
+                       "joint was not written"},
+        {kStatusShade, "shade: a hit record's instance, BLAS slot or primitive, or a device-resident material or texture index, is out of range (the record "
+                       "got no surface, or an untextured albedo of 0)"},
+    };
     uint32_t st = 0;
     if (int r = joinLanes(c)) return r;   // (launches on lane 1 set the status word too)
     HIP_TRY(hipMemcpyAsync(&st, c->status, 4, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
-    if (st & 1u) {
-        hipMemsetAsync(c->status, 0, 4, c->stream);
-        return fail(TBVH_E_FORMAT, "traversal stack overflow (tree deeper than the spill area allows)");
-    }
-    if (st & 2u) {
-        hipMemsetAsync(c->status, 0, 4, c->stream);
-        return fail(TBVH_E_FORMAT, "refit: a triangle record refers to a primitive beyond the vertex array");
-    }
-    if (st & 4u) {
-        hipMemsetAsync(c->status, 0, 4, c->stream);
-        return fail(TBVH_E_FORMAT, "wide TLAS build: the node capacity did not hold the collapsed tree");
-    }
-    if (st & 16u) {
-        hipMemsetAsync(c->status, 0, 4, c->stream);
-        return fail(TBVH_E_FORMAT, "sphere query: a triangle record refers to a primitive beyond the vertex array");
-    }
-    if (st & kStatusMeshIndex) {
-        hipMemsetAsync(c->status, 0, 4, c->stream);
-        return fail(TBVH_E_FORMAT, "mesh: a vertex index of a device-resident index buffer is not a vertex (index >= n_verts)");
-    }
-    if (st & kStatusPoseJoint) {
-        hipMemsetAsync(c->status, 0, 4, c->stream);
-        return fail(TBVH_E_FORMAT, "pose: a joint index of a device-resident joint array is not a joint (index >= n_joints); that vertex was not written");
-    }
-    if (st & kStatusOmmIndex) {
-        hipMemsetAsync(c->status, 0, 4, c->stream);
-        return fail(TBVH_E_FORMAT, "opacity micromap bake: a device-resident index is not a UV (>= n_uv; clamped) or a texture index is not a texture (>= n_textures; taken as none)");
-    }
-    if (st & kStatusGraph) {
-        hipMemsetAsync(c->status, 0, 4, c->stream);
-        return fail(TBVH_E_FORMAT, "scene graph: a sampler, node, key state or key position of a graph was out of range on the device; that channel, node, instance or joint was not written");
-    }
-    if (st & kStatusShade) {
-        hipMemsetAsync(c->status, 0, 4, c->stream);
-        return fail(TBVH_E_FORMAT, "shade: a hit record's instance, BLAS slot or primitive, or a device-resident material or texture index, is out of range (the record got no surface, or an untextured albedo of 0)");
-    }
+    for (const auto& e : kStatusErrors)
+        if (st & e.bit) {
+            hipMemsetAsync(c->status, 0, 4, c->stream);
+            return fail(TBVH_E_FORMAT, "%s", e.message);
+        }
     return 0;
 }
 }  // namespace tbvh_capi
