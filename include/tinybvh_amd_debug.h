@@ -77,6 +77,20 @@ int tbvh_debug_runahead_script(const uint64_t* ops6, uint64_t n_ops, int depth, 
  * 90 / 91 / 92), padded node copy walked}.  TBVH_E_INVALID for other word counts or 0 rays per block. */
 int tbvh_debug_launch_plan(const uint64_t* facts, uint32_t n_facts, uint32_t* out, uint32_t n_out);
 
+/* Which two-level kernel serves a TLAS, and through which arrays it enters each BLAS (tinybvh_amd/csrc/tlas_plan.h: the function the library itself calls when
+ * a TLAS is classified), from the facts it reads; no device, no context.  One case is 5 + n fact words {BLAS count n, the TLAS has had an any-hit query, its
+ * nodes are on the device, nodes an 8-wide TLAS tree would need, blocks a 4-wide one would need} followed by one word per BLAS {layout | pinned by
+ * tbvh_set_variant << 8 | has an 8-wide copy << 9 | has a 4-wide copy << 10}, and gives 13 + n plan words: for closest-hit queries {class layout (0 = mixed),
+ * mix of BVH8_CWBVH and BVH_GPU, kernel family (0 flat loop with the sphere step, 1 k_tlas4, 2 k_tlas8, 3 voxel sets, 4 k_tlas2, 5 flat loop), bytes of a stack
+ * entry}, the same four for any-hit queries, {any-hit queries have a class of their own, the 8-wide tree is wanted, it fits its index range, the 4-wide tree is
+ * wanted, it fits} and one word per BLAS {closest-hit view | any-hit view << 8; 0 its own arrays, 1 its 8-wide copy, 2 its 4-wide copy}.  facts may hold
+ * several cases back to back (n_words in all); out takes their plans back to back (n_out in all).  TBVH_E_INVALID when the word counts do not match. */
+int tbvh_debug_tlas_plan(const uint64_t* facts, uint32_t n_words, uint32_t* out, uint32_t n_out);
+/* The facts a live TLAS would state right now (facts_out: 5 + its BLAS count words) and the plan it has stored (plan_out: 13 + its BLAS count words), in the
+ * words of tbvh_debug_tlas_plan.  The stored plan is the one its launches read: it equals the plan of the facts at all times.  Changes nothing, does not
+ * synchronize.  TBVH_E_INVALID for a scene that is not a TLAS (or a BVH_DOUBLE one). */
+int tbvh_debug_tlas_state(tbvh_scene* scene, uint64_t* facts_out, uint32_t* plan_out);
+
 /* The wave-packet kernel's child filter (tinybvh_amd/csrc/packet_cull.h) beside its exact per-lane test, for ONE 64-ray chunk against n_nodes BVH8_CWBVH nodes
  * (80 bytes each), on the host as k_cwbvh_packet runs them; no device, no context.  rays64: 64 ray records of 64 bytes (O, D, rD, hit; O and rD are read);
  * have_mask: bit l = lane l holds a ray (at least one); tcull64: each lane's cull distance as the kernel forms it (cull_bound(hit.t), -1 for a ray that is out

@@ -16,8 +16,9 @@ Every test runs over the rows of tests/tlas_edges_lib.py (CONFIGS), one per clas
     g    BVH4_GPU (1) + BVH8_CWBVH (72)      k_tlas_flat_*                     k_tlas_flat_*
     h    spheres + BVH4_GPU                  k_tlas_flat_sph_*                 k_tlas_flat_sph_*
 
-(derived from reclassifyTlas / blasView / launchTlasKernels: see the helper's docstring).  Where a copy decides the class, the scene fixture asserts
-that device_bytes of the BLAS grows exactly when that copy is made, as tests/test_bvh_gpu_wide_copy.py does.
+(the rule is tinybvh_amd/csrc/tlas_plan.h; tests/test_tlas_plan_host.py holds these rows to it on the CPU).  The scene fixture asserts through
+TLAS.debug_plan() that each row's TLAS has stored the kernel family and views the table names, for Intersect at the upload and for IsOccluded after the first
+one, and, where a copy decides the class, that device_bytes of the BLAS grows exactly when that copy is made, as tests/test_bvh_gpu_wide_copy.py does.
 
 The expectation is the restated BVH::IntersectTLAS under the library's tie rule (oracle/tbvh_oracle.c), pinned on these very instances and rays
 against the real reference by test_restated_tlas_traversal_equals_the_reference_on_hostile_instances.  Row h takes the TLAS restatement of
@@ -51,7 +52,8 @@ ROWS = list(E.CONFIGS)
 class Scene:
     """The BLASes of one row, the hostile-instance TLAS over them, its rays and the oracle's records for them (computed once)."""
 
-    def __init__(self, ctx, oracle, cu, key):
+    def __init__(self, ctx, oracle, cu, key, on_upload=None):
+        """on_upload(scene): called once the TLAS is uploaded and the expectation computed, before the TLAS's first query (tests/test_tlas_plan_gpu.py)"""
         self.key, self.row, self.ctx, self.oracle, self.cu = key, E.CONFIGS[key], ctx, oracle, cu
         row = self.row
         vs = E.meshes()
@@ -75,14 +77,19 @@ class Scene:
         self.tlas = tb.TLAS(ctx).Build(self.inst, self.blas)
         self.bounds = self.tlas._blas_bounds(self.blas)
         after_build = [b.device_bytes for b in self.blas]
+        E.assert_kernel(self.tlas.debug_plan()[1]["closest"], row.intersect)      # the row reaches the kernel it is named after (tlas_plan.h)
         self.rays, self.groups = E.ray_groups(self.inst, self.tri_meshes)
+        self.diag = E.scene_diagonal(self.inst)
+        self.want = self.expect(self.rays)
+        if on_upload:
+            on_upload(self)
         self.tlas.IsOccluded(self.rays[:64])     # the TLAS's first any-hit query makes the 8-wide copies
         after_occ = [b.device_bytes for b in self.blas]
+        plan = self.tlas.debug_plan()[1]
+        E.assert_kernel(plan["closest"], row.intersect); E.assert_kernel(plan["any"], row.occluded)
         for k, (at_build, at_occ) in enumerate(row.grows):   # the observable for the kernel class (module docstring)
             assert (after_build[k] > before[k]) == at_build, (key, k, "4-wide copy at the TLAS upload", before[k], after_build[k])
             assert (after_occ[k] > after_build[k]) == at_occ, (key, k, "8-wide copy at the first IsOccluded", after_build[k], after_occ[k])
-        self.diag = E.scene_diagonal(self.inst)
-        self.want = self.expect(self.rays)
 
     def host_tree(self):
         h = self.tlas.host

@@ -2,10 +2,12 @@
 the table of BLAS configurations, one per class of two-level kernel and kind of query, the hostile instance families, the ray groups traced
 through them, hand-made TLAS trees (Wald nodes for the oracle, Aila-Laine nodes for TLAS.Upload) and the deep-chain scene.
 
-Which kernel serves a configuration follows from capi_scene.hip (reclassifyTlas), capi_copies.hip (blasView) and capi_query.hip
-(launchTlasKernels).  A BLAS with variant 0 is entered by closest-hit queries through its 4-wide copy (BVH_GPU, BVH8_CWBVH; made at the TLAS
+Which kernel serves a configuration is the rule of tinybvh_amd/csrc/tlas_plan.h, which capi_scene.hip (reclassifyTlas) applies and capi_query.hip
+(enqueueKernels) reads.  A BLAS with variant 0 is entered by closest-hit queries through its 4-wide copy (BVH_GPU, BVH8_CWBVH; made at the TLAS
 upload, from 64 entries on) and by any-hit queries through its 8-wide copy (BVH_GPU, BVH4_GPU; made by the TLAS's first IsOccluded); a forced
-variant on the BLAS pins the uploaded nodes for both.  Any-hit queries get a class of their own only where the 8-wide kernel serves it.
+variant on the BLAS pins the uploaded nodes for both.  Any-hit queries get a class of their own only where the 8-wide kernel serves it.  The table is
+checked twice: tests/test_tlas_plan_host.py holds each row to the rule on the CPU, and the scene fixture of tests/test_tlas_edges_gpu.py asserts through
+TLAS.debug_plan() that the row's live TLAS stores that family and those views (assert_kernel below).
 
     row  BLASes (variant)                    Intersect                         IsOccluded
     a    BVH4_GPU                            k_tlas4, uploaded nodes           k_tlas8, 8-wide copies
@@ -47,6 +49,18 @@ CONFIGS = {
     "g": Row((L4, L8), (1, 72), ((False, False), (False, False)), "flat", "flat"),
     "h": Row((LS, L4), (0, 0), ((False, False), (False, False)), "flatsph", "flatsph"),
 }
+
+# a Row's kernel name in the words of TLAS.debug_plan() / tbvh_debug_tlas_plan: (family, mix, the view every BLAS is entered through, or None where it
+# depends on the BLAS's layout)
+KERNEL_PLAN = {"tlas4": ("Tlas4", False, None), "tlas8": ("Tlas8", False, "own"), "tlas8copy": ("Tlas8", False, "copy8"), "tlas8mixed": ("Tlas8", True, "own"),
+               "tlas2": ("Tlas2", False, "own"), "flat": ("TlasFlat", False, "own"), "flatsph": ("TlasSphere", False, "own")}
+
+
+def assert_kernel(kind, name):
+    """kind: plan["closest"] or plan["any"] of TLAS.debug_plan(); name: a Row's `intersect` or `occluded`"""
+    family, mix, view = KERNEL_PLAN[name]
+    assert kind["family"] == family and kind["mix"] == mix, (name, kind)
+    assert view is None or all(v == view for v in kind["views"]), (name, kind)
 
 
 # ---- BLAS meshes ------------------------------------------------------------------------------------------------------------------------

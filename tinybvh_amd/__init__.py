@@ -912,6 +912,24 @@ def make_instances(transforms: np.ndarray, blas_idx, mask: int = 0xFFFF) -> np.n
     return inst
 
 
+TLAS_FAMILIES = ("TlasSphere", "Tlas4", "Tlas8", "TlasVoxel", "Tlas2", "TlasFlat")   # tlas_plan.h: TlasFamily
+TLAS_VIEWS = ("own", "copy8", "copy4")                                                # tlas_plan.h: TlasView
+
+
+def tlas_facts_dict(w) -> dict:
+    """one case of tbvh_debug_tlas_plan's fact words, named"""
+    blas = [{"layout": int(x) & 0xFF, "pinned": bool(int(x) >> 8 & 1), "has8": bool(int(x) >> 9 & 1), "has4": bool(int(x) >> 10 & 1)} for x in w[5:]]
+    return {"any_hit_seen": bool(w[1]), "has_nodes": bool(w[2]), "cap8": int(w[3]), "cap4": int(w[4]), "blas": blas, "words": np.array(w, np.uint64)}
+
+
+def tlas_plan_dict(w) -> dict:
+    """one case of tbvh_debug_tlas_plan's plan words, named"""
+    kind = lambda k, shift: {"layout": int(w[k]), "mix": bool(w[k + 1]), "family": TLAS_FAMILIES[int(w[k + 2])], "entry_bytes": int(w[k + 3]),
+                             "views": [TLAS_VIEWS[int(x) >> shift & 0xFF] for x in w[13:]]}
+    return {"closest": kind(0, 0), "any": kind(4, 8), "any_own": bool(w[8]), "want8": bool(w[9]), "fits8": bool(w[10]), "want4": bool(w[11]), "fits4": bool(w[12]),
+            "words": np.array(w, np.uint32)}
+
+
 class TLAS(_Scene):
     """Top-level BVH over BLAS instances: BVH_GPU nodes over BLASInstance records
     (BVH_GPU::Build(BLASInstance*, ...), tiny_bvh.h:4575-4581; tiny_bvh_gpu2.cpp:108-136)."""
@@ -953,6 +971,14 @@ class TLAS(_Scene):
               "tbvh_update_tlas")
         return self
 
+
+    def debug_plan(self):
+        """(facts, plan) as dicts: the facts this TLAS would state right now and the plan it has stored (tbvh_debug_tlas_state; the word layout is
+        tbvh_debug_tlas_plan's, include/tinybvh_amd_debug.h); each also carries its raw words under "words"."""
+        n = len(self.blas)
+        fw, pw = np.zeros(5 + n, np.uint64), np.zeros(13 + n, np.uint32)
+        check(lib.tbvh_debug_tlas_state(self._h, _ptr(fw), _ptr(pw)), "tbvh_debug_tlas_state")
+        return tlas_facts_dict(fw), tlas_plan_dict(pw)
 
     def _blas_bounds(self, blas: list) -> np.ndarray:
         bounds = np.zeros((len(blas), 6), np.float32)

@@ -83,6 +83,8 @@ SYMBOLS = {
     "tbvh_debug_probe_memory_stats": (_i, [_vp, _vp]),
     "tbvh_debug_runahead_script": (_i, [_vp, _u64, _i, _vp]),
     "tbvh_debug_launch_plan": (_i, [_vp, _u32, _vp, _u32]),
+    "tbvh_debug_tlas_plan": (_i, [_vp, _u32, _vp, _u32]),
+    "tbvh_debug_tlas_state": (_i, [_vp, _vp, _vp]),
     "tbvh_debug_packet_cull": (_i, [_vp, _u64, _vp, _u64, _vp, _vp, _vp, _vp]),
     "tbvh_set_timing": (_i, [_vp, _i]),
     "tbvh_upload_bvh_gpu": (_i, [_vp, _vp, _u64, _vp, _u64, _vp, _u64, _pp]),

@@ -304,6 +304,42 @@ int tbvh_debug_launch_plan(const uint64_t* facts, uint32_t nFacts, uint32_t* out
     return 0;
 }
 
+// What reclassifyTlas plans for a TLAS (tlas_plan.h: the function it calls), from facts stated as words; no device, no scene (tests/test_tlas_plan_host.py).
+int tbvh_debug_tlas_plan(const uint64_t* facts, uint32_t nWords, uint32_t* out, uint32_t nOut) {
+    if (!facts || !out) return fail(TBVH_E_INVALID, "tbvh_debug_tlas_plan: null argument");
+    std::vector<TlasBlasFacts> blas;
+    std::vector<TlasView> v0, v1;
+    uint32_t at = 0, atOut = 0;
+    while (at < nWords) {   // cases back to back, each as long as its BLAS count says
+        const uint64_t n = nWords - at >= kTlasFactHead ? facts[at] : ~0ull;
+        if (n == 0 || n > nWords - at - kTlasFactHead || n > nOut - atOut || kTlasPlanHead > nOut - atOut - n)
+            return fail(TBVH_E_INVALID, "tbvh_debug_tlas_plan: the case at word %u does not fit %u fact words and %u plan words", at, nWords, nOut);
+        blas.resize(n); v0.resize(n); v1.resize(n);
+        for (uint64_t i = 0; i < n; i++) blas[i] = tlasBlasFactsFromWord(facts[at + kTlasFactHead + i]);
+        TlasFacts f;
+        f.blas = blas.data(); f.nBlas = (uint32_t)n; f.anyHitSeen = facts[at + 1] != 0; f.hasNodes = facts[at + 2] != 0; f.cap8 = facts[at + 3]; f.cap4 = facts[at + 4];
+        TlasView* const view[2] = {v0.data(), v1.data()};
+        const TlasPlan p = planTlas(f, view);
+        tlasPlanToWords(p, view, f.nBlas, out + atOut);
+        at += kTlasFactHead + (uint32_t)n; atOut += kTlasPlanHead + (uint32_t)n;
+    }
+    if (atOut != nOut) return fail(TBVH_E_INVALID, "tbvh_debug_tlas_plan: %u plan words for cases that fill %u", nOut, atOut);
+    return 0;
+}
+
+// ... and the facts a live TLAS would state now beside the plan it has stored (tests/test_tlas_plan_gpu.py)
+int tbvh_debug_tlas_state(tbvh_scene* s, uint64_t* factsOut, uint32_t* planOut) {
+    if (!s || !s->isTlas || s->layout == TBVH_LAYOUT_BVH_DOUBLE || !factsOut || !planOut) return fail(TBVH_E_INVALID, "tbvh_debug_tlas_state: not a TLAS, or a null argument");
+    TBVH_LOCK(s->ctx);
+    std::vector<TlasBlasFacts> blas;
+    const TlasFacts f = tlasFactsNow(s, blas);
+    factsOut[0] = f.nBlas; factsOut[1] = f.anyHitSeen; factsOut[2] = f.hasNodes; factsOut[3] = f.cap8; factsOut[4] = f.cap4;
+    for (uint32_t i = 0; i < f.nBlas; i++) factsOut[kTlasFactHead + i] = tlasBlasFactsToWord(blas[i]);
+    const TlasView* const view[2] = {s->tlas.view[0].data(), s->tlas.view[1].data()};
+    tlasPlanToWords(s->tlas.plan, view, f.nBlas, planOut);
+    return 0;
+}
+
 int tbvh_debug_set_overlap_depth(tbvh_context* c, int depth) {
     if (!c) return fail(TBVH_E_INVALID, "tbvh_debug_set_overlap_depth: null context");
     if (depth < 1 || depth > LaneBook::kMaxDepth) return fail(TBVH_E_INVALID, "tbvh_debug_set_overlap_depth: depth %d (1..%d)", depth, LaneBook::kMaxDepth);

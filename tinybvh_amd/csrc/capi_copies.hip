@@ -185,18 +185,14 @@ static tbvh_scene* buildCopy(tbvh_scene* s, int target, bool forTlas) {
     return w;
 }
 
-// What a TLAS traverses for BLAS b, by the kind of query (round 6; 1000 instances of a 100 k-triangle BLAS, camera / shadow / random MRays/s in DESIGN.md par. 3.5):
-// closest hits through a 4-wide stream — a BVH4_GPU BLAS's own, the 4-wide copy of a BVH_GPU / BVH8_CWBVH one (k_tlas4 is the fastest two-level kernel for
-// closest hits) —, any-hit queries through 8-wide nodes — a BVH8_CWBVH BLAS's own, the 8-wide copy of the others (k_tlas8 is the fastest there).  A forced
-// variant on the BLAS (tbvh_set_variant) pins the uploaded nodes; allow4 = false: the closest-hit view without the 4-wide copies (reclassifyTlas's fallback).
-const tbvh_scene* blasView(const tbvh_scene* b, bool any, bool allow4) {
-    const tbvh_scene* w8 = b->copies.copy8;
-    const tbvh_scene* w4 = b->copies.copy4;
-    if (b->variant != 0) return b;
-    if (!any && allow4 && w4 && (b->layout == TBVH_LAYOUT_BVH_GPU || b->layout == TBVH_LAYOUT_CWBVH)) return w4;   // closest hits: the 4-wide kernel
-    const bool viaCopy = w8 && (b->layout == TBVH_LAYOUT_BVH_GPU || (any && b->layout == TBVH_LAYOUT_BVH4_GPU));
-    return viaCopy ? w8 : b;
+// What a TLAS traverses for BLAS b is tlas_plan.h's rule (sentences 1 - 4) over these facts; the numbers behind it (1000 instances of a 100 k-triangle BLAS,
+// camera / shadow / random MRays/s) are in DESIGN.md par. 3.5: k_tlas4 is the fastest two-level kernel for closest hits, k_tlas8 for any-hit queries.
+TlasBlasFacts tlasBlasFacts(const tbvh_scene* b) {
+    TlasBlasFacts f;
+    f.layout = b->layout; f.pinned = b->variant != 0; f.has8 = b->copies.copy8 != nullptr; f.has4 = b->copies.copy4 != nullptr;
+    return f;
 }
+const tbvh_scene* blasView(const tbvh_scene* b, TlasView v) { return v == kViewWide4 ? b->copies.copy4 : v == kViewWide8 ? b->copies.copy8 : b; }
 
 // the 8-wide copy is of a BVH_GPU / BVH4_GPU scene, the 4-wide one of a BVH_GPU / BVH8_CWBVH one and always for the TLASes over it
 static bool layoutHasCopy(const tbvh_scene* s, CopyKind kind) {
@@ -231,7 +227,7 @@ void dropCopiesAfterUpdate(tbvh_scene* s) {
     s->copies.policy.dropped(live);
     hipStreamSynchronize(s->ctx->stream);
     freeCopy(s, kCopyWide8); freeCopy(s, kCopyWide4);
-    forEachTlasOver(s, [](tbvh_scene* t) { (void)reclassifyTlas(t); t->blasRecopyPending = true; return 0; });   // (the TLASes enter this BLAS through its own nodes meanwhile)
+    forEachTlasOver(s, [](tbvh_scene* t) { (void)reclassifyTlas(t); t->tlas.blasRecopyPending = true; return 0; });   // (the TLASes enter this BLAS through its own nodes meanwhile)
 }
 
 // one query on BLAS b (or through a TLAS over it) since its copies were dropped: they come back once the blob has settled
@@ -243,11 +239,11 @@ static void countQueryOn(tbvh_scene* b) {
 
 void countQueryForRecopy(tbvh_scene* s) {
     if (!s->isTlas) { if (s->copies.pending()) countQueryOn(s); return; }
-    if (!s->blasRecopyPending) return;
+    if (!s->tlas.blasRecopyPending) return;
     bool still = false;
-    for (tbvh_scene* b : s->blasList)
+    for (tbvh_scene* b : s->tlas.blasList)
         if (b->copies.pending()) { countQueryOn(b); still |= b->copies.pending() != 0; }
-    s->blasRecopyPending = still;
+    s->tlas.blasRecopyPending = still;
 }
 
 tbvh_scene* wideCopyForQuery(tbvh_scene* s) { return s->variant == 0 && !s->copies.tlasOnly ? s->copies.copy8 : nullptr; }

@@ -65,7 +65,7 @@ TlasLayout tlasLayout(uint64_t capNodes, uint64_t capIdx, uint64_t capInst, uint
 struct TlasParts { NodeDbl* nodes; uint64_t* idx; InstanceDbl* inst; BlasDbl* blas; };
 TlasParts tlasParts(const tbvh_scene* s) {
     char* base = (char*)s->nodes.get();
-    const TlasLayout l = tlasLayout(s->dblCapNodes, s->dblCapIdx, s->dblCapInst, s->nBlas);
+    const TlasLayout l = tlasLayout(s->dblCapNodes, s->dblCapIdx, s->dblCapInst, s->tlas.nBlas);
     return TlasParts{(NodeDbl*)base, (uint64_t*)(base + l.oIdx), (InstanceDbl*)(base + l.oInst), (BlasDbl*)(base + l.oBlas)};
 }
 
@@ -235,7 +235,7 @@ int tbvh_upload_tlas_double(tbvh_context* c, const void* nodes64, uint64_t nNode
     for (uint64_t i = 0; i < nBlas; i++) descs[i] = BlasDbl{(const NodeDbl*)blas[i]->nodes.get(), (const TriDbl*)blas[i]->tris.get()};
     tbvh_scene* s = newScene(c, TBVH_LAYOUT_BVH_DOUBLE);
     if (!s) return fail(TBVH_E_NOMEM, "out of host memory");
-    s->isTlas = true; s->nTlasNodes = nNodes; s->nTlasIdx = nIdx; s->nInst = nInst; s->nBlas = nBlas; s->nNodes = (uint32_t)nNodes;
+    s->isTlas = true; s->tlas.nTlasNodes = nNodes; s->tlas.nTlasIdx = nIdx; s->tlas.nInst = nInst; s->tlas.nBlas = nBlas; s->nNodes = (uint32_t)nNodes;
     s->dblCapNodes = nNodes; s->dblCapIdx = nIdx; s->dblCapInst = nInst;
     const TlasLayout lay = tlasLayout(nNodes, nIdx, nInst, nBlas);
     const uint64_t oIdx = lay.oIdx, oInst = lay.oInst, oBlas = lay.oBlas, total = lay.total;
@@ -249,7 +249,7 @@ int tbvh_upload_tlas_double(tbvh_context* c, const void* nodes64, uint64_t nNode
         tbvh_free_scene(s);
         return fail(TBVH_E_HIP, "tbvh_upload_tlas_double: copy to the device failed");
     }
-    for (uint64_t i = 0; i < nBlas; i++) { s->blasList.push_back(blas[i]); blas[i]->usedBy.push_back(s); }   // (the BLASes outlive the TLAS: tbvh_free_scene)
+    for (uint64_t i = 0; i < nBlas; i++) { s->tlas.blasList.push_back(blas[i]); blas[i]->usedBy.push_back(s); }   // (the BLASes outlive the TLAS: tbvh_free_scene)
     s->bytes = total;
     *out = s;
     return 0;
@@ -375,21 +375,21 @@ int checkDoubleScene(const tbvh_scene* s, bool wantTlas, const char* who) {
     return 0;
 }
 
-void accountTlas(tbvh_scene* s) { s->bytes = tlasLayout(s->dblCapNodes, s->dblCapIdx, s->dblCapInst, s->nBlas).total + s->buildScratch.count(); }
+void accountTlas(tbvh_scene* s) { s->bytes = tlasLayout(s->dblCapNodes, s->dblCapIdx, s->dblCapInst, s->tlas.nBlas).total + s->buildScratch.count(); }
 
 // The TLAS in a new allocation whose parts hold capNodes / capIdx / capInst (each at least what the scene holds now): everything is carried over, the
 // BLAS descriptors with it, so the scene answers as before; synchronizes, then the old allocation goes.  A failure leaves the scene as it was.
 int moveTlas(tbvh_scene* s, uint64_t capNodes, uint64_t capIdx, uint64_t capInst, const char* who) {
     tbvh_context* c = s->ctx;
-    const TlasLayout l = tlasLayout(capNodes, capIdx, capInst, s->nBlas);
+    const TlasLayout l = tlasLayout(capNodes, capIdx, capInst, s->tlas.nBlas);
     DevBuf<float4> fresh;
     if (fresh.alloc(l.total / 16) != hipSuccess) return fail(TBVH_E_NOMEM, "%s: out of device memory", who);
     const TlasParts o = tlasParts(s);
     char* base = (char*)fresh.get();
-    if (hipMemcpyAsync(base, o.nodes, s->nTlasNodes * sizeof(NodeDbl), hipMemcpyDeviceToDevice, c->stream) != hipSuccess ||
-        hipMemcpyAsync(base + l.oIdx, o.idx, s->nTlasIdx * 8, hipMemcpyDeviceToDevice, c->stream) != hipSuccess ||
-        hipMemcpyAsync(base + l.oInst, o.inst, s->nInst * sizeof(InstanceDbl), hipMemcpyDeviceToDevice, c->stream) != hipSuccess ||
-        hipMemcpyAsync(base + l.oBlas, o.blas, s->nBlas * sizeof(BlasDbl), hipMemcpyDeviceToDevice, c->stream) != hipSuccess ||
+    if (hipMemcpyAsync(base, o.nodes, s->tlas.nTlasNodes * sizeof(NodeDbl), hipMemcpyDeviceToDevice, c->stream) != hipSuccess ||
+        hipMemcpyAsync(base + l.oIdx, o.idx, s->tlas.nTlasIdx * 8, hipMemcpyDeviceToDevice, c->stream) != hipSuccess ||
+        hipMemcpyAsync(base + l.oInst, o.inst, s->tlas.nInst * sizeof(InstanceDbl), hipMemcpyDeviceToDevice, c->stream) != hipSuccess ||
+        hipMemcpyAsync(base + l.oBlas, o.blas, s->tlas.nBlas * sizeof(BlasDbl), hipMemcpyDeviceToDevice, c->stream) != hipSuccess ||
         hipStreamSynchronize(c->stream) != hipSuccess)
         return fail(TBVH_E_HIP, "%s: moving the TLAS failed", who);
     s->nodes = std::move(fresh);
@@ -408,7 +408,7 @@ int tbvh_rebuild_tlas_double_device(tbvh_scene* s, const void* transformsDbl16, 
     if (transformsDbl16 && onDevice && (((uintptr_t)transformsDbl16) & 7)) return fail(TBVH_E_INVALID, "%s: device transforms must be 8-byte aligned", who);
     tbvh_context* c = s->ctx;
     TBVH_ENTER(c);
-    const uint64_t n = s->nInst;
+    const uint64_t n = s->tlas.nInst;
     if (n == 0 || n > 0x7fffffffull) return fail(TBVH_E_INVALID, "%s: %llu instances", who, (unsigned long long)n);
     // an LBVH over n leaves has 2n - 1 nodes and n index entries: the first rebuild moves an uploaded TLAS that holds fewer
     const uint64_t nNodes = 2 * n - 1;
@@ -432,8 +432,8 @@ int tbvh_rebuild_tlas_double_device(tbvh_scene* s, const void* transformsDbl16, 
     }
     const TlasParts p = tlasParts(s);
     HIP_TRY(timedBegin(c));
-    HIP_TRY(launch_tlas_dbl_rebuild(p.nodes, p.idx, p.inst, p.blas, s->nBlas, xf, (uint32_t)n, s->buildScratch, s->sortTempBytes, c->stream));
-    s->nTlasNodes = nNodes; s->nTlasIdx = n; s->nNodes = (uint32_t)nNodes;
+    HIP_TRY(launch_tlas_dbl_rebuild(p.nodes, p.idx, p.inst, p.blas, s->tlas.nBlas, xf, (uint32_t)n, s->buildScratch, s->sortTempBytes, c->stream));
+    s->tlas.nTlasNodes = nNodes; s->tlas.nTlasIdx = n; s->nNodes = (uint32_t)nNodes;
     HIP_TRY(timedEnd(c));
     return 0;
 }
@@ -446,8 +446,8 @@ int tbvh_update_tlas_double(tbvh_scene* s, const void* nodes64, uint64_t nNodes,
     if (validateDouble((const NodeDbl*)nodes64, nNodes, idx, nIdx, nInst, who, "n_inst")) return TBVH_E_INVALID;
     const InstanceDbl* inst = (const InstanceDbl*)instances320;
     for (uint64_t i = 0; i < nInst; i++)
-        if (inst[i].blasIdx >= s->nBlas)
-            return fail(TBVH_E_INVALID, "%s: instance %llu: blasIdx %llu >= n_blas = %llu", who, (unsigned long long)i, (unsigned long long)inst[i].blasIdx, (unsigned long long)s->nBlas);
+        if (inst[i].blasIdx >= s->tlas.nBlas)
+            return fail(TBVH_E_INVALID, "%s: instance %llu: blasIdx %llu >= n_blas = %llu", who, (unsigned long long)i, (unsigned long long)inst[i].blasIdx, (unsigned long long)s->tlas.nBlas);
     tbvh_context* c = s->ctx;
     TBVH_ENTER(c);
     if (nNodes > s->dblCapNodes || nIdx > s->dblCapIdx || nInst > s->dblCapInst)   // the TLAS grew
@@ -458,7 +458,7 @@ int tbvh_update_tlas_double(tbvh_scene* s, const void* nodes64, uint64_t nNodes,
         hipMemcpyAsync(p.inst, inst, nInst * sizeof(InstanceDbl), hipMemcpyHostToDevice, c->stream) != hipSuccess ||
         hipStreamSynchronize(c->stream) != hipSuccess)   // (the caller's arrays may go away)
         return fail(TBVH_E_HIP, "%s: copy to the device failed", who);
-    s->nTlasNodes = nNodes; s->nTlasIdx = nIdx; s->nInst = nInst; s->nNodes = (uint32_t)nNodes;
+    s->tlas.nTlasNodes = nNodes; s->tlas.nTlasIdx = nIdx; s->tlas.nInst = nInst; s->nNodes = (uint32_t)nNodes;
     return 0;
 }
 
@@ -469,14 +469,14 @@ int tbvh_tlas_double_download(tbvh_scene* s, void* nodes64, uint64_t capNodes, u
     tbvh_context* c = s->ctx;
     TBVH_ENTER(c);
     HIP_TRY(hipStreamSynchronize(c->stream));
-    if (nNodesOut) *nNodesOut = s->nTlasNodes;
-    if (nodes64 && capNodes < s->nTlasNodes) return fail(TBVH_E_INVALID, "%s: node buffer too small", who);
-    if (idx && capIdx < s->nTlasIdx) return fail(TBVH_E_INVALID, "%s: index buffer too small", who);
-    if (instances320 && capInst < s->nInst) return fail(TBVH_E_INVALID, "%s: instance buffer too small", who);
+    if (nNodesOut) *nNodesOut = s->tlas.nTlasNodes;
+    if (nodes64 && capNodes < s->tlas.nTlasNodes) return fail(TBVH_E_INVALID, "%s: node buffer too small", who);
+    if (idx && capIdx < s->tlas.nTlasIdx) return fail(TBVH_E_INVALID, "%s: index buffer too small", who);
+    if (instances320 && capInst < s->tlas.nInst) return fail(TBVH_E_INVALID, "%s: instance buffer too small", who);
     const TlasParts p = tlasParts(s);
-    if (nodes64) HIP_TRY(hipMemcpy(nodes64, p.nodes, s->nTlasNodes * sizeof(NodeDbl), hipMemcpyDeviceToHost));
-    if (idx) HIP_TRY(hipMemcpy(idx, p.idx, s->nTlasIdx * 8, hipMemcpyDeviceToHost));
-    if (instances320) HIP_TRY(hipMemcpy(instances320, p.inst, s->nInst * sizeof(InstanceDbl), hipMemcpyDeviceToHost));
+    if (nodes64) HIP_TRY(hipMemcpy(nodes64, p.nodes, s->tlas.nTlasNodes * sizeof(NodeDbl), hipMemcpyDeviceToHost));
+    if (idx) HIP_TRY(hipMemcpy(idx, p.idx, s->tlas.nTlasIdx * 8, hipMemcpyDeviceToHost));
+    if (instances320) HIP_TRY(hipMemcpy(instances320, p.inst, s->tlas.nInst * sizeof(InstanceDbl), hipMemcpyDeviceToHost));
     return 0;
 }
 

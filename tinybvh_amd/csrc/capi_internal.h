@@ -31,6 +31,7 @@
 #include "overlap_lanes.h"
 #include "probe_memory.h"
 #include "ray_pool.h"
+#include "tlas_plan.h"
 
 using namespace tbvh;
 using tbvh_capi::DevBuf;
@@ -42,6 +43,8 @@ using tbvh_capi::kCopyWide8;
 static_assert(kLayoutBvhGpu == TBVH_LAYOUT_BVH_GPU && kLayoutBvh4Gpu == TBVH_LAYOUT_BVH4_GPU && kLayoutCwbvh == TBVH_LAYOUT_CWBVH,
               "kernels.h and the public header agree on the layout codes");
 static_assert(tbvh_capi::kPlanLayoutCwbvh == TBVH_LAYOUT_CWBVH, "launch_plan.h and the public header agree on BVH8_CWBVH's code");
+static_assert(tbvh_capi::kTlasLayoutSphere == TBVH_LAYOUT_BVH2_WALD && tbvh_capi::kTlasLayoutBvhGpu == TBVH_LAYOUT_BVH_GPU && tbvh_capi::kTlasLayoutBvh4Gpu == TBVH_LAYOUT_BVH4_GPU &&
+              tbvh_capi::kTlasLayoutCwbvh == TBVH_LAYOUT_CWBVH && tbvh_capi::kTlasLayoutVoxel == TBVH_LAYOUT_VOXELSET, "tlas_plan.h and the public header agree on the layout codes");
 
 namespace tbvh_capi {
 int fail(int code, const char* fmt, ...);   // sets tbvh_last_error() of the calling thread, returns code
@@ -234,6 +237,41 @@ struct CwbvhLayouts {
     bool levelOrder = false;     // the node array is in level order (made on the device): the hybrid copy needs no renumbering
 };
 
+// What only a TLAS holds (capi_scene.hip makes, classifies, updates and rebuilds it; a BVH_DOUBLE TLAS — capi_double.hip — uses the counts and the BLAS
+// list).  WHICH arrays each BLAS is entered through, which wide trees are kept and which kernel serves a query is `plan` (tlas_plan.h), stated again by
+// reclassifyTlas whenever a fact it reads changes; `bytes` of the scene is derived from what is held here (tlasBytes).
+struct TlasState {
+    DevBuf<uint32_t> tlasIdx;
+    DevBuf<float4> instances;   // 12 per instance
+    uint64_t nInst = 0, nBlas = 0, nTlasNodes = 0, nTlasIdx = 0;
+    std::vector<tbvh_scene*> blasList;   // its BLASes, in blasIdx order
+    bool blasSpheres = false;         // some BLAS is a sphere BLAS (capi_custom.hip): every query takes the flat loop with the sphere step, BLASes in their own layouts
+    bool anyHitSeen = false;          // the TLAS has had an any-hit query: only then do its BVH4_GPU BLASes get their 8-wide copies and the second wide tree is kept (a frame loop that only
+                                      // ever calls Intersect pays for neither: per frame the second tree's rebuild and the copies' refit cost 0.27 ms at 1000 instances)
+    bool blasRecopyPending = false;   // the copies of some BLAS are waiting to be made again (copy_policy.h)
+    // the plan in force, the views it chose per BLAS ([0] closest-hit, [1] any-hit) and the descriptor tables uploaded for them; blasDescAny only while any-hit
+    // queries have a class of their own (BVH4_GPU BLASes: their own stream for closest hits — k_tlas4 —, their 8-wide copies for IsOccluded — k_tlas8, + 28 % on 1000 instances)
+    tbvh_capi::TlasPlan plan;
+    std::vector<tbvh_capi::TlasView> view[2];
+    DevBuf<BlasDesc> blasDesc, blasDescAny;
+    // the same TLAS collapsed 4-wide in the BVH4_GPU node format (kernels_tlas4.hip) and 8-wide in the BVH8_CWBVH one (kernels_tlas8.hip), whichever the plan
+    // wants, kept current by every upload / update / device rebuild; one scratch area for both builds
+    DevBuf<float4> tlas4;             // count(): blocks
+    DevBuf<float4> tlas8;             // 5 per node: count() / 5 = nodes the wide tree may have (allocated after tlas8Refs: never there without them)
+    DevBuf<uint32_t> tlas8Refs;       // instance references: the same number
+    DevBuf<void> tlas4Scratch;
+    // device-side TLAS rebuild (kernels_tlasbuild.hip)
+    DevBuf<float> blasBounds;         // 6 floats per BLAS
+    // tbvh_tlas_set_builder: 0 = LBVH, 2 = the reference's SAH tree (kernels_sahbuild.hip over the instance records, then the device Aila-Laine encode).
+    // The SAH build keeps its Wald nodes (2 n) and its scratch here, sized for tlasSahFor instances: no allocation per frame; `bytes` counts them.
+    int tlasBuilder = 0;
+    DevBuf<float4> tlasWald;
+    DevBuf<void> tlasSah;
+    uint64_t tlasSahFor = 0;
+    size_t tlasSahSort = 0, tlasSahScan = 0;
+    DevBuf<float> xformStage;         // staged transforms (16 floats per instance) when the caller passes host memory
+};
+
 struct tbvh_scene {
     tbvh_context* ctx = nullptr;
     int layout = 0;
@@ -248,48 +286,18 @@ struct tbvh_scene {
     uint64_t capNodeBlocks = 0, capTriBlocks = 0;   // what the allocations hold (tbvh_update_*: a re-converted blob of at most this size goes in place)
     uint64_t topoHash = 0;       // CWBVH: hash of every node's (imask, child base): an update with the same topology keeps the hybrid copy's numbering
     uint64_t bytes = 0;
-    // TLAS (layout = BVH_GPU nodes in `nodes`)
+    // TLAS (layout = BVH_GPU nodes in `nodes`; a BVH_DOUBLE TLAS keeps its counts and BLAS list in `tlas` too)
     bool isTlas = false;
-    DevBuf<uint32_t> tlasIdx;
-    DevBuf<float4> instances;   // 12 per instance
-    DevBuf<BlasDesc> blasDesc;
-    int blasLayout = 0;
-    bool blasMixCw2 = false;          // blasLayout == 0 and every BLAS is BVH8_CWBVH or BVH_GPU: the reference's two BLAS types (traverse_tlas.cl:50-72)
-    bool blasSpheres = false;         // some BLAS is a sphere BLAS (capi_custom.hip): every query takes the flat loop with the sphere step, BLASes in their own layouts
-    // any-hit queries may enter the BLASes through other arrays than closest-hit ones (BVH4_GPU BLASes: their own stream for closest hits — k_tlas4 —, their
-    // 8-wide copies for IsOccluded — k_tlas8, + 28 % on 1000 instances —: capi_scene.hip: reclassifyTlas); blasDescAny empty: the same as above
-    DevBuf<BlasDesc> blasDescAny;
-    bool anyHitSeen = false;          // the TLAS has had an any-hit query: only then do its BVH4_GPU BLASes get their copies and the second wide tree is kept (a frame loop that only
-                                      // ever calls Intersect pays for neither: per frame the second tree's rebuild and the copies' refit cost 0.27 ms at 1000 instances)
-    int blasLayoutAny = -1;
-    bool blasMixCw2Any = false;
-    uint64_t nInst = 0, nBlas = 0, nTlasNodes = 0, nTlasIdx = 0;
-    // the same TLAS collapsed 4-wide in the BVH4_GPU node format (kernels_tlas4.hip), kept current by every upload / update / device rebuild;
-    // only for TLASes whose BLASes are all BVH4_GPU
-    DevBuf<float4> tlas4;             // count(): blocks
-    DevBuf<void> tlas4Scratch;
-    // ... or 8-wide in the BVH8_CWBVH node format (kernels_tlas8.hip) for TLASes whose BLASes are all BVH8_CWBVH; same scratch
-    DevBuf<float4> tlas8;             // 5 per node: count() / 5 = nodes the wide tree may have (allocated after tlas8Refs: never there without them)
-    DevBuf<uint32_t> tlas8Refs;       // instance references: the same number
-    // device-side TLAS rebuild (kernels_tlasbuild.hip)
-    DevBuf<float> blasBounds;         // 6 floats per BLAS
-    // tbvh_tlas_set_builder: 0 = LBVH, 2 = the reference's SAH tree (kernels_sahbuild.hip over the instance records, then the device Aila-Laine encode).
-    // The SAH build keeps its Wald nodes (2 n) and its scratch here, sized for tlasSahFor instances: no allocation per frame; `bytes` counts them.
-    int tlasBuilder = 0;
-    DevBuf<float4> tlasWald;
-    DevBuf<void> tlasSah;
-    uint64_t tlasSahFor = 0;
-    size_t tlasSahSort = 0, tlasSahScan = 0;
-    DevBuf<float> xformStage;         // staged transforms (16 floats per instance) when the caller passes host memory
+    TlasState tlas;
     // BLAS <-> TLAS references: a TLAS snapshots its BLASes' device pointers (BlasDesc), so a BLAS knows the TLASes that
     // use it (their descriptors are refreshed when its opacity maps change) and outlives them (tbvh_free_scene on a BLAS
     // that is still referenced only marks it; the memory goes when the last TLAS over it is freed)
-    std::vector<tbvh_scene*> blasList;   // TLAS: its BLASes, in blasIdx order
     std::vector<tbvh_scene*> usedBy;     // BLAS: the TLASes built over it (one entry per reference)
     bool zombie = false;                 // BLAS: freed by the caller while still referenced
+    // scratch of the device builds that sort: a TLAS's rebuild (fp32 and fp64) and a sphere BLAS's build share it, so it is the scene's, not the TLAS's
     DevBuf<void> buildScratch;
     size_t sortTempBytes = 0;
-    uint64_t buildScratchFor = 0;     // instance count the scratch was sized for
+    uint64_t buildScratchFor = 0;     // instance / sphere count the scratch was sized for
     // device-side BLAS refit (kernels_refit.hip)
     DevBuf<void> refitScratch;
     std::vector<uint32_t> b4Levels;   // BVH4_GPU: first node of every tree level in the item list (filled by the first refit)
@@ -307,7 +315,6 @@ struct tbvh_scene {
     uint64_t meshIdxTris = 0;
     DevBuf<uint32_t> idxStage;           // staged host indices of tbvh_intersect_spheres_mesh (a per-frame query: no allocation per call)
     WideCopies copies;
-    bool blasRecopyPending = false;      // TLAS: the copies of some BLAS are waiting to be made again
     uint64_t raysTraced = 0;             // rays of every query launched on this scene (a TLAS counts its own): what a refit weighs the copies' refit against
     // a sphere BLAS that moves (capi_custom.hip: tbvh_build_device_custom_spheres / tbvh_rebuild_custom_spheres_device / tbvh_refit_custom_spheres): the
     // sphere count and the builder a rebuild repeats (an uploaded scene: LBVH, one sphere per leaf).  The build keeps its scratch in buildScratch
@@ -420,7 +427,8 @@ int checkStatus(tbvh_context* c);   // synchronizes the stream, turns the device
 int ensureStage(tbvh_context* c, uint64_t n);      // (capi_query.hip) the host-array staging buffers hold at least n ray records ...
 int ensureStageOcc(tbvh_context* c, uint64_t n);   // ... and n any-hit result bytes
 tbvh_scene* newScene(tbvh_context* c, int layout);
-int reclassifyTlas(tbvh_scene* t);   // (capi_scene.hip) descriptors, kernel class and wide trees of a TLAS from its BLASes as they are now
+TlasFacts tlasFactsNow(const tbvh_scene* s, std::vector<TlasBlasFacts>& blas);   // (capi_scene.hip) the facts of TLAS s as they are now; `blas` holds the per-BLAS part
+int reclassifyTlas(tbvh_scene* t);   // (capi_scene.hip) the plan (tlas_plan.h), descriptors and wide trees of a TLAS from its BLASes as they are now
 // ---- derived copies (capi_copies.hip): WideCopies and CwbvhLayouts are made, dropped, refitted and selected there and nowhere else -----------
 uint64_t cwbvhTopologyHash(const tbvh::Vec4* nodes, uint32_t nNodes);
 int prepareIncoherentCopies(tbvh_scene* s);   // launchQuery: a probed launch on the scene (the first one builds, or finds them unwanted)
@@ -434,7 +442,8 @@ tbvh_scene* wideCopyForQuery(tbvh_scene* s);   // the 8-wide copy the scene's ow
 tbvh_scene* tunedScene(tbvh_scene* s);         // the scene whose CohTuner decides for queries on s: its 8-wide copy if it has one
 void shareOpacityMaps(tbvh_scene* s);          // the copies read the owner's maps
 int refitCopies(tbvh_scene* s, const tbvh::MeshSrc& src);   // tail of a refit of s: its copies follow in place, or go (CopyPolicy::refit)
-const tbvh_scene* blasView(const tbvh_scene* b, bool any, bool allow4 = true);   // what a TLAS traverses for BLAS b, by the kind of query
+TlasBlasFacts tlasBlasFacts(const tbvh_scene* b);                         // what tlas_plan.h reads of BLAS b
+const tbvh_scene* blasView(const tbvh_scene* b, TlasView v);              // the scene whose arrays a TLAS enters b through under view v
 // f(t) for each distinct TLAS t over BLAS b (usedBy holds one entry per reference), until one returns non-zero: that value, or 0
 template <class F>
 int forEachTlasOver(tbvh_scene* b, F f) {

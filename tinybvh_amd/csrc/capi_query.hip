@@ -224,23 +224,20 @@ static LaneFootprint footprintOf(const RayRec* d_rays, uint64_t n, const uint8_t
 
 // ---- which kernels a scene's queries run, and how wide their stack entries are ---------------------------------------------------------------------
 enum class KernelFamily { kBvh2, kBvh4, kCwbvh, kSphere, kVoxel, kTlasSphere, kTlas4, kTlas8, kTlasVoxel, kTlas2, kTlasFlat, kNone };
-// The class of BLAS layouts a TLAS query walks: any-hit queries may have a class of their own (capi_scene.hip: reclassifyTlas)
-struct TlasClass { int layout; bool mix; const BlasDesc* desc; };
-static TlasClass tlasClass(const tbvh_scene* s, bool any) {
-    const bool own = any && s->blasDescAny != nullptr;
-    return own ? TlasClass{s->blasLayoutAny, s->blasMixCw2Any, s->blasDescAny} : TlasClass{s->blasLayout, s->blasMixCw2, s->blasDesc};
-}
+// A TLAS's family, class and descriptor table for each kind of query are its stored plan's (tlas_plan.h; capi_scene.hip: reclassifyTlas keeps it current).
+static const TlasKindPlan& tlasKind(const tbvh_scene* s, bool any) { return s->tlas.plan.kind[any ? 1 : 0]; }
+static const BlasDesc* tlasDesc(const tbvh_scene* s, bool any) { return any && s->tlas.plan.anyOwn ? s->tlas.blasDescAny.get() : s->tlas.blasDesc.get(); }
 
-// The two-level kernels: one per BLAS layout (and one for BVH8_CWBVH and BVH_GPU BLASes mixed), each walking the TLAS form made for it at upload.
-static KernelFamily kernelFamily(const tbvh_scene* s, const TlasClass& t) {
+static KernelFamily kernelFamily(const tbvh_scene* s, bool any) {
     if (s->isTlas) {
-        // sphere BLASes, alone or with triangle BLASes walked in their own layouts: the flat loop with the sphere step
-        if (s->blasSpheres) return KernelFamily::kTlasSphere;
-        if (s->tlas4 && t.layout == TBVH_LAYOUT_BVH4_GPU) return KernelFamily::kTlas4;           // BVH4_GPU BLASes: the unified 4-wide kernel
-        if (s->tlas8 && (t.layout == TBVH_LAYOUT_CWBVH || t.mix)) return KernelFamily::kTlas8;   // BVH8_CWBVH BLASes (or those and BVH_GPU ones): 8-wide
-        if (t.layout == TBVH_LAYOUT_VOXELSET) return KernelFamily::kTlasVoxel;   // voxel sets; tbvh_upload_tlas admits them only all together
-        if (t.layout == TBVH_LAYOUT_BVH_GPU) return KernelFamily::kTlas2;     // BVH_GPU BLASes: the TLAS already has their node format
-        return KernelFamily::kTlasFlat;
+        switch (tlasKind(s, any).family) {
+        case TlasFamily::kTlasSphere: return KernelFamily::kTlasSphere;
+        case TlasFamily::kTlas4: return KernelFamily::kTlas4;
+        case TlasFamily::kTlas8: return KernelFamily::kTlas8;
+        case TlasFamily::kTlasVoxel: return KernelFamily::kTlasVoxel;
+        case TlasFamily::kTlas2: return KernelFamily::kTlas2;
+        case TlasFamily::kTlasFlat: return KernelFamily::kTlasFlat;
+        }
     }
     return s->layout == TBVH_LAYOUT_BVH_GPU ? KernelFamily::kBvh2 : s->layout == TBVH_LAYOUT_BVH4_GPU ? KernelFamily::kBvh4
            : s->layout == TBVH_LAYOUT_CWBVH ? KernelFamily::kCwbvh : s->layout == TBVH_LAYOUT_VOXELSET ? KernelFamily::kVoxel
@@ -248,10 +245,9 @@ static KernelFamily kernelFamily(const tbvh_scene* s, const TlasClass& t) {
 }
 
 // Stack entries per lane in the spill area, which holds spillEntries 32-bit words per lane: half as many where a family pushes 8-byte entries.
-static uint32_t stackEntriesPerLane(const tbvh_context* c, KernelFamily f) {
-    using F = KernelFamily;
-    const bool eightBytes = f == F::kCwbvh || f == F::kSphere || f == F::kTlasSphere || f == F::kTlas8 || f == F::kTlasFlat;
-    return eightBytes ? c->spillEntries / 2 : c->spillEntries;
+static uint32_t stackEntriesPerLane(const tbvh_scene* s, bool any, KernelFamily f) {
+    const bool eightBytes = s->isTlas ? tlasKind(s, any).entryBytes == 8 : (f == KernelFamily::kCwbvh || f == KernelFamily::kSphere);
+    return eightBytes ? s->ctx->spillEntries / 2 : s->ctx->spillEntries;
 }
 
 // One coherent-flavor kernel of a two-flavor launch, in the schedule the scene's tuner asks for; timed by the tuner's own events while it still measures.
@@ -434,7 +430,7 @@ static void harvestVerdicts(tbvh_context* c) {
 // Something the launch does before its kernels would enqueue work on lane 0 or replace arrays that launches in flight read (a derived copy made or made
 // again, a TLAS re-classified): such a launch joins the lanes first.
 static bool launchPrepares(const tbvh_scene* s, uint64_t n, bool any) {
-    if (s->isTlas) return s->blasRecopyPending || (any && !s->anyHitSeen && !s->blasSpheres);
+    if (s->isTlas) return s->tlas.blasRecopyPending || (any && !s->tlas.anyHitSeen && !s->tlas.blasSpheres);
     if (s->copies.pending()) return true;
     return n >= 1024u && s->variant == 0 && !s->copies.tried8 && (s->layout == TBVH_LAYOUT_BVH_GPU || s->layout == TBVH_LAYOUT_BVH4_GPU);
 }
@@ -448,9 +444,9 @@ static int prepareScene(tbvh_scene* s, uint64_t n, bool any, bool sizeKnown, tbv
     if (!s->isTlas && (!sizeKnown || n >= 1024u)) makeCopyOnce(s, kCopyWide8);   // first query of a BVH_GPU / BVH4_GPU scene
     if ((*wide = wideCopyForQuery(s))) return 0;
     // the first IsOccluded through this TLAS: its BVH4_GPU and BVH_GPU BLASes are entered through 8-wide copies by any-hit queries
-    if (any && s->isTlas && !s->anyHitSeen && !s->blasSpheres) {
-        s->anyHitSeen = true;
-        for (tbvh_scene* b : s->blasList) makeCopyOnce(b, kCopyWide8);   // (re-classifies the TLASes over b, this one included)
+    if (any && s->isTlas && !s->tlas.anyHitSeen && !s->tlas.blasSpheres) {
+        s->tlas.anyHitSeen = true;
+        for (tbvh_scene* b : s->tlas.blasList) makeCopyOnce(b, kCopyWide8);   // (re-classifies the TLASes over b, this one included)
         if (int r = reclassifyTlas(s)) return r;
     }
     return 0;
@@ -572,22 +568,23 @@ static void armProbe(tbvh_scene* s, const LaunchPlan& plan, Launch& L, QueryArgs
 // Step 7, the kernels, by the scene's kernel family.
 static int enqueueKernels(tbvh_scene* s, QueryArgs& q, const LaunchPlan& plan, const Launch& L) {
     tbvh_context* c = s->ctx;
-    const TlasClass t = s->isTlas ? tlasClass(s, L.any) : TlasClass{s->layout, false, nullptr};
-    const KernelFamily family = kernelFamily(s, t);
+    const KernelFamily family = kernelFamily(s, L.any);
+    const TlasKindPlan t = s->isTlas ? tlasKind(s, L.any) : TlasKindPlan();
+    const BlasDesc* const desc = s->isTlas ? tlasDesc(s, L.any) : nullptr;
     const uint32_t blocks = plan.blocks, blocks7 = plan.blocks7Tlas;
-    q.spillStride = stackEntriesPerLane(c, family);
+    q.spillStride = stackEntriesPerLane(s, L.any, family);
     switch (family) {
     case KernelFamily::kBvh2: launch_bvh2(L.any, s->variant, s->nodes, s->tris, q, c->status, blocks, L.st); break;
     case KernelFamily::kBvh4: launch_bvh4(L.any, s->variant, s->nodes, q, c->status, blocks, L.st); break;
     case KernelFamily::kCwbvh: return launchCwbvhKernels(s, q, plan, L);
     case KernelFamily::kSphere: launch_custom(L.any, s->nodes, s->tris, q, c->status, blocks, L.st); break;
     case KernelFamily::kVoxel: launch_voxel(L.any, (const uint32_t*)s->nodes.get(), nullptr, nullptr, nullptr, nullptr, q, c->status, blocks, L.st); break;
-    case KernelFamily::kTlasSphere: launch_tlas_custom(L.any, t.layout, s->nodes, s->tlasIdx, s->instances, t.desc, q, c->status, blocks, L.st); break;
-    case KernelFamily::kTlas4: launch_tlas4(L.any, 0, s->tlas4, s->instances, t.desc, q, c->status, blocks, L.st, blocks7); break;
-    case KernelFamily::kTlas8: launch_tlas8(L.any, 0, s->tlas8, s->tlas8Refs, s->instances, t.desc, q, c->status, blocks, L.st, blocks7, t.mix); break;
-    case KernelFamily::kTlasVoxel: launch_voxel(L.any, nullptr, s->nodes, s->tlasIdx, s->instances, t.desc, q, c->status, blocks, L.st); break;
-    case KernelFamily::kTlas2: launch_tlas2(L.any, 0, s->nodes, s->tlasIdx, s->instances, t.desc, q, c->status, blocks, L.st, blocks7); break;
-    case KernelFamily::kTlasFlat: launch_tlas(L.any, t.layout, s->nodes, s->tlasIdx, s->instances, t.desc, q, c->status, blocks, L.st); break;
+    case KernelFamily::kTlasSphere: launch_tlas_custom(L.any, t.layout, s->nodes, s->tlas.tlasIdx, s->tlas.instances, desc, q, c->status, blocks, L.st); break;
+    case KernelFamily::kTlas4: launch_tlas4(L.any, 0, s->tlas.tlas4, s->tlas.instances, desc, q, c->status, blocks, L.st, blocks7); break;
+    case KernelFamily::kTlas8: launch_tlas8(L.any, 0, s->tlas.tlas8, s->tlas.tlas8Refs, s->tlas.instances, desc, q, c->status, blocks, L.st, blocks7, t.mix); break;
+    case KernelFamily::kTlasVoxel: launch_voxel(L.any, nullptr, s->nodes, s->tlas.tlasIdx, s->tlas.instances, desc, q, c->status, blocks, L.st); break;
+    case KernelFamily::kTlas2: launch_tlas2(L.any, 0, s->nodes, s->tlas.tlasIdx, s->tlas.instances, desc, q, c->status, blocks, L.st, blocks7); break;
+    case KernelFamily::kTlasFlat: launch_tlas(L.any, t.layout, s->nodes, s->tlas.tlasIdx, s->tlas.instances, desc, q, c->status, blocks, L.st); break;
     case KernelFamily::kNone: return fail(TBVH_E_INVALID, "scene layout %d has no query kernel", s->layout);
     }
     return 0;

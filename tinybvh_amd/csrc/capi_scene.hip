@@ -141,138 +141,122 @@ int tbvh_upload_cwbvh(tbvh_context* c, const void* nodes16, uint64_t nNodeBlocks
 }
 
 namespace {
-// (re)build the wide TLAS(es) from the BVH_GPU nodes on the device — 8-wide in the BVH8_CWBVH node format, 4-wide in the BVH4_GPU one, whichever the
-// two-level kernels of this TLAS's closest-hit and any-hit queries walk; asynchronous on the context's stream
-// the scratch area the two wide builds share holds what this TLAS needs
-int reserveTlasWideScratch(tbvh_scene* s) {
-    HIP_TRY(s->tlas4Scratch.reserve(tlas_wide_scratch_bytes(s->nTlasNodes, s->nInst)));
-    return 0;
+// `bytes` of a TLAS, from what it holds: node, index and instance arrays by their live counts, both wide trees and the 8-wide tree's references by their
+// allocated capacity, the SAH builder's Wald nodes and scratch.  (The shared scratch areas and staging buffers are not counted, as they never were.)
+void accountTlas(tbvh_scene* s) {
+    const TlasState& t = s->tlas;
+    s->bytes = t.nTlasNodes * 64 + t.nTlasIdx * 4 + t.nInst * 192 + (t.tlas4.count() + t.tlas8.count()) * 16 + t.tlas8Refs.count() * 4 + t.tlasSah.count() +
+               t.tlasWald.count() * 16;
 }
 
+// the 8-wide TLAS in the BVH8_CWBVH node format, from the BVH_GPU nodes on the device; asynchronous on the context's stream
 int buildTlasWide8(tbvh_scene* s) {
     tbvh_context* c = s->ctx;
-    const uint64_t cap = tlas8_cap_nodes(s->nTlasNodes, s->nInst);
-    if (cap > 0x00ffffffull) {   // wide-node indices share a word with 8 flag bits in places: the flat loop serves larger TLASes — and a wide
-        // TLAS left from an earlier, smaller upload must not be traversed in its place (launchQuery keys on the pointer)
-        s->tlas8.reset(); s->tlas8Refs.reset();
-        return 0;
+    TlasState& t = s->tlas;
+    const uint64_t cap = tlas8_cap_nodes(t.nTlasNodes, t.nInst);
+    if (cap * 5 > t.tlas8.count()) {
+        // both go before either is made again, and the nodes — whose size is the capacity — are made last: a failure of either allocation leaves no wide
+        // tree and capacity 0, so the next build allocates again
+        t.tlas8.reset(); t.tlas8Refs.reset();
+        HIP_TRY(t.tlas8Refs.alloc(cap));
+        HIP_TRY(t.tlas8.alloc(cap * 5));
     }
-    if (cap * 5 > s->tlas8.count()) {
-        // both go before either is made again, and the nodes — whose size is the capacity, and which launchQuery keys on — are made last: a failure
-        // of either allocation leaves no wide tree and capacity 0, so the next build allocates again
-        s->tlas8.reset(); s->tlas8Refs.reset();
-        HIP_TRY(s->tlas8Refs.alloc(cap));
-        HIP_TRY(s->tlas8.alloc(cap * 5));
-        s->bytes += cap * 84;
-    }
-    if (int r = reserveTlasWideScratch(s)) return r;
-    const uint32_t cap8 = (uint32_t)(s->tlas8.count() / 5);
-    launch_tlas8_build(s->nodes, (uint32_t)s->nTlasNodes, s->tlasIdx, (uint32_t)s->nTlasIdx, s->instances, (uint32_t)s->nInst, s->tlas8, cap8, s->tlas8Refs,
-                       cap8, s->tlas4Scratch, c->status, c->stream);
+    HIP_TRY(t.tlas4Scratch.reserve(tlas_wide_scratch_bytes(t.nTlasNodes, t.nInst)));   // (the scratch area the two wide builds share)
+    const uint32_t cap8 = (uint32_t)(t.tlas8.count() / 5);
+    launch_tlas8_build(s->nodes, (uint32_t)t.nTlasNodes, t.tlasIdx, (uint32_t)t.nTlasIdx, t.instances, (uint32_t)t.nInst, t.tlas8, cap8, t.tlas8Refs, cap8, t.tlas4Scratch,
+                       c->status, c->stream);
     HIP_TRY(hipGetLastError());
     return 0;
 }
 
+// ... and the 4-wide one in the BVH4_GPU node format
 int buildTlasWide4(tbvh_scene* s) {
     tbvh_context* c = s->ctx;
-    const uint64_t cap = tlas4_cap_blocks(s->nTlasNodes, s->nInst);
-    if (cap > 0x7fffffffull) {   // beyond 31-bit block offsets: the flat loop serves this TLAS; drop a 4-wide TLAS of an earlier, smaller upload
-        s->tlas4.reset();
-        return 0;
-    }
-    if (cap > s->tlas4.count()) {
-        HIP_TRY(s->tlas4.alloc(cap));
-        s->bytes += cap * 16;
-    }
-    if (int r = reserveTlasWideScratch(s)) return r;
-    launch_tlas4_build(s->nodes, (uint32_t)s->nTlasNodes, s->tlasIdx, (uint32_t)s->nTlasIdx, s->instances, (uint32_t)s->nInst, s->tlas4, (uint32_t)s->tlas4.count(), s->tlas4Scratch, c->status, c->stream);
+    TlasState& t = s->tlas;
+    const uint64_t cap = tlas4_cap_blocks(t.nTlasNodes, t.nInst);
+    if (cap > t.tlas4.count()) HIP_TRY(t.tlas4.alloc(cap));
+    HIP_TRY(t.tlas4Scratch.reserve(tlas_wide_scratch_bytes(t.nTlasNodes, t.nInst)));
+    launch_tlas4_build(s->nodes, (uint32_t)t.nTlasNodes, t.tlasIdx, (uint32_t)t.nTlasIdx, t.instances, (uint32_t)t.nInst, t.tlas4, (uint32_t)t.tlas4.count(), t.tlas4Scratch, c->status,
+                       c->stream);
     HIP_TRY(hipGetLastError());
     return 0;
 }
 
-int buildTlas4(tbvh_scene* s) {
-    const bool any2 = (bool)s->blasDescAny;
-    const bool want8 = s->blasLayout == TBVH_LAYOUT_CWBVH || s->blasMixCw2 || (any2 && (s->blasLayoutAny == TBVH_LAYOUT_CWBVH || s->blasMixCw2Any));
-    const bool want4 = s->blasLayout == TBVH_LAYOUT_BVH4_GPU || (any2 && s->blasLayoutAny == TBVH_LAYOUT_BVH4_GPU);
-    if (want8) if (int r = buildTlasWide8(s)) return r;   // (the two builds share the scratch area: in order on one stream)
-    if (want4) if (int r = buildTlasWide4(s)) return r;
-    return 0;
+// The TLAS's nodes are new (upload, update, device rebuild) or its plan is (reclassifyTlas): which wide trees fit is stated again for the TLAS's size as it
+// is now, and the trees the plan wants are built from the BVH_GPU nodes on the device.  A wanted tree beyond its node format's index range is not built — the
+// plan has sent those queries to the flat loop — and one left from an earlier, smaller TLAS goes, so that it is neither kept nor counted.  A tree that cannot
+// be allocated is an error of the call; the plan then says "does not fit", so that no later launch walks a tree that is not there.
+int buildWideTlas(tbvh_scene* s) {
+    TlasState& t = s->tlas;
+    const uint64_t cap8 = tlas8_cap_nodes(t.nTlasNodes, t.nInst), cap4 = tlas4_cap_blocks(t.nTlasNodes, t.nInst);
+    planTlasFit(t.plan, (bool)s->nodes, cap8, cap4);
+    int r = 0;
+    if (t.plan.want8 && !t.plan.fits8) { t.tlas8.reset(); t.tlas8Refs.reset(); }
+    if (t.plan.want4 && !t.plan.fits4) t.tlas4.reset();
+    if (t.plan.fits8 && (r = buildTlasWide8(s)) != 0) planTlasFit(t.plan, true, ~0ull, cap4);   // (the two builds share the scratch area: in order on one stream)
+    if (!r && t.plan.fits4 && (r = buildTlasWide4(s)) != 0) planTlasFit(t.plan, true, cap8, ~0ull);
+    accountTlas(s);
+    return r;
 }
 
 int tlasCopy(tbvh_scene* s, const void* nodes64, uint64_t nNodes, const uint32_t* idx, uint64_t nIdx, const void* inst, uint64_t nInst) {
     tbvh_context* c = s->ctx;
+    TlasState& t = s->tlas;
     // same hardening as the BLAS uploads: the TLAS kernels index instances[idx[]] and blas[blasIdx] unguarded
     if (const char* why = validate_bvh_gpu((const NodeAL*)nodes64, nNodes, nIdx)) return fail(why == kValidateNoMemory ? TBVH_E_NOMEM : TBVH_E_FORMAT, "TLAS: %s", why);
     for (uint64_t i = 0; i < nIdx; i++) if (idx[i] >= nInst) return fail(TBVH_E_FORMAT, "TLAS: primIdx[%llu] = %u is not an instance (%llu instances)", (unsigned long long)i, idx[i], (unsigned long long)nInst);
     const BLASInstanceCheck* ic = (const BLASInstanceCheck*)inst;
-    for (uint64_t i = 0; i < nInst; i++) if (ic[i].blasIdx >= s->nBlas) return fail(TBVH_E_FORMAT, "instance %llu: blasIdx %u out of range (%llu BLASes)", (unsigned long long)i, ic[i].blasIdx, (unsigned long long)s->nBlas);
+    for (uint64_t i = 0; i < nInst; i++) if (ic[i].blasIdx >= t.nBlas) return fail(TBVH_E_FORMAT, "instance %llu: blasIdx %u out of range (%llu BLASes)", (unsigned long long)i, ic[i].blasIdx, (unsigned long long)t.nBlas);
     HIP_TRY(s->nodes.reserve(nNodes * 4));
-    HIP_TRY(s->tlasIdx.reserve(nIdx));
-    HIP_TRY(s->instances.reserve(nInst * 12));
+    HIP_TRY(t.tlasIdx.reserve(nIdx));
+    HIP_TRY(t.instances.reserve(nInst * 12));
     HIP_TRY(hipMemcpyAsync(s->nodes, nodes64, nNodes * 64, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(s->tlasIdx, idx, nIdx * 4, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(s->instances, inst, nInst * 192, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(t.tlasIdx, idx, nIdx * 4, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(t.instances, inst, nInst * 192, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));  // the caller may reuse its host arrays right away
-    s->bytes = nNodes * 64 + nIdx * 4 + nInst * 192;
-    s->nInst = nInst; s->nTlasNodes = nNodes; s->nTlasIdx = nIdx;
-    return buildTlas4(s);
+    t.nInst = nInst; t.nTlasNodes = nNodes; t.nTlasIdx = nIdx;
+    return buildWideTlas(s);
 }
 }  // namespace
 
 extern "C++" {
 namespace tbvh_capi {
-// The BLAS descriptors of TLAS t and the class of two-level kernel that serves each kind of query, from its BLASes as they are NOW (their copies come and
-// go: a tbvh_update_* drops them, queries bring them back, tbvh_set_variant switches between copy and nodes); builds the wide TLAS(es) those kernels walk.
-// With every BLAS copied, BLASes of different layouts under one TLAS share one kernel class per kind of query instead of the flat three-state loop.
-int reclassifyTlas(tbvh_scene* t) {
-    const size_t nBlas = t->blasList.size();
-    if (t->blasSpheres) {   // sphere BLASes (capi_custom.hip): one class for both kinds of query, every BLAS through its own arrays (no copies, no wide TLAS)
-        std::vector<BlasDesc> desc(nBlas);
-        int layout = 0;
+// the facts of TLAS s as they are now; `blas` holds the per-BLAS part
+TlasFacts tlasFactsNow(const tbvh_scene* s, std::vector<TlasBlasFacts>& blas) {
+    const TlasState& t = s->tlas;
+    blas.resize(t.blasList.size());
+    for (size_t i = 0; i < blas.size(); i++) blas[i] = tlasBlasFacts(t.blasList[i]);
+    TlasFacts f;
+    f.blas = blas.data(); f.nBlas = (uint32_t)blas.size(); f.anyHitSeen = t.anyHitSeen; f.hasNodes = (bool)s->nodes;
+    f.cap8 = tlas8_cap_nodes(t.nTlasNodes, t.nInst); f.cap4 = tlas4_cap_blocks(t.nTlasNodes, t.nInst);
+    return f;
+}
+
+// The plan of TLAS s (tlas_plan.h) from its BLASes as they are NOW (their copies come and go: a tbvh_update_* drops them, queries bring them back,
+// tbvh_set_variant switches between copy and nodes), the one or two descriptor tables of the views it chose, the wide trees it wants.  With every BLAS
+// copied, BLASes of different layouts under one TLAS share one kernel class per kind of query instead of the flat three-state loop.
+int reclassifyTlas(tbvh_scene* s) {
+    TlasState& t = s->tlas;
+    std::vector<TlasBlasFacts> blas;
+    const TlasFacts f = tlasFactsNow(s, blas);
+    const size_t nBlas = blas.size();
+    for (auto& v : t.view) v.resize(nBlas);
+    TlasView* const view[2] = {t.view[0].data(), t.view[1].data()};
+    t.plan = planTlas(f, view);
+    HIP_TRY(hipStreamSynchronize(s->ctx->stream));   // (launches in flight read the old descriptors)
+    std::vector<BlasDesc> desc(nBlas);
+    for (int kind = 0; kind < (t.plan.anyOwn ? 2 : 1); kind++) {
         for (size_t i = 0; i < nBlas; i++) {
-            const tbvh_scene* b = t->blasList[i];
-            layout = i == 0 ? b->layout : (layout == b->layout ? layout : 0);
-            desc[i] = BlasDesc{b->nodes, b->tris, b->opmap, b->opmapN, (uint32_t)b->layout};
+            const tbvh_scene* b = t.blasList[i];
+            const tbvh_scene* v = blasView(b, t.view[kind][i]);
+            desc[i] = BlasDesc{v->nodes, v->tris, b->opmap, b->opmapN, (uint32_t)v->layout};
         }
-        t->blasLayout = layout; t->blasMixCw2 = false; t->blasLayoutAny = -1; t->blasMixCw2Any = false;
-        if (!t->blasDesc) HIP_TRY(t->blasDesc.alloc(nBlas));
-        HIP_TRY(hipStreamSynchronize(t->ctx->stream));   // (launches in flight read the old descriptors)
-        HIP_TRY(hipMemcpy(t->blasDesc, desc.data(), nBlas * sizeof(BlasDesc), hipMemcpyHostToDevice));
-        t->blasDescAny.reset();
-        return 0;
+        DevBuf<BlasDesc>& table = kind ? t.blasDescAny : t.blasDesc;
+        if (!table) HIP_TRY(table.alloc(nBlas));
+        HIP_TRY(hipMemcpy(table, desc.data(), nBlas * sizeof(BlasDesc), hipMemcpyHostToDevice));
     }
-    std::vector<BlasDesc> desc[2] = {std::vector<BlasDesc>(nBlas), std::vector<BlasDesc>(nBlas)};
-    int layout[2] = {0, 0};
-    bool mix[2] = {false, false}, same = true;
-    for (int pass = 0; pass < 3; pass++) {
-        // pass 0: closest hits, BVH_GPU / BVH8_CWBVH BLASes through their 4-wide copies; pass 1 (only if pass 0 ended in the flat loop: a BLAS too small
-        // for a copy next to copied ones): closest hits without the 4-wide copies; pass 2: any-hit queries
-        const int any = pass == 2;
-        if (pass == 1 && (layout[0] != 0 || mix[0])) continue;
-        bool anyBvh4 = false;
-        for (size_t i = 0; i < nBlas; i++) {
-            const tbvh_scene* b = t->blasList[i];
-            const tbvh_scene* v = blasView(b, any != 0, pass == 0);
-            layout[any] = i == 0 ? v->layout : (layout[any] == v->layout ? layout[any] : 0);   // 0: the BLASes mix layouts (traverse_tlas.cl:50-72)
-            anyBvh4 |= v->layout == TBVH_LAYOUT_BVH4_GPU;
-            desc[any][i].nodes = v->nodes; desc[any][i].tris = v->tris; desc[any][i].opmap = b->opmap; desc[any][i].opmapN = b->opmapN; desc[any][i].layout = (uint32_t)v->layout;
-            if (any) same &= desc[1][i].nodes == desc[0][i].nodes;
-        }
-        mix[any] = layout[any] == 0 && !anyBvh4;
-    }
-    // a class of its own for any-hit queries only where it is served by the 8-wide kernel (some BVH4_GPU BLASes with a copy and some without would
-    // take the flat loop: then IsOccluded stays with Intersect's arrays)
-    const bool any2 = t->anyHitSeen && !same && (layout[1] == TBVH_LAYOUT_CWBVH || mix[1]);
-    t->blasLayout = layout[0]; t->blasMixCw2 = mix[0];
-    t->blasLayoutAny = any2 ? layout[1] : -1; t->blasMixCw2Any = any2 && mix[1];
-    if (!t->blasDesc) HIP_TRY(t->blasDesc.alloc(nBlas));
-    HIP_TRY(hipStreamSynchronize(t->ctx->stream));   // (launches in flight read the old descriptors)
-    HIP_TRY(hipMemcpy(t->blasDesc, desc[0].data(), nBlas * sizeof(BlasDesc), hipMemcpyHostToDevice));
-    if (any2) {
-        if (!t->blasDescAny) HIP_TRY(t->blasDescAny.alloc(nBlas));
-        HIP_TRY(hipMemcpy(t->blasDescAny, desc[1].data(), nBlas * sizeof(BlasDesc), hipMemcpyHostToDevice));
-    } else t->blasDescAny.reset();
-    if (t->nodes) return buildTlas4(t);
+    if (!t.plan.anyOwn) t.blasDescAny.reset();
+    if (s->nodes) return buildWideTlas(s);
     return 0;
 }
 }  // namespace tbvh_capi
@@ -300,9 +284,8 @@ int tbvh_upload_tlas(tbvh_context* c, const void* nodes64, uint64_t nNodes, cons
         makeCopyOnce(blas[i], kCopyWide4);
     tbvh_scene* s = newScene(c, TBVH_LAYOUT_BVH_GPU);
     if (!s) return fail(TBVH_E_NOMEM, "out of host memory");
-    s->isTlas = true; s->nBlas = nBlas; s->blasSpheres = spheres;
-    s->blasLayout = -1;   // (not classified yet)
-    for (uint64_t i = 0; i < nBlas; i++) { s->blasList.push_back(blas[i]); blas[i]->usedBy.push_back(s); }
+    s->isTlas = true; s->tlas.nBlas = nBlas; s->tlas.blasSpheres = spheres;
+    for (uint64_t i = 0; i < nBlas; i++) { s->tlas.blasList.push_back(blas[i]); blas[i]->usedBy.push_back(s); }
     if (int r = reclassifyTlas(s)) { tbvh_free_scene(s); return r; }
     if (int r = tlasCopy(s, nodes64, nNodes, idx, nIdx, inst, nInst)) { tbvh_free_scene(s); return r; }
     *out = s;
@@ -757,19 +740,19 @@ int tbvh_rebuild_tlas_device(tbvh_scene* s, const void* transforms, int onDevice
     if (!s || !s->isTlas) return fail(TBVH_E_INVALID, "tbvh_rebuild_tlas_device: not a TLAS");
     tbvh_context* c = s->ctx;
     TBVH_ENTER(c);
-    const uint64_t n = s->nInst;
+    const uint64_t n = s->tlas.nInst;
     if (n == 0 || n > 0x7fffffffull) return fail(TBVH_E_INVALID, "tbvh_rebuild_tlas_device: %llu instances", (unsigned long long)n);
     if (blasBounds6) {
-        if (nBlas != s->nBlas) return fail(TBVH_E_INVALID, "tbvh_rebuild_tlas_device: %llu BLAS bounds for a TLAS over %llu BLASes", (unsigned long long)nBlas, (unsigned long long)s->nBlas);
-        if (!s->blasBounds) HIP_TRY(s->blasBounds.alloc(s->nBlas * 6));
-        HIP_TRY(hipMemcpyAsync(s->blasBounds, blasBounds6, s->nBlas * 24, hipMemcpyHostToDevice, c->stream));
+        if (nBlas != s->tlas.nBlas) return fail(TBVH_E_INVALID, "tbvh_rebuild_tlas_device: %llu BLAS bounds for a TLAS over %llu BLASes", (unsigned long long)nBlas, (unsigned long long)s->tlas.nBlas);
+        if (!s->tlas.blasBounds) HIP_TRY(s->tlas.blasBounds.alloc(s->tlas.nBlas * 6));
+        HIP_TRY(hipMemcpyAsync(s->tlas.blasBounds, blasBounds6, s->tlas.nBlas * 24, hipMemcpyHostToDevice, c->stream));
         HIP_TRY(hipStreamSynchronize(c->stream));   // the caller's array may go away
     }
-    if (!s->blasBounds) return fail(TBVH_E_INVALID, "tbvh_rebuild_tlas_device: the first call needs blas_bounds6");
+    if (!s->tlas.blasBounds) return fail(TBVH_E_INVALID, "tbvh_rebuild_tlas_device: the first call needs blas_bounds6");
     // an LBVH over n leaves has 2n - 1 nodes and n index entries
     const uint64_t nNodes = 2 * n - 1;
     HIP_TRY(s->nodes.reserve(nNodes * 4));
-    HIP_TRY(s->tlasIdx.reserve(n));
+    HIP_TRY(s->tlas.tlasIdx.reserve(n));
     if (s->buildScratchFor != n) {
         s->buildScratchFor = 0;
         HIP_TRY(s->buildScratch.alloc(tlas_build_scratch_bytes((uint32_t)n, &s->sortTempBytes)));
@@ -779,37 +762,35 @@ int tbvh_rebuild_tlas_device(tbvh_scene* s, const void* transforms, int onDevice
     if (transforms) {
         if (onDevice) xf = (const float*)transforms;
         else {
-            HIP_TRY(s->xformStage.reserve(n * 16));   // (tbvh_update_tlas may have grown the instance array since the last rebuild)
-            HIP_TRY(hipMemcpyAsync(s->xformStage, transforms, n * 64, hipMemcpyHostToDevice, c->stream));
-            xf = s->xformStage;
+            HIP_TRY(s->tlas.xformStage.reserve(n * 16));   // (tbvh_update_tlas may have grown the instance array since the last rebuild)
+            HIP_TRY(hipMemcpyAsync(s->tlas.xformStage, transforms, n * 64, hipMemcpyHostToDevice, c->stream));
+            xf = s->tlas.xformStage;
         }
     }
-    if (s->tlasBuilder == 2) {
+    if (s->tlas.tlasBuilder == 2) {
         if (n > 0x3fffffffull) return fail(TBVH_E_INVALID, "tbvh_rebuild_tlas_device: %llu instances: the SAH builder takes at most 2^30 - 1", (unsigned long long)n);
-        if (s->tlasSahFor != n) {
-            s->tlasSahFor = 0;
-            HIP_TRY(s->tlasSah.alloc(sah_scratch_bytes((uint32_t)n, &s->tlasSahSort, &s->tlasSahScan)));
-            HIP_TRY(s->tlasWald.alloc(n * 4));
-            s->tlasSahFor = n;
+        if (s->tlas.tlasSahFor != n) {
+            s->tlas.tlasSahFor = 0;
+            HIP_TRY(s->tlas.tlasSah.alloc(sah_scratch_bytes((uint32_t)n, &s->tlas.tlasSahSort, &s->tlas.tlasSahScan)));
+            HIP_TRY(s->tlas.tlasWald.alloc(n * 4));
+            s->tlas.tlasSahFor = n;
         }
         // the existing instance update, the reference's BVH::Build( BLASInstance*, n ) over the updated records, BVH_GPU::ConvertFrom: all on the stream
         HIP_TRY(timedBegin(c));
-        HIP_TRY(launch_tlas_instance_update(s->instances, xf, s->blasBounds, (uint32_t)n, (uint32_t)s->nBlas, s->buildScratch, s->sortTempBytes, c->stream));
+        HIP_TRY(launch_tlas_instance_update(s->tlas.instances, xf, s->tlas.blasBounds, (uint32_t)n, (uint32_t)s->tlas.nBlas, s->buildScratch, s->sortTempBytes, c->stream));
         uint32_t nWald = 0;
-        HIP_TRY(run_sah_build(SahSrc(sah_boxes_instances(s->instances.get())), (uint32_t)n, 0, c->sahSmallSubtree, c->sahOneGroup, s->tlasWald, s->tlasIdx, s->tlasSah,
-                              s->tlasSahSort, s->tlasSahScan, c->status, c->stream, &nWald));
-        HIP_TRY(run_al_encode(s->tlasWald, nWald, (uint32_t)n, s->tlasSah, s->tlasSahSort, s->tlasSahScan, s->nodes, c->stream));
-        s->nTlasNodes = nWald - 1; s->nTlasIdx = n;
-        s->bytes = s->nTlasNodes * 64 + n * 4 + n * 192 + s->tlasSah.count() + s->tlasWald.count() * 16;
-        if (int r = buildTlas4(s)) return r;
+        HIP_TRY(run_sah_build(SahSrc(sah_boxes_instances(s->tlas.instances.get())), (uint32_t)n, 0, c->sahSmallSubtree, c->sahOneGroup, s->tlas.tlasWald, s->tlas.tlasIdx, s->tlas.tlasSah,
+                              s->tlas.tlasSahSort, s->tlas.tlasSahScan, c->status, c->stream, &nWald));
+        HIP_TRY(run_al_encode(s->tlas.tlasWald, nWald, (uint32_t)n, s->tlas.tlasSah, s->tlas.tlasSahSort, s->tlas.tlasSahScan, s->nodes, c->stream));
+        s->tlas.nTlasNodes = nWald - 1; s->tlas.nTlasIdx = n;
+        if (int r = buildWideTlas(s)) return r;
         HIP_TRY(timedEnd(c));
         return 0;
     }
     HIP_TRY(timedBegin(c));
-    HIP_TRY(launch_tlas_rebuild(s->nodes, s->tlasIdx, s->instances, xf, s->blasBounds, (uint32_t)n, (uint32_t)s->nBlas, s->buildScratch, s->sortTempBytes, c->stream));
-    s->bytes = nNodes * 64 + n * 4 + n * 192;
-    s->nTlasNodes = nNodes; s->nTlasIdx = n;
-    if (int r = buildTlas4(s)) return r;
+    HIP_TRY(launch_tlas_rebuild(s->nodes, s->tlas.tlasIdx, s->tlas.instances, xf, s->tlas.blasBounds, (uint32_t)n, (uint32_t)s->tlas.nBlas, s->buildScratch, s->sortTempBytes, c->stream));
+    s->tlas.nTlasNodes = nNodes; s->tlas.nTlasIdx = n;
+    if (int r = buildWideTlas(s)) return r;
     HIP_TRY(timedEnd(c));
     return 0;
 }
@@ -819,7 +800,7 @@ int tbvh_tlas_set_builder(tbvh_scene* s, int builder) {
     if (!s || !s->isTlas) return fail(TBVH_E_INVALID, "tbvh_tlas_set_builder: not a TLAS");
     if (builder != 0 && builder != 2) return fail(TBVH_E_INVALID, "tbvh_tlas_set_builder: builder %d (0 = LBVH, 2 = the reference's SAH tree)", builder);
     TBVH_LOCK(s->ctx);
-    s->tlasBuilder = builder;
+    s->tlas.tlasBuilder = builder;
     return 0;
 }
 
@@ -830,11 +811,11 @@ int tbvh_tlas_download(tbvh_scene* s, void* nodes64, uint64_t capNodes, uint32_t
     tbvh_context* c = s->ctx;
     TBVH_ENTER(c);
     HIP_TRY(hipStreamSynchronize(c->stream));
-    const uint64_t n = s->nInst, nNodes = s->nTlasNodes;
+    const uint64_t n = s->tlas.nInst, nNodes = s->tlas.nTlasNodes;
     if (nNodesOut) *nNodesOut = nNodes;
     if (nodes64) { if (capNodes < nNodes) return fail(TBVH_E_INVALID, "tbvh_tlas_download: node buffer too small"); HIP_TRY(hipMemcpy(nodes64, s->nodes, nNodes * 64, hipMemcpyDeviceToHost)); }
-    if (idx) { if (capIdx < n) return fail(TBVH_E_INVALID, "tbvh_tlas_download: index buffer too small"); HIP_TRY(hipMemcpy(idx, s->tlasIdx, n * 4, hipMemcpyDeviceToHost)); }
-    if (instances192) { if (capInst < n) return fail(TBVH_E_INVALID, "tbvh_tlas_download: instance buffer too small"); HIP_TRY(hipMemcpy(instances192, s->instances, n * 192, hipMemcpyDeviceToHost)); }
+    if (idx) { if (capIdx < n) return fail(TBVH_E_INVALID, "tbvh_tlas_download: index buffer too small"); HIP_TRY(hipMemcpy(idx, s->tlas.tlasIdx, n * 4, hipMemcpyDeviceToHost)); }
+    if (instances192) { if (capInst < n) return fail(TBVH_E_INVALID, "tbvh_tlas_download: instance buffer too small"); HIP_TRY(hipMemcpy(instances192, s->tlas.instances, n * 192, hipMemcpyDeviceToHost)); }
     return 0;
 }
 
@@ -849,7 +830,7 @@ void tbvh_free_scene(tbvh_scene* s) {
     freeCopy(s, kCopyWide4);
     if (s->isTlas) {
         std::vector<tbvh_scene*> mine;
-        mine.swap(s->blasList);
+        mine.swap(s->tlas.blasList);
         for (tbvh_scene* b : mine) {
             for (size_t i = 0; i < b->usedBy.size(); i++) if (b->usedBy[i] == s) { b->usedBy.erase(b->usedBy.begin() + i); break; }
             if (b->zombie && b->usedBy.empty()) { b->zombie = false; tbvh_free_scene(b); }

@@ -207,8 +207,8 @@ int tbvh_shade_hits_device(tbvh_shading* sh, tbvh_scene* s, const void* dRays, u
     if (!n) return 0;
     HIP_TRY(timedBegin(c));
     if (s->isTlas)
-        launch_shade_hits(sh->tables(), s->instances, s->nInst, (const uint32_t*)((const char*)s->blasDesc.get() + offsetof(BlasDesc, layout)), sizeof(BlasDesc) / 4,
-                          (uint32_t)s->nBlas, dRays, n, strideBytes, dOut48, c->status, c->stream);
+        launch_shade_hits(sh->tables(), s->tlas.instances, s->tlas.nInst, (const uint32_t*)((const char*)s->tlas.blasDesc.get() + offsetof(BlasDesc, layout)), sizeof(BlasDesc) / 4,
+                          (uint32_t)s->tlas.nBlas, dRays, n, strideBytes, dOut48, c->status, c->stream);
     else
         launch_shade_hits(sh->tables(), nullptr, 0, nullptr, 0, 0, dRays, n, strideBytes, dOut48, c->status, c->stream);
     HIP_TRY(hipGetLastError());

@@ -79,13 +79,13 @@ int tbvh_wavefront_render(tbvh_wavefront* w, tbvh_scene* scene, const void* dVer
     TBVH_REFUSE_DOUBLE(scene, "tbvh_wavefront_render");
     TBVH_REFUSE_VOXEL(scene, "tbvh_wavefront_render");
     TBVH_REFUSE_CUSTOM(scene, "tbvh_wavefront_render");
-    if (scene && scene->isTlas && scene->blasSpheres)
+    if (scene && scene->isTlas && scene->tlas.blasSpheres)
         return fail(TBVH_E_INVALID, "tbvh_wavefront_render: a TLAS with sphere BLASes (custom geometry) takes the queries only (the path tracer shades triangles)");
-    if (scene && scene->isTlas && !scene->blasList.empty() && scene->blasList[0]->layout == TBVH_LAYOUT_VOXELSET)
+    if (scene && scene->isTlas && !scene->tlas.blasList.empty() && scene->tlas.blasList[0]->layout == TBVH_LAYOUT_VOXELSET)
         return fail(TBVH_E_INVALID, "tbvh_wavefront_render: a TLAS over VOXELSET scenes takes the queries only (the path tracer shades triangles)");
     if (!w || !scene || !cam || !p) return fail(TBVH_E_INVALID, "tbvh_wavefront_render: null argument");
     if (scene->isTlas) {
-        if (w->nBlasVerts < scene->nBlas) return fail(TBVH_E_INVALID, "tbvh_wavefront_render: a TLAS scene needs tbvh_wavefront_set_blas_vertices (%llu BLASes)", (unsigned long long)scene->nBlas);
+        if (w->nBlasVerts < scene->tlas.nBlas) return fail(TBVH_E_INVALID, "tbvh_wavefront_render: a TLAS scene needs tbvh_wavefront_set_blas_vertices (%llu BLASes)", (unsigned long long)scene->tlas.nBlas);
     } else if (!dVerts) return fail(TBVH_E_INVALID, "tbvh_wavefront_render: null vertex array");
     if (scene->ctx != w->ctx) return fail(TBVH_E_INVALID, "scene and wavefront belong to different contexts");
     const uint32_t fullH = w->fullHeight ? w->fullHeight : w->height;
@@ -123,7 +123,7 @@ int tbvh_wavefront_render(tbvh_wavefront* w, tbvh_scene* scene, const void* dVer
         a.out = w->rays[nxt]; a.auxOut = w->aux[nxt]; a.nOut = QP(d + 1);
         a.shadow = w->shadow; a.shadowAux = w->shadowAux; a.nShadow = QS(d);
         a.verts = (const float4*)dVerts; a.accum = w->accum;
-        a.blasVerts = scene->isTlas ? w->blasVerts : nullptr; a.instances = scene->isTlas ? scene->instances : nullptr;
+        a.blasVerts = scene->isTlas ? w->blasVerts : nullptr; a.instances = scene->isTlas ? scene->tlas.instances : nullptr;
         a.blueNoise = w->blueNoise; a.sampleIdx = p->sample_index; a.width = w->width; a.height = fullH; a.pixelOffset = w->firstRow * w->width;
         memcpy(a.lightPos, p->light_pos, 12); memcpy(a.lightColor, p->light_color, 12); memcpy(a.skyLo, p->sky_lo, 12); memcpy(a.skyHi, p->sky_hi, 12);
         a.lightSize[0] = p->light_size[0]; a.lightSize[1] = p->light_size[1]; a.flags = p->flags;
