@@ -236,6 +236,8 @@ int tbvh_tlas_download(tbvh_scene* tlas, void* tlas_nodes64, uint64_t cap_nodes,
                        void* instances192, uint64_t cap_instances, uint64_t* n_nodes_out);
 void     tbvh_free_scene(tbvh_scene* scene);
 int      tbvh_scene_layout(const tbvh_scene* scene);
+/* What the scene costs on the device, a function of what it holds when asked (never of the calls that led there): arrays the caller uploaded at what they hold
+ * now, buffers the library made for itself — derived copies, opacity maps, held mesh indices, wide TLAS trees — at their allocation; takes the context's lock. */
 uint64_t tbvh_scene_device_bytes(const tbvh_scene* scene);
 
 /* ------------------------------------------------------------------------------------

@@ -133,6 +133,13 @@ int tbvh_debug_get_sah_thresholds(tbvh_context* ctx, uint32_t out[2]);
  * tbvh_pinned_malloc) and the library's pinned host buffers are not.  Both return to their earlier values once everything created since was freed:
  * what tests/test_device_memory.py asserts.  Needs no device and no context. */
 int tbvh_debug_device_allocations(uint64_t out[2]);
+/* tbvh_scene_device_bytes of any scene term by term, filled by the same list of terms (tinybvh_amd/csrc/capi_scene.hip: sceneBytesByWord): out[0] the arrays
+ * as uploaded, converted or built, [1] the re-layouts of a BVH8_CWBVH scene (padded nodes, hybrid nodes, 64-byte triangle records), [2] the wide copies (each
+ * copy's own tbvh_scene_device_bytes, now), [3] opacity maps (on the scene they were set on), [4] the index buffer a scene made from an indexed mesh holds,
+ * [5] an fp32 TLAS's wide trees, references and SAH Wald nodes, or an fp64 TLAS's one allocation, [6] counted scratch and staging (sphere and fp64 scenes, the
+ * SAH TLAS builder), [7] what the scene holds and does NOT count (a triangle scene's refit scratch and staging, the hybrid copy's numbering, a TLAS's shared
+ * scratch, bounds, staged transforms and descriptor tables), at allocation size.  out[0] + ... + out[6] == tbvh_scene_device_bytes( scene ), always. */
+int tbvh_debug_scene_bytes(const tbvh_scene* scene, uint64_t out[8]);
 
 /* The device address of one of a scene graph's arrays (what: the TBVH_GRAPH_* codes of tbvh_scenegraph_download; TBVH_GRAPH_COMBINED: the last walk's), so that a
  * test can overwrite a table or a key state on the device and see the kernels' own range checks answer (tests/test_scenegraph_gpu.py).  Not for products: the

@@ -494,6 +494,13 @@ class _Scene:
     def device_bytes(self) -> int:
         return int(lib.tbvh_scene_device_bytes(self._h))
 
+    def debug_bytes(self) -> list:
+        """device_bytes term by term (tbvh_debug_scene_bytes; the eight words are include/tinybvh_amd_debug.h's): words 0 to 6 sum to device_bytes,
+        word 7 is what the scene holds and does not count."""
+        out = np.zeros(8, np.uint64)
+        check(lib.tbvh_debug_scene_bytes(self._h, _ptr(out)), "tbvh_debug_scene_bytes")
+        return [int(x) for x in out]
+
     def _build_mesh(self, layout: int, verts, indices, kw) -> "_Scene":
         """Build over an indexed / strided mesh on the host and upload (tbvh_host_build_mesh + tbvh_upload_host_mesh)."""
         self.host = HostBVH(verts, layout, indices=indices, **kw)

@@ -118,6 +118,7 @@ SYMBOLS = {
     "tbvh_free_scene": (None, [_vp]),
     "tbvh_scene_layout": (_i, [_vp]),
     "tbvh_scene_device_bytes": (_u64, [_vp]),
+    "tbvh_debug_scene_bytes": (_i, [_vp, _vp]),
     "tbvh_intersect": (_i, [_vp, _vp, _u64, _u32]),
     "tbvh_occluded": (_i, [_vp, _vp, _u64, _u32, _vp]),
     "tbvh_intersect_sharded": (_i, [_vp, _u32, _vp, _u64, _u32]),

@@ -1,6 +1,6 @@
 // capi_copies.hip — what the library derives from a scene's arrays and keeps beside them: the wide copies of a BLAS in another layout (WideCopies) and
 // the re-layouts of a BVH8_CWBVH scene's own arrays (CwbvhLayouts).  Everything that makes, drops, refits or selects one is here; WHEN the wide copies
-// go and come back is CopyPolicy's arithmetic (copy_policy.h).  `bytes` of the owner counts them all.
+// go and come back is CopyPolicy's arithmetic (copy_policy.h).  The owner's bytes count them all, as they are when asked (capi_scene.hip: sceneBytes).
 #include "capi_internal.h"
 
 using namespace tbvh;
@@ -19,7 +19,6 @@ static int padCwbvhIfLarge(tbvh_scene* s) {
     launch_cwbvh_pad(s->nodes, s->cw.padded, s->nNodes, c->stream);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(c->stream));
-    s->bytes += (uint64_t)s->nNodes * 128;
     return 0;
 }
 
@@ -88,7 +87,6 @@ int prepareIncoherentCopies(tbvh_scene* s) {
     HIP_TRY(hipMemsetAsync(s->cw.hybrid, 0, hybridBytes(s->nNodes, K), c->stream));
     if (int r = rederiveCwbvhLayouts(s)) return r;
     HIP_TRY(hipStreamSynchronize(c->stream));
-    s->bytes += hybridBytes(s->nNodes, K) + nT * 64;
     return 0;
 }
 
@@ -119,7 +117,6 @@ void freeCopy(tbvh_scene* s, CopyKind kind) {
     tbvh_scene* w = slot;
     if (!w) return;
     slot = nullptr;
-    s->bytes -= w->bytes < s->bytes ? w->bytes : 0;
     tbvh_free_scene(w);   // (the opacity maps it read are the owner's: tbvh_scene::opmapOwn)
 }
 
@@ -206,7 +203,7 @@ static int makeCopy(tbvh_scene* s, CopyKind kind) {
     (four ? s->copies.tried4 : s->copies.tried8) = true;
     const bool has = !s->isTlas && layoutHasCopy(s, kind);
     if (tbvh_scene* w = has ? buildCopy(s, four ? TBVH_LAYOUT_BVH4_GPU : TBVH_LAYOUT_CWBVH, four || !s->usedBy.empty()) : nullptr) {
-        (four ? s->copies.copy4 : s->copies.copy8) = w; s->bytes += w->bytes;
+        (four ? s->copies.copy4 : s->copies.copy8) = w;
         if (!four) {
             // a copy below the size at which the scene's OWN queries gain from it (made for the TLASes over the scene): those queries keep the uploaded nodes
             const uint64_t entries = s->layout == TBVH_LAYOUT_BVH_GPU ? s->nTriBlocks / 3 : w->nTriBlocks / 3;
@@ -274,7 +271,7 @@ extern "C" int tbvh_cwbvh_set_hybrid(tbvh_scene* s, int64_t packedNodes) {
     tbvh_context* c = s->ctx;
     TBVH_ENTER(c);
     HIP_TRY(hipStreamSynchronize(c->stream));
-    if (s->cw.hybrid) { s->bytes -= hybridBytes(s->nNodes, s->cw.packed); s->cw.hybrid.reset(); }
+    s->cw.hybrid.reset();
     s->cw.tried = true;   // the caller decides now: no lazy build behind its back
     if (packedNodes < 0) return 0;
     if (s->nTriBlocks / 3 >= (1ull << 27)) return fail(TBVH_E_INVALID, "tbvh_cwbvh_set_hybrid: 2^27 triangle records or more");
@@ -287,11 +284,9 @@ extern "C" int tbvh_cwbvh_set_hybrid(tbvh_scene* s, int64_t packedNodes) {
     HIP_TRY(s->cw.hybrid.alloc(hybridBlocks(s->nNodes, K)));
     HIP_TRY(hipMemsetAsync(s->cw.hybrid, 0, hybridBytes(s->nNodes, K), c->stream));
     s->cw.packed = K;
-    s->bytes += hybridBytes(s->nNodes, K);
     if (!s->cw.trisPadded && s->nTriBlocks) {
         const uint64_t nT = s->nTriBlocks / 3;
         HIP_TRY(s->cw.trisPadded.alloc(nT * 4));
-        s->bytes += nT * 64;
     }
     if (int r = rederiveCwbvhLayouts(s)) return r;
     HIP_TRY(hipStreamSynchronize(c->stream));

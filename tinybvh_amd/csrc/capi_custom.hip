@@ -47,7 +47,6 @@ int tbvh_upload_custom_spheres(tbvh_context* c, const void* nodes32, uint64_t nN
     }
     s->nNodes = (uint32_t)nNodes;
     s->nNodeBlocks = nNodes * 2; s->nTriBlocks = nIdx * 2;
-    s->bytes = nNodes * 32 + nIdx * 32;
     s->sphN = nSpheres;
     *out = s;
     return 0;
@@ -81,11 +80,6 @@ int tbvh_host_build_custom_spheres(const void* spheres16, uint64_t n, tbvh_hostb
 }  // extern "C"
 
 namespace {
-
-// what a sphere scene holds on the device: the two arrays the kernels walk and everything the build, rebuild and refit calls keep between frames
-uint64_t sphereSceneBytes(const tbvh_scene* s) {
-    return (s->nodes.count() + s->tris.count()) * 16 + s->sphIdx.count() * 4 + s->buildScratch.count() + s->refitScratch.count() + s->vertStage.count();
-}
 
 // the refusals the calls on an existing sphere scene share; 0: s is a sphere BLAS and spheres16 / n are usable
 int checkMovingSpheres(const char* who, const tbvh_scene* s, const void* spheres16, uint64_t n) {
@@ -150,7 +144,6 @@ int buildSphereTree(tbvh_scene* s, const char* who, const float4* dSph, uint64_t
     HIP_TRY(hipStreamSynchronize(c->stream));   // (the caller's spheres may change; a launch error surfaces here)
     s->nNodes = built;
     s->nNodeBlocks = (uint64_t)built * 2; s->nTriBlocks = n * 2;
-    s->bytes = sphereSceneBytes(s);
     return 0;
 }
 
@@ -217,7 +210,6 @@ int tbvh_refit_custom_spheres(tbvh_scene* s, const void* spheres16, uint64_t n, 
     HIP_TRY(launch_refit_spheres(s->nodes, s->nNodes, s->tris, s->nTriBlocks / 2, dSph, n, (uint32_t*)s->refitScratch.get(), c->stream));
     HIP_TRY(timedEnd(c));
     HIP_TRY(hipStreamSynchronize(c->stream));   // (the caller's spheres may change)
-    s->bytes = sphereSceneBytes(s);
     return 0;
 }
 

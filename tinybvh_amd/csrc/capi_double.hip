@@ -211,7 +211,6 @@ int tbvh_upload_bvh_double(tbvh_context* c, const void* nodes64, uint64_t nNodes
     if (hipGetLastError() != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) return bail(TBVH_E_HIP, "triangle gather failed");
     s->nNodes = (uint32_t)nNodes;
     s->dblTris = nTris; s->dblRecs = nIdx;
-    s->bytes = nNodes * sizeof(NodeDbl) + nIdx * sizeof(TriDbl);
     *out = s;
     return 0;
 }
@@ -250,7 +249,6 @@ int tbvh_upload_tlas_double(tbvh_context* c, const void* nodes64, uint64_t nNode
         return fail(TBVH_E_HIP, "tbvh_upload_tlas_double: copy to the device failed");
     }
     for (uint64_t i = 0; i < nBlas; i++) { s->tlas.blasList.push_back(blas[i]); blas[i]->usedBy.push_back(s); }   // (the BLASes outlive the TLAS: tbvh_free_scene)
-    s->bytes = total;
     *out = s;
     return 0;
 }
@@ -375,8 +373,6 @@ int checkDoubleScene(const tbvh_scene* s, bool wantTlas, const char* who) {
     return 0;
 }
 
-void accountTlas(tbvh_scene* s) { s->bytes = tlasLayout(s->dblCapNodes, s->dblCapIdx, s->dblCapInst, s->tlas.nBlas).total + s->buildScratch.count(); }
-
 // The TLAS in a new allocation whose parts hold capNodes / capIdx / capInst (each at least what the scene holds now): everything is carried over, the
 // BLAS descriptors with it, so the scene answers as before; synchronizes, then the old allocation goes.  A failure leaves the scene as it was.
 int moveTlas(tbvh_scene* s, uint64_t capNodes, uint64_t capIdx, uint64_t capInst, const char* who) {
@@ -394,7 +390,6 @@ int moveTlas(tbvh_scene* s, uint64_t capNodes, uint64_t capIdx, uint64_t capInst
         return fail(TBVH_E_HIP, "%s: moving the TLAS failed", who);
     s->nodes = std::move(fresh);
     s->dblCapNodes = capNodes; s->dblCapIdx = capIdx; s->dblCapInst = capInst;
-    accountTlas(s);
     return 0;
 }
 
@@ -417,9 +412,8 @@ int tbvh_rebuild_tlas_double_device(tbvh_scene* s, const void* transformsDbl16, 
     if (s->buildScratchFor != n) {
         s->buildScratchFor = 0;
         const size_t bytes = tlas_dbl_build_scratch_bytes((uint32_t)n, &s->sortTempBytes);
-        if (s->buildScratch.alloc(bytes) != hipSuccess) { accountTlas(s); return fail(TBVH_E_NOMEM, "%s: out of device memory for %zu bytes of scratch", who, bytes); }
+        if (s->buildScratch.alloc(bytes) != hipSuccess) return fail(TBVH_E_NOMEM, "%s: out of device memory for %zu bytes of scratch", who, bytes);
         s->buildScratchFor = n;
-        accountTlas(s);
     }
     const double* xf = nullptr;
     if (transformsDbl16) {
@@ -514,13 +508,10 @@ int tbvh_refit_double(tbvh_scene* s, const void* vertsDbl3, uint64_t nTris, int 
             return fail(TBVH_E_HIP, "%s: the parent pass failed", who);
         s->refitScratch = std::move(keep);
         s->dblLeaves = nLeaves;
-        s->bytes += (uint64_t)nNodes * 12;
     }
     const double* dv = (const double*)vertsDbl3;
     if (!onDevice) {
-        const size_t had = s->vertStage.count();
-        if (s->vertStage.reserve(nTris * 72) != hipSuccess) { s->bytes -= had; return fail(TBVH_E_NOMEM, "%s: out of device memory for the vertices", who); }
-        s->bytes += s->vertStage.count() - had;
+        if (s->vertStage.reserve(nTris * 72) != hipSuccess) return fail(TBVH_E_NOMEM, "%s: out of device memory for the vertices", who);
         HIP_TRY(hipMemcpyAsync(s->vertStage, vertsDbl3, nTris * 72, hipMemcpyHostToDevice, c->stream));
         dv = (const double*)s->vertStage.get();
     }

@@ -239,7 +239,7 @@ struct CwbvhLayouts {
 
 // What only a TLAS holds (capi_scene.hip makes, classifies, updates and rebuilds it; a BVH_DOUBLE TLAS — capi_double.hip — uses the counts and the BLAS
 // list).  WHICH arrays each BLAS is entered through, which wide trees are kept and which kernel serves a query is `plan` (tlas_plan.h), stated again by
-// reclassifyTlas whenever a fact it reads changes; `bytes` of the scene is derived from what is held here (tlasBytes).
+// reclassifyTlas whenever a fact it reads changes; what the scene reports as its bytes is derived from what is held here (sceneBytes).
 struct TlasState {
     DevBuf<uint32_t> tlasIdx;
     DevBuf<float4> instances;   // 12 per instance
@@ -263,7 +263,7 @@ struct TlasState {
     // device-side TLAS rebuild (kernels_tlasbuild.hip)
     DevBuf<float> blasBounds;         // 6 floats per BLAS
     // tbvh_tlas_set_builder: 0 = LBVH, 2 = the reference's SAH tree (kernels_sahbuild.hip over the instance records, then the device Aila-Laine encode).
-    // The SAH build keeps its Wald nodes (2 n) and its scratch here, sized for tlasSahFor instances: no allocation per frame; `bytes` counts them.
+    // The SAH build keeps its Wald nodes (2 n) and its scratch here, sized for tlasSahFor instances: no allocation per frame; sceneBytes counts them.
     int tlasBuilder = 0;
     DevBuf<float4> tlasWald;
     DevBuf<void> tlasSah;
@@ -285,7 +285,6 @@ struct tbvh_scene {
     uint64_t nNodeBlocks = 0, nTriBlocks = 0;
     uint64_t capNodeBlocks = 0, capTriBlocks = 0;   // what the allocations hold (tbvh_update_*: a re-converted blob of at most this size goes in place)
     uint64_t topoHash = 0;       // CWBVH: hash of every node's (imask, child base): an update with the same topology keeps the hybrid copy's numbering
-    uint64_t bytes = 0;
     // TLAS (layout = BVH_GPU nodes in `nodes`; a BVH_DOUBLE TLAS keeps its counts and BLAS list in `tlas` too)
     bool isTlas = false;
     TlasState tlas;
@@ -307,9 +306,8 @@ struct tbvh_scene {
     uint32_t* opmap = nullptr;
     DevBuf<uint32_t> opmapOwn;
     uint32_t opmapN = 0;
-    uint64_t opmapBytes = 0;
-    // a scene made from an INDEXED mesh (tbvh_*_mesh with indices) keeps its own device copy of the index buffer, 12 bytes per triangle, counted in
-    // `bytes`: tbvh_refit_mesh with indices == NULL then means "the indices the scene holds" — the per-frame call of an animated mesh passes the
+    // a scene made from an INDEXED mesh (tbvh_*_mesh with indices) keeps its own device copy of the index buffer, 12 bytes per triangle, counted by
+    // sceneBytes: tbvh_refit_mesh with indices == NULL then means "the indices the scene holds" — the per-frame call of an animated mesh passes the
     // shared vertices only.  The derived copies (WideCopies) hold none: their refit is handed the owner's source.
     DevBuf<uint32_t> meshIdx;
     uint64_t meshIdxTris = 0;
@@ -319,7 +317,7 @@ struct tbvh_scene {
     // a sphere BLAS that moves (capi_custom.hip: tbvh_build_device_custom_spheres / tbvh_rebuild_custom_spheres_device / tbvh_refit_custom_spheres): the
     // sphere count and the builder a rebuild repeats (an uploaded scene: LBVH, one sphere per leaf).  The build keeps its scratch in buildScratch
     // (sized for buildScratchFor spheres) and its primIdx here, the refit its pass words in refitScratch, host spheres are staged in vertStage: no
-    // allocation per frame; `bytes` counts them all.
+    // allocation per frame; sceneBytes counts them all.
     uint64_t sphN = 0;
     int sphBuilder = 0;                  // 0 LBVH, 1 PLOC, 2 SAH (tbvh_build_device_custom_spheres_sah; sphMaxLeaf 0 = the leaves BVH::Build makes)
     uint32_t sphMaxLeaf = 1, sphRadius = 16;
@@ -327,7 +325,7 @@ struct tbvh_scene {
     DevBuf<uint32_t> sphIdx;
     // BVH_DOUBLE scenes that move (capi_double.hip).  A TLAS: what the parts of its one allocation hold (tlasParts lays them out by these, so a smaller
     // tree goes in place); the rebuild keeps its scratch in buildScratch (sized for buildScratchFor instances).  A BLAS: its triangle count, and from the
-    // first refit on parent[] | leaf list | flags in refitScratch (dblLeaves leaves); host vertices are staged in vertStage.  `bytes` counts them all.
+    // first refit on parent[] | leaf list | flags in refitScratch (dblLeaves leaves); host vertices are staged in vertStage.  sceneBytes counts them all.
     uint64_t dblCapNodes = 0, dblCapIdx = 0, dblCapInst = 0;
     uint64_t dblTris = 0, dblRecs = 0;
     uint32_t dblLeaves = 0;
@@ -427,6 +425,12 @@ int checkStatus(tbvh_context* c);   // synchronizes the stream, turns the device
 int ensureStage(tbvh_context* c, uint64_t n);      // (capi_query.hip) the host-array staging buffers hold at least n ray records ...
 int ensureStageOcc(tbvh_context* c, uint64_t n);   // ... and n any-hit result bytes
 tbvh_scene* newScene(tbvh_context* c, int layout);
+// (capi_scene.hip) what scene s costs on the device, as a function of what it holds NOW: the one list of terms behind tbvh_scene_device_bytes, planLaunch's
+// blobBytes and tbvh_debug_scene_bytes.  word[0..6] are counted, word[7] is held but not counted (the words: include/tinybvh_amd_debug.h).  Follows the
+// scene's wide copies: the caller holds the context's lock.
+struct SceneBytes { uint64_t word[8]; };
+SceneBytes sceneBytesByWord(const tbvh_scene* s);
+uint64_t sceneBytes(const tbvh_scene* s);   // word[0] + ... + word[6]
 TlasFacts tlasFactsNow(const tbvh_scene* s, std::vector<TlasBlasFacts>& blas);   // (capi_scene.hip) the facts of TLAS s as they are now; `blas` holds the per-BLAS part
 int reclassifyTlas(tbvh_scene* t);   // (capi_scene.hip) the plan (tlas_plan.h), descriptors and wide trees of a TLAS from its BLASes as they are now
 // ---- derived copies (capi_copies.hip): WideCopies and CwbvhLayouts are made, dropped, refitted and selected there and nowhere else -----------

@@ -59,12 +59,11 @@ int keepMeshIndices(tbvh_scene* s, const MeshSrc& src) {
     if (!src.indices) return 0;
     if (s->meshIdx && s->meshIdxTris != src.nTris) {
         HIP_TRY(hipStreamSynchronize(s->ctx->stream));
-        s->meshIdx.reset();
-        s->bytes -= s->meshIdxTris * 12; s->meshIdxTris = 0;
+        s->meshIdx.reset(); s->meshIdxTris = 0;
     }
     if (!s->meshIdx) {
         HIP_TRY(s->meshIdx.alloc(src.nTris * 3));
-        s->meshIdxTris = src.nTris; s->bytes += src.nTris * 12;
+        s->meshIdxTris = src.nTris;
     }
     HIP_TRY(hipMemcpyAsync(s->meshIdx, src.indices, src.nTris * 12, hipMemcpyDeviceToDevice, s->ctx->stream));
     return 0;

@@ -472,7 +472,7 @@ static int planLaunch(tbvh_scene* s, uint64_t n, bool sizeKnown, const Launch& L
     tbvh_context* c = s->ctx;
     LaunchFacts f;
     f.isTlas = s->isTlas; f.layout = s->layout; f.variant = s->variant; f.n = n; f.sizeKnown = sizeKnown; f.any = L.any;
-    f.blobBytes = (!s->isTlas && s->layout == TBVH_LAYOUT_CWBVH) ? (s->nNodeBlocks + s->nTriBlocks) * 16 : s->bytes;   // (without the library's own copies)
+    f.blobBytes = (!s->isTlas && s->layout == TBVH_LAYOUT_CWBVH) ? (s->nNodeBlocks + s->nTriBlocks) * 16 : sceneBytes(s);   // (BVH8_CWBVH: without the library's own copies)
     f.gridOverride = c->gridOverride; f.numCUs = (uint32_t)c->numCUs; f.blocks = c->blocks; f.raysPerBlock = c->raysPerBlock;
     f.expFlags = c->expFlags; f.cohTunerMode = c->cohTunerMode; f.probeMemoryOn = c->probeMemoryOn; f.skipTiming = c->skipTiming;
     for (int k = 0; k < 4; k++) f.decided[k] = s->cohTuner[L.any ? 1 : 0][k].decided;

@@ -15,6 +15,58 @@ tbvh_scene* newScene(tbvh_context* c, int layout) {
     return s;
 }
 
+// ---- what a scene costs on the device ------------------------------------------------------------------------------------------------------
+// A function of what the scene holds now, never of the route to it; nothing keeps a running total beside the buffers.  The rule:
+//   * arrays the CALLER uploaded count at what they hold now (nNodeBlocks, nTriBlocks, nTlasNodes ...): an update with a smaller blob lowers the number,
+//     whatever the allocation still has room for;
+//   * buffers the LIBRARY made for itself count at their allocation (DevBuf::count()).
+// The terms, one line each, with the word of tbvh_debug_scene_bytes they go to (words 0 to 6 are the number; 7 is held and NOT counted):
+//   [0] the arrays as uploaded / converted / built: triangle layouts and the fp32 TLAS by their live counts, an fp64 BLAS by its node and record counts; a
+//       sphere BLAS and a voxel set by their allocations (a device-built sphere tree lives in arrays the library sized for 2 n nodes)
+//   [1] a BVH8_CWBVH scene's re-layouts (CwbvhLayouts): padded nodes, hybrid nodes, 64-byte triangle records
+//   [2] the wide copies, each asked for ITS bytes now: a copy that grows or goes is right by construction
+//   [3] opacity maps, on the scene that owns them (a copy shares its owner's pointer and holds none)
+//   [4] the index buffer a scene made from an indexed mesh holds
+//   [5] an fp32 TLAS's wide trees, the 8-wide tree's references and the SAH builder's Wald nodes; an fp64 TLAS's one allocation (capi_double.hip: tlasLayout( its
+//       capacities ).total, which is what `nodes` was allocated with)
+//   [6] counted scratch and staging: the SAH TLAS builder's scratch, a sphere BLAS's primIdx, and ON SPHERE AND fp64 SCENES ONLY buildScratch, refitScratch, vertStage
+//   [7] everything else a scene holds: buildScratch, refitScratch and vertStage of every other kind of scene, idxStage, the hybrid copy's numbering (cw.perm), a
+//       TLAS's shared wide-build scratch, BLAS bounds, staged transforms and descriptor tables
+//       (the eight words do NOT claim to sum to the scene's allocations: the room an uploaded array keeps beyond what it holds now is in none of them)
+// KNOWN INCONSISTENCY, kept as it was: a triangle scene's refit scratch (144 bytes per node: more than the tree) and staging are not counted, a sphere or fp64
+// scene's are.  Counting them would move blobBytes of refitted BVH_GPU / BVH4_GPU scenes across launch_plan.h's 48 MB and 384 MB lines; that wants numbers.
+SceneBytes sceneBytesByWord(const tbvh_scene* s) {
+    SceneBytes b{};
+    uint64_t* w = b.word;
+    const TlasState& t = s->tlas;
+    const bool dbl = s->layout == TBVH_LAYOUT_BVH_DOUBLE, sphere = s->layout == TBVH_LAYOUT_BVH2_WALD, voxel = s->layout == TBVH_LAYOUT_VOXELSET;
+    const bool tlas32 = s->isTlas && !dbl, tlas64 = s->isTlas && dbl, blas64 = !s->isTlas && dbl;
+    const bool triangles = !s->isTlas && !dbl && !sphere && !voxel;   // BVH_GPU, BVH4_GPU, BVH8_CWBVH
+    if (triangles) w[0] += (s->nNodeBlocks + s->nTriBlocks) * 16;
+    if (tlas32) w[0] += t.nTlasNodes * 64 + t.nTlasIdx * 4 + t.nInst * 192;
+    if (blas64) w[0] += (uint64_t)s->nNodes * sizeof(NodeDbl) + s->dblRecs * sizeof(TriDbl);
+    if (sphere || voxel) w[0] += (s->nodes.count() + s->tris.count()) * 16;
+    w[1] += (s->cw.padded.count() + s->cw.hybrid.count() + s->cw.trisPadded.count()) * 16;
+    if (s->copies.copy8) w[2] += sceneBytes(s->copies.copy8);
+    if (s->copies.copy4) w[2] += sceneBytes(s->copies.copy4);
+    w[3] += s->opmapOwn.count() * 4;
+    w[4] += s->meshIdx.count() * 4;
+    if (tlas32) w[5] += (t.tlas4.count() + t.tlas8.count() + t.tlasWald.count()) * 16 + t.tlas8Refs.count() * 4;
+    if (tlas64) w[5] += s->nodes.count() * 16;
+    w[6] += t.tlasSah.count() + s->sphIdx.count() * 4;
+    w[sphere || dbl ? 6 : 7] += s->buildScratch.count() + s->refitScratch.count() + s->vertStage.count();
+    w[7] += (s->idxStage.count() + s->cw.perm.count()) * 4;
+    w[7] += t.tlas4Scratch.count() + (t.blasBounds.count() + t.xformStage.count()) * 4 + (t.blasDesc.count() + t.blasDescAny.count()) * sizeof(BlasDesc);
+    return b;
+}
+
+uint64_t sceneBytes(const tbvh_scene* s) {
+    const SceneBytes b = sceneBytesByWord(s);
+    uint64_t sum = 0;
+    for (int k = 0; k < 7; k++) sum += b.word[k];
+    return sum;
+}
+
 // ---- device refit (tbvh_refit / tbvh_refit_mesh below) ----------------------------------------------------------------------------------
 // the refit itself: src is device-resident (the caller's arrays, the scene's vertex staging buffer, the scene's held index buffer)
 int refitDeviceSource(tbvh_scene* s, const MeshSrc& src) {
@@ -51,7 +103,7 @@ extern "C" {
 
 // What a BVH_GPU upload and an in-place update share (skipped when e comes in as an error): the blob's nodes go into s->nodes, its primIdx names triangles,
 // whose vertices the gather finds through the mesh (flat: 3 float4 per triangle) and writes to s->tris, an indexed mesh leaves its indices with the scene
-// (counted in s->bytes: set before); synchronous.  e: the first HIP error — the caller words it and cleans up —, r: keepMeshIndices' code; general: the gather
+// (sceneBytes counts them); synchronous.  e: the first HIP error — the caller words it and cleans up —, r: keepMeshIndices' code; general: the gather
 // read through indices or a stride, so checkStatus is due (device-resident indices: the gather reports an index that is not a vertex)
 struct BvhGpuFill { hipError_t e; int r; bool indexed, general; };
 static BvhGpuFill fillBvhGpu(tbvh_scene* s, hipError_t e, const void* nodes64, uint64_t nNodes, const uint32_t* primIdx, uint64_t nIdx, const tbvh_mesh& mesh) {
@@ -78,7 +130,6 @@ static int uploadBvhGpuImpl(tbvh_context* c, const void* nodes64, uint64_t nNode
     if (e == hipSuccess) e = s->tris.alloc((nIdx ? nIdx : 1) * 3);
     s->nNodeBlocks = nNodes * 4; s->nTriBlocks = nIdx * 3;
     s->capNodeBlocks = s->nNodeBlocks; s->capTriBlocks = s->nTriBlocks;
-    s->bytes = nNodes * 64 + nIdx * 48;
     const BvhGpuFill f = fillBvhGpu(s, e, nodes64, nNodes, primIdx, nIdx, mesh);
     if (f.e != hipSuccess) { tbvh_free_scene(s); return fail(TBVH_E_HIP, "BVH_GPU upload failed: %s", hipGetErrorString(f.e)); }
     int r = f.r;
@@ -110,7 +161,7 @@ int tbvh_upload_bvh4_gpu(tbvh_context* c, const void* blocks16, uint64_t nBlocks
     if (e == hipSuccess) e = hipMemcpyAsync(s->nodes, blocks16, nBlocks * 16, hipMemcpyHostToDevice, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
     if (e != hipSuccess) { tbvh_free_scene(s); return fail(TBVH_E_HIP, "BVH4_GPU upload failed: %s", hipGetErrorString(e)); }
-    s->nNodeBlocks = nBlocks; s->capNodeBlocks = nBlocks; s->bytes = nBlocks * 16;
+    s->nNodeBlocks = nBlocks; s->capNodeBlocks = nBlocks;
     *out = s;
     return 0;
 }
@@ -134,21 +185,12 @@ int tbvh_upload_cwbvh(tbvh_context* c, const void* nodes16, uint64_t nNodeBlocks
     s->nNodeBlocks = nNodeBlocks; s->nTriBlocks = nTriBlocks;
     s->capNodeBlocks = nNodeBlocks; s->capTriBlocks = nTriBlocks ? nTriBlocks : 1;
     s->topoHash = cwbvhTopologyHash((const Vec4*)nodes16, s->nNodes);
-    s->bytes = (nNodeBlocks + nTriBlocks) * 16;
     if (int r = resetCwbvhLayouts(s)) { tbvh_free_scene(s); return r; }
     *out = s;
     return 0;
 }
 
 namespace {
-// `bytes` of a TLAS, from what it holds: node, index and instance arrays by their live counts, both wide trees and the 8-wide tree's references by their
-// allocated capacity, the SAH builder's Wald nodes and scratch.  (The shared scratch areas and staging buffers are not counted, as they never were.)
-void accountTlas(tbvh_scene* s) {
-    const TlasState& t = s->tlas;
-    s->bytes = t.nTlasNodes * 64 + t.nTlasIdx * 4 + t.nInst * 192 + (t.tlas4.count() + t.tlas8.count()) * 16 + t.tlas8Refs.count() * 4 + t.tlasSah.count() +
-               t.tlasWald.count() * 16;
-}
-
 // the 8-wide TLAS in the BVH8_CWBVH node format, from the BVH_GPU nodes on the device; asynchronous on the context's stream
 int buildTlasWide8(tbvh_scene* s) {
     tbvh_context* c = s->ctx;
@@ -195,7 +237,6 @@ int buildWideTlas(tbvh_scene* s) {
     if (t.plan.want4 && !t.plan.fits4) t.tlas4.reset();
     if (t.plan.fits8 && (r = buildTlasWide8(s)) != 0) planTlasFit(t.plan, true, ~0ull, cap4);   // (the two builds share the scratch area: in order on one stream)
     if (!r && t.plan.fits4 && (r = buildTlasWide4(s)) != 0) planTlasFit(t.plan, true, cap8, ~0ull);
-    accountTlas(s);
     return r;
 }
 
@@ -314,8 +355,7 @@ static int updateBvhGpuImpl(const char* who, tbvh_scene* s, const void* nodes64,
     const BvhGpuFill f = fillBvhGpu(s, hipSuccess, nodes64, nNodes, primIdx, nIdx, *mesh);
     if (f.e != hipSuccess) return fail(TBVH_E_HIP, "%s: %s", who, hipGetErrorString(f.e));
     if (!f.indexed && s->meshIdx) {   // re-uploaded from vertices without indices: a held index buffer would describe another mesh
-        s->meshIdx.reset();
-        s->bytes -= s->meshIdxTris * 12; s->meshIdxTris = 0;
+        s->meshIdx.reset(); s->meshIdxTris = 0;
     }
     s->nNodeBlocks = nNodes * 4; s->nTriBlocks = nIdx * 3;
     dropCopiesAfterUpdate(s);   // (the copies are of the old tree: they come back once the blob has settled — copy_policy.h)
@@ -364,13 +404,11 @@ static int updateCwbvhImpl(tbvh_scene* s, const void* nodes16, uint64_t nNodeBlo
     const uint32_t nNodes = (uint32_t)(nNodeBlocks / 5);
     const uint64_t hash = cwbvhTopologyHash((const Vec4*)nodes16, nNodes);
     const bool sameShape = nNodes == s->nNodes && nTriBlocks == s->nTriBlocks && hash == s->topoHash;
-    s->bytes -= (s->nNodeBlocks + s->nTriBlocks) * 16; s->bytes += (nNodeBlocks + nTriBlocks) * 16;
     s->nNodes = nNodes; s->nNodeBlocks = nNodeBlocks; s->nTriBlocks = nTriBlocks; s->topoHash = hash;
     s->refitScratch.reset();   // (sized and filled for the old tree)
     if (!sameShape) for (auto& kind : s->cohTuner) for (CohTuner& tu : kind) if (!tu.pinned) { tu.drop_pending(); tu = CohTuner(); }   // (its timings were taken on the old tree)
     if (sameShape) return rederiveCwbvhLayouts(s);   // boxes and vertices moved, the tree did not: the derived copies keep their numbering and are re-derived on the device
     // another tree in the same allocation: the derived copies go; they come back as at upload
-    s->bytes = (nNodeBlocks + nTriBlocks) * 16 + s->opmapBytes;
     return resetCwbvhLayouts(s);
 }
 
@@ -411,7 +449,7 @@ int convertDeviceImpl4(tbvh_context* c, const float4* dN2, uint64_t nNodes2, con
     if (e == hipSuccess) e = hipMemcpyAsync(s->nodes, blocks, nBlocks * 16, hipMemcpyDeviceToDevice, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
     if (e != hipSuccess) { tbvh_free_scene(s); return fail(TBVH_E_HIP, "BVH2 -> BVH4_GPU: %s", hipGetErrorString(e)); }
-    s->nNodeBlocks = nBlocks; s->capNodeBlocks = nBlocks; s->bytes = nBlocks * 16;
+    s->nNodeBlocks = nBlocks; s->capNodeBlocks = nBlocks;
     *out = s;
     return 0;
 }
@@ -450,7 +488,6 @@ int convertDeviceImpl(tbvh_context* c, int layout, const float4* dN2, uint64_t n
     if (e != hipSuccess) { tbvh_free_scene(s); return fail(TBVH_E_HIP, "BVH2 -> CWBVH: %s", hipGetErrorString(e)); }
     s->nNodes = nWide; s->nNodeBlocks = (uint64_t)nWide * 5; s->nTriBlocks = nWideTris * 3;
     s->capNodeBlocks = s->nNodeBlocks; s->capTriBlocks = nWideTris ? s->nTriBlocks : 3;
-    s->bytes = (s->nNodeBlocks + s->nTriBlocks) * 16;
     if (int r = resetCwbvhLayouts(s, true)) { tbvh_free_scene(s); return r; }   // (level order is close to priority order: the incoherent-batch copies need no renumbering)
     *out = s;
     return 0;
@@ -634,12 +671,9 @@ int allocOpacityMaps(tbvh_context* c, uint32_t N, uint64_t nTris, const char* wh
 int installOpacityMaps(tbvh_scene* s, DevBuf<uint32_t>&& fresh, uint32_t N) {
     tbvh_context* c = s->ctx;
     HIP_TRY(hipStreamSynchronize(c->stream));   // no query may still read the old maps
-    const uint64_t freshBytes = fresh.count() * 4;
     DevBuf<uint32_t> old = std::move(s->opmapOwn);
-    const uint64_t oldBytes = s->opmapBytes;
     s->opmapOwn = std::move(fresh);
-    s->opmap = s->opmapOwn; s->opmapN = N; s->opmapBytes = freshBytes;
-    s->bytes += freshBytes; s->bytes -= oldBytes;
+    s->opmap = s->opmapOwn; s->opmapN = N;
     shareOpacityMaps(s);
     const int r = refreshBlasDescs(s);   // the descriptors are rewritten before the old maps go
     if (r != 0) (void)old.release();   // (a failed refresh may have left a descriptor on the old maps: leak them rather than dangle)
@@ -842,7 +876,20 @@ void tbvh_free_scene(tbvh_scene* s) {
     delete s;   // (its device buffers go here: the device is current, the stream idle)
 }
 int tbvh_scene_layout(const tbvh_scene* s) { return s ? s->layout : TBVH_E_INVALID; }
-uint64_t tbvh_scene_device_bytes(const tbvh_scene* s) { return s ? s->bytes : 0; }
+// (the lock: the number follows the scene's wide copies, which queries on other threads make and free)
+uint64_t tbvh_scene_device_bytes(const tbvh_scene* s) {
+    if (!s) return 0;
+    TBVH_LOCK(s->ctx);
+    return sceneBytes(s);
+}
+
+int tbvh_debug_scene_bytes(const tbvh_scene* s, uint64_t out[8]) {
+    if (!s || !out) return fail(TBVH_E_INVALID, "tbvh_debug_scene_bytes: null argument");
+    TBVH_LOCK(s->ctx);
+    const SceneBytes b = sceneBytesByWord(s);
+    std::memcpy(out, b.word, sizeof b.word);
+    return 0;
+}
 
 int tbvh_debug_coherent_schedule(tbvh_scene* s, int anyhit, uint32_t out[4]) {
     if (!s || !out) return fail(TBVH_E_INVALID, "tbvh_debug_coherent_schedule: null argument");

@@ -66,7 +66,6 @@ int tbvh_upload_voxelset(tbvh_context* c, const uint32_t* grid, const uint32_t* 
         return fail(TBVH_E_HIP, "tbvh_upload_voxelset: copy to the device failed");
     }
     s->nNodes = (uint32_t)nBricks;
-    s->bytes = words * 4;
     *out = s;
     return 0;
 }
