@@ -100,6 +100,13 @@ int tbvh_debug_tlas_state(tbvh_scene* scene, uint64_t* facts_out, uint32_t* plan
 int tbvh_debug_packet_cull(const void* nodes80, uint64_t n_nodes, const void* rays64, uint64_t have_mask, const float* tcull64, uint8_t* maybe_out,
                            uint8_t* exact_out, uint32_t* chunk_flags);
 
+/* The ray / triangle test in its two forms (tinybvh_amd/csrc/device_common.h), on the host; no device, no context: tri_test with its early-outs (the per-lane
+ * kernels) and tri_test_flat, the branch-free form of the wave-packet kernel.  n pairs: od6 = {O.xyz, D.xyz}, tri9 = {v0, e1 = v1 - v0, e2 = v2 - v0}, tmax = the
+ * ray's closest hit so far (inclusive).  Per pair: accept_* = 1 when the form reports a hit, tuv_* = its {t, u, v} (the branching form writes them only when it
+ * accepts: zeros otherwise; the flat form always).  The two must agree on accept, and bit for bit on t, u, v wherever they accept. */
+int tbvh_debug_tri_test_flat(const float* od6, const float* tri9, const float* tmax, uint64_t n, uint8_t* accept_branch, uint8_t* accept_flat, float* tuv_branch,
+                             float* tuv_flat);
+
 /* Diagnostic kernel variants of BVH8_CWBVH scenes (0 = default): 72 / 52 force the strict / the coherent schedule whatever
  * the probe says, 90 the incoherent flavor on the copies of tbvh_cwbvh_set_hybrid, 75 / 88 split the last rays whatever the batch size, 59 / 61 / 73 / 78 / 82 / 83 are the instrumented
  * kernels behind tbvh_debug_stats.  Returns TBVH_E_INVALID for anything else. */

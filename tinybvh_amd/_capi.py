@@ -86,6 +86,7 @@ SYMBOLS = {
     "tbvh_debug_tlas_plan": (_i, [_vp, _u32, _vp, _u32]),
     "tbvh_debug_tlas_state": (_i, [_vp, _vp, _vp]),
     "tbvh_debug_packet_cull": (_i, [_vp, _u64, _vp, _u64, _vp, _vp, _vp, _vp]),
+    "tbvh_debug_tri_test_flat": (_i, [_vp, _vp, _vp, _u64, _vp, _vp, _vp, _vp]),
     "tbvh_set_timing": (_i, [_vp, _i]),
     "tbvh_upload_bvh_gpu": (_i, [_vp, _vp, _u64, _vp, _u64, _vp, _u64, _pp]),
     "tbvh_upload_bvh4_gpu": (_i, [_vp, _vp, _u64, _pp]),

@@ -1,6 +1,7 @@
 // capi_context.hip — contexts, streams, timing, debug knobs, device buffers and the ceilings bench.py measures (include/tinybvh_amd.h).
 #include "capi_internal.h"
 #include "packet_cull.h"
+#include "device_common.h"
 
 using namespace tbvh;
 using namespace tbvh_capi;
@@ -430,6 +431,25 @@ int tbvh_debug_packet_cull(const void* nodes80, uint64_t nNodes, const void* ray
             }
         }
         maybeOut[n] = (uint8_t)maybe; exactOut[n] = (uint8_t)exact;
+    }
+    return 0;
+}
+
+// The ray / triangle test in its two forms (device_common.h), on the host (tests/test_tri_flat_host.py): tri_test with its early-outs, as the per-lane kernels run
+// it, and tri_test_flat, as the wave-packet kernel runs it.  Both are made of the same helpers; the library is built with -ffp-contract=off on the host too.
+int tbvh_debug_tri_test_flat(const float* od6, const float* tri9, const float* tmax, uint64_t n, uint8_t* acceptBranch, uint8_t* acceptFlat, float* tuvBranch,
+                             float* tuvFlat) {
+    if (n && (!od6 || !tri9 || !tmax || !acceptBranch || !acceptFlat || !tuvBranch || !tuvFlat)) return fail(TBVH_E_INVALID, "tbvh_debug_tri_test_flat: null argument");
+    for (uint64_t i = 0; i < n; i++) {
+        const float* r = od6 + 6 * i;
+        const float* t = tri9 + 9 * i;
+        const float3 O = make_float3(r[0], r[1], r[2]), D = make_float3(r[3], r[4], r[5]);
+        const float3 v0 = make_float3(t[0], t[1], t[2]), e1 = make_float3(t[3], t[4], t[5]), e2 = make_float3(t[6], t[7], t[8]);
+        TriHit hb = {0.f, 0.f, 0.f}, hf = {0.f, 0.f, 0.f};
+        acceptBranch[i] = tri_test(O, D, v0, e1, e2, tmax[i], hb) ? 1 : 0;
+        acceptFlat[i] = tri_test_flat(O, D, v0, e1, e2, tmax[i], hf) ? 1 : 0;
+        tuvBranch[3 * i] = hb.t; tuvBranch[3 * i + 1] = hb.u; tuvBranch[3 * i + 2] = hb.v;
+        tuvFlat[3 * i] = hf.t; tuvFlat[3 * i + 1] = hf.u; tuvFlat[3 * i + 2] = hf.v;
     }
     return 0;
 }

@@ -11,6 +11,9 @@ constexpr int kPacketWG = 64;
 
 __device__ __forceinline__ uint32_t sgpr(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
 
+// This lane's bit of a wave-uniform lane mask (a ballot's result, or several OR-ed together): the scalar pair IS the predicate, no instruction is spent.
+__device__ __forceinline__ bool pk_lane_bit(unsigned long long waveMask) { return __builtin_amdgcn_inverse_ballot_w64(waveMask); }
+
 // The children of the wave's current node against THIS lane's ray; the planes come from LDS (decoded once for the wave, near / far in the order of the
 // wave's octant).  Returns the WAVE's ordered hit mask (a child counts when any lane's ray enters its box).  Empty slots (meta byte 0) cost
 // no vector instruction — a wave-uniform branch.  They are rare where it matters: counted over ALL nodes of the bench scene's tree the mean is 5.6 children
@@ -60,11 +63,32 @@ __device__ __forceinline__ uint32_t pk_test_children(const float (*planes)[8], f
     return pk_test_children_of<MIXED>(planes, ax, ay, az, ox, oy, oz, tcull, m.placedL, m.nonEmpty);
 }
 
-// The few children the wave's filter left (`todo`: 1.4 of a camera wave's 7.6 on average, often none), one after the other: nothing is read from LDS and
-// no branch is taken for a slot that is not in the mask.  Wave-octant order only (a mixed chunk does not use the filter).
+// The few children the wave's filter left (`todo`: 1.4 of a camera wave's 7.6 on average, often none; not zero here), one after the other: nothing is read from
+// LDS and no branch is taken for a slot that is not in the mask.  Wave-octant order only (a mixed chunk does not use the filter).
+// PEEL = false: the plain loop (the closest-hit kernel with opacity micromaps has no registers left for a second child's planes).
+template <bool PEEL>
 __device__ __forceinline__ uint32_t pk_test_survivors(const float (*planes)[8], float ax, float ay, float az, float ox, float oy, float oz, float tcull,
                                                       uint32_t placedL, uint32_t todo) {
     uint32_t hitmask = 0;
+    if constexpr (PEEL) {
+    // The first two survivors peeled (more than two are rare): both slot numbers up front, both children's planes and `placed` words fetched before the first
+    // test — the loop below pays an LDS round trip per survivor —, one merged update of the hit mask.  `todo` is not zero.
+    const uint32_t c0 = (uint32_t)__builtin_ctz(todo);
+    todo &= todo - 1u;
+    const float4 qa0 = *(const float4*)&planes[c0][0];
+    const float2 qb0 = *(const float2*)&planes[c0][4];
+    const uint32_t placed0 = (uint32_t)__builtin_amdgcn_readlane((int)placedL, (int)c0);
+    if (todo == 0u)
+        return wave_ballot(pk_child_exact<false>(qa0.x, qa0.y, qa0.z, qa0.w, qb0.x, qb0.y, ax, ay, az, ox, oy, oz, tcull)) != 0ull ? placed0 : 0u;
+    const uint32_t c1 = (uint32_t)__builtin_ctz(todo);
+    todo &= todo - 1u;
+    const float4 qa1 = *(const float4*)&planes[c1][0];
+    const float2 qb1 = *(const float2*)&planes[c1][4];
+    const uint32_t placed1 = (uint32_t)__builtin_amdgcn_readlane((int)placedL, (int)c1);
+    const bool in0 = wave_ballot(pk_child_exact<false>(qa0.x, qa0.y, qa0.z, qa0.w, qb0.x, qb0.y, ax, ay, az, ox, oy, oz, tcull)) != 0ull;
+    const bool in1 = wave_ballot(pk_child_exact<false>(qa1.x, qa1.y, qa1.z, qa1.w, qb1.x, qb1.y, ax, ay, az, ox, oy, oz, tcull)) != 0ull;
+    hitmask = (in0 ? placed0 : 0u) | (in1 ? placed1 : 0u);
+    }
     while (todo != 0u) {
         const uint32_t c = (uint32_t)__builtin_ctz(todo);
         todo &= todo - 1u;

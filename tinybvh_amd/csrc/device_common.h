@@ -30,31 +30,31 @@ __device__ __forceinline__ float as_f32(uint32_t u) { return __uint_as_float(u);
 // bit-identical to the oracle, and to BVH::Intersect as built by oracle/Makefile.
 struct TriHit { float t, u, v; };
 
-__device__ __forceinline__ float3 crossA(float3 a, float3 b) {  // first product fused
+__host__ __device__ __forceinline__ float3 crossA(float3 a, float3 b) {  // first product fused
     float3 r;
     r.x = __builtin_fmaf(a.y, b.z, -(a.z * b.y));
     r.y = __builtin_fmaf(a.z, b.x, -(a.x * b.z));
     r.z = __builtin_fmaf(a.x, b.y, -(a.y * b.x));
     return r;
 }
-__device__ __forceinline__ float3 crossB(float3 a, float3 b) {  // second product fused
+__host__ __device__ __forceinline__ float3 crossB(float3 a, float3 b) {  // second product fused
     float3 r;
     r.x = __builtin_fmaf(-a.z, b.y, a.y * b.z);
     r.y = __builtin_fmaf(-a.x, b.z, a.z * b.x);
     r.z = __builtin_fmaf(-a.y, b.x, a.x * b.y);
     return r;
 }
-__device__ __forceinline__ float dot_zxy(float3 a, float3 b) {
+__host__ __device__ __forceinline__ float dot_zxy(float3 a, float3 b) {
     return __builtin_fmaf(a.z, b.z, __builtin_fmaf(a.x, b.x, a.y * b.y));
 }
-__device__ __forceinline__ float dot_zyx(float3 a, float3 b) {
+__host__ __device__ __forceinline__ float dot_zyx(float3 a, float3 b) {
     return __builtin_fmaf(a.z, b.z, __builtin_fmaf(a.y, b.y, a.x * b.x));
 }
 
 // Opacity micromaps (BVHBase::SetOpacityMicroMaps, tiny_bvh.h:823-826): n x n bits per triangle; a hit whose
 // barycentrics fall on a clear bit is no hit (IntersectTri / TriOccludes, tiny_bvh.h:8514-8522, 8562-8570).
 struct Omm { const uint32_t* map; uint32_t n; };   // map == nullptr: none
-__device__ __forceinline__ bool omm_opaque(Omm om, uint32_t prim, float u, float v) {
+__host__ __device__ __forceinline__ bool omm_opaque(Omm om, uint32_t prim, float u, float v) {
     const float fN = (float)om.n;
     const int row = (int)((u + v) * fN), diag = (int)((1 - u) * fN);
     const int idx = (row * row) + (int)(v * fN) + (diag - ((int)om.n - 1 - row));
@@ -65,7 +65,7 @@ __device__ __forceinline__ bool omm_opaque(Omm om, uint32_t prim, float u, float
 // Returns true when the triangle {v0, e1, e2} is hit within [0, tmax] (both ends
 // inclusive, like the reference: rejects only t < 0 || t > tmax) and, with opacity
 // micromaps set, the hit point is opaque.
-__device__ __forceinline__ bool tri_test(float3 O, float3 D, float3 v0, float3 e1, float3 e2,
+__host__ __device__ __forceinline__ bool tri_test(float3 O, float3 D, float3 v0, float3 e1, float3 e2,
                                          float tmax, TriHit& h, Omm om = Omm{nullptr, 0u}, uint32_t prim = 0u) {
     const float3 hh = crossA(D, e2);
     const float a = dot_zxy(e1, hh);
@@ -81,6 +81,31 @@ __device__ __forceinline__ bool tri_test(float3 O, float3 D, float3 v0, float3 e
     if (om.map && !omm_opaque(om, prim, u, v)) return false;
     h.t = t; h.u = u; h.v = v;
     return true;
+}
+
+// The same test without a branch, for the wave-packet kernel (kernels_cwbvh_packet.hip): there all 64 lanes hold a ray and every triangle is tested by all of
+// them, so the early-outs above skip no vector instruction once a single lane passes, and each costs the wave an exec save / restore and a branch on the
+// scalar unit (53 scalar instructions and 6 branches per triangle with them: profiles/packet_scalar.txt).  a, f, u, v, t are computed unconditionally with
+// the helpers and in the order of tri_test; the predicate is made of the same comparisons with the same negations, so a NaN or an infinity in a lane (f = inf
+// behind an edge-on triangle, a NaN vertex) is rejected or accepted exactly as above, and t, u, v of an accepted hit are the same bits
+// (tests/test_tri_flat_host.py runs both forms on the host).  h is written whether or not the test passes.
+__host__ __device__ __forceinline__ bool tri_test_flat(float3 O, float3 D, float3 v0, float3 e1, float3 e2,
+                                                       float tmax, TriHit& h, Omm om = Omm{nullptr, 0u}, uint32_t prim = 0u) {
+    const float3 hh = crossA(D, e2);
+    const float a = dot_zxy(e1, hh);
+    const float f = 1.0f / a;
+    const float3 s = make_float3(O.x - v0.x, O.y - v0.y, O.z - v0.z);
+    const float u = f * dot_zxy(s, hh);
+    const float3 q = crossB(s, e1);
+    const float v = f * dot_zyx(D, q);
+    const float t = f * dot_zxy(e2, q);
+    const bool edgeOn = __builtin_fabsf(a) < 0.000001f;
+    const bool outside = (u < 0) | (v < 0) | (u + v > 1);
+    const bool beyond = (t < 0) | (t > tmax);
+    bool ok = !edgeOn & !outside & !beyond;
+    if (om.map) ok = ok && omm_opaque(om, prim, u, v);
+    h.t = t; h.u = u; h.v = v;
+    return ok;
 }
 
 // Put right after the three loads of a triangle record: all three go out together.  Left alone the compiler sinks the third (v0, first needed behind
