@@ -148,6 +148,16 @@ int tbvh_debug_device_allocations(uint64_t out[2]);
  * scratch, bounds, staged transforms and descriptor tables), at allocation size.  out[0] + ... + out[6] == tbvh_scene_device_bytes( scene ), always. */
 int tbvh_debug_scene_bytes(const tbvh_scene* scene, uint64_t out[8]);
 
+/* The core the device LBVH builders share (tinybvh_amd/csrc/lbvh.h), run on the host; no device, no context (tests/test_lbvh_host.py).
+ * topology: the Karras range search over n sorted keys (key_bits 32: the low words are the keys; 64), for the interior nodes i = 0 .. n - 2:
+ * out4[4 i ..] = {left, right, lo, hi}, the children in Karras ids (interior node g -> g, leaf g -> n - 1 + g) and the node's sorted range.  2 <= n < 2^31.
+ * ordered: the order-preserving encoding of the centre bounds: bits 32: encoded[i] = the code of (float)values[i] and decoded[i] its decoding; 64: of values[i].
+ * build_scratch_bytes: the scratch allocation of the six device builders for n primitives, given hipcub's temporary sizes: out = {LBVH, PLOC, fp32 TLAS,
+ * fp64 TLAS, SAH, SBVH}. */
+int tbvh_debug_lbvh_topology(const uint64_t* keys, uint64_t n, int key_bits, uint32_t* out4);
+int tbvh_debug_lbvh_ordered(const double* values, uint64_t n, int bits, uint64_t* encoded, double* decoded);
+int tbvh_debug_build_scratch_bytes(uint32_t n, uint64_t sort_temp_bytes, uint64_t scan_temp_bytes, uint64_t out[6]);
+
 /* The device address of one of a scene graph's arrays (what: the TBVH_GRAPH_* codes of tbvh_scenegraph_download; TBVH_GRAPH_COMBINED: the last walk's), so that a
  * test can overwrite a table or a key state on the device and see the kernels' own range checks answer (tests/test_scenegraph_gpu.py).  Not for products: the
  * arrays are the graph's private state. */

@@ -1,8 +1,9 @@
 """Shared pieces of the tests of BVH_Double scenes that move (test_double_anim_host.py, test_double_anim_gpu.py): the device TLAS builder
-restated in numpy (63-bit Morton keys, stable sort, Karras topology, the library's node numbering), a validity check of such a tree, the
+restated in numpy (lbvh_ref.py: 63-bit Morton keys, stable sort, Karras topology; here the fp64 node records), a validity check of such a tree, the
 bottom-up recomputation of a BLAS's boxes, and the scene / ray batch the query tests share."""
 import numpy as np
 
+import lbvh_ref
 import tinybvh_amd as tb
 from double_lib import instance_scene, random_rays_dbl
 
@@ -32,94 +33,21 @@ def bounds_of(blas_verts) -> np.ndarray:
     return np.stack([np.concatenate([v.min(0), v.max(0)]) for v in blas_verts])
 
 
-def _spread21(v: np.ndarray) -> np.ndarray:
-    v = v.astype(np.uint64) & np.uint64(0x1fffff)
-    for shift, mask in ((32, 0x001f00000000ffff), (16, 0x001f0000ff0000ff), (8, 0x100f00f00f00f00f), (4, 0x10c30c30c30c30c3), (2, 0x1249249249249249)):
-        v = (v | (v << np.uint64(shift))) & np.uint64(mask)
-    return v
-
-
 def morton63(lo: np.ndarray, hi: np.ndarray) -> np.ndarray:
     """21 bits per axis of the box centres relative to the centre bounds, in double (kernels_double_anim.hip: k_morton_dbl)."""
-    c = 0.5 * lo + 0.5 * hi
-    cl, ch = c.min(0), c.max(0)
-    ext = ch - cl
-    with np.errstate(divide="ignore", invalid="ignore"):
-        u = np.where(ext > 0, (c - cl) / ext, 0.0)
-    u = np.where(u > 0, np.where(u < 1, u, 1.0), 0.0)
-    q = np.minimum((u * 2097151.0).astype(np.uint64), np.uint64(2097151))
-    return (_spread21(q[:, 0]) << np.uint64(2)) | (_spread21(q[:, 1]) << np.uint64(1)) | _spread21(q[:, 2])
-
-
-def _clz64(x: int) -> int:
-    return 64 - int(x).bit_length()
+    return lbvh_ref.morton63(0.5 * lo + 0.5 * hi)
 
 
 def karras_tlas(inst: np.ndarray):
     """(nodes, idx) over the instance boxes exactly as the device builds them: root 0, the children of Karras interior node i at 1 + 2 i and
     2 + 2 i, one instance per leaf, every interior box the union of its children's."""
-    n = inst.shape[0]
     lo, hi = inst["aabbMin"], inst["aabbMax"]
-    nodes = np.zeros(2 * n - 1, tb.NODE_DBL_DTYPE)
-    keys = morton63(lo, hi)
-    order = np.argsort(keys, kind="stable")
-    k = [int(x) for x in keys[order]]
-    idx = order.astype(np.uint64)
-
-    def leaf(slot, j):
-        nodes[slot]["aabbMin"], nodes[slot]["aabbMax"], nodes[slot]["leftFirst"], nodes[slot]["triCount"] = lo[order[j]], hi[order[j]], j, 1
-
-    if n == 1:
-        leaf(0, 0)
-        return nodes, idx
-
-    def delta(i, j):
-        if j < 0 or j >= n:
-            return -1
-        return 64 + (32 - (i ^ j).bit_length()) if k[i] == k[j] else _clz64(k[i] ^ k[j])
-
-    slot_of = {0: 0}          # Karras interior node -> slot
-    children = {}
-    for i in range(n - 1):
-        d = 1 if delta(i, i + 1) - delta(i, i - 1) >= 0 else -1
-        dmin = delta(i, i - d)
-        lmax = 2
-        while delta(i, i + lmax * d) > dmin:
-            lmax <<= 1
-        l, t = 0, lmax >> 1
-        while t >= 1:
-            if delta(i, i + (l + t) * d) > dmin:
-                l += t
-            t >>= 1
-        j = i + l * d
-        dnode = delta(i, j)
-        s, t = 0, (l + 1) >> 1
-        while True:
-            if delta(i, i + (s + t) * d) > dnode:
-                s += t
-            if t <= 1:
-                break
-            t = (t + 1) >> 1
-        gamma = i + s * d + min(d, 0)
-        a, b = min(i, j), max(i, j)
-        children[i] = (("leaf", gamma) if a == gamma else ("node", gamma), ("leaf", gamma + 1) if b == gamma + 1 else ("node", gamma + 1))
-    # slots top-down, boxes bottom-up
-    order_nodes, stack = [], [0]
-    while stack:
-        i = stack.pop()
-        order_nodes.append(i)
-        for c, (kind, g) in enumerate(children[i]):
-            if kind == "leaf":
-                leaf(1 + 2 * i + c, g)
-            else:
-                slot_of[g] = 1 + 2 * i + c
-                stack.append(g)
-    for i in reversed(order_nodes):
-        s, c = slot_of[i], 1 + 2 * i
-        nodes[s]["aabbMin"] = np.minimum(nodes[c]["aabbMin"], nodes[c + 1]["aabbMin"])
-        nodes[s]["aabbMax"] = np.maximum(nodes[c]["aabbMax"], nodes[c + 1]["aabbMax"])
-        nodes[s]["leftFirst"], nodes[s]["triCount"] = c, 0
-    return nodes, idx
+    tree, box, order = lbvh_ref.build(morton63(lo, hi), 64, "pairs", lo, hi)
+    nodes = np.zeros(2 * inst.shape[0] - 1, tb.NODE_DBL_DTYPE)
+    for slot, is_leaf, a, _ in tree:
+        nodes[slot]["aabbMin"], nodes[slot]["aabbMax"] = box[slot]
+        nodes[slot]["leftFirst"], nodes[slot]["triCount"] = a, 1 if is_leaf else 0
+    return nodes, order.astype(np.uint64)
 
 
 def check_tlas_tree(nodes: np.ndarray, idx: np.ndarray, inst: np.ndarray):

@@ -155,6 +155,9 @@ SYMBOLS = {
     "tbvh_debug_get_sah_thresholds": (_i, [_vp, C.POINTER(_u32)]),
     "tbvh_tlas_set_builder": (_i, [_vp, _i]),
     "tbvh_debug_device_allocations": (_i, [C.POINTER(_u64)]),
+    "tbvh_debug_lbvh_topology": (_i, [_vp, _u64, _i, _vp]),
+    "tbvh_debug_lbvh_ordered": (_i, [_vp, _u64, _i, _vp, _vp]),
+    "tbvh_debug_build_scratch_bytes": (_i, [_u32, _u64, _u64, _vp]),
     "tbvh_cwbvh_set_hybrid": (_i, [_vp, C.c_int64]),
     "tbvh_bin_rays_device": (_i, [_vp, _vp, _vp, _u64, C.POINTER(C.c_float), _u32, _u32, _vp]),
     "tbvh_generate_primary_device": (_i, [_vp, C.POINTER(Camera), _vp, _u64, _u64]),

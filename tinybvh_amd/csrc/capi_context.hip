@@ -2,6 +2,9 @@
 #include "capi_internal.h"
 #include "packet_cull.h"
 #include "device_common.h"
+#include "lbvh.h"
+#include "sahbuild.h"
+#include "sbvhbuild.h"
 
 using namespace tbvh;
 using namespace tbvh_capi;
@@ -182,6 +185,35 @@ void tbvh_shutdown(tbvh_context* c) {
 int tbvh_debug_device_allocations(uint64_t out[2]) {
     if (!out) return fail(TBVH_E_INVALID, "tbvh_debug_device_allocations: null argument");
     out[0] = g_devBufLive.load(); out[1] = g_devBufBytes.load();
+    return 0;
+}
+
+int tbvh_debug_lbvh_topology(const uint64_t* keys, uint64_t n, int keyBits, uint32_t* out4) {
+    if (!keys || !out4 || n < 2 || n > 0x7fffffffull || (keyBits != 32 && keyBits != 64))
+        return fail(TBVH_E_INVALID, "tbvh_debug_lbvh_topology: null argument, n = %llu (2 .. 2^31 - 1) or key_bits = %d (32 or 64)", (unsigned long long)n, keyBits);
+    std::vector<uint32_t> k32;
+    if (keyBits == 32) k32.assign(keys, keys + n);   // (the low words)
+    for (int i = 0; i < (int)n - 1; i++) {
+        const lbvh::KarrasNode k = keyBits == 32 ? lbvh::karras_node(k32.data(), (int)n, i) : lbvh::karras_node(keys, (int)n, i);
+        out4[4 * (size_t)i] = k.left; out4[4 * (size_t)i + 1] = k.right; out4[4 * (size_t)i + 2] = k.lo; out4[4 * (size_t)i + 3] = k.hi;
+    }
+    return 0;
+}
+
+int tbvh_debug_lbvh_ordered(const double* values, uint64_t n, int bits, uint64_t* encoded, double* decoded) {
+    if ((n && (!values || !encoded || !decoded)) || (bits != 32 && bits != 64)) return fail(TBVH_E_INVALID, "tbvh_debug_lbvh_ordered: null argument or bits = %d (32 or 64)", bits);
+    for (uint64_t i = 0; i < n; i++) {
+        if (bits == 32) { const uint32_t e = lbvh::ordered_encode((float)values[i]); encoded[i] = e; decoded[i] = lbvh::ordered_decode(e); }
+        else { encoded[i] = lbvh::ordered_encode(values[i]); decoded[i] = lbvh::ordered_decode(encoded[i]); }
+    }
+    return 0;
+}
+
+int tbvh_debug_build_scratch_bytes(uint32_t n, uint64_t sortTemp, uint64_t scanTemp, uint64_t out[6]) {
+    if (!out) return fail(TBVH_E_INVALID, "tbvh_debug_build_scratch_bytes: null argument");
+    out[0] = lbvh_scratch_total(n, sortTemp); out[1] = ploc_scratch_total(n, sortTemp, scanTemp);
+    out[2] = tlas_build_scratch_total(n, sortTemp); out[3] = tlas_dbl_build_scratch_total(n, sortTemp);
+    out[4] = sah_scratch_total(n, sortTemp, scanTemp); out[5] = sbvh_scratch_total(n, scanTemp);
     return 0;
 }
 

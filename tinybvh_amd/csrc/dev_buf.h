@@ -1,6 +1,7 @@
 // dev_buf.h — DevBuf<T>: the one owner of device memory behind the C ABI (capi_*.hip).  A move-only handle on ONE hipMalloc allocation of
 // count() elements of T (DevBuf<void>: of bytes), released by reset() or the destructor.  It reports hipError_t and never sets the library's
 // error text: every call site decides the code and the message.  No allocator policy, no pooling, no copy helpers.
+// ScratchCarver: how the device builders (kernels_*build.hip) divide one such allocation into their arrays.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -57,6 +58,24 @@ public:
 private:
     T* p_ = nullptr;
     size_t n_ = 0;
+};
+
+// One scratch allocation divided into parts, in the order they are taken, every part 256-byte aligned.  A null base only measures: the parts
+// come back null and total() is the size to allocate.
+class ScratchCarver {
+public:
+    explicit ScratchCarver(void* base) : base_(static_cast<char*>(base)) {}
+    void* take_bytes(size_t bytes) {
+        void* p = base_ ? base_ + off_ : nullptr;
+        off_ += (bytes + 255) & ~(size_t)255;
+        return p;
+    }
+    template <class T> T* take(size_t count) { return static_cast<T*>(take_bytes(count * sizeof(T))); }
+    size_t total() const { return off_; }
+
+private:
+    char* base_;
+    size_t off_ = 0;
 };
 
 }  // namespace tbvh_capi

@@ -1,5 +1,6 @@
 // kernels.h — host-visible launchers of the device kernels (defined in kernels_*.hip).
 #pragma once
+#include <cstdio>
 #include <vector>
 #include "device_common.h"
 #include "mesh_source.h"
@@ -118,6 +119,21 @@ void launch_custom(bool anyhit, const float4* nodes, const float4* recs, const Q
 // BLAS, 0 when they mix with BVH_GPU / BVH4_GPU / BVH8_CWBVH BLASes (BlasDesc::layout per BLAS: nodes = Wald nodes, tris = sphere records)
 void launch_tlas_custom(bool anyhit, int blasLayout, const float4* tlasNodes, const uint32_t* tlasIdx, const float4* instances,
                         const BlasDesc* blas, const QueryArgs& q, uint32_t* status, uint32_t blocks, hipStream_t s);
+
+// ---- what the LBVH builders' launchers share (the kernels' shared core is lbvh.h) ----
+// the centre bounds before a build: three minima at the ordered encoding's largest value, three maxima at its smallest; wordBytes: 4 (float) or 8
+inline hipError_t reset_centre_bounds(void* bounds, size_t wordBytes, hipStream_t s) {
+    const hipError_t e = hipMemsetAsync(bounds, 0xff, 3 * wordBytes, s);
+    return e != hipSuccess ? e : hipMemsetAsync((char*)bounds + 3 * wordBytes, 0x00, 3 * wordBytes, s);
+}
+// after a launch of a rebuild `who`: names the step that failed and returns its error (the caller declares hipError_t e)
+#define TBVH_STEP(who, what) do { if ((e = hipGetLastError()) != hipSuccess) { fprintf(stderr, "[tinybvh_amd] %s: %s: %s\n", who, what, hipGetErrorString(e)); return e; } } while (0)
+// the size of each builder's scratch allocation given hipcub's temporary sizes: no device needed (the *_scratch_bytes below ask hipcub first);
+// sah_scratch_total and sbvh_scratch_total are in sahbuild.h and sbvhbuild.h
+size_t lbvh_scratch_total(uint32_t n, size_t sortTempBytes);
+size_t ploc_scratch_total(uint32_t n, size_t sortTempBytes, size_t scanTempBytes);
+size_t tlas_build_scratch_total(uint32_t n, size_t sortTempBytes);
+size_t tlas_dbl_build_scratch_total(uint32_t n, size_t sortTempBytes);
 
 // device TLAS rebuild (kernels_tlasbuild.hip)
 size_t tlas_build_scratch_bytes(uint32_t n, size_t* sortTempBytes);

@@ -3,7 +3,8 @@
 //
 // For content that changes topology every frame, or scenes whose host build (BVH::Build,
 // tiny_bvh.h:2124-2461: seconds for Bistro) is the bottleneck: 63-bit Morton codes of the triangle
-// centroids, radix sort, Karras 2012 topology, bottom-up boxes.  The result is written directly in the
+// centroids, radix sort, Karras 2012 topology (keys, prefix lengths and the range search: lbvh.h, shared with the
+// TLAS builders), bottom-up boxes.  The result is written directly in the
 // layout BVH::Build produces — 32-byte nodes {aabbMin, leftFirst, aabbMax, triCount}, root at 0, node 1
 // unused, the two children of a node adjacent (tiny_bvh.h:1050-1062) — plus a primIdx array, so it feeds
 // tbvh_convert_bvh2_device (kernels_convert.hip) and every other BVH2 consumer unchanged:
@@ -17,33 +18,18 @@
 #include <hipcub/hipcub.hpp>
 
 #include "cwbvh_encode.h"
+#include "dev_buf.h"
 #include "device_common.h"
 #include "kernels.h"
+#include "lbvh.h"
 #include "sah_split.h"
 
 namespace tbvh {
 
 namespace {
 
-__device__ __forceinline__ uint32_t enc_f32(float f) {   // order-preserving float -> uint
-    const uint32_t b = as_u32(f);
-    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
-__device__ __forceinline__ float dec_f32(uint32_t e) { return as_f32((e & 0x80000000u) ? (e & 0x7fffffffu) : ~e); }
-
-__device__ __forceinline__ unsigned long long spread21(uint32_t v) {   // 21 bits -> every third bit of 63
-    unsigned long long x = v & 0x1fffffull;
-    x = (x | x << 32) & 0x1f00000000ffffull;
-    x = (x | x << 16) & 0x1f0000ff0000ffull;
-    x = (x | x << 8) & 0x100f00f00f00f00full;
-    x = (x | x << 4) & 0x10c30c30c30c30c3ull;
-    x = (x | x << 2) & 0x1249249249249249ull;
-    return x;
-}
-
-// per-triangle box + centroid bounds of the scene.  Grid-stride over the triangles, wave reduction, then ONE set of six
-// atomics per wave at the very end: the six words share a cache line, and same-line atomics are serialised memory-side
-// (~12 ns each): one set per 64 triangles cost 3 ms for Bistro, one per wave of a 2048-block grid costs nothing.
+// per-triangle box + centroid bounds of the scene.  Grid-stride over the triangles, then ONE set of six atomics per wave at the very end
+// (lbvh.h: wave_centre_bounds): one set per wave of a 2048-block grid costs nothing.
 // (GENERAL: mesh_source.h; a triangle whose vertex index is out of range gets a box at the origin here — the conversion's leaf writer, which fetches
 // the same triangle, reports it and the build fails)
 template <bool GENERAL>
@@ -59,18 +45,12 @@ __global__ void k_tri_boxes(const MeshSrc verts, uint32_t n, float4* __restrict_
         const float3 c = make_float3(0.5f * (mn.x + mx.x), 0.5f * (mn.y + mx.y), 0.5f * (mn.z + mx.z));
         cmn = min3(cmn, c); cmx = max3(cmx, c);
     }
-    for (int o = 32; o > 0; o >>= 1) {
-        cmn = min3(cmn, make_float3(__shfl_xor(cmn.x, o), __shfl_xor(cmn.y, o), __shfl_xor(cmn.z, o)));
-        cmx = max3(cmx, make_float3(__shfl_xor(cmx.x, o), __shfl_xor(cmx.y, o), __shfl_xor(cmx.z, o)));
-    }
-    if ((threadIdx.x & 63u) == 0 && cmn.x <= cmx.x) {
-        atomicMin(centreBounds + 0, enc_f32(cmn.x)); atomicMin(centreBounds + 1, enc_f32(cmn.y)); atomicMin(centreBounds + 2, enc_f32(cmn.z));
-        atomicMax(centreBounds + 3, enc_f32(cmx.x)); atomicMax(centreBounds + 4, enc_f32(cmx.y)); atomicMax(centreBounds + 5, enc_f32(cmx.z));
-    }
+    float lo[3] = {cmn.x, cmn.y, cmn.z}, hi[3] = {cmx.x, cmx.y, cmx.z};
+    lbvh::wave_centre_bounds(lo, hi, centreBounds);
 }
 
 // the second box source: custom-geometry spheres {x, y, z, r} (capi_custom.hip).  A sphere's box is the demos' sphereAABB, pos - r and pos + r (one
-// float operation per component); loop, wave reduction and the one set of atomics per wave are k_tri_boxes'.  Nothing after this kernel knows
+// float operation per component); the loop and the one set of atomics per wave are k_tri_boxes'.  Nothing after this kernel knows
 // where the boxes came from.  (r <= 0 and non-finite values are not refused: an inverted or NaN box only moves its Morton key.)
 __global__ void k_sphere_boxes(const float4* __restrict__ spheres, uint32_t n, float4* __restrict__ triMin, float4* __restrict__ triMax,
                                uint32_t* __restrict__ centreBounds) {
@@ -85,14 +65,8 @@ __global__ void k_sphere_boxes(const float4* __restrict__ spheres, uint32_t n, f
         const float3 c = make_float3(0.5f * (mn.x + mx.x), 0.5f * (mn.y + mx.y), 0.5f * (mn.z + mx.z));
         cmn = min3(cmn, c); cmx = max3(cmx, c);
     }
-    for (int o = 32; o > 0; o >>= 1) {
-        cmn = min3(cmn, make_float3(__shfl_xor(cmn.x, o), __shfl_xor(cmn.y, o), __shfl_xor(cmn.z, o)));
-        cmx = max3(cmx, make_float3(__shfl_xor(cmx.x, o), __shfl_xor(cmx.y, o), __shfl_xor(cmx.z, o)));
-    }
-    if ((threadIdx.x & 63u) == 0 && cmn.x <= cmx.x) {
-        atomicMin(centreBounds + 0, enc_f32(cmn.x)); atomicMin(centreBounds + 1, enc_f32(cmn.y)); atomicMin(centreBounds + 2, enc_f32(cmn.z));
-        atomicMax(centreBounds + 3, enc_f32(cmx.x)); atomicMax(centreBounds + 4, enc_f32(cmx.y)); atomicMax(centreBounds + 5, enc_f32(cmx.z));
-    }
+    float lo[3] = {cmn.x, cmn.y, cmn.z}, hi[3] = {cmx.x, cmx.y, cmx.z};
+    lbvh::wave_centre_bounds(lo, hi, centreBounds);
 }
 
 __global__ void k_tri_morton(const float4* __restrict__ triMin, const float4* __restrict__ triMax, const uint32_t* __restrict__ centreBounds,
@@ -102,60 +76,23 @@ __global__ void k_tri_morton(const float4* __restrict__ triMin, const float4* __
     const float4 a = triMin[i], b = triMax[i];
     const float c[3] = {0.5f * (a.x + b.x), 0.5f * (a.y + b.y), 0.5f * (a.z + b.z)};
     uint32_t q[3];
-    for (int k = 0; k < 3; k++) {
-        const float lo = dec_f32(centreBounds[k]), hi = dec_f32(centreBounds[3 + k]);
-        const float ext = hi - lo;
-        float u = ext > 0 ? (c[k] - lo) / ext : 0.f;
-        u = u < 0 ? 0.f : (u > 1 ? 1.f : u);
-        const uint32_t v = (uint32_t)(u * 2097151.0f);
-        q[k] = v > 2097151u ? 2097151u : v;
-    }
+    for (int k = 0; k < 3; k++) q[k] = lbvh::morton_axis(c[k], lbvh::ordered_decode(centreBounds[k]), lbvh::ordered_decode(centreBounds[3 + k]), 2097151u);
     // 63-bit codes (21 bits per axis): with 30-bit codes a 2.8 M-triangle scene puts dozens of triangles into one
     // cell, and everything below that is split by array position instead of by space
-    keys[i] = (spread21(q[0]) << 2) | (spread21(q[1]) << 1) | spread21(q[2]);
+    keys[i] = lbvh::morton63(q);
     vals[i] = i;
 }
 
-__device__ __forceinline__ int delta(const unsigned long long* __restrict__ keys, int n, int i, int j) {
-    if (j < 0 || j >= n) return -1;
-    const unsigned long long a = keys[i], b = keys[j];
-    return a == b ? 64 + __clz((uint32_t)(i ^ j)) : __clzll(a ^ b);
-}
-
-// Karras 2012.  Per interior node i: its two children (leaf k is numbered n - 1 + k), its sorted range.
+// Karras 2012 (lbvh.h).  Per interior node i: its two children (leaf k is numbered n - 1 + k), its sorted range.
 // parent[c] = i, bit 31 set for the right child.
 __global__ void k_topology(const unsigned long long* __restrict__ keys, uint32_t n, uint32_t* __restrict__ parent, uint2* __restrict__ children, uint2* __restrict__ range) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    const int N = (int)n;
-    if (i >= N - 1) return;
-    const int d = delta(keys, N, i, i + 1) - delta(keys, N, i, i - 1) >= 0 ? 1 : -1;
-    const int dmin = delta(keys, N, i, i - d);
-    int lmax = 2;
-    while (delta(keys, N, i, i + lmax * d) > dmin) lmax <<= 1;
-    int l = 0;
-    for (int t = lmax >> 1; t >= 1; t >>= 1)
-        if (delta(keys, N, i, i + (l + t) * d) > dmin) l += t;
-    const int j = i + l * d;
-    const int dnode = delta(keys, N, i, j);
-    int s = 0;
-    for (int t = (l + 1) >> 1;; t = (t + 1) >> 1) {
-        if (delta(keys, N, i, i + (s + t) * d) > dnode) s += t;
-        if (t <= 1) break;
-    }
-    const int gamma = i + s * d + (d < 0 ? d : 0);
-    const int lo = i < j ? i : j, hi = i < j ? j : i;
-    const uint32_t left = lo == gamma ? (uint32_t)(N - 1 + gamma) : (uint32_t)gamma;
-    const uint32_t right = hi == gamma + 1 ? (uint32_t)(N - 1 + gamma + 1) : (uint32_t)(gamma + 1);
-    children[i] = make_uint2(left, right);
-    range[i] = make_uint2((uint32_t)lo, (uint32_t)(hi - lo + 1));
-    parent[left] = (uint32_t)i;
-    parent[right] = (uint32_t)i | 0x80000000u;
-}
-
-__device__ __forceinline__ float3 ld_agent3(const float4* p) {   // written by another CU during this kernel: bypass the non-coherent L1
-    const float* f = (const float*)p;
-    return make_float3(__hip_atomic_load(f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT), __hip_atomic_load(f + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT),
-                       __hip_atomic_load(f + 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+    if (i >= (int)n - 1) return;
+    const lbvh::KarrasNode k = lbvh::karras_node(keys, (int)n, i);
+    children[i] = make_uint2(k.left, k.right);
+    range[i] = make_uint2(k.lo, k.hi - k.lo + 1);
+    parent[k.left] = (uint32_t)i;
+    parent[k.right] = (uint32_t)i | 0x80000000u;
 }
 
 // position of a node in the output array: the root at 0, the children of Karras node p at 2 + 2p and 3 + 2p
@@ -319,17 +256,17 @@ struct PlocScratch {
     size_t total;
 };
 PlocScratch carve_ploc(void* base, uint32_t n, size_t sortTempBytes, size_t scanTempBytes) {
-    char* p = (char*)base;
-    auto take = [&](size_t bytes) { char* r = p; p += (bytes + 255) & ~(size_t)255; return r; };
+    tbvh_capi::ScratchCarver c(base);
+    const size_t N = n;
     PlocScratch s;
-    s.triMin = (float4*)take((size_t)n * 16); s.triMax = (float4*)take((size_t)n * 16);
-    s.clA = (float4*)take((size_t)n * 32); s.clB = (float4*)take((size_t)n * 32);
-    s.keysA = (unsigned long long*)take((size_t)n * 8); s.keysB = (unsigned long long*)take((size_t)n * 8);
-    s.flags = (unsigned long long*)take((size_t)n * 8); s.scan = (unsigned long long*)take((size_t)n * 8);
-    s.valsA = (uint32_t*)take((size_t)n * 4); s.nn = (uint32_t*)take((size_t)n * 4);
-    s.bounds = (uint32_t*)take(64); s.counters = (uint32_t*)take(64);
-    s.sortTemp = take(sortTempBytes); s.scanTemp = take(scanTempBytes);
-    s.total = (size_t)(p - (char*)base);
+    s.triMin = c.take<float4>(N); s.triMax = c.take<float4>(N);
+    s.clA = c.take<float4>(2 * N); s.clB = c.take<float4>(2 * N);
+    s.keysA = c.take<unsigned long long>(N); s.keysB = c.take<unsigned long long>(N);
+    s.flags = c.take<unsigned long long>(N); s.scan = c.take<unsigned long long>(N);
+    s.valsA = c.take<uint32_t>(N); s.nn = c.take<uint32_t>(N);
+    s.bounds = c.take<uint32_t>(16); s.counters = c.take<uint32_t>(16);
+    s.sortTemp = c.take_bytes(sortTempBytes); s.scanTemp = c.take_bytes(scanTempBytes);
+    s.total = c.total();
     return s;
 }
 
@@ -342,19 +279,19 @@ struct Scratch {
     size_t total;
 };
 Scratch carve(void* base, uint32_t n, size_t sortTempBytes) {
-    char* p = (char*)base;
-    auto take = [&](size_t bytes) { char* r = p; p += (bytes + 255) & ~(size_t)255; return r; };
+    tbvh_capi::ScratchCarver c(base);
+    const size_t N = n;
     Scratch s;
-    s.triMin = (float4*)take((size_t)n * 16); s.triMax = (float4*)take((size_t)n * 16);
-    s.boxMin = (float4*)take((size_t)n * 32); s.boxMax = (float4*)take((size_t)n * 32);   // 2n - 1 Karras nodes
-    s.keysA = (unsigned long long*)take((size_t)n * 8); s.keysB = (unsigned long long*)take((size_t)n * 8);
-    s.valsA = (uint32_t*)take((size_t)n * 4);
-    s.parent = (uint32_t*)take((size_t)n * 8);
-    s.children = (uint2*)take((size_t)n * 8); s.range = (uint2*)take((size_t)n * 8);
-    s.flags = (uint32_t*)take((size_t)n * 4);
-    s.bounds = (uint32_t*)take(64);
-    s.sortTemp = take(sortTempBytes);
-    s.total = (size_t)(p - (char*)base);
+    s.triMin = c.take<float4>(N); s.triMax = c.take<float4>(N);
+    s.boxMin = c.take<float4>(2 * N); s.boxMax = c.take<float4>(2 * N);   // 2n - 1 Karras nodes
+    s.keysA = c.take<unsigned long long>(N); s.keysB = c.take<unsigned long long>(N);
+    s.valsA = c.take<uint32_t>(N);
+    s.parent = c.take<uint32_t>(2 * N);
+    s.children = c.take<uint2>(N); s.range = c.take<uint2>(N);
+    s.flags = c.take<uint32_t>(N);
+    s.bounds = c.take<uint32_t>(16);
+    s.sortTemp = c.take_bytes(sortTempBytes);
+    s.total = c.total();
     return s;
 }
 
@@ -372,8 +309,9 @@ size_t lbvh_scratch_bytes(uint32_t n, size_t* sortTempBytes) {
     size_t tmp = 0;
     hipcub::DeviceRadixSort::SortPairs(nullptr, tmp, (const unsigned long long*)nullptr, (unsigned long long*)nullptr, (const uint32_t*)nullptr, (uint32_t*)nullptr, (int)n, 0, 63);
     *sortTempBytes = tmp;
-    return carve(nullptr, n, tmp).total;
+    return lbvh_scratch_total(n, tmp);
 }
+size_t lbvh_scratch_total(uint32_t n, size_t sortTempBytes) { return carve(nullptr, n, sortTempBytes).total; }
 
 // verts: 3 float4 per triangle (device).  Out: nodes32 (2n BVHNode records; [1] unused), primIdx (n entries = the
 // triangles in Morton order).  maxLeaf: 1..3 triangles per leaf.  spheres (device, {x, y, z, r} x n): the primitives are these spheres, `verts` is
@@ -382,8 +320,7 @@ hipError_t launch_lbvh_build(const MeshSrc& verts, uint32_t n, uint32_t maxLeaf,
                              hipStream_t s, const float4* spheres) {
     const Scratch sc = carve(scratch, n, sortTempBytes);
     hipError_t e;
-    if ((e = hipMemsetAsync(sc.bounds, 0xff, 12, s)) != hipSuccess) return e;
-    if ((e = hipMemsetAsync(sc.bounds + 3, 0x00, 12, s)) != hipSuccess) return e;
+    if ((e = reset_centre_bounds(sc.bounds, 4, s)) != hipSuccess) return e;
     if ((e = hipMemsetAsync(sc.flags, 0, (size_t)n * 4, s)) != hipSuccess) return e;
     if ((e = hipMemsetAsync(nodes32, 0, 64, s)) != hipSuccess) return e;   // root + the unused node 1
     const uint32_t bs = 256, nb = (n + bs - 1) / bs;
@@ -410,8 +347,9 @@ size_t ploc_scratch_bytes(uint32_t n, size_t* sortTempBytes, size_t* scanTempByt
     hipcub::DeviceRadixSort::SortPairs(nullptr, tmp, (const unsigned long long*)nullptr, (unsigned long long*)nullptr, (const uint32_t*)nullptr, (uint32_t*)nullptr, (int)n, 0, 63);
     hipcub::DeviceScan::ExclusiveSum(nullptr, tmp2, (const unsigned long long*)nullptr, (unsigned long long*)nullptr, (int)n);
     *sortTempBytes = tmp; *scanTempBytes = tmp2;
-    return carve_ploc(nullptr, n, tmp, tmp2).total;
+    return ploc_scratch_total(n, tmp, tmp2);
 }
+size_t ploc_scratch_total(uint32_t n, size_t sortTempBytes, size_t scanTempBytes) { return carve_ploc(nullptr, n, sortTempBytes, scanTempBytes).total; }
 
 // PLOC build (see above).  Out as launch_lbvh_build: nodes32 (2n BVHNode records, [1] unused), primIdx (the triangles in Morton order); one
 // triangle per leaf.  radius: search window to each side (8, 16 or 32).  steps (optional): number of clustering steps taken.  spheres: as for
@@ -420,8 +358,7 @@ hipError_t launch_ploc_build(const MeshSrc& verts, uint32_t n, uint32_t radius, 
                              size_t scanTempBytes, hipStream_t s, uint32_t* steps, const float4* spheres) {
     const PlocScratch sc = carve_ploc(scratch, n, sortTempBytes, scanTempBytes);
     hipError_t e;
-    if ((e = hipMemsetAsync(sc.bounds, 0xff, 12, s)) != hipSuccess) return e;
-    if ((e = hipMemsetAsync(sc.bounds + 3, 0x00, 12, s)) != hipSuccess) return e;
+    if ((e = reset_centre_bounds(sc.bounds, 4, s)) != hipSuccess) return e;
     const uint32_t bs = 256, nb = (n + bs - 1) / bs;
     launch_prim_boxes(verts, spheres, n, sc.triMin, sc.triMax, sc.bounds, s);
     hipLaunchKernelGGL(k_tri_morton, dim3(nb), dim3(bs), 0, s, sc.triMin, sc.triMax, sc.bounds, n, sc.keysA, sc.valsA);

@@ -4,7 +4,8 @@
 // (tiny_bvh_anim_double.cpp:110: "just move build to Tick if instance transforms are not static"): BLASInstanceEx::Update for every
 // instance (tiny_bvh.h:8432-8472: invert the transform, world box of the 8 transformed BLAS-box corners) and
 // BVH_Double::Build( BLASInstanceEx*, ... ) (tiny_bvh.h:7955-...).  The instance records keep the reference's 320-byte format and the
-// result is a BVH_Double node array + instance index list, exactly what k_double traverses.  Five steps, as kernels_tlasbuild.hip:
+// result is a BVH_Double node array + instance index list, exactly what k_double traverses.  Five steps; the encoding of the bounds, the keys,
+// the prefix lengths and the Karras range search are lbvh.h's, shared with the fp32 builders:
 //   1. instance update, one thread per instance: the expressions of capi_double.hip: updateInstanceDbl, operation for operation (the
 //      Makefile's -ffp-contract=off keeps them uncontracted), so device-updated and host-updated records are bit-identical.  The BLAS box
 //      is node 0 of the BLAS (tiny_bvh.h:8133: aabbMin / aabbMax = bvhNode[0]'s), read through the BlasDbl descriptors: no bounds argument.
@@ -30,8 +31,10 @@
 
 #include <cstdio>
 
+#include "dev_buf.h"
 #include "device_common.h"
 #include "kernels.h"
+#include "lbvh.h"
 
 namespace tbvh {
 
@@ -39,15 +42,6 @@ namespace {
 
 constexpr double kDblFar = 1e300;   // BVH_DBL_FAR, tiny_bvh.h:145
 constexpr uint32_t kNoParent = 0xffffffffu;
-
-__device__ __forceinline__ uint64_t enc_f64(double d) {   // order-preserving double -> uint64
-    const uint64_t b = (uint64_t)__double_as_longlong(d);
-    return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
-}
-__device__ __forceinline__ double dec_f64(uint64_t e) {
-    const uint64_t b = (e >> 63) ? (e & 0x7fffffffffffffffull) : ~e;
-    return __longlong_as_double((long long)b);
-}
 
 __device__ __forceinline__ double ld_agent(const double* p) {   // bypass this CU's (non-coherent) L1: a sibling on another CU wrote it
     return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -66,7 +60,7 @@ __device__ __forceinline__ void write_union(NodeDbl* __restrict__ nodes, uint64_
 
 // ---- 1. BLASInstanceEx::Update + InvertTransform (tiny_bvh.h:8432-8472), one thread per instance ----------------------------------
 __global__ void k_instance_update_dbl(InstanceDbl* __restrict__ instances, const double* __restrict__ transforms, const BlasDbl* __restrict__ blas,
-                                      uint32_t n, uint64_t nBlas, unsigned long long* __restrict__ centreBounds) {
+                                      uint32_t n, uint64_t nBlas, uint64_t* __restrict__ centreBounds) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     double cLo[3] = {kDblFar, kDblFar, kDblFar}, cHi[3] = {-kDblFar, -kDblFar, -kDblFar};   // this lane's centre, reduced over the wave below
     if (i < n) {
@@ -121,77 +115,33 @@ __global__ void k_instance_update_dbl(InstanceDbl* __restrict__ instances, const
             if (c > -kDblFar && c < kDblFar) cLo[a] = cHi[a] = c;   // (a NaN or infinite box — w == 0 — takes no part in the bounds; its key is 0)
         }
     }
-    // one set of six atomics per wave: the six words share a cache line and same-line atomics are serialised memory-side
-    for (int a = 0; a < 3; a++)
-        for (int o = 32; o > 0; o >>= 1) { cLo[a] = fmin(cLo[a], __shfl_xor(cLo[a], o)); cHi[a] = fmax(cHi[a], __shfl_xor(cHi[a], o)); }
-    if ((threadIdx.x & 63u) == 0)
-        for (int a = 0; a < 3; a++)
-            if (cLo[a] <= cHi[a]) { atomicMin(centreBounds + a, (unsigned long long)enc_f64(cLo[a])); atomicMax(centreBounds + 3 + a, (unsigned long long)enc_f64(cHi[a])); }
+    lbvh::wave_centre_bounds(cLo, cHi, centreBounds);   // one set of six atomics per wave, an axis without a finite centre left out
 }
 
 // ---- 2. Morton keys ---------------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ uint64_t spread21(uint64_t v) {   // 21 bits -> every third bit
-    v &= 0x1fffffull;
-    v = (v | (v << 32)) & 0x001f00000000ffffull;
-    v = (v | (v << 16)) & 0x001f0000ff0000ffull;
-    v = (v | (v << 8)) & 0x100f00f00f00f00full;
-    v = (v | (v << 4)) & 0x10c30c30c30c30c3ull;
-    v = (v | (v << 2)) & 0x1249249249249249ull;
-    return v;
-}
-
-__global__ void k_morton_dbl(const InstanceDbl* __restrict__ instances, const unsigned long long* __restrict__ centreBounds, uint32_t n,
+__global__ void k_morton_dbl(const InstanceDbl* __restrict__ instances, const uint64_t* __restrict__ centreBounds, uint32_t n,
                              uint64_t* __restrict__ keys, uint32_t* __restrict__ vals) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const InstanceDbl& in = instances[i];
-    uint64_t q[3];
+    uint32_t q[3];
     for (int a = 0; a < 3; a++) {
         const double c = 0.5 * in.aabbMin[a] + 0.5 * in.aabbMax[a];
-        const double lo = dec_f64(centreBounds[a]), hi = dec_f64(centreBounds[3 + a]);
-        const double ext = hi - lo;
-        double u = ext > 0 ? (c - lo) / ext : 0.;
-        u = u > 0 ? (u < 1 ? u : 1.) : 0.;   // (NaN -> 0)
-        const uint64_t v = (uint64_t)(u * 2097151.0);
-        q[a] = v > 2097151ull ? 2097151ull : v;
+        q[a] = lbvh::morton_axis(c, lbvh::ordered_decode(centreBounds[a]), lbvh::ordered_decode(centreBounds[3 + a]), 2097151u);   // (a NaN centre: cell 0)
     }
-    keys[i] = (spread21(q[0]) << 2) | (spread21(q[1]) << 1) | spread21(q[2]);
+    keys[i] = lbvh::morton63(q);
     vals[i] = i;
 }
 
 // ---- 4. Karras 2012 topology ---------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ int delta64(const uint64_t* __restrict__ keys, int n, int i, int j) {
-    if (j < 0 || j >= n) return -1;
-    const uint64_t a = keys[i], b = keys[j];
-    return a == b ? 64 + __clz((uint32_t)(i ^ j)) : __clzll((long long)(a ^ b));
-}
-
 // Karras ids: interior node i -> i, leaf k -> (n - 1) + k.  parent[id] = the Karras interior node above id, slot[id] = where id goes in the
 // BVH_Double node array: the root at 0, the children of interior node i at 1 + 2 i and 2 + 2 i.
 __global__ void k_lbvh_topology_dbl(const uint64_t* __restrict__ keys, uint32_t n, uint32_t* __restrict__ parent, uint32_t* __restrict__ slot) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    const int N = (int)n;
-    if (i >= N - 1) return;
-    const int d = delta64(keys, N, i, i + 1) - delta64(keys, N, i, i - 1) >= 0 ? 1 : -1;
-    const int dmin = delta64(keys, N, i, i - d);
-    int lmax = 2;
-    while (delta64(keys, N, i, i + lmax * d) > dmin) lmax <<= 1;
-    int l = 0;
-    for (int t = lmax >> 1; t >= 1; t >>= 1)
-        if (delta64(keys, N, i, i + (l + t) * d) > dmin) l += t;
-    const int j = i + l * d;
-    const int dnode = delta64(keys, N, i, j);
-    int s = 0;
-    for (int t = (l + 1) >> 1;; t = (t + 1) >> 1) {
-        if (delta64(keys, N, i, i + (s + t) * d) > dnode) s += t;
-        if (t <= 1) break;
-    }
-    const int gamma = i + s * d + (d < 0 ? d : 0);
-    const int lo = i < j ? i : j, hi = i < j ? j : i;
-    const uint32_t left = lo == gamma ? (uint32_t)(N - 1 + gamma) : (uint32_t)gamma;
-    const uint32_t right = hi == gamma + 1 ? (uint32_t)(N - 1 + gamma + 1) : (uint32_t)(gamma + 1);
-    parent[left] = (uint32_t)i; slot[left] = 1u + 2u * (uint32_t)i;
-    parent[right] = (uint32_t)i; slot[right] = 2u + 2u * (uint32_t)i;
+    if (i >= (int)n - 1) return;
+    const lbvh::KarrasNode k = lbvh::karras_node(keys, (int)n, i);
+    parent[k.left] = (uint32_t)i; slot[k.left] = 1u + 2u * (uint32_t)i;
+    parent[k.right] = (uint32_t)i; slot[k.right] = 2u + 2u * (uint32_t)i;
     if (i == 0) slot[0] = 0u;
 }
 
@@ -295,24 +245,24 @@ __global__ void k_refit_dbl(NodeDbl* __restrict__ nodes, uint32_t nNodes, TriDbl
 struct Scratch {
     uint64_t *keysA, *keysB;
     uint32_t *valsA, *valsB, *parent, *slot, *flags;
-    unsigned long long* bounds;
+    uint64_t* bounds;
     double* xforms;
     void* sortTemp;
     size_t total;
 };
 // one allocation, carved up here (every part 256-byte aligned); base may be null to just measure
 Scratch carve(void* base, uint32_t n, size_t sortTempBytes) {
-    char* p = (char*)base;
-    auto take = [&](size_t bytes) { char* r = p; p += (bytes + 255) & ~(size_t)255; return r; };
+    tbvh_capi::ScratchCarver c(base);
+    const size_t N = n;
     Scratch s;
-    s.keysA = (uint64_t*)take((size_t)n * 8); s.keysB = (uint64_t*)take((size_t)n * 8);
-    s.valsA = (uint32_t*)take((size_t)n * 4); s.valsB = (uint32_t*)take((size_t)n * 4);
-    s.parent = (uint32_t*)take((size_t)n * 8); s.slot = (uint32_t*)take((size_t)n * 8);   // 2n - 1 Karras ids
-    s.flags = (uint32_t*)take((size_t)n * 4);
-    s.bounds = (unsigned long long*)take(64);
-    s.xforms = (double*)take((size_t)n * 128);   // staged host transforms
-    s.sortTemp = take(sortTempBytes);
-    s.total = (size_t)(p - (char*)base);
+    s.keysA = c.take<uint64_t>(N); s.keysB = c.take<uint64_t>(N);
+    s.valsA = c.take<uint32_t>(N); s.valsB = c.take<uint32_t>(N);
+    s.parent = c.take<uint32_t>(2 * N); s.slot = c.take<uint32_t>(2 * N);   // 2n - 1 Karras ids
+    s.flags = c.take<uint32_t>(N);
+    s.bounds = c.take<uint64_t>(8);
+    s.xforms = c.take<double>(16 * N);   // staged host transforms
+    s.sortTemp = c.take_bytes(sortTempBytes);
+    s.total = c.total();
     return s;
 }
 
@@ -322,8 +272,9 @@ size_t tlas_dbl_build_scratch_bytes(uint32_t n, size_t* sortTempBytes) {
     size_t tmp = 0;
     hipcub::DeviceRadixSort::SortPairs(nullptr, tmp, (const uint64_t*)nullptr, (uint64_t*)nullptr, (const uint32_t*)nullptr, (uint32_t*)nullptr, (int)n, 0, 64);
     *sortTempBytes = tmp;
-    return carve(nullptr, n, tmp).total;
+    return tlas_dbl_build_scratch_total(n, tmp);
 }
+size_t tlas_dbl_build_scratch_total(uint32_t n, size_t sortTempBytes) { return carve(nullptr, n, sortTempBytes).total; }
 
 double* tlas_dbl_xform_stage(void* scratch, uint32_t n, size_t sortTempBytes) { return carve(scratch, n, sortTempBytes).xforms; }
 
@@ -331,25 +282,22 @@ hipError_t launch_tlas_dbl_rebuild(NodeDbl* tlasNodes, uint64_t* tlasIdx, Instan
                                    uint32_t n, void* scratch, size_t sortTempBytes, hipStream_t s) {
     const Scratch sc = carve(scratch, n, sortTempBytes);
     hipError_t e;
-    if ((e = hipMemsetAsync(sc.bounds, 0xff, 24, s)) != hipSuccess) return e;       // centre minima: +max in the ordered encoding
-    if ((e = hipMemsetAsync(sc.bounds + 3, 0x00, 24, s)) != hipSuccess) return e;    // centre maxima
+    if ((e = reset_centre_bounds(sc.bounds, 8, s)) != hipSuccess) return e;
     if ((e = hipMemsetAsync(sc.flags, 0, (size_t)n * 4, s)) != hipSuccess) return e;
     const uint32_t bs = 128, nb = (n + bs - 1) / bs;
-#define TBVH_STEP(what) do { if ((e = hipGetLastError()) != hipSuccess) { fprintf(stderr, "[tinybvh_amd] TLAS_Double rebuild: %s: %s\n", what, hipGetErrorString(e)); return e; } } while (0)
     hipLaunchKernelGGL(k_instance_update_dbl, dim3(nb), dim3(bs), 0, s, instances, transformsDev, blas, n, nBlas, sc.bounds);
-    TBVH_STEP("instance update");
+    TBVH_STEP("TLAS_Double rebuild", "instance update");
     hipLaunchKernelGGL(k_morton_dbl, dim3(nb), dim3(bs), 0, s, instances, sc.bounds, n, sc.keysA, sc.valsA);
-    TBVH_STEP("morton keys");
+    TBVH_STEP("TLAS_Double rebuild", "morton keys");
     size_t tmp = sortTempBytes;
     if ((e = hipcub::DeviceRadixSort::SortPairs(sc.sortTemp, tmp, sc.keysA, sc.keysB, sc.valsA, sc.valsB, (int)n, 0, 64, s)) != hipSuccess) {
         fprintf(stderr, "[tinybvh_amd] TLAS_Double rebuild: radix sort (%zu temp bytes): %s\n", sortTempBytes, hipGetErrorString(e));
         return e;
     }
     if (n > 1) hipLaunchKernelGGL(k_lbvh_topology_dbl, dim3(nb), dim3(bs), 0, s, sc.keysB, n, sc.parent, sc.slot);
-    TBVH_STEP("topology");
+    TBVH_STEP("TLAS_Double rebuild", "topology");
     hipLaunchKernelGGL(k_lbvh_nodes_dbl, dim3(nb), dim3(bs), 0, s, sc.valsB, instances, sc.parent, sc.slot, sc.flags, n, tlasNodes, tlasIdx);
-    TBVH_STEP("nodes");
-#undef TBVH_STEP
+    TBVH_STEP("TLAS_Double rebuild", "nodes");
     return hipGetLastError();
 }
 

@@ -25,6 +25,7 @@
 #include <vector>
 
 #include "dev_buf.h"
+#include "dev_buf.h"
 #include "sah_split.h"
 #include "sahbuild.h"
 
@@ -51,20 +52,18 @@ struct SahScratch {
     uint32_t* groupBins;          // k_sah_one_group's global bins, n x 672 bytes, for inputs it may build (n <= kSahOneGroupMax), else null
 };
 
-size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
-
 SahScratch carve(void* base, uint32_t n, size_t sortTempBytes, size_t scanTempBytes, size_t* total) {
+    tbvh_capi::ScratchCarver c(base);
+    const size_t N = n;
     SahScratch s;
-    size_t off = 0;
-    auto take = [&](size_t bytes) { void* p = base ? (char*)base + off : nullptr; off += align256(bytes); return p; };
-    s.fmin = (float4*)take((size_t)n * 16); s.fmax = (float4*)take((size_t)n * 16);
-    s.idxB = (uint32_t*)take((size_t)n * 4); s.posA = (uint32_t*)take((size_t)n * 4); s.posB = (uint32_t*)take((size_t)n * 4);
-    s.tbox = (float4*)take((size_t)n * 2 * 32); s.taux = (uint4*)take((size_t)n * 2 * 16); s.cursor = (uint2*)take((size_t)n * 2 * 8);
-    s.ctr = (uint32_t*)take(kCtrWords * 4);
-    s.keysA = (unsigned long long*)take((size_t)n * 8); s.keysB = (unsigned long long*)take((size_t)n * 8);
-    s.sortTemp = take(sortTempBytes); s.scanTemp = take(scanTempBytes);
-    s.groupBins = n <= kSahOneGroupMax ? (uint32_t*)take((size_t)n * sah::kNodeBinWords * 4) : nullptr;
-    if (total) *total = off;
+    s.fmin = c.take<float4>(N); s.fmax = c.take<float4>(N);
+    s.idxB = c.take<uint32_t>(N); s.posA = c.take<uint32_t>(N); s.posB = c.take<uint32_t>(N);
+    s.tbox = c.take<float4>(4 * N); s.taux = c.take<uint4>(2 * N); s.cursor = c.take<uint2>(2 * N);   // 2 n temporary nodes
+    s.ctr = c.take<uint32_t>(kCtrWords);
+    s.keysA = c.take<unsigned long long>(N); s.keysB = c.take<unsigned long long>(N);
+    s.sortTemp = c.take_bytes(sortTempBytes); s.scanTemp = c.take_bytes(scanTempBytes);
+    s.groupBins = n <= kSahOneGroupMax ? c.take<uint32_t>(N * sah::kNodeBinWords) : nullptr;
+    if (total) *total = c.total();
     return s;
 }
 
@@ -680,11 +679,15 @@ inline uint32_t blocksFor(uint64_t n, uint32_t per) { return (uint32_t)((n + per
 }  // namespace
 
 size_t sah_scratch_bytes(uint32_t n, size_t* sortTempBytes, size_t* scanTempBytes) {
-    size_t sortTemp = 0, scanTemp = 0, total = 0;
+    size_t sortTemp = 0, scanTemp = 0;
     hipcub::DeviceRadixSort::SortKeys(nullptr, sortTemp, (const unsigned long long*)nullptr, (unsigned long long*)nullptr, (int)n, 0, 64);
     hipcub::DeviceScan::ExclusiveSum(nullptr, scanTemp, (const uint32_t*)nullptr, (uint32_t*)nullptr, (int)(2 * n));
     *sortTempBytes = sortTemp; *scanTempBytes = scanTemp;
-    carve(nullptr, n, sortTemp, scanTemp, &total);
+    return sah_scratch_total(n, sortTemp, scanTemp);
+}
+size_t sah_scratch_total(uint32_t n, size_t sortTempBytes, size_t scanTempBytes) {
+    size_t total = 0;
+    carve(nullptr, n, sortTempBytes, scanTempBytes, &total);
     return total;
 }
 

@@ -29,6 +29,7 @@
 
 #include <vector>
 
+#include "dev_buf.h"
 #include "sbvhbuild.h"
 
 namespace tbvh {
@@ -64,22 +65,19 @@ struct SbvhScratch {
     void* scanTemp;
 };
 
-size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
-
 SbvhScratch carve(void* base, uint32_t n, size_t scanTempBytes, size_t* total) {
+    tbvh_capi::ScratchCarver c(base);
     SbvhScratch s;
-    size_t off = 0;
-    auto take = [&](size_t bytes) { void* p = base ? (char*)base + off : nullptr; off += align256(bytes); return p; };
     const size_t cap = (size_t)n + n / 2, capNodes = (size_t)n * 3 + 2;
-    s.frag = (Frag*)take(cap * sizeof(Frag));
-    s.idx = (uint32_t*)take(cap * 4); s.tmp = (uint32_t*)take(cap * 4);
-    s.cls = (uint8_t*)take(cap); s.cut = (float*)take(cap * 4);
-    s.tbox = (float4*)take(capNodes * 32); s.slice = (uint2*)take(capNodes * 8); s.aux = (uint4*)take(capNodes * 16); s.refs = (uint2*)take(capNodes * 8);
-    s.dec = (NodeDec*)take((cap + 2) * sizeof(NodeDec));
-    s.ctr = (uint32_t*)take(kCtrWords * 4);
-    s.extra = (uint32_t*)take(capNodes * 4); s.offset = (uint32_t*)take(capNodes * 4);
-    s.scanTemp = take(scanTempBytes);
-    if (total) *total = off;
+    s.frag = c.take<Frag>(cap);
+    s.idx = c.take<uint32_t>(cap); s.tmp = c.take<uint32_t>(cap);
+    s.cls = c.take<uint8_t>(cap); s.cut = c.take<float>(cap);
+    s.tbox = c.take<float4>(2 * capNodes); s.slice = c.take<uint2>(capNodes); s.aux = c.take<uint4>(capNodes); s.refs = c.take<uint2>(capNodes);
+    s.dec = c.take<NodeDec>(cap + 2);
+    s.ctr = c.take<uint32_t>(kCtrWords);
+    s.extra = c.take<uint32_t>(capNodes); s.offset = c.take<uint32_t>(capNodes);
+    s.scanTemp = c.take_bytes(scanTempBytes);
+    if (total) *total = c.total();
     return s;
 }
 
@@ -537,10 +535,14 @@ inline uint32_t blocksFor(uint64_t n, uint32_t per) { return (uint32_t)((n + per
 }  // namespace
 
 size_t sbvh_scratch_bytes(uint32_t n, size_t* scanTempBytes) {
-    size_t scanTemp = 0, total = 0;
+    size_t scanTemp = 0;
     hipcub::DeviceScan::ExclusiveSum(nullptr, scanTemp, (const uint32_t*)nullptr, (uint32_t*)nullptr, (int)(3 * (size_t)n + 2));
     *scanTempBytes = scanTemp;
-    carve(nullptr, n, scanTemp, &total);
+    return sbvh_scratch_total(n, scanTemp);
+}
+size_t sbvh_scratch_total(uint32_t n, size_t scanTempBytes) {
+    size_t total = 0;
+    carve(nullptr, n, scanTempBytes, &total);
     return total;
 }
 

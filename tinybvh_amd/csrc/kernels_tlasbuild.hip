@@ -8,7 +8,8 @@
 // BVH_GPU (Aila-Laine) node array + instance index list, exactly what k_tlas traverses.
 //
 // The tree is an LBVH (30-bit Morton codes of the instance-box centres, radix sort, Karras 2012
-// topology in one pass, bottom-up boxes with one atomic flag per interior node) instead of the
+// topology in one pass — keys, prefix lengths and the range search are lbvh.h's, shared with the
+// triangle and fp64 builders — bottom-up boxes with one atomic flag per interior node) instead of the
 // reference's binned-SAH build: a different but valid TLAS — hit records do not depend on the TLAS
 // shape (up to exact-distance ties), which tests/test_tlas_device_build.py checks against the
 // oracle.  One leaf per instance, like the reference (TLAS leaves hold exactly one instance after
@@ -18,21 +19,14 @@
 
 #include <cstdio>
 
+#include "dev_buf.h"
 #include "device_common.h"
 #include "kernels.h"
+#include "lbvh.h"
 
 namespace tbvh {
 
 namespace {
-
-__device__ __forceinline__ uint32_t enc_f32(float f) {   // order-preserving float -> uint
-    const uint32_t b = as_u32(f);
-    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
-__device__ __forceinline__ float dec_f32(uint32_t e) {
-    const uint32_t b = (e & 0x80000000u) ? (e & 0x7fffffffu) : ~e;
-    return as_f32(b);
-}
 
 // BLASInstance::InvertTransform (tiny_bvh.h:8402-8427): the float cofactor formula, evaluated operation for operation
 // like the reference build — the same table and order as host_builder.cpp: invert4x4, where the order was found by
@@ -113,20 +107,7 @@ __global__ void k_instance_update(float4* __restrict__ instances, const float* _
     instMax[i] = make_float4(mx[0], mx[1], mx[2], 0.f);
     for (int a = 0; a < 3; a++) cLo[a] = cHi[a] = 0.5f * (mn[a] + mx[a]);
     }
-    // one set of six atomics per wave: the six words share a cache line and same-line atomics are serialised memory-side
-    // (~12 ns each); one set per instance made them 70 of the 80 us of a 1000-instance rebuild
-    for (int a = 0; a < 3; a++)
-        for (int o = 32; o > 0; o >>= 1) { cLo[a] = fminf(cLo[a], __shfl_xor(cLo[a], o)); cHi[a] = fmaxf(cHi[a], __shfl_xor(cHi[a], o)); }
-    if ((threadIdx.x & 63u) == 0 && cLo[0] <= cHi[0])
-        for (int a = 0; a < 3; a++) { atomicMin(centreBounds + a, enc_f32(cLo[a])); atomicMax(centreBounds + 3 + a, enc_f32(cHi[a])); }
-}
-
-__device__ __forceinline__ uint32_t spread10(uint32_t v) {   // 10 bits -> every third bit
-    v = (v * 0x00010001u) & 0xFF0000FFu;
-    v = (v * 0x00000101u) & 0x0F00F00Fu;
-    v = (v * 0x00000011u) & 0xC30C30C3u;
-    v = (v * 0x00000005u) & 0x49249249u;
-    return v;
+    lbvh::wave_centre_bounds(cLo, cHi, centreBounds);   // one set of six atomics per wave
 }
 
 __global__ void k_morton(const float4* __restrict__ instMin, const float4* __restrict__ instMax, const uint32_t* __restrict__ centreBounds,
@@ -136,59 +117,19 @@ __global__ void k_morton(const float4* __restrict__ instMin, const float4* __res
     const float4 a = instMin[i], b = instMax[i];
     const float c[3] = {0.5f * (a.x + b.x), 0.5f * (a.y + b.y), 0.5f * (a.z + b.z)};
     uint32_t q[3];
-    for (int k = 0; k < 3; k++) {
-        const float lo = dec_f32(centreBounds[k]), hi = dec_f32(centreBounds[3 + k]);
-        const float ext = hi - lo;
-        float u = ext > 0 ? (c[k] - lo) / ext : 0.f;
-        u = u < 0 ? 0.f : (u > 1 ? 1.f : u);
-        const uint32_t v = (uint32_t)(u * 1023.0f);
-        q[k] = v > 1023u ? 1023u : v;
-    }
-    keys[i] = (spread10(q[0]) << 2) | (spread10(q[1]) << 1) | spread10(q[2]);
+    for (int k = 0; k < 3; k++) q[k] = lbvh::morton_axis(c[k], lbvh::ordered_decode(centreBounds[k]), lbvh::ordered_decode(centreBounds[3 + k]), 1023u);
+    keys[i] = lbvh::morton30(q);
     vals[i] = i;
 }
 
-// Karras 2012, "Maximizing parallelism in the construction of BVHs, octrees and k-d trees":
-// interior node i covers a range of the sorted keys found by binary search on common-prefix
-// lengths; equal keys are told apart by their position.
-__device__ __forceinline__ int delta(const uint32_t* __restrict__ keys, int n, int i, int j) {
-    if (j < 0 || j >= n) return -1;
-    const uint32_t a = keys[i], b = keys[j];
-    return a == b ? 32 + __clz((uint32_t)(i ^ j)) : __clz(a ^ b);
-}
-
-// Node numbering of the result: interior node i -> node i (root = 0), leaf k -> node (n - 1) + k.
+// Karras 2012 (lbvh.h).  Node numbering of the result: interior node i -> node i (root = 0), leaf k -> node (n - 1) + k.
 __global__ void k_lbvh_topology(const uint32_t* __restrict__ keys, uint32_t n, uint32_t* __restrict__ parent, uint2* __restrict__ children) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    const int N = (int)n;
-    if (i >= N - 1) return;
-    const int d = delta(keys, N, i, i + 1) - delta(keys, N, i, i - 1) >= 0 ? 1 : -1;
-    const int dmin = delta(keys, N, i, i - d);
-    int lmax = 2;
-    while (delta(keys, N, i, i + lmax * d) > dmin) lmax <<= 1;
-    int l = 0;
-    for (int t = lmax >> 1; t >= 1; t >>= 1)
-        if (delta(keys, N, i, i + (l + t) * d) > dmin) l += t;
-    const int j = i + l * d;
-    const int dnode = delta(keys, N, i, j);
-    int s = 0;
-    for (int t = (l + 1) >> 1;; t = (t + 1) >> 1) {
-        if (delta(keys, N, i, i + (s + t) * d) > dnode) s += t;
-        if (t <= 1) break;
-    }
-    const int gamma = i + s * d + (d < 0 ? d : 0);
-    const int lo = i < j ? i : j, hi = i < j ? j : i;
-    const uint32_t left = lo == gamma ? (uint32_t)(N - 1 + gamma) : (uint32_t)gamma;
-    const uint32_t right = hi == gamma + 1 ? (uint32_t)(N - 1 + gamma + 1) : (uint32_t)(gamma + 1);
-    children[i] = make_uint2(left, right);
-    parent[left] = (uint32_t)i;
-    parent[right] = (uint32_t)i;
-}
-
-__device__ __forceinline__ float4 ld_agent(const float4* p) {   // bypass this CU's (non-coherent) L1: a sibling on another CU wrote it
-    const float* f = (const float*)p;
-    return make_float4(__hip_atomic_load(f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT), __hip_atomic_load(f + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT),
-                       __hip_atomic_load(f + 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT), 0.f);
+    if (i >= (int)n - 1) return;
+    const lbvh::KarrasNode k = lbvh::karras_node(keys, (int)n, i);
+    children[i] = make_uint2(k.left, k.right);
+    parent[k.left] = (uint32_t)i;
+    parent[k.right] = (uint32_t)i;
 }
 
 // One thread per leaf: write the leaf node, then climb; the second thread to reach an interior
@@ -215,7 +156,7 @@ __global__ void k_lbvh_nodes(const uint32_t* __restrict__ sortedIdx, const float
         if (atomicAdd(flags + node, 1u) == 0u) return;   // first to arrive: the sibling subtree is not finished yet
         __threadfence();
         const uint2 ch = children[node];
-        const float4 lmn = ld_agent(boxMin + ch.x), lmx = ld_agent(boxMax + ch.x), rmn = ld_agent(boxMin + ch.y), rmx = ld_agent(boxMax + ch.y);
+        const float4 lmn = lbvh::ld_agent(boxMin + ch.x), lmx = lbvh::ld_agent(boxMax + ch.x), rmn = lbvh::ld_agent(boxMin + ch.y), rmx = lbvh::ld_agent(boxMax + ch.y);
         float4* o = nodes + (size_t)node * 4;
         o[0] = make_float4(lmn.x, lmn.y, lmn.z, as_f32(ch.x));
         o[1] = make_float4(lmx.x, lmx.y, lmx.z, as_f32(ch.y));
@@ -241,19 +182,19 @@ struct Scratch {
 };
 // one allocation, carved up here (every part 256-byte aligned); base may be null to just measure
 Scratch carve(void* base, uint32_t n, size_t sortTempBytes) {
-    char* p = (char*)base;
-    auto take = [&](size_t bytes) { char* r = p; p += (bytes + 255) & ~(size_t)255; return r; };
+    tbvh_capi::ScratchCarver c(base);
+    const size_t N = n;
     Scratch s;
-    s.instMin = (float4*)take((size_t)n * 16); s.instMax = (float4*)take((size_t)n * 16);
-    s.boxMin = (float4*)take((size_t)n * 32);  s.boxMax = (float4*)take((size_t)n * 32);   // 2n - 1 nodes
-    s.keysA = (uint32_t*)take((size_t)n * 4); s.keysB = (uint32_t*)take((size_t)n * 4);
-    s.valsA = (uint32_t*)take((size_t)n * 4); s.valsB = (uint32_t*)take((size_t)n * 4);
-    s.parent = (uint32_t*)take((size_t)n * 8);
-    s.children = (uint2*)take((size_t)n * 8);
-    s.flags = (uint32_t*)take((size_t)n * 4);
-    s.bounds = (uint32_t*)take(64);
-    s.sortTemp = take(sortTempBytes);
-    s.total = (size_t)(p - (char*)base);
+    s.instMin = c.take<float4>(N); s.instMax = c.take<float4>(N);
+    s.boxMin = c.take<float4>(2 * N); s.boxMax = c.take<float4>(2 * N);   // 2n - 1 nodes
+    s.keysA = c.take<uint32_t>(N); s.keysB = c.take<uint32_t>(N);
+    s.valsA = c.take<uint32_t>(N); s.valsB = c.take<uint32_t>(N);
+    s.parent = c.take<uint32_t>(2 * N);
+    s.children = c.take<uint2>(N);
+    s.flags = c.take<uint32_t>(N);
+    s.bounds = c.take<uint32_t>(16);
+    s.sortTemp = c.take_bytes(sortTempBytes);
+    s.total = c.total();
     return s;
 }
 }  // namespace
@@ -262,8 +203,9 @@ size_t tlas_build_scratch_bytes(uint32_t n, size_t* sortTempBytes) {
     size_t tmp = 0;
     hipcub::DeviceRadixSort::SortPairs(nullptr, tmp, (const uint32_t*)nullptr, (uint32_t*)nullptr, (const uint32_t*)nullptr, (uint32_t*)nullptr, (int)n, 0, 30);
     *sortTempBytes = tmp;
-    return carve(nullptr, n, tmp).total;
+    return tlas_build_scratch_total(n, tmp);
 }
+size_t tlas_build_scratch_total(uint32_t n, size_t sortTempBytes) { return carve(nullptr, n, sortTempBytes).total; }
 
 hipError_t launch_tlas_rebuild(float4* tlasNodes, uint32_t* tlasIdx, float4* instances, const float* transformsDev, const float* blasBoundsDev,
                                uint32_t n, uint32_t nBlas, void* scratch, size_t sortTempBytes, hipStream_t s) {
@@ -273,22 +215,19 @@ hipError_t launch_tlas_rebuild(float4* tlasNodes, uint32_t* tlasIdx, float4* ins
     uint2* children = sc.children;
     void* sortTemp = sc.sortTemp;
     hipError_t e;
-    if ((e = hipMemsetAsync(bounds, 0xff, 12, s)) != hipSuccess) return e;       // centre minima: +max in the ordered encoding
-    if ((e = hipMemsetAsync(bounds + 3, 0x00, 12, s)) != hipSuccess) return e;    // centre maxima
+    if ((e = reset_centre_bounds(bounds, 4, s)) != hipSuccess) return e;
     if ((e = hipMemsetAsync(flags, 0, (size_t)n * 4, s)) != hipSuccess) return e;
     const uint32_t bs = 128, nb = (n + bs - 1) / bs;
-#define TBVH_STEP(what) do { if ((e = hipGetLastError()) != hipSuccess) { fprintf(stderr, "[tinybvh_amd] TLAS rebuild: %s: %s\n", what, hipGetErrorString(e)); return e; } } while (0)
     hipLaunchKernelGGL(k_instance_update, dim3(nb), dim3(bs), 0, s, instances, transformsDev, blasBoundsDev, n, nBlas, instMin, instMax, bounds);
-    TBVH_STEP("instance update");
+    TBVH_STEP("TLAS rebuild", "instance update");
     hipLaunchKernelGGL(k_morton, dim3(nb), dim3(bs), 0, s, instMin, instMax, bounds, n, keysA, valsA);
-    TBVH_STEP("morton codes");
+    TBVH_STEP("TLAS rebuild", "morton codes");
     size_t tmp = sortTempBytes;
     if ((e = hipcub::DeviceRadixSort::SortPairs(sortTemp, tmp, keysA, keysB, valsA, valsB, (int)n, 0, 30, s)) != hipSuccess) { fprintf(stderr, "[tinybvh_amd] TLAS rebuild: radix sort (%zu temp bytes): %s\n", sortTempBytes, hipGetErrorString(e)); return e; }
     if (n > 1) hipLaunchKernelGGL(k_lbvh_topology, dim3(nb), dim3(bs), 0, s, keysB, n, parent, children);
-    TBVH_STEP("topology");
+    TBVH_STEP("TLAS rebuild", "topology");
     hipLaunchKernelGGL(k_lbvh_nodes, dim3(nb), dim3(bs), 0, s, valsB, instMin, instMax, parent, children, flags, boxMin, boxMax, n, tlasNodes, tlasIdx);
-    TBVH_STEP("nodes");
-#undef TBVH_STEP
+    TBVH_STEP("TLAS rebuild", "nodes");
     return hipGetLastError();
 }
 
@@ -297,8 +236,7 @@ hipError_t launch_tlas_instance_update(float4* instances, const float* transform
                                        size_t sortTempBytes, hipStream_t s) {
     const Scratch sc = carve(scratch, n, sortTempBytes);
     hipError_t e;
-    if ((e = hipMemsetAsync(sc.bounds, 0xff, 12, s)) != hipSuccess) return e;
-    if ((e = hipMemsetAsync(sc.bounds + 3, 0x00, 12, s)) != hipSuccess) return e;
+    if ((e = reset_centre_bounds(sc.bounds, 4, s)) != hipSuccess) return e;
     const uint32_t bs = 128, nb = (n + bs - 1) / bs;
     hipLaunchKernelGGL(k_instance_update, dim3(nb), dim3(bs), 0, s, instances, transformsDev, blasBoundsDev, n, nBlas, sc.instMin, sc.instMax, sc.bounds);
     return hipGetLastError();

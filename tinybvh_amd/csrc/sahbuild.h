@@ -59,6 +59,7 @@ struct SahSrc {
 // device memory of one build, carved out of one allocation of sah_scratch_bytes( n ) bytes; the bins of the widest level are a second, transient
 // allocation of run_sah_build's own (672 bytes per node of that level: kernels_sahbuild.hip)
 size_t sah_scratch_bytes(uint32_t n, size_t* sortTempBytes, size_t* scanTempBytes);
+size_t sah_scratch_total(uint32_t n, size_t sortTempBytes, size_t scanTempBytes);   // the same without asking hipcub: no device needed
 // Builds into nodes32 (2 n nodes of two float4) and primIdx (n) on stream s; synchronises once per level (one 64-byte read-back of the counters).  *nNodesOut:
 // the nodes written.  A bad vertex index of a device-resident index buffer raises kStatusMeshIndex in *status and is never dereferenced.
 // smallSubtree: subtrees of at most this many primitives are finished by one wave each instead of by the per-level kernels (0: none are; a value

@@ -38,6 +38,7 @@ namespace tbvh {
 
 // device memory of one build, carved out of one allocation of sbvh_scratch_bytes( n ) bytes
 size_t sbvh_scratch_bytes(uint32_t n, size_t* scanTempBytes);
+size_t sbvh_scratch_total(uint32_t n, size_t scanTempBytes);   // the same without asking hipcub: no device needed
 // Builds into nodes32 (room for 3 n nodes of two float4) and primIdx (room for n + n / 2) on stream s; synchronises once per level (one small
 // read-back of the counters).  *nNodesOut, *nIdxOut: the nodes and references written; *stats (may be null): what the twin counts.  A bad vertex
 // index of a device-resident index buffer raises kStatusMeshIndex in *status and is never dereferenced.
