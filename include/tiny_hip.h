@@ -206,6 +206,56 @@ public:
     // VoxelSet::Intersect( Ray& ) / IsOccluded( const Ray& ) over a host tinybvh::Ray[] (after UpdateTopGrid)
     void Intersect(tinybvh::Ray* rays, size_t n) { Check(tbvh_intersect(s, rays, n, sizeof(tinybvh::Ray)), "tbvh_intersect"); }
     void IsOccluded(const tinybvh::Ray* rays, size_t n, uint8_t* out) { Check(tbvh_occluded(s, rays, n, sizeof(tinybvh::Ray), out), "tbvh_occluded"); }
+    // ---- editing on the device (tinybvh_amd.h: "editing a voxel set"; DESIGN.md par. 21): the set changes where it lies, TLASes over it keep working.
+    // The host arrays above do not follow device edits until Arrays() reads them back.
+    void CreateOnDevice(uint64_t brickCapacity = 1024) {   // an empty set as the reference's constructor leaves it
+        if (s) { tbvh_free_scene(s); s = nullptr; }
+        Check(tbvh_voxelset_create(ctx, brickCapacity, &s), "tbvh_voxelset_create");
+    }
+    void Reserve(uint64_t nBricks) { Check(tbvh_voxelset_reserve(s, nBricks), "tbvh_voxelset_reserve"); }
+    // n records { x, y, z, v }: the result of Set( x, y, z, v ) on each in turn; onDevice: the records are in device memory (16-byte aligned)
+    void SetOnDevice(const uint32_t* xyzv, uint64_t n, bool onDevice = false) { Check(tbvh_voxelset_set(s, xyzv, n, onDevice ? 1 : 0), "tbvh_voxelset_set"); }
+    void UpdateTopGridOnDevice() { Check(tbvh_voxelset_update_top_grid(s), "tbvh_voxelset_update_top_grid"); }
+    // the device's arrays read back into this object's; returns the bricks in use (freeBrickPtr)
+    uint64_t Arrays(const uint32_t** gridOut = nullptr, const uint32_t** brickOut = nullptr, const uint32_t** topOut = nullptr) {
+        uint64_t used = 0;
+        Check(tbvh_voxelset_download(s, nullptr, nullptr, 0, nullptr, &used), "tbvh_voxelset_download");
+        brick.assign((size_t)used * 512, 0u);
+        Check(tbvh_voxelset_download(s, grid.data(), brick.data(), used, top.data(), nullptr), "tbvh_voxelset_download");
+        if (gridOut) *gridOut = grid.data();
+        if (brickOut) *brickOut = brick.data();
+        if (topOut) *topOut = top.data();
+        return used;
+    }
+    // VoxelSet::GetNormal( const Ray& ) for a host tinybvh::Ray[] that holds hits on this set: normals16 gets { nx, ny, nz, 0 } per ray, zeros for a miss
+    void Normals(const tinybvh::Ray* rays, size_t n, float* normals16) {
+        Check(tbvh_voxel_normals(ctx, s, rays, (uint32_t)sizeof(tinybvh::Ray), n, normals16), "tbvh_voxel_normals");
+    }
+    // the scene-to-voxels loop of tiny_bvh_foliage.cpp:222-258 on the device: every opaque hit of 3 x 256^2 axis rays through `traced` (a triangle BLAS or a
+    // TLAS over triangle BLASes of this context) becomes a Set here, then UpdateTopGrid.  shading: the table whose alpha skips a hit and whose albedo is the
+    // value, or nullptr (params.color).  VoxelizeBounds / VoxelizeMatrix: the demo's bounding cube (216-220) and its matrix T (256-262, row-major).
+    tbvh_voxelize_stats Voxelize(tbvh_scene* traced, const tbvh_voxelize_params& params, tbvh_shading* shading = nullptr) {
+        tbvh_voxelize_stats st{};
+        Check(tbvh_voxelize_device(traced, shading, &params, s, &st), "tbvh_voxelize_device");
+        return st;
+    }
+    static tbvh_voxelize_params VoxelizeBounds(const float bmin[3], const float bmax[3]) {
+        tbvh_voxelize_params p{};
+        float c[3];
+        for (int k = 0; k < 3; k++) { p.ext[k] = bmax[k] - bmin[k]; c[k] = (bmax[k] + bmin[k]) * 0.5f; }
+        p.maxSize = p.ext[1] > p.ext[0] ? p.ext[1] : p.ext[0];
+        if (p.ext[2] > p.maxSize) p.maxSize = p.ext[2];
+        const float half = 0.525f * p.maxSize;
+        for (int k = 0; k < 3; k++) p.bmin[k] = c[k] - half;
+        p.color = 0xFFFFFFu;
+        return p;
+    }
+    static void VoxelizeMatrix(const tbvh_voxelize_params& p, float T[16]) {
+        const float scale = 1.0f / p.maxSize;
+        for (int k = 0; k < 16; k++) T[k] = 0;
+        T[0] = T[5] = T[10] = scale; T[15] = 1;
+        T[3] = -p.bmin[0] * scale; T[7] = -p.bmin[1] * scale; T[11] = -p.bmin[2] * scale;
+    }
     tbvh_scene* Handle() const { return s; }
     tbvh_context* Ctx() const { return ctx; }
 private:

@@ -1453,6 +1453,129 @@ class VoxelSet(_Scene):
         self.arrays = (grid, bricks, top)
         return self
 
+    # ---- editing on the device (capi_voxel_edit.hip, DESIGN.md par. 21): the set is changed where it lies, TLASes over it keep working ----------
+    def CreateOnDevice(self, brick_capacity: int = 1024) -> "VoxelSet":
+        """An empty set on the device as the reference's constructor leaves it (tbvh_voxelset_create): grid zero, freeBrickPtr = 1, top grid zero."""
+        if self._h:
+            self.free()
+            self._h = C.c_void_p()
+        check(lib.tbvh_voxelset_create(self.ctx._h, int(brick_capacity), C.byref(self._h)), "tbvh_voxelset_create")
+        return self
+
+    def Reserve(self, n_bricks: int) -> "VoxelSet":
+        """Room for n_bricks bricks (brick 0 included) without another reallocation (tbvh_voxelset_reserve)."""
+        check(lib.tbvh_voxelset_reserve(self._h, int(n_bricks)), "tbvh_voxelset_reserve")
+        return self
+
+    def Capacity(self):
+        """(capacity, used) in bricks, brick 0 included (tbvh_voxelset_capacity)."""
+        cap, used = C.c_uint64(0), C.c_uint64(0)
+        check(lib.tbvh_voxelset_capacity(self._h, C.byref(cap), C.byref(used)), "tbvh_voxelset_capacity")
+        return int(cap.value), int(used.value)
+
+    def SetOnDevice(self, xyzv, n: int = None) -> "VoxelSet":
+        """VoxelSet::Set for a batch of records {x, y, z, v}, the result that of calling Set on them in turn (tbvh_voxelset_set): an (n, 4) uint32 host
+        array, or a device pointer (int) with n=.  The top grid follows at UpdateTopGridOnDevice, as in the reference."""
+        if isinstance(xyzv, int):
+            check(lib.tbvh_voxelset_set(self._h, C.c_void_p(xyzv), int(n), 1), "tbvh_voxelset_set")
+            return self
+        recs = np.ascontiguousarray(xyzv, np.uint32).reshape(-1, 4)
+        check(lib.tbvh_voxelset_set(self._h, _ptr(recs), recs.shape[0], 0), "tbvh_voxelset_set")
+        return self
+
+    def UpdateTopGridOnDevice(self) -> "VoxelSet":
+        """VoxelSet::UpdateTopGrid on the device (tbvh_voxelset_update_top_grid)."""
+        check(lib.tbvh_voxelset_update_top_grid(self._h), "tbvh_voxelset_update_top_grid")
+        return self
+
+    def Arrays(self):
+        """(grid, bricks[:used], top) as the device holds them now (tbvh_voxelset_download)."""
+        n = C.c_uint64(0)
+        check(lib.tbvh_voxelset_download(self._h, None, None, 0, None, C.byref(n)), "tbvh_voxelset_download")
+        grid = np.zeros(32768, np.uint32); bricks = np.zeros(n.value * 512, np.uint32); top = np.zeros(16, np.uint32)
+        check(lib.tbvh_voxelset_download(self._h, _ptr(grid), _ptr(bricks), n.value, _ptr(top), None), "tbvh_voxelset_download")
+        return grid, bricks, top
+
+    def Voxelize(self, scene, bmin, max_size, ext, shading=None, color: int = 0xFFFFFF, max_hits_per_ray: int = 4096) -> dict:
+        """The scene-to-voxels loop of tiny_bvh_foliage.cpp:222-258 on the device (tbvh_voxelize_device): 3 x 256^2 axis rays marched through `scene` (a
+        triangle BLAS or a TLAS over triangle BLASes), every opaque hit a Set on this set, then UpdateTopGrid.  bmin, max_size, ext: voxelize_bounds();
+        shading: a Shading table (alpha 0 skips a hit, the albedo is the value) or None (every hit gets `color`).  Returns the statistics."""
+        from ._capi import VoxelizeParams, VoxelizeStats
+        p = VoxelizeParams((C.c_float * 3)(*[float(v) for v in bmin]), float(max_size), (C.c_float * 3)(*[float(v) for v in ext]), int(color), int(max_hits_per_ray))
+        st = VoxelizeStats()
+        check(lib.tbvh_voxelize_device(scene._h, shading._h if shading is not None else None, C.byref(p), self._h, C.byref(st)), "tbvh_voxelize_device")
+        return {"rounds": int(st.rounds), "records": int(st.records), "rays_cut": int(st.rays_cut), "bricks": int(st.bricks)}
+
+    def Normals(self, rays, n: int = None, d_out: int = 0, stride: int = 64):
+        """VoxelSet::GetNormal for a batch of hit records (tbvh_voxel_normals): a RAY_DTYPE host array -> an (n, 4) float32 array {nx, ny, nz, 0}
+        (zeros for a miss), or a device pointer (int) with n= and d_out= (tbvh_voxel_normals_device)."""
+        return voxel_normals(self.ctx, self, rays, n, d_out, stride)
+
+
+def voxelize_bounds(bounds6):
+    """The bounding cube of tiny_bvh_foliage.cpp:216-220 from scene bounds (min xyz, max xyz): (bmin, maxSize, ext) with ext = bmax - bmin,
+    maxSize its largest component and bmin = c - 0.525 * maxSize, in fp32, every product and sum rounded."""
+    b = np.asarray(bounds6, np.float32).reshape(6)
+    lo, hi = b[:3], b[3:]
+    ext = (hi - lo).astype(np.float32)
+    c = ((hi + lo) * np.float32(0.5)).astype(np.float32)
+    m = np.float32(ext[1] if ext[1] > ext[0] else ext[0])
+    if ext[2] > m:
+        m = np.float32(ext[2])
+    return (c - np.float32(0.525) * m).astype(np.float32), m, ext
+
+
+def voxelize_matrix(bmin, max_size) -> np.ndarray:
+    """The demo's matrix T (tiny_bvh_foliage.cpp:256-262), row-major 4 x 4: world space into the voxel object's unit cube."""
+    s = np.float32(1.0) / np.float32(max_size)
+    T = np.zeros((4, 4), np.float32)
+    T[0, 0] = T[1, 1] = T[2, 2] = s
+    T[:3, 3] = -np.asarray(bmin, np.float32) * s
+    T[3, 3] = 1
+    return T
+
+
+def voxel_normals(ctx: Context, scene, rays, n: int = None, d_out: int = 0, stride: int = 64):
+    """GetNormal for hit records of one voxel set (scene None or a VoxelSet) or of a TLAS over voxel sets, whose normals come back in the hit
+    instance's object space (tbvh_voxel_normals / tbvh_voxel_normals_device; see VoxelSet.Normals)."""
+    h = scene._h if scene is not None else None
+    if isinstance(rays, int):
+        check(lib.tbvh_voxel_normals_device(ctx._h, h, C.c_void_p(rays), int(stride), int(n), C.c_void_p(d_out)), "tbvh_voxel_normals_device")
+        return d_out
+    rays = np.ascontiguousarray(rays)
+    out = np.zeros((rays.shape[0], 4), np.float32)
+    check(lib.tbvh_voxel_normals(ctx._h, h, _ptr(rays), rays.dtype.itemsize, rays.shape[0], _ptr(out)), "tbvh_voxel_normals")
+    return out
+
+
+def host_voxel_normals(rays, instances=None):
+    """The CPU twin of voxel_normals (tbvh_host_voxel_normals): instances = the TLAS's BLASInstance records, or None for one set."""
+    rays = np.ascontiguousarray(rays)
+    out = np.zeros((rays.shape[0], 4), np.float32)
+    inst = None if instances is None else np.ascontiguousarray(instances)
+    check(lib.tbvh_host_voxel_normals(None if inst is None else _ptr(inst), 0 if inst is None else inst.shape[0], _ptr(rays), rays.dtype.itemsize, rays.shape[0],
+                                      _ptr(out)), "tbvh_host_voxel_normals")
+    return out
+
+
+class HostVoxelEdit(HostVoxelSet):
+    """The CPU twin of the device editing calls: an empty set (the reference's constructor) or a copy of given arrays, Set per record in turn,
+    UpdateTopGrid (tbvh_host_voxelset_create / _set / _update_top_grid); arrays() are its grid, used bricks and top grid."""
+
+    def __init__(self):
+        h = C.c_void_p()
+        check(lib.tbvh_host_voxelset_create(C.byref(h)), "tbvh_host_voxelset_create")
+        super().__init__(h)
+
+    def Set(self, xyzv) -> "HostVoxelEdit":
+        recs = np.ascontiguousarray(xyzv, np.uint32).reshape(-1, 4)
+        check(lib.tbvh_host_voxelset_set(self._h, _ptr(recs), recs.shape[0]), "tbvh_host_voxelset_set")
+        return self
+
+    def UpdateTopGrid(self) -> "HostVoxelEdit":
+        check(lib.tbvh_host_voxelset_update_top_grid(self._h), "tbvh_host_voxelset_update_top_grid")
+        return self
+
 
 # ---- custom geometry: sphere BLASes (BVH::Build( customGetAABB, n ) + the anim demo's sphere callback) ----------------------------------------
 def host_build_custom_spheres(spheres: np.ndarray):

@@ -35,6 +35,14 @@ class OmmSource(C.Structure):   # tbvh_omm_source
                 ("n_tris", C.c_uint64), ("tri_texture", C.c_void_p), ("textures", C.POINTER(AlphaTexture)), ("n_textures", C.c_uint32)]
 
 
+class VoxelizeParams(C.Structure):   # tbvh_voxelize_params
+    _fields_ = [("bmin", C.c_float * 3), ("maxSize", C.c_float), ("ext", C.c_float * 3), ("color", C.c_uint32), ("max_hits_per_ray", C.c_uint32)]
+
+
+class VoxelizeStats(C.Structure):   # tbvh_voxelize_stats
+    _fields_ = [("rounds", C.c_uint32), ("reserved", C.c_uint32), ("records", C.c_uint64), ("rays_cut", C.c_uint64), ("bricks", C.c_uint64)]
+
+
 class SceneGraphDesc(C.Structure):   # tbvh_scenegraph_desc
     _fields_ = [("flags", C.c_uint32), ("n_nodes", C.c_uint64), ("parent", C.c_void_p), ("visit_order", C.c_void_p), ("translation", C.c_void_p), ("rotation", C.c_void_p),
                 ("scale", C.c_void_p), ("matrix", C.c_void_p), ("local_transform", C.c_void_p), ("n_weights", C.c_void_p), ("weights", C.c_void_p),
@@ -195,6 +203,20 @@ SYMBOLS = {
     "tbvh_upload_voxelset": (_i, [_vp, _vp, _vp, _u64, _vp, _pp]),
     "tbvh_host_build_voxelset": (_i, [_vp, _u32, _u32, _u32, _pp]),
     "tbvh_upload_voxelset_dense": (_i, [_vp, _vp, _u32, _u32, _u32, _pp]),
+    # editing voxel sets, GetNormal (capi_voxel_edit.hip, voxel_edit_host.cpp)
+    "tbvh_voxelset_create": (_i, [_vp, _u64, _pp]),
+    "tbvh_voxelset_reserve": (_i, [_vp, _u64]),
+    "tbvh_voxelset_capacity": (_i, [_vp, _vp, _vp]),
+    "tbvh_voxelset_set": (_i, [_vp, _vp, _u64, _i]),
+    "tbvh_voxelset_update_top_grid": (_i, [_vp]),
+    "tbvh_voxelset_download": (_i, [_vp, _vp, _vp, _u64, _vp, _vp]),
+    "tbvh_host_voxelset_create": (_i, [_pp]),
+    "tbvh_host_voxelset_set": (_i, [_vp, _vp, _u64]),
+    "tbvh_host_voxelset_update_top_grid": (_i, [_vp]),
+    "tbvh_voxel_normals_device": (_i, [_vp, _vp, _vp, _u32, _u64, _vp]),
+    "tbvh_voxel_normals": (_i, [_vp, _vp, _vp, _u32, _u64, _vp]),
+    "tbvh_voxelize_device": (_i, [_vp, _vp, _vp, _vp, _vp]),
+    "tbvh_host_voxel_normals": (_i, [_vp, _u64, _vp, _u32, _u64, _vp]),
     # custom-geometry sphere BLASes (capi_custom.hip)
     "tbvh_upload_custom_spheres": (_i, [_vp, _vp, _u64, _vp, _u64, _vp, _u64, _pp]),
     "tbvh_host_build_custom_spheres": (_i, [_vp, _u64, _pp]),

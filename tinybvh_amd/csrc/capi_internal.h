@@ -326,6 +326,11 @@ struct tbvh_scene {
     // BVH_DOUBLE scenes that move (capi_double.hip).  A TLAS: what the parts of its one allocation hold (tlasParts lays them out by these, so a smaller
     // tree goes in place); the rebuild keeps its scratch in buildScratch (sized for buildScratchFor instances).  A BLAS: its triangle count, and from the
     // first refit on parent[] | leaf list | flags in refitScratch (dblLeaves leaves); host vertices are staged in vertStage.  sceneBytes counts them all.
+    // a voxel set that is edited (capi_voxel_edit.hip): `nodes` holds [top 16 | grid 32768 | bricks capacity x 512] and nNodes the USED bricks; the batched
+    // Set keeps its fixed-size work area (first record per grid cell, the sort's arrays, counters) in voxWork, one winner word per voxel of the pool in
+    // voxWinner (all zero between calls) and staged host records in voxStage.  sceneBytes counts all three.
+    DevBuf<uint32_t> voxWork, voxWinner, voxStage;
+    size_t voxSortTemp = 0;
     uint64_t dblCapNodes = 0, dblCapIdx = 0, dblCapInst = 0;
     uint64_t dblTris = 0, dblRecs = 0;
     uint32_t dblLeaves = 0;

@@ -1,6 +1,7 @@
 // capi_query.hip — the query path: launchQuery and its steps (the plan of launch_plan.h carried out: lane, counter pool, probe, kernels), host-array
 // staging, multi-device sharding, ray generators.
 #include "capi_internal.h"
+#include "voxel_edit.h"
 
 using namespace tbvh;
 using namespace tbvh_capi;
@@ -649,6 +650,7 @@ int checkStatus(tbvh_context* c) {
                        "joint was not written"},
         {kStatusShade, "shade: a hit record's instance, BLAS slot or primitive, or a device-resident material or texture index, is out of range (the record "
                        "got no surface, or an untextured albedo of 0)"},
+        {kStatusVoxelNormal, "voxel normals: a hit record's instance index is not an instance of the TLAS (that record got zeros)"},
     };
     uint32_t st = 0;
     if (int r = joinLanes(c)) return r;   // (launches on lane 1 set the status word too)

@@ -29,7 +29,8 @@ tbvh_scene* newScene(tbvh_context* c, int layout) {
 //   [4] the index buffer a scene made from an indexed mesh holds
 //   [5] an fp32 TLAS's wide trees, the 8-wide tree's references and the SAH builder's Wald nodes; an fp64 TLAS's one allocation (capi_double.hip: tlasLayout( its
 //       capacities ).total, which is what `nodes` was allocated with)
-//   [6] counted scratch and staging: the SAH TLAS builder's scratch, a sphere BLAS's primIdx, and ON SPHERE AND fp64 SCENES ONLY buildScratch, refitScratch, vertStage
+//   [6] counted scratch and staging: the SAH TLAS builder's scratch, a sphere BLAS's primIdx, an edited voxel set's work area, winner words and staged records,
+//       and ON SPHERE AND fp64 SCENES ONLY buildScratch, refitScratch, vertStage
 //   [7] everything else a scene holds: buildScratch, refitScratch and vertStage of every other kind of scene, idxStage, the hybrid copy's numbering (cw.perm), a
 //       TLAS's shared wide-build scratch, BLAS bounds, staged transforms and descriptor tables
 //       (the eight words do NOT claim to sum to the scene's allocations: the room an uploaded array keeps beyond what it holds now is in none of them)
@@ -53,7 +54,7 @@ SceneBytes sceneBytesByWord(const tbvh_scene* s) {
     w[4] += s->meshIdx.count() * 4;
     if (tlas32) w[5] += (t.tlas4.count() + t.tlas8.count() + t.tlasWald.count()) * 16 + t.tlas8Refs.count() * 4;
     if (tlas64) w[5] += s->nodes.count() * 16;
-    w[6] += t.tlasSah.count() + s->sphIdx.count() * 4;
+    w[6] += t.tlasSah.count() + s->sphIdx.count() * 4 + (s->voxWork.count() + s->voxWinner.count() + s->voxStage.count()) * 4;
     w[sphere || dbl ? 6 : 7] += s->buildScratch.count() + s->refitScratch.count() + s->vertStage.count();
     w[7] += (s->idxStage.count() + s->cw.perm.count()) * 4;
     w[7] += t.tlas4Scratch.count() + (t.blasBounds.count() + t.xformStage.count()) * 4 + (t.blasDesc.count() + t.blasDescAny.count()) * sizeof(BlasDesc);

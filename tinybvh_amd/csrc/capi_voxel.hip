@@ -4,40 +4,22 @@
 // A VOXELSET scene keeps ONE device allocation in `nodes`: [top grid 16 | grid 32768 | bricks n_bricks x 512] uint32 words, which is also
 // what a TLAS's BlasDesc::nodes points at.  tbvh_free_scene frees it like any scene's nodes.
 #include "capi_internal.h"
+#include "voxel_edit.h"
 
 using namespace tbvh;
 using namespace tbvh_capi;
 
 namespace {
 
-constexpr uint32_t kObjDim = 256, kBrickDim = 8, kGridDim = 32, kGroupDim = 4, kTopDim = 8;   // VoxelSet::objectDim = 256 (tiny_bvh.h:1008-1022)
-constexpr uint64_t kGridWords = (uint64_t)kGridDim * kGridDim * kGridDim, kBrickWords = (uint64_t)kBrickDim * kBrickDim * kBrickDim, kTopWords = 16;
-constexpr uint64_t kMaxBricks = 1ull << 22;   // (device offsets are 32-bit: 16 + 32768 + 2^22 x 512 < 2^31)
+constexpr uint32_t kObjDim = kVoxObjDim;   // VoxelSet::objectDim = 256 (tiny_bvh.h:1008-1022); the dimensions are voxel_edit.h's
+constexpr uint64_t kGridWords = kVoxGridWords, kBrickWords = kVoxBrickWords, kTopWords = kVoxTopWords, kMaxBricks = kVoxMaxBricks;
 
-// VoxelSet::Set (tiny_bvh.h:3786-3807): a brick is numbered when its first voxel is set (freeBrickPtr, brick 0 skipped); the pool's
-// reallocation does not change the numbering, so a growing vector stands for it
-void setVoxel(tbvh_hostbvh* h, uint32_t x, uint32_t y, uint32_t z, uint32_t v) {
-    const uint32_t g = x / kBrickDim + (y / kBrickDim) * kGridDim + (z / kBrickDim) * kGridDim * kGridDim;
-    uint32_t b = h->vgrid[g];
-    if (!b) {
-        b = h->vgrid[g] = (uint32_t)(h->vbricks.size() / kBrickWords);
-        h->vbricks.resize(h->vbricks.size() + kBrickWords, 0u);
-    }
-    h->vbricks[(size_t)b * kBrickWords + (x & (kBrickDim - 1)) + (y & (kBrickDim - 1)) * kBrickDim + (z & (kBrickDim - 1)) * kBrickDim * kBrickDim] = v;
-}
-
-// VoxelSet::UpdateTopGrid (tiny_bvh.h:3809-3827)
+// VoxelSet::Set (tiny_bvh.h:3786-3807) and UpdateTopGrid (3809-3827): voxel_edit.h, shared with the editing entry points (capi_voxel_edit.hip,
+// voxel_edit_host.cpp)
+void setVoxel(tbvh_hostbvh* h, uint32_t x, uint32_t y, uint32_t z, uint32_t v) { voxel_set_host(h->vgrid, h->vbricks, x, y, z, v); }
 void updateTopGrid(tbvh_hostbvh* h) {
     h->vtop.assign(kTopWords, 0u);
-    for (uint32_t x = 0; x < kTopDim; x++) for (uint32_t y = 0; y < kTopDim; y++) for (uint32_t z = 0; z < kTopDim; z++) {
-        const uint32_t* base = h->vgrid.data() + x * kGroupDim + y * kGroupDim * kGridDim + z * kGroupDim * kGridDim * kGridDim;
-        bool has = false;
-        for (uint32_t u = 0; u < kGroupDim && !has; u++) for (uint32_t v = 0; v < kGroupDim && !has; v++) for (uint32_t w = 0; w < kGroupDim && !has; w++)
-            has = base[u + v * kGridDim + w * kGridDim * kGridDim] != 0;
-        if (!has) continue;
-        const uint32_t ti = x + y * kTopDim + z * kTopDim * kTopDim;
-        h->vtop[ti >> 5] |= 1u << (ti & 31);
-    }
+    voxel_update_top_grid_host(h->vgrid.data(), h->vtop.data());
 }
 
 }  // namespace
@@ -90,6 +72,35 @@ int tbvh_host_build_voxelset(const uint32_t* values, uint32_t nx, uint32_t ny, u
         return fail(TBVH_E_NOMEM, "out of host memory while building");
     }
     *out = h;
+    return 0;
+}
+
+// ---- the CPU twins of the editing calls (capi_voxel_edit.hip): the reference's constructor, Set per record in turn, UpdateTopGrid ------------------
+int tbvh_host_voxelset_create(tbvh_hostbvh** out) {
+    if (!out) return fail(TBVH_E_INVALID, "tbvh_host_voxelset_create: null argument");
+    tbvh_hostbvh* h = new (std::nothrow) tbvh_hostbvh;
+    if (!h) return fail(TBVH_E_NOMEM, "out of host memory");
+    h->layout = TBVH_LAYOUT_VOXELSET;
+    try {
+        h->vgrid.assign(kGridWords, 0u);
+        h->vbricks.assign(kBrickWords, 0u);   // brick 0: never written (freeBrickPtr = 1)
+        h->vtop.assign(kTopWords, 0u);
+    } catch (const std::bad_alloc&) {
+        delete h;
+        return fail(TBVH_E_NOMEM, "out of host memory");
+    }
+    *out = h;
+    return 0;
+}
+
+int tbvh_host_voxelset_set(tbvh_hostbvh* h, const uint32_t* xyzv, uint64_t n) {
+    if (!h || h->layout != TBVH_LAYOUT_VOXELSET) return fail(TBVH_E_INVALID, "tbvh_host_voxelset_set: not a voxel set");
+    return voxel_host_set_records(h->vgrid, h->vbricks, xyzv, n);   // (voxel_edit_host.cpp: the refusals first, then setVoxel's Set per record)
+}
+
+int tbvh_host_voxelset_update_top_grid(tbvh_hostbvh* h) {
+    if (!h || h->layout != TBVH_LAYOUT_VOXELSET) return fail(TBVH_E_INVALID, "tbvh_host_voxelset_update_top_grid: not a voxel set");
+    updateTopGrid(h);
     return 0;
 }
 

@@ -200,6 +200,38 @@ struct ShadeTables;
 void launch_shade_hits(const ShadeTables& tb, const float4* instances, uint64_t nInst, const uint32_t* blasLayout, uint32_t blasStride, uint32_t nBlas, const void* rays,
                        uint64_t n, uint32_t strideBytes, void* out48, uint32_t* status, hipStream_t s);
 void launch_shade_continue(void* rays, uint32_t strideBytes, const void* out48, uint64_t n, unsigned long long* nContinued, hipStream_t s);
+// (kernels_voxel_edit.hip) the batched VoxelSet::Set in deterministic passes over records { x, y, z, v } (voxel_edit.h), vox = the set's one allocation:
+//   mark   — work.cellFirst[g] = the smallest record index touching a grid cell g that has no brick; counters[0] = such cells, [1] = records out of range (skipped
+//            by every pass); the launch resets the work area first
+//   number — the marked cells sorted by that index: grid[cell of rank r] = used + r (nNew of them; the caller has read counters[0] and zeroed the bricks)
+//   winner — winner[brick * 512 + voxel] = 1 + the largest record index writing that voxel
+//   store  — the record that is its voxel's winner stores v and clears the winner word: the words are all zero again afterwards
+// launch_voxel_top_grid is UpdateTopGrid (512 lanes, one top cell each); launch_voxel_normals GetNormal per hit record (voxel_edit.h: voxel_normal_record)
+struct VoxelEditWork {
+    uint32_t *cellFirst, *cellIds, *sortedFirst, *sortedCells;   // 32768 words each
+    uint32_t* counters;                                          // 64 words
+    void* sortTemp;
+    size_t sortTempBytes;
+};
+size_t voxel_edit_work_words(size_t* sortTempBytes);             // the work area's size in uint32 words
+VoxelEditWork voxel_edit_work(uint32_t* base, size_t sortTempBytes);
+void launch_voxel_mark(const uint32_t* vox, const uint4* recs, uint64_t n, const VoxelEditWork& w, hipStream_t s);
+hipError_t launch_voxel_number(uint32_t* vox, const VoxelEditWork& w, uint32_t used, uint32_t nNew, hipStream_t s);
+void launch_voxel_winner(const uint32_t* vox, const uint4* recs, uint64_t n, uint32_t* winner, hipStream_t s);
+void launch_voxel_store(uint32_t* vox, const uint4* recs, uint64_t n, uint32_t* winner, hipStream_t s);
+void launch_voxel_top_grid(uint32_t* vox, hipStream_t s);
+// ... and the scene-to-voxels loop (tiny_bvh_foliage.cpp:222-258).  launch_voxelize_rays: the 3 x 256^2 axis rays, ids and hit numbers (0).  launch_voxelize_step:
+// one round after trace (and shade: out48, or nullptr for the constant colour) over n live rays — a ray without a hit below 10000 ends, one with maxHits hits
+// behind it is cut (counters[2]), a hit with alpha != 0 appends a record { x, y, z, v } and its key id << 32 | hit number (counters[1], never reset: the
+// records of all rounds), and the ray, advanced, goes to the next round's arrays (counters[0]).  launch_voxelize_sort: the records in key order.
+struct VoxelizeArgs;
+void launch_voxelize_rays(const VoxelizeArgs& p, RayRec* rays, uint32_t* ids, uint32_t* hitNo, hipStream_t s);
+void launch_voxelize_step(const VoxelizeArgs& p, const RayRec* rays, const uint32_t* ids, const uint32_t* hitNo, const float4* out48, uint64_t n, RayRec* raysOut,
+                          uint32_t* idsOut, uint32_t* hitNoOut, unsigned long long* keys, uint4* recs, uint32_t* counters, hipStream_t s);
+size_t voxelize_sort_temp_bytes(uint64_t n);
+hipError_t launch_voxelize_sort(const unsigned long long* keys, unsigned long long* keysOut, uint32_t* order, uint32_t* orderOut, const uint4* recs, uint4* recsOut,
+                                uint64_t n, void* temp, size_t tempBytes, hipStream_t s);
+void launch_voxel_normals(const float4* instances, uint64_t nInst, const void* rays, uint32_t strideBytes, uint64_t n, float4* out, uint32_t* status, hipStream_t s);
 
 // ray generators (kernels_raygen.hip)
 struct CameraArgs {

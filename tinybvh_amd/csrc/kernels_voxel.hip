@@ -30,6 +30,7 @@
 #include "lane_stack.h"
 #include "ray_pool.h"
 #include "kernels.h"
+#include "voxel_edit.h"
 
 namespace tbvh {
 
@@ -43,7 +44,7 @@ constexpr uint32_t kGridOff = 16u, kBrickOff = 16u + 32768u;
 __device__ __forceinline__ float vmin(float a, float b) { return a < b ? a : b; }   // tinybvh_min (tiny_bvh.h:445)
 __device__ __forceinline__ float vmax(float a, float b) { return a > b ? a : b; }   // tinybvh_max (tiny_bvh.h:446)
 __device__ __forceinline__ int32_t vclamp(int32_t x, int32_t a, int32_t b) { return x > a ? (x < b ? x : b) : a; }   // tiny_bvh.h:458
-__device__ __forceinline__ int32_t cvt_x86(float f) { return (f >= -2147483648.0f && f < 2147483648.0f) ? (int32_t)f : INT32_MIN; }
+__device__ __forceinline__ int32_t cvt_x86(float f) { return voxel_cvt_x86(f); }   // (voxel_edit.h: shared with the voxelise step)
 __device__ __forceinline__ float safercp(float x) {   // tinybvh_safercp (tiny_bvh.h:442)
     if (x > 1e-12f || x < -1e-12f) return 1.0f / x;
     return x >= 0 ? kFar : -kFar;
@@ -245,16 +246,10 @@ __global__ __launch_bounds__(WG) void k_voxel(const uint32_t* __restrict__ vox, 
                 const float4 b0 = ip[8], b1 = ip[9];                      // aabbMin|blasIdx, aabbMax|mask
                 if (as_u32(b1.w) & rayMask) {                              // tiny_bvh.h:3326
                     const float4 r0 = ip[4], r1 = ip[5], r2 = ip[6], r3 = ip[7];   // invTransform rows
-                    // tinybvh_transform_point / _vector with the reference build's contraction (kernels_tlas.hip; oracle/tbvh_oracle.c: orc_xform_point / orc_xform_vec)
-                    const float3 O = wO, D = wD;
-                    const float px = __builtin_fmaf(r0.z, O.z, __builtin_fmaf(r0.x, O.x, r0.y * O.y)) + r0.w;
-                    const float py = __builtin_fmaf(r1.z, O.z, __builtin_fmaf(r1.x, O.x, r1.y * O.y)) + r1.w;
-                    const float pz = __builtin_fmaf(r2.z, O.z, __builtin_fmaf(r2.x, O.x, r2.y * O.y)) + r2.w;
-                    const float w = __builtin_fmaf(r3.z, O.z, __builtin_fmaf(r3.x, O.x, r3.y * O.y)) + r3.w;
-                    const float3 lD = make_float3(__builtin_fmaf(r0.z, D.z, __builtin_fmaf(r0.x, D.x, r0.y * D.y)), __builtin_fmaf(r1.z, D.z, __builtin_fmaf(r1.x, D.x, r1.y * D.y)),
-                                                  __builtin_fmaf(r2.z, D.z, __builtin_fmaf(r2.x, D.x, r2.y * D.y)));
-                    if (w == 1) s.O = make_float3(px, py, pz);
-                    else { const float iw = 1.f / w; s.O = make_float3(px * iw, py * iw, pz * iw); }
+                    // tinybvh_transform_point / _vector with the reference build's contraction (voxel_edit.h, shared with the normals of a TLAS hit)
+                    float3 lO, lD;
+                    voxel_instance_ray(r0, r1, r2, r3, wO, wD, lO, lD);
+                    s.O = lO;
                     s.D = lD;
                     s.rD = make_float3(safercp(lD.x), safercp(lD.y), safercp(lD.z));
                     s.vox = (const uint32_t*)blas[as_u32(b0.w)].nodes;
