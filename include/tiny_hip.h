@@ -433,6 +433,53 @@ private:
     tbvh_shading* p = nullptr;
 };
 
+// tinyscene::SkyDome on the device (tbvh_sky_*): pixels as SkyDome::pixels after Load, 3 floats per texel, copied
+class SkyDome {
+public:
+    SkyDome(const float* pixels12, uint32_t width, uint32_t height, tbvh_context* own = nullptr, int device = 0) : ctx(own ? own : Context(device)) {
+        Check(tbvh_sky_create(ctx, pixels12, width, height, 0, &p), "tbvh_sky_create");
+    }
+    SkyDome(const SkyDome&) = delete;
+    SkyDome& operator=(const SkyDome&) = delete;
+    ~SkyDome() { tbvh_sky_free(p); }
+    // n device-resident directions (float4, xyz read) -> the texel as ( z, y, x ) and its index; asynchronous on the context's stream
+    void SampleDevice(const void* dDirs16, size_t n, void* dOut16) { Check(tbvh_sky_sample_device(p, dDirs16, n, dOut16), "tbvh_sky_sample_device"); }
+    tbvh_sky* Handle() const { return p; }
+private:
+    tbvh_context* ctx;
+    tbvh_sky* p = nullptr;
+};
+
+// A frame of the reference's CPU viewers (tiny_bvh_gltf.cpp / tiny_bvh_foliage.cpp: WorkerThread, Trace, SampleSky) rendered on the device (tbvh_viewer_*):
+// eye, p1, p2, p3 as UpdateCamera leaves them; Pixels() is the window buffer (0x00BBGGRR, width * height words).  scene: a TLAS or a single triangle BLAS;
+// sky may be null (every sample is 0).
+class Viewer {
+public:
+    Viewer(uint32_t width, uint32_t height, tbvh_context* own = nullptr, int device = 0) : ctx(own ? own : Context(device)), w(width), h(height) {
+        Check(tbvh_viewer_create(ctx, width, height, &p), "tbvh_viewer_create");
+    }
+    Viewer(const Viewer&) = delete;
+    Viewer& operator=(const Viewer&) = delete;
+    ~Viewer() { tbvh_viewer_destroy(p); }
+    // stats == nullptr: asynchronous on the context's stream
+    void Render(tbvh_scene* scene, const Shading& shading, const SkyDome* sky, const float eye[3], const float p1[3], const float p2[3], const float p3[3],
+                uint32_t mode = TBVH_VIEWER_GLTF, const float* lightDir = nullptr, uint32_t maxRounds = 0, tbvh_viewer_stats* stats = nullptr) {
+        tbvh_camera cam;
+        for (int k = 0; k < 3; k++) { cam.eye[k] = eye[k]; cam.p1[k] = p1[k]; cam.p2[k] = p2[k]; cam.p3[k] = p3[k]; }
+        cam.width = w; cam.height = h; cam.spp_x = cam.spp_y = 1;
+        tbvh_viewer_params params = {mode, maxRounds, {lightDir ? lightDir[0] : 0.f, lightDir ? lightDir[1] : 0.f, lightDir ? lightDir[2] : 0.f}, 0u};
+        Check(tbvh_viewer_render(p, scene, shading.Handle(), sky ? sky->Handle() : nullptr, &cam, &params, stats), "tbvh_viewer_render");
+    }
+    void Pixels(uint32_t* pixels) { Check(tbvh_viewer_read_pixels(p, pixels), "tbvh_viewer_read_pixels"); }   // synchronous
+    void RGB(void* rgb16) { Check(tbvh_viewer_read_rgb(p, rgb16), "tbvh_viewer_read_rgb"); }
+    void* RaysDevice() { void* d = nullptr; Check(tbvh_viewer_rays(p, &d), "tbvh_viewer_rays"); return d; }
+    tbvh_viewer* Handle() const { return p; }
+private:
+    tbvh_context* ctx;
+    uint32_t w, h;
+    tbvh_viewer* p = nullptr;
+};
+
 // tinyocl::Buffer( bytes ) for a ray array that is traced many times (tiny_bvh_speedtest.cpp:1101-1108 wraps its ray array in one per GPU block): page-locked
 // host memory of the library's for the object's lifetime (tbvh_pinned_malloc); a PACKED 64-byte ray array in it goes up by DMA straight from there.
 class PinnedBuffer {

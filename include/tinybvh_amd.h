@@ -46,7 +46,7 @@
 extern "C" {
 #endif
 
-#define TBVH_ABI_VERSION 5   /* 5 (additions, nothing changed: hits resolved to shading data — tbvh_shading_*, tbvh_shade_hits / _device, tbvh_shade_continue_device, tbvh_host_shade_hits, tbvh_pose_attach_fat_tris, tbvh_host_pose_skin_normals / _morph_normals / _update_fat_tris); 5 (additions, nothing changed: indexed and strided triangle meshes — tbvh_mesh and the tbvh_*_mesh entry points, tbvh_flatten_mesh_device); 5 (additions, nothing changed: custom-geometry sphere BLASes — tbvh_upload_custom_spheres, tbvh_host_build_custom_spheres, TLASes over them); 5 (additions, nothing changed: tbvh_intersect_spheres / _device); 5 (additions, nothing changed: VoxelSet scenes — TBVH_LAYOUT_VOXELSET, tbvh_upload_voxelset / _voxelset_dense, tbvh_host_build_voxelset, TLASes over voxel sets); 5 (additions, nothing changed: BVH_Double scenes — TBVH_LAYOUT_BVH_DOUBLE, tbvh_upload_bvh_double / _tlas_double, tbvh_intersect_ex / _occluded_ex (+ _device), tbvh_host_build_double / _tlas_double); 5: tbvh_pinned_malloc / _free, tbvh_scene_get / _set_schedule_hint, tbvh_measure_link_bandwidth, TBVH_BUILD_SPLIT_TRIANGLES / _WHOLE_TRIANGLES, development aids moved to tinybvh_amd_debug.h (nothing removed from the library); 4: tbvh_update_bvh_gpu / _bvh4_gpu / _cwbvh, tbvh_time_history, contexts are thread-safe; 3: deterministic ties, tbvh_bin_rays_device, tbvh_cwbvh_set_hybrid, device-resident multi-device calls */
+#define TBVH_ABI_VERSION 5   /* 5 (additions, nothing changed: a viewer frame lit and finished on the device — tbvh_sky_*, tbvh_viewer_*, tbvh_host_sky_* / tbvh_host_viewer_*); 5 (additions, nothing changed: hits resolved to shading data — tbvh_shading_*, tbvh_shade_hits / _device, tbvh_shade_continue_device, tbvh_host_shade_hits, tbvh_pose_attach_fat_tris, tbvh_host_pose_skin_normals / _morph_normals / _update_fat_tris); 5 (additions, nothing changed: indexed and strided triangle meshes — tbvh_mesh and the tbvh_*_mesh entry points, tbvh_flatten_mesh_device); 5 (additions, nothing changed: custom-geometry sphere BLASes — tbvh_upload_custom_spheres, tbvh_host_build_custom_spheres, TLASes over them); 5 (additions, nothing changed: tbvh_intersect_spheres / _device); 5 (additions, nothing changed: VoxelSet scenes — TBVH_LAYOUT_VOXELSET, tbvh_upload_voxelset / _voxelset_dense, tbvh_host_build_voxelset, TLASes over voxel sets); 5 (additions, nothing changed: BVH_Double scenes — TBVH_LAYOUT_BVH_DOUBLE, tbvh_upload_bvh_double / _tlas_double, tbvh_intersect_ex / _occluded_ex (+ _device), tbvh_host_build_double / _tlas_double); 5: tbvh_pinned_malloc / _free, tbvh_scene_get / _set_schedule_hint, tbvh_measure_link_bandwidth, TBVH_BUILD_SPLIT_TRIANGLES / _WHOLE_TRIANGLES, development aids moved to tinybvh_amd_debug.h (nothing removed from the library); 4: tbvh_update_bvh_gpu / _bvh4_gpu / _cwbvh, tbvh_time_history, contexts are thread-safe; 3: deterministic ties, tbvh_bin_rays_device, tbvh_cwbvh_set_hybrid, device-resident multi-device calls */
 
 /* error codes */
 #define TBVH_OK            0
@@ -69,6 +69,8 @@ typedef struct tbvh_context tbvh_context;  /* one HIP device + stream + scratch 
 typedef struct tbvh_scene   tbvh_scene;    /* one uploaded layout (BLAS or TLAS)         */
 typedef struct tbvh_hostbvh tbvh_hostbvh;  /* host-built blobs (see "host builder")      */
 typedef struct tbvh_shading tbvh_shading;  /* a shading table (see "hits resolved to shading data") */
+typedef struct tbvh_sky     tbvh_sky;      /* a sky dome (see "a viewer frame lit and finished on the device") */
+typedef struct tbvh_viewer  tbvh_viewer;   /* a viewer frame's buffers (same section)    */
 
 /* ------------------------------------------------------------------------------------
  * context — replaces tinyocl::Kernel::InitCL (tiny_ocl.h:945-1139)
@@ -1122,7 +1124,8 @@ int tbvh_host_bake_opacity_micromaps(const tbvh_omm_source* src, uint32_t N, uin
  * raytracer.cl's Trace): hit.inst -> BLASInstance::blasIdx -> FatTri[ hit.prim ] -> Material -> texel, giving an albedo, an alpha decision, the geometric
  * normal and the interpolated (optionally normal-mapped) normal, both in world space.  A tbvh_shading (one or more per context) owns device copies of
  * the materials, the texture descriptors and, per BLAS slot, the tinyscene::FatTri records (192 bytes each, taken verbatim as the BVH blobs are); the
- * scene graph, glTF loading, texture decoding, mips, HDR (fdata) textures, the second UV layer and sky / fog / tone mapping stay with the caller.
+ * scene graph, glTF loading, texture decoding, mips, HDR (fdata) textures, the second UV layer and fog stay with the caller (the sky, the sun term and the
+ * pack to pixels of the reference's two CPU viewers: tbvh_viewer_*, below).
  *   - the arithmetic is the reference's, float operation for float operation, as its build (g++ -O3 -mavx2 -mfma) performs it: tinybvh_amd/csrc/shade.h,
  *     DESIGN.md par. 16.  One deliberate difference: a tiny negative texture coordinate wraps to exactly 1.0f, and the reference then reads the next
  *     row's first texel or, in the last row, past its array; here the reference's linear index is clamped to width * height - 1 — identical wherever the
@@ -1197,6 +1200,82 @@ int tbvh_host_pose_skin_normals(uint64_t n_verts, const uint32_t* joints4, const
 int tbvh_host_pose_morph_normals(const float* normals12, uint64_t n_verts, uint32_t n_targets, void* out16);
 int tbvh_host_pose_update_fat_tris(void* fat_tris192, uint64_t n_tris, const void* verts16, const void* normals16, uint64_t n_verts, const uint32_t* indices,
                                    int skin);
+
+/* ----------------------------------------------------------------------------------
+ * a viewer frame lit and finished on the device — the rest of Trace and WorkerThread of the reference's two CPU viewers (tiny_bvh_gltf.cpp:76-86,
+ * 137-175; tiny_bvh_foliage.cpp:67-77, 128-190, the triangle branch) around Intersect and GetShadingData above: the row-major pinhole rays, the alpha
+ * loop of up to 8 rounds, SampleSky, the sun term with its shadow ray, and the clamp and pack to 0x00BBGGRR.  A frame goes from a camera to pixels
+ * without leaving the device: the records that continue are compacted into a device-side queue whose count the host never reads.
+ *   - the arithmetic is the reference's as its build (g++ -O3 -mavx2 -mfma) performs it: tinybvh_amd/csrc/viewer.h, DESIGN.md par. 22, one copy for the
+ *     kernels and the tbvh_host_* twins, which therefore agree in every bit.  atan2 and acos are viewer.h's own polynomials, not libm's: a sky texel
+ *     can differ from the reference's where a texel coordinate lies within a measured margin of an integer (par. 22).
+ *   - deliberate differences, all in SampleSky: D.y is clamped to [-1, 1] before acos (the reference's behaviour there is undefined); a negative or
+ *     non-finite texel coordinate converts to 0; nothing outside the w * h texels is ever read.  An infinite direction component gives an unspecified
+ *     texel of the sky.
+ *   - generator: ray i is pixel ( i % width, i / width ): u = (float)px / width, v = (float)py / height, D = normalize( p1 + u ( p2 - p1 ) +
+ *     v ( p3 - p1 ) - eye ), then the Ray constructor (normalised again, rD = safercp, hit.t = 1e30, mask 0xFFFF).  Any positive width and height whose
+ *     product is below 2^31; spp_x / spp_y of the camera are not looked at.  tbvh_generate_primary_device (4 x 4 tiles, spp) is unchanged.
+ *   - sky: 12 bytes per texel as SkyDome::pixels, 1 .. 2^31 - 1 texels; the object keeps its own device copy.  tbvh_sky_sample_device: n directions
+ *     (float4, xyz read) in, per direction the texel as ( z, y, x ) and its index (the bits of w) out.  tbvh_host_sky_prepare: the two arithmetic passes of
+ *     SkyDome::Load in place (from_hdr != 0: sqrtf first; then p * p * scale, scale3 NULL = 1): file decoding stays with the caller.
+ *   - mode TBVH_VIEWER_GLTF: a hit on a colour-textured material whose texel has x + y + z <= 5 is masked and continues from O = I + D * 1e-4, for up to
+ *     max_rounds rounds (0 = 8; the last round's masked layer is shaded as it is); hit.t >= 10000 gives SampleSky( D ); otherwise R = D - 2 dot( iN, D ) iN
+ *     and the colour is albedo * ( 0.5 * SampleSky( R ) + max( 0.2, dot( iN, L ) ) ).  A table that names no colour texture runs one round.
+ *   - mode TBVH_VIEWER_FOLIAGE: one round; a texel with alpha <= 2 gives albedo ( 1, 0, 1 ); the shadow ray is Ray( I + L * 0.001, L, 1000 ), traced as an
+ *     any-hit query on the same scene (a pixel without a hit below 10000 gets a null ray, tmax 0, whose flag is not read); the colour is
+ *     albedo * ( shaded ? 0.3 : 1 ) * ( 0.25 + max( 0.2, dot( iN, L ) ) ).
+ *   - light_dir: L as the reference's static; NULL or all zero = normalize( 2, 4, 5 ).  pack: E = min( c, 1 ) * 255, (int)E.x + ( (int)E.y << 8 ) +
+ *     ( (int)E.z << 16 ).  Colours are float4 ( r, g, b, 0 ).
+ *   - the stage entry points (one kernel each, asynchronous on the context's stream, records 16-byte aligned, a stride of 64 or more that is a multiple
+ *     of 16) take what the queries and tbvh_shade_hits_device leave; tbvh_viewer_light_device: sky NULL samples 0 as the demos' `if (!sky) return 0`,
+ *     d_occ (foliage: one byte per pixel from tbvh_occluded_device over tbvh_viewer_shadow_rays_device's rays) NULL means nothing is shaded, `shading`
+ *     may be NULL (only its context is checked).  tbvh_host_viewer_continue is the gltf alpha rule and continue step over host records (materials as
+ *     given to tbvh_shading_create, n_textures their texture count; continued: one byte per record, or NULL), for callers that run the loop themselves.
+ *   - tbvh_viewer_render: scene a fp32 TLAS or a single triangle BLAS, the rule of tbvh_shade_hits; BVH_DOUBLE, VOXELSET and sphere scenes, a camera
+ *     whose size is not the viewer's, and a scene, table, sky or viewer of different contexts: TBVH_E_INVALID.  Asynchronous unless `stats` is given;
+ *     the frame is bracketed by ONE event pair (frame_ms; tbvh_time_last_ms() after the call = the frame).  Queue order is free, the frame is not:
+ *     everything lands by pixel index, two renders give the same bytes.  Bad device-resident indices keep the status-word behaviour of
+ *     tbvh_shade_hits_device.  tbvh_viewer_rays: the final records (a continued pixel's record is the one of its last round), device memory owned by
+ *     the viewer.  A sky or viewer still alive at tbvh_shutdown is freed by it.
+ * ---------------------------------------------------------------------------------- */
+#define TBVH_VIEWER_GLTF    0u
+#define TBVH_VIEWER_FOLIAGE 1u
+typedef struct tbvh_viewer_params {
+    uint32_t mode;            /* TBVH_VIEWER_GLTF / TBVH_VIEWER_FOLIAGE                       */
+    uint32_t max_rounds;      /* 1 .. 8 rounds of the alpha loop, 0 = 8                       */
+    float light_dir[3];       /* all zero = normalize( 2, 4, 5 )                              */
+    uint32_t flags;           /* 0                                                            */
+} tbvh_viewer_params;
+typedef struct tbvh_viewer_stats {
+    uint64_t rays[8];         /* nearest-hit rays traced in round r                           */
+    uint64_t shadow_rays;     /* shadow rays that are not null (foliage)                      */
+    float frame_ms;           /* HIP-event time of the whole frame                            */
+} tbvh_viewer_stats;
+int  tbvh_sky_create(tbvh_context* ctx, const float* pixels12, uint32_t width, uint32_t height, int on_device, tbvh_sky** out);
+void tbvh_sky_free(tbvh_sky* sky);   /* waits for the context's stream, then frees */
+int  tbvh_sky_sample_device(tbvh_sky* sky, const void* d_dirs16, uint64_t n, void* d_out16);
+int  tbvh_host_sky_sample(const float* pixels12, uint32_t width, uint32_t height, const void* dirs16, uint64_t n, void* out16);
+int  tbvh_host_sky_prepare(float* pixels12, uint64_t n_texels, const float* scale3, int from_hdr);
+int  tbvh_viewer_generate_device(tbvh_context* ctx, const tbvh_camera* cam, void* d_rays64, uint64_t first, uint64_t n);
+int  tbvh_viewer_shadow_rays_device(tbvh_context* ctx, const void* d_rays, uint32_t ray_stride_bytes, uint64_t n, const float* light_dir, void* d_shadow64);
+int  tbvh_viewer_light_device(tbvh_context* ctx, uint32_t mode, tbvh_shading* shading, tbvh_sky* sky, const void* d_rays, uint32_t ray_stride_bytes, const void* d_out48,
+                              const uint8_t* d_occ, uint64_t n, const float* light_dir, void* d_rgb16);
+int  tbvh_viewer_pack_device(tbvh_context* ctx, const void* d_rgb16, uint64_t n, uint32_t* d_pixels);
+/* The same arithmetic on the CPU (viewer.h compiled for the host), host arrays in and out, no context, one thread. */
+int  tbvh_host_viewer_generate(const tbvh_camera* cam, void* rays64, uint64_t first, uint64_t n);
+int  tbvh_host_viewer_continue(const tbvh_material* materials, uint32_t n_materials, uint32_t n_textures, void* rays, uint32_t ray_stride_bytes, const void* out48, uint64_t n,
+                               uint8_t* continued, uint64_t* n_continued);
+int  tbvh_host_viewer_shadow_rays(const void* rays, uint32_t ray_stride_bytes, uint64_t n, const float* light_dir, void* shadow64);
+int  tbvh_host_viewer_light(uint32_t mode, const float* sky_pixels12, uint32_t sky_width, uint32_t sky_height, const void* rays, uint32_t ray_stride_bytes, const void* out48,
+                            const uint8_t* occ, uint64_t n, const float* light_dir, void* rgb16);
+int  tbvh_host_viewer_pack(const void* rgb16, uint64_t n, uint32_t* pixels);
+int  tbvh_viewer_create(tbvh_context* ctx, uint32_t width, uint32_t height, tbvh_viewer** out);
+void tbvh_viewer_destroy(tbvh_viewer* viewer);   /* waits for the context's stream, then frees */
+int  tbvh_viewer_render(tbvh_viewer* viewer, tbvh_scene* scene, tbvh_shading* shading, tbvh_sky* sky, const tbvh_camera* cam, const tbvh_viewer_params* params,
+                        tbvh_viewer_stats* stats);
+int  tbvh_viewer_read_pixels(tbvh_viewer* viewer, uint32_t* pixels);   /* width * height words; synchronous; reports the status word */
+int  tbvh_viewer_read_rgb(tbvh_viewer* viewer, void* rgb16);           /* width * height float4; likewise */
+int  tbvh_viewer_rays(tbvh_viewer* viewer, void** d_rays64);
 
 /* ----------------------------------------------------------------------------------
  * the animated scene graph on the device — Scene::UpdateSceneGraph of tiny_scene.h (3664-3697) without the BLAS and TLAS builds: Animation::Update ->

@@ -186,6 +186,10 @@ int tbvh_debug_host_scenegraph_check_chains(struct tbvh_host_scenegraph* g, uint
 int tbvh_debug_wavefront_queues(tbvh_wavefront* w, void* rays0, void* aux0, void* rays1, void* aux1, void* shadow, void* shadow_aux, uint8_t* occ,
                                 uint64_t counters[18]);
 
+/* viewer.h's own atan2f (kind 0: out[i] = atan2( a[i], b[i] )) and acosf (kind 1: out[i] = acos( a[i] ), b not read) on the CPU, for tools/viewer_math_error.c,
+ * which measures their distance from float64 libm (DESIGN.md par. 22: the SKY_EDGE margin).  Host arrays, no context. */
+int tbvh_debug_viewer_math(int kind, const float* a, const float* b, uint64_t n, float* out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -2209,3 +2209,219 @@ class Shading:
             self.free()
         except Exception:
             pass
+
+
+# ---- a viewer frame lit and finished on the device (capi_viewer.hip) ------------------------------------------------------------------------
+VIEWER_GLTF, VIEWER_FOLIAGE = 0, 1
+
+
+def viewer_camera(eye, p1, p2, p3, width: int, height: int) -> Camera:
+    """The view pyramid of the reference's viewers (eye and the corners p1, p2, p3 as UpdateCamera leaves them) for a width x height frame."""
+    cam = Camera()
+    for name, v in (("eye", eye), ("p1", p1), ("p2", p2), ("p3", p3)):
+        getattr(cam, name)[:] = [float(np.float32(x)) for x in v]
+    cam.width, cam.height, cam.spp_x, cam.spp_y = int(width), int(height), 1, 1
+    return cam
+
+
+def _light_dir(light_dir):
+    if light_dir is None:
+        return None, None
+    l = np.ascontiguousarray(light_dir, np.float32).reshape(3)
+    return l, _ptr(l)
+
+
+def _sky_pixels(pixels):
+    """(h, w, 3) float32, C-contiguous: SkyDome::pixels"""
+    p = np.ascontiguousarray(pixels, np.float32)
+    if p.ndim != 3 or p.shape[2] != 3:
+        raise ValueError("sky pixels: an (h, w, 3) float32 array")
+    return p
+
+
+def load_sky_bin(path: str) -> np.ndarray:
+    """The reference's `.hdr.bin` sky cache (SkyDome::Load: two ints, then width * height texels of 3 floats) as an (h, w, 3) array — the cached texels, which
+    SkyDome::Load then squares and scales: host_sky_prepare."""
+    with open(path, "rb") as f:
+        w, h = (int(x) for x in np.frombuffer(f.read(8), "<i4"))
+        if w <= 0 or h <= 0:
+            raise ValueError(f"{path}: a {w} x {h} sky")
+        data = np.frombuffer(f.read(12 * w * h), "<f4")
+    if data.size != 3 * w * h:
+        raise ValueError(f"{path}: {data.size} floats for a {w} x {h} sky")
+    return data.reshape(h, w, 3).copy()
+
+
+def host_sky_prepare(pixels, scale=(1.0, 1.0, 1.0), from_hdr: bool = False) -> np.ndarray:
+    """The two arithmetic passes of SkyDome::Load (tbvh_host_sky_prepare) on a copy: sqrtf when the texels come straight from the HDR file, then p * p * scale."""
+    p = _sky_pixels(pixels).copy()
+    s = np.ascontiguousarray(scale, np.float32).reshape(3)
+    check(lib.tbvh_host_sky_prepare(_ptr(p), p.shape[0] * p.shape[1], _ptr(s), int(bool(from_hdr))), "tbvh_host_sky_prepare")
+    return p
+
+
+def host_sky_sample(pixels, dirs) -> np.ndarray:
+    """SampleSky on the CPU (tbvh_host_sky_sample): (n, 4) float32 = the texel as ( z, y, x ) and the bits of its index.  pixels None: no sky, all zero."""
+    d = np.zeros((np.asarray(dirs).shape[0], 4), np.float32)
+    d[:, :3] = np.asarray(dirs, np.float32)[:, :3]
+    out = np.zeros_like(d)
+    if pixels is None:
+        check(lib.tbvh_host_sky_sample(None, 0, 0, _ptr(d), d.shape[0], _ptr(out)), "tbvh_host_sky_sample")
+    else:
+        p = _sky_pixels(pixels)
+        check(lib.tbvh_host_sky_sample(_ptr(p), p.shape[1], p.shape[0], _ptr(d), d.shape[0], _ptr(out)), "tbvh_host_sky_sample")
+    return out
+
+
+def host_viewer_generate(cam: Camera, first: int = 0, n=None) -> np.ndarray:
+    """WorkerThread's rays on the CPU (tbvh_host_viewer_generate): ray i is pixel ( i % width, i / width )."""
+    n = cam.width * cam.height - first if n is None else int(n)
+    rays = _aligned(np.zeros(max(n, 0), RAY_DTYPE))
+    check(lib.tbvh_host_viewer_generate(C.byref(cam), _ptr(rays) if n else None, int(first), n), "tbvh_host_viewer_generate")
+    return rays
+
+
+def host_viewer_continue(materials, n_textures: int, rays: np.ndarray, out48: np.ndarray):
+    """The gltf alpha rule and continue step on host records, in place (tbvh_host_viewer_continue): the (n,) bool array of the records that stepped on."""
+    mats = np.ascontiguousarray(materials, MATERIAL_DTYPE).reshape(-1)
+    n = rays.shape[0]
+    if rays.ctypes.data & 15 or not rays.flags.c_contiguous or not rays.flags.writeable:
+        raise ValueError("host_viewer_continue: rays must be a writeable, C-contiguous, 16-byte aligned array")
+    o = _aligned(out48, np.float32)
+    went = np.zeros(n, np.uint8)
+    check(lib.tbvh_host_viewer_continue(_ptr(mats), mats.size, int(n_textures), _ptr(rays) if n else None, rays.strides[0] if n else 64, _ptr(o) if n else None, n, _ptr(went), None),
+          "tbvh_host_viewer_continue")
+    return went.astype(bool)
+
+
+def host_viewer_shadow_rays(rays: np.ndarray, light_dir=None) -> np.ndarray:
+    r = _aligned(rays)
+    n = r.shape[0]
+    out = _aligned(np.zeros(n, RAY_DTYPE))
+    l, lp = _light_dir(light_dir)
+    check(lib.tbvh_host_viewer_shadow_rays(_ptr(r) if n else None, r.strides[0] if n else 64, n, lp, _ptr(out) if n else None), "tbvh_host_viewer_shadow_rays")
+    return out
+
+
+def host_viewer_light(mode: int, sky_pixels, rays: np.ndarray, out48: np.ndarray, occ=None, light_dir=None) -> np.ndarray:
+    """One colour per record on the CPU (tbvh_host_viewer_light): (n, 4) float32 ( r, g, b, 0 )."""
+    r = _aligned(rays)
+    n = r.shape[0]
+    o = _aligned(out48, np.float32)
+    rgb = _aligned(np.zeros((n, 4), np.float32))
+    p = None if sky_pixels is None else _sky_pixels(sky_pixels)
+    oc = None if occ is None else np.ascontiguousarray(occ, np.uint8)
+    l, lp = _light_dir(light_dir)
+    check(lib.tbvh_host_viewer_light(int(mode), None if p is None else _ptr(p), 0 if p is None else p.shape[1], 0 if p is None else p.shape[0], _ptr(r) if n else None,
+                                     r.strides[0] if n else 64, _ptr(o) if n else None, None if oc is None else _ptr(oc), n, lp, _ptr(rgb) if n else None), "tbvh_host_viewer_light")
+    return rgb
+
+
+def host_viewer_pack(rgb: np.ndarray) -> np.ndarray:
+    c = _aligned(rgb, np.float32).reshape(-1, 4)
+    out = np.zeros(c.shape[0], np.uint32)
+    check(lib.tbvh_host_viewer_pack(_ptr(c) if c.shape[0] else None, c.shape[0], _ptr(out) if c.shape[0] else None), "tbvh_host_viewer_pack")
+    return out
+
+
+def viewer_generate(ctx: Context, cam: Camera, d_rays: int, first: int = 0, n=None):
+    """tbvh_viewer_generate_device: asynchronous, 64 bytes per ray into d_rays."""
+    n = cam.width * cam.height - first if n is None else int(n)
+    check(lib.tbvh_viewer_generate_device(ctx._h, C.byref(cam), C.c_void_p(int(d_rays)), int(first), n), "tbvh_viewer_generate_device")
+
+
+def viewer_shadow_rays(ctx: Context, d_rays: int, n: int, d_shadow: int, light_dir=None, stride: int = 64):
+    l, lp = _light_dir(light_dir)
+    check(lib.tbvh_viewer_shadow_rays_device(ctx._h, C.c_void_p(int(d_rays)), int(stride), int(n), lp, C.c_void_p(int(d_shadow))), "tbvh_viewer_shadow_rays_device")
+
+
+def viewer_light(ctx: Context, mode: int, sky, d_rays: int, d_out48: int, n: int, d_rgb: int, d_occ: int = 0, light_dir=None, stride: int = 64, shading=None):
+    """tbvh_viewer_light_device: asynchronous; sky: a SkyDome or None."""
+    l, lp = _light_dir(light_dir)
+    check(lib.tbvh_viewer_light_device(ctx._h, int(mode), None if shading is None else shading._h, None if sky is None else sky._h, C.c_void_p(int(d_rays)), int(stride),
+                                       C.c_void_p(int(d_out48)), C.c_void_p(int(d_occ)) if d_occ else None, int(n), lp, C.c_void_p(int(d_rgb))), "tbvh_viewer_light_device")
+
+
+def viewer_pack(ctx: Context, d_rgb: int, n: int, d_pixels: int):
+    check(lib.tbvh_viewer_pack_device(ctx._h, C.c_void_p(int(d_rgb)), int(n), C.c_void_p(int(d_pixels))), "tbvh_viewer_pack_device")
+
+
+class SkyDome:
+    """A sky dome on the device (tbvh_sky_*): pixels as SkyDome::pixels, an (h, w, 3) float32 array, copied."""
+
+    def __init__(self, ctx: Context, pixels):
+        self.ctx = ctx
+        self._h = C.c_void_p()
+        p = _sky_pixels(pixels)
+        self.height, self.width = p.shape[:2]
+        check(lib.tbvh_sky_create(ctx._h, _ptr(p), self.width, self.height, 0, C.byref(self._h)), "tbvh_sky_create")
+
+    def SampleDevice(self, d_dirs: int, n: int, d_out: int) -> "SkyDome":
+        check(lib.tbvh_sky_sample_device(self._h, C.c_void_p(int(d_dirs)), int(n), C.c_void_p(int(d_out))), "tbvh_sky_sample_device")
+        return self
+
+    def free(self):
+        if self._h and self.ctx._h:   # (a closed context has freed its skies itself: tbvh_shutdown)
+            lib.tbvh_sky_free(self._h)
+        self._h = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+class Viewer:
+    """A frame of the reference's CPU viewers rendered on the device (tbvh_viewer_*): Render( scene, shading, sky, cam ) goes from the camera to pixels
+    without leaving it; Pixels() are the 0x00BBGGRR words, RGB() the colours before the clamp, Rays() the final ray records."""
+
+    def __init__(self, ctx: Context, width: int, height: int):
+        self.ctx = ctx
+        self.width, self.height = int(width), int(height)
+        self._h = C.c_void_p()
+        check(lib.tbvh_viewer_create(ctx._h, self.width, self.height, C.byref(self._h)), "tbvh_viewer_create")
+
+    def Render(self, scene: "_Scene", shading: Shading, sky, cam: Camera, mode: int = VIEWER_GLTF, light_dir=None, max_rounds: int = 0, stats: bool = True):
+        """tbvh_viewer_render.  stats: wait for the frame and return {"rays": per round, "shadow_rays", "frame_ms"}; False: asynchronous, returns None."""
+        p = _capi.ViewerParams()
+        p.mode, p.max_rounds, p.flags = int(mode), int(max_rounds), 0
+        if light_dir is not None:
+            p.light_dir[:] = [float(np.float32(x)) for x in light_dir]
+        st = _capi.ViewerStats()
+        check(lib.tbvh_viewer_render(self._h, scene._h, shading._h, None if sky is None else sky._h, C.byref(cam), C.byref(p), C.byref(st) if stats else None), "tbvh_viewer_render")
+        if not stats:
+            return None
+        return {"rays": [int(x) for x in st.rays], "shadow_rays": int(st.shadow_rays), "frame_ms": float(st.frame_ms)}
+
+    def Pixels(self) -> np.ndarray:
+        out = np.zeros((self.height, self.width), np.uint32)
+        check(lib.tbvh_viewer_read_pixels(self._h, _ptr(out)), "tbvh_viewer_read_pixels")
+        return out
+
+    def RGB(self) -> np.ndarray:
+        out = np.zeros((self.height, self.width, 4), np.float32)
+        check(lib.tbvh_viewer_read_rgb(self._h, _ptr(out)), "tbvh_viewer_read_rgb")
+        return out
+
+    def RaysDevice(self) -> int:
+        p = C.c_void_p()
+        check(lib.tbvh_viewer_rays(self._h, C.byref(p)), "tbvh_viewer_rays")
+        return p.value
+
+    def Rays(self) -> np.ndarray:
+        """the final ray records (a continued pixel's record is the one of its last round), copied back"""
+        out = np.zeros(self.width * self.height, RAY_DTYPE)
+        self.ctx.from_device(out, self.RaysDevice())
+        return out
+
+    def free(self):
+        if self._h and self.ctx._h:   # (a closed context has freed its viewers itself: tbvh_shutdown)
+            lib.tbvh_viewer_destroy(self._h)
+        self._h = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass

@@ -67,6 +67,14 @@ class WfStats(C.Structure):
     _fields_ = [("extend_rays", _u64 * 8), ("shadow_rays", _u64 * 8), ("frame_ms", C.c_float)]
 
 
+class ViewerParams(C.Structure):   # tbvh_viewer_params
+    _fields_ = [("mode", _u32), ("max_rounds", _u32), ("light_dir", C.c_float * 3), ("flags", _u32)]
+
+
+class ViewerStats(C.Structure):   # tbvh_viewer_stats
+    _fields_ = [("rays", _u64 * 8), ("shadow_rays", _u64), ("frame_ms", C.c_float)]
+
+
 SYMBOLS = {
     "tbvh_debug_wide_copy_bvh2": (_i, [_i, _vp, _u64, _vp, _u64, _vp, _u64, _u32, _vp, _u64, C.POINTER(_u64), _vp, _u64, C.POINTER(_u64)]),
     "tbvh_wavefront_create": (_i, [_vp, _u32, _u32, _pp]),
@@ -297,6 +305,28 @@ SYMBOLS = {
     "tbvh_host_pose_morph_normals": (_i, [_vp, _u64, _u32, _vp]),
     "tbvh_host_pose_update_fat_tris": (_i, [_vp, _u64, _vp, _vp, _u64, _vp, _i]),
     "tbvh_host_shade_hits": (_i, [_vp, _u32, _vp, _u32, _vp, _vp, _u32, _vp, _u64, _vp, _u64, _u32, _vp]),
+    # a viewer frame lit and finished on the device (capi_viewer.hip)
+    "tbvh_sky_create": (_i, [_vp, _vp, _u32, _u32, _i, _pp]),
+    "tbvh_sky_free": (None, [_vp]),
+    "tbvh_sky_sample_device": (_i, [_vp, _vp, _u64, _vp]),
+    "tbvh_host_sky_sample": (_i, [_vp, _u32, _u32, _vp, _u64, _vp]),
+    "tbvh_host_sky_prepare": (_i, [_vp, _u64, _vp, _i]),
+    "tbvh_viewer_generate_device": (_i, [_vp, C.POINTER(Camera), _vp, _u64, _u64]),
+    "tbvh_viewer_shadow_rays_device": (_i, [_vp, _vp, _u32, _u64, _vp, _vp]),
+    "tbvh_viewer_light_device": (_i, [_vp, _u32, _vp, _vp, _vp, _u32, _vp, _vp, _u64, _vp, _vp]),
+    "tbvh_viewer_pack_device": (_i, [_vp, _vp, _u64, _vp]),
+    "tbvh_host_viewer_generate": (_i, [C.POINTER(Camera), _vp, _u64, _u64]),
+    "tbvh_host_viewer_continue": (_i, [_vp, _u32, _u32, _vp, _u32, _vp, _u64, _vp, C.POINTER(_u64)]),
+    "tbvh_host_viewer_shadow_rays": (_i, [_vp, _u32, _u64, _vp, _vp]),
+    "tbvh_host_viewer_light": (_i, [_u32, _vp, _u32, _u32, _vp, _u32, _vp, _vp, _u64, _vp, _vp]),
+    "tbvh_host_viewer_pack": (_i, [_vp, _u64, _vp]),
+    "tbvh_viewer_create": (_i, [_vp, _u32, _u32, _pp]),
+    "tbvh_viewer_destroy": (None, [_vp]),
+    "tbvh_viewer_render": (_i, [_vp, _vp, _vp, _vp, C.POINTER(Camera), C.POINTER(ViewerParams), C.POINTER(ViewerStats)]),
+    "tbvh_viewer_read_pixels": (_i, [_vp, _vp]),
+    "tbvh_viewer_read_rgb": (_i, [_vp, _vp]),
+    "tbvh_viewer_rays": (_i, [_vp, _pp]),
+    "tbvh_debug_viewer_math": (_i, [_i, _vp, _vp, _u64, _vp]),
 }
 
 

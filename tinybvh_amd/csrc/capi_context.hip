@@ -169,6 +169,7 @@ void tbvh_shutdown(tbvh_context* c) {
     while (!c->scenes.empty()) tbvh_free_scene(c->scenes.back());
     freePosesOf(c);
     freeGraphsOf(c);
+    freeViewersOf(c);
     freeShadingsOf(c);
     freeOmmStagingOf(c);
     for (const tbvh_context::PinnedRange& r : c->pinned) hipHostFree(r.host);   // (memory of tbvh_pinned_malloc the caller never gave back goes with the context)

@@ -174,6 +174,8 @@ struct tbvh_context {
     std::vector<struct tbvh_pose*> poses;   // (capi_pose.hip) the poses made on this context: tbvh_shutdown frees those the caller has not
     std::vector<struct tbvh_scenegraph*> graphs;   // (capi_scenegraph.hip) likewise the scene graphs
     std::vector<struct tbvh_shading*> shadings;   // (capi_shade.hip) likewise the shading tables
+    std::vector<struct tbvh_sky*> skies;          // (capi_viewer.hip) likewise the sky domes ...
+    std::vector<struct tbvh_viewer*> viewers;     // ... and the viewer frames
     // (capi_omm.hip) the texture descriptors of a bake go up through a pinned area, in stream order, into ommDesc: a device-resident bake stays asynchronous;
     // the area is reused once the previous bake's copy has left it (ommEv)
     DevBuf<void> ommDesc;
@@ -495,4 +497,9 @@ void freeShadingsOf(tbvh_context* c);   // (capi_shade.hip) likewise
 tbvh_context* shadingContext(const struct tbvh_shading* sh);
 void shadingSlotRecords(const struct tbvh_shading* sh, uint32_t slot, float4** tris, uint64_t* nTris);
 void detachPosesFrom(tbvh_context* c, const struct tbvh_shading* sh);   // (capi_pose.hip) the table goes: the poses attached to it pose vertices only from here on
+// (capi_shade.hip) what a viewer frame needs of a shading table: the shading kernel over records on the device (nDev: their count in device memory, or null),
+// not timed, and the material table for the gltf alpha rule
+void shadingLaunch(const struct tbvh_shading* sh, tbvh_scene* s, const void* dRays, uint64_t n, uint32_t strideBytes, void* dOut48, const unsigned long long* nDev);
+void shadingMaterials(const struct tbvh_shading* sh, const struct tbvh::ShadeMat** mats, uint32_t* nMats, uint32_t* nTex, bool* anyColorTexture);
+void freeViewersOf(tbvh_context* c);   // (capi_viewer.hip) tbvh_shutdown: the sky domes and viewer frames still alive
 }  // namespace tbvh_capi

@@ -36,6 +36,7 @@ static_assert(sizeof(BlasDesc) % 4 == 0 && offsetof(BlasDesc, layout) % 4 == 0, 
 struct tbvh_shading {
     tbvh_context* ctx = nullptr;
     uint32_t nMats = 0, nTex = 0;
+    bool anyColorTex = false;                // some material may name a colour texture (device-resident materials: there are textures at all)
     DevBuf<ShadeMat> mats;
     DevBuf<ShadeTex> tex;                    // the descriptors, their texel pointers on the device
     std::vector<DevBuf<uint32_t>> texels;    // the texels that came from the host (device-resident ones stay the caller's)
@@ -102,6 +103,17 @@ void shadingSlotRecords(const tbvh_shading* sh, uint32_t slot, float4** tris, ui
     *tris = has ? sh->tris[slot].get() : nullptr;
     *nTris = has ? sh->slots[slot].nTris : 0;
 }
+void shadingLaunch(const tbvh_shading* sh, tbvh_scene* s, const void* dRays, uint64_t n, uint32_t strideBytes, void* dOut48, const unsigned long long* nDev) {
+    tbvh_context* c = sh->ctx;
+    if (s->isTlas)
+        launch_shade_hits(sh->tables(), s->tlas.instances, s->tlas.nInst, (const uint32_t*)((const char*)s->tlas.blasDesc.get() + offsetof(BlasDesc, layout)), sizeof(BlasDesc) / 4,
+                          (uint32_t)s->tlas.nBlas, dRays, n, strideBytes, dOut48, c->status, c->stream, nDev);
+    else
+        launch_shade_hits(sh->tables(), nullptr, 0, nullptr, 0, 0, dRays, n, strideBytes, dOut48, c->status, c->stream, nDev);
+}
+void shadingMaterials(const tbvh_shading* sh, const ShadeMat** mats, uint32_t* nMats, uint32_t* nTex, bool* anyColorTexture) {
+    *mats = sh->mats.get(); *nMats = sh->nMats; *nTex = sh->nTex; *anyColorTexture = sh->anyColorTex;
+}
 }  // namespace tbvh_capi
 
 extern "C" {
@@ -113,6 +125,9 @@ int tbvh_shading_create(tbvh_context* c, const tbvh_material* materials, uint32_
     tbvh_shading* sh = new (std::nothrow) tbvh_shading;
     if (!sh) return fail(TBVH_E_NOMEM, "tbvh_shading_create: out of host memory");
     sh->ctx = c; sh->nMats = nMats; sh->nTex = nTex;
+    sh->anyColorTex = onDevice && nTex;
+    if (!onDevice)
+        for (uint32_t k = 0; k < nMats; k++) sh->anyColorTex |= materials[k].color_texture != TBVH_OMM_NO_TEXTURE;
     std::vector<ShadeTex> desc(nTex);
     int r = 0;
     if (sh->mats.alloc(nMats) != hipSuccess || (nTex && sh->tex.alloc(nTex) != hipSuccess)) r = allocFail("tbvh_shading_create", nMats * sizeof(ShadeMat) + nTex * sizeof(ShadeTex));
@@ -206,11 +221,7 @@ int tbvh_shade_hits_device(tbvh_shading* sh, tbvh_scene* s, const void* dRays, u
     TBVH_ENTER(c);
     if (!n) return 0;
     HIP_TRY(timedBegin(c));
-    if (s->isTlas)
-        launch_shade_hits(sh->tables(), s->tlas.instances, s->tlas.nInst, (const uint32_t*)((const char*)s->tlas.blasDesc.get() + offsetof(BlasDesc, layout)), sizeof(BlasDesc) / 4,
-                          (uint32_t)s->tlas.nBlas, dRays, n, strideBytes, dOut48, c->status, c->stream);
-    else
-        launch_shade_hits(sh->tables(), nullptr, 0, nullptr, 0, 0, dRays, n, strideBytes, dOut48, c->status, c->stream);
+    shadingLaunch(sh, s, dRays, n, strideBytes, dOut48, nullptr);
     HIP_TRY(hipGetLastError());
     HIP_TRY(timedEnd(c));
     return 0;

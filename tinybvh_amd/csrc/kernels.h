@@ -197,9 +197,27 @@ void launch_omm_bake(const OmmSrc& src, uint32_t N, uint32_t* out, uint32_t* sta
 // out48 alpha is 0 step on; how many did is ADDED to *nContinued when that is not null)
 constexpr uint32_t kStatusShade = 256u;
 struct ShadeTables;
+// nDev: null, or the record count in device memory (a queue filled on the device: at most n records, the grid is sized for n)
 void launch_shade_hits(const ShadeTables& tb, const float4* instances, uint64_t nInst, const uint32_t* blasLayout, uint32_t blasStride, uint32_t nBlas, const void* rays,
-                       uint64_t n, uint32_t strideBytes, void* out48, uint32_t* status, hipStream_t s);
+                       uint64_t n, uint32_t strideBytes, void* out48, uint32_t* status, hipStream_t s, const unsigned long long* nDev = nullptr);
 void launch_shade_continue(void* rays, uint32_t strideBytes, const void* out48, uint64_t n, unsigned long long* nContinued, hipStream_t s);
+// (kernels_viewer.hip) a viewer frame lit and finished on the device, one pixel per lane through viewer.h: WorkerThread's row-major generator, SampleSky, the
+// alpha loop's queue (compact: round 0's masked records, stepped on, with their pixel; requeue: over the device-side count, masked again -> the next queue,
+// everything else scattered back to its pixel; cap = the frame's pixel count bounds every slot and pixel index), the foliage viewer's shadow rays (*nReal += the
+// rays that are not null), the light of either mode with its sky gather, and the pack to 0x00BBGGRR
+struct ViewerCam;
+struct ViewerSky;
+struct ShadeMat;
+void launch_viewer_generate(const ViewerCam& cam, void* rays64, uint64_t first, uint64_t n, hipStream_t s);
+void launch_sky_sample(const ViewerSky& sky, const void* dirs16, uint64_t n, void* out16, hipStream_t s);
+void launch_viewer_compact(const void* rays64, const void* out48, uint64_t n, const ShadeMat* mats, uint32_t nMats, uint32_t nTex, void* qRays64, uint32_t* qPix,
+                           unsigned long long* qCount, hipStream_t s);
+void launch_viewer_requeue(const void* qRays64, const uint32_t* qPix, const void* qOut48, const unsigned long long* qCount, uint64_t cap, const ShadeMat* mats, uint32_t nMats,
+                           uint32_t nTex, bool lastRound, void* nextRays64, uint32_t* nextPix, unsigned long long* nextCount, void* rays64, void* out48, hipStream_t s);
+void launch_viewer_shadow_rays(const void* rays, uint32_t strideBytes, uint64_t n, const float L[3], void* shadow64, unsigned long long* nReal, hipStream_t s);
+void launch_viewer_light(uint32_t mode, const ViewerSky& sky, const void* rays, uint32_t strideBytes, const void* out48, const uint8_t* occ, uint64_t n, const float L[3],
+                         void* rgb16, hipStream_t s);
+void launch_viewer_pack(const void* rgb16, uint64_t n, uint32_t* pixels, hipStream_t s);
 // (kernels_voxel_edit.hip) the batched VoxelSet::Set in deterministic passes over records { x, y, z, v } (voxel_edit.h), vox = the set's one allocation:
 //   mark   — work.cellFirst[g] = the smallest record index touching a grid cell g that has no brick; counters[0] = such cells, [1] = records out of range (skipped
 //            by every pass); the launch resets the work area first

@@ -8,7 +8,7 @@
 //                    ISA has 4 global_load_dwordx4, 4 dwordx3, 2 dwordx2, 4 dwords and — through the pointers read from the tables — 4 flat_load_dwordx4, 3 dwordx3, 2 dwords.  Output: three 16-byte stores per lane, consecutive
 //                    lanes 48 bytes apart.
 //                    Every index is compared with its table's size before it becomes an address (shade.h: shade_hit); a bad one sets kStatusShade
-//                    with a vector atomic, once per wave.
+//                    with a vector atomic, once per wave.  nDev (optional): the record count in device memory, for a queue filled on the device.
 //   k_shade_continue the alpha-continue step of the reference's renderers (tiny_bvh_gltf.cpp:140-150): a record whose shading came back with alpha == 0
 //                    steps on — O = ( O + D * t ) + D * 1e-4, every product and sum rounded, hit.t = 1e30, u v prim cleared — and is ready for the next
 //                    tbvh_intersect_device; every other record is left as it is (traced again it keeps its hit: nothing closer is recorded twice).
@@ -25,9 +25,9 @@ constexpr uint32_t kShadeBlock = 256;
 
 __global__ __launch_bounds__(kShadeBlock) void k_shade_hits(ShadeTables tb, const float4* __restrict__ instances, uint64_t nInst, const uint32_t* __restrict__ blasLayout,
                                                             uint32_t blasStride, uint32_t nBlas, const char* __restrict__ rays, uint64_t n, uint32_t strideBytes,
-                                                            float4* __restrict__ out, uint32_t* __restrict__ status) {
+                                                            float4* __restrict__ out, uint32_t* __restrict__ status, const unsigned long long* __restrict__ nDev) {
     const uint64_t i = (uint64_t)blockIdx.x * kShadeBlock + threadIdx.x;
-    const bool live = i < n;
+    const bool live = i < (nDev && *nDev < n ? *nDev : n);   // (a queue filled on the device: its count, never beyond the n the grid was sized for)
     float4 r1 = make_float4(0.f, 0.f, 0.f, 0.f), r2 = r1, r3 = make_float4(1e30f, 0.f, 0.f, 0.f);
     if (live) {
         const float4* rec = (const float4*)(rays + i * strideBytes);
@@ -72,11 +72,11 @@ __global__ __launch_bounds__(kShadeBlock) void k_shade_continue(char* __restrict
 }  // namespace
 
 void launch_shade_hits(const ShadeTables& tb, const float4* instances, uint64_t nInst, const uint32_t* blasLayout, uint32_t blasStride, uint32_t nBlas, const void* rays,
-                       uint64_t n, uint32_t strideBytes, void* out48, uint32_t* status, hipStream_t s) {
+                       uint64_t n, uint32_t strideBytes, void* out48, uint32_t* status, hipStream_t s, const unsigned long long* nDev) {
     if (!n) return;
     const dim3 grid((uint32_t)((n + kShadeBlock - 1) / kShadeBlock));
     hipLaunchKernelGGL(k_shade_hits, grid, dim3(kShadeBlock), 0, s, tb, instances, nInst, blasLayout, blasStride, nBlas, (const char*)rays, n, strideBytes, (float4*)out48,
-                       status);
+                       status, nDev);
 }
 
 void launch_shade_continue(void* rays, uint32_t strideBytes, const void* out48, uint64_t n, unsigned long long* nContinued, hipStream_t s) {
