@@ -2,13 +2,13 @@
 (compiled per session into a pytest temp dir), the box sets, the golden directory (DESIGN.md par. 20).  The comparisons are sahbuild_lib's."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
-import pytest
 
+import native_build as nb
 import tinybvh_amd as tb
-from sahbuild_lib import (assert_same_tree, have_reference, leaf_sets, node_digest, reference_dir)  # noqa: F401  (re-exported)
+from native_build import _i, _u32, _u64, _vp
+from sahbuild_lib import assert_same_tree, leaf_sets, node_digest  # noqa: F401  (re-exported)
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 GOLDEN = os.path.join(HERE, "golden", "boxbuild")
@@ -16,7 +16,6 @@ MIXED_SIZES = (1, 2, 3, 63, 64, 65, 1023, 1024, 1025)
 SETS = ("LATTICE1000", "IDENT700", "GEO256", "MIXED1000", "FAR", "FLAT") + tuple(f"MIXED{n}" for n in MIXED_SIZES)
 TLAS_SIZES = (1, 2, 3, 64, 65, 1000)
 MAX_NODE_BYTES = 24 << 10   # a fixture keeps the node bytes of a small tree; of a larger one their count and SHA-256
-_vp, _u32, _u64, _i = C.c_void_p, C.c_uint32, C.c_uint64, C.c_int
 _cache = {}
 
 
@@ -129,20 +128,11 @@ class RefBox:
 
 def compile_ref_shim(d):
     """the reference with oracle/Makefile's flags; None when the reference is absent"""
-    if not have_reference():
-        return None
-    so = os.path.join(str(d), "libboxbuild_ref.so")
-    subprocess.check_call(["g++", "-std=c++20", "-O3", "-mavx2", "-mfma", "-fPIC", "-shared", "-w", "-I" + reference_dir(),
-                           os.path.join(HERE, "boxbuild_ref_shim.cpp"), "-o", so, "-lpthread"])
-    return RefBox(so)
+    so = nb.compile_ref_shim(d, "boxbuild_ref_shim.cpp")
+    return so and RefBox(so)
 
 
-@pytest.fixture(scope="session")
-def box_ref(tmp_path_factory):
-    r = compile_ref_shim(tmp_path_factory.mktemp("boxbuild_ref"))
-    if r is None:
-        pytest.skip("the reference checkout (TBVH_REFERENCE) is absent")
-    return r
+box_ref = nb.ref_fixture("boxbuild_ref", compile_ref_shim)
 
 
 def al_leaf_sets(nodes64, idx):

@@ -2,29 +2,16 @@
 tests/custom_ref_shim.cpp, both compiled per session into a pytest temp dir, sphere sets, rays and TLAS scenes (DESIGN.md par. 12)."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
-import pytest
 
+import native_build as nb
 import tinybvh_amd as tb
+from native_build import _i, _p, _u32, _u64, _vp
 from tinybvh_amd import scenes
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 GOLDEN = os.path.join(HERE, "golden", "custom")
-_vp, _u64, _i, _u32 = C.c_void_p, C.c_uint64, C.c_int, C.c_uint32
-
-
-def _p(a):
-    return C.c_void_p(a.ctypes.data)
-
-
-def reference_dir():
-    return os.environ.get("TBVH_REFERENCE", "/root/reference")
-
-
-def have_reference():
-    return os.path.isfile(os.path.join(reference_dir(), "tiny_bvh.h"))
 
 
 class _BlasDesc(C.Structure):
@@ -177,32 +164,17 @@ class RefCustom:
 
 
 def compile_oracle(d):
-    so = os.path.join(str(d), "liboracle_custom.so")
-    subprocess.check_call(["cc", "-O2", "-std=c11", "-ffp-contract=off", "-fPIC", "-shared", os.path.join(HERE, "oracle_custom.c"), "-o", so, "-lm"])
-    return CustomOracle(so)
+    return CustomOracle(nb.compile_c_oracle(d, "oracle_custom"))
 
 
 def compile_ref_shim(d):
     """the reference with oracle/Makefile's flags; None when the reference is absent"""
-    if not have_reference():
-        return None
-    so = os.path.join(str(d), "libcustom_ref.so")
-    subprocess.check_call(["g++", "-std=c++20", "-O3", "-mavx2", "-mfma", "-fPIC", "-shared", "-w", "-I" + reference_dir(),
-                           os.path.join(HERE, "custom_ref_shim.cpp"), "-o", so, "-lpthread"])
-    return RefCustom(so)
+    so = nb.compile_ref_shim(d, "custom_ref_shim.cpp")
+    return so and RefCustom(so)
 
 
-@pytest.fixture(scope="session")
-def cu_oracle(tmp_path_factory):
-    return compile_oracle(tmp_path_factory.mktemp("oracle_custom"))
-
-
-@pytest.fixture(scope="session")
-def cu_ref(tmp_path_factory):
-    r = compile_ref_shim(tmp_path_factory.mktemp("custom_ref"))
-    if r is None:
-        pytest.skip("the reference checkout (TBVH_REFERENCE) is absent")
-    return r
+cu_oracle = nb.oracle_fixture("oracle_custom", compile_oracle)
+cu_ref = nb.ref_fixture("custom_ref", compile_ref_shim)
 
 
 # ---- sphere sets ------------------------------------------------------------------------------------------------------------------------

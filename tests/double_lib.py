@@ -1,22 +1,14 @@
 """Shared pieces of the BVH_Double tests: the restated oracle (tests/oracle_double.c, compiled per session into a pytest temp dir
-with -ffp-contract=off), scenes promoted to double and rays built in double."""
+without contraction), scenes promoted to double and rays built in double."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
-import pytest
 
+import native_build as nb
 import tinybvh_amd as tb
+from native_build import _i, _p, _u64, _vp
 from tinybvh_amd import rays as R
 from tinybvh_amd import scenes
-
-HERE = os.path.dirname(os.path.abspath(__file__))
-_vp, _u64, _i = C.c_void_p, C.c_uint64, C.c_int
-
-
-def _p(a):
-    return C.c_void_p(a.ctypes.data)
 
 
 class OracleDouble:
@@ -71,12 +63,11 @@ class OracleDouble:
         return out
 
 
-@pytest.fixture(scope="session")
-def odbl(tmp_path_factory):
-    d = tmp_path_factory.mktemp("oracle_double")
-    so = str(d / "liboracle_double.so")
-    subprocess.check_call(["cc", "-O2", "-ffp-contract=off", "-fPIC", "-shared", os.path.join(HERE, "oracle_double.c"), "-o", so, "-lm"])
-    return OracleDouble(so)
+def compile_oracle(d):
+    return OracleDouble(nb.compile_c_oracle(d, "oracle_double", extra=()))   # (the one restatement built at the compiler's default language level)
+
+
+odbl = nb.oracle_fixture("oracle_double", compile_oracle)
 
 
 # ---- scenes and rays in double -----------------------------------------------------------------------------------------------------

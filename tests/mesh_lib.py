@@ -2,30 +2,17 @@
 pytest temp dir), the golden directory, and the one mesh, ray set, sphere set and moved frame the goldens are made of (DESIGN.md par. 13)."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
-import pytest
 
+import native_build as nb
 import tinybvh_amd as tb
+from native_build import _i, _p, _u32, _u64, _vp
 from tinybvh_amd import rays as R
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 GOLDEN = os.path.join(HERE, "golden", "mesh")
 GOLDEN_STEP = 24   # every 24th triangle of the bunny: the golden file stays under 1 MB
-_vp, _u32, _u64, _i = C.c_void_p, C.c_uint32, C.c_uint64, C.c_int
-
-
-def _p(a):
-    return C.c_void_p(a.ctypes.data)
-
-
-def reference_dir():
-    return os.environ.get("TBVH_REFERENCE", "/root/reference")
-
-
-def have_reference():
-    return os.path.exists(os.path.join(reference_dir(), "tiny_bvh.h"))
 
 
 class RefMesh:
@@ -86,20 +73,11 @@ class RefMesh:
 
 def compile_ref_shim(d):
     """the reference with oracle/Makefile's flags; None when the reference is absent"""
-    if not have_reference():
-        return None
-    so = os.path.join(str(d), "libmesh_ref.so")
-    subprocess.check_call(["g++", "-std=c++20", "-O3", "-mavx2", "-mfma", "-fPIC", "-shared", "-w", "-I" + reference_dir(),
-                           os.path.join(HERE, "mesh_ref_shim.cpp"), "-o", so, "-lpthread"])
-    return RefMesh(so)
+    so = nb.compile_ref_shim(d, "mesh_ref_shim.cpp")
+    return so and RefMesh(so)
 
 
-@pytest.fixture(scope="session")
-def mesh_ref(tmp_path_factory):
-    r = compile_ref_shim(tmp_path_factory.mktemp("mesh_ref"))
-    if r is None:
-        pytest.skip("the reference checkout (TBVH_REFERENCE) is absent")
-    return r
+mesh_ref = nb.ref_fixture("mesh_ref", compile_ref_shim)
 
 
 # ---- the golden case ------------------------------------------------------------------------------------------------------------------

@@ -1,12 +1,14 @@
 """Shared by the opacity-micromap bake tests (test_omm_host.py, test_omm_gpu.py), tools/make_omm_golden.py and tools/omm_bake_bench.py (so: NumPy and the
-compilers only, no test framework and no GPU library; the tests' fixtures are in tests/omm_fixtures.py): deterministic alpha textures and UV meshes, the
+compilers only, no GPU library): deterministic alpha textures and UV meshes, the
 plain-C restatement of CreateOpacityMicroMap (tests/oracle_omm.c), the real reference behind tests/omm_ref_shim.cpp (compiled per session into a pytest temp
-dir when the reference checkout is present), and the goldens under tests/golden/omm (DESIGN.md par. 15)."""
+dir when the reference checkout is present), the two session fixtures over them, and the goldens under tests/golden/omm (DESIGN.md par. 15)."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
+
+import native_build as nb
+from native_build import _p, _u32
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 GOLDEN = os.path.join(HERE, "golden", "omm")
@@ -15,19 +17,6 @@ GOLDEN_TRIS = 301
 NO_TEXTURE = 0xFFFFFFFF
 ALPHAS = np.array([0, 1, 2, 3, 128, 255], np.uint32)   # the reference's test is alpha > 2: hit from both sides
 ALL_N = (1, 2, 4, 8, 32, 64)
-_vp, _u32 = C.c_void_p, C.c_uint32
-
-
-def _p(a):
-    return C.c_void_p(a.ctypes.data)
-
-
-def reference_dir():
-    return os.environ.get("TBVH_REFERENCE", "/root/reference")
-
-
-def have_reference():
-    return os.path.exists(os.path.join(reference_dir(), "tiny_bvh.h")) and os.path.exists(os.path.join(reference_dir(), "tiny_scene.h"))
 
 
 def words_per_tri(N):
@@ -70,28 +59,17 @@ class _BakeFns:
 
 
 def compile_oracle(d):
-    so = os.path.join(str(d), "liboracle_omm.so")
-    subprocess.check_call(["cc", "-O2", "-std=c11", "-ffp-contract=off", "-fPIC", "-shared", os.path.join(HERE, "oracle_omm.c"), "-o", so, "-lm"])
-    return _BakeFns(so, "oorc")
+    return _BakeFns(nb.compile_c_oracle(d, "oracle_omm"), "oorc")
 
 
 def compile_ref_shim(d):
-    """The real CreateOpacityMicroMap with oracle/Makefile's flags; None when the reference is absent.  tiny_scene.h has a bare `#elif` that g++ refuses: a
-    temp copy with that one directive turned into `#else` goes first on the include path (nothing of it is kept) — as tests/pose_lib.py does it."""
-    if not have_reference():
-        return None
-    d = str(d)
-    with open(os.path.join(reference_dir(), "tiny_scene.h"), encoding="utf-8", errors="surrogateescape") as f:
-        lines = f.read().split("\n")
-    for i, line in enumerate(lines):
-        if line.strip() == "#elif":
-            lines[i] = "#else"
-    with open(os.path.join(d, "tiny_scene.h"), "w", encoding="utf-8", errors="surrogateescape") as f:
-        f.write("\n".join(lines))
-    so = os.path.join(d, "libomm_ref.so")
-    subprocess.check_call(["g++", "-std=c++20", "-O3", "-mavx2", "-mfma", "-fPIC", "-shared", "-w", "-I" + d, "-I" + reference_dir(),
-                           "-I" + os.path.join(reference_dir(), "external"), os.path.join(HERE, "omm_ref_shim.cpp"), "-o", so, "-lpthread"])
-    return _BakeFns(so, "oref")
+    """The real CreateOpacityMicroMap with oracle/Makefile's flags; None when the reference is absent"""
+    so = nb.compile_ref_shim(d, "omm_ref_shim.cpp", scene_header=True, need=("tiny_bvh.h", "tiny_scene.h"))
+    return so and _BakeFns(so, "oref")
+
+
+omm_oracle = nb.oracle_fixture("oracle_omm", compile_oracle)
+omm_ref = nb.ref_fixture("omm_ref", compile_ref_shim)
 
 
 # ---- generators ----------------------------------------------------------------------------------------------------------------------------

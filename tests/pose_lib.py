@@ -1,31 +1,20 @@
 """Shared by the pose tests (test_pose_host.py, test_pose_gpu.py), tools/make_pose_golden.py and tools/pose_anim_bench.py (so: NumPy and the compilers only, no
-test framework and no GPU library; the tests' fixtures are in tests/pose_fixtures.py): deterministic skinned / morphed versions of the committed
+GPU library): deterministic skinned / morphed versions of the committed
 bunny, the plain-C restatement of Mesh::SetPose (tests/oracle_pose.c), the real reference behind tests/pose_ref_shim.cpp (compiled per session into a
-pytest temp dir when the reference checkout is present), and the goldens under tests/golden/pose (DESIGN.md par. 14)."""
+pytest temp dir when the reference checkout is present), the two session fixtures over them, and the goldens under tests/golden/pose (DESIGN.md par. 14)."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
+
+import native_build as nb
+from native_build import _p, _u32, _vp
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 GOLDEN = os.path.join(HERE, "golden", "pose")
 GOLDEN_STEP = 16        # every 16th triangle of the bunny
 N_JOINTS = 24
 SMALL = 3 * 313         # the second frame of a golden is kept for this many vertices only (file size)
-_vp, _u32 = C.c_void_p, C.c_uint32
-
-
-def _p(a):
-    return C.c_void_p(a.ctypes.data)
-
-
-def reference_dir():
-    return os.environ.get("TBVH_REFERENCE", "/root/reference")
-
-
-def have_reference():
-    return os.path.exists(os.path.join(reference_dir(), "tiny_bvh.h"))
 
 
 def bunny(step=8):
@@ -82,28 +71,17 @@ class _PoseFns:
 
 
 def compile_oracle(d):
-    so = os.path.join(str(d), "liboracle_pose.so")
-    subprocess.check_call(["cc", "-O2", "-std=c11", "-ffp-contract=off", "-fPIC", "-shared", os.path.join(HERE, "oracle_pose.c"), "-o", so, "-lm"])
-    return _PoseFns(so, "porc")
+    return _PoseFns(nb.compile_c_oracle(d, "oracle_pose"), "porc")
 
 
 def compile_ref_shim(d):
-    """The real Mesh::SetPose with oracle/Makefile's flags; None when the reference is absent.  tiny_scene.h has a bare `#elif` that g++ refuses: a
-    temp copy with that one directive turned into `#else` goes first on the include path (nothing of it is kept)."""
-    if not have_reference() or not os.path.exists(os.path.join(reference_dir(), "tiny_scene.h")):
-        return None
-    d = str(d)
-    with open(os.path.join(reference_dir(), "tiny_scene.h"), encoding="utf-8", errors="surrogateescape") as f:
-        lines = f.read().split("\n")
-    for i, line in enumerate(lines):
-        if line.strip() == "#elif":
-            lines[i] = "#else"
-    with open(os.path.join(d, "tiny_scene.h"), "w", encoding="utf-8", errors="surrogateescape") as f:
-        f.write("\n".join(lines))
-    so = os.path.join(d, "libpose_ref.so")
-    subprocess.check_call(["g++", "-std=c++20", "-O3", "-mavx2", "-mfma", "-fPIC", "-shared", "-w", "-I" + d, "-I" + reference_dir(),
-                           "-I" + os.path.join(reference_dir(), "external"), os.path.join(HERE, "pose_ref_shim.cpp"), "-o", so, "-lpthread"])
-    return _PoseFns(so, "pref")
+    """The real Mesh::SetPose with oracle/Makefile's flags; None when the reference is absent"""
+    so = nb.compile_ref_shim(d, "pose_ref_shim.cpp", scene_header=True, need=("tiny_bvh.h", "tiny_scene.h"))
+    return so and _PoseFns(so, "pref")
+
+
+pose_oracle = nb.oracle_fixture("oracle_pose", compile_oracle)
+pose_ref = nb.ref_fixture("pose_ref", compile_ref_shim)
 
 
 # ---- generators ----------------------------------------------------------------------------------------------------------------------------

@@ -6,7 +6,7 @@ constructor) — and NOT from the kernels.  Plain numpy; nothing here needs a GP
 Each generator comes twice:
 
   *_f32   the documented operations, one numpy float32 operation per C operation, in C's evaluation order (a + b + c = (a + b) + c; no
-          fused sums, no linalg.norm).  The library is built with -ffp-contract=off and HIP's correctly rounded divide and square root,
+          fused sums, no linalg.norm).  The library is built without contraction and with HIP's correctly rounded divide and square root,
           so the device should give these bits.
   *_f64   the same formulas in float64 on the float32 inputs, with everything integer (pixel mapping, hash, xorshift draws) exact and
           the draw itself — float32(draw) * float32(2.3283064365387e-10) — taken over unchanged.  It also returns, per component, a

@@ -3,26 +3,17 @@ per session into a pytest temp dir), the scenes, the golden directory and the co
 import ctypes as C
 import hashlib
 import os
-import subprocess
 
 import numpy as np
-import pytest
 
+import native_build as nb
+from native_build import _i, _u32, _u64, _vp
 from tinybvh_amd import scenes
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 GOLDEN = os.path.join(HERE, "golden", "sahbuild")
 GOLDEN_SCENES = ("SOUP500", "FLAT", "QUADS", "STREET45K")
-_vp, _u32, _u64, _i = C.c_void_p, C.c_uint32, C.c_uint64, C.c_int
 _cache = {}
-
-
-def reference_dir():
-    return os.environ.get("TBVH_REFERENCE", "/root/reference")
-
-
-def have_reference():
-    return os.path.exists(os.path.join(reference_dir(), "tiny_bvh.h"))
 
 
 def quad_grid(n=32):
@@ -117,20 +108,11 @@ class RefSah:
 
 def compile_ref_shim(d):
     """the reference with oracle/Makefile's flags; None when the reference is absent"""
-    if not have_reference():
-        return None
-    so = os.path.join(str(d), "libsahbuild_ref.so")
-    subprocess.check_call(["g++", "-std=c++20", "-O3", "-mavx2", "-mfma", "-fPIC", "-shared", "-w", "-I" + reference_dir(),
-                           os.path.join(HERE, "sahbuild_ref_shim.cpp"), "-o", so, "-lpthread"])
-    return RefSah(so)
+    so = nb.compile_ref_shim(d, "sahbuild_ref_shim.cpp")
+    return so and RefSah(so)
 
 
-@pytest.fixture(scope="session")
-def sah_ref(tmp_path_factory):
-    r = compile_ref_shim(tmp_path_factory.mktemp("sahbuild_ref"))
-    if r is None:
-        pytest.skip("the reference checkout (TBVH_REFERENCE) is absent")
-    return r
+sah_ref = nb.ref_fixture("sahbuild_ref", compile_ref_shim)
 
 
 def leaf_sets(nodes, prim_idx):

@@ -3,11 +3,11 @@ oracle/_ref, the indexed form behind tests/sbvhbuild_ref_shim.cpp, compiled per 
 comparisons (DESIGN.md par. 19)."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
-import pytest
 
+import native_build as nb
+from native_build import _i, _u32, _u64, _vp
 from tinybvh_amd import scenes
 import sahbuild_lib as sl
 
@@ -21,7 +21,6 @@ SOUPS = [f"SOUP{n}" for n in (1, 2, 3, 5, 9, 63, 64, 65, 255, 256, 257, 1023, 10
 REFERENCE_SIZES = {"SOUP500": (972, 501), "S": (5192, 3013), "FAR": (3612, 2025), "FLAT": (802, 550), "TWO": (1170, 600), "QUADS": (2048, 2048),
                    "LATTICE": (2000, 1000), "POINT": (2, 700), "LONG300": (644, 366), "LONG2000": (3944, 2459), "LONGFLAT": (2308, 2074),
                    "BLOB20K": (21086, 19748), "ATRIUMROT30K": (38796, 30930), "STREET45K": (70888, 45000), "STREETROT262K": (301864, 281157)}
-_vp, _u32, _u64, _i = C.c_void_p, C.c_uint32, C.c_uint64, C.c_int
 _cache = {}
 
 
@@ -97,20 +96,11 @@ class RefSbvhIndexed:
 
 def compile_ref_shim(d):
     """the reference with oracle/Makefile's flags; None when the reference is absent"""
-    if not sl.have_reference():
-        return None
-    so = os.path.join(str(d), "libsbvhbuild_ref.so")
-    subprocess.check_call(["g++", "-std=c++20", "-O3", "-mavx2", "-mfma", "-fPIC", "-shared", "-w", "-I" + sl.reference_dir(),
-                           os.path.join(HERE, "sbvhbuild_ref_shim.cpp"), "-o", so, "-lpthread"])
-    return RefSbvhIndexed(so)
+    so = nb.compile_ref_shim(d, "sbvhbuild_ref_shim.cpp")
+    return so and RefSbvhIndexed(so)
 
 
-@pytest.fixture(scope="session")
-def sbvh_ref_indexed(tmp_path_factory):
-    r = compile_ref_shim(tmp_path_factory.mktemp("sbvhbuild_ref"))
-    if r is None:
-        pytest.skip("the reference checkout (TBVH_REFERENCE) is absent")
-    return r
+sbvh_ref_indexed = nb.ref_fixture("sbvhbuild_ref", compile_ref_shim)
 
 
 def assert_same_tree(got, want, what=""):

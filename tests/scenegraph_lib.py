@@ -1,12 +1,13 @@
 """Shared by the scene graph tests (test_scenegraph_host.py, test_scenegraph_gpu.py) and tools/make_scenegraph_golden.py (so: NumPy, the package's ctypes
-layer and the compilers only; no test framework, no GPU): a builder for scene graph descriptors, the seeded synthetic graph, the scripted frame sequence,
+layer and the compilers only; no GPU): a builder for scene graph descriptors, the seeded synthetic graph, the scripted frame sequence,
 the real reference behind tests/scenegraph_ref_shim.cpp (compiled per session into a temp dir when the reference checkout is present), the slerp tolerance of
 tests/oracle_scenegraph.c, and the goldens under tests/golden/graph (DESIGN.md par. 17)."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
+
+import native_build as nb
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
@@ -16,14 +17,6 @@ VEC3, QUAT, FLOAT = 0, 1, 2
 TRS, LOCAL, COMBINED, CHANNEL_T, CHANNEL_K, INSTANCES, JOINTS, WEIGHTS, STALE, TRIG = range(10)
 WHATS = {"trs": TRS, "local": LOCAL, "combined": COMBINED, "t": CHANNEL_T, "k": CHANNEL_K, "inst": INSTANCES, "joints": JOINTS, "weights": WEIGHTS}
 IDENT = np.eye(4, dtype=np.float32).reshape(16)
-
-
-def reference_dir():
-    return os.environ.get("TBVH_REFERENCE", "/root/reference")
-
-
-def have_reference():
-    return os.path.exists(os.path.join(reference_dir(), "tiny_bvh.h")) and os.path.exists(os.path.join(reference_dir(), "tiny_scene.h"))
 
 
 # ---- descriptors ---------------------------------------------------------------------------------------------------------------------------
@@ -321,21 +314,11 @@ class RefGraph:
 
 
 def compile_ref_shim(d):
-    """the real tiny_scene.h with oracle/Makefile's flags; None when the reference is absent.  The `#elif` -> `#else` temp copy is tests/pose_lib.py's."""
-    if not have_reference():
+    """the real tiny_scene.h with oracle/Makefile's flags (and its private members open to the shim); None when the reference is absent"""
+    so = nb.compile_ref_shim(d, "scenegraph_ref_shim.cpp", extra=("-fno-access-control", "-I" + os.path.join(ROOT, "include")), scene_header=True,
+                             need=("tiny_bvh.h", "tiny_scene.h"))
+    if so is None:
         return None
-    d = str(d)
-    with open(os.path.join(reference_dir(), "tiny_scene.h"), encoding="utf-8", errors="surrogateescape") as f:
-        lines = f.read().split("\n")
-    for i, line in enumerate(lines):
-        if line.strip() == "#elif":
-            lines[i] = "#else"
-    with open(os.path.join(d, "tiny_scene.h"), "w", encoding="utf-8", errors="surrogateescape") as f:
-        f.write("\n".join(lines))
-    so = os.path.join(d, "libscenegraph_ref.so")
-    subprocess.check_call(["g++", "-std=c++20", "-O3", "-mavx2", "-mfma", "-fno-access-control", "-fPIC", "-shared", "-w", "-I" + d, "-I" + reference_dir(),
-                           "-I" + os.path.join(reference_dir(), "external"), "-I" + os.path.join(ROOT, "include"), os.path.join(HERE, "scenegraph_ref_shim.cpp"),
-                           "-o", so, "-lpthread"])
     lib = C.CDLL(so)
     for name in ("sgref_local_from_trs", "sgref_advance", "sgref_advance_animation", "sgref_update_nodes", "sgref_set_time", "sgref_reset", "sgref_set_local", "sgref_mul", "sgref_invert", "sgref_slerp"):
         getattr(lib, name).restype = None
@@ -438,10 +421,7 @@ TRIG_U_SOURCE = "assumed: no HIP math API accuracy table or OCML documentation i
 
 
 def compile_oracle(d):
-    so = os.path.join(str(d), "liboracle_scenegraph.so")
-    subprocess.check_call(["cc", "-O2", "-std=c11", "-ffp-contract=off", "-fPIC", "-shared", "-I" + os.path.join(ROOT, "include"), os.path.join(HERE, "oracle_scenegraph.c"),
-                           "-o", so, "-lm"])
-    lib = C.CDLL(so)
+    lib = C.CDLL(nb.compile_c_oracle(d, "oracle_scenegraph", extra=("-std=c11", "-I" + os.path.join(ROOT, "include"))))
     lib.sgorc_slerp.restype = C.c_int
     lib.sgorc_slerp_spread.restype = C.c_float
     lib.sgorc_create.restype = C.c_void_p
@@ -529,7 +509,7 @@ DRONE_DURATION = 25.0
 
 
 def drone_path():
-    return os.path.join(reference_dir(), "testdata", "drone", "scene.gltf")
+    return os.path.join(nb.reference_dir(), "testdata", "drone", "scene.gltf")
 
 
 def search_frames(d, candidates):

@@ -8,7 +8,10 @@ import functools
 import os
 
 import numpy as np
+import pytest
 
+import native_build as nb
+import shade_lib as _L
 import tinybvh_amd as tb
 from custom_lib import bunny_verts
 from shade_lib import FATTRI_DTYPE, MATERIAL_DTYPE, NO_TEXTURE, REF_OUT_OF_BOUNDS, TU_INTEGER, WRAPPED
@@ -241,39 +244,24 @@ def host_posed(case, kind, frame):
     return tb.host_pose_fat_tris(fat, v, n, indices=case["indices"], skin=True)
 
 
-# ---- session fixtures (pytest is imported only when a test module asks for them) -----------------------------------------------------------------
-try:
-    import pytest
-except ImportError:   # tools/ import this module without a test framework
-    pytest = None
+# ---- session fixtures ----------------------------------------------------------------------------------------------------------------------------
+shade_oracle = nb.oracle_fixture("oracle_shade", _L.compile_oracle)
+shade_ref = nb.ref_fixture("shade_ref", _L.compile_ref_shim)
 
-if pytest is not None:
-    import shade_lib as _L
 
-    @pytest.fixture(scope="session")
-    def shade_oracle(tmp_path_factory):
-        return _L.compile_oracle(tmp_path_factory.mktemp("oracle_shade"))
-
-    @pytest.fixture(scope="session")
-    def shade_ref(tmp_path_factory):
-        r = _L.compile_ref_shim(tmp_path_factory.mktemp("shade_ref"))
-        if r is None:
-            pytest.skip("the reference checkout (TBVH_REFERENCE) is absent")
-        return r
-
-    @pytest.fixture(scope="session")
-    def shade_sets(shade_oracle, oracle):
-        """{name: (records, instances, the restatement's (n, 12) records, its flags)} for the traced and the synthetic set, computed once and never changed"""
-        sc = scene()
-        traced, inst = traced_on_the_cpu(oracle)
-        syn = sc.synthetic_records()
-        sets = {}
-        for name, r in (("traced", traced), ("synthetic", syn)):
-            out, flags = shade_oracle.shade(sc.materials, sc.textures, sc.fat, r, inst)
-            for a in (r, out, flags):
-                a.flags.writeable = False
-            sets[name] = (r, inst, out, flags)
-        assert_classes_present(syn, sets["synthetic"][2], sets["synthetic"][3])
-        hit = traced["t"] < 1e30
-        assert traced.shape[0] == CAMERA_SIDE ** 2 and hit.sum() > 300 and (~hit).sum() > 300 and set(np.unique(traced["inst"][hit])) == {0, 1, 2, 3, 4}
-        return sets
+@pytest.fixture(scope="session")
+def shade_sets(shade_oracle, oracle):
+    """{name: (records, instances, the restatement's (n, 12) records, its flags)} for the traced and the synthetic set, computed once and never changed"""
+    sc = scene()
+    traced, inst = traced_on_the_cpu(oracle)
+    syn = sc.synthetic_records()
+    sets = {}
+    for name, r in (("traced", traced), ("synthetic", syn)):
+        out, flags = shade_oracle.shade(sc.materials, sc.textures, sc.fat, r, inst)
+        for a in (r, out, flags):
+            a.flags.writeable = False
+        sets[name] = (r, inst, out, flags)
+    assert_classes_present(syn, sets["synthetic"][2], sets["synthetic"][3])
+    hit = traced["t"] < 1e30
+    assert traced.shape[0] == CAMERA_SIDE ** 2 and hit.sum() > 300 and (~hit).sum() > 300 and set(np.unique(traced["inst"][hit])) == {0, 1, 2, 3, 4}
+    return sets

@@ -1,19 +1,20 @@
 """Shared by the shading tests (test_shade_host.py, test_shade_gpu.py), tools/make_shade_golden.py and tools/shade_bench.py (so: NumPy and the compilers only, no
-test framework and no GPU library; the tests' scene is in tests/shade_fixtures.py): the plain-C restatement of GetShadingData (tests/oracle_shade.c), the real
+GPU library; the tests' scene is in tests/shade_fixtures.py): the plain-C restatement of GetShadingData (tests/oracle_shade.c), the real
 reference behind tests/shade_ref_shim.cpp (compiled per session into a pytest temp dir when the reference checkout is present), and the goldens under
 tests/golden/shade (DESIGN.md par. 16)."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
+
+import native_build as nb
+from native_build import _p, _u32, _u64, _vp
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 GOLDEN = os.path.join(HERE, "golden", "shade")
 NO_TEXTURE = 0xFFFFFFFF
 # oracle_shade.c's flags
 WRAPPED, REF_OUT_OF_BOUNDS, NO_SURFACE, BAD_INDEX, TU_INTEGER = 1, 2, 4, 8, 16
-_vp, _u32, _u64 = C.c_void_p, C.c_uint32, C.c_uint64
 
 FATTRI_DTYPE = np.dtype([
     ("u0", "<f4"), ("u1", "<f4"), ("u2", "<f4"), ("ltriIdx", "<i4"),
@@ -29,18 +30,6 @@ assert FATTRI_DTYPE.itemsize == 192 and MATERIAL_DTYPE.itemsize == 20
 
 class _Tex(C.Structure):
     _fields_ = [("texels", C.c_void_p), ("width", C.c_uint32), ("height", C.c_uint32)]
-
-
-def _p(a):
-    return C.c_void_p(a.ctypes.data)
-
-
-def reference_dir():
-    return os.environ.get("TBVH_REFERENCE", "/root/reference")
-
-
-def have_reference():
-    return all(os.path.exists(os.path.join(reference_dir(), f)) for f in ("tiny_bvh.h", "tiny_scene.h", "tiny_bvh_foliage.cpp"))
 
 
 def _slots(fat_tris):
@@ -119,28 +108,13 @@ class RealReference:
 
 
 def compile_oracle(d):
-    so = os.path.join(str(d), "liboracle_shade.so")
-    subprocess.check_call(["cc", "-O2", "-std=c11", "-ffp-contract=off", "-fPIC", "-shared", os.path.join(HERE, "oracle_shade.c"), "-o", so, "-lm"])
-    return Restatement(so)
+    return Restatement(nb.compile_c_oracle(d, "oracle_shade"))
 
 
 def compile_ref_shim(d):
-    """The real GetShadingData with oracle/Makefile's flags; None when the reference is absent.  tiny_scene.h has a bare `#elif` that g++ refuses: a temp
-    copy with that one directive turned into `#else` goes first on the include path (nothing of it is kept) — as tests/pose_lib.py does it."""
-    if not have_reference():
-        return None
-    d = str(d)
-    with open(os.path.join(reference_dir(), "tiny_scene.h"), encoding="utf-8", errors="surrogateescape") as f:
-        lines = f.read().split("\n")
-    for i, line in enumerate(lines):
-        if line.strip() == "#elif":
-            lines[i] = "#else"
-    with open(os.path.join(d, "tiny_scene.h"), "w", encoding="utf-8", errors="surrogateescape") as f:
-        f.write("\n".join(lines))
-    so = os.path.join(d, "libshade_ref.so")
-    subprocess.check_call(["g++", "-std=c++20", "-O3", "-mavx2", "-mfma", "-fPIC", "-shared", "-w", "-I" + d, "-I" + reference_dir(),
-                           "-I" + os.path.join(reference_dir(), "external"), os.path.join(HERE, "shade_ref_shim.cpp"), "-o", so, "-lpthread"])
-    return RealReference(so)
+    """The real GetShadingData with oracle/Makefile's flags; None when the reference is absent"""
+    so = nb.compile_ref_shim(d, "shade_ref_shim.cpp", scene_header=True, need=("tiny_bvh.h", "tiny_scene.h", "tiny_bvh_foliage.cpp"))
+    return so and RealReference(so)
 
 
 def golden(name):

@@ -2,28 +2,15 @@
 both compiled per session into a pytest temp dir, the meshes, the seeded sphere sets and the rounding class of DESIGN.md par. 11."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
-import pytest
 
+import native_build as nb
+from native_build import _i, _p, _u64, _vp
 from tinybvh_amd import scenes
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 GOLDEN = os.path.join(HERE, "golden", "spheres")
-_vp, _u64, _i = C.c_void_p, C.c_uint64, C.c_int
-
-
-def _p(a):
-    return C.c_void_p(a.ctypes.data)
-
-
-def reference_dir():
-    return os.environ.get("TBVH_REFERENCE", "/root/reference")
-
-
-def have_reference():
-    return os.path.isfile(os.path.join(reference_dir(), "tiny_bvh.h"))
 
 
 class SphereOracle:
@@ -140,32 +127,17 @@ class RefSpheres:
 
 
 def compile_oracle(d):
-    so = os.path.join(str(d), "liboracle_sphere.so")
-    subprocess.check_call(["cc", "-O2", "-std=c11", "-ffp-contract=off", "-fPIC", "-shared", os.path.join(HERE, "oracle_sphere.c"), "-o", so, "-lm"])
-    return SphereOracle(so)
+    return SphereOracle(nb.compile_c_oracle(d, "oracle_sphere"))
 
 
 def compile_ref_shim(d):
     """the reference with oracle/Makefile's flags; None when the reference is absent"""
-    if not have_reference():
-        return None
-    so = os.path.join(str(d), "libsphere_ref.so")
-    subprocess.check_call(["g++", "-std=c++20", "-O3", "-mavx2", "-mfma", "-fPIC", "-shared", "-w", "-I" + reference_dir(),
-                           os.path.join(HERE, "sphere_ref_shim.cpp"), "-o", so, "-lpthread"])
-    return RefSpheres(so)
+    so = nb.compile_ref_shim(d, "sphere_ref_shim.cpp")
+    return so and RefSpheres(so)
 
 
-@pytest.fixture(scope="session")
-def sph_oracle(tmp_path_factory):
-    return compile_oracle(tmp_path_factory.mktemp("oracle_sphere"))
-
-
-@pytest.fixture(scope="session")
-def sph_ref(tmp_path_factory):
-    r = compile_ref_shim(tmp_path_factory.mktemp("sphere_ref"))
-    if r is None:
-        pytest.skip("the reference checkout (TBVH_REFERENCE) is absent")
-    return r
+sph_oracle = nb.oracle_fixture("oracle_sphere", compile_oracle)
+sph_ref = nb.ref_fixture("sphere_ref", compile_ref_shim)
 
 
 # ---- meshes ---------------------------------------------------------------------------------------------------------------------------

@@ -222,13 +222,8 @@ def test_stale_uv_class(cu_oracle):
 def test_tiny_hip_sphere_binding_compiles(tmp_path):
     """tinyhip::SphereBVH against the real tiny_bvh.h: Build, Upload, Intersect, IsOccluded, Handle (examples/sphere_bvh.cpp; the program
     build() makes of it runs on the GPU in tests/test_custom_gpu.py: test_tiny_hip_sphere_binding_runs)"""
-    import subprocess
-    from custom_lib import have_reference, reference_dir
-    if not have_reference():
-        pytest.skip("tiny_bvh.h not found (TBVH_REFERENCE)")
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    subprocess.check_call(["g++", "-std=c++20", "-fsyntax-only", "-w", "-I" + reference_dir(), "-I" + os.path.join(root, "include"),
-                           os.path.join(root, "examples", "sphere_bvh.cpp")])
+    from native_build import ROOT, syntax_check
+    syntax_check(tmp_path, '#include "%s"\n' % os.path.join(ROOT, "examples", "sphere_bvh.cpp"))
 
 
 

@@ -4,7 +4,6 @@ of the device TLAS builder (double_anim_lib.karras_tlas), which test_double_anim
 import ctypes as C
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
@@ -13,6 +12,7 @@ import tinybvh_amd as tb
 from tinybvh_amd import _capi
 from double_lib import odbl  # noqa: F401 (fixture)
 from double_anim_lib import TREE_SHAPE_CAP, bounds_of, check_tlas_tree, karras_tlas, morton63, refit_boxes, tlas_rays, tlas_scene
+from native_build import syntax_check
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ("tbvh_rebuild_tlas_double_device", "tbvh_update_tlas_double", "tbvh_tlas_double_download", "tbvh_double_download", "tbvh_refit_double")
@@ -53,19 +53,14 @@ def test_null_handles_are_refused_by_name():
 
 
 def test_tiny_hip_double_anim_binding_compiles(tmp_path):
-    ref = os.environ.get("TBVH_REFERENCE", "/root/reference")
-    if not os.path.exists(os.path.join(ref, "tiny_bvh.h")):
-        pytest.skip("tiny_bvh.h not found (TBVH_REFERENCE)")
-    src = tmp_path / "double_anim_binding.cpp"
-    src.write_text('#include "tiny_bvh.h"\n#include "tiny_hip.h"\n'
-                   "void f(tinybvh::BVH_Double& b, tinybvh::BVH_Double& tlas, const double* xf, tinybvh::bvhdbl3* verts) {\n"
-                   "    tinyhip::Scene s(b); std::vector<tinyhip::Scene*> v{&s}; tinyhip::Scene t(tlas, v);\n"
-                   "    t.RebuildOnDevice(); t.RebuildOnDevice(xf); t.RebuildOnDevice(xf, true); t.Update(tlas);\n"
-                   "    s.Refit(verts, b.triCount); s.Refit(verts, b.triCount, true);\n"
-                   "    std::vector<tinybvh::BVH_Double::BVHNode> n = s.Download();\n"
-                   "    std::vector<uint64_t> idx(tlas.idxCount); std::vector<tinybvh::BLASInstanceEx> inst(tlas.triCount); n.resize(2 * tlas.triCount);\n"
-                   "    uint64_t used = t.Download(n.data(), n.size(), idx.data(), idx.size(), inst.data(), inst.size()); (void)used;\n}\n")
-    subprocess.check_call(["g++", "-std=c++20", "-fsyntax-only", "-w", "-I" + ref, "-I" + os.path.join(ROOT, "include"), str(src)])
+    syntax_check(tmp_path, '#include "tiny_bvh.h"\n#include "tiny_hip.h"\n'
+                 "void f(tinybvh::BVH_Double& b, tinybvh::BVH_Double& tlas, const double* xf, tinybvh::bvhdbl3* verts) {\n"
+                 "    tinyhip::Scene s(b); std::vector<tinyhip::Scene*> v{&s}; tinyhip::Scene t(tlas, v);\n"
+                 "    t.RebuildOnDevice(); t.RebuildOnDevice(xf); t.RebuildOnDevice(xf, true); t.Update(tlas);\n"
+                 "    s.Refit(verts, b.triCount); s.Refit(verts, b.triCount, true);\n"
+                 "    std::vector<tinybvh::BVH_Double::BVHNode> n = s.Download();\n"
+                 "    std::vector<uint64_t> idx(tlas.idxCount); std::vector<tinybvh::BLASInstanceEx> inst(tlas.triCount); n.resize(2 * tlas.triCount);\n"
+                 "    uint64_t used = t.Download(n.data(), n.size(), idx.data(), idx.size(), inst.data(), inst.size()); (void)used;\n}\n")
 
 
 def test_morton_keys_resolve_a_cluster_far_from_the_rest():

@@ -1,16 +1,12 @@
 """BVH_Double on the host: the record layouts, the two double-precision builders, the restated oracle against brute force, and the
 tiny_hip.h binding against the real tiny_bvh.h when it is present."""
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
 import tinybvh_amd as tb
 from tinybvh_amd import scenes
 from double_lib import instance_scene, odbl, random_rays_dbl, rotated_soup, to_dbl  # noqa: F401 (odbl: fixture)
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from native_build import syntax_check
 
 
 def test_record_layouts():
@@ -159,12 +155,7 @@ def test_oracle_rule0_matches_brute_force(odbl, name):
 
 
 def test_tiny_hip_double_binding_compiles(tmp_path):
-    ref = os.environ.get("TBVH_REFERENCE", "/root/reference")
-    if not os.path.exists(os.path.join(ref, "tiny_bvh.h")):
-        pytest.skip("tiny_bvh.h not found (TBVH_REFERENCE)")
-    src = tmp_path / "double_binding.cpp"
-    src.write_text('#include "tiny_bvh.h"\n#include "tiny_hip.h"\n'
-                   "void f(tinybvh::BVH_Double& b, tinybvh::BVH_Double& tlas, tinybvh::RayEx* r, uint8_t* o) {\n"
-                   "    tinyhip::Scene s(b); std::vector<tinyhip::Scene*> v{&s}; tinyhip::Scene t(tlas, v);\n"
-                   "    s.Intersect(r, 4); s.IsOccluded(r, 4, o); t.Intersect(r, 4); t.IsOccluded(r, 4, o);\n}\n")
-    subprocess.check_call(["g++", "-std=c++20", "-fsyntax-only", "-w", "-I" + ref, "-I" + os.path.join(ROOT, "include"), str(src)])
+    syntax_check(tmp_path, '#include "tiny_bvh.h"\n#include "tiny_hip.h"\n'
+                 "void f(tinybvh::BVH_Double& b, tinybvh::BVH_Double& tlas, tinybvh::RayEx* r, uint8_t* o) {\n"
+                 "    tinyhip::Scene s(b); std::vector<tinyhip::Scene*> v{&s}; tinyhip::Scene t(tlas, v);\n"
+                 "    s.Intersect(r, 4); s.IsOccluded(r, 4, o); t.Intersect(r, 4); t.IsOccluded(r, 4, o);\n}\n")

@@ -12,6 +12,7 @@ from tinybvh_amd import _capi, scenes
 from tinybvh_amd import rays as R
 import mesh_lib as ml
 from mesh_lib import bunny, flatten, mesh_ref  # noqa: F401  (mesh_ref: the session fixture)
+from native_build import syntax_check
 from oracle_lib import compare_hits
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -232,12 +233,8 @@ def test_the_library_builder_over_the_indexed_mesh_gives_the_golden_hits(oracle_
     assert c["bit_identical"] == c["same_prim"], c
 
 
-def test_tiny_hip_indexed_binding_compiles():
+def test_tiny_hip_indexed_binding_compiles(tmp_path):
     """tinyhip::Scene( const BVH_GPU& ), Refit( const bvhvec4slice& ) and IntersectSpheres( .., const bvhvec4slice&, .. ) against the real tiny_bvh.h
     (examples/indexed_mesh.cpp; the program build() makes of it runs on the GPU in tests/test_mesh_gpu.py), and the existing hosts still compile"""
-    import subprocess
-    if not ml.have_reference():
-        pytest.skip("tiny_bvh.h not found (TBVH_REFERENCE)")
     for name in ("indexed_mesh", "speedtest_gpu_section", "sphere_bvh"):
-        subprocess.check_call(["g++", "-std=c++20", "-fsyntax-only", "-w", "-I" + ml.reference_dir(), "-I" + os.path.join(ROOT, "include"),
-                               os.path.join(ROOT, "examples", name + ".cpp")])
+        syntax_check(tmp_path, '#include "%s"\n' % os.path.join(ROOT, "examples", name + ".cpp"))

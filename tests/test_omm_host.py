@@ -10,7 +10,7 @@ import pytest
 import tinybvh_amd as tb
 from tinybvh_amd import _capi
 import omm_lib as O
-from omm_fixtures import omm_oracle, omm_ref  # noqa: F401  (fixtures)
+from omm_lib import omm_oracle, omm_ref  # noqa: F401  (fixtures)
 
 
 def one_by_one():

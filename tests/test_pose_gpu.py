@@ -9,7 +9,7 @@ import tinybvh_amd as tb
 from tinybvh_amd import rays as R
 from oracle_lib import compare_hits
 import pose_lib as P
-from pose_fixtures import pose_oracle  # noqa: F401  (fixture)
+from pose_lib import pose_oracle  # noqa: F401  (fixture)
 
 pytestmark = pytest.mark.gpu
 

@@ -9,7 +9,7 @@ import pytest
 import tinybvh_amd as tb
 from tinybvh_amd import _capi
 import pose_lib as P
-from pose_fixtures import pose_oracle, pose_ref  # noqa: F401  (fixtures)
+from pose_lib import pose_oracle, pose_ref  # noqa: F401  (fixtures)
 
 
 def same_bytes(a, b):

@@ -6,6 +6,8 @@ import subprocess
 
 import pytest
 
+import native_build as nb
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -25,18 +27,13 @@ def test_animated_scene_example():
     assert out.stdout.count("camera rays hit the animated tube") == 8 and "animated scene ok" in out.stdout
 
 
-def _reference():
-    ref = os.environ.get("TBVH_REFERENCE", "/root/reference")
-    return ref if os.path.exists(os.path.join(ref, "tiny_bvh.h")) else None
-
-
 def test_tiny_hip_scenegraph_binding_compiles(tmp_path):
-    """examples/scenegraph_binding.cpp instantiates every member of tinyhip::SceneGraph (tiny_hip.h needs tiny_bvh.h: skipped without the reference header)"""
-    ref = _reference()
-    if ref is None:
-        pytest.skip("the reference header (TBVH_REFERENCE) is absent")
+    """examples/scenegraph_binding.cpp instantiates every member of tinyhip::SceneGraph (tiny_hip.h needs tiny_bvh.h: skipped without the reference header).
+    Compiled and linked against the library, which is more than native_build.syntax_check asks."""
+    if not nb.have_reference():
+        pytest.skip(nb.NO_REFERENCE)
     lib = os.path.join(ROOT, "tinybvh_amd")
-    subprocess.check_call(["g++", "-std=c++20", "-O2", "-mavx2", "-mfma", "-w", "-I" + ref, "-I" + os.path.join(ROOT, "include"), os.path.join(ROOT, "examples", "scenegraph_binding.cpp"),
+    subprocess.check_call(["g++", "-std=c++20", "-O2", *nb.REF_ISA, "-w", "-I" + nb.reference_dir(), "-I" + os.path.join(ROOT, "include"), os.path.join(ROOT, "examples", "scenegraph_binding.cpp"),
                            "-L" + lib, "-ltinybvh_amd", "-Wl,-rpath," + lib, "-lpthread", "-o", str(tmp_path / "scenegraph_binding")])
 
 

@@ -10,6 +10,7 @@ import tinybvh_amd as tb
 import shade_fixtures as SF
 import viewer_fixtures as F
 import viewer_lib as L
+from native_build import NO_REFERENCE
 from viewer_fixtures import viewer_oracle  # noqa: F401  (fixture)
 
 
@@ -272,7 +273,7 @@ def cpu_frame(ref, sc, inst, cam, mode, sky, max_rounds=8):
 def reference_frame(request, tmp_path_factory):
     ref = L.compile_ref_shim(tmp_path_factory.mktemp("viewer_ref_" + request.param), foliage=request.param == "foliage")
     if ref is None:
-        pytest.skip("the reference checkout (TBVH_REFERENCE) is absent")
+        pytest.skip(NO_REFERENCE)
     sc = F.scene()
     inst = filled_instances(sc)
     sky = F.sky(F.FRAME_SKY)

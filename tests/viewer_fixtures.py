@@ -7,8 +7,10 @@ import functools
 
 import numpy as np
 
+import native_build as nb
 import tinybvh_amd as tb
 import shade_fixtures as SF
+import viewer_lib
 from shade_lib import FATTRI_DTYPE, MATERIAL_DTYPE, NO_TEXTURE
 
 SKY_SHAPES = [(1, 1), (5, 7), (8, 16)]          # (h, w): 1 x 1, 7 x 5, 16 x 8
@@ -179,14 +181,4 @@ def synthetic_lighting_records(n=2048 + 37, seed=3):
 
 
 # ---- session fixtures -----------------------------------------------------------------------------------------------------------------------------
-try:
-    import pytest
-except ImportError:
-    pytest = None
-
-if pytest is not None:
-    import viewer_lib as _L
-
-    @pytest.fixture(scope="session")
-    def viewer_oracle(tmp_path_factory):
-        return _L.compile_oracle(tmp_path_factory.mktemp("oracle_viewer"))
+viewer_oracle = nb.oracle_fixture("oracle_viewer", viewer_lib.compile_oracle)

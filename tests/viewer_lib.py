@@ -4,18 +4,16 @@ into a pytest temp dir when the reference checkout is present), and the SKY_EDGE
 import ctypes as C
 import os
 import re
-import subprocess
 
 import numpy as np
+
+import native_build as nb
+from native_build import _p, _u32, _u64, _vp
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 SKY_EDGE_U, SKY_EDGE_V, SKY_CLAMPED_Y, SKY_NAN = 1, 2, 4, 8
-_vp, _u32, _u64, _f64 = C.c_void_p, C.c_uint32, C.c_uint64, C.c_double
-
-
-def _p(a):
-    return C.c_void_p(a.ctypes.data)
+_f64 = C.c_double
 
 
 def measured_ulps():
@@ -176,18 +174,11 @@ def same_through_the_rounds(a, b, n):
 
 
 def compile_oracle(d):
-    so = os.path.join(str(d), "liboracle_viewer.so")
-    subprocess.check_call(["cc", "-O2", "-std=c11", "-ffp-contract=off", "-fPIC", "-shared", os.path.join(HERE, "oracle_viewer.c"), "-o", so, "-lm"])
-    return Restatement(so)
+    return Restatement(nb.compile_c_oracle(d, "oracle_viewer"))
 
 
 # ---- the real reference ---------------------------------------------------------------------------------------------------------------------------
-def reference_dir():
-    return os.environ.get("TBVH_REFERENCE", "/root/reference")
-
-
-def have_reference():
-    return all(os.path.exists(os.path.join(reference_dir(), f)) for f in ("tiny_bvh.h", "tiny_scene.h", "tiny_bvh_gltf.cpp", "tiny_bvh_foliage.cpp"))
+REF_FILES = ("tiny_bvh.h", "tiny_scene.h", "tiny_bvh_gltf.cpp", "tiny_bvh_foliage.cpp")   # what the shim needs of the reference checkout
 
 
 class RealReference:
@@ -264,20 +255,7 @@ class RealReference:
 
 
 def compile_ref_shim(d, foliage=False):
-    """The real viewer file with oracle/Makefile's flags; None when the reference is absent.  tiny_scene.h has a bare `#elif` that g++ refuses: a temp copy with
-    that one directive turned into `#else` goes first on the include path (nothing of it is kept) — as tests/shade_lib.py does it."""
-    if not have_reference():
-        return None
-    d = str(d)
-    with open(os.path.join(reference_dir(), "tiny_scene.h"), encoding="utf-8", errors="surrogateescape") as f:
-        lines = f.read().split("\n")
-    for i, line in enumerate(lines):
-        if line.strip() == "#elif":
-            lines[i] = "#else"
-    with open(os.path.join(d, "tiny_scene.h"), "w", encoding="utf-8", errors="surrogateescape") as f:
-        f.write("\n".join(lines))
-    so = os.path.join(d, "libviewer_ref_foliage.so" if foliage else "libviewer_ref.so")
-    subprocess.check_call(["g++", "-std=c++20", "-O3", "-mavx2", "-mfma", "-fPIC", "-shared", "-w", "-I" + d, "-I" + reference_dir(),
-                           "-I" + os.path.join(reference_dir(), "external")] + (["-DVIEWER_REF_FOLIAGE"] if foliage else []) +
-                          [os.path.join(HERE, "viewer_ref_shim.cpp"), "-o", so, "-lpthread"])
-    return RealReference(so)
+    """The real viewer file (tiny_bvh_gltf.cpp, or tiny_bvh_foliage.cpp) with oracle/Makefile's flags; None when the reference is absent"""
+    so = nb.compile_ref_shim(d, "viewer_ref_shim.cpp", out="viewer_ref_foliage" if foliage else None, defines=("VIEWER_REF_FOLIAGE",) if foliage else (),
+                             scene_header=True, need=REF_FILES)
+    return so and RealReference(so)

@@ -2,21 +2,16 @@
 dir), the Set cases, the rays of the normals tests and the goldens under tests/golden/voxeledit (tools/make_voxel_edit_golden.py)."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
-import pytest
 
+import native_build as nb
 import tinybvh_amd as tb
-from voxel_lib import GRID_WORDS, BRICK_WORDS, TOP_WORDS, dense_to_xyzv, have_reference, reference_dir, scene_dense
+from native_build import _p, _u32, _u64, _vp
+from voxel_lib import GRID_WORDS, BRICK_WORDS, TOP_WORDS, dense_to_xyzv, scene_dense
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 GOLDEN_EDIT = os.path.join(HERE, "golden", "voxeledit")
-_vp, _u64, _u32 = C.c_void_p, C.c_uint64, C.c_uint32
-
-
-def _p(a):
-    return C.c_void_p(a.ctypes.data)
 
 
 class RefVoxelEdit:
@@ -64,20 +59,11 @@ class RefVoxelEdit:
 
 def compile_edit_ref_shim(d):
     """the reference with oracle/Makefile's flags plus -DNDEBUG; None when the reference is absent"""
-    if not have_reference():
-        return None
-    so = os.path.join(str(d), "libvoxel_edit_ref.so")
-    subprocess.check_call(["g++", "-std=c++20", "-O3", "-mavx2", "-mfma", "-DNDEBUG", "-fPIC", "-shared", "-w", "-I" + reference_dir(),
-                           os.path.join(HERE, "voxel_edit_ref_shim.cpp"), "-o", so, "-lpthread"])
-    return RefVoxelEdit(so)
+    so = nb.compile_ref_shim(d, "voxel_edit_ref_shim.cpp", defines=("NDEBUG",))
+    return so and RefVoxelEdit(so)
 
 
-@pytest.fixture(scope="session")
-def edit_ref(tmp_path_factory):
-    r = compile_edit_ref_shim(tmp_path_factory.mktemp("voxel_edit_ref"))
-    if r is None:
-        pytest.skip("the reference checkout (TBVH_REFERENCE) is absent")
-    return r
+edit_ref = nb.ref_fixture("voxel_edit_ref", compile_edit_ref_shim)
 
 
 def host_twin(batches, top=True):

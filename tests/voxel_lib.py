@@ -2,29 +2,16 @@
 compiled per session into a pytest temp dir, the fixtures' scenes and the seeded ray sets."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
-import pytest
 
+import native_build as nb
 import tinybvh_amd as tb
+from native_build import _i, _p, _u32, _u64, _vp
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 GOLDEN = os.path.join(HERE, "golden", "voxels")
-_vp, _u64, _u32, _i = C.c_void_p, C.c_uint64, C.c_uint32, C.c_int
 GRID_WORDS, BRICK_WORDS, TOP_WORDS = 32 * 32 * 32, 512, 16
-
-
-def _p(a):
-    return C.c_void_p(a.ctypes.data)
-
-
-def reference_dir():
-    return os.environ.get("TBVH_REFERENCE", "/root/reference")
-
-
-def have_reference():
-    return os.path.isfile(os.path.join(reference_dir(), "tiny_bvh.h"))
 
 
 def dense_to_xyzv(dense):
@@ -167,32 +154,17 @@ class RefVoxels:
 
 
 def compile_oracle(d):
-    so = os.path.join(str(d), "liboracle_voxel.so")
-    subprocess.check_call(["cc", "-O2", "-std=c11", "-ffp-contract=off", "-fPIC", "-shared", os.path.join(HERE, "oracle_voxel.c"), "-o", so, "-lm"])
-    return VoxelOracle(so)
+    return VoxelOracle(nb.compile_c_oracle(d, "oracle_voxel"))
 
 
 def compile_ref_shim(d):
     """the reference with oracle/Makefile's flags plus -DNDEBUG; None when the reference is absent"""
-    if not have_reference():
-        return None
-    so = os.path.join(str(d), "libvoxel_ref.so")
-    subprocess.check_call(["g++", "-std=c++20", "-O3", "-mavx2", "-mfma", "-DNDEBUG", "-fPIC", "-shared", "-w", "-I" + reference_dir(),
-                           os.path.join(HERE, "voxel_ref_shim.cpp"), "-o", so, "-lpthread"])
-    return RefVoxels(so)
+    so = nb.compile_ref_shim(d, "voxel_ref_shim.cpp", defines=("NDEBUG",))
+    return so and RefVoxels(so)
 
 
-@pytest.fixture(scope="session")
-def vox_oracle(tmp_path_factory):
-    return compile_oracle(tmp_path_factory.mktemp("oracle_voxel"))
-
-
-@pytest.fixture(scope="session")
-def vox_ref(tmp_path_factory):
-    r = compile_ref_shim(tmp_path_factory.mktemp("voxel_ref"))
-    if r is None:
-        pytest.skip("the reference checkout (TBVH_REFERENCE) is absent")
-    return r
+vox_oracle = nb.oracle_fixture("oracle_voxel", compile_oracle)
+vox_ref = nb.ref_fixture("voxel_ref", compile_ref_shim)
 
 
 # ---- scenes ---------------------------------------------------------------------------------------------------------------------------

@@ -20,10 +20,11 @@ import tinybvh_amd as tb  # noqa: E402
 import shade_fixtures as SF  # noqa: E402
 import viewer_fixtures as F  # noqa: E402
 import viewer_lib as L  # noqa: E402
+from native_build import have_reference  # noqa: E402
 
 
 def main():
-    if not L.have_reference():
+    if not have_reference(*L.REF_FILES):
         sys.exit("tools/make_viewer_golden.py needs the reference checkout (TBVH_REFERENCE)")
     os.makedirs(L.GOLDEN, exist_ok=True)
     sc = F.scene()
