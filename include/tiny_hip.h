@@ -134,6 +134,11 @@ public:
         const tbvh_mesh m = MeshOf(verts, nullptr);
         Check(tbvh_refit_mesh(s, &m), "tbvh_refit_mesh");
     }
+    // WATERTIGHT_TRITEST (tiny_bvh.h:141) as a choice per scene instead of a build-time define: TBVH_TRITEST_MOLLER_TRUMBORE (the default) or
+    // TBVH_TRITEST_WATERTIGHT; verts = the scene's bvhvec4 vertex array, 3 per triangle, as Refit takes it (nullptr on a scene that is watertight already).
+    // Triangle BLASes only (tinybvh_amd.h: tbvh_set_triangle_test).
+    void SetTriangleTest(int test, const tinybvh::bvhvec4* verts = nullptr, size_t triCount = 0) { Check(tbvh_set_triangle_test(s, test, verts, triCount, 0), "tbvh_set_triangle_test"); }
+    int TriangleTest() const { return tbvh_scene_triangle_test(s); }
     // BVHBase::SetOpacityMicroMaps( maps, N ) (tiny_bvh.h:823-826): N x N bits per triangle, (N * N + 31) / 32 words each, copied to the device; honoured by
     // Intersect and IsOccluded, also of the TLASes over this scene.  maps == nullptr or N == 0 removes them.
     void SetOpacityMicroMaps(const uint32_t* maps, uint32_t N, size_t triCount) { Check(tbvh_set_opacity_micromaps(s, maps, N, triCount, 0), "tbvh_set_opacity_micromaps"); }

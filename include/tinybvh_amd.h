@@ -190,7 +190,9 @@ int tbvh_build_device_ploc(tbvh_context* ctx, const void* verts16, uint64_t n_tr
 /* (the reference's own binned-SAH tree built on the device: tbvh_build_device_sah, declared with tbvh_build_bvh2_sah_device below, after tbvh_mesh) */
 
 /* Read a BLAS scene's device blobs back (tests, caching a refitted blob): which = 0 nodes, 1 triangle
- * records (BVH_GPU: the gathered {v0|prim, e1, e2} form; BVH4_GPU has none).  dst = NULL only reports the size. */
+ * records (BVH_GPU: the gathered {v0|prim, e1, e2} form; BVH4_GPU has none).  dst = NULL only reports the size.
+ * A scene in watertight mode (tbvh_set_triangle_test) returns the SAME edge-form records: the mode leaves them as they are and reads
+ * its triangles from a vertex copy of its own, which this call does not return. */
 int tbvh_scene_download(tbvh_scene* scene, int which, void* dst, uint64_t cap_bytes, uint64_t* bytes_out);
 
 /* Opacity micromaps — BVHBase::SetOpacityMicroMaps (tiny_bvh.h:823-826): N x N bits per triangle (N * N bits rounded up to
@@ -287,7 +289,10 @@ int tbvh_pinned_free(tbvh_context* ctx, void* ptr);
  * grazing a triangle's edge, a ray that starts in or skims the plane of an axis-aligned triangle, coplanar triangles within ulps
  * of one t — two traversals of one scene can part: the 8-wide copy a BVH_GPU / BVH4_GPU scene is traced through and the
  * wave-packet kernel test more candidates than the native / per-lane kernels and report more of these (real) hits.  DESIGN.md
- * par. 4 has the classes and measured rates; tbvh_set_variant(scene, 1) and TBVH_COHERENT_TUNER=2 pin one traversal.)
+ * par. 4 has the classes and measured rates; tbvh_set_variant(scene, 1) and TBVH_COHERENT_TUNER=2 pin one traversal.
+ * A scene in watertight mode — tbvh_set_triangle_test below — removes the first of these, the hit grazing an edge or a vertex: every
+ * ray gets the closest triangle the watertight test accepts among ALL the scene's triangles, whatever the traversal; coplanar ties
+ * and rays that start in a wall's plane are untouched by it.)
  * Rays with a zero-length direction (rD = 1e30, tinybvh_safercp) or an infinite origin get the reference's answer; rays with NaN components
  * or an infinite direction component are traced without fault and without disturbing other rays, but what they report is unspecified
  * (the reference's own answer for them depends on the order of its comparisons).  Degenerate and duplicate triangles are fine
@@ -300,6 +305,45 @@ int tbvh_occluded_device(tbvh_scene* scene, const void* d_rays64, uint64_t n_ray
  * tiny_bvh.h:695-703) and its record is always written (a miss stores {tmax, 0, 0, 0}).  For
  * callers that re-trace a resident batch, e.g. one frame after another. */
 int tbvh_intersect_device_fresh(tbvh_scene* scene, void* d_rays64, uint64_t n_rays, float tmax);
+
+/* ---- the triangle test, per scene: WATERTIGHT_TRITEST of the reference (tiny_bvh.h:141, 8486-8507; Woop, Benthin, Wald 2013) -----------------------
+ * The default test, Moeller-Trumbore, loses rays between the two triangles of a shared edge: of rays aimed at the vertices and edges of a closed mesh from
+ * inside it, 8-13 % come back as misses on this repository's fixtures (DESIGN.md par. 4.6; 12-17 % on the instance the mode was first measured on), most of them inside the triangle test, where no traversal order recovers them.  A scene
+ * set to TBVH_TRITEST_WATERTIGHT returns, for every ray, the closest triangle that the reference's watertight test — evaluated WITHOUT contraction, each
+ * product and sum rounded on its own; built with -mfma the reference's own test still leaks — accepts among all of the scene's triangles: prim exact,
+ * t / u / v bit-identical to IntersectTri over every triangle in index order, the smaller index on an exact tie; tbvh_occluded* likewise TriOccludes
+ * (under opacity micromaps, where the reference's TriOccludes does not compile: occluded exactly where IntersectTri finds a hit).
+ * u, v mean what they mean under the default (v1's and v2's weight), so opacity micromaps and tbvh_shade_hits read them unchanged.  A closed mesh with
+ * bit-identical shared vertices is closed.  The node test beside it is conservative (a box the exact ray touches is never culled).
+ *   scene     a BVH_GPU, BVH4_GPU or BVH8_CWBVH BLAS however it was made (uploaded blob, SBVH blobs included; device conversion or build; mesh scenes).
+ *             BVH_GPU / BVH4_GPU scenes are traced through their 8-wide copy, which a watertight scene gets whatever its size.
+ *   verts16   the caller's vertex array as tbvh_refit takes it (3 float4 per triangle, primitive order; on_device as there).  The test needs v1 and v2
+ *             themselves — v0 + e1 is not v1 — so the scene keeps a copy, 48 bytes per triangle, counted by tbvh_scene_device_bytes.  NULL is allowed on a
+ *             scene that is already watertight (its vertices stay) and ONLY there: no other scene holds its vertices — one made from an indexed mesh holds
+ *             its index buffer, one built or converted on the device its records — so every other scene, those included, is handed the flat array.  A record whose primitive index is >= n_tris is no hit and reported as TBVH_E_FORMAT by
+ *             the next synchronising call.  tbvh_scene_download(which = 1) returns the records as uploaded, {v0|prim, e1, e2} or the layout's own, in either mode.
+ *   test 0    restores the default exactly: the records and derived copies were never touched, the vertex copy goes.
+ * Geometry that moves: tbvh_refit, tbvh_refit_mesh, tbvh_pose_refit and tbvh_update_bvh_gpu / _mesh hand the scene new vertices, and it tests those from then
+ * on.  tbvh_update_bvh4_gpu and tbvh_update_cwbvh carry none: call tbvh_set_triangle_test( scene, 1, new_verts, .. ) after them.
+ * Refused with TBVH_E_INVALID, the scene left as it was: a null scene, a test other than 0 / 1, BVH_DOUBLE, voxel and sphere scenes, a TLAS, a scene pinned
+ * with tbvh_set_variant (and tbvh_set_variant != 0 on a watertight scene), a BLAS a live TLAS is built over, test 1 without vertices on a scene holding none.
+ * Two levels: a TLAS has no call of its own.  tbvh_upload_tlas reads the mode off its BLASes — all watertight, or all not; a mix, and watertight triangle BLASes next
+ * to sphere or voxel BLASes, are refused (TBVH_E_INVALID, the text says why).  Both kinds of query on such a TLAS run the watertight form of the 8-wide two-level
+ * kernel, every BLAS entered through BVH8_CWBVH arrays, the instance transform evaluated as the reference's source is written (nothing fused): inst, prim exact and
+ * t / u / v bit-identical to the reference's test through its own instance transform.  tbvh_scene_triangle_test on a TLAS reports its BLASes' mode.  The packet,
+ * native 2- / 4-wide, 4-wide two-level and flat kernels have no watertight form; a watertight scene is never routed to them (a tree the 8-wide TLAS format cannot
+ * hold — beyond 2^24 nodes — is an error of the upload).
+ * Everything that goes through the ordinary queries — the sharded calls (set every replica), tbvh_voxelize_device, the viewer frame, the wavefront tracer,
+ * tbvh_shade_hits — simply works on a watertight BLAS.
+ * Cost (MI355X, 2.83 M triangles, 4.2 M rays, tools/watertight_bench.py; DESIGN.md par. 4.6): a watertight scene traces camera rays at 0.79, diffuse
+ * bounce rays at 0.76 and shadow rays at 0.85 of the default's rate (3.43 / 2.52 / 4.58 against 4.33 / 3.32 / 5.39 GRays/s) — the dependent vertex fetch, the wider boxes and the loss of the probed schedules. */
+#define TBVH_TRITEST_MOLLER_TRUMBORE 0
+#define TBVH_TRITEST_WATERTIGHT      1
+int tbvh_set_triangle_test(tbvh_scene* scene, int test, const void* verts16, uint64_t n_tris, int on_device);
+int tbvh_scene_triangle_test(const tbvh_scene* scene);
+/* The two tests on the host, one ray / triangle pair: ray64 = a ray record (hit.t = the ray's tmax), v0, v1, v2 = 3 floats each.  1 = accepted (*t, *u, *v
+ * written), 0 = rejected, < 0 = TBVH_E_*.  Test 0 runs the default over {v0, v1 - v0, v2 - v0}. */
+int tbvh_host_tri_test(int test, const void* ray64, const float* v0, const float* v1, const float* v2, float* t, float* u, float* v);
 
 /* ONE ray array over SEVERAL devices (the reference has a single process-global OpenCL device, tiny_ocl.h:362-364;
  * SURVEY.md §8(e)): scenes[i] is the same BVH uploaded through the context of device i (the BVH is replicated), the

@@ -107,6 +107,10 @@ int tbvh_debug_packet_cull(const void* nodes80, uint64_t n_nodes, const void* ra
 int tbvh_debug_tri_test_flat(const float* od6, const float* tri9, const float* tmax, uint64_t n, uint8_t* accept_branch, uint8_t* accept_flat, float* tuv_branch,
                              float* tuv_flat);
 
+/* tbvh_host_tri_test over n pairs (tests/test_watertight_host.py): rays64 = n ray records, tris9 = n x {v0, v1, v2}; accept: n bytes; tuv: n x 3 floats (0 where
+ * rejected); uvw: NULL or n x 3 floats, the watertight test's edge functions U, V, W (test 1 only); roles: 0 = IntersectTri's vertex roles, 1 = TriOccludes'. */
+int tbvh_debug_tri_test_batch(int test, int roles, const void* rays64, const float* tris9, uint64_t n, uint8_t* accept, float* tuv, float* uvw);
+
 /* Diagnostic kernel variants of BVH8_CWBVH scenes (0 = default): 72 / 52 force the strict / the coherent schedule whatever
  * the probe says, 90 the incoherent flavor on the copies of tbvh_cwbvh_set_hybrid, 75 / 88 split the last rays whatever the batch size, 59 / 61 / 73 / 78 / 82 / 83 are the instrumented
  * kernels behind tbvh_debug_stats.  Returns TBVH_E_INVALID for anything else. */

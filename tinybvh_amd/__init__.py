@@ -22,6 +22,7 @@ LAYOUT_BVH_DOUBLE = 3
 LAYOUT_BVH_GPU = 5
 LAYOUT_BVH4_GPU = 8
 LAYOUT_CWBVH = 10
+TRITEST_MOLLER_TRUMBORE, TRITEST_WATERTIGHT = 0, 1   # TBVH_TRITEST_* (tbvh_set_triangle_test)
 LAYOUT_VOXELSET = 12
 # wavefront materials: v0.w of a triangle's first vertex = type << 24 | 0xRRGGBB (wavefront.cl:12-13, 160)
 MATERIAL_DIFFUSE, MATERIAL_LIGHT, MATERIAL_SPECULAR = 0, 1, 2
@@ -563,6 +564,30 @@ class _Scene:
         assert m.size % wpt == 0
         check(lib.tbvh_set_opacity_micromaps(self._h, _ptr(m), N, m.size // wpt, 0), "tbvh_set_opacity_micromaps")
         return self
+
+    def SetTriangleTest(self, test: str, vertices=None):
+        """The scene's triangle test (tbvh_set_triangle_test; WATERTIGHT_TRITEST, tiny_bvh.h:141): "moller-trumbore" (the default) or "watertight".
+        vertices: the (3 n_tris, 4) float32 array the scene was built from, as Refit takes it, or a (device pointer, n_tris) pair; None on a scene that is
+        watertight already.  Triangle BLASes only; the C entry point refuses everything else and says why."""
+        codes = {"moller-trumbore": TRITEST_MOLLER_TRUMBORE, "watertight": TRITEST_WATERTIGHT}
+        if test not in codes:
+            raise ValueError(f"triangle test {test!r}: one of {sorted(codes)}")
+        if vertices is None:
+            ptr, n_tris, dev = None, 0, 0
+        elif isinstance(vertices, tuple):
+            ptr, n_tris, dev = C.c_void_p(int(vertices[0])), int(vertices[1]), 1
+        else:
+            vertices = np.ascontiguousarray(vertices, np.float32)
+            assert vertices.ndim == 2 and vertices.shape[1] == 4 and vertices.shape[0] % 3 == 0
+            ptr, n_tris, dev = _ptr(vertices), vertices.shape[0] // 3, 0
+        check(lib.tbvh_set_triangle_test(self._h, codes[test], ptr, n_tris, dev), "tbvh_set_triangle_test")
+        return self
+
+    @property
+    def triangle_test(self) -> str:
+        r = lib.tbvh_scene_triangle_test(self._h)
+        check(min(r, 0), "tbvh_scene_triangle_test")
+        return "watertight" if r == TRITEST_WATERTIGHT else "moller-trumbore"
 
     def BakeOpacityMicroMaps(self, uv, textures, N: int = 32, indices=None, tri_texture=None):
         """Mesh::CreateOpacityMicroMaps( N ) of tiny_scene.h on the device, installed on this scene without a host round trip (tbvh_bake_set_opacity_micromaps):

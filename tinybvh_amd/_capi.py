@@ -114,6 +114,10 @@ SYMBOLS = {
     "tbvh_update_cwbvh": (_i, [_vp, _vp, _u64, _vp, _u64]),
     "tbvh_rebuild_tlas_device": (_i, [_vp, _vp, _i, _vp, _u64]),
     "tbvh_refit": (_i, [_vp, _vp, _u64, _i]),
+    "tbvh_set_triangle_test": (_i, [_vp, _i, _vp, _u64, _i]),
+    "tbvh_scene_triangle_test": (_i, [_vp]),
+    "tbvh_host_tri_test": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "tbvh_debug_tri_test_batch": (_i, [_i, _i, _vp, _vp, _u64, _vp, _vp, _vp]),
     "tbvh_set_opacity_micromaps": (_i, [_vp, _vp, _u32, _u64, _i]),
     "tbvh_scene_download": (_i, [_vp, _i, _vp, _u64, _vp]),
     "tbvh_build_device": (_i, [_vp, _vp, _u64, _i, _i, _u32, _vp]),

@@ -327,14 +327,14 @@ int tbvh_debug_runahead_script(const uint64_t* ops6, uint64_t nOps, int depth, i
 // (tests/test_launch_plan_host.py).
 int tbvh_debug_launch_plan(const uint64_t* facts, uint32_t nFacts, uint32_t* out, uint32_t nOut) {
     if (!facts || !out) return fail(TBVH_E_INVALID, "tbvh_debug_launch_plan: null argument");
-    if (nFacts != kLaunchFactWords || nOut != kLaunchPlanWords)
+    if (!(nFacts == kLaunchFactWords && nOut == kLaunchPlanWords) && !(nFacts == kLaunchFactWordsTest && nOut == kLaunchPlanWordsTest))   // (as before the triangle test, or with it)
         return fail(TBVH_E_INVALID, "tbvh_debug_launch_plan: %u facts and %u plan words (this library: %u and %u)", nFacts, nOut, kLaunchFactWords,
                     kLaunchPlanWords);
-    const LaunchFacts f = launchFactsFromWords(facts);
+    const LaunchFacts f = launchFactsFromWords(facts, nFacts);
     if (!f.raysPerBlock) return fail(TBVH_E_INVALID, "tbvh_debug_launch_plan: raysPerBlock is 0");
     LaunchPlan p = planBatch(f);
     planShape(p, f);
-    launchPlanToWords(p, out);
+    launchPlanToWords(p, out, nOut);
     return 0;
 }
 

@@ -132,7 +132,8 @@ void freeCopy(tbvh_scene* s, CopyKind kind) {
 // puts the whole TLAS on the flat loop), so small blobs get one too (from 64 entries; TBVH_WIDE_COPY_MIN still rules when set).
 static tbvh_scene* buildCopy(tbvh_scene* s, int target, bool forTlas) {
     tbvh_context* c = s->ctx;
-    const uint64_t minIdx = wideCopyMin(forTlas ? 64 : kWideCopyMin);
+    // (a watertight BVH_GPU / BVH4_GPU scene has no other kernel than the 8-wide one: a copy whatever its size, whatever TBVH_WIDE_COPY_MIN says)
+    const uint64_t minIdx = (s->triTest && target == TBVH_LAYOUT_CWBVH) ? 1 : wideCopyMin(forTlas ? 64 : kWideCopyMin);
     std::vector<Node2> n2;
     std::vector<Vec4> blob, recs;
     const float4* dRecs = nullptr;
@@ -186,7 +187,7 @@ static tbvh_scene* buildCopy(tbvh_scene* s, int target, bool forTlas) {
 // camera / shadow / random MRays/s) are in DESIGN.md par. 3.5: k_tlas4 is the fastest two-level kernel for closest hits, k_tlas8 for any-hit queries.
 TlasBlasFacts tlasBlasFacts(const tbvh_scene* b) {
     TlasBlasFacts f;
-    f.layout = b->layout; f.pinned = b->variant != 0; f.has8 = b->copies.copy8 != nullptr; f.has4 = b->copies.copy4 != nullptr;
+    f.layout = b->layout; f.pinned = b->variant != 0; f.has8 = b->copies.copy8 != nullptr; f.has4 = b->copies.copy4 != nullptr; f.watertight = b->triTest != 0;
     return f;
 }
 const tbvh_scene* blasView(const tbvh_scene* b, TlasView v) { return v == kViewWide4 ? b->copies.copy4 : v == kViewWide8 ? b->copies.copy8 : b; }
@@ -207,7 +208,8 @@ static int makeCopy(tbvh_scene* s, CopyKind kind) {
         if (!four) {
             // a copy below the size at which the scene's OWN queries gain from it (made for the TLASes over the scene): those queries keep the uploaded nodes
             const uint64_t entries = s->layout == TBVH_LAYOUT_BVH_GPU ? s->nTriBlocks / 3 : w->nTriBlocks / 3;
-            s->copies.tlasOnly = entries < kWideCopyMin && wideCopyMin(0) == 0;   // (0: the variable is not set)
+            s->copies.tlasOnly = entries < kWideCopyMin && wideCopyMin(0) == 0 && !s->triTest;   // (0: the variable is not set)
+            shareTriangleTest(s);
         }
     }
     forEachTlasOver(s, [](tbvh_scene* t) { (void)reclassifyTlas(t); return 0; });   // (the copy's arrays are new ones — or gone)
@@ -216,6 +218,16 @@ static int makeCopy(tbvh_scene* s, CopyKind kind) {
 
 void makeCopyOnce(tbvh_scene* b, CopyKind kind) {
     if (layoutHasCopy(b, kind) && !(kind == kCopyWide4 ? b->copies.tried4 : b->copies.tried8) && b->variant == 0) makeCopy(b, kind);
+}
+
+int ensureWatertightCopy(tbvh_scene* s) {
+    if (!s->triTest || s->isTlas || !layoutHasCopy(s, kCopyWide8)) return 0;
+    if (!s->copies.copy8) makeCopy(s, kCopyWide8);
+    if (!s->copies.copy8)
+        return fail(TBVH_E_INVALID, "a watertight BVH_GPU / BVH4_GPU scene is traced through its 8-wide copy, and none could be made (a blob whose root is a leaf, or no memory)");
+    s->copies.tlasOnly = false;
+    shareTriangleTest(s);
+    return 0;
 }
 
 void dropCopiesAfterUpdate(tbvh_scene* s) {

@@ -314,8 +314,15 @@ struct tbvh_scene {
     DevBuf<uint32_t> meshIdx;
     uint64_t meshIdxTris = 0;
     DevBuf<uint32_t> idxStage;           // staged host indices of tbvh_intersect_spheres_mesh (a per-frame query: no allocation per call)
+    // the scene's triangle test (tbvh_set_triangle_test, capi_watertight.hip).  A watertight scene holds its own copy of the caller's vertices, 3 float4 per
+    // triangle in primitive order (sceneBytes counts it; refits write it again): the watertight kernels fetch a triangle through its record's primitive
+    // index.  Like the opacity maps, what the kernels read is a plain pointer on every scene: an 8-wide copy shares its owner's.
+    int triTest = 0;
+    const float4* wtVerts = nullptr;
+    uint64_t wtTris = 0;
+    DevBuf<float4> wtVertsOwn;
     WideCopies copies;
-    uint64_t raysTraced = 0;             // rays of every query launched on this scene (a TLAS counts its own): what a refit weighs the copies' refit against
+    uint64_t raysTraced = 0;            // rays of every query launched on this scene (a TLAS counts its own): what a refit weighs the copies' refit against
     // a sphere BLAS that moves (capi_custom.hip: tbvh_build_device_custom_spheres / tbvh_rebuild_custom_spheres_device / tbvh_refit_custom_spheres): the
     // sphere count and the builder a rebuild repeats (an uploaded scene: LBVH, one sphere per leaf).  The build keeps its scratch in buildScratch
     // (sized for buildScratchFor spheres) and its primIdx here, the refit its pass words in refitScratch, host spheres are staged in vertStage: no
@@ -452,6 +459,9 @@ void countQueryForRecopy(tbvh_scene* s);     // ... and the query side of it (la
 tbvh_scene* wideCopyForQuery(tbvh_scene* s);   // the 8-wide copy the scene's own queries run on, or nullptr: they run on s
 tbvh_scene* tunedScene(tbvh_scene* s);         // the scene whose CohTuner decides for queries on s: its 8-wide copy if it has one
 void shareOpacityMaps(tbvh_scene* s);          // the copies read the owner's maps
+void shareTriangleTest(tbvh_scene* s);         // ... and the owner's triangle test and vertices (capi_watertight.hip)
+int ensureWatertightCopy(tbvh_scene* s);       // (capi_copies.hip) a watertight BVH_GPU / BVH4_GPU scene is traced through its 8-wide copy whatever its size: made now if it is not there
+int refreshWatertightVerts(tbvh_scene* s, const tbvh::MeshSrc& src);   // (capi_watertight.hip) tail of a refit: a watertight scene's vertices are src's from here on
 int refitCopies(tbvh_scene* s, const tbvh::MeshSrc& src);   // tail of a refit of s: its copies follow in place, or go (CopyPolicy::refit)
 TlasBlasFacts tlasBlasFacts(const tbvh_scene* b);                         // what tlas_plan.h reads of BLAS b
 const tbvh_scene* blasView(const tbvh_scene* b, TlasView v);              // the scene whose arrays a TLAS enters b through under view v

@@ -306,6 +306,16 @@ static void launchSceneKernel(tbvh_scene* s, const QueryArgs& q, const LaunchPla
 static int launchCwbvhKernels(tbvh_scene* s, QueryArgs& q, const LaunchPlan& P, const Launch& L) {
     tbvh_context* c = s->ctx;
     const float4* tris = s->tris;
+    if (P.watertight) {   // the scene's test is the watertight one: its instantiations of the per-lane kernel, and no other (a missing vertex array is an error, never another kernel)
+        if (!s->wtVerts) return fail(TBVH_E_INVALID, "a scene in watertight mode without its vertices");
+        QueryArgs qw = q;
+        qw.wtVerts = s->wtVerts; qw.wtTris = (uint32_t)s->wtTris;   // (in the place of stats and hybridK: device_common.h)
+        // the split-ray forms (batches below 12 M rays) hold 5 waves per SIMD: a persistent grid beyond 20 workgroups per CU would only queue the rest up as a tail
+        const uint32_t resident = (uint32_t)c->numCUs * 4u * kWatertightWavesPerSimd;
+        const uint32_t blocksWt = (split_rays_wanted(qw) && !c->gridOverride && P.blocksBase > resident) ? resident : P.blocksBase;
+        launch_cwbvh_watertight(L.any, s->nodes, s->tris, qw, c->status, blocksWt, L.st);
+        return 0;
+    }
 #ifdef TBVH_EXPERIMENTS
     if ((c->expFlags & 2u) && s->cw.trisPadded) { tris = s->cw.trisPadded; q.flags |= 2u; }   // experiment: 64-byte triangle records in the ordinary kernels too
 #endif
@@ -433,6 +443,7 @@ static void harvestVerdicts(tbvh_context* c) {
 static bool launchPrepares(const tbvh_scene* s, uint64_t n, bool any) {
     if (s->isTlas) return s->tlas.blasRecopyPending || (any && !s->tlas.anyHitSeen && !s->tlas.blasSpheres);
     if (s->copies.pending()) return true;
+    if (s->triTest && !s->copies.copy8 && (s->layout == TBVH_LAYOUT_BVH_GPU || s->layout == TBVH_LAYOUT_BVH4_GPU)) return true;   // (ensureWatertightCopy)
     return n >= 1024u && s->variant == 0 && !s->copies.tried8 && (s->layout == TBVH_LAYOUT_BVH_GPU || s->layout == TBVH_LAYOUT_BVH4_GPU);
 }
 
@@ -443,6 +454,7 @@ static int prepareScene(tbvh_scene* s, uint64_t n, bool any, bool sizeKnown, tbv
     s->raysTraced += n;   // (what tbvh_refit weighs the refit of a scene's copies against)
     countQueryForRecopy(s);   // copies dropped by a tbvh_update_* come back once the blob has settled
     if (!s->isTlas && (!sizeKnown || n >= 1024u)) makeCopyOnce(s, kCopyWide8);   // first query of a BVH_GPU / BVH4_GPU scene
+    if (s->triTest && !s->isTlas) if (int r = ensureWatertightCopy(s)) return r;   // a watertight BVH_GPU / BVH4_GPU scene: the 8-wide copy whatever the batch
     if ((*wide = wideCopyForQuery(s))) return 0;
     // the first IsOccluded through this TLAS: its BVH4_GPU and BVH_GPU BLASes are entered through 8-wide copies by any-hit queries
     if (any && s->isTlas && !s->tlas.anyHitSeen && !s->tlas.blasSpheres) {
@@ -455,7 +467,8 @@ static int prepareScene(tbvh_scene* s, uint64_t n, bool any, bool sizeKnown, tbv
 
 static QueryArgs queryArgsOf(const tbvh_scene* s, RayRec* d_rays, uint64_t n, uint8_t* d_occ, bool fresh, float freshTmax, const unsigned long long* nDev) {
     const tbvh_context* c = s->ctx;
-    QueryArgs q;
+    QueryArgs q;   // (stats and hybridK share their storage with a watertight scene's wtVerts and wtTris — device_common.h —, which only launchCwbvhKernels sets, on
+                   // the copy it hands its watertight kernels: whoever else builds a QueryArgs for such a scene must set them too)
     q.rays = d_rays; q.nRays = n; q.occluded = d_occ;
     q.poolParts = c->poolParts;
     q.stats = c->counter + 8;
@@ -476,6 +489,7 @@ static int planLaunch(tbvh_scene* s, uint64_t n, bool sizeKnown, const Launch& L
     f.blobBytes = (!s->isTlas && s->layout == TBVH_LAYOUT_CWBVH) ? (s->nNodeBlocks + s->nTriBlocks) * 16 : sceneBytes(s);   // (BVH8_CWBVH: without the library's own copies)
     f.gridOverride = c->gridOverride; f.numCUs = (uint32_t)c->numCUs; f.blocks = c->blocks; f.raysPerBlock = c->raysPerBlock;
     f.expFlags = c->expFlags; f.cohTunerMode = c->cohTunerMode; f.probeMemoryOn = c->probeMemoryOn; f.skipTiming = c->skipTiming;
+    f.triTest = s->triTest;
     for (int k = 0; k < 4; k++) f.decided[k] = s->cohTuner[L.any ? 1 : 0][k].decided;
     *plan = planBatch(f);
     if (plan->probed && !s->cw.tried) {   // first launch of this class on the scene: the derived copies for incoherent batches (not part of the query's time)
@@ -574,6 +588,8 @@ static int enqueueKernels(tbvh_scene* s, QueryArgs& q, const LaunchPlan& plan, c
     const BlasDesc* const desc = s->isTlas ? tlasDesc(s, L.any) : nullptr;
     const uint32_t blocks = plan.blocks, blocks7 = plan.blocks7Tlas;
     q.spillStride = stackEntriesPerLane(s, L.any, family);
+    if (s->isTlas && s->tlas.plan.watertight && family != KernelFamily::kTlas8)   // (a missing kernel is an error, never another kernel)
+        return fail(TBVH_E_INVALID, "a TLAS over watertight BLASes without its 8-wide tree: no other two-level kernel has a watertight form");
     switch (family) {
     case KernelFamily::kBvh2: launch_bvh2(L.any, s->variant, s->nodes, s->tris, q, c->status, blocks, L.st); break;
     case KernelFamily::kBvh4: launch_bvh4(L.any, s->variant, s->nodes, q, c->status, blocks, L.st); break;
@@ -582,7 +598,7 @@ static int enqueueKernels(tbvh_scene* s, QueryArgs& q, const LaunchPlan& plan, c
     case KernelFamily::kVoxel: launch_voxel(L.any, (const uint32_t*)s->nodes.get(), nullptr, nullptr, nullptr, nullptr, q, c->status, blocks, L.st); break;
     case KernelFamily::kTlasSphere: launch_tlas_custom(L.any, t.layout, s->nodes, s->tlas.tlasIdx, s->tlas.instances, desc, q, c->status, blocks, L.st); break;
     case KernelFamily::kTlas4: launch_tlas4(L.any, 0, s->tlas.tlas4, s->tlas.instances, desc, q, c->status, blocks, L.st, blocks7); break;
-    case KernelFamily::kTlas8: launch_tlas8(L.any, 0, s->tlas.tlas8, s->tlas.tlas8Refs, s->tlas.instances, desc, q, c->status, blocks, L.st, blocks7, t.mix); break;
+    case KernelFamily::kTlas8: launch_tlas8(L.any, 0, s->tlas.tlas8, s->tlas.tlas8Refs, s->tlas.instances, desc, q, c->status, blocks, L.st, blocks7, t.mix, s->tlas.plan.watertight); break;
     case KernelFamily::kTlasVoxel: launch_voxel(L.any, nullptr, s->nodes, s->tlas.tlasIdx, s->tlas.instances, desc, q, c->status, blocks, L.st); break;
     case KernelFamily::kTlas2: launch_tlas2(L.any, 0, s->nodes, s->tlas.tlasIdx, s->tlas.instances, desc, q, c->status, blocks, L.st, blocks7); break;
     case KernelFamily::kTlasFlat: launch_tlas(L.any, t.layout, s->nodes, s->tlas.tlasIdx, s->tlas.instances, desc, q, c->status, blocks, L.st); break;
@@ -650,6 +666,7 @@ int checkStatus(tbvh_context* c) {
                        "joint was not written"},
         {kStatusShade, "shade: a hit record's instance, BLAS slot or primitive, or a device-resident material or texture index, is out of range (the record "
                        "got no surface, or an untextured albedo of 0)"},
+        {kStatusWatertightPrim, "watertight test: a triangle record names a primitive beyond the vertices given to tbvh_set_triangle_test (that triangle was no hit)"},
         {kStatusVoxelNormal, "voxel normals: a hit record's instance index is not an instance of the TLAS (that record got zeros)"},
     };
     uint32_t st = 0;

@@ -25,7 +25,7 @@ tbvh_scene* newScene(tbvh_context* c, int layout) {
 //       sphere BLAS and a voxel set by their allocations (a device-built sphere tree lives in arrays the library sized for 2 n nodes)
 //   [1] a BVH8_CWBVH scene's re-layouts (CwbvhLayouts): padded nodes, hybrid nodes, 64-byte triangle records
 //   [2] the wide copies, each asked for ITS bytes now: a copy that grows or goes is right by construction
-//   [3] opacity maps, on the scene that owns them (a copy shares its owner's pointer and holds none)
+//   [3] opacity maps and a watertight scene's vertex copy (tbvh_set_triangle_test), on the scene that owns them (a copy shares its owner's pointer and holds none)
 //   [4] the index buffer a scene made from an indexed mesh holds
 //   [5] an fp32 TLAS's wide trees, the 8-wide tree's references and the SAH builder's Wald nodes; an fp64 TLAS's one allocation (capi_double.hip: tlasLayout( its
 //       capacities ).total, which is what `nodes` was allocated with)
@@ -50,7 +50,7 @@ SceneBytes sceneBytesByWord(const tbvh_scene* s) {
     w[1] += (s->cw.padded.count() + s->cw.hybrid.count() + s->cw.trisPadded.count()) * 16;
     if (s->copies.copy8) w[2] += sceneBytes(s->copies.copy8);
     if (s->copies.copy4) w[2] += sceneBytes(s->copies.copy4);
-    w[3] += s->opmapOwn.count() * 4;
+    w[3] += s->opmapOwn.count() * 4 + s->wtVertsOwn.count() * 16;   // (and a watertight scene's vertices, likewise on the scene that owns them)
     w[4] += s->meshIdx.count() * 4;
     if (tlas32) w[5] += (t.tlas4.count() + t.tlas8.count() + t.tlasWald.count()) * 16 + t.tlas8Refs.count() * 4;
     if (tlas64) w[5] += s->nodes.count() * 16;
@@ -83,6 +83,7 @@ int refitDeviceSource(tbvh_scene* s, const MeshSrc& src) {
         HIP_TRY(timedBegin(c));
         HIP_TRY(run_refit_bvh4(s->nodes, s->nNodeBlocks, src, items, capNodes, counter, childBox, s->b4Levels, c->status, c->stream));
         HIP_TRY(timedEnd(c));
+        if (int r = refreshWatertightVerts(s, src)) return r;   // a watertight scene tests the new vertices
         return refitCopies(s, src);   // the 8-wide copy follows
     }
     if (s->layout != TBVH_LAYOUT_CWBVH && s->layout != TBVH_LAYOUT_BVH_GPU)
@@ -94,6 +95,7 @@ int refitDeviceSource(tbvh_scene* s, const MeshSrc& src) {
     HIP_TRY(launch_refit(s->layout, s->nodes, nNodes, s->tris, nRecords, src, s->refitScratch, c->status, c->stream));
     HIP_TRY(timedEnd(c));
     if (int r = rederiveCwbvhLayouts(s)) return r;   // the padded / hybrid nodes and the 64-byte triangle records would be stale now
+    if (int r = refreshWatertightVerts(s, src)) return r;   // a watertight scene tests the new vertices
     return refitCopies(s, src);                      // the 8-wide and the 4-wide copy follow
 }
 }  // namespace tbvh_capi
@@ -279,6 +281,8 @@ TlasFacts tlasFactsNow(const tbvh_scene* s, std::vector<TlasBlasFacts>& blas) {
 // copied, BLASes of different layouts under one TLAS share one kernel class per kind of query instead of the flat three-state loop.
 int reclassifyTlas(tbvh_scene* s) {
     TlasState& t = s->tlas;
+    // a watertight BVH_GPU / BVH4_GPU BLAS is entered through its 8-wide copy and nothing else: if an update dropped it, it comes back now
+    for (tbvh_scene* b : t.blasList) if (b->triTest && !b->copies.copy8) if (int r = ensureWatertightCopy(b)) return r;
     std::vector<TlasBlasFacts> blas;
     const TlasFacts f = tlasFactsNow(s, blas);
     const size_t nBlas = blas.size();
@@ -286,6 +290,26 @@ int reclassifyTlas(tbvh_scene* s) {
     TlasView* const view[2] = {t.view[0].data(), t.view[1].data()};
     t.plan = planTlas(f, view);
     HIP_TRY(hipStreamSynchronize(s->ctx->stream));   // (launches in flight read the old descriptors)
+    if (t.plan.watertight) {   // one table of BlasDescWt (kernels.h): the views' arrays and each BLAS's vertices
+        for (size_t i = 0; i < nBlas; i++)
+            if (!t.blasList[i]->triTest || !t.blasList[i]->wtVerts) return fail(TBVH_E_INVALID, "TLAS: BLAS %llu is not in watertight mode while others are (all or none)", (unsigned long long)i);
+        std::vector<BlasDescWt> dw(nBlas);
+        for (size_t i = 0; i < nBlas; i++) {
+            const tbvh_scene* b = t.blasList[i];
+            const tbvh_scene* v = blasView(b, t.view[0][i]);
+            if (v->layout != TBVH_LAYOUT_CWBVH) return fail(TBVH_E_INVALID, "TLAS: watertight BLAS %llu has no 8-wide form to be entered through", (unsigned long long)i);
+            dw[i] = BlasDescWt{BlasDesc{v->nodes, v->tris, b->opmap, b->opmapN, (uint32_t)v->layout}, b->wtVerts, b->wtTris, {0, 0}};
+        }
+        if (t.blasDesc.count() < nBlas * 2) { t.blasDesc.reset(); HIP_TRY(t.blasDesc.alloc(nBlas * 2)); }
+        HIP_TRY(hipMemcpy(t.blasDesc, dw.data(), nBlas * sizeof(BlasDescWt), hipMemcpyHostToDevice));
+        t.blasDescAny.reset();
+        if (s->nodes) {
+            if (int r = buildWideTlas(s)) return r;
+            if (t.plan.kind[0].family != TlasFamily::kTlas8 || t.plan.kind[1].family != TlasFamily::kTlas8)
+                return fail(TBVH_E_INVALID, "TLAS over watertight BLASes: the 8-wide TLAS tree does not fit, and no other two-level kernel has a watertight form");
+        }
+        return 0;
+    }
     std::vector<BlasDesc> desc(nBlas);
     for (int kind = 0; kind < (t.plan.anyOwn ? 2 : 1); kind++) {
         for (size_t i = 0; i < nBlas; i++) {
@@ -313,6 +337,15 @@ int tbvh_upload_tlas(tbvh_context* c, const void* nodes64, uint64_t nNodes, cons
         if (b->layout != TBVH_LAYOUT_CWBVH && b->layout != TBVH_LAYOUT_BVH4_GPU && b->layout != TBVH_LAYOUT_BVH_GPU && b->layout != TBVH_LAYOUT_VOXELSET &&
             b->layout != TBVH_LAYOUT_BVH2_WALD)
             return fail(TBVH_E_INVALID, "BLAS %llu: layout %d cannot be a BLAS", (unsigned long long)i, b->layout);
+        // a TLAS has no triangle test of its own: it reads the mode off its BLASes, which must agree — one kernel serves all of them
+        bool anyWt = false;
+        for (uint64_t k = 0; k < nBlas; k++) anyWt |= blas[k] && blas[k]->triTest != 0;
+        if (anyWt && (b->layout == TBVH_LAYOUT_VOXELSET || b->layout == TBVH_LAYOUT_BVH2_WALD))
+            return fail(TBVH_E_INVALID, "BLAS %llu is a %s next to watertight triangle BLASes (tbvh_set_triangle_test): the watertight two-level kernel enters triangle BLASes only",
+                        (unsigned long long)i, b->layout == TBVH_LAYOUT_VOXELSET ? "voxel set" : "sphere BLAS");
+        if ((b->triTest != 0) != (blas[0]->triTest != 0))
+            return fail(TBVH_E_INVALID, "BLAS %llu is %s watertight mode (tbvh_set_triangle_test) and BLAS 0 is %s: a TLAS takes BLASes that are all watertight or all not, "
+                                        "because one two-level kernel, with one triangle test, traces all of them", (unsigned long long)i, b->triTest ? "in" : "not in", blas[0]->triTest ? "in" : "not in");
         // voxel sets only all together (kernels_voxel.hip); a TLAS mixing them with triangle BLASes would need the kernels_tlas* loops to enter them
         if ((b->layout == TBVH_LAYOUT_VOXELSET) != (blas[0]->layout == TBVH_LAYOUT_VOXELSET))
             return fail(TBVH_E_INVALID, "BLAS %llu: a TLAS over voxel sets takes voxel sets only (BLAS 0 has layout %d, this one %d)", (unsigned long long)i, blas[0]->layout, b->layout);
@@ -321,7 +354,8 @@ int tbvh_upload_tlas(tbvh_context* c, const void* nodes64, uint64_t nNodes, cons
     bool spheres = false;
     for (uint64_t i = 0; i < nBlas; i++) spheres |= blas[i]->layout == TBVH_LAYOUT_BVH2_WALD;
     TBVH_ENTER(c);
-    for (uint64_t i = 0; i < nBlas && !spheres; i++)   // closest-hit queries enter BVH_GPU and BVH8_CWBVH BLASes through 4-wide copies (blasView), made now; the 8-wide copies any-hit queries
+    if (blas[0]->triTest) { for (uint64_t i = 0; i < nBlas; i++) if (int r = ensureWatertightCopy(blas[i])) return r; }
+    else for (uint64_t i = 0; i < nBlas && !spheres; i++)   // closest-hit queries enter BVH_GPU and BVH8_CWBVH BLASes through 4-wide copies (blasView), made now; the 8-wide copies any-hit queries
                                                        // enter BVH_GPU and BVH4_GPU BLASes through are made by the TLAS's first any-hit query (launchQuery)
         makeCopyOnce(blas[i], kCopyWide4);
     tbvh_scene* s = newScene(c, TBVH_LAYOUT_BVH_GPU);
@@ -330,6 +364,10 @@ int tbvh_upload_tlas(tbvh_context* c, const void* nodes64, uint64_t nNodes, cons
     for (uint64_t i = 0; i < nBlas; i++) { s->tlas.blasList.push_back(blas[i]); blas[i]->usedBy.push_back(s); }
     if (int r = reclassifyTlas(s)) { tbvh_free_scene(s); return r; }
     if (int r = tlasCopy(s, nodes64, nNodes, idx, nIdx, inst, nInst)) { tbvh_free_scene(s); return r; }
+    if (s->tlas.plan.watertight && (s->tlas.plan.kind[0].family != TlasFamily::kTlas8 || s->tlas.plan.kind[1].family != TlasFamily::kTlas8)) {
+        tbvh_free_scene(s);   // (a missing kernel is an error of the upload, never another kernel at the first query)
+        return fail(TBVH_E_INVALID, "TLAS over watertight BLASes: the 8-wide TLAS tree does not fit, and no other two-level kernel has a watertight form");
+    }
     *out = s;
     return 0;
 }
@@ -360,6 +398,12 @@ static int updateBvhGpuImpl(const char* who, tbvh_scene* s, const void* nodes64,
     }
     s->nNodeBlocks = nNodes * 4; s->nTriBlocks = nIdx * 3;
     dropCopiesAfterUpdate(s);   // (the copies are of the old tree: they come back once the blob has settled — copy_policy.h)
+    if (s->triTest && !f.r) {   // a watertight scene tests the vertices this blob was made from
+        DeviceMesh dm;
+        if (int r = stageMesh(c, *mesh, dm)) return r;
+        if (int r = refreshWatertightVerts(s, dm.src)) return r;
+        HIP_TRY(hipStreamSynchronize(c->stream));   // (the staged copy goes with this call)
+    }
     return !f.r && f.general ? checkStatus(c) : f.r;
 }
 
@@ -948,6 +992,7 @@ int tbvh_set_variant(tbvh_scene* s, int v) {
     // ... and BVH_GPU / BVH4_GPU scenes one: 1 = trace the nodes as uploaded (k_bvh2 / k_bvh4) even when the scene has an 8-wide copy (tests, A/B)
     const bool ok = v == 0 || (!s->isTlas && s->layout == TBVH_LAYOUT_CWBVH && cwbvh_variant_valid(v)) || (!s->isTlas && (s->layout == TBVH_LAYOUT_BVH_GPU || s->layout == TBVH_LAYOUT_BVH4_GPU) && v == 1);
     if (!ok) return fail(TBVH_E_INVALID, "unknown variant %d for layout %d", v, s->layout);
+    if (v != 0 && s->triTest) return fail(TBVH_E_INVALID, "tbvh_set_variant: the scene is in watertight mode (tbvh_set_triangle_test); the pinned kernels have no watertight form");
     const bool viewChanges = !s->isTlas && s->copies.live() && (s->variant == 0) != (v == 0);
     s->variant = v;
     if (viewChanges) return refreshBlasDescs(s);   // (the TLASes over this BLAS enter it through the copy, or through its own nodes)

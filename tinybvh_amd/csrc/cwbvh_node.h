@@ -63,11 +63,25 @@ __device__ __forceinline__ uint32_t cw_oct(float3 D) { return 7u - ((D.x < 0 ? 4
 // Slab-test the 8 children against [0, tmax] (inclusive at both ends, like the oracle's box rule).
 // negX / negY / negZ: rD.x < 0 etc. — callers that keep them per ray (kernels_cwbvh.hip: set when a lane takes a ray) save the three compares of
 // every node test: as loop-carried bools they live in scalar lane masks that the twelve near / far selects read directly.
+// CONSERVATIVE (the watertight instantiations; DESIGN.md par. 4.6 has the derivation): every slab is widened by  2^-18 m |rD|  in t, m = the largest
+// |coordinate| any point of the node's box has relative to O.  That covers what this form rounds — (n0 - O) * rD twice, the fma once, rD itself against the
+// exact 1 / D: at most 7.1 u m |rD|, u = 2^-24 — and the 21 u m by which the exact ray may pass beside a triangle that the ROUNDED edge functions of
+// tri_test_wt accept: a child whose exact box the exact ray touches within [0, tmax], or misses by less than that, is never culled.  An axis with
+// rD = +-inf gets a NaN or -inf / +inf interval, which the min / max below ignore: it never culls.
+template <bool CONSERVATIVE = false>
 __device__ __forceinline__ CwNodeHits cw_test_node(const CwNode& nr, float3 O, float3 rD, float tmax, uint32_t octinv4, bool negX, bool negY, bool negZ) {
     const float4 n0 = nr.n0, n1 = nr.n1, n2 = nr.n2, n3 = nr.n3, n4 = nr.n4;
     const uint32_t ew = as_u32(n0.w);
     const float ax = ldexpf(rD.x, (int)(int8_t)(ew)), ay = ldexpf(rD.y, (int)(int8_t)(ew >> 8)), az = ldexpf(rD.z, (int)(int8_t)(ew >> 16));
     const float ox = (n0.x - O.x) * rD.x, oy = (n0.y - O.y) * rD.y, oz = (n0.z - O.z) * rD.z;
+    float oxn = ox, oxf = ox, oyn = oy, oyf = oy, ozn = oz, ozf = oz;   // the origin term of the near / far planes
+    if (CONSERVATIVE) {
+        const float m = cw_fmax3(__builtin_fabsf(n0.x - O.x) + ldexpf(255.f, (int)(int8_t)(ew)), __builtin_fabsf(n0.y - O.y) + ldexpf(255.f, (int)(int8_t)(ew >> 8)),
+                                 __builtin_fabsf(n0.z - O.z) + ldexpf(255.f, (int)(int8_t)(ew >> 16)));
+        const float k = m * 3.814697265625e-06f;   // 2^-18
+        const float px = k * __builtin_fabsf(rD.x), py = k * __builtin_fabsf(rD.y), pz = k * __builtin_fabsf(rD.z);
+        oxn = ox - px; oxf = ox + px; oyn = oy - py; oyf = oy + py; ozn = oz - pz; ozf = oz + pz;
+    }
     uint32_t hitmask = 0;
 #pragma unroll
     for (int half = 0; half < 2; half++) {
@@ -89,9 +103,9 @@ __device__ __forceinline__ CwNodeHits cw_test_node(const CwNode& nr, float3 O, f
 #pragma unroll
         for (int i = 0; i < 4; i++) {
             const int sh = 8 * i;
-            const float tnx = __builtin_fmaf((float)((lox >> sh) & 255), ax, ox), tfx = __builtin_fmaf((float)((hix >> sh) & 255), ax, ox);
-            const float tny = __builtin_fmaf((float)((loy >> sh) & 255), ay, oy), tfy = __builtin_fmaf((float)((hiy >> sh) & 255), ay, oy);
-            const float tnz = __builtin_fmaf((float)((loz >> sh) & 255), az, oz), tfz = __builtin_fmaf((float)((hiz >> sh) & 255), az, oz);
+            const float tnx = __builtin_fmaf((float)((lox >> sh) & 255), ax, oxn), tfx = __builtin_fmaf((float)((hix >> sh) & 255), ax, oxf);
+            const float tny = __builtin_fmaf((float)((loy >> sh) & 255), ay, oyn), tfy = __builtin_fmaf((float)((hiy >> sh) & 255), ay, oyf);
+            const float tnz = __builtin_fmaf((float)((loz >> sh) & 255), az, ozn), tfz = __builtin_fmaf((float)((hiz >> sh) & 255), az, ozf);
             const float cmin = __builtin_fmaxf(cw_fmax3(tnx, tny, tnz), 0.0f);
             const float cmax = __builtin_fminf(cw_fmin3(tfx, tfy, tfz), tmax);
             // (child bits) << (bit index), both bytes picked by SDWA selects in ONE instruction (the compiler spends a v_bfe_u32 and, for the odd

@@ -108,6 +108,54 @@ __host__ __device__ __forceinline__ bool tri_test_flat(float3 O, float3 D, float
     return ok;
 }
 
+// ---- the watertight test (WATERTIGHT_TRITEST, tiny_bvh.h:8486-8507; Woop, Benthin, Wald 2013), a scene's choice (tbvh_set_triangle_test) ----------
+// The ray's part, tiny_bvh.h:8489-8491: kz = the largest |D| component (tinybvh_maxdim), kx, ky the next two in cyclic order, swapped for D[kz] < 0;
+// Sz = rD[kz] AS THE RAY RECORD HOLDS IT, Sx = D[kx] * Sz, Sy = D[ky] * Sz.
+struct WtPre { uint32_t kx, ky, kz; float Sx, Sy, Sz; };
+__host__ __device__ __forceinline__ float wt_axis(float3 v, uint32_t k) { return k == 0u ? v.x : (k == 1u ? v.y : v.z); }
+__host__ __device__ __forceinline__ WtPre wt_precalc(float3 D, float3 rD) {
+#pragma clang fp contract(off)
+    WtPre p;
+    const uint32_t r = __builtin_fabsf(D.x) > __builtin_fabsf(D.y) ? 0u : 1u;
+    p.kz = __builtin_fabsf(D.z) > __builtin_fabsf(wt_axis(D, r)) ? 2u : r;
+    p.kx = (1u << p.kz) & 3u; p.ky = (1u << p.kx) & 3u;
+    if (wt_axis(D, p.kz) < 0) { const uint32_t s = p.kx; p.kx = p.ky; p.ky = s; }
+    p.Sz = wt_axis(rD, p.kz); p.Sx = wt_axis(D, p.kx) * p.Sz; p.Sy = wt_axis(D, p.ky) * p.Sz;
+    return p;
+}
+// The triangle's part, tiny_bvh.h:8493-8507, with EVERY product and sum rounded on its own (the region below says so whatever the file is compiled with): the
+// edge function of an edge is then the exact negative of the same edge's function in the neighbouring triangle — the same two products, subtracted the other
+// way round — so a ray cannot fall between the two.  Built with contraction (g++ -mfma fuses Cx * By - Cy * Bx) the reference's own test loses that and leaks
+// (DESIGN.md par. 4.6).  Roles as IntersectTri has them: C = vC - O, A = vA - O, B = vB - O with (vC, vA, vB) = (v0, v1, v2), so u, v are the barycentrics of
+// v1, v2 as in tri_test.  occRoles: TriOccludes' roles (tiny_bvh.h:8542-8544: A, B, C = v0, v1, v2), i.e. the caller passes (v2, v0, v1): the same three edge
+// functions, summed in another order (det and T may round differently), and u, v are then taken from V, W, which are IntersectTri's U, V.
+// Range of t: the library's, 0 <= t <= tmax (hit_wins decides among equal t), where tiny_bvh.h:8506 has t < tmax.  uvw: the three edge functions, for tests.
+__host__ __device__ __forceinline__ bool tri_test_wt(float3 O, const WtPre& p, float3 vC, float3 vA, float3 vB, float tmax, TriHit& h, Omm om = Omm{nullptr, 0u},
+                                                     uint32_t prim = 0u, bool occRoles = false, float* uvw = nullptr) {
+#pragma clang fp contract(off)
+    const float3 C = make_float3(vC.x - O.x, vC.y - O.y, vC.z - O.z);
+    const float3 A = make_float3(vA.x - O.x, vA.y - O.y, vA.z - O.z);
+    const float3 B = make_float3(vB.x - O.x, vB.y - O.y, vB.z - O.z);
+    const float Akz = wt_axis(A, p.kz), Bkz = wt_axis(B, p.kz), Ckz = wt_axis(C, p.kz);
+    const float Ax = wt_axis(A, p.kx) - p.Sx * Akz, Ay = wt_axis(A, p.ky) - p.Sy * Akz;
+    const float Bx = wt_axis(B, p.kx) - p.Sx * Bkz, By = wt_axis(B, p.ky) - p.Sy * Bkz;
+    const float Cx = wt_axis(C, p.kx) - p.Sx * Ckz, Cy = wt_axis(C, p.ky) - p.Sy * Ckz;
+    const float U = Cx * By - Cy * Bx, V = Ax * Cy - Ay * Cx, W = Bx * Ay - By * Ax;
+    if (uvw) { uvw[0] = U; uvw[1] = V; uvw[2] = W; }
+    if ((U < 0 || V < 0 || W < 0) && (U > 0 || V > 0 || W > 0)) return false;
+    const float det = U + V + W;
+    if (det == 0) return false;
+    const float Az = p.Sz * Akz, Bz = p.Sz * Bkz, Cz = p.Sz * Ckz;
+    const float T = U * Az + V * Bz + W * Cz;
+    const float invDet = 1.0f / det, t = T * invDet;
+    if (t < 0 || t > tmax) return false;
+    const float u = (occRoles ? V : U) * invDet, v = (occRoles ? W : V) * invDet;
+    // (a NaN vertex passes every compare above, as in the reference; its u, v must not become a map index: the reference reads out of bounds there)
+    if (om.map && (u != u || v != v || !omm_opaque(om, prim, u, v))) return false;
+    h.t = t; h.u = u; h.v = v;
+    return true;
+}
+
 // Put right after the three loads of a triangle record: all three go out together.  Left alone the compiler sinks the third (v0, first needed behind
 // the determinant test) into that branch — one load fewer for an edge-on triangle, a second memory round trip for every other one.
 __device__ __forceinline__ void tri_loads_together(const float4& v0) { asm volatile("" :: "v"(v0.x), "v"(v0.y), "v"(v0.z), "v"(v0.w)); }
@@ -165,7 +213,14 @@ struct QueryArgs {
     uint32_t* counter;     // dynamic ray-fetch counters (persistent kernels): poolParts of them, 256 bytes apart
     uint32_t* counterNext; // the counter area of the next launch on this context: zeroed by this one (ray_pool.h: RayPool::init); nullptr: no
     uint32_t poolParts;    // log2 of the number of partitions of the batch, each with its own counter (ray_pool.h)
-    unsigned long long* stats;  // instrumented variants: lane-utilisation counters
+    // A scene in watertight mode (tbvh_set_triangle_test) hands its kernels two more words — its vertices, 3 float4 per triangle in primitive order, fetched
+    // through a record's primitive index (v0 + e1 is not v1), and their count: a primitive index >= wtTris is never used as an address.  They SHARE the
+    // storage of two members no watertight instantiation reads (it is never instrumented and never walks the hybrid node copy), so that the struct, and with
+    // it the argument layout and the code of every other kernel, is what it was.  capi_query.hip sets them last, on the copy it launches with.
+    union {
+        unsigned long long* stats;  // instrumented variants: lane-utilisation counters
+        const float4* wtVerts;      // watertight instantiations (kernels_cwbvh.hip: WT)
+    };
     const unsigned long long* nRaysDev;  // if non-null the batch size is read from device memory (on-device queues)
     uint64_t splitBelow;   // batches of fewer rays split their last rays over idle lanes (ray_split.h); 0: never (TBVH_SPLIT_RAYS=0)
     Omm omm;               // opacity micromaps of the scene (map == nullptr: none)
@@ -177,12 +232,16 @@ struct QueryArgs {
     uint32_t* probe;
     uint32_t baseBlocks;
     uint32_t flags;        // 1 = non-temporal ray loads / hit stores, 2 = triangle records padded to 64 bytes (experiments); 16 = take the batch for coherent whatever the probe finds (variant 91); 32 = the first kernel of a two-flavor launch runs the strict schedule (PROBED == 4)
-    uint32_t hybridK;      // BVH8_CWBVH, hybrid node array (cwbvh_node.h: kNodeHybrid): nodes below this index are packed, the others one per line
+    union {
+        uint32_t hybridK;  // BVH8_CWBVH, hybrid node array (cwbvh_node.h: kNodeHybrid): nodes below this index are packed, the others one per line
+        uint32_t wtTris;   // watertight instantiations: triangles in wtVerts
+    };
     // the same two probe counts once more, for the host: two words of host-coherent pinned memory that the kernel publishing `probe` also stores
     // (cwbvh_probe.h: probe_publish); nullptr: nobody remembers this launch's verdict.  flags & 64: the launch is the incoherent flavor ALONE (capi_query.hip:
     // a buffer whose last launches were incoherent) — its block 0 takes the sample and publishes it, no wave acts on it.
     uint32_t* probeHost = nullptr;
 };
+constexpr uint32_t kStatusWatertightPrim = 2048u;   // status word: a triangle record of a watertight scene names a primitive beyond the vertices it was given
 
 // Host side: does this launch use the kernels with split rays?  Batches below the threshold, and the wavefront stages (ray count
 // known to the device only); at 16.7 M rays the tail is 5 % of a launch and those kernels' register cap costs as much as it gains.

@@ -20,11 +20,18 @@ void launch_bvh4(bool anyhit, int variant, const float4* data, const QueryArgs& 
 void launch_cwbvh_packet(bool anyhit, const float4* nodes, const float4* tris, const QueryArgs& q, uint32_t* status, uint32_t blocks, hipStream_t s);
 void launch_cwbvh(bool anyhit, int variant, const float4* nodes, const float4* tris, const QueryArgs& q, uint32_t* status,
                   uint32_t blocks, hipStream_t s, int nodeStride = 5, bool shallow = false, uint32_t blocks7 = 0xFFFFFFFFu);   // blocks7: grid of the kernels built for 7 waves per SIMD
+// a scene in watertight mode (tbvh_set_triangle_test): q.wtVerts / q.wtTris are set; packed nodes and 48-byte records only
+constexpr uint32_t kWatertightWavesPerSimd = 5;   // what the split-ray forms of those kernels are built for (kernels_cwbvh.hip): 20 one-wave workgroups per CU are resident
+void launch_cwbvh_watertight(bool anyhit, const float4* nodes, const float4* tris, const QueryArgs& q, uint32_t* status, uint32_t blocks, hipStream_t s);
 void launch_cwbvh_derive_hybrid(const float4* src, const uint32_t* perm, float4* dst, uint32_t nNodes, uint32_t hybridK, const float4* tris, hipStream_t s);   // tris: the packed 48-byte records (one per node is embedded in its line), or nullptr
 bool cwbvh_variant_valid(int variant);     // diagnostic variants of the BVH8_CWBVH kernel (tbvh_set_variant); the other layouts have none
 void launch_cwbvh_pad(const float4* src, float4* dst, uint32_t nNodes, hipStream_t s);
 void launch_cwbvh_pad_tris(const float4* src, float4* dst, uint64_t nTris, hipStream_t s);
 struct BlasDesc { const float4* nodes; const float4* tris; const uint32_t* opmap; uint32_t opmapN; uint32_t layout; };  // one per BLAS of a TLAS (layout: TBVH_LAYOUT_*)
+// ... of a TLAS over watertight BLASes (tbvh_set_triangle_test; kernels_tlas8.hip: WT): the same, then the BLAS's vertices (3 float4 per triangle in primitive
+// order) and their count.  A table of its own type, so that BlasDesc and every kernel reading it stay what they were; it travels through the same pointer.
+struct BlasDescWt { BlasDesc d; const float4* wtVerts; uint64_t wtTris; uint64_t pad[2]; };
+static_assert(sizeof(BlasDesc) == 32 && sizeof(BlasDescWt) == 64, "a watertight descriptor is two plain ones wide");
 void launch_tlas(bool anyhit, int blasLayout, const float4* tlasNodes, const uint32_t* tlasIdx, const float4* instances,
                  const BlasDesc* blas, const QueryArgs& q, uint32_t* status, uint32_t blocks, hipStream_t s);
 // 4-wide TLAS in the BVH4_GPU node format + the unified two-level kernel for BVH4_GPU BLASes (kernels_tlas4.hip)
@@ -39,7 +46,7 @@ uint64_t tlas8_cap_nodes(uint64_t nAL, uint64_t nInst);
 void launch_tlas8_build(const float4* al, uint32_t nAL, const uint32_t* idx, uint32_t nIdx, const float4* inst, uint32_t nInst, float4* nodes, uint32_t capNodes,
                         uint32_t* instRef, uint32_t capRefs, void* scratch, uint32_t* status, hipStream_t s);
 void launch_tlas8(bool anyhit, int variant, const float4* tlasNodes, const uint32_t* instRef, const float4* instances, const BlasDesc* blas, const QueryArgs& q,
-                  uint32_t* status, uint32_t blocks, hipStream_t s, uint32_t blocks7, bool mixed = false);
+                  uint32_t* status, uint32_t blocks, hipStream_t s, uint32_t blocks7, bool mixed = false, bool watertight = false);   // watertight: blas is a BlasDescWt table
 void launch_tlas2(bool anyhit, int variant, const float4* tlasNodes, const uint32_t* tlasIdx, const float4* instances, const BlasDesc* blas, const QueryArgs& q,
                   uint32_t* status, uint32_t blocks, hipStream_t s, uint32_t blocks7);   // BVH_GPU BLASes (kernels_tlas2.hip)
 // BVH_Double scenes (kernels_double.hip; records as tinybvh defines them, tiny_bvh.h:733-761, 1035-1090, 1462-1474)

@@ -37,8 +37,10 @@ constexpr int WG = 64;
 // STATS (experiment builds): q.stats[0] wave iterations, [1] sum of active lanes, [2] sum of lanes visiting a node,
 // [3] triangle-phase iterations, [4] sum of lanes in them, [5] node phases whose lanes all visit ONE node with ONE octant,
 // [6] sum of lanes in those, [7] node-phase iterations
-template <bool ANYHIT, int LDS_N, int REFILL_MIN, int TRI_MIN, bool SPEC, bool HAS_OMM, int STATS = 0, int NSTRIDE = 5, int PROBED = 0, int STEAL = 0, int MINW = 8, int TRI2 = 0>
-__global__ __launch_bounds__(WG, (STEAL || TRI2 || (SPEC && PROBED == 2)) ? MINW : 1) void k_cwbvh(const float4* __restrict__ nodes, const float4* __restrict__ tris,
+// WT (a scene in watertight mode, tbvh_set_triangle_test): the triangle test is tri_test_wt over the triangle's three VERTICES, fetched through the record's
+// primitive index from q.wtVerts (v0 + e1 is not v1), and the node test is the conservative one (cwbvh_node.h).  WT = 0 compiles to what it was.
+template <bool ANYHIT, int LDS_N, int REFILL_MIN, int TRI_MIN, bool SPEC, bool HAS_OMM, int STATS = 0, int NSTRIDE = 5, int PROBED = 0, int STEAL = 0, int MINW = 8, int TRI2 = 0, int WT = 0>
+__global__ __launch_bounds__(WG, (STEAL || TRI2 || (SPEC && PROBED == 2) || WT) ? MINW : 1) void k_cwbvh(const float4* __restrict__ nodes, const float4* __restrict__ tris,
                                               QueryArgs q, uint32_t* __restrict__ status) {
     __shared__ uint2 stk[LDS_N][WG];
     const uint32_t glane = blockIdx.x * WG + threadIdx.x;
@@ -98,6 +100,8 @@ __global__ __launch_bounds__(WG, (STEAL || TRI2 || (SPEC && PROBED == 2)) ? MINW
     bool active = false;
     uint64_t ri = 0;
     float3 O = make_float3(0, 0, 0), D = O, rD = O;
+    WtPre wp = {0u, 0u, 0u, 0.f, 0.f, 0.f};   // WT only: the ray's part of the watertight test
+    static_assert(!WT || (TRI2 == 0 && NSTRIDE != kNodeHybrid && STATS == 0), "the watertight test has no two-triangle pass, no embedded triangles, and its two words lie where the counters' and the hybrid copy's do (QueryArgs)");
     float4 hit = make_float4(0, 0, 0, 0);
     bool found = false;
     bool negX = false, negY = false, negZ = false;   // rD.x < 0 ...: per ray, kept in scalar lane masks (cw_test_node)
@@ -131,6 +135,7 @@ __global__ __launch_bounds__(WG, (STEAL || TRI2 || (SPEC && PROBED == 2)) ? MINW
                     oct = cw_oct(D);
                     octinv4 = oct * 0x01010101u;
                     negX = rD.x < 0; negY = rD.y < 0; negZ = rD.z < 0;
+                    if (WT) wp = wt_precalc(D, rD);
                     ng = make_uint2(0u, 0x80000000u); tg = make_uint2(0u, 0u); tg2 = make_uint2(0u, 0u);
                     st.reset();
                     active = true;
@@ -165,6 +170,7 @@ __global__ __launch_bounds__(WG, (STEAL || TRI2 || (SPEC && PROBED == 2)) ? MINW
                     found = false;
                     oct = cw_oct(D); octinv4 = oct * 0x01010101u;
                     negX = rD.x < 0; negY = rD.y < 0; negZ = rD.z < 0;
+                    if (WT) wp = wt_precalc(D, rD);
                     ng = part; tg = make_uint2(0u, 0u); tg2 = make_uint2(0u, 0u);
                     st.reset();
                     active = true;
@@ -214,6 +220,29 @@ __global__ __launch_bounds__(WG, (STEAL || TRI2 || (SPEC && PROBED == 2)) ? MINW
                 return tris + (tri64 ? (size_t)((__umulhi(tg.x, 0xAAAAAAABu) >> 1) + k) * 4u : (size_t)tg.x + k * 3u);   // (experiment) records padded to 64 bytes: tg.x counts float4s of the packed array
             };
             const float4* tp = record(ti);
+            if (WT) {
+                // the record gives the primitive, the scene's vertex array the triangle (a record naming no triangle of that array is no hit, and reported)
+                const float4 rec = tp[2];
+                const uint32_t prim = as_u32(rec.w);
+                TriHit h;
+                bool ok = prim < q.wtTris;
+                if (!ok) atomicOr(status, kStatusWatertightPrim);
+                else {
+                    const float4* vp = q.wtVerts + (size_t)prim * 3u;
+                    const float3 w0 = xyz(vp[0]), w1 = xyz(vp[1]), w2 = xyz(vp[2]);
+                    // closest hit: IntersectTri's roles (C, A, B = v0, v1, v2); any hit: TriOccludes' (A, B, C = v0, v1, v2) — except under a micromap, where
+                    // the reference's TriOccludes has no u, v to look up (it does not compile): there the any-hit test IS IntersectTri's, so that a ray is
+                    // occluded exactly when the closest-hit query finds it a hit
+                    ok = (ANYHIT && !HAS_OMM) ? tri_test_wt(O, wp, w2, w0, w1, hit.x, h, Omm{nullptr, 0}, prim, true)
+                                              : tri_test_wt(O, wp, w0, w1, w2, hit.x, h, HAS_OMM ? q.omm : Omm{nullptr, 0}, prim, false);
+                }
+                if (ok && (ANYHIT || (tail && grp >= 0) || hit_wins(h.t, prim, found, hit))) {
+                    found = true;
+                    if (ANYHIT) done = true;
+                    else hit = make_float4(h.t, h.u, h.v, rec.w);
+                    if (tail && grp >= 0) split_publish<ANYHIT>(split, grp, hit);
+                }
+            } else {
             const float4 e2 = tp[0], e1 = tp[1], v0 = tp[2];
             // TRI2 (experiment, round 5): a lane whose group holds a second triangle tests it in the SAME pass — all six loads out together, two tests
             // one after the other —, so a 2- or 3-triangle group costs the lane one pass less in which it sits out the node phase
@@ -252,6 +281,7 @@ __global__ __launch_bounds__(WG, (STEAL || TRI2 || (SPEC && PROBED == 2)) ? MINW
                     if (tail && grp >= 0) split_publish<ANYHIT>(split, grp, hit);
                 }
             }
+            }   // (!WT)
             if ((SPEC || PROBED == 1) && tg.y == 0) { tg = tg2; tg2 = make_uint2(0u, 0u); if (NSTRIDE == kNodeHybrid) tgn = tgn2; }
         }
         // ---- node phase ---------------------------------------------------------------------------------------
@@ -259,7 +289,7 @@ __global__ __launch_bounds__(WG, (STEAL || TRI2 || (SPEC && PROBED == 2)) ? MINW
             if (!done && tg.y == 0) {
                 if (!preHave) done = true;
                 else {
-                    const CwNodeHits r = cw_test_node(preNode, O, rD, cull_bound(hit.x), octinv4, negX, negY, negZ);
+                    const CwNodeHits r = cw_test_node<WT != 0>(preNode, O, rD, cull_bound(hit.x), octinv4, negX, negY, negZ);
                     ng = make_uint2(r.childBase, (r.hitmask & 0xFF000000u) | r.imask);
                     tg = make_uint2(r.triBase, r.hitmask & 0x00FFFFFFu);
                     if (NSTRIDE == kNodeHybrid) tgn = cw_hybrid_offset(preCi, hybridK);
@@ -280,7 +310,7 @@ __global__ __launch_bounds__(WG, (STEAL || TRI2 || (SPEC && PROBED == 2)) ? MINW
                     if (lane_rank(m) == 0) { sNodeIter++; sNode += __popcll(m); if (uni) { sRefill++; sRefilled += __popcll(m); } }   // [5], [6]: uniform node phases, lanes in them
                 }
                 if (cw_has_child(ng)) st.push(ng);
-                const CwNodeHits r = cw_test_node(cw_load_node<NSTRIDE>(nodes, ci, hybridK), O, rD, cull_bound(hit.x), octinv4, negX, negY, negZ);
+                const CwNodeHits r = cw_test_node<WT != 0>(cw_load_node<NSTRIDE>(nodes, ci, hybridK), O, rD, cull_bound(hit.x), octinv4, negX, negY, negZ);
                 ng = make_uint2(r.childBase, (r.hitmask & 0xFF000000u) | r.imask);
                 const uint2 nt = make_uint2(r.triBase, r.hitmask & 0x00FFFFFFu);
                 if (tg.y == 0) { tg = nt; if (NSTRIDE == kNodeHybrid) tgn = cw_hybrid_offset(ci, hybridK); }
@@ -326,11 +356,11 @@ __global__ __launch_bounds__(WG, (STEAL || TRI2 || (SPEC && PROBED == 2)) ? MINW
     }
 }
 
-template <bool ANYHIT, int LDS_N, int REFILL_MIN, int TRI_MIN, bool SPEC, int STATS = 0, int NSTRIDE = 5, int PROBED = 0, int STEAL = 0, int MINW = 8, int TRI2 = 0>
+template <bool ANYHIT, int LDS_N, int REFILL_MIN, int TRI_MIN, bool SPEC, int STATS = 0, int NSTRIDE = 5, int PROBED = 0, int STEAL = 0, int MINW = 8, int TRI2 = 0, int WT = 0>
 void launch_k(const float4* nodes, const float4* tris, const QueryArgs& q, uint32_t* status, uint32_t blocks, hipStream_t s) {
     // without opacity micromaps on the scene the check is compiled out (+1-2 %)
-    if (q.omm.map) hipLaunchKernelGGL((k_cwbvh<ANYHIT, LDS_N, REFILL_MIN, TRI_MIN, SPEC, true, STATS, NSTRIDE, PROBED, STEAL, MINW, TRI2>), dim3(blocks), dim3(WG), 0, s, nodes, tris, q, status);
-    else hipLaunchKernelGGL((k_cwbvh<ANYHIT, LDS_N, REFILL_MIN, TRI_MIN, SPEC, false, STATS, NSTRIDE, PROBED, STEAL, MINW, TRI2>), dim3(blocks), dim3(WG), 0, s, nodes, tris, q, status);
+    if (q.omm.map) hipLaunchKernelGGL((k_cwbvh<ANYHIT, LDS_N, REFILL_MIN, TRI_MIN, SPEC, true, STATS, NSTRIDE, PROBED, STEAL, MINW, TRI2, WT>), dim3(blocks), dim3(WG), 0, s, nodes, tris, q, status);
+    else hipLaunchKernelGGL((k_cwbvh<ANYHIT, LDS_N, REFILL_MIN, TRI_MIN, SPEC, false, STATS, NSTRIDE, PROBED, STEAL, MINW, TRI2, WT>), dim3(blocks), dim3(WG), 0, s, nodes, tris, q, status);
 }
 
 __global__ void k_pad_nodes(const float4* __restrict__ src, float4* __restrict__ dst, uint32_t nNodes) {
@@ -495,6 +525,15 @@ void launch_cwbvh(bool anyhit, int variant, const float4* nodes, const float4* t
     sel.firstOfTwo = q.probe && q.baseBlocks == 0; sel.strictFirst = (q.flags & 32u) != 0; sel.shallow = shallow; sel.expFlags = q.flags;
     for (const LaunchRow& row : kLaunchTable)
         if (row.when(sel)) { row.fn(anyhit, nodes, tris, q, status, row.cap28 ? capped : blocks, s); return; }
+}
+
+// A scene in watertight mode (launch_plan.h routes it here and nowhere else): the strict per-lane schedule with split rays, 8 stack entries in LDS, on the packed
+// nodes as uploaded, closest hit and any hit, with and without opacity micromaps.  Built for kWtWaves waves per SIMD: the six words of the ray's precalculation
+// and the vertex fetch do not fit the 64 VGPRs of 8 waves, and the closest-hit kernels with split rays not the 80 of 6, without scratch (DESIGN.md par. 4.6 has the counts).
+constexpr int kWtWaves = (int)kWatertightWavesPerSimd;
+void launch_cwbvh_watertight(bool anyhit, const float4* nodes, const float4* tris, const QueryArgs& q, uint32_t* status, uint32_t blocks, hipStream_t s) {
+    if (split_rays_wanted(q)) launch_both<8, 16, 1, false, 0, 5, 0, 16, kWtWaves, 0, 1>(anyhit, nodes, tris, q, status, blocks, s);
+    else launch_both<8, 16, 1, false, 0, 5, 0, 0, kWtWaves, 0, 1>(anyhit, nodes, tris, q, status, blocks, s);
 }
 
 namespace {

@@ -33,6 +33,31 @@ __device__ __forceinline__ float safercp(float x) {
 // =====================================================================================================================
 // traversal
 // =====================================================================================================================
+// the watertight instantiations' two differences at a call site each, so that the other instantiations' statements stay word for word what they were
+template <bool WT> __device__ __forceinline__ BlasDesc tlas8_desc(const BlasDesc* blas, uint32_t i) {
+    if constexpr (WT) return ((const BlasDescWt*)blas)[i].d;
+    else return blas[i];
+}
+template <bool WT> __device__ __forceinline__ CwNodeHits tlas8_test_node(const CwNode& n, float3 O, float3 rD, float tmax, uint32_t octinv4) {
+    if constexpr (WT) return cw_test_node<true>(n, O, rD, tmax, octinv4, rD.x < 0, rD.y < 0, rD.z < 0);
+    else return cw_test_node(n, O, rD, tmax, octinv4);
+}
+
+template <bool WT, bool ANYHIT>
+__device__ __forceinline__ bool tlas8_tri(float3 O, float3 D, const WtPre& wp, float4 v0, float4 e1, float4 e2, float tmax, TriHit& h, const BlasDesc* blas, uint32_t blasIdx,
+                                          uint32_t* status) {
+    if constexpr (WT) {
+        const uint32_t prim = as_u32(v0.w);
+        const BlasDescWt bw = ((const BlasDescWt*)blas)[blasIdx];
+        if ((uint64_t)prim >= bw.wtTris) { atomicOr(status, kStatusWatertightPrim); return false; }   // a record naming no triangle of the array: no hit, reported
+        const GlobalF4 vp(bw.wtVerts);
+        const float3 w0 = xyz(vp[(size_t)prim * 3u]), w1 = xyz(vp[(size_t)prim * 3u + 1u]), w2 = xyz(vp[(size_t)prim * 3u + 2u]);
+        const Omm om = Omm{bw.d.opmap, bw.d.opmapN};
+        // closest hit, and any hit under a micromap: IntersectTri's roles; any hit without one: TriOccludes' (kernels_cwbvh.hip has the reasons)
+        return (ANYHIT && !om.map) ? tri_test_wt(O, wp, w2, w0, w1, tmax, h, Omm{nullptr, 0u}, prim, true) : tri_test_wt(O, wp, w0, w1, w2, tmax, h, om, prim, false);
+    } else return tri_test(O, D, xyz(v0), xyz(e1), xyz(e2), tmax, h);
+}
+
 enum : uint32_t { S_NODE = 0, S_TRI = 1, S_INST = 2, S_NODE2 = 3, S_TRI2 = 4 };   // S_NODE2 / S_TRI2: a BVH_GPU BLAS under the 8-wide TLAS (MIXED)
 
 // STEAL > 0 (idle lanes needed): once the ray pool is dry, idle lanes take the top stack entry — a node group of the BLAS or of the TLAS, or a
@@ -40,7 +65,11 @@ enum : uint32_t { S_NODE = 0, S_TRI = 1, S_INST = 2, S_NODE2 = 3, S_TRI2 = 4 }; 
 // MIXED: the BLASes are BVH8_CWBVH or BVH_GPU, instance by instance (BlasDesc::layout) — the two BLAS types of the reference's traverse_tlas
 // (traverse_tlas.cl:50-72: blasType 4 = compressed-wide static geometry, 2 / 3 = Aila-Laine nodes for geometry that is refitted or rebuilt).
 // The TLAS is the 8-wide one; a BVH_GPU BLAS adds two lane states with the k_bvh2 node step and leaf loop; its stack entries are node indices.
-template <bool ANYHIT, int LDS_N, int REFILL_MIN, int PN, int PT, int PI, bool STATS, int STEAL = 0, bool FUSE = false, bool MIXED = false>
+// WT: every BLAS is in watertight mode (tbvh_set_triangle_test; `blas` is a BlasDescWt table): the triangle test is tri_test_wt over the triangle's vertices, fetched
+// through the record's primitive index from the BLAS's vertex array, with the ray's precalculation made anew from the INSTANCE-space ray at every entry; the
+// node test of both levels is the conservative one (cwbvh_node.h); and the instance transform is the reference's source as written, every product and sum
+// rounded on its own (tinybvh_transform_point / _vector, tiny_bvh.h:513-528) — the uncontracted build is the one the mode restates.  WT = 0 compiles to what it was.
+template <bool ANYHIT, int LDS_N, int REFILL_MIN, int PN, int PT, int PI, bool STATS, int STEAL = 0, bool FUSE = false, bool MIXED = false, bool WT = false>
 __device__ __forceinline__ void tlas8_body(const float4* __restrict__ tlasNodes, const uint32_t* __restrict__ instRef, const float4* __restrict__ instances,
                                            const BlasDesc* __restrict__ blas, const QueryArgs& q, uint32_t* __restrict__ status) {
     __shared__ uint2 stk[LDS_N][WG];
@@ -53,6 +82,8 @@ __device__ __forceinline__ void tlas8_body(const float4* __restrict__ tlasNodes,
     bool active = false, found = false, inBlas = false;
     uint64_t ri = 0;
     float3 O = make_float3(0, 0, 0), D = O, rD = O;   // the ray in the CURRENT space
+    static_assert(!WT || (!MIXED && !STATS), "watertight BLASes are all entered through BVH8_CWBVH arrays; no instrumented form");
+    WtPre wp = {0u, 0u, 0u, 0.f, 0.f, 0.f};           // WT: the watertight precalculation of the instance-space ray
     float4 hit = make_float4(0, 0, 0, 0);
     uint32_t hitInst = 0, rayMask = 0, state = S_NODE, curInst = 0, blasIdx = 0, oct = 0;
     int base = 0;
@@ -106,7 +137,8 @@ __device__ __forceinline__ void tlas8_body(const float4* __restrict__ tlasNodes,
                 if (m.takes) {
                     found = false; st.sp = 0; base = 0; blas2 = false; triLeft = 0;
                     if (lvl) {   // (back at its empty stack the lane "returns" to a TLAS level with nothing left: done)
-                        const BlasDesc bd = blas[blasIdx];
+                        const BlasDesc bd = tlas8_desc<WT>(blas, blasIdx);
+                        if constexpr (WT) wp = wt_precalc(D, rD);
                         inBlas = true; cur = GlobalF4(bd.nodes); btris = GlobalF4(bd.tris);
                         blas2 = MIXED && donor2;
                     } else {
@@ -186,9 +218,10 @@ __device__ __forceinline__ void tlas8_body(const float4* __restrict__ tlasNodes,
             const uint32_t ta = tg.x + ti * 3u;
             const float4 e2 = btris[ta], e1 = btris[ta + 1], v0 = btris[ta + 2];
             TriHit h;
-            if (tri_test(O, D, xyz(v0), xyz(e1), xyz(e2), hit.x, h) && (ANYHIT || (tail && grp >= 0) || hit_wins(h.t, as_u32(v0.w), curInst, found, hit, hitInst))) {
-                const BlasDesc bd = blas[blasIdx];   // opacity micromaps are per BLAS: looked up only for a candidate hit
-                if (!bd.opmap || omm_opaque(Omm{bd.opmap, bd.opmapN}, as_u32(v0.w), h.u, h.v)) {
+            // (WT: the record gives the primitive, the BLAS's vertex array the triangle; the micromap is looked up inside the watertight test — tlas8_tri_wt)
+            if (tlas8_tri<WT, ANYHIT>(O, D, wp, v0, e1, e2, hit.x, h, blas, blasIdx, status) && (ANYHIT || (tail && grp >= 0) || hit_wins(h.t, as_u32(v0.w), curInst, found, hit, hitInst))) {
+                const BlasDesc bd = tlas8_desc<WT>(blas, blasIdx);   // opacity micromaps are per BLAS: looked up only for a candidate hit
+                if (WT || !bd.opmap || omm_opaque(Omm{bd.opmap, bd.opmapN}, as_u32(v0.w), h.u, h.v)) {
                     found = true; hitInst = curInst;
                     if (ANYHIT) done = true;
                     else hit = make_float4(h.t, h.u, h.v, v0.w);
@@ -216,12 +249,22 @@ __device__ __forceinline__ void tlas8_body(const float4* __restrict__ tlasNodes,
                 const float w = __builtin_fmaf(r3.z, O.z, __builtin_fmaf(r3.x, O.x, r3.y * O.y)) + r3.w;
                 const float3 lD = make_float3(__builtin_fmaf(r0.z, D.z, __builtin_fmaf(r0.x, D.x, r0.y * D.y)), __builtin_fmaf(r1.z, D.z, __builtin_fmaf(r1.x, D.x, r1.y * D.y)),
                                               __builtin_fmaf(r2.z, D.z, __builtin_fmaf(r2.x, D.x, r2.y * D.y)));
+                if constexpr (WT) {   // the same sums left to right with nothing fused (the file is built with -ffp-contract=off): the uncontracted build of the source
+                    const float qx = ((r0.x * O.x + r0.y * O.y) + r0.z * O.z) + r0.w, qy = ((r1.x * O.x + r1.y * O.y) + r1.z * O.z) + r1.w;
+                    const float qz = ((r2.x * O.x + r2.y * O.y) + r2.z * O.z) + r2.w, qw = ((r3.x * O.x + r3.y * O.y) + r3.z * O.z) + r3.w;
+                    const float3 qD = make_float3((r0.x * D.x + r0.y * D.y) + r0.z * D.z, (r1.x * D.x + r1.y * D.y) + r1.z * D.z, (r2.x * D.x + r2.y * D.y) + r2.z * D.z);
+                    if (qw == 1) O = make_float3(qx, qy, qz);
+                    else { const float iw = 1.f / qw; O = make_float3(qx * iw, qy * iw, qz * iw); }
+                    D = qD;
+                } else {
                 if (w == 1) O = make_float3(px, py, pz);
                 else { const float iw = 1.f / w; O = make_float3(px * iw, py * iw, pz * iw); }
                 D = lD;
+                }
                 rD = make_float3(safercp(D.x), safercp(D.y), safercp(D.z));
                 blasIdx = as_u32(b0.w);
-                const BlasDesc bd = blas[blasIdx];
+                const BlasDesc bd = tlas8_desc<WT>(blas, blasIdx);
+                if constexpr (WT) wp = wt_precalc(D, rD);
                 cur = GlobalF4(bd.nodes); btris = GlobalF4(bd.tris);
                 curInst = ii; base = st.sp; inBlas = true;
                 oct = cw_oct(D);
@@ -240,7 +283,7 @@ __device__ __forceinline__ void tlas8_body(const float4* __restrict__ tlasNodes,
             if (cw_has_child(ng)) {
                 const uint32_t ci = cw_next_child(ng, oct);
                 if (cw_has_child(ng)) st.push(ng);
-                const CwNodeHits r = cw_test_node(cw_load_node(cur, ci), O, rD, cull_bound(hit.x), oct * 0x01010101u);
+                const CwNodeHits r = tlas8_test_node<WT>(cw_load_node(cur, ci), O, rD, cull_bound(hit.x), oct * 0x01010101u);
                 ng = make_uint2(r.childBase, (r.hitmask & 0xFF000000u) | r.imask);
                 tg = make_uint2(r.triBase, r.hitmask & 0x00FFFFFFu);
             }
@@ -285,23 +328,28 @@ __device__ __forceinline__ void tlas8_body(const float4* __restrict__ tlasNodes,
     }
 }
 
-template <bool ANYHIT, int LDS_N = 12, int REFILL_MIN = 16, int PN = 24, int PT = 8, int PI = 8, bool STATS = false, int STEAL = 0, int WAVES = 6, bool FUSE = false, bool MIXED = false>
+template <bool ANYHIT, int LDS_N = 12, int REFILL_MIN = 16, int PN = 24, int PT = 8, int PI = 8, bool STATS = false, int STEAL = 0, int WAVES = 6, bool FUSE = false, bool MIXED = false, bool WT = false>
 __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(WAVES, WAVES))) void k_tlas8(const float4* __restrict__ tlasNodes, const uint32_t* __restrict__ instRef,
                                                                                            const float4* __restrict__ instances, const BlasDesc* __restrict__ blas,
                                                                                            QueryArgs q, uint32_t* __restrict__ status) {
-    tlas8_body<ANYHIT, LDS_N, REFILL_MIN, PN, PT, PI, STATS, STEAL, FUSE, MIXED>(tlasNodes, instRef, instances, blas, q, status);
+    tlas8_body<ANYHIT, LDS_N, REFILL_MIN, PN, PT, PI, STATS, STEAL, FUSE, MIXED, WT>(tlasNodes, instRef, instances, blas, q, status);
 }
 
 }  // namespace
 
 void launch_tlas8(bool anyhit, int variant, const float4* tlasNodes, const uint32_t* instRef, const float4* instances, const BlasDesc* blas, const QueryArgs& q,
-                  uint32_t* status, uint32_t blocks, hipStream_t s, uint32_t blocks7, bool mixed) {
+                  uint32_t* status, uint32_t blocks, hipStream_t s, uint32_t blocks7, bool mixed, bool watertight) {
 #define TBVH_T8(...)                                                                                                                                \
     do {                                                                                                                                            \
         if (anyhit) hipLaunchKernelGGL((k_tlas8<true, __VA_ARGS__>), dim3(blocks), dim3(WG), 0, s, tlasNodes, instRef, instances, blas, q, status);  \
         else hipLaunchKernelGGL((k_tlas8<false, __VA_ARGS__>), dim3(blocks), dim3(WG), 0, s, tlasNodes, instRef, instances, blas, q, status);        \
     } while (0)
     (void)variant;
+    if (watertight) {   // every BLAS watertight, entered through BVH8_CWBVH arrays (tlas_plan.h): closest and any hit; built for 5 waves per SIMD like the single-level forms
+        if (split_rays_wanted(q)) TBVH_T8(8, 16, 24, 8, 8, false, 16, 5, true, false, true);
+        else TBVH_T8(10, 16, 24, 8, 8, false, 0, 5, true, false, true);
+        return;
+    }
     // batches below 12 M rays, and the wavefront stages (ray count known to the device only), split their last rays over idle lanes (ray_split.h)
     // 7 waves per SIMD on 28 workgroups per CU (kernels_tlas4.hip): +4…5 %.  LDS sets the stack entries kept there: 8 next to the split groups
     // (with 12 only 20 waves per CU fit; 8.3 M camera rays +7 % over 10), 10 without them

@@ -37,6 +37,7 @@ struct LaunchFacts {
     int decided[4] = {0, 0, 0, 0};   // what the scene's tuners (closest or any hit, as `any` says) have settled on, per size class
     bool hasPadded = false, hasHybrid = false, hasTrisPadded = false;   // the scene's derived copies (tbvh_scene::cw)
     bool probeMemoryOn = true, skipTiming = false;
+    int triTest = 0;              // the scene's triangle test (tbvh_set_triangle_test): 1 = watertight
 };
 
 // The kernels of a launch on a single-level BVH8_CWBVH scene (capi_query.hip: launchCwbvhKernels)
@@ -61,6 +62,8 @@ struct LaunchPlan {
     bool wantsVerdictSlot = false;       // (planShape) ... and whose verdict the host can read back: it asks for a slot and is remembered
     CwbvhShape shape = CwbvhShape::kOneKernel;   // (planShape)
     bool autoPad = false;                // (planShape) kOneKernel and the kernel behind of kFlavorAndBehind walk the padded node copy
+    bool watertight = false;             // the scene is in watertight mode: ONE kernel, a watertight instantiation of the per-lane k_cwbvh on the packed nodes — never probed,
+                                         //   so never the packet kernel or a two-flavor launch, no padded or hybrid copy, no verdict slot
 };
 
 inline uint32_t fullGrid7(const LaunchFacts& f) { return f.numCUs * 28u; }
@@ -89,7 +92,8 @@ inline int tunedSchedule(const LaunchFacts& f, int sizeClass) { return f.cohTune
 // Step 1: everything that does not read the scene's derived copies.
 inline LaunchPlan planBatch(const LaunchFacts& f) {
     LaunchPlan p;
-    const bool cwbvh = !f.isTlas && f.layout == kPlanLayoutCwbvh, noProbe = (f.expFlags & 64u) != 0;
+    p.watertight = !f.isTlas && f.triTest != 0;
+    const bool cwbvh = !f.isTlas && f.layout == kPlanLayoutCwbvh, noProbe = (f.expFlags & 64u) != 0 || p.watertight;
     p.small = !f.isTlas && !f.gridOverride && f.blobBytes < kSmallSceneBytes;
     p.huge = !p.small && f.blobBytes > kHugeSceneBytes;
     // persistent grid: 24 one-wave workgroups per CU for large batches (a third more on a small scene); small batches get about one workgroup per
@@ -114,9 +118,10 @@ inline LaunchPlan planBatch(const LaunchFacts& f) {
 // Step 2: what reads the derived copies, stated in `f` as they are after step 1's consequence (see above).
 inline void planShape(LaunchPlan& p, const LaunchFacts& f) {
     const bool copies = f.hasHybrid && f.hasTrisPadded;
-    p.autoPad = f.variant == 0 && f.hasPadded;   // nodes beyond the Infinity Cache: the padded copy (padCwbvhIfLarge)
+    p.autoPad = f.variant == 0 && f.hasPadded && !p.watertight;   // nodes beyond the Infinity Cache: the padded copy (padCwbvhIfLarge)
     const bool twoFlavors = (p.probed || p.probedSmall) && f.variant == 0 && ((!p.autoPad && copies) || p.probedSmall) && !(f.expFlags & 4u);
-    p.shape = (f.variant == 90 && copies) ? CwbvhShape::kVariant90
+    p.shape = p.watertight                ? CwbvhShape::kOneKernel   // (its own kernel: capi_query.hip, launchCwbvhKernels; tbvh_set_variant refuses such a scene anyway)
+              : (f.variant == 90 && copies) ? CwbvhShape::kVariant90
               : f.variant == 91           ? CwbvhShape::kVariant91
               : f.variant == 92           ? CwbvhShape::kVariant92
               : !twoFlavors               ? CwbvhShape::kOneKernel
@@ -129,19 +134,22 @@ inline void planShape(LaunchPlan& p, const LaunchFacts& f) {
 }
 
 // The facts and the plan as flat words, in the order of the structs' members: what tbvh_debug_launch_plan reads and writes.
-constexpr uint32_t kLaunchFactWords = 22, kLaunchPlanWords = 15;
+// (a 23rd fact word, the scene's triangle test, and a 16th plan word, `watertight`, are optional: callers from before the mode state 22 and read 15)
+constexpr uint32_t kLaunchFactWords = 22, kLaunchPlanWords = 15, kLaunchFactWordsTest = 23, kLaunchPlanWordsTest = 16;
 
-inline LaunchFacts launchFactsFromWords(const uint64_t* w) {
+inline LaunchFacts launchFactsFromWords(const uint64_t* w, uint32_t nWords = kLaunchFactWords) {
     LaunchFacts f;
     f.isTlas = w[0] != 0; f.layout = (int)w[1]; f.variant = (int)w[2]; f.blobBytes = w[3]; f.n = w[4]; f.sizeKnown = w[5] != 0; f.any = w[6] != 0;
     f.gridOverride = w[7] != 0; f.numCUs = (uint32_t)w[8]; f.blocks = (uint32_t)w[9]; f.raysPerBlock = (uint32_t)w[10]; f.expFlags = (uint32_t)w[11];
     f.cohTunerMode = (int)w[12];
     for (int k = 0; k < 4; k++) f.decided[k] = (int)w[13 + k];
     f.hasPadded = w[17] != 0; f.hasHybrid = w[18] != 0; f.hasTrisPadded = w[19] != 0; f.probeMemoryOn = w[20] != 0; f.skipTiming = w[21] != 0;
+    if (nWords > kLaunchFactWords) f.triTest = (int)w[22];
     return f;
 }
 
-inline void launchPlanToWords(const LaunchPlan& p, uint32_t* out) {
+inline void launchPlanToWords(const LaunchPlan& p, uint32_t* out, uint32_t nWords = kLaunchPlanWords) {
+    if (nWords > kLaunchPlanWords) out[kLaunchPlanWords] = p.watertight;
     const uint32_t w[kLaunchPlanWords] = {p.small, p.huge, p.probed, p.probedSmall, p.probedSmallCancelled, (uint32_t)p.sizeClass, p.blocksBase, p.blocks,
                                           p.blocks7Tlas, p.blocks7Cwbvh, p.tunerMeasures, p.soloCandidate, p.wantsVerdictSlot, (uint32_t)p.shape, p.autoPad};
     for (uint32_t k = 0; k < kLaunchPlanWords; k++) out[k] = w[k];

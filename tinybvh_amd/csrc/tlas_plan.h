@@ -25,6 +25,10 @@
 //   15. Class VOXELSET -> TlasVoxel (tbvh_upload_tlas admits voxel sets only all together).
 //   16. Class BVH_GPU -> Tlas2 (the TLAS already has their node format).
 //   17. Otherwise TlasFlat, with the class layout (0 = per instance).
+//   18. A TLAS whose BLASes are in watertight mode (tbvh_set_triangle_test; tbvh_upload_tlas admits all or none) has one class for both kinds: every BLAS
+//       through BVH8_CWBVH arrays — its own, or its 8-wide copy, which a watertight BVH_GPU / BVH4_GPU BLAS always has —, no 4-wide copies, the 8-wide tree,
+//       Tlas8 in its watertight form.  No other two-level kernel has one: a plan that comes out otherwise (the 8-wide tree does not fit) is an error of the
+//       caller's operation, never another kernel.
 // Tlas8, TlasFlat and TlasSphere push 8-byte stack entries, the others 4-byte ones.
 #pragma once
 #include <cstdint>
@@ -41,6 +45,7 @@ struct TlasBlasFacts {
     int layout = 0;
     bool pinned = false;          // variant != 0
     bool has8 = false, has4 = false;   // its 8-wide / 4-wide copy exists
+    bool watertight = false;           // its triangle test (tbvh_set_triangle_test)
 };
 
 struct TlasFacts {
@@ -62,6 +67,7 @@ struct TlasPlan {
     TlasKindPlan kind[2];         // [0] closest-hit, [1] any-hit (equal to [0] without a class of its own)
     bool anyOwn = false;          // any-hit queries have views and a class of their own
     bool spheres = false;
+    bool watertight = false;      // sentence 18
     bool want8 = false, fits8 = false, want4 = false, fits4 = false;
 };
 
@@ -94,13 +100,15 @@ inline void planTlasFit(TlasPlan& p, bool hasNodes, uint64_t cap8, uint64_t cap4
 // The plan of a TLAS.  view[0] / view[1]: nBlas entries each, the closest-hit and any-hit view of every BLAS.
 inline TlasPlan planTlas(const TlasFacts& f, TlasView* const* view) {
     TlasPlan p;
-    for (uint32_t i = 0; i < f.nBlas; i++) p.spheres |= f.blas[i].layout == kTlasLayoutSphere;
+    for (uint32_t i = 0; i < f.nBlas; i++) { p.spheres |= f.blas[i].layout == kTlasLayoutSphere; p.watertight |= f.blas[i].watertight; }
     // sentences 5 and 6 over one kind's views
     auto form = [&](int kind, bool any, bool allow4) {
         int layout = 0;
         bool bvh4 = false;
         for (uint32_t i = 0; i < f.nBlas; i++) {
-            const TlasView v = p.spheres ? kViewOwn : tlasBlasView(f.blas[i], any, allow4);
+            const TlasView v = p.spheres ? kViewOwn
+                               : p.watertight ? ((f.blas[i].layout != kTlasLayoutCwbvh && f.blas[i].has8 && !f.blas[i].pinned) ? kViewWide8 : kViewOwn)   // sentence 18
+                                              : tlasBlasView(f.blas[i], any, allow4);
             const int l = tlasViewLayout(f.blas[i], v);
             view[kind][i] = v;
             layout = i == 0 ? l : (layout == l ? layout : 0);
@@ -110,8 +118,8 @@ inline TlasPlan planTlas(const TlasFacts& f, TlasView* const* view) {
         p.kind[kind].mix = !p.spheres && layout == 0 && !bvh4;
     };
     form(0, false, true);
-    if (!p.spheres && p.kind[0].layout == 0 && !p.kind[0].mix) form(0, false, false);   // sentence 7
-    if (!p.spheres) {
+    if (!p.spheres && !p.watertight && p.kind[0].layout == 0 && !p.kind[0].mix) form(0, false, false);   // sentence 7
+    if (!p.spheres && !p.watertight) {
         form(1, true, true);
         bool differs = false;
         for (uint32_t i = 0; i < f.nBlas; i++) differs |= view[1][i] != view[0][i];
@@ -131,17 +139,17 @@ inline TlasPlan planTlas(const TlasFacts& f, TlasView* const* view) {
 
 // The facts and the plan as flat words: what tbvh_debug_tlas_plan reads and writes and tbvh_debug_tlas_state reports.
 //   facts: {BLAS count n, anyHitSeen, nodes present, 8-wide capacity in nodes, 4-wide capacity in blocks}, then one word per BLAS:
-//          layout | pinned << 8 | has an 8-wide copy << 9 | has a 4-wide copy << 10
+//          layout | pinned << 8 | has an 8-wide copy << 9 | has a 4-wide copy << 10 | watertight << 11
 //   plan:  closest-hit {class layout, mix, family, stack entry bytes}, any-hit {the same four}, any-hit has a class of its own, 8-wide tree wanted, fits,
 //          4-wide tree wanted, fits, then one word per BLAS: closest-hit view | any-hit view << 8 (0 own arrays, 1 8-wide copy, 2 4-wide copy)
 constexpr uint32_t kTlasFactHead = 5, kTlasPlanHead = 13;
 
 inline TlasBlasFacts tlasBlasFactsFromWord(uint64_t w) {
     TlasBlasFacts b;
-    b.layout = (int)(w & 0xff); b.pinned = (w >> 8 & 1) != 0; b.has8 = (w >> 9 & 1) != 0; b.has4 = (w >> 10 & 1) != 0;
+    b.layout = (int)(w & 0xff); b.pinned = (w >> 8 & 1) != 0; b.has8 = (w >> 9 & 1) != 0; b.has4 = (w >> 10 & 1) != 0; b.watertight = (w >> 11 & 1) != 0;
     return b;
 }
-inline uint64_t tlasBlasFactsToWord(const TlasBlasFacts& b) { return (uint64_t)(b.layout & 0xff) | (uint64_t)b.pinned << 8 | (uint64_t)b.has8 << 9 | (uint64_t)b.has4 << 10; }
+inline uint64_t tlasBlasFactsToWord(const TlasBlasFacts& b) { return (uint64_t)(b.layout & 0xff) | (uint64_t)b.pinned << 8 | (uint64_t)b.has8 << 9 | (uint64_t)b.has4 << 10 | (uint64_t)b.watertight << 11; }
 
 inline void tlasPlanToWords(const TlasPlan& p, const TlasView* const* view, uint32_t nBlas, uint32_t* out) {
     for (int k = 0; k < 2; k++) {
