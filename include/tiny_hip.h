@@ -69,7 +69,7 @@ public:
         Check(tbvh_upload_cwbvh(ctx, b.bvh8Data, b.usedBlocks, b.bvh8Tris, (uint64_t)b.bvh8.idxCount * 3, &s), "tbvh_upload_cwbvh");
     }
 #ifdef DOUBLE_PRECISION_SUPPORT
-    // BVH_Double (tiny_bvh.h:1035-1090): traced in fp64 over RayEx records (tbvh_upload_bvh_double; custom geometry is not supported)
+    // BVH_Double (tiny_bvh.h:1035-1090): traced in fp64 over RayEx records (tbvh_upload_bvh_double; custom geometry: SphereBVH_Double below)
     explicit Scene(const tinybvh::BVH_Double& b, int device = 0, tbvh_context* own = nullptr) : dev(device), ctx(own ? own : Context(device)) {
         Check(tbvh_upload_bvh_double(ctx, b.bvhNode, b.usedNodes, b.primIdx, b.idxCount, b.verts, b.triCount, &s), "tbvh_upload_bvh_double");
     }
@@ -164,6 +164,10 @@ public:
     void SetTlasBuilder(bool sah) { Check(tbvh_tlas_set_builder(s, sah ? 2 : 0), "tbvh_tlas_set_builder"); }
     int Device() const { return dev; }
     tbvh_context* Ctx() const { return ctx; }
+protected:
+    // for a class whose own constructor uploads (SphereBVH_Double): no scene yet, Slot() receives it
+    Scene(int device, tbvh_context* own) : dev(device), ctx(own ? own : Context(device)) {}
+    tbvh_scene** Slot() { return &s; }
 private:
     tbvh_mesh MeshOf(const tinybvh::bvhvec4slice& v, const uint32_t* indices) const {
         tbvh_mesh m;
@@ -176,6 +180,29 @@ private:
     const uint32_t* vertIdx = nullptr;   // Scene( const BVH_GPU& ): the BVH's index buffer (the caller's), vertex and triangle counts
     uint32_t nVerts = 0, meshTris = 0;
 };
+
+#ifdef DOUBLE_PRECISION_SUPPORT
+// BVH_Double over custom geometry, for the primitive of the reference's fp64 demos (tiny_bvh_custom_double.cpp, the sphere bunny of
+// tiny_bvh_anim_double.cpp): struct Sphere { bvhdbl3 pos; double r; }, 32 bytes.  It is a Scene: Intersect / IsOccluded over RayEx records (a hit writes
+// t, prim and inst and leaves u, v alone), and Scene( tlas, blas ) takes it in its BLAS list next to triangle BVH_Double scenes.  The callbacks are not
+// called: the device runs the sphere test of tiny_bvh_anim_double.cpp (tinybvh_amd.h, "double precision, custom geometry"; IsOccluded answers what
+// the closest-hit query would find, where the reference discards the callback's result).
+class SphereBVH_Double : public Scene {
+public:
+    // b after b.Build( &sphereAABB, n ); spheres: the array the callbacks read
+    SphereBVH_Double(const tinybvh::BVH_Double& b, const void* spheres32, size_t n, int device = 0, tbvh_context* own = nullptr) : Scene(device, own) {
+        Check(tbvh_upload_custom_spheres_double(Ctx(), b.bvhNode, b.usedNodes, b.primIdx, b.idxCount, spheres32, n, Slot()), "tbvh_upload_custom_spheres_double");
+    }
+    // obj.Build( &sphereAABB, n ) on the device (an LBVH, one sphere per leaf); onDevice: spheres32 is device memory
+    SphereBVH_Double(const void* spheres32, size_t n, bool onDevice = false, int device = 0, tbvh_context* own = nullptr) : Scene(device, own) {
+        Check(tbvh_build_device_custom_spheres_double(Ctx(), spheres32, n, onDevice ? 1 : 0, Slot()), "tbvh_build_device_custom_spheres_double");
+    }
+    // ... again per frame, in the same scene: the TLASes over it keep working and need only their RebuildOnDevice() for the new root box
+    void RebuildOnDevice(const void* spheres32, size_t n, bool onDevice = false) {
+        Check(tbvh_rebuild_custom_spheres_double_device(Handle(), spheres32, n, onDevice ? 1 : 0), "tbvh_rebuild_custom_spheres_double_device");
+    }
+};
+#endif
 
 // VoxelSet (tiny_bvh.h:988-1030) on the device, with the reference's method names: Set fills a brick map on the host exactly as VoxelSet::Set
 // does (tiny_bvh.h:3786-3807: the same brick numbering, so the same arrays), UpdateTopGrid (3809-3827) completes it and uploads it

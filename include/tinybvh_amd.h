@@ -636,7 +636,7 @@ int tbvh_upload_host(tbvh_context* ctx, const tbvh_hostbvh* h, const void* verts
  * Blobs are validated before anything is allocated (TBVH_E_FORMAT names the first bad entry: child or leaf range, primIdx, blasIdx, fewer than
  * 2^32 nodes, not a tree).  A BVH_DOUBLE scene takes the four _ex queries, the calls of the next section (scenes that move), tbvh_free_scene, tbvh_scene_layout (3) and
  * tbvh_scene_device_bytes; every other entry point refuses it (TBVH_E_INVALID), and the _ex queries refuse the fp32 layouts.  Custom geometry (customIntersect) in
- * double precision is not supported: upload needs triangles (fp32 sphere BLASes: the custom-geometry section below).
+ * double precision is the demos' sphere: the section "double precision, custom geometry" below (fp32 sphere BLASes: the custom-geometry section further down).
  * ---------------------------------------------------------------------------------- */
 int tbvh_upload_bvh_double(tbvh_context* ctx, const void* nodes64, uint64_t n_nodes, const uint64_t* prim_idx, uint64_t n_idx,
                            const void* verts_dbl3, uint64_t n_tris, tbvh_scene** out);
@@ -695,6 +695,44 @@ int tbvh_tlas_double_download(tbvh_scene* tlas, void* nodes64, uint64_t cap_node
                               void* instances320, uint64_t cap_inst, uint64_t* n_nodes_out);
 int tbvh_double_download(tbvh_scene* blas, void* nodes64, uint64_t cap_nodes, uint64_t* n_nodes_out);
 int tbvh_refit_double(tbvh_scene* blas, const void* verts_dbl3, uint64_t n_tris, int on_device);
+
+/* ----------------------------------------------------------------------------------
+ * double precision, custom geometry — BVH_Double::Build( customGetAABB, n ) traced through customIntersect / customIsOccluded, for the one
+ * primitive the reference's fp64 demos use (tiny_bvh_custom_double.cpp, the sphere bunny of tiny_bvh_anim_double.cpp): their
+ * struct Sphere { bvhdbl3 pos; double r; }, 32 bytes (spheres32).  Such a scene is a BVH_DOUBLE scene (tbvh_scene_layout 3): it takes the four
+ * _ex queries, tbvh_double_download, and tbvh_upload_tlas_double takes it as a BLAS next to triangle BVH_DOUBLE BLASes
+ * (tbvh_rebuild_tlas_double_device / tbvh_update_tlas_double work over such a TLAS unchanged: they read node 0 of each BLAS).
+ * tbvh_refit_double refuses it (TBVH_E_INVALID, nothing launched): there is no sphere refit in fp64, rebuild instead.
+ *
+ * The primitive test is the callback of tiny_bvh_anim_double.cpp, the form that stays right when |D| != 1:
+ *   mag = sqrt(dot(D, D)), reciMag = 1 / mag, oc = O - pos, b = dot(oc, D) * reciMag, c = dot(oc, oc) - r * r, d = b * b - c; d <= 0 misses;
+ *   t = -b - sqrt(d) is a candidate iff t < tmax_in * mag && t > 0 and records hit.t = t * reciMag
+ * each operation a separate IEEE double operation in that order.  A candidate is checked against the record's INCOMING hit.t; the ray keeps
+ * the candidate with the smallest recorded distance, then the smaller prim, then the smaller instance (spheres and triangles alike).  A hit
+ * writes t, prim and inst (ray.instIdx for a BLAS, as the reference's custom branch does; the instance under a TLAS) and leaves u, v as the
+ * record had them; a miss leaves the record untouched.
+ * DEVIATION, deliberate: occlusion is 1 iff some sphere is a candidate.  The reference's BVH_Double::IsOccluded calls customIsOccluded and
+ * discards the result (tiny_bvh.h:8278-8279), so there a custom BLAS never occludes; its fp32 path returns it.
+ *
+ * tbvh_upload_custom_spheres_double: the reference's own BVH_Double::bvhNode / primIdx after Build( customGetAABB, n ), plus the spheres.
+ *   Validated like tbvh_upload_bvh_double, against n_spheres, before anything is allocated (TBVH_E_FORMAT names the first bad entry); every r
+ *   must be finite and >= 0.  The spheres are gathered into leaf order: one 48-byte record {pos, r, prim, 0} per primIdx entry.
+ * tbvh_host_build_custom_spheres_double: tbvh_host_build_double's machinery over the boxes pos - r / pos + r (one operation per component).
+ * tbvh_build_device_custom_spheres_double / tbvh_rebuild_custom_spheres_double_device: the demos' obj.Build( &sphereAABB, n ) per frame, on
+ *   the device: the fp64 LBVH of tbvh_rebuild_tlas_double_device over the sphere boxes: 2 n - 1 nodes, root 0, one sphere per leaf, n = 1 a leaf
+ *   root.  on_device = 1: spheres32 is device memory (8-byte aligned).  A rebuild of n <= the scene's capacity allocates nothing and writes in
+ *   place, so TLASes over the scene keep their pointers and need only tbvh_rebuild_tlas_double_device( tlas, NULL, 0 ) for the new root box; a
+ *   larger n, or the first rebuild of an uploaded scene, moves the scene and re-points the TLASes over it.  Synchronous.
+ * tbvh_custom_spheres_double_download: nodes, primIdx and the gathered spheres (in primIdx order) as they are on the device; any buffer may be
+ *   NULL; *n_nodes_out / *n_idx_out (may be NULL) = the counts.
+ * ---------------------------------------------------------------------------------- */
+int tbvh_upload_custom_spheres_double(tbvh_context* ctx, const void* nodes64, uint64_t n_nodes, const uint64_t* prim_idx, uint64_t n_idx,
+                                      const void* spheres32, uint64_t n_spheres, tbvh_scene** out);
+int tbvh_host_build_custom_spheres_double(const void* spheres32, uint64_t n_spheres, tbvh_hostbvh** out);
+int tbvh_build_device_custom_spheres_double(tbvh_context* ctx, const void* spheres32, uint64_t n_spheres, int on_device, tbvh_scene** out);
+int tbvh_rebuild_custom_spheres_double_device(tbvh_scene* blas, const void* spheres32, uint64_t n_spheres, int on_device);
+int tbvh_custom_spheres_double_download(tbvh_scene* blas, void* nodes64, uint64_t cap_nodes, uint64_t* prim_idx, uint64_t cap_idx,
+                                        void* spheres32, uint64_t cap_spheres, uint64_t* n_nodes_out, uint64_t* n_idx_out);
 
 /* ----------------------------------------------------------------------------------
  * voxel sets — VoxelSet (tiny_bvh.h:988-1030, 3772-4158): a brick map over the unit cube (object space (0,0,0)-(1,1,1)) of a fixed

@@ -1372,6 +1372,93 @@ class TLAS_Double(_SceneDouble):
         return nodes, idx, inst
 
 
+# ---- double precision, custom geometry: sphere BLASes (BVH_Double::Build( customGetAABB, n ) + the double demos' sphere callback) ------------
+def _spheres_dbl(spheres) -> np.ndarray:
+    """(n, 4) float64 {x, y, z, r}: the demos' struct Sphere { bvhdbl3 pos; double r; }"""
+    return np.ascontiguousarray(spheres, np.float64).reshape(-1, 4)
+
+
+def host_build_custom_spheres_double(spheres: np.ndarray) -> HostBVHDouble:
+    """tbvh_host_build_custom_spheres_double over (n, 4) float64 spheres {x, y, z, r}: a BVH_Double over the boxes pos -/+ r."""
+    sph = _spheres_dbl(spheres)
+    h = C.c_void_p()
+    check(lib.tbvh_host_build_custom_spheres_double(_ptr(sph), sph.shape[0], C.byref(h)), "tbvh_host_build_custom_spheres_double")
+    return HostBVHDouble(h)
+
+
+class SphereBVH_Double(_SceneDouble):
+    """A BVH_Double over custom geometry whose primitives are spheres {x, y, z, r} in float64, traced on the device with the sphere callback of
+    the reference's double anim demo (kernels_double_custom.hip, DESIGN.md par. 9).  Intersect / IsOccluded take RayEx records; a hit writes
+    t, prim and inst = instIdx and leaves u, v as they were.  TLAS_Double takes it as a BLAS, alone or next to BVH_Double BLASes."""
+
+    def Build(self, spheres: np.ndarray) -> "SphereBVH_Double":
+        """The library's host builder over the boxes pos -/+ r, then Upload."""
+        self.host = host_build_custom_spheres_double(spheres)
+        return self.Upload(self.host.nodes(), self.host.prim_idx(), spheres)
+
+    def Upload(self, nodes: np.ndarray, prim_idx: np.ndarray, spheres: np.ndarray) -> "SphereBVH_Double":
+        """The reference's own arrays after Build( customGetAABB, n ): BVH_Double::bvhNode (NODE_DBL_DTYPE or raw 64-byte records), primIdx
+        (uint64) and the spheres by primitive index (tbvh_upload_custom_spheres_double: validated before anything is allocated)."""
+        nodes = np.ascontiguousarray(nodes); prim_idx = np.ascontiguousarray(prim_idx, np.uint64)
+        sph = _spheres_dbl(spheres)
+        if self._h:
+            self.free()
+            self._h = C.c_void_p()
+        check(lib.tbvh_upload_custom_spheres_double(self.ctx._h, _ptr(nodes), nodes.nbytes // 64, _ptr(prim_idx), prim_idx.size, _ptr(sph), sph.shape[0],
+                                                    C.byref(self._h)), "tbvh_upload_custom_spheres_double")
+        self.spheres = sph
+        return self
+
+    @staticmethod
+    def _sphere_arg(spheres):
+        """(pointer, n, on_device, host array or None) of a numpy array of {x, y, z, r} or a (device_pointer, n) pair"""
+        if isinstance(spheres, tuple):
+            return C.c_void_p(int(spheres[0])), int(spheres[1]), 1, None
+        a = _spheres_dbl(spheres)
+        return _ptr(a), a.shape[0], 0, a
+
+    def BuildOnDevice(self, spheres) -> "SphereBVH_Double":
+        """An LBVH over the boxes pos -/+ r, one sphere per leaf, built on the device (tbvh_build_device_custom_spheres_double).  spheres: a
+        numpy array or a (device_pointer, n) pair."""
+        ptr, n, on_device, keep = self._sphere_arg(spheres)
+        if self._h:
+            self.free()
+            self._h = C.c_void_p()
+        check(lib.tbvh_build_device_custom_spheres_double(self.ctx._h, ptr, n, on_device, C.byref(self._h)), "tbvh_build_device_custom_spheres_double")
+        self.spheres = keep
+        return self
+
+    def RebuildOnDevice(self, spheres) -> "SphereBVH_Double":
+        """A new tree over moved spheres in the same scene (tbvh_rebuild_custom_spheres_double_device); a TLAS_Double over it needs no new
+        upload, only its RebuildOnDevice() for the instance boxes."""
+        ptr, n, on_device, keep = self._sphere_arg(spheres)
+        check(lib.tbvh_rebuild_custom_spheres_double_device(self._h, ptr, n, on_device), "tbvh_rebuild_custom_spheres_double_device")
+        self.spheres = keep
+        return self
+
+    def Download(self):
+        """(nodes as NODE_DBL_DTYPE, prim_idx, the gathered spheres in prim_idx order) as they are on the device now
+        (tbvh_custom_spheres_double_download)."""
+        nn, ni = C.c_uint64(0), C.c_uint64(0)
+        check(lib.tbvh_custom_spheres_double_download(self._h, None, 0, None, 0, None, 0, C.byref(nn), C.byref(ni)), "tbvh_custom_spheres_double_download")
+        nodes = np.zeros(nn.value, NODE_DBL_DTYPE); idx = np.zeros(ni.value, np.uint64); gathered = np.zeros((ni.value, 4), np.float64)
+        check(lib.tbvh_custom_spheres_double_download(self._h, _ptr(nodes), nn.value, _ptr(idx), ni.value, _ptr(gathered), ni.value, None, None),
+              "tbvh_custom_spheres_double_download")
+        return nodes, idx, gathered
+
+    @property
+    def bounds(self) -> np.ndarray:
+        """aabbMin, aabbMax of the root box (what BLASInstanceEx::Update reads from a BLAS)."""
+        if self.spheres is None:   # device-resident spheres: the root as it is on the device
+            n = C.c_uint64(0)
+            check(lib.tbvh_double_download(self._h, None, 0, C.byref(n)), "tbvh_double_download")
+            nodes = np.zeros(n.value, NODE_DBL_DTYPE)
+            check(lib.tbvh_double_download(self._h, _ptr(nodes), n.value, None), "tbvh_double_download")
+            return np.concatenate([nodes[0]["aabbMin"], nodes[0]["aabbMax"]])
+        s = self.spheres
+        return np.concatenate([(s[:, :3] - s[:, 3:4]).min(0), (s[:, :3] + s[:, 3:4]).max(0)])
+
+
 # ---- voxel sets: VoxelSet (tiny_bvh.h:988-1030, 3772-4158) -----------------------------------------------------------------------------
 VOXEL_OBJECT_DIM = 256   # VoxelSet::objectDim, the reference's compiled value (the only one supported)
 

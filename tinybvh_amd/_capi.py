@@ -211,6 +211,12 @@ SYMBOLS = {
     "tbvh_tlas_double_download": (_i, [_vp, _vp, _u64, _vp, _u64, _vp, _u64, _vp]),
     "tbvh_double_download": (_i, [_vp, _vp, _u64, _vp]),
     "tbvh_refit_double": (_i, [_vp, _vp, _u64, _i]),
+    # ... over custom geometry: spheres {pos, r} (capi_double.hip, kernels_double_custom.hip)
+    "tbvh_upload_custom_spheres_double": (_i, [_vp, _vp, _u64, _vp, _u64, _vp, _u64, _pp]),
+    "tbvh_host_build_custom_spheres_double": (_i, [_vp, _u64, _pp]),
+    "tbvh_build_device_custom_spheres_double": (_i, [_vp, _vp, _u64, _i, _pp]),
+    "tbvh_rebuild_custom_spheres_double_device": (_i, [_vp, _vp, _u64, _i]),
+    "tbvh_custom_spheres_double_download": (_i, [_vp, _vp, _u64, _vp, _u64, _vp, _u64, _vp, _vp]),
     # VoxelSet scenes (capi_voxel.hip)
     "tbvh_upload_voxelset": (_i, [_vp, _vp, _vp, _u64, _vp, _pp]),
     "tbvh_host_build_voxelset": (_i, [_vp, _u32, _u32, _u32, _pp]),

@@ -5,7 +5,10 @@
 // descriptors], each part 16-byte aligned.  Those buffers count 16-byte blocks: a NodeDbl is 4 of them, a TriDbl 5.  Nothing else of the fp32 machinery (copies, tuners, refit, updates) applies to it: the entry
 // points of those refuse a BVH_DOUBLE scene.  Double scenes that move have calls of their own at the end of this file (the kernels are
 // kernels_double_anim.hip): tbvh_rebuild_tlas_double_device / tbvh_update_tlas_double for a TLAS, tbvh_refit_double for a BLAS, and the downloads.
+// A BVH_DOUBLE BLAS over custom geometry (spheres {pos, r}; custom_sphere_dbl.h, kernels_double_custom.hip) is the last section: `tris` holds its 48-byte
+// records, dblSpheres marks it; the _ex queries and tbvh_upload_tlas_double take it, a TLAS with such a BLAS (tlas.blasSpheres) is traced by the sphere kernels.
 #include "capi_internal.h"
+#include "custom_sphere_dbl.h"
 
 using namespace tbvh;
 using namespace tbvh_capi;
@@ -54,6 +57,13 @@ int validateDouble(const NodeDbl* n, uint64_t nNodes, const uint64_t* idx, uint6
 
 bool isDouble(const tbvh_scene* s) { return s->layout == TBVH_LAYOUT_BVH_DOUBLE; }
 
+// BLAS b as a TLAS's descriptor.  In a TLAS with a sphere BLAS (tagged) the low bit of the record pointer says which kind each BLAS is
+// (kernels_double_custom.hip reads it; records are 16-byte aligned); a TLAS of triangle BLASes keeps the plain pointers k_double reads.
+BlasDbl blasDescDbl(const tbvh_scene* b, bool tagged) {
+    const uintptr_t recs = (uintptr_t)b->tris.get() | (tagged && b->dblSpheres ? 1u : 0u);
+    return BlasDbl{(const NodeDbl*)b->nodes.get(), (const TriDbl*)recs};
+}
+
 // TLAS parts inside its one allocation, laid out for what each part may hold (dblCap*: at upload what it holds; a device rebuild needs 2 n - 1 nodes)
 struct TlasLayout { uint64_t oIdx, oInst, oBlas, total; };
 TlasLayout tlasLayout(uint64_t capNodes, uint64_t capIdx, uint64_t capInst, uint64_t nBlas) {
@@ -89,7 +99,8 @@ int launchDouble(tbvh_scene* s, RayExRec* dRays, uint64_t n, uint8_t* dOcc) {
     const uint64_t want = (n + 127) / 128, lo = (uint64_t)c->numCUs * 4u;
     const uint32_t blocks = (uint32_t)(want < lo ? lo : (want > c->blocks ? c->blocks : want));
     HIP_TRY(timedBegin(c));
-    launch_double(dOcc != nullptr, s->isTlas, q, c->status, blocks, c->stream);
+    if (s->isTlas ? s->tlas.blasSpheres : s->dblSpheres) launch_double_custom(dOcc != nullptr, s->isTlas, q, c->status, blocks, c->stream);
+    else launch_double(dOcc != nullptr, s->isTlas, q, c->status, blocks, c->stream);
     HIP_TRY(hipGetLastError());
     HIP_TRY(timedEnd(c));
     c->poolCur ^= 1; c->poolClean = true;
@@ -230,12 +241,15 @@ int tbvh_upload_tlas_double(tbvh_context* c, const void* nodes64, uint64_t nNode
         if (inst[i].blasIdx >= nBlas)
             return fail(TBVH_E_FORMAT, "tbvh_upload_tlas_double: instance %llu: blasIdx %llu >= n_blas = %llu", (unsigned long long)i, (unsigned long long)inst[i].blasIdx, (unsigned long long)nBlas);
     TBVH_ENTER(c);
+    bool spheres = false;
+    for (uint64_t i = 0; i < nBlas; i++) spheres |= blas[i]->dblSpheres;
     std::vector<BlasDbl> descs(nBlas);
-    for (uint64_t i = 0; i < nBlas; i++) descs[i] = BlasDbl{(const NodeDbl*)blas[i]->nodes.get(), (const TriDbl*)blas[i]->tris.get()};
+    for (uint64_t i = 0; i < nBlas; i++) descs[i] = blasDescDbl(blas[i], spheres);
     tbvh_scene* s = newScene(c, TBVH_LAYOUT_BVH_DOUBLE);
     if (!s) return fail(TBVH_E_NOMEM, "out of host memory");
     s->isTlas = true; s->tlas.nTlasNodes = nNodes; s->tlas.nTlasIdx = nIdx; s->tlas.nInst = nInst; s->tlas.nBlas = nBlas; s->nNodes = (uint32_t)nNodes;
     s->dblCapNodes = nNodes; s->dblCapIdx = nIdx; s->dblCapInst = nInst;
+    s->tlas.blasSpheres = spheres;
     const TlasLayout lay = tlasLayout(nNodes, nIdx, nInst, nBlas);
     const uint64_t oIdx = lay.oIdx, oInst = lay.oInst, oBlas = lay.oBlas, total = lay.total;
     if (s->nodes.alloc(total / 16) != hipSuccess) { tbvh_free_scene(s); return fail(TBVH_E_NOMEM, "tbvh_upload_tlas_double: out of device memory"); }
@@ -489,6 +503,7 @@ int tbvh_double_download(tbvh_scene* s, void* nodes64, uint64_t capNodes, uint64
 int tbvh_refit_double(tbvh_scene* s, const void* vertsDbl3, uint64_t nTris, int onDevice) {
     const char* who = "tbvh_refit_double";
     if (int r = checkDoubleScene(s, false, who)) return r;
+    if (s->dblSpheres) return fail(TBVH_E_INVALID, "%s: a sphere BLAS has no refit: tbvh_rebuild_custom_spheres_double_device builds it again", who);
     if (!vertsDbl3) return fail(TBVH_E_INVALID, "%s: null vertex array", who);
     if (nTris != s->dblTris) return fail(TBVH_E_INVALID, "%s: %llu triangles, the scene was uploaded with %llu", who, (unsigned long long)nTris, (unsigned long long)s->dblTris);
     if (onDevice && (((uintptr_t)vertsDbl3) & 7)) return fail(TBVH_E_INVALID, "%s: device vertices must be 8-byte aligned", who);
@@ -519,6 +534,191 @@ int tbvh_refit_double(tbvh_scene* s, const void* vertsDbl3, uint64_t nTris, int 
     HIP_TRY(timedBegin(c));
     HIP_TRY(launch_refit_dbl((NodeDbl*)s->nodes.get(), nNodes, (TriDbl*)s->tris.get(), s->dblRecs, dv, nTris, parent + nNodes, s->dblLeaves, parent, parent + 2 * (size_t)nNodes, c->stream));
     HIP_TRY(timedEnd(c));
+    return 0;
+}
+
+}  // extern "C"
+
+// ---- custom geometry: sphere BLASes (custom_sphere_dbl.h, kernels_double_custom.hip) --------------------------------------------------------
+
+namespace {
+
+// every r finite and >= 0 (a NaN r would make a NaN box; a negative one an inverted box around a sphere the test still hits)
+int validateSpheresDbl(const SphereDbl* sph, uint64_t n, const char* who) {
+    for (uint64_t i = 0; i < n; i++)
+        if (!(sph[i].r >= 0) || !(sph[i].r <= 1.79769313486231570815e+308))
+            return fail(TBVH_E_FORMAT, "%s: sphere %llu: r = %g is not a finite number >= 0", who, (unsigned long long)i, sph[i].r);
+    return 0;
+}
+
+int checkSphereSceneDbl(const tbvh_scene* s, const char* who) {
+    if (int r = checkDoubleScene(s, false, who)) return r;
+    if (!s->dblSpheres) return fail(TBVH_E_INVALID, "%s: a triangle BVH_DOUBLE scene, not a sphere BLAS", who);
+    return 0;
+}
+
+// A new tree over n spheres in scene s (device build).  The scene's arrays hold 2 n - 1 nodes and n records; smaller ones (a larger n, or the first rebuild
+// of an uploaded scene) are replaced, and the descriptors of the TLASes over the scene re-pointed BEFORE anything is built.  n <= capacity: in place, no allocation.
+int buildSphereTreeDbl(tbvh_scene* s, const char* who, const void* spheres32, uint64_t n, int onDevice) {
+    tbvh_context* c = s->ctx;
+    const uint64_t nNodes = 2 * n - 1, nodeBlocks = nNodes * (sizeof(NodeDbl) / 16), recBlocks = n * (sizeof(SphereRecDbl) / 16);
+    if (s->buildScratchFor < n || !s->buildScratch) {
+        s->buildScratchFor = 0;
+        const size_t bytes = spheres_dbl_build_scratch_bytes((uint32_t)n, &s->sortTempBytes);
+        if (s->buildScratch.alloc(bytes) != hipSuccess) { (void)hipGetLastError(); return fail(TBVH_E_NOMEM, "%s: out of device memory (%zu bytes of build scratch)", who, bytes); }
+        s->buildScratchFor = n;
+    }
+    const void* dSph = spheres32;
+    if (!onDevice) {
+        if (s->vertStage.reserve(n * sizeof(SphereDbl)) != hipSuccess) { (void)hipGetLastError(); return fail(TBVH_E_NOMEM, "%s: out of device memory (staging %llu spheres)", who, (unsigned long long)n); }
+        HIP_TRY(hipMemcpyAsync(s->vertStage, spheres32, n * sizeof(SphereDbl), hipMemcpyHostToDevice, c->stream));
+        dSph = s->vertStage.get();
+    }
+    if (s->nodes.count() < nodeBlocks || s->tris.count() < recBlocks) {
+        DevBuf<float4> nodes, recs;
+        if (nodes.alloc(nodeBlocks) != hipSuccess || recs.alloc(recBlocks) != hipSuccess) { (void)hipGetLastError(); return fail(TBVH_E_NOMEM, "%s: out of device memory (%llu spheres)", who, (unsigned long long)n); }
+        HIP_TRY(hipStreamSynchronize(c->stream));   // (queries in flight read the old arrays)
+        DevBuf<float4> oldNodes = std::move(s->nodes), oldRecs = std::move(s->tris);
+        s->nodes = std::move(nodes); s->tris = std::move(recs);
+        const int r = forEachTlasOver(s, [&](tbvh_scene* t) {
+            const TlasParts p = tlasParts(t);
+            for (uint64_t i = 0; i < t->tlas.nBlas; i++) {
+                if (t->tlas.blasList[i] != s) continue;
+                const BlasDbl d = blasDescDbl(s, t->tlas.blasSpheres);
+                if (hipMemcpy(p.blas + i, &d, sizeof d, hipMemcpyHostToDevice) != hipSuccess) return fail(TBVH_E_HIP, "%s: re-pointing a TLAS failed", who);
+            }
+            return 0;
+        });
+        if (r) { (void)oldNodes.release(); (void)oldRecs.release(); return r; }   // (a descriptor may still point at the old arrays: leak them rather than dangle)
+    }
+    HIP_TRY(timedBegin(c));
+    // (a smaller n than the scratch was sized for carves smaller parts out of the same allocation)
+    HIP_TRY(launch_spheres_dbl_build((NodeDbl*)s->nodes.get(), s->tris.get(), dSph, (uint32_t)n, s->buildScratch, s->sortTempBytes, c->stream));
+    HIP_TRY(timedEnd(c));
+    HIP_TRY(hipStreamSynchronize(c->stream));   // (the caller's spheres may change; a launch error surfaces here)
+    s->nNodes = (uint32_t)nNodes;
+    s->dblTris = n; s->dblRecs = n;
+    return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int tbvh_upload_custom_spheres_double(tbvh_context* c, const void* nodes64, uint64_t nNodes, const uint64_t* primIdx, uint64_t nIdx, const void* spheres32,
+                                      uint64_t nSpheres, tbvh_scene** out) {
+    const char* who = "tbvh_upload_custom_spheres_double";
+    if (!c || !nodes64 || !primIdx || !spheres32 || !out || !nIdx || !nSpheres) return fail(TBVH_E_INVALID, "%s: null/empty argument", who);
+    if (int r = validateDouble((const NodeDbl*)nodes64, nNodes, primIdx, nIdx, nSpheres, who, "n_spheres")) return r;
+    if (int r = validateSpheresDbl((const SphereDbl*)spheres32, nSpheres, who)) return r;
+    TBVH_ENTER(c);
+    tbvh_scene* s = newScene(c, TBVH_LAYOUT_BVH_DOUBLE);
+    if (!s) return fail(TBVH_E_NOMEM, "out of host memory");
+    s->dblSpheres = true;
+    DevBuf<uint64_t> dIdx;
+    DevBuf<double> dSph;
+    auto bail = [&](int code, const char* what) { tbvh_free_scene(s); return fail(code, "%s: %s", who, what); };
+    if (s->nodes.alloc(nNodes * (sizeof(NodeDbl) / 16)) != hipSuccess || s->tris.alloc(nIdx * (sizeof(SphereRecDbl) / 16)) != hipSuccess ||
+        dIdx.alloc(nIdx) != hipSuccess || dSph.alloc(nSpheres * 4) != hipSuccess)
+        return bail(TBVH_E_NOMEM, "out of device memory");
+    if (hipMemcpyAsync(s->nodes, nodes64, nNodes * sizeof(NodeDbl), hipMemcpyHostToDevice, c->stream) != hipSuccess ||
+        hipMemcpyAsync(dIdx, primIdx, nIdx * 8, hipMemcpyHostToDevice, c->stream) != hipSuccess ||
+        hipMemcpyAsync(dSph, spheres32, nSpheres * sizeof(SphereDbl), hipMemcpyHostToDevice, c->stream) != hipSuccess)
+        return bail(TBVH_E_HIP, "copy to the device failed");
+    launch_gather_spheres_dbl(dIdx, dSph.get(), s->tris.get(), nIdx, c->stream);
+    if (hipGetLastError() != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) return bail(TBVH_E_HIP, "sphere gather failed");
+    s->nNodes = (uint32_t)nNodes;
+    s->dblTris = nSpheres; s->dblRecs = nIdx;
+    *out = s;
+    return 0;
+}
+
+int tbvh_host_build_custom_spheres_double(const void* spheres32, uint64_t n, tbvh_hostbvh** out) {
+    const char* who = "tbvh_host_build_custom_spheres_double";
+    if (!spheres32 || !out || n == 0) return fail(TBVH_E_INVALID, "%s: null/empty argument", who);
+    if (n > 0x3fffffffull) return fail(TBVH_E_INVALID, "%s: too many spheres", who);
+    const SphereDbl* sph = (const SphereDbl*)spheres32;
+    if (int r = validateSpheresDbl(sph, n, who)) return r;
+    tbvh_hostbvh* h = new (std::nothrow) tbvh_hostbvh;
+    if (!h) return fail(TBVH_E_NOMEM, "out of host memory");
+    h->layout = TBVH_LAYOUT_BVH_DOUBLE;
+    try {
+        // as tbvh_host_build_double: the topology of the fp32 builder on the boxes translated by their centre, every node box then recomputed in double
+        double lo[3] = {kDblFarHost, kDblFarHost, kDblFarHost}, hi[3] = {-kDblFarHost, -kDblFarHost, -kDblFarHost};
+        for (uint64_t i = 0; i < n; i++) {
+            double mn[3], mx[3];
+            sphere_box_dbl(sph[i], mn, mx);
+            for (int a = 0; a < 3; a++) { lo[a] = std::min(lo[a], mn[a]); hi[a] = std::max(hi[a], mx[a]); }
+        }
+        double ctr[3];
+        for (int a = 0; a < 3; a++) ctr[a] = lo[a] * 0.5 + hi[a] * 0.5;
+        std::vector<float> boxes(n * 6);
+        for (uint64_t i = 0; i < n; i++) {
+            double mn[3], mx[3];
+            sphere_box_dbl(sph[i], mn, mx);
+            for (int a = 0; a < 3; a++) { boxes[i * 6 + a] = (float)(mn[a] - ctr[a]); boxes[i * 6 + 3 + a] = (float)(mx[a] - ctr[a]); }
+        }
+        BuildParams bp;   // (as tbvh_host_build_custom_spheres)
+        build_bvh2_boxes(boxes.data(), (uint32_t)n, bp, h->bvh2);
+        doubleFromTopology(h->bvh2, [&](uint64_t p, double* mn, double* mx) { sphere_box_dbl(sph[p], mn, mx); }, h->dnodes);
+        h->didx.assign(h->bvh2.primIdx.begin(), h->bvh2.primIdx.end());
+    } catch (const std::bad_alloc&) {
+        delete h;
+        return fail(TBVH_E_NOMEM, "out of host memory while building");
+    }
+    *out = h;
+    return 0;
+}
+
+int tbvh_build_device_custom_spheres_double(tbvh_context* c, const void* spheres32, uint64_t n, int onDevice, tbvh_scene** out) {
+    const char* who = "tbvh_build_device_custom_spheres_double";
+    if (!c || !spheres32 || !out || !n) return fail(TBVH_E_INVALID, "%s: null/empty argument", who);
+    if (n > 0x7fffffffull) return fail(TBVH_E_INVALID, "%s: %llu spheres: at most 2^31 - 1", who, (unsigned long long)n);
+    if (onDevice && (((uintptr_t)spheres32) & 7)) return fail(TBVH_E_INVALID, "%s: device spheres must be 8-byte aligned", who);
+    TBVH_ENTER(c);
+    tbvh_scene* s = newScene(c, TBVH_LAYOUT_BVH_DOUBLE);
+    if (!s) return fail(TBVH_E_NOMEM, "out of host memory");
+    s->dblSpheres = true;
+    if (int r = buildSphereTreeDbl(s, who, spheres32, n, onDevice)) { tbvh_free_scene(s); return r; }
+    *out = s;
+    return 0;
+}
+
+int tbvh_rebuild_custom_spheres_double_device(tbvh_scene* s, const void* spheres32, uint64_t n, int onDevice) {
+    const char* who = "tbvh_rebuild_custom_spheres_double_device";
+    if (int r = checkSphereSceneDbl(s, who)) return r;
+    if (!spheres32 || !n) return fail(TBVH_E_INVALID, "%s: null/empty argument", who);
+    if (n > 0x7fffffffull) return fail(TBVH_E_INVALID, "%s: %llu spheres: at most 2^31 - 1", who, (unsigned long long)n);
+    if (onDevice && (((uintptr_t)spheres32) & 7)) return fail(TBVH_E_INVALID, "%s: device spheres must be 8-byte aligned", who);
+    tbvh_context* c = s->ctx;
+    TBVH_ENTER(c);
+    return buildSphereTreeDbl(s, who, spheres32, n, onDevice);
+}
+
+int tbvh_custom_spheres_double_download(tbvh_scene* s, void* nodes64, uint64_t capNodes, uint64_t* primIdx, uint64_t capIdx, void* spheres32, uint64_t capSpheres,
+                                        uint64_t* nNodesOut, uint64_t* nIdxOut) {
+    const char* who = "tbvh_custom_spheres_double_download";
+    if (int r = checkSphereSceneDbl(s, who)) return r;
+    tbvh_context* c = s->ctx;
+    TBVH_ENTER(c);
+    const uint64_t nNodes = s->nNodes, nIdx = s->dblRecs;
+    if (nNodesOut) *nNodesOut = nNodes;
+    if (nIdxOut) *nIdxOut = nIdx;
+    if (nodes64 && capNodes < nNodes) return fail(TBVH_E_INVALID, "%s: node buffer too small", who);
+    if (primIdx && capIdx < nIdx) return fail(TBVH_E_INVALID, "%s: index buffer too small", who);
+    if (spheres32 && capSpheres < nIdx) return fail(TBVH_E_INVALID, "%s: sphere buffer too small", who);
+    if (!nodes64 && !primIdx && !spheres32) return 0;
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    if (nodes64) HIP_TRY(hipMemcpy(nodes64, s->nodes.get(), nNodes * sizeof(NodeDbl), hipMemcpyDeviceToHost));
+    if (primIdx || spheres32) {   // the records {pos, r, prim, 0} come back whole and are taken apart here
+        std::vector<SphereRecDbl> recs;
+        try { recs.resize(nIdx); } catch (const std::bad_alloc&) { return fail(TBVH_E_NOMEM, "out of host memory"); }
+        HIP_TRY(hipMemcpy(recs.data(), s->tris.get(), nIdx * sizeof(SphereRecDbl), hipMemcpyDeviceToHost));
+        for (uint64_t k = 0; k < nIdx; k++) {
+            if (spheres32) std::memcpy((SphereDbl*)spheres32 + k, &recs[k], sizeof(SphereDbl));
+            if (primIdx) primIdx[k] = recs[k].prim;
+        }
+    }
     return 0;
 }
 

@@ -343,6 +343,10 @@ struct tbvh_scene {
     uint64_t dblCapNodes = 0, dblCapIdx = 0, dblCapInst = 0;
     uint64_t dblTris = 0, dblRecs = 0;
     uint32_t dblLeaves = 0;
+    // a BVH_DOUBLE BLAS over custom geometry (capi_double.hip, custom_sphere_dbl.h): `tris` holds 48-byte sphere records, dblRecs of them over dblTris
+    // spheres; a device build sizes `nodes` / `tris` for the 2 n - 1 nodes / n records of its tree and keeps its scratch in buildScratch, host spheres
+    // are staged in vertStage.  sceneBytes counts the allocations, so a rebuild in place leaves the scene's bytes as they were.
+    bool dblSpheres = false;
 };
 
 struct BLASInstanceCheck { float m[32]; float mn[3]; uint32_t blasIdx; float mx[3]; uint32_t mask; uint32_t pad[8]; };

@@ -45,7 +45,8 @@ SceneBytes sceneBytesByWord(const tbvh_scene* s) {
     const bool triangles = !s->isTlas && !dbl && !sphere && !voxel;   // BVH_GPU, BVH4_GPU, BVH8_CWBVH
     if (triangles) w[0] += (s->nNodeBlocks + s->nTriBlocks) * 16;
     if (tlas32) w[0] += t.nTlasNodes * 64 + t.nTlasIdx * 4 + t.nInst * 192;
-    if (blas64) w[0] += (uint64_t)s->nNodes * sizeof(NodeDbl) + s->dblRecs * sizeof(TriDbl);
+    if (blas64 && !s->dblSpheres) w[0] += (uint64_t)s->nNodes * sizeof(NodeDbl) + s->dblRecs * sizeof(TriDbl);
+    if (blas64 && s->dblSpheres) w[0] += (s->nodes.count() + s->tris.count()) * 16;   // (as an fp32 sphere BLAS: what it holds at its allocation)
     if (sphere || voxel) w[0] += (s->nodes.count() + s->tris.count()) * 16;
     w[1] += (s->cw.padded.count() + s->cw.hybrid.count() + s->cw.trisPadded.count()) * 16;
     if (s->copies.copy8) w[2] += sceneBytes(s->copies.copy8);

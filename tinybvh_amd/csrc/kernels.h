@@ -96,6 +96,15 @@ hipError_t launch_tlas_dbl_rebuild(NodeDbl* tlasNodes, uint64_t* tlasIdx, Instan
 void launch_parents_dbl(const NodeDbl* nodes, uint32_t nNodes, uint32_t* parent, uint32_t* leaves, uint32_t* frontA, uint32_t* frontB, uint32_t* nLeavesOut, hipStream_t s);
 hipError_t launch_refit_dbl(NodeDbl* nodes, uint32_t nNodes, TriDbl* tris, uint64_t nRecs, const double* verts, uint64_t nTris, const uint32_t* leaves,
                             uint32_t nLeaves, const uint32_t* parent, uint32_t* flags, hipStream_t s);
+// BVH_Double over custom geometry: spheres {pos, r} of 32 bytes, gathered into 48-byte records {pos, r, prim, 0} (custom_sphere_dbl.h).  Queries and the
+// upload's gather are kernels_double_custom.hip: q.tris holds a sphere BLAS's records; under a TLAS the low bit of a BlasDbl's `tris` marks a sphere BLAS.
+// The build is kernels_double_anim.hip's LBVH with the spheres as its box source: 2 n - 1 nodes over the boxes pos -/+ r into nodes / recs48 (a record
+// carries its primIdx entry); the scratch is one allocation of spheres_dbl_build_scratch_bytes(n).
+void launch_double_custom(bool anyhit, bool tlas, const DoubleArgs& q, uint32_t* status, uint32_t blocks, hipStream_t s);
+void launch_gather_spheres_dbl(const uint64_t* primIdx, const void* spheres32, void* recs48, uint64_t nIdx, hipStream_t s);
+size_t spheres_dbl_build_scratch_bytes(uint32_t n, size_t* sortTempBytes);
+hipError_t launch_spheres_dbl_build(NodeDbl* nodes, void* recs48, const void* spheres32, uint32_t n, void* scratch, size_t sortTempBytes,
+                                    hipStream_t s);
 
 // VoxelSet scenes (kernels_voxel.hip): vox = one set's [top grid 16 | grid 32768 | bricks] words; tlasNodes != nullptr: a BVH_GPU-format TLAS over
 // BLASInstance records whose BLASes are all voxel sets (BlasDesc::nodes = each set's array)

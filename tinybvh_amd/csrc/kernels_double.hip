@@ -21,6 +21,7 @@
 // sp > blasBase, the TLAS only once the BLAS is left, so a popped index always belongs to the tree `nodes` points at, overflow or not.  Persistent one-wave workgroups with per-lane ray replacement
 // (ray_pool.h), as in kernels_query.hip.
 #include "device_common.h"
+#include "double_step.h"
 #include "lane_stack.h"
 #include "ray_pool.h"
 #include "kernels.h"
@@ -32,42 +33,6 @@ namespace {
 constexpr int WG = 64;
 constexpr int LDS_N = 16;
 constexpr int REFILL_MIN = 16;
-constexpr double kDblFar = 1e300;              // BVH_DBL_FAR, tiny_bvh.h:145
-
-struct D3 { double x, y, z; };
-
-__device__ __forceinline__ double dmin(double a, double b) { return a < b ? a : b; }   // tinybvh_min (double), tiny_bvh.h:447
-__device__ __forceinline__ double dmax(double a, double b) { return a > b ? a : b; }   // tinybvh_max (double), tiny_bvh.h:448
-__device__ __forceinline__ D3 sub(D3 a, D3 b) { return D3{a.x - b.x, a.y - b.y, a.z - b.z}; }
-__device__ __forceinline__ D3 cross(D3 a, D3 b) { return D3{a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x}; }
-__device__ __forceinline__ double dot(D3 a, D3 b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
-
-// tinybvh_transform_point / tinybvh_transform_vector (tiny_bvh.h:576-590)
-__device__ __forceinline__ D3 xform_point(D3 v, const double* T) {
-    const D3 r{T[0] * v.x + T[1] * v.y + T[2] * v.z + T[3], T[4] * v.x + T[5] * v.y + T[6] * v.z + T[7], T[8] * v.x + T[9] * v.y + T[10] * v.z + T[11]};
-    const double w = T[12] * v.x + T[13] * v.y + T[14] * v.z + T[15];
-    if (w == 1) return r;
-    const double rw = 1. / w;
-    return D3{r.x * rw, r.y * rw, r.z * rw};
-}
-__device__ __forceinline__ D3 xform_vector(D3 v, const double* T) {
-    return D3{T[0] * v.x + T[1] * v.y + T[2] * v.z, T[4] * v.x + T[5] * v.y + T[6] * v.z, T[8] * v.x + T[9] * v.y + T[10] * v.z};
-}
-__device__ __forceinline__ double guarded_rcp(double d) { return d > 1e-24 ? (1.0 / d) : (d < -1e-24 ? (1.0 / d) : kDblFar); }   // tiny_bvh.h:8336-8338
-
-// BVH_Double::BVHNode::Intersect (tiny_bvh.h:8363-8375), culling against `bound` (the closest hit so far plus the slack)
-__device__ __forceinline__ double node_dist(const double2* n, D3 O, D3 rD, double bound) {
-    const double2 a = n[0], b = n[1], c = n[2];   // {mn.x, mn.y}, {mn.z, mx.x}, {mx.y, mx.z}
-    const double tx1 = (a.x - O.x) * rD.x, tx2 = (b.y - O.x) * rD.x;
-    double tmin = dmin(tx1, tx2), tmax = dmax(tx1, tx2);
-    const double ty1 = (a.y - O.y) * rD.y, ty2 = (c.x - O.y) * rD.y;
-    tmin = dmax(tmin, dmin(ty1, ty2));
-    tmax = dmin(tmax, dmax(ty1, ty2));
-    const double tz1 = (b.x - O.z) * rD.z, tz2 = (c.y - O.z) * rD.z;
-    tmin = dmax(tmin, dmin(tz1, tz2));
-    tmax = dmin(tmax, dmax(tz1, tz2));
-    return (tmax >= tmin && tmin < bound && tmax >= 0) ? tmin : kDblFar;
-}
 
 template <bool ANYHIT, bool TLAS>
 __global__ __launch_bounds__(WG) void k_double(DoubleArgs q, uint32_t* __restrict__ status) {

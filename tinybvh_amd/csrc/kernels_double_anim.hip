@@ -20,6 +20,10 @@
 // The tree is an LBVH instead of the host builder's binned-SAH tree: a different but valid TLAS — hit records do not depend on the TLAS
 // shape (device_common.h: hit_wins_dbl), up to rays that a box of one tree culls within the eight-ulp slack and the other's does not.
 //
+// Sphere BLAS build (tbvh_build_device_custom_spheres_double / tbvh_rebuild_custom_spheres_double_device): steps 2-5 with a second box source, the
+// boxes pos -/+ r of spheres {pos, r}; the same numbering (2 n - 1 nodes, root 0, one sphere per leaf, n = 1 a leaf root), the leaf thread also
+// writes the 48-byte record the traversal reads.
+//
 // BLAS refit.  The reference has no BVH_Double::Refit; this is the fp64 twin of kernels_refit.hip: same topology, new vertices.  One
 // thread per leaf rewrites its TriDbl records ({v0, e1 = v1 - v0, e2 = v2 - v0, prim}: the subtractions of k_gather_tris_dbl; prim comes
 // from the record), takes the leaf box from the three VERTICES (v0 + e1 would round) and climbs by parent index under the same
@@ -31,6 +35,7 @@
 
 #include <cstdio>
 
+#include "custom_sphere_dbl.h"
 #include "dev_buf.h"
 #include "device_common.h"
 #include "kernels.h"
@@ -173,6 +178,66 @@ __global__ void k_lbvh_nodes_dbl(const uint32_t* __restrict__ sortedIdx, const I
     }
 }
 
+
+// ---- the second box source: spheres {pos, r} (a BVH_Double over custom geometry: custom_sphere_dbl.h, kernels_double_custom.hip) -----------------
+// The demos' obj.Build( &sphereAABB, n ) per frame: steps 2-5 above over the boxes pos -/+ r.  Step 1 has no records to update: it only reduces the
+// centre bounds.  Step 5's leaf thread also writes the gathered record {pos, r, prim, 0} the traversal reads (the record carries its primIdx entry).
+__global__ void k_sphere_centres_dbl(const SphereDbl* __restrict__ sph, uint32_t n, uint64_t* __restrict__ centreBounds) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    double cLo[3] = {kDblFar, kDblFar, kDblFar}, cHi[3] = {-kDblFar, -kDblFar, -kDblFar};
+    if (i < n) {
+        double mn[3], mx[3];
+        sphere_box_dbl(sph[i], mn, mx);
+        for (int a = 0; a < 3; a++) {
+            const double c = 0.5 * mn[a] + 0.5 * mx[a];
+            if (c > -kDblFar && c < kDblFar) cLo[a] = cHi[a] = c;   // (a NaN or infinite box takes no part in the bounds; its key is 0)
+        }
+    }
+    lbvh::wave_centre_bounds(cLo, cHi, centreBounds);
+}
+
+__global__ void k_morton_spheres_dbl(const SphereDbl* __restrict__ sph, const uint64_t* __restrict__ centreBounds, uint32_t n, uint64_t* __restrict__ keys,
+                                     uint32_t* __restrict__ vals) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    double mn[3], mx[3];
+    sphere_box_dbl(sph[i], mn, mx);
+    uint32_t q[3];
+    for (int a = 0; a < 3; a++) {
+        const double c = 0.5 * mn[a] + 0.5 * mx[a];
+        q[a] = lbvh::morton_axis(c, lbvh::ordered_decode(centreBounds[a]), lbvh::ordered_decode(centreBounds[3 + a]), 2097151u);
+    }
+    keys[i] = lbvh::morton63(q);
+    vals[i] = i;
+}
+
+__global__ void k_lbvh_nodes_spheres_dbl(const uint32_t* __restrict__ sortedIdx, const SphereDbl* __restrict__ sph, const uint32_t* __restrict__ parent,
+                                         const uint32_t* __restrict__ slot, uint32_t* __restrict__ flags, uint32_t n, NodeDbl* __restrict__ nodes,
+                                         SphereRecDbl* __restrict__ recs) {
+    const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= n) return;
+    const uint32_t p = sortedIdx[k];   // (< n: a permutation of the values k_morton_spheres_dbl wrote)
+    const SphereDbl s = sph[p];
+    recs[k] = SphereRecDbl{{s.pos[0], s.pos[1], s.pos[2]}, s.r, p, 0};
+    const uint32_t id = n - 1 + k;
+    NodeDbl* ln = nodes + (n == 1 ? 0u : slot[id]);   // with a single sphere the leaf IS the root
+    sphere_box_dbl(s, ln->mn, ln->mx);
+    ln->leftFirst = k; ln->triCount = 1;
+    if (n == 1) return;
+    __threadfence();
+    uint32_t node = parent[id];
+    for (;;) {
+        if (atomicAdd(flags + node, 1u) == 0u) return;   // first to arrive: the sibling subtree is not finished yet
+        __threadfence();
+        const uint32_t at = slot[node], c = 1u + 2u * node;
+        write_union(nodes, at, c);
+        nodes[at].leftFirst = c; nodes[at].triCount = 0;
+        if (node == 0) return;
+        __threadfence();
+        node = parent[node];
+    }
+}
+
 // ---- refit ----------------------------------------------------------------------------------------------------------------------------
 // Once per scene, ONE workgroup: walk the tree from the root level by level (two frontier lists in global memory), parent[] of every node
 // reached and the list of the leaves reached.  A tree (validated at upload) reaches every node at most once, so at most nNodes entries are
@@ -251,7 +316,7 @@ struct Scratch {
     size_t total;
 };
 // one allocation, carved up here (every part 256-byte aligned); base may be null to just measure
-Scratch carve(void* base, uint32_t n, size_t sortTempBytes) {
+Scratch carve(void* base, uint32_t n, size_t sortTempBytes, bool xforms = true) {
     tbvh_capi::ScratchCarver c(base);
     const size_t N = n;
     Scratch s;
@@ -260,7 +325,7 @@ Scratch carve(void* base, uint32_t n, size_t sortTempBytes) {
     s.parent = c.take<uint32_t>(2 * N); s.slot = c.take<uint32_t>(2 * N);   // 2n - 1 Karras ids
     s.flags = c.take<uint32_t>(N);
     s.bounds = c.take<uint64_t>(8);
-    s.xforms = c.take<double>(16 * N);   // staged host transforms
+    s.xforms = xforms ? c.take<double>(16 * N) : nullptr;   // staged host transforms (a TLAS's only)
     s.sortTemp = c.take_bytes(sortTempBytes);
     s.total = c.total();
     return s;
@@ -298,6 +363,36 @@ hipError_t launch_tlas_dbl_rebuild(NodeDbl* tlasNodes, uint64_t* tlasIdx, Instan
     TBVH_STEP("TLAS_Double rebuild", "topology");
     hipLaunchKernelGGL(k_lbvh_nodes_dbl, dim3(nb), dim3(bs), 0, s, sc.valsB, instances, sc.parent, sc.slot, sc.flags, n, tlasNodes, tlasIdx);
     TBVH_STEP("TLAS_Double rebuild", "nodes");
+    return hipGetLastError();
+}
+
+size_t spheres_dbl_build_scratch_bytes(uint32_t n, size_t* sortTempBytes) {
+    size_t tmp = 0;
+    hipcub::DeviceRadixSort::SortPairs(nullptr, tmp, (const uint64_t*)nullptr, (uint64_t*)nullptr, (const uint32_t*)nullptr, (uint32_t*)nullptr, (int)n, 0, 64);
+    *sortTempBytes = tmp;
+    return carve(nullptr, n, tmp, false).total;
+}
+
+hipError_t launch_spheres_dbl_build(NodeDbl* nodes, void* recs48, const void* spheres32, uint32_t n, void* scratch, size_t sortTempBytes, hipStream_t s) {
+    const Scratch sc = carve(scratch, n, sortTempBytes, false);
+    const SphereDbl* sph = (const SphereDbl*)spheres32;
+    hipError_t e;
+    if ((e = reset_centre_bounds(sc.bounds, 8, s)) != hipSuccess) return e;
+    if ((e = hipMemsetAsync(sc.flags, 0, (size_t)n * 4, s)) != hipSuccess) return e;
+    const uint32_t bs = 128, nb = (n + bs - 1) / bs;
+    hipLaunchKernelGGL(k_sphere_centres_dbl, dim3(nb), dim3(bs), 0, s, sph, n, sc.bounds);
+    TBVH_STEP("SphereBVH_Double build", "centre bounds");
+    hipLaunchKernelGGL(k_morton_spheres_dbl, dim3(nb), dim3(bs), 0, s, sph, sc.bounds, n, sc.keysA, sc.valsA);
+    TBVH_STEP("SphereBVH_Double build", "morton keys");
+    size_t tmp = sortTempBytes;
+    if ((e = hipcub::DeviceRadixSort::SortPairs(sc.sortTemp, tmp, sc.keysA, sc.keysB, sc.valsA, sc.valsB, (int)n, 0, 64, s)) != hipSuccess) {
+        fprintf(stderr, "[tinybvh_amd] SphereBVH_Double build: radix sort (%zu temp bytes): %s\n", sortTempBytes, hipGetErrorString(e));
+        return e;
+    }
+    if (n > 1) hipLaunchKernelGGL(k_lbvh_topology_dbl, dim3(nb), dim3(bs), 0, s, sc.keysB, n, sc.parent, sc.slot);
+    TBVH_STEP("SphereBVH_Double build", "topology");
+    hipLaunchKernelGGL(k_lbvh_nodes_spheres_dbl, dim3(nb), dim3(bs), 0, s, sc.valsB, sph, sc.parent, sc.slot, sc.flags, n, nodes, (SphereRecDbl*)recs48);
+    TBVH_STEP("SphereBVH_Double build", "nodes");
     return hipGetLastError();
 }
 
