@@ -102,6 +102,8 @@ class RefCustomDouble:
         L.cdref_tlas_free.argtypes = [_vp]
         L.cdref_tlas_blob.argtypes = [_vp, _i, C.POINTER(_vp)]; L.cdref_tlas_blob.restype = _u64
         L.cdref_tlas_intersect.argtypes = [_vp, _vp, _u64]
+        L.cdref_occluded.argtypes = [_vp, _vp, _u64, _vp]
+        L.cdref_tlas_occluded.argtypes = [_vp, _vp, _u64, _vp]
 
     def build_spheres(self, sph):
         s = np.ascontiguousarray(sph, np.float64).reshape(-1, 4)
@@ -131,6 +133,13 @@ class RefCustomDouble:
         r = np.ascontiguousarray(rays).copy()
         (self.lib.cdref_tlas_intersect if tlas else self.lib.cdref_intersect)(h, _p(r), r.shape[0])
         return r
+
+    def occluded(self, h, rays, tlas=False):
+        """IsOccluded of a triangle BLAS or of a TLAS over triangle BLASes (the custom branch discards its callback's answer)"""
+        r = np.ascontiguousarray(rays)
+        out = np.zeros(r.shape[0], np.uint8)
+        (self.lib.cdref_tlas_occluded if tlas else self.lib.cdref_occluded)(h, _p(r), r.shape[0], _p(out))
+        return out
 
     def tlas_build(self, inst, blas_handles):
         """inst is updated in place, as BVH_Double::Build( BLASInstanceEx*, ... ) does"""

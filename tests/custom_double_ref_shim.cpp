@@ -5,7 +5,8 @@
 // fp64 path rounds once per operation), into the pytest temp dir; nothing of the reference is copied into the repository.  The callbacks below are
 // this project's own: a sphere {pos, r} of doubles per primitive, tested by the operations of include/tinybvh_amd.h ("double precision, custom
 // geometry"), component by component.  The callbacks take no context, so every sphere BLAS gets a slot of its own (at most kSlots per process).
-// There is no occlusion entry: the reference discards its callback's answer (tiny_bvh.h:8278-8279), which the library does not restate.
+// The occlusion entries (cdref_occluded, cdref_tlas_occluded) are for triangle scenes only: over custom geometry the reference discards its
+// callback's answer (tiny_bvh.h:8278-8279), which the library does not restate.
 #include <cmath>
 #include <cstdint>
 #include <cstring>
@@ -135,6 +136,29 @@ void cdref_tlas_intersect(void* h, void* rays128, uint64_t n) {
     Tlas* t = (Tlas*)h;
     RayEx* r = (RayEx*)rays128;
     for (uint64_t i = 0; i < n; i++) t->tlas.Intersect(r[i]);
+}
+
+// BVH_Double::IsOccluded of a triangle BLAS (for triangle scenes only: the custom branch discards its callback's answer)
+void cdref_occluded(void* h, const void* rays128, uint64_t n, uint8_t* out) {
+    const BVH_Double& bvh = ((Blas*)h)->bvh;
+    const RayEx* r = (const RayEx*)rays128;
+    for (uint64_t i = 0; i < n; i++) out[i] = bvh.IsOccluded(r[i]) ? 1 : 0;
+}
+// BVH_Double::IsOccluded of a TLAS over triangle BLASes.  IsOccludedTLAS hands the BLASes a RayEx whose hit.t it never sets (tiny_bvh.h:8322): what the
+// BLAS walk compares against is whatever the stack held.  fillStack writes the ray's own hit.t into every slot of the stack the call is about to use, so
+// that read gives the value IntersectTLAS copies there (tmp.hit = ray.hit).  Whether that took is checked against the reference itself (tests/test_double_edges_host.py: a ray is occluded iff the closest
+// hit of the reference's Intersect lies before tmax), so a compiler that keeps the slot elsewhere fails a test instead of passing one.
+__attribute__((noinline)) void fillStack(double v) {
+    volatile double slots[8192];
+    for (int i = 0; i < 8192; i++) slots[i] = v;
+}
+void cdref_tlas_occluded(void* h, const void* rays128, uint64_t n, uint8_t* out) {
+    Tlas* t = (Tlas*)h;
+    const RayEx* r = (const RayEx*)rays128;
+    for (uint64_t i = 0; i < n; i++) {
+        fillStack(r[i].hit.t);
+        out[i] = t->tlas.IsOccluded(r[i]) ? 1 : 0;
+    }
 }
 
 }  // extern "C"

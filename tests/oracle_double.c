@@ -15,8 +15,9 @@
  * library's rule (tinybvh_amd/csrc/device_common.h: hit_wins_dbl, cull_bound_dbl): at equal t a found hit is replaced by the smaller prim,
  * then the smaller instance, and box culls allow eight ulps (t * (1 + 2^-49)) beyond the closest hit.
  *
- * This file is pinned to the real reference only through the checks in tests/test_double_host.py (rule 0 against a brute-force fp64 closest
- * hit over all triangles, t bit-identical where the minimum is unique): it is not compiled against tiny_bvh.h.
+ * This file is not compiled against tiny_bvh.h.  It is pinned to the real reference by tests/test_double_edges_host.py (rule 0 against
+ * BVH_Double::Intersect and IsOccluded on a TLAS of hostile instances, every byte) and by tests/test_double_host.py (rule 0 against a brute-force
+ * fp64 closest hit over all triangles, t bit-identical where the minimum is unique).
  */
 #include <math.h>
 #include <stdint.h>
