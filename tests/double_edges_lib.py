@@ -2,11 +2,11 @@
 tlas_edges_lib.py, written in float64 over RAYEX_DTYPE and INSTANCE_EX_DTYPE (nothing is cast from the fp32 records).
 
 Two rows of BLASes, by the rule of capi_double.hip (launchDouble): a TLAS_Double with a sphere BLAS (tlas.blasSpheres, set by tbvh_upload_tlas_double)
-is traced by k_double_custom<*, true>, every other by k_double<*, true>.
+is traced by the sphere form k_double<true, *, true>, every other by the triangle-only form k_double<false, *, true>.
 
     row  BLASes                            kernel
-    T    BVH_Double + BVH_Double           k_double<*, true>           oracle_double.c
-    M    SphereBVH_Double + BVH_Double     k_double_custom<*, true>    oracle_custom_double.c
+    T    BVH_Double + BVH_Double           k_double<false, *, true>    oracle_double.c
+    M    SphereBVH_Double + BVH_Double     k_double<true, *, true>     oracle_custom_double.c
 
 Meshes and spheres lie on a grid of 2^-16, the instances' centres on multiples of 5: under the axis-aligned families an axis ray through a vertex
 keeps instance-space coordinates EQUAL to the vertex's, so (plane - O) is exactly 0 where rD is inf (closest hit) or 1e300 (any hit, guarded_rcp):

@@ -1,5 +1,5 @@
 /* oracle_custom_double.c — a restatement, in plain C, of BVH_Double over custom geometry (spheres) as the reference's double demos trace it
- * (tiny_bvh_custom_double.cpp, tiny_bvh_anim_double.cpp), the checker of kernels_double_custom.hip.
+ * (tiny_bvh_custom_double.cpp, tiny_bvh_anim_double.cpp), the checker of the sphere forms of kernels_double.hip.
  *
  * The callback is the one of tiny_bvh_anim_double.cpp, the form that stays right when |D| != 1:
  *   mag = sqrt(dot(D, D)), reciMag = 1 / mag, oc = O - pos, b = dot(oc, D) * reciMag, c = dot(oc, oc) - r * r, d = b * b - c; d <= 0 misses;

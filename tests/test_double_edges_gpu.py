@@ -2,13 +2,15 @@
 IsOccluded equal to the restated oracle under the library's rule (rule 1), which tests/test_double_edges_host.py pins to the real reference.
 
 Two rows, picked by the rule of capi_double.hip (launchDouble): a TLAS_Double one of whose BLASes is a sphere BLAS (tlas.blasSpheres, set by
-tbvh_upload_tlas_double) is traced by k_double_custom<*, true>, every other by k_double<*, true>.
+tbvh_upload_tlas_double) is traced by the sphere form of the one kernel, k_double<true, *, true>, which reads the tag bit of every BLAS descriptor; every
+other by the triangle-only form k_double<false, *, true>, which reads plain pointers.
 
-    T   BVH_Double + BVH_Double          k_double<*, true>          oracle_double.c
-    M   SphereBVH_Double + BVH_Double    k_double_custom<*, true>   oracle_custom_double.c
+    T   BVH_Double + BVH_Double          k_double<false, *, true>   oracle_double.c
+    M   SphereBVH_Double + BVH_Double    k_double<true, *, true>    oracle_custom_double.c
 
 The library has no call that names the kernel of an fp64 TLAS.  What row M shows of it: a hit on a sphere instance comes back with the u, v the record went in
-with, which only k_double_custom does (test_fresh_rays asserts it).
+with, which only the sphere form does (test_fresh_rays asserts it).  Row T's scene goes through BOTH forms in
+test_triangle_scene_answers_the_same_through_both_forms: listing a sphere BLAS that no instance references is enough to pick the sphere form.
 
 Two trees per row: the host-built TLAS as uploaded, and the same TLAS after RebuildOnDevice(), whose expectation is the oracle on Download() and whose
 instance records equal the host's Update bit for bit.
@@ -47,9 +49,21 @@ class Row:
         self.blases = [(tb.SphereBVH_Double if kind == "sph" else tb.BVH_Double)(ctx).Upload(nodes, idx, prims) for kind, nodes, idx, prims in self.host.blas]
 
 
+@pytest.fixture(scope="module")
+def rows(ctx):
+    """the rows made so far, by name: row T serves its own tests and the test of both forms"""
+    return {}
+
+
+def row_of(rows, ctx, name):
+    if name not in rows:
+        rows[name] = Row(ctx, name)
+    return rows[name]
+
+
 @pytest.fixture(scope="module", params=["T", "M"])
-def row(request, ctx):
-    return Row(ctx, request.param)
+def row(request, ctx, rows):
+    return row_of(rows, ctx, request.param)
 
 
 class Live:
@@ -77,17 +91,23 @@ class Live:
         return got
 
 
-@pytest.fixture(scope="module", params=["uploaded", "rebuilt"])
-def live(request, ctx, row, odbl, ocd):
+def make_live(kind, ctx, row, odbl, ocd, blases=None):
+    """the row's TLAS over `blases` (the row's own list by default), as uploaded or after RebuildOnDevice()"""
     sc = row.host
-    if request.param == "uploaded":
-        tl = tb.TLAS_Double(ctx).Upload(sc.tn, sc.ti, sc.inst, row.blases)
+    blases = row.blases if blases is None else blases
+    if kind == "uploaded":
+        tl = tb.TLAS_Double(ctx).Upload(sc.tn, sc.ti, sc.inst, blases)
         return Live(row, tl, (sc.tn, sc.ti), sc.inst, oracle_of(sc, odbl, ocd))
-    tl = tb.TLAS_Double(ctx).Upload(sc.tn, sc.ti, sc.raw_inst, row.blases)   # the records go up WITHOUT inverse and bounds
+    tl = tb.TLAS_Double(ctx).Upload(sc.tn, sc.ti, sc.raw_inst, blases)   # the records go up WITHOUT inverse and bounds
     tl.RebuildOnDevice()
     tn, ti, inst = tl.Download()
     same_instances(inst, sc.inst, "device instance update")
     return Live(row, tl, (tn, ti), inst, oracle_of(sc, odbl, ocd))
+
+
+@pytest.fixture(scope="module", params=["uploaded", "rebuilt"])
+def live(request, ctx, row, odbl, ocd):
+    return make_live(request.param, ctx, row, odbl, ocd)
 
 
 # ---- 1 -----------------------------------------------------------------------------------------------------------------------------------
@@ -104,6 +124,27 @@ def test_fresh_rays(live):
         got = live.check(dec, "decorated")
         on_sphere = E.changed(got, dec) & sc.on_sphere(got)
         assert (got["u"][on_sphere] == 7.0).all() and (got["v"][on_sphere] == 9.0).all() and (got["u"][E.changed(got, dec) & ~on_sphere] != 7.0).all()
+
+
+@pytest.mark.parametrize("kind", ["uploaded", "rebuilt"])
+def test_triangle_scene_answers_the_same_through_both_forms(kind, ctx, rows, odbl, ocd):
+    """Row T's scene twice: as it is (the triangle-only form), and with a one-sphere SphereBVH_Double added to the BLAS list, which no instance references and
+    no ray can reach (the sphere form: every descriptor carries the tag bit's place, and both triangle BLASes have it clear).  Each upload's records and
+    occlusion bytes are oracle_double.c's over the tree it holds, and the two uploads answer alike."""
+    row = row_of(rows, ctx, "T")
+    sc = row.host
+    one = np.array([[0.25, -0.5, 0.125, 0.75]])
+    h = tb.host_build_custom_spheres_double(one)
+    sphere = tb.SphereBVH_Double(ctx).Upload(h.nodes(), h.prim_idx(), one)
+    plain = make_live(kind, ctx, row, odbl, ocd)
+    tagged = make_live(kind, ctx, row, odbl, ocd, row.blases + [sphere])
+    assert (sc.inst["blasIdx"] < len(row.blases)).all()
+    a, b = plain.check(sc.rays, f"{kind}, triangle BLASes only"), tagged.check(sc.rays, f"{kind}, a sphere BLAS listed")
+    E.same_records(a, b, f"{kind}: the two forms, Intersect")
+    assert E.changed(a, sc.rays).sum() > 4000
+    for name, rays in batches(sc, plain.fresh).items():
+        a, b = plain.check_occ(rays, f"{kind}, triangle BLASes only, {name}"), tagged.check_occ(rays, f"{kind}, a sphere BLAS listed, {name}")
+        E.same_bytes(a, b, f"{kind}: the two forms, IsOccluded, {name}")
 
 
 # ---- 2 -----------------------------------------------------------------------------------------------------------------------------------

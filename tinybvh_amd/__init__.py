@@ -1388,7 +1388,7 @@ def host_build_custom_spheres_double(spheres: np.ndarray) -> HostBVHDouble:
 
 class SphereBVH_Double(_SceneDouble):
     """A BVH_Double over custom geometry whose primitives are spheres {x, y, z, r} in float64, traced on the device with the sphere callback of
-    the reference's double anim demo (kernels_double_custom.hip, DESIGN.md par. 9).  Intersect / IsOccluded take RayEx records; a hit writes
+    the reference's double anim demo (the sphere forms of kernels_double.hip, DESIGN.md par. 9).  Intersect / IsOccluded take RayEx records; a hit writes
     t, prim and inst = instIdx and leaves u, v as they were.  TLAS_Double takes it as a BLAS, alone or next to BVH_Double BLASes."""
 
     def Build(self, spheres: np.ndarray) -> "SphereBVH_Double":

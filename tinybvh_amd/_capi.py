@@ -211,7 +211,7 @@ SYMBOLS = {
     "tbvh_tlas_double_download": (_i, [_vp, _vp, _u64, _vp, _u64, _vp, _u64, _vp]),
     "tbvh_double_download": (_i, [_vp, _vp, _u64, _vp]),
     "tbvh_refit_double": (_i, [_vp, _vp, _u64, _i]),
-    # ... over custom geometry: spheres {pos, r} (capi_double.hip, kernels_double_custom.hip)
+    # ... over custom geometry: spheres {pos, r} (capi_double.hip, the sphere forms of kernels_double.hip)
     "tbvh_upload_custom_spheres_double": (_i, [_vp, _vp, _u64, _vp, _u64, _vp, _u64, _pp]),
     "tbvh_host_build_custom_spheres_double": (_i, [_vp, _u64, _pp]),
     "tbvh_build_device_custom_spheres_double": (_i, [_vp, _vp, _u64, _i, _pp]),

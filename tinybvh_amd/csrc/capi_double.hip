@@ -5,8 +5,8 @@
 // descriptors], each part 16-byte aligned.  Those buffers count 16-byte blocks: a NodeDbl is 4 of them, a TriDbl 5.  Nothing else of the fp32 machinery (copies, tuners, refit, updates) applies to it: the entry
 // points of those refuse a BVH_DOUBLE scene.  Double scenes that move have calls of their own at the end of this file (the kernels are
 // kernels_double_anim.hip): tbvh_rebuild_tlas_double_device / tbvh_update_tlas_double for a TLAS, tbvh_refit_double for a BLAS, and the downloads.
-// A BVH_DOUBLE BLAS over custom geometry (spheres {pos, r}; custom_sphere_dbl.h, kernels_double_custom.hip) is the last section: `tris` holds its 48-byte
-// records, dblSpheres marks it; the _ex queries and tbvh_upload_tlas_double take it, a TLAS with such a BLAS (tlas.blasSpheres) is traced by the sphere kernels.
+// A BVH_DOUBLE BLAS over custom geometry (spheres {pos, r}; custom_sphere_dbl.h) is the last section: `tris` holds its 48-byte records, dblSpheres
+// marks it; the _ex queries and tbvh_upload_tlas_double take it, a TLAS with such a BLAS (tlas.blasSpheres) is traced by k_double's sphere forms.
 #include "capi_internal.h"
 #include "custom_sphere_dbl.h"
 
@@ -58,7 +58,7 @@ int validateDouble(const NodeDbl* n, uint64_t nNodes, const uint64_t* idx, uint6
 bool isDouble(const tbvh_scene* s) { return s->layout == TBVH_LAYOUT_BVH_DOUBLE; }
 
 // BLAS b as a TLAS's descriptor.  In a TLAS with a sphere BLAS (tagged) the low bit of the record pointer says which kind each BLAS is
-// (kernels_double_custom.hip reads it; records are 16-byte aligned); a TLAS of triangle BLASes keeps the plain pointers k_double reads.
+// (k_double's sphere forms read it; records are 16-byte aligned); a TLAS of triangle BLASes keeps the plain pointers the triangle-only forms read.
 BlasDbl blasDescDbl(const tbvh_scene* b, bool tagged) {
     const uintptr_t recs = (uintptr_t)b->tris.get() | (tagged && b->dblSpheres ? 1u : 0u);
     return BlasDbl{(const NodeDbl*)b->nodes.get(), (const TriDbl*)recs};
@@ -99,8 +99,7 @@ int launchDouble(tbvh_scene* s, RayExRec* dRays, uint64_t n, uint8_t* dOcc) {
     const uint64_t want = (n + 127) / 128, lo = (uint64_t)c->numCUs * 4u;
     const uint32_t blocks = (uint32_t)(want < lo ? lo : (want > c->blocks ? c->blocks : want));
     HIP_TRY(timedBegin(c));
-    if (s->isTlas ? s->tlas.blasSpheres : s->dblSpheres) launch_double_custom(dOcc != nullptr, s->isTlas, q, c->status, blocks, c->stream);
-    else launch_double(dOcc != nullptr, s->isTlas, q, c->status, blocks, c->stream);
+    launch_double(s->isTlas ? s->tlas.blasSpheres : s->dblSpheres, dOcc != nullptr, s->isTlas, q, c->status, blocks, c->stream);
     HIP_TRY(hipGetLastError());
     HIP_TRY(timedEnd(c));
     c->poolCur ^= 1; c->poolClean = true;
@@ -195,6 +194,91 @@ void updateInstanceDbl(InstanceDbl& in, const double* bb) {
     }
 }
 
+// every r finite and >= 0 (a NaN r would make a NaN box; a negative one an inverted box around a sphere the test still hits)
+int validateSpheresDbl(const SphereDbl* sph, uint64_t n, const char* who) {
+    for (uint64_t i = 0; i < n; i++)
+        if (!(sph[i].r >= 0) || !(sph[i].r <= 1.79769313486231570815e+308))
+            return fail(TBVH_E_FORMAT, "%s: sphere %llu: r = %g is not a finite number >= 0", who, (unsigned long long)i, sph[i].r);
+    return 0;
+}
+
+// The two kinds of BLAS an upload makes: the caller's primitives (primBytes each) go up and `gather` makes one record of recBytes per index entry in the
+// scene's `tris`.  spheres: the primitives are SphereDbl (dblSpheres); primWhat / gatherFailed: the messages' words.
+struct BlasKindDbl {
+    size_t primBytes, recBytes;
+    void (*gather)(const uint64_t* primIdx, const void* prims, void* recs, uint64_t nIdx, hipStream_t s);
+    bool spheres;
+    const char *primWhat, *gatherFailed;
+};
+const BlasKindDbl kTriBlasDbl{72, sizeof(TriDbl), launch_gather_tris_dbl, false, "n_tris", "triangle gather failed"};
+const BlasKindDbl kSphereBlasDbl{sizeof(SphereDbl), sizeof(SphereRecDbl), launch_gather_spheres_dbl, true, "n_spheres", "sphere gather failed"};
+
+// A BLAS upload: the checks of the blob, before anything is allocated, then nodes, index list and primitives go up and the records are gathered.
+int uploadBlasDbl(tbvh_context* c, const char* who, const BlasKindDbl& k, const void* nodes64, uint64_t nNodes, const uint64_t* primIdx, uint64_t nIdx,
+                  const void* prims, uint64_t nPrims, tbvh_scene** out) {
+    if (!c || !nodes64 || !primIdx || !prims || !out || !nIdx || !nPrims) return fail(TBVH_E_INVALID, "%s: null/empty argument", who);
+    if (int r = validateDouble((const NodeDbl*)nodes64, nNodes, primIdx, nIdx, nPrims, who, k.primWhat)) return r;
+    if (k.spheres)
+        if (int r = validateSpheresDbl((const SphereDbl*)prims, nPrims, who)) return r;
+    TBVH_ENTER(c);
+    tbvh_scene* s = newScene(c, TBVH_LAYOUT_BVH_DOUBLE);
+    if (!s) return fail(TBVH_E_NOMEM, "out of host memory");
+    s->dblSpheres = k.spheres;
+    DevBuf<uint64_t> dIdx;
+    DevBuf<double> dPrims;
+    auto bail = [&](int code, const char* what) { tbvh_free_scene(s); return fail(code, "%s: %s", who, what); };
+    if (s->nodes.alloc(nNodes * (sizeof(NodeDbl) / 16)) != hipSuccess || s->tris.alloc(nIdx * (k.recBytes / 16)) != hipSuccess ||
+        dIdx.alloc(nIdx) != hipSuccess || dPrims.alloc(nPrims * (k.primBytes / 8)) != hipSuccess)
+        return bail(TBVH_E_NOMEM, "out of device memory");
+    if (hipMemcpyAsync(s->nodes, nodes64, nNodes * sizeof(NodeDbl), hipMemcpyHostToDevice, c->stream) != hipSuccess ||
+        hipMemcpyAsync(dIdx, primIdx, nIdx * 8, hipMemcpyHostToDevice, c->stream) != hipSuccess ||
+        hipMemcpyAsync(dPrims, prims, nPrims * k.primBytes, hipMemcpyHostToDevice, c->stream) != hipSuccess)
+        return bail(TBVH_E_HIP, "copy to the device failed");
+    k.gather(dIdx, dPrims.get(), s->tris.get(), nIdx, c->stream);
+    if (hipGetLastError() != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) return bail(TBVH_E_HIP, k.gatherFailed);
+    s->nNodes = (uint32_t)nNodes;
+    s->dblTris = nPrims; s->dblRecs = nIdx;
+    *out = s;
+    return 0;
+}
+
+// what the four _ex queries refuse before they look at the rays, in this order; dRays: a device ray array, or null
+int checkExQuery(const tbvh_scene* s, const char* who, const void* dRays = nullptr) {
+    TBVH_REFUSE_CUSTOM(s, who);
+    if (!isDouble(s)) return fail(TBVH_E_INVALID, "%s: scene layout %d is not BVH_DOUBLE (RayEx queries need a BVH_Double scene)", who, s->layout);
+    if (((uintptr_t)dRays) & 15) return fail(TBVH_E_INVALID, "%s: ray array must be 16-byte aligned", who);
+    return 0;
+}
+
+// A double tree over n double boxes through the fp32 box builder (the recipe above): the bounds of the boxes, their centre, the boxes translated
+// by it and rounded to float, build_bvh2_boxes with the caller's parameters, then every node box again in double.  h: the caller's new tbvh_hostbvh,
+// which goes to *out or, on a failure, away.
+int hostBuildOverBoxesDbl(tbvh_hostbvh* h, uint64_t n, const std::function<void(uint64_t i, double* mn, double* mx)>& box, const BuildParams& bp, tbvh_hostbvh** out) {
+    h->layout = TBVH_LAYOUT_BVH_DOUBLE;
+    try {
+        double lo[3] = {kDblFarHost, kDblFarHost, kDblFarHost}, hi[3] = {-kDblFarHost, -kDblFarHost, -kDblFarHost}, mn[3], mx[3];
+        for (uint64_t i = 0; i < n; i++) {
+            box(i, mn, mx);
+            for (int a = 0; a < 3; a++) { lo[a] = std::min(lo[a], mn[a]); hi[a] = std::max(hi[a], mx[a]); }
+        }
+        double ctr[3];
+        for (int a = 0; a < 3; a++) ctr[a] = lo[a] * 0.5 + hi[a] * 0.5;
+        std::vector<float> boxes(n * 6);
+        for (uint64_t i = 0; i < n; i++) {
+            box(i, mn, mx);
+            for (int a = 0; a < 3; a++) { boxes[i * 6 + a] = (float)(mn[a] - ctr[a]); boxes[i * 6 + 3 + a] = (float)(mx[a] - ctr[a]); }
+        }
+        build_bvh2_boxes(boxes.data(), (uint32_t)n, bp, h->bvh2);
+        doubleFromTopology(h->bvh2, box, h->dnodes);
+        h->didx.assign(h->bvh2.primIdx.begin(), h->bvh2.primIdx.end());
+    } catch (const std::bad_alloc&) {
+        delete h;
+        return fail(TBVH_E_NOMEM, "out of host memory while building");
+    }
+    *out = h;
+    return 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -203,27 +287,7 @@ extern "C" {
 
 int tbvh_upload_bvh_double(tbvh_context* c, const void* nodes64, uint64_t nNodes, const uint64_t* primIdx, uint64_t nIdx, const void* vertsDbl3, uint64_t nTris,
                            tbvh_scene** out) {
-    if (!c || !nodes64 || !primIdx || !vertsDbl3 || !out || !nIdx || !nTris) return fail(TBVH_E_INVALID, "tbvh_upload_bvh_double: null/empty argument");
-    if (int r = validateDouble((const NodeDbl*)nodes64, nNodes, primIdx, nIdx, nTris, "tbvh_upload_bvh_double", "n_tris")) return r;
-    TBVH_ENTER(c);
-    tbvh_scene* s = newScene(c, TBVH_LAYOUT_BVH_DOUBLE);
-    if (!s) return fail(TBVH_E_NOMEM, "out of host memory");
-    DevBuf<uint64_t> dIdx;
-    DevBuf<double> dVerts;
-    auto bail = [&](int code, const char* what) { tbvh_free_scene(s); return fail(code, "tbvh_upload_bvh_double: %s", what); };
-    if (s->nodes.alloc(nNodes * (sizeof(NodeDbl) / 16)) != hipSuccess || s->tris.alloc(nIdx * (sizeof(TriDbl) / 16)) != hipSuccess ||
-        dIdx.alloc(nIdx) != hipSuccess || dVerts.alloc(nTris * 9) != hipSuccess)
-        return bail(TBVH_E_NOMEM, "out of device memory");
-    if (hipMemcpyAsync(s->nodes, nodes64, nNodes * sizeof(NodeDbl), hipMemcpyHostToDevice, c->stream) != hipSuccess ||
-        hipMemcpyAsync(dIdx, primIdx, nIdx * 8, hipMemcpyHostToDevice, c->stream) != hipSuccess ||
-        hipMemcpyAsync(dVerts, vertsDbl3, nTris * 72, hipMemcpyHostToDevice, c->stream) != hipSuccess)
-        return bail(TBVH_E_HIP, "copy to the device failed");
-    launch_gather_tris_dbl(dIdx, dVerts, (TriDbl*)s->tris.get(), nIdx, c->stream);
-    if (hipGetLastError() != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) return bail(TBVH_E_HIP, "triangle gather failed");
-    s->nNodes = (uint32_t)nNodes;
-    s->dblTris = nTris; s->dblRecs = nIdx;
-    *out = s;
-    return 0;
+    return uploadBlasDbl(c, "tbvh_upload_bvh_double", kTriBlasDbl, nodes64, nNodes, primIdx, nIdx, vertsDbl3, nTris, out);
 }
 
 int tbvh_upload_tlas_double(tbvh_context* c, const void* nodes64, uint64_t nNodes, const uint64_t* idx, uint64_t nIdx, const void* instances320, uint64_t nInst,
@@ -271,32 +335,26 @@ int tbvh_upload_tlas_double(tbvh_context* c, const void* nodes64, uint64_t nNode
 
 int tbvh_intersect_ex_device(tbvh_scene* s, void* dRays, uint64_t n) {
     if (!s || (!dRays && n)) return fail(TBVH_E_INVALID, "tbvh_intersect_ex_device: null argument");
-    TBVH_REFUSE_CUSTOM(s, "tbvh_intersect_ex_device");
-    if (!isDouble(s)) return fail(TBVH_E_INVALID, "tbvh_intersect_ex_device: scene layout %d is not BVH_DOUBLE (RayEx queries need a BVH_Double scene)", s->layout);
-    if (((uintptr_t)dRays) & 15) return fail(TBVH_E_INVALID, "tbvh_intersect_ex_device: ray array must be 16-byte aligned");
+    if (int r = checkExQuery(s, "tbvh_intersect_ex_device", dRays)) return r;
     return launchDouble(s, (RayExRec*)dRays, n, nullptr);
 }
 
 int tbvh_occluded_ex_device(tbvh_scene* s, const void* dRays, uint64_t n, uint8_t* dOcc) {
     if (!s || ((!dRays || !dOcc) && n)) return fail(TBVH_E_INVALID, "tbvh_occluded_ex_device: null argument");
-    TBVH_REFUSE_CUSTOM(s, "tbvh_occluded_ex_device");
-    if (!isDouble(s)) return fail(TBVH_E_INVALID, "tbvh_occluded_ex_device: scene layout %d is not BVH_DOUBLE (RayEx queries need a BVH_Double scene)", s->layout);
-    if (((uintptr_t)dRays) & 15) return fail(TBVH_E_INVALID, "tbvh_occluded_ex_device: ray array must be 16-byte aligned");
+    if (int r = checkExQuery(s, "tbvh_occluded_ex_device", dRays)) return r;
     return launchDouble(s, (RayExRec*)dRays, n, dOcc);
 }
 
 int tbvh_intersect_ex(tbvh_scene* s, void* rays, uint64_t n) {
     if (!s || (!rays && n)) return fail(TBVH_E_INVALID, "tbvh_intersect_ex: null argument");
-    TBVH_REFUSE_CUSTOM(s, "tbvh_intersect_ex");
-    if (!isDouble(s)) return fail(TBVH_E_INVALID, "tbvh_intersect_ex: scene layout %d is not BVH_DOUBLE (RayEx queries need a BVH_Double scene)", s->layout);
+    if (int r = checkExQuery(s, "tbvh_intersect_ex")) return r;
     if (n == 0) return 0;
     return hostQueryEx(s, rays, n, nullptr, "tbvh_intersect_ex");
 }
 
 int tbvh_occluded_ex(tbvh_scene* s, const void* rays, uint64_t n, uint8_t* occ) {
     if (!s || ((!rays || !occ) && n)) return fail(TBVH_E_INVALID, "tbvh_occluded_ex: null argument");
-    TBVH_REFUSE_CUSTOM(s, "tbvh_occluded_ex");
-    if (!isDouble(s)) return fail(TBVH_E_INVALID, "tbvh_occluded_ex: scene layout %d is not BVH_DOUBLE (RayEx queries need a BVH_Double scene)", s->layout);
+    if (int r = checkExQuery(s, "tbvh_occluded_ex")) return r;
     if (n == 0) return 0;
     return hostQueryEx(s, (void*)rays, n, occ, "tbvh_occluded_ex");
 }
@@ -344,30 +402,11 @@ int tbvh_host_build_tlas_double(void* instances320, uint64_t nInst, const double
         if (inst[i].blasIdx >= nBlas) return fail(TBVH_E_INVALID, "tbvh_host_build_tlas_double: instance %llu: blasIdx %llu out of range", (unsigned long long)i, (unsigned long long)inst[i].blasIdx);
     tbvh_hostbvh* h = new (std::nothrow) tbvh_hostbvh;
     if (!h) return fail(TBVH_E_NOMEM, "out of host memory");
-    h->layout = TBVH_LAYOUT_BVH_DOUBLE;
-    try {
-        double lo[3] = {kDblFarHost, kDblFarHost, kDblFarHost}, hi[3] = {-kDblFarHost, -kDblFarHost, -kDblFarHost};
-        for (uint64_t i = 0; i < nInst; i++) {
-            updateInstanceDbl(inst[i], blasBounds6 + 6 * inst[i].blasIdx);
-            for (int a = 0; a < 3; a++) { lo[a] = std::min(lo[a], inst[i].aabbMin[a]); hi[a] = std::max(hi[a], inst[i].aabbMax[a]); }
-        }
-        double ctr[3];
-        for (int a = 0; a < 3; a++) ctr[a] = lo[a] * 0.5 + hi[a] * 0.5;
-        std::vector<float> boxes(nInst * 6);
-        for (uint64_t i = 0; i < nInst; i++)
-            for (int a = 0; a < 3; a++) { boxes[i * 6 + a] = (float)(inst[i].aabbMin[a] - ctr[a]); boxes[i * 6 + 3 + a] = (float)(inst[i].aabbMax[a] - ctr[a]); }
-        BuildParams bp; bp.maxLeafTris = 1; bp.threads = 1;   // (as tbvh_host_build_tlas)
-        build_bvh2_boxes(boxes.data(), (uint32_t)nInst, bp, h->bvh2);
-        doubleFromTopology(h->bvh2, [&](uint64_t p, double* mn, double* mx) {
-            for (int a = 0; a < 3; a++) { mn[a] = inst[p].aabbMin[a]; mx[a] = inst[p].aabbMax[a]; }
-        }, h->dnodes);
-        h->didx.assign(h->bvh2.primIdx.begin(), h->bvh2.primIdx.end());
-    } catch (const std::bad_alloc&) {
-        delete h;
-        return fail(TBVH_E_NOMEM, "out of host memory while building");
-    }
-    *out = h;
-    return 0;
+    for (uint64_t i = 0; i < nInst; i++) updateInstanceDbl(inst[i], blasBounds6 + 6 * inst[i].blasIdx);
+    BuildParams bp; bp.maxLeafTris = 1; bp.threads = 1;   // (as tbvh_host_build_tlas)
+    return hostBuildOverBoxesDbl(h, nInst, [&](uint64_t p, double* mn, double* mx) {
+        for (int a = 0; a < 3; a++) { mn[a] = inst[p].aabbMin[a]; mx[a] = inst[p].aabbMax[a]; }
+    }, bp, out);
 }
 
 }  // extern "C"
@@ -539,17 +578,9 @@ int tbvh_refit_double(tbvh_scene* s, const void* vertsDbl3, uint64_t nTris, int 
 
 }  // extern "C"
 
-// ---- custom geometry: sphere BLASes (custom_sphere_dbl.h, kernels_double_custom.hip) --------------------------------------------------------
+// ---- custom geometry: sphere BLASes (custom_sphere_dbl.h) ------------------------------------------------------------------------------------
 
 namespace {
-
-// every r finite and >= 0 (a NaN r would make a NaN box; a negative one an inverted box around a sphere the test still hits)
-int validateSpheresDbl(const SphereDbl* sph, uint64_t n, const char* who) {
-    for (uint64_t i = 0; i < n; i++)
-        if (!(sph[i].r >= 0) || !(sph[i].r <= 1.79769313486231570815e+308))
-            return fail(TBVH_E_FORMAT, "%s: sphere %llu: r = %g is not a finite number >= 0", who, (unsigned long long)i, sph[i].r);
-    return 0;
-}
 
 int checkSphereSceneDbl(const tbvh_scene* s, const char* who) {
     if (int r = checkDoubleScene(s, false, who)) return r;
@@ -607,30 +638,7 @@ extern "C" {
 
 int tbvh_upload_custom_spheres_double(tbvh_context* c, const void* nodes64, uint64_t nNodes, const uint64_t* primIdx, uint64_t nIdx, const void* spheres32,
                                       uint64_t nSpheres, tbvh_scene** out) {
-    const char* who = "tbvh_upload_custom_spheres_double";
-    if (!c || !nodes64 || !primIdx || !spheres32 || !out || !nIdx || !nSpheres) return fail(TBVH_E_INVALID, "%s: null/empty argument", who);
-    if (int r = validateDouble((const NodeDbl*)nodes64, nNodes, primIdx, nIdx, nSpheres, who, "n_spheres")) return r;
-    if (int r = validateSpheresDbl((const SphereDbl*)spheres32, nSpheres, who)) return r;
-    TBVH_ENTER(c);
-    tbvh_scene* s = newScene(c, TBVH_LAYOUT_BVH_DOUBLE);
-    if (!s) return fail(TBVH_E_NOMEM, "out of host memory");
-    s->dblSpheres = true;
-    DevBuf<uint64_t> dIdx;
-    DevBuf<double> dSph;
-    auto bail = [&](int code, const char* what) { tbvh_free_scene(s); return fail(code, "%s: %s", who, what); };
-    if (s->nodes.alloc(nNodes * (sizeof(NodeDbl) / 16)) != hipSuccess || s->tris.alloc(nIdx * (sizeof(SphereRecDbl) / 16)) != hipSuccess ||
-        dIdx.alloc(nIdx) != hipSuccess || dSph.alloc(nSpheres * 4) != hipSuccess)
-        return bail(TBVH_E_NOMEM, "out of device memory");
-    if (hipMemcpyAsync(s->nodes, nodes64, nNodes * sizeof(NodeDbl), hipMemcpyHostToDevice, c->stream) != hipSuccess ||
-        hipMemcpyAsync(dIdx, primIdx, nIdx * 8, hipMemcpyHostToDevice, c->stream) != hipSuccess ||
-        hipMemcpyAsync(dSph, spheres32, nSpheres * sizeof(SphereDbl), hipMemcpyHostToDevice, c->stream) != hipSuccess)
-        return bail(TBVH_E_HIP, "copy to the device failed");
-    launch_gather_spheres_dbl(dIdx, dSph.get(), s->tris.get(), nIdx, c->stream);
-    if (hipGetLastError() != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) return bail(TBVH_E_HIP, "sphere gather failed");
-    s->nNodes = (uint32_t)nNodes;
-    s->dblTris = nSpheres; s->dblRecs = nIdx;
-    *out = s;
-    return 0;
+    return uploadBlasDbl(c, "tbvh_upload_custom_spheres_double", kSphereBlasDbl, nodes64, nNodes, primIdx, nIdx, spheres32, nSpheres, out);
 }
 
 int tbvh_host_build_custom_spheres_double(const void* spheres32, uint64_t n, tbvh_hostbvh** out) {
@@ -641,33 +649,8 @@ int tbvh_host_build_custom_spheres_double(const void* spheres32, uint64_t n, tbv
     if (int r = validateSpheresDbl(sph, n, who)) return r;
     tbvh_hostbvh* h = new (std::nothrow) tbvh_hostbvh;
     if (!h) return fail(TBVH_E_NOMEM, "out of host memory");
-    h->layout = TBVH_LAYOUT_BVH_DOUBLE;
-    try {
-        // as tbvh_host_build_double: the topology of the fp32 builder on the boxes translated by their centre, every node box then recomputed in double
-        double lo[3] = {kDblFarHost, kDblFarHost, kDblFarHost}, hi[3] = {-kDblFarHost, -kDblFarHost, -kDblFarHost};
-        for (uint64_t i = 0; i < n; i++) {
-            double mn[3], mx[3];
-            sphere_box_dbl(sph[i], mn, mx);
-            for (int a = 0; a < 3; a++) { lo[a] = std::min(lo[a], mn[a]); hi[a] = std::max(hi[a], mx[a]); }
-        }
-        double ctr[3];
-        for (int a = 0; a < 3; a++) ctr[a] = lo[a] * 0.5 + hi[a] * 0.5;
-        std::vector<float> boxes(n * 6);
-        for (uint64_t i = 0; i < n; i++) {
-            double mn[3], mx[3];
-            sphere_box_dbl(sph[i], mn, mx);
-            for (int a = 0; a < 3; a++) { boxes[i * 6 + a] = (float)(mn[a] - ctr[a]); boxes[i * 6 + 3 + a] = (float)(mx[a] - ctr[a]); }
-        }
-        BuildParams bp;   // (as tbvh_host_build_custom_spheres)
-        build_bvh2_boxes(boxes.data(), (uint32_t)n, bp, h->bvh2);
-        doubleFromTopology(h->bvh2, [&](uint64_t p, double* mn, double* mx) { sphere_box_dbl(sph[p], mn, mx); }, h->dnodes);
-        h->didx.assign(h->bvh2.primIdx.begin(), h->bvh2.primIdx.end());
-    } catch (const std::bad_alloc&) {
-        delete h;
-        return fail(TBVH_E_NOMEM, "out of host memory while building");
-    }
-    *out = h;
-    return 0;
+    const BuildParams bp;   // (as tbvh_host_build_custom_spheres)
+    return hostBuildOverBoxesDbl(h, n, [&](uint64_t p, double* mn, double* mx) { sphere_box_dbl(sph[p], mn, mx); }, bp, out);
 }
 
 int tbvh_build_device_custom_spheres_double(tbvh_context* c, const void* spheres32, uint64_t n, int onDevice, tbvh_scene** out) {

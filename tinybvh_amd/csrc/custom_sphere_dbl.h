@@ -1,6 +1,6 @@
 // custom_sphere_dbl.h — custom-geometry sphere BLASes in double precision (BVH_Double::Build( customGetAABB, n ) traced through customIntersect /
 // customIsOccluded, as tiny_bvh_custom_double.cpp and tiny_bvh_anim_double.cpp do): the record, the box and the primitive test, for the device
-// (kernels_double_custom.hip) and for the host code of capi_double.hip.
+// (the sphere forms of kernels_double.hip, the box source of kernels_double_anim.hip) and for the host code of capi_double.hip.
 //
 // A sphere is the demos' struct Sphere { bvhdbl3 pos; double r; }, 32 bytes.  Gathered at upload (and by a device build) in primIdx order, one
 // 48-byte record per index entry: {pos, r, prim, 0}, three aligned 16-byte reads.

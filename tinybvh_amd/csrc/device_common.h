@@ -195,7 +195,7 @@ __device__ __forceinline__ bool hit_wins(float t, uint32_t prim, uint32_t inst, 
 }
 
 // The same rule for BVH_Double scenes (kernels_double.hip): the slack of the box culls is again eight ulps, 2^-49 in double, and a
-// candidate that tri_test_dbl has accepted against the closest hit so far replaces it iff it is strictly closer or, at EQUAL distance, a hit
+// candidate that the triangle step has accepted against the closest hit so far replaces it iff it is strictly closer or, at EQUAL distance, a hit
 // has been found already and the candidate has the smaller primitive index, then the smaller instance.  The reference's own test is strict
 // (t < ray.hit.t, tiny_bvh.h:8194): the ray's tmax itself is never a hit, and among equal distances the FIRST found stays.
 __device__ __host__ __forceinline__ double cull_bound_dbl(double t) { return t * 1.0000000000000017763568394002504646778106689453125; }

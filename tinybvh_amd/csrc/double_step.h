@@ -1,6 +1,6 @@
-// double_step.h — the fp64 pieces the BVH_Double traversals share (kernels_double.hip: triangles; kernels_double_custom.hip: spheres, and triangles next
-// to them under a TLAS): the reference's min / max, its vector helpers and transforms, and BVH_Double::BVHNode::Intersect.  Everything is an
-// expression of tiny_bvh.h restated operation for operation; the Makefile's -ffp-contract=off keeps each a separate IEEE operation.
+// double_step.h — the fp64 pieces of the BVH_Double traversal (kernels_double.hip): the reference's min / max, its vector helpers and transforms,
+// BVH_Double::BVHNode::Intersect, and the triangle test in the spelling the sphere TLAS forms use.  Everything is an expression of tiny_bvh.h
+// restated operation for operation; the Makefile's -ffp-contract=off keeps each a separate IEEE operation.
 #pragma once
 #include "device_common.h"
 

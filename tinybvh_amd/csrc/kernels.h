@@ -82,8 +82,9 @@ struct DoubleArgs {
     const InstanceDbl* inst;
     const BlasDbl* blas;
 };
-void launch_double(bool anyhit, bool tlas, const DoubleArgs& q, uint32_t* status, uint32_t blocks, hipStream_t s);
-void launch_gather_tris_dbl(const uint64_t* primIdx, const double* verts, TriDbl* out, uint64_t nIdx, hipStream_t s);
+// spheres: q.tris holds a sphere BLAS's records (custom_sphere_dbl.h); under a TLAS, the TLAS lists a sphere BLAS and the low bit of a BlasDbl's `tris` marks one
+void launch_double(bool spheres, bool anyhit, bool tlas, const DoubleArgs& q, uint32_t* status, uint32_t blocks, hipStream_t s);
+void launch_gather_tris_dbl(const uint64_t* primIdx, const void* verts72, void* recs80, uint64_t nIdx, hipStream_t s);   // (the signature of the spheres' gather)
 // BVH_Double scenes that move (kernels_double_anim.hip).  TLAS rebuild: BLASInstanceEx::Update of every instance (transformsDev: 16 doubles per instance, or
 // nullptr: the transforms in the records; the BLAS boxes are node 0 of each BLAS), then an LBVH of 2 n - 1 nodes over the instance boxes into tlasNodes /
 // tlasIdx.  The scratch is one allocation of tlas_dbl_build_scratch_bytes(n); host transforms are staged in its part tlas_dbl_xform_stage names.
@@ -96,11 +97,10 @@ hipError_t launch_tlas_dbl_rebuild(NodeDbl* tlasNodes, uint64_t* tlasIdx, Instan
 void launch_parents_dbl(const NodeDbl* nodes, uint32_t nNodes, uint32_t* parent, uint32_t* leaves, uint32_t* frontA, uint32_t* frontB, uint32_t* nLeavesOut, hipStream_t s);
 hipError_t launch_refit_dbl(NodeDbl* nodes, uint32_t nNodes, TriDbl* tris, uint64_t nRecs, const double* verts, uint64_t nTris, const uint32_t* leaves,
                             uint32_t nLeaves, const uint32_t* parent, uint32_t* flags, hipStream_t s);
-// BVH_Double over custom geometry: spheres {pos, r} of 32 bytes, gathered into 48-byte records {pos, r, prim, 0} (custom_sphere_dbl.h).  Queries and the
-// upload's gather are kernels_double_custom.hip: q.tris holds a sphere BLAS's records; under a TLAS the low bit of a BlasDbl's `tris` marks a sphere BLAS.
+// BVH_Double over custom geometry: spheres {pos, r} of 32 bytes, gathered into 48-byte records {pos, r, prim, 0} (custom_sphere_dbl.h).  Queries are
+// launch_double's sphere forms; the upload's gather stands beside the triangles' in kernels_double.hip.
 // The build is kernels_double_anim.hip's LBVH with the spheres as its box source: 2 n - 1 nodes over the boxes pos -/+ r into nodes / recs48 (a record
 // carries its primIdx entry); the scratch is one allocation of spheres_dbl_build_scratch_bytes(n).
-void launch_double_custom(bool anyhit, bool tlas, const DoubleArgs& q, uint32_t* status, uint32_t blocks, hipStream_t s);
 void launch_gather_spheres_dbl(const uint64_t* primIdx, const void* spheres32, void* recs48, uint64_t nIdx, hipStream_t s);
 size_t spheres_dbl_build_scratch_bytes(uint32_t n, size_t* sortTempBytes);
 hipError_t launch_spheres_dbl_build(NodeDbl* nodes, void* recs48, const void* spheres32, uint32_t n, void* scratch, size_t sortTempBytes,

@@ -123,15 +123,46 @@ __global__ void k_instance_update_dbl(InstanceDbl* __restrict__ instances, const
     lbvh::wave_centre_bounds(cLo, cHi, centreBounds);   // one set of six atomics per wave, an axis without a finite centre left out
 }
 
+// ---- the box sources of steps 2-5 -----------------------------------------------------------------------------------------------------------
+// A box source supplies the box of primitive i and says what the leaf thread writes beside the leaf node (`side`, indexed by sorted position).
+// Instances: the world box step 1 wrote into the record; beside the leaf goes the instance's index, tlasIdx[k].
+struct InstanceBoxes {
+    using Prim = InstanceDbl;
+    using Side = uint64_t;
+    struct Box {
+        const Prim& in;
+        __device__ __forceinline__ double lo(int a) const { return in.aabbMin[a]; }
+        __device__ __forceinline__ double hi(int a) const { return in.aabbMax[a]; }
+    };
+    static __device__ __forceinline__ Box box(const Prim& in) { return Box{in}; }
+    static __device__ __forceinline__ void leaf(Side* __restrict__ tlasIdx, uint32_t k, uint32_t i, const Prim&) { tlasIdx[k] = i; }
+};
+// Spheres {pos, r} (a BVH_Double over custom geometry, custom_sphere_dbl.h; the demos' obj.Build( &sphereAABB, n ) per frame): the boxes pos -/+ r;
+// beside the leaf goes the gathered record {pos, r, prim, 0} the traversal reads (the record carries its primIdx entry).
+struct SphereBoxes {
+    using Prim = SphereDbl;
+    using Side = SphereRecDbl;
+    struct Box {
+        double mn[3], mx[3];
+        __device__ __forceinline__ double lo(int a) const { return mn[a]; }
+        __device__ __forceinline__ double hi(int a) const { return mx[a]; }
+    };
+    static __device__ __forceinline__ Box box(const Prim& s) { Box b; sphere_box_dbl(s, b.mn, b.mx); return b; }
+    static __device__ __forceinline__ void leaf(Side* __restrict__ recs, uint32_t k, uint32_t i, const Prim& s) {
+        recs[k] = SphereRecDbl{{s.pos[0], s.pos[1], s.pos[2]}, s.r, i, 0};
+    }
+};
+
 // ---- 2. Morton keys ---------------------------------------------------------------------------------------------------------------------
-__global__ void k_morton_dbl(const InstanceDbl* __restrict__ instances, const uint64_t* __restrict__ centreBounds, uint32_t n,
+template <class Src>
+__global__ void k_morton_dbl(const typename Src::Prim* __restrict__ prims, const uint64_t* __restrict__ centreBounds, uint32_t n,
                              uint64_t* __restrict__ keys, uint32_t* __restrict__ vals) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    const InstanceDbl& in = instances[i];
+    const typename Src::Box b = Src::box(prims[i]);
     uint32_t q[3];
     for (int a = 0; a < 3; a++) {
-        const double c = 0.5 * in.aabbMin[a] + 0.5 * in.aabbMax[a];
+        const double c = 0.5 * b.lo(a) + 0.5 * b.hi(a);
         q[a] = lbvh::morton_axis(c, lbvh::ordered_decode(centreBounds[a]), lbvh::ordered_decode(centreBounds[3 + a]), 2097151u);   // (a NaN centre: cell 0)
     }
     keys[i] = lbvh::morton63(q);
@@ -150,18 +181,20 @@ __global__ void k_lbvh_topology_dbl(const uint64_t* __restrict__ keys, uint32_t 
     if (i == 0) slot[0] = 0u;
 }
 
-// ---- 5. nodes: one thread per leaf writes the leaf node, then climbs ---------------------------------------------------------------------
-__global__ void k_lbvh_nodes_dbl(const uint32_t* __restrict__ sortedIdx, const InstanceDbl* __restrict__ instances, const uint32_t* __restrict__ parent,
+// ---- 5. nodes: one thread per leaf writes what stands beside the leaf and the leaf node, then climbs ------------------------------------------
+template <class Src>
+__global__ void k_lbvh_nodes_dbl(const uint32_t* __restrict__ sortedIdx, const typename Src::Prim* __restrict__ prims, const uint32_t* __restrict__ parent,
                                  const uint32_t* __restrict__ slot, uint32_t* __restrict__ flags, uint32_t n, NodeDbl* __restrict__ nodes,
-                                 uint64_t* __restrict__ tlasIdx) {
+                                 typename Src::Side* __restrict__ side) {
     const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
     if (k >= n) return;
-    const uint32_t inst = sortedIdx[k];   // (< n: a permutation of the values k_morton_dbl wrote)
-    tlasIdx[k] = inst;
+    const uint32_t p = sortedIdx[k];   // (< n: a permutation of the values k_morton_dbl wrote)
+    const typename Src::Prim& prim = prims[p];
+    Src::leaf(side, k, p, prim);
     const uint32_t id = n - 1 + k;
-    const InstanceDbl& in = instances[inst];
-    NodeDbl* ln = nodes + (n == 1 ? 0u : slot[id]);   // with a single instance the leaf IS the root
-    for (int a = 0; a < 3; a++) { ln->mn[a] = in.aabbMin[a]; ln->mx[a] = in.aabbMax[a]; }
+    NodeDbl* ln = nodes + (n == 1 ? 0u : slot[id]);   // with a single primitive the leaf IS the root
+    const typename Src::Box b = Src::box(prim);
+    for (int a = 0; a < 3; a++) { ln->mn[a] = b.lo(a); ln->mx[a] = b.hi(a); }
     ln->leftFirst = k; ln->triCount = 1;
     if (n == 1) return;
     __threadfence();
@@ -178,10 +211,7 @@ __global__ void k_lbvh_nodes_dbl(const uint32_t* __restrict__ sortedIdx, const I
     }
 }
 
-
-// ---- the second box source: spheres {pos, r} (a BVH_Double over custom geometry: custom_sphere_dbl.h, kernels_double_custom.hip) -----------------
-// The demos' obj.Build( &sphereAABB, n ) per frame: steps 2-5 above over the boxes pos -/+ r.  Step 1 has no records to update: it only reduces the
-// centre bounds.  Step 5's leaf thread also writes the gathered record {pos, r, prim, 0} the traversal reads (the record carries its primIdx entry).
+// Step 1 of a sphere build: there are no records to update, it only reduces the centre bounds.
 __global__ void k_sphere_centres_dbl(const SphereDbl* __restrict__ sph, uint32_t n, uint64_t* __restrict__ centreBounds) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     double cLo[3] = {kDblFar, kDblFar, kDblFar}, cHi[3] = {-kDblFar, -kDblFar, -kDblFar};
@@ -194,48 +224,6 @@ __global__ void k_sphere_centres_dbl(const SphereDbl* __restrict__ sph, uint32_t
         }
     }
     lbvh::wave_centre_bounds(cLo, cHi, centreBounds);
-}
-
-__global__ void k_morton_spheres_dbl(const SphereDbl* __restrict__ sph, const uint64_t* __restrict__ centreBounds, uint32_t n, uint64_t* __restrict__ keys,
-                                     uint32_t* __restrict__ vals) {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    double mn[3], mx[3];
-    sphere_box_dbl(sph[i], mn, mx);
-    uint32_t q[3];
-    for (int a = 0; a < 3; a++) {
-        const double c = 0.5 * mn[a] + 0.5 * mx[a];
-        q[a] = lbvh::morton_axis(c, lbvh::ordered_decode(centreBounds[a]), lbvh::ordered_decode(centreBounds[3 + a]), 2097151u);
-    }
-    keys[i] = lbvh::morton63(q);
-    vals[i] = i;
-}
-
-__global__ void k_lbvh_nodes_spheres_dbl(const uint32_t* __restrict__ sortedIdx, const SphereDbl* __restrict__ sph, const uint32_t* __restrict__ parent,
-                                         const uint32_t* __restrict__ slot, uint32_t* __restrict__ flags, uint32_t n, NodeDbl* __restrict__ nodes,
-                                         SphereRecDbl* __restrict__ recs) {
-    const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
-    if (k >= n) return;
-    const uint32_t p = sortedIdx[k];   // (< n: a permutation of the values k_morton_spheres_dbl wrote)
-    const SphereDbl s = sph[p];
-    recs[k] = SphereRecDbl{{s.pos[0], s.pos[1], s.pos[2]}, s.r, p, 0};
-    const uint32_t id = n - 1 + k;
-    NodeDbl* ln = nodes + (n == 1 ? 0u : slot[id]);   // with a single sphere the leaf IS the root
-    sphere_box_dbl(s, ln->mn, ln->mx);
-    ln->leftFirst = k; ln->triCount = 1;
-    if (n == 1) return;
-    __threadfence();
-    uint32_t node = parent[id];
-    for (;;) {
-        if (atomicAdd(flags + node, 1u) == 0u) return;   // first to arrive: the sibling subtree is not finished yet
-        __threadfence();
-        const uint32_t at = slot[node], c = 1u + 2u * node;
-        write_union(nodes, at, c);
-        nodes[at].leftFirst = c; nodes[at].triCount = 0;
-        if (node == 0) return;
-        __threadfence();
-        node = parent[node];
-    }
 }
 
 // ---- refit ----------------------------------------------------------------------------------------------------------------------------
@@ -331,15 +319,40 @@ Scratch carve(void* base, uint32_t n, size_t sortTempBytes, bool xforms = true) 
     return s;
 }
 
-}  // namespace
+constexpr uint32_t kBuildBlock = 128;   // every build step is one thread per primitive in blocks of this size
 
-size_t tlas_dbl_build_scratch_bytes(uint32_t n, size_t* sortTempBytes) {
+// steps 2-5 over a box source: keys, the radix sort, the topology, then the nodes (flags: one word per Karras interior node, zeroed here)
+template <class Src>
+hipError_t lbvh_over(const char* who, const typename Src::Prim* prims, typename Src::Side* side, NodeDbl* nodes, uint32_t n, const Scratch& sc, size_t sortTempBytes,
+                     hipStream_t s) {
+    hipError_t e;
+    const uint32_t bs = kBuildBlock, nb = (n + bs - 1) / bs;
+    hipLaunchKernelGGL(k_morton_dbl<Src>, dim3(nb), dim3(bs), 0, s, prims, sc.bounds, n, sc.keysA, sc.valsA);
+    TBVH_STEP(who, "morton keys");
+    size_t tmp = sortTempBytes;
+    if ((e = hipcub::DeviceRadixSort::SortPairs(sc.sortTemp, tmp, sc.keysA, sc.keysB, sc.valsA, sc.valsB, (int)n, 0, 64, s)) != hipSuccess) {
+        fprintf(stderr, "[tinybvh_amd] %s: radix sort (%zu temp bytes): %s\n", who, sortTempBytes, hipGetErrorString(e));
+        return e;
+    }
+    if (n > 1) hipLaunchKernelGGL(k_lbvh_topology_dbl, dim3(nb), dim3(bs), 0, s, sc.keysB, n, sc.parent, sc.slot);
+    TBVH_STEP(who, "topology");
+    if ((e = hipMemsetAsync(sc.flags, 0, (size_t)n * 4, s)) != hipSuccess) return e;
+    hipLaunchKernelGGL(k_lbvh_nodes_dbl<Src>, dim3(nb), dim3(bs), 0, s, sc.valsB, prims, sc.parent, sc.slot, sc.flags, n, nodes, side);
+    TBVH_STEP(who, "nodes");
+    return hipGetLastError();
+}
+
+size_t sort_temp_bytes(uint32_t n) {
     size_t tmp = 0;
     hipcub::DeviceRadixSort::SortPairs(nullptr, tmp, (const uint64_t*)nullptr, (uint64_t*)nullptr, (const uint32_t*)nullptr, (uint32_t*)nullptr, (int)n, 0, 64);
-    *sortTempBytes = tmp;
-    return tlas_dbl_build_scratch_total(n, tmp);
+    return tmp;
 }
+
+}  // namespace
+
+size_t tlas_dbl_build_scratch_bytes(uint32_t n, size_t* sortTempBytes) { return tlas_dbl_build_scratch_total(n, *sortTempBytes = sort_temp_bytes(n)); }
 size_t tlas_dbl_build_scratch_total(uint32_t n, size_t sortTempBytes) { return carve(nullptr, n, sortTempBytes).total; }
+size_t spheres_dbl_build_scratch_bytes(uint32_t n, size_t* sortTempBytes) { return carve(nullptr, n, *sortTempBytes = sort_temp_bytes(n), false).total; }
 
 double* tlas_dbl_xform_stage(void* scratch, uint32_t n, size_t sortTempBytes) { return carve(scratch, n, sortTempBytes).xforms; }
 
@@ -348,29 +361,9 @@ hipError_t launch_tlas_dbl_rebuild(NodeDbl* tlasNodes, uint64_t* tlasIdx, Instan
     const Scratch sc = carve(scratch, n, sortTempBytes);
     hipError_t e;
     if ((e = reset_centre_bounds(sc.bounds, 8, s)) != hipSuccess) return e;
-    if ((e = hipMemsetAsync(sc.flags, 0, (size_t)n * 4, s)) != hipSuccess) return e;
-    const uint32_t bs = 128, nb = (n + bs - 1) / bs;
-    hipLaunchKernelGGL(k_instance_update_dbl, dim3(nb), dim3(bs), 0, s, instances, transformsDev, blas, n, nBlas, sc.bounds);
+    hipLaunchKernelGGL(k_instance_update_dbl, dim3((n + kBuildBlock - 1) / kBuildBlock), dim3(kBuildBlock), 0, s, instances, transformsDev, blas, n, nBlas, sc.bounds);
     TBVH_STEP("TLAS_Double rebuild", "instance update");
-    hipLaunchKernelGGL(k_morton_dbl, dim3(nb), dim3(bs), 0, s, instances, sc.bounds, n, sc.keysA, sc.valsA);
-    TBVH_STEP("TLAS_Double rebuild", "morton keys");
-    size_t tmp = sortTempBytes;
-    if ((e = hipcub::DeviceRadixSort::SortPairs(sc.sortTemp, tmp, sc.keysA, sc.keysB, sc.valsA, sc.valsB, (int)n, 0, 64, s)) != hipSuccess) {
-        fprintf(stderr, "[tinybvh_amd] TLAS_Double rebuild: radix sort (%zu temp bytes): %s\n", sortTempBytes, hipGetErrorString(e));
-        return e;
-    }
-    if (n > 1) hipLaunchKernelGGL(k_lbvh_topology_dbl, dim3(nb), dim3(bs), 0, s, sc.keysB, n, sc.parent, sc.slot);
-    TBVH_STEP("TLAS_Double rebuild", "topology");
-    hipLaunchKernelGGL(k_lbvh_nodes_dbl, dim3(nb), dim3(bs), 0, s, sc.valsB, instances, sc.parent, sc.slot, sc.flags, n, tlasNodes, tlasIdx);
-    TBVH_STEP("TLAS_Double rebuild", "nodes");
-    return hipGetLastError();
-}
-
-size_t spheres_dbl_build_scratch_bytes(uint32_t n, size_t* sortTempBytes) {
-    size_t tmp = 0;
-    hipcub::DeviceRadixSort::SortPairs(nullptr, tmp, (const uint64_t*)nullptr, (uint64_t*)nullptr, (const uint32_t*)nullptr, (uint32_t*)nullptr, (int)n, 0, 64);
-    *sortTempBytes = tmp;
-    return carve(nullptr, n, tmp, false).total;
+    return lbvh_over<InstanceBoxes>("TLAS_Double rebuild", instances, tlasIdx, tlasNodes, n, sc, sortTempBytes, s);
 }
 
 hipError_t launch_spheres_dbl_build(NodeDbl* nodes, void* recs48, const void* spheres32, uint32_t n, void* scratch, size_t sortTempBytes, hipStream_t s) {
@@ -378,22 +371,9 @@ hipError_t launch_spheres_dbl_build(NodeDbl* nodes, void* recs48, const void* sp
     const SphereDbl* sph = (const SphereDbl*)spheres32;
     hipError_t e;
     if ((e = reset_centre_bounds(sc.bounds, 8, s)) != hipSuccess) return e;
-    if ((e = hipMemsetAsync(sc.flags, 0, (size_t)n * 4, s)) != hipSuccess) return e;
-    const uint32_t bs = 128, nb = (n + bs - 1) / bs;
-    hipLaunchKernelGGL(k_sphere_centres_dbl, dim3(nb), dim3(bs), 0, s, sph, n, sc.bounds);
+    hipLaunchKernelGGL(k_sphere_centres_dbl, dim3((n + kBuildBlock - 1) / kBuildBlock), dim3(kBuildBlock), 0, s, sph, n, sc.bounds);
     TBVH_STEP("SphereBVH_Double build", "centre bounds");
-    hipLaunchKernelGGL(k_morton_spheres_dbl, dim3(nb), dim3(bs), 0, s, sph, sc.bounds, n, sc.keysA, sc.valsA);
-    TBVH_STEP("SphereBVH_Double build", "morton keys");
-    size_t tmp = sortTempBytes;
-    if ((e = hipcub::DeviceRadixSort::SortPairs(sc.sortTemp, tmp, sc.keysA, sc.keysB, sc.valsA, sc.valsB, (int)n, 0, 64, s)) != hipSuccess) {
-        fprintf(stderr, "[tinybvh_amd] SphereBVH_Double build: radix sort (%zu temp bytes): %s\n", sortTempBytes, hipGetErrorString(e));
-        return e;
-    }
-    if (n > 1) hipLaunchKernelGGL(k_lbvh_topology_dbl, dim3(nb), dim3(bs), 0, s, sc.keysB, n, sc.parent, sc.slot);
-    TBVH_STEP("SphereBVH_Double build", "topology");
-    hipLaunchKernelGGL(k_lbvh_nodes_spheres_dbl, dim3(nb), dim3(bs), 0, s, sc.valsB, sph, sc.parent, sc.slot, sc.flags, n, nodes, (SphereRecDbl*)recs48);
-    TBVH_STEP("SphereBVH_Double build", "nodes");
-    return hipGetLastError();
+    return lbvh_over<SphereBoxes>("SphereBVH_Double build", sph, (SphereRecDbl*)recs48, nodes, n, sc, sortTempBytes, s);
 }
 
 void launch_parents_dbl(const NodeDbl* nodes, uint32_t nNodes, uint32_t* parent, uint32_t* leaves, uint32_t* frontA, uint32_t* frontB, uint32_t* nLeavesOut, hipStream_t s) {

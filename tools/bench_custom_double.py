@@ -1,4 +1,4 @@
-"""fp64 custom-geometry (sphere BLAS) rates for DESIGN.md par. 9 / profiles/custom_double.txt (kernels_double_custom.hip).
+"""fp64 custom-geometry (sphere BLAS) rates for DESIGN.md par. 9 / profiles/custom_double.txt (the sphere forms of kernels_double.hip).
 Two sphere sets: the bunny as spheres (69 630, tests/golden/meshes/bunny.npz, the demos' recipe) and a soup of 1 M spheres; camera, shadow and diffuse
 batches; a single BLAS, and 1000 instances under a TLAS_Double.  Each next to the fp64 triangle BVH_Double of the same primitive count and to the
 fp32 SphereBVH of the same set (context: other arithmetic, the same geometry).  M rays/s from Context.time_last_ms: one warm-up, then the median
